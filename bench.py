@@ -20,11 +20,17 @@ Numerics: the headline mode is the FASTEST PARITY-GATED mode -- the first of bf1
 exact-f32 mode's on every stream of the batch (checked live, before the timed region; the f32 tokens are themselves checked
 against the CPU oracle on a sample).  Every mode's time, token match and encoder error are in `modes`.  `--numerics X` forces one.
 
-The single JSON line also carries (N = 1): `roofline` of the kernel site with the largest summed launch time in the timed
-region (HIP events on the launch stream), the other sites, the decode chain, short legs for BASELINE configs[2] (beam 4),
-configs[4] (full-context encoder 32 x 30 s), the joint lattice and the C64 chunking, per-chunk RTF percentiles
-(online_rnnt_delay.py:99-131), the first-call time and the CPU baseline.  Streams shard across ranks with no data-path
-collective (weak scaling); weights are broadcast once over RCCL.
+A plain run does only what the headline needs: set-up, the parity gate (stopping at the first mode that passes), `--warmup`
+steps, exactly `--steps` timed steps, and one JSON line with the headline (`value`, `ms_per_step`, `dtype`, ...).
+
+With `--full` the line also carries (N = 1): `roofline` of the kernel site with the largest summed launch time in the timed
+region (HIP events on the launch stream), the other sites, every numerics mode, the decode chain, short legs for BASELINE
+configs[2] (beam 4), configs[4] (full-context encoder 32 x 30 s), the joint lattice and the C64 chunking, per-chunk RTF
+percentiles (online_rnnt_delay.py:99-131), the first-call time and the CPU baseline.  Streams shard across ranks with no
+data-path collective (weak scaling); weights are broadcast once over RCCL.
+
+`--dump-outputs DIR` writes the tokens of the last timed step (rank 0's streams) as DIR/tokens.npy (float64 [streams, longest],
+-1 after a stream's last token) and DIR/token_counts.npy; the inputs and weights are seeded, so two builds can be compared.
 """
 import argparse
 import json
@@ -194,6 +200,18 @@ PMC_PREFIX = {"block_front": ["void block_front"], "block_back": ["void block_ba
               "ffn": ["void ffn_as"], "ffn_qkv": ["void ffn_as"], "ffn_merged": ["void ffn_as"], "out_pw1": ["void ffn_as"], "conv1": ["conv1_relu_rows"]}
 
 
+def dump_outputs(d, toks):
+    """tokens of the last timed step: DIR/tokens.npy float64 [streams, longest] (-1 after a stream's last token), DIR/token_counts.npy"""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    counts = np.array([len(t) for t in toks], dtype=np.float64)
+    arr = np.full((len(toks), max(int(counts.max(initial=0)), 1)), -1.0)
+    for b, t in enumerate(toks):
+        arr[b, :len(t)] = t
+    np.save(os.path.join(d, "tokens.npy"), arr)
+    np.save(os.path.join(d, "token_counts.npy"), counts)
+
+
 def spawn_ranks(args):
     """--gpus N without a launcher: start N rank processes (before anything here touches the GPU) and relay rank 0's line."""
     port = 29500 + os.getpid() % 2000
@@ -221,7 +239,10 @@ def main():
     ap.add_argument("--chunk", type=int, default=16, help="fbank frames per chunk (online_rnnt_decode.py semantics)")
     ap.add_argument("--numerics", default="auto", choices=["auto", "fp32", "bf16x3", "f16x3", "bf16"],
                     help="auto = fastest parity-gated mode (tokens equal to the exact-f32 mode's on every stream)")
-    ap.add_argument("--site", default="auto", help="launch site timed in the timed region (auto = the one with the largest summed launch time)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: every numerics mode, site survey and roofline, decode chain, margins, legs, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the tokens of the last timed step as DIR/*.npy")
+    ap.add_argument("--site", default="auto", help="(--full) launch site timed in the timed region (auto = the one with the largest summed launch time)")
     ap.add_argument("--cpu-streams", type=int, default=8, help="streams of the same workload timed on the CPU oracle (rank 0, N=1)")
     ap.add_argument("--cpu-threads", type=int, default=8)
     ap.add_argument("--in-flight", type=int, default=2, choices=[1, 2, 3, 4],
@@ -234,6 +255,8 @@ def main():
                     help="bias on the blank logit of the seeded weights: sets the greedy symbol rate (SURVEY.md §8d asks for 0.3-1 symbols per "
                          "encoder frame; 12.0 gives 0.75, the fixtures' 11.0 gives 1.40, 14.0 gives 0.17)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args)
 
@@ -285,33 +308,48 @@ def main():
                               max_tokens=max_tokens or ef * 10 + 16, device=local_rank, max_beam=max_beam, numerics=mode, packed=(wblob, wvocab))
 
     # ---- parity gate: one untimed pass per mode -> tokens, first-call time; encoder error vs fp32 ----------------------------
-    modes = ["fp32", "bf16x3", "f16x3", "bf16"] if args.numerics == "auto" else sorted({"fp32", args.numerics}, key=["fp32", "bf16x3", "f16x3", "bf16"].index)
-    sbs, info = {}, {}
     cs = torch.cuda.current_stream().cuda_stream
     plan_args = ([a for a, _ in plan], [b - a for a, b in plan], [4 * i for i in range(len(plan))])
-    for m in modes:
-        sb = make_sb(m)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        toks = sb.decode_script(x, args.chunk, pipelined=True)
-        torch.cuda.synchronize()
-        first_ms = (time.perf_counter() - t0) * 1e3
-        sb.reset()
-        sb.engine.encoder_chunks(x.data_ptr(), args.frames, plan_args[0], plan_args[1], plan_args[2], plan_args[2], cs, greedy=False)
-        enc = sb.engine.enc_frames(cs)
-        sbs[m] = sb
-        info[m] = {"tokens": toks, "first_call_ms": round(first_ms, 2), "enc": enc}
-    ref = info["fp32"]
-    for m in modes:
-        same = sum(int(a == b) for a, b in zip(info[m]["tokens"], ref["tokens"]))
-        info[m]["streams_with_fp32_tokens"] = same
-        info[m]["enc_max_abs_err_vs_fp32"] = float(np.abs(info[m]["enc"].astype(np.float64) - ref["enc"]).max())
-    for m in modes:
-        del info[m]["enc"]
-    if args.numerics == "auto":
-        choice = next(m for m in PARITY_ORDER if info[m]["streams_with_fp32_tokens"] == B)
+    sbs, info = {}, {}
+    if args.full:
+        modes = ["fp32", "bf16x3", "f16x3", "bf16"] if args.numerics == "auto" else sorted({"fp32", args.numerics}, key=["fp32", "bf16x3", "f16x3", "bf16"].index)
+        for m in modes:
+            sb = make_sb(m)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            toks = sb.decode_script(x, args.chunk, pipelined=True)
+            torch.cuda.synchronize()
+            first_ms = (time.perf_counter() - t0) * 1e3
+            sb.reset()
+            sb.engine.encoder_chunks(x.data_ptr(), args.frames, plan_args[0], plan_args[1], plan_args[2], plan_args[2], cs, greedy=False)
+            enc = sb.engine.enc_frames(cs)
+            sbs[m] = sb
+            info[m] = {"tokens": toks, "first_call_ms": round(first_ms, 2), "enc": enc}
+        ref = info["fp32"]
+        for m in modes:
+            same = sum(int(a == b) for a, b in zip(info[m]["tokens"], ref["tokens"]))
+            info[m]["streams_with_fp32_tokens"] = same
+            info[m]["enc_max_abs_err_vs_fp32"] = float(np.abs(info[m]["enc"].astype(np.float64) - ref["enc"]).max())
+        for m in modes:
+            del info[m]["enc"]
+        if args.numerics == "auto":
+            choice = next(m for m in PARITY_ORDER if info[m]["streams_with_fp32_tokens"] == B)
+        else:
+            choice = args.numerics
+    elif args.numerics == "auto":
+        # the same choice as above with fewer passes: the modes in PARITY_ORDER, stopping at the first whose tokens equal fp32's
+        sbs["fp32"] = make_sb("fp32")
+        ref_toks = sbs["fp32"].decode_script(x, args.chunk, pipelined=True)
+        for m in PARITY_ORDER:
+            sbm = sbs["fp32"] if m == "fp32" else make_sb(m)
+            if m == "fp32" or sbm.decode_script(x, args.chunk, pipelined=True) == ref_toks:
+                sbs[m], choice = sbm, m
+                break
+            del sbm
     else:
         choice = args.numerics
+        sbs[choice] = make_sb(choice)
+        sbs[choice].decode_script(x, args.chunk, pipelined=True)    # first call (allocations, tables) outside the timed region
     if world > 1:   # every rank runs the mode rank 0 chose
         c = torch.tensor([["fp32", "bf16x3", "f16x3", "bf16"].index(choice)], device=dev if not rehearsal else "cpu")
         dist.broadcast(c, src=0)
@@ -323,34 +361,7 @@ def main():
     def step():
         return sb.decode_script(x, args.chunk, pipelined=True)
 
-    # ---- site survey (untimed): one step per launch site -> which kernel dominates -------------------------------------------
-    sites = ["conv1", "conv2", "embed", "conv1_minor", "conv2_minor", "embed_minor", "attn", "enc_proj", "block_front", "block_back", "ffn", "ffn_qkv", "ffn_merged", "out_pw1", "ffn1", "ffn2", "qkv", "attn_out", "pw1", "pw2", "dwconv"]   # sites without launches drop out
-    survey = {}
-    for _ in range(args.warmup):
-        toks = step()
-    for sname in sites:
-        sb.engine.profile_begin(TAGS[sname])
-        step()
-        torch.cuda.synchronize()
-        ms, nl = sb.engine.profile_end()
-        fl, by = site_flops_bytes(sname, B, plan)
-        survey[sname] = roof(sname, choice, fl, by, ms, nl, 1)
-    live = {k: v for k, v in survey.items() if v}
-    site = args.site if args.site != "auto" else max(live, key=lambda k: live[k]["ms_per_step"])
-
-    # ---- one batch in flight (untimed extra): the latency of a batch and the dominant site's launches alone on the device --------
-    torch.cuda.synchronize()
-    sb.engine.profile_begin(TAGS[site])
-    t0 = time.perf_counter()
-    n_single = min(args.steps, 5)
-    for _ in range(n_single):
-        toks = step()
-    torch.cuda.synchronize()
-    single_s = (time.perf_counter() - t0) / n_single
-    iso_ms, iso_launches = sb.engine.profile_end()
-    launches, gsteps = sb.engine.counters()
-
-    # ---- timed region: EXACTLY K steps, barrier + synchronize on both sides, max over ranks -------------------------------------
+    # ---- contexts of the timed region and the runner that keeps `nfl` batches in flight ---------------------------------------------
     import threading
     nfl = args.in_flight if args.steps >= 6 else 1              # fewer steps than that cannot fill the two-context pipeline
     ctxs = [sb]
@@ -359,35 +370,71 @@ def main():
         sbk.decode_script(x, args.chunk, pipelined=True)         # first call (allocations, tables) outside the timed region
         ctxs.append(sbk)
     torch.cuda.synchronize()
-    share = [args.steps // nfl + (1 if k < args.steps % nfl else 0) for k in range(nfl)]
-    results = [None] * nfl
-
     wstreams = [torch.cuda.Stream(device=dev) for _ in range(nfl)]
-    gate = threading.Barrier(sum(1 for k in range(nfl) if share[k] > 0) + 1)
 
-    def worker(idx, sbk, n):
-        with torch.cuda.stream(wstreams[idx]):
-            gate.wait()                                          # threads and streams exist before the clock starts
-            for _ in range(n):
-                results[idx] = sbk.decode_script(x, args.chunk, pipelined=True)
-        wstreams[idx].synchronize()
+    def in_flight(n):
+        """n steps shared out over the contexts (one host thread and HIP stream each), barrier + synchronize on both sides:
+        (wall seconds, steps of each context, tokens of each context's last step)"""
+        share = [n // nfl + (1 if k < n % nfl else 0) for k in range(nfl)]
+        results = [None] * nfl
+        gate = threading.Barrier(sum(1 for k in range(nfl) if share[k] > 0) + 1)
 
-    threads = [threading.Thread(target=worker, args=(k, ctxs[k], share[k])) for k in range(nfl) if share[k] > 0]
-    for th in threads:
-        th.start()
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
-    sb.engine.profile_begin(TAGS[site])
-    t0 = time.perf_counter()
-    gate.wait()
-    for th in threads:
-        th.join()
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    elapsed = time.perf_counter() - t0
-    site_ms, site_launches = sb.engine.profile_end()
+        def worker(idx, sbk, n_k):
+            with torch.cuda.stream(wstreams[idx]):
+                gate.wait()                                      # threads and streams exist before the clock starts
+                for _ in range(n_k):
+                    results[idx] = sbk.decode_script(x, args.chunk, pipelined=True)
+            wstreams[idx].synchronize()
+
+        threads = [threading.Thread(target=worker, args=(k, ctxs[k], share[k])) for k in range(nfl) if share[k] > 0]
+        for th in threads:
+            th.start()
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        gate.wait()
+        for th in threads:
+            th.join()
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        return time.perf_counter() - t0, share, results
+
+    if args.warmup:
+        in_flight(args.warmup)
+
+    if args.full:
+        # ---- site survey (untimed): one step per launch site -> which kernel dominates -------------------------------------------
+        sites = ["conv1", "conv2", "embed", "conv1_minor", "conv2_minor", "embed_minor", "attn", "enc_proj", "block_front", "block_back", "ffn", "ffn_qkv", "ffn_merged", "out_pw1", "ffn1", "ffn2", "qkv", "attn_out", "pw1", "pw2", "dwconv"]   # sites without launches drop out
+        survey = {}
+        for sname in sites:
+            sb.engine.profile_begin(TAGS[sname])
+            step()
+            torch.cuda.synchronize()
+            ms, nl = sb.engine.profile_end()
+            fl, by = site_flops_bytes(sname, B, plan)
+            survey[sname] = roof(sname, choice, fl, by, ms, nl, 1)
+        live = {k: v for k, v in survey.items() if v}
+        site = args.site if args.site != "auto" else max(live, key=lambda k: live[k]["ms_per_step"])
+
+        # ---- one batch in flight (untimed extra): the latency of a batch and the dominant site's launches alone on the device --------
+        torch.cuda.synchronize()
+        sb.engine.profile_begin(TAGS[site])
+        t0 = time.perf_counter()
+        n_single = min(args.steps, 5)
+        for _ in range(n_single):
+            toks = step()
+        torch.cuda.synchronize()
+        single_s = (time.perf_counter() - t0) / n_single
+        iso_ms, iso_launches = sb.engine.profile_end()
+        launches, gsteps = sb.engine.counters()
+        sb.engine.profile_begin(TAGS[site])                      # the timed region's launches of that site on context 0
+
+    # ---- timed region: EXACTLY K steps, barrier + synchronize on both sides, max over ranks -------------------------------------
+    elapsed, share, results = in_flight(args.steps)
+    if args.full:
+        site_ms, site_launches = sb.engine.profile_end()
     toks = results[0]
     tokens_same = all(r is None or r == toks for r in results)
     if world > 1:
@@ -398,10 +445,34 @@ def main():
         if world > 1:
             dist.destroy_process_group()
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, toks)
 
     total_frames = world * B * args.frames
     value = total_frames * args.steps / elapsed
     syms = np.array([len(t) for t in toks], dtype=np.float64) / enc_frames
+    out = {
+        "metric": "audio-frames/sec, streaming RNN-T greedy decode",
+        "value": round(value, 1), "unit": "audio-frames/s", "rtfx": round(value / 100.0, 1), "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": choice, "data": "synthetic",
+        "config": {"workload": f"configs[1]: batch={B}/GPU synthetic {args.frames / 100:.0f} s 80-dim fbank, streaming chunk={args.chunk} "
+                               f"(online_rnnt_decode.py semantics), greedy decode, whole-utterance call (tokens identical to the per-chunk API)",
+                   "streams_per_gpu": B, "frames_per_stream": args.frames, "chunk_frames": args.chunk, "chunks": len(plan), "encoder_frames_per_stream": enc_frames,
+                   "symbols_per_encoder_frame": {"mean": round(float(syms.mean()), 3), "slowest_stream": round(float(syms.max()), 3)},
+                   "weights": f"seeded synthetic (seed 0, blank_bias {args.blank_bias})", "parallelism": f"streams sharded x{world}, no data-path collective",
+                   "numerics": {"headline": choice, "selection": "fastest parity-gated mode: first of bf16x3, f16x3, fp32 whose greedy tokens equal the exact-f32 mode's on every stream" if args.numerics == "auto" else "forced by --numerics",
+                                "storage": "fp32", "accumulate": "fp32", "decoder_arithmetic": "fp32 (VALU)"}},
+        "batches_in_flight": nfl,
+        "tokens_identical_across_contexts": bool(tokens_same),
+        "weight_broadcast_ms": round(bcast_ms, 3),
+    }
+    if not args.full:
+        print(json.dumps(out))
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
     fl, by = site_flops_bytes(site, B, plan)
     roofline = roof(site, choice, fl, by, site_ms, site_launches, share[0])
     if roofline:
@@ -419,26 +490,12 @@ def main():
             if site in ("ffn", "ffn_qkv", "ffn_merged", "out_pw1"):   # one kernel name for three launch kinds: the profile cannot tell them apart
                 roofline["traffic_note"] = "mean over ALL ffn_as launches of the step (FFN + q/k/v, linear_out + pointwise_conv1, FFN + norm_final share one kernel name), not this site alone"
     other_sites = {k: v for k, v in live.items() if k != site}
-
-    out = {
-        "metric": "audio-frames/sec, streaming RNN-T greedy decode",
-        "value": round(value, 1), "unit": "audio-frames/s", "rtfx": round(value / 100.0, 1), "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": choice, "data": "synthetic",
-        "config": {"workload": f"configs[1]: batch={B}/GPU synthetic {args.frames / 100:.0f} s 80-dim fbank, streaming chunk={args.chunk} "
-                               f"(online_rnnt_decode.py semantics), greedy decode, whole-utterance call (tokens identical to the per-chunk API)",
-                   "streams_per_gpu": B, "frames_per_stream": args.frames, "chunk_frames": args.chunk, "chunks": len(plan), "encoder_frames_per_stream": enc_frames,
-                   "symbols_per_encoder_frame": {"mean": round(float(syms.mean()), 3), "slowest_stream": round(float(syms.max()), 3)},
-                   "weights": f"seeded synthetic (seed 0, blank_bias {args.blank_bias})", "parallelism": f"streams sharded x{world}, no data-path collective",
-                   "numerics": {"headline": choice, "selection": "fastest parity-gated mode: first of bf16x3, f16x3, fp32 whose greedy tokens equal the exact-f32 mode's on every stream" if args.numerics == "auto" else "forced by --numerics",
-                                "storage": "fp32", "accumulate": "fp32", "decoder_arithmetic": "fp32 (VALU)"}},
-        "batches_in_flight": nfl,
+    out.update({
         "one_batch_in_flight": {"ms_per_step": round(single_s * 1e3, 3), "value": round(world * B * args.frames / single_s, 1), "unit": "audio-frames/s",
                                 "note": "latency of one 64-stream batch with nothing else on the GPU (this rank); the headline keeps two batches in flight on two contexts"},
-        "tokens_identical_across_contexts": bool(tokens_same),
-        "kernel_launches_per_step": int(launches), "greedy_evaluations_per_step": int(gsteps), "weight_broadcast_ms": round(bcast_ms, 3),
+        "kernel_launches_per_step": int(launches), "greedy_evaluations_per_step": int(gsteps),
         "roofline": roofline, "roofline_other_sites": other_sites,
-    }
+    })
     if world > 1:
         print(json.dumps(out))
         dist.destroy_process_group()

@@ -8,7 +8,7 @@ O=$R/gpurun_out/prof_${1:-x}
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 for leg in ${2:-step joint}; do
-  if [ $leg = step ]; then CMD="python3 $R/bench.py --no-legs --no-cpu --numerics bf16x3 --steps 10"; else CMD="python3 $R/bench.py --legs joint --no-cpu --numerics bf16x3 --steps 2 --in-flight 1"; fi
+  if [ $leg = step ]; then CMD="python3 $R/bench.py --full --no-legs --no-cpu --numerics bf16x3 --steps 10"; else CMD="python3 $R/bench.py --full --legs joint --no-cpu --numerics bf16x3 --steps 2 --in-flight 1"; fi
   echo kt $leg start; timeout -k 10 ${PASS_LIMIT:-150} rocprofv3 --kernel-trace --stats -d $O/kt_$leg -o kt -- $CMD > $O/bench_kt_$leg.json 2> $O/kt_$leg.err
   echo kt $leg done
   timeout -k 10 ${PASS_LIMIT:-150} rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY --output-format csv -d $O/mfma_$leg -o mfma -- $CMD > $O/bench_mfma_$leg.json 2> $O/mfma_$leg.err
