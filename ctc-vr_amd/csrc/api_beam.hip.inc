@@ -234,3 +234,221 @@ int rnnt_frames_discard(rnnt_ctx* ctx, void* stream) {
     HIPCHK(hipMemsetAsync(ctx->fidx, 0, ctx->cfg.max_streams * sizeof(int), s));
     return RNNT_OK;
 }
+
+// ---- device-resident beam search (rnnt_beam_decode) ----------------------------------------------------------------------------
+namespace {
+// per-row lengths / scores / hashes [2][max_rows] and per-stream counts (allocated once), token lists [2][max_rows][lcap] (grown)
+int beam_dev_buffers(rnnt_ctx* ctx, size_t lcap) {
+    const size_t R = ctx->max_rows, Bm = ctx->cfg.max_streams;
+    int rc;
+    if (!ctx->bd_len && (rc = dmalloc(ctx, &ctx->bd_len, 2 * R))) return rc;
+    if (!ctx->bd_sc && (rc = dmalloc(ctx, &ctx->bd_sc, 2 * R))) return rc;
+    if (!ctx->bd_hs && (rc = dmalloc(ctx, &ctx->bd_hs, 2 * R))) return rc;
+    if (!ctx->bd_nh && (rc = dmalloc(ctx, &ctx->bd_nh, Bm))) return rc;
+    if (!ctx->bd_fend && (rc = dmalloc(ctx, &ctx->bd_fend, Bm))) return rc;
+    return grow(ctx, &ctx->bd_tok, &ctx->bd_tok_cap, 2 * R * lcap);
+}
+
+unsigned long long beam_hash(const int* t, size_t n) {
+    unsigned long long h = BEAM_HASH0;
+    for (size_t i = 0; i < n; ++i) h = beam_hash_step(h, t[i]);
+    return h;
+}
+
+BeamMergeP beam_merge_params(rnnt_ctx* ctx, int t, size_t lcap, int n_steps, int k, int beam, int width, int f) {
+    const size_t R = ctx->max_rows;
+    BeamMergeP m;
+    memset(&m, 0, sizeof(m));
+    m.tk_in = ctx->bd_tok + t * R * lcap; m.tk_out = ctx->bd_tok + (t ^ 1) * R * lcap;
+    m.len_in = ctx->bd_len + t * R; m.len_out = ctx->bd_len + (t ^ 1) * R;
+    m.sc_in = ctx->bd_sc + t * R; m.sc_out = ctx->bd_sc + (t ^ 1) * R;
+    m.hs_in = ctx->bd_hs + t * R; m.hs_out = ctx->bd_hs + (t ^ 1) * R;
+    m.nh = ctx->bd_nh; m.fend = ctx->bd_fend;
+    m.steps = ctx->b_steps; m.blank_lp = ctx->b_blank; m.top_lp = ctx->b_toplp; m.top_tok = ctx->b_toptok;
+    m.tok_next = ctx->b_tok; m.frame_next = ctx->b_frame; m.live = ctx->b_active; m.src_row = ctx->b_srcrow; m.src_step = ctx->b_srcstep;
+    m.slots = ctx->cfg.n_steps + 1; m.lcap = (int)lcap; m.n_steps = n_steps; m.k = k; m.beam = beam; m.width = width;
+    m.blank = ctx->cfg.blank_id; m.f = f; m.fstride = ctx->fstride;
+    return m;
+}
+}  // namespace
+
+// rnnt_beam_advance with the whole frame loop on the device: per frame one beam_chain launch (fixed-slot rows, dead rows exit at
+// once) and one beam_merge_dev launch (candidates, stable order, de-duplication, truncation, state gather, next frame's inputs);
+// no host copy and no synchronisation between frames.  Stream b covers frames [frame_begin, frame_end_host[b]).  Supported:
+// beam_size <= 16, vocab <= 512, n_steps <= 10, the chain kernel enabled; otherwise RNNT_ERR_ARG / RNNT_ERR_STATE and the caller
+// uses rnnt_beam_advance.
+int rnnt_beam_decode(rnnt_ctx* ctx, int32_t frame_begin, const int32_t* frame_end_host, int32_t beam_size, void* stream) {
+    if (!ctx) return RNNT_ERR_ARG;
+    if (!ctx->finalized || ctx->n_streams < 1) return fail(ctx, RNNT_ERR_STATE, "rnnt_beam_decode: no weights / no streams");
+    if (ctx->max_rows == 0) return fail(ctx, RNNT_ERR_STATE, "rnnt_beam_decode: context created with max_beam = 0");
+    if (!ctx->use_beam_chain) return fail(ctx, RNNT_ERR_STATE, "rnnt_beam_decode: RNNT_BEAM_CHAIN=0 (the device merge follows beam_chain only); use rnnt_beam_advance");
+    const int V = ctx->cfg.vocab_size, NS = ctx->cfg.n_steps, B = ctx->n_streams;
+    if (beam_size < 1 || beam_size > ctx->cfg.max_beam || beam_size > BM_MAX_BEAM)
+        return fail(ctx, RNNT_ERR_ARG, "rnnt_beam_decode: beam_size %d outside [1, min(max_beam %d, %d)]", beam_size, ctx->cfg.max_beam, BM_MAX_BEAM);
+    if (V > 512 || NS > BM_MAX_STEPS) return fail(ctx, RNNT_ERR_ARG, "rnnt_beam_decode: vocab %d > 512 or n_steps %d > %d; use rnnt_beam_advance", V, NS, BM_MAX_STEPS);
+    if ((int)ctx->beams.size() != B) return fail(ctx, RNNT_ERR_STATE, "rnnt_beam_decode: call rnnt_streams_reset first");
+    std::vector<int> fend(B), nh(B);
+    int fmax = frame_begin, width = beam_size;
+    size_t lmax = 0;
+    for (int b = 0; b < B; ++b) {
+        fend[b] = frame_end_host ? frame_end_host[b] : ctx->frames_buffered;
+        if (frame_begin < 0 || fend[b] < frame_begin || fend[b] > ctx->frames_buffered)
+            return fail(ctx, RNNT_ERR_ARG, "rnnt_beam_decode: stream %d: frames [%d, %d) not buffered", b, frame_begin, fend[b]);
+        fmax = std::max(fmax, fend[b]);
+        nh[b] = (int)ctx->beams[b].size();
+        width = std::max(width, nh[b]);
+        for (const rnnt_ctx::Hyp& h : ctx->beams[b]) lmax = std::max(lmax, h.tokens.size());
+    }
+    if (width > BM_MAX_BEAM || (size_t)B * width > (size_t)ctx->max_rows)
+        return fail(ctx, RNNT_ERR_ARG, "rnnt_beam_decode: %d hypotheses per stream; use rnnt_beam_advance", width);
+    if (fmax == frame_begin) return RNNT_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const int R = B * width, F = fmax - frame_begin, slots = NS + 1;
+    const int k = beam_size < V - 1 ? beam_size : V - 1;                                                // :467
+    const size_t lcap = lmax + (size_t)F * NS;   // a hypothesis grows by at most n_steps tokens per frame: no overflow
+    if (lcap > (size_t)INT_MAX / 2 || (size_t)R * lcap > ((size_t)1 << 31)) return fail(ctx, RNNT_ERR_SHAPE, "rnnt_beam_decode: token pool too large");
+    int rc;
+    if ((rc = beam_dev_buffers(ctx, lcap))) return rc;
+    // ---- upload: hypotheses into fixed slots (row b * width + i), next-frame inputs, compacted pool rows -> fixed-slot rows -----
+    std::vector<int> tok(R, ctx->cfg.blank_id), frame(R, 0), live(R, 0), len(R, 0), srow(R, 0), sstep(R, 0);
+    std::vector<double> sc(R, 0.0);
+    std::vector<unsigned long long> hs(R, BEAM_HASH0);
+    std::vector<int> toks((size_t)R * std::max<size_t>(lmax, 1), 0);
+    for (int b = 0, crow = 0; b < B; ++b)
+        for (int i = 0; i < nh[b]; ++i, ++crow) {
+            const rnnt_ctx::Hyp& h = ctx->beams[b][i];
+            const int r = b * width + i;
+            tok[r] = h.tokens.empty() ? ctx->cfg.blank_id : h.tokens.back();                                 // :429
+            frame[r] = b * ctx->fstride + frame_begin;
+            live[r] = frame_begin < fend[b] ? 1 : 0;
+            len[r] = (int)h.tokens.size();
+            sc[r] = h.log_prob;
+            hs[r] = beam_hash(h.tokens.data(), h.tokens.size());
+            srow[r] = crow;
+            std::copy(h.tokens.begin(), h.tokens.end(), toks.begin() + (size_t)r * lmax);
+        }
+    const size_t Rm = ctx->max_rows;
+    int* tk0 = ctx->bd_tok;
+    HIPCHK(hipMemcpyAsync(ctx->b_tok, tok.data(), R * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->b_frame, frame.data(), R * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->b_active, live.data(), R * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->b_srcrow, srow.data(), R * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->b_srcstep, sstep.data(), R * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->bd_len, len.data(), R * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->bd_sc, sc.data(), R * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->bd_hs, hs.data(), R * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->bd_nh, nh.data(), B * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->bd_fend, fend.data(), B * sizeof(int), hipMemcpyHostToDevice, s));
+    if (lmax > 0)
+        HIPCHK(hipMemcpy2DAsync(tk0, lcap * sizeof(int), toks.data(), lmax * sizeof(int), lmax * sizeof(int), R, hipMemcpyHostToDevice, s));
+    int cur = ctx->pool_cur, t = 0;
+    hipLaunchKernelGGL(beam_gather, dim3(R), dim3(128), 0, s, ctx->pool[cur], ctx->pool[cur ^ 1], ctx->b_srcrow, ctx->b_srcstep, R, slots);
+    LAUNCHCHK("beam_gather");
+    cur ^= 1;
+    // ---- frame loop: launches only ----------------------------------------------------------------------------------------------
+    BeamChainP c;
+    memset(&c, 0, sizeof(c));
+    c.whh = ctx->whh_il; c.egate = ctx->egate; c.wpr = ctx->wpr; c.bpr = ctx->bpr; c.wpf = ctx->wpf; c.bpf = ctx->bpf;
+    c.wout = ctx->wout; c.bout = ctx->bout; c.encp = ctx->encp; c.frame = ctx->b_frame; c.tok_in = ctx->b_tok; c.live = ctx->b_active;
+    c.steps = ctx->b_steps; c.blank_lp = ctx->b_blank; c.top_lp = ctx->b_toplp; c.top_tok = ctx->b_toptok;
+    c.vocab = V; c.blank = ctx->cfg.blank_id; c.k = k; c.n_steps = NS; c.slots = slots;
+    for (int f = frame_begin; f < fmax; ++f) {
+        c.pool = ctx->pool[cur];
+        hipLaunchKernelGGL(beam_chain, dim3(R), dim3(512), 0, s, c);
+        LAUNCHCHK("beam_chain");
+        BeamMergeP m = beam_merge_params(ctx, t, lcap, NS, k, beam_size, width, f);
+        m.pool_in = ctx->pool[cur]; m.pool_out = ctx->pool[cur ^ 1];
+        hipLaunchKernelGGL(beam_merge_dev, dim3(B), dim3(BM_NT), 0, s, m);
+        LAUNCHCHK("beam_merge_dev");
+        cur ^= 1; t ^= 1;
+    }
+    // ---- compaction (rows of stream b after those of streams < b, as rnnt_beam_advance leaves them), one download, one sync -----
+    hipLaunchKernelGGL(beam_compact, dim3(R), dim3(128), 0, s, ctx->pool[cur], ctx->pool[cur ^ 1], slots, ctx->bd_tok + t * Rm * lcap,
+                       ctx->bd_tok + (t ^ 1) * Rm * lcap, (int)lcap, ctx->bd_len + t * Rm, ctx->bd_len + (t ^ 1) * Rm, ctx->bd_sc + t * Rm,
+                       ctx->bd_sc + (t ^ 1) * Rm, ctx->bd_nh, width);
+    LAUNCHCHK("beam_compact");
+    cur ^= 1; t ^= 1;
+    std::vector<int> out_tok((size_t)R * lcap);
+    HIPCHK(hipMemcpyAsync(nh.data(), ctx->bd_nh, B * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(len.data(), ctx->bd_len + t * Rm, R * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(sc.data(), ctx->bd_sc + t * Rm, R * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out_tok.data(), ctx->bd_tok + t * Rm * lcap, (size_t)R * lcap * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    ctx->pool_cur = cur;
+    for (int b = 0, crow = 0; b < B; ++b) {
+        ctx->beams[b].resize(nh[b]);
+        for (int i = 0; i < nh[b]; ++i, ++crow) {
+            const int* p = out_tok.data() + (size_t)crow * lcap;
+            ctx->beams[b][i].tokens.assign(p, p + len[crow]);
+            ctx->beams[b][i].log_prob = sc[crow];
+        }
+    }
+    return RNNT_OK;
+}
+
+// One beam_merge_dev launch on flat host inputs for ONE stream (test seam against rnnt_beam_merge_host on adversarial inputs):
+// same arguments and results as rnnt_beam_merge_host (src_row = the hypothesis index).  Uses the context's beam scratch only:
+// the state pools and the hypotheses of rnnt_beam_advance / rnnt_beam_decode are left alone.  Synchronises.
+int rnnt_beam_merge_device(rnnt_ctx* ctx, int32_t n_hyp, const int32_t* hyp_len, const int32_t* hyp_tokens, const double* hyp_score,
+                           const int32_t* steps, const float* blank_lp, const float* top_lp, const int32_t* top_tok, int32_t n_steps,
+                           int32_t k, int32_t beam_size, int32_t* out_len, int32_t* out_tokens, double* out_score, int32_t* out_src_row,
+                           int32_t* out_src_step, void* stream) {
+    if (!ctx) return RNNT_ERR_ARG;
+    if (!hyp_len || !hyp_score || !steps || !blank_lp || !top_lp || !top_tok || !out_len || !out_tokens || !out_score)
+        return fail(ctx, RNNT_ERR_ARG, "rnnt_beam_merge_device: null argument");
+    if (ctx->max_rows == 0) return fail(ctx, RNNT_ERR_STATE, "rnnt_beam_merge_device: context created with max_beam = 0");
+    const int width = std::max(n_hyp, beam_size);
+    if (n_hyp < 1 || beam_size < 1 || width > BM_MAX_BEAM || width > ctx->max_rows || k < 1 || k > BM_MAX_BEAM || k > ctx->cfg.max_beam ||
+        n_steps < 1 || n_steps > BM_MAX_STEPS || n_steps > ctx->cfg.n_steps)
+        return fail(ctx, RNNT_ERR_ARG, "rnnt_beam_merge_device: n_hyp %d, beam %d, k %d, n_steps %d outside the supported range", n_hyp, beam_size, k, n_steps);
+    size_t lmax = 0, ntok = 0;
+    for (int i = 0; i < n_hyp; ++i) {
+        if (hyp_len[i] < 0 || steps[i] < 0 || steps[i] > n_steps) return fail(ctx, RNNT_ERR_ARG, "rnnt_beam_merge_device: bad hypothesis %d", i);
+        lmax = std::max(lmax, (size_t)hyp_len[i]);
+        ntok += hyp_len[i];
+    }
+    if (ntok && !hyp_tokens) return fail(ctx, RNNT_ERR_ARG, "rnnt_beam_merge_device: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t lcap = lmax + n_steps, Rm = ctx->max_rows;
+    int rc;
+    if ((rc = beam_dev_buffers(ctx, lcap))) return rc;
+    std::vector<int> toks((size_t)width * lcap, 0), len(width, 0), nh(1, n_hyp), fend(1, 1);
+    std::vector<double> sc(width, 0.0);
+    std::vector<unsigned long long> hs(width, BEAM_HASH0);
+    for (int i = 0, off = 0; i < n_hyp; off += hyp_len[i], ++i) {
+        std::copy(hyp_tokens + off, hyp_tokens + off + hyp_len[i], toks.begin() + (size_t)i * lcap);
+        len[i] = hyp_len[i];
+        sc[i] = hyp_score[i];
+        hs[i] = beam_hash(hyp_tokens + off, hyp_len[i]);
+    }
+    HIPCHK(hipMemcpyAsync(ctx->bd_tok, toks.data(), toks.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->bd_len, len.data(), width * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->bd_sc, sc.data(), width * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->bd_hs, hs.data(), width * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->bd_nh, nh.data(), sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->bd_fend, fend.data(), sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->b_steps, steps, n_hyp * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->b_blank, blank_lp, (size_t)n_hyp * n_steps * sizeof(float), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->b_toplp, top_lp, (size_t)n_hyp * n_steps * k * sizeof(float), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->b_toptok, top_tok, (size_t)n_hyp * n_steps * k * sizeof(int), hipMemcpyHostToDevice, s));
+    BeamMergeP m = beam_merge_params(ctx, 0, lcap, n_steps, k, beam_size, width, 0);   // pool_in == nullptr: no state gather
+    hipLaunchKernelGGL(beam_merge_dev, dim3(1), dim3(BM_NT), 0, s, m);
+    LAUNCHCHK("beam_merge_dev");
+    std::vector<int> srow(width), sstep(width);
+    HIPCHK(hipMemcpyAsync(nh.data(), ctx->bd_nh, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(len.data(), ctx->bd_len + Rm, width * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(sc.data(), ctx->bd_sc + Rm, width * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(toks.data(), ctx->bd_tok + Rm * lcap, toks.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(srow.data(), ctx->b_srcrow, width * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(sstep.data(), ctx->b_srcstep, width * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    size_t off = 0;
+    for (int a = 0; a < nh[0]; ++a) {
+        out_len[a] = len[a];
+        for (int q = 0; q < len[a]; ++q) out_tokens[off++] = toks[(size_t)a * lcap + q];
+        out_score[a] = sc[a];
+        if (out_src_row) out_src_row[a] = srow[a];
+        if (out_src_step) out_src_step[a] = sstep[a];
+    }
+    return nh[0];
+}

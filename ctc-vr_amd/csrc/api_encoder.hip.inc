@@ -42,34 +42,23 @@ int rnnt_encoder_chunk(rnnt_ctx* ctx, const float* fbank_dev, int32_t T, int32_t
     return RNNT_OK;
 }
 
-// Greedy decode of a PADDED batch of whole utterances of different lengths in one call (utils/utils.py:29-50 pads a batch,
-// online_rnnt_eval.py:86-94 decodes every utterance with its own audio_lens): stream b runs the decode script's chunk loop
-// (online_rnnt_decode.py:81-117: chunks of chunk_frames, a remainder shorter than max(16, chunk_frames) merged into the last
-// chunk, chunks under 7 frames skipped) over its own lens_host[b] frames, so its tokens are those of a B = 1 run.
-// The common full-size chunks run for all streams at once in the layer-major schedule; every stream's last chunk is subsampled
-// per tail-length class and takes part in the same launches with its own key window and positional offset (host_lm.hip.inc).
-// Needs freshly reset streams; the stream state is not meaningful afterwards (reset before the next call).  Streams whose
-// utterance is a single chunk (fewer than chunk_frames + max(16, chunk_frames) frames, but at least 7) are not supported by this
-// entry point (RNNT_ERR_SHAPE): run them with rnnt_encoder_chunks.  frames_out [n_streams] (optional): encoder frames per stream.
-int rnnt_decode_ragged(rnnt_ctx* ctx, const float* fbank_dev, int32_t total_frames, const int32_t* lens_host, int32_t chunk_frames,
-                       int32_t* frames_out, void* stream) {
-    if (!ctx || !fbank_dev || !lens_host) return fail(ctx, RNNT_ERR_ARG, "rnnt_decode_ragged: null argument");
-    if (!ctx->finalized || ctx->n_streams < 1) return fail(ctx, RNNT_ERR_STATE, "rnnt_decode_ragged: no weights / no streams");
-    if (ctx->cache_len || ctx->kv_start || ctx->conv_pos || ctx->frames_buffered)
-        return fail(ctx, RNNT_ERR_STATE, "rnnt_decode_ragged needs freshly reset streams");
-    if (!ctx->use_lm || !ctx->use_persistent) return fail(ctx, RNNT_ERR_STATE, "rnnt_decode_ragged needs the layer-major schedule and the resident decoder");
+namespace {
+// Planning and encoder launches shared by rnnt_decode_ragged and rnnt_encode_ragged: every stream's chunk plan over its own
+// lens_host[b] frames, the layer-major launches over the common chunks plus every stream's tail chunk, and the stream state a
+// uniform call over the common chunks would leave.  greedy != 0: only enc_proj is formed (the greedy decoder reads nothing else);
+// greedy == 0: after_norm frames (encbuf) and enc_proj (encp) of every stream's rows.  The caller has checked the context state.
+int ragged_encode(rnnt_ctx* ctx, const char* who, const float* fbank_dev, int32_t total_frames, const int32_t* lens_host, int32_t chunk_frames,
+                  int greedy, hipStream_t s, RaggedPlan& rg) {
     const int cf = chunk_frames, minc = cf > 16 ? cf : 16;
     if (cf < 7 || cf + minc - 1 > ctx->cfg.max_chunk_frames)
-        return fail(ctx, RNNT_ERR_SHAPE, "rnnt_decode_ragged: chunk_frames %d (a merged last chunk has up to %d frames; max_chunk_frames %d)", cf, cf + minc - 1, ctx->cfg.max_chunk_frames);
-    hipStream_t s = (hipStream_t)stream;
+        return fail(ctx, RNNT_ERR_SHAPE, "%s: chunk_frames %d (a merged last chunk has up to %d frames; max_chunk_frames %d)", who, cf, cf + minc - 1, ctx->cfg.max_chunk_frames);
     const int B = ctx->n_streams;
-    RaggedPlan rg;
     rg.nb.assign(B, 0); rg.tail.assign(B, ChunkInfo{0, 0, 0, 0, 0, 0, 0, 0}); rg.frames.assign(B, 0);
     int Kmax = 0;
     std::vector<int> tail_len(B, 0);
     for (int b = 0; b < B; ++b) {
         const int T = lens_host[b];
-        if (T < 0 || T > total_frames) return fail(ctx, RNNT_ERR_SHAPE, "rnnt_decode_ragged: stream %d has %d of %d frames", b, T, total_frames);
+        if (T < 0 || T > total_frames) return fail(ctx, RNNT_ERR_SHAPE, "%s: stream %d has %d of %d frames", who, b, T, total_frames);
         if (T < 7) continue;                                        // shorter than the conv front-end's receptive field: skipped (:356-359)
         int off = 0, n = 0;                                         // the decode script's slicing rule (:87-93)
         while (off < T) {
@@ -79,11 +68,11 @@ int rnnt_decode_ragged(rnnt_ctx* ctx, const float* fbank_dev, int32_t total_fram
             ++n;
             off = end;
         }
-        if (n < 1) return fail(ctx, RNNT_ERR_SHAPE, "rnnt_decode_ragged: stream %d (%d frames) is a single chunk; use rnnt_encoder_chunks for it", b, T);
+        if (n < 1) return fail(ctx, RNNT_ERR_SHAPE, "%s: stream %d (%d frames) is a single chunk; use rnnt_encoder_chunks for it", who, b, T);
         rg.nb[b] = n;
         Kmax = n > Kmax ? n : Kmax;
     }
-    if (Kmax < 2) return fail(ctx, RNNT_ERR_SHAPE, "rnnt_decode_ragged: the longest utterance must have at least three chunks");
+    if (Kmax < 2) return fail(ctx, RNNT_ERR_SHAPE, "%s: the longest utterance must have at least three chunks", who);
     // the reference's per-chunk bookkeeping (encoder.py:254-264) for the common chunks: offset = required_cache_size = c * (cf / 4)
     std::vector<ChunkInfo> ci(Kmax);
     struct St { int cache_len, kv_start, conv_pos, fb; };
@@ -127,11 +116,36 @@ int rnnt_decode_ragged(rnnt_ctx* ctx, const float* fbank_dev, int32_t total_fram
     int rc;
     bool done = false;
     const std::vector<int> key = {-1};
-    if ((rc = encoder_chunks_lm(ctx, s, fbank_dev, total_frames, starts.data(), ci, key, 1, &done, nullptr, nullptr, &rg))) return rc;
-    if (!done) return fail(ctx, RNNT_ERR_STATE, "rnnt_decode_ragged: the layer-major schedule cannot run this plan");
+    if ((rc = encoder_chunks_lm(ctx, s, fbank_dev, total_frames, starts.data(), ci, key, greedy, &done, nullptr, nullptr, &rg))) return rc;
+    if (!done) return fail(ctx, RNNT_ERR_STATE, "%s: the layer-major schedule cannot run this plan", who);
     // the state a uniform call over the common chunks would leave (not meaningful for the shorter streams: reset before reuse)
     ctx->cache_len = after[Kmax - 1].cache_len; ctx->kv_start = after[Kmax - 1].kv_start; ctx->conv_pos = after[Kmax - 1].conv_pos;
     ctx->frames_buffered = rg.F;
+    return RNNT_OK;
+}
+}  // namespace
+
+// Greedy decode of a PADDED batch of whole utterances of different lengths in one call (utils/utils.py:29-50 pads a batch,
+// online_rnnt_eval.py:86-94 decodes every utterance with its own audio_lens): stream b runs the decode script's chunk loop
+// (online_rnnt_decode.py:81-117: chunks of chunk_frames, a remainder shorter than max(16, chunk_frames) merged into the last
+// chunk, chunks under 7 frames skipped) over its own lens_host[b] frames, so its tokens are those of a B = 1 run.
+// The common full-size chunks run for all streams at once in the layer-major schedule; every stream's last chunk is subsampled
+// per tail-length class and takes part in the same launches with its own key window and positional offset (host_lm.hip.inc).
+// Needs freshly reset streams; the stream state is not meaningful afterwards (reset before the next call).  Streams whose
+// utterance is a single chunk (fewer than chunk_frames + max(16, chunk_frames) frames, but at least 7) are not supported by this
+// entry point (RNNT_ERR_SHAPE): run them with rnnt_encoder_chunks.  frames_out [n_streams] (optional): encoder frames per stream.
+int rnnt_decode_ragged(rnnt_ctx* ctx, const float* fbank_dev, int32_t total_frames, const int32_t* lens_host, int32_t chunk_frames,
+                       int32_t* frames_out, void* stream) {
+    if (!ctx || !fbank_dev || !lens_host) return fail(ctx, RNNT_ERR_ARG, "rnnt_decode_ragged: null argument");
+    if (!ctx->finalized || ctx->n_streams < 1) return fail(ctx, RNNT_ERR_STATE, "rnnt_decode_ragged: no weights / no streams");
+    if (ctx->cache_len || ctx->kv_start || ctx->conv_pos || ctx->frames_buffered)
+        return fail(ctx, RNNT_ERR_STATE, "rnnt_decode_ragged needs freshly reset streams");
+    if (!ctx->use_lm || !ctx->use_persistent) return fail(ctx, RNNT_ERR_STATE, "rnnt_decode_ragged needs the layer-major schedule and the resident decoder");
+    hipStream_t s = (hipStream_t)stream;
+    const int B = ctx->n_streams;
+    RaggedPlan rg;
+    int rc;
+    if ((rc = ragged_encode(ctx, "rnnt_decode_ragged", fbank_dev, total_frames, lens_host, chunk_frames, 1, s, rg))) return rc;
     HIPCHK(hipMemcpyAsync(ctx->klen, rg.frames.data(), B * sizeof(int), hipMemcpyHostToDevice, s));   // per-stream frame limits of the decoder
     HIPCHK(hipStreamSynchronize(s));                                // rg.frames dies at scope end
     if ((rc = init_decoder_ctrl(ctx, s, rg.F))) return rc;
@@ -139,6 +153,23 @@ int rnnt_decode_ragged(rnnt_ctx* ctx, const float* fbank_dev, int32_t total_fram
     if ((rc = finish_persistent_decoder(ctx, s))) return rc;
     ctx->frames_decoded = rg.F;
     if (frames_out) for (int b = 0; b < B; ++b) frames_out[b] = rg.frames[b];
+    return RNNT_OK;
+}
+
+// The planning and encoder launches of rnnt_decode_ragged without the greedy decoder: stream b's frames_out[b] encoder frames
+// stay in the frame buffer (encbuf after_norm, encp joint-projected) for rnnt_beam_decode with frame_end_host = frames_out.
+// Same preconditions and refusals as rnnt_decode_ragged; does not synchronise.
+int rnnt_encode_ragged(rnnt_ctx* ctx, const float* fbank_dev, int32_t total_frames, const int32_t* lens_host, int32_t chunk_frames,
+                       int32_t* frames_out, void* stream) {
+    if (!ctx || !fbank_dev || !lens_host) return fail(ctx, RNNT_ERR_ARG, "rnnt_encode_ragged: null argument");
+    if (!ctx->finalized || ctx->n_streams < 1) return fail(ctx, RNNT_ERR_STATE, "rnnt_encode_ragged: no weights / no streams");
+    if (ctx->cache_len || ctx->kv_start || ctx->conv_pos || ctx->frames_buffered)
+        return fail(ctx, RNNT_ERR_STATE, "rnnt_encode_ragged needs freshly reset streams");
+    if (!ctx->use_lm) return fail(ctx, RNNT_ERR_STATE, "rnnt_encode_ragged needs the layer-major schedule");
+    RaggedPlan rg;
+    int rc;
+    if ((rc = ragged_encode(ctx, "rnnt_encode_ragged", fbank_dev, total_frames, lens_host, chunk_frames, 0, (hipStream_t)stream, rg))) return rc;
+    if (frames_out) for (int b = 0; b < ctx->n_streams; ++b) frames_out[b] = rg.frames[b];
     return RNNT_OK;
 }
 

@@ -128,6 +128,16 @@ int encoder_chunks_lm(rnnt_ctx* ctx, hipStream_t s, const float* fbank_dev, int 
     }
     float* x = ctx->lm_x;
     bool ctx_in_done = false;                                      // (c) already launched on the side stream
+    // An error exit between the fork onto the side stream and the join still joins it: work already enqueued there writes x, lm_g
+    // and the side slabs, and must not run on unordered with whatever the caller enqueues next on `s`.
+    struct SideJoin {
+        rnnt_ctx* ctx; hipStream_t s; bool armed;
+        ~SideJoin() {
+            if (!armed) return;
+            (void)hipEventRecord(ctx->sub_ev[1], ctx->sub_stream);
+            (void)hipStreamWaitEvent(s, ctx->sub_ev[1], 0);
+        }
+    } side_join{ctx, s, false};
     // ---- (a) subsampling: every run of equal-length chunks in one slab, stream-major ------------------------------------------
     if ((rc = grow(ctx, &ctx->wf_starts, &ctx->wf_starts_cap, (size_t)C))) return rc;
     HIPCHK(hipMemcpyAsync(ctx->wf_starts, chunk_start, C * sizeof(int), hipMemcpyHostToDevice, s));
@@ -166,6 +176,7 @@ int encoder_chunks_lm(rnnt_ctx* ctx, hipStream_t s, const float* fbank_dev, int 
             }
             HIPCHK(hipEventRecord(ctx->sub_ev[0], s));            // fbank, chunk starts and everything earlier on the caller's stream
             HIPCHK(hipStreamWaitEvent(ctx->sub_stream, ctx->sub_ev[0], 0));
+            side_join.armed = true;
             // (c) the left context of every layer's conv module depends on nothing of this call either: it rides along
             hipLaunchKernelGGL(lm_ctx_in, dim3(grid_for((long long)L * B * RNNT_LORDER * D)), dim3(256), 0, ctx->sub_stream, ctx->gring, ctx->lm_g, B, Bm,
                                ctx->cap, gs, ci[0].ring_pos);
@@ -186,7 +197,10 @@ int encoder_chunks_lm(rnnt_ctx* ctx, hipStream_t s, const float* fbank_dev, int 
                                     nc * ci[c0].tq, F, ci[c0].fpos - fb0, c0 != 0)))
                 return rc;
         }
-        if (side) HIPCHK(hipStreamWaitEvent(s, ctx->sub_ev[1], 0));   // join: layer 0 reads every class's rows of x
+        if (side) {
+            side_join.armed = false;
+            HIPCHK(hipStreamWaitEvent(s, ctx->sub_ev[1], 0));     // join: layer 0 reads every class's rows of x
+        }
     }
     // ---- (a') ragged batch: every stream's tail chunk, one subsampling pass per tail length ---------------------------------------
     if (rg) {

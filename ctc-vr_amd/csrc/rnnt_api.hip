@@ -148,6 +148,13 @@ struct rnnt_ctx {
     struct Hyp { std::vector<int> tokens; double log_prob; };
     std::vector<std::vector<Hyp>> beams;
     int use_beam_chain = 1;    // RNNT_BEAM_CHAIN=0: launched extension steps (5 kernels + one host sync per step)
+    // device-resident bookkeeping (rnnt_beam_decode): token lists [2][max_rows][bd_lcap] (ping-pong, grown on demand), per-row
+    // lengths / scores / hashes [2][max_rows], hypotheses per stream and per-stream end frames [max_streams]
+    int* bd_tok = nullptr;
+    size_t bd_tok_cap = 0;
+    int *bd_len = nullptr, *bd_nh = nullptr, *bd_fend = nullptr;
+    double* bd_sc = nullptr;
+    unsigned long long* bd_hs = nullptr;
     // feature front-end (rnnt_fbank): DFT / mel matrices for (fb_rate, fb_nfft) and grow-only work buffers
     float *fb_dft = nullptr, *fb_mel = nullptr, *fb_pad = nullptr, *fb_spec = nullptr, *fb_pow = nullptr;
     size_t fb_pad_cap = 0, fb_spec_cap = 0, fb_pow_cap = 0;

@@ -87,6 +87,7 @@ struct BeamChainP {
     float* pool;                 // [R][slots][512] (h | c); slot 0 = state before the first evaluation
     const int* frame;            // [R] row of encp
     const int* tok_in;           // [R] predictor input token of the first evaluation
+    const int* live;             // [R] or nullptr: rows with live[r] == 0 do nothing (fixed-slot rows of rnnt_beam_decode)
     int* steps; float* blank_lp; float* top_lp; int* top_tok;
     int vocab, blank, k, n_steps, slots;
 };
@@ -98,6 +99,7 @@ __global__ __launch_bounds__(512) void beam_chain(BeamChainP p) {
     __shared__ float lg[512];
     __shared__ int s_ctl[2];
     const int tid = threadIdx.x, r = blockIdx.x;
+    if (p.live && !ldgi(p.live + r)) return;                       // whole workgroup: before the first barrier
     float* pool = p.pool + (long long)r * p.slots * 512;
     if (tid < RNNT_D) { hs[0][tid] = ldg1(pool + tid); cs[tid] = ldg1(pool + RNNT_D + tid); }
     int tok = ldgi(p.tok_in + r);
@@ -193,6 +195,192 @@ __global__ void beam_gather(const float* __restrict__ old_pool, float* __restric
     const float* s = old_pool + ((long long)src_row[r] * slots + src_step[r]) * 512;
     float* d = new_pool + (long long)r * slots * 512;
     for (int i = threadIdx.x; i < 512; i += blockDim.x) d[i] = s[i];
+}
+
+// ------------------------------------------------------------------------------------------------
+// beam_merge_dev: the host half of one encoder frame (beam_merge_stream in api_beam.hip.inc, which stays the oracle) on the
+// device, one workgroup per stream, followed by the state gather of beam_gather -- so that rnnt_beam_decode never returns to the
+// host inside its frame loop.  Rows are fixed slots: hypothesis i of stream b is row b * width + i.
+//   candidates  in the reference's order: per hypothesis, per evaluation st < steps[r], the blank candidate (pool slot st), then
+//               the k top non-blank ones (slot st + 1); the chain continues with the best non-blank while st < n - 1
+//   scores      f64, the host's additions in the host's order: lp + (double)blank_lp, lp + (double)top_lp[j], lp += top_lp[0]
+//   order       std::stable_sort descending: repeated block-wide argmax, ties to the lower candidate index
+//   de-dup      first wins, on the full token sequence: 64-bit running hash first, then length, then every token
+//   truncation  to `beam` survivors
+// A stream past its last frame (f >= fend[b]) is carried over unchanged into the other buffers.
+// ------------------------------------------------------------------------------------------------
+constexpr int BM_MAX_BEAM = 16, BM_MAX_STEPS = 10, BM_MAX_CAND = BM_MAX_BEAM * BM_MAX_STEPS * (BM_MAX_BEAM + 1), BM_NT = 256;
+constexpr unsigned long long BEAM_HASH0 = 0xcbf29ce484222325ull;
+// running hash of a token sequence (FNV-1a over 32-bit tokens): extended one token at a time, host and device alike
+__host__ __device__ inline unsigned long long beam_hash_step(unsigned long long h, int tok) {
+    return (h ^ (unsigned long long)(unsigned)tok) * 0x100000001b3ull;
+}
+
+struct BeamMergeP {
+    const float* pool_in; float* pool_out;      // state pools [rows][slots][512]; pool_in == nullptr: no state gather
+    const int* tk_in; int* tk_out;              // token lists [rows][lcap]
+    const int* len_in; int* len_out;            // [rows]
+    const double* sc_in; double* sc_out;        // [rows]
+    const unsigned long long* hs_in; unsigned long long* hs_out;   // [rows]
+    int* nh;                                    // [B] hypotheses per stream (read, then rewritten)
+    const int* fend;                            // [B] first frame a stream does not have
+    const int* steps; const float* blank_lp; const float* top_lp; const int* top_tok;   // beam_chain's outputs, [rows][n_steps](...)
+    int* tok_next; int* frame_next; int* live;  // [rows] inputs of the next frame's beam_chain
+    int* src_row; int* src_step;                // [rows] pool slot each survivor came from
+    int slots, lcap, n_steps, k, beam, width, blank, f, fstride;
+};
+
+__global__ __launch_bounds__(BM_NT) void beam_merge_dev(BeamMergeP p) {
+    __shared__ double sc[BM_MAX_CAND];
+    __shared__ unsigned char taken[BM_MAX_CAND];
+    __shared__ int h_base[BM_MAX_BEAM + 1], h_len[BM_MAX_BEAM];
+    __shared__ int chain[BM_MAX_BEAM][BM_MAX_STEPS];                 // chain tokens: best non-blank of evaluation st
+    __shared__ unsigned long long h_hash[BM_MAX_BEAM][BM_MAX_STEPS];  // hash of parent + chain[0..st)
+    __shared__ int acc[BM_MAX_BEAM], acc_len[BM_MAX_BEAM];
+    __shared__ unsigned long long acc_hash[BM_MAX_BEAM];
+    __shared__ double red_v[BM_NT / 64];
+    __shared__ int red_i[BM_NT / 64];
+    __shared__ int s_best;
+    const int b = blockIdx.x, tid = threadIdx.x, K1 = p.k + 1, row0 = b * p.width;
+    const int nh = p.nh[b];
+    if (p.f >= p.fend[b]) {                                          // stream finished: carry its rows over unchanged
+        for (int i = 0; i < nh; ++i) {
+            const int r = row0 + i, len = p.len_in[r];
+            for (int q = tid; q < len; q += BM_NT) p.tk_out[(long long)r * p.lcap + q] = p.tk_in[(long long)r * p.lcap + q];
+            if (p.pool_in)
+                for (int e = tid; e < 512; e += BM_NT) p.pool_out[(long long)r * p.slots * 512 + e] = p.pool_in[(long long)r * p.slots * 512 + e];
+            if (tid == 0) { p.len_out[r] = len; p.sc_out[r] = p.sc_in[r]; p.hs_out[r] = p.hs_in[r]; }
+        }
+        if (tid < p.width) p.live[row0 + tid] = 0;
+        return;
+    }
+    if (tid < nh) h_len[tid] = p.len_in[row0 + tid];
+    if (tid == 0) {
+        int c = 0;
+        for (int i = 0; i < nh; ++i) { h_base[i] = c; c += p.steps[row0 + i] * K1; }
+        h_base[nh] = c;
+    }
+    __syncthreads();
+    const int C = h_base[nh];
+    if (tid < nh) {                                                  // one thread per hypothesis: the host's additions, in order
+        const int i = tid, r = row0 + i, n = p.steps[r];
+        double lp = p.sc_in[r];
+        unsigned long long h = p.hs_in[r];
+        for (int st = 0; st < n; ++st) {
+            const long long o = (long long)r * p.n_steps + st;
+            double* c = sc + h_base[i] + st * K1;
+            c[0] = lp + (double)p.blank_lp[o];
+            for (int j = 0; j < p.k; ++j) c[1 + j] = lp + (double)p.top_lp[o * p.k + j];
+            h_hash[i][st] = h;
+            const int t0 = p.top_tok[o * p.k];
+            chain[i][st] = t0;
+            if (st < n - 1) { h = beam_hash_step(h, t0); lp += (double)p.top_lp[o * p.k]; }
+        }
+    }
+    for (int c = tid; c < C; c += BM_NT) taken[c] = 0;
+    __syncthreads();
+    // candidate c -> (hypothesis i, evaluation st, top index j; j = -1: blank)
+    auto decode = [&](int c, int& i, int& st, int& j) {
+        i = 0;
+        while (c >= h_base[i + 1]) ++i;
+        const int q = c - h_base[i];
+        st = q / K1;
+        j = q - st * K1 - 1;
+    };
+    auto top_tok = [&](int i, int st, int j) { return p.top_tok[((long long)(row0 + i) * p.n_steps + st) * p.k + j]; };
+    auto tok_at = [&](int i, int st, int j, int q) {
+        const int pl = h_len[i];
+        if (q < pl) return p.tk_in[(long long)(row0 + i) * p.lcap + q];
+        if (q < pl + st) return chain[i][q - pl];
+        return top_tok(i, st, j);
+    };
+    const int lane = tid & 63, w = tid >> 6;
+    int n_acc = 0;
+    while (n_acc < p.beam) {
+        double bv = -INFINITY;
+        int bi = 0x7fffffff;
+        for (int c = tid; c < C; c += BM_NT)
+            if (!taken[c] && (sc[c] > bv || (sc[c] == bv && c < bi))) { bv = sc[c]; bi = c; }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const double ov = __shfl_xor(bv, off, 64);
+            const int oi = __shfl_xor(bi, off, 64);
+            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+        }
+        if (lane == 0) { red_v[w] = bv; red_i[w] = bi; }
+        __syncthreads();
+        if (tid == 0) {
+            for (int q = 1; q < BM_NT / 64; ++q)
+                if (red_v[q] > bv || (red_v[q] == bv && red_i[q] < bi)) { bv = red_v[q]; bi = red_i[q]; }
+            s_best = bi;
+            if (bi != 0x7fffffff) taken[bi] = 1;
+        }
+        __syncthreads();
+        const int c = s_best;
+        if (c == 0x7fffffff) break;                                  // candidates exhausted
+        int i, st, j;
+        decode(c, i, st, j);
+        const int len = h_len[i] + st + (j >= 0 ? 1 : 0);
+        const unsigned long long hc = j >= 0 ? beam_hash_step(h_hash[i][st], top_tok(i, st, j)) : h_hash[i][st];
+        bool dup = false;
+        for (int a = 0; a < n_acc && !dup; ++a) {
+            if (acc_hash[a] != hc || acc_len[a] != len) continue;    // uniform across the workgroup
+            int i2, st2, j2;
+            decode(acc[a], i2, st2, j2);
+            int diff = 0;
+            for (int q = tid; q < len; q += BM_NT) diff |= tok_at(i, st, j, q) != tok_at(i2, st2, j2, q);
+            dup = !__syncthreads_or(diff);                           // equal hashes of different sequences never merge
+        }
+        if (!dup) {
+            if (tid == 0) { acc[n_acc] = c; acc_len[n_acc] = len; acc_hash[n_acc] = hc; }
+            ++n_acc;
+        }
+        __syncthreads();
+    }
+    // survivors -> rows row0 + a of the other buffers: token list, score, hash, LSTM state, inputs of the next frame
+    for (int a = 0; a < n_acc; ++a) {
+        const int c = acc[a], nr = row0 + a, len = acc_len[a];
+        int i, st, j;
+        decode(c, i, st, j);
+        const int sstep = j >= 0 ? st + 1 : st;
+        for (int q = tid; q < len; q += BM_NT) p.tk_out[(long long)nr * p.lcap + q] = tok_at(i, st, j, q);
+        if (p.pool_in) {
+            const float* src = p.pool_in + ((long long)(row0 + i) * p.slots + sstep) * 512;
+            float* dst = p.pool_out + (long long)nr * p.slots * 512;
+            for (int e = tid; e < 512; e += BM_NT) dst[e] = src[e];
+        }
+        if (tid == 0) {
+            p.len_out[nr] = len;
+            p.sc_out[nr] = sc[c];
+            p.hs_out[nr] = acc_hash[a];
+            p.tok_next[nr] = len > 0 ? tok_at(i, st, j, len - 1) : p.blank;   // online_rnnt_model.py:429
+            p.frame_next[nr] = b * p.fstride + p.f + 1;
+            p.live[nr] = p.f + 1 < p.fend[b] ? 1 : 0;
+            p.src_row[nr] = row0 + i;
+            p.src_step[nr] = sstep;
+        }
+    }
+    if (tid >= n_acc && tid < p.width) p.live[row0 + tid] = 0;
+    if (tid == 0) p.nh[b] = n_acc;
+}
+
+// End of rnnt_beam_decode: fixed-slot row r = b * width + i (i < nh[b]) -> compacted row (hypotheses of streams < b) + i,
+// LSTM state into slot 0 of the other pool, token list / length / score into the other token buffers.
+__global__ __launch_bounds__(128) void beam_compact(const float* __restrict__ pool_in, float* __restrict__ pool_out, int slots,
+                                                    const int* __restrict__ tk_in, int* __restrict__ tk_out, int lcap,
+                                                    const int* __restrict__ len_in, int* __restrict__ len_out,
+                                                    const double* __restrict__ sc_in, double* __restrict__ sc_out,
+                                                    const int* __restrict__ nh, int width) {
+    const int r = blockIdx.x, b = r / width, i = r - b * width;
+    if (i >= nh[b]) return;
+    int dst = i;
+    for (int q = 0; q < b; ++q) dst += nh[q];
+    const float* s = pool_in + (long long)r * slots * 512;
+    float* d = pool_out + (long long)dst * slots * 512;
+    for (int e = threadIdx.x; e < 512; e += blockDim.x) d[e] = s[e];
+    const int len = len_in[r];
+    for (int q = threadIdx.x; q < len; q += blockDim.x) tk_out[(long long)dst * lcap + q] = tk_in[(long long)r * lcap + q];
+    if (threadIdx.x == 0) { len_out[dst] = len; sc_out[dst] = sc_in[r]; }
 }
 
 // log_softmax over the last dimension, in place, one wave per row (joint lattice mode 1).  A row (n <= 512 floats) is read

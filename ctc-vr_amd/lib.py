@@ -39,6 +39,9 @@ SIGNATURES = {
     "rnnt_beam_hyp_count": (c_i32, [c_vp, c_i32, c_i32p]),
     "rnnt_beam_get_hyp": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32p, ctypes.POINTER(ctypes.c_double)]),
     "rnnt_beam_merge_host": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rnnt_beam_decode": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp]),
+    "rnnt_beam_merge_device": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rnnt_encode_ragged": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp]),
     "rnnt_frames_discard": (c_i32, [c_vp, c_vp]),
     "rnnt_predictor_step": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "rnnt_joint": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
@@ -75,7 +78,13 @@ def numerics_id(mode=None):
 
 
 class RnntError(RuntimeError):
-    pass
+    def __init__(self, msg, status=None):
+        super().__init__(msg)
+        self.status = status      # the call's rnnt_status (None: not from a library call)
+
+
+# rnnt_status values of a refusal (call outside its supported range / sequence), as opposed to a HIP failure
+ERR_ARG, ERR_STATE = -1, -5
 
 
 def load(build_if_needed=True):
@@ -139,7 +148,7 @@ class RnntEngine:
 
     def _chk(self, rc, what):
         if rc != 0:
-            raise RnntError(f"{what}: {self.lib.rnnt_last_error(self.ctx).decode()} (status {rc})")
+            raise RnntError(f"{what}: {self.lib.rnnt_last_error(self.ctx).decode()} (status {rc})", rc)
 
     # ---- weights ----------------------------------------------------------------------------
     def load_state_dict(self, sd, stream=None, numerics=None):
@@ -241,6 +250,52 @@ class RnntEngine:
     def beam_advance(self, frame_begin, frame_end, beam_size, stream=None):
         """Native beam search over buffered frames [frame_begin, frame_end) of every stream (bookkeeping in the library)."""
         self._chk(self.lib.rnnt_beam_advance(self.ctx, frame_begin, frame_end, beam_size, stream), "rnnt_beam_advance")
+
+    def beam_decode(self, frame_begin, frame_ends=None, beam_size=4, stream=None):
+        """rnnt_beam_decode: the beam recursion over buffered frames [frame_begin, frame_ends[b]) of every stream, the whole frame
+        loop on the device (frame_ends None: every buffered frame).  Raises RnntError when the call refuses (beam_size > 16,
+        vocab > 512, RNNT_BEAM_CHAIN=0): rnnt_beam_advance is the path for those."""
+        fe = None
+        if frame_ends is not None:
+            fe = np.ascontiguousarray(frame_ends, np.int32)
+            assert fe.size == self.n_streams
+        self._chk(self.lib.rnnt_beam_decode(self.ctx, frame_begin, None if fe is None else _np_ptr(fe), beam_size, stream), "rnnt_beam_decode")
+
+    def encode_ragged(self, fbank_ptr, total_frames, lens, chunk_frames, stream=None):
+        """rnnt_encode_ragged: the encoder half of decode_ragged (no greedy decode); returns encoder frames per stream, which stay
+        buffered for beam_decode(0, frames)."""
+        a = np.ascontiguousarray(lens, np.int32)
+        assert a.size == self.n_streams
+        fo = np.zeros(self.n_streams, np.int32)
+        self._chk(self.lib.rnnt_encode_ragged(self.ctx, fbank_ptr, total_frames, _np_ptr(a), chunk_frames, _np_ptr(fo), stream), "rnnt_encode_ragged")
+        return fo
+
+    def beam_merge_device(self, hyps, steps, blank_lp, top_lp, top_tok, beam_size, stream=None):
+        """rnnt_beam_merge_device for one stream: hyps [(tokens, score)], steps [n], blank_lp [n][n_steps], top_lp / top_tok
+        [n][n_steps][k] -> [(tokens, score, src_row, src_step)] of the survivors (the shape of rnnt_beam_merge_host's results)."""
+        n = len(hyps)
+        hl = np.array([len(t) for t, _ in hyps], np.int32)
+        ht = np.array([x for t, _ in hyps for x in t] or [0], np.int32)
+        hs = np.array([sc for _, sc in hyps], np.float64)
+        st = np.ascontiguousarray(steps, np.int32)
+        bl = np.ascontiguousarray(blank_lp, np.float32)
+        tl = np.ascontiguousarray(top_lp, np.float32)
+        tt = np.ascontiguousarray(top_tok, np.int32)
+        n_steps, k = tl.shape[1], tl.shape[2]
+        cap = max(n, beam_size)
+        out_len = np.zeros(cap, np.int32)
+        out_tok = np.zeros(cap * (int(hl.max(initial=0)) + n_steps) + 1, np.int32)
+        out_sc, out_row, out_step = np.zeros(cap, np.float64), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        m = self.lib.rnnt_beam_merge_device(self.ctx, n, _np_ptr(hl), _np_ptr(ht), _np_ptr(hs), _np_ptr(st), _np_ptr(bl), _np_ptr(tl), _np_ptr(tt),
+                                            n_steps, k, beam_size, _np_ptr(out_len), _np_ptr(out_tok), _np_ptr(out_sc), _np_ptr(out_row),
+                                            _np_ptr(out_step), stream)
+        if m < 0:
+            self._chk(m, "rnnt_beam_merge_device")
+        out, o = [], 0
+        for a in range(m):
+            out.append((out_tok[o:o + out_len[a]].tolist(), float(out_sc[a]), int(out_row[a]), int(out_step[a])))
+            o += out_len[a]
+        return out
 
     def beam_hyps(self, b):
         """[(tokens, log_prob), ...] of stream b in device-row order."""

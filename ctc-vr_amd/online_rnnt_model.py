@@ -11,7 +11,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 import torch
 
-from .lib import RnntEngine, RnntError
+from .lib import ERR_ARG, ERR_STATE, RnntEngine, RnntError
 
 
 def _stream_ptr():
@@ -445,7 +445,24 @@ class StreamingBatch:
         self.offset = 0
         self.beams = None
 
-    def process_chunk_beam(self, chunks: torch.Tensor, beam_size: int = 4):
+    def _beam_frames(self, frames, beam_size, s, device_merge):
+        """The beam recursion over buffered frames [0, frames) of every stream (frames: int, or one end per stream).
+        device_merge: rnnt_beam_decode (frame loop on the device); a refusal (outside its supported range) falls back to
+        rnnt_beam_advance when every stream has the same frames and returns False otherwise.  Returns True when done."""
+        uniform = isinstance(frames, int)
+        if device_merge:
+            try:
+                self.engine.beam_decode(0, None if uniform else [int(f) for f in frames], beam_size, s)
+                return True
+            except RnntError as e:
+                if e.status not in (ERR_ARG, ERR_STATE):
+                    raise
+        if not uniform:
+            return False
+        self.engine.beam_advance(0, frames, beam_size, s)
+        return True
+
+    def process_chunk_beam(self, chunks: torch.Tensor, beam_size: int = 4, device_merge: bool = False):
         """process_single_chunk_beam_search semantics for every stream (online_rnnt_model.py:605-645)."""
         assert chunks.size(0) == self.n and chunks.is_cuda and chunks.dtype == torch.float32 and chunks.is_contiguous()
         if chunks.size(1) < 7:
@@ -458,8 +475,8 @@ class StreamingBatch:
                 self.beams = [[BeamHypothesis([], 0.0)] for _ in range(self.n)]
             for t in range(tq):
                 self.beams = beam_advance_frame(self.engine, t, self.beams, self.blank_id, beam_size, s)
-        else:                                                  # bookkeeping inside the library (rnnt_beam_advance)
-            self.engine.beam_advance(0, tq, beam_size, s)
+        else:                                                  # bookkeeping inside the library (rnnt_beam_advance / rnnt_beam_decode)
+            self._beam_frames(tq, beam_size, s, device_merge)
             self.beams = self._native_beams()
         self.engine.frames_discard(s)
         return self.beams
@@ -467,11 +484,14 @@ class StreamingBatch:
     def _native_beams(self):
         return [[BeamHypothesis(t, lp) for t, lp in self.engine.beam_hyps(b)] for b in range(self.n)]
 
-    def beam_script(self, audios: torch.Tensor, chunk_frames: int, beam_size: int = 4, pipelined: bool = False):
+    def beam_script(self, audios: torch.Tensor, chunk_frames: int, beam_size: int = 4, pipelined: bool = False,
+                    device_merge: bool = False):
         """Beam loop of online_rnnt_decode.py:123-178 over [B,T,80]; returns the final beams per stream.
         pipelined=True: the whole utterance's encoder in one rnnt_encoder_chunks call, then ONE rnnt_beam_advance over
         all frames (same hypotheses: the beam recursion only consumes encoder frames in order); needs
-        max_enc_frames >= the utterance's encoder frames."""
+        max_enc_frames >= the utterance's encoder frames.
+        device_merge=True: rnnt_beam_decode instead of rnnt_beam_advance (the frame loop on the device; bitwise the same
+        hypotheses), rnnt_beam_advance where it refuses."""
         from .layout import chunk_plan
         self.reset()
         if pipelined and not self.python_beam:
@@ -484,13 +504,59 @@ class StreamingBatch:
             s = _stream_ptr()
             frames = self.engine.encoder_chunks(audios.data_ptr(), audios.size(1), [a for a, _ in plan], [b - a for a, b in plan], offs, offs, s, greedy=False)
             self.offset = o
-            self.engine.beam_advance(0, frames, beam_size, s)
+            self._beam_frames(frames, beam_size, s, device_merge)
             self.beams = self._native_beams()
             self.engine.frames_discard(s)
             return self.beams
         for (a, b) in chunk_plan(audios.size(1), chunk_frames):
-            self.process_chunk_beam(audios[:, a:b, :].contiguous(), beam_size)
+            self.process_chunk_beam(audios[:, a:b, :].contiguous(), beam_size, device_merge)
         return self.beams
+
+    def beam_script_ragged(self, audios: torch.Tensor, audio_lens, chunk_frames: int, beam_size: int = 4) -> List[List[BeamHypothesis]]:
+        """Beam loop of online_rnnt_decode.py:123-178 for a PADDED batch of utterances of different lengths (utils/utils.py:29-50;
+        online_rnnt_eval.py:86-94): stream b is beam-decoded over its own audio_lens[b] frames with its own chunk plan (tail-merge
+        rule, < 7-frame skip), so its final beam equals a B = 1 beam_script(pipelined=True) run of that utterance.  Utterances of at
+        least two chunks go through ONE rnnt_encode_ragged call and ONE rnnt_beam_decode call (per-stream frame ends); single-chunk
+        utterances, and everything when the ragged call refuses, run as LENGTH CLASSES (one beam_script(pipelined=True,
+        device_merge=True) per length).  An utterance shorter than 7 frames gives an empty beam (online_rnnt_model.py:615-618)."""
+        assert audios.is_cuda and audios.dtype == torch.float32 and audios.size(0) == self.n
+        lens = [int(v) for v in (audio_lens.tolist() if hasattr(audio_lens, "tolist") else audio_lens)]
+        assert len(lens) == self.n and max(lens) <= audios.size(1) and min(lens) >= 0
+        out: List[Optional[List[BeamHypothesis]]] = [None] * self.n
+        two_chunks = chunk_frames + max(16, chunk_frames)
+        done = set()
+        if audios.is_contiguous() and not self.python_beam:
+            ragged = [b for b in range(self.n) if lens[b] >= two_chunks or lens[b] < 7]
+            big = [lens[b] for b in ragged if lens[b] >= two_chunks]
+            if big and max(big) >= 2 * chunk_frames + max(16, chunk_frames):    # the longest one has at least three chunks
+                self.reset()
+                rset = set(ragged)
+                call_lens = [lens[b] if b in rset else 0 for b in range(self.n)]
+                s = _stream_ptr()
+                frames = self.engine.encode_ragged(audios.data_ptr(), audios.size(1), call_lens, chunk_frames, s)
+                if self._beam_frames(frames.tolist(), beam_size, s, True):
+                    beams = self._native_beams()
+                    for b in ragged:
+                        out[b] = beams[b] if lens[b] >= 7 else []
+                    done = rset
+                self.engine.frames_discard(s)
+                self.beams = None
+        n_all = self.n
+        try:
+            for T_ in sorted({lens[b] for b in range(n_all) if b not in done}, reverse=True):
+                idx = [b for b in range(n_all) if lens[b] == T_ and b not in done]
+                if T_ < 7:                                   # shorter than the conv front-end's receptive field: skipped (:615-618)
+                    for b in idx:
+                        out[b] = []
+                    continue
+                sub = audios[torch.tensor(idx, device=audios.device), :T_, :].contiguous()
+                self.n = len(idx)
+                beams = self.beam_script(sub, chunk_frames, beam_size, pipelined=True, device_merge=True)
+                for b, bm in zip(idx, beams):
+                    out[b] = bm
+        finally:
+            self.n = n_all
+        return out
 
     def process_chunk(self, chunks: torch.Tensor, decode: bool = True):
         """chunks [B,T,80] on the device; process_single_chunk semantics for every stream."""

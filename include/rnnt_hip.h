@@ -141,6 +141,12 @@ int rnnt_frames_consume(rnnt_ctx* ctx, void* stream);
 int rnnt_decode_ragged(rnnt_ctx* ctx, const float* fbank_dev, int32_t total_frames, const int32_t* lens_host, int32_t chunk_frames,
                        int32_t* frames_out, void* stream);
 
+/* The encoder half of rnnt_decode_ragged (same chunk plans, launches and refusals) without the greedy decoder: stream b's
+ * frames_out[b] encoder frames stay in the frame buffer for rnnt_beam_decode(ctx, 0, frames_out, ...).  Needs freshly reset
+ * streams.  Does not synchronise. */
+int rnnt_encode_ragged(rnnt_ctx* ctx, const float* fbank_dev, int32_t total_frames, const int32_t* lens_host, int32_t chunk_frames,
+                       int32_t* frames_out, void* stream);
+
 /* -- beam search: device half of _decode_chunk_beam_search (model/online_rnnt_model.py:419-503) -- */
 /* One encoder frame, all live hypotheses ("rows") of all streams at once.  For every row the library runs the
  * reference's greedy extension chain (<= n_steps evaluations: predictor step, joint, log_softmax, blank
@@ -178,6 +184,23 @@ int rnnt_beam_merge_host(int32_t n_hyp, const int32_t* hyp_len, const int32_t* h
                          const int32_t* steps, const float* blank_lp, const float* top_lp, const int32_t* top_tok,
                          int32_t n_steps, int32_t k, int32_t beam_size, int32_t* out_len, int32_t* out_tokens,
                          double* out_score, int32_t* out_src_row, int32_t* out_src_step);
+/* Device-resident beam search: the same recursion as rnnt_beam_advance with the whole frame loop on the device -- per frame
+ * one extension-chain launch and one merge launch (candidate order, double-precision scores with the host's additions in the
+ * host's order, stable descending order, first-wins de-duplication on the full token sequence, truncation, state gather), no
+ * host copy and no synchronisation inside the loop; one synchronisation at the end.  Stream b covers the buffered frames
+ * [frame_begin, frame_end_host[b]) (frame_end_host NULL: frames_buffered for every stream), so a padded batch of utterances of
+ * different lengths is beam-decoded in one call.  Afterwards rnnt_beam_hyp_count / rnnt_beam_get_hyp / rnnt_beam_get_states
+ * read exactly what rnnt_beam_advance leaves (bitwise the same hypotheses, scores and states): the two calls can be mixed chunk
+ * by chunk.  Supported: beam_size <= 16 (and <= max_beam), vocab_size <= 512, n_steps <= 10; otherwise RNNT_ERR_ARG, and with
+ * RNNT_BEAM_CHAIN=0 RNNT_ERR_STATE: use rnnt_beam_advance then. */
+int rnnt_beam_decode(rnnt_ctx* ctx, int32_t frame_begin, const int32_t* frame_end_host, int32_t beam_size, void* stream);
+/* The merge of rnnt_beam_decode run once on the device for one stream, on flat host inputs: same arguments and results as
+ * rnnt_beam_merge_host (test seam; needs a context created with max_beam >= k; n_hyp, beam_size, k <= 16, n_steps <= 10).
+ * Leaves the context's hypotheses and state pools alone.  Synchronises. */
+int rnnt_beam_merge_device(rnnt_ctx* ctx, int32_t n_hyp, const int32_t* hyp_len, const int32_t* hyp_tokens, const double* hyp_score,
+                           const int32_t* steps, const float* blank_lp, const float* top_lp, const int32_t* top_tok,
+                           int32_t n_steps, int32_t k, int32_t beam_size, int32_t* out_len, int32_t* out_tokens,
+                           double* out_score, int32_t* out_src_row, int32_t* out_src_step, void* stream);
 /* drop all buffered encoder frames (beam path; the greedy path uses rnnt_frames_consume). */
 int rnnt_frames_discard(rnnt_ctx* ctx, void* stream);
 
