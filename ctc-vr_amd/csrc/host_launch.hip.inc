@@ -624,6 +624,11 @@ int greedy_drain(rnnt_ctx* ctx, hipStream_t s, int n_frames, int done_steps) {
 // (3) the give-up bound of a wait is 5 s.  A host mutex around launch..finish (tried in round 3) serialises the two contexts'
 // whole steps, because the decoder is ENQUEUED right behind its encoder: two batches in flight fell from 6.95 to 9.2 ms per batch.
 // tests/test_gpu_parity.py::test_two_contexts_in_flight[64] runs this configuration.
+// greedy_flow (RNNT_COOP=1) holds FLOW_VOCAB rows of W_out per stream group: a larger vocabulary would never see its rows
+// >= FLOW_VOCAB, so such a context keeps greedy_stream
+bool coop_decoder_ok(const rnnt_ctx* ctx) {
+    return ctx->use_coop && ctx->n_streams <= 64 && ctx->cfg.vocab_size <= FLOW_VOCAB;
+}
 bool multi_decoder_ok(const rnnt_ctx* ctx) {
     return ctx->use_multi && !ctx->use_coop && GM_PARTS * ctx->n_streams <= ctx->n_cus && (ctx->cfg.vocab_size + GM_PARTS - 1) / GM_PARTS <= 128;
 }
@@ -656,7 +661,7 @@ int launch_multi_decoder(rnnt_ctx* ctx, hipStream_t s, int n_total, int n_steps_
 
 int launch_persistent_decoder(rnnt_ctx* ctx, hipStream_t s, int n_total, int n_steps_override = 0, const int* nlim = nullptr) {
     if (multi_decoder_ok(ctx)) return launch_multi_decoder(ctx, s, n_total, n_steps_override, nlim);
-    if (ctx->use_coop && ctx->n_streams <= 64 && !nlim && !n_steps_override) {
+    if (coop_decoder_ok(ctx) && !nlim && !n_steps_override) {
         // cooperative decoder: 4 x 16 resident workgroups, weights stationary in LDS, tagged-word exchanges
         FlowP c;
         memset(&c, 0, sizeof(c));
@@ -696,7 +701,7 @@ int launch_persistent_decoder(rnnt_ctx* ctx, hipStream_t s, int n_total, int n_s
 }
 
 int init_decoder_ctrl(rnnt_ctx* ctx, hipStream_t s, int frames_ready) {
-    if (ctx->use_coop && ctx->n_streams <= 64)   // tags restart at 1 every launch: no word of an earlier launch may survive
+    if (coop_decoder_ok(ctx))   // tags restart at 1 every launch: no word of an earlier launch may survive
         HIPCHK(hipMemsetAsync(ctx->flow_buf, 0, (size_t)FLOW_WORDS * sizeof(unsigned long long), s));
     hipLaunchKernelGGL(fill_i32, dim3(1), dim3(64), 0, s, ctx->dec_ctrl, 0, 32LL);
     LAUNCHCHK("fill_i32");
@@ -739,7 +744,7 @@ int finish_persistent_decoder(rnnt_ctx* ctx, hipStream_t s) {
                         "us per symbol: W_hh %.2f, cell+W_c %.2f, wait X1 %.2f\n",
                 t[8], t[9], t[0] / ev / 100.0, t[6] / ev / 100.0, t[4] / ev / 100.0, t[5] / ev / 100.0, t[1] / sy / 100.0, t[2] / sy / 100.0, t[3] / sy / 100.0);
     }
-    if (getenv("RNNT_COOP_DBG") && ctx->use_coop && ctx->n_streams <= 64) {
+    if (getenv("RNNT_COOP_DBG") && coop_decoder_ok(ctx)) {
         long long t[16];
         (void)hipMemcpy(t, ctx->flow_buf + FLOW_WORDS, sizeof(t), hipMemcpyDeviceToHost);
         const double ev = t[11] > 0 ? (double)t[11] : 1.0;

@@ -356,6 +356,7 @@ __device__ __forceinline__ void st_tag(unsigned long long* p, unsigned payload, 
 #define FLOW_CG 16
 #define FLOW_LD 260
 #define FLOW_NONE 0x7fffffff
+#define FLOW_VOCAB (FLOW_CG * 26)   // W_out rows held by a stream group (26 per column group): larger vocabularies take another decoder
 
 // wait until all NW words of this thread carry `tag`; false = abort (timeout or another workgroup gave up)
 template <int NW>

@@ -93,10 +93,11 @@ def test_predictor_and_joint_step_api(seed, models, numerics):
         assert np.array_equal(out.argmax(-1).cpu().numpy(), g[key].argmax(-1))
 
 
-@pytest.mark.parametrize("shape", [(1, 1, 1), (3, 37, 11), (5, 64, 28), (2, 129, 3)])
+@pytest.mark.parametrize("shape", [(1, 1, 1), (3, 37, 11), (5, 64, 28), (2, 129, 3), (8, 160, 28)])
 def test_joint_lattice_shapes(shape, models, numerics, np_state_dict):
     """rnnt_joint in lattice form (joint.py:48-69, online_rnnt_model.py:243,446-447) on row counts that are not multiples of the
-    kernel's 64-row tile, through the persistent row-tile queue: logits and log-softmax within LOGIT_TOL of the oracle, same
+    kernel's 64-row tile; (8, 160, 28) is 560 tiles, more than the persistent grid's 2 workgroups per CU on 256 CUs, so workgroups
+    take further tiles from the row-tile queue (test_decode_edges.py sizes such lattices by the CU count): logits and log-softmax within LOGIT_TOL of the oracle, same
     argmax, and two calls bit-identical (the queue hands tiles to workgroups in a different order every launch)."""
     from oracle import rnnt_oracle as O
     B, Tn, U = shape
