@@ -33,6 +33,8 @@ int rnnt_create(const rnnt_config* cfg, rnnt_ctx** out) {
     if (const char* e_ = getenv("RNNT_LM_SIDE")) ctx->lm_side = atoi(e_);
     if (const char* e_ = getenv("RNNT_LM_QKV_TAIL")) ctx->lm_qkv_tail = atoi(e_);
     if (const char* e_ = getenv("RNNT_LM_OUT_CHAIN")) ctx->lm_out_chain = atoi(e_);
+    if (const char* e_ = getenv("RNNT_ATTN_BF")) ctx->attn_bf = atoi(e_);
+    if (const char* e_ = getenv("RNNT_ATTN_RESIDENT")) ctx->attn_resident = atoi(e_);
     if (const char* se = getenv("RNNT_WF_SUB_ASYNC")) ctx->wf_sub_async = (se[0] == '0') ? 0 : 1;
     const int B = cfg->max_streams;
     ctx->tmax = sub_len(cfg->max_chunk_frames);
@@ -106,7 +108,7 @@ void rnnt_destroy(rnnt_ctx* ctx) {
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
     for (float* q : {ctx->fb_dft, ctx->fb_mel, ctx->fb_pad, ctx->fb_spec, ctx->fb_pow}) if (q) (void)hipFree(q);
     void* wf[] = {ctx->wf_x, ctx->wf_h, ctx->wf_q, ctx->wf_a, ctx->wf_d, ctx->wf_y1, ctx->wf_y2, ctx->wf_starts, ctx->wf_gtab, ctx->wf_atab,
-                  ctx->wf_dtab, ctx->wf_ltab, ctx->lm_x, ctx->lm_h, ctx->lm_q, ctx->lm_a, ctx->lm_d, ctx->lm_g, ctx->lm_y1, ctx->lm_y2, ctx->lm_y1b, ctx->lm_y2b, ctx->lm_blocks,
+                  ctx->wf_dtab, ctx->wf_ltab, ctx->lm_x, ctx->lm_h, ctx->lm_q, ctx->lm_a, ctx->lm_d, ctx->lm_g, ctx->lm_y1, ctx->lm_y2, ctx->lm_y1b, ctx->lm_y2b, ctx->lm_blocks, ctx->lm_rhdr, ctx->lm_rrows,
                   ctx->rg_fb, ctx->rg_xt, ctx->rg_ent, ctx->bd_tok, ctx->bd_len, ctx->bd_sc, ctx->bd_hs, ctx->bd_nh, ctx->bd_fend};
     for (void* q : wf)
         if (q) (void)hipFree(q);

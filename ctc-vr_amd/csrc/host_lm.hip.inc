@@ -42,6 +42,18 @@ struct RaggedPlan {
     int F = 0;                        // rows per stream = max(frames)
 };
 
+int lm_res_upload(rnnt_ctx* ctx, hipStream_t s, const std::vector<std::vector<LmRow>>& tabs) {
+    ctx->lm_res_ok = 0;
+    if (!lm_res_plan(tabs, ctx->lm_rhdr_host, ctx->lm_rrows_host, ctx->lm_res_stride)) return RNNT_OK;
+    int rc;
+    if ((rc = grow(ctx, &ctx->lm_rhdr, &ctx->lm_rhdr_cap, ctx->lm_rhdr_host.size()))) return rc;
+    if ((rc = grow(ctx, &ctx->lm_rrows, &ctx->lm_rrows_cap, ctx->lm_rrows_host.size()))) return rc;
+    HIPCHK(hipMemcpyAsync(ctx->lm_rhdr, ctx->lm_rhdr_host.data(), ctx->lm_rhdr_host.size() * sizeof(LmResHdr), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->lm_rrows, ctx->lm_rrows_host.data(), ctx->lm_rrows_host.size() * sizeof(LmRow), hipMemcpyHostToDevice, s));
+    ctx->lm_res_ok = 1;
+    return RNNT_OK;
+}
+
 // ---- A-stationary kernels (rnnt_gemm_as.hip.h), split-operand modes ------------------------------------------------------------
 constexpr int AS_MT = 3;     // 48 rows per workgroup: 251 workgroups at M = 12032 (64 streams x 188 frames), one per CU
 template <int NUM>
@@ -282,6 +294,9 @@ int encoder_chunks_lm(rnnt_ctx* ctx, hipStream_t s, const float* fbank_dev, int 
         if ((rc = grow(ctx, &ctx->lm_blocks, &ctx->lm_blocks_cap, flat.size()))) return rc;
         HIPCHK(hipMemcpyAsync(ctx->lm_blocks, flat.data(), flat.size() * sizeof(LmBlock), hipMemcpyHostToDevice, s));
         ctx->lm_key.clear();                                        // never equal to a uniform call's key
+        std::vector<std::vector<LmRow>> tabs(B);
+        for (int b = 0; b < B; ++b) tabs[b] = lm_rows_of(per[b].data(), per[b].size());
+        if ((rc = lm_res_upload(ctx, s, tabs))) return rc;
     } else if (plan_key != ctx->lm_key) {
         std::vector<LmBlock>& blocks = ctx->lm_blocks_host;
         blocks.clear();
@@ -309,11 +324,18 @@ int encoder_chunks_lm(rnnt_ctx* ctx, hipStream_t s, const float* fbank_dev, int 
         flush();
         if ((rc = grow(ctx, &ctx->lm_blocks, &ctx->lm_blocks_cap, blocks.size()))) return rc;
         HIPCHK(hipMemcpyAsync(ctx->lm_blocks, blocks.data(), blocks.size() * sizeof(LmBlock), hipMemcpyHostToDevice, s));
+        if ((rc = lm_res_upload(ctx, s, {lm_rows_of(blocks.data(), blocks.size())}))) return rc;
         ctx->lm_key = plan_key;
     }
     const int n_blocks = rg ? rg_blocks : (int)ctx->lm_blocks_host.size();
     if ((rc = ensure_dyn_lds(ctx, reinterpret_cast<const void*>(&rel_attention_lm_mfma), LM2_LDS))) return rc;
-    if (ctx->numerics == RNNT_NUM_BF16X3) rc = ensure_dyn_lds(ctx, reinterpret_cast<const void*>(&rel_attention_lm_bf<2, false>), LMB_LDS);
+    // rel_attention_lm_res when every table fits its plan (split-operand modes), else rel_attention_lm_bf
+    const bool attn_res = ctx->lm_res_ok && ctx->attn_resident && ctx->attn_bf && ctx->numerics != RNNT_NUM_F32;
+    if (attn_res) {
+        if (ctx->numerics == RNNT_NUM_BF16X3) rc = ensure_dyn_lds(ctx, reinterpret_cast<const void*>(&rel_attention_lm_res<2, false>), LMR_LDS);
+        else if (ctx->numerics == RNNT_NUM_F16X3) rc = ensure_dyn_lds(ctx, reinterpret_cast<const void*>(&rel_attention_lm_res<2, true>), LMR_LDS);
+        else rc = ensure_dyn_lds(ctx, reinterpret_cast<const void*>(&rel_attention_lm_res<1, false>), LMR_LDS);
+    } else if (ctx->numerics == RNNT_NUM_BF16X3) rc = ensure_dyn_lds(ctx, reinterpret_cast<const void*>(&rel_attention_lm_bf<2, false>), LMB_LDS);
     else if (ctx->numerics == RNNT_NUM_F16X3) rc = ensure_dyn_lds(ctx, reinterpret_cast<const void*>(&rel_attention_lm_bf<2, true>), LMB_LDS);
     else if (ctx->numerics == RNNT_NUM_BF16) rc = ensure_dyn_lds(ctx, reinterpret_cast<const void*>(&rel_attention_lm_bf<1, false>), LMB_LDS);
     if (rc) return rc;
@@ -399,9 +421,14 @@ int encoder_chunks_lm(rnnt_ctx* ctx, hipStream_t s, const float* fbank_dev, int 
         {
             ProfScope prof(ctx, s, TAG_ATTN);
             LmAttnP a{ctx->lm_q, kc, vc, w.ptab, w.pu, w.pv, ctx->lm_a, ctx->lm_blocks, F, (long long)ctx->tcap, klen_dev, rg ? 1 : 0};
-            static const int attn_bf = getenv("RNNT_ATTN_BF") ? atoi(getenv("RNNT_ATTN_BF")) : 1;   // 0: exact-f32 MFMA attention in every mode
             const dim3 ag(B * RNNT_H, n_blocks);
-            if (ctx->numerics == RNNT_NUM_F32 || !attn_bf) hipLaunchKernelGGL(rel_attention_lm_mfma, ag, dim3(256), LM2_LDS, s, a);
+            if (attn_res) {
+                const LmResP r{ctx->lm_q, kc, vc, w.ptab, w.pu, w.pv, ctx->lm_a, ctx->lm_rhdr, ctx->lm_rrows, ctx->lm_res_stride, F, (long long)ctx->tcap,
+                               klen_dev, rg ? 1 : 0};
+                if (ctx->numerics == RNNT_NUM_BF16X3) hipLaunchKernelGGL((rel_attention_lm_res<2, false>), dim3(B * RNNT_H), dim3(64 * LMR_NW), LMR_LDS, s, r);
+                else if (ctx->numerics == RNNT_NUM_F16X3) hipLaunchKernelGGL((rel_attention_lm_res<2, true>), dim3(B * RNNT_H), dim3(64 * LMR_NW), LMR_LDS, s, r);
+                else hipLaunchKernelGGL((rel_attention_lm_res<1, false>), dim3(B * RNNT_H), dim3(64 * LMR_NW), LMR_LDS, s, r);
+            } else if (ctx->numerics == RNNT_NUM_F32 || !ctx->attn_bf) hipLaunchKernelGGL(rel_attention_lm_mfma, ag, dim3(256), LM2_LDS, s, a);
             else if (ctx->numerics == RNNT_NUM_BF16X3) hipLaunchKernelGGL((rel_attention_lm_bf<2, false>), ag, dim3(256), LMB_LDS, s, a);
             else if (ctx->numerics == RNNT_NUM_F16X3) hipLaunchKernelGGL((rel_attention_lm_bf<2, true>), ag, dim3(256), LMB_LDS, s, a);
             else hipLaunchKernelGGL((rel_attention_lm_bf<1, false>), ag, dim3(256), LMB_LDS, s, a);

@@ -132,6 +132,8 @@ struct rnnt_ctx {
     int lm_ffn_merge = 0;                      // RNNT_LM_FFN_MERGE=1: one launch per layer boundary (better alone, worse with two batches in flight)
     int lm_qkv_tail = 1, lm_out_chain = 1;     // RNNT_LM_QKV_TAIL=0 / RNNT_LM_OUT_CHAIN=0: q/k/v and pointwise_conv1 as launches of their own
     int lm_side = 1;                           // RNNT_LM_SIDE=0: the tail chunk class's subsampling in line instead of on the side stream
+    int attn_bf = 1;                           // RNNT_ATTN_BF=0: exact-f32 MFMA attention (rel_attention_lm_mfma) in every mode
+    int attn_resident = 1;                     // RNNT_ATTN_RESIDENT=0: always the tiled rel_attention_lm_bf, never rel_attention_lm_res
     float *lm_x = nullptr, *lm_h = nullptr, *lm_q = nullptr, *lm_a = nullptr, *lm_d = nullptr, *lm_g = nullptr, *lm_y1 = nullptr, *lm_y2 = nullptr;
     size_t lm_y1_cap = 0, lm_y2_cap = 0, lm_blocks_cap = 0;
     float *lm_y1b = nullptr, *lm_y2b = nullptr;      // slabs of the tail chunk class (subsampled on sub_stream beside the main class)
@@ -144,6 +146,13 @@ struct rnnt_ctx {
     LmBlock* lm_blocks = nullptr;
     std::vector<LmBlock> lm_blocks_host;
     std::vector<int> lm_key;
+    // rel_attention_lm_res tables (host_lm.hip.inc: lm_res_plan), rebuilt with the block table
+    LmResHdr* lm_rhdr = nullptr;
+    LmRow* lm_rrows = nullptr;
+    size_t lm_rhdr_cap = 0, lm_rrows_cap = 0;
+    std::vector<LmResHdr> lm_rhdr_host;
+    std::vector<LmRow> lm_rrows_host;
+    int lm_res_ok = 0, lm_res_stride = 0;
     // native beam bookkeeping (rnnt_beam_advance): per stream, hypotheses in device-row order
     struct Hyp { std::vector<int> tokens; double log_prob; };
     std::vector<std::vector<Hyp>> beams;

@@ -8,6 +8,11 @@
 // the keys the chunk-by-chunk loop would have cached for it, at that chunk's positional window, and (2) the causal depthwise
 // conv, which is simply a causal conv over the utterance with the stream's 30-row left context.
 #pragma once
+#include <algorithm>
+#include <climits>
+#include <cstring>
+#include <utility>
+#include <vector>
 
 // ------------------------------------------------------------------------------------------------
 // Attention of ALL chunks of a call (RelPositionMultiHeadedAttention scores / softmax / PV, attention.py:400-418,170-177).
@@ -597,5 +602,356 @@ __global__ __launch_bounds__(256) void rel_attention_lm_bf(LmAttnP P) {
 #pragma unroll
         for (int dd = 0; dd < 2; ++dd)
             stg4(P.out + m * RNNT_D + h * RNNT_DK + 16 * (2 * hf + dd) + 4 * kq, make_float4(o[dd][0] * li, o[dd][1] * li, o[dd][2] * li, o[dd][3] * li));
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// rel_attention_lm_res<NSPLIT,F16>: rel_attention_lm_bf with every key of the (stream, head) resident in LDS.  rel_attention_lm_bf
+// gives each 32-row block its own workgroup, so a stream-head's few 64-key tiles are loaded, split and staged once per BLOCK (about
+// four times per launch for a 10 s batch), and every tile pays three workgroup barriers between its phases.  Here ONE workgroup
+// takes a (stream, head): its K rows and transposed V rows are staged once, as split 16-bit planes in 32-key units (K: the
+// lmb_off row image, one row per key; V^T: lmb_off images [64 d][64 keys], two units per image, unit u = half u & 1 of image
+// u >> 1), and after that single barrier every wave runs a FlashAttention-2 loop of its own over its 16-row query tiles:
+//   S = (Q + u) K^T   on the accumulators (swapped operands: a lane holds query row i and keys 16 kt + 4 kq + 0..3)
+//   G = (Q + v) P^T   over the 64 + LMR_PEXT positional rows the tile's live rows address, operands streamed from L2 (the table is
+//                     shared by every stream) and split in registers, to the wave's LDS slab; read back shifted by pshift - pmin
+//   online softmax in f32 (v_exp_f32, as rel_attention_lm_bf), row max / sum over the four lane groups of a row
+//   P                 to the same slab (the wave's own G reads of the tile are complete: P depends on them), read back in PV
+//                     operand layout and split there;  O = alpha O + P V on the accumulators;  out = O / l, 16-byte stores
+// The keys are tiled in 64 from the start of each SEGMENT (a maximal run of key rows some row's window covers: chunk 0's parked rows
+// are a segment of their own), which for the uniform plans is the block origin amin of rel_attention_lm_bf, so a row's online-
+// softmax rescale steps are the same; only the order of the f32 row reductions differs (~1 ulp).  Query tiles are dealt to the
+// waves heaviest first, in snake order (later tiles see more keys).  The host (lm_res_plan) selects this kernel only when every
+// table's keys fit LMR_UNITS units and every query tile's pshift spread per segment fits LMR_PEXT; otherwise rel_attention_lm_bf.
+// grid = B*H, block = 64 LMR_NW, dynamic LDS = LMR_LDS bytes.
+// ------------------------------------------------------------------------------------------------
+#define LMR_NW 8
+#define LMR_UNITS 7
+#define LMR_SEGS 4
+#define LMR_PEXT 12
+#define LMR_GLD 76                                       // slab row (floats): 64 keys + LMR_PEXT; 76 = 12 mod 32 -> conflict-free 16-byte rows
+#define LMR_KBYTES (LMR_UNITS * 32 * 128)
+#define LMR_VBYTES (((LMR_UNITS + 1) / 2) * 8192)
+#define LMR_LDS (2 * LMR_KBYTES + 2 * LMR_VBYTES + LMR_NW * 16 * LMR_GLD * 4)
+struct LmResHdr {
+    int n_rows, nseg;
+    int lo[LMR_SEGS], hi[LMR_SEGS], u0[LMR_SEGS];         // segment s: key rows [lo, hi), stored from unit u0 on
+    int ukey[LMR_UNITS], ucnt[LMR_UNITS];                 // unit u: first key row, valid keys (0: unused)
+};
+struct LmResP {
+    const float* q;
+    const float* kc;
+    const float* vc;
+    const float* ptab;
+    const float* bias_u;
+    const float* bias_v;
+    float* out;
+    const LmResHdr* hdr;  // [1] or [B] (per_stream)
+    const LmRow* rows;    // [1 or B][row_stride]: the table's query rows in frame order
+    int row_stride;
+    int F;
+    long long kv_stride;
+    const int* klen;
+    int per_stream;
+};
+// (host) the query rows of n blocks, in block order
+inline std::vector<LmRow> lm_rows_of(const LmBlock* blk, size_t n) {
+    std::vector<LmRow> rows;
+    for (size_t j = 0; j < n; ++j)
+        for (int k = 0; k < blk[j].n_rows; ++k) rows.push_back(blk[j].r[k]);
+    return rows;
+}
+
+// rel_attention_lm_res tables: per block table (one, or one per stream), its query rows in frame order, the key SEGMENTS (maximal
+// runs of cache rows some row's window covers; chunk 0's parked rows form one of their own) and their 32-key units.  false: some
+// table does not fit the kernel's plan -- more than LMR_UNITS units or LMR_SEGS segments (30 s utterances, the full-context pass),
+// or a 16-row query tile whose rows in one segment spread their pshift by more than LMR_PEXT -- and rel_attention_lm_bf runs.
+inline bool lm_res_plan(const std::vector<std::vector<LmRow>>& tabs, std::vector<LmResHdr>& hdr, std::vector<LmRow>& flat, int& stride) {
+    stride = 1;
+    for (const auto& t : tabs) stride = std::max(stride, (int)t.size());
+    hdr.assign(tabs.size(), LmResHdr{});
+    flat.assign(tabs.size() * (size_t)stride, LmRow{-1, 0, 0, 0});
+    for (size_t k = 0; k < tabs.size(); ++k) {
+        const std::vector<LmRow>& rw = tabs[k];
+        LmResHdr& h = hdr[k];
+        memset(&h, 0, sizeof(h));
+        h.n_rows = (int)rw.size();
+        std::vector<std::pair<int, int>> w, seg;
+        for (const LmRow& r : rw)
+            if (r.ke > r.ks) w.push_back({r.ks, r.ke});
+        std::sort(w.begin(), w.end());
+        for (const auto& x : w) {
+            if (!seg.empty() && x.first <= seg.back().second) seg.back().second = std::max(seg.back().second, x.second);
+            else seg.push_back(x);
+        }
+        if ((int)seg.size() > LMR_SEGS) return false;
+        int nu = 0;
+        for (size_t sg = 0; sg < seg.size(); ++sg) {
+            h.lo[sg] = seg[sg].first; h.hi[sg] = seg[sg].second; h.u0[sg] = nu;
+            for (int a = seg[sg].first; a < seg[sg].second; a += 32) {
+                if (nu >= LMR_UNITS) return false;
+                h.ukey[nu] = a; h.ucnt[nu] = std::min(32, seg[sg].second - a);
+                ++nu;
+            }
+        }
+        h.nseg = (int)seg.size();
+        for (size_t q0 = 0; q0 < rw.size(); q0 += 16)
+            for (const auto& sgm : seg) {
+                int pmn = INT_MAX, pmx = INT_MIN;
+                for (size_t r = q0; r < std::min(rw.size(), q0 + 16); ++r)
+                    if (rw[r].ke > rw[r].ks && rw[r].ks >= sgm.first && rw[r].ks < sgm.second) {
+                        pmn = std::min(pmn, rw[r].pshift); pmx = std::max(pmx, rw[r].pshift);
+                    }
+                if (pmn <= pmx && pmx - pmn > LMR_PEXT) return false;
+            }
+        std::copy(rw.begin(), rw.end(), flat.begin() + k * (size_t)stride);
+    }
+    return true;
+}
+// ABL (tools/attn_check.hip only; 0 in the library): ablations for timing, results meaningless -- bit 1 no K/V loads (zeros staged),
+// bit 2 no positional term (no loads, no G MFMAs), bit 4 no online softmax (scores used as probabilities, no reductions / exp)
+template <int NSPLIT, bool F16, int ABL = 0>
+__global__ __launch_bounds__(64 * LMR_NW) void rel_attention_lm_res(LmResP P) {
+    constexpr bool LO = NSPLIT == 2;
+    extern __shared__ __attribute__((aligned(16))) unsigned char lmr_smem[];
+    unsigned char* Kh = lmr_smem;                        // [32 LMR_UNITS keys][64 d]
+    unsigned char* Kl = Kh + LMR_KBYTES;
+    unsigned char* Vh = Kl + LMR_KBYTES;                 // [units / 2][64 d][64 keys]
+    unsigned char* Vl = Vh + LMR_VBYTES;
+    const int b = blockIdx.x / RNNT_H, h = blockIdx.x % RNNT_H;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int i = lane & 15, kq = lane >> 4;
+    float* slab = reinterpret_cast<float*>(Vl + LMR_VBYTES) + wave * 16 * LMR_GLD;
+    const LmResHdr* __restrict__ hd = P.hdr + (P.per_stream ? b : 0);
+    const LmRow* __restrict__ rows = P.rows + (P.per_stream ? (long long)b * P.row_stride : 0);
+    const float* kbase = P.kc + (long long)b * P.kv_stride * RNNT_D + h * RNNT_DK;
+    const float* vbase = P.vc + (long long)b * P.kv_stride * RNNT_D + h * RNNT_DK;
+    const float* pbase = P.ptab + h * RNNT_DK;
+    // ---- stage every unit once: K rows (8-float chunk c8 of key r of unit u), V^T (4-float piece c4 of the keys 4 kg .. + 3) ----------
+    {
+        constexpr int NK = (LMR_UNITS * 256 + 64 * LMR_NW - 1) / (64 * LMR_NW), NV = (LMR_UNITS * 128 + 64 * LMR_NW - 1) / (64 * LMR_NW);
+        float4 rk[NK][2], rv[NV][4];
+#pragma unroll
+        for (int j = 0; j < NK; ++j) {
+            const int e = tid + 64 * LMR_NW * j, u = e >> 8, r = (e >> 3) & 31, c8 = e & 7;
+            rk[j][0] = make_float4(0.f, 0.f, 0.f, 0.f); rk[j][1] = rk[j][0];
+            if (!(ABL & 1) && u < LMR_UNITS && r < ldgi(&hd->ucnt[u])) {
+                const float* p_ = kbase + (long long)(ldgi(&hd->ukey[u]) + r) * RNNT_D + 8 * c8;
+                rk[j][0] = ldg4(p_); rk[j][1] = ldg4(p_ + 4);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int e = tid + 64 * LMR_NW * j, u = e >> 7, kg = (e >> 4) & 7, c4 = e & 15;
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj) {
+                rv[j][jj] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (!(ABL & 1) && u < LMR_UNITS && 4 * kg + jj < ldgi(&hd->ucnt[u])) rv[j][jj] = ldg4(vbase + (long long)(ldgi(&hd->ukey[u]) + 4 * kg + jj) * RNNT_D + 4 * c4);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NK; ++j) {
+            const int e = tid + 64 * LMR_NW * j, u = e >> 8, r = (e >> 3) & 31, c8 = e & 7;
+            if (u < LMR_UNITS) {
+                uint4 hv, lv;
+                split8_16<F16, LO>(rk[j][0], rk[j][1], hv, lv);
+                *reinterpret_cast<uint4*>(Kh + lmb_off(32 * u + r, c8)) = hv;
+                if constexpr (LO) *reinterpret_cast<uint4*>(Kl + lmb_off(32 * u + r, c8)) = lv;
+            }
+        }
+        auto put4 = [&](int off, float x0, float x1, float x2, float x3) {   // four keys' values -> 8 bytes per plane
+            float r0, r1, r2, r3, d0, d1;
+            uint2 hv, lv;
+            hv.x = pack2_16<F16>(x0, x1, r0, r1);
+            hv.y = pack2_16<F16>(x2, x3, r2, r3);
+            *reinterpret_cast<uint2*>(Vh + off) = hv;
+            if constexpr (LO) {
+                lv.x = pack2_16<F16>(r0, r1, d0, d1);
+                lv.y = pack2_16<F16>(r2, r3, d0, d1);
+                *reinterpret_cast<uint2*>(Vl + off) = lv;
+            }
+        };
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int e = tid + 64 * LMR_NW * j, u = e >> 7, kg = (e >> 4) & 7, c4 = e & 15;
+            if (u < LMR_UNITS) {   // row d = 4 c4 + dd of image u >> 1; keys 4 kg .. + 3 of the unit = half (kg & 1) of chunk 4 (u & 1) + (kg >> 1)
+                const int base = (u >> 1) * 8192, ch = 4 * (u & 1) + (kg >> 1), vo = (kg & 1) * 8;
+                put4(base + lmb_off(4 * c4 + 0, ch) + vo, rv[j][0].x, rv[j][1].x, rv[j][2].x, rv[j][3].x);
+                put4(base + lmb_off(4 * c4 + 1, ch) + vo, rv[j][0].y, rv[j][1].y, rv[j][2].y, rv[j][3].y);
+                put4(base + lmb_off(4 * c4 + 2, ch) + vo, rv[j][0].z, rv[j][1].z, rv[j][2].z, rv[j][3].z);
+                put4(base + lmb_off(4 * c4 + 3, ch) + vo, rv[j][0].w, rv[j][1].w, rv[j][2].w, rv[j][3].w);
+            }
+        }
+    }
+    __syncthreads();                                                // the only workgroup barrier
+    const int n_rows = ldgi(&hd->n_rows), nseg = ldgi(&hd->nseg);
+    const int nq = (n_rows + 15) >> 4;
+    for (int rnd = 0;; ++rnd) {
+        const int pos = rnd * LMR_NW + ((rnd & 1) ? LMR_NW - 1 - wave : wave);
+        if (pos >= nq) break;
+        const int row = 16 * (nq - 1 - pos) + i;                     // this lane's query row
+        int f = -1, ks = 0, ke = 0, psh = 0;
+        if (row < n_rows) {
+            f = ldgi(&rows[row].f);
+            if (f >= 0) {
+                ks = ldgi(&rows[row].ks); ke = ldgi(&rows[row].ke); psh = ldgi(&rows[row].pshift);
+                if (P.klen) ke = min(ke, ks + ldgi(P.klen + b));
+            }
+        }
+        // (Q + u), (Q + v) of row `row`, d = 32 s + 8 kq .. + 8 of k-step s, as operand planes
+        uint4 quh[2], qul[2], qvh[2], qvl[2];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const int d = 32 * s + 8 * kq;
+            float4 q0 = make_float4(0.f, 0.f, 0.f, 0.f), q1 = q0;
+            if (f >= 0) {
+                const float* qp = P.q + ((long long)b * P.F + f) * RNNT_D + h * RNNT_DK + d;
+                q0 = ldg4(qp); q1 = ldg4(qp + 4);
+            }
+            const float4 u0 = ldg4(P.bias_u + h * RNNT_DK + d), u1 = ldg4(P.bias_u + h * RNNT_DK + d + 4);
+            const float4 v0 = ldg4(P.bias_v + h * RNNT_DK + d), v1 = ldg4(P.bias_v + h * RNNT_DK + d + 4);
+            split8_16<F16, LO>(make_float4(q0.x + u0.x, q0.y + u0.y, q0.z + u0.z, q0.w + u0.w), make_float4(q1.x + u1.x, q1.y + u1.y, q1.z + u1.z, q1.w + u1.w), quh[s], qul[s]);
+            split8_16<F16, LO>(make_float4(q0.x + v0.x, q0.y + v0.y, q0.z + v0.z, q0.w + v0.w), make_float4(q1.x + v1.x, q1.y + v1.y, q1.z + v1.z, q1.w + v1.w), qvh[s], qvl[s]);
+        }
+        f32x4_ o[4];
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) o[dt] = (f32x4_){0.f, 0.f, 0.f, 0.f};
+        float mrun = -INFINITY, lrun = 0.f;
+        for (int sg = 0; sg < nseg; ++sg) {
+            const int lo = ldgi(&hd->lo[sg]), hi = ldgi(&hd->hi[sg]), ub = ldgi(&hd->u0[sg]);
+            for (int a0 = lo; a0 < hi; a0 += 64) {
+                // live: the row's window lies in THIS segment (chunk 0's parked rows may sit within 64 keys of another segment's last
+                // tile) and overlaps the tile; then at least one of its keys is in the tile and staged (ke <= hi)
+                const bool live = f >= 0 && ks >= lo && ks < hi && ke > ks && ks < a0 + 64 && ke > a0;
+                if (!__any(live)) continue;                          // (wave-uniform)
+                __builtin_amdgcn_wave_barrier();                     // the previous tile's P reads precede this tile's G writes
+                const bool two = a0 + 32 < hi;                       // the tile's second 32-key unit exists
+                const int ut = ub + ((a0 - lo) >> 6) * 2;            // first unit of the tile
+                int pm = live ? psh : 0x7fffffff;                    // smallest pshift of the tile's live rows
+#pragma unroll
+                for (int o_ = 1; o_ < 16; o_ <<= 1) pm = min(pm, __shfl_xor(pm, o_, 64));
+                // positional operands: rows a0 + pm + 16 gt + i, d = 32 s + 8 kq .. + 8 (issued first: their L2 latency hides under S)
+                float4 pr[5][2][2];
+#pragma unroll
+                for (int gt = 0; gt < 5; ++gt)
+#pragma unroll
+                    for (int s = 0; s < 2; ++s) {
+                        const int prow = a0 + pm + 16 * gt + i;
+                        pr[gt][s][0] = make_float4(0.f, 0.f, 0.f, 0.f); pr[gt][s][1] = pr[gt][s][0];
+                        if (!(ABL & 2) && (gt < 3 || two) && prow >= 0 && prow < RNNT_PE_LEN) {
+                            const float* p_ = pbase + (long long)prow * RNNT_D + 32 * s + 8 * kq;
+                            pr[gt][s][0] = ldg4(p_); pr[gt][s][1] = ldg4(p_ + 4);
+                        }
+                    }
+                // S = (Q + u) K^T: acc[kt][r] = key 16 kt + 4 kq + r of row i
+                f32x4_ sa[4];
+#pragma unroll
+                for (int kt = 0; kt < 4; ++kt) {
+                    sa[kt] = (f32x4_){0.f, 0.f, 0.f, 0.f};
+                    if (kt < 2 || two) {
+#pragma unroll
+                        for (int s = 0; s < 2; ++s) {
+                            const int off = lmb_off(32 * ut + 16 * kt + i, kq + 4 * s);
+                            const uint4 kh = *reinterpret_cast<const uint4*>(Kh + off);
+                            if constexpr (LO) {
+                                const uint4 kl = *reinterpret_cast<const uint4*>(Kl + off);
+                                sa[kt] = mfma16_<F16>(kh, qul[s], sa[kt]);
+                                sa[kt] = mfma16_<F16>(kl, quh[s], sa[kt]);
+                            }
+                            sa[kt] = mfma16_<F16>(kh, quh[s], sa[kt]);
+                        }
+                    }
+                }
+                // G = (Q + v) P^T over positional columns 16 gt + 4 kq + r -> slab row i (columns >= LMR_GLD are never read)
+#pragma unroll
+                for (int gt = 0; gt < 5; ++gt) {
+                    if (!(ABL & 2) && (gt < 3 || two)) {
+                        f32x4_ acc = (f32x4_){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                        for (int s = 0; s < 2; ++s) {
+                            uint4 ph, pl;
+                            split8_16<F16, LO>(pr[gt][s][0], pr[gt][s][1], ph, pl);
+                            if constexpr (LO) {
+                                acc = mfma16_<F16>(ph, qvl[s], acc);
+                                acc = mfma16_<F16>(pl, qvh[s], acc);
+                            }
+                            acc = mfma16_<F16>(ph, qvh[s], acc);
+                        }
+                        if (16 * gt + 4 * kq < LMR_GLD) *reinterpret_cast<f32x4_*>(&slab[i * LMR_GLD + 16 * gt + 4 * kq]) = acc;
+                    }
+                }
+                __builtin_amdgcn_wave_barrier();                     // (slab traffic is between lanes of this wave: keep program order)
+                // scores, online softmax (f32; v_exp_f32 as rel_attention_lm_bf)
+                const int prel = live ? psh - pm : 0;
+                float mx = -INFINITY;
+#pragma unroll
+                for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int k = 16 * kt + 4 * kq + r, a = a0 + k;
+                        const bool valid = live && (kt < 2 || two) && a >= ks && a < ke;
+                        sa[kt][r] = valid ? (sa[kt][r] + slab[i * LMR_GLD + k + prel]) * 0.125f : -INFINITY;
+                        if constexpr ((ABL & 4) != 0) sa[kt][r] = valid ? sa[kt][r] : 0.f;
+                        mx = fmaxf(mx, sa[kt][r]);
+                    }
+                if constexpr ((ABL & 4) == 0) {
+                mx = fmaxf(mx, xor_partner<16>(mx));
+                mx = fmaxf(mx, xor_partner<32>(mx));
+                const float mnew = fmaxf(mrun, mx);
+                float sm = 0.f;
+#pragma unroll
+                for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        sa[kt][r] = sa[kt][r] > -INFINITY ? __builtin_amdgcn_exp2f((sa[kt][r] - mnew) * 1.4426950408889634f) : 0.f;
+                        sm += sa[kt][r];
+                    }
+                sm += xor_partner<16>(sm);
+                sm += xor_partner<32>(sm);
+                const float alpha = live ? __builtin_amdgcn_exp2f((mrun - mnew) * 1.4426950408889634f) : 1.0f;   // first live tile: exp2(-inf) = 0
+                if (live) mrun = mnew;
+                lrun = lrun * alpha + sm;
+#pragma unroll
+                for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) o[dt][r] *= alpha;
+                } else {
+                    if (live) lrun = 1.f;
+                }
+                // P over the slab (this wave's G reads of the tile are done: P depends on them), back in PV operand layout
+                __builtin_amdgcn_wave_barrier();
+#pragma unroll
+                for (int kt = 0; kt < 4; ++kt)
+                    if (kt < 2 || two) *reinterpret_cast<f32x4_*>(&slab[i * LMR_GLD + 16 * kt + 4 * kq]) = sa[kt];
+                __builtin_amdgcn_wave_barrier();
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    if (s == 0 || two) {
+                        const float* pp = &slab[i * LMR_GLD + 32 * s + 8 * kq];
+                        uint4 ph, pl;
+                        split8_16<F16, LO>(*reinterpret_cast<const float4*>(pp), *reinterpret_cast<const float4*>(pp + 4), ph, pl);
+                        const int u = ut + s, base = (u >> 1) * 8192;
+#pragma unroll
+                        for (int dt = 0; dt < 4; ++dt) {
+                            const int off = base + lmb_off(16 * dt + i, 4 * (u & 1) + kq);
+                            const uint4 vh = *reinterpret_cast<const uint4*>(Vh + off);
+                            if constexpr (LO) {
+                                const uint4 vl = *reinterpret_cast<const uint4*>(Vl + off);
+                                o[dt] = mfma16_<F16>(vh, pl, o[dt]);
+                                o[dt] = mfma16_<F16>(vl, ph, o[dt]);
+                            }
+                            o[dt] = mfma16_<F16>(vh, ph, o[dt]);
+                        }
+                    }
+                }
+            }
+        }
+        if (f >= 0) {                                               // d = 16 dt + 4 kq + 0..3 of row f -> 16-byte stores
+            const float li = lrun > 0.f ? 1.0f / lrun : 0.f;
+            const long long m = (long long)b * P.F + f;
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt)
+                stg4(P.out + m * RNNT_D + h * RNNT_DK + 16 * dt + 4 * kq, make_float4(o[dt][0] * li, o[dt][1] * li, o[dt][2] * li, o[dt][3] * li));
+        }
     }
 }
