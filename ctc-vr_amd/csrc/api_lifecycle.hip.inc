@@ -35,6 +35,7 @@ int rnnt_create(const rnnt_config* cfg, rnnt_ctx** out) {
     if (const char* e_ = getenv("RNNT_LM_OUT_CHAIN")) ctx->lm_out_chain = atoi(e_);
     if (const char* e_ = getenv("RNNT_ATTN_BF")) ctx->attn_bf = atoi(e_);
     if (const char* e_ = getenv("RNNT_ATTN_RESIDENT")) ctx->attn_resident = atoi(e_);
+    if (const char* e_ = getenv("RNNT_CONV1_FUSE")) ctx->conv1_fuse = atoi(e_);
     if (const char* se = getenv("RNNT_WF_SUB_ASYNC")) ctx->wf_sub_async = (se[0] == '0') ? 0 : 1;
     const int B = cfg->max_streams;
     ctx->tmax = sub_len(cfg->max_chunk_frames);

@@ -324,35 +324,66 @@ int run_layer(rnnt_ctx* ctx, hipStream_t s, int l, int B, int tq, int T2, int kv
     return launch_ln(ctx, s, d.lnf);
 }
 
+static bool conv2_bw_on() {
+    static const int conv2_bw = getenv("RNNT_CONV2_BW") ? atoi(getenv("RNNT_CONV2_BW")) : 1;
+    return conv2_bw != 0;
+}
+// conv2 of M rows forms its conv1 operand itself (gemm_bw_c1): no conv1 launch, no y1 slab.  The same condition as gemm_bw's, plus
+// the per-context knob; the caller must also allow it (fuse_ok: the layer-major schedule's main classes).
+static bool conv2_fused(const rnnt_ctx* ctx, long long M) {
+    return ctx->conv1_fuse && ctx->numerics != RNNT_NUM_F32 && conv2_bw_on() && ctx->conv2_wp && M >= 32768 && M < (1ll << 31);
+}
 // Conv2dSubsampling4 (+ x16) (subsampling.py:203-228) of `nc` equal-length chunks of every stream at once:
 // virtual stream v = c*B + b; output rows (v, r) -> xout[(v*tq + r)][256].  starts_dev == null: one chunk at 0.
 // out_cn > 0 (layer-major encoder): virtual streams in stream-major order (v = b*nc + c) and output row m -> xout row
 // (m / out_cn)*out_rows + (m % out_cn) + out_r0, i.e. the nc chunks' frames of stream b land at frames out_r0.. of its utterance.
+// fuse_ok: y1 may be null where conv2_fused(ctx, nc * B * sub_len(T) * RNNT_FSUB) holds.
 int run_subsample(rnnt_ctx* ctx, hipStream_t s, const float* fbank, int B, int Tstride, int T, const int* starts_dev, int nc,
-                  float* y1, float* y2, float* xout, int out_cn = 0, int out_rows = 0, int out_r0 = 0, bool minor = false) {
+                  float* y1, float* y2, float* xout, int out_cn = 0, int out_rows = 0, int out_r0 = 0, bool minor = false, bool fuse_ok = false) {
     // minor: not the call's main chunk class -- its launches are profiled under their own tags, so that a site's average launch time
     // is the average of launches of ONE kind (the bench's roofline is checked against the kernel's rocprof average)
     const int tag1 = minor ? TAG_CONV1_MINOR : TAG_CONV1, tag2 = minor ? TAG_CONV2_MINOR : TAG_CONV2, tag3 = minor ? TAG_EMBED_MINOR : TAG_EMBED;
     const int t1 = sub1_len(T), tq = sub_len(T);
     const int VB = nc * B;
     int rc;
-    { ProfScope prof(ctx, s, tag1);
-    static const int c1_rows = getenv("RNNT_CONV1_ROWS") ? atoi(getenv("RNNT_CONV1_ROWS")) : 1;
-    if (c1_rows && (long long)VB * ((t1 + C1_TB - 1) / C1_TB) >= 256)   // enough (stream, 8-row block) pairs to fill the chip: coalesced row stores
-        hipLaunchKernelGGL(conv1_relu_rows, dim3(VB, (t1 + C1_TB - 1) / C1_TB), dim3(256), 0, s, fbank, ctx->conv1_wt, ctx->conv1_b, y1, B, Tstride, t1,
-                           starts_dev, nc, out_cn > 0 ? 1 : 0);
-    else
-        hipLaunchKernelGGL(conv1_relu, dim3(grid_for((long long)VB * t1 * RNNT_F1 * D)), dim3(256), 0, s, fbank, ctx->conv1_wt, ctx->conv1_b,
-                           y1, B, Tstride, t1, starts_dev, nc, out_cn > 0 ? 1 : 0); }
-    LAUNCHCHK("conv1_relu");
+    const bool fused = fuse_ok && conv2_fused(ctx, (long long)VB * tq * RNNT_FSUB);
+    if (!fused) {
+        if (!y1) return fail(ctx, RNNT_ERR_STATE, "run_subsample: no conv1 slab");
+        ProfScope prof(ctx, s, tag1);
+        static const int c1_rows = getenv("RNNT_CONV1_ROWS") ? atoi(getenv("RNNT_CONV1_ROWS")) : 1;
+        if (c1_rows && (long long)VB * ((t1 + C1_TB - 1) / C1_TB) >= 256)   // enough (stream, 8-row block) pairs to fill the chip: coalesced row stores
+            hipLaunchKernelGGL(conv1_relu_rows, dim3(VB, (t1 + C1_TB - 1) / C1_TB), dim3(256), 0, s, fbank, ctx->conv1_wt, ctx->conv1_b, y1, B, Tstride, t1,
+                               starts_dev, nc, out_cn > 0 ? 1 : 0);
+        else
+            hipLaunchKernelGGL(conv1_relu, dim3(grid_for((long long)VB * t1 * RNNT_F1 * D)), dim3(256), 0, s, fbank, ctx->conv1_wt, ctx->conv1_b,
+                               y1, B, Tstride, t1, starts_dev, nc, out_cn > 0 ? 1 : 0);
+        LAUNCHCHK("conv1_relu");
+    }
     // conv2 as implicit GEMM: rows (v,t',f), K = (kh, kw, ci) = 3 segments of 768 contiguous floats of y1
     GemmP g = plain_gemm(y1, 0, ctx->conv2_w, 2304, ctx->conv2_b, y2, D, VB * tq * RNNT_FSUB, D, 2304, EPI_RELU);
     g.a_n1 = tq * RNNT_FSUB; g.a_n2 = RNNT_FSUB;
     g.a_s0 = (long long)t1 * RNNT_F1 * D; g.a_s1 = 2LL * RNNT_F1 * D; g.a_s2 = 2LL * D;
     g.a_seg = 768; g.a_seg_stride = (long long)RNNT_F1 * D;
     static const int conv2_lds = getenv("RNNT_CONV2_LDS") ? atoi(getenv("RNNT_CONV2_LDS")) : 1;
-    static const int conv2_bw = getenv("RNNT_CONV2_BW") ? atoi(getenv("RNNT_CONV2_BW")) : 1;
-    if (ctx->numerics != RNNT_NUM_F32 && conv2_bw && ctx->conv2_wp && g.M >= 32768) {
+    const bool conv2_bw = conv2_bw_on();
+    if (fused) {
+        // the same tiles with the conv1 operand formed from the fbank in the tile staging (gemm_bw_c1): g.A stays null
+        ProfScope prof(ctx, s, tag2);
+        g.A = nullptr;
+        if ((rc = prepare_gemm(ctx, g))) return rc;
+        const dim3 grid((g.M + 127) / 128);
+        const Conv1Src src{fbank, ctx->conv1_wt, ctx->conv1_b, starts_dev, B, Tstride, nc, out_cn > 0 ? 1 : 0};
+        static const bool nw8 = getenv("RNNT_BW_NW") ? atoi(getenv("RNNT_BW_NW")) == 8 : true;
+#define BWC_LAUNCH(NUM_) { if (nw8) hipLaunchKernelGGL((gemm_bw_c1<NUM_, 8>), grid, dim3(512), 0, s, g, ctx->conv2_wp, src); \
+                           else hipLaunchKernelGGL((gemm_bw_c1<NUM_, 4>), grid, dim3(256), 0, s, g, ctx->conv2_wp, src); }
+        switch (ctx->numerics) {
+            case RNNT_NUM_BF16: BWC_LAUNCH(RNNT_NUM_BF16) break;
+            case RNNT_NUM_F16X3: BWC_LAUNCH(RNNT_NUM_F16X3) break;
+            default: BWC_LAUNCH(RNNT_NUM_BF16X3) break;
+        }
+#undef BWC_LAUNCH
+        LAUNCHCHK("gemm_bw_c1");
+    } else if (ctx->numerics != RNNT_NUM_F32 && conv2_bw && ctx->conv2_wp && g.M >= 32768) {
         // whole-utterance slab: 128 x 256 tiles, weights streamed from L2 in fragment order, A rows four k-steps ahead (gemm_bw)
         ProfScope prof(ctx, s, tag2);
         if ((rc = prepare_gemm(ctx, g))) return rc;

@@ -157,10 +157,15 @@ int encoder_chunks_lm(rnnt_ctx* ctx, hipStream_t s, const float* fbank_dev, int 
         const size_t slab_bytes = 2048ull << 20;
         struct Cls { int c0, c1; };
         std::vector<Cls> cls;                                      // runs of equal-length chunks (one slab each)
+        // (the bound is on the class's largest slab: y1 -- or y2 where conv2 forms the conv1 operand itself and no y1 exists; a run that
+        // is cut by the y1 bound and whose pieces would still be fused is cut by the y2 bound instead, so fusing never adds a class)
+        auto fused_cls = [&](int c0, int nc) { return conv2_fused(ctx, (long long)nc * B * ci[c0].tq * RNNT_FSUB); };
         for (int c0 = 0; c0 < C;) {
-            int c1 = c0 + 1;
-            const size_t per1 = (size_t)B * sub1_len(ci[c0].len) * RNNT_F1 * D;
+            int c1 = c0 + 1, e1 = c0 + 1;
+            const size_t per1 = (size_t)B * sub1_len(ci[c0].len) * RNNT_F1 * D, per2 = (size_t)B * ci[c0].tq * RNNT_FSUB * D;
             while (c1 < C && ci[c1].len == ci[c0].len && (size_t)(c1 - c0 + 1) * per1 * sizeof(float) <= slab_bytes) ++c1;
+            while (e1 < C && ci[e1].len == ci[c0].len && (size_t)(e1 - c0 + 1) * per2 * sizeof(float) <= slab_bytes) ++e1;
+            if (e1 > c1 && fused_cls(c0, e1 - c0)) c1 = e1;
             cls.push_back({c0, c1});
             c0 = c1;
         }
@@ -174,7 +179,7 @@ int encoder_chunks_lm(rnnt_ctx* ctx, hipStream_t s, const float* fbank_dev, int 
             const int c0 = cls[k].c0, nc = cls[k].c1 - cls[k].c0;
             const size_t per1 = (size_t)B * sub1_len(ci[c0].len) * RNNT_F1 * D, per2 = (size_t)B * ci[c0].tq * RNNT_FSUB * D;
             if (side && k + 1 == cls.size()) { need1b = per1 * nc; need2b = per2 * nc; }
-            else { need1 = std::max(need1, per1 * nc); need2 = std::max(need2, per2 * nc); }
+            else { if (!fused_cls(c0, nc)) need1 = std::max(need1, per1 * nc); need2 = std::max(need2, per2 * nc); }
         }
         if ((rc = grow(ctx, &ctx->lm_y1, &ctx->lm_y1_cap, need1))) return rc;
         if ((rc = grow(ctx, &ctx->lm_y2, &ctx->lm_y2_cap, need2))) return rc;
@@ -206,7 +211,7 @@ int encoder_chunks_lm(rnnt_ctx* ctx, hipStream_t s, const float* fbank_dev, int 
             const int c0 = cls[k].c0, nc = cls[k].c1 - cls[k].c0;
             if ((long long)nc * B * ci[c0].tq * RNNT_FSUB >= (1ll << 31)) return fail(ctx, RNNT_ERR_SHAPE, "subsampling slab too large");
             if ((rc = run_subsample(ctx, s, fbank_dev, B, total_frames, ci[c0].len, ctx->wf_starts + c0, nc, ctx->lm_y1, ctx->lm_y2, x,
-                                    nc * ci[c0].tq, F, ci[c0].fpos - fb0, c0 != 0)))
+                                    nc * ci[c0].tq, F, ci[c0].fpos - fb0, c0 != 0, true)))
                 return rc;
         }
         if (side) {

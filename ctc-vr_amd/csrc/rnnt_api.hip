@@ -134,6 +134,7 @@ struct rnnt_ctx {
     int lm_side = 1;                           // RNNT_LM_SIDE=0: the tail chunk class's subsampling in line instead of on the side stream
     int attn_bf = 1;                           // RNNT_ATTN_BF=0: exact-f32 MFMA attention (rel_attention_lm_mfma) in every mode
     int attn_resident = 1;                     // RNNT_ATTN_RESIDENT=0: always the tiled rel_attention_lm_bf, never rel_attention_lm_res
+    int conv1_fuse = 1;                        // RNNT_CONV1_FUSE=0: conv1_relu_rows + gemm_bw over the y1 slab, never gemm_bw_c1
     float *lm_x = nullptr, *lm_h = nullptr, *lm_q = nullptr, *lm_a = nullptr, *lm_d = nullptr, *lm_g = nullptr, *lm_y1 = nullptr, *lm_y2 = nullptr;
     size_t lm_y1_cap = 0, lm_y2_cap = 0, lm_blocks_cap = 0;
     float *lm_y1b = nullptr, *lm_y2b = nullptr;      // slabs of the tail chunk class (subsampled on sub_stream beside the main class)

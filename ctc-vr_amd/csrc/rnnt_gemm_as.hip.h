@@ -824,26 +824,58 @@ __global__ __launch_bounds__(64 * NW) void ffn_as(FfnP P) {
 // is what the per-CU L2 fetch rate (~45 GB/s) can feed.  Same products and k order as gemm_bf.
 // ------------------------------------------------------------------------------------------------
 // NW waves (4 or 8): every wave owns 256 / NW output columns of all 128 rows; 8 = two waves per SIMD.
-template <int NUM, int NW = 4>
-__global__ __launch_bounds__(64 * NW) void gemm_bw(GemmP p, const uint4* __restrict__ wp) {
+//
+// FUSE (gemm_bw_c1, conv2 only): the A operand is conv1's output, FORMED in the tile staging and never in memory.  Row m is
+// (virtual stream v, t', f') and k-step k covers channels 32 (k & 7) .. + 31 of tap (kh, kw) = k >> 3, so the eight floats a
+// stager splits are y1[v][2t' + kh][2f' + kw][c .. c + 7] = relu(b1[c] + nine fmaf over the 3 x 3 fbank patch at rows
+// start + 4t' + 2kh, columns 4f' + 2kw) in conv1_relu_rows' exact order: bit-identical to the slab's values.  The stagers are
+// remapped (wave -> channel group sc, lane -> row) so that the 9 x 8 weights + 8 biases of a k-step are wave-uniform and come
+// through the scalar cache into SGPRs (80 per k-step, one k-step ahead); the patch (9 VGPRs per row) is reloaded from L2 once
+// per tap (8 k-steps), before the MFMAs of the k-step that ends the previous tap.  The Ah / Al slots of a quarter wave are then
+// 16 consecutive rows at one sc: bf_swz gives rows r, r+4, r+8, r+12 four different 16-byte slots, so the store stays conflict-free.
+struct Conv1Src {
+    const float* x;          // fbank [B][T][80]
+    const float* w1t;        // [9][256]
+    const float* b1;         // [256]
+    const int* starts;       // first fbank frame of every chunk (null: one chunk at 0)
+    int B, T, n_chunks, b_major;
+};
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ float ldc1(const float* p) { return *(const __attribute__((address_space(4))) float*)p; }   // uniform address: scalar load
+#else
+__device__ __forceinline__ float ldc1(const float* p) { return *p; }
+#endif
+template <int NUM, int NW, bool FUSE>
+__device__ __forceinline__ void gemm_bw_body(const GemmP& p, const uint4* __restrict__ wp, const Conv1Src& c1) {
     using C = FuseCfg<NUM>;
     constexpr bool F16 = C::F16, LO = C::PLANES == 2;
     constexpr int U = C::PLANES, MT = 8, NTW = 16 / NW, NT = 64 * NW, AJ = NT >= 512 ? 1 : 512 / NT;   // AJ: 8-float A chunks per thread and k-step (NW = 16: the first 512 threads stage)
+    static_assert(!FUSE || NW <= 8, "fused staging maps waves 0..7");
     __shared__ uint4 Ah[2][512];
     __shared__ uint4 Al[LO ? 2 : 1][LO ? 512 : 1];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = lane & 15, q = lane >> 4;
     const int bm0 = blockIdx.x * 128;
     if (bm0 >= p.M) return;
-    const int srow = (tid & 511) >> 2, sc = tid & 3;
+    const int uwave = __builtin_amdgcn_readfirstlane(wave);
+    const int srow = FUSE ? (uwave >> 2) * 64 + lane : (tid & 511) >> 2, sc = FUSE ? (uwave & 3) : (tid & 3);
     const bool stager = NT <= 512 || tid < 512;
     const float* ag[AJ];
 #pragma unroll
-    for (int j = 0; j < AJ; ++j) ag[j] = p.A + a_row_off(p, min(bm0 + srow + (NT / 4) * j, p.M - 1));
+    for (int j = 0; j < AJ; ++j) {
+        const int m = min(bm0 + srow + (NT / 4) * j, p.M - 1);
+        if constexpr (FUSE) {                                        // origin of the row's 7 x 7 fbank window
+            const int v = fastdiv(m, p.a_n1, p.a_n1_magic, p.a_n1_shift), r1 = m - v * p.a_n1;
+            const int tp = fastdiv(r1, p.a_n2, p.a_n2_magic, p.a_n2_shift), fp = r1 - tp * p.a_n2;
+            const int cidx = c1.b_major ? v % c1.n_chunks : v / c1.B, b = c1.b_major ? v / c1.n_chunks : v - cidx * c1.B;
+            const int st0 = c1.starts ? ldgi(c1.starts + cidx) : 0;
+            ag[j] = c1.x + ((long long)b * c1.T + st0 + 4 * tp) * RNNT_IDIM + 4 * fp;
+        } else ag[j] = p.A + a_row_off(p, m);
+    }
     const bool aplain = p.a_plain != 0;
     const int KT = p.K >> 5;
     // the A stream comes from HBM (1.09 GB for conv2): its loads run FOUR k-steps ahead of the MFMAs in a register ring
-    float4 ra[4][AJ][2];
+    float4 ra[FUSE ? 1 : 4][AJ][2];
     auto gload = [&](float4 (&r)[AJ][2], int blk) {
         if (BW_ABL & 1) { for (int j = 0; j < AJ; ++j) { r[j][0] = make_float4(0.5f, 0.25f, 1.f, 2.f); r[j][1] = r[j][0]; } return; }
         if (!stager) return;
@@ -851,6 +883,46 @@ __global__ __launch_bounds__(64 * NW) void gemm_bw(GemmP p, const uint4* __restr
         const long long ko = aplain ? (long long)kk : a_k_off(p, kk);
 #pragma unroll
         for (int j = 0; j < AJ; ++j) { r[j][0] = ldg4_nt(ag[j] + ko); r[j][1] = ldg4_nt(ag[j] + ko + 4); }   // streamed once: keep the weights in L2
+    };
+    // FUSE: the producer's operands -- the rows' patches of the current tap (VGPRs) and the k-step's conv1 weights + biases (SGPRs)
+    // (the weights in two halves of four channels: the first is asked for before the k-step's MFMAs, the second at the head of
+    // the producer behind the first half's 36 fmaf -- all 80 values live across the MFMAs spilled SGPRs into VGPR lanes)
+    float xp[FUSE ? AJ : 1][9], cw[2][FUSE ? 9 : 1][4], cb[2][4];
+    auto pload = [&](int tap) {
+        const int kh = tap / 3, kw = tap - 3 * kh;
+#pragma unroll
+        for (int j = 0; j < AJ; ++j)
+#pragma unroll
+            for (int r = 0; r < 3; ++r)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) xp[j][r * 3 + c] = ldg1(ag[j] + (2 * kh + r) * RNNT_IDIM + 2 * kw + c);
+    };
+    auto wload = [&](int blk, int half) {
+        const int c0 = (blk & 7) * 32 + 8 * sc + 4 * half;
+#pragma unroll
+        for (int t = 0; t < 9; ++t)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) cw[half][t][e] = ldc1(c1.w1t + t * RNNT_D + c0 + e);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) cb[half][e] = ldc1(c1.b1 + c0 + e);
+    };
+    auto produce = [&](float4 (&r)[AJ][2], int blk) {
+        if (BW_ABL & 1) { for (int j = 0; j < AJ; ++j) { r[j][0] = make_float4(0.5f, 0.25f, 1.f, 2.f); r[j][1] = r[j][0]; } return; }
+        wload(blk, 1);
+#pragma unroll
+        for (int half = 0; half < 2; ++half)
+#pragma unroll
+            for (int j = 0; j < AJ; ++j) {
+                float y[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float acc = cb[half][e];
+#pragma unroll
+                    for (int t = 0; t < 9; ++t) acc = fmaf(xp[j][t], cw[half][t][e], acc);   // conv1_relu_rows' order: kh outer, kw inner
+                    y[e] = fmaxf(acc, 0.f);
+                }
+                r[j][half] = make_float4(y[0], y[1], y[2], y[3]);
+            }
     };
     auto lstore = [&](int buf, const float4 (&r)[AJ][2]) {
         if (!stager) return;
@@ -906,10 +978,14 @@ __global__ __launch_bounds__(64 * NW) void gemm_bw(GemmP p, const uint4* __restr
     // weight fragments BW_WD k-steps ahead in a ring of four register sets (one k-step of MFMAs is shorter than an L2 round trip
     // under load: with one k-step of run-ahead every k-step began with a wait)
     uint4 wb[4][NTW * U];
+    if constexpr (FUSE) { pload(0); wload(0, 0); }
+    else {
 #pragma unroll
-    for (int k = 0; k < 4; ++k) gload(ra[k], k);                     // KT >= 4 and KT % 4 == 0 (host check)
+        for (int k = 0; k < 4; ++k) gload(ra[k], k);                 // KT >= 4 and KT % 4 == 0 (host check)
+    }
 #pragma unroll
     for (int k = 0; k < BW_WD; ++k) bload(wb[k], k);
+    if constexpr (FUSE) produce(ra[0], 0);
     lstore(0, ra[0]);
     __syncthreads();
 #ifdef AS_TRACE
@@ -925,12 +1001,18 @@ __global__ __launch_bounds__(64 * NW) void gemm_bw(GemmP p, const uint4* __restr
             // LDS buffer k & 1 holds A(k); ring slots (s+1..s+3) % 4 hold A(k+1..k+3); slot s is free again
             // loads return in issue order: the weight fragments go first, the far-ahead A rows behind them
             if (k + BW_WD < KT) bload(wb[(s + BW_WD) & 3], k + BW_WD);
-            if (k + 4 < KT) gload(ra[s], k + 4);
+            if constexpr (FUSE) {
+                // A(k+1) is formed after the MFMAs of this k-step: its weights, and at a tap boundary its patch, are asked for now
+                if (k + 1 < KT) { if (((k + 1) & 7) == 0) pload((k + 1) >> 3); wload(k + 1, 0); }
+            } else if (k + 4 < KT) gload(ra[s], k + 4);
             BW_STAMP(0)                                              // load issue
             mma(s & 1, wb[s]);
             BW_STAMP(1)                                              // wait for the weight fragments + A fragment reads + MFMAs
-            if (k + 1 < KT && !(BW_ABL & 8)) lstore((s + 1) & 1, ra[(s + 1) & 3]);
-            BW_STAMP(2)                                              // wait for the A rows + split + LDS stores
+            if (k + 1 < KT && !(BW_ABL & 8)) {
+                if constexpr (FUSE) { produce(ra[0], k + 1); lstore((s + 1) & 1, ra[0]); }
+                else lstore((s + 1) & 1, ra[(s + 1) & 3]);
+            }
+            BW_STAMP(2)                                              // wait for the A rows (FUSE: the producer arithmetic) + split + LDS stores
             if (!(BW_ABL & 16)) __syncthreads();
             BW_STAMP(3)                                              // barrier
         }
@@ -940,3 +1022,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_bw(GemmP p, const uint4* __restr
 #endif
     as_epilogue_t<MT, NTW>(p, acc, bm0, wave * 16 * NTW, lane);
 }
+template <int NUM, int NW = 4>
+__global__ __launch_bounds__(64 * NW) void gemm_bw(GemmP p, const uint4* __restrict__ wp) { gemm_bw_body<NUM, NW, false>(p, wp, Conv1Src{}); }
+template <int NUM, int NW = 8>
+__global__ __launch_bounds__(64 * NW) void gemm_bw_c1(GemmP p, const uint4* __restrict__ wp, Conv1Src c1) { gemm_bw_body<NUM, NW, true>(p, wp, c1); }

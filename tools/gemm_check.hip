@@ -266,7 +266,90 @@ static void problem_ffn(int M, bool lno) {
     printf("  ffn_as<%d>  %8.1f us  %7.1f TFLOP/s (algorithmic, both contractions)  max |err| vs double reference %.3e  runs differing: %d/2\n",
            MT, us, 4.0 * M * 256 * 1024 / us / 1e6, worst, nondet);
 }
+// conv2 at the bench shape (64 streams x 61 chunks of 16 frames: M = 222528, K = 2304) from a seeded fbank: conv1_relu_rows + gemm_bw
+// over the y1 slab against gemm_bw_c1, which forms the same operand in its tile staging.  Bitwise comparison, times, stamps.
+// Build with -DBW_ABL=1 (no producer arithmetic / no A loads), 2 (no weight loads), 4 (no MFMAs) for the ablations (wrong results).
+static void div_magic_(int d, unsigned& magic, int& shift) {
+    if (d <= 1) { magic = 0; shift = 0; return; }
+    int l = 0;
+    while ((1ll << l) < d) ++l;
+    shift = l - 1;
+    magic = (unsigned)(((1ull << (32 + shift)) + (unsigned long long)d - 1) / (unsigned long long)d);
+}
+static int problem_conv1_fused() {
+    const int B = 64, NC = 61, LEN = 16, T = 1000, t1 = (LEN - 1) / 2, tq = (t1 - 1) / 2, VB = B * NC, M = VB * tq * RNNT_FSUB, K = 2304;
+    printf("conv1 + conv2, fused against unfused: %d streams x %d chunks of %d frames, M=%d N=256 K=%d\n", B, NC, LEN, M, K);
+    std::mt19937 rng(321);
+    std::normal_distribution<float> nd(0.f, 1.f);
+    std::vector<float> hx((size_t)B * T * RNNT_IDIM), hw1(9 * 256), hb1(256), hW((size_t)256 * K), hb(256);
+    std::vector<int> hst(NC);
+    for (auto& v : hx) v = nd(rng) * 2.f - 4.f;
+    for (auto& v : hw1) v = nd(rng) * 0.3f;
+    for (auto& v : hb1) v = nd(rng) * 0.1f;
+    for (auto& v : hW) v = nd(rng) * 0.02f;
+    for (auto& v : hb) v = nd(rng) * 0.1f;
+    for (int c = 0; c < NC; ++c) hst[c] = c * LEN;
+    float *x, *w1, *b1, *W, *bias, *y1, *C0, *C1; int* st; uint4* Wp;
+    const size_t ny1 = (size_t)VB * t1 * RNNT_F1 * 256, nC = (size_t)M * 256;
+    CK(hipMalloc(&x, hx.size() * 4)); CK(hipMalloc(&w1, hw1.size() * 4)); CK(hipMalloc(&b1, 1024)); CK(hipMalloc(&W, hW.size() * 4)); CK(hipMalloc(&bias, 1024));
+    CK(hipMalloc(&y1, ny1 * 4)); CK(hipMalloc(&C0, nC * 4)); CK(hipMalloc(&C1, nC * 4)); CK(hipMalloc(&st, NC * 4)); CK(hipMalloc(&Wp, hW.size() * 4));
+    CK(hipMemcpy(x, hx.data(), hx.size() * 4, hipMemcpyHostToDevice)); CK(hipMemcpy(w1, hw1.data(), hw1.size() * 4, hipMemcpyHostToDevice));
+    CK(hipMemcpy(b1, hb1.data(), 1024, hipMemcpyHostToDevice)); CK(hipMemcpy(W, hW.data(), hW.size() * 4, hipMemcpyHostToDevice));
+    CK(hipMemcpy(bias, hb.data(), 1024, hipMemcpyHostToDevice)); CK(hipMemcpy(st, hst.data(), NC * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL((pack_frag<RNNT_NUM_BF16X3>), dim3(1024), dim3(256), 0, 0, W, 256, K, K, Wp);
+    CK(hipDeviceSynchronize());
+    GemmP g; memset(&g, 0, sizeof(g));
+    g.A = y1; g.W = W; g.bias = bias; g.C = C0; g.M = M; g.N = 256; g.K = K; g.ldw = K; g.epi = EPI_RELU; g.alpha = 1.f; g.x_n = 1;
+    g.a_n1 = tq * RNNT_FSUB; g.a_n2 = RNNT_FSUB; g.a_s0 = (long long)t1 * RNNT_F1 * 256; g.a_s1 = 2LL * RNNT_F1 * 256; g.a_s2 = 2LL * 256;
+    g.a_seg = 768; g.a_seg_stride = (long long)RNNT_F1 * 256; g.c_n = INT_MAX; g.c_mod = INT_MAX; g.c_s1 = 256; g.c_plain = 1;
+    div_magic_(g.a_n1, g.a_n1_magic, g.a_n1_shift); div_magic_(g.a_n2, g.a_n2_magic, g.a_n2_shift); div_magic_(g.a_seg, g.a_seg_magic, g.a_seg_shift);
+    GemmP gf = g; gf.A = nullptr; gf.C = C1;
+    const Conv1Src src{x, w1, b1, st, B, T, NC, 1};
+    const dim3 grid((M + 127) / 128), grid1(VB, (t1 + C1_TB - 1) / C1_TB);
+    hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+    auto stamps = [&]() {
+        std::vector<long long> tr(4096 * 8);
+        CK(hipMemcpyFromSymbol(tr.data(), HIP_SYMBOL(as_trace), tr.size() * 8));
+        double sm[4] = {0, 0, 0, 0};
+        for (int b = 0; b < 1024; ++b) for (int k = 0; k < 4; ++k) sm[k] += (double)tr[(b * 4) * 8 + k];
+        printf("             wave 0 of the first 1024 tiles, clocks per k-step: load issue %.0f, weights wait + A reads + MFMAs %.0f, A wait / producer + split + LDS stores %.0f, barrier %.0f\n",
+               sm[0] / 1024 / (K / 32), sm[1] / 1024 / (K / 32), sm[2] / 1024 / (K / 32), sm[3] / 1024 / (K / 32));
+    };
+    auto timed = [&](const char* nm, auto launch, bool stamp) {
+        launch();
+        CK(hipDeviceSynchronize());
+        CK(hipEventRecord(e0, 0));
+        for (int r = 0; r < 5; ++r) launch();
+        CK(hipEventRecord(e1, 0));
+        CK(hipDeviceSynchronize());
+        float ms; CK(hipEventElapsedTime(&ms, e0, e1));
+        printf("  %-28s %8.1f us\n", nm, ms * 1e3 / 5);
+        if (stamp) stamps();
+        return ms * 1e3 / 5;
+    };
+    CK(hipMemset(C0, 0xff, nC * 4)); CK(hipMemset(C1, 0xff, nC * 4));
+    const double tc1 = timed("conv1_relu_rows", [&] { hipLaunchKernelGGL(conv1_relu_rows, grid1, dim3(256), 0, 0, x, w1, b1, y1, B, T, t1, st, NC, 1); }, false);
+    const double tc2 = timed("gemm_bw<8> over the y1 slab", [&] { hipLaunchKernelGGL((gemm_bw<RNNT_NUM_BF16X3, 8>), grid, dim3(512), 0, 0, g, Wp); }, true);
+    printf("  %-28s %8.1f us\n", "conv1 + conv2 unfused", tc1 + tc2);
+    std::vector<float> o0(nC), o1(nC);
+    CK(hipMemcpy(o0.data(), C0, nC * 4, hipMemcpyDeviceToHost));
+    int bad = 0;
+    auto check = [&](const char* nm) {
+        CK(hipMemcpy(o1.data(), C1, nC * 4, hipMemcpyDeviceToHost));
+        const bool same = !memcmp(o0.data(), o1.data(), nC * 4);
+        double sum = 0; for (size_t e = 0; e < nC; e += 97) sum += o1[e];
+        printf("  %-28s bit-identical to the unfused output: %d   (sampled output sum %.6e)\n", nm, (int)same, sum);
+        if (!same) ++bad;
+        CK(hipMemset(C1, 0xff, nC * 4));
+    };
+    timed("gemm_bw_c1<8>", [&] { hipLaunchKernelGGL((gemm_bw_c1<RNNT_NUM_BF16X3, 8>), grid, dim3(512), 0, 0, gf, Wp, src); }, true);
+    check("gemm_bw_c1<8>");
+    timed("gemm_bw_c1<4>", [&] { hipLaunchKernelGGL((gemm_bw_c1<RNNT_NUM_BF16X3, 4>), grid, dim3(256), 0, 0, gf, Wp, src); }, true);
+    check("gemm_bw_c1<4>");
+    return (BW_ABL) ? 0 : bad;
+}
 int main() {
+    if (getenv("GC_CONV1F")) return problem_conv1_fused();
     if (!getenv("GC_CONV2")) {
         problem_ffn(12032, false);
         problem_ffn(12032, true);
