@@ -3,6 +3,8 @@
 int rnnt_greedy_decode(rnnt_ctx* ctx, void* stream) {
     if (!ctx) return RNNT_ERR_ARG;
     if (!ctx->finalized || ctx->n_streams < 1) return fail(ctx, RNNT_ERR_STATE, "rnnt_greedy_decode: no weights / no streams");
+    if (ctx->pool_mode && ctx->frames_buffered > 0)   // frames of an encoder-only pool call: only the active slots' rows are defined
+        return fail(ctx, RNNT_ERR_STATE, "rnnt_greedy_decode: stream pool frames are decoded by rnnt_pool_chunk(greedy != 0)");
     hipStream_t s = (hipStream_t)stream;
     const int nf = ctx->frames_buffered;
     if (nf <= ctx->frames_decoded) return RNNT_OK;

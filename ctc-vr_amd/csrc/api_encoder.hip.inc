@@ -5,6 +5,7 @@ int rnnt_encoder_chunk(rnnt_ctx* ctx, const float* fbank_dev, int32_t T, int32_t
                        int32_t* frames_out, void* stream) {
     if (!ctx || !fbank_dev) return fail(ctx, RNNT_ERR_ARG, "rnnt_encoder_chunk: null argument");
     if (!ctx->finalized || ctx->n_streams < 1) return fail(ctx, RNNT_ERR_STATE, "rnnt_encoder_chunk: no weights / no streams");
+    if (ctx->pool_mode) return fail(ctx, RNNT_ERR_STATE, "rnnt_encoder_chunk: the slots have positions of their own (stream pool); call rnnt_streams_reset first");
     if (T < 7 || T > ctx->cfg.max_chunk_frames) return fail(ctx, RNNT_ERR_SHAPE, "chunk of %d frames outside [7, %d]", T, ctx->cfg.max_chunk_frames);
     hipStream_t s = (hipStream_t)stream;
     const int B = ctx->n_streams;
@@ -138,6 +139,7 @@ int rnnt_decode_ragged(rnnt_ctx* ctx, const float* fbank_dev, int32_t total_fram
                        int32_t* frames_out, void* stream) {
     if (!ctx || !fbank_dev || !lens_host) return fail(ctx, RNNT_ERR_ARG, "rnnt_decode_ragged: null argument");
     if (!ctx->finalized || ctx->n_streams < 1) return fail(ctx, RNNT_ERR_STATE, "rnnt_decode_ragged: no weights / no streams");
+    if (ctx->pool_mode) return fail(ctx, RNNT_ERR_STATE, "rnnt_decode_ragged: the slots have positions of their own (stream pool); call rnnt_streams_reset first");
     if (ctx->cache_len || ctx->kv_start || ctx->conv_pos || ctx->frames_buffered)
         return fail(ctx, RNNT_ERR_STATE, "rnnt_decode_ragged needs freshly reset streams");
     if (!ctx->use_lm || !ctx->use_persistent) return fail(ctx, RNNT_ERR_STATE, "rnnt_decode_ragged needs the layer-major schedule and the resident decoder");
@@ -163,6 +165,7 @@ int rnnt_encode_ragged(rnnt_ctx* ctx, const float* fbank_dev, int32_t total_fram
                        int32_t* frames_out, void* stream) {
     if (!ctx || !fbank_dev || !lens_host) return fail(ctx, RNNT_ERR_ARG, "rnnt_encode_ragged: null argument");
     if (!ctx->finalized || ctx->n_streams < 1) return fail(ctx, RNNT_ERR_STATE, "rnnt_encode_ragged: no weights / no streams");
+    if (ctx->pool_mode) return fail(ctx, RNNT_ERR_STATE, "rnnt_encode_ragged: the slots have positions of their own (stream pool); call rnnt_streams_reset first");
     if (ctx->cache_len || ctx->kv_start || ctx->conv_pos || ctx->frames_buffered)
         return fail(ctx, RNNT_ERR_STATE, "rnnt_encode_ragged needs freshly reset streams");
     if (!ctx->use_lm) return fail(ctx, RNNT_ERR_STATE, "rnnt_encode_ragged needs the layer-major schedule");
@@ -184,6 +187,7 @@ int rnnt_encoder_chunks(rnnt_ctx* ctx, const float* fbank_dev, int32_t total_fra
     if (!ctx || !fbank_dev || !chunk_start || !chunk_len || !offsets || !required || n_chunks < 1)
         return fail(ctx, RNNT_ERR_ARG, "rnnt_encoder_chunks: bad argument");
     if (!ctx->finalized || ctx->n_streams < 1) return fail(ctx, RNNT_ERR_STATE, "rnnt_encoder_chunks: no weights / no streams");
+    if (ctx->pool_mode) return fail(ctx, RNNT_ERR_STATE, "rnnt_encoder_chunks: the slots have positions of their own (stream pool); call rnnt_streams_reset first");
     hipStream_t s = (hipStream_t)stream;
     const int B = ctx->n_streams, C = n_chunks;
     const int Mmax = ctx->cfg.max_streams * ctx->tmax;

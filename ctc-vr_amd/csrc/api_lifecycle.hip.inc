@@ -98,6 +98,9 @@ void rnnt_destroy(rnnt_ctx* ctx) {
     for (int l = 0; l < L; ++l)
         if (ctx->lw[l].ptab) (void)hipFree(ctx->lw[l].ptab);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
+    if (ctx->pool_tab) (void)hipFree(ctx->pool_tab);
+    if (ctx->pool_tab_host) (void)hipHostFree(ctx->pool_tab_host);
+    if (ctx->pool_ev) (void)hipEventDestroy(ctx->pool_ev);
     for (hipEvent_t e : ctx->prof_ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->wf_ev) (void)hipEventDestroy(e);
     if (ctx->dec_stream) (void)hipStreamDestroy(ctx->dec_stream);
@@ -463,6 +466,8 @@ int rnnt_streams_reset(rnnt_ctx* ctx, int32_t n_streams, void* stream) {
     ctx->cache_len = 0; ctx->kv_start = 0; ctx->conv_pos = 0;
     ctx->frames_buffered = 0; ctx->frames_decoded = 0;
     ctx->launches = 0; ctx->greedy_steps = 0;
+    ctx->pool_mode = false;                      // all slots share one position again
+    ctx->slot_pos.assign(B, rnnt_ctx::SlotPos{0, 0, 0});
     hipLaunchKernelGGL(conv_ring_init, dim3(grid_for((long long)L * B * ctx->cap * D)), dim3(256), 0, s, ctx->gring, ctx->xring, ctx->glu0, B, ctx->cap);
     LAUNCHCHK("conv_ring_init");
     hipLaunchKernelGGL(decode_state_reset, dim3(grid_for((long long)2 * B * D)), dim3(256), 0, s, ctx->h, ctx->c, ctx->sel, ctx->key, ctx->fidx, ctx->nsym,

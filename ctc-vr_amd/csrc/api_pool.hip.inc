@@ -1,0 +1,220 @@
+// C ABI: the stream pool -- slots of one context that open, advance and close independently (rnnt_stream_open, rnnt_pool_chunk,
+// rnnt_stream_get_tokens).  Included by rnnt_api.hip inside extern "C".
+//
+// Every stream's state already lives per stream on the device (K/V cache, the two conv rings, LSTM h/c, last token, token buffer);
+// the lock-step entry points only share its POSITION (cache_len, kv_start, conv_pos).  Here the position is per slot: plain host
+// integers in ctx->slot_pos, advanced by the reference's bookkeeping (encoder.py:254-264) and mirrored for each call into one
+// small device table (PoolRow per active row + the slot list of the decoder), written by ONE async copy from pinned memory.  The
+// rows of a call are compact -- row i * t' + f is frame f of active row i -- and every access to per-stream storage goes through
+// slots[i]: the K/V and ring appends through GemmP::c_tab, attention / depthwise conv / decoder through their pool forms.  Idle
+// slots are neither read nor written, and no launch is sized by them.
+//
+// Contract: what a slot computes is what a context holding only that stream computes through rnnt_encoder_chunk +
+// rnnt_greedy_decode + rnnt_frames_consume, bit for bit.  Two things make that hold: every per-slot loop bound comes from the
+// slot's own position (never from the launch's maximum), and kernel / tile choices that depend on the row count are made as for
+// one stream's rows (ctx->gemm_m_cap; the resident decoder is the one a single stream gets).
+
+namespace {
+
+int pool_alloc(rnnt_ctx* ctx) {
+    if (ctx->pool_tab) return RNNT_OK;
+    const size_t n = (size_t)ctx->cfg.max_streams * (POOL_ROW_INTS + 1);
+    int rc;
+    if ((rc = dmalloc(ctx, &ctx->pool_tab, n))) return rc;
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&ctx->pool_tab_host), n * sizeof(int)));
+    HIPCHK(hipEventCreateWithFlags(&ctx->pool_ev, hipEventDisableTiming));
+    return RNNT_OK;
+}
+
+// from here on every slot has its own position (the lock-step entry points refuse until rnnt_streams_reset)
+void pool_enter(rnnt_ctx* ctx) {
+    if (ctx->pool_mode) return;
+    ctx->slot_pos.assign(ctx->cfg.max_streams, rnnt_ctx::SlotPos{ctx->cache_len, ctx->kv_start, ctx->conv_pos});
+    ctx->pool_mode = true;
+}
+
+struct GemmCapScope {   // row-count dependent kernel choices as for one stream, for the launches of one pool call
+    rnnt_ctx* ctx;
+    explicit GemmCapScope(rnnt_ctx* c) : ctx(c) { ctx->gemm_m_cap = 1023; }
+    ~GemmCapScope() { ctx->gemm_m_cap = 0; }
+};
+
+// attention of one layer for the n active rows.  The kernel is chosen PER ROW exactly as launch_attn chooses it for that row's
+// T2 (attn_stream_ok): the streaming kernel for <= 4 new frames and <= 4096 keys, the LDS-tiled one otherwise; a launch whose
+// grid holds rows of the other kind lets their workgroups exit.  LDS of the streaming kernel: sized for the deepest row it serves.
+int launch_attn_pool(rnnt_ctx* ctx, hipStream_t s, const AttnP& a, const PoolRow* rows_dev, const PoolRow* rows_host, int n) {
+    ProfScope prof(ctx, s, TAG_ATTN);
+    int n_stream = 0, max_t2 = 1;
+    for (int i = 0; i < n; ++i)
+        if (attn_stream_ok(ctx, a.tq, rows_host[i].T2)) { ++n_stream; max_t2 = rows_host[i].T2 > max_t2 ? rows_host[i].T2 : max_t2; }
+    if (n_stream > 0) {
+        const int cap = attn_t2cap(max_t2);
+        const size_t lds = attn_stream_lds(cap);
+        if (lds > 48 * 1024) { const int rc = ensure_dyn_lds(ctx, reinterpret_cast<const void*>(&rel_attention_stream_pool), lds); if (rc) return rc; }
+        hipLaunchKernelGGL(rel_attention_stream_pool, dim3(n * RNNT_H), dim3(256), lds, s, a, rows_dev, cap);
+        LAUNCHCHK("rel_attention_stream_pool");
+    }
+    if (n_stream < n) {
+        const int sel = n_stream == 0 ? 2 : 0;   // all rows, or only those beyond the streaming kernel's range
+        const int nq = a.tq <= 4 ? 1 : (a.tq <= 8 ? 2 : 4);
+        dim3 grid(n * RNNT_H, (a.tq + 4 * nq - 1) / (4 * nq));
+        if (nq == 1) hipLaunchKernelGGL(rel_attention_pool<1>, grid, dim3(256), 0, s, a, rows_dev, sel);
+        else if (nq == 2) hipLaunchKernelGGL(rel_attention_pool<2>, grid, dim3(256), 0, s, a, rows_dev, sel);
+        else hipLaunchKernelGGL(rel_attention_pool<4>, grid, dim3(256), 0, s, a, rows_dev, sel);
+        LAUNCHCHK("rel_attention_pool");
+    }
+    return RNNT_OK;
+}
+
+// run_layer for the n active rows of a pool call: the same 11 launches, per-slot positions from the table
+int run_layer_pool(rnnt_ctx* ctx, hipStream_t s, int l, int n, int tq, const PoolRow* rows_dev, const PoolRow* rows_host) {
+    LayerDescs d;
+    LayerBufs bf{ctx->x, ctx->hbuf, ctx->qbuf, ctx->abuf, ctx->dbuf};
+    int rc = build_layer(ctx, l, n, tq, tq, 0, 0, 0, nullptr, bf, d);   // positions of the descriptors are placeholders: the table has them
+    if (rc) return rc;
+    const int* tab = reinterpret_cast<const int*>(rows_dev);
+    for (int i = 1; i < 3; ++i) { d.qkv[i].c_tab = tab; d.qkv[i].c_tab_col = POOL_COL_KV_W0; d.qkv[i].c_r0 = 0; }
+    d.pw1.c_tab = tab; d.pw1.c_tab_col = POOL_COL_RING_W0; d.pw1.c_r0 = 0;
+    if ((rc = launch_gemm(ctx, s, 0, &d.ffn1m, 1, TAG_FFN1))) return rc;
+    if ((rc = launch_gemm(ctx, s, 0, &d.ffn2m, 1, TAG_FFN2))) return rc;
+    if ((rc = launch_gemm(ctx, s, 0, d.qkv, 3, TAG_QKV))) return rc;
+    if ((rc = launch_attn_pool(ctx, s, d.attn, rows_dev, rows_host, n))) return rc;
+    if ((rc = launch_gemm(ctx, s, 0, &d.out, 1, TAG_ATTN_OUT))) return rc;
+    if ((rc = launch_gemm(ctx, s, 0, &d.pw1, 1, TAG_PW1))) return rc;
+    {
+        ProfScope prof(ctx, s, TAG_DWCONV);
+        hipLaunchKernelGGL(dwconv_bn_silu_pool, dim3(grid_for((long long)n * tq * D)), dim3(256), 0, s, d.dw, rows_dev);
+        LAUNCHCHK("dwconv_bn_silu_pool");
+    }
+    if ((rc = launch_gemm(ctx, s, 0, &d.pw2, 1, TAG_PW2))) return rc;
+    if ((rc = launch_gemm(ctx, s, 0, &d.ffn1, 1, TAG_FFN1))) return rc;
+    if ((rc = launch_gemm(ctx, s, 0, &d.ffn2, 1, TAG_FFN2))) return rc;
+    return launch_ln(ctx, s, d.lnf);
+}
+
+}  // namespace
+
+int rnnt_stream_open(rnnt_ctx* ctx, int32_t slot, void* stream) {
+    if (!ctx) return RNNT_ERR_ARG;
+    if (!ctx->finalized || ctx->n_streams < 1) return fail(ctx, RNNT_ERR_STATE, "rnnt_stream_open: no weights / no streams");
+    if (slot < 0 || slot >= ctx->n_streams) return fail(ctx, RNNT_ERR_ARG, "rnnt_stream_open: slot %d outside [0, %d)", slot, ctx->n_streams);
+    if (ctx->frames_buffered != 0) return fail(ctx, RNNT_ERR_STATE, "rnnt_stream_open: %d buffered frames (consume or discard them first)", ctx->frames_buffered);
+    hipStream_t s = (hipStream_t)stream;
+    int rc;
+    if ((rc = pool_alloc(ctx))) return rc;
+    hipLaunchKernelGGL(stream_slot_reset, dim3(grid_for((long long)L * ctx->cap * D)), dim3(256), 0, s, ctx->gring, ctx->xring, ctx->glu0,
+                       ctx->cfg.max_streams, ctx->cap, slot, ctx->h, ctx->c, ctx->sel, ctx->key, ctx->fidx, ctx->nsym, ctx->count, ctx->tok,
+                       ctx->cfg.blank_id);
+    LAUNCHCHK("stream_slot_reset");
+    pool_enter(ctx);
+    ctx->slot_pos[slot] = rnnt_ctx::SlotPos{0, 0, 0};
+    return RNNT_OK;
+}
+
+int rnnt_pool_chunk(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, const float* fbank_dev, int32_t T, const int32_t* offsets_host,
+                    const int32_t* required_host, int32_t greedy, int32_t* frames_out, void* stream) {
+    if (!ctx || !slots_host || !fbank_dev || !offsets_host || !required_host) return fail(ctx, RNNT_ERR_ARG, "rnnt_pool_chunk: null argument");
+    if (!ctx->finalized || ctx->n_streams < 1) return fail(ctx, RNNT_ERR_STATE, "rnnt_pool_chunk: no weights / no streams");
+    if (greedy && !ctx->use_persistent) return fail(ctx, RNNT_ERR_STATE, "rnnt_pool_chunk: the greedy decode of a pool call needs the resident decoder");
+    if (ctx->frames_buffered != 0)
+        return fail(ctx, RNNT_ERR_STATE, "rnnt_pool_chunk: %d buffered frames of an earlier call (rnnt_frames_discard / rnnt_frames_consume first)", ctx->frames_buffered);
+    const int n = n_active;
+    if (n < 1 || n > ctx->n_streams) return fail(ctx, RNNT_ERR_ARG, "rnnt_pool_chunk: %d active slots of %d", n, ctx->n_streams);
+    if (T < 7 || T > ctx->cfg.max_chunk_frames) return fail(ctx, RNNT_ERR_SHAPE, "chunk of %d frames outside [7, %d]", T, ctx->cfg.max_chunk_frames);
+    const int tq = sub_len(T);
+    if (tq > ctx->fcap) return fail(ctx, RNNT_ERR_SHAPE, "encoder-frame buffer capacity %d exceeded", ctx->fcap);
+    // ---- validate every listed slot before anything changes: a wrong slot is a write into another caller's cache --------------------
+    auto pos_of = [&](int slot) { return ctx->pool_mode ? ctx->slot_pos[slot] : rnnt_ctx::SlotPos{ctx->cache_len, ctx->kv_start, ctx->conv_pos}; };
+    std::vector<char> seen((size_t)ctx->n_streams, 0);
+    std::vector<PoolRow> rows((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        const int slot = slots_host[i];
+        if (slot < 0 || slot >= ctx->n_streams) return fail(ctx, RNNT_ERR_ARG, "rnnt_pool_chunk: row %d: slot %d outside [0, %d)", i, slot, ctx->n_streams);
+        if (seen[slot]) return fail(ctx, RNNT_ERR_ARG, "rnnt_pool_chunk: slot %d listed twice", slot);
+        seen[slot] = 1;
+        const rnnt_ctx::SlotPos p = pos_of(slot);
+        PoolRow& r = rows[i];
+        r.slot = slot;
+        r.T2 = p.cache_len + tq;                           // attention_key_size (encoder.py:256)
+        r.kv_row0 = p.kv_start;
+        r.pos_start = offsets_host[i] - p.cache_len;       // encoder.py:257
+        r.ring_pos = p.conv_pos;
+        r.kv_w0 = p.kv_start + p.cache_len;
+        r.ring_w0 = p.conv_pos % ctx->cap;
+        r.zero = 0;
+        if (r.pos_start < 0 || r.pos_start + r.T2 > RNNT_PE_LEN)
+            return fail(ctx, RNNT_ERR_SHAPE, "slot %d: positional window [%d, %d) outside the 5000-entry table", slot, r.pos_start, r.pos_start + r.T2);
+        if (p.kv_start + r.T2 > ctx->tcap) return fail(ctx, RNNT_ERR_SHAPE, "slot %d: K/V cache capacity %d exceeded", slot, ctx->tcap);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    int rc;
+    if ((rc = pool_alloc(ctx))) return rc;
+    // ---- the call's table: one async copy, no synchronisation before the launches ---------------------------------------------------
+    HIPCHK(hipEventSynchronize(ctx->pool_ev));             // the previous call's copy has left the pinned buffer (normally long ago)
+    memcpy(ctx->pool_tab_host, rows.data(), (size_t)n * sizeof(PoolRow));
+    for (int i = 0; i < n; ++i) ctx->pool_tab_host[(size_t)n * POOL_ROW_INTS + i] = rows[i].slot;
+    HIPCHK(hipMemcpyAsync(ctx->pool_tab, ctx->pool_tab_host, (size_t)n * (POOL_ROW_INTS + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipEventRecord(ctx->pool_ev, s));
+    const PoolRow* rows_dev = reinterpret_cast<const PoolRow*>(ctx->pool_tab);
+    const int* slots_dev = ctx->pool_tab + (size_t)n * POOL_ROW_INTS;
+    pool_enter(ctx);
+    {
+        GemmCapScope cap_scope(ctx);
+        if ((rc = run_subsample(ctx, s, fbank_dev, n, T, T, nullptr, 1, ctx->y1, ctx->y2, ctx->x))) return rc;
+        for (int l = 0; l < L; ++l)
+            if ((rc = run_layer_pool(ctx, s, l, n, tq, rows_dev, rows.data()))) return rc;
+        // after_norm in place over the compact rows, then the joint's encoder projection into frames [0, t') of every active slot
+        if ((rc = launch_ln(ctx, s, LnP{ctx->x, ctx->after_g, ctx->after_b, ctx->x, n * tq, BIG, 0, 0LL, (long long)D}))) return rc;
+        GemmP g = plain_gemm(ctx->x, D, ctx->wenc, D, ctx->benc, ctx->encp, D, n * tq, D, D);
+        g.c_n = tq; g.c_s0 = (long long)ctx->fstride * D; g.c_r0 = 0; g.c_mod = BIG; g.c_s1 = D;
+        g.c_tab = ctx->pool_tab; g.c_tab_col = POOL_COL_ZERO;
+        if ((rc = launch_gemm(ctx, s, 0, &g, 1, TAG_ENC_PROJ))) return rc;
+    }
+    // ---- the reference's cache bookkeeping, per slot (encoder.py:259-264,288) ------------------------------------------------------------
+    for (int i = 0; i < n; ++i) {
+        rnnt_ctx::SlotPos& p = ctx->slot_pos[rows[i].slot];
+        const int T2 = rows[i].T2, req = required_host[i];
+        const int next_start = req < 0 ? 0 : (req == 0 ? T2 : (T2 - req > 0 ? T2 - req : 0));
+        p.kv_start += next_start;
+        p.cache_len = T2 - next_start;
+        if (p.cache_len == 0) p.kv_start = 0;
+        p.conv_pos += tq;
+    }
+    if (frames_out) *frames_out = tq;
+    if (!greedy) {   // frames [0, t') of the active slots stay buffered for rnnt_get_enc_frames until rnnt_frames_discard
+        hipLaunchKernelGGL(pool_scatter_frames, dim3(grid_for((long long)n * tq * (D / 4))), dim3(256), 0, s, ctx->x, ctx->encbuf, rows_dev, n, tq,
+                           (long long)ctx->fstride * D);
+        LAUNCHCHK("pool_scatter_frames");
+        ctx->frames_buffered = tq;
+        ctx->frames_decoded = 0;
+        return RNNT_OK;
+    }
+    // ---- greedy decode of the new frames of exactly the active slots; grids sized by the rows of the call ----------------------------
+    const int per = pool_multi_ok(ctx) ? (ctx->n_cus / GM_PARTS > 0 ? ctx->n_cus / GM_PARTS : 1) : n;   // greedy_multi: the whole grid resident
+    for (int i0 = 0; i0 < n; i0 += per) {
+        const int cnt = n - i0 < per ? n - i0 : per;
+        if ((rc = init_decoder_ctrl(ctx, s, tq))) return rc;
+        if ((rc = launch_persistent_decoder(ctx, s, tq, 0, nullptr, slots_dev + i0, cnt))) return rc;
+        if ((rc = finish_persistent_decoder(ctx, s))) return rc;   // synchronises
+    }
+    return RNNT_OK;
+}
+
+int rnnt_stream_get_tokens(rnnt_ctx* ctx, int32_t slot, int32_t from, int32_t cap, int32_t* tokens_host, int32_t* n_out, void* stream) {
+    if (!ctx) return RNNT_ERR_ARG;
+    if (slot < 0 || slot >= ctx->n_streams || from < 0 || cap < 0 || (cap > 0 && !tokens_host))
+        return fail(ctx, RNNT_ERR_ARG, "rnnt_stream_get_tokens: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipMemcpyAsync(ctx->pinned + 5, ctx->count + slot, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    int count = ctx->pinned[5];
+    if (count > ctx->cfg.max_tokens) count = ctx->cfg.max_tokens;   // the counter runs on when the buffer is full
+    const int avail = count > from ? count - from : 0;
+    if (n_out) *n_out = avail;
+    const int ncopy = avail < cap ? avail : cap;
+    if (ncopy > 0) {
+        HIPCHK(hipMemcpyAsync(tokens_host, ctx->tokens + (size_t)slot * ctx->cfg.max_tokens + from, (size_t)ncopy * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    return RNNT_OK;
+}

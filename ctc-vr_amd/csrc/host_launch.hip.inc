@@ -175,6 +175,9 @@ int launch_gemm(rnnt_ctx* ctx, hipStream_t s, int /*unused*/, const GemmP* gs, i
         if (gs[i].K != K) return fail(ctx, RNNT_ERR_SHAPE, "grouped gemm needs one K");
     const int epi0 = gs[0].epi;
     const bool dense_epi = epi0 != EPI_LSTM && epi0 != EPI_ARGMAX;
+    // Stream pool: the kernel and tile are chosen as for ONE stream's rows (never the large-M forms), so that a slot's sums do not
+    // depend on how many neighbours share the call.  The grids still cover all maxM rows.
+    const int selM = ctx->gemm_m_cap && maxM > ctx->gemm_m_cap ? ctx->gemm_m_cap : maxM;
     if (ctx->numerics != RNNT_NUM_F32 && dense_epi && K % 32 == 0 && all_planes(gb, ng)) {
         const int nm = ctx->numerics;
         // Tile choice measured with tools/gemm_check.hip at M = 12032 (bf16x3): 64x64 tiles beat 128x128 / 128x64 on every shape
@@ -185,13 +188,13 @@ int launch_gemm(rnnt_ctx* ctx, hipStream_t s, int /*unused*/, const GemmP* gs, i
         // override altogether (gemm_bf_body static_asserts MT <= 2): the default path never dispatched them (conv2 of a whole
         // batch runs gemm_bw), and a kernel with an unexplained race does not stay in the product.
         if (gs[0].a_tanh) launch_gemm_bf<2, 2, true>(nm, s, gb, maxM, maxN, ng);
-        else if (maxM >= 1024 && maxN >= 256) launch_gemm_bf<2, 2>(nm, s, gb, maxM, maxN, ng);
-        else if (maxN >= 512 || maxM >= 1024) launch_gemm_bf<1, 2>(nm, s, gb, maxM, maxN, ng);
+        else if (selM >= 1024 && maxN >= 256) launch_gemm_bf<2, 2>(nm, s, gb, maxM, maxN, ng);
+        else if (maxN >= 512 || selM >= 1024) launch_gemm_bf<1, 2>(nm, s, gb, maxM, maxN, ng);
         else launch_gemm_bf<1, 1>(nm, s, gb, maxM, maxN, ng);
         LAUNCHCHK("gemm_bf");
         return RNNT_OK;
     }
-    if (maxM >= 1024 && K % 32 == 0 && dense_epi) {
+    if (selM >= 1024 && K % 32 == 0 && dense_epi) {
         // large M (full-context encoder, batched subsampling, joint lattice): LDS-tiled kernel, no split-K
         if (gs[0].a_tanh) launch_gemm_ns<2, 2, true>(s, gb, maxM, maxN, ng);
         else if (maxN >= 512) launch_gemm_ns<2, 2>(s, gb, maxM, maxN, ng);
@@ -351,7 +354,7 @@ int run_subsample(rnnt_ctx* ctx, hipStream_t s, const float* fbank, int B, int T
         if (!y1) return fail(ctx, RNNT_ERR_STATE, "run_subsample: no conv1 slab");
         ProfScope prof(ctx, s, tag1);
         static const int c1_rows = getenv("RNNT_CONV1_ROWS") ? atoi(getenv("RNNT_CONV1_ROWS")) : 1;
-        if (c1_rows && (long long)VB * ((t1 + C1_TB - 1) / C1_TB) >= 256)   // enough (stream, 8-row block) pairs to fill the chip: coalesced row stores
+        if (c1_rows && !ctx->gemm_m_cap && (long long)VB * ((t1 + C1_TB - 1) / C1_TB) >= 256)   // enough (stream, 8-row block) pairs to fill the chip: coalesced row stores
             hipLaunchKernelGGL(conv1_relu_rows, dim3(VB, (t1 + C1_TB - 1) / C1_TB), dim3(256), 0, s, fbank, ctx->conv1_wt, ctx->conv1_b, y1, B, Tstride, t1,
                                starts_dev, nc, out_cn > 0 ? 1 : 0);
         else
@@ -383,7 +386,7 @@ int run_subsample(rnnt_ctx* ctx, hipStream_t s, const float* fbank, int B, int T
         }
 #undef BWC_LAUNCH
         LAUNCHCHK("gemm_bw_c1");
-    } else if (ctx->numerics != RNNT_NUM_F32 && conv2_bw && ctx->conv2_wp && g.M >= 32768) {
+    } else if (ctx->numerics != RNNT_NUM_F32 && conv2_bw && ctx->conv2_wp && g.M >= 32768 && !ctx->gemm_m_cap) {
         // whole-utterance slab: 128 x 256 tiles, weights streamed from L2 in fragment order, A rows four k-steps ahead (gemm_bw)
         ProfScope prof(ctx, s, tag2);
         if ((rc = prepare_gemm(ctx, g))) return rc;
@@ -400,7 +403,7 @@ int run_subsample(rnnt_ctx* ctx, hipStream_t s, const float* fbank, int B, int T
         LAUNCHCHK("gemm_bw");
     } else if (ctx->numerics != RNNT_NUM_F32) {
         if ((rc = launch_gemm(ctx, s, 0, &g, 1, tag2))) return rc;
-    } else if (conv2_lds && g.M >= 2048) {   // big M: LDS-tiled 64x64 tiles (full-line operand staging); N = 256 -> 4 column tiles
+    } else if (conv2_lds && g.M >= 2048 && !ctx->gemm_m_cap) {   // big M: LDS-tiled 64x64 tiles (full-line operand staging); N = 256 -> 4 column tiles
         ProfScope prof(ctx, s, tag2);
         GemmBatch gb;
         memset(&gb, 0, sizeof(gb));
@@ -660,24 +663,28 @@ int greedy_drain(rnnt_ctx* ctx, hipStream_t s, int n_frames, int done_steps) {
 bool coop_decoder_ok(const rnnt_ctx* ctx) {
     return ctx->use_coop && ctx->n_streams <= 64 && ctx->cfg.vocab_size <= FLOW_VOCAB;
 }
+bool pool_multi_ok(const rnnt_ctx* ctx) {   // multi_decoder_ok of a context with ONE stream
+    return ctx->use_multi && !ctx->use_coop && GM_PARTS <= ctx->n_cus && (ctx->cfg.vocab_size + GM_PARTS - 1) / GM_PARTS <= 128;
+}
 bool multi_decoder_ok(const rnnt_ctx* ctx) {
     return ctx->use_multi && !ctx->use_coop && GM_PARTS * ctx->n_streams <= ctx->n_cus && (ctx->cfg.vocab_size + GM_PARTS - 1) / GM_PARTS <= 128;
 }
-int launch_multi_decoder(rnnt_ctx* ctx, hipStream_t s, int n_total, int n_steps_override, const int* nlim) {
+// slots != null (stream pool): n_rows stream groups, group i decoding stream slots[i] (device array) over its frames [0, n_total).
+int launch_multi_decoder(rnnt_ctx* ctx, hipStream_t s, int n_total, int n_steps_override, const int* nlim, const int* slots = nullptr, int n_rows = 0) {
     DecMP d;
     memset(&d, 0, sizeof(d));
     d.whh = ctx->whh_il; d.egate = ctx->egate; d.wjc = ctx->wjc; d.bjc = ctx->bjc; d.wout = ctx->wout; d.bout = ctx->bout;
     d.encp = ctx->encp; d.h = ctx->h; d.c = ctx->c; d.sel = ctx->sel; d.tok = ctx->tok; d.fidx = ctx->fidx; d.nsym = ctx->nsym;
     d.count = ctx->count; d.tokens = ctx->tokens; d.ctrl = ctx->dec_ctrl; d.x1 = ctx->gm_x1; d.xa = ctx->gm_xa;
     d.fstride_f = (long long)ctx->fstride * D; d.bstride = (long long)ctx->cfg.max_streams * D;
-    d.B = ctx->n_streams; d.vocab = ctx->cfg.vocab_size; d.blank = ctx->cfg.blank_id;
+    d.B = slots ? n_rows : ctx->n_streams; d.vocab = ctx->cfg.vocab_size; d.blank = ctx->cfg.blank_id;
     d.n_steps = n_steps_override > 0 ? n_steps_override : ctx->cfg.n_steps;
-    d.max_tokens = ctx->cfg.max_tokens; d.n_total = n_total; d.nlim = nlim;
+    d.max_tokens = ctx->cfg.max_tokens; d.n_total = n_total; d.nlim = nlim; d.slots = slots;
     d.timeout_ticks = 500000000ll;
     d.rows_per = (ctx->cfg.vocab_size + GM_PARTS - 1) / GM_PARTS;
     static const bool gdbg = getenv("RNNT_GM_DBG") != nullptr;
     d.dbg = gdbg ? reinterpret_cast<long long*>(ctx->flow_buf + FLOW_WORDS) : nullptr;
-    const int B = ctx->n_streams;
+    const int B = d.B;
     // (The grid on a high- or low-priority side stream, ordered by events, was tried for the two-batches-in-flight mode: 6.79 and
     // 6.33 ms per batch against 6.10-6.19 on the caller's stream.)
     // tags restart at 1 every launch: no word of an earlier launch may survive
@@ -690,9 +697,12 @@ int launch_multi_decoder(rnnt_ctx* ctx, hipStream_t s, int n_total, int n_steps_
     return RNNT_OK;
 }
 
-int launch_persistent_decoder(rnnt_ctx* ctx, hipStream_t s, int n_total, int n_steps_override = 0, const int* nlim = nullptr) {
-    if (multi_decoder_ok(ctx)) return launch_multi_decoder(ctx, s, n_total, n_steps_override, nlim);
-    if (coop_decoder_ok(ctx) && !nlim && !n_steps_override) {
+int launch_persistent_decoder(rnnt_ctx* ctx, hipStream_t s, int n_total, int n_steps_override = 0, const int* nlim = nullptr,
+                              const int* slots = nullptr, int n_rows = 0) {
+    // stream pool: the decoder a context holding only that stream would run (greedy_multi wherever the context allows it at all; the
+    // caller launches at most n_cus / GM_PARTS rows at a time so that the grid is resident at once)
+    if (slots ? pool_multi_ok(ctx) : multi_decoder_ok(ctx)) return launch_multi_decoder(ctx, s, n_total, n_steps_override, nlim, slots, n_rows);
+    if (coop_decoder_ok(ctx) && !nlim && !n_steps_override && !slots) {
         // cooperative decoder: 4 x 16 resident workgroups, weights stationary in LDS, tagged-word exchanges
         FlowP c;
         memset(&c, 0, sizeof(c));
@@ -720,8 +730,9 @@ int launch_persistent_decoder(rnnt_ctx* ctx, hipStream_t s, int n_total, int n_s
     d.max_tokens = ctx->cfg.max_tokens; d.n_total = n_total;
     if (n_steps_override > 0) d.n_steps = n_steps_override;
     d.nlim = nlim;
+    if (slots) { d.slots = slots; d.B = n_rows; }
     d.timeout_ticks = 500000000ll;   // 5 s of the 100 MHz real-time counter: every wait in the kernel is bounded
-    const int B = ctx->n_streams;
+    const int B = d.B;
     static const int kf = getenv("RNNT_DEC_KF") ? atoi(getenv("RNNT_DEC_KF")) : 4;   // frames per vocabulary pass
     if (kf == 1) hipLaunchKernelGGL(greedy_stream<1>, dim3(B), dim3(512), 0, s, d);
     else if (kf == 2) hipLaunchKernelGGL(greedy_stream<2>, dim3(B), dim3(512), 0, s, d);

@@ -107,6 +107,17 @@ struct rnnt_ctx {
     int cache_len = 0, kv_start = 0, conv_pos = 0;
     int frames_buffered = 0, frames_decoded = 0;
     int64_t launches = 0, greedy_steps = 0;
+    // stream pool (api_pool.hip.inc): once rnnt_stream_open or rnnt_pool_chunk has run, every slot has its own position and the three
+    // scalars above are dead until the next rnnt_streams_reset.  Positions are host integers advanced by the reference's bookkeeping
+    // (encoder.py:254-264) and mirrored per call into ONE device table: n PoolRow entries followed by the n slot indices the decoder
+    // reads, written by one async copy from the pinned host copy (pool_ev: that copy has left the host buffer).
+    struct SlotPos { int cache_len, kv_start, conv_pos; };
+    std::vector<SlotPos> slot_pos;
+    bool pool_mode = false;
+    int* pool_tab = nullptr;                   // device: [max_streams] PoolRow + [max_streams] int
+    int* pool_tab_host = nullptr;              // pinned
+    hipEvent_t pool_ev = nullptr;
+    int gemm_m_cap = 0;                        // > 0 during a pool call: GEMM kernels / tiles are chosen as for at most this many rows
     // wavefront (whole-utterance) path: per-chunk x rows, per-layer scratch, subsampling slabs, descriptor tables
     float *wf_x = nullptr, *wf_h = nullptr, *wf_q = nullptr, *wf_a = nullptr, *wf_d = nullptr, *wf_y1 = nullptr, *wf_y2 = nullptr;
     int wf_slab = 0;
@@ -191,4 +202,5 @@ extern "C" {
 #include "api_beam.hip.inc"
 #include "api_ops.hip.inc"
 #include "api_state.hip.inc"
+#include "api_pool.hip.inc"
 }  // extern "C"

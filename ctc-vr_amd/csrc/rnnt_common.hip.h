@@ -48,6 +48,25 @@ enum {
     EPI_DB = 9         // C = 10 * log10(max(acc + bias, 1e-10))   (AmplitudeToDB, power spectrogram)
 };
 
+// One active row of a stream-pool call (rnnt_pool_chunk): the slot whose storage the row's frames belong to and that slot's own
+// positions.  The host mirrors its per-slot bookkeeping into one table of these per call; kernels read it through the slot
+// indirection instead of taking one position for the whole batch.  kv_w0 / ring_w0 / zero are the row bases of the three C maps
+// that append to per-slot storage (GemmP::c_tab): K/V rows, the post-GLU ring, the encoder-frame buffer.
+struct PoolRow {
+    int slot;        // stream index in [0, n_streams)
+    int T2;          // keys of this chunk: cache_len + t' (encoder.py:256)
+    int kv_row0;     // K/V row of key 0
+    int pos_start;   // positional-table row of key 0 (encoder.py:257)
+    int ring_pos;    // conv-ring frame index of the chunk's first frame
+    int kv_w0;       // kv_row0 + cache_len: K/V row of the chunk's first new frame
+    int ring_w0;     // ring_pos % cap
+    int zero;        // frame-buffer row of the chunk's first frame (pool calls start every slot's buffer at 0)
+};
+#define POOL_ROW_INTS 8
+#define POOL_COL_KV_W0 5
+#define POOL_COL_RING_W0 6
+#define POOL_COL_ZERO 7
+
 struct GemmP {
     const float* A;
     const float* W;
@@ -98,6 +117,10 @@ struct GemmP {
     // 16-bit operand planes of W (rnnt_gemm_bf.hip.h): same element index as W inside the weight blob; null = exact f32 only
     const unsigned short* Wh;
     const unsigned short* Wl;
+    // stream pool: row group q = m / c_n is active row q of the call; its C rows go to slot c_tab[q].slot's storage at the row base
+    // in column c_tab_col of its PoolRow: off(m,n) = slot*c_s0 + (((m % c_n) + base) % c_mod)*c_s1 + n.  null = the plain map above.
+    const int* c_tab;
+    int c_tab_col;
     unsigned a_n1_magic, a_n2_magic, a_seg_magic, c_n_magic, x_n_magic;
     int a_n1_shift, a_n2_shift, a_seg_shift, c_n_shift, x_n_shift;   // q = umulhi(n, magic) >> shift, exact for n < 2^31
 };

@@ -105,6 +105,7 @@ struct DecP {
     int B, vocab, blank, n_steps, max_tokens, n_total;
     long long timeout_ticks;   // s_memrealtime ticks (100 MHz)
     const int* nlim;           // optional per-stream frame count (offline search over padded batches); null = n_total for all
+    const int* slots;          // stream pool: workgroup i decodes stream slots[i] over its frames [0, n_total), B = active rows; null = stream i
 };
 
 template <int SPW, int NTH, int U = 2, typename Epi>
@@ -170,13 +171,13 @@ __global__ __launch_bounds__(512) void greedy_stream(DecP p) {
     __shared__ int redi[NTH / 16][KF];
     __shared__ int s_ctl[4];
     const int tid = threadIdx.x;
-    const int b = blockIdx.x;
-    if (b >= p.B) return;
+    if ((int)blockIdx.x >= p.B) return;
+    const int b = p.slots ? ldgi(p.slots + blockIdx.x) : (int)blockIdx.x;   // the stream whose state this workgroup owns
     {
         const long long off = (long long)(ldgi(p.sel + b) & 1) * p.bstride + (long long)b * RNNT_D;
         if (tid < RNNT_D) { hs[0][tid] = ldg1(p.h + off + tid); cs[tid] = ldg1(p.c + off + tid); }
     }
-    int tok = ldgi(p.tok + b), fidx = ldgi(p.fidx + b), nsym = ldgi(p.nsym + b), count = ldgi(p.count + b);   // uniform
+    int tok = ldgi(p.tok + b), fidx = p.slots ? 0 : ldgi(p.fidx + b), nsym = ldgi(p.nsym + b), count = ldgi(p.count + b);   // uniform
     const int n_total = p.nlim ? min(p.n_total, ldgi(p.nlim + b)) : p.n_total;
     int evals = 0, seen_ready = 0;
     bool dirty = true;
@@ -299,7 +300,7 @@ __global__ __launch_bounds__(512) void greedy_stream(DecP p) {
         stg1(p.c + (long long)b * RNNT_D + tid, cs[tid]);
     }
     if (tid == 0) {
-        p.sel[b] = 0; p.tok[b] = tok; p.fidx[b] = fidx; p.nsym[b] = nsym; p.count[b] = count;
+        p.sel[b] = 0; p.tok[b] = tok; p.fidx[b] = p.slots ? 0 : fidx; p.nsym[b] = nsym; p.count[b] = count;   // pool: frames consumed
         atomicAdd(p.ctrl + 2, evals);
     }
 }
@@ -731,6 +732,7 @@ struct DecMP {
     int B, vocab, blank, n_steps, max_tokens, n_total;
     long long timeout_ticks;
     const int* nlim;
+    const int* slots;            // stream pool: stream group i (mailboxes i) decodes stream slots[i] over its frames [0, n_total); null = stream i
     int rows_per;                // ceil(vocab / 4): vocabulary rows of a part (<= 128), resident in LDS
     long long* dbg;              // optional [16]: phase timers of workgroup (stream 0, part 0), 100 MHz ticks (RNNT_GM_DBG=1)
 };
@@ -781,8 +783,9 @@ __global__ __launch_bounds__(512) void greedy_multi(DecMP p) {
     static_assert(KF == 4, "thread (frame, row) mapping of the logit finish assumes KF * 128 == 512");
     const int tid0 = threadIdx.x;
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int b = (slot >> 2) * 8 + xcd, pw = slot & 3;   // the four parts of a stream share blockIdx % 8 (one XCD: speed hint only)
-    if (b >= p.B) return;
+    const int bi = (slot >> 2) * 8 + xcd, pw = slot & 3;  // the four parts of a stream share blockIdx % 8 (one XCD: speed hint only)
+    if (bi >= p.B) return;
+    const int b = p.slots ? ldgi(p.slots + bi) : bi;      // the stream whose state this group owns (stream pool: a slot); mailboxes stay at bi
     // ---- resident weights ------------------------------------------------------------------------------------------------
     const int cell_unit = 64 * pw + (tid0 >> 3);          // threads 0, 8, ... own the 64 hidden units of this part
     const bool cell = (tid0 & 7) == 0;
@@ -821,11 +824,11 @@ __global__ __launch_bounds__(512) void greedy_multi(DecMP p) {
     cc2 = cc;
     if (tid == 0) *s_bad = 0;
     }
-    int tok = ldgi(p.tok + b), fidx = ldgi(p.fidx + b), nsym = ldgi(p.nsym + b), count = ldgi(p.count + b);
+    int tok = ldgi(p.tok + b), fidx = p.slots ? 0 : ldgi(p.fidx + b), nsym = ldgi(p.nsym + b), count = ldgi(p.count + b);
     const int n_total = p.nlim ? min(p.n_total, ldgi(p.nlim + b)) : p.n_total;
     const float* encp = p.encp + (long long)b * p.fstride_f;
-    unsigned long long* x1b = p.x1 + (long long)b * GM_PARTS * GM_X1;
-    unsigned long long* xab = p.xa + (long long)b * GM_PARTS * 2 * KF;
+    unsigned long long* x1b = p.x1 + (long long)bi * GM_PARTS * GM_X1;
+    unsigned long long* xab = p.xa + (long long)bi * GM_PARTS * 2 * KF;
     const long long x1par = (long long)p.B * GM_PARTS * GM_X1, xapar = (long long)p.B * GM_PARTS * 2 * KF;
     unsigned ev1 = 0, ev3 = 0;
     int evals = 0, seen_ready = 0;
@@ -1089,7 +1092,7 @@ __global__ __launch_bounds__(512) void greedy_multi(DecMP p) {
     if (pw == 0 && tid0 < RNNT_D) stg1(p.h + (long long)b * RNNT_D + tid0, hs[tid0]);
     if (cell) stg1(p.c + (long long)b * RNNT_D + cell_unit, cc);
     if (pw == 0 && tid0 == 0) {
-        p.sel[b] = 0; p.tok[b] = tok; p.fidx[b] = fidx; p.nsym[b] = nsym; p.count[b] = count;
+        p.sel[b] = 0; p.tok[b] = tok; p.fidx[b] = p.slots ? 0 : fidx; p.nsym[b] = nsym; p.count[b] = count;   // pool: frames consumed
         atomicAdd(p.ctrl + 2, evals);
     }
     (void)bad;

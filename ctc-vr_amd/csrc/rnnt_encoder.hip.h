@@ -138,7 +138,7 @@ struct AttnP {
 // NQ = query slots per wave: a workgroup covers 4*NQ queries (wave w owns queries w, w+4, ...).  Streaming chunks
 // have t' = 3..5 new frames, so NQ = 1 or 2 avoids computing 16 query slots for 3 queries.
 template <int NQ>
-__device__ __forceinline__ void rel_attention_body(const AttnP& P) {
+__device__ __forceinline__ void rel_attention_body(const AttnP& P, int bh) {
     const float* __restrict__ q = P.q;
     const float* __restrict__ kc = P.kc;
     const float* __restrict__ vc = P.vc;
@@ -157,7 +157,7 @@ __device__ __forceinline__ void rel_attention_body(const AttnP& P) {
     __shared__ __attribute__((aligned(16))) float Qu[QB * RNNT_DK];
     __shared__ __attribute__((aligned(16))) float Qv[QB * RNNT_DK];
     __shared__ float Pm[QB * ATT_TK];
-    const int b = blockIdx.x / RNNT_H, h = blockIdx.x % RNNT_H;
+    const int b = bh / RNNT_H, h = bh % RNNT_H;
     const int q0 = blockIdx.y * QB;
     const int nq = min(QB, tq - q0);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -253,11 +253,33 @@ __device__ __forceinline__ void rel_attention_body(const AttnP& P) {
     }
 }
 template <int NQ>
-__global__ __launch_bounds__(256) void rel_attention(AttnP p) { rel_attention_body<NQ>(p); }
+__global__ __launch_bounds__(256) void rel_attention(AttnP p) { rel_attention_body<NQ>(p, blockIdx.x); }
 template <int NQ>
 __global__ __launch_bounds__(256) void rel_attention_tab(const AttnP* __restrict__ tab) {
     const AttnP p = tab[blockIdx.z];
-    rel_attention_body<NQ>(p);
+    rel_attention_body<NQ>(p, blockIdx.x);
+}
+// Stream pool (rnnt_pool_chunk): workgroup (active row i, head) takes its key count, K/V row, positional window and slot from
+// row i of the call's PoolRow table.  The index is blockIdx-derived, so the row is wave-uniform and read with scalar loads into
+// SGPRs.  P carries the layer's pointers and t'; q / out are the call's compact rows [n_active * t'], K / V the slot's own rows.
+// The body then runs exactly as for a context that holds only this stream (b = 0): every loop bound is the slot's own T2, so the
+// order of every sum is the order rel_attention uses for that T2, whatever the other rows of the launch hold.
+// `sel`: the rows this launch serves -- 1: those within the streaming kernel's key range (T2 <= 4096, attn_stream_ok), 0: those beyond
+// it, 2: all.  The per-chunk API picks the kernel by the stream's own T2; a workgroup whose row belongs to the other launch exits.
+__device__ __forceinline__ bool pool_attn_desc(AttnP& P, const PoolRow* __restrict__ rows, int i, int sel) {
+    const PoolRow r = rows[i];
+    if (sel != 2 && (r.T2 <= 4096 ? 1 : 0) != sel) return false;
+    P.q += (long long)i * P.tq * RNNT_D;
+    P.out += (long long)i * P.tq * RNNT_D;
+    P.kc += (long long)r.slot * P.kv_stride * RNNT_D;
+    P.vc += (long long)r.slot * P.kv_stride * RNNT_D;
+    P.T2 = r.T2; P.kv_start = r.kv_row0; P.pos_start = r.pos_start;
+    return true;
+}
+template <int NQ>
+__global__ __launch_bounds__(256) void rel_attention_pool(AttnP p, const PoolRow* __restrict__ rows, int sel) {
+    if (!pool_attn_desc(p, rows, blockIdx.x / RNNT_H, sel)) return;
+    rel_attention_body<NQ>(p, blockIdx.x % RNNT_H);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -388,6 +410,13 @@ __global__ __launch_bounds__(256) void rel_attention_stream(AttnP p, int t2cap) 
     extern __shared__ __attribute__((aligned(16))) float att_smem[];
     rel_attention_stream_body(p, att_smem, t2cap, blockIdx.x);
 }
+// Stream pool form (see rel_attention_pool): t2cap sizes the LDS score rows for the deepest active slot of the launch; a workgroup
+// only touches the first T2 entries of its own rows.
+__global__ __launch_bounds__(256) void rel_attention_stream_pool(AttnP p, const PoolRow* __restrict__ rows, int t2cap) {
+    extern __shared__ __attribute__((aligned(16))) float att_smem[];
+    if (!pool_attn_desc(p, rows, blockIdx.x / RNNT_H, 1)) return;
+    rel_attention_stream_body(p, att_smem, t2cap, blockIdx.x % RNNT_H);
+}
 // Table form, 1-D grid of ceil(bh_total / 8) * 8 * n_desc workgroups dealt round-robin over the 8 XCDs: XCD x takes the
 // (stream, head) pairs x, x + 8, ... and runs ALL descriptors of a pair back to back.  With two chunks of a layer per
 // stage the second chunk reads the K/V rows the first one has just pulled into that XCD's L2 (its own three rows more),
@@ -423,7 +452,10 @@ struct DwP {
     float* xring;
     int B, tq, cap, pos;
 };
-__device__ __forceinline__ void dwconv_body(const DwP& P) {
+// POOL (rnnt_pool_chunk): row group b of out / xres is active row b of the call; its rings are slot rows[b].slot's and its ring
+// position rows[b].ring_pos.  Same taps in the same order as the lock-step form.
+template <bool POOL>
+__device__ __forceinline__ void dwconv_body(const DwP& P, const PoolRow* __restrict__ rows) {
     const float* __restrict__ g = P.g;
     const float* __restrict__ wdw_t = P.wdw_t;
     const float* __restrict__ bdw = P.bdw;
@@ -432,12 +464,15 @@ __device__ __forceinline__ void dwconv_body(const DwP& P) {
     float* __restrict__ out = P.out;
     const float* __restrict__ xres = P.xres;
     float* __restrict__ xring = P.xring;
-    const int B = P.B, tq = P.tq, cap = P.cap, pos = P.pos;
+    const int B = P.B, tq = P.tq, cap = P.cap;
+    int pos = P.pos;
     const long long n = (long long)B * tq * RNNT_D;
     for (long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x; id < n; id += (long long)gridDim.x * blockDim.x) {
         const int c = (int)(id & 255);
         const int m = (int)(id >> 8);
-        const int b = m / tq, r = m % tq;
+        int b = m / tq;
+        const int r = m % tq;
+        if (POOL) { pos = ldgi(&rows[b].ring_pos); b = ldgi(&rows[b].slot); }
         const float* gb = g + (long long)b * cap * RNNT_D + c;
         float acc = ldg1(bdw + c);
         int ridx = (pos + r - RNNT_LORDER + cap * 64) % cap;   // ring row of the oldest tap (operand kept positive)
@@ -452,10 +487,11 @@ __device__ __forceinline__ void dwconv_body(const DwP& P) {
         if (xring) stg1(xring + ((long long)b * cap + (pos + r) % cap) * RNNT_D + c, ldg1(xres + id));
     }
 }
-__global__ void dwconv_bn_silu(DwP p) { dwconv_body(p); }
+__global__ void dwconv_bn_silu(DwP p) { dwconv_body<false>(p, nullptr); }
+__global__ void dwconv_bn_silu_pool(DwP p, const PoolRow* __restrict__ rows) { dwconv_body<true>(p, rows); }
 __global__ void dwconv_bn_silu_tab(const DwP* __restrict__ tab) {
     const DwP p = tab[blockIdx.z];
-    dwconv_body(p);
+    dwconv_body<false>(p, nullptr);
 }
 
 // fill the 30 left-context rows of a fresh stream: g ring <- GLU(b_pw1) (zero input through the
@@ -468,5 +504,36 @@ __global__ void conv_ring_init(float* __restrict__ g, float* __restrict__ xring,
         const int l = (int)(id / ((long long)B * cap * RNNT_D));
         g[id] = glu0[l * RNNT_D + c];
         xring[id] = 0.f;
+    }
+}
+
+// rnnt_stream_open: the state rnnt_streams_reset gives every stream, for ONE slot.  Rings of all 12 layers (post-GLU ring <-
+// GLU(b_pw1), conv-input ring <- 0), both LSTM state buffers <- 0, committed buffer 0, last token = blank, token count 0, frame
+// index 0.  The K/V rows need no clearing: the slot's cache length is 0 on the host.  Touches no other slot's storage.
+__global__ void stream_slot_reset(float* __restrict__ g, float* __restrict__ xring, const float* __restrict__ glu0 /*[L][256]*/, int B, int cap, int slot,
+                                  float* __restrict__ h, float* __restrict__ c, int* sel, unsigned long long* key, int* fidx, int* nsym, int* count, int* tok, int blank) {
+    const long long per = (long long)cap * RNNT_D, n = (long long)RNNT_L * per;
+    for (long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x; id < n; id += (long long)gridDim.x * blockDim.x) {
+        const int l = (int)(id / per);
+        const long long off = ((long long)l * B + slot) * per + (id - (long long)l * per);
+        g[off] = glu0[l * RNNT_D + (int)(id & 255)];
+        xring[off] = 0.f;
+        if (id < 2 * RNNT_D) {   // [2][B][256]: buffer id / 256, unit id % 256
+            const long long so = (id >> 8) * (long long)B * RNNT_D + (long long)slot * RNNT_D + (id & 255);
+            h[so] = 0.f; c[so] = 0.f;
+        }
+        if (id == 0) { sel[slot] = 0; key[slot] = 0ull; fidx[slot] = 0; nsym[slot] = 0; count[slot] = 0; tok[slot] = blank; }
+    }
+}
+// rnnt_pool_chunk with greedy == 0: the after_norm rows of the call (compact, [n_active * tq][256]) into frames [0, tq) of their
+// slots' rows of the encoder-frame buffer, for rnnt_get_enc_frames.
+__global__ void pool_scatter_frames(const float* __restrict__ src, float* __restrict__ dst, const PoolRow* __restrict__ rows, int n_active, int tq,
+                                    long long fstride_f) {
+    const long long n = (long long)n_active * tq * (RNNT_D / 4);
+    for (long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x; id < n; id += (long long)gridDim.x * blockDim.x) {
+        const int c4 = (int)(id & 63);
+        const int m = (int)(id >> 6);
+        const int i = m / tq, f = m - i * tq;
+        stg4(dst + (long long)ldgi(&rows[i].slot) * fstride_f + (long long)f * RNNT_D + c4 * 4, ldg4(src + (long long)m * RNNT_D + c4 * 4));
     }
 }

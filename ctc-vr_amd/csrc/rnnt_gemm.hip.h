@@ -32,6 +32,12 @@ __device__ __forceinline__ long long a_k_off(const GemmP& p, int kk) {
 __device__ __forceinline__ long long c_row_off(const GemmP& p, int m) {
     if (p.c_plain) return (long long)m * p.c_s1;
     const int q = fastdiv(m, p.c_n, p.c_n_magic, p.c_n_shift);
+    if (p.c_tab) {   // stream pool: the row group's slot and row base come from its PoolRow
+        const int* e = p.c_tab + (long long)q * POOL_ROW_INTS;
+        int r = m - q * p.c_n + ldgi(e + p.c_tab_col);
+        if (r >= p.c_mod) r -= p.c_mod;
+        return (long long)ldgi(e) * p.c_s0 + (long long)r * p.c_s1;
+    }
     int r = m - q * p.c_n + p.c_r0;
     if (r >= p.c_mod) r -= p.c_mod;
     return (long long)q * p.c_s0 + (long long)r * p.c_s1;

@@ -43,6 +43,9 @@ SIGNATURES = {
     "rnnt_beam_merge_device": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rnnt_encode_ragged": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp]),
     "rnnt_frames_discard": (c_i32, [c_vp, c_vp]),
+    "rnnt_stream_open": (c_i32, [c_vp, c_i32, c_vp]),
+    "rnnt_pool_chunk": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32p, c_vp]),
+    "rnnt_stream_get_tokens": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32p, c_vp]),
     "rnnt_predictor_step": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "rnnt_joint": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "rnnt_encoder_full": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32p, c_vp]),
@@ -85,6 +88,7 @@ class RnntError(RuntimeError):
 
 # rnnt_status values of a refusal (call outside its supported range / sequence), as opposed to a HIP failure
 ERR_ARG, ERR_STATE = -1, -5
+ERR_SHAPE = -2
 
 
 def load(build_if_needed=True):
@@ -118,7 +122,8 @@ def _np_ptr(a):
 
 
 class RnntEngine:
-    """One context = one GPU = up to `max_streams` lock-stepped streams."""
+    """One context = one GPU = up to `max_streams` streams: lock-stepped (encoder_chunk / encoder_chunks / decode_ragged), or the
+    slots of a stream pool that open, advance and close independently (stream_open / pool_chunk / stream_tokens)."""
 
     def __init__(self, max_streams=1, max_chunk_frames=64, max_cache_frames=1024, max_enc_frames=1024, max_tokens=4096,
                  vocab_size=412, blank_id=5, n_steps=10, device=0, max_beam=0):
@@ -194,6 +199,32 @@ class RnntEngine:
         self._chk(self.lib.rnnt_encoder_chunk(self.ctx, fbank_ptr, chunk_frames, offset, required_cache_size, ctypes.byref(t), stream),
                   "rnnt_encoder_chunk")
         return t.value
+
+    # ---- stream pool ------------------------------------------------------------------------
+    def stream_open(self, slot, stream=None):
+        """rnnt_stream_open: reset ONE slot (fresh caches, zero predictor state, no tokens); no other slot is touched."""
+        self._chk(self.lib.rnnt_stream_open(self.ctx, slot, stream), "rnnt_stream_open")
+
+    def pool_chunk(self, slots, fbank_ptr, chunk_frames, offsets, required, greedy=True, stream=None):
+        """rnnt_pool_chunk: one chunk of `chunk_frames` frames for every listed slot, row i of the device tensor at fbank_ptr
+        ([len(slots), chunk_frames, 80]) belonging to slots[i] and encoded with (offsets[i], required[i]) at that slot's own
+        position; greedy: decode + consume the new frames of exactly those slots.  Returns t', the new encoder frames per slot."""
+        a, o, r = (np.ascontiguousarray(v, np.int32) for v in (slots, offsets, required))
+        assert a.ndim == 1 and a.size == o.size == r.size
+        t = c_i32(0)
+        self._chk(self.lib.rnnt_pool_chunk(self.ctx, a.size, _np_ptr(a), fbank_ptr, chunk_frames, _np_ptr(o), _np_ptr(r), 1 if greedy else 0,
+                                           ctypes.byref(t), stream), "rnnt_pool_chunk")
+        return t.value
+
+    def stream_tokens(self, slot, start=0, stream=None):
+        """rnnt_stream_get_tokens: tokens [start, count) of one slot."""
+        n = c_i32(0)
+        self._chk(self.lib.rnnt_stream_get_tokens(self.ctx, slot, start, 0, None, ctypes.byref(n), stream), "rnnt_stream_get_tokens")
+        if n.value == 0:
+            return []
+        out = np.zeros(n.value, np.int32)
+        self._chk(self.lib.rnnt_stream_get_tokens(self.ctx, slot, start, out.size, _np_ptr(out), ctypes.byref(n), stream), "rnnt_stream_get_tokens")
+        return out[:min(n.value, out.size)].tolist()
 
     def decode_ragged(self, fbank_ptr, total_frames, lens, chunk_frames, stream=None):
         """rnnt_decode_ragged: every stream over its own lens[b] frames (decode-script chunk loop), one call; returns encoder frames per stream."""

@@ -49,3 +49,36 @@ def evaluate_rtf(model, utterances, chunk_frames, beam_size=4, frame_shift_s=0.0
                 dur = c.shape[1] * frame_shift_s
                 rtfs.append(dt / dur if dur > 0 else 0.0)  # :55-59
     return {"greedy": _stats(g_rtf), "beam": _stats(b_rtf)}
+
+
+def evaluate_rtf_pool(pool, utterances, arrivals, chunk_frames, frame_shift_s=0.01):
+    """Pool mode: the same per-chunk real-time factor for callers that connect at staggered times and share one context
+    (StreamPool).  utterances: [T,80] float tensors on the pool's device; arrivals[k]: the step at which utterance k connects (it
+    waits while the pool is full).  Every step, each live caller delivers its next chunk (_chunks above), then ONE pool.step()
+    encodes and decodes all of them; a chunk's processing time is the wall time of the step that carried it (the caller waits for
+    that step to get its tokens, :50-53), divided by the chunk's own audio duration (:55-59).  Returns {'greedy': stats over all
+    chunks (:99-131), 'step_ms': stats of the step times, 'tokens': per utterance}."""
+    waiting = sorted(range(len(utterances)), key=lambda k: (arrivals[k], k))
+    live, rtfs, step_ms = {}, [], []
+    tokens = [None] * len(utterances)
+    t = 0
+    while waiting or live:
+        while waiting and arrivals[waiting[0]] <= t and len(live) < pool.n:
+            k = waiting.pop(0)
+            live[pool.open()] = [k, list(_chunks(utterances[k].shape[0], chunk_frames))]
+        durs = []
+        for slot, (k, plan) in live.items():
+            a, b = plan.pop(0)
+            if pool.feed(slot, utterances[k][a:b]):
+                durs.append((b - a) * frame_shift_s)
+        if durs:
+            t0 = time.time()
+            pool.step()
+            dt = time.time() - t0
+            step_ms.append(dt * 1e3)
+            rtfs.extend(dt / d for d in durs)
+        for slot in [s for s, (_, plan) in live.items() if not plan]:
+            tokens[live[slot][0]] = pool.close(slot)
+            del live[slot]
+        t += 1
+    return {"greedy": _stats(rtfs), "step_ms": _stats(step_ms), "tokens": tokens}

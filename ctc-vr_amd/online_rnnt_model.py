@@ -4,9 +4,11 @@ behaviour for the streaming inference path; the arithmetic runs in librnnt_hip.s
 never on the CPU.  PyTorch is used only for device memory and streams.
 
 Additions over the reference (which is batch-1 only, :277-278,348-349): `StreamingBatch`, B lock-stepped
-independent streams in one context; each stream's result equals the reference's B=1 result.
+independent streams in one context, and `StreamPool`, slots of one context that open, advance and close
+independently (callers that connect and hang up whenever they like); each stream's result equals the
+reference's B=1 result.
 """
-from typing import List, Optional, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -643,3 +645,135 @@ class StreamingBatch:
             self.engine.greedy_decode(s)
             self.engine.frames_consume(s)
         return self.engine.tokens(_stream_ptr())
+
+
+def pool_plan(queue, offsets):
+    """The library calls of one StreamPool.step as a pure function (no GPU, no tensors).
+
+    queue: [(slot, length)] in feed order, several entries per slot allowed; offsets: {slot: encoder offset so far}.
+    Returns (calls, new_offsets, index): calls = [(length, [slot, ...], [offset, ...])], one rnnt_pool_chunk each, and index[k] =
+    (call, row) of queue entry k (None for a skipped one).  A call holds ONE chunk length and every slot at most once; a slot's
+    chunks keep their feed order across calls (its r-th queued chunk goes into round r, rounds run one after the other, and
+    inside a round the length classes run in ascending length).  Per slot the bookkeeping is process_single_chunk's
+    (model/online_rnnt_model.py:356-359,364-370,384-385): a chunk shorter than 7 frames is skipped without touching the offset, a
+    chunk is encoded with offset = required_cache_size = the slot's offset so far, and the offset then grows by length // 4."""
+    offs = dict(offsets)
+    rounds: List[Dict[int, List[Tuple[int, int]]]] = []        # round -> length -> [(slot, queue index)]
+    depth: Dict[int, int] = {}
+    index: List[Optional[Tuple[int, int]]] = [None] * len(queue)
+    for k, (slot, length) in enumerate(queue):
+        if length < 7:
+            continue
+        r = depth.get(slot, 0)
+        depth[slot] = r + 1
+        while len(rounds) <= r:
+            rounds.append({})
+        rounds[r].setdefault(int(length), []).append((slot, k))
+    calls = []
+    for rnd in rounds:
+        for length in sorted(rnd):
+            slots, call_offs = [], []
+            for slot, k in rnd[length]:
+                index[k] = (len(calls), len(slots))
+                slots.append(slot)
+                call_offs.append(offs.get(slot, 0))
+                offs[slot] = offs.get(slot, 0) + length // 4
+            calls.append((length, slots, call_offs))
+    return calls, offs, index
+
+
+class StreamPool:
+    """A context's slots, each with its own life (not in the reference, which is B=1): open() a slot when a caller connects, feed()
+    it a chunk whenever the caller has one, step() to advance whatever subset of slots has chunks queued -- each at its own cache
+    length, positional window and encoder offset, through rnnt_pool_chunk -- and close() it when the caller hangs up.  The tokens of
+    an utterance are those of process_single_chunk on a model that holds only that stream, whatever the other slots do.  Greedy
+    only (the beam state of the context is per context, not per slot)."""
+
+    def __init__(self, state_dict, n_slots: int, vocab_size: int = 412, blank_id: int = 5, max_chunk_frames: int = 64,
+                 max_cache_frames: int = 512, max_tokens: int = 4096, device: int = 0, numerics=None, packed=None, engine=None):
+        """state_dict / packed: as StreamingBatch.  engine: an object with reset / stream_open / pool_chunk / stream_tokens to drive
+        instead of a new RnntEngine (a recording fake in the CPU tests)."""
+        self.n = n_slots
+        self.blank_id = blank_id
+        if engine is None:
+            engine = RnntEngine(max_streams=n_slots, max_chunk_frames=max_chunk_frames, max_cache_frames=max_cache_frames,
+                                max_enc_frames=max(16, (max_chunk_frames + 3) // 4), max_tokens=max_tokens, vocab_size=vocab_size,
+                                blank_id=blank_id, n_steps=10, device=device, max_beam=0)
+            if packed is not None:
+                assert state_dict is None and int(packed[1]) == vocab_size, "packed=(blob, vocab): vocab must equal vocab_size"
+                engine.load_packed(packed[0], int(packed[1]), numerics=numerics)
+            else:
+                engine.load_state_dict(state_dict, numerics=numerics)
+        self.engine = engine
+        self.reset()
+
+    def reset(self):
+        """All slots free; the context freshly reset (the lock-step entry points work again until the first open)."""
+        self.engine.reset(self.n, self._stream(None))
+        self._free = list(range(self.n))
+        self._offset: Dict[int, int] = {}
+        self._ntok: Dict[int, int] = {}
+        self._queue: List[Tuple[int, torch.Tensor]] = []
+        self._carry: Dict[int, List[int]] = {}          # increments of other slots produced by the step inside a close()
+
+    @staticmethod
+    def _stream(t):
+        return _stream_ptr() if (t is None and torch.cuda.is_available()) or (t is not None and t.is_cuda) else None
+
+    def open(self) -> int:
+        """The lowest free slot, reset for a new utterance (reset_streaming_cache for that slot alone)."""
+        if not self._free:
+            raise RnntError(f"stream pool full: all {self.n} slots are open")
+        slot = self._free.pop(0)
+        self.engine.stream_open(slot, self._stream(None))
+        self._offset[slot] = 0
+        self._ntok[slot] = 0
+        return slot
+
+    def feed(self, slot: int, chunk: torch.Tensor) -> bool:
+        """Queue one chunk [T, 80] (float32, on the device) for an open slot; the next step() encodes and decodes it.  A chunk of
+        fewer than 7 frames is skipped as in process_single_chunk (:356-359): returns False and the slot's offset stays."""
+        if slot not in self._offset:
+            raise RnntError(f"slot {slot} is not open")
+        assert chunk.dim() == 2 and chunk.size(1) == 80 and chunk.dtype == torch.float32
+        if chunk.size(0) < 7:
+            print(f"Warning: Chunk too small ({chunk.size(0)} frames), skipping")
+            return False
+        self._queue.append((slot, chunk))
+        return True
+
+    def step(self) -> Dict[int, List[int]]:
+        """Advance every slot that has chunks queued: one rnnt_pool_chunk call per chunk length (pool_plan), the rows of a call
+        gathered into one contiguous device tensor.  Returns {slot: tokens emitted by this step} for the slots that advanced."""
+        out, self._carry = self._carry, {}
+        if not self._queue:
+            return out
+        calls, offs, index = pool_plan([(slot, c.size(0)) for slot, c in self._queue], self._offset)
+        rows: List[List[Optional[torch.Tensor]]] = [[None] * len(slots) for _, slots, _ in calls]
+        for (slot, c), at in zip(self._queue, index):
+            rows[at[0]][at[1]] = c
+        touched = []
+        for (length, slots, call_offs), chunks in zip(calls, rows):
+            x = torch.stack(chunks, 0).contiguous()
+            self.engine.pool_chunk(slots, x.data_ptr(), length, call_offs, call_offs, True, self._stream(x))
+            touched.extend(s for s in slots if s not in touched)
+        self._offset = offs
+        self._queue = []
+        for slot in touched:
+            new = self.engine.stream_tokens(slot, self._ntok[slot], self._stream(None))
+            self._ntok[slot] += len(new)
+            out[slot] = out.get(slot, []) + new
+        return out
+
+    def close(self, slot: int) -> List[int]:
+        """Finish the slot's utterance (queued chunks are processed first) and free the slot; returns all its tokens."""
+        if slot not in self._offset:
+            raise RnntError(f"slot {slot} is not open")
+        if any(s == slot for s, _ in self._queue):
+            self._carry = self.step()                   # the other slots' increments are handed out by the next step()
+        self._carry.pop(slot, None)
+        toks = self.engine.stream_tokens(slot, 0, self._stream(None))
+        del self._offset[slot], self._ntok[slot]
+        self._free.append(slot)
+        self._free.sort()
+        return toks

@@ -16,7 +16,8 @@
  * pointers are ordinary host memory.  A context is confined to one host thread at a time; all
  * work of one call is enqueued on the hipStream_t passed as `stream` (void*; NULL = default
  * stream).  Calls that return data to the host synchronise that stream.
- * All streams of one context advance in lock step (same chunk length per call).
+ * All streams of one context advance in lock step (same chunk length per call) through rnnt_encoder_chunk / rnnt_encoder_chunks /
+ * rnnt_decode_ragged; the stream pool (rnnt_stream_open, rnnt_pool_chunk) gives every slot a position of its own instead.
  */
 #ifndef RNNT_HIP_H
 #define RNNT_HIP_H
@@ -50,7 +51,7 @@ typedef enum {
                                /* must stay below 65504 in magnitude (LayerNorm / activation outputs and weights do)       */
 
 typedef struct {
-    int32_t max_streams;       /* B: lock-stepped streams held by the context                     */
+    int32_t max_streams;       /* B: streams (lock-stepped, or stream-pool slots) held by the context */
     int32_t max_chunk_frames;  /* largest fbank chunk (input frames) passed to rnnt_encoder_chunk  */
     int32_t max_cache_frames;  /* K/V cache capacity per stream, in encoder frames (<= 5000)       */
     int32_t max_enc_frames;    /* encoder-output frame buffer per stream (frames awaiting decode)  */
@@ -130,6 +131,38 @@ int rnnt_get_tokens(rnnt_ctx* ctx, int32_t* counts_host, int32_t* tokens_host, v
 
 /* drop decoded frames from the encoder-frame buffer (keeps undecoded ones). */
 int rnnt_frames_consume(rnnt_ctx* ctx, void* stream);
+
+/* -- stream pool: slots that open, advance and close independently ------------------------------ */
+/* The n_streams slots of a context, each with its own life: a slot is opened (reset on its own), fed chunks whenever its caller
+ * has one, and simply re-opened for the next caller, while its neighbours are anywhere in their own utterances or idle.
+ * Contract: the tokens, encoder frames and cached state of an utterance that runs in a slot are those of the same utterance run
+ * alone (n_streams = 1) through rnnt_encoder_chunk + rnnt_greedy_decode + rnnt_frames_consume, bit for bit, whatever the other
+ * slots do.  Once rnnt_stream_open or rnnt_pool_chunk has run, the slots' positions may differ: rnnt_encoder_chunk,
+ * rnnt_encoder_chunks, rnnt_decode_ragged and rnnt_encode_ragged refuse with RNNT_ERR_STATE until the next rnnt_streams_reset, and
+ * the read-back getters return each slot's own state.  Pool calls leave the context's beam-search state alone.
+ *
+ * rnnt_stream_open: reset_streaming_cache (model/online_rnnt_model.py:145-164) for ONE slot in [0, n_streams) -- empty K/V cache,
+ * conv left context of a fresh stream, zero LSTM state, last token = blank, token count 0, position 0.  Touches no other slot.
+ * Valid after rnnt_streams_reset(ctx, n), which opens all n slots at once. */
+int rnnt_stream_open(rnnt_ctx* ctx, int32_t slot, void* stream);
+/* forward_chunk (wenet/transformer/encoder.py:203-299) for the n_active listed slots (distinct, in [0, n_streams)): row i of
+ * fbank_dev [n_active, chunk_frames, 80] belongs to slot slots_host[i] and is encoded with offsets_host[i] / required_host[i] at
+ * that slot's own cache length, K/V row, positional window and conv-ring position, exactly as rnnt_encoder_chunk would for a
+ * context holding only that stream.  One chunk length per call; *frames_out receives t'.
+ *   greedy != 0: the greedy decode of the new frames of the active slots follows and the frames are consumed (one call = encode +
+ *     decode + consume; synchronises like rnnt_greedy_decode).  Read tokens with rnnt_stream_get_tokens / rnnt_get_tokens.
+ *   greedy == 0: encoder only.  The new frames stay buffered as frames [0, t') of the active slots' rows, readable with
+ *     rnnt_get_enc_frames (rows of idle slots are undefined), and must be dropped with rnnt_frames_discard before the next pool
+ *     call, which otherwise refuses with RNNT_ERR_STATE.  Does not synchronise.
+ * Slots not listed are neither read nor written: K/V rows, both rings, h, c, last token, token buffer and count stay bitwise as
+ * they were.  Refusals (duplicated or out-of-range slot: RNNT_ERR_ARG; chunk outside [7, max_chunk_frames], a positional window
+ * outside the 5000-entry table or a full K/V cache of ANY listed slot: RNNT_ERR_SHAPE; frames still buffered: RNNT_ERR_STATE) are
+ * decided on the host before the first launch and change no slot's state. */
+int rnnt_pool_chunk(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, const float* fbank_dev, int32_t chunk_frames,
+                    const int32_t* offsets_host, const int32_t* required_host, int32_t greedy, int32_t* frames_out, void* stream);
+/* tokens [from, count) of one slot, at most cap of them into tokens_host; *n_out = count - from (0 if from >= count), so a caller
+ * polls only its own increments.  Synchronises. */
+int rnnt_stream_get_tokens(rnnt_ctx* ctx, int32_t slot, int32_t from, int32_t cap, int32_t* tokens_host, int32_t* n_out, void* stream);
 
 /* Greedy decode of a padded batch of whole utterances of DIFFERENT lengths in one call (utils/utils.py:29-50 pads a batch,
  * online_rnnt_eval.py:86-94 decodes every utterance with its own audio_lens): stream b runs the decode script's chunk loop
