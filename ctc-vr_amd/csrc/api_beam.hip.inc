@@ -42,14 +42,14 @@ int rnnt_beam_frame(rnnt_ctx* ctx, int32_t frame_idx, int32_t n_rows, const int3
         float* sout = pool + (size_t)(st + 1) * 512;
         GemmP g1 = plain_gemm(sin, slots * 512, ctx->whh_il, D, nullptr, sout, D, R, 4 * D, D, EPI_LSTM);
         g1.X = ctx->egate; g1.I = ctx->b_tok; g1.X2 = sin + D; g1.Y2 = sout + D; g1.lstm_ld = slots * 512;
-        if ((rc = launch_gemm(ctx, s, 0, &g1, 1, TAG_LSTM))) return rc;
+        if ((rc = launch_gemm(ctx, s, &g1, 1, TAG_LSTM))) return rc;
         GemmP g2 = plain_gemm(sout, slots * 512, ctx->wpr, D, ctx->bpr, ctx->bpred, D, R, D, D);
-        if ((rc = launch_gemm(ctx, s, 0, &g2, 1, TAG_PRED_PROJ))) return rc;
+        if ((rc = launch_gemm(ctx, s, &g2, 1, TAG_PRED_PROJ))) return rc;
         GemmP g3 = plain_gemm(ctx->bpred, D, ctx->wpf, D, ctx->bpf, ctx->bz, D, R, D, D, EPI_TANH_ADD);
         g3.X = ctx->encp; g3.I = ctx->b_frame; g3.x_n = 1; g3.x_s0 = 0; g3.x_s1 = D;
-        if ((rc = launch_gemm(ctx, s, 0, &g3, 1, TAG_JOINT_TANH))) return rc;
+        if ((rc = launch_gemm(ctx, s, &g3, 1, TAG_JOINT_TANH))) return rc;
         GemmP g4 = plain_gemm(ctx->bz, D, ctx->wout, D, ctx->bout, ctx->blogits, ctx->vpad, R, V, D);
-        if ((rc = launch_gemm(ctx, s, 0, &g4, 1, TAG_JOINT_OUT))) return rc;
+        if ((rc = launch_gemm(ctx, s, &g4, 1, TAG_JOINT_OUT))) return rc;
         hipLaunchKernelGGL(beam_reduce, dim3(R), dim3(64), 0, s, ctx->blogits, ctx->vpad, V, ctx->cfg.blank_id, beam_k, st, NS, bo);
         LAUNCHCHK("beam_reduce");
         HIPCHK(hipMemcpyAsync(ctx->pinned + 1, ctx->n_active + 1, sizeof(int), hipMemcpyDeviceToHost, s));

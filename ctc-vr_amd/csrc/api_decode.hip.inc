@@ -10,9 +10,7 @@ int rnnt_greedy_decode(rnnt_ctx* ctx, void* stream) {
     if (nf <= ctx->frames_decoded) return RNNT_OK;
     int rc;
     if (ctx->use_persistent) {
-        if ((rc = init_decoder_ctrl(ctx, s, nf))) return rc;
-        if ((rc = launch_persistent_decoder(ctx, s, nf))) return rc;
-        if ((rc = finish_persistent_decoder(ctx, s))) return rc;
+        if ((rc = decode_resident(ctx, s, nf))) return rc;
         ctx->frames_decoded = nf;
         return RNNT_OK;
     }

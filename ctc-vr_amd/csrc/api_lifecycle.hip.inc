@@ -24,7 +24,6 @@ int rnnt_create(const rnnt_config* cfg, rnnt_ctx** out) {
     if (const char* be = getenv("RNNT_BEAM_CHAIN")) ctx->use_beam_chain = (be[0] == '0') ? 0 : 1;
     if (const char* fu = getenv("RNNT_FUSED")) ctx->use_fused = atoi(fu);   // 0 off, 1 split-operand modes (default), 2 every mode
     if (const char* fe = getenv("RNNT_FUSE_AFTER_NORM")) ctx->fuse_after_norm = (fe[0] == '0') ? 0 : 1;
-    if (const char* ge = getenv("RNNT_WF_GROUPS")) { const int g = atoi(ge); ctx->wf_groups = g < 1 ? 1 : (g > 4 ? 4 : g); }
     if (const char* me = getenv("RNNT_WF_MERGE")) { const int m = atoi(me); ctx->wf_merge = m < 1 ? 1 : (m > WF_MERGE_MAX ? WF_MERGE_MAX : m); }
     if (const char* le = getenv("RNNT_LM")) ctx->use_lm = (le[0] == '0') ? 0 : 1;
     if (const char* ae2 = getenv("RNNT_AS")) ctx->use_as = (ae2[0] == '0') ? 0 : 1;
@@ -102,12 +101,10 @@ void rnnt_destroy(rnnt_ctx* ctx) {
     if (ctx->pool_tab_host) (void)hipHostFree(ctx->pool_tab_host);
     if (ctx->pool_ev) (void)hipEventDestroy(ctx->pool_ev);
     for (hipEvent_t e : ctx->prof_ev) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ctx->wf_ev) (void)hipEventDestroy(e);
     if (ctx->dec_stream) (void)hipStreamDestroy(ctx->dec_stream);
     for (hipEvent_t e : ctx->sub_ev) if (e) (void)hipEventDestroy(e);
     for (auto& g : ctx->dec_graphs) (void)hipGraphExecDestroy(g.exec);
     if (ctx->cap_stream) (void)hipStreamDestroy(ctx->cap_stream);
-    for (hipStream_t x : ctx->grp_stream) if (x) (void)hipStreamDestroy(x);
     if (ctx->sub_stream) (void)hipStreamDestroy(ctx->sub_stream);
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
     for (float* q : {ctx->fb_dft, ctx->fb_mel, ctx->fb_pad, ctx->fb_spec, ctx->fb_pow}) if (q) (void)hipFree(q);
@@ -443,12 +440,12 @@ int rnnt_finalize_weights(rnnt_ctx* ctx, int32_t numerics_mode, void* stream) {
     for (int l = 0; l < L; ++l) {
         if (!ctx->lw[l].ptab && (rc = dmalloc(ctx, &ctx->lw[l].ptab, (size_t)RNNT_PE_LEN * D))) return rc;
         GemmP g = plain_gemm(ctx->pe, D, ctx->lw[l].wpos, D, nullptr, ctx->lw[l].ptab, D, RNNT_PE_LEN, D, D);
-        if ((rc = launch_gemm(ctx, s, 0, &g, 1))) return rc;
+        if ((rc = launch_gemm(ctx, s, &g, 1))) return rc;
     }
     if (!ctx->egate && (rc = dmalloc(ctx, &ctx->egate, (size_t)V * 4 * D))) return rc;
     {
         GemmP g = plain_gemm(ctx->pred_embed, D, ctx->wih_il, D, ctx->b_lstm_il, ctx->egate, 4 * D, V, 4 * D, D);
-        if ((rc = launch_gemm(ctx, s, 0, &g, 1))) return rc;
+        if ((rc = launch_gemm(ctx, s, &g, 1))) return rc;
     }
     HIPCHK(hipStreamSynchronize(s));
     ctx->numerics = numerics_mode;
@@ -463,11 +460,11 @@ int rnnt_streams_reset(rnnt_ctx* ctx, int32_t n_streams, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     const int B = ctx->cfg.max_streams;
     ctx->n_streams = n_streams;
-    ctx->cache_len = 0; ctx->kv_start = 0; ctx->conv_pos = 0;
+    ctx->pos = SlotPos{0, 0, 0};
     ctx->frames_buffered = 0; ctx->frames_decoded = 0;
     ctx->launches = 0; ctx->greedy_steps = 0;
     ctx->pool_mode = false;                      // all slots share one position again
-    ctx->slot_pos.assign(B, rnnt_ctx::SlotPos{0, 0, 0});
+    ctx->slot_pos.assign(B, SlotPos{0, 0, 0});
     hipLaunchKernelGGL(conv_ring_init, dim3(grid_for((long long)L * B * ctx->cap * D)), dim3(256), 0, s, ctx->gring, ctx->xring, ctx->glu0, B, ctx->cap);
     LAUNCHCHK("conv_ring_init");
     hipLaunchKernelGGL(decode_state_reset, dim3(grid_for((long long)2 * B * D)), dim3(256), 0, s, ctx->h, ctx->c, ctx->sel, ctx->key, ctx->fidx, ctx->nsym,

@@ -9,9 +9,9 @@ int rnnt_predictor_step(rnnt_ctx* ctx, const int32_t* tokens_dev, const float* h
     int rc;
     GemmP g1 = plain_gemm(h_in, D, ctx->whh_il, D, nullptr, h_out, D, rows, 4 * D, D, EPI_LSTM);
     g1.X = ctx->egate; g1.I = tokens_dev; g1.X2 = c_in; g1.Y2 = c_out;
-    if ((rc = launch_gemm(ctx, s, 0, &g1, 1))) return rc;
+    if ((rc = launch_gemm(ctx, s, &g1, 1))) return rc;
     GemmP g2 = plain_gemm(h_out, D, ctx->wpr, D, ctx->bpr, out_dev, D, rows, D, D);
-    return launch_gemm(ctx, s, 0, &g2, 1);
+    return launch_gemm(ctx, s, &g2, 1);
 }
 
 int rnnt_joint(rnnt_ctx* ctx, const float* enc_dev, const float* pred_dev, int32_t B, int32_t T, int32_t U, int32_t mode, float* logits_dev,
@@ -30,9 +30,9 @@ int rnnt_joint(rnnt_ctx* ctx, const float* enc_dev, const float* pred_dev, int32
     // joint_lattice_rows takes e and p multiplied by 2 log2(e): tanh(e + p) = 1 - 2 / (exp2(e' + p') + 1) (rnnt_joint.hip.h)
     const float pre = rows_kernel ? JR_PRESCALE : 1.0f;
     GemmP ge = plain_gemm(enc_dev, D, ctx->wenc, D, ctx->benc, e, D, B * T, D, D, rows_kernel ? EPI_SCALE : EPI_BIAS, pre);
-    if ((rc = launch_gemm(ctx, s, 0, &ge, 1))) return rc;
+    if ((rc = launch_gemm(ctx, s, &ge, 1))) return rc;
     GemmP gp = plain_gemm(pred_dev, D, ctx->wpf, D, ctx->bpf, pp, D, B * U, D, D, rows_kernel ? EPI_SCALE : EPI_BIAS, pre);
-    if ((rc = launch_gemm(ctx, s, 0, &gp, 1))) return rc;
+    if ((rc = launch_gemm(ctx, s, &gp, 1))) return rc;
     if (rows_kernel) {
         // split-operand modes: ONE lattice kernel with the (log-)softmax on the accumulators (joint_lattice_rows, rnnt_joint.hip.h):
         // persistent 64-row workgroups, two per CU, over a dynamic row-tile queue
@@ -152,7 +152,7 @@ int rnnt_ctc_argmax(rnnt_ctx* ctx, const float* fbank_dev, const int32_t* lens_h
     HIPCHK(hipMemsetAsync(keys, 0, rows * sizeof(unsigned long long), s));
     GemmP g = plain_gemm(enc, D, ctx->wctc, D, ctx->bctc, nullptr, 0, (int)rows, ctx->cfg.vocab_size, D, EPI_ARGMAX);
     g.key = keys;
-    if ((rc = launch_gemm(ctx, s, 0, &g, 1))) return rc;   // EPI_ARGMAX always takes the gemm16 (split-K) kernel
+    if ((rc = launch_gemm(ctx, s, &g, 1))) return rc;   // EPI_ARGMAX always takes the gemm16 (split-K) kernel
     hipLaunchKernelGGL(unpack_keys, dim3(grid_for((long long)rows)), dim3(256), 0, s, keys, ids, (long long)rows);
     LAUNCHCHK("unpack_keys");
     HIPCHK(hipMemcpyAsync(ids_host, ids, rows * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -171,7 +171,7 @@ int rnnt_ctc_logprobs(rnnt_ctx* ctx, const float* enc_dev, int32_t rows, float* 
     const int V = ctx->cfg.vocab_size;
     int rc;
     GemmP g = plain_gemm(enc_dev, D, ctx->wctc, D, ctx->bctc, out_dev, V, rows, V, D);
-    if ((rc = launch_gemm(ctx, s, 0, &g, 1))) return rc;
+    if ((rc = launch_gemm(ctx, s, &g, 1))) return rc;
     hipLaunchKernelGGL(log_softmax_rows, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, out_dev, (long long)rows, V);
     LAUNCHCHK("log_softmax_rows");
     return RNNT_OK;
@@ -200,11 +200,9 @@ int rnnt_greedy_search_full(rnnt_ctx* ctx, const float* fbank_dev, const int32_t
     {   // joint.enc_ffn of every frame, [B*tq, 256] -> enc_proj [B][fstride][256]
         GemmP g = plain_gemm(ctx->scratch, D, ctx->wenc, D, ctx->benc, ctx->encp, D, (int)rows, D, D);
         g.c_n = tq; g.c_s0 = (long long)ctx->fstride * D; g.c_r0 = 0; g.c_mod = BIG; g.c_s1 = D;
-        if ((rc = launch_gemm(ctx, s, 0, &g, 1, TAG_ENC_PROJ))) return rc;
+        if ((rc = launch_gemm(ctx, s, &g, 1, TAG_ENC_PROJ))) return rc;
     }
-    if ((rc = init_decoder_ctrl(ctx, s, tq))) return rc;
-    if ((rc = launch_persistent_decoder(ctx, s, tq, n_steps, ctx->klen))) return rc;
-    if ((rc = finish_persistent_decoder(ctx, s))) return rc;
+    if ((rc = decode_resident(ctx, s, tq, ctx->klen, nullptr, 0, n_steps))) return rc;
     ctx->n_streams = 0;                                                                        // streaming state is not meaningful afterwards
     HIPCHK(hipMemcpyAsync(counts_host, ctx->count, B * sizeof(int), hipMemcpyDeviceToHost, s));
     if (tokens_host) HIPCHK(hipMemcpyAsync(tokens_host, ctx->tokens, (size_t)B * ctx->cfg.max_tokens * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -277,11 +275,11 @@ int rnnt_fbank(rnnt_ctx* ctx, const float* wave_dev, int32_t B, int32_t n_sample
     // windowed DFT: implicit frames (row t of stream b starts at b*pstride + t*hop), K = n_fft
     GemmP g1 = plain_gemm(ctx->fb_pad, hop, ctx->fb_dft, n_fft, nullptr, ctx->fb_spec, n2p, (int)M, n2p, n_fft);
     g1.a_n1 = T; g1.a_n2 = T; g1.a_s0 = pstride; g1.a_s1 = 0; g1.a_s2 = hop;
-    if ((rc = launch_gemm(ctx, s, 0, &g1, 1))) return rc;
+    if ((rc = launch_gemm(ctx, s, &g1, 1))) return rc;
     hipLaunchKernelGGL(power_spectrum, dim3(grid_for(M * kp)), dim3(256), 0, s, ctx->fb_spec, ctx->fb_pow, M, nfreq, kp, n2p);
     LAUNCHCHK("power_spectrum");
     GemmP g2 = plain_gemm(ctx->fb_pow, kp, ctx->fb_mel, kp, nullptr, out_dev, n_mels, (int)M, n_mels, kp, EPI_DB);
-    if ((rc = launch_gemm(ctx, s, 0, &g2, 1))) return rc;
+    if ((rc = launch_gemm(ctx, s, &g2, 1))) return rc;
     if (frames_out) *frames_out = T;
     return RNNT_OK;
 }

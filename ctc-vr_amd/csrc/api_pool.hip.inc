@@ -2,8 +2,8 @@
 // rnnt_stream_get_tokens).  Included by rnnt_api.hip inside extern "C".
 //
 // Every stream's state already lives per stream on the device (K/V cache, the two conv rings, LSTM h/c, last token, token buffer);
-// the lock-step entry points only share its POSITION (cache_len, kv_start, conv_pos).  Here the position is per slot: plain host
-// integers in ctx->slot_pos, advanced by the reference's bookkeeping (encoder.py:254-264) and mirrored for each call into one
+// the lock-step entry points only share its POSITION (SlotPos: cache_len, kv_start, conv_pos).  Here the position is per slot: plain
+// host integers in ctx->slot_pos, planned and advanced by the same SlotPos methods as ctx->pos, and mirrored for each call into one
 // small device table (PoolRow per active row + the slot list of the decoder), written by ONE async copy from pinned memory.  The
 // rows of a call are compact -- row i * t' + f is frame f of active row i -- and every access to per-stream storage goes through
 // slots[i]: the K/V and ring appends through GemmP::c_tab, attention / depthwise conv / decoder through their pool forms.  Idle
@@ -29,7 +29,7 @@ int pool_alloc(rnnt_ctx* ctx) {
 // from here on every slot has its own position (the lock-step entry points refuse until rnnt_streams_reset)
 void pool_enter(rnnt_ctx* ctx) {
     if (ctx->pool_mode) return;
-    ctx->slot_pos.assign(ctx->cfg.max_streams, rnnt_ctx::SlotPos{ctx->cache_len, ctx->kv_start, ctx->conv_pos});
+    ctx->slot_pos.assign(ctx->cfg.max_streams, ctx->pos);
     ctx->pool_mode = true;
 }
 
@@ -56,12 +56,7 @@ int launch_attn_pool(rnnt_ctx* ctx, hipStream_t s, const AttnP& a, const PoolRow
     }
     if (n_stream < n) {
         const int sel = n_stream == 0 ? 2 : 0;   // all rows, or only those beyond the streaming kernel's range
-        const int nq = a.tq <= 4 ? 1 : (a.tq <= 8 ? 2 : 4);
-        dim3 grid(n * RNNT_H, (a.tq + 4 * nq - 1) / (4 * nq));
-        if (nq == 1) hipLaunchKernelGGL(rel_attention_pool<1>, grid, dim3(256), 0, s, a, rows_dev, sel);
-        else if (nq == 2) hipLaunchKernelGGL(rel_attention_pool<2>, grid, dim3(256), 0, s, a, rows_dev, sel);
-        else hipLaunchKernelGGL(rel_attention_pool<4>, grid, dim3(256), 0, s, a, rows_dev, sel);
-        LAUNCHCHK("rel_attention_pool");
+        LAUNCH_ATTN_TILED(rel_attention_pool, s, n * RNNT_H, a.tq, 1, a, rows_dev, sel);
     }
     return RNNT_OK;
 }
@@ -75,20 +70,20 @@ int run_layer_pool(rnnt_ctx* ctx, hipStream_t s, int l, int n, int tq, const Poo
     const int* tab = reinterpret_cast<const int*>(rows_dev);
     for (int i = 1; i < 3; ++i) { d.qkv[i].c_tab = tab; d.qkv[i].c_tab_col = POOL_COL_KV_W0; d.qkv[i].c_r0 = 0; }
     d.pw1.c_tab = tab; d.pw1.c_tab_col = POOL_COL_RING_W0; d.pw1.c_r0 = 0;
-    if ((rc = launch_gemm(ctx, s, 0, &d.ffn1m, 1, TAG_FFN1))) return rc;
-    if ((rc = launch_gemm(ctx, s, 0, &d.ffn2m, 1, TAG_FFN2))) return rc;
-    if ((rc = launch_gemm(ctx, s, 0, d.qkv, 3, TAG_QKV))) return rc;
+    if ((rc = launch_gemm(ctx, s, &d.ffn1m, 1, TAG_FFN1))) return rc;
+    if ((rc = launch_gemm(ctx, s, &d.ffn2m, 1, TAG_FFN2))) return rc;
+    if ((rc = launch_gemm(ctx, s, d.qkv, 3, TAG_QKV))) return rc;
     if ((rc = launch_attn_pool(ctx, s, d.attn, rows_dev, rows_host, n))) return rc;
-    if ((rc = launch_gemm(ctx, s, 0, &d.out, 1, TAG_ATTN_OUT))) return rc;
-    if ((rc = launch_gemm(ctx, s, 0, &d.pw1, 1, TAG_PW1))) return rc;
+    if ((rc = launch_gemm(ctx, s, &d.out, 1, TAG_ATTN_OUT))) return rc;
+    if ((rc = launch_gemm(ctx, s, &d.pw1, 1, TAG_PW1))) return rc;
     {
         ProfScope prof(ctx, s, TAG_DWCONV);
         hipLaunchKernelGGL(dwconv_bn_silu_pool, dim3(grid_for((long long)n * tq * D)), dim3(256), 0, s, d.dw, rows_dev);
         LAUNCHCHK("dwconv_bn_silu_pool");
     }
-    if ((rc = launch_gemm(ctx, s, 0, &d.pw2, 1, TAG_PW2))) return rc;
-    if ((rc = launch_gemm(ctx, s, 0, &d.ffn1, 1, TAG_FFN1))) return rc;
-    if ((rc = launch_gemm(ctx, s, 0, &d.ffn2, 1, TAG_FFN2))) return rc;
+    if ((rc = launch_gemm(ctx, s, &d.pw2, 1, TAG_PW2))) return rc;
+    if ((rc = launch_gemm(ctx, s, &d.ffn1, 1, TAG_FFN1))) return rc;
+    if ((rc = launch_gemm(ctx, s, &d.ffn2, 1, TAG_FFN2))) return rc;
     return launch_ln(ctx, s, d.lnf);
 }
 
@@ -107,7 +102,7 @@ int rnnt_stream_open(rnnt_ctx* ctx, int32_t slot, void* stream) {
                        ctx->cfg.blank_id);
     LAUNCHCHK("stream_slot_reset");
     pool_enter(ctx);
-    ctx->slot_pos[slot] = rnnt_ctx::SlotPos{0, 0, 0};
+    ctx->slot_pos[slot] = SlotPos{0, 0, 0};
     return RNNT_OK;
 }
 
@@ -124,7 +119,8 @@ int rnnt_pool_chunk(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, 
     const int tq = sub_len(T);
     if (tq > ctx->fcap) return fail(ctx, RNNT_ERR_SHAPE, "encoder-frame buffer capacity %d exceeded", ctx->fcap);
     // ---- validate every listed slot before anything changes: a wrong slot is a write into another caller's cache --------------------
-    auto pos_of = [&](int slot) { return ctx->pool_mode ? ctx->slot_pos[slot] : rnnt_ctx::SlotPos{ctx->cache_len, ctx->kv_start, ctx->conv_pos}; };
+    auto pos_of = [&](int slot) { return ctx->pool_mode ? ctx->slot_pos[slot] : ctx->pos; };
+    std::string err;
     std::vector<char> seen((size_t)ctx->n_streams, 0);
     std::vector<PoolRow> rows((size_t)n);
     for (int i = 0; i < n; ++i) {
@@ -132,19 +128,11 @@ int rnnt_pool_chunk(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, 
         if (slot < 0 || slot >= ctx->n_streams) return fail(ctx, RNNT_ERR_ARG, "rnnt_pool_chunk: row %d: slot %d outside [0, %d)", i, slot, ctx->n_streams);
         if (seen[slot]) return fail(ctx, RNNT_ERR_ARG, "rnnt_pool_chunk: slot %d listed twice", slot);
         seen[slot] = 1;
-        const rnnt_ctx::SlotPos p = pos_of(slot);
+        ChunkInfo k;
+        if (!pos_of(slot).plan(tq, offsets_host[i], ctx->tcap, k, err)) return fail(ctx, RNNT_ERR_SHAPE, "slot %d: %s", slot, err.c_str());
         PoolRow& r = rows[i];
-        r.slot = slot;
-        r.T2 = p.cache_len + tq;                           // attention_key_size (encoder.py:256)
-        r.kv_row0 = p.kv_start;
-        r.pos_start = offsets_host[i] - p.cache_len;       // encoder.py:257
-        r.ring_pos = p.conv_pos;
-        r.kv_w0 = p.kv_start + p.cache_len;
-        r.ring_w0 = p.conv_pos % ctx->cap;
-        r.zero = 0;
-        if (r.pos_start < 0 || r.pos_start + r.T2 > RNNT_PE_LEN)
-            return fail(ctx, RNNT_ERR_SHAPE, "slot %d: positional window [%d, %d) outside the 5000-entry table", slot, r.pos_start, r.pos_start + r.T2);
-        if (p.kv_start + r.T2 > ctx->tcap) return fail(ctx, RNNT_ERR_SHAPE, "slot %d: K/V cache capacity %d exceeded", slot, ctx->tcap);
+        r.slot = slot; r.T2 = k.T2; r.kv_row0 = k.kv_row0; r.pos_start = k.pos_start; r.ring_pos = k.ring_pos;
+        r.kv_w0 = k.kv_w0(); r.ring_w0 = k.ring_pos % ctx->cap; r.zero = 0;
     }
     hipStream_t s = (hipStream_t)stream;
     int rc;
@@ -168,18 +156,9 @@ int rnnt_pool_chunk(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, 
         GemmP g = plain_gemm(ctx->x, D, ctx->wenc, D, ctx->benc, ctx->encp, D, n * tq, D, D);
         g.c_n = tq; g.c_s0 = (long long)ctx->fstride * D; g.c_r0 = 0; g.c_mod = BIG; g.c_s1 = D;
         g.c_tab = ctx->pool_tab; g.c_tab_col = POOL_COL_ZERO;
-        if ((rc = launch_gemm(ctx, s, 0, &g, 1, TAG_ENC_PROJ))) return rc;
+        if ((rc = launch_gemm(ctx, s, &g, 1, TAG_ENC_PROJ))) return rc;
     }
-    // ---- the reference's cache bookkeeping, per slot (encoder.py:259-264,288) ------------------------------------------------------------
-    for (int i = 0; i < n; ++i) {
-        rnnt_ctx::SlotPos& p = ctx->slot_pos[rows[i].slot];
-        const int T2 = rows[i].T2, req = required_host[i];
-        const int next_start = req < 0 ? 0 : (req == 0 ? T2 : (T2 - req > 0 ? T2 - req : 0));
-        p.kv_start += next_start;
-        p.cache_len = T2 - next_start;
-        if (p.cache_len == 0) p.kv_start = 0;
-        p.conv_pos += tq;
-    }
+    for (int i = 0; i < n; ++i) ctx->slot_pos[rows[i].slot].advance(rows[i].T2, tq, required_host[i]);
     if (frames_out) *frames_out = tq;
     if (!greedy) {   // frames [0, t') of the active slots stay buffered for rnnt_get_enc_frames until rnnt_frames_discard
         hipLaunchKernelGGL(pool_scatter_frames, dim3(grid_for((long long)n * tq * (D / 4))), dim3(256), 0, s, ctx->x, ctx->encbuf, rows_dev, n, tq,
@@ -193,9 +172,7 @@ int rnnt_pool_chunk(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, 
     const int per = pool_multi_ok(ctx) ? (ctx->n_cus / GM_PARTS > 0 ? ctx->n_cus / GM_PARTS : 1) : n;   // greedy_multi: the whole grid resident
     for (int i0 = 0; i0 < n; i0 += per) {
         const int cnt = n - i0 < per ? n - i0 : per;
-        if ((rc = init_decoder_ctrl(ctx, s, tq))) return rc;
-        if ((rc = launch_persistent_decoder(ctx, s, tq, 0, nullptr, slots_dev + i0, cnt))) return rc;
-        if ((rc = finish_persistent_decoder(ctx, s))) return rc;   // synchronises
+        if ((rc = decode_resident(ctx, s, tq, nullptr, slots_dev + i0, cnt))) return rc;   // synchronises
     }
     return RNNT_OK;
 }

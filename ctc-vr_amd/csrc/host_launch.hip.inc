@@ -156,7 +156,7 @@ static bool all_planes(const GemmBatch& gb, int ng) {
 // One to three GEMM descriptors of one K in one launch.  Exact-f32 mode: gemm_ns (LDS-tiled) for large M, gemm16 (16-row
 // tiles, split-K) otherwise.  Split-operand modes: gemm_bf for everything but the LSTM-cell / fused-argmax epilogues (greedy
 // decode: matrix-vector shaped, weight-bandwidth bound, stays exact f32) and weights outside the blob.
-int launch_gemm(rnnt_ctx* ctx, hipStream_t s, int /*unused*/, const GemmP* gs, int ng, int tag = TAG_NONE) {
+int launch_gemm(rnnt_ctx* ctx, hipStream_t s, const GemmP* gs, int ng, int tag = TAG_NONE) {
     ProfScope prof(ctx, s, tag);
     GemmBatch gb;
     memset(&gb, 0, sizeof(gb));
@@ -280,6 +280,19 @@ static bool attn_stream_ok(const rnnt_ctx* ctx, int tq, int T2) {
 static int attn_t2cap(int T2) { return (T2 + 63) / 64 * 64; }
 static size_t attn_stream_lds(int t2cap) { return (size_t)(4 * t2cap + 16 * 4 * RNNT_DK) * sizeof(float); }
 
+// The LDS-tiled attention kernels (rel_attention, rel_attention_tab, rel_attention_pool): KERNEL<NQ> with NQ query rows per wave chosen
+// by the most new frames `tq` of anything the launch serves, on the grid (gx, query tiles, gz); the rest are the kernel's arguments.
+static int attn_nq(int tq) { return tq <= 4 ? 1 : (tq <= 8 ? 2 : 4); }
+#define LAUNCH_ATTN_TILED(KERNEL, s, gx, tq, gz, ...)                                                  \
+    do {                                                                                               \
+        const int nq_ = attn_nq(tq);                                                                   \
+        const dim3 grid_(gx, ((tq) + 4 * nq_ - 1) / (4 * nq_), gz);                                    \
+        if (nq_ == 1) hipLaunchKernelGGL(KERNEL<1>, grid_, dim3(256), 0, s, __VA_ARGS__);              \
+        else if (nq_ == 2) hipLaunchKernelGGL(KERNEL<2>, grid_, dim3(256), 0, s, __VA_ARGS__);         \
+        else hipLaunchKernelGGL(KERNEL<4>, grid_, dim3(256), 0, s, __VA_ARGS__);                       \
+        LAUNCHCHK(#KERNEL);                                                                            \
+    } while (0)
+
 int launch_attn(rnnt_ctx* ctx, hipStream_t s, const AttnP& a, int B) {
     ProfScope prof(ctx, s, TAG_ATTN);
     if (attn_stream_ok(ctx, a.tq, a.T2)) {
@@ -288,12 +301,7 @@ int launch_attn(rnnt_ctx* ctx, hipStream_t s, const AttnP& a, int B) {
         LAUNCHCHK("rel_attention_stream");
         return RNNT_OK;
     }
-    const int nq = a.tq <= 4 ? 1 : (a.tq <= 8 ? 2 : 4);
-    dim3 grid(B * RNNT_H, (a.tq + 4 * nq - 1) / (4 * nq));
-    if (nq == 1) hipLaunchKernelGGL(rel_attention<1>, grid, dim3(256), 0, s, a);
-    else if (nq == 2) hipLaunchKernelGGL(rel_attention<2>, grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(rel_attention<4>, grid, dim3(256), 0, s, a);
-    LAUNCHCHK("rel_attention");
+    LAUNCH_ATTN_TILED(rel_attention, s, B * RNNT_H, a.tq, 1, a);
     return RNNT_OK;
 }
 int launch_dw(rnnt_ctx* ctx, hipStream_t s, const DwP& d) {
@@ -314,16 +322,16 @@ int run_layer(rnnt_ctx* ctx, hipStream_t s, int l, int B, int tq, int T2, int kv
     LayerBufs bf{ctx->x, ctx->hbuf, ctx->qbuf, ctx->abuf, ctx->dbuf};
     int rc = build_layer(ctx, l, B, tq, T2, kv_row0, pos_start, ring_pos, klen_dev, bf, d);
     if (rc) return rc;
-    if ((rc = launch_gemm(ctx, s, 0, &d.ffn1m, 1, TAG_FFN1))) return rc;
-    if ((rc = launch_gemm(ctx, s, 0, &d.ffn2m, 1, TAG_FFN2))) return rc;
-    if ((rc = launch_gemm(ctx, s, 0, d.qkv, 3, TAG_QKV))) return rc;
+    if ((rc = launch_gemm(ctx, s, &d.ffn1m, 1, TAG_FFN1))) return rc;
+    if ((rc = launch_gemm(ctx, s, &d.ffn2m, 1, TAG_FFN2))) return rc;
+    if ((rc = launch_gemm(ctx, s, d.qkv, 3, TAG_QKV))) return rc;
     if ((rc = launch_attn(ctx, s, d.attn, B))) return rc;
-    if ((rc = launch_gemm(ctx, s, 0, &d.out, 1, TAG_ATTN_OUT))) return rc;
-    if ((rc = launch_gemm(ctx, s, 0, &d.pw1, 1, TAG_PW1))) return rc;
+    if ((rc = launch_gemm(ctx, s, &d.out, 1, TAG_ATTN_OUT))) return rc;
+    if ((rc = launch_gemm(ctx, s, &d.pw1, 1, TAG_PW1))) return rc;
     if ((rc = launch_dw(ctx, s, d.dw))) return rc;
-    if ((rc = launch_gemm(ctx, s, 0, &d.pw2, 1, TAG_PW2))) return rc;
-    if ((rc = launch_gemm(ctx, s, 0, &d.ffn1, 1, TAG_FFN1))) return rc;
-    if ((rc = launch_gemm(ctx, s, 0, &d.ffn2, 1, TAG_FFN2))) return rc;
+    if ((rc = launch_gemm(ctx, s, &d.pw2, 1, TAG_PW2))) return rc;
+    if ((rc = launch_gemm(ctx, s, &d.ffn1, 1, TAG_FFN1))) return rc;
+    if ((rc = launch_gemm(ctx, s, &d.ffn2, 1, TAG_FFN2))) return rc;
     return launch_ln(ctx, s, d.lnf);
 }
 
@@ -369,6 +377,17 @@ int run_subsample(rnnt_ctx* ctx, hipStream_t s, const float* fbank, int B, int T
     g.a_seg = 768; g.a_seg_stride = (long long)RNNT_F1 * D;
     static const int conv2_lds = getenv("RNNT_CONV2_LDS") ? atoi(getenv("RNNT_CONV2_LDS")) : 1;
     const bool conv2_bw = conv2_bw_on();
+    // gemm_bw / gemm_bw_c1 of the numerics mode on `grid`, 8 waves (two per SIMD) or 4 (RNNT_BW_NW=4, same results)
+    static const bool nw8 = getenv("RNNT_BW_NW") ? atoi(getenv("RNNT_BW_NW")) == 8 : true;
+#define BW_LAUNCH_NUM(KERNEL, NUM_, ...) { if (nw8) hipLaunchKernelGGL((KERNEL<NUM_, 8>), grid, dim3(512), 0, s, __VA_ARGS__); \
+                                           else hipLaunchKernelGGL((KERNEL<NUM_, 4>), grid, dim3(256), 0, s, __VA_ARGS__); }
+#define BW_LAUNCH(KERNEL, ...)                                                                         \
+    switch (ctx->numerics) {                                                                           \
+        case RNNT_NUM_BF16: BW_LAUNCH_NUM(KERNEL, RNNT_NUM_BF16, __VA_ARGS__) break;                   \
+        case RNNT_NUM_F16X3: BW_LAUNCH_NUM(KERNEL, RNNT_NUM_F16X3, __VA_ARGS__) break;                 \
+        default: BW_LAUNCH_NUM(KERNEL, RNNT_NUM_BF16X3, __VA_ARGS__) break;                            \
+    }                                                                                                  \
+    LAUNCHCHK(#KERNEL)
     if (fused) {
         // the same tiles with the conv1 operand formed from the fbank in the tile staging (gemm_bw_c1): g.A stays null
         ProfScope prof(ctx, s, tag2);
@@ -376,33 +395,17 @@ int run_subsample(rnnt_ctx* ctx, hipStream_t s, const float* fbank, int B, int T
         if ((rc = prepare_gemm(ctx, g))) return rc;
         const dim3 grid((g.M + 127) / 128);
         const Conv1Src src{fbank, ctx->conv1_wt, ctx->conv1_b, starts_dev, B, Tstride, nc, out_cn > 0 ? 1 : 0};
-        static const bool nw8 = getenv("RNNT_BW_NW") ? atoi(getenv("RNNT_BW_NW")) == 8 : true;
-#define BWC_LAUNCH(NUM_) { if (nw8) hipLaunchKernelGGL((gemm_bw_c1<NUM_, 8>), grid, dim3(512), 0, s, g, ctx->conv2_wp, src); \
-                           else hipLaunchKernelGGL((gemm_bw_c1<NUM_, 4>), grid, dim3(256), 0, s, g, ctx->conv2_wp, src); }
-        switch (ctx->numerics) {
-            case RNNT_NUM_BF16: BWC_LAUNCH(RNNT_NUM_BF16) break;
-            case RNNT_NUM_F16X3: BWC_LAUNCH(RNNT_NUM_F16X3) break;
-            default: BWC_LAUNCH(RNNT_NUM_BF16X3) break;
-        }
-#undef BWC_LAUNCH
-        LAUNCHCHK("gemm_bw_c1");
+        BW_LAUNCH(gemm_bw_c1, g, ctx->conv2_wp, src);
     } else if (ctx->numerics != RNNT_NUM_F32 && conv2_bw && ctx->conv2_wp && g.M >= 32768 && !ctx->gemm_m_cap) {
         // whole-utterance slab: 128 x 256 tiles, weights streamed from L2 in fragment order, A rows four k-steps ahead (gemm_bw)
         ProfScope prof(ctx, s, tag2);
         if ((rc = prepare_gemm(ctx, g))) return rc;
         const dim3 grid((g.M + 127) / 128);
-        static const bool nw8 = getenv("RNNT_BW_NW") ? atoi(getenv("RNNT_BW_NW")) == 8 : true;   // 8 waves = two per SIMD (same results)
-#define BW_LAUNCH(NUM_) { if (nw8) hipLaunchKernelGGL((gemm_bw<NUM_, 8>), grid, dim3(512), 0, s, g, ctx->conv2_wp); \
-                          else hipLaunchKernelGGL((gemm_bw<NUM_, 4>), grid, dim3(256), 0, s, g, ctx->conv2_wp); }
-        switch (ctx->numerics) {
-            case RNNT_NUM_BF16: BW_LAUNCH(RNNT_NUM_BF16) break;
-            case RNNT_NUM_F16X3: BW_LAUNCH(RNNT_NUM_F16X3) break;
-            default: BW_LAUNCH(RNNT_NUM_BF16X3) break;
-        }
+        BW_LAUNCH(gemm_bw, g, ctx->conv2_wp);
 #undef BW_LAUNCH
-        LAUNCHCHK("gemm_bw");
+#undef BW_LAUNCH_NUM
     } else if (ctx->numerics != RNNT_NUM_F32) {
-        if ((rc = launch_gemm(ctx, s, 0, &g, 1, tag2))) return rc;
+        if ((rc = launch_gemm(ctx, s, &g, 1, tag2))) return rc;
     } else if (conv2_lds && g.M >= 2048 && !ctx->gemm_m_cap) {   // big M: LDS-tiled 64x64 tiles (full-line operand staging); N = 256 -> 4 column tiles
         ProfScope prof(ctx, s, tag2);
         GemmBatch gb;
@@ -412,12 +415,11 @@ int run_subsample(rnnt_ctx* ctx, hipStream_t s, const float* fbank, int B, int T
         if (conv2_lds == 2 && nc > 1) launch_gemm_ns<2, 2, false, true>(s, gb, g.M, g.N, 1);   // experiment: non-temporal A
         else launch_gemm_ns<2, 2>(s, gb, g.M, g.N, 1);
         LAUNCHCHK("gemm_ns");
-    } else if ((rc = launch_gemm(ctx, s, 0, &g, 1, tag2))) return rc;
+    } else if ((rc = launch_gemm(ctx, s, &g, 1, tag2))) return rc;
     // Linear(4864 -> 256) * sqrt(256); y2 is [VB*t', f*256 + c] (weight columns permuted to match)
     GemmP go = plain_gemm(y2, RNNT_FSUB * D, ctx->emb_w, RNNT_FSUB * D, ctx->emb_b, xout, D, VB * tq, D, RNNT_FSUB * D, EPI_SCALE, 16.0f);
     if (out_cn > 0) { go.c_n = out_cn; go.c_s0 = (long long)out_rows * D; go.c_r0 = out_r0; go.c_mod = BIG; go.c_s1 = D; }
-    if ((rc = launch_gemm(ctx, s, 0, &go, 1, tag3))) return rc;
-    return RNNT_OK;
+    return launch_gemm(ctx, s, &go, 1, tag3);
 }
 
 // ---- fused Conformer-block kernels (rnnt_fused.hip.h) ---------------------------------------------------------------------
@@ -476,31 +478,27 @@ int launch_gemm_tab(rnnt_ctx* ctx, hipStream_t s, const GemmP* tab_dev, int n, i
     ProfScope prof(ctx, s, tag);
     static const int ns_mode = getenv("RNNT_GEMM_NS") ? atoi(getenv("RNNT_GEMM_NS")) : 1;
     static const int ns_min = getenv("RNNT_NS_MIN_GROUPS") ? atoi(getenv("RNNT_NS_MIN_GROUPS")) : 2;   // pipeline fill/drain stages have few pairs
+    // XCDs per descriptor of the 1-D grids (see gemm_ns_tab): the largest split that keeps the groups balanced
+    static const int x_env = getenv("RNNT_XCD_X") ? atoi(getenv("RNNT_XCD_X")) : 0;
+    auto pick_x = [&](int ntn) {
+        if (x_env == 1 || x_env == 2 || x_env == 4 || x_env == 8) return x_env;
+        for (int X = 2; X < 8; X *= 2)
+            if (n % (8 / X) == 0 && ntn % X == 0) return X;
+        return 8;
+    };
+    auto grid_for_tab = [&](int ntn, int ntm, int X) {
+        const int dpg = (n + 8 / X - 1) / (8 / X), cpx = (ntn + X - 1) / X;
+        return dim3(8 * dpg * cpx * ntm);
+    };
+    const int ntn = N >= 512 ? (N + 63) / 64 : (N + 31) / 32, ntm = (maxM + 31) / 32, X = pick_x(ntn);   // 32-row tiles, 64 or 32 columns
     if (ctx->numerics != RNNT_NUM_F32 && K % 32 == 0) {   // split-operand modes: every stage GEMM on the 16-bit MFMA kernel
-        static const int x_env = getenv("RNNT_XCD_X") ? atoi(getenv("RNNT_XCD_X")) : 0;
-        auto pick_x = [&](int ntn) {
-            if (x_env == 1 || x_env == 2 || x_env == 4 || x_env == 8) return x_env;
-            for (int X = 2; X < 8; X *= 2)
-                if (n % (8 / X) == 0 && ntn % X == 0) return X;
-            return 8;
-        };
-        auto grid_for_tab = [&](int ntn, int ntm, int X) {
-            const int dpg = (n + 8 / X - 1) / (8 / X), cpx = (ntn + X - 1) / X;
-            return dim3(8 * dpg * cpx * ntm);
-        };
 #define BF_TAB(MT_, NT_)                                                                                                   \
     switch (ctx->numerics) {                                                                                               \
         case RNNT_NUM_BF16: hipLaunchKernelGGL((gemm_bf_tab<1, false, MT_, NT_>), grid_for_tab(ntn, ntm, X), dim3(256), 0, s, tab_dev, n, ntn, ntm, X); break; \
         case RNNT_NUM_F16X3: hipLaunchKernelGGL((gemm_bf_tab<2, true, MT_, NT_>), grid_for_tab(ntn, ntm, X), dim3(256), 0, s, tab_dev, n, ntn, ntm, X); break; \
         default: hipLaunchKernelGGL((gemm_bf_tab<2, false, MT_, NT_>), grid_for_tab(ntn, ntm, X), dim3(256), 0, s, tab_dev, n, ntn, ntm, X); break; \
     }
-        if (N >= 512) {
-            const int ntn = (N + 63) / 64, ntm = (maxM + 31) / 32, X = pick_x(ntn);
-            BF_TAB(1, 2)
-        } else {
-            const int ntn = (N + 31) / 32, ntm = (maxM + 31) / 32, X = pick_x(ntn);
-            BF_TAB(1, 1)
-        }
+        if (N >= 512) BF_TAB(1, 2) else BF_TAB(1, 1)
 #undef BF_TAB
         LAUNCHCHK("gemm_bf_tab");
         return RNNT_OK;
@@ -508,33 +506,14 @@ int launch_gemm_tab(rnnt_ctx* ctx, hipStream_t s, const GemmP* tab_dev, int n, i
     if (ns_mode && n >= ns_min && K % 32 == 0) {   // enough groups: no split-K, epilogue from registers
         // tile choice from tools/microbench2.hip (12 groups x 192 rows): the kernel is occupancy/latency-bound, so the
         // narrow shapes want many small workgroups; only K = 1024 profits from 64-deep K blocks (half the barriers)
-        // XCDs per descriptor (see gemm_ns_tab): the largest split that keeps the groups balanced
-        static const int x_env = getenv("RNNT_XCD_X") ? atoi(getenv("RNNT_XCD_X")) : 0;
-        auto pick_x = [&](int ntn) {
-            if (x_env == 1 || x_env == 2 || x_env == 4 || x_env == 8) return x_env;
-            for (int X = 2; X < 8; X *= 2)
-                if (n % (8 / X) == 0 && ntn % X == 0) return X;
-            return 8;
-        };
-        auto grid_for_tab = [&](int ntn, int ntm, int X) {
-            const int dpg = (n + 8 / X - 1) / (8 / X), cpx = (ntn + X - 1) / X;
-            return dim3(8 * dpg * cpx * ntm);
-        };
 #define NS_TAB(MT_, NT_, BK_)                                                                                              \
     switch (prefetch_depth()) {                                                                                            \
         case 1: hipLaunchKernelGGL((gemm_ns_tab<MT_, NT_, BK_, 1>), grid_for_tab(ntn, ntm, X), dim3(256), 0, s, tab_dev, n, ntn, ntm, X); break; \
         default: hipLaunchKernelGGL((gemm_ns_tab<MT_, NT_, BK_, 2>), grid_for_tab(ntn, ntm, X), dim3(256), 0, s, tab_dev, n, ntn, ntm, X); break; \
     }
-        if (N >= 512) {                       // ffn1 / pointwise_conv1: 32x64 tiles
-            const int ntn = (N + 63) / 64, ntm = (maxM + 31) / 32, X = pick_x(ntn);
-            NS_TAB(1, 2, 32)
-        } else if (K >= 1024) {               // ffn2: 32x32 tiles, BK = 64
-            const int ntn = (N + 31) / 32, ntm = (maxM + 31) / 32, X = pick_x(ntn);
-            NS_TAB(1, 1, 64)
-        } else {                              // q/k/v, linear_out, pointwise_conv2: 32x32 tiles
-            const int ntn = (N + 31) / 32, ntm = (maxM + 31) / 32, X = pick_x(ntn);
-            NS_TAB(1, 1, 32)
-        }
+        if (N >= 512) NS_TAB(1, 2, 32)            // ffn1 / pointwise_conv1: 32x64 tiles
+        else if (K >= 1024) NS_TAB(1, 1, 64)      // ffn2: 32x32 tiles, BK = 64
+        else NS_TAB(1, 1, 32)                     // q/k/v, linear_out, pointwise_conv2: 32x32 tiles
 #undef NS_TAB
         LAUNCHCHK("gemm_ns_tab");
         return RNNT_OK;
@@ -574,16 +553,16 @@ int greedy_steps_raw(rnnt_ctx* ctx, hipStream_t s, int n) {
         g1.X = ctx->egate; g1.I = ctx->tok; g1.X2 = ctx->c; g1.Y2 = ctx->c;
         g1.Asel = ctx->sel; g1.asel_stride = bs; g1.asel_invert = 0;
         g1.act_idx = ctx->fidx; g1.act_lim = ctx->n_active + 2;
-        if ((rc = launch_gemm(ctx, s, 0, &g1, 1, TAG_LSTM))) return rc;
+        if ((rc = launch_gemm(ctx, s, &g1, 1, TAG_LSTM))) return rc;
         GemmP g3 = plain_gemm(ctx->h, D, ctx->wjc, D, ctx->bjc, ctx->z, D, B, D, D, EPI_TANH_ADD);
         g3.Asel = ctx->sel; g3.asel_stride = bs; g3.asel_invert = 1;   // candidate h' lives in the other buffer
         g3.X = ctx->encp; g3.I = ctx->fidx; g3.x_n = 1; g3.x_s0 = (long long)ctx->fstride * D; g3.x_s1 = D;
         g3.act_idx = ctx->fidx; g3.act_lim = ctx->n_active + 2;
-        if ((rc = launch_gemm(ctx, s, 0, &g3, 1, TAG_JOINT_TANH))) return rc;
+        if ((rc = launch_gemm(ctx, s, &g3, 1, TAG_JOINT_TANH))) return rc;
         GemmP g4 = plain_gemm(ctx->z, D, ctx->wout, D, ctx->bout, ctx->logits, ctx->vpad, B, V, D, EPI_ARGMAX);
         g4.key = ctx->key; g4.I = ctx->fidx; g4.nframes = ctx->n_active + 2;
         g4.act_idx = ctx->fidx; g4.act_lim = ctx->n_active + 2;
-        if ((rc = launch_gemm(ctx, s, 0, &g4, 1, TAG_JOINT_OUT))) return rc;
+        if ((rc = launch_gemm(ctx, s, &g4, 1, TAG_JOINT_OUT))) return rc;
     }
     return RNNT_OK;
 }
@@ -795,6 +774,28 @@ int finish_persistent_decoder(rnnt_ctx* ctx, hipStream_t s) {
     }
     if (ctx->pinned[13] != 0) return fail(ctx, RNNT_ERR_STATE, "persistent decoder gave up (code %d: 1 = frame wait, 2 = barrier, 3 = idle bound)", ctx->pinned[13]);
     return RNNT_OK;
+}
+
+// the resident decoder over buffered frames that are all there: control block, launch, wait (synchronises s)
+int decode_resident(rnnt_ctx* ctx, hipStream_t s, int n_total, const int* nlim = nullptr, const int* slots = nullptr, int n_rows = 0, int n_steps = 0) {
+    int rc;
+    if ((rc = init_decoder_ctrl(ctx, s, n_total))) return rc;
+    if ((rc = launch_persistent_decoder(ctx, s, n_total, n_steps, nlim, slots, n_rows))) return rc;
+    return finish_persistent_decoder(ctx, s);
+}
+
+// The encoder's last two launches for a chunk: after_norm of rows x [B * tq] into frames [fpos, fpos + tq) of every stream's frame
+// buffer, then the joint's encoder projection of those frames.  ln_prologue (a greedy decode reads only enc_proj): after_norm runs in
+// the projection's LayerNorm prologue instead and the normalised frames are not materialised.
+int emit_frames(rnnt_ctx* ctx, hipStream_t s, const float* x, int B, int tq, int fpos, bool ln_prologue = false) {
+    const long long fs = (long long)ctx->fstride * D;
+    int rc;
+    if (!ln_prologue && (rc = launch_ln(ctx, s, LnP{x, ctx->after_g, ctx->after_b, ctx->encbuf, B * tq, tq, fpos, fs, (long long)D}))) return rc;
+    GemmP g = plain_gemm(ln_prologue ? x : ctx->encbuf + (size_t)fpos * D, D, ctx->wenc, D, ctx->benc, ctx->encp, D, B * tq, D, D);
+    if (ln_prologue) { g.ln_g = ctx->after_g; g.ln_b = ctx->after_b; }
+    else { g.a_n1 = tq; g.a_n2 = tq; g.a_s0 = fs; g.a_s1 = 0; g.a_s2 = D; }
+    g.c_n = tq; g.c_s0 = fs; g.c_r0 = fpos; g.c_mod = BIG; g.c_s1 = D;
+    return launch_gemm(ctx, s, &g, 1, TAG_ENC_PROJ);
 }
 
 template <typename T>

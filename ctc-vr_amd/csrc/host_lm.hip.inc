@@ -8,8 +8,6 @@
 
 namespace {
 
-struct ChunkInfo { int len, tq, T2, kv_row0, pos_start, ring_pos, fpos; size_t xoff; };
-
 // Is the plan one the layer-major schedule can run?  K/V rows of the call must have distinct homes in the cache:
 //   (A) no cache reset between chunks: rows advance contiguously from the first chunk's append position;
 //   (B) the usual fresh stream: the first chunk's K/V are dropped after it (required_cache_size = 0 -> the cache restarts at
@@ -19,7 +17,7 @@ struct LmPlan { bool ok; int c_r0, c_mod, park0; };
 LmPlan lm_plan(const rnnt_ctx* ctx, const std::vector<ChunkInfo>& ci, int F) {
     LmPlan p{false, 0, BIG, -1};
     const int C = (int)ci.size();
-    auto wrow = [&](int c) { return ci[c].kv_row0 + ci[c].T2 - ci[c].tq; };
+    auto wrow = [&](int c) { return ci[c].kv_w0(); };
     bool contiguous = true;
     for (int c = 1; c < C; ++c) contiguous = contiguous && wrow(c) == wrow(c - 1) + ci[c - 1].tq;
     if (contiguous) { p.ok = true; p.c_r0 = wrow(0); return p; }
@@ -407,11 +405,11 @@ int encoder_chunks_lm(rnnt_ctx* ctx, hipStream_t s, const float* fbank_dev, int 
         } else {
         g = plain_gemm(x, D, w.w1m, D, w.b1m, ctx->lm_h, FF, Mi, FF, D, EPI_SILU);
         g.ln_g = w.ln_ffm_g; g.ln_b = w.ln_ffm_b;
-        if ((rc = launch_gemm(ctx, s, 0, &g, 1, TAG_FFN1))) return rc;
+        if ((rc = launch_gemm(ctx, s, &g, 1, TAG_FFN1))) return rc;
         dbg("ffn1m", l, ctx->lm_h, M * FF);
         g = plain_gemm(ctx->lm_h, FF, w.w2m, FF, w.b2m, x, D, Mi, D, FF, EPI_RESID, 0.5f);
         g.R = x;
-        if ((rc = launch_gemm(ctx, s, 0, &g, 1, TAG_FFN2))) return rc;
+        if ((rc = launch_gemm(ctx, s, &g, 1, TAG_FFN2))) return rc;
         }
         dbg("ffn2m", l, x, M * D);
         if (tail) {
@@ -419,7 +417,7 @@ int encoder_chunks_lm(rnnt_ctx* ctx, hipStream_t s, const float* fbank_dev, int 
         } else if (as) {
             const uint4* wp[3] = {ld->wq, ld->wk, ld->wv};
             if ((rc = launch_gemm_as(ctx, s, qkv, wp, 3, TAG_QKV))) return rc;
-        } else if ((rc = launch_gemm(ctx, s, 0, qkv, 3, TAG_QKV))) return rc;
+        } else if ((rc = launch_gemm(ctx, s, qkv, 3, TAG_QKV))) return rc;
         }
         dbg("q", l, ctx->lm_q, M * D);
         dbg("kcache", l, kc, (long long)B * ctx->tcap * D);
@@ -457,13 +455,13 @@ int encoder_chunks_lm(rnnt_ctx* ctx, hipStream_t s, const float* fbank_dev, int 
         } else {
         g = plain_gemm(ctx->lm_a, D, w.wo, D, w.bo, x, D, Mi, D, D, EPI_RESID, 1.0f);
         g.R = x;
-        if ((rc = launch_gemm(ctx, s, 0, &g, 1, TAG_ATTN_OUT))) return rc;
+        if ((rc = launch_gemm(ctx, s, &g, 1, TAG_ATTN_OUT))) return rc;
         dbg("out", l, x, M * D);
         g = gpw1;
         if (as) {
             const uint4* wp[1] = {ld->pw1};
             if ((rc = launch_gemm_as(ctx, s, &g, wp, 1, TAG_PW1))) return rc;
-        } else if ((rc = launch_gemm(ctx, s, 0, &g, 1, TAG_PW1))) return rc;
+        } else if ((rc = launch_gemm(ctx, s, &g, 1, TAG_PW1))) return rc;
         dbg("pw1", l, gl, (long long)B * gs * D);
         }
         // pointwise_conv2 + residual in front of the FFN, inside its launch (x' stays in LDS): RNNT_LM_PW2_HEAD=0 keeps the two launches;
@@ -506,7 +504,7 @@ int encoder_chunks_lm(rnnt_ctx* ctx, hipStream_t s, const float* fbank_dev, int 
         g = plain_gemm(ctx->lm_d, D, w.pw2, D, w.bpw2, x, D, Mi, D, D, EPI_RESID, 1.0f);
         g.R = x;
         if (klen_dev) { g.rowlen = klen_dev; g.rowlen_n = F; }   // full-context pass: the conv module's output is zero on padded frames (convolution.py:148-150)
-        if ((rc = launch_gemm(ctx, s, 0, &g, 1, TAG_PW2))) return rc;
+        if ((rc = launch_gemm(ctx, s, &g, 1, TAG_PW2))) return rc;
         dbg("pw2", l, x, M * D);
         // x += 0.5 * FFN(LN(x)); x = LN_final(x)
         if (as) {
@@ -516,31 +514,18 @@ int encoder_chunks_lm(rnnt_ctx* ctx, hipStream_t s, const float* fbank_dev, int 
         }
         g = plain_gemm(x, D, w.w1, D, w.b1, ctx->lm_h, FF, Mi, FF, D, EPI_SILU);
         g.ln_g = w.ln_ff_g; g.ln_b = w.ln_ff_b;
-        if ((rc = launch_gemm(ctx, s, 0, &g, 1, TAG_FFN1))) return rc;
+        if ((rc = launch_gemm(ctx, s, &g, 1, TAG_FFN1))) return rc;
         dbg("ffn1", l, ctx->lm_h, M * FF);
         g = plain_gemm(ctx->lm_h, FF, w.w2, FF, w.b2, x, D, Mi, D, FF, EPI_RESID, 0.5f);
         g.R = x;
-        if ((rc = launch_gemm(ctx, s, 0, &g, 1, TAG_FFN2))) return rc;
+        if ((rc = launch_gemm(ctx, s, &g, 1, TAG_FFN2))) return rc;
         dbg("ffn2", l, x, M * D);
         if ((rc = launch_ln(ctx, s, LnP{x, w.ln_fin_g, w.ln_fin_b, x, Mi, BIG, 0, 0LL, (long long)D}))) return rc;
     }
     // ---- (e) after_norm into the frame buffer + joint.enc_ffn of every new frame ----------------------------------------------------
     if (out_plain) {
         if ((rc = launch_ln(ctx, s, LnP{x, ctx->after_g, ctx->after_b, out_plain, Mi, BIG, 0, 0LL, (long long)D}))) return rc;
-    } else if (greedy && ctx->use_persistent && ctx->fuse_after_norm) {
-        // greedy decode reads only enc_proj: after_norm goes into the projection's LayerNorm prologue and the normalised frames
-        // are not materialised (rnnt_get_enc_frames is not defined after such a call)
-        GemmP g = plain_gemm(x, D, ctx->wenc, D, ctx->benc, ctx->encp, D, Mi, D, D);
-        g.ln_g = ctx->after_g; g.ln_b = ctx->after_b;
-        g.c_n = F; g.c_s0 = (long long)ctx->fstride * D; g.c_r0 = fb0; g.c_mod = BIG; g.c_s1 = D;
-        if ((rc = launch_gemm(ctx, s, 0, &g, 1, TAG_ENC_PROJ))) return rc;
-    } else {
-        if ((rc = launch_ln(ctx, s, LnP{x, ctx->after_g, ctx->after_b, ctx->encbuf, Mi, F, fb0, (long long)ctx->fstride * D, (long long)D}))) return rc;
-        GemmP g = plain_gemm(ctx->encbuf + (size_t)fb0 * D, D, ctx->wenc, D, ctx->benc, ctx->encp, D, Mi, D, D);
-        g.a_n1 = F; g.a_n2 = F; g.a_s0 = (long long)ctx->fstride * D; g.a_s1 = 0; g.a_s2 = D;
-        g.c_n = F; g.c_s0 = (long long)ctx->fstride * D; g.c_r0 = fb0; g.c_mod = BIG; g.c_s1 = D;
-        if ((rc = launch_gemm(ctx, s, 0, &g, 1, TAG_ENC_PROJ))) return rc;
-    }
+    } else if ((rc = emit_frames(ctx, s, x, B, F, fb0, greedy && ctx->use_persistent && ctx->fuse_after_norm))) return rc;
     *handled = true;
     return RNNT_OK;
 }

@@ -35,6 +35,42 @@ struct HostTensor {
     std::vector<int64_t> dims;
 };
 
+// One chunk of a call: fbank frames, t' new encoder frames, key window [kv_row0, kv_row0 + T2), first positional row, ring frame count,
+// and where its frames go (fpos: frame buffer, xoff: x rows).
+struct ChunkInfo {
+    int len, tq, T2, kv_row0, pos_start, ring_pos, fpos; size_t xoff;
+    int kv_w0() const { return kv_row0 + T2 - tq; }   // the row its new K/V rows are appended at
+};
+
+// A stream's position in the reference's chunk loop (encoder.py:254-264,288).  The lock-step entry points share one (rnnt_ctx::pos),
+// every slot of the stream pool has its own; every entry point plans a chunk and moves on through these two methods.
+struct SlotPos {
+    int cache_len, kv_start, conv_pos;
+    // the windows of a chunk of tq new frames at `offset`; false (err: the bound it breaks) when they leave the positional table or the K/V buffer
+    bool plan(int tq, int offset, int tcap, ChunkInfo& out, std::string& err) const {
+        out.tq = tq;
+        out.T2 = cache_len + tq;               // attention_key_size (encoder.py:256)
+        out.pos_start = offset - cache_len;    // encoder.py:257
+        out.kv_row0 = kv_start;
+        out.ring_pos = conv_pos;
+        const bool in_table = out.pos_start >= 0 && out.pos_start + out.T2 <= RNNT_PE_LEN, in_cache = kv_start + out.T2 <= tcap;
+        if (!in_table) err = "positional window [" + std::to_string(out.pos_start) + ", " + std::to_string(out.pos_start + out.T2) + ") outside the 5000-entry table";
+        else if (!in_cache) err = "K/V cache capacity " + std::to_string(tcap) + " exceeded";
+        return in_table && in_cache;
+    }
+    // the cache truncation after a chunk with T2 keys (encoder.py:259-264); an empty cache re-bases its window at row 0
+    void advance(int T2, int tq, int required) {
+        const int next_start = required < 0 ? 0 : (required == 0 ? T2 : (T2 - required > 0 ? T2 - required : 0));
+        kv_start += next_start;
+        cache_len = T2 - next_start;
+        if (cache_len == 0) kv_start = 0;
+        conv_pos += tq;
+    }
+};
+
+// the launches of a wavefront stage (rnnt_ctx::WfLaunch): the eight GEMM shape classes first (they index wf_run_stage's shape table)
+enum WfType { WF_FFN1M, WF_FFN2M, WF_QKV, WF_OUT, WF_PW1, WF_PW2, WF_FFN1, WF_FFN2, WF_ATTN, WF_DW, WF_LN, WF_BLOCK_FRONT, WF_BLOCK_BACK };
+
 }  // namespace
 
 struct rnnt_ctx {
@@ -104,14 +140,13 @@ struct rnnt_ctx {
 
     // stream state (all streams lock step)
     int n_streams = 0;
-    int cache_len = 0, kv_start = 0, conv_pos = 0;
+    SlotPos pos{0, 0, 0};
     int frames_buffered = 0, frames_decoded = 0;
     int64_t launches = 0, greedy_steps = 0;
-    // stream pool (api_pool.hip.inc): once rnnt_stream_open or rnnt_pool_chunk has run, every slot has its own position and the three
-    // scalars above are dead until the next rnnt_streams_reset.  Positions are host integers advanced by the reference's bookkeeping
+    // stream pool (api_pool.hip.inc): once rnnt_stream_open or rnnt_pool_chunk has run, every slot has its own position and `pos`
+    // above is dead until the next rnnt_streams_reset.  Positions are host integers advanced by the reference's bookkeeping
     // (encoder.py:254-264) and mirrored per call into ONE device table: n PoolRow entries followed by the n slot indices the decoder
     // reads, written by one async copy from the pinned host copy (pool_ev: that copy has left the host buffer).
-    struct SlotPos { int cache_len, kv_start, conv_pos; };
     std::vector<SlotPos> slot_pos;
     bool pool_mode = false;
     int* pool_tab = nullptr;                   // device: [max_streams] PoolRow + [max_streams] int
@@ -126,16 +161,15 @@ struct rnnt_ctx {
     GemmP* wf_gtab = nullptr; AttnP* wf_atab = nullptr; DwP* wf_dtab = nullptr; LnP* wf_ltab = nullptr;
     size_t wf_gcap = 0, wf_acap = 0, wf_dcap = 0, wf_lcap = 0;
     hipStream_t dec_stream = nullptr;          // decode runs here while the encoder wavefront runs on the caller's stream
-    hipStream_t grp_stream[4] = {nullptr, nullptr, nullptr, nullptr};   // layer groups 1.. of the wavefront (group 0 = caller's stream)
     hipStream_t sub_stream = nullptr;          // subsampling slabs
-    int wf_groups = 1, wf_sub_async = 1;       // RNNT_WF_GROUPS (1..4; default 1: see api_encoder.hip.inc), RNNT_WF_SUB_ASYNC
+    int wf_sub_async = 1;                      // RNNT_WF_SUB_ASYNC=0: the wavefront's subsampling slabs on the caller's stream
     int wf_merge = 2;                          // RNNT_WF_MERGE (1..WF_MERGE_MAX): chunks of one layer per wavefront stage
     // descriptor tables of the last rnnt_encoder_chunks call, reused when the next call has the same plan and entry state
-    struct WfLaunch { int type, off, n, maxM, maxT2; };   // type 0..7 gemm (ffn1m ffn2m qkv out pw1 pw2 ffn1 ffn2), 10 attn, 11 dw, 12 ln
+    struct WfLaunch { WfType type; int off, n, maxM, maxT2; };
     std::vector<WfLaunch> wf_seq;
     std::vector<std::array<int, 13>> wf_lstart;
     std::vector<int> wf_sc_first, wf_key;
-    std::vector<hipEvent_t> ev_pool;
+    std::vector<hipEvent_t> ev_pool;           // events of a wavefront call (wf_buffers)
     // layer-major schedule (host_lm.hip.inc): activations over all B*F rows of a call, per-layer linear post-GLU rows, one
     // subsampling slab, attention block table (reused while the plan and the entry state stay the same)
     int use_lm = 1;                            // RNNT_LM=0: wavefront schedule for every whole-utterance call
@@ -185,7 +219,6 @@ struct rnnt_ctx {
     std::vector<DecGraph> dec_graphs;          // K greedy steps captured once per (n_streams, K)
     bool capturing = false;
     int use_graphs = 1;
-    std::vector<hipEvent_t> wf_ev;
     // optional per-kernel-site timing with HIP events on the launch stream (bench.py roofline leg)
     int prof_tag = -1;
     std::vector<hipEvent_t> prof_ev;
