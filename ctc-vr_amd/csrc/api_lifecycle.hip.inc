@@ -110,7 +110,8 @@ void rnnt_destroy(rnnt_ctx* ctx) {
     for (float* q : {ctx->fb_dft, ctx->fb_mel, ctx->fb_pad, ctx->fb_spec, ctx->fb_pow}) if (q) (void)hipFree(q);
     void* wf[] = {ctx->wf_x, ctx->wf_h, ctx->wf_q, ctx->wf_a, ctx->wf_d, ctx->wf_y1, ctx->wf_y2, ctx->wf_starts, ctx->wf_gtab, ctx->wf_atab,
                   ctx->wf_dtab, ctx->wf_ltab, ctx->lm_x, ctx->lm_h, ctx->lm_q, ctx->lm_a, ctx->lm_d, ctx->lm_g, ctx->lm_y1, ctx->lm_y2, ctx->lm_y1b, ctx->lm_y2b, ctx->lm_blocks, ctx->lm_rhdr, ctx->lm_rrows,
-                  ctx->rg_fb, ctx->rg_xt, ctx->rg_ent, ctx->bd_tok, ctx->bd_len, ctx->bd_sc, ctx->bd_hs, ctx->bd_nh, ctx->bd_fend};
+                  ctx->rg_fb, ctx->rg_xt, ctx->rg_ent, ctx->bd_tok, ctx->bd_len, ctx->bd_sc, ctx->bd_hs, ctx->bd_nh, ctx->bd_fend,
+                  ctx->ps_pool[0], ctx->ps_pool[1], ctx->ps_tok, ctx->ps_len, ctx->ps_sc, ctx->ps_hs, ctx->ps_nh};
     for (void* q : wf)
         if (q) (void)hipFree(q);
     delete ctx;
@@ -475,5 +476,5 @@ int rnnt_streams_reset(rnnt_ctx* ctx, int32_t n_streams, void* stream) {
         ctx->pool_cur = 0;
         HIPCHK(hipMemsetAsync(ctx->pool[0], 0, (size_t)ctx->max_rows * (ctx->cfg.n_steps + 1) * 512 * sizeof(float), s));
     }
-    return RNNT_OK;
+    return pool_beam_reset(ctx, s, 0, B);   // the per-slot beam state of the stream pool, once it exists
 }

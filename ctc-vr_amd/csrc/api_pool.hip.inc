@@ -1,5 +1,5 @@
 // C ABI: the stream pool -- slots of one context that open, advance and close independently (rnnt_stream_open, rnnt_pool_chunk,
-// rnnt_stream_get_tokens).  Included by rnnt_api.hip inside extern "C".
+// rnnt_pool_chunk_beam, rnnt_stream_get_tokens, rnnt_stream_get_beam, rnnt_stream_get_beam_states).  Included by rnnt_api.hip inside extern "C".
 //
 // Every stream's state already lives per stream on the device (K/V cache, the two conv rings, LSTM h/c, last token, token buffer);
 // the lock-step entry points only share its POSITION (SlotPos: cache_len, kv_start, conv_pos).  Here the position is per slot: plain
@@ -18,12 +18,30 @@ namespace {
 
 int pool_alloc(rnnt_ctx* ctx) {
     if (ctx->pool_tab) return RNNT_OK;
-    const size_t n = (size_t)ctx->cfg.max_streams * (POOL_ROW_INTS + 1);
+    const size_t n = (size_t)ctx->cfg.max_streams * (POOL_ROW_INTS + 2);   // + the slot list + the beam buffer index per active row
     int rc;
     if ((rc = dmalloc(ctx, &ctx->pool_tab, n))) return rc;
     HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&ctx->pool_tab_host), n * sizeof(int)));
     HIPCHK(hipEventCreateWithFlags(&ctx->pool_ev, hipEventDisableTiming));
     return RNNT_OK;
+}
+
+// the per-slot beam state (rnnt_ctx::ps_*), on the first beam call of a context with max_beam > 0: every slot starts with one
+// empty hypothesis (no beam call has run in any of them yet)
+int pool_beam_alloc(rnnt_ctx* ctx, hipStream_t s) {
+    if (ctx->ps_nh) return RNNT_OK;
+    const size_t R = ctx->max_rows, B = ctx->cfg.max_streams, state = R * (ctx->cfg.n_steps + 1) * 512;
+    int rc;
+    if (!ctx->ps_pool[0] && (rc = dmalloc(ctx, &ctx->ps_pool[0], state))) return rc;
+    if (!ctx->ps_pool[1] && (rc = dmalloc(ctx, &ctx->ps_pool[1], state))) return rc;
+    if (!ctx->ps_tok && (rc = dmalloc(ctx, &ctx->ps_tok, 2 * R * (size_t)ctx->cfg.max_tokens))) return rc;
+    if (!ctx->ps_len && (rc = dmalloc(ctx, &ctx->ps_len, 2 * R))) return rc;
+    if (!ctx->ps_sc && (rc = dmalloc(ctx, &ctx->ps_sc, 2 * R))) return rc;
+    if (!ctx->ps_hs && (rc = dmalloc(ctx, &ctx->ps_hs, 2 * R))) return rc;
+    if ((rc = dmalloc(ctx, &ctx->ps_nh, B))) return rc;
+    ctx->ps_cur.assign(B, 0);
+    ctx->ps_lbound.assign(B, 0);
+    return pool_beam_reset(ctx, s, 0, (int)B);
 }
 
 // from here on every slot has its own position (the lock-step entry points refuse until rnnt_streams_reset)
@@ -101,20 +119,34 @@ int rnnt_stream_open(rnnt_ctx* ctx, int32_t slot, void* stream) {
                        ctx->cfg.max_streams, ctx->cap, slot, ctx->h, ctx->c, ctx->sel, ctx->key, ctx->fidx, ctx->nsym, ctx->count, ctx->tok,
                        ctx->cfg.blank_id);
     LAUNCHCHK("stream_slot_reset");
+    if ((rc = pool_beam_reset(ctx, s, slot, 1))) return rc;   // the slot's beam: one empty hypothesis (once the beam state exists)
     pool_enter(ctx);
     ctx->slot_pos[slot] = SlotPos{0, 0, 0};
     return RNNT_OK;
 }
 
-int rnnt_pool_chunk(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, const float* fbank_dev, int32_t T, const int32_t* offsets_host,
-                    const int32_t* required_host, int32_t greedy, int32_t* frames_out, void* stream) {
-    if (!ctx || !slots_host || !fbank_dev || !offsets_host || !required_host) return fail(ctx, RNNT_ERR_ARG, "rnnt_pool_chunk: null argument");
-    if (!ctx->finalized || ctx->n_streams < 1) return fail(ctx, RNNT_ERR_STATE, "rnnt_pool_chunk: no weights / no streams");
-    if (greedy && !ctx->use_persistent) return fail(ctx, RNNT_ERR_STATE, "rnnt_pool_chunk: the greedy decode of a pool call needs the resident decoder");
+namespace {
+enum { POOL_ENCODE = 0, POOL_GREEDY = 1, POOL_BEAM = 2 };
+
+// rnnt_pool_chunk (mode POOL_ENCODE / POOL_GREEDY) and rnnt_pool_chunk_beam (POOL_BEAM): validation, the call's table, the encoder
+// launches and the position bookkeeping are one code path; only what follows the encoder differs.
+int pool_chunk_run(rnnt_ctx* ctx, const char* fn, int32_t n_active, const int32_t* slots_host, const float* fbank_dev, int32_t T,
+                   const int32_t* offsets_host, const int32_t* required_host, int mode, int32_t beam_size, int32_t* frames_out, void* stream) {
+    if (!ctx || !slots_host || !fbank_dev || !offsets_host || !required_host) return fail(ctx, RNNT_ERR_ARG, "%s: null argument", fn);
+    if (!ctx->finalized || ctx->n_streams < 1) return fail(ctx, RNNT_ERR_STATE, "%s: no weights / no streams", fn);
+    if (mode == POOL_GREEDY && !ctx->use_persistent) return fail(ctx, RNNT_ERR_STATE, "%s: the greedy decode of a pool call needs the resident decoder", fn);
+    const int V = ctx->cfg.vocab_size, NS = ctx->cfg.n_steps, W = ctx->cfg.max_beam;
+    if (mode == POOL_BEAM) {   // rnnt_beam_decode's range
+        if (ctx->max_rows == 0) return fail(ctx, RNNT_ERR_STATE, "%s: context created with max_beam = 0", fn);
+        if (!ctx->use_beam_chain) return fail(ctx, RNNT_ERR_STATE, "%s: RNNT_BEAM_CHAIN=0 (the device merge follows the chain kernel only)", fn);
+        if (beam_size < 1 || beam_size > W || beam_size > BM_MAX_BEAM)
+            return fail(ctx, RNNT_ERR_ARG, "%s: beam_size %d outside [1, min(max_beam %d, %d)]", fn, beam_size, W, BM_MAX_BEAM);
+        if (V > 512 || NS > BM_MAX_STEPS) return fail(ctx, RNNT_ERR_ARG, "%s: vocab %d > 512 or n_steps %d > %d", fn, V, NS, BM_MAX_STEPS);
+    }
     if (ctx->frames_buffered != 0)
-        return fail(ctx, RNNT_ERR_STATE, "rnnt_pool_chunk: %d buffered frames of an earlier call (rnnt_frames_discard / rnnt_frames_consume first)", ctx->frames_buffered);
+        return fail(ctx, RNNT_ERR_STATE, "%s: %d buffered frames of an earlier call (rnnt_frames_discard / rnnt_frames_consume first)", fn, ctx->frames_buffered);
     const int n = n_active;
-    if (n < 1 || n > ctx->n_streams) return fail(ctx, RNNT_ERR_ARG, "rnnt_pool_chunk: %d active slots of %d", n, ctx->n_streams);
+    if (n < 1 || n > ctx->n_streams) return fail(ctx, RNNT_ERR_ARG, "%s: %d active slots of %d", fn, n, ctx->n_streams);
     if (T < 7 || T > ctx->cfg.max_chunk_frames) return fail(ctx, RNNT_ERR_SHAPE, "chunk of %d frames outside [7, %d]", T, ctx->cfg.max_chunk_frames);
     const int tq = sub_len(T);
     if (tq > ctx->fcap) return fail(ctx, RNNT_ERR_SHAPE, "encoder-frame buffer capacity %d exceeded", ctx->fcap);
@@ -125,8 +157,8 @@ int rnnt_pool_chunk(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, 
     std::vector<PoolRow> rows((size_t)n);
     for (int i = 0; i < n; ++i) {
         const int slot = slots_host[i];
-        if (slot < 0 || slot >= ctx->n_streams) return fail(ctx, RNNT_ERR_ARG, "rnnt_pool_chunk: row %d: slot %d outside [0, %d)", i, slot, ctx->n_streams);
-        if (seen[slot]) return fail(ctx, RNNT_ERR_ARG, "rnnt_pool_chunk: slot %d listed twice", slot);
+        if (slot < 0 || slot >= ctx->n_streams) return fail(ctx, RNNT_ERR_ARG, "%s: row %d: slot %d outside [0, %d)", fn, i, slot, ctx->n_streams);
+        if (seen[slot]) return fail(ctx, RNNT_ERR_ARG, "%s: slot %d listed twice", fn, slot);
         seen[slot] = 1;
         ChunkInfo k;
         if (!pos_of(slot).plan(tq, offsets_host[i], ctx->tcap, k, err)) return fail(ctx, RNNT_ERR_SHAPE, "slot %d: %s", slot, err.c_str());
@@ -136,12 +168,37 @@ int rnnt_pool_chunk(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, 
     }
     hipStream_t s = (hipStream_t)stream;
     int rc;
+    if (mode == POOL_BEAM) {
+        // token capacity: a hypothesis grows by at most n_steps tokens per frame.  ps_lbound is a conservative bound of the slot's
+        // longest one; only when it would pass max_tokens is it refreshed from the device's lengths (one small synchronising copy, rare)
+        const int grow_by = tq * NS;
+        for (int i = 0; i < n; ++i) {
+            const int slot = rows[i].slot;
+            if (!ctx->ps_nh) {
+                if (grow_by > ctx->cfg.max_tokens) return fail(ctx, RNNT_ERR_SHAPE, "%s: slot %d: %d new tokens possible, max_tokens %d", fn, slot, grow_by, ctx->cfg.max_tokens);
+                continue;
+            }
+            if (ctx->ps_lbound[slot] + grow_by <= ctx->cfg.max_tokens) continue;
+            std::vector<int> len((size_t)W + 1);
+            HIPCHK(hipMemcpyAsync(len.data(), ctx->ps_len + (size_t)ctx->ps_cur[slot] * ctx->max_rows + (size_t)slot * W, W * sizeof(int), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(len.data() + W, ctx->ps_nh + slot, sizeof(int), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            int longest = 0;
+            for (int h = 0; h < len[W] && h < W; ++h) longest = std::max(longest, len[h]);
+            ctx->ps_lbound[slot] = longest;
+            if (longest + grow_by > ctx->cfg.max_tokens)
+                return fail(ctx, RNNT_ERR_SHAPE, "%s: slot %d: longest hypothesis %d + %d new tokens possible exceeds max_tokens %d", fn, slot, longest, grow_by, ctx->cfg.max_tokens);
+        }
+    }
     if ((rc = pool_alloc(ctx))) return rc;
+    if (mode == POOL_BEAM && (rc = pool_beam_alloc(ctx, s))) return rc;
     // ---- the call's table: one async copy, no synchronisation before the launches ---------------------------------------------------
     HIPCHK(hipEventSynchronize(ctx->pool_ev));             // the previous call's copy has left the pinned buffer (normally long ago)
     memcpy(ctx->pool_tab_host, rows.data(), (size_t)n * sizeof(PoolRow));
     for (int i = 0; i < n; ++i) ctx->pool_tab_host[(size_t)n * POOL_ROW_INTS + i] = rows[i].slot;
-    HIPCHK(hipMemcpyAsync(ctx->pool_tab, ctx->pool_tab_host, (size_t)n * (POOL_ROW_INTS + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+    if (mode == POOL_BEAM)
+        for (int i = 0; i < n; ++i) ctx->pool_tab_host[(size_t)n * (POOL_ROW_INTS + 1) + i] = ctx->ps_cur[rows[i].slot];
+    HIPCHK(hipMemcpyAsync(ctx->pool_tab, ctx->pool_tab_host, (size_t)n * (POOL_ROW_INTS + (mode == POOL_BEAM ? 2 : 1)) * sizeof(int), hipMemcpyHostToDevice, s));
     HIPCHK(hipEventRecord(ctx->pool_ev, s));
     const PoolRow* rows_dev = reinterpret_cast<const PoolRow*>(ctx->pool_tab);
     const int* slots_dev = ctx->pool_tab + (size_t)n * POOL_ROW_INTS;
@@ -160,7 +217,35 @@ int rnnt_pool_chunk(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, 
     }
     for (int i = 0; i < n; ++i) ctx->slot_pos[rows[i].slot].advance(rows[i].T2, tq, required_host[i]);
     if (frames_out) *frames_out = tq;
-    if (!greedy) {   // frames [0, t') of the active slots stay buffered for rnnt_get_enc_frames until rnnt_frames_discard
+    if (mode == POOL_BEAM) {
+        // ---- the per-frame loop of _decode_chunk_beam_search over frames [0, t') of exactly the active slots: launches only -------------
+        BeamChainP c;
+        memset(&c, 0, sizeof(c));
+        c.whh = ctx->whh_il; c.egate = ctx->egate; c.wpr = ctx->wpr; c.bpr = ctx->bpr; c.wpf = ctx->wpf; c.bpf = ctx->bpf;
+        c.wout = ctx->wout; c.bout = ctx->bout; c.encp = ctx->encp;
+        c.steps = ctx->b_steps; c.blank_lp = ctx->b_blank; c.top_lp = ctx->b_toplp; c.top_tok = ctx->b_toptok;
+        c.vocab = V; c.blank = ctx->cfg.blank_id; c.k = beam_size < V - 1 ? beam_size : V - 1; c.n_steps = NS; c.slots = NS + 1;   // :467
+        BeamMergeP m;
+        memset(&m, 0, sizeof(m));
+        m.steps = ctx->b_steps; m.blank_lp = ctx->b_blank; m.top_lp = ctx->b_toplp; m.top_tok = ctx->b_toptok;
+        m.slots = NS + 1; m.lcap = ctx->cfg.max_tokens; m.n_steps = NS; m.k = c.k; m.beam = beam_size; m.width = W;
+        m.blank = ctx->cfg.blank_id; m.fstride = ctx->fstride;
+        BeamPoolP q = pool_beam_params(ctx);
+        q.slots = slots_dev; q.cur0 = ctx->pool_tab + (size_t)n * (POOL_ROW_INTS + 1);
+        for (int f = 0; f < tq; ++f) {
+            q.f = f; m.f = f;
+            hipLaunchKernelGGL(beam_chain_pool, dim3(n * W), dim3(512), 0, s, c, q);
+            LAUNCHCHK("beam_chain_pool");
+            hipLaunchKernelGGL(beam_merge_pool, dim3(n), dim3(BM_NT), 0, s, m, q);
+            LAUNCHCHK("beam_merge_pool");
+        }
+        for (int i = 0; i < n; ++i) {
+            ctx->ps_cur[rows[i].slot] ^= tq & 1;
+            ctx->ps_lbound[rows[i].slot] += tq * NS;
+        }
+        return RNNT_OK;   // the frames are consumed: frames_buffered stays 0
+    }
+    if (mode == POOL_ENCODE) {   // frames [0, t') of the active slots stay buffered for rnnt_get_enc_frames until rnnt_frames_discard
         hipLaunchKernelGGL(pool_scatter_frames, dim3(grid_for((long long)n * tq * (D / 4))), dim3(256), 0, s, ctx->x, ctx->encbuf, rows_dev, n, tq,
                            (long long)ctx->fstride * D);
         LAUNCHCHK("pool_scatter_frames");
@@ -174,6 +259,76 @@ int rnnt_pool_chunk(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, 
         const int cnt = n - i0 < per ? n - i0 : per;
         if ((rc = decode_resident(ctx, s, tq, nullptr, slots_dev + i0, cnt))) return rc;   // synchronises
     }
+    return RNNT_OK;
+}
+}  // namespace
+
+int rnnt_pool_chunk(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, const float* fbank_dev, int32_t T, const int32_t* offsets_host,
+                    const int32_t* required_host, int32_t greedy, int32_t* frames_out, void* stream) {
+    return pool_chunk_run(ctx, "rnnt_pool_chunk", n_active, slots_host, fbank_dev, T, offsets_host, required_host, greedy ? POOL_GREEDY : POOL_ENCODE, 0,
+                          frames_out, stream);
+}
+
+int rnnt_pool_chunk_beam(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, const float* fbank_dev, int32_t T, const int32_t* offsets_host,
+                         const int32_t* required_host, int32_t beam_size, int32_t* frames_out, void* stream) {
+    return pool_chunk_run(ctx, "rnnt_pool_chunk_beam", n_active, slots_host, fbank_dev, T, offsets_host, required_host, POOL_BEAM, beam_size, frames_out,
+                          stream);
+}
+
+namespace {
+// the slot's hypothesis count and lengths from its current buffer set (synchronises); allocates the beam state if this is its first use
+int pool_beam_peek(rnnt_ctx* ctx, const char* fn, int slot, hipStream_t s, std::vector<int>& len, int& nh) {
+    if (!ctx->finalized || ctx->n_streams < 1) return fail(ctx, RNNT_ERR_STATE, "%s: no weights / no streams", fn);
+    if (ctx->max_rows == 0) return fail(ctx, RNNT_ERR_STATE, "%s: context created with max_beam = 0", fn);
+    if (slot < 0 || slot >= ctx->n_streams) return fail(ctx, RNNT_ERR_ARG, "%s: slot %d outside [0, %d)", fn, slot, ctx->n_streams);
+    int rc;
+    if ((rc = pool_beam_alloc(ctx, s))) return rc;
+    const int W = ctx->cfg.max_beam;
+    len.assign((size_t)W + 1, 0);
+    HIPCHK(hipMemcpyAsync(len.data(), ctx->ps_len + (size_t)ctx->ps_cur[slot] * ctx->max_rows + (size_t)slot * W, W * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(len.data() + W, ctx->ps_nh + slot, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    nh = len[W];
+    return RNNT_OK;
+}
+}  // namespace
+
+int rnnt_stream_get_beam(rnnt_ctx* ctx, int32_t slot, int32_t cap_hyps, int32_t cap_tokens, int32_t* n_hyp, int32_t* lens_host, int32_t* tokens_host,
+                         double* scores_host, void* stream) {
+    if (!ctx) return RNNT_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int> len;
+    int nh = 0, rc;
+    if ((rc = pool_beam_peek(ctx, "rnnt_stream_get_beam", slot, s, len, nh))) return rc;
+    if (n_hyp) *n_hyp = nh;
+    if (!lens_host && !tokens_host && !scores_host) return RNNT_OK;
+    if (cap_hyps < nh) return fail(ctx, RNNT_ERR_ARG, "rnnt_stream_get_beam: %d hypotheses, room for %d", nh, cap_hyps);
+    const size_t row0 = (size_t)ctx->ps_cur[slot] * ctx->max_rows + (size_t)slot * ctx->cfg.max_beam, lcap = (size_t)ctx->cfg.max_tokens;
+    for (int i = 0; i < nh; ++i) {
+        if (lens_host) lens_host[i] = len[i];
+        if (!tokens_host || len[i] == 0) continue;
+        if (cap_tokens < len[i]) return fail(ctx, RNNT_ERR_ARG, "rnnt_stream_get_beam: hypothesis %d has %d tokens, room for %d", i, len[i], cap_tokens);
+        HIPCHK(hipMemcpyAsync(tokens_host + (size_t)i * cap_tokens, ctx->ps_tok + (row0 + i) * lcap, (size_t)len[i] * sizeof(int), hipMemcpyDeviceToHost, s));
+    }
+    if (scores_host && nh > 0) HIPCHK(hipMemcpyAsync(scores_host, ctx->ps_sc + row0, (size_t)nh * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return RNNT_OK;
+}
+
+int rnnt_stream_get_beam_states(rnnt_ctx* ctx, int32_t slot, int32_t cap_hyps, float* h_host, float* c_host, void* stream) {
+    if (!ctx) return RNNT_ERR_ARG;
+    if (!h_host || !c_host) return fail(ctx, RNNT_ERR_ARG, "rnnt_stream_get_beam_states: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int> len;
+    int nh = 0, rc;
+    if ((rc = pool_beam_peek(ctx, "rnnt_stream_get_beam_states", slot, s, len, nh))) return rc;
+    if (cap_hyps < nh) return fail(ctx, RNNT_ERR_ARG, "rnnt_stream_get_beam_states: %d hypotheses, room for %d", nh, cap_hyps);
+    if (nh == 0) return RNNT_OK;
+    const size_t pitch = (size_t)(ctx->cfg.n_steps + 1) * 512 * sizeof(float);
+    const float* pool = ctx->ps_pool[ctx->ps_cur[slot]] + (size_t)slot * ctx->cfg.max_beam * (ctx->cfg.n_steps + 1) * 512;
+    HIPCHK(hipMemcpy2DAsync(h_host, D * sizeof(float), pool, pitch, D * sizeof(float), nh, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpy2DAsync(c_host, D * sizeof(float), pool + D, pitch, D * sizeof(float), nh, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
     return RNNT_OK;
 }
 

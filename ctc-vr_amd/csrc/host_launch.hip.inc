@@ -808,4 +808,23 @@ int grow(rnnt_ctx* ctx, T** p, size_t* cap, size_t need) {
     return rc;
 }
 
+// ---- per-slot beam state of the stream pool (rnnt_pool_chunk_beam; kernels in rnnt_beam.hip.h) --------------------------------------
+BeamPoolP pool_beam_params(const rnnt_ctx* ctx) {
+    BeamPoolP q;
+    memset(&q, 0, sizeof(q));
+    q.pool[0] = ctx->ps_pool[0]; q.pool[1] = ctx->ps_pool[1];
+    q.tk = ctx->ps_tok; q.len = ctx->ps_len; q.sc = ctx->ps_sc; q.hs = ctx->ps_hs; q.nh = ctx->ps_nh;
+    q.rows = ctx->max_rows; q.W = ctx->cfg.max_beam; q.lcap = ctx->cfg.max_tokens; q.fstride = ctx->fstride;
+    return q;
+}
+
+// one empty hypothesis in buffer set 0 for slots [slot0, slot0 + n); no-op until the state is allocated (pool_beam_alloc resets all)
+int pool_beam_reset(rnnt_ctx* ctx, hipStream_t s, int slot0, int n) {
+    if (!ctx->ps_nh) return RNNT_OK;
+    hipLaunchKernelGGL(beam_slot_reset, dim3(n), dim3(256), 0, s, pool_beam_params(ctx), slot0, ctx->cfg.n_steps + 1);
+    LAUNCHCHK("beam_slot_reset");
+    for (int b = slot0; b < slot0 + n; ++b) { ctx->ps_cur[b] = 0; ctx->ps_lbound[b] = 0; }
+    return RNNT_OK;
+}
+
 }  // namespace

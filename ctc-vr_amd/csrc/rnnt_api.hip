@@ -210,6 +210,15 @@ struct rnnt_ctx {
     int *bd_len = nullptr, *bd_nh = nullptr, *bd_fend = nullptr;
     double* bd_sc = nullptr;
     unsigned long long* bd_hs = nullptr;
+    // per-slot beam state of the stream pool (rnnt_pool_chunk_beam), separate from the lock-step state above and allocated on the
+    // first beam call: hypothesis i of slot b is row b * max_beam + i of two buffer sets -- state pools, token lists
+    // [2][max_rows][max_tokens], lengths / scores / hashes [2][max_rows] -- plus the hypotheses per slot.  Slots advance
+    // independently, so the current set is per slot (ps_cur, host); ps_lbound is a host upper bound of the slot's longest hypothesis.
+    float* ps_pool[2] = {nullptr, nullptr};
+    int *ps_tok = nullptr, *ps_len = nullptr, *ps_nh = nullptr;
+    double* ps_sc = nullptr;
+    unsigned long long* ps_hs = nullptr;
+    std::vector<int> ps_cur, ps_lbound;
     // feature front-end (rnnt_fbank): DFT / mel matrices for (fb_rate, fb_nfft) and grow-only work buffers
     float *fb_dft = nullptr, *fb_mel = nullptr, *fb_pad = nullptr, *fb_spec = nullptr, *fb_pow = nullptr;
     size_t fb_pad_cap = 0, fb_spec_cap = 0, fb_pow_cap = 0;

@@ -92,18 +92,17 @@ struct BeamChainP {
     int vocab, blank, k, n_steps, slots;
 };
 
-__global__ __launch_bounds__(512) void beam_chain(BeamChainP p) {
+// The chain of row r (its outputs go to steps / blank_lp / top_lp / top_tok [r]): `pool` is the row's state slots, `tok` the predictor
+// input of the first evaluation, `enc` the projected encoder frame.  One body for beam_chain and beam_chain_pool: the arithmetic of
+// a row does not depend on how the row was found.
+__device__ __forceinline__ void beam_chain_row(const BeamChainP& p, const int r, float* pool, int tok, const float* enc) {
     constexpr int NTH = 512;
     __shared__ __attribute__((aligned(16))) float hs[1][RNNT_D], cs[RNNT_D], h2[1][RNNT_D], pr[1][RNNT_D], zs[1][RNNT_D];
     __shared__ __attribute__((aligned(16))) float gates[4 * RNNT_D];
     __shared__ float lg[512];
     __shared__ int s_ctl[2];
-    const int tid = threadIdx.x, r = blockIdx.x;
-    if (p.live && !ldgi(p.live + r)) return;                       // whole workgroup: before the first barrier
-    float* pool = p.pool + (long long)r * p.slots * 512;
+    const int tid = threadIdx.x;
     if (tid < RNNT_D) { hs[0][tid] = ldg1(pool + tid); cs[tid] = ldg1(pool + RNNT_D + tid); }
-    int tok = ldgi(p.tok_in + r);
-    const float* enc = p.encp + (long long)ldgi(p.frame + r) * RNNT_D;
     __syncthreads();
     int st = 0;
     for (; st < p.n_steps; ++st) {
@@ -187,6 +186,12 @@ __global__ __launch_bounds__(512) void beam_chain(BeamChainP p) {
     if (tid == 0) p.steps[r] = st;
 }
 
+__global__ __launch_bounds__(512) void beam_chain(BeamChainP p) {
+    const int r = blockIdx.x;
+    if (p.live && !ldgi(p.live + r)) return;                       // whole workgroup: before the first barrier
+    beam_chain_row(p, r, p.pool + (long long)r * p.slots * 512, ldgi(p.tok_in + r), p.encp + (long long)ldgi(p.frame + r) * RNNT_D);
+}
+
 // new_pool[r][0] <- old_pool[src_row[r]][src_step[r]]  (state = [h(256) | c(256)])
 __global__ void beam_gather(const float* __restrict__ old_pool, float* __restrict__ new_pool, const int* __restrict__ src_row,
                             const int* __restrict__ src_step, int n_new, int slots) {
@@ -230,7 +235,10 @@ struct BeamMergeP {
     int slots, lcap, n_steps, k, beam, width, blank, f, fstride;
 };
 
-__global__ __launch_bounds__(BM_NT) void beam_merge_dev(BeamMergeP p) {
+// One stream's merge (rows row0 .. row0 + width of p's buffers; b: its entry of nh / fend and its frame-buffer row).  One body for
+// beam_merge_dev and beam_merge_pool.  fend == nullptr: the stream has frame f; tok_next == nullptr: the next chain finds its own
+// inputs (beam_chain_pool), so tok_next / frame_next / live / src_row / src_step are not written.
+__device__ __forceinline__ void beam_merge_stream_dev(const BeamMergeP& p, const int b) {
     __shared__ double sc[BM_MAX_CAND];
     __shared__ unsigned char taken[BM_MAX_CAND];
     __shared__ int h_base[BM_MAX_BEAM + 1], h_len[BM_MAX_BEAM];
@@ -241,9 +249,9 @@ __global__ __launch_bounds__(BM_NT) void beam_merge_dev(BeamMergeP p) {
     __shared__ double red_v[BM_NT / 64];
     __shared__ int red_i[BM_NT / 64];
     __shared__ int s_best;
-    const int b = blockIdx.x, tid = threadIdx.x, K1 = p.k + 1, row0 = b * p.width;
+    const int tid = threadIdx.x, K1 = p.k + 1, row0 = b * p.width;
     const int nh = p.nh[b];
-    if (p.f >= p.fend[b]) {                                          // stream finished: carry its rows over unchanged
+    if (p.fend && p.f >= p.fend[b]) {                                          // stream finished: carry its rows over unchanged
         for (int i = 0; i < nh; ++i) {
             const int r = row0 + i, len = p.len_in[r];
             for (int q = tid; q < len; q += BM_NT) p.tk_out[(long long)r * p.lcap + q] = p.tk_in[(long long)r * p.lcap + q];
@@ -353,15 +361,73 @@ __global__ __launch_bounds__(BM_NT) void beam_merge_dev(BeamMergeP p) {
             p.len_out[nr] = len;
             p.sc_out[nr] = sc[c];
             p.hs_out[nr] = acc_hash[a];
-            p.tok_next[nr] = len > 0 ? tok_at(i, st, j, len - 1) : p.blank;   // online_rnnt_model.py:429
-            p.frame_next[nr] = b * p.fstride + p.f + 1;
-            p.live[nr] = p.f + 1 < p.fend[b] ? 1 : 0;
-            p.src_row[nr] = row0 + i;
-            p.src_step[nr] = sstep;
+            if (p.tok_next) {
+                p.tok_next[nr] = len > 0 ? tok_at(i, st, j, len - 1) : p.blank;   // online_rnnt_model.py:429
+                p.frame_next[nr] = b * p.fstride + p.f + 1;
+                p.live[nr] = p.f + 1 < p.fend[b] ? 1 : 0;
+                p.src_row[nr] = row0 + i;
+                p.src_step[nr] = sstep;
+            }
         }
     }
-    if (tid >= n_acc && tid < p.width) p.live[row0 + tid] = 0;
+    if (p.tok_next && tid >= n_acc && tid < p.width) p.live[row0 + tid] = 0;
     if (tid == 0) p.nh[b] = n_acc;
+}
+
+__global__ __launch_bounds__(BM_NT) void beam_merge_dev(BeamMergeP p) { beam_merge_stream_dev(p, blockIdx.x); }
+
+// ------------------------------------------------------------------------------------------------
+// Stream pool (rnnt_pool_chunk_beam): every slot keeps its beam in HBM between calls, in FIXED rows -- hypothesis i of slot b is row
+// b * W + i (W = max_beam) of two buffer sets (token lists [2][rows][lcap], lengths / scores / hashes [2][rows], state pools
+// [2] x [rows][n_steps + 1][512]) -- and slots advance independently, so which set is current is per slot: cur0[a] at the call's
+// first frame for active row a (host bookkeeping, sent with the call's table), flipped once per frame.  A launch covers the ACTIVE
+// slots only: workgroup -> (active row, hypothesis) -> slot through the table; idle slots are neither read nor written.
+// ------------------------------------------------------------------------------------------------
+struct BeamPoolP {
+    const int* slots;            // [n] slot of active row a (the decoder's slot list of the pool table)
+    const int* cur0;             // [n] current buffer set of that slot at frame 0 of the call
+    float* pool[2];              // state pools
+    int* tk; int* len; double* sc; unsigned long long* hs;   // [2][rows](...)
+    int* nh;                     // [slots] hypotheses per slot
+    int rows, W, lcap, f, fstride;
+};
+
+// beam_chain for the live rows of the active slots at frame f of the call: input token = the hypothesis' last token (blank for the
+// empty one, online_rnnt_model.py:429), encoder frame row slot * fstride + f, state pool of the slot's current set.
+__global__ __launch_bounds__(512) void beam_chain_pool(BeamChainP p, BeamPoolP q) {
+    const int a = blockIdx.x / q.W, i = blockIdx.x - a * q.W;
+    const int slot = ldgi(q.slots + a);
+    if (i >= ldgi(q.nh + slot)) return;                            // no hypothesis in this row: before the first barrier
+    const int cur = (ldgi(q.cur0 + a) + q.f) & 1, r = slot * q.W + i;
+    const long long cr = (long long)cur * q.rows + r;
+    const int len = ldgi(q.len + cr);
+    const int tok = len > 0 ? ldgi(q.tk + cr * q.lcap + len - 1) : p.blank;
+    beam_chain_row(p, r, q.pool[cur] + (long long)r * p.slots * 512, tok, p.encp + ((long long)slot * q.fstride + q.f) * RNNT_D);
+}
+
+// beam_merge_dev's algorithm for one ACTIVE slot per workgroup: from the slot's current buffer set into its other one (the host
+// flips its index once per frame).  p carries the call's scalars and beam_chain_pool's outputs; its buffer pointers are set here.
+__global__ __launch_bounds__(BM_NT) void beam_merge_pool(BeamMergeP p, BeamPoolP q) {
+    const int a = blockIdx.x, slot = ldgi(q.slots + a);
+    const int cur = (ldgi(q.cur0 + a) + q.f) & 1, nxt = cur ^ 1;
+    const long long ri = (long long)cur * q.rows, ro = (long long)nxt * q.rows;
+    p.pool_in = q.pool[cur]; p.pool_out = q.pool[nxt];
+    p.tk_in = q.tk + ri * q.lcap; p.tk_out = q.tk + ro * q.lcap;
+    p.len_in = q.len + ri; p.len_out = q.len + ro;
+    p.sc_in = q.sc + ri; p.sc_out = q.sc + ro;
+    p.hs_in = q.hs + ri; p.hs_out = q.hs + ro;
+    p.nh = q.nh;
+    beam_merge_stream_dev(p, slot);
+}
+
+// rnnt_stream_open / rnnt_streams_reset for the per-slot beam state of slots [slot0, slot0 + gridDim.x): one empty hypothesis with
+// score 0.0, the initial hash and the zero LSTM state (online_rnnt_model.py:407-415) in buffer set 0 (the host's index goes to 0
+// with it).  Touches no other slot.
+__global__ __launch_bounds__(256) void beam_slot_reset(BeamPoolP q, int slot0, int state_slots) {
+    const int slot = slot0 + blockIdx.x, r0 = slot * q.W;
+    for (int e = threadIdx.x; e < 512; e += 256) q.pool[0][(long long)r0 * state_slots * 512 + e] = 0.f;
+    if (threadIdx.x < q.W) { q.len[r0 + threadIdx.x] = 0; q.sc[r0 + threadIdx.x] = 0.0; q.hs[r0 + threadIdx.x] = BEAM_HASH0; }
+    if (threadIdx.x == 0) q.nh[slot] = 1;
 }
 
 // End of rnnt_beam_decode: fixed-slot row r = b * width + i (i < nh[b]) -> compacted row (hypotheses of streams < b) + i,

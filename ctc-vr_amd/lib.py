@@ -46,6 +46,9 @@ SIGNATURES = {
     "rnnt_stream_open": (c_i32, [c_vp, c_i32, c_vp]),
     "rnnt_pool_chunk": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32p, c_vp]),
     "rnnt_stream_get_tokens": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32p, c_vp]),
+    "rnnt_pool_chunk_beam": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32p, c_vp]),
+    "rnnt_stream_get_beam": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32p, c_vp, c_vp, c_vp, c_vp]),
+    "rnnt_stream_get_beam_states": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "rnnt_predictor_step": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "rnnt_joint": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "rnnt_encoder_full": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32p, c_vp]),
@@ -123,7 +126,8 @@ def _np_ptr(a):
 
 class RnntEngine:
     """One context = one GPU = up to `max_streams` streams: lock-stepped (encoder_chunk / encoder_chunks / decode_ragged), or the
-    slots of a stream pool that open, advance and close independently (stream_open / pool_chunk / stream_tokens)."""
+    slots of a stream pool that open, advance and close independently (stream_open / pool_chunk / stream_tokens, and per-slot beam
+    search through pool_chunk_beam / stream_beam / stream_beam_states)."""
 
     def __init__(self, max_streams=1, max_chunk_frames=64, max_cache_frames=1024, max_enc_frames=1024, max_tokens=4096,
                  vocab_size=412, blank_id=5, n_steps=10, device=0, max_beam=0):
@@ -225,6 +229,40 @@ class RnntEngine:
         out = np.zeros(n.value, np.int32)
         self._chk(self.lib.rnnt_stream_get_tokens(self.ctx, slot, start, out.size, _np_ptr(out), ctypes.byref(n), stream), "rnnt_stream_get_tokens")
         return out[:min(n.value, out.size)].tolist()
+
+    def pool_chunk_beam(self, slots, fbank_ptr, chunk_frames, offsets, required, beam_size=4, stream=None):
+        """rnnt_pool_chunk_beam: pool_chunk's encoder for the listed slots, then the beam recursion over the new frames of exactly
+        those slots, each on its own device-resident beam; the frames are consumed.  Does not synchronise (stream_beam does).
+        Returns t'.  Raises RnntError when the call refuses (max_beam = 0, beam_size > min(max_beam, 16), vocab > 512, ...)."""
+        a, o, r = (np.ascontiguousarray(v, np.int32) for v in (slots, offsets, required))
+        assert a.ndim == 1 and a.size == o.size == r.size
+        t = c_i32(0)
+        self._chk(self.lib.rnnt_pool_chunk_beam(self.ctx, a.size, _np_ptr(a), fbank_ptr, chunk_frames, _np_ptr(o), _np_ptr(r), beam_size,
+                                                ctypes.byref(t), stream), "rnnt_pool_chunk_beam")
+        return t.value
+
+    def stream_beam(self, slot, stream=None):
+        """rnnt_stream_get_beam: [(tokens, log_prob), ...] of one slot in beam order."""
+        n = c_i32(0)
+        self._chk(self.lib.rnnt_stream_get_beam(self.ctx, slot, 0, 0, ctypes.byref(n), None, None, None, stream), "rnnt_stream_get_beam")
+        if n.value == 0:
+            return []
+        lens = np.zeros(n.value, np.int32)
+        self._chk(self.lib.rnnt_stream_get_beam(self.ctx, slot, n.value, 0, ctypes.byref(n), _np_ptr(lens), None, None, stream), "rnnt_stream_get_beam")
+        cap = max(int(lens.max()), 1)
+        toks, sc = np.zeros((n.value, cap), np.int32), np.zeros(n.value, np.float64)
+        self._chk(self.lib.rnnt_stream_get_beam(self.ctx, slot, n.value, cap, ctypes.byref(n), _np_ptr(lens), _np_ptr(toks), _np_ptr(sc), stream),
+                  "rnnt_stream_get_beam")
+        return [(toks[i, :lens[i]].tolist(), float(sc[i])) for i in range(n.value)]
+
+    def stream_beam_states(self, slot, stream=None):
+        """rnnt_stream_get_beam_states: (h, c), each [n_hyp, 256], of one slot's hypotheses in beam order."""
+        n = c_i32(0)
+        self._chk(self.lib.rnnt_stream_get_beam(self.ctx, slot, 0, 0, ctypes.byref(n), None, None, None, stream), "rnnt_stream_get_beam")
+        h, c = np.zeros((n.value, 256), np.float32), np.zeros((n.value, 256), np.float32)
+        if n.value:
+            self._chk(self.lib.rnnt_stream_get_beam_states(self.ctx, slot, n.value, _np_ptr(h), _np_ptr(c), stream), "rnnt_stream_get_beam_states")
+        return h, c
 
     def decode_ragged(self, fbank_ptr, total_frames, lens, chunk_frames, stream=None):
         """rnnt_decode_ragged: every stream over its own lens[b] frames (decode-script chunk loop), one call; returns encoder frames per stream."""

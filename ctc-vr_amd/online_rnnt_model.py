@@ -647,7 +647,7 @@ class StreamingBatch:
         return self.engine.tokens(_stream_ptr())
 
 
-def pool_plan(queue, offsets):
+def pool_plan(queue, offsets, beams=None):
     """The library calls of one StreamPool.step as a pure function (no GPU, no tensors).
 
     queue: [(slot, length)] in feed order, several entries per slot allowed; offsets: {slot: encoder offset so far}.
@@ -656,9 +656,14 @@ def pool_plan(queue, offsets):
     chunks keep their feed order across calls (its r-th queued chunk goes into round r, rounds run one after the other, and
     inside a round the length classes run in ascending length).  Per slot the bookkeeping is process_single_chunk's
     (model/online_rnnt_model.py:356-359,364-370,384-385): a chunk shorter than 7 frames is skipped without touching the offset, a
-    chunk is encoded with offset = required_cache_size = the slot's offset so far, and the offset then grows by length // 4."""
+    chunk is encoded with offset = required_cache_size = the slot's offset so far, and the offset then grows by length // 4.
+
+    beams: {slot: beam size} (0 or absent = greedy), None = all greedy and the result above.  With it every call is
+    (length, slots, offsets, beam_size): one chunk length AND one beam size per call -- beam_size 0 is an rnnt_pool_chunk call,
+    beam_size > 0 an rnnt_pool_chunk_beam call -- so greedy and beam slots never share a call; inside a round the classes run in
+    ascending (length, beam size).  Feed order per slot and the round structure are the same."""
     offs = dict(offsets)
-    rounds: List[Dict[int, List[Tuple[int, int]]]] = []        # round -> length -> [(slot, queue index)]
+    rounds: List[Dict[Tuple[int, int], List[Tuple[int, int]]]] = []   # round -> (length, beam) -> [(slot, queue index)]
     depth: Dict[int, int] = {}
     index: List[Optional[Tuple[int, int]]] = [None] * len(queue)
     for k, (slot, length) in enumerate(queue):
@@ -668,17 +673,17 @@ def pool_plan(queue, offsets):
         depth[slot] = r + 1
         while len(rounds) <= r:
             rounds.append({})
-        rounds[r].setdefault(int(length), []).append((slot, k))
+        rounds[r].setdefault((int(length), int(beams.get(slot, 0)) if beams else 0), []).append((slot, k))
     calls = []
     for rnd in rounds:
-        for length in sorted(rnd):
+        for length, beam in sorted(rnd):
             slots, call_offs = [], []
-            for slot, k in rnd[length]:
+            for slot, k in rnd[(length, beam)]:
                 index[k] = (len(calls), len(slots))
                 slots.append(slot)
                 call_offs.append(offs.get(slot, 0))
                 offs[slot] = offs.get(slot, 0) + length // 4
-            calls.append((length, slots, call_offs))
+            calls.append((length, slots, call_offs) if beams is None else (length, slots, call_offs, beam))
     return calls, offs, index
 
 
@@ -686,19 +691,25 @@ class StreamPool:
     """A context's slots, each with its own life (not in the reference, which is B=1): open() a slot when a caller connects, feed()
     it a chunk whenever the caller has one, step() to advance whatever subset of slots has chunks queued -- each at its own cache
     length, positional window and encoder offset, through rnnt_pool_chunk -- and close() it when the caller hangs up.  The tokens of
-    an utterance are those of process_single_chunk on a model that holds only that stream, whatever the other slots do.  Greedy
-    only (the beam state of the context is per context, not per slot)."""
+    an utterance are those of process_single_chunk on a model that holds only that stream, whatever the other slots do.
+    Beam search per slot (max_beam > 0): open(beam_size=k) gives the slot a beam of its own, resident on the device, advanced by
+    rnnt_pool_chunk_beam; beams(slot) returns what process_single_chunk_beam_search returns after each chunk, and close(slot) the
+    final hypotheses.  Greedy and beam slots live side by side in one pool; a library call holds slots of one kind."""
 
     def __init__(self, state_dict, n_slots: int, vocab_size: int = 412, blank_id: int = 5, max_chunk_frames: int = 64,
-                 max_cache_frames: int = 512, max_tokens: int = 4096, device: int = 0, numerics=None, packed=None, engine=None):
-        """state_dict / packed: as StreamingBatch.  engine: an object with reset / stream_open / pool_chunk / stream_tokens to drive
-        instead of a new RnntEngine (a recording fake in the CPU tests)."""
+                 max_cache_frames: int = 512, max_tokens: int = 4096, device: int = 0, numerics=None, packed=None, engine=None,
+                 max_beam: int = 0):
+        """state_dict / packed: as StreamingBatch.  engine: an object with reset / stream_open / pool_chunk / stream_tokens (and
+        pool_chunk_beam / stream_beam for beam slots) to drive instead of a new RnntEngine (a recording fake in the CPU tests).
+        max_beam: the largest beam_size open() may be given (0: greedy only)."""
         self.n = n_slots
         self.blank_id = blank_id
+        self.max_beam = max_beam
+        self.vocab_size = vocab_size
         if engine is None:
             engine = RnntEngine(max_streams=n_slots, max_chunk_frames=max_chunk_frames, max_cache_frames=max_cache_frames,
                                 max_enc_frames=max(16, (max_chunk_frames + 3) // 4), max_tokens=max_tokens, vocab_size=vocab_size,
-                                blank_id=blank_id, n_steps=10, device=device, max_beam=0)
+                                blank_id=blank_id, n_steps=10, device=device, max_beam=max_beam)
             if packed is not None:
                 assert state_dict is None and int(packed[1]) == vocab_size, "packed=(blob, vocab): vocab must equal vocab_size"
                 engine.load_packed(packed[0], int(packed[1]), numerics=numerics)
@@ -713,6 +724,7 @@ class StreamPool:
         self._free = list(range(self.n))
         self._offset: Dict[int, int] = {}
         self._ntok: Dict[int, int] = {}
+        self._beam: Dict[int, int] = {}                 # beam size of the open slots (0 = greedy)
         self._queue: List[Tuple[int, torch.Tensor]] = []
         self._carry: Dict[int, List[int]] = {}          # increments of other slots produced by the step inside a close()
 
@@ -720,14 +732,20 @@ class StreamPool:
     def _stream(t):
         return _stream_ptr() if (t is None and torch.cuda.is_available()) or (t is not None and t.is_cuda) else None
 
-    def open(self) -> int:
-        """The lowest free slot, reset for a new utterance (reset_streaming_cache for that slot alone)."""
+    def open(self, beam_size: int = 0) -> int:
+        """The lowest free slot, reset for a new utterance (reset_streaming_cache for that slot alone).  beam_size > 0: the slot's
+        utterance is beam-searched with that beam (its hypotheses start as the one empty hypothesis); raises RnntError at once
+        when this pool cannot do it."""
+        if beam_size < 0 or beam_size > 0 and (beam_size > min(self.max_beam, 16) or self.vocab_size > 512):
+            raise RnntError(f"stream pool: beam_size {beam_size} outside [0, min(max_beam {self.max_beam}, 16)] or vocabulary "
+                            f"{self.vocab_size} > 512")
         if not self._free:
             raise RnntError(f"stream pool full: all {self.n} slots are open")
         slot = self._free.pop(0)
         self.engine.stream_open(slot, self._stream(None))
         self._offset[slot] = 0
         self._ntok[slot] = 0
+        self._beam[slot] = int(beam_size)
         return slot
 
     def feed(self, slot: int, chunk: torch.Tensor) -> bool:
@@ -743,18 +761,23 @@ class StreamPool:
         return True
 
     def step(self) -> Dict[int, List[int]]:
-        """Advance every slot that has chunks queued: one rnnt_pool_chunk call per chunk length (pool_plan), the rows of a call
-        gathered into one contiguous device tensor.  Returns {slot: tokens emitted by this step} for the slots that advanced."""
+        """Advance every slot that has chunks queued: one rnnt_pool_chunk call per chunk length of the greedy slots and one
+        rnnt_pool_chunk_beam call per (chunk length, beam size) of the beam slots (pool_plan), the rows of a call gathered into one
+        contiguous device tensor.  Returns {slot: tokens emitted by this step} for the GREEDY slots that advanced; a beam slot's
+        hypotheses are read with beams(slot)."""
         out, self._carry = self._carry, {}
         if not self._queue:
             return out
-        calls, offs, index = pool_plan([(slot, c.size(0)) for slot, c in self._queue], self._offset)
-        rows: List[List[Optional[torch.Tensor]]] = [[None] * len(slots) for _, slots, _ in calls]
+        calls, offs, index = pool_plan([(slot, c.size(0)) for slot, c in self._queue], self._offset, self._beam)
+        rows: List[List[Optional[torch.Tensor]]] = [[None] * len(call[1]) for call in calls]
         for (slot, c), at in zip(self._queue, index):
             rows[at[0]][at[1]] = c
         touched = []
-        for (length, slots, call_offs), chunks in zip(calls, rows):
+        for (length, slots, call_offs, beam), chunks in zip(calls, rows):
             x = torch.stack(chunks, 0).contiguous()
+            if beam > 0:
+                self.engine.pool_chunk_beam(slots, x.data_ptr(), length, call_offs, call_offs, beam, self._stream(x))
+                continue
             self.engine.pool_chunk(slots, x.data_ptr(), length, call_offs, call_offs, True, self._stream(x))
             touched.extend(s for s in slots if s not in touched)
         self._offset = offs
@@ -765,15 +788,23 @@ class StreamPool:
             out[slot] = out.get(slot, []) + new
         return out
 
-    def close(self, slot: int) -> List[int]:
-        """Finish the slot's utterance (queued chunks are processed first) and free the slot; returns all its tokens."""
+    def beams(self, slot: int) -> List[BeamHypothesis]:
+        """The current hypotheses of a beam slot, in beam order: what process_single_chunk_beam_search returns after each chunk
+        (:605-645), also after a skipped < 7-frame chunk (:616-619).  Chunks still queued are not in them: step() first."""
+        if self._beam.get(slot, 0) <= 0:
+            raise RnntError(f"slot {slot} is not an open beam slot")
+        return [BeamHypothesis(t, lp) for t, lp in self.engine.stream_beam(slot, self._stream(None))]
+
+    def close(self, slot: int):
+        """Finish the slot's utterance (queued chunks are processed first) and free the slot; returns all its tokens (greedy slot)
+        or its final hypotheses (beam slot)."""
         if slot not in self._offset:
             raise RnntError(f"slot {slot} is not open")
         if any(s == slot for s, _ in self._queue):
             self._carry = self.step()                   # the other slots' increments are handed out by the next step()
         self._carry.pop(slot, None)
-        toks = self.engine.stream_tokens(slot, 0, self._stream(None))
-        del self._offset[slot], self._ntok[slot]
+        res = self.beams(slot) if self._beam[slot] > 0 else self.engine.stream_tokens(slot, 0, self._stream(None))
+        del self._offset[slot], self._ntok[slot], self._beam[slot]
         self._free.append(slot)
         self._free.sort()
-        return toks
+        return res

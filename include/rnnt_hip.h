@@ -139,7 +139,13 @@ int rnnt_frames_consume(rnnt_ctx* ctx, void* stream);
  * alone (n_streams = 1) through rnnt_encoder_chunk + rnnt_greedy_decode + rnnt_frames_consume, bit for bit, whatever the other
  * slots do.  Once rnnt_stream_open or rnnt_pool_chunk has run, the slots' positions may differ: rnnt_encoder_chunk,
  * rnnt_encoder_chunks, rnnt_decode_ragged and rnnt_encode_ragged refuse with RNNT_ERR_STATE until the next rnnt_streams_reset, and
- * the read-back getters return each slot's own state.  Pool calls leave the context's beam-search state alone.
+ * the read-back getters return each slot's own state.  Pool calls leave the context's beam-search state alone: the lock-step
+ * hypotheses and state pools of rnnt_beam_advance / rnnt_beam_decode / rnnt_beam_select.  The pool's own beam search
+ * (rnnt_pool_chunk_beam) keeps a beam PER SLOT, resident on the device between calls and separate from that state: hypothesis i of
+ * slot b is the fixed row b * max_beam + i (token list of capacity max_tokens, length, f64 score, 64-bit sequence hash, LSTM state),
+ * allocated on the first beam call of a context created with max_beam > 0.  rnnt_stream_open also resets its slot's beam to the one
+ * empty hypothesis with score 0 and the zero LSTM state (online_rnnt_model.py:407-415), rnnt_streams_reset those of all slots.  A
+ * slot's greedy state and its beam are independent: greedy and beam calls may be mixed freely across the slots of a context.
  *
  * rnnt_stream_open: reset_streaming_cache (model/online_rnnt_model.py:145-164) for ONE slot in [0, n_streams) -- empty K/V cache,
  * conv left context of a fresh stream, zero LSTM state, last token = blank, token count 0, position 0.  Touches no other slot.
@@ -160,6 +166,28 @@ int rnnt_stream_open(rnnt_ctx* ctx, int32_t slot, void* stream);
  * decided on the host before the first launch and change no slot's state. */
 int rnnt_pool_chunk(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, const float* fbank_dev, int32_t chunk_frames,
                     const int32_t* offsets_host, const int32_t* required_host, int32_t greedy, int32_t* frames_out, void* stream);
+/* rnnt_pool_chunk for the listed slots (same arguments, validation, encoder launches and position bookkeeping), followed by the
+ * per-frame loop of _decode_chunk_beam_search (model/online_rnnt_model.py:419-518) over the new frames [0, t') of exactly those
+ * slots, each on its own resident beam: per frame one extension-chain launch over the active slots' rows and one merge launch with
+ * one workgroup per active slot (rnnt_beam_decode's kernels' arithmetic; no upload of hypotheses, no gather / compaction, no
+ * download).  The frames are consumed: one call = encode + beam + consume.  Does not synchronise; the getters below do.
+ * Contract: a slot's hypotheses, their order, f64 scores and LSTM states are those of a one-stream context run chunk by chunk
+ * through rnnt_encoder_chunk + rnnt_beam_decode + rnnt_frames_discard, bit for bit, whatever the other slots do.
+ * beam_size applies to every row of the call and may change from call to call.  Range: that of rnnt_beam_decode (beam_size <=
+ * min(max_beam, 16), vocab_size <= 512, n_steps <= 10, the chain kernel enabled).  Refusals, all decided on the host before the first
+ * launch and changing no slot's state or position: every refusal of rnnt_pool_chunk; beam_size outside the range, vocab_size > 512:
+ * RNNT_ERR_ARG; max_beam = 0 or RNNT_BEAM_CHAIN=0: RNNT_ERR_STATE; a listed slot whose longest hypothesis + t' * n_steps would pass
+ * max_tokens: RNNT_ERR_SHAPE (the library keeps a conservative host bound per slot and reads the slot's true lengths back, with one
+ * small synchronising copy, only when that bound is reached). */
+int rnnt_pool_chunk_beam(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, const float* fbank_dev, int32_t chunk_frames,
+                         const int32_t* offsets_host, const int32_t* required_host, int32_t beam_size, int32_t* frames_out, void* stream);
+/* the slot's hypotheses in beam order: *n_hyp of them, lens_host [cap_hyps], tokens_host [cap_hyps][cap_tokens] (row i holds
+ * lens_host[i] tokens), scores_host [cap_hyps] (f64).  Any output pointer may be NULL (all NULL: query *n_hyp only; tokens_host NULL:
+ * query the lengths).  RNNT_ERR_ARG when cap_hyps or cap_tokens is too small for a requested output.  Synchronises. */
+int rnnt_stream_get_beam(rnnt_ctx* ctx, int32_t slot, int32_t cap_hyps, int32_t cap_tokens, int32_t* n_hyp, int32_t* lens_host,
+                         int32_t* tokens_host, double* scores_host, void* stream);
+/* LSTM state of the slot's hypotheses, in beam order: h_host, c_host [n_hyp][256] (cap_hyps >= n_hyp).  Synchronises. */
+int rnnt_stream_get_beam_states(rnnt_ctx* ctx, int32_t slot, int32_t cap_hyps, float* h_host, float* c_host, void* stream);
 /* tokens [from, count) of one slot, at most cap of them into tokens_host; *n_out = count - from (0 if from >= count), so a caller
  * polls only its own increments.  Synchronises. */
 int rnnt_stream_get_tokens(rnnt_ctx* ctx, int32_t slot, int32_t from, int32_t cap, int32_t* tokens_host, int32_t* n_out, void* stream);
