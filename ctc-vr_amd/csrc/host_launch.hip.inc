@@ -30,7 +30,8 @@ int fail(rnnt_ctx* ctx, int code, const char* fmt, ...) {
 enum { TAG_NONE = 0, TAG_CONV1 = 1, TAG_CONV2 = 2, TAG_EMBED = 3, TAG_FFN1 = 4, TAG_FFN2 = 5, TAG_QKV = 6, TAG_ATTN = 7, TAG_ATTN_OUT = 8,
        TAG_PW1 = 9, TAG_DWCONV = 10, TAG_PW2 = 11, TAG_LN = 12, TAG_ENC_PROJ = 13, TAG_LSTM = 20, TAG_PRED_PROJ = 21,
        TAG_JOINT_TANH = 22, TAG_JOINT_OUT = 23, TAG_GREEDY_UPDATE = 24, TAG_BLOCK_FRONT = 30, TAG_BLOCK_BACK = 31, TAG_FFN_FUSED = 32, TAG_FFN_QKV = 33, TAG_OUT_PW1 = 34, TAG_FFN_MERGED = 35,
-       TAG_CONV1_MINOR = 36, TAG_CONV2_MINOR = 37, TAG_EMBED_MINOR = 38 };   // subsampling of the minor chunk classes of a whole-utterance call (the tail chunk)
+       TAG_CONV1_MINOR = 36, TAG_CONV2_MINOR = 37, TAG_EMBED_MINOR = 38,   // subsampling of the minor chunk classes of a whole-utterance call (the tail chunk)
+       TAG_SCORE_PICK = 40, TAG_SCORE_ALPHA = 41 };   // rnnt_transducer_nll: the picked lattice (fused kernel, or lattice + gather), transducer_alpha
 
 struct ProfScope {   // records a start/stop event pair around one launch when its site is selected
     rnnt_ctx* ctx; hipStream_t s; bool on;

@@ -223,6 +223,13 @@ struct rnnt_ctx {
     float *fb_dft = nullptr, *fb_mel = nullptr, *fb_pad = nullptr, *fb_spec = nullptr, *fb_pow = nullptr;
     size_t fb_pad_cap = 0, fb_spec_cap = 0, fb_pow_cap = 0;
     int fb_rate = 0, fb_nfft = 0;
+    // teacher-forced scoring (api_score.hip.inc): grow-only work buffers -- predictor outputs / LSTM ping-pong / internal pick
+    // lattice (sc_f), step tokens / targets / lengths (sc_i), per-utterance results (sc_nll), and the materialised log-softmax
+    // lattice of the fallback path or the CTC log-probabilities (sc_lat)
+    float *sc_f = nullptr, *sc_lat = nullptr;
+    int* sc_i = nullptr;
+    double* sc_nll = nullptr;
+    size_t sc_f_cap = 0, sc_lat_cap = 0, sc_i_cap = 0, sc_nll_cap = 0;
     hipStream_t cap_stream = nullptr;          // stream-capture scratch stream
     struct DecGraph { int n_streams, k; hipGraphExec_t exec; };
     std::vector<DecGraph> dec_graphs;          // K greedy steps captured once per (n_streams, K)
@@ -243,6 +250,7 @@ extern "C" {
 #include "api_decode.hip.inc"
 #include "api_beam.hip.inc"
 #include "api_ops.hip.inc"
+#include "api_score.hip.inc"
 #include "api_state.hip.inc"
 #include "api_pool.hip.inc"
 }  // extern "C"

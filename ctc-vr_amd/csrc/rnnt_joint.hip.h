@@ -71,6 +71,10 @@ struct JointRP {
     int ntiles;                  // ceil(M / 64)
     int* counter;                // dynamic row-tile queue: zeroed by the host before every launch (tiles >= gridDim.x are drawn from it)
     int stagger;                 // start delay step (s_sleep units of 64 clocks) x a per-workgroup hash in 0..15; 0 = none
+    // pick form (PICK = true; `out` unused): the lattice's consumer, the transducer likelihood, reads two columns of a row
+    const int* targets;          // [B][tstride] int32 labels; row (b, t, u) picks targets[b][min(u, tstride - 1)] (null: the blank)
+    float* pick;                 // [M][2]: log-softmax at `blank`, log-softmax at the row's target
+    int tstride, blank;
 };
 
 // W_out [V][256] f32 -> the ring's stage stream.  Piece (stage g, slot j) holds for lane l the 8 k-consecutive 16-bit values
@@ -156,8 +160,13 @@ __device__ __forceinline__ void jr_vmcnt4() { asm volatile("s_waitcnt vmcnt(4)" 
 __device__ __forceinline__ void jr_vmcnt3() { asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); }
 __device__ __forceinline__ void jr_vmcnt0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
-template <int NSPLIT, bool F16, bool LSM>
+// PICK (with LSM): the same contraction and the same log-softmax on the accumulators, but instead of the 26 row stores the two
+// values the transducer recursion reads leave the chip -- 8 bytes per lattice row instead of 4 V.  Column v of a row sits in tile
+// v / 16, lane group (v % 16) / 4, register v % 4; it is selected by compile-time-unrolled compares (a dynamic index would send
+// the accumulators to scratch) and stored by the lane that owns it.  Bitwise the values the LSM form writes at those columns.
+template <int NSPLIT, bool F16, bool LSM, bool PICK = false>
 __global__ __launch_bounds__(256, JR_WGS_PER_CU) void joint_lattice_rows(JointRP P) {
+    static_assert(!PICK || LSM, "the pick form is defined on the log-softmax");
     constexpr bool LO = NSPLIT == 2;
     constexpr int NSTG = LO ? 16 : 8;                          // ring stages per row tile
     constexpr int TPS = LO ? 13 : 26;                          // vocabulary tiles per stage
@@ -209,11 +218,13 @@ __global__ __launch_bounds__(256, JR_WGS_PER_CU) void joint_lattice_rows(JointRP
     // loads before the softmax arithmetic / the stores was tried: hipcc rotates the loop and keeps prologue loads alive across
     // the k-loop, spilling 30+ registers.  Interleaving the store burst with the next tile's loads and formation in four rounds --
     // seven stores, two k-steps -- compiles clean at 256 registers and is slower: 418 vs 408 us split, 346 vs 281 us plain bf16.)
+    int vt = 0;                                                // pick form: the target column of this lane's row of the current tile
     auto form_a = [&](int tl) {
         const int am = min(tl * JR_ROWS + wave * 16 + i, (int)P.M - 1);   // M < 2^31 (host check)
         const int bt = am / P.U;                               // (b, t) row of e
         const int u = am - bt * P.U;
         const int bb = bt / P.T;
+        if constexpr (PICK) vt = P.targets ? ldgi(P.targets + (long long)bb * P.tstride + min(u, P.tstride - 1)) : P.blank;
         const float* eg = P.e + (long long)bt * RNNT_D + 8 * kq;
         const float* pg = P.p + (long long)(bb * P.U + u) * RNNT_D + 8 * kq;
         float4 ld[8][4];
@@ -322,6 +333,21 @@ __global__ __launch_bounds__(256, JR_WGS_PER_CU) void joint_lattice_rows(JointRP
             for (int t = 0; t < JR_NT; ++t) { acc[t][0] -= lse; acc[t][1] -= lse; acc[t][2] -= lse; acc[t][3] -= lse; }
         }
         JR_STAMP(3);                                           // epilogue arithmetic
+        if constexpr (PICK) {
+            if (m < P.M) {
+                int vb = P.blank;
+                asm volatile("" : "+v"(vb));                  // a VGPR: as a uniform the 26 tile compares are hoisted into SGPR pairs, which spill
+                const int tb = vb >> 4, tt = vt >> 4;
+                f32x4_ qb = acc[0], qt = acc[0];
+#pragma unroll
+                for (int t = 1; t < JR_NT; ++t) { qb = tb == t ? acc[t] : qb; qt = tt == t ? acc[t] : qt; }
+                const int rb = vb & 3, rt = vt & 3;
+                const float xb = rb == 0 ? qb[0] : (rb == 1 ? qb[1] : (rb == 2 ? qb[2] : qb[3]));
+                const float xt = rt == 0 ? qt[0] : (rt == 1 ? qt[1] : (rt == 2 ? qt[2] : qt[3]));
+                if (((vb >> 2) & 3) == kq) stg1(P.pick + 2 * m, xb);
+                if (((vt >> 2) & 3) == kq) stg1(P.pick + 2 * m + 1, xt);
+            }
+        } else
         if (JR_ABLATE & 1) {
 #pragma unroll
             for (int t = 0; t < JR_NT; ++t) asm volatile("" :: "v"(acc[t]));

@@ -1,0 +1,93 @@
+// Teacher-forced scoring: the forward (alpha) recursions of the transducer and CTC likelihoods, and the gather behind the
+// fallback of the fused lattice kernel.  Forward only: no gradients.
+// Part of rnnt_kernels.hip.h (include that umbrella, not this file).
+//
+// The transducer likelihood is the sum over all monotonic alignments (torchaudio.functional.rnnt_loss with reduction "none",
+// online_rnnt_model.py:247-255; its clamp only touches gradients); the CTC one is nn.CTCLoss(reduction="none")
+// (online_rnnt_model.py:22-23).  Both recursions run in f64 like the beam scores: one workgroup per utterance, a chain of
+// T_b + U_b (transducer) or T_b (CTC) dependent steps with one barrier each, so they are latency-bound and not tuned here.
+#pragma once
+
+#define SCORE_UMAX 255           // labels per utterance: transducer threads cover u = 0..255, CTC threads s = 0..510
+
+// fallback of joint_lattice_rows<.., PICK>: the two columns of a materialised log-softmax lattice lat [M][V], M = B * T * U1
+__global__ void pick_gather(const float* __restrict__ lat, const int* __restrict__ targets, float* __restrict__ pick, long long M, int T,
+                            int U1, int V, int tstride, int blank) {
+    for (long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x; m < M; m += (long long)gridDim.x * blockDim.x) {
+        const long long bt = m / U1;
+        const int u = (int)(m - bt * U1);
+        int vt = targets ? ldgi(targets + (bt / T) * tstride + min(u, tstride - 1)) : blank;
+        vt = min(max(vt, 0), V - 1);                           // padded cells only: valid labels are checked on the host
+        pick[2 * m] = ldg1(lat + m * V + blank);
+        pick[2 * m + 1] = ldg1(lat + m * V + vt);
+    }
+}
+
+__device__ __forceinline__ double score_logaddexp(double a, double b) {
+    const double mx = fmax(a, b), mn = fmin(a, b);
+    return mx == -INFINITY ? mx : mx + log1p(exp(mn - mx));
+}
+
+// alpha[0,0] = 0; alpha[t,u] = logaddexp(alpha[t-1,u] + pick[t-1,u][0], alpha[t,u-1] + pick[t,u-1][1]);
+// nll = -(alpha[T_b-1,U_b] + pick[T_b-1,U_b][0]).  Anti-diagonal wavefront: on diagonal d thread u owns cell (d - u, u), keeps its
+// own alpha in a register and hands it to thread u + 1 through LDS (two buffers: one barrier per diagonal).
+// pick [B][T][U1][2]; lens [2][B]: T_b in [1, T], U_b in [0, U1 - 1]; launched with 256 threads, U1 <= 256.
+__global__ __launch_bounds__(256) void transducer_alpha(const float* __restrict__ pick, const int* __restrict__ lens, int B, int T, int U1,
+                                                        double* __restrict__ nll) {
+    __shared__ double xa[2][SCORE_UMAX + 1];
+    const int b = blockIdx.x, u = threadIdx.x;
+    const int Tb = ldgi(lens + b), Ub = ldgi(lens + B + b);
+    const float* pb = pick + (long long)b * T * U1 * 2;
+    double a = -INFINITY;
+    const int nd = Tb + Ub;                                    // diagonals 0 .. T_b + U_b - 1
+    for (int d = 0; d < nd; ++d) {
+        const int t = d - u;
+        const bool live = u <= Ub && t >= 0 && t < Tb;
+        if (live) {
+            if (d == 0) a = 0.0;
+            else {
+                // `a` still holds alpha[t-1,u] (the cell this thread owned on diagonal d - 1), the neighbour's alpha[t,u-1] is in LDS
+                const double below = t > 0 ? a + (double)ldg1(pb + ((long long)(t - 1) * U1 + u) * 2) : -INFINITY;
+                const double left = u > 0 ? xa[(d - 1) & 1][u - 1] + (double)ldg1(pb + ((long long)t * U1 + u - 1) * 2 + 1) : -INFINITY;
+                a = t == 0 ? left : (u == 0 ? below : score_logaddexp(below, left));
+            }
+        }
+        xa[d & 1][u] = a;
+        __syncthreads();
+    }
+    if (u == Ub) nll[b] = -(a + (double)ldg1(pb + ((long long)(Tb - 1) * U1 + Ub) * 2));
+}
+
+// Standard CTC forward over the S = 2 L_b + 1 extended states (blank, y_1, blank, ..., y_L, blank) and T_b frames, the
+// recursion of nn.CTCLoss: alpha_t[s] = logsumexp(alpha_{t-1}[s], alpha_{t-1}[s-1], alpha_{t-1}[s-2] if y differs) + lp[t][ext s].
+// nll = -logaddexp(alpha[S-1], alpha[S-2]); an infeasible pair (fewer frames than labels plus adjacent repeats) keeps both at
+// -inf and gives +inf.  lp [B][T][V] log-probabilities; targets [B][tstride]; lens [2][B]; launched with 512 threads.
+__global__ __launch_bounds__(512) void ctc_alpha(const float* __restrict__ lp, const int* __restrict__ targets, const int* __restrict__ lens,
+                                                 int B, int T, int V, int tstride, int blank, double* __restrict__ nll) {
+    __shared__ double xa[2][2 * SCORE_UMAX + 2];
+    const int b = blockIdx.x, s = threadIdx.x;
+    const int Tb = ldgi(lens + b), Lb = ldgi(lens + B + b);
+    const int S = 2 * Lb + 1;
+    const bool live = s < S;
+    const float* lb = lp + (long long)b * T * V;
+    int col = blank, skip = 0;
+    if (live && (s & 1)) {
+        col = ldgi(targets + (long long)b * tstride + (s >> 1));
+        skip = s >= 3 && ldgi(targets + (long long)b * tstride + (s >> 1) - 1) != col;
+    }
+    double a = live && s < 2 ? (double)ldg1(lb + col) : -INFINITY;
+    xa[0][s] = a;
+    __syncthreads();
+    for (int t = 1; t < Tb; ++t) {
+        if (live) {
+            const double* pv = xa[(t - 1) & 1];
+            const double a1 = s >= 1 ? pv[s - 1] : -INFINITY, a2 = skip ? pv[s - 2] : -INFINITY;
+            double mx = fmax(a, fmax(a1, a2));
+            if (mx == -INFINITY) mx = 0.0;
+            a = log(exp(a - mx) + exp(a1 - mx) + exp(a2 - mx)) + mx + (double)ldg1(lb + (long long)t * V + col);
+        }
+        xa[t & 1][s] = a;
+        __syncthreads();
+    }
+    if (s == S - 1) nll[b] = -score_logaddexp(a, S > 1 ? xa[(Tb - 1) & 1][S - 2] : -INFINITY);
+}

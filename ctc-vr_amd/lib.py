@@ -54,6 +54,8 @@ SIGNATURES = {
     "rnnt_encoder_full": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32p, c_vp]),
     "rnnt_ctc_argmax": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32p, c_vp]),
     "rnnt_ctc_logprobs": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp]),
+    "rnnt_transducer_nll": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "rnnt_ctc_nll": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "rnnt_fbank": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32p, c_vp]),
     "rnnt_greedy_search_full": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "rnnt_get_att_cache": (c_i32, [c_vp, c_i32, c_vp, c_i32p, c_vp]),
@@ -412,6 +414,29 @@ class RnntEngine:
 
     def ctc_logprobs(self, enc_ptr, rows, out_ptr, stream=None):
         self._chk(self.lib.rnnt_ctc_logprobs(self.ctx, enc_ptr, rows, out_ptr, stream), "rnnt_ctc_logprobs")
+
+    def _score_args(self, enc_lens, targets, target_lens, B):
+        el, tl = np.ascontiguousarray(enc_lens, np.int32), np.ascontiguousarray(target_lens, np.int32)
+        tg = np.ascontiguousarray(targets, np.int32)
+        tg = tg.reshape(B, tg.size // B)
+        assert el.size == B and tl.size == B
+        return el, tg, tl, tg.shape[1]
+
+    def transducer_nll(self, enc_ptr, enc_lens, targets, target_lens, B, T, pick_ptr=None, stream=None):
+        """rnnt_transducer_nll: per-row transducer negative log-likelihood (float64 [B]) of targets [B, Umax] given encoder frames
+        enc [B, T, 256] on the device; pick_ptr: optional device float [B, T, Umax + 1, 2] receiving the picked lattice."""
+        el, tg, tl, umax = self._score_args(enc_lens, targets, target_lens, B)
+        nll = np.zeros(B, np.float64)
+        self._chk(self.lib.rnnt_transducer_nll(self.ctx, enc_ptr, _np_ptr(el), _np_ptr(tg), _np_ptr(tl), B, T, umax, _np_ptr(nll), pick_ptr, stream),
+                  "rnnt_transducer_nll")
+        return nll
+
+    def ctc_nll(self, enc_ptr, enc_lens, targets, target_lens, B, T, stream=None):
+        """rnnt_ctc_nll: per-row CTC negative log-likelihood (float64 [B], +inf where the frames cannot hold the transcript)."""
+        el, tg, tl, umax = self._score_args(enc_lens, targets, target_lens, B)
+        nll = np.zeros(B, np.float64)
+        self._chk(self.lib.rnnt_ctc_nll(self.ctx, enc_ptr, _np_ptr(el), _np_ptr(tg), _np_ptr(tl), B, T, umax, _np_ptr(nll), stream), "rnnt_ctc_nll")
+        return nll
 
     def greedy_search_full(self, fbank_ptr, lens, B, T, n_steps=64, stream=None):
         """Offline greedy search over the full-context encoder (model/component/transducer.py:22-70) -> list of token lists."""

@@ -81,6 +81,25 @@ def beam_advance_frame(engine, frame_idx, beams, blank_id, beam_size, stream=Non
     return new_beams
 
 
+def compose_losses(nll_rnnt, nll_ctc, text_lens, ctc_weight):
+    """The loss composition of the reference's forward with texts (model/online_rnnt_model.py:247-263) from per-utterance
+    negative log-likelihoods, in float64 on the host: loss_rnnt = mean(nll_rnnt) (rnnt_loss reduction="mean"); total =
+    (1 - ctc_weight) * loss_rnnt; with nll_ctc given (the caller passes it only when ctc_weight > 0 and the head is loaded),
+    loss_ctc = mean over the batch of nll_b / max(L_b, 1) with infinite terms zeroed (nn.CTCLoss(reduction="mean",
+    zero_infinity=True), :22-23) and total += ctc_weight * loss_ctc.  Returns (total, loss_dict) with the reference's keys."""
+    nll_rnnt = np.asarray(nll_rnnt, np.float64)
+    loss_rnnt = float(nll_rnnt.mean())
+    loss_dict = {"loss_rnnt": loss_rnnt}
+    total = (1.0 - ctc_weight) * loss_rnnt
+    if nll_ctc is not None:
+        per = np.asarray(nll_ctc, np.float64).copy()
+        per[~np.isfinite(per)] = 0.0
+        loss_ctc = float((per / np.maximum(np.asarray(text_lens, np.float64), 1.0)).mean())
+        loss_dict["loss_ctc"] = loss_ctc
+        total = total + ctc_weight * loss_ctc
+    return total, loss_dict
+
+
 class _EncoderView:
     """Attribute surface the reference's callers read: encoder.static_chunk_size and
     encoder.embed.subsampling_rate (model/online_rnnt_model.py:283-287)."""
@@ -135,6 +154,7 @@ class OnlineRNNTModel:
     def load_state_dict(self, state_dict, strict: bool = True):
         self._engine.load_state_dict(state_dict, numerics=self.numerics)
         self._loaded = True
+        self._ctc_loaded = "ctc_head.ctc_lo.weight" in state_dict and "ctc_head.ctc_lo.bias" in state_dict
 
     # ---- streaming state (model/online_rnnt_model.py:138-164) ----------------------------------------
     def extract_audio_features(self, waveform, sample_rate, n_fft=1024):
@@ -327,13 +347,67 @@ class OnlineRNNTModel:
             hyps.append(hyp)
         return hyps
 
+    # ---- teacher-forced scoring (model/online_rnnt_model.py:224-266 under torch.no_grad()) ----------------------------
+    def _encode_for_scoring(self, audios, audio_lens, texts, text_lens):
+        """Full-context encoder of a padded batch + the host arrays of a scoring call: (enc [B, T', 256] on the device, valid
+        encoder frames [B], targets [B, Umax] int32, target lengths [B]).  Invalidates the streaming state."""
+        self._require_loaded()
+        B, T = audios.size(0), audios.size(1)
+        x = audios.to(self.device, torch.float32).contiguous()
+        lens = audio_lens.detach().cpu().numpy().astype(np.int32).reshape(B)
+        tq = ((T - 3) // 2 + 1 - 3) // 2 + 1
+        enc = torch.empty(B, tq, 256, device=self.device)
+        self._engine.encoder_full(x.data_ptr(), lens, B, T, enc.data_ptr(), _stream_ptr())
+        self._chunks_done = None
+        n1 = np.maximum(0, (np.minimum(lens, T) - 1) // 2)         # valid frames after masks[:, :, 2::2][:, :, 2::2]
+        enc_lens = np.maximum(0, (n1 - 1) // 2).astype(np.int32)
+        tg = np.ascontiguousarray(texts.detach().cpu().numpy().astype(np.int32).reshape(B, -1) if texts.numel() else np.zeros((B, 0), np.int32))
+        tl = text_lens.detach().cpu().numpy().astype(np.int32).reshape(B)
+        return enc, enc_lens, tg, tl
+
+    def transducer_nll(self, audios: torch.Tensor, audio_lens: torch.Tensor, texts: torch.Tensor, text_lens: torch.Tensor) -> torch.Tensor:
+        """Per-utterance transducer negative log-likelihood, float64 [B]: torchaudio.functional.rnnt_loss(reduction="none") of
+        the reference's lattice (:241-255), i.e. minus the log of the sum over all monotonic alignments, computed on the device
+        (rnnt_transducer_nll) without materialising the [B, T, U+1, V] lattice.  texts [B, Umax] (entries beyond text_lens are
+        ignored, the reference pads with ignore_id).  Deviation, on purpose: the reference's `self.encoder(x, lens)` draws a
+        RANDOM chunk mask even in eval mode, so its loss is not reproducible; this runs the deterministic
+        full-context encoder (rnnt_encoder_full, decoding_chunk_size=-1).  Invalidates the streaming state, as
+        greedy_search_full does."""
+        enc, enc_lens, tg, tl = self._encode_for_scoring(audios, audio_lens, texts, text_lens)
+        nll = self._engine.transducer_nll(enc.data_ptr(), enc_lens, tg, tl, enc.size(0), enc.size(1), None, _stream_ptr())
+        return torch.from_numpy(nll)
+
+    def ctc_nll(self, audios: torch.Tensor, audio_lens: torch.Tensor, texts: torch.Tensor, text_lens: torch.Tensor) -> torch.Tensor:
+        """Per-utterance CTC negative log-likelihood, float64 [B]: nn.CTCLoss(blank, reduction="none") on the CTC head's
+        log-softmax (:22-32) over the same deterministic full-context encoder as transducer_nll (rnnt_ctc_nll); +inf where the
+        frames cannot hold the transcript.  Invalidates the streaming state."""
+        enc, enc_lens, tg, tl = self._encode_for_scoring(audios, audio_lens, texts, text_lens)
+        nll = self._engine.ctc_nll(enc.data_ptr(), enc_lens, tg, tl, enc.size(0), enc.size(1), _stream_ptr())
+        return torch.from_numpy(nll)
+
+    def _has_ctc_head(self) -> bool:
+        return bool(getattr(self, "_ctc_loaded", False))
+
     def forward(self, audios, audio_lens, texts=None, text_lens=None):
-        """Inference branches of the reference's forward (model/online_rnnt_model.py:224-272): a streaming model goes to
+        """The reference's forward (model/online_rnnt_model.py:224-272).  Without texts: a streaming model goes to
         streaming_inference (:271-272); a non-streaming model runs the full-context encoder and basic_greedy_search
-        (:234-235,268; model/component/transducer.py:22-70, n_steps=64) for the whole batch.  The training branch
-        (texts given: joint lattice + rnnt_loss) is outside the accelerated path."""
+        (:234-235,268; model/component/transducer.py:22-70, n_steps=64) for the whole batch.
+        With texts (the validation loop's call under torch.no_grad(), online_rnnt_train.py:184-200): returns
+        (None, total_loss, loss_dict) with loss_rnnt = mean over the batch of transducer_nll (rnnt_loss reduction="mean"),
+        total = (1 - ctc_weight) * loss_rnnt, and, when ctc_weight > 0 and the CTC head is loaded, loss_ctc =
+        nn.CTCLoss(reduction="mean", zero_infinity=True) of ctc_nll and total += ctc_weight * loss_ctc (compose_losses).
+        total_loss is a float64 tensor without a graph: this is scoring, not training.  The first element is None where the
+        reference returns joint_out: the [B, T, U+1, V] lattice is never materialised (rnnt_joint gives it to whoever wants
+        it).  The encoder is the deterministic full-context one (see transducer_nll)."""
         if texts is not None:
-            raise NotImplementedError("training forward (loss) is outside the accelerated path (SURVEY.md §8a)")
+            enc, enc_lens, tg, tl = self._encode_for_scoring(audios, audio_lens, texts, text_lens)
+            B, tq, s = enc.size(0), enc.size(1), _stream_ptr()
+            nll_rnnt = self._engine.transducer_nll(enc.data_ptr(), enc_lens, tg, tl, B, tq, None, s)
+            nll_ctc = None
+            if self.ctc_weight > 0.0 and self._has_ctc_head():
+                nll_ctc = self._engine.ctc_nll(enc.data_ptr(), enc_lens, tg, tl, B, tq, s)
+            total, loss_dict = compose_losses(nll_rnnt, nll_ctc, tl, self.ctc_weight)
+            return None, torch.tensor(total, dtype=torch.float64), loss_dict
         if self.streaming:
             return self.streaming_inference(audios, audio_lens)
         return self.greedy_search_full(audios, audio_lens), None, None

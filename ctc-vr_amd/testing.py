@@ -149,3 +149,49 @@ def greedy_margins(sd_np, enc_frames, tokens, blank=BLANK, device="cuda", n_step
     ok &= u_ == nt
     return mmin.cpu().numpy(), ok.cpu().numpy()
 
+
+
+# ---- teacher-forced scoring: float64 restatements of the transducer likelihood (tests) -----------------------------------------
+def _logaddexp(a, b):
+    mx, mn = (a, b) if a >= b else (b, a)
+    return mx if mx == -math.inf else mx + math.log1p(math.exp(mn - mx))
+
+
+def transducer_nll_ref(pick, T_b, U_b):
+    """-log of the sum over all monotonic alignments of one utterance, as a float64 dynamic programme.  pick [T, U1, 2]:
+    pick[t, u, 0] = log P(blank | t, u), pick[t, u, 1] = log P(y_{u+1} | t, u); valid cells t < T_b, u <= U_b (label slot
+    u < U_b), nothing else is read.  alpha[0,0] = 0; alpha[t,u] = logaddexp(alpha[t-1,u] + pick[t-1,u,0], alpha[t,u-1] +
+    pick[t,u-1,1]); nll = -(alpha[T_b-1,U_b] + pick[T_b-1,U_b,0])."""
+    p = np.asarray(pick, np.float64)
+    alpha = np.full((T_b, U_b + 1), -math.inf)
+    for t in range(T_b):
+        for u in range(U_b + 1):
+            if t == 0 and u == 0:
+                alpha[t, u] = 0.0
+                continue
+            below = alpha[t - 1, u] + p[t - 1, u, 0] if t > 0 else -math.inf
+            left = alpha[t, u - 1] + p[t, u - 1, 1] if u > 0 else -math.inf
+            alpha[t, u] = _logaddexp(below, left)
+    return -(alpha[T_b - 1, U_b] + p[T_b - 1, U_b, 0])
+
+
+def transducer_nll_bruteforce(pick, T_b, U_b):
+    """The same likelihood as an explicit sum over every alignment: each one is an order of T_b - 1 blanks and U_b labels
+    (C(T_b - 1 + U_b, U_b) of them) followed by the final blank at (T_b - 1, U_b); exact summation (math.fsum) of the path
+    probabilities relative to the best path."""
+    from itertools import combinations
+    p = np.asarray(pick, np.float64)
+    n = T_b - 1 + U_b
+    logs = []
+    for labels_at in combinations(range(n), U_b):
+        at, t, u, lp = set(labels_at), 0, 0, 0.0
+        for k in range(n):
+            if k in at:
+                lp += p[t, u, 1]
+                u += 1
+            else:
+                lp += p[t, u, 0]
+                t += 1
+        logs.append(lp + p[T_b - 1, U_b, 0])
+    mx = max(logs)
+    return -(mx + math.log(math.fsum(math.exp(v - mx) for v in logs)))

@@ -295,6 +295,35 @@ int rnnt_ctc_argmax(rnnt_ctx* ctx, const float* fbank_dev, const int32_t* lens_h
  * prefix_beam_search.py:66,99-101), whose frame loop runs in the facade over rnnt_encoder_full / rnnt_predictor_step / rnnt_joint. */
 int rnnt_ctc_logprobs(rnnt_ctx* ctx, const float* enc_dev, int32_t rows, float* out_dev, void* stream);
 
+/* -- teacher-forced scoring: how likely is a GIVEN transcript (forward only, no gradients) ----------------------------------- */
+/* Transducer negative log-likelihood: the RNN-T term of the reference's forward with texts (model/online_rnnt_model.py:240-255),
+ * torchaudio.functional.rnnt_loss(reduction="none") -- minus the log of the sum over all monotonic alignments; its `clamp` only
+ * touches gradients.  Per row b: joint.enc_ffn of its frames, the predictor over [blank, y_1 .. y_Umax] from the zero state
+ * (add_blank + predictor(ys_in_pad), model/component/transducer.py:8-19; Umax + 1 steps of rnnt_predictor_step's GEMMs),
+ * joint.pred_ffn, then ONE lattice kernel that keeps the log-softmax in its accumulators and writes only the two values the
+ * recursion reads per cell -- pick[b][t][u][0] = log P(blank | t, u), pick[b][t][u][1] = log P(y_{u+1} | t, u) -- and the
+ * alpha recursion in f64 (anti-diagonal wavefront, one workgroup per row).  One copy of B doubles, one synchronisation.
+ *   enc_dev [B, T, 256] device; enc_lens_host [B] (T_b in [1, T]); targets_host [B, Umax] int32; target_lens_host [B] (U_b in
+ *   [0, Umax]); nll_host [B] double; pick_dev: NULL, or device float [B, T, Umax + 1, 2] that receives the picked lattice
+ *   (for every cell t < T_b, u <= U_b, label slot u < U_b: bitwise rnnt_joint(mode 1) at those two columns; other cells undefined).
+ * Rows need not be distinct utterances: the same frames with B transcripts is hypothesis rescoring.  Entries of targets_host
+ * beyond a row's length, and frames beyond T_b, are never read into a result.  Like rnnt_joint the call leaves streaming, pool
+ * and beam state alone.  Exact-f32 mode and vocabularies outside the lattice kernel's range (> 416 or not a multiple of 4)
+ * materialise the whole log-softmax lattice in a grow-only buffer and gather the two columns: same values, slow by design.
+ * Refusals, all decided on the host before the first launch: null pointer, B < 1, T_b outside [1, T], U_b outside [0, Umax], a
+ * label outside [0, vocab) or equal to blank_id inside a row's length: RNNT_ERR_ARG; Umax > 255 or a lattice beyond the context
+ * scratch (rnnt_joint's check): RNNT_ERR_SHAPE; weights not finalized: RNNT_ERR_STATE. */
+int rnnt_transducer_nll(rnnt_ctx* ctx, const float* enc_dev, const int32_t* enc_lens_host, const int32_t* targets_host,
+                        const int32_t* target_lens_host, int32_t B, int32_t T, int32_t Umax, double* nll_host, float* pick_dev,
+                        void* stream);
+/* CTC negative log-likelihood: OnlineCTC.forward's nn.CTCLoss (model/online_rnnt_model.py:22-32) with reduction="none" on
+ * log_softmax(ctc_lo(enc)) -- rnnt_ctc_logprobs over the B*T frames, then the forward recursion over the 2 L_b + 1 extended
+ * states in f64 (one workgroup per row).  Same arguments, ranges and refusals as rnnt_transducer_nll (L_b <= Umax <= 255); a
+ * transcript its frames cannot hold (fewer frames than labels plus adjacent repeats) gives +inf.  RNNT_ERR_STATE without
+ * ctc_head.ctc_lo.{weight,bias}.  Synchronises. */
+int rnnt_ctc_nll(rnnt_ctx* ctx, const float* enc_dev, const int32_t* enc_lens_host, const int32_t* targets_host,
+                 const int32_t* target_lens_host, int32_t B, int32_t T, int32_t Umax, double* nll_host, void* stream);
+
 /* Offline greedy search: basic_greedy_search (model/component/transducer.py:22-70) behind
  * OnlineRNNTModel.forward(audios, audio_lens) of a non-streaming model (model/online_rnnt_model.py:234-235,268):
  * full-context encoder + per-utterance greedy loop over its valid frames, <= n_steps symbols per frame (reference
@@ -326,7 +355,8 @@ const float* rnnt_enc_frames_dev(rnnt_ctx* ctx, int32_t* frames_out, int32_t* st
 /* per-launch-site timing with HIP events recorded on the launch stream (bench.py roofline leg).
  * tag selects ONE launch site: 1 conv1, 2 conv2 (implicit GEMM), 3 embed linear, 4 FFN w_1, 5 FFN w_2, 6 QKV,
  * 7 attention, 8 attention out-proj, 9 pointwise_conv1+GLU, 10 depthwise conv, 11 pointwise_conv2, 13 joint enc
- * projection, 20 LSTM cell, 21 predictor projection, 22 joint pred_ffn+tanh, 23 joint ffn_out.
+ * projection, 20 LSTM cell, 21 predictor projection, 22 joint pred_ffn+tanh, 23 joint ffn_out, 40 the picked lattice of
+ * rnnt_transducer_nll, 41 its alpha recursion.
  * rnnt_profile_end synchronises the recorded events and returns the summed kernel time and launch count. */
 int rnnt_profile_begin(rnnt_ctx* ctx, int32_t tag);
 int rnnt_profile_end(rnnt_ctx* ctx, double* total_ms, int64_t* n_launches);
