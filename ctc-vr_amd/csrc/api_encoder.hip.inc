@@ -526,7 +526,7 @@ int rnnt_encoder_chunks(rnnt_ctx* ctx, const float* fbank_dev, int32_t total_fra
             if (ss != s && ctx->overlap_ok == 1 && (rc = probe_overlap(ctx, ss, s2))) return rc;
         }
         resident = ctx->use_persistent && ctx->overlap_ok == 1;
-        multi_seq = resident && multi_decoder_ok(ctx);
+        multi_seq = resident && multi_decoder_ok(ctx, ctx->n_streams);
         if (resident && !multi_seq && (rc = init_decoder_ctrl(ctx, s, fb0))) return rc;
         HIPCHK(hipEventRecord(ev[2 * C + 2], s));          // everything enqueued before this call (reset, earlier decode)
         HIPCHK(hipStreamWaitEvent(s2, ev[2 * C + 2], 0));

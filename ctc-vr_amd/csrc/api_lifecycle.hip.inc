@@ -17,7 +17,6 @@ int rnnt_create(const rnnt_config* cfg, rnnt_ctx** out) {
     HIPCHK(hipSetDevice(cfg->device));
     if (const char* ng = getenv("RNNT_NO_GRAPH")) ctx->use_graphs = (ng[0] == '1') ? 0 : 1;
     if (const char* pe = getenv("RNNT_PERSISTENT")) ctx->use_persistent = (pe[0] == '0') ? 0 : 1;
-    if (const char* ce = getenv("RNNT_COOP")) ctx->use_coop = (ce[0] == '0') ? 0 : 1;
     if (const char* me = getenv("RNNT_DEC_MULTI")) ctx->use_multi = (me[0] == '0') ? 0 : 1;
     HIPCHK(hipDeviceGetAttribute(&ctx->n_cus, hipDeviceAttributeMultiprocessorCount, cfg->device));
     if (const char* ae = getenv("RNNT_ATTN_STREAM")) ctx->attn_stream = (ae[0] == '0') ? 0 : 1;
@@ -64,9 +63,9 @@ int rnnt_create(const rnnt_config* cfg, rnnt_ctx** out) {
     ALLOC(pred, (size_t)B * D); ALLOC(z, (size_t)B * D); ALLOC(logits, (size_t)B * ctx->vpad);
     ALLOC(tok, B); ALLOC(fidx, B); ALLOC(nsym, B); ALLOC(count, B); ALLOC(tokens, (size_t)B * cfg->max_tokens);
     ALLOC(n_active, 4); ALLOC(klen, B); ALLOC(dec_ctrl, 32);
-    ALLOC(flow_buf, FLOW_WORDS + 16);
+    ALLOC(gm_dbg, 16);
     ALLOC(gm_x1, (size_t)2 * B * GM_PARTS * GM_X1);
-    ALLOC(gm_xa, (size_t)2 * B * GM_PARTS * 2 * GM_KF);
+    ALLOC(gm_xa, (size_t)2 * B * GM_PARTS * 2 * GREEDY_KF);
     if (cfg->max_beam > 0) {
         ctx->max_rows = B * cfg->max_beam;
         const size_t R = ctx->max_rows, NS = cfg->n_steps, KB = cfg->max_beam;
@@ -88,7 +87,7 @@ int rnnt_create(const rnnt_config* cfg, rnnt_ctx** out) {
 void rnnt_destroy(rnnt_ctx* ctx) {
     if (!ctx) return;
     void* ptrs[] = {ctx->joint_wfrag, ctx->joint_counter, ctx->blob, ctx->blob_hi, ctx->blob_lo, ctx->fuse_w, ctx->layers_dev, ctx->wf_ftab, ctx->egate, ctx->y1, ctx->y2, ctx->x, ctx->hbuf, ctx->qbuf, ctx->abuf, ctx->dbuf, ctx->kcache, ctx->vcache,
-                    ctx->gring, ctx->xring, ctx->encbuf, ctx->encp, ctx->h, ctx->c, ctx->sel, ctx->key, ctx->dec_ctrl, ctx->flow_buf, ctx->pred, ctx->z, ctx->logits,
+                    ctx->gring, ctx->xring, ctx->encbuf, ctx->encp, ctx->h, ctx->c, ctx->sel, ctx->key, ctx->dec_ctrl, ctx->gm_dbg, ctx->pred, ctx->z, ctx->logits,
                     ctx->tok, ctx->fidx, ctx->nsym, ctx->count, ctx->tokens, ctx->n_active, ctx->klen, ctx->scratch, ctx->gm_x1, ctx->gm_xa,
                     ctx->pool[0], ctx->pool[1], ctx->bpred, ctx->bz, ctx->blogits, ctx->b_blank, ctx->b_toplp, ctx->b_toptok,
                     ctx->b_tok, ctx->b_frame, ctx->b_active, ctx->b_steps, ctx->b_srcrow, ctx->b_srcstep};

@@ -254,7 +254,7 @@ int pool_chunk_run(rnnt_ctx* ctx, const char* fn, int32_t n_active, const int32_
         return RNNT_OK;
     }
     // ---- greedy decode of the new frames of exactly the active slots; grids sized by the rows of the call ----------------------------
-    const int per = pool_multi_ok(ctx) ? (ctx->n_cus / GM_PARTS > 0 ? ctx->n_cus / GM_PARTS : 1) : n;   // greedy_multi: the whole grid resident
+    const int per = multi_decoder_ok(ctx, 1) ? (ctx->n_cus / GM_PARTS > 0 ? ctx->n_cus / GM_PARTS : 1) : n;   // greedy_multi: the whole grid resident
     for (int i0 = 0; i0 < n; i0 += per) {
         const int cnt = n - i0 < per ? n - i0 : per;
         if ((rc = decode_resident(ctx, s, tq, nullptr, slots_dev + i0, cnt))) return rc;   // synchronises

@@ -1,5 +1,5 @@
 // Host-side helpers of librnnt_hip.so: error/alloc utilities, GEMM descriptor preparation and launchers, per-layer descriptor
-// builders, the launched decode path, the resident-decoder launchers and the stream-overlap probe.  Included by rnnt_api.hip.
+// builders, the encoder's frame emission and the stream pool's beam state helpers.  Included by rnnt_api.hip.
 
 namespace {
 
@@ -65,8 +65,6 @@ int ensure_dyn_lds(rnnt_ctx* ctx, const void* fn, size_t bytes) {
     return RNNT_OK;
 }
 
-constexpr int GM_KF = 4;   // frames per vocabulary pass of greedy_multi
-constexpr size_t FLOW_XH_WORDS = 2 * 64 * 256, FLOW_WORDS = 2 * FLOW_XH_WORDS + 2 * 4 * 16 * 16 * 4;   // greedy_flow exchange buffers
 constexpr int WF_MERGE_MAX = 4;   // chunks of one layer per wavefront stage (rnnt_encoder_chunks), upper bound
 inline int sub_len(int T) { return ((T - 3) / 2 + 1 - 3) / 2 + 1; }   // subsampling.py:188-193
 inline int sub1_len(int T) { return (T - 3) / 2 + 1; }
@@ -529,260 +527,6 @@ int launch_gemm_tab(rnnt_ctx* ctx, hipStream_t s, const GemmP* tab_dev, int n, i
     else { if (wk == 8) launch_gemm16_tab<8, 1, 1>(s, tab_dev, n, maxM, N); else launch_gemm16_tab<4, 1, 1>(s, tab_dev, n, maxM, N); }
     LAUNCHCHK("gemm16_tab");
     return RNNT_OK;
-}
-
-// `n` lock-step greedy evaluations for all streams over the buffered frames (n_frames in device memory)
-// (_decode_chunk_streaming_logic inner loop, online_rnnt_model.py:196-220), 4 launches per evaluation:
-//   greedy_decide   apply the previous argmax to every stream's state machine (token / frame / state-buffer select)
-//   LSTM cell       gates = E[tok] + h * W_hh^T, candidate (h', c') into the non-committed buffer (predictor.py:200-204)
-//   joint tanh      z = tanh(enc_ffn(enc)[t_b] + (pred_ffn o projection)(h')) (joint.py:54-66, folded Linear pair)
-//   joint out       logits = z * W_out^T + b, argmax fused into the epilogue (packed atomicMax; online_rnnt_model.py:212)
-// Streams without frames idle.
-GreedyState greedy_state(rnnt_ctx* ctx) {
-    return GreedyState{ctx->tok, ctx->fidx, ctx->nsym, ctx->count, ctx->tokens, ctx->sel, ctx->key, ctx->n_active, ctx->pinned + 8};
-}
-
-int greedy_steps_raw(rnnt_ctx* ctx, hipStream_t s, int n) {
-    const int B = ctx->n_streams, V = ctx->cfg.vocab_size;
-    const long long bs = (long long)ctx->cfg.max_streams * D;   // floats between the two state buffers
-    GreedyState st = greedy_state(ctx);
-    int rc;
-    for (int it = 0; it < n; ++it) {
-        hipLaunchKernelGGL(greedy_decide, dim3(1), dim3(64), 0, s, B, ctx->cfg.blank_id, ctx->cfg.n_steps, ctx->cfg.max_tokens, 0, st);
-        LAUNCHCHK("greedy_decide");
-        GemmP g1 = plain_gemm(ctx->h, D, ctx->whh_il, D, nullptr, ctx->h, D, B, 4 * D, D, EPI_LSTM);
-        g1.X = ctx->egate; g1.I = ctx->tok; g1.X2 = ctx->c; g1.Y2 = ctx->c;
-        g1.Asel = ctx->sel; g1.asel_stride = bs; g1.asel_invert = 0;
-        g1.act_idx = ctx->fidx; g1.act_lim = ctx->n_active + 2;
-        if ((rc = launch_gemm(ctx, s, &g1, 1, TAG_LSTM))) return rc;
-        GemmP g3 = plain_gemm(ctx->h, D, ctx->wjc, D, ctx->bjc, ctx->z, D, B, D, D, EPI_TANH_ADD);
-        g3.Asel = ctx->sel; g3.asel_stride = bs; g3.asel_invert = 1;   // candidate h' lives in the other buffer
-        g3.X = ctx->encp; g3.I = ctx->fidx; g3.x_n = 1; g3.x_s0 = (long long)ctx->fstride * D; g3.x_s1 = D;
-        g3.act_idx = ctx->fidx; g3.act_lim = ctx->n_active + 2;
-        if ((rc = launch_gemm(ctx, s, &g3, 1, TAG_JOINT_TANH))) return rc;
-        GemmP g4 = plain_gemm(ctx->z, D, ctx->wout, D, ctx->bout, ctx->logits, ctx->vpad, B, V, D, EPI_ARGMAX);
-        g4.key = ctx->key; g4.I = ctx->fidx; g4.nframes = ctx->n_active + 2;
-        g4.act_idx = ctx->fidx; g4.act_lim = ctx->n_active + 2;
-        if ((rc = launch_gemm(ctx, s, &g4, 1, TAG_JOINT_OUT))) return rc;
-    }
-    return RNNT_OK;
-}
-
-// n greedy steps over the first n_frames buffered frames; the step sequence has static arguments, so it is captured
-// once per (n_streams, n) into a hipGraph and replayed with ONE host call (the path is launch-bound: 5 kernels/step).
-int greedy_steps(rnnt_ctx* ctx, hipStream_t s, int n, int n_frames) {
-    int rc;
-    hipLaunchKernelGGL(fill_i32, dim3(1), dim3(64), 0, s, ctx->n_active + 2, n_frames, 1LL);
-    LAUNCHCHK("fill_i32");
-    ctx->greedy_steps += n;
-    if (!ctx->use_graphs || ctx->prof_tag >= 20) return greedy_steps_raw(ctx, s, n);   // decode sites being timed: eager
-    for (auto& g : ctx->dec_graphs)
-        if (g.n_streams == ctx->n_streams && g.k == n) {
-            HIPCHK(hipGraphLaunch(g.exec, s));
-            ctx->launches += 4 * n;
-            return RNNT_OK;
-        }
-    if (!ctx->cap_stream) HIPCHK(hipStreamCreateWithFlags(&ctx->cap_stream, hipStreamNonBlocking));
-    hipGraph_t graph = nullptr;
-    const int64_t l0 = ctx->launches;
-    HIPCHK(hipStreamBeginCapture(ctx->cap_stream, hipStreamCaptureModeThreadLocal));
-    ctx->capturing = true;
-    rc = greedy_steps_raw(ctx, ctx->cap_stream, n);
-    ctx->capturing = false;
-    hipError_t e = hipStreamEndCapture(ctx->cap_stream, &graph);
-    ctx->launches = l0;
-    if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-    if (e != hipSuccess) return fail(ctx, RNNT_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(e));
-    hipGraphExec_t exec = nullptr;
-    e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    if (e != hipSuccess) return fail(ctx, RNNT_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(e));
-    ctx->dec_graphs.push_back({ctx->n_streams, n, exec});
-    HIPCHK(hipGraphLaunch(exec, s));
-    ctx->launches += 4 * n;
-    return RNNT_OK;
-}
-
-// run step batches until every stream has consumed all n_frames frames (host checks a device counter)
-int greedy_drain(rnnt_ctx* ctx, hipStream_t s, int n_frames, int done_steps) {
-    hipLaunchKernelGGL(fill_i32, dim3(1), dim3(64), 0, s, ctx->n_active + 2, n_frames, 1LL);
-    LAUNCHCHK("fill_i32");
-    const int max_steps = (n_frames - ctx->frames_decoded) * (ctx->cfg.n_steps + 1) + 8;
-    int rc;
-    while (true) {
-        // apply the last evaluation and count the streams that still have frames
-        hipLaunchKernelGGL(greedy_decide, dim3(1), dim3(64), 0, s, ctx->n_streams, ctx->cfg.blank_id, ctx->cfg.n_steps, ctx->cfg.max_tokens, 1,
-                           greedy_state(ctx));
-        LAUNCHCHK("greedy_decide");
-        HIPCHK(hipMemcpyAsync(ctx->pinned, ctx->n_active, sizeof(int), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        if (ctx->pinned[0] <= 0) break;
-        if (done_steps > max_steps) return fail(ctx, RNNT_ERR_STATE, "greedy decode did not terminate");
-        static const int dstep = getenv("RNNT_DRAIN_STEPS") ? atoi(getenv("RNNT_DRAIN_STEPS")) : 4;
-        if ((rc = greedy_steps(ctx, s, dstep, n_frames))) return rc;
-        done_steps += dstep;
-    }
-    return RNNT_OK;
-}
-
-// Persistent greedy decoder: one resident workgroup per 2 streams decodes every frame up to n_total, waiting on
-// dec_ctrl[0] (frames_ready).  The control block must have been initialised on a stream this one is ordered after.
-// greedy_multi (4 CUs per stream, weights stationary) is usable when the whole grid can be resident at once
-// greedy_multi is a resident grid of 4 workgroups per stream that spin on each other's mailboxes; it is launched normally, not
-// cooperatively, and multi_decoder_ok only checks THIS context's 4 * B <= n_cus.  Two contexts of one process on one device (the
-// two-batches-in-flight mode of bench.py / INTEGRATION.md) put 2 x 256 such workgroups on 256 CUs.  That is safe, not lucky:
-// (1) a workgroup only ever waits for the three other workgroups of ITS OWN stream, never for another stream or another
-// context, so the first grid always drains; (2) every workgroup of the second grid becomes resident as soon as a CU is free, and
-// 4 * B <= n_cus means all of them are resident once the first grid has drained -- until then its early workgroups spin on
-// partners that are not resident yet, which costs time (at most the first grid's remaining decode, ~4 ms), not progress;
-// (3) the give-up bound of a wait is 5 s.  A host mutex around launch..finish (tried in round 3) serialises the two contexts'
-// whole steps, because the decoder is ENQUEUED right behind its encoder: two batches in flight fell from 6.95 to 9.2 ms per batch.
-// tests/test_gpu_parity.py::test_two_contexts_in_flight[64] runs this configuration.
-// greedy_flow (RNNT_COOP=1) holds FLOW_VOCAB rows of W_out per stream group: a larger vocabulary would never see its rows
-// >= FLOW_VOCAB, so such a context keeps greedy_stream
-bool coop_decoder_ok(const rnnt_ctx* ctx) {
-    return ctx->use_coop && ctx->n_streams <= 64 && ctx->cfg.vocab_size <= FLOW_VOCAB;
-}
-bool pool_multi_ok(const rnnt_ctx* ctx) {   // multi_decoder_ok of a context with ONE stream
-    return ctx->use_multi && !ctx->use_coop && GM_PARTS <= ctx->n_cus && (ctx->cfg.vocab_size + GM_PARTS - 1) / GM_PARTS <= 128;
-}
-bool multi_decoder_ok(const rnnt_ctx* ctx) {
-    return ctx->use_multi && !ctx->use_coop && GM_PARTS * ctx->n_streams <= ctx->n_cus && (ctx->cfg.vocab_size + GM_PARTS - 1) / GM_PARTS <= 128;
-}
-// slots != null (stream pool): n_rows stream groups, group i decoding stream slots[i] (device array) over its frames [0, n_total).
-int launch_multi_decoder(rnnt_ctx* ctx, hipStream_t s, int n_total, int n_steps_override, const int* nlim, const int* slots = nullptr, int n_rows = 0) {
-    DecMP d;
-    memset(&d, 0, sizeof(d));
-    d.whh = ctx->whh_il; d.egate = ctx->egate; d.wjc = ctx->wjc; d.bjc = ctx->bjc; d.wout = ctx->wout; d.bout = ctx->bout;
-    d.encp = ctx->encp; d.h = ctx->h; d.c = ctx->c; d.sel = ctx->sel; d.tok = ctx->tok; d.fidx = ctx->fidx; d.nsym = ctx->nsym;
-    d.count = ctx->count; d.tokens = ctx->tokens; d.ctrl = ctx->dec_ctrl; d.x1 = ctx->gm_x1; d.xa = ctx->gm_xa;
-    d.fstride_f = (long long)ctx->fstride * D; d.bstride = (long long)ctx->cfg.max_streams * D;
-    d.B = slots ? n_rows : ctx->n_streams; d.vocab = ctx->cfg.vocab_size; d.blank = ctx->cfg.blank_id;
-    d.n_steps = n_steps_override > 0 ? n_steps_override : ctx->cfg.n_steps;
-    d.max_tokens = ctx->cfg.max_tokens; d.n_total = n_total; d.nlim = nlim; d.slots = slots;
-    d.timeout_ticks = 500000000ll;
-    d.rows_per = (ctx->cfg.vocab_size + GM_PARTS - 1) / GM_PARTS;
-    static const bool gdbg = getenv("RNNT_GM_DBG") != nullptr;
-    d.dbg = gdbg ? reinterpret_cast<long long*>(ctx->flow_buf + FLOW_WORDS) : nullptr;
-    const int B = d.B;
-    // (The grid on a high- or low-priority side stream, ordered by events, was tried for the two-batches-in-flight mode: 6.79 and
-    // 6.33 ms per batch against 6.10-6.19 on the caller's stream.)
-    // tags restart at 1 every launch: no word of an earlier launch may survive
-    HIPCHK(hipMemsetAsync(ctx->gm_x1, 0, (size_t)2 * B * GM_PARTS * GM_X1 * sizeof(unsigned long long), s));
-    HIPCHK(hipMemsetAsync(ctx->gm_xa, 0, (size_t)2 * B * GM_PARTS * 2 * GM_KF * sizeof(unsigned long long), s));
-    const size_t lds = ((size_t)d.rows_per * GM_WLD + 4 * D + GM_KF * D + 16 * GM_KF + GM_PARTS * 2 * GM_KF + 8 + GM_KF * 4 * 128) * sizeof(float);
-    { const int rc_attr = ensure_dyn_lds(ctx, reinterpret_cast<const void*>(&greedy_multi<GM_KF>), 160 * 1024); if (rc_attr) return rc_attr; }
-    hipLaunchKernelGGL(greedy_multi<GM_KF>, dim3((unsigned)((B + 7) / 8 * 8 * GM_PARTS)), dim3(512), lds, s, d);
-    LAUNCHCHK("greedy_multi");
-    return RNNT_OK;
-}
-
-int launch_persistent_decoder(rnnt_ctx* ctx, hipStream_t s, int n_total, int n_steps_override = 0, const int* nlim = nullptr,
-                              const int* slots = nullptr, int n_rows = 0) {
-    // stream pool: the decoder a context holding only that stream would run (greedy_multi wherever the context allows it at all; the
-    // caller launches at most n_cus / GM_PARTS rows at a time so that the grid is resident at once)
-    if (slots ? pool_multi_ok(ctx) : multi_decoder_ok(ctx)) return launch_multi_decoder(ctx, s, n_total, n_steps_override, nlim, slots, n_rows);
-    if (coop_decoder_ok(ctx) && !nlim && !n_steps_override && !slots) {
-        // cooperative decoder: 4 x 16 resident workgroups, weights stationary in LDS, tagged-word exchanges
-        FlowP c;
-        memset(&c, 0, sizeof(c));
-        c.whh = ctx->whh_il; c.egate = ctx->egate; c.wjc = ctx->wjc; c.bjc = ctx->bjc; c.wout = ctx->wout; c.bout = ctx->bout;
-        c.encp = ctx->encp; c.h = ctx->h; c.c = ctx->c; c.sel = ctx->sel; c.tok = ctx->tok; c.fidx = ctx->fidx;
-        c.nsym = ctx->nsym; c.count = ctx->count; c.tokens = ctx->tokens; c.ctrl = ctx->dec_ctrl;
-        c.xh = ctx->flow_buf; c.xz = ctx->flow_buf + FLOW_XH_WORDS; c.xa = ctx->flow_buf + 2 * FLOW_XH_WORDS;
-        c.fstride_f = (long long)ctx->fstride * D; c.bstride = (long long)ctx->cfg.max_streams * D;
-        c.B = ctx->n_streams; c.vocab = ctx->cfg.vocab_size; c.blank = ctx->cfg.blank_id; c.n_steps = ctx->cfg.n_steps;
-        c.max_tokens = ctx->cfg.max_tokens; c.n_total = n_total;
-        c.timeout_ticks = 300000000ll;   // 3 s per wait (100 MHz counter)
-        static const bool fdbg = getenv("RNNT_COOP_DBG") != nullptr;
-        c.dbg = fdbg ? reinterpret_cast<long long*>(ctx->flow_buf + FLOW_WORDS) : nullptr;
-        hipLaunchKernelGGL(greedy_flow, dim3(FLOW_G), dim3(256), 0, s, c);
-        LAUNCHCHK("greedy_flow");
-        return RNNT_OK;
-    }
-    DecP d;
-    memset(&d, 0, sizeof(d));
-    d.whh = ctx->whh_il; d.egate = ctx->egate; d.wjc = ctx->wjc; d.bjc = ctx->bjc; d.wout = ctx->wout; d.bout = ctx->bout;
-    d.encp = ctx->encp; d.h = ctx->h; d.c = ctx->c; d.sel = ctx->sel; d.tok = ctx->tok; d.fidx = ctx->fidx; d.nsym = ctx->nsym;
-    d.count = ctx->count; d.tokens = ctx->tokens; d.ctrl = ctx->dec_ctrl;
-    d.fstride_f = (long long)ctx->fstride * D; d.bstride = (long long)ctx->cfg.max_streams * D;
-    d.B = ctx->n_streams; d.vocab = ctx->cfg.vocab_size; d.blank = ctx->cfg.blank_id; d.n_steps = ctx->cfg.n_steps;
-    d.max_tokens = ctx->cfg.max_tokens; d.n_total = n_total;
-    if (n_steps_override > 0) d.n_steps = n_steps_override;
-    d.nlim = nlim;
-    if (slots) { d.slots = slots; d.B = n_rows; }
-    d.timeout_ticks = 500000000ll;   // 5 s of the 100 MHz real-time counter: every wait in the kernel is bounded
-    const int B = d.B;
-    static const int kf = getenv("RNNT_DEC_KF") ? atoi(getenv("RNNT_DEC_KF")) : 4;   // frames per vocabulary pass
-    if (kf == 1) hipLaunchKernelGGL(greedy_stream<1>, dim3(B), dim3(512), 0, s, d);
-    else if (kf == 2) hipLaunchKernelGGL(greedy_stream<2>, dim3(B), dim3(512), 0, s, d);
-    else if (kf == 8) hipLaunchKernelGGL(greedy_stream<8>, dim3(B), dim3(512), 0, s, d);
-    else hipLaunchKernelGGL(greedy_stream<4>, dim3(B), dim3(512), 0, s, d);
-    LAUNCHCHK("greedy_stream");
-    return RNNT_OK;
-}
-
-int init_decoder_ctrl(rnnt_ctx* ctx, hipStream_t s, int frames_ready) {
-    if (coop_decoder_ok(ctx))   // tags restart at 1 every launch: no word of an earlier launch may survive
-        HIPCHK(hipMemsetAsync(ctx->flow_buf, 0, (size_t)FLOW_WORDS * sizeof(unsigned long long), s));
-    hipLaunchKernelGGL(fill_i32, dim3(1), dim3(64), 0, s, ctx->dec_ctrl, 0, 32LL);
-    LAUNCHCHK("fill_i32");
-    hipLaunchKernelGGL(publish_frames, dim3(1), dim3(1), 0, s, ctx->dec_ctrl, frames_ready);
-    LAUNCHCHK("publish_frames");
-    return RNNT_OK;
-}
-
-// One-time check that a kernel on `s2` can stay resident while kernels on `s` run (what the pipelined resident decoder
-// relies on).  Bounded to 20 ms; on failure the pipelined path falls back to graph-launched evaluation batches.
-int probe_overlap(rnnt_ctx* ctx, hipStream_t s, hipStream_t s2) {
-    hipLaunchKernelGGL(fill_i32, dim3(1), dim3(64), 0, s, ctx->dec_ctrl, 0, 32LL);
-    LAUNCHCHK("fill_i32");
-    HIPCHK(hipStreamSynchronize(s));
-    hipLaunchKernelGGL(probe_overlap_wait, dim3(1), dim3(1), 0, s2, ctx->dec_ctrl, 2000000LL);
-    LAUNCHCHK("probe_overlap_wait");
-    hipLaunchKernelGGL(publish_frames, dim3(1), dim3(1), 0, s, ctx->dec_ctrl, 1);
-    LAUNCHCHK("publish_frames");
-    HIPCHK(hipStreamSynchronize(s2));
-    HIPCHK(hipStreamSynchronize(s));
-    int r[2] = {0, 0};
-    HIPCHK(hipMemcpy(r, ctx->dec_ctrl, sizeof(r), hipMemcpyDeviceToHost));
-    ctx->overlap_ok = r[1] ? 1 : 0;
-    if (!ctx->overlap_ok)
-        fprintf(stderr, "[rnnt] kernels of two HIP streams do not overlap here (serialising profiler or shared hardware queue): "
-                        "the resident decoder is replaced by launched evaluation batches\n");
-    return RNNT_OK;
-}
-
-// wait for the decoder and check its error word; updates the evaluation counter
-int finish_persistent_decoder(rnnt_ctx* ctx, hipStream_t s) {
-    HIPCHK(hipMemcpyAsync(ctx->pinned + 12, ctx->dec_ctrl, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    ctx->greedy_steps += ctx->pinned[14];
-    if (getenv("RNNT_GM_DBG") && multi_decoder_ok(ctx)) {
-        long long t[16];
-        (void)hipMemcpy(t, ctx->flow_buf + FLOW_WORDS, sizeof(t), hipMemcpyDeviceToHost);
-        const double ev = t[8] > 0 ? (double)t[8] : 1.0, sy = t[9] > 0 ? (double)t[9] : 1.0;
-        fprintf(stderr, "[greedy_multi] stream 0: %lld passes, %lld symbols; us per pass: frames %.2f, decide-tail %.2f, z+logits %.2f, wait XA %.2f; "
-                        "us per symbol: W_hh %.2f, cell+W_c %.2f, wait X1 %.2f\n",
-                t[8], t[9], t[0] / ev / 100.0, t[6] / ev / 100.0, t[4] / ev / 100.0, t[5] / ev / 100.0, t[1] / sy / 100.0, t[2] / sy / 100.0, t[3] / sy / 100.0);
-    }
-    if (getenv("RNNT_COOP_DBG") && coop_decoder_ok(ctx)) {
-        long long t[16];
-        (void)hipMemcpy(t, ctx->flow_buf + FLOW_WORDS, sizeof(t), hipMemcpyDeviceToHost);
-        const double ev = t[11] > 0 ? (double)t[11] : 1.0;
-        fprintf(stderr, "[flow] workgroup 0: %lld evals; us/eval: wait XA %.2f, decide+L %.2f, wait XH %.2f, J %.2f, wait XZ %.2f, O+send %.2f; polls/eval: XA %.2f XH %.2f XZ %.2f\n",
-                t[11], t[0] / ev / 100.0, t[1] / ev / 100.0, t[2] / ev / 100.0, t[3] / ev / 100.0, t[4] / ev / 100.0, t[5] / ev / 100.0, t[8] / ev, t[9] / ev, t[10] / ev);
-    }
-    if (ctx->pinned[13] != 0) return fail(ctx, RNNT_ERR_STATE, "persistent decoder gave up (code %d: 1 = frame wait, 2 = barrier, 3 = idle bound)", ctx->pinned[13]);
-    return RNNT_OK;
-}
-
-// the resident decoder over buffered frames that are all there: control block, launch, wait (synchronises s)
-int decode_resident(rnnt_ctx* ctx, hipStream_t s, int n_total, const int* nlim = nullptr, const int* slots = nullptr, int n_rows = 0, int n_steps = 0) {
-    int rc;
-    if ((rc = init_decoder_ctrl(ctx, s, n_total))) return rc;
-    if ((rc = launch_persistent_decoder(ctx, s, n_total, n_steps, nlim, slots, n_rows))) return rc;
-    return finish_persistent_decoder(ctx, s);
 }
 
 // The encoder's last two launches for a chunk: after_norm of rows x [B * tq] into frames [fpos, fpos + tq) of every stream's frame

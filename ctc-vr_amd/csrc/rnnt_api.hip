@@ -117,16 +117,15 @@ struct rnnt_ctx {
     float *h = nullptr, *c = nullptr, *pred = nullptr, *z = nullptr, *logits = nullptr;
     int *tok = nullptr, *fidx = nullptr, *nsym = nullptr, *count = nullptr, *tokens = nullptr, *n_active = nullptr, *klen = nullptr, *sel = nullptr;
     unsigned long long* key = nullptr;
-    int* dec_ctrl = nullptr;   // persistent decoder control block: [0] frames_ready, [1] error, [2] evaluations, [3..6] cooperative decoder
+    int* dec_ctrl = nullptr;   // persistent decoder control block: [0] frames_ready, [1] error, [2] evaluations, [4] abort word of greedy_multi
     int use_persistent = 1;
     int attn_stream = 1;       // RNNT_ATTN_STREAM=0: LDS-tiled attention kernel for every chunk
     int fuse_after_norm = 1;   // RNNT_FUSE_AFTER_NORM=0: keep after_norm as its own launch in the pipelined greedy path
     int overlap_ok = -1;       // -1 not probed; 1: kernels of the decode stream run concurrently with the caller's stream
-    int use_coop = 0;          // RNNT_COOP=1: cooperative weights-stationary decoder (n_streams <= 64), experiment
     int use_multi = 1;         // RNNT_DEC_MULTI=0: one CU per stream (greedy_stream) instead of greedy_multi (4 CUs per stream)
     int n_cus = 0;
     unsigned long long *gm_x1 = nullptr, *gm_xa = nullptr;   // greedy_multi mailboxes
-    unsigned long long* flow_buf = nullptr;   // greedy_flow exchange words: xh [2][64][256] | xz [2][64][256] | xa [2][4][16][16][4]
+    long long* gm_dbg = nullptr;              // [16] greedy_multi phase timers (RNNT_GM_DBG=1)
     const float *wjc = nullptr, *bjc = nullptr;   // folded joint.pred_ffn o predictor.projection
     const float *wctc = nullptr, *bctc = nullptr; // ctc_head.ctc_lo (optional)
     // beam search: state pools [rows][n_steps+1][512] (ping-pong), per-row buffers
@@ -242,6 +241,7 @@ struct rnnt_ctx {
 };
 
 #include "host_launch.hip.inc"
+#include "host_decode.hip.inc"
 #include "host_lm.hip.inc"
 
 extern "C" {

@@ -12,7 +12,7 @@
 //   rnnt_joint     joint_lattice_rows: the T x U joint lattice (tanh-add, projection, log-softmax) as one persistent kernel, pack_joint_w
 //   rnnt_encoder   conv1_relu, layer_norm, rel_attention (LDS tiles, online softmax), rel_attention_stream (<= 4 queries,
 //                  direct row streaming), dwconv_bn_silu, conv_ring_init
-//   rnnt_decode    greedy_decide (launched path), greedy_stream (resident decoder), greedy_flow (cooperative experiment),
+//   rnnt_decode    greedy_decide (launched path), greedy_stream / greedy_multi (resident decoders),
 //                  publish_frames, probe_overlap_wait, unpack_keys
 //   rnnt_frontend  reflect_pad, power_spectrum (rnnt_fbank)
 //   rnnt_beam      beam_chain, beam_reduce, beam_gather, log_softmax_rows

@@ -1,4 +1,5 @@
-// Greedy decoding: launched decision kernel, resident per-stream decoder (greedy_stream), cooperative experiment (greedy_flow), control helpers.
+// Greedy decoding: launched decision kernel (greedy_decide), the two resident decoders' parameter block (DecP), the resident per-stream
+// decoder (greedy_stream), control helpers, the resident four-CUs-per-stream decoder (greedy_multi).  Host side: host_decode.hip.inc.
 // Part of rnnt_kernels.hip.h (include that umbrella, not this file).
 #pragma once
 
@@ -99,7 +100,7 @@ struct DecP {
     int* nsym;
     int* count;
     int* tokens;          // [B][max_tokens]
-    int* ctrl;            // [0] frames_ready (published by the encoder stream), [1] error flag, [2] evaluations (stats)
+    int* ctrl;            // [0] frames_ready (published by the encoder stream), [1] error flag, [2] evaluations (stats), [4] abort (greedy_multi)
     long long fstride_f;  // floats between streams in encp
     long long bstride;    // floats between the two state buffers
     int B, vocab, blank, n_steps, max_tokens, n_total;
@@ -107,6 +108,7 @@ struct DecP {
     const int* nlim;           // optional per-stream frame count (offline search over padded batches); null = n_total for all
     const int* slots;          // stream pool: workgroup i decodes stream slots[i] over its frames [0, n_total), B = active rows; null = stream i
 };
+constexpr int GREEDY_KF = 4;   // frames per vocabulary pass of both resident decoders (the one instantiation of each)
 
 template <int SPW, int NTH, int U = 2, typename Epi>
 __device__ __forceinline__ void dec_matvec(const float* __restrict__ W, int nrows, const float (*x)[RNNT_D], Epi epi) {
@@ -311,376 +313,6 @@ __global__ void unpack_keys(const unsigned long long* __restrict__ key, int* __r
         out[i] = (int)(0xFFFFFFFFu - (unsigned)(key[i] & 0xFFFFFFFFull));
 }
 
-// ------------------------------------------------------------------------------------------------
-// greedy_flow: cooperative, weights-STATIONARY greedy decoder for B <= 64 streams (experiment, RNNT_COOP=1).
-// Workgroup g = sg * 16 + cg owns streams [16 sg, 16 sg + 16) and column group cg of every weight matrix, resident in
-// LDS for the whole call: W_hh rows [64 cg, +64) (16 hidden units x 4 gates), W_c rows [16 cg, +16), W_out rows
-// [26 cg, +26).  An evaluation is three exchanges among the 16 workgroups of a stream group
-//     h' slices  ->  z slices  ->  per-workgroup argmax partials (+ frames_ready from cg 0)
-// and every exchanged 32-bit value travels as ONE 8-byte word (payload | tag << 32, tag = evaluation number), written
-// with a single write-through store and read with an L1-bypassing load: a word is valid iff its tag matches, so there
-// is no counter, no store drain and no fence on the exchange path -- a consumer's cost is the round trips it needs to
-// see all its words (the barrier-based predecessor paid ~10 us per exchange for drain + atomic + poll + load).  Buffers
-// alternate by evaluation parity; a workgroup can only be one exchange ahead of the slowest of its group, so a slot is
-// never rewritten before every reader has passed it.  Every workgroup derives the same decisions from the same words
-// and keeps the stream state (token, frame, counts) privately; cell states live in registers of the lanes that own them.
-// The predictor is re-evaluated only for streams that emitted (dirty), as in greedy_stream.  Spins are wall-clock bounded.
-// ------------------------------------------------------------------------------------------------
-struct FlowP {
-    const float* whh; const float* egate; const float* wjc; const float* bjc; const float* wout; const float* bout;
-    const float* encp;
-    float* h; float* c;                 // [2][bstride] state buffers (committed one by sel[]; written back to buffer 0)
-    int* sel; int* tok; int* fidx; int* nsym; int* count; int* tokens;
-    unsigned long long* xh;             // [2][64][256] tagged h' words
-    unsigned long long* xz;             // [2][64][256] tagged z words
-    unsigned long long* xa;             // [2][4][16][16][4] tagged (ordered max, index, frames_ready, -) per (group, workgroup, stream)
-    int* ctrl;                          // [0] frames_ready, [1] error, [2] evaluations, [4] abort
-    long long fstride_f, bstride;
-    int B, vocab, blank, n_steps, max_tokens, n_total;
-    long long timeout_ticks;
-    long long* dbg;                     // optional [16]: phase timers (100 MHz ticks) and poll iterations of workgroup 0
-};
-
-__device__ __forceinline__ float ld_sc1f(const float* p) {
-    return __uint_as_float(__hip_atomic_load(reinterpret_cast<const unsigned*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-__device__ __forceinline__ int ld_sc1i(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_sc1i(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ unsigned long long ld_tag(const unsigned long long* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st_tag(unsigned long long* p, unsigned payload, unsigned tag) {
-    __hip_atomic_store(p, ((unsigned long long)tag << 32) | payload, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-#define FLOW_G 64      // workgroups: 4 stream groups x 16 column groups
-#define FLOW_CG 16
-#define FLOW_LD 260
-#define FLOW_NONE 0x7fffffff
-#define FLOW_VOCAB (FLOW_CG * 26)   // W_out rows held by a stream group (26 per column group): larger vocabularies take another decoder
-
-// wait until all NW words of this thread carry `tag`; false = abort (timeout or another workgroup gave up)
-template <int NW>
-__device__ __forceinline__ bool flow_wait(const FlowP& p, const unsigned long long* src, unsigned tag, unsigned* out, int* s_flag, long long* polls) {
-    const long long t0 = (long long)__builtin_amdgcn_s_memrealtime();
-    while (true) {
-        ++*polls;
-        unsigned long long v[NW];
-#pragma unroll
-        for (int j = 0; j < NW; ++j) v[j] = ld_tag(src + j);
-        int ok = 1;
-#pragma unroll
-        for (int j = 0; j < NW; ++j) {
-            ok &= (unsigned)(v[j] >> 32) == tag ? 1 : 0;
-            out[j] = (unsigned)v[j];
-        }
-        if (__syncthreads_and(ok)) return true;
-        if (threadIdx.x == 0) {
-            int bad = ld_sc1i(p.ctrl + 4) != 0 ? 1 : 0;
-            if (!bad && (long long)__builtin_amdgcn_s_memrealtime() - t0 > p.timeout_ticks) {
-                st_sc1i(p.ctrl + 1, 2);
-                st_sc1i(p.ctrl + 4, 1);
-                bad = 1;
-            }
-            *s_flag = bad;
-        }
-        __syncthreads();
-        if (*s_flag) return false;
-        __builtin_amdgcn_s_sleep(1);
-    }
-}
-
-__global__ __launch_bounds__(256) void greedy_flow(FlowP p) {
-    __shared__ __attribute__((aligned(16))) float Wl[64 * FLOW_LD], Wj[16 * FLOW_LD], Wo[32 * FLOW_LD];
-    __shared__ __attribute__((aligned(16))) float Hn[16 * FLOW_LD];     // h' of every stream (= committed h of the streams that emitted)
-    __shared__ __attribute__((aligned(16))) float X[16 * FLOW_LD];      // z of every stream
-    __shared__ __attribute__((aligned(16))) float red[4 * 256];
-    __shared__ int s_tok[16], s_fidx[16], s_nsym[16], s_count[16], s_act[16], s_had[16], s_dirty[16], s_emit[16];
-    __shared__ unsigned s_pv[16][16];
-    __shared__ int s_pi[16][16];
-    __shared__ unsigned s_bv[2][16];
-    __shared__ int s_bi[2][16];
-    __shared__ int s_flag, s_nf, s_done, s_any;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int sg = blockIdx.x / FLOW_CG, cg = blockIdx.x % FLOW_CG;
-    const int i = lane & 15, kq = lane >> 4;
-    const int b0 = 16 * sg;
-    const int nb = min(16, p.B - b0);
-    if (nb <= 0) return;                                       // the whole stream group is absent
-    // ---- resident weight slices ---------------------------------------------------------------------------------------
-    for (int e = tid; e < 64 * 64; e += 256) {
-        const int r = e >> 6, c4 = (e & 63) * 4;
-        *reinterpret_cast<float4*>(&Wl[r * FLOW_LD + c4]) = ldg4(p.whh + (long long)(64 * cg + r) * RNNT_D + c4);
-        if (r < 16) *reinterpret_cast<float4*>(&Wj[r * FLOW_LD + c4]) = ldg4(p.wjc + (long long)(16 * cg + r) * RNNT_D + c4);
-        if (r < 32) *reinterpret_cast<float4*>(&Wo[r * FLOW_LD + c4]) = ldg4(p.wout + (long long)min(26 * cg + min(r, 25), p.vocab - 1) * RNNT_D + c4);
-    }
-    // ---- private copy of the streams' state --------------------------------------------------------------------------------
-    {
-        const int m = tid >> 4, c16 = (tid & 15) * 16;
-        const int bb = b0 + min(m, nb - 1);
-        const float* hp = p.h + (long long)(ldgi(p.sel + bb) & 1) * p.bstride + (long long)bb * RNNT_D + c16;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) *reinterpret_cast<float4*>(&Hn[m * FLOW_LD + c16 + 4 * j]) = ldg4(hp + 4 * j);
-    }
-    if (tid < 16) {
-        const bool v = tid < nb;
-        const int bb = b0 + tid;
-        s_tok[tid] = v ? ldgi(p.tok + bb) : p.blank;
-        s_fidx[tid] = v ? ldgi(p.fidx + bb) : p.n_total;
-        s_nsym[tid] = v ? ldgi(p.nsym + bb) : 0;
-        s_count[tid] = v ? ldgi(p.count + bb) : 0;
-        s_act[tid] = 0; s_had[tid] = 0; s_dirty[tid] = 1; s_emit[tid] = 0;
-    }
-    // cell state of my (stream 4 kq + r, unit 16 cg + 4 wave + i / 4), held by the lanes with i % 4 == 0
-    const int unit = 16 * cg + 4 * wave + (i >> 2);
-    float cc[4], hc[4], cc2[4], hh2[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int bb = b0 + min(4 * kq + r, nb - 1);
-        const long long off = (long long)(ldgi(p.sel + bb) & 1) * p.bstride + (long long)bb * RNNT_D + unit;
-        cc[r] = ldg1(p.c + off);
-        hc[r] = ldg1(p.h + off);
-        cc2[r] = cc[r];
-        hh2[r] = hc[r];
-    }
-    unsigned e = 1;                                            // evaluation number = tag
-    int seen_nf = 0, evals = 0;
-    long long polls[3] = {0, 0, 0}, tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tl = (long long)__builtin_amdgcn_s_memrealtime();
-#define FLOW_T(k) { if (p.dbg && blockIdx.x == 0 && tid == 0) { const long long t_ = (long long)__builtin_amdgcn_s_memrealtime(); tacc[k] += t_ - tl; tl = t_; } }
-    // round 0: no argmax yet, only frames_ready from cg 0
-    if (tid < 16) {
-        unsigned long long* q = p.xa + ((((size_t)(e & 1) * 4 + sg) * 16 + cg) * 16 + tid) * 4;
-        st_tag(q + 0, 0u, e);
-        st_tag(q + 1, (unsigned)FLOW_NONE, e);
-        st_tag(q + 2, cg == 0 ? (unsigned)ld_sc1i(p.ctrl) : 0u, e);
-    }
-    __syncthreads();
-    while (true) {
-        const unsigned par = e & 1;
-        FLOW_T(5)
-        // ---- D: gather the 16 partials of every stream, decide -----------------------------------------------------------
-        {
-            unsigned w3[3];
-            const int wg = tid >> 4, m = tid & 15;
-            if (!flow_wait<3>(p, p.xa + ((((size_t)par * 4 + sg) * 16 + wg) * 16 + m) * 4, e, w3, &s_flag, &polls[0])) return;
-            FLOW_T(0)
-            s_pv[wg][m] = w3[0];
-            s_pi[wg][m] = (int)w3[1];
-            if (tid == 0) s_nf = (int)w3[2];
-        }
-        __syncthreads();
-        if (tid < 16) {
-            const int m = tid;
-            unsigned bv = 0u;
-            int bi = FLOW_NONE;
-            for (int g = 0; g < 16; ++g) {
-                const unsigned v = s_pv[g][m];
-                const int ix = s_pi[g][m];
-                if (v > bv || (v == bv && ix < bi)) { bv = v; bi = ix; }
-            }
-            int emit = 0;
-            if (s_had[m] && bi != FLOW_NONE) {
-                if (bi == p.blank) { s_fidx[m] += 1; s_nsym[m] = 0; }
-                else {
-                    const int cnt = s_count[m];
-                    if (cg == 0 && cnt < p.max_tokens) p.tokens[(long long)(b0 + m) * p.max_tokens + cnt] = bi;
-                    s_count[m] = cnt + 1;
-                    s_tok[m] = bi;
-                    const int ns = s_nsym[m] + 1;
-                    if (ns >= p.n_steps) { s_nsym[m] = 0; s_fidx[m] += 1; } else { s_nsym[m] = ns; }
-                    s_dirty[m] = 1;
-                    emit = 1;
-                }
-            }
-            s_emit[m] = emit;
-            const int f = s_fidx[m];
-            const int act = (m < nb && f < p.n_total && f < s_nf) ? 1 : 0;
-            s_act[m] = act;
-            const unsigned long long m16 = 0xFFFFull;
-            const unsigned long long anyact = __ballot(act != 0) & m16, notdone = __ballot(m < nb && f < p.n_total) & m16;
-            if (m == 0) { s_done = notdone == 0ull ? 1 : 0; s_any = anyact != 0ull ? 1 : 0; }
-        }
-        __syncthreads();
-        // commit the cell / hidden state of the streams that emitted (their Hn row already is the new h)
-        if ((i & 3) == 0) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (s_emit[4 * kq + r]) { cc[r] = cc2[r]; hc[r] = hh2[r]; }
-        }
-        if (s_done) break;
-        if (s_nf > seen_nf) {   // new encoder frames were published: one agent-scope acquire before reading enc_proj rows
-            if (tid == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            seen_nf = s_nf;
-            __syncthreads();
-        }
-        const bool anyact = s_any != 0;
-        if (anyact) {
-            // ---- L: gates of my 16 units for the 16 streams; new candidate (h', c') only where the predictor input changed ----
-            {
-                f32x4_ acc = (f32x4_){0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-                for (int u = 0; u < 16; ++u) {
-                    const float4 a = *reinterpret_cast<const float4*>(&Hn[i * FLOW_LD + 16 * u + 4 * kq]);
-                    const float4 w = *reinterpret_cast<const float4*>(&Wl[(16 * wave + i) * FLOW_LD + 16 * u + 4 * kq]);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, w.x, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, w.y, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, w.z, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, w.w, acc, 0, 0, 0);
-                }
-                const int n = 64 * cg + 16 * wave + i;             // gate column (interleaved i,f,g,o)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int m = 4 * kq + r;
-                    const float v = acc[r] + ldg1(p.egate + (long long)s_tok[m] * (4 * RNNT_D) + n);
-                    const float gf = __shfl_down(v, 1, 64), gg = __shfl_down(v, 2, 64), go = __shfl_down(v, 3, 64);
-                    if ((i & 3) == 0) {
-                        if (s_dirty[m] && m < nb) {
-                            const float c2v = sigmoidf_(gf) * cc[r] + sigmoidf_(v) * tanhf(gg);
-                            cc2[r] = c2v;
-                            hh2[r] = sigmoidf_(go) * tanhf(c2v);
-                        }
-                        st_tag(p.xh + ((size_t)par * 64 + b0 + m) * RNNT_D + unit, __float_as_uint(hh2[r]), e);
-                    }
-                }
-            }
-            __syncthreads();                                       // everybody has read Hn and s_dirty
-            if (tid < 16) s_dirty[tid] = 0;
-            // ---- J: all h' of my streams -> z = tanh(enc_proj[t] + h' W_c^T + b_c), my 16 columns ------------------------------
-            {
-                unsigned w16[16];
-                const int m = tid >> 4, c16 = (tid & 15) * 16;
-                FLOW_T(1)
-                if (!flow_wait<16>(p, p.xh + ((size_t)par * 64 + b0 + m) * RNNT_D + c16, e, w16, &s_flag, &polls[1])) return;
-                FLOW_T(2)
-#pragma unroll
-                for (int j = 0; j < 16; ++j) Hn[m * FLOW_LD + c16 + j] = __uint_as_float(w16[j]);
-            }
-            __syncthreads();
-            {
-                f32x4_ acc = (f32x4_){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int u = 4 * wave; u < 4 * wave + 4; ++u) {
-                    const float4 a = *reinterpret_cast<const float4*>(&Hn[i * FLOW_LD + 16 * u + 4 * kq]);
-                    const float4 w = *reinterpret_cast<const float4*>(&Wj[i * FLOW_LD + 16 * u + 4 * kq]);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, w.x, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, w.y, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, w.z, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, w.w, acc, 0, 0, 0);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) red[wave * 256 + r * 64 + lane] = acc[r];
-            }
-            __syncthreads();
-            {   // 256 outputs (16 streams x 16 columns), one per thread
-                const int r = tid >> 6, ln = tid & 63;
-                const float sum = (red[tid] + red[256 + tid]) + (red[512 + tid] + red[768 + tid]);
-                const int m = 4 * (ln >> 4) + r, n = 16 * cg + (ln & 15);
-                float ev = 0.f;
-                if (s_act[m]) ev = ldg1(p.encp + (long long)(b0 + m) * p.fstride_f + (long long)s_fidx[m] * RNNT_D + n);
-                st_tag(p.xz + ((size_t)par * 64 + b0 + m) * RNNT_D + n, __float_as_uint(tanhf(sum + ldg1(p.bjc + n) + ev)), e);
-            }
-            // ---- O: all z of my streams -> logits of my 26 vocabulary rows -> argmax partial ----------------------------------------
-            {
-                unsigned w16[16];
-                const int m = tid >> 4, c16 = (tid & 15) * 16;
-                FLOW_T(3)
-                if (!flow_wait<16>(p, p.xz + ((size_t)par * 64 + b0 + m) * RNNT_D + c16, e, w16, &s_flag, &polls[2])) return;
-                FLOW_T(4)
-#pragma unroll
-                for (int j = 0; j < 16; ++j) X[m * FLOW_LD + c16 + j] = __uint_as_float(w16[j]);
-            }
-            __syncthreads();
-            {
-                const int tile = wave >> 1, kh = wave & 1;
-                f32x4_ acc = (f32x4_){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int u = 8 * kh; u < 8 * kh + 8; ++u) {
-                    const float4 a = *reinterpret_cast<const float4*>(&X[i * FLOW_LD + 16 * u + 4 * kq]);
-                    const float4 w = *reinterpret_cast<const float4*>(&Wo[(16 * tile + i) * FLOW_LD + 16 * u + 4 * kq]);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, w.x, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, w.y, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, w.z, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, w.w, acc, 0, 0, 0);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) red[wave * 256 + r * 64 + lane] = acc[r];
-            }
-            __syncthreads();
-            if (tid < 128) {   // 2 tiles x (4 regs x 64 lanes): thread = (tile, lane), loops the 4 regs
-                const int t2 = tid >> 6, ln = tid & 63;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float sum = red[(2 * t2) * 256 + r * 64 + ln] + red[(2 * t2 + 1) * 256 + r * 64 + ln];
-                    const int m = 4 * (ln >> 4) + r;
-                    const int jr = 16 * t2 + (ln & 15);            // local vocabulary row 0..31 (26 valid)
-                    const int n = 26 * cg + jr;
-                    const bool nin = jr < 26 && n < p.vocab;
-                    float v = nin ? sum + ldg1(p.bout + min(n, p.vocab - 1)) : -INFINITY;
-                    int bi = nin ? n : FLOW_NONE;
-#pragma unroll
-                    for (int o = 8; o > 0; o >>= 1) {
-                        const float ov = __shfl_xor(v, o, 16);
-                        const int oi = __shfl_xor(bi, o, 16);
-                        if (ov > v || (ov == v && oi < bi)) { v = ov; bi = oi; }
-                    }
-                    if ((ln & 15) == 0) {
-                        unsigned uu = 0u;
-                        if (bi != FLOW_NONE) {
-                            uu = __float_as_uint(v);
-                            uu = (uu & 0x80000000u) ? ~uu : (uu | 0x80000000u);   // order-preserving; > 0 for every real value
-                        }
-                        s_bv[t2][m] = uu;
-                        s_bi[t2][m] = bi;
-                    }
-                }
-            }
-            __syncthreads();
-            ++evals;
-        } else {
-            __builtin_amdgcn_s_sleep(64);                          // nothing decodable: wait for the encoder
-            if (tid < 16) { s_bv[0][tid] = 0u; s_bv[1][tid] = 0u; s_bi[0][tid] = FLOW_NONE; s_bi[1][tid] = FLOW_NONE; }
-            __syncthreads();
-        }
-        // ---- partial argmax of my rows + frames_ready (cg 0) for the next evaluation -------------------------------------------
-        if (tid < 16) {
-            const int m = tid;
-            unsigned bv = s_bv[0][m];
-            int bi = s_bi[0][m];
-            if (s_bv[1][m] > bv || (s_bv[1][m] == bv && s_bi[1][m] < bi)) { bv = s_bv[1][m]; bi = s_bi[1][m]; }
-            if (!s_act[m]) { bv = 0u; bi = FLOW_NONE; }
-            s_had[m] = s_act[m];
-            unsigned long long* q = p.xa + ((((size_t)((e + 1) & 1) * 4 + sg) * 16 + cg) * 16 + m) * 4;
-            st_tag(q + 0, bv, e + 1);
-            st_tag(q + 1, (unsigned)bi, e + 1);
-            st_tag(q + 2, cg == 0 ? (unsigned)ld_sc1i(p.ctrl) : 0u, e + 1);
-        }
-        __syncthreads();
-        ++e;
-    }
-    // ---- canonical state for the host / the next call (buffer 0 becomes the committed one) ---------------------------------
-    if ((i & 3) == 0) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int m = 4 * kq + r;
-            if (m < nb) {
-                stg1(p.h + (long long)(b0 + m) * RNNT_D + unit, hc[r]);
-                stg1(p.c + (long long)(b0 + m) * RNNT_D + unit, cc[r]);
-            }
-        }
-    }
-    if (cg == 0 && tid < nb) {
-        const int b = b0 + tid;
-        p.tok[b] = s_tok[tid]; p.fidx[b] = s_fidx[tid]; p.nsym[b] = s_nsym[tid]; p.sel[b] = 0; p.count[b] = s_count[tid];
-    }
-    if (cg == 0 && tid == 0) atomicAdd(p.ctrl + 2, evals);
-    if (p.dbg && blockIdx.x == 0 && tid == 0) {
-        for (int k = 0; k < 8; ++k) p.dbg[k] = tacc[k];
-        for (int k = 0; k < 3; ++k) p.dbg[8 + k] = polls[k];
-        p.dbg[11] = evals;
-    }
-#undef FLOW_T
-}
-
 // frames_ready <- n (one thread; the kernel boundary before it released the encoder's writes)
 __global__ void publish_frames(int* ctrl, int n) {
     __hip_atomic_store(ctrl, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -719,20 +351,23 @@ __global__ void probe_overlap_wait(int* ctrl, long long ticks) {
 // order than greedy_stream's, i.e. equal to float32 rounding.  Needs 4 * B workgroups resident at once (B <= 64 on 256 CUs);
 // every wait is wall-clock bounded and an abort word releases the whole grid.
 // ------------------------------------------------------------------------------------------------
+
+// Agent-scope relaxed accesses of the exchange: L1-bypassing loads and write-through stores, one 8-byte word per value.
+__device__ __forceinline__ int ld_sc1i(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void st_sc1i(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ unsigned long long ld_tag(const unsigned long long* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void st_tag(unsigned long long* p, unsigned payload, unsigned tag) {
+    __hip_atomic_store(p, ((unsigned long long)tag << 32) | payload, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 #define GM_PARTS 4
 #define GM_X1 320            // words per part: 64 h' + 256 pp partials
 #define GM_WLD 260           // LDS row stride of the W_out slice (floats)
-struct DecMP {
-    const float* whh; const float* egate; const float* wjc; const float* bjc; const float* wout; const float* bout; const float* encp;
-    float* h; float* c;
-    int* sel; int* tok; int* fidx; int* nsym; int* count; int* tokens; int* ctrl;
+struct DecMP : DecP {           // slots: stream group i (mailboxes i) decodes stream slots[i]
     unsigned long long* x1;      // [2][B][4][GM_X1]
     unsigned long long* xa;      // [2][B][4][2 * KF]
-    long long fstride_f, bstride;
-    int B, vocab, blank, n_steps, max_tokens, n_total;
-    long long timeout_ticks;
-    const int* nlim;
-    const int* slots;            // stream pool: stream group i (mailboxes i) decodes stream slots[i] over its frames [0, n_total); null = stream i
     int rows_per;                // ceil(vocab / 4): vocabulary rows of a part (<= 128), resident in LDS
     long long* dbg;              // optional [16]: phase timers of workgroup (stream 0, part 0), 100 MHz ticks (RNNT_GM_DBG=1)
 };

@@ -341,15 +341,15 @@ def test_greedy_decode_grid(cfg, regime):
     _check_greedy(cfg[0], cfg[1], regime, ("per_chunk", "whole", "ragged"))
 
 
-PATHS = {"bf16x3": {}, "f16x3": {}, "dec_multi0": {"RNNT_DEC_MULTI": "0"}, "persistent0": {"RNNT_PERSISTENT": "0"}, "coop": {"RNNT_COOP": "1"}}
+PATHS = {"bf16x3": {}, "f16x3": {}, "dec_multi0": {"RNNT_DEC_MULTI": "0"}, "persistent0": {"RNNT_PERSISTENT": "0"}}
 
 
 @pytest.mark.parametrize("regime", ["mixed", "saturated"])
 @pytest.mark.parametrize("cfg", [(6, 0), (129, 128), (512, 0), (513, 0), (4336, 0)], ids=lambda c: f"V{c[0]}_blank{c[1]}")
 @pytest.mark.parametrize("path", list(PATHS))
 def test_greedy_decode_paths(path, cfg, regime, monkeypatch):
-    """The split numerics modes and the alternative decoders (greedy_stream for every V, the launched evaluation batches, the
-    cooperative decoder) on the configurations at greedy_multi's boundaries, at the high symbol rates where multi-frame
+    """The split numerics modes and the alternative decoders (greedy_stream for every V, the launched evaluation
+    batches) on the configurations at greedy_multi's boundaries, at the high symbol rates where multi-frame
     speculation is redone and the n_steps cap carries token and state across frames."""
     for k, v in PATHS[path].items():
         monkeypatch.setenv(k, v)

@@ -371,10 +371,10 @@ def test_full_size_properties(np_state_dict, numerics):
         assert pipelined[b] == want, b
 
 
-@pytest.mark.parametrize("env", [{"RNNT_PERSISTENT": "0"}, {"RNNT_COOP": "1"}, {"RNNT_ATTN_STREAM": "0"}, {"RNNT_LM": "0"},
+@pytest.mark.parametrize("env", [{"RNNT_PERSISTENT": "0"}, {"RNNT_ATTN_STREAM": "0"}, {"RNNT_LM": "0"},
                                  {"RNNT_LM": "0", "RNNT_FUSED": "0"}])
 def test_alternative_decoder_paths(np_state_dict, env, monkeypatch):
-    """The launched decode path (what a serialising profiler falls back to), the cooperative decoder, the LDS-tiled attention and
+    """The launched decode path (what a serialising profiler falls back to), the LDS-tiled attention and
     the wavefront schedules (fused / unfused; what a whole-utterance call with a cache reset in its middle falls back to from
     the layer-major schedule) produce the reference's tokens too."""
     from ctc_vr_amd.online_rnnt_model import StreamingBatch
