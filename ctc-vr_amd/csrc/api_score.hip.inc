@@ -1,10 +1,11 @@
-// C ABI: teacher-forced scoring -- the transducer and CTC negative log-likelihoods of given transcripts (forward only).
+// C ABI: teacher-forced scoring -- the transducer and CTC negative log-likelihoods of given transcripts (forward only) -- and
+// forced alignment: the best path of a given transcript and the frame of each of its tokens.
 // Included by rnnt_api.hip inside extern "C".  Kernels: joint_lattice_rows<.., PICK> (rnnt_joint.hip.h), rnnt_score.hip.h.
 
 // lengths and labels of a scoring call, checked on the host before anything is launched (what: the entry point's name)
 static int score_check(rnnt_ctx* ctx, const char* what, const float* enc_dev, const int32_t* enc_lens, const int32_t* targets, const int32_t* target_lens,
-                       int32_t B, int32_t T, int32_t Umax, double* nll_host) {
-    if (!ctx || !enc_dev || !enc_lens || !target_lens || !nll_host || (Umax > 0 && !targets)) return fail(ctx, RNNT_ERR_ARG, "%s: null argument", what);
+                       int32_t B, int32_t T, int32_t Umax, double* nll_host, bool labels = true) {
+    if (!ctx || !enc_dev || !enc_lens || !target_lens || !nll_host || (labels && Umax > 0 && !targets)) return fail(ctx, RNNT_ERR_ARG, "%s: null argument", what);
     if (B < 1 || T < 1 || Umax < 0) return fail(ctx, RNNT_ERR_ARG, "%s: B=%d T=%d Umax=%d", what, B, T, Umax);
     if (!ctx->finalized) return fail(ctx, RNNT_ERR_STATE, "weights not finalized");
     if (Umax > SCORE_UMAX) return fail(ctx, RNNT_ERR_SHAPE, "%s: Umax=%d exceeds %d labels", what, Umax, SCORE_UMAX);
@@ -12,7 +13,7 @@ static int score_check(rnnt_ctx* ctx, const char* what, const float* enc_dev, co
     for (int b = 0; b < B; ++b) {
         if (enc_lens[b] < 1 || enc_lens[b] > T) return fail(ctx, RNNT_ERR_ARG, "%s: utterance %d has %d frames, outside [1, %d]", what, b, enc_lens[b], T);
         if (target_lens[b] < 0 || target_lens[b] > Umax) return fail(ctx, RNNT_ERR_ARG, "%s: utterance %d has %d labels, outside [0, %d]", what, b, target_lens[b], Umax);
-        for (int u = 0; u < target_lens[b]; ++u) {
+        for (int u = 0; labels && u < target_lens[b]; ++u) {
             const int y = targets[(size_t)b * Umax + u];
             if (y < 0 || y >= V) return fail(ctx, RNNT_ERR_ARG, "%s: label %d of utterance %d is %d, outside [0, %d)", what, u, b, y, V);
             if (y == blank) return fail(ctx, RNNT_ERR_ARG, "%s: label %d of utterance %d is the blank (%d)", what, u, b, blank);
@@ -23,7 +24,8 @@ static int score_check(rnnt_ctx* ctx, const char* what, const float* enc_dev, co
 
 // The int work buffer of a scoring call, uploaded in ONE copy: targets [B][ts] (entries beyond a row's length replaced by the
 // blank: they are neither validated nor used, and the padded cells they reach stay defined) | lens [2][B] | tok [U1][B] (the
-// predictor's input of step u: blank, then y_1 .. y_U; transducer only).  ts = max(Umax, 1).
+// predictor's input of step u: blank, then y_1 .. y_U; transducer only).  ts = max(Umax, 1).  targets may be null when the
+// caller brings its own lattice: the rows then stay blank.
 static int score_upload(rnnt_ctx* ctx, hipStream_t s, const int32_t* enc_lens, const int32_t* targets, const int32_t* target_lens, int B,
                         int Umax, bool with_tok, std::vector<int>& host, int** tg_dev, int** lens_dev, int** tok_dev) {
     const int ts = Umax > 0 ? Umax : 1, U1 = Umax + 1, blank = ctx->cfg.blank_id;
@@ -33,7 +35,7 @@ static int score_upload(rnnt_ctx* ctx, hipStream_t s, const int32_t* enc_lens, c
     for (int b = 0; b < B; ++b) {
         lens[b] = enc_lens[b];
         lens[B + b] = target_lens[b];
-        for (int u = 0; u < target_lens[b]; ++u) {
+        for (int u = 0; targets && u < target_lens[b]; ++u) {
             host[(size_t)b * ts + u] = targets[(size_t)b * Umax + u];
             if (with_tok) tok[(size_t)(u + 1) * B + b] = targets[(size_t)b * Umax + u];
         }
@@ -48,27 +50,25 @@ static int score_upload(rnnt_ctx* ctx, hipStream_t s, const int32_t* enc_lens, c
     return RNNT_OK;
 }
 
-// Transducer negative log-likelihood of B (frames, transcript) rows: -log of the sum over all monotonic alignments
-// (torchaudio.functional.rnnt_loss, reduction "none"; online_rnnt_model.py:241-255).  joint.enc_ffn over the B*T frames, the
-// predictor over [blank, y_1 .. y_Umax] from the zero state (add_blank + predictor(ys_in_pad), model/component/transducer.py:8-19)
-// as Umax + 1 steps of rnnt_predictor_step's two GEMMs over B rows, joint.pred_ffn, the picked lattice (two values per cell
-// instead of the vocabulary), transducer_alpha, one copy of B doubles, one synchronisation.
-int rnnt_transducer_nll(rnnt_ctx* ctx, const float* enc_dev, const int32_t* enc_lens_host, const int32_t* targets_host, const int32_t* target_lens_host,
-                        int32_t B, int32_t T, int32_t Umax, double* nll_host, float* pick_dev, void* stream) {
+// The picked lattice of B (frames, transcript) rows, shared by rnnt_transducer_nll and rnnt_transducer_align: joint.enc_ffn over the
+// B*T frames, the predictor over [blank, y_1 .. y_Umax] from the zero state (add_blank + predictor(ys_in_pad),
+// model/component/transducer.py:8-19) as Umax + 1 steps of rnnt_predictor_step's two GEMMs over B rows, joint.pred_ffn, then the
+// pick kernel or its fallback.  Uploads the int work buffer from `host`, which the caller keeps until it has synchronised; *pick_out is pick_dev, or the internal lattice when that is null.
+static int score_pick(rnnt_ctx* ctx, const char* what, const float* enc_dev, const int32_t* enc_lens_host, const int32_t* targets_host,
+                      const int32_t* target_lens_host, int32_t B, int32_t T, int32_t Umax, float* pick_dev, void* stream, std::vector<int>& host,
+                      float** pick_out, int** lens_out) {
     int rc;
-    if ((rc = score_check(ctx, "rnnt_transducer_nll", enc_dev, enc_lens_host, targets_host, target_lens_host, B, T, Umax, nll_host))) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int V = ctx->cfg.vocab_size, U1 = Umax + 1, ts = Umax > 0 ? Umax : 1;
     const long long Mrows = (long long)B * T * U1;
     const size_t needf = (size_t)B * T * D + (size_t)B * U1 * D;   // rnnt_joint's own check: e and p live in the context scratch
     if (needf > ctx->scratch_floats || Mrows >= 0x7fffffffLL - JR_ROWS)
-        return fail(ctx, RNNT_ERR_SHAPE, "rnnt_transducer_nll: lattice B=%d T=%d U=%d exceeds the context scratch", B, T, U1);
+        return fail(ctx, RNNT_ERR_SHAPE, "%s: lattice B=%d T=%d U=%d exceeds the context scratch", what, B, T, U1);
     const bool rows_kernel = ctx->numerics != RNNT_NUM_F32 && ctx->joint_wfrag && V <= JR_NT * 16 && V % 4 == 0;
     // work floats: pred [B][U1][256] | h, c ping-pong [2][2][B][256] | pick [B][T][U1][2] when the caller keeps none
     const size_t n_pred = (size_t)B * U1 * D, n_state = (size_t)B * D;
     if ((rc = grow(ctx, &ctx->sc_f, &ctx->sc_f_cap, n_pred + 4 * n_state + (pick_dev ? 0 : (size_t)Mrows * 2)))) return rc;
     if (!rows_kernel && (rc = grow(ctx, &ctx->sc_lat, &ctx->sc_lat_cap, (size_t)Mrows * V))) return rc;
-    std::vector<int> host;
     int *tg, *lens, *tok;
     if ((rc = score_upload(ctx, s, enc_lens_host, targets_host, target_lens_host, B, Umax, true, host, &tg, &lens, &tok))) return rc;
     float* pred = ctx->sc_f;
@@ -120,9 +120,28 @@ int rnnt_transducer_nll(rnnt_ctx* ctx, const float* enc_dev, const int32_t* enc_
                            ctx->cfg.blank_id);
         LAUNCHCHK("pick_gather");
     }
+    *pick_out = pick;
+    *lens_out = lens;
+    return RNNT_OK;
+}
+
+// Transducer negative log-likelihood of B (frames, transcript) rows: -log of the sum over all monotonic alignments
+// (torchaudio.functional.rnnt_loss, reduction "none"; online_rnnt_model.py:241-255): the picked lattice (two values per cell
+// instead of the vocabulary), transducer_alpha, one copy of B doubles, one synchronisation.
+int rnnt_transducer_nll(rnnt_ctx* ctx, const float* enc_dev, const int32_t* enc_lens_host, const int32_t* targets_host, const int32_t* target_lens_host,
+                        int32_t B, int32_t T, int32_t Umax, double* nll_host, float* pick_dev, void* stream) {
+    int rc;
+    if ((rc = score_check(ctx, "rnnt_transducer_nll", enc_dev, enc_lens_host, targets_host, target_lens_host, B, T, Umax, nll_host))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int> host;
+    float* pick;
+    int* lens;
+    if ((rc = score_pick(ctx, "rnnt_transducer_nll", enc_dev, enc_lens_host, targets_host, target_lens_host, B, T, Umax, pick_dev, stream, host, &pick,
+                         &lens)))
+        return rc;
     {
         ProfScope prof(ctx, s, TAG_SCORE_ALPHA);
-        hipLaunchKernelGGL(transducer_alpha, dim3(B), dim3(256), 0, s, pick, lens, B, T, U1, ctx->sc_nll);
+        hipLaunchKernelGGL(transducer_alpha, dim3(B), dim3(256), 0, s, pick, lens, B, T, Umax + 1, ctx->sc_nll);
         LAUNCHCHK("transducer_alpha");
     }
     HIPCHK(hipMemcpyAsync(nll_host, ctx->sc_nll, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -146,9 +165,127 @@ int rnnt_ctc_nll(rnnt_ctx* ctx, const float* enc_dev, const int32_t* enc_lens_ho
     int *tg, *lens, *tok;
     if ((rc = score_upload(ctx, s, enc_lens_host, targets_host, target_lens_host, B, Umax, false, host, &tg, &lens, &tok))) return rc;
     if ((rc = rnnt_ctc_logprobs(ctx, enc_dev, B * T, ctx->sc_lat, stream))) return rc;
-    hipLaunchKernelGGL(ctc_alpha, dim3(B), dim3(512), 0, s, ctx->sc_lat, tg, lens, B, T, V, Umax > 0 ? Umax : 1, ctx->cfg.blank_id, ctx->sc_nll);
-    LAUNCHCHK("ctc_alpha");
+    {
+        ProfScope prof(ctx, s, TAG_SCORE_ALPHA);
+        hipLaunchKernelGGL(ctc_alpha, dim3(B), dim3(512), 0, s, ctx->sc_lat, tg, lens, B, T, V, Umax > 0 ? Umax : 1, ctx->cfg.blank_id, ctx->sc_nll);
+        LAUNCHCHK("ctc_alpha");
+    }
     HIPCHK(hipMemcpyAsync(nll_host, ctx->sc_nll, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return RNNT_OK;
+}
+
+// ---- forced alignment ------------------------------------------------------------------------------------------------------------------
+// Device outputs of an alignment call, downloaded in ONE copy: best [B] f64 | nll [B] f64 | path [B][n] int32.
+static size_t align_out_doubles(int B, size_t n) { return 2 * (size_t)B + ((size_t)B * n + 1) / 2; }
+
+static int align_check(rnnt_ctx* ctx, const char* what, const float* dev, const int32_t* enc_lens, const int32_t* targets, const int32_t* target_lens,
+                       int32_t B, int32_t T, int32_t Umax, double* best_host, int32_t* path_host, bool labels) {
+    if (ctx && !path_host) return fail(ctx, RNNT_ERR_ARG, "%s: null argument", what);
+    return score_check(ctx, what, dev, enc_lens, targets, target_lens, B, T, Umax, best_host, labels);
+}
+
+// back-pointer words and outputs of one call (n path entries per row); grow-only
+static int align_buffers(rnnt_ctx* ctx, size_t bp_words, int B, size_t n) {
+    int rc;
+    if ((rc = grow(ctx, &ctx->al_bp, &ctx->al_bp_cap, bp_words))) return rc;
+    return grow(ctx, &ctx->al_out, &ctx->al_out_cap, align_out_doubles(B, n));
+}
+
+static int align_download(rnnt_ctx* ctx, hipStream_t s, int B, size_t n, double* best_host, double* nll_host, int32_t* path_host) {
+    std::vector<double> host(align_out_doubles(B, n));
+    HIPCHK(hipMemcpyAsync(host.data(), ctx->al_out, host.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    memcpy(best_host, host.data(), (size_t)B * sizeof(double));
+    if (nll_host) memcpy(nll_host, host.data() + B, (size_t)B * sizeof(double));
+    memcpy(path_host, host.data() + 2 * (size_t)B, (size_t)B * n * sizeof(int32_t));
+    return RNNT_OK;
+}
+
+static int transducer_viterbi_run(rnnt_ctx* ctx, hipStream_t s, const float* pick, const int* lens, int B, int T, int Umax, double* best_host,
+                                  double* nll_host, int32_t* emit_host) {
+    const int ts = Umax > 0 ? Umax : 1;
+    {
+        ProfScope prof(ctx, s, TAG_SCORE_VITERBI);
+        hipLaunchKernelGGL(transducer_viterbi, dim3(B), dim3(256), 0, s, pick, lens, B, T, Umax + 1, ts, ctx->al_bp, ctx->al_out,
+                           reinterpret_cast<int*>(ctx->al_out + 2 * (size_t)B));
+        LAUNCHCHK("transducer_viterbi");
+    }
+    return align_download(ctx, s, B, ts, best_host, nll_host, emit_host);
+}
+
+// The best alignment over a caller's picked lattice: only lengths go up, transducer_viterbi, one download.
+int rnnt_transducer_align_pick(rnnt_ctx* ctx, const float* pick_dev, const int32_t* enc_lens_host, const int32_t* target_lens_host, int32_t B, int32_t T,
+                               int32_t Umax, double* best_host, int32_t* emit_host, void* stream) {
+    int rc;
+    if ((rc = align_check(ctx, "rnnt_transducer_align_pick", pick_dev, enc_lens_host, nullptr, target_lens_host, B, T, Umax, best_host, emit_host, false)))
+        return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = align_buffers(ctx, (size_t)B * (Umax + 1) * ((T + 31) / 32), B, Umax > 0 ? Umax : 1))) return rc;
+    std::vector<int> host;
+    int *tg, *lens, *tok;
+    if ((rc = score_upload(ctx, s, enc_lens_host, nullptr, target_lens_host, B, Umax, false, host, &tg, &lens, &tok))) return rc;
+    return transducer_viterbi_run(ctx, s, pick_dev, lens, B, T, Umax, best_host, nullptr, emit_host);
+}
+
+// rnnt_transducer_nll's pipeline with transducer_viterbi behind the picked lattice; with nll_host, transducer_alpha over the same
+// lattice first, so one call gives the total likelihood and the best path.
+int rnnt_transducer_align(rnnt_ctx* ctx, const float* enc_dev, const int32_t* enc_lens_host, const int32_t* targets_host, const int32_t* target_lens_host,
+                          int32_t B, int32_t T, int32_t Umax, double* best_host, int32_t* emit_host, double* nll_host, float* pick_dev, void* stream) {
+    int rc;
+    if ((rc = align_check(ctx, "rnnt_transducer_align", enc_dev, enc_lens_host, targets_host, target_lens_host, B, T, Umax, best_host, emit_host, true)))
+        return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = align_buffers(ctx, (size_t)B * (Umax + 1) * ((T + 31) / 32), B, Umax > 0 ? Umax : 1))) return rc;
+    std::vector<int> host;
+    float* pick;
+    int* lens;
+    if ((rc = score_pick(ctx, "rnnt_transducer_align", enc_dev, enc_lens_host, targets_host, target_lens_host, B, T, Umax, pick_dev, stream, host, &pick,
+                         &lens)))
+        return rc;
+    if (nll_host) {
+        ProfScope prof(ctx, s, TAG_SCORE_ALPHA);
+        hipLaunchKernelGGL(transducer_alpha, dim3(B), dim3(256), 0, s, pick, lens, B, T, Umax + 1, ctx->al_out + B);
+        LAUNCHCHK("transducer_alpha");
+    }
+    return transducer_viterbi_run(ctx, s, pick, lens, B, T, Umax, best_host, nll_host, emit_host);
+}
+
+static int ctc_viterbi_run(rnnt_ctx* ctx, hipStream_t s, const float* lp, const int32_t* enc_lens_host, const int32_t* targets_host,
+                           const int32_t* target_lens_host, int B, int T, int Umax, double* best_host, int32_t* align_host) {
+    int rc;
+    const int ts = Umax > 0 ? Umax : 1;
+    if ((rc = align_buffers(ctx, (size_t)B * (2 * ts + 1) * ((T + 15) / 16), B, T))) return rc;
+    std::vector<int> host;
+    int *tg, *lens, *tok;
+    if ((rc = score_upload(ctx, s, enc_lens_host, targets_host, target_lens_host, B, Umax, false, host, &tg, &lens, &tok))) return rc;
+    {
+        ProfScope prof(ctx, s, TAG_SCORE_VITERBI);
+        hipLaunchKernelGGL(ctc_viterbi, dim3(B), dim3(512), 0, s, lp, tg, lens, B, T, ctx->cfg.vocab_size, ts, ctx->cfg.blank_id, ctx->al_bp,
+                           ctx->al_out, reinterpret_cast<int*>(ctx->al_out + 2 * (size_t)B));
+        LAUNCHCHK("ctc_viterbi");
+    }
+    return align_download(ctx, s, B, T, best_host, nullptr, align_host);
+}
+
+// The best CTC path over a caller's log-probabilities [B][T][vocab]: ctc_viterbi alone.  Needs no CTC head.
+int rnnt_ctc_align_logprobs(rnnt_ctx* ctx, const float* lp_dev, const int32_t* enc_lens_host, const int32_t* targets_host, const int32_t* target_lens_host,
+                            int32_t B, int32_t T, int32_t Umax, double* best_host, int32_t* align_host, void* stream) {
+    int rc;
+    if ((rc = align_check(ctx, "rnnt_ctc_align_logprobs", lp_dev, enc_lens_host, targets_host, target_lens_host, B, T, Umax, best_host, align_host, true)))
+        return rc;
+    return ctc_viterbi_run(ctx, (hipStream_t)stream, lp_dev, enc_lens_host, targets_host, target_lens_host, B, T, Umax, best_host, align_host);
+}
+
+// rnnt_ctc_logprobs over the B*T frames, then ctc_viterbi: the per-frame alignment torchaudio's forced_align returns.
+int rnnt_ctc_align(rnnt_ctx* ctx, const float* enc_dev, const int32_t* enc_lens_host, const int32_t* targets_host, const int32_t* target_lens_host,
+                   int32_t B, int32_t T, int32_t Umax, double* best_host, int32_t* align_host, void* stream) {
+    int rc;
+    if ((rc = align_check(ctx, "rnnt_ctc_align", enc_dev, enc_lens_host, targets_host, target_lens_host, B, T, Umax, best_host, align_host, true)))
+        return rc;
+    if (!ctx->wctc) return fail(ctx, RNNT_ERR_STATE, "rnnt_ctc_align: ctc_head.ctc_lo.* not loaded");
+    if ((long long)B * T >= 0x7fffffffLL) return fail(ctx, RNNT_ERR_SHAPE, "rnnt_ctc_align: B=%d T=%d frames in one call", B, T);
+    if ((rc = grow(ctx, &ctx->sc_lat, &ctx->sc_lat_cap, (size_t)B * T * ctx->cfg.vocab_size))) return rc;
+    if ((rc = rnnt_ctc_logprobs(ctx, enc_dev, B * T, ctx->sc_lat, stream))) return rc;
+    return ctc_viterbi_run(ctx, (hipStream_t)stream, ctx->sc_lat, enc_lens_host, targets_host, target_lens_host, B, T, Umax, best_host, align_host);
 }

@@ -229,6 +229,10 @@ struct rnnt_ctx {
     int* sc_i = nullptr;
     double* sc_nll = nullptr;
     size_t sc_f_cap = 0, sc_lat_cap = 0, sc_i_cap = 0, sc_nll_cap = 0;
+    // forced alignment (api_score.hip.inc): grow-only back-pointer words and the outputs of one call (best | nll | path)
+    unsigned* al_bp = nullptr;
+    double* al_out = nullptr;
+    size_t al_bp_cap = 0, al_out_cap = 0;
     hipStream_t cap_stream = nullptr;          // stream-capture scratch stream
     struct DecGraph { int n_streams, k; hipGraphExec_t exec; };
     std::vector<DecGraph> dec_graphs;          // K greedy steps captured once per (n_streams, K)

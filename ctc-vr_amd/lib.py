@@ -56,6 +56,10 @@ SIGNATURES = {
     "rnnt_ctc_logprobs": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp]),
     "rnnt_transducer_nll": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "rnnt_ctc_nll": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "rnnt_transducer_align": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rnnt_transducer_align_pick": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "rnnt_ctc_align": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "rnnt_ctc_align_logprobs": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "rnnt_fbank": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32p, c_vp]),
     "rnnt_greedy_search_full": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "rnnt_get_att_cache": (c_i32, [c_vp, c_i32, c_vp, c_i32p, c_vp]),
@@ -437,6 +441,41 @@ class RnntEngine:
         nll = np.zeros(B, np.float64)
         self._chk(self.lib.rnnt_ctc_nll(self.ctx, enc_ptr, _np_ptr(el), _np_ptr(tg), _np_ptr(tl), B, T, umax, _np_ptr(nll), stream), "rnnt_ctc_nll")
         return nll
+
+    def transducer_align(self, enc_ptr, enc_lens, targets, target_lens, B, T, want_nll=False, pick_ptr=None, stream=None):
+        """rnnt_transducer_align: the best alignment of targets [B, Umax] over encoder frames enc [B, T, 256] on the device ->
+        (best float64 [B], emit int32 [B, max(Umax, 1)]: the frame of each label, -1 beyond a row's length), plus nll float64 [B]
+        (what transducer_nll returns) when want_nll; pick_ptr as in transducer_nll."""
+        el, tg, tl, umax = self._score_args(enc_lens, targets, target_lens, B)
+        best, emit = np.zeros(B, np.float64), np.zeros((B, max(umax, 1)), np.int32)
+        nll = np.zeros(B, np.float64) if want_nll else None
+        self._chk(self.lib.rnnt_transducer_align(self.ctx, enc_ptr, _np_ptr(el), _np_ptr(tg), _np_ptr(tl), B, T, umax, _np_ptr(best), _np_ptr(emit),
+                                                 _np_ptr(nll) if want_nll else None, pick_ptr, stream), "rnnt_transducer_align")
+        return (best, emit, nll) if want_nll else (best, emit)
+
+    def transducer_align_pick(self, pick_ptr, enc_lens, target_lens, B, T, umax, stream=None):
+        """rnnt_transducer_align_pick: the same over a picked lattice [B, T, umax + 1, 2] already on the device -> (best, emit)."""
+        el, tl = np.ascontiguousarray(enc_lens, np.int32), np.ascontiguousarray(target_lens, np.int32)
+        assert el.size == B and tl.size == B
+        best, emit = np.zeros(B, np.float64), np.zeros((B, max(umax, 1)), np.int32)
+        self._chk(self.lib.rnnt_transducer_align_pick(self.ctx, pick_ptr, _np_ptr(el), _np_ptr(tl), B, T, umax, _np_ptr(best), _np_ptr(emit), stream),
+                  "rnnt_transducer_align_pick")
+        return best, emit
+
+    def ctc_align(self, enc_ptr, enc_lens, targets, target_lens, B, T, stream=None):
+        """rnnt_ctc_align: CTC forced alignment -> (best float64 [B], -inf where the frames cannot hold the transcript; align int32
+        [B, T]: the label (blank included) of each frame, -1 beyond a row's frames and on an infeasible row)."""
+        return self._ctc_align(self.lib.rnnt_ctc_align, "rnnt_ctc_align", enc_ptr, enc_lens, targets, target_lens, B, T, stream)
+
+    def ctc_align_logprobs(self, lp_ptr, enc_lens, targets, target_lens, B, T, stream=None):
+        """rnnt_ctc_align_logprobs: the same over log-probabilities [B, T, vocab] already on the device."""
+        return self._ctc_align(self.lib.rnnt_ctc_align_logprobs, "rnnt_ctc_align_logprobs", lp_ptr, enc_lens, targets, target_lens, B, T, stream)
+
+    def _ctc_align(self, fn, name, dev_ptr, enc_lens, targets, target_lens, B, T, stream):
+        el, tg, tl, umax = self._score_args(enc_lens, targets, target_lens, B)
+        best, align = np.zeros(B, np.float64), np.zeros((B, T), np.int32)
+        self._chk(fn(self.ctx, dev_ptr, _np_ptr(el), _np_ptr(tg), _np_ptr(tl), B, T, umax, _np_ptr(best), _np_ptr(align), stream), name)
+        return best, align
 
     def greedy_search_full(self, fbank_ptr, lens, B, T, n_steps=64, stream=None):
         """Offline greedy search over the full-context encoder (model/component/transducer.py:22-70) -> list of token lists."""

@@ -100,6 +100,33 @@ def compose_losses(nll_rnnt, nll_ctc, text_lens, ctc_weight):
     return total, loss_dict
 
 
+def peaks_from_ctc_alignment(align, blank_id=0):
+    """The peak frame of each token of a per-frame CTC alignment (blank included), the semantics of WeNet's gen_ctc_peak_time
+    (wenet/utils/ctc_utils.py): the first frame of every run of equal non-blank labels."""
+    peaks, t, n = [], 0, len(align)
+    while t < n:
+        if align[t] != blank_id:
+            peaks.append(t)
+        first = t
+        while t < n and align[t] == align[first]:
+            t += 1
+    return peaks
+
+
+def timestamps_from_peaks(peaks, max_duration, frame_rate=0.04, max_token_duration=1.0):
+    """[(start_s, end_s)] per token from its peak frame, the semantics of WeNet's gen_timestamps_from_peak: a token reaches half
+    way to its neighbours' peaks but at most max_token_duration / 2 from its own, the first one not before 0 and the last one
+    not beyond max_duration.  Same operations in the same order, so the floats are equal."""
+    half = max_token_duration / 2
+    last = len(peaks) - 1
+    times = []
+    for i, pk in enumerate(peaks):
+        start = max(0, pk * frame_rate - half) if i == 0 else max((peaks[i - 1] + pk) / 2 * frame_rate, pk * frame_rate - half)
+        end = min(max_duration, pk * frame_rate + half) if i == last else min((pk + peaks[i + 1]) / 2 * frame_rate, pk * frame_rate + half)
+        times.append((start, end))
+    return times
+
+
 class _EncoderView:
     """Attribute surface the reference's callers read: encoder.static_chunk_size and
     encoder.embed.subsampling_rate (model/online_rnnt_model.py:283-287)."""
@@ -384,6 +411,32 @@ class OnlineRNNTModel:
         enc, enc_lens, tg, tl = self._encode_for_scoring(audios, audio_lens, texts, text_lens)
         nll = self._engine.ctc_nll(enc.data_ptr(), enc_lens, tg, tl, enc.size(0), enc.size(1), _stream_ptr())
         return torch.from_numpy(nll)
+
+    FRAME_SECONDS = 0.04     # one encoder frame: 4x subsampling of 10 ms features, WeNet's frame_rate default
+
+    def align(self, audios: torch.Tensor, audio_lens: torch.Tensor, texts: torch.Tensor, text_lens: torch.Tensor, method: str = "rnnt"):
+        """Forced alignment of given transcripts over the deterministic full-context encoder (see transducer_nll): per utterance
+        {"tokens", "frames", "times": [(start_s, end_s)], "log_prob"}.  method "rnnt": the best transducer path
+        (rnnt_transducer_align), frames = the frame at which each token is emitted; "ctc": the best CTC path (rnnt_ctc_align, what
+        WeNet's force_align asks of torchaudio), frames = its peaks (peaks_from_ctc_alignment).  times = timestamps_from_peaks
+        with max_duration = the utterance's encoder frames * 0.04 s; log_prob is the best path's.  A transcript the CTC frames
+        cannot hold has log_prob -inf and no frames.  Invalidates the streaming state."""
+        assert method in ("rnnt", "ctc"), method
+        enc, enc_lens, tg, tl = self._encode_for_scoring(audios, audio_lens, texts, text_lens)
+        B, tq, s = enc.size(0), enc.size(1), _stream_ptr()
+        if method == "rnnt":
+            best, emit = self._engine.transducer_align(enc.data_ptr(), enc_lens, tg, tl, B, tq, stream=s)
+        else:
+            best, ali = self._engine.ctc_align(enc.data_ptr(), enc_lens, tg, tl, B, tq, s)
+        out = []
+        for b in range(B):
+            if method == "rnnt":
+                frames = emit[b, :tl[b]].tolist()
+            else:
+                frames = peaks_from_ctc_alignment(ali[b, :enc_lens[b]].tolist(), self.blank_id) if np.isfinite(best[b]) else []
+            times = timestamps_from_peaks(frames, int(enc_lens[b]) * self.FRAME_SECONDS, self.FRAME_SECONDS)
+            out.append({"tokens": tg[b, :tl[b]].tolist(), "frames": frames, "times": times, "log_prob": float(best[b])})
+        return out
 
     def _has_ctc_head(self) -> bool:
         return bool(getattr(self, "_ctc_loaded", False))

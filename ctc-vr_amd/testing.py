@@ -195,3 +195,147 @@ def transducer_nll_bruteforce(pick, T_b, U_b):
         logs.append(lp + p[T_b - 1, U_b, 0])
     mx = max(logs)
     return -(mx + math.log(math.fsum(math.exp(v - mx) for v in logs)))
+
+
+# ---- forced alignment: float64 restatements of the two Viterbi recursions (tests) ----------------------------------------------
+def _transducer_forward(p, T_b, U_b):
+    """v[t, u] and the move into each cell (True: the label move from (t, u-1)); the blank move wins ties."""
+    v = np.full((T_b, U_b + 1), -math.inf)
+    label = np.zeros((T_b, U_b + 1), bool)
+    for t in range(T_b):
+        for u in range(U_b + 1):
+            if t == 0 and u == 0:
+                v[t, u] = 0.0
+                continue
+            below = v[t - 1, u] + p[t - 1, u, 0] if t > 0 else -math.inf
+            left = v[t, u - 1] + p[t, u - 1, 1] if u > 0 else -math.inf
+            label[t, u] = t == 0 or (u > 0 and not below >= left)
+            v[t, u] = left if label[t, u] else below
+    return v, label
+
+
+def transducer_align_ref(pick, T_b, U_b):
+    """The best monotonic alignment of one utterance over its picked lattice (layout and valid cells as transducer_nll_ref):
+    v[0,0] = 0; v[t,u] = max(v[t-1,u] + pick[t-1,u,0], v[t,u-1] + pick[t,u-1,1]), the blank move (from (t-1,u)) taken when its
+    value is >= the label move's; best = v[T_b-1,U_b] + pick[T_b-1,U_b,0].  Returns (best, emit, margin): emit [U_b] int32, the
+    frame at which each label is emitted; margin = best minus the best score of any complete path through a cell off the best
+    path (forward plus backward Viterbi), inf when every cell lies on it."""
+    p = np.asarray(pick, np.float64)
+    v, label = _transducer_forward(p, T_b, U_b)
+    best = v[T_b - 1, U_b] + p[T_b - 1, U_b, 0]
+    emit = np.full(U_b, -1, np.int32)
+    on_path = np.zeros((T_b, U_b + 1), bool)
+    t, u = T_b - 1, U_b
+    on_path[t, u] = True
+    while t > 0 or u > 0:
+        if label[t, u]:
+            u -= 1
+            emit[u] = t
+        else:
+            t -= 1
+        on_path[t, u] = True
+    w = np.full((T_b, U_b + 1), -math.inf)          # best score from cell (t, u) to the end, final blank included
+    for t in range(T_b - 1, -1, -1):
+        for u in range(U_b, -1, -1):
+            if t == T_b - 1 and u == U_b:
+                w[t, u] = p[t, u, 0]
+                continue
+            up = p[t, u, 0] + w[t + 1, u] if t + 1 < T_b else -math.inf
+            right = p[t, u, 1] + w[t, u + 1] if u < U_b else -math.inf
+            w[t, u] = max(up, right)
+    through = (v + w)[~on_path]
+    margin = best - through.max() if through.size else math.inf
+    return best, emit, margin
+
+
+def transducer_align_bruteforce(pick, T_b, U_b):
+    """Every alignment (an order of T_b - 1 blanks and U_b labels, then the final blank), each summed in path order from the
+    start.  Returns [(score, emit tuple)] sorted best first; among equal scores the path the tie rule names comes first: walking
+    back from the end, the blank move is preferred where two paths part, which leaves the label before that cell at an earlier
+    frame -- the smaller emission frames, compared from the last label backwards."""
+    from itertools import combinations
+    p = np.asarray(pick, np.float64)
+    n = T_b - 1 + U_b
+    out = []
+    for labels_at in combinations(range(n), U_b):
+        at, t, u, lp, emit = set(labels_at), 0, 0, 0.0, []
+        for k in range(n):
+            if k in at:
+                lp = lp + p[t, u, 1]
+                emit.append(t)
+                u += 1
+            else:
+                lp = lp + p[t, u, 0]
+                t += 1
+        out.append((lp + p[T_b - 1, U_b, 0], tuple(emit)))
+    out.sort(key=lambda se: (-se[0], tuple(reversed(se[1]))))
+    return out
+
+
+def _ctc_ext(targets, blank):
+    ext = [blank]
+    for y in targets:
+        ext += [int(y), blank]
+    return ext
+
+
+def ctc_align_ref(lp, targets, T_b, blank):
+    """The best CTC path of one utterance: lp [T, V] log-probabilities, extended states (blank, y_1, blank, .., y_L, blank);
+    v_t[s] = max(v_{t-1}[s], v_{t-1}[s-1], v_{t-1}[s-2] if s is a label that differs from the one before) + lp[t, ext s]; the
+    largest wins and among equals staying beats s-1 beats s-2; the path ends in S-1 if v[S-1] >= v[S-2] (or S == 1), else in
+    S-2.  Returns (best, align [T_b] int32: the label of each frame's state, blank included); (-inf, all -1) for a transcript
+    its frames cannot hold."""
+    p = np.asarray(lp, np.float64)
+    ext = _ctc_ext(targets, blank)
+    S = len(ext)
+    v = np.full(S, -math.inf)
+    for s in range(min(S, 2)):
+        v[s] = p[0, ext[s]]
+    step = np.zeros((T_b, S), np.int64)
+    for t in range(1, T_b):
+        nv = np.full(S, -math.inf)
+        for s in range(S):
+            m, k = v[s], 0
+            if s >= 1 and v[s - 1] > m:
+                m, k = v[s - 1], 1
+            if s >= 3 and (s & 1) and ext[s - 2] != ext[s] and v[s - 2] > m:
+                m, k = v[s - 2], 2
+            nv[s] = m + p[t, ext[s]]
+            step[t, s] = k
+        v = nv
+    s = S - 1 if S == 1 or v[S - 1] >= v[S - 2] else S - 2
+    best = v[s]
+    align = np.full(T_b, -1, np.int32)
+    if best == -math.inf:
+        return best, align
+    for t in range(T_b - 1, -1, -1):
+        align[t] = ext[s]
+        s -= step[t, s]
+    return float(best), align
+
+
+def ctc_align_bruteforce(lp, targets, T_b, blank):
+    """Every state sequence of T_b frames that starts in state 0 or 1, moves by 0, 1 or (between different labels) 2 states and
+    ends in S-1 or S-2, each summed in frame order.  Returns [(score, state tuple)] sorted best first; among equal scores the one
+    the tie rule names first: the last state S-1 before S-2, then, walking back, the higher earlier state (the smaller step)."""
+    p = np.asarray(lp, np.float64)
+    ext = _ctc_ext(targets, blank)
+    S = len(ext)
+    out = []
+
+    def walk(t, s, score, path):
+        if t == T_b - 1:
+            if s >= S - 2:
+                out.append((score, tuple(path)))
+            return
+        for k in (0, 1, 2):
+            n = s + k
+            if n >= S or (k == 2 and not ((n & 1) and ext[n] != ext[s])):
+                continue
+            path.append(n)
+            walk(t + 1, n, score + p[t + 1, ext[n]], path)
+            path.pop()
+    for s0 in range(min(S, 2)):
+        walk(0, s0, p[0, ext[s0]], [s0])
+    out.sort(key=lambda sp: (-sp[0], tuple(-s for s in reversed(sp[1]))))
+    return out

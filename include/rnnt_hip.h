@@ -324,6 +324,42 @@ int rnnt_transducer_nll(rnnt_ctx* ctx, const float* enc_dev, const int32_t* enc_
 int rnnt_ctc_nll(rnnt_ctx* ctx, const float* enc_dev, const int32_t* enc_lens_host, const int32_t* targets_host,
                  const int32_t* target_lens_host, int32_t B, int32_t T, int32_t Umax, double* nll_host, void* stream);
 
+/* -- forced alignment: WHERE in the frames each token of a given transcript lies (the reference's WeNet layer: force_align,
+ * gen_ctc_peak_time, gen_timestamps_from_peak, DecodeResult.times; wenet/utils/ctc_utils.py) ------------------------------------ */
+/* The best monotonic alignment of each row's transcript: the max-plus (Viterbi) twin of rnnt_transducer_nll's recursion in f64,
+ * over the same picked lattice -- v[0,0] = 0, v[t,u] = max(v[t-1,u] + pick[t-1,u][0], v[t,u-1] + pick[t,u-1][1]),
+ * best = v[T_b-1,U_b] + pick[T_b-1,U_b][0] -- with one-bit back-pointers and the back-trace in the same launch.  Where both moves
+ * reach a cell with equal values the blank move (from (t-1,u)) wins; additions and comparisons only, so the result is bitwise its
+ * float64 restatement (ctc_vr_amd.testing.transducer_align_ref), ties included.
+ *   best_host [B] double: log-probability of the best path; emit_host [B, max(Umax, 1)] int32: emit[b][u] = the frame at which
+ *   label u is emitted (non-decreasing in u), -1 for u >= U_b; nll_host: NULL, or [B] double that receives what
+ *   rnnt_transducer_nll returns for the same arguments (transducer_alpha over the same lattice); pick_dev as there.
+ * Other arguments, ranges and refusals as rnnt_transducer_nll; best_host and emit_host must not be NULL.  One upload, one
+ * download, one synchronisation; streaming, pool and beam state are left alone. */
+int rnnt_transducer_align(rnnt_ctx* ctx, const float* enc_dev, const int32_t* enc_lens_host, const int32_t* targets_host,
+                          const int32_t* target_lens_host, int32_t B, int32_t T, int32_t Umax, double* best_host,
+                          int32_t* emit_host, double* nll_host, float* pick_dev, void* stream);
+/* The same recursion over a lattice the caller already holds: pick_dev [B, T, Umax + 1, 2] device floats in
+ * rnnt_transducer_nll's layout; only cells t < T_b, u <= U_b (label slot u < U_b) are read.  No labels, hence no label checks;
+ * the other refusals as above (without the scratch limit: nothing is projected). */
+int rnnt_transducer_align_pick(rnnt_ctx* ctx, const float* pick_dev, const int32_t* enc_lens_host, const int32_t* target_lens_host,
+                               int32_t B, int32_t T, int32_t Umax, double* best_host, int32_t* emit_host, void* stream);
+/* CTC forced alignment: rnnt_ctc_logprobs over the B*T frames, then the Viterbi twin of rnnt_ctc_nll's recursion in f64 over the
+ * 2 L_b + 1 extended states: v_t[s] = max(v_{t-1}[s], v_{t-1}[s-1], v_{t-1}[s-2] if the labels differ) + lp[t][ext s]; among
+ * equal values staying beats s-1, which beats s-2; the path ends in the last state if v[S-1] >= v[S-2], else in the last label.
+ *   best_host [B] double; align_host [B, T] int32: the label of the state occupied at frame t, blank_id included (the per-frame
+ *   form torchaudio's forced_align returns), -1 for t >= T_b.
+ * A transcript its frames cannot hold gives best = -inf and a row of -1; it is no error (the mirror of rnnt_ctc_nll's +inf).
+ * Arguments, ranges and refusals as rnnt_ctc_nll. */
+int rnnt_ctc_align(rnnt_ctx* ctx, const float* enc_dev, const int32_t* enc_lens_host, const int32_t* targets_host,
+                   const int32_t* target_lens_host, int32_t B, int32_t T, int32_t Umax, double* best_host, int32_t* align_host,
+                   void* stream);
+/* The same over log-probabilities the caller already holds: lp_dev [B, T, vocab] device floats (they need not normalise: the
+ * recursion only adds).  Needs no CTC head; the other refusals as rnnt_ctc_align. */
+int rnnt_ctc_align_logprobs(rnnt_ctx* ctx, const float* lp_dev, const int32_t* enc_lens_host, const int32_t* targets_host,
+                            const int32_t* target_lens_host, int32_t B, int32_t T, int32_t Umax, double* best_host,
+                            int32_t* align_host, void* stream);
+
 /* Offline greedy search: basic_greedy_search (model/component/transducer.py:22-70) behind
  * OnlineRNNTModel.forward(audios, audio_lens) of a non-streaming model (model/online_rnnt_model.py:234-235,268):
  * full-context encoder + per-utterance greedy loop over its valid frames, <= n_steps symbols per frame (reference
@@ -356,7 +392,7 @@ const float* rnnt_enc_frames_dev(rnnt_ctx* ctx, int32_t* frames_out, int32_t* st
  * tag selects ONE launch site: 1 conv1, 2 conv2 (implicit GEMM), 3 embed linear, 4 FFN w_1, 5 FFN w_2, 6 QKV,
  * 7 attention, 8 attention out-proj, 9 pointwise_conv1+GLU, 10 depthwise conv, 11 pointwise_conv2, 13 joint enc
  * projection, 20 LSTM cell, 21 predictor projection, 22 joint pred_ffn+tanh, 23 joint ffn_out, 40 the picked lattice of
- * rnnt_transducer_nll, 41 its alpha recursion.
+ * rnnt_transducer_nll, 41 its alpha recursion (and rnnt_ctc_nll's), 42 the Viterbi launch of the rnnt_*_align calls.
  * rnnt_profile_end synchronises the recorded events and returns the summed kernel time and launch count. */
 int rnnt_profile_begin(rnnt_ctx* ctx, int32_t tag);
 int rnnt_profile_end(rnnt_ctx* ctx, double* total_ms, int64_t* n_launches);
