@@ -1,0 +1,243 @@
+// C ABI: WeNet's CTC-fused prefix beam search (wenet/transducer/search/prefix_beam_search.py:42-148) for a padded batch, the whole
+// frame loop on the device.  Included by rnnt_api.hip inside extern "C".  Kernels: rnnt_prefix.hip.h.
+
+// The merge of one frame for ONE utterance as a pure function (no context, no GPU; CPU tests), the C++ statement of
+// prefix_beam_search.py:105-145: candidates per hypothesis j, per rank t with f64((f32)score_j + top_lp[j][t]); a blank candidate
+// keeps the tokens of j and state slot 0, any other token appends and takes slot 1; sequential prefix fusion in candidate order
+// (log_add of the list [survivor, candidate] in double, the first one's tokens and state stay); stable descending sort;
+// truncation.  Hypotheses are passed flat: hyp_len[n_hyp], hyp_tokens (concatenated), hyp_score[n_hyp]; top_lp / top_tok
+// [n_hyp][k]; outputs likewise (out_tokens needs room for beam_size * (longest input + 1) ints).  Returns the number of survivors.
+int rnnt_prefix_merge_host(int32_t n_hyp, const int32_t* hyp_len, const int32_t* hyp_tokens, const double* hyp_score, const float* top_lp,
+                           const int32_t* top_tok, int32_t k, int32_t blank, int32_t beam_size, int32_t* out_len, int32_t* out_tokens,
+                           double* out_score, int32_t* out_src_row, int32_t* out_src_slot) {
+    if (n_hyp < 1 || k < 1 || beam_size < 1 || !hyp_len || !hyp_score || !top_lp || !top_tok || !out_len || !out_tokens || !out_score) return RNNT_ERR_ARG;
+    struct Cand { std::vector<int> tokens; double score; int row, slot; };
+    std::vector<Cand> fused;
+    size_t off = 0;
+    for (int j = 0; j < n_hyp; ++j) {
+        if (hyp_len[j] < 0 || (hyp_len[j] > 0 && !hyp_tokens)) return RNNT_ERR_ARG;
+        const float s32 = (float)hyp_score[j];                                      // torch.tensor([s.score])
+        for (int t = 0; t < k; ++t) {
+            const float sum = s32 + top_lp[(size_t)j * k + t];                      // :105, f32
+            const int tok = top_tok[(size_t)j * k + t];
+            Cand c{std::vector<int>(hyp_tokens + off, hyp_tokens + off + hyp_len[j]), (double)sum, j, tok == blank ? 0 : 1};
+            if (tok != blank) c.tokens.push_back(tok);
+            bool merged = false;
+            for (Cand& f : fused)
+                if (f.tokens == c.tokens) {
+                    f.score = prefix_log_add(f.score, c.score);                     // :136-138
+                    merged = true;
+                    break;
+                }
+            if (!merged) fused.push_back(std::move(c));
+        }
+        off += hyp_len[j];
+    }
+    std::stable_sort(fused.begin(), fused.end(), [](const Cand& a, const Cand& b) { return a.score > b.score; });
+    if ((int)fused.size() > beam_size) fused.resize(beam_size);
+    off = 0;
+    for (size_t a = 0; a < fused.size(); ++a) {
+        out_len[a] = (int)fused[a].tokens.size();
+        for (int t : fused[a].tokens) out_tokens[off++] = t;
+        out_score[a] = fused[a].score;
+        if (out_src_row) out_src_row[a] = fused[a].row;
+        if (out_src_slot) out_src_slot[a] = fused[a].slot;
+    }
+    return (int)fused.size();
+}
+
+namespace {
+// The call's own grow-only buffers: rows = B * beam fixed rows, token lists of lcap ints, `frames` = B * T projected frames.
+struct PrefixBuf {
+    float *encp, *ctc, *pool[2], *top_lp;
+    int *tk[2], *len[2], *nh, *lens, *top_tok, *src_row, *src_slot;
+    double* sc[2];
+    unsigned long long* hs[2];
+};
+int prefix_buffers(rnnt_ctx* ctx, size_t B, size_t rows, size_t lcap, size_t frames, bool with_ctc, int k, PrefixBuf& o) {
+    const size_t V = ctx->cfg.vocab_size;
+    int rc;
+    if ((rc = grow(ctx, &ctx->pb_f, &ctx->pb_f_cap, frames * D + (with_ctc ? frames * V : 0) + 2 * rows * 1024 + rows * k))) return rc;
+    if ((rc = grow(ctx, &ctx->pb_i, &ctx->pb_i_cap, 2 * rows * lcap + 2 * rows + 2 * B + rows * k + 2 * rows))) return rc;
+    if ((rc = grow(ctx, &ctx->pb_d, &ctx->pb_d_cap, 4 * rows))) return rc;
+    float* f = ctx->pb_f;
+    o.encp = f; f += frames * D;
+    o.ctc = with_ctc ? f : nullptr; f += with_ctc ? frames * V : 0;
+    o.pool[0] = f; o.pool[1] = f + rows * 1024; f += 2 * rows * 1024;
+    o.top_lp = f;
+    int* i = ctx->pb_i;
+    o.tk[0] = i; o.tk[1] = i + rows * lcap; i += 2 * rows * lcap;
+    o.len[0] = i; o.len[1] = i + rows; i += 2 * rows;
+    o.nh = i; o.lens = i + B; i += 2 * B;
+    o.top_tok = i; i += rows * k;
+    o.src_row = i; o.src_slot = i + rows;
+    o.sc[0] = ctx->pb_d; o.sc[1] = ctx->pb_d + rows;
+    o.hs[0] = reinterpret_cast<unsigned long long*>(ctx->pb_d + 2 * rows); o.hs[1] = o.hs[0] + rows;
+    return RNNT_OK;
+}
+
+PrefixMergeP prefix_merge_params(const PrefixBuf& u, int t, bool states, int lcap, int k, int beam, int blank, int f) {
+    PrefixMergeP m;
+    memset(&m, 0, sizeof(m));
+    if (states) { m.pool_in = u.pool[t]; m.pool_out = u.pool[t ^ 1]; }
+    m.tk_in = u.tk[t]; m.tk_out = u.tk[t ^ 1];
+    m.len_in = u.len[t]; m.len_out = u.len[t ^ 1];
+    m.sc_in = u.sc[t]; m.sc_out = u.sc[t ^ 1];
+    m.hs_in = u.hs[t]; m.hs_out = u.hs[t ^ 1];
+    m.nh = u.nh; m.lens = u.lens; m.top_lp = u.top_lp; m.top_tok = u.top_tok; m.src_row = u.src_row; m.src_slot = u.src_slot;
+    m.lcap = lcap; m.k = k; m.beam = beam; m.blank = blank; m.f = f;
+    return m;
+}
+}  // namespace
+
+// Prefix beam search of a padded batch in one call: joint.enc_ffn and the CTC log-probabilities of the B*T frames once, then per
+// frame one prefix_step launch (one workgroup per live hypothesis) and one prefix_merge launch (one workgroup per utterance) over
+// fixed rows b * beam + i with ping-pong buffers; one upload (the lengths), one download (prefix_pack's block), one
+// synchronisation.  Touches nothing but its own buffers: streaming, pool and lock-step beam state stay as they are.
+int rnnt_prefix_beam_decode(rnnt_ctx* ctx, const float* enc_dev, const int32_t* enc_lens_host, int32_t B, int32_t T, int32_t beam_size,
+                            float ctc_weight, float transducer_weight, int32_t cap_tokens, int32_t* n_hyp_host, int32_t* lens_host,
+                            int32_t* tokens_host, double* scores_host, float* h_host, float* c_host, void* stream) {
+    if (!ctx || !enc_dev || !enc_lens_host || !n_hyp_host || !lens_host || !tokens_host || !scores_host || (!h_host != !c_host))
+        return fail(ctx, RNNT_ERR_ARG, "rnnt_prefix_beam_decode: null argument");
+    if (!ctx->finalized) return fail(ctx, RNNT_ERR_STATE, "weights not finalized");
+    const int V = ctx->cfg.vocab_size, blank = ctx->cfg.blank_id;
+    if (B < 1 || T < 0) return fail(ctx, RNNT_ERR_ARG, "rnnt_prefix_beam_decode: B=%d T=%d", B, T);
+    if (V > 512) return fail(ctx, RNNT_ERR_ARG, "rnnt_prefix_beam_decode: vocab %d > 512", V);
+    if (beam_size < 1 || beam_size > PB_MAX_BEAM || beam_size > V)
+        return fail(ctx, RNNT_ERR_ARG, "rnnt_prefix_beam_decode: beam_size %d outside [1, min(%d, vocab %d)]", beam_size, PB_MAX_BEAM, V);
+    if (!(ctc_weight >= 0.f) || !(transducer_weight >= 0.f) || (ctc_weight == 0.f && transducer_weight == 0.f))
+        return fail(ctx, RNNT_ERR_ARG, "rnnt_prefix_beam_decode: weights %g / %g (negative, or both zero)", ctc_weight, transducer_weight);
+    int fmax = 0;
+    for (int b = 0; b < B; ++b) {
+        if (enc_lens_host[b] < 0 || enc_lens_host[b] > T)
+            return fail(ctx, RNNT_ERR_ARG, "rnnt_prefix_beam_decode: utterance %d has %d frames, outside [0, %d]", b, enc_lens_host[b], T);
+        fmax = std::max(fmax, enc_lens_host[b]);
+    }
+    if (cap_tokens < 1 + fmax) return fail(ctx, RNNT_ERR_ARG, "rnnt_prefix_beam_decode: cap_tokens %d < 1 + %d frames", cap_tokens, fmax);
+    const bool with_ctc = ctc_weight > 0.f;
+    if (with_ctc && !ctx->wctc) return fail(ctx, RNNT_ERR_STATE, "rnnt_prefix_beam_decode: ctc_weight > 0 and ctc_head.ctc_lo.* not loaded");
+    const size_t frames = (size_t)B * T, R = (size_t)B * beam_size, lcap = (size_t)fmax + 1;
+    if (frames * 512 >= ((size_t)1 << 31) || R * lcap >= ((size_t)1 << 31))
+        return fail(ctx, RNNT_ERR_SHAPE, "rnnt_prefix_beam_decode: B=%d T=%d beam=%d too large for one call", B, T, beam_size);
+    hipStream_t s = (hipStream_t)stream;
+    const int k = beam_size, with_states = h_host ? 1 : 0;
+    int rc;
+    PrefixBuf u;
+    if ((rc = prefix_buffers(ctx, B, R, lcap, frames, with_ctc, k, u))) return rc;
+    const size_t out_bytes = R * sizeof(double) + sizeof(int) * ((size_t)B + R + R * lcap) + (with_states ? 2 * R * D * sizeof(float) : 0);
+    const size_t out_doubles = (out_bytes + sizeof(double) - 1) / sizeof(double);
+    if ((rc = grow(ctx, &ctx->pb_out, &ctx->pb_out_cap, out_doubles))) return rc;
+    HIPCHK(hipMemcpyAsync(u.lens, enc_lens_host, B * sizeof(int), hipMemcpyHostToDevice, s));            // the upload
+    hipLaunchKernelGGL(prefix_init, dim3(B), dim3(256), 0, s, u.pool[0], u.tk[0], u.len[0], u.sc[0], u.hs[0], u.nh, beam_size, (int)lcap, blank);
+    LAUNCHCHK("prefix_init");
+    if (fmax > 0) {   // once per call: joint.enc_ffn and log_softmax(ctc_lo(.)) over the B*T frames, with the kernel / tile choices of a
+                      // small call whatever B is, so that an utterance's sums do not depend on the batch it is in
+        GemmCapScope cap(ctx);
+        GemmP g = plain_gemm(enc_dev, D, ctx->wenc, D, ctx->benc, u.encp, D, (int)frames, D, D);
+        if ((rc = launch_gemm(ctx, s, &g, 1, TAG_ENC_PROJ))) return rc;
+        if (with_ctc && (rc = rnnt_ctc_logprobs(ctx, enc_dev, (int)frames, u.ctc, stream))) return rc;
+    }
+    PrefixStepP p;
+    memset(&p, 0, sizeof(p));
+    p.whh = ctx->whh_il; p.egate = ctx->egate; p.wpr = ctx->wpr; p.bpr = ctx->bpr; p.wpf = ctx->wpf; p.bpf = ctx->bpf;
+    p.wout = ctx->wout; p.bout = ctx->bout; p.encp = u.encp; p.ctc = u.ctc; p.nh = u.nh; p.lens = u.lens;
+    p.top_lp = u.top_lp; p.top_tok = u.top_tok; p.vocab = V; p.k = k; p.beam = beam_size; p.T = T; p.lcap = (int)lcap;
+    p.tw = transducer_weight; p.cw = ctc_weight;
+    int t = 0;
+    for (int f = 0; f < fmax; ++f) {   // launches only
+        p.pool = u.pool[t]; p.tk = u.tk[t]; p.len = u.len[t]; p.f = f;
+        {
+            ProfScope prof(ctx, s, TAG_PREFIX_STEP);
+            hipLaunchKernelGGL(prefix_step, dim3((unsigned)R), dim3(512), 0, s, p);
+            LAUNCHCHK("prefix_step");
+        }
+        {
+            ProfScope prof(ctx, s, TAG_PREFIX_MERGE);
+            hipLaunchKernelGGL(prefix_merge, dim3(B), dim3(PB_NT), 0, s, prefix_merge_params(u, t, true, (int)lcap, k, beam_size, blank, f));
+            LAUNCHCHK("prefix_merge");
+        }
+        t ^= 1;
+    }
+    hipLaunchKernelGGL(prefix_pack, dim3((unsigned)R), dim3(256), 0, s, u.pool[t], u.tk[t], u.len[t], u.sc[t], u.nh, B, beam_size, (int)lcap,
+                       with_states, ctx->pb_out);
+    LAUNCHCHK("prefix_pack");
+    std::vector<double> out(out_doubles);
+    HIPCHK(hipMemcpyAsync(out.data(), ctx->pb_out, out_bytes, hipMemcpyDeviceToHost, s));                // the download
+    HIPCHK(hipStreamSynchronize(s));
+    const int* oi = reinterpret_cast<const int*>(out.data() + R);
+    const int *o_len = oi + B, *o_tk = o_len + R;
+    const float* o_h = reinterpret_cast<const float*>(o_tk + R * lcap);
+    memcpy(scores_host, out.data(), R * sizeof(double));
+    memcpy(n_hyp_host, oi, B * sizeof(int));
+    memcpy(lens_host, o_len, R * sizeof(int));
+    for (size_t r = 0; r < R; ++r) memcpy(tokens_host + r * cap_tokens, o_tk + r * lcap, (size_t)o_len[r] * sizeof(int));
+    if (with_states) {
+        memcpy(h_host, o_h, R * D * sizeof(float));
+        memcpy(c_host, o_h + R * D, R * D * sizeof(float));
+    }
+    return RNNT_OK;
+}
+
+// One prefix_merge launch on flat host inputs for ONE utterance (test seam against rnnt_prefix_merge_host): same arguments and
+// results.  Uses the prefix search's own buffers only; no LSTM state is gathered.  Synchronises.
+int rnnt_prefix_merge_device(rnnt_ctx* ctx, int32_t n_hyp, const int32_t* hyp_len, const int32_t* hyp_tokens, const double* hyp_score,
+                             const float* top_lp, const int32_t* top_tok, int32_t k, int32_t blank, int32_t beam_size, int32_t* out_len,
+                             int32_t* out_tokens, double* out_score, int32_t* out_src_row, int32_t* out_src_slot, void* stream) {
+    if (!ctx) return RNNT_ERR_ARG;
+    if (!hyp_len || !hyp_score || !top_lp || !top_tok || !out_len || !out_tokens || !out_score)
+        return fail(ctx, RNNT_ERR_ARG, "rnnt_prefix_merge_device: null argument");
+    if (n_hyp < 1 || n_hyp > PB_MAX_BEAM || k < 1 || k > PB_MAX_BEAM || beam_size < 1 || beam_size > PB_MAX_BEAM)
+        return fail(ctx, RNNT_ERR_ARG, "rnnt_prefix_merge_device: n_hyp %d, k %d, beam %d outside [1, %d]", n_hyp, k, beam_size, PB_MAX_BEAM);
+    size_t lmax = 0, ntok = 0;
+    for (int i = 0; i < n_hyp; ++i) {
+        if (hyp_len[i] < 0) return fail(ctx, RNNT_ERR_ARG, "rnnt_prefix_merge_device: bad hypothesis %d", i);
+        lmax = std::max(lmax, (size_t)hyp_len[i]);
+        ntok += hyp_len[i];
+    }
+    if (ntok && !hyp_tokens) return fail(ctx, RNNT_ERR_ARG, "rnnt_prefix_merge_device: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t lcap = lmax + 1, width = std::max(n_hyp, beam_size);
+    int rc;
+    PrefixBuf u;
+    if ((rc = prefix_buffers(ctx, 1, width, lcap, 0, false, k, u))) return rc;
+    std::vector<int> toks(width * lcap, 0), len(width, 0), nh(1, n_hyp);
+    std::vector<double> sc(width, 0.0);
+    std::vector<unsigned long long> hs(width, BEAM_HASH0);
+    for (int i = 0, off = 0; i < n_hyp; off += hyp_len[i], ++i) {
+        std::copy(hyp_tokens + off, hyp_tokens + off + hyp_len[i], toks.begin() + (size_t)i * lcap);
+        len[i] = hyp_len[i];
+        sc[i] = hyp_score[i];
+        hs[i] = beam_hash(hyp_tokens + off, hyp_len[i]);
+    }
+    HIPCHK(hipMemcpyAsync(u.tk[0], toks.data(), toks.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(u.len[0], len.data(), width * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(u.sc[0], sc.data(), width * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(u.hs[0], hs.data(), width * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(u.nh, nh.data(), sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(u.top_lp, top_lp, (size_t)n_hyp * k * sizeof(float), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(u.top_tok, top_tok, (size_t)n_hyp * k * sizeof(int), hipMemcpyHostToDevice, s));
+    PrefixMergeP m = prefix_merge_params(u, 0, false, (int)lcap, k, beam_size, blank, 0);
+    m.lens = nullptr;                                                // the utterance has this frame
+    {
+        ProfScope prof(ctx, s, TAG_PREFIX_MERGE);
+        hipLaunchKernelGGL(prefix_merge, dim3(1), dim3(PB_NT), 0, s, m);
+        LAUNCHCHK("prefix_merge");
+    }
+    std::vector<int> srow(width), sslot(width);
+    HIPCHK(hipMemcpyAsync(nh.data(), u.nh, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(len.data(), u.len[1], width * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(sc.data(), u.sc[1], width * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(toks.data(), u.tk[1], toks.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(srow.data(), u.src_row, width * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(sslot.data(), u.src_slot, width * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    size_t off = 0;
+    for (int a = 0; a < nh[0]; ++a) {
+        out_len[a] = len[a];
+        for (int q = 0; q < len[a]; ++q) out_tokens[off++] = toks[(size_t)a * lcap + q];
+        out_score[a] = sc[a];
+        if (out_src_row) out_src_row[a] = srow[a];
+        if (out_src_slot) out_src_slot[a] = sslot[a];
+    }
+    return nh[0];
+}

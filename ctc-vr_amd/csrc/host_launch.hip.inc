@@ -32,7 +32,8 @@ enum { TAG_NONE = 0, TAG_CONV1 = 1, TAG_CONV2 = 2, TAG_EMBED = 3, TAG_FFN1 = 4, 
        TAG_JOINT_TANH = 22, TAG_JOINT_OUT = 23, TAG_GREEDY_UPDATE = 24, TAG_BLOCK_FRONT = 30, TAG_BLOCK_BACK = 31, TAG_FFN_FUSED = 32, TAG_FFN_QKV = 33, TAG_OUT_PW1 = 34, TAG_FFN_MERGED = 35,
        TAG_CONV1_MINOR = 36, TAG_CONV2_MINOR = 37, TAG_EMBED_MINOR = 38,   // subsampling of the minor chunk classes of a whole-utterance call (the tail chunk)
        TAG_SCORE_PICK = 40, TAG_SCORE_ALPHA = 41,     // scoring: the picked lattice (fused kernel, or lattice + gather); transducer_alpha / ctc_alpha
-       TAG_SCORE_VITERBI = 42 };                      // forced alignment: transducer_viterbi / ctc_viterbi, back-trace included
+       TAG_SCORE_VITERBI = 42,                        // forced alignment: transducer_viterbi / ctc_viterbi, back-trace included
+       TAG_PREFIX_STEP = 43, TAG_PREFIX_MERGE = 44 }; // prefix beam search: prefix_step / prefix_merge, one launch each per frame
 
 struct ProfScope {   // records a start/stop event pair around one launch when its site is selected
     rnnt_ctx* ctx; hipStream_t s; bool on;

@@ -233,6 +233,13 @@ struct rnnt_ctx {
     unsigned* al_bp = nullptr;
     double* al_out = nullptr;
     size_t al_bp_cap = 0, al_out_cap = 0;
+    // prefix beam search (api_prefix.hip.inc): its own grow-only buffers, sized by B * beam rows and T + 1 tokens -- projected frames /
+    // CTC log-probabilities / state pools / top-k values (pb_f), token lists / lengths / counts / top-k tokens (pb_i), scores and
+    // hashes (pb_d), and the packed block of one call's results (pb_out)
+    float* pb_f = nullptr;
+    int* pb_i = nullptr;
+    double *pb_d = nullptr, *pb_out = nullptr;
+    size_t pb_f_cap = 0, pb_i_cap = 0, pb_d_cap = 0, pb_out_cap = 0;
     hipStream_t cap_stream = nullptr;          // stream-capture scratch stream
     struct DecGraph { int n_streams, k; hipGraphExec_t exec; };
     std::vector<DecGraph> dec_graphs;          // K greedy steps captured once per (n_streams, K)
@@ -257,4 +264,5 @@ extern "C" {
 #include "api_score.hip.inc"
 #include "api_state.hip.inc"
 #include "api_pool.hip.inc"
+#include "api_prefix.hip.inc"
 }  // extern "C"

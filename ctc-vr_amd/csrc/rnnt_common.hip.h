@@ -16,6 +16,7 @@
 //                  publish_frames, probe_overlap_wait, unpack_keys
 //   rnnt_frontend  reflect_pad, power_spectrum (rnnt_fbank)
 //   rnnt_beam      beam_chain, beam_reduce, beam_gather, log_softmax_rows
+//   rnnt_prefix    prefix_step, prefix_merge, prefix_init, prefix_pack (rnnt_prefix_beam_decode)
 //   rnnt_misc      fill_i32, gather_att_cache, gather_cnn_cache
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,0 +1,290 @@
+// Prefix beam search kernels (rnnt_prefix_beam_decode): WeNet's CTC-fused prefix beam search
+// (wenet/transducer/search/prefix_beam_search.py:42-148) for a padded batch, two launches per encoder frame.
+// Part of rnnt_kernels.hip.h (include that umbrella, not this file).
+//
+// Rows are fixed: hypothesis i of utterance b is row b * beam + i of two buffer sets (token lists [rows][lcap], lengths, f64 scores,
+// 64-bit running hashes as in beam_merge_stream_dev, LSTM states [rows][2][512]: slot 0 = the hypothesis' state, slot 1 = the
+// state after its last token went through the predictor).  prefix_step reads the current set and writes slot 1 and the row's
+// top-k; prefix_merge reads the current set and writes the other one.  A hypothesis always holds its leading blank, so len >= 1.
+#pragma once
+
+constexpr int PB_MAX_BEAM = 16, PB_MAX_CAND = PB_MAX_BEAM * PB_MAX_BEAM, PB_NT = 256, PB_NONE = 0x7fffffff;
+
+struct PrefixStepP {
+    const float* whh; const float* egate; const float* wpr; const float* bpr; const float* wpf; const float* bpf;
+    const float* wout; const float* bout;
+    const float* encp;           // [B][T][256] joint.enc_ffn of the frames
+    const float* ctc;            // [B][T][vocab] CTC log-probabilities, or nullptr (ctc_weight == 0: the term is 0.f)
+    float* pool;                 // [rows][2][512] (h | c) of the current set
+    const int* tk; const int* len;   // current set
+    const int* nh;               // [B] hypotheses per utterance
+    const int* lens;             // [B] frames per utterance
+    float* top_lp; int* top_tok; // [rows][k]
+    int vocab, k, beam, T, f, lcap;
+    float tw, cw;
+};
+
+// One evaluation of beam_chain_row's arithmetic (same operands, same order) for one live hypothesis at frame f: LSTM cell on
+// (embed[last token], slot 0) -> slot 1, predictor.projection, joint.pred_ffn + projected frame, tanh, vocabulary projection,
+// log-softmax; then the shallow fusion log(tw * exp(lp) + cw * exp(ctc)) in f32 with separately rounded products and sum
+// (prefix_beam_search.py:99-101) and the top-k over the WHOLE vocabulary, blank included (:104): value descending, lower index
+// first on equal values.
+__global__ __launch_bounds__(512) void prefix_step(PrefixStepP p) {
+    constexpr int NTH = 512;
+    __shared__ __attribute__((aligned(16))) float hs[1][RNNT_D], cs[RNNT_D], h2[1][RNNT_D], pr[1][RNNT_D], zs[1][RNNT_D];
+    __shared__ __attribute__((aligned(16))) float gates[4 * RNNT_D];
+    __shared__ float lg[512];
+    const int r = blockIdx.x, b = r / p.beam, i = r - b * p.beam, tid = threadIdx.x;
+    if (i >= ldgi(p.nh + b) || p.f >= ldgi(p.lens + b)) return;    // whole workgroup: before the first barrier
+    const int tok = ldgi(p.tk + (long long)r * p.lcap + ldgi(p.len + r) - 1);
+    float* pool = p.pool + (long long)r * 1024;
+    const long long fr = (long long)b * p.T + p.f;
+    const float* enc = p.encp + fr * RNNT_D;
+    if (tid < RNNT_D) { hs[0][tid] = ldg1(pool + tid); cs[tid] = ldg1(pool + RNNT_D + tid); }
+    __syncthreads();
+    dec_matvec<1, NTH>(p.whh, 4 * RNNT_D, hs, [&](int n, const float* acc) {                       // predictor.forward_step (predictor.py:185-210)
+        gates[n] = acc[0] + ldg1(p.egate + (long long)tok * (4 * RNNT_D) + n);
+    });
+    __syncthreads();
+    if (tid < RNNT_D) {
+        const float4 gt = *reinterpret_cast<const float4*>(&gates[4 * tid]);
+        const float cc = sigmoidf_(gt.y) * cs[tid] + sigmoidf_(gt.x) * tanhf(gt.z);
+        const float hh = sigmoidf_(gt.w) * tanhf(cc);
+        h2[0][tid] = hh;
+        stg1(pool + 512 + tid, hh);
+        stg1(pool + 512 + RNNT_D + tid, cc);
+    }
+    __syncthreads();
+    dec_matvec<1, NTH>(p.wpr, RNNT_D, h2, [&](int n, const float* acc) { pr[0][n] = acc[0] + ldg1(p.bpr + n); });   // predictor.projection
+    __syncthreads();
+    dec_matvec<1, NTH>(p.wpf, RNNT_D, pr, [&](int n, const float* acc) {                           // joint (joint.py:54-66)
+        zs[0][n] = tanhf(acc[0] + ldg1(p.bpf + n) + ldg1(enc + n));
+    });
+    __syncthreads();
+    dec_matvec<1, NTH>(p.wout, p.vocab, zs, [&](int n, const float* acc) { lg[n] = acc[0] + ldg1(p.bout + n); });
+    __syncthreads();
+    if (tid >= 64) return;                                          // no barrier below
+    const int lane = tid;
+    const float* ctc = p.ctc ? p.ctc + fr * p.vocab : nullptr;
+    float v[8];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int idx = lane + 64 * j;
+        v[j] = idx < p.vocab ? lg[idx] : -INFINITY;
+        mx = fmaxf(mx, v[j]);
+    }
+    mx = wave_max(mx);
+    float se = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) se += (lane + 64 * j) < p.vocab ? expf(v[j] - mx) : 0.f;
+    const float lse = logf(wave_sum(se));
+    unsigned avail = 0;                                             // bit j: token lane + 64 j exists and is not chosen yet
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int idx = lane + 64 * j;
+        if (idx < p.vocab) {
+            const float lp = (v[j] - mx) - lse;
+            const float c = ctc ? __fmul_rn(p.cw, expf(ldg1(ctc + idx))) : 0.f;
+            v[j] = logf(__fadd_rn(__fmul_rn(p.tw, expf(lp)), c));
+            avail |= 1u << j;
+        }
+    }
+    for (int t = 0; t < p.k; ++t) {                                 // k <= vocab: a token is always left
+        float bv = -INFINITY;
+        int bi = PB_NONE;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (((avail >> j) & 1u) && (bi == PB_NONE || v[j] > bv)) { bv = v[j]; bi = lane + 64 * j; }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const float ov = __shfl_xor(bv, off, 64);
+            const int oi = __shfl_xor(bi, off, 64);
+            if (oi != PB_NONE && (bi == PB_NONE || ov > bv || (ov == bv && oi < bi))) { bv = ov; bi = oi; }
+        }
+        if ((bi & 63) == lane) avail &= ~(1u << (bi >> 6));         // remove the winner
+        if (lane == 0) {
+            p.top_lp[(long long)r * p.k + t] = bv;
+            p.top_tok[(long long)r * p.k + t] = bi;
+        }
+    }
+}
+
+struct PrefixMergeP {
+    const float* pool_in; float* pool_out;      // [rows][2][512]; pool_in == nullptr: no state gather (rnnt_prefix_merge_device)
+    const int* tk_in; int* tk_out;              // [rows][lcap]
+    const int* len_in; int* len_out;            // [rows]
+    const double* sc_in; double* sc_out;        // [rows]
+    const unsigned long long* hs_in; unsigned long long* hs_out;   // [rows]
+    int* nh;                                    // [B] hypotheses per utterance (read, then rewritten)
+    const int* lens;                            // [B] frames per utterance
+    const float* top_lp; const int* top_tok;    // [rows][k]
+    int* src_row; int* src_slot;                // [rows] where each survivor's state came from (hypothesis index, slot)
+    int lcap, k, beam, blank, f;
+};
+
+// list form of wenet.utils.common.log_add for two values, as Python evaluates it: -inf if both are, else max + log(sum of exp)
+__host__ __device__ inline double prefix_log_add(double a, double b) {
+    if (a == -INFINITY && b == -INFINITY) return -INFINITY;
+    const double m = a > b ? a : b;
+    return m + log(exp(a - m) + exp(b - m));
+}
+
+// The host half of one frame of prefix_beam_search.py:105-145 for one utterance per workgroup:
+//   candidates  c = j * k + t in the reference's order (per hypothesis j, per rank t): f64((f32)score_j + top_lp[j][t]); a blank
+//               keeps row j's tokens and slot 0, any other token appends and takes slot 1
+//   fusion      sequential in candidate order (:130-142): a candidate whose sequence equals an earlier survivor's is log-added
+//               into it, the first one's tokens and state stay.  rep[c] = the first candidate with c's sequence (hash, then
+//               length, then every token); every first candidate then adds its followers in ascending order
+//   order       stable descending sort of the survivors: repeated block-wide argmax, ties to the lower candidate index
+//   truncation  to `beam`; tokens, hashes and states gathered into rows row0 + a of the other set
+// An utterance past its last frame (f >= lens[b]) is carried over unchanged.
+__global__ __launch_bounds__(PB_NT) void prefix_merge(PrefixMergeP p) {
+    __shared__ double sc[PB_MAX_CAND];
+    __shared__ unsigned long long hsh[PB_MAX_CAND];
+    __shared__ int clen[PB_MAX_CAND], ctok[PB_MAX_CAND], first[PB_MAX_CAND], rep[PB_MAX_CAND];
+    __shared__ unsigned char taken[PB_MAX_CAND];
+    __shared__ int h_len[PB_MAX_BEAM], acc[PB_MAX_BEAM];
+    __shared__ double red_v[PB_NT / 64];
+    __shared__ int red_i[PB_NT / 64];
+    __shared__ int s_best;
+    const int tid = threadIdx.x, b = blockIdx.x, row0 = b * p.beam;
+    const int nh = p.nh[b];
+    if (p.lens && p.f >= p.lens[b]) {                                // finished: carry the rows over unchanged
+        for (int i = 0; i < nh; ++i) {
+            const int r = row0 + i, len = p.len_in[r];
+            for (int q = tid; q < len; q += PB_NT) p.tk_out[(long long)r * p.lcap + q] = p.tk_in[(long long)r * p.lcap + q];
+            if (p.pool_in)
+                for (int e = tid; e < 512; e += PB_NT) p.pool_out[(long long)r * 1024 + e] = p.pool_in[(long long)r * 1024 + e];
+            if (tid == 0) { p.len_out[r] = len; p.sc_out[r] = p.sc_in[r]; p.hs_out[r] = p.hs_in[r]; }
+        }
+        return;
+    }
+    const int C = nh * p.k;                                          // <= 256 = PB_NT
+    if (tid < nh) h_len[tid] = p.len_in[row0 + tid];
+    if (tid < C) {
+        const int j = tid / p.k, r = row0 + j;
+        const int tok = p.top_tok[(long long)row0 * p.k + tid];
+        const float s32 = (float)p.sc_in[r];                         // torch.tensor([s.score]): the running double rounded to f32
+        sc[tid] = (double)__fadd_rn(s32, p.top_lp[(long long)row0 * p.k + tid]);   // f32 add (:105), widened by .item()
+        const bool bl = tok == p.blank;
+        ctok[tid] = tok;
+        clen[tid] = p.len_in[r] + (bl ? 0 : 1);
+        hsh[tid] = bl ? p.hs_in[r] : beam_hash_step(p.hs_in[r], tok);
+        taken[tid] = 0;
+    }
+    __syncthreads();
+    if (tid < C) {                                                   // first candidate with the same hash and length
+        int m = tid;
+        for (int c = 0; c < tid; ++c)
+            if (hsh[c] == hsh[tid] && clen[c] == clen[tid]) { m = c; break; }
+        first[tid] = m;
+        rep[tid] = tid;
+    }
+    __syncthreads();
+    auto tok_at = [&](int c, int q) {
+        const int j = c / p.k;
+        return q < h_len[j] ? p.tk_in[(long long)(row0 + j) * p.lcap + q] : ctok[c];
+    };
+    for (int c = 1; c < C; ++c) {                                    // uniform: everything the loop branches on is in LDS
+        if (first[c] == c) continue;
+        const int len = clen[c];
+        for (int d = first[c]; d < c; ++d) {                         // equal hashes of different sequences never merge
+            if (rep[d] != d || hsh[d] != hsh[c] || clen[d] != len) continue;
+            int diff = 0;
+            for (int q = tid; q < len; q += PB_NT) diff |= tok_at(c, q) != tok_at(d, q);
+            if (!__syncthreads_or(diff)) {
+                if (tid == 0) rep[c] = d;
+                break;
+            }
+        }
+        __syncthreads();
+    }
+    __syncthreads();
+    if (tid < C && rep[tid] == tid) {                                // the followers' log_add, in candidate order
+        double s = sc[tid];
+        for (int c = tid + 1; c < C; ++c)
+            if (rep[c] == tid) s = prefix_log_add(s, sc[c]);
+        sc[tid] = s;
+    }
+    __syncthreads();
+    const int lane = tid & 63, w = tid >> 6;
+    int n_acc = 0;
+    while (n_acc < p.beam) {
+        double bv = -INFINITY;
+        int bi = PB_NONE;
+        if (tid < C && rep[tid] == tid && !taken[tid]) { bv = sc[tid]; bi = tid; }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const double ov = __shfl_xor(bv, off, 64);
+            const int oi = __shfl_xor(bi, off, 64);
+            if (oi != PB_NONE && (bi == PB_NONE || ov > bv || (ov == bv && oi < bi))) { bv = ov; bi = oi; }
+        }
+        if (lane == 0) { red_v[w] = bv; red_i[w] = bi; }
+        __syncthreads();
+        if (tid == 0) {
+            for (int q = 1; q < PB_NT / 64; ++q)
+                if (red_i[q] != PB_NONE && (bi == PB_NONE || red_v[q] > bv || (red_v[q] == bv && red_i[q] < bi))) { bv = red_v[q]; bi = red_i[q]; }
+            s_best = bi;
+            if (bi != PB_NONE) { taken[bi] = 1; acc[n_acc] = bi; }
+        }
+        __syncthreads();
+        if (s_best == PB_NONE) break;                                // survivors exhausted
+        ++n_acc;
+    }
+    for (int a = 0; a < n_acc; ++a) {
+        const int c = acc[a], j = c / p.k, nr = row0 + a, len = clen[c], slot = ctok[c] == p.blank ? 0 : 1;
+        for (int q = tid; q < len; q += PB_NT) p.tk_out[(long long)nr * p.lcap + q] = tok_at(c, q);
+        if (p.pool_in) {
+            const float* src = p.pool_in + ((long long)(row0 + j) * 2 + slot) * 512;
+            float* dst = p.pool_out + (long long)nr * 1024;
+            for (int e = tid; e < 512; e += PB_NT) dst[e] = src[e];
+        }
+        if (tid == 0) {
+            p.len_out[nr] = len;
+            p.sc_out[nr] = sc[c];
+            p.hs_out[nr] = hsh[c];
+            p.src_row[nr] = j;
+            p.src_slot[nr] = slot;
+        }
+    }
+    if (tid == 0) p.nh[b] = n_acc;
+}
+
+// Start of a call: every utterance holds the one hypothesis [blank] with score 0 and the zero LSTM state (:68-77) in set 0.
+__global__ __launch_bounds__(256) void prefix_init(float* pool, int* tk, int* len, double* sc, unsigned long long* hs, int* nh, int beam,
+                                                   int lcap, int blank) {
+    const int b = blockIdx.x, r = b * beam;
+    for (int e = threadIdx.x; e < 512; e += 256) pool[(long long)r * 1024 + e] = 0.f;
+    if (threadIdx.x == 0) {
+        tk[(long long)r * lcap] = blank;
+        len[r] = 1;
+        sc[r] = 0.0;
+        hs[r] = beam_hash_step(BEAM_HASH0, blank);
+        nh[b] = 1;
+    }
+}
+
+// End of a call: the final set into ONE block for one download: scores f64 [rows] | n_hyp [B] | lengths [rows] | tokens
+// [rows][lcap] | h [rows][256] | c [rows][256] (states only if with_states).  Rows without a hypothesis are zero.
+__global__ __launch_bounds__(256) void prefix_pack(const float* pool, const int* tk, const int* len, const double* sc, const int* nh, int B,
+                                                   int beam, int lcap, int with_states, double* out) {
+    const int r = blockIdx.x, b = r / beam, i = r - b * beam, rows = B * beam, tid = threadIdx.x;
+    int* oi = reinterpret_cast<int*>(out + rows);
+    int* o_len = oi + B;
+    int* o_tk = o_len + rows;
+    float* o_h = reinterpret_cast<float*>(o_tk + (long long)rows * lcap);
+    float* o_c = o_h + (long long)rows * RNNT_D;
+    const bool live = i < nh[b];
+    const int n = live ? len[r] : 0;
+    for (int q = tid; q < lcap; q += 256) o_tk[(long long)r * lcap + q] = q < n ? tk[(long long)r * lcap + q] : 0;
+    if (with_states) {
+        o_h[(long long)r * RNNT_D + tid] = live ? pool[(long long)r * 1024 + tid] : 0.f;
+        o_c[(long long)r * RNNT_D + tid] = live ? pool[(long long)r * 1024 + RNNT_D + tid] : 0.f;
+    }
+    if (tid == 0) {
+        out[r] = live ? sc[r] : 0.0;
+        o_len[r] = n;
+        if (i == 0) oi[b] = nh[b];
+    }
+}

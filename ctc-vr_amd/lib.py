@@ -54,6 +54,9 @@ SIGNATURES = {
     "rnnt_encoder_full": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32p, c_vp]),
     "rnnt_ctc_argmax": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32p, c_vp]),
     "rnnt_ctc_logprobs": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp]),
+    "rnnt_prefix_beam_decode": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, ctypes.c_float, ctypes.c_float, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rnnt_prefix_merge_host": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rnnt_prefix_merge_device": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rnnt_transducer_nll": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "rnnt_ctc_nll": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "rnnt_transducer_align": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
@@ -128,6 +131,38 @@ def load(build_if_needed=True):
 
 def _np_ptr(a):
     return a.ctypes.data_as(c_vp)
+
+
+def _prefix_merge_call(fn, head, hyps, top_lp, top_tok, blank, beam_size, tail=()):
+    """Flat arguments of rnnt_prefix_merge_host / rnnt_prefix_merge_device -> the call's return value and
+    [(tokens, score, src_row, src_slot)] of the survivors."""
+    n = len(hyps)
+    hl = np.array([len(t) for t, _ in hyps], np.int32)
+    ht = np.array([x for t, _ in hyps for x in t] or [0], np.int32)
+    hs = np.array([sc for _, sc in hyps], np.float64)
+    tl = np.ascontiguousarray(top_lp, np.float32).reshape(n, -1)
+    tt = np.ascontiguousarray(top_tok, np.int32).reshape(n, -1)
+    k = tl.shape[1]
+    assert tt.shape == tl.shape
+    cap = max(beam_size, 1)
+    out_len, out_tok = np.zeros(cap, np.int32), np.zeros(cap * (int(hl.max(initial=0)) + 1) + 1, np.int32)
+    out_sc, out_row, out_slot = np.zeros(cap, np.float64), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+    m = fn(*head, n, _np_ptr(hl), _np_ptr(ht), _np_ptr(hs), _np_ptr(tl), _np_ptr(tt), k, blank, beam_size, _np_ptr(out_len), _np_ptr(out_tok),
+           _np_ptr(out_sc), _np_ptr(out_row), _np_ptr(out_slot), *tail)
+    out, o = [], 0
+    for a in range(max(m, 0)):
+        out.append((out_tok[o:o + out_len[a]].tolist(), float(out_sc[a]), int(out_row[a]), int(out_slot[a])))
+        o += out_len[a]
+    return m, out
+
+
+def prefix_merge_host(hyps, top_lp, top_tok, blank, beam_size):
+    """rnnt_prefix_merge_host (no context, no GPU): one frame's merge of the prefix beam search for one utterance.  hyps
+    [(tokens, score)], top_lp / top_tok [n][k] -> [(tokens, score, src_row, src_slot)] of the survivors, best first."""
+    m, out = _prefix_merge_call(load().rnnt_prefix_merge_host, (), hyps, top_lp, top_tok, blank, beam_size)
+    if m < 0:
+        raise RnntError(f"rnnt_prefix_merge_host: bad argument (status {m})", m)
+    return out
 
 
 class RnntEngine:
@@ -418,6 +453,33 @@ class RnntEngine:
 
     def ctc_logprobs(self, enc_ptr, rows, out_ptr, stream=None):
         self._chk(self.lib.rnnt_ctc_logprobs(self.ctx, enc_ptr, rows, out_ptr, stream), "rnnt_ctc_logprobs")
+
+    # ---- prefix beam search ------------------------------------------------------------------
+    def prefix_beam_decode(self, enc_ptr, enc_lens, B, T, beam_size=5, ctc_weight=0.3, transducer_weight=0.7, want_states=False, stream=None):
+        """rnnt_prefix_beam_decode: WeNet's CTC-fused prefix beam search over encoder frames enc [B, T, 256] on the device, row b
+        over its first enc_lens[b] frames, the whole frame loop on the device.  Returns per utterance [(tokens incl. the leading
+        blank, score)], best first; with want_states also (h, c), each [B, beam_size, 256] (rows beyond an utterance's hypotheses
+        are zero)."""
+        el = np.ascontiguousarray(enc_lens, np.int32)
+        assert el.size == B
+        w = max(beam_size, 1)
+        cap = int(el.max(initial=0)) + 1
+        nh, lens = np.zeros(B, np.int32), np.zeros((B, w), np.int32)
+        toks, sc = np.zeros((B, w, cap), np.int32), np.zeros((B, w), np.float64)
+        h = np.zeros((B, w, 256), np.float32) if want_states else None
+        c = np.zeros((B, w, 256), np.float32) if want_states else None
+        self._chk(self.lib.rnnt_prefix_beam_decode(self.ctx, enc_ptr, _np_ptr(el), B, T, beam_size, ctc_weight, transducer_weight, cap, _np_ptr(nh),
+                                                   _np_ptr(lens), _np_ptr(toks), _np_ptr(sc), _np_ptr(h) if want_states else None,
+                                                   _np_ptr(c) if want_states else None, stream), "rnnt_prefix_beam_decode")
+        hyps = [[(toks[b, i, :lens[b, i]].tolist(), float(sc[b, i])) for i in range(nh[b])] for b in range(B)]
+        return (hyps, h, c) if want_states else hyps
+
+    def prefix_merge_device(self, hyps, top_lp, top_tok, blank, beam_size, stream=None):
+        """rnnt_prefix_merge_device: prefix_merge_host's arguments and results through one prefix_merge launch."""
+        m, out = _prefix_merge_call(self.lib.rnnt_prefix_merge_device, (self.ctx,), hyps, top_lp, top_tok, blank, beam_size, (stream,))
+        if m < 0:
+            self._chk(m, "rnnt_prefix_merge_device")
+        return out
 
     def _score_args(self, enc_lens, targets, target_lens, B):
         el, tl = np.ascontiguousarray(enc_lens, np.int32), np.ascontiguousarray(target_lens, np.int32)

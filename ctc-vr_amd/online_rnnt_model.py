@@ -531,6 +531,33 @@ class OnlineRNNTModel:
         self._prefix_states = (h, c)
         return list(zip(hyps, scores))
 
+    def prefix_beam_search_batch(self, audios: torch.Tensor, audio_lens: torch.Tensor, beam_size: int = 5, ctc_weight: float = 0.3,
+                                 transducer_weight: float = 0.7, walk_padding: bool = True):
+        """prefix_beam_search for a padded batch audios [B, T, 80] of utterances of different lengths, with the frame loop on the
+        device: one rnnt_encoder_full call and one rnnt_prefix_beam_decode call (two launches per encoder frame, one
+        synchronisation at the end).  walk_padding: every utterance walks all T' encoder frames, the padded ones included, as the
+        reference does (:64,76) and prefix_beam_search above; False: each stops after its own valid frames.  Equal values in the
+        top-k are taken lower index first (torch.topk leaves that order open).
+        Returns one [(tokens incl. the leading blank, score)] per utterance, best first; the hypotheses' final LSTM states stay in
+        self._prefix_states_batch, one (h, c) pair of host tensors [n_hyp, 256] per utterance.  Invalidates the streaming state."""
+        self._require_loaded()
+        B, T = audios.size(0), audios.size(1)
+        x = audios.to(self.device, torch.float32).contiguous()
+        lens = audio_lens.detach().cpu().numpy().astype(np.int32).reshape(B)
+        tq = ((T - 3) // 2 + 1 - 3) // 2 + 1
+        s = _stream_ptr()
+        enc = torch.empty(B, tq, 256, device=self.device)
+        self._engine.encoder_full(x.data_ptr(), lens, B, T, enc.data_ptr(), s)
+        self._chunks_done = None
+        if walk_padding:
+            enc_lens = np.full(B, tq, np.int32)
+        else:
+            n1 = np.maximum(0, (np.minimum(lens, T) - 1) // 2)     # valid frames after masks[:, :, 2::2][:, :, 2::2]
+            enc_lens = np.maximum(0, (n1 - 1) // 2).astype(np.int32)
+        hyps, h, c = self._engine.prefix_beam_decode(enc.data_ptr(), enc_lens, B, tq, beam_size, ctc_weight, transducer_weight, True, s)
+        self._prefix_states_batch = [(torch.from_numpy(h[b, :len(hyps[b])].copy()), torch.from_numpy(c[b, :len(hyps[b])].copy())) for b in range(B)]
+        return hyps
+
     def greedy_search_full(self, audios, audio_lens, n_steps: int = 64):
         """basic_greedy_search over the deterministic full-context encoder; audios [B,T,80] with B <= max_streams,
         T <= max_chunk_frames, ((T-3)//2+1-3)//2+1 <= max_enc_frames.  Invalidates the streaming state."""

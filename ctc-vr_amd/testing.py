@@ -339,3 +339,35 @@ def ctc_align_bruteforce(lp, targets, T_b, blank):
         walk(0, s0, p[0, ext[s0]], [s0])
     out.sort(key=lambda sp: (-sp[0], tuple(-s for s in reversed(sp[1]))))
     return out
+
+
+# ---- prefix beam search: one frame's merge for one utterance (tests) ------------------------------------------------------------
+def _log_add(args):
+    """wenet.utils.common.log_add in the list form its prefix-beam-search call site uses."""
+    if all(a == -math.inf for a in args):
+        return -math.inf
+    a_max = max(args)
+    return a_max + math.log(sum(math.exp(a - a_max) for a in args))
+
+
+def prefix_merge_ref(hyps, top_lp, top_tok, blank, beam_size):
+    """The merge of wenet/transducer/search/prefix_beam_search.py:105-145 for one utterance in Python lists and doubles.  hyps
+    [(tokens, score)], top_lp / top_tok [n][k].  Candidates per hypothesis j, per rank t: the running double score rounded to f32
+    (torch.tensor([s.score])), added to the f32 top value in f32 (:105), widened to double (.item()); a blank candidate keeps the
+    tokens and state slot 0 of j, any other token appends and takes slot 1; a candidate whose tokens equal an earlier survivor's is
+    log-added into it and the first one's tokens and state stay (:130-142); stable descending sort; truncation.
+    Returns [(tokens, score, src_row, src_slot)]."""
+    fused = []
+    for j, (toks, score) in enumerate(hyps):
+        s32 = np.float32(score)
+        for lp, tok in zip(top_lp[j], top_tok[j]):
+            tok = int(tok)
+            cand = [list(toks) + ([] if tok == blank else [tok]), float(np.float32(s32 + np.float32(lp))), j, 0 if tok == blank else 1]
+            for f in fused:
+                if f[0] == cand[0]:
+                    f[1] = _log_add([f[1], cand[1]])
+                    break
+            else:
+                fused.append(cand)
+    fused.sort(key=lambda v: v[1], reverse=True)
+    return [tuple(f) for f in fused[:beam_size]]

@@ -292,8 +292,53 @@ int rnnt_ctc_argmax(rnnt_ctx* ctx, const float* fbank_dev, const int32_t* lens_h
 
 /* OnlineCTC.log_softmax (model/online_rnnt_model.py:34-35) on encoder frames already on the device: out_dev [rows, vocab] =
  * log_softmax(ctc_lo(enc_dev [rows, 256])).  The CTC term of the WeNet prefix beam search (wenet/transducer/search/
- * prefix_beam_search.py:66,99-101), whose frame loop runs in the facade over rnnt_encoder_full / rnnt_predictor_step / rnnt_joint. */
+ * prefix_beam_search.py:66,99-101), whose frame loop runs in the facade over rnnt_encoder_full / rnnt_predictor_step / rnnt_joint
+ * (OnlineRNNTModel.prefix_beam_search), or entirely on the device in rnnt_prefix_beam_decode below. */
 int rnnt_ctc_logprobs(rnnt_ctx* ctx, const float* enc_dev, int32_t rows, float* out_dev, void* stream);
+
+/* -- prefix beam search: WeNet's CTC-fused search (wenet/transducer/search/prefix_beam_search.py:42-148), batched and ragged ---- */
+/* One symbol at most per encoder frame, CTC shallow fusion, prefix merging with log-add, for a padded batch of utterances of
+ * different lengths in one call: row b walks frames [0, enc_lens_host[b]) of enc_dev [B, T, 256] (the output of rnnt_encoder_full,
+ * device).  The reference walks every frame of its (batch-1) encoder output, padded ones included (:64,76): pass T for every row
+ * to do the same, or the valid frame counts to stop each row at its own end.  Once per call: joint.enc_ffn and
+ * log_softmax(ctc_lo(.)) (rnnt_ctc_logprobs) over the B*T frames.  Per frame two launches over the fixed rows b * beam_size + i,
+ * no host copy and no synchronisation:
+ *   prefix_step   one workgroup per live hypothesis: the LSTM cell on its last token, projection, joint, log-softmax (one
+ *                 evaluation of rnnt_beam_decode's chain arithmetic); fusion log(tw * exp(lp) + cw * exp(ctc[t])) in f32 (:99-101);
+ *                 top-beam_size over the WHOLE vocabulary, blank included (:104), value descending and, on equal values, the lower
+ *                 index first (torch.topk leaves the order of equal values unspecified; this is the order the library defines)
+ *   prefix_merge  one workgroup per utterance: candidates per hypothesis, per rank; score = f64((f32)running score + top value)
+ *                 (:105); a blank keeps tokens and state, a token extends both (:110-126); a candidate whose token sequence
+ *                 equals an earlier survivor's is log-added into it in f64 (the list form log_add([a, b]): -inf if both are, else
+ *                 max + log(sum exp)) and the first one's tokens and state stay (:130-142); stable descending sort, truncation
+ * Results, hypotheses best first: n_hyp_host [B]; lens_host [B, beam_size]; tokens_host [B, beam_size, cap_tokens] (row (b, i)
+ * holds lens_host[b][i] tokens INCLUDING the leading blank, as the reference's hyp does; the rest of a row is not written);
+ * scores_host [B, beam_size] f64; h_host / c_host: both NULL, or [B, beam_size, 256] receiving the hypotheses' LSTM states.
+ * Entries of hypotheses i >= n_hyp_host[b] are zero.  A row of length 0 returns the one start hypothesis [blank] with score 0 and
+ * the zero state.  With ctc_weight == 0 the CTC head is not needed and the CTC term is the literal 0.f.
+ * One upload, one download, one synchronisation at the end.  The call leaves streaming, pool and lock-step beam state alone and
+ * works on a context created with max_beam = 0: its buffers are its own, grow-only, sized by B * beam_size rows and T + 1 tokens.
+ * Refusals, all decided on the host before the first launch: null pointer (h_host / c_host: one without the other), B < 1, a
+ * length outside [0, T], beam_size outside [1, min(16, vocab_size)], vocab_size > 512, a negative weight or both weights zero,
+ * cap_tokens < 1 + the longest length: RNNT_ERR_ARG; weights not finalized, ctc_weight > 0 without ctc_head.ctc_lo.*:
+ * RNNT_ERR_STATE. */
+int rnnt_prefix_beam_decode(rnnt_ctx* ctx, const float* enc_dev, const int32_t* enc_lens_host, int32_t B, int32_t T, int32_t beam_size,
+                            float ctc_weight, float transducer_weight, int32_t cap_tokens, int32_t* n_hyp_host, int32_t* lens_host,
+                            int32_t* tokens_host, double* scores_host, float* h_host, float* c_host, void* stream);
+/* prefix_merge's step for ONE utterance as a pure function (no context, no GPU; CPU tests): hyp_len [n_hyp], hyp_tokens
+ * (concatenated), hyp_score [n_hyp] f64, top_lp / top_tok [n_hyp][k] in; survivors best first out -- out_len, out_tokens
+ * (concatenated; room for beam_size * (longest input + 1) ints), out_score, and where each survivor's LSTM state comes from:
+ * out_src_row = the hypothesis index, out_src_slot = 0 (its state, blank candidate) or 1 (the state after its last token).
+ * Returns the number of survivors, or RNNT_ERR_ARG. */
+int rnnt_prefix_merge_host(int32_t n_hyp, const int32_t* hyp_len, const int32_t* hyp_tokens, const double* hyp_score,
+                           const float* top_lp, const int32_t* top_tok, int32_t k, int32_t blank, int32_t beam_size,
+                           int32_t* out_len, int32_t* out_tokens, double* out_score, int32_t* out_src_row, int32_t* out_src_slot);
+/* The same through ONE prefix_merge launch (test seam; n_hyp, k, beam_size <= 16; any context, weights not needed).  Uses the
+ * prefix search's own buffers only.  Synchronises. */
+int rnnt_prefix_merge_device(rnnt_ctx* ctx, int32_t n_hyp, const int32_t* hyp_len, const int32_t* hyp_tokens, const double* hyp_score,
+                             const float* top_lp, const int32_t* top_tok, int32_t k, int32_t blank, int32_t beam_size,
+                             int32_t* out_len, int32_t* out_tokens, double* out_score, int32_t* out_src_row, int32_t* out_src_slot,
+                             void* stream);
 
 /* -- teacher-forced scoring: how likely is a GIVEN transcript (forward only, no gradients) ----------------------------------- */
 /* Transducer negative log-likelihood: the RNN-T term of the reference's forward with texts (model/online_rnnt_model.py:240-255),
@@ -392,7 +437,8 @@ const float* rnnt_enc_frames_dev(rnnt_ctx* ctx, int32_t* frames_out, int32_t* st
  * tag selects ONE launch site: 1 conv1, 2 conv2 (implicit GEMM), 3 embed linear, 4 FFN w_1, 5 FFN w_2, 6 QKV,
  * 7 attention, 8 attention out-proj, 9 pointwise_conv1+GLU, 10 depthwise conv, 11 pointwise_conv2, 13 joint enc
  * projection, 20 LSTM cell, 21 predictor projection, 22 joint pred_ffn+tanh, 23 joint ffn_out, 40 the picked lattice of
- * rnnt_transducer_nll, 41 its alpha recursion (and rnnt_ctc_nll's), 42 the Viterbi launch of the rnnt_*_align calls.
+ * rnnt_transducer_nll, 41 its alpha recursion (and rnnt_ctc_nll's), 42 the Viterbi launch of the rnnt_*_align calls, 43 prefix_step
+ * and 44 prefix_merge of rnnt_prefix_beam_decode (one launch each per frame).
  * rnnt_profile_end synchronises the recorded events and returns the summed kernel time and launch count. */
 int rnnt_profile_begin(rnnt_ctx* ctx, int32_t tag);
 int rnnt_profile_end(rnnt_ctx* ctx, double* total_ms, int64_t* n_launches);
