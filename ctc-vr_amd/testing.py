@@ -6,7 +6,7 @@ with NumPy's Philox bit generator (stream-stable across platforms).  The key set
 shapes are exactly the 504-entry state dict of the reference's OnlineRNNTModel
 (model/online_rnnt_model.py:58-143).
 
-Nothing here touches /root/reference or oracle/.
+Nothing here touches the reference; only encoder_stream_ref imports the CPU oracle (oracle/rnnt_oracle.py), when it is called.
 """
 import math
 import numpy as np
@@ -371,3 +371,48 @@ def prefix_merge_ref(hyps, top_lp, top_tok, blank, beam_size):
                 fused.append(cand)
     fused.sort(key=lambda v: v[1], reverse=True)
     return [tuple(f) for f in fused[:beam_size]]
+
+
+# ---- streaming encoder: one stream through the oracle's forward_chunk under any window policy (tests) ---------------------------
+_REF_SD = {}
+
+
+def ref_state_dict(np_sd, dtype=None):
+    """The state dict as torch CPU tensors with every floating-point entry cast to `dtype` (default float64), kept per (dict, dtype)."""
+    import torch
+    dtype = dtype or torch.float64
+    key = (id(np_sd), dtype)
+    if key not in _REF_SD:
+        _REF_SD[key] = (np_sd, {k: torch.from_numpy(np.asarray(v)).to(dtype) if np.asarray(v).dtype.kind == "f" else torch.from_numpy(np.asarray(v))
+                                for k, v in np_sd.items()})
+    return _REF_SD[key][1]
+
+
+def encoder_stream_ref(np_sd, x, plan, dtype=None):
+    """One stream (B = 1) chunk by chunk through the oracle's forward_chunk (wenet/transformer/encoder.py:203-299) on the state
+    dict cast to `dtype` (default float64; the cast dict is kept per (state dict, dtype)).  x [T, 80] fbank frames (numpy or
+    torch); plan = [(start, length, offset, required_cache_size)], chunk c covering x[start:start + length].  The caches are
+    carried from chunk to chunk as the reference's caller does.  Returns one dict per chunk in the reference's layouts, as numpy
+    arrays of `dtype`: "frames" [t', 256] (after after_norm), "att" [12, 4, cache_len, 128] and "cnn" [12, 1, 256, 30] as they
+    stand after the chunk, plus the chunk's "pos_start" (first row of its positional window) and "cache_len"."""
+    import torch
+    from oracle import rnnt_oracle as O
+    dtype = dtype or torch.float64
+    sd = ref_state_dict(np_sd, dtype)
+    xs = torch.as_tensor(np.asarray(x)).to(dtype)
+    assert xs.dim() == 2, "one stream per call: x is [T, 80]"
+    att, cnn = torch.zeros((0, 0, 0, 0), dtype=dtype), torch.zeros((0, 0, 0, 0), dtype=dtype)
+    out = []
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)     # rows are few (t' <= ~20): float64 matrix-vector products with many threads are very slow
+    try:
+        with torch.no_grad():
+            for start, length, offset, required in plan:
+                tr = {}
+                y, att, cnn = O.forward_chunk(sd, xs[None, start:start + length], offset, required, att, cnn, tr)
+                assert y.dtype == dtype and att.dtype == dtype and cnn.dtype == dtype
+                out.append({"frames": y[0].numpy().copy(), "att": att.numpy().copy(), "cnn": cnn.numpy().copy(),
+                            "pos_start": int(tr["pos_start"]), "cache_len": int(att.size(2))})
+    finally:
+        torch.set_num_threads(threads)
+    return out

@@ -101,7 +101,13 @@ int rnnt_streams_reset(rnnt_ctx* ctx, int32_t n_streams, void* stream);
  * (model/online_rnnt_model.py:175-181), for all streams at once.
  *   fbank_dev  [n_streams, chunk_frames, 80] float32, device
  *   offset, required_cache_size: the reference's arguments (estimated encoder offset; see
- *       model/online_rnnt_model.py:364-370).
+ *       model/online_rnnt_model.py:364-370).  required_cache_size < 0 keeps every key, 0 keeps none,
+ *       R > 0 keeps the last R (encoder.py:259-264).  R bounds the attention window only: the K/V rows
+ *       of a stream are appended to a linear buffer of max_cache_frames rows through which the window
+ *       slides, so max_cache_frames bounds the encoder frames of the utterance (since the last reset,
+ *       or since the cache last became empty), not the window.  Refused with RNNT_ERR_SHAPE, with no
+ *       change of frames, caches or tokens (also by rnnt_encoder_chunks and rnnt_pool_chunk): a chunk
+ *       whose key window would end beyond row max_cache_frames, and offset < the present cache length.
  * K/V and conv caches live in the context.  The t' = ((T-3)/2+1-3)/2+1 output frames of every
  * stream are appended to the context's encoder-frame buffer; *frames_out receives t'. */
 int rnnt_encoder_chunk(rnnt_ctx* ctx, const float* fbank_dev, int32_t chunk_frames, int32_t offset,

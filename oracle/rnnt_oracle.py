@@ -14,7 +14,8 @@ tests/test_oracle_golden.py.
 
 Every function cites the reference file:line it follows (paths relative to the reference
 root).  All arithmetic is float32; tokens and indices are Python ints, beam scores are Python
-floats (double) exactly as in the reference.
+floats (double) exactly as in the reference.  The encoder functions are dtype-generic: on a float64
+state dict and input they run in float64 throughout (testing.encoder_stream_ref, the tests' reference).
 """
 import math
 from typing import Dict, List, Optional, Tuple
@@ -70,6 +71,11 @@ def feed_forward(sd: SD, p: str, x: Tensor) -> Tensor:
     return F.linear(h, sd[p + ".w_2.weight"], sd[p + ".w_2.bias"])
 
 
+def _f32_at_least(scores: Tensor) -> Tensor:
+    """The reference's scores.float() (attention.py:164,170); float64 scores (the tests' high-precision runs) stay float64."""
+    return scores if scores.dtype == torch.float64 else scores.float()
+
+
 def rel_attention(sd: SD, p: str, x: Tensor, pos_emb: Tensor,
                   k_cache: Optional[Tensor], v_cache: Optional[Tensor],
                   mask: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
@@ -96,9 +102,9 @@ def rel_attention(sd: SD, p: str, x: Tensor, pos_emb: Tensor,
     if mask is not None and mask.size(-1) > 0:                                   # :158-164
         m = mask.unsqueeze(-3).eq(0)[..., :scores.size(-1)]
         scores = scores.masked_fill(m, -float("inf"))
-        attn = torch.softmax(scores.float(), dim=-1).masked_fill(m, 0.0)
+        attn = torch.softmax(_f32_at_least(scores), dim=-1).masked_fill(m, 0.0)
     else:
-        attn = torch.softmax(scores.float(), dim=-1)                             # :170
+        attn = torch.softmax(_f32_at_least(scores), dim=-1)                      # :170
     o = torch.matmul(attn, v).transpose(1, 2).contiguous().view(B, t, D)          # :174-177
     return F.linear(o, sd[p + ".linear_out.weight"], sd[p + ".linear_out.bias"]), k, v
 
