@@ -165,11 +165,71 @@ int rnnt_load_packed(rnnt_ctx* ctx, const float* blob, int64_t n_floats, int32_t
     return RNNT_OK;
 }
 
+// f32 -> nearest f16 value (ties to even) as f32: the rounding of pack2_16<true>, on the host
+static inline float round_f16_host(float x) {
+    uint32_t u;
+    memcpy(&u, &x, 4);
+    const uint32_t sign = u & 0x80000000u;
+    uint32_t a = u & 0x7fffffffu;
+    if (a >= 0x7f800000u) return x;                      // inf / nan
+    if (a >= 0x477ff000u) a = 0x7f800000u;               // >= 65520 rounds to inf
+    else if (a < 0x38800000u) {                          // below 2^-14: f16 subnormal, quantum 2^-24 = the ulp of f32 in [0.5, 1)
+        float f;
+        memcpy(&f, &a, 4);
+        f = (f + 0.5f) - 0.5f;
+        memcpy(&a, &f, 4);
+    } else {
+        a += 0xfffu + ((a >> 13) & 1u);
+        a &= ~0x1fffu;
+    }
+    a |= sign;
+    float r;
+    memcpy(&r, &a, 4);
+    return r;
+}
+
+// The operand range of the f16x3 mode (include/rnnt_hip.h): every GEMM weight the mode carries as two f16 planes must survive the
+// split.  |w| > 65504 overflows the hi plane; the lo plane of any |w| < 2^-3 is an f16 subnormal, its error absolute (up to 2^-25)
+// instead of relative, so a tensor of small weights loses precision with every halving.  A tensor whose planes miss it by more than
+// RNNT_F16X3_SPLIT_LIMIT of its r.m.s. magnitude is refused by name: the mode never returns frames off the parity bar silently.
+// linear_pos, weight_ih and predictor.embed only feed tables that finalize derives in exact f32; conv.0 and the depthwise conv run in f32.
+static int f16x3_refusal(rnnt_ctx* ctx) {
+    static const char* const skip[] = {"depthwise_conv", "linear_pos", "pos_enc", "pos_bias", "embed.conv.0", "predictor.embed", "weight_ih"};
+    for (const auto& kv : ctx->host) {
+        const HostTensor& t = kv.second;
+        if (t.dims.size() < 2) continue;
+        bool skipped = false;
+        for (const char* s : skip) skipped = skipped || kv.first.find(s) != std::string::npos;
+        if (skipped) continue;
+        double err2 = 0.0, mag2 = 0.0;
+        float amax = 0.f;
+        for (const float x : t.data) {
+            const float hi = round_f16_host(x);
+            const float lo = round_f16_host(x - hi);
+            const double e = (double)x - ((double)hi + (double)lo);
+            err2 += e * e;
+            mag2 += (double)x * (double)x;
+            amax = fmaxf(amax, fabsf(x));
+        }
+        if (!(amax <= 65504.f))
+            return fail(ctx, RNNT_ERR_ARG, "rnnt_finalize_weights: f16x3 cannot carry %s: largest |w| %.4g is above 65504; use bf16x3 or fp32", kv.first.c_str(), (double)amax);
+        if (mag2 > 0.0 && sqrt(err2) > RNNT_F16X3_SPLIT_LIMIT * sqrt(mag2))
+            return fail(ctx, RNNT_ERR_ARG, "rnnt_finalize_weights: f16x3 cannot carry %s: its two f16 planes miss it by %.3g of its r.m.s. magnitude "
+                        "(largest |w| %.3g), above RNNT_F16X3_SPLIT_LIMIT %.3g; use bf16x3 or fp32", kv.first.c_str(), sqrt(err2 / mag2), (double)amax,
+                        (double)RNNT_F16X3_SPLIT_LIMIT);
+    }
+    return RNNT_OK;
+}
+
 int rnnt_finalize_weights(rnnt_ctx* ctx, int32_t numerics_mode, void* stream) {
     if (!ctx) return RNNT_ERR_ARG;
     if (numerics_mode != RNNT_NUMERICS_FP32 && numerics_mode != RNNT_NUMERICS_BF16X3 && numerics_mode != RNNT_NUMERICS_BF16 &&
         numerics_mode != RNNT_NUMERICS_F16X3)
         return fail(ctx, RNNT_ERR_ARG, "unsupported numerics mode %d", numerics_mode);
+    if (numerics_mode == RNNT_NUMERICS_F16X3) {
+        const int rc = f16x3_refusal(ctx);               // before anything of the context changes: a refused call leaves it as it was
+        if (rc) return rc;
+    }
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(ctx->cfg.device));
     // everything that caches pointers into the weight blob dies here: wavefront descriptor tables and the captured decode

@@ -30,9 +30,9 @@ int rnnt_joint(rnnt_ctx* ctx, const float* enc_dev, const float* pred_dev, int32
     // joint_lattice_rows takes e and p multiplied by 2 log2(e): tanh(e + p) = 1 - 2 / (exp2(e' + p') + 1) (rnnt_joint.hip.h)
     const float pre = rows_kernel ? JR_PRESCALE : 1.0f;
     GemmP ge = plain_gemm(enc_dev, D, ctx->wenc, D, ctx->benc, e, D, B * T, D, D, rows_kernel ? EPI_SCALE : EPI_BIAS, pre);
-    if ((rc = launch_gemm(ctx, s, &ge, 1))) return rc;
+    if ((rc = launch_gemm_f32(ctx, s, &ge, 1))) return rc;   // exact f32 in every mode: the tanh argument (host_launch.hip.inc)
     GemmP gp = plain_gemm(pred_dev, D, ctx->wpf, D, ctx->bpf, pp, D, B * U, D, D, rows_kernel ? EPI_SCALE : EPI_BIAS, pre);
-    if ((rc = launch_gemm(ctx, s, &gp, 1))) return rc;
+    if ((rc = launch_gemm_f32(ctx, s, &gp, 1))) return rc;
     if (rows_kernel) {
         // split-operand modes: ONE lattice kernel with the (log-)softmax on the accumulators (joint_lattice_rows, rnnt_joint.hip.h):
         // persistent 64-row workgroups, two per CU, over a dynamic row-tile queue

@@ -88,9 +88,9 @@ static int score_pick(rnnt_ctx* ctx, const char* what, const float* enc_dev, con
         float* e = ctx->scratch;
         float* pp = e + (size_t)B * T * D;
         GemmP ge = plain_gemm(enc_dev, D, ctx->wenc, D, ctx->benc, e, D, B * T, D, D, EPI_SCALE, JR_PRESCALE);
-        if ((rc = launch_gemm(ctx, s, &ge, 1))) return rc;
+        if ((rc = launch_gemm_f32(ctx, s, &ge, 1))) return rc;   // as rnnt_joint: the pick stays bitwise its lattice
         GemmP gp = plain_gemm(pred, D, ctx->wpf, D, ctx->bpf, pp, D, B * U1, D, D, EPI_SCALE, JR_PRESCALE);
-        if ((rc = launch_gemm(ctx, s, &gp, 1))) return rc;
+        if ((rc = launch_gemm_f32(ctx, s, &gp, 1))) return rc;
         ProfScope prof(ctx, s, TAG_SCORE_PICK);
         JointRP jp;
         memset(&jp, 0, sizeof(jp));

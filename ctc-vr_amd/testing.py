@@ -151,6 +151,41 @@ def greedy_margins(sd_np, enc_frames, tokens, blank=BLANK, device="cuda", n_step
 
 
 
+# ---- split-operand modes: the two 16-bit planes of an f32 operand (tests) -------------------------------------------------------
+def _round16(x32, kind):
+    """float32 -> the nearest bf16 / f16 value (ties to even), returned as float32"""
+    if kind == "f16":
+        with np.errstate(over="ignore"):
+            return x32.astype(np.float16).astype(np.float32)
+    assert kind == "bf16", kind
+    u = np.ascontiguousarray(x32).view(np.uint32).astype(np.uint64)
+    u = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16) << 16
+    return u.astype(np.uint32).view(np.float32).reshape(x32.shape)
+
+
+def split_planes_ref(x, kind):
+    """What a split-operand mode carries of an f32 operand: pack2_16 / split8_16 (rnnt_gemm_bf.hip.h) restated.  hi = round16(x),
+    lo = round16(x - hi) with the residual formed in float32 as the kernel forms it; returns hi + lo in float64.  kind: "bf16"
+    (8-bit planes, f32 exponent range) or "f16" (11-bit planes; a lo plane below 2^-14 is subnormal, its error absolute 2^-25;
+    |x| > 65504 overflows)."""
+    x32 = np.ascontiguousarray(np.asarray(x, np.float32))
+    with np.errstate(invalid="ignore"):                                    # an overflowed hi plane: inf, and a nan sum
+        hi = _round16(x32, kind)
+        lo = _round16(x32 - hi, kind)
+        return hi.astype(np.float64) + lo.astype(np.float64)
+
+
+def split_error_ref(x, kind):
+    """Relative root-mean-square error of split_planes_ref over a tensor: |hi + lo - x|_2 / |x|_2 (0 for an all-zero tensor, inf
+    where a plane overflows).  rnnt_finalize_weights compares this figure of each GEMM weight with RNNT_F16X3_SPLIT_LIMIT."""
+    x64 = np.asarray(x, np.float32).astype(np.float64)
+    got = split_planes_ref(x, kind)
+    if not np.isfinite(got).all():
+        return math.inf
+    den = float(np.sqrt((x64 * x64).sum()))
+    return float(np.sqrt(((got - x64) ** 2).sum())) / den if den > 0 else 0.0
+
+
 # ---- teacher-forced scoring: float64 restatements of the transducer likelihood (tests) -----------------------------------------
 def _logaddexp(a, b):
     mx, mn = (a, b) if a >= b else (b, a)
@@ -377,13 +412,17 @@ def prefix_merge_ref(hyps, top_lp, top_tok, blank, beam_size):
 _REF_SD = {}
 
 
-def ref_state_dict(np_sd, dtype=None):
-    """The state dict as torch CPU tensors with every floating-point entry cast to `dtype` (default float64), kept per (dict, dtype)."""
+def ref_state_dict(np_sd, dtype=None, share=None):
+    """The state dict as torch CPU tensors with every floating-point entry cast to `dtype` (default float64), kept per (dict, dtype).
+    share: another state dict; an entry that is the very same array there takes that dict's cast tensor instead of a copy of its
+    own (variants of one set of weights that differ in a few tensors)."""
     import torch
     dtype = dtype or torch.float64
     key = (id(np_sd), dtype)
     if key not in _REF_SD:
-        _REF_SD[key] = (np_sd, {k: torch.from_numpy(np.asarray(v)).to(dtype) if np.asarray(v).dtype.kind == "f" else torch.from_numpy(np.asarray(v))
+        shared = ref_state_dict(share, dtype) if share is not None else {}
+        _REF_SD[key] = (np_sd, {k: shared[k] if share is not None and share.get(k) is v
+                                else torch.from_numpy(np.asarray(v)).to(dtype) if np.asarray(v).dtype.kind == "f" else torch.from_numpy(np.asarray(v))
                                 for k, v in np_sd.items()})
     return _REF_SD[key][1]
 

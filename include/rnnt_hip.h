@@ -47,8 +47,20 @@ typedef enum {
 #define RNNT_NUMERICS_BF16X3 1 /* split bf16: x = hi + lo, hi*hi + hi*lo + lo*hi on v_mfma_f32_16x16x32_bf16, fp32        */
                                /* accumulate; ~1e-5 relative per product; parity-gated (tokens exact, logits <= 1e-3)      */
 #define RNNT_NUMERICS_BF16   2 /* plain bf16 operands, fp32 accumulate: perf mode, token-match rate reported, no parity   */
-#define RNNT_NUMERICS_F16X3  3 /* split f16 (11-bit planes): ~5e-7 relative per product, same cost as bf16x3; operands     */
-                               /* must stay below 65504 in magnitude (LayerNorm / activation outputs and weights do)       */
+#define RNNT_NUMERICS_F16X3  3 /* split f16 (11-bit planes): ~5e-7 relative per product, same cost as bf16x3; operand      */
+                               /* range below                                                                               */
+/* Operand range of each mode (operands: the weights and the activations a contraction reads; the planes carry no scale).
+ *   FP32, BF16X3, BF16: the f32 exponent range.  A bf16 plane has the f32 exponent, so the relative error of hi + lo (2^-17) does
+ *           not depend on the magnitude: a power-of-two rescale of an operand pair changes nothing (measured: DESIGN.md).
+ *   F16X3:  upper limit 65504 (the largest f16; above it the hi plane is inf).  Lower limit 2^-3 for full precision: the lo plane
+ *           of any |x| < 2^-3 lies below 2^-14, an f16 subnormal, and its error is absolute (up to 2^-25) instead of relative, so
+ *           the planes of a tensor of magnitude m miss it by about 2^-25 / m: 3e-7 at m = 1/16 (seeded weights), 1.8e-5 at 2^-10,
+ *           1.4e-4 at 2^-13; below 2^-25 nothing is left of the operand.  Activations of the encoder (LayerNorm outputs, O(1)) sit
+ *           inside the range.  Weights are checked: rnnt_finalize_weights(F16X3) returns RNNT_ERR_ARG, naming the tensor, for a GEMM
+ *           weight above 65504 or whose two planes miss it by more than RNNT_F16X3_SPLIT_LIMIT of its r.m.s. magnitude (a tensor
+ *           at the limit moves the encoder frames by about 4e-4 of the 1e-3 parity bar; measured: DESIGN.md).  Nothing is
+ *           launched or changed on the device by a refused call; BF16X3 or FP32 take the same loaded tensors. */
+#define RNNT_F16X3_SPLIT_LIMIT 1e-4
 
 typedef struct {
     int32_t max_streams;       /* B: streams (lock-stepped, or stream-pool slots) held by the context */
