@@ -112,7 +112,8 @@ void rnnt_destroy(rnnt_ctx* ctx) {
                   ctx->rg_fb, ctx->rg_xt, ctx->rg_ent, ctx->bd_tok, ctx->bd_len, ctx->bd_sc, ctx->bd_hs, ctx->bd_nh, ctx->bd_fend,
                   ctx->ps_pool[0], ctx->ps_pool[1], ctx->ps_tok, ctx->ps_len, ctx->ps_sc, ctx->ps_hs, ctx->ps_nh,
                   ctx->sc_f, ctx->sc_lat, ctx->sc_i, ctx->sc_nll, ctx->al_bp, ctx->al_out,
-                  ctx->pb_f, ctx->pb_i, ctx->pb_d, ctx->pb_out};
+                  ctx->pb_f, ctx->pb_i, ctx->pb_d, ctx->pb_out,
+                  ctx->cg_i, ctx->cg_d, ctx->cp_i, ctx->cp_d, ctx->cp_lp};
     for (void* q : wf)
         if (q) (void)hipFree(q);
     delete ctx;

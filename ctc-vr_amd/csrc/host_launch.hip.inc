@@ -33,7 +33,8 @@ enum { TAG_NONE = 0, TAG_CONV1 = 1, TAG_CONV2 = 2, TAG_EMBED = 3, TAG_FFN1 = 4, 
        TAG_CONV1_MINOR = 36, TAG_CONV2_MINOR = 37, TAG_EMBED_MINOR = 38,   // subsampling of the minor chunk classes of a whole-utterance call (the tail chunk)
        TAG_SCORE_PICK = 40, TAG_SCORE_ALPHA = 41,     // scoring: the picked lattice (fused kernel, or lattice + gather); transducer_alpha / ctc_alpha
        TAG_SCORE_VITERBI = 42,                        // forced alignment: transducer_viterbi / ctc_viterbi, back-trace included
-       TAG_PREFIX_STEP = 43, TAG_PREFIX_MERGE = 44 }; // prefix beam search: prefix_step / prefix_merge, one launch each per frame
+       TAG_PREFIX_STEP = 43, TAG_PREFIX_MERGE = 44,   // prefix beam search: prefix_step / prefix_merge, one launch each per frame
+       TAG_CTC_PREFIX = 45 };                         // CTC prefix beam search: ctc_prefix_search, one launch per call
 
 struct ProfScope {   // records a start/stop event pair around one launch when its site is selected
     rnnt_ctx* ctx; hipStream_t s; bool on;

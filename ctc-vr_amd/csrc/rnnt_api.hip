@@ -10,6 +10,7 @@
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <string>
 #include <algorithm>
@@ -69,6 +70,12 @@ struct SlotPos {
 };
 
 // the launches of a wavefront stage (rnnt_ctx::WfLaunch): the eight GEMM shape classes first (they index wf_run_stage's shape table)
+// ContextGraph of the CTC prefix beam search (api_ctc_prefix.hip.inc) as flat tables: node ids in creation order, root = 0
+struct CtxGraph {
+    std::vector<int> token, is_end, fail, output, off, ctok, cid;
+    std::vector<double> tscore, nscore, oscore;
+};
+
 enum WfType { WF_FFN1M, WF_FFN2M, WF_QKV, WF_OUT, WF_PW1, WF_PW2, WF_FFN1, WF_FFN2, WF_ATTN, WF_DW, WF_LN, WF_BLOCK_FRONT, WF_BLOCK_BACK };
 
 }  // namespace
@@ -240,6 +247,15 @@ struct rnnt_ctx {
     int* pb_i = nullptr;
     double *pb_d = nullptr, *pb_out = nullptr;
     size_t pb_f_cap = 0, pb_i_cap = 0, pb_d_cap = 0, pb_out_cap = 0;
+    // CTC prefix beam search (api_ctc_prefix.hip.inc): the context graph of rnnt_context_set (host tables, device ints / doubles) and
+    // the call's own grow-only buffers -- lengths, prefix and time arenas, packed results (cp_i), scores (cp_d), log-probabilities
+    // of rnnt_ctc_prefix_beam_decode (cp_lp)
+    CtxGraph cg;
+    bool cg_on = false;
+    int *cg_i = nullptr, *cp_i = nullptr;
+    double *cg_d = nullptr, *cp_d = nullptr;
+    float* cp_lp = nullptr;
+    size_t cg_i_cap = 0, cg_d_cap = 0, cp_i_cap = 0, cp_d_cap = 0, cp_lp_cap = 0;
     hipStream_t cap_stream = nullptr;          // stream-capture scratch stream
     struct DecGraph { int n_streams, k; hipGraphExec_t exec; };
     std::vector<DecGraph> dec_graphs;          // K greedy steps captured once per (n_streams, K)
@@ -265,4 +281,5 @@ extern "C" {
 #include "api_state.hip.inc"
 #include "api_pool.hip.inc"
 #include "api_prefix.hip.inc"
+#include "api_ctc_prefix.hip.inc"
 }  // extern "C"

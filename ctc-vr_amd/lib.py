@@ -57,6 +57,13 @@ SIGNATURES = {
     "rnnt_prefix_beam_decode": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, ctypes.c_float, ctypes.c_float, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rnnt_prefix_merge_host": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rnnt_prefix_merge_device": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rnnt_context_set": (c_i32, [c_vp, c_i32, c_vp, c_vp, ctypes.c_double]),
+    "rnnt_context_walk_host": (c_i32, [c_i32, c_vp, c_vp, ctypes.c_double, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "rnnt_context_dump_host": (c_i32, [c_i32, c_vp, c_vp, ctypes.c_double, c_i32p, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rnnt_ctc_prefix_beam_host": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, ctypes.c_double, c_i32, c_vp, c_vp, c_vp,
+                                          c_vp, c_vp, c_vp]),
+    "rnnt_ctc_prefix_beam_logprobs": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rnnt_ctc_prefix_beam_decode": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rnnt_transducer_nll": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "rnnt_ctc_nll": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "rnnt_transducer_align": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
@@ -163,6 +170,74 @@ def prefix_merge_host(hyps, top_lp, top_tok, blank, beam_size):
     if m < 0:
         raise RnntError(f"rnnt_prefix_merge_host: bad argument (status {m})", m)
     return out
+
+
+def _phrase_args(phrases):
+    """[[token, ...], ...] -> (n, lens int32, concatenated tokens int32) of the context-graph entry points."""
+    phrases = [list(map(int, ph)) for ph in (phrases or [])]
+    lens = np.array([len(ph) for ph in phrases] or [0], np.int32)
+    toks = np.array([t for ph in phrases for t in ph] or [0], np.int32)
+    return len(phrases), lens, toks
+
+
+def context_walk_host(phrases, context_score, tokens):
+    """rnnt_context_walk_host (no context, no GPU): feed `tokens` through ContextGraph.forward_one_step from the root of the graph
+    over `phrases` -> (step scores float64 [n], node ids int32 [n], finalize's score of the last state)."""
+    n, pl, pt = _phrase_args(phrases)
+    tk = np.array(list(tokens) or [0], np.int32)
+    m = len(tokens)
+    sc, st, fin = np.zeros(max(m, 1), np.float64), np.zeros(max(m, 1), np.int32), ctypes.c_double(0.0)
+    rc = load().rnnt_context_walk_host(n, _np_ptr(pl), _np_ptr(pt), float(context_score), m, _np_ptr(tk), _np_ptr(sc), _np_ptr(st), ctypes.byref(fin))
+    if rc != 0:
+        raise RnntError(f"rnnt_context_walk_host: bad argument (status {rc})", rc)
+    return sc[:m], st[:m], fin.value
+
+
+def context_dump_host(phrases, context_score):
+    """rnnt_context_dump_host: the node tables of the graph over `phrases` in node-id (creation) order -> dict of token, node_score,
+    output_score, is_end, fail, output (-1: none)."""
+    n, pl, pt = _phrase_args(phrases)
+    cap = 1 + int(pl.sum())
+    nn = c_i32(0)
+    tok, end, fl, out = (np.zeros(cap, np.int32) for _ in range(4))
+    ns, os_ = np.zeros(cap, np.float64), np.zeros(cap, np.float64)
+    rc = load().rnnt_context_dump_host(n, _np_ptr(pl), _np_ptr(pt), float(context_score), ctypes.byref(nn), _np_ptr(tok), _np_ptr(ns), _np_ptr(os_),
+                                       _np_ptr(end), _np_ptr(fl), _np_ptr(out))
+    if rc != 0:
+        raise RnntError(f"rnnt_context_dump_host: bad argument (status {rc})", rc)
+    k = nn.value
+    return {"token": tok[:k], "node_score": ns[:k], "output_score": os_[:k], "is_end": end[:k], "fail": fl[:k], "output": out[:k]}
+
+
+def _ctc_prefix_out(B, beam, cap):
+    w = max(beam, 1)
+    return (np.zeros(B, np.int32), np.zeros((B, w), np.int32), np.zeros((B, w, cap), np.int32), np.zeros((B, w, cap), np.int32),
+            np.zeros((B, w), np.float64), np.zeros((B, w), np.float64))
+
+
+def _ctc_prefix_hyps(out):
+    """The raw result arrays -> per utterance [(tokens, score, times, context score)] in the order the search returns."""
+    nh, lens, toks, times, sc, cs = out
+    return [[(toks[b, i, :lens[b, i]].tolist(), float(sc[b, i]), times[b, i, :lens[b, i]].tolist(), float(cs[b, i])) for i in range(nh[b])]
+            for b in range(len(nh))]
+
+
+def ctc_prefix_beam_host(lp, enc_lens, blank, beam_size, phrases=None, context_score=0.0, raw=False):
+    """rnnt_ctc_prefix_beam_host (no context, no GPU): WeNet's ctc_prefix_beam_search over lp [B, T, vocab] float32, row b over its
+    first enc_lens[b] frames, biased by the graph over `phrases` when given.  Per utterance [(tokens, score, times, context score)];
+    raw: also the result arrays (n_hyp, lens, tokens, times, scores, context scores) as the C call filled them."""
+    lp = np.ascontiguousarray(lp, np.float32)
+    B, T, V = lp.shape
+    el = np.ascontiguousarray(enc_lens, np.int32)
+    assert el.size == B
+    n, pl, pt = _phrase_args(phrases)
+    cap = max(int(el.max(initial=0)), 1)
+    out = _ctc_prefix_out(B, beam_size, cap)
+    rc = load().rnnt_ctc_prefix_beam_host(_np_ptr(lp), _np_ptr(el), B, T, V, blank, beam_size, n, _np_ptr(pl), _np_ptr(pt), float(context_score), cap,
+                                          *[_np_ptr(a) for a in out])
+    if rc != 0:
+        raise RnntError(f"rnnt_ctc_prefix_beam_host: bad argument (status {rc})", rc)
+    return (_ctc_prefix_hyps(out), out) if raw else _ctc_prefix_hyps(out)
 
 
 class RnntEngine:
@@ -473,6 +548,30 @@ class RnntEngine:
                                                    _np_ptr(c) if want_states else None, stream), "rnnt_prefix_beam_decode")
         hyps = [[(toks[b, i, :lens[b, i]].tolist(), float(sc[b, i])) for i in range(nh[b])] for b in range(B)]
         return (hyps, h, c) if want_states else hyps
+
+    # ---- CTC prefix beam search with contextual biasing ------------------------------------------
+    def context_set(self, phrases, context_score=6.0):
+        """rnnt_context_set: build and upload the context graph over phrases [[token, ...], ...]; an empty list clears it."""
+        n, pl, pt = _phrase_args(phrases)
+        self._chk(self.lib.rnnt_context_set(self.ctx, n, _np_ptr(pl), _np_ptr(pt), float(context_score)), "rnnt_context_set")
+
+    def _ctc_prefix(self, fn, name, dev_ptr, enc_lens, B, T, beam_size, use_context, raw, stream):
+        el = np.ascontiguousarray(enc_lens, np.int32)
+        assert el.size == B
+        out = _ctc_prefix_out(B, beam_size, max(int(el.max(initial=0)), 1))
+        self._chk(fn(self.ctx, dev_ptr, _np_ptr(el), B, T, beam_size, 1 if use_context else 0, out[2].shape[2], *[_np_ptr(a) for a in out], stream), name)
+        return (_ctc_prefix_hyps(out), out) if raw else _ctc_prefix_hyps(out)
+
+    def ctc_prefix_beam_logprobs(self, lp_ptr, enc_lens, B, T, beam_size=10, use_context=False, raw=False, stream=None):
+        """rnnt_ctc_prefix_beam_logprobs: ctc_prefix_beam_search over log-probabilities [B, T, vocab] on the device, one launch.  Per
+        utterance [(tokens, score, times, context score)] in the reference's order; raw as in ctc_prefix_beam_host."""
+        return self._ctc_prefix(self.lib.rnnt_ctc_prefix_beam_logprobs, "rnnt_ctc_prefix_beam_logprobs", lp_ptr, enc_lens, B, T, beam_size, use_context,
+                                raw, stream)
+
+    def ctc_prefix_beam_decode(self, enc_ptr, enc_lens, B, T, beam_size=10, use_context=False, raw=False, stream=None):
+        """rnnt_ctc_prefix_beam_decode: the same over encoder frames [B, T, 256] (rnnt_ctc_logprobs first)."""
+        return self._ctc_prefix(self.lib.rnnt_ctc_prefix_beam_decode, "rnnt_ctc_prefix_beam_decode", enc_ptr, enc_lens, B, T, beam_size, use_context,
+                                raw, stream)
 
     def prefix_merge_device(self, hyps, top_lp, top_tok, blank, beam_size, stream=None):
         """rnnt_prefix_merge_device: prefix_merge_host's arguments and results through one prefix_merge launch."""

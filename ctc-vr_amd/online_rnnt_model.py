@@ -127,6 +127,15 @@ def timestamps_from_peaks(peaks, max_duration, frame_rate=0.04, max_token_durati
     return times
 
 
+class ContextBias:
+    """Hot words for OnlineRNNTModel.ctc_prefix_beam_search: phrases as lists of token ids (no blank, no empty phrase) and the bonus
+    per matched token, as the reference's ContextGraph(context_score=6.0) takes them after tokenisation."""
+
+    def __init__(self, phrases: List[List[int]], context_score: float = 6.0):
+        self.phrases = [[int(t) for t in ph] for ph in phrases]
+        self.context_score = float(context_score)
+
+
 class _EncoderView:
     """Attribute surface the reference's callers read: encoder.static_chunk_size and
     encoder.embed.subsampling_rate (model/online_rnnt_model.py:283-287)."""
@@ -166,6 +175,7 @@ class OnlineRNNTModel:
                                   n_steps=10, device=device, max_beam=max_beam)
         self.numerics = numerics          # None -> $RNNT_NUMERICS or "fp32" (lib.numerics_id)
         self._loaded = False
+        self._context_bias = None         # the ContextBias whose graph the context holds (ctc_prefix_beam_search)
         self._chunks_done = None          # None = reset_streaming_cache not called yet (attributes are None, :138-143)
         self._tok_count = 0
         self.streaming_beam_hypotheses = None
@@ -557,6 +567,32 @@ class OnlineRNNTModel:
         hyps, h, c = self._engine.prefix_beam_decode(enc.data_ptr(), enc_lens, B, tq, beam_size, ctc_weight, transducer_weight, True, s)
         self._prefix_states_batch = [(torch.from_numpy(h[b, :len(hyps[b])].copy()), torch.from_numpy(c[b, :len(hyps[b])].copy())) for b in range(B)]
         return hyps
+
+    def ctc_prefix_beam_search(self, audios: torch.Tensor, audio_lens: torch.Tensor, beam_size: int = 10, context: Optional["ContextBias"] = None):
+        """WeNet's ctc_prefix_beam_search (wenet/transformer/search.py:125-247) on the CTC head over the deterministic full-context
+        encoder, for a padded batch audios [B, T, 80]: one rnnt_encoder_full call and one rnnt_ctc_prefix_beam_decode call (the CTC
+        log-probabilities, then ONE launch that walks every utterance's own valid frames).  context: a ContextBias whose phrases
+        boost the hypotheses that match them (wenet/utils/context_graph.py); None: no biasing.  Equal values of a frame are taken
+        lower index first (torch.topk leaves that order open).
+        Returns per utterance [(tokens, score, times)] in the reference's order (nbest, nbest_scores, nbest_times): best first by
+        score + running context score; with a context the returned scores carry finalize's correction and need not descend.
+        Invalidates the streaming state."""
+        self._require_loaded()
+        B, T = audios.size(0), audios.size(1)
+        x = audios.to(self.device, torch.float32).contiguous()
+        lens = audio_lens.detach().cpu().numpy().astype(np.int32).reshape(B)
+        tq = ((T - 3) // 2 + 1 - 3) // 2 + 1
+        s = _stream_ptr()
+        enc = torch.empty(B, tq, 256, device=self.device)
+        self._engine.encoder_full(x.data_ptr(), lens, B, T, enc.data_ptr(), s)
+        self._chunks_done = None
+        n1 = np.maximum(0, (np.minimum(lens, T) - 1) // 2)         # valid frames after masks[:, :, 2::2][:, :, 2::2]
+        enc_lens = np.maximum(0, (n1 - 1) // 2).astype(np.int32)
+        if context is not self._context_bias:                       # the graph lives in the context until another one replaces it
+            self._engine.context_set(context.phrases if context is not None else [], context.context_score if context is not None else 0.0)
+            self._context_bias = context
+        hyps = self._engine.ctc_prefix_beam_decode(enc.data_ptr(), enc_lens, B, tq, beam_size, context is not None, False, s)
+        return [[(tok, score, times) for tok, score, times, _ in row] for row in hyps]
 
     def greedy_search_full(self, audios, audio_lens, n_steps: int = 64):
         """basic_greedy_search over the deterministic full-context encoder; audios [B,T,80] with B <= max_streams,

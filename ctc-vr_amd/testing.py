@@ -408,6 +408,225 @@ def prefix_merge_ref(hyps, top_lp, top_tok, blank, beam_size):
     return [tuple(f) for f in fused[:beam_size]]
 
 
+# ---- CTC prefix beam search with a context graph (wenet/transformer/search.py:125-247, wenet/utils/context_graph.py) ------------
+class context_graph_ref:
+    """The Aho-Corasick automaton of context_graph.py:144-210 over phrases [[token, ...], ...] as flat Python lists indexed by node
+    id (creation order, root = 0): token (-1 at the root), token_score, node_score (= depth * context_score by repeated addition),
+    output_score, is_end, next (dict token -> child), fail, output (-1: none).  is_end is decided when a node is created, so a
+    phrase that ends on a node an earlier phrase created does not mark it.  The fail arc of a node over `token` starts from its
+    parent's fail arc f: f's child if there is one; else step to f's fail arc, and while that node has no child over the token keep
+    stepping, stopping right AFTER a step that lands on the root; then take the child if there is one.  The output arc is the first
+    is_end node on the fail chain (none once the chain reaches the root) and its output_score is added to the node's."""
+
+    def __init__(self, phrases, context_score):
+        self.context_score = float(context_score)
+        self.token, self.token_score, self.node_score, self.output_score, self.is_end, self.next = [-1], [0.0], [0.0], [0.0], [False], [{}]
+        for ph in phrases:
+            node = 0
+            for i, tok in enumerate(ph):
+                tok = int(tok)
+                if tok not in self.next[node]:
+                    end = i == len(ph) - 1
+                    ns = self.node_score[node] + self.context_score
+                    self.next[node][tok] = len(self.token)
+                    self.token.append(tok); self.token_score.append(self.context_score); self.node_score.append(ns)
+                    self.output_score.append(ns if end else 0.0); self.is_end.append(end); self.next.append({})
+                node = self.next[node][tok]
+        n = len(self.token)
+        self.fail, self.output = [0] * n, [-1] * n
+        queue = list(self.next[0].values())
+        while queue:
+            cur = queue.pop(0)
+            for tok, node in self.next[cur].items():
+                f = self.fail[cur]
+                if tok in self.next[f]:
+                    f = self.next[f][tok]
+                else:
+                    f = self.fail[f]
+                    while tok not in self.next[f]:
+                        f = self.fail[f]
+                        if f == 0:
+                            break
+                    f = self.next[f].get(tok, f)
+                self.fail[node] = f
+                out = f
+                while out >= 0 and not self.is_end[out]:
+                    out = self.fail[out]
+                    if out == 0:
+                        out = -1
+                self.output[node] = out
+                if out >= 0:
+                    self.output_score[node] += self.output_score[out]
+                queue.append(node)
+
+    def step(self, state, tok):
+        """forward_one_step (:212-247): (score of the step, node it lands in)."""
+        if tok in self.next[state]:
+            node = self.next[state][tok]
+            score = self.token_score[node]
+        else:
+            node = self.fail[state]
+            while tok not in self.next[node]:
+                node = self.fail[node]
+                if node == 0:
+                    break
+            node = self.next[node].get(tok, node)
+            score = self.node_score[node] - self.node_score[state]
+        return score + self.output_score[node], node
+
+    def finalize(self, state):
+        return -self.node_score[state]
+
+    def walk(self, tokens):
+        """tokens from the root -> (step scores, node ids, finalize's score of the last state)."""
+        state, scores, states = 0, [], []
+        for tok in tokens:
+            sc, state = self.step(state, int(tok))
+            scores.append(sc); states.append(state)
+        return scores, states, self.finalize(state)
+
+
+def _log_add2(a, b):
+    if a == -math.inf and b == -math.inf:
+        return -math.inf
+    m = max(a, b)
+    return m + math.log(math.exp(a - m) + math.exp(b - m))
+
+
+class _PrefixEntry:
+    __slots__ = ("s", "ns", "v_s", "v_ns", "cur", "times_s", "times_ns", "ctx_state", "ctx_score", "touched")
+
+    def __init__(self):
+        self.s = self.ns = self.v_s = self.v_ns = self.cur = -math.inf
+        self.times_s, self.times_ns, self.ctx_state, self.ctx_score, self.touched = [], [], 0, 0.0, False
+
+    def score(self):
+        return _log_add2(self.s, self.ns)
+
+    def viterbi(self):
+        return self.v_s if self.v_s > self.v_ns else self.v_ns
+
+    def times(self):
+        return self.times_s if self.v_s > self.v_ns else self.times_ns
+
+    def total(self):
+        return self.score() + self.ctx_score
+
+
+def _gap_stats(stats, vals, beam_size, name):
+    for i, (a, b) in enumerate(zip(vals, vals[1:])):
+        if a == b == -math.inf:
+            stats["inf_ties"] = stats.get("inf_ties", 0) + 1
+        elif a == b:
+            stats[name] = stats.get(name, 0) + 1
+            if i == beam_size - 1:
+                stats["cut_ties"] = stats.get("cut_ties", 0) + 1
+        elif a > -math.inf:
+            stats["nonzero_gap"] = min(stats.get("nonzero_gap", math.inf), a - b)
+
+
+def ctc_prefix_beam_ref(lp, length, blank, beam_size, graph=None, stats=None):
+    """WeNet's ctc_prefix_beam_search (search.py:139-236) for ONE utterance in plain Python: lp [T, vocab] float32, frames
+    [0, length), graph a context_graph_ref or None.  Per frame: the top beam_size of the row, value descending and lower index first
+    on equal values; outer loop over those tokens, inner over the hypotheses in their order; blank / repeat / other as the
+    reference writes them (v_s and times_s ASSIGNED by a blank; strict `<` in the Viterbi updates; the repeat's times_ns[-1] = t
+    only when the token's value also exceeds the entry's current one); an entry's context comes from the first contribution that
+    touches it, and since it is a function of the token string alone every later contribution must agree, which is asserted; sort
+    by score + context score descending, stable over first insertion, truncate.  At the end a graph REPLACES every context score
+    by finalize's and the list is not re-sorted.
+    Returns (hyps, prune_gap, top_gap): hyps [(tokens, score, times, context score)]; prune_gap the smallest difference between
+    consecutive total scores of any frame's sorted entries, top_gap between consecutive values of any frame's top beam_size + 1
+    (inf where there is nothing to compare).  stats: a dict whose "stale_times" counts the repeats that raised v_ns and kept the
+    entry's times_ns, "both_live" the frames in which some hypothesis P and a hypothesis P + u were both live, "top_ties" / "prune_ties"
+    the exact ties between consecutive finite top values / total scores ("inf_ties": between two -inf), "cut_ties" those of them that sit on the truncation boundary, and
+    "nonzero_gap" the smallest difference that is not an exact tie (of either kind), and "rebuilt_parent" the extensions P + u that
+    meet a live hypothesis P + u whose parent was a DIFFERENT incarnation of P (P was pruned and came back while P + u stayed
+    live): an implementation that names prefixes by the node that created them must still merge the two."""
+    lp = np.asarray(lp, np.float32)
+    start = _PrefixEntry()
+    start.s, start.v_s, start.v_ns = 0.0, 0.0, 0.0
+    cur = [((), start)]
+    prune_gap = top_gap = math.inf
+    born = {(): 0}                      # stats only: the frame at which the live prefix was (last) created
+    parent_born = {}                    # ... and the birth frame of the parent it was created from
+
+    def context(entry, src, tok):
+        if graph is None:
+            return
+        state, score = src.ctx_state, src.ctx_score
+        if tok is not None:
+            sc, state = graph.step(src.ctx_state, tok)
+            score = src.ctx_score + sc
+        if entry.touched:
+            assert entry.ctx_state == state and entry.ctx_score == score, "the context is a function of the token string alone"
+        else:
+            entry.ctx_state, entry.ctx_score, entry.touched = state, score, True
+
+    for t in range(int(length)):
+        row = lp[t] + np.float32(0.0)
+        order = sorted(range(row.size), key=lambda v: (-row[v], v))
+        vals = [float(row[v]) for v in order[:beam_size + 1]]
+        for a, b in zip(vals, vals[1:]):
+            if a > -math.inf:
+                top_gap = min(top_gap, a - b)
+        if stats is not None:
+            _gap_stats(stats, vals, beam_size, "top_ties")
+        nxt = {}
+        if stats is not None and any(q[:-1] == pfx for q, _ in cur for pfx, _ in cur if q):
+            stats["both_live"] = stats.get("both_live", 0) + 1
+        for u in order[:beam_size]:
+            prob = float(row[u])
+            for prefix, h in cur:
+                last = prefix[-1] if prefix else None
+                if u == blank:
+                    e = nxt.setdefault(prefix, _PrefixEntry())
+                    e.s = _log_add2(e.s, h.score() + prob)
+                    e.v_s = h.viterbi() + prob
+                    e.times_s = list(h.times())
+                    context(e, h, None)
+                    continue
+                if u == last:
+                    e = nxt.setdefault(prefix, _PrefixEntry())
+                    e.ns = _log_add2(e.ns, h.ns + prob)
+                    if e.v_ns < h.v_ns + prob:
+                        e.v_ns = h.v_ns + prob
+                        if e.cur < prob:
+                            e.cur = prob
+                            e.times_ns = list(h.times_ns)
+                            e.times_ns[-1] = t
+                        elif stats is not None:
+                            stats["stale_times"] = stats.get("stale_times", 0) + 1
+                    context(e, h, None)
+                    add, vit, tm = h.s, h.v_s, h.times_s
+                else:
+                    add, vit, tm = h.score(), h.viterbi(), h.times()
+                if stats is not None and prefix + (u,) in born and parent_born[prefix + (u,)] != born[prefix]:
+                    stats["rebuilt_parent"] = stats.get("rebuilt_parent", 0) + 1
+                e = nxt.setdefault(prefix + (u,), _PrefixEntry())
+                e.ns = _log_add2(e.ns, add + prob)
+                if e.v_ns < vit + prob:
+                    e.v_ns, e.cur = vit + prob, prob
+                    e.times_ns = list(tm) + [t]
+                context(e, h, u)
+        ranked = sorted(nxt.items(), key=lambda kv: kv[1].total(), reverse=True)
+        tot = [e.total() for _, e in ranked]
+        for a, b in zip(tot, tot[1:]):
+            if a > -math.inf:
+                prune_gap = min(prune_gap, a - b)
+        if stats is not None:
+            _gap_stats(stats, tot, beam_size, "prune_ties")
+        cur = ranked[:beam_size]
+        if stats is not None:
+            old = born
+            born = {q: old.get(q, t + 1) for q, _ in cur}
+            parent_born = {q: parent_born[q] if q in old else old[q[:-1]] for q, _ in cur if q}
+    out = []
+    for prefix, h in cur:
+        cs = graph.finalize(h.ctx_state) if graph is not None else 0.0
+        out.append((list(prefix), h.score() + cs, list(h.times()), cs))
+    return out, prune_gap, top_gap
+
+
 # ---- streaming encoder: one stream through the oracle's forward_chunk under any window policy (tests) ---------------------------
 _REF_SD = {}
 

@@ -358,6 +358,60 @@ int rnnt_prefix_merge_device(rnnt_ctx* ctx, int32_t n_hyp, const int32_t* hyp_le
                              int32_t* out_len, int32_t* out_tokens, double* out_score, int32_t* out_src_row, int32_t* out_src_slot,
                              void* stream);
 
+/* -- CTC prefix beam search with contextual biasing: WeNet's ctc_prefix_beam_search (wenet/transformer/search.py:125-247) --------- */
+/* The context graph ("hot words") of wenet/utils/context_graph.py:144-210 over n_phrases token lists (phrase_tokens_host holds them
+ * concatenated, phrase_lens_host their lengths), built on the host and uploaded; n_phrases == 0 clears it.  Trie in phrase order,
+ * node ids in creation order (root = 0); every node carries token_score, node_score (depth x context_score by repeated addition),
+ * output_score and is_end (decided when the node is created); fail and output arcs from the reference's breadth-first fill, its
+ * quirks included.  All scores f64.  Device form: flat node arrays and a CSR of (token, child) sorted by token per node.
+ * Refusals, RNNT_ERR_ARG: an empty phrase, a token outside [0, vocab_size), the blank inside a phrase, more than 4096 nodes. */
+int rnnt_context_set(rnnt_ctx* ctx, int32_t n_phrases, const int32_t* phrase_lens_host, const int32_t* phrase_tokens_host,
+                     double context_score);
+/* Test seams of the graph (no context, no GPU; tokens need only be >= 0).  walk: feeds tokens [n_tokens] through forward_one_step
+ * (:212-247) from the root; step_score_out / state_out [n_tokens] receive every step's score and the node it lands in,
+ * *finalize_out what finalize (:249-265) returns for the last state.  dump: the node tables in node-id order (each pointer may be
+ * NULL; room for 1 + the total phrase length): token (-1 at the root), node_score, output_score, is_end, fail id, output id (-1: none). */
+int rnnt_context_walk_host(int32_t n_phrases, const int32_t* phrase_lens, const int32_t* phrase_tokens, double context_score,
+                           int32_t n_tokens, const int32_t* tokens, double* step_score_out, int32_t* state_out, double* finalize_out);
+int rnnt_context_dump_host(int32_t n_phrases, const int32_t* phrase_lens, const int32_t* phrase_tokens, double context_score,
+                           int32_t* n_nodes_out, int32_t* token_out, double* node_score_out, double* output_score_out,
+                           int32_t* is_end_out, int32_t* fail_out, int32_t* output_out);
+/* The search over log-probabilities lp_dev [B, T, vocab] f32 already on the device (any context; weights are not needed), row b over
+ * frames [0, enc_lens_host[b]), in ONE launch: ctc_prefix_search, one workgroup per utterance with the frame loop inside.  Per row
+ * the semantics of search.py:139-236:
+ *   start       the empty prefix with s = 0, ns = -inf, v_s = 0, v_ns = 0 (sic), context state root, context score 0
+ *   first prune top-beam_size of the frame over the whole vocabulary, blank included: value descending and, on equal values, the
+ *               lower index first (torch.topk leaves that order open; this is the order the library defines)
+ *   expansion   outer loop over those tokens, inner over the hypotheses in their order, the value widened to f64; blank, repeat of
+ *               the last token and other as written: v_s and times_s are ASSIGNED by a blank, the Viterbi updates use strict <, the
+ *               repeat's times_ns[-1] = t happens only when cur_token_prob < prob as well; log_add is the two-argument form in f64
+ *               (-inf if both are, else max + log(sum exp)); an entry takes its context from the first contribution that touches it
+ *   second prune sort by score() + context score descending, stable over first insertion, truncate to beam_size
+ *   end         with a graph every survivor's context score is REPLACED by finalize's -node_score (sic) and the list is NOT
+ *               re-sorted; score = log_add(s, ns) + that; times = times_s if v_s > v_ns else times_ns
+ * use_context == 0 (or no graph): context scores are 0.  Results in that order: n_hyp_host [B]; lens_host [B, beam_size];
+ * tokens_host / times_host [B, beam_size, cap_tokens] (no leading blank: the reference's prefixes have none); scores_host
+ * [B, beam_size] f64; ctx_scores_host [B, beam_size] f64 or NULL.  Entries of hypotheses i >= n_hyp_host[b] and of a row beyond its
+ * length are zero (a times list shorter than its tokens, possible only with -inf values, is zero-filled).  A row of length 0
+ * returns the one empty hypothesis with score 0.  Touches only its own grow-only buffers.
+ * Refusals, decided on the host before the launch: null pointer, B < 1, a length outside [0, T], beam_size outside
+ * [1, min(16, vocab_size)], vocab_size > 512, cap_tokens below the longest length: RNNT_ERR_ARG; use_context with no graph set:
+ * RNNT_ERR_STATE. */
+int rnnt_ctc_prefix_beam_logprobs(rnnt_ctx* ctx, const float* lp_dev, const int32_t* enc_lens_host, int32_t B, int32_t T,
+                                  int32_t beam_size, int32_t use_context, int32_t cap_tokens, int32_t* n_hyp_host, int32_t* lens_host,
+                                  int32_t* tokens_host, int32_t* times_host, double* scores_host, double* ctx_scores_host, void* stream);
+/* The same over encoder frames enc_dev [B, T, 256]: rnnt_ctc_logprobs over the B*T frames first.  RNNT_ERR_STATE without
+ * ctc_head.ctc_lo.* or before rnnt_finalize_weights. */
+int rnnt_ctc_prefix_beam_decode(rnnt_ctx* ctx, const float* enc_dev, const int32_t* enc_lens_host, int32_t B, int32_t T,
+                                int32_t beam_size, int32_t use_context, int32_t cap_tokens, int32_t* n_hyp_host, int32_t* lens_host,
+                                int32_t* tokens_host, int32_t* times_host, double* scores_host, double* ctx_scores_host, void* stream);
+/* The same search as a pure C++ function (no context, no GPU): lp_host [B, T, vocab], the graph passed as phrases (n_phrases == 0:
+ * none).  The CPU seam the device path is compared against: tokens, times and order exact. */
+int rnnt_ctc_prefix_beam_host(const float* lp_host, const int32_t* enc_lens_host, int32_t B, int32_t T, int32_t vocab, int32_t blank,
+                              int32_t beam_size, int32_t n_phrases, const int32_t* phrase_lens, const int32_t* phrase_tokens,
+                              double context_score, int32_t cap_tokens, int32_t* n_hyp_host, int32_t* lens_host, int32_t* tokens_host,
+                              int32_t* times_host, double* scores_host, double* ctx_scores_host);
+
 /* -- teacher-forced scoring: how likely is a GIVEN transcript (forward only, no gradients) ----------------------------------- */
 /* Transducer negative log-likelihood: the RNN-T term of the reference's forward with texts (model/online_rnnt_model.py:240-255),
  * torchaudio.functional.rnnt_loss(reduction="none") -- minus the log of the sum over all monotonic alignments; its `clamp` only
@@ -456,7 +510,8 @@ const float* rnnt_enc_frames_dev(rnnt_ctx* ctx, int32_t* frames_out, int32_t* st
  * 7 attention, 8 attention out-proj, 9 pointwise_conv1+GLU, 10 depthwise conv, 11 pointwise_conv2, 13 joint enc
  * projection, 20 LSTM cell, 21 predictor projection, 22 joint pred_ffn+tanh, 23 joint ffn_out, 40 the picked lattice of
  * rnnt_transducer_nll, 41 its alpha recursion (and rnnt_ctc_nll's), 42 the Viterbi launch of the rnnt_*_align calls, 43 prefix_step
- * and 44 prefix_merge of rnnt_prefix_beam_decode (one launch each per frame).
+ * and 44 prefix_merge of rnnt_prefix_beam_decode (one launch each per frame), 45 ctc_prefix_search of the rnnt_ctc_prefix_beam_*
+ * calls (one launch per call).
  * rnnt_profile_end synchronises the recorded events and returns the summed kernel time and launch count. */
 int rnnt_profile_begin(rnnt_ctx* ctx, int32_t tag);
 int rnnt_profile_end(rnnt_ctx* ctx, double* total_ms, int64_t* n_launches);
