@@ -241,12 +241,12 @@ namespace {
 int beam_dev_buffers(rnnt_ctx* ctx, size_t lcap) {
     const size_t R = ctx->max_rows, Bm = ctx->cfg.max_streams;
     int rc;
-    if (!ctx->bd_len && (rc = dmalloc(ctx, &ctx->bd_len, 2 * R))) return rc;
-    if (!ctx->bd_sc && (rc = dmalloc(ctx, &ctx->bd_sc, 2 * R))) return rc;
-    if (!ctx->bd_hs && (rc = dmalloc(ctx, &ctx->bd_hs, 2 * R))) return rc;
-    if (!ctx->bd_nh && (rc = dmalloc(ctx, &ctx->bd_nh, Bm))) return rc;
-    if (!ctx->bd_fend && (rc = dmalloc(ctx, &ctx->bd_fend, Bm))) return rc;
-    return grow(ctx, &ctx->bd_tok, &ctx->bd_tok_cap, 2 * R * lcap);
+    if ((rc = reserve(ctx, ctx->bd_len, 2 * R))) return rc;
+    if ((rc = reserve(ctx, ctx->bd_sc, 2 * R))) return rc;
+    if ((rc = reserve(ctx, ctx->bd_hs, 2 * R))) return rc;
+    if ((rc = reserve(ctx, ctx->bd_nh, Bm))) return rc;
+    if ((rc = reserve(ctx, ctx->bd_fend, Bm))) return rc;
+    return reserve(ctx, ctx->bd_tok, 2 * R * lcap);
 }
 
 unsigned long long beam_hash(const int* t, size_t n) {

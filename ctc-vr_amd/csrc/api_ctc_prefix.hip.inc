@@ -207,8 +207,8 @@ int rnnt_context_set(rnnt_ctx* ctx, int32_t n_phrases, const int32_t* phrase_len
     int rc = ctx_graph_build(n_phrases, phrase_lens_host, phrase_tokens_host, context_score, ctx->cfg.vocab_size, ctx->cfg.blank_id, g, err);
     if (rc) return fail(ctx, rc, "rnnt_context_set: %s", err.c_str());
     const size_t n = g.token.size(), m = g.ctok.size();
-    if ((rc = grow(ctx, &ctx->cg_i, &ctx->cg_i_cap, 2 * n + 1 + 2 * m))) return rc;
-    if ((rc = grow(ctx, &ctx->cg_d, &ctx->cg_d_cap, 3 * n))) return rc;
+    if ((rc = reserve(ctx, ctx->cg_i, 2 * n + 1 + 2 * m))) return rc;
+    if ((rc = reserve(ctx, ctx->cg_d, 3 * n))) return rc;
     HIPCHK(hipDeviceSynchronize());                                  // a search still reading the previous tables
     std::vector<int> hi;
     hi.insert(hi.end(), g.fail.begin(), g.fail.end());
@@ -303,9 +303,23 @@ int rnnt_ctc_prefix_beam_host(const float* lp_host, const int32_t* enc_lens_host
     return RNNT_OK;
 }
 
+// The block of a search's results that is downloaded in one copy, on the device or in its host copy: n_hyp [B] | lens [R] |
+// tokens [R][lcap] | times [R][lcap]; total: its ints.
+struct CpOut { int *nh, *len, *tok, *time; size_t total; };
+static CpOut cp_out(Carve<int>& c, size_t B, size_t R, size_t lcap) {
+    CpOut o;
+    const size_t at = c.off;
+    o.nh = c.take(B);
+    o.len = c.take(R);
+    o.tok = c.take(R * lcap);
+    o.time = c.take(R * lcap);
+    o.total = c.off - at;
+    return o;
+}
+
 // ctc_prefix_beam_search over log-probabilities lp_dev [B, T, vocab] already on the device: one upload (the lengths), ONE launch of
 // ctc_prefix_search (one workgroup per utterance, frame loop inside, results packed by its epilogue), one download, one
-// synchronisation.  Any context; weights are not needed.  Touches only its own grow-only buffers.
+// synchronisation.  Any context; weights are not needed.  Touches only its own buffers.
 int rnnt_ctc_prefix_beam_logprobs(rnnt_ctx* ctx, const float* lp_dev, const int32_t* enc_lens_host, int32_t B, int32_t T, int32_t beam_size,
                                   int32_t use_context, int32_t cap_tokens, int32_t* n_hyp_host, int32_t* lens_host, int32_t* tokens_host,
                                   int32_t* times_host, double* scores_host, double* ctx_scores_host, void* stream) {
@@ -320,21 +334,24 @@ int rnnt_ctc_prefix_beam_logprobs(rnnt_ctx* ctx, const float* lp_dev, const int3
     if ((size_t)B * T * V >= ((size_t)1 << 40) || (size_t)B * astride >= ((size_t)1 << 30) || R * lcap >= ((size_t)1 << 30))
         return fail(ctx, RNNT_ERR_SHAPE, "rnnt_ctc_prefix_beam_logprobs: B=%d T=%d beam=%d too large for one call", B, T, beam_size);
     hipStream_t s = (hipStream_t)stream;
-    // ints: lengths [B] | prefix arena [B][astride] int2 | time arena likewise | n_hyp [B] | lens [R] | tokens [R][lcap] | times [R][lcap]
-    const size_t arena_ints = 2 * (size_t)B * astride, out_ints = (size_t)B + R + 2 * R * lcap;
-    if ((rc = grow(ctx, &ctx->cp_i, &ctx->cp_i_cap, (size_t)B + (B & 1) + 2 * arena_ints + out_ints))) return rc;
-    if ((rc = grow(ctx, &ctx->cp_d, &ctx->cp_d_cap, 2 * R))) return rc;
+    // ints: lengths [B] | prefix arena [B][astride] int2 | time arena likewise | the downloaded block (cp_out)
     CtcPrefixP p;
     memset(&p, 0, sizeof(p));
-    int* i = ctx->cp_i;
-    int* d_lens = i; i += (size_t)B + (B & 1);                       // keeps the int2 arenas 8-byte aligned
-    p.parena = reinterpret_cast<int2*>(i); i += arena_ints;
-    p.tarena = reinterpret_cast<int2*>(i); i += arena_ints;
-    int* d_out = i;
-    p.o_nh = i; i += B;
-    p.o_len = i; i += R;
-    p.o_tok = i; i += R * lcap;
-    p.o_time = i;
+    int* d_lens;
+    CpOut o;
+    Carve<int> i;
+    auto lay = [&] {
+        d_lens = i.take((size_t)B + (B & 1));                         // keeps the int2 arenas 8-byte aligned
+        p.parena = reinterpret_cast<int2*>(i.take(2 * (size_t)B * astride));
+        p.tarena = reinterpret_cast<int2*>(i.take(2 * (size_t)B * astride));
+        o = cp_out(i, B, R, lcap);
+    };
+    lay();   // sizes
+    if ((rc = reserve(ctx, ctx->cp_i, i.off))) return rc;
+    if ((rc = reserve(ctx, ctx->cp_d, 2 * R))) return rc;
+    i = {ctx->cp_i};
+    lay();   // pointers
+    p.o_nh = o.nh; p.o_len = o.len; p.o_tok = o.tok; p.o_time = o.time;
     p.o_sc = ctx->cp_d; p.o_cs = ctx->cp_d + R;
     p.lp = lp_dev; p.lens = d_lens; p.T = T; p.V = V; p.blank = ctx->cfg.blank_id; p.beam = beam_size; p.lcap = (int)lcap;
     if (use_context) {
@@ -348,22 +365,23 @@ int rnnt_ctc_prefix_beam_logprobs(rnnt_ctx* ctx, const float* lp_dev, const int3
         hipLaunchKernelGGL(ctc_prefix_search, dim3(B), dim3(CP_NT), 0, s, p);
         LAUNCHCHK("ctc_prefix_search");
     }
-    std::vector<int> oi(out_ints);
+    std::vector<int> oi(o.total);
     std::vector<double> od(2 * R);
-    HIPCHK(hipMemcpyAsync(oi.data(), d_out, out_ints * sizeof(int), hipMemcpyDeviceToHost, s));          // the download (two blocks)
+    HIPCHK(hipMemcpyAsync(oi.data(), o.nh, o.total * sizeof(int), hipMemcpyDeviceToHost, s));            // the download (two blocks)
     HIPCHK(hipMemcpyAsync(od.data(), ctx->cp_d, 2 * R * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    const int *o_len = oi.data() + B, *o_tok = o_len + R, *o_time = o_tok + R * lcap;
-    memcpy(n_hyp_host, oi.data(), B * sizeof(int));
-    memcpy(lens_host, o_len, R * sizeof(int));
+    Carve<int> hc{oi.data()};
+    const CpOut h = cp_out(hc, B, R, lcap);
+    memcpy(n_hyp_host, h.nh, B * sizeof(int));
+    memcpy(lens_host, h.len, R * sizeof(int));
     memcpy(scores_host, od.data(), R * sizeof(double));
     if (ctx_scores_host) memcpy(ctx_scores_host, od.data() + R, R * sizeof(double));
     std::fill(tokens_host, tokens_host + R * cap_tokens, 0);
     std::fill(times_host, times_host + R * cap_tokens, 0);
     const size_t ncopy = std::min<size_t>(lcap, cap_tokens);
     for (size_t r = 0; r < R; ++r) {
-        memcpy(tokens_host + r * cap_tokens, o_tok + r * lcap, ncopy * sizeof(int));
-        memcpy(times_host + r * cap_tokens, o_time + r * lcap, ncopy * sizeof(int));
+        memcpy(tokens_host + r * cap_tokens, h.tok + r * lcap, ncopy * sizeof(int));
+        memcpy(times_host + r * cap_tokens, h.time + r * lcap, ncopy * sizeof(int));
     }
     return RNNT_OK;
 }
@@ -381,7 +399,7 @@ int rnnt_ctc_prefix_beam_decode(rnnt_ctx* ctx, const float* enc_dev, const int32
     if (!ctx->finalized) return fail(ctx, RNNT_ERR_STATE, "weights not finalized");
     if (!ctx->wctc) return fail(ctx, RNNT_ERR_STATE, "rnnt_ctc_prefix_beam_decode: ctc_head.ctc_lo.* not loaded");
     if ((long long)B * T >= 0x7fffffffLL / 512) return fail(ctx, RNNT_ERR_SHAPE, "rnnt_ctc_prefix_beam_decode: B=%d T=%d frames in one call", B, T);
-    if ((rc = grow(ctx, &ctx->cp_lp, &ctx->cp_lp_cap, std::max<size_t>((size_t)B * T * ctx->cfg.vocab_size, 1)))) return rc;
+    if ((rc = reserve(ctx, ctx->cp_lp, std::max<size_t>((size_t)B * T * ctx->cfg.vocab_size, 1)))) return rc;
     if (fmax > 0) {   // the kernel and tile choices of a small call whatever B is: an utterance's sums do not depend on its batch
         GemmCapScope cap(ctx);
         if ((rc = rnnt_ctc_logprobs(ctx, enc_dev, B * T, ctx->cp_lp, stream))) return rc;

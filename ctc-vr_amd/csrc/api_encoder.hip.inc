@@ -170,21 +170,18 @@ int wf_plan(rnnt_ctx* ctx, int total_frames, int C, const int32_t* chunk_start, 
 // per-chunk x rows, per-layer scratch and the subsampling slabs (once per context); the chunk-start table
 int wf_buffers(rnnt_ctx* ctx, int C) {
     int rc;
-    if (!ctx->wf_x) {
-        const size_t Bm = ctx->cfg.max_streams, Mmax = Bm * ctx->tmax;
-        size_t per_chunk = Bm * ctx->t1max * RNNT_F1 * D * sizeof(float);
-        ctx->wf_slab = (int)((192ull << 20) / per_chunk);
-        if (ctx->wf_slab < 1) ctx->wf_slab = 1;
-        if (ctx->wf_slab > 16) ctx->wf_slab = 16;
-        if ((rc = dmalloc(ctx, &ctx->wf_x, Bm * ctx->fcap * D))) return rc;
-        if ((rc = dmalloc(ctx, &ctx->wf_h, (size_t)L * WF_MERGE_MAX * Mmax * FF))) return rc;
-        if ((rc = dmalloc(ctx, &ctx->wf_q, (size_t)L * WF_MERGE_MAX * Mmax * D))) return rc;
-        if ((rc = dmalloc(ctx, &ctx->wf_a, (size_t)L * WF_MERGE_MAX * Mmax * D))) return rc;
-        if ((rc = dmalloc(ctx, &ctx->wf_d, (size_t)L * WF_MERGE_MAX * Mmax * D))) return rc;
-        if ((rc = dmalloc(ctx, &ctx->wf_y1, (size_t)ctx->wf_slab * Bm * ctx->t1max * RNNT_F1 * D))) return rc;
-        if ((rc = dmalloc(ctx, &ctx->wf_y2, (size_t)ctx->wf_slab * Mmax * RNNT_FSUB * D))) return rc;
-    }
-    return grow(ctx, &ctx->wf_starts, &ctx->wf_starts_cap, (size_t)C);
+    const size_t Bm = ctx->cfg.max_streams, Mmax = Bm * ctx->tmax;
+    const size_t per_chunk = Bm * ctx->t1max * RNNT_F1 * D * sizeof(float);
+    // context constants only: the same value on every call, so the wf_y1 / wf_y2 sizes below cannot drift between calls
+    ctx->wf_slab = (int)std::min<size_t>(std::max<size_t>((192ull << 20) / per_chunk, 1), 16);
+    if ((rc = reserve(ctx, ctx->wf_x, Bm * ctx->fcap * D))) return rc;
+    if ((rc = reserve(ctx, ctx->wf_h, (size_t)L * WF_MERGE_MAX * Mmax * FF))) return rc;
+    if ((rc = reserve(ctx, ctx->wf_q, (size_t)L * WF_MERGE_MAX * Mmax * D))) return rc;
+    if ((rc = reserve(ctx, ctx->wf_a, (size_t)L * WF_MERGE_MAX * Mmax * D))) return rc;
+    if ((rc = reserve(ctx, ctx->wf_d, (size_t)L * WF_MERGE_MAX * Mmax * D))) return rc;
+    if ((rc = reserve(ctx, ctx->wf_y1, (size_t)ctx->wf_slab * Bm * ctx->t1max * RNNT_F1 * D))) return rc;
+    if ((rc = reserve(ctx, ctx->wf_y2, (size_t)ctx->wf_slab * Mmax * RNNT_FSUB * D))) return rc;
+    return reserve(ctx, ctx->wf_starts, (size_t)C);
 }
 
 // fused schedule (rnnt_fused.hip.h), 3 launches per stage: one FuseItem per active layer + the attention descriptor of every pair
@@ -324,11 +321,11 @@ int wf_build_tables(rnnt_ctx* ctx, hipStream_t s, int total_frames, const std::v
     gt.reserve((size_t)C * L * 12); at.reserve((size_t)C * L); dt.reserve((size_t)C * L); lt.reserve((size_t)C * (L + 1));
     int rc;
     if ((rc = fused ? wf_build_fused(ctx, ci, NS, at, ft) : wf_build_unfused(ctx, ci, NS, gt, at, dt, lt))) return rc;
-    if ((rc = grow(ctx, &ctx->wf_gtab, &ctx->wf_gcap, gt.size()))) return rc;
-    if ((rc = grow(ctx, &ctx->wf_atab, &ctx->wf_acap, at.size()))) return rc;
-    if ((rc = grow(ctx, &ctx->wf_dtab, &ctx->wf_dcap, dt.size()))) return rc;
-    if ((rc = grow(ctx, &ctx->wf_ltab, &ctx->wf_lcap, lt.size()))) return rc;
-    if ((rc = grow(ctx, &ctx->wf_ftab, &ctx->wf_fcap, ft.size()))) return rc;
+    if ((rc = reserve(ctx, ctx->wf_gtab, gt.size()))) return rc;
+    if ((rc = reserve(ctx, ctx->wf_atab, at.size()))) return rc;
+    if ((rc = reserve(ctx, ctx->wf_dtab, dt.size()))) return rc;
+    if ((rc = reserve(ctx, ctx->wf_ltab, lt.size()))) return rc;
+    if ((rc = reserve(ctx, ctx->wf_ftab, ft.size()))) return rc;
     HIPCHK(hipMemcpyAsync(ctx->wf_gtab, gt.data(), gt.size() * sizeof(GemmP), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(ctx->wf_atab, at.data(), at.size() * sizeof(AttnP), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(ctx->wf_dtab, dt.data(), dt.size() * sizeof(DwP), hipMemcpyHostToDevice, s));

@@ -45,7 +45,7 @@ int rnnt_create(const rnnt_config* cfg, rnnt_ctx** out) {
     ctx->vpad = (cfg->vocab_size + 31) / 32 * 32;
     const size_t M = (size_t)B * ctx->tmax;
     int rc;
-#define ALLOC(p, n) if ((rc = dmalloc(ctx, &ctx->p, (size_t)(n)))) return rc
+#define ALLOC(p, n) if ((rc = reserve(ctx, ctx->p, (size_t)(n)))) return rc
     ALLOC(y1, (size_t)B * ctx->t1max * RNNT_F1 * D);
     ALLOC(y2, M * RNNT_FSUB * D);
     ALLOC(x, M * D);
@@ -74,50 +74,19 @@ int rnnt_create(const rnnt_config* cfg, rnnt_ctx** out) {
         ALLOC(b_blank, R * NS); ALLOC(b_toplp, R * NS * KB); ALLOC(b_toptok, R * NS * KB);
         ALLOC(b_tok, R); ALLOC(b_frame, R); ALLOC(b_active, R); ALLOC(b_steps, R); ALLOC(b_srcrow, R); ALLOC(b_srcstep, R);
     }
-    ctx->scratch_floats = (size_t)L * RNNT_H * ctx->tcap * 128;
-    if (ctx->scratch_floats < (size_t)B * ctx->fstride * D) ctx->scratch_floats = (size_t)B * ctx->fstride * D;
-    ALLOC(scratch, ctx->scratch_floats);
+    ALLOC(scratch, std::max((size_t)L * RNNT_H * ctx->tcap * 128, (size_t)B * ctx->fstride * D));
+    ALLOC(pinned, 16);
 #undef ALLOC
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&ctx->pinned), 64));
     HIPCHK(hipMemset(ctx->encbuf, 0, (size_t)B * ctx->fstride * D * sizeof(float)));
     HIPCHK(hipMemset(ctx->encp, 0, (size_t)B * ctx->fstride * D * sizeof(float)));
     return RNNT_OK;
 }
 
 void rnnt_destroy(rnnt_ctx* ctx) {
-    if (!ctx) return;
-    void* ptrs[] = {ctx->joint_wfrag, ctx->joint_counter, ctx->blob, ctx->blob_hi, ctx->blob_lo, ctx->fuse_w, ctx->layers_dev, ctx->wf_ftab, ctx->egate, ctx->y1, ctx->y2, ctx->x, ctx->hbuf, ctx->qbuf, ctx->abuf, ctx->dbuf, ctx->kcache, ctx->vcache,
-                    ctx->gring, ctx->xring, ctx->encbuf, ctx->encp, ctx->h, ctx->c, ctx->sel, ctx->key, ctx->dec_ctrl, ctx->gm_dbg, ctx->pred, ctx->z, ctx->logits,
-                    ctx->tok, ctx->fidx, ctx->nsym, ctx->count, ctx->tokens, ctx->n_active, ctx->klen, ctx->scratch, ctx->gm_x1, ctx->gm_xa,
-                    ctx->pool[0], ctx->pool[1], ctx->bpred, ctx->bz, ctx->blogits, ctx->b_blank, ctx->b_toplp, ctx->b_toptok,
-                    ctx->b_tok, ctx->b_frame, ctx->b_active, ctx->b_steps, ctx->b_srcrow, ctx->b_srcstep};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    for (int l = 0; l < L; ++l)
-        if (ctx->lw[l].ptab) (void)hipFree(ctx->lw[l].ptab);
-    if (ctx->pinned) (void)hipHostFree(ctx->pinned);
-    if (ctx->pool_tab) (void)hipFree(ctx->pool_tab);
-    if (ctx->pool_tab_host) (void)hipHostFree(ctx->pool_tab_host);
-    if (ctx->pool_ev) (void)hipEventDestroy(ctx->pool_ev);
-    for (hipEvent_t e : ctx->prof_ev) (void)hipEventDestroy(e);
-    if (ctx->dec_stream) (void)hipStreamDestroy(ctx->dec_stream);
-    for (hipEvent_t e : ctx->sub_ev) if (e) (void)hipEventDestroy(e);
-    for (auto& g : ctx->dec_graphs) (void)hipGraphExecDestroy(g.exec);
-    if (ctx->cap_stream) (void)hipStreamDestroy(ctx->cap_stream);
-    if (ctx->sub_stream) (void)hipStreamDestroy(ctx->sub_stream);
-    for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
-    for (float* q : {ctx->fb_dft, ctx->fb_mel, ctx->fb_pad, ctx->fb_spec, ctx->fb_pow}) if (q) (void)hipFree(q);
-    void* wf[] = {ctx->wf_x, ctx->wf_h, ctx->wf_q, ctx->wf_a, ctx->wf_d, ctx->wf_y1, ctx->wf_y2, ctx->wf_starts, ctx->wf_gtab, ctx->wf_atab,
-                  ctx->wf_dtab, ctx->wf_ltab, ctx->lm_x, ctx->lm_h, ctx->lm_q, ctx->lm_a, ctx->lm_d, ctx->lm_g, ctx->lm_y1, ctx->lm_y2, ctx->lm_y1b, ctx->lm_y2b, ctx->lm_blocks, ctx->lm_rhdr, ctx->lm_rrows,
-                  ctx->rg_fb, ctx->rg_xt, ctx->rg_ent, ctx->bd_tok, ctx->bd_len, ctx->bd_sc, ctx->bd_hs, ctx->bd_nh, ctx->bd_fend,
-                  ctx->ps_pool[0], ctx->ps_pool[1], ctx->ps_tok, ctx->ps_len, ctx->ps_sc, ctx->ps_hs, ctx->ps_nh,
-                  ctx->sc_f, ctx->sc_lat, ctx->sc_i, ctx->sc_nll, ctx->al_bp, ctx->al_out,
-                  ctx->pb_f, ctx->pb_i, ctx->pb_d, ctx->pb_out,
-                  ctx->cg_i, ctx->cg_d, ctx->cp_i, ctx->cp_d, ctx->cp_lp};
-    for (void* q : wf)
-        if (q) (void)hipFree(q);
-    delete ctx;
+    if (ctx) delete ctx;
 }
+
+int64_t rnnt_live_device_bytes(void) { return live_device_bytes.load(); }
 
 int rnnt_load_tensor(rnnt_ctx* ctx, const char* name, const float* host_data, int32_t ndim, const int64_t* dims) {
     if (!ctx || !name || ndim < 0 || ndim > 8) return fail(ctx, RNNT_ERR_ARG, "rnnt_load_tensor: bad argument");
@@ -412,20 +381,19 @@ int rnnt_finalize_weights(rnnt_ctx* ctx, int32_t numerics_mode, void* stream) {
     // upload (the allocation is kept when the size is unchanged: a reload of the same architecture re-copies in place)
     while (blob.size() % 8) blob.push_back(0.f);
     int rc;
-    if (!ctx->blob || ctx->blob_floats != blob.size()) {
+    if (ctx->blob.cap != blob.size()) {
         HIPCHK(hipStreamSynchronize(s));
-        for (void* q : {(void*)ctx->blob, (void*)ctx->blob_hi, (void*)ctx->blob_lo}) if (q) (void)hipFree(q);
-        ctx->blob = nullptr; ctx->blob_hi = ctx->blob_lo = nullptr;
-        if ((rc = dmalloc(ctx, &ctx->blob, blob.size()))) return rc;
-        ctx->blob_floats = blob.size();
+        ctx->blob_hi.release();   // the planes have the blob's size; allocated below when the mode reads them
+        ctx->blob_lo.release();
+        if ((rc = reserve_exact(ctx, ctx->blob, blob.size()))) return rc;
     }
     HIPCHK(hipMemcpyAsync(ctx->blob, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice, s));
     for (auto& f : fix) *f.first = ctx->blob + f.second;
     ctx->numerics = RNNT_NUM_F32;   // the derived tables below are always exact f32
     if (numerics_mode != RNNT_NUMERICS_FP32) {
         // hi / lo 16-bit planes of every weight, same element index as the blob (gemm_bf reads them through GemmP::Wh / Wl)
-        if (!ctx->blob_hi && (rc = dmalloc(ctx, &ctx->blob_hi, blob.size()))) return rc;
-        if (!ctx->blob_lo && (rc = dmalloc(ctx, &ctx->blob_lo, blob.size()))) return rc;
+        if ((rc = reserve(ctx, ctx->blob_hi, blob.size()))) return rc;
+        if ((rc = reserve(ctx, ctx->blob_lo, blob.size()))) return rc;
         const long long n8 = (long long)(blob.size() / 8);
         if (numerics_mode == RNNT_NUMERICS_F16X3) hipLaunchKernelGGL(split_planes<true>, dim3(grid_for(n8)), dim3(256), 0, s, ctx->blob, ctx->blob_hi, ctx->blob_lo, n8);
         else hipLaunchKernelGGL(split_planes<false>, dim3(grid_for(n8)), dim3(256), 0, s, ctx->blob, ctx->blob_hi, ctx->blob_lo, n8);
@@ -437,14 +405,11 @@ int rnnt_finalize_weights(rnnt_ctx* ctx, int32_t numerics_mode, void* stream) {
         const size_t per_w = nm == RNNT_NUMERICS_BF16 ? 8 : 4;              // weights per 16-byte vector
         const size_t layer_w = (size_t)4 * FF * D + 5 * D * D + 2 * D * D;   // w1m w2m w1 w2 | wq wk wv wo pw2 | pw1
         const size_t vecs = ((size_t)L * layer_w + (size_t)D * 2304) / per_w;          // + conv2 [256][2304] for gemm_bw
-        if (!ctx->fuse_w || ctx->fuse_w_vecs != vecs) {
+        if (ctx->fuse_w.cap != vecs) {
             HIPCHK(hipStreamSynchronize(s));
-            if (ctx->fuse_w) (void)hipFree(ctx->fuse_w);
-            ctx->fuse_w = nullptr;
-            if ((rc = dmalloc(ctx, &ctx->fuse_w, vecs))) return rc;
-            ctx->fuse_w_vecs = vecs;
+            if ((rc = reserve_exact(ctx, ctx->fuse_w, vecs))) return rc;
         }
-        if (!ctx->layers_dev && (rc = dmalloc(ctx, &ctx->layers_dev, (size_t)L))) return rc;
+        if ((rc = reserve(ctx, ctx->layers_dev, (size_t)L))) return rc;
         std::vector<LayerDev> ld(L);
         uint4* cur = ctx->fuse_w;
         auto pack = [&](const float* W, int N, int K) -> const uint4* {
@@ -484,14 +449,11 @@ int rnnt_finalize_weights(rnnt_ctx* ctx, int32_t numerics_mode, void* stream) {
     if (numerics_mode != RNNT_NUMERICS_FP32 && V <= JR_NT * 16 && V % 4 == 0) {
         const bool lo = numerics_mode != RNNT_NUMERICS_BF16;
         const size_t bytes = (size_t)(lo ? 16 : 8) * JR_SLOT;
-        if (!ctx->joint_wfrag || ctx->joint_wfrag_bytes != bytes) {
+        if (ctx->joint_wfrag.cap != bytes) {
             HIPCHK(hipStreamSynchronize(s));
-            if (ctx->joint_wfrag) (void)hipFree(ctx->joint_wfrag);
-            ctx->joint_wfrag = nullptr;
-            if ((rc = dmalloc(ctx, &ctx->joint_wfrag, bytes))) return rc;
-            ctx->joint_wfrag_bytes = bytes;
+            if ((rc = reserve_exact(ctx, ctx->joint_wfrag, bytes))) return rc;
         }
-        if (!ctx->joint_counter && (rc = dmalloc(ctx, &ctx->joint_counter, (size_t)4))) return rc;
+        if ((rc = reserve(ctx, ctx->joint_counter, (size_t)4))) return rc;
         const dim3 g((unsigned)(bytes / 16 + 255) / 256), b(256);
         if (numerics_mode == RNNT_NUMERICS_F16X3) hipLaunchKernelGGL((pack_joint_w<true, true>), g, b, 0, s, ctx->wout, (int)V, ctx->joint_wfrag);
         else if (lo) hipLaunchKernelGGL((pack_joint_w<false, true>), g, b, 0, s, ctx->wout, (int)V, ctx->joint_wfrag);
@@ -501,11 +463,12 @@ int rnnt_finalize_weights(rnnt_ctx* ctx, int32_t numerics_mode, void* stream) {
     // derived tables on the device: P_l = pe * W_pos^T (attention.py:396, batch-invariant), input-gate
     // table E = embed * W_ih^T + b_ih + b_hh (predictor.py:200,204)
     for (int l = 0; l < L; ++l) {
-        if (!ctx->lw[l].ptab && (rc = dmalloc(ctx, &ctx->lw[l].ptab, (size_t)RNNT_PE_LEN * D))) return rc;
+        if ((rc = reserve(ctx, ctx->ptab[l], (size_t)RNNT_PE_LEN * D))) return rc;
+        ctx->lw[l].ptab = ctx->ptab[l];
         GemmP g = plain_gemm(ctx->pe, D, ctx->lw[l].wpos, D, nullptr, ctx->lw[l].ptab, D, RNNT_PE_LEN, D, D);
         if ((rc = launch_gemm(ctx, s, &g, 1))) return rc;
     }
-    if (!ctx->egate && (rc = dmalloc(ctx, &ctx->egate, (size_t)V * 4 * D))) return rc;
+    if ((rc = reserve(ctx, ctx->egate, (size_t)V * 4 * D))) return rc;
     {
         GemmP g = plain_gemm(ctx->pred_embed, D, ctx->wih_il, D, ctx->b_lstm_il, ctx->egate, 4 * D, V, 4 * D, D);
         if ((rc = launch_gemm(ctx, s, &g, 1))) return rc;

@@ -21,7 +21,7 @@ int rnnt_joint(rnnt_ctx* ctx, const float* enc_dev, const float* pred_dev, int32
     hipStream_t s = (hipStream_t)stream;
     const int V = ctx->cfg.vocab_size;
     const size_t needf = (size_t)B * T * D + (size_t)B * U * D;
-    if (needf > ctx->scratch_floats) return fail(ctx, RNNT_ERR_SHAPE, "joint lattice B=%d T=%d U=%d exceeds the context scratch", B, T, U);
+    if (needf > ctx->scratch.cap) return fail(ctx, RNNT_ERR_SHAPE, "joint lattice B=%d T=%d U=%d exceeds the context scratch", B, T, U);
     float* e = ctx->scratch;
     float* pp = e + (size_t)B * T * D;
     int rc;
@@ -143,7 +143,7 @@ int rnnt_ctc_argmax(rnnt_ctx* ctx, const float* fbank_dev, const int32_t* lens_h
     hipStream_t s = (hipStream_t)stream;
     const int tq = sub_len(T);
     const size_t rows = (size_t)B * tq;
-    if (rows * D + rows * 3 > ctx->scratch_floats) return fail(ctx, RNNT_ERR_SHAPE, "rnnt_ctc_argmax: B=%d T=%d exceeds the context scratch", B, T);
+    if (rows * D + rows * 3 > ctx->scratch.cap) return fail(ctx, RNNT_ERR_SHAPE, "rnnt_ctc_argmax: B=%d T=%d exceeds the context scratch", B, T);
     float* enc = ctx->scratch;
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(ctx->scratch + ((rows * D + 1) / 2) * 2);
     int* ids = reinterpret_cast<int*>(keys + rows);
@@ -191,7 +191,7 @@ int rnnt_greedy_search_full(rnnt_ctx* ctx, const float* fbank_dev, const int32_t
     hipStream_t s = (hipStream_t)stream;
     const int tq = sub_len(T);
     const size_t rows = (size_t)B * tq;
-    if (rows * D > ctx->scratch_floats) return fail(ctx, RNNT_ERR_SHAPE, "rnnt_greedy_search_full: B=%d T=%d exceeds the context scratch", B, T);
+    if (rows * D > ctx->scratch.cap) return fail(ctx, RNNT_ERR_SHAPE, "rnnt_greedy_search_full: B=%d T=%d exceeds the context scratch", B, T);
     if (tq > ctx->fcap) return fail(ctx, RNNT_ERR_SHAPE, "rnnt_greedy_search_full: %d encoder frames exceed max_enc_frames %d", tq, ctx->fcap);
     int rc, fo = 0;
     if ((rc = rnnt_streams_reset(ctx, B, stream))) return rc;                                   // zero predictor state, token = blank
@@ -233,10 +233,8 @@ int rnnt_fbank(rnnt_ctx* ctx, const float* wave_dev, int32_t B, int32_t n_sample
     int rc;
     if (ctx->fb_rate != sample_rate || ctx->fb_nfft != n_fft) {   // matrices in double on the host, once per (rate, n_fft)
         HIPCHK(hipStreamSynchronize(s));
-        if (ctx->fb_dft) { (void)hipFree(ctx->fb_dft); ctx->fb_dft = nullptr; }
-        if (ctx->fb_mel) { (void)hipFree(ctx->fb_mel); ctx->fb_mel = nullptr; }
-        if ((rc = dmalloc(ctx, &ctx->fb_dft, (size_t)n2p * n_fft))) return rc;
-        if ((rc = dmalloc(ctx, &ctx->fb_mel, (size_t)n_mels * kp))) return rc;
+        if ((rc = reserve_exact(ctx, ctx->fb_dft, (size_t)n2p * n_fft))) return rc;
+        if ((rc = reserve_exact(ctx, ctx->fb_mel, (size_t)n_mels * kp))) return rc;
         const double pi = 3.14159265358979323846;
         std::vector<float> dft((size_t)n2p * n_fft, 0.f), mel((size_t)n_mels * kp, 0.f);
         std::vector<double> win(n_fft);
@@ -267,9 +265,9 @@ int rnnt_fbank(rnnt_ctx* ctx, const float* wave_dev, int32_t B, int32_t n_sample
         ctx->fb_rate = sample_rate;
         ctx->fb_nfft = n_fft;
     }
-    if ((rc = grow(ctx, &ctx->fb_pad, &ctx->fb_pad_cap, (size_t)B * pstride))) return rc;
-    if ((rc = grow(ctx, &ctx->fb_spec, &ctx->fb_spec_cap, (size_t)M * n2p))) return rc;
-    if ((rc = grow(ctx, &ctx->fb_pow, &ctx->fb_pow_cap, (size_t)M * kp))) return rc;
+    if ((rc = reserve(ctx, ctx->fb_pad, (size_t)B * pstride))) return rc;
+    if ((rc = reserve(ctx, ctx->fb_spec, (size_t)M * n2p))) return rc;
+    if ((rc = reserve(ctx, ctx->fb_pow, (size_t)M * kp))) return rc;
     hipLaunchKernelGGL(reflect_pad, dim3(grid_for((long long)B * pstride)), dim3(256), 0, s, wave_dev, ctx->fb_pad, B, n_samples, n_fft / 2, pstride);
     LAUNCHCHK("reflect_pad");
     // windowed DFT: implicit frames (row t of stream b starts at b*pstride + t*hop), K = n_fft

@@ -17,12 +17,11 @@
 namespace {
 
 int pool_alloc(rnnt_ctx* ctx) {
-    if (ctx->pool_tab) return RNNT_OK;
     const size_t n = (size_t)ctx->cfg.max_streams * (POOL_ROW_INTS + 2);   // + the slot list + the beam buffer index per active row
     int rc;
-    if ((rc = dmalloc(ctx, &ctx->pool_tab, n))) return rc;
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&ctx->pool_tab_host), n * sizeof(int)));
-    HIPCHK(hipEventCreateWithFlags(&ctx->pool_ev, hipEventDisableTiming));
+    if ((rc = reserve(ctx, ctx->pool_tab, n))) return rc;
+    if ((rc = reserve(ctx, ctx->pool_tab_host, n))) return rc;
+    if (!ctx->pool_ev) HIPCHK(hipEventCreateWithFlags(&ctx->pool_ev, hipEventDisableTiming));
     return RNNT_OK;
 }
 
@@ -32,13 +31,13 @@ int pool_beam_alloc(rnnt_ctx* ctx, hipStream_t s) {
     if (ctx->ps_nh) return RNNT_OK;
     const size_t R = ctx->max_rows, B = ctx->cfg.max_streams, state = R * (ctx->cfg.n_steps + 1) * 512;
     int rc;
-    if (!ctx->ps_pool[0] && (rc = dmalloc(ctx, &ctx->ps_pool[0], state))) return rc;
-    if (!ctx->ps_pool[1] && (rc = dmalloc(ctx, &ctx->ps_pool[1], state))) return rc;
-    if (!ctx->ps_tok && (rc = dmalloc(ctx, &ctx->ps_tok, 2 * R * (size_t)ctx->cfg.max_tokens))) return rc;
-    if (!ctx->ps_len && (rc = dmalloc(ctx, &ctx->ps_len, 2 * R))) return rc;
-    if (!ctx->ps_sc && (rc = dmalloc(ctx, &ctx->ps_sc, 2 * R))) return rc;
-    if (!ctx->ps_hs && (rc = dmalloc(ctx, &ctx->ps_hs, 2 * R))) return rc;
-    if ((rc = dmalloc(ctx, &ctx->ps_nh, B))) return rc;
+    if ((rc = reserve(ctx, ctx->ps_pool[0], state))) return rc;
+    if ((rc = reserve(ctx, ctx->ps_pool[1], state))) return rc;
+    if ((rc = reserve(ctx, ctx->ps_tok, 2 * R * (size_t)ctx->cfg.max_tokens))) return rc;
+    if ((rc = reserve(ctx, ctx->ps_len, 2 * R))) return rc;
+    if ((rc = reserve(ctx, ctx->ps_sc, 2 * R))) return rc;
+    if ((rc = reserve(ctx, ctx->ps_hs, 2 * R))) return rc;
+    if ((rc = reserve(ctx, ctx->ps_nh, B))) return rc;   // last: its presence says the state exists (pool_beam_reset)
     ctx->ps_cur.assign(B, 0);
     ctx->ps_lbound.assign(B, 0);
     return pool_beam_reset(ctx, s, 0, (int)B);
@@ -200,7 +199,7 @@ int pool_chunk_run(rnnt_ctx* ctx, const char* fn, int32_t n_active, const int32_
         for (int i = 0; i < n; ++i) ctx->pool_tab_host[(size_t)n * (POOL_ROW_INTS + 1) + i] = ctx->ps_cur[rows[i].slot];
     HIPCHK(hipMemcpyAsync(ctx->pool_tab, ctx->pool_tab_host, (size_t)n * (POOL_ROW_INTS + (mode == POOL_BEAM ? 2 : 1)) * sizeof(int), hipMemcpyHostToDevice, s));
     HIPCHK(hipEventRecord(ctx->pool_ev, s));
-    const PoolRow* rows_dev = reinterpret_cast<const PoolRow*>(ctx->pool_tab);
+    const PoolRow* rows_dev = reinterpret_cast<const PoolRow*>(ctx->pool_tab.p);
     const int* slots_dev = ctx->pool_tab + (size_t)n * POOL_ROW_INTS;
     pool_enter(ctx);
     {

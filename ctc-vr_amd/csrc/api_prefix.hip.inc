@@ -47,7 +47,7 @@ int rnnt_prefix_merge_host(int32_t n_hyp, const int32_t* hyp_len, const int32_t*
 }
 
 namespace {
-// The call's own grow-only buffers: rows = B * beam fixed rows, token lists of lcap ints, `frames` = B * T projected frames.
+// The call's own buffers: rows = B * beam fixed rows, token lists of lcap ints, `frames` = B * T projected frames.
 struct PrefixBuf {
     float *encp, *ctc, *pool[2], *top_lp;
     int *tk[2], *len[2], *nh, *lens, *top_tok, *src_row, *src_slot;
@@ -56,23 +56,31 @@ struct PrefixBuf {
 };
 int prefix_buffers(rnnt_ctx* ctx, size_t B, size_t rows, size_t lcap, size_t frames, bool with_ctc, int k, PrefixBuf& o) {
     const size_t V = ctx->cfg.vocab_size;
+    Carve<float> f;
+    Carve<int> i;
+    Carve<double> d;
+    auto lay = [&] {
+        o.encp = f.take(frames * D);
+        o.ctc = with_ctc ? f.take(frames * V) : nullptr;
+        for (float*& q : o.pool) q = f.take(rows * 1024);
+        o.top_lp = f.take(rows * k);
+        for (int*& q : o.tk) q = i.take(rows * lcap);
+        for (int*& q : o.len) q = i.take(rows);
+        o.nh = i.take(B);
+        o.lens = i.take(B);
+        o.top_tok = i.take(rows * k);
+        o.src_row = i.take(rows);
+        o.src_slot = i.take(rows);
+        for (double*& q : o.sc) q = d.take(rows);
+        for (unsigned long long*& q : o.hs) q = reinterpret_cast<unsigned long long*>(d.take(rows));
+    };
+    lay();   // sizes
     int rc;
-    if ((rc = grow(ctx, &ctx->pb_f, &ctx->pb_f_cap, frames * D + (with_ctc ? frames * V : 0) + 2 * rows * 1024 + rows * k))) return rc;
-    if ((rc = grow(ctx, &ctx->pb_i, &ctx->pb_i_cap, 2 * rows * lcap + 2 * rows + 2 * B + rows * k + 2 * rows))) return rc;
-    if ((rc = grow(ctx, &ctx->pb_d, &ctx->pb_d_cap, 4 * rows))) return rc;
-    float* f = ctx->pb_f;
-    o.encp = f; f += frames * D;
-    o.ctc = with_ctc ? f : nullptr; f += with_ctc ? frames * V : 0;
-    o.pool[0] = f; o.pool[1] = f + rows * 1024; f += 2 * rows * 1024;
-    o.top_lp = f;
-    int* i = ctx->pb_i;
-    o.tk[0] = i; o.tk[1] = i + rows * lcap; i += 2 * rows * lcap;
-    o.len[0] = i; o.len[1] = i + rows; i += 2 * rows;
-    o.nh = i; o.lens = i + B; i += 2 * B;
-    o.top_tok = i; i += rows * k;
-    o.src_row = i; o.src_slot = i + rows;
-    o.sc[0] = ctx->pb_d; o.sc[1] = ctx->pb_d + rows;
-    o.hs[0] = reinterpret_cast<unsigned long long*>(ctx->pb_d + 2 * rows); o.hs[1] = o.hs[0] + rows;
+    if ((rc = reserve(ctx, ctx->pb_f, f.off))) return rc;
+    if ((rc = reserve(ctx, ctx->pb_i, i.off))) return rc;
+    if ((rc = reserve(ctx, ctx->pb_d, d.off))) return rc;
+    f = {ctx->pb_f}; i = {ctx->pb_i}; d = {ctx->pb_d};
+    lay();   // pointers
     return RNNT_OK;
 }
 
@@ -126,7 +134,7 @@ int rnnt_prefix_beam_decode(rnnt_ctx* ctx, const float* enc_dev, const int32_t* 
     if ((rc = prefix_buffers(ctx, B, R, lcap, frames, with_ctc, k, u))) return rc;
     const size_t out_bytes = R * sizeof(double) + sizeof(int) * ((size_t)B + R + R * lcap) + (with_states ? 2 * R * D * sizeof(float) : 0);
     const size_t out_doubles = (out_bytes + sizeof(double) - 1) / sizeof(double);
-    if ((rc = grow(ctx, &ctx->pb_out, &ctx->pb_out_cap, out_doubles))) return rc;
+    if ((rc = reserve(ctx, ctx->pb_out, out_doubles))) return rc;
     HIPCHK(hipMemcpyAsync(u.lens, enc_lens_host, B * sizeof(int), hipMemcpyHostToDevice, s));            // the upload
     hipLaunchKernelGGL(prefix_init, dim3(B), dim3(256), 0, s, u.pool[0], u.tk[0], u.len[0], u.sc[0], u.hs[0], u.nh, beam_size, (int)lcap, blank);
     LAUNCHCHK("prefix_init");

@@ -26,27 +26,36 @@ static int score_check(rnnt_ctx* ctx, const char* what, const float* enc_dev, co
 // blank: they are neither validated nor used, and the padded cells they reach stay defined) | lens [2][B] | tok [U1][B] (the
 // predictor's input of step u: blank, then y_1 .. y_U; transducer only).  ts = max(Umax, 1).  targets may be null when the
 // caller brings its own lattice: the rows then stay blank.
+struct ScoreInts { int *tg, *lens, *tok; size_t total; };
+static ScoreInts score_ints(Carve<int> c, size_t B, size_t ts, size_t tok_rows) {
+    ScoreInts o;
+    o.tg = c.take(B * ts);
+    o.lens = c.take(2 * B);
+    o.tok = c.take(tok_rows * B);
+    o.total = c.off;
+    return o;
+}
 static int score_upload(rnnt_ctx* ctx, hipStream_t s, const int32_t* enc_lens, const int32_t* targets, const int32_t* target_lens, int B,
                         int Umax, bool with_tok, std::vector<int>& host, int** tg_dev, int** lens_dev, int** tok_dev) {
-    const int ts = Umax > 0 ? Umax : 1, U1 = Umax + 1, blank = ctx->cfg.blank_id;
-    host.assign((size_t)B * ts + 2 * (size_t)B + (with_tok ? (size_t)U1 * B : 0), blank);
-    int* lens = host.data() + (size_t)B * ts;
-    int* tok = lens + 2 * (size_t)B;
+    const int ts = Umax > 0 ? Umax : 1, blank = ctx->cfg.blank_id;
+    const size_t tok_rows = with_tok ? Umax + 1 : 0;
+    const size_t total = score_ints({}, B, ts, tok_rows).total;
+    host.assign(total, blank);
+    const ScoreInts h = score_ints({host.data()}, B, ts, tok_rows);
     for (int b = 0; b < B; ++b) {
-        lens[b] = enc_lens[b];
-        lens[B + b] = target_lens[b];
+        h.lens[b] = enc_lens[b];
+        h.lens[B + b] = target_lens[b];
         for (int u = 0; targets && u < target_lens[b]; ++u) {
-            host[(size_t)b * ts + u] = targets[(size_t)b * Umax + u];
-            if (with_tok) tok[(size_t)(u + 1) * B + b] = targets[(size_t)b * Umax + u];
+            h.tg[(size_t)b * ts + u] = targets[(size_t)b * Umax + u];
+            if (with_tok) h.tok[(size_t)(u + 1) * B + b] = targets[(size_t)b * Umax + u];
         }
     }
     int rc;
-    if ((rc = grow(ctx, &ctx->sc_i, &ctx->sc_i_cap, host.size()))) return rc;
-    if ((rc = grow(ctx, &ctx->sc_nll, &ctx->sc_nll_cap, (size_t)B))) return rc;
-    HIPCHK(hipMemcpyAsync(ctx->sc_i, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice, s));
-    *tg_dev = ctx->sc_i;
-    *lens_dev = ctx->sc_i + (size_t)B * ts;
-    *tok_dev = *lens_dev + 2 * (size_t)B;
+    if ((rc = reserve(ctx, ctx->sc_i, total))) return rc;
+    if ((rc = reserve(ctx, ctx->sc_nll, (size_t)B))) return rc;
+    HIPCHK(hipMemcpyAsync(ctx->sc_i, host.data(), total * sizeof(int), hipMemcpyHostToDevice, s));
+    const ScoreInts d = score_ints({ctx->sc_i}, B, ts, tok_rows);
+    *tg_dev = d.tg; *lens_dev = d.lens; *tok_dev = d.tok;
     return RNNT_OK;
 }
 
@@ -62,13 +71,13 @@ static int score_pick(rnnt_ctx* ctx, const char* what, const float* enc_dev, con
     const int V = ctx->cfg.vocab_size, U1 = Umax + 1, ts = Umax > 0 ? Umax : 1;
     const long long Mrows = (long long)B * T * U1;
     const size_t needf = (size_t)B * T * D + (size_t)B * U1 * D;   // rnnt_joint's own check: e and p live in the context scratch
-    if (needf > ctx->scratch_floats || Mrows >= 0x7fffffffLL - JR_ROWS)
+    if (needf > ctx->scratch.cap || Mrows >= 0x7fffffffLL - JR_ROWS)
         return fail(ctx, RNNT_ERR_SHAPE, "%s: lattice B=%d T=%d U=%d exceeds the context scratch", what, B, T, U1);
     const bool rows_kernel = ctx->numerics != RNNT_NUM_F32 && ctx->joint_wfrag && V <= JR_NT * 16 && V % 4 == 0;
     // work floats: pred [B][U1][256] | h, c ping-pong [2][2][B][256] | pick [B][T][U1][2] when the caller keeps none
     const size_t n_pred = (size_t)B * U1 * D, n_state = (size_t)B * D;
-    if ((rc = grow(ctx, &ctx->sc_f, &ctx->sc_f_cap, n_pred + 4 * n_state + (pick_dev ? 0 : (size_t)Mrows * 2)))) return rc;
-    if (!rows_kernel && (rc = grow(ctx, &ctx->sc_lat, &ctx->sc_lat_cap, (size_t)Mrows * V))) return rc;
+    if ((rc = reserve(ctx, ctx->sc_f, n_pred + 4 * n_state + (pick_dev ? 0 : (size_t)Mrows * 2)))) return rc;
+    if (!rows_kernel && (rc = reserve(ctx, ctx->sc_lat, (size_t)Mrows * V))) return rc;
     int *tg, *lens, *tok;
     if ((rc = score_upload(ctx, s, enc_lens_host, targets_host, target_lens_host, B, Umax, true, host, &tg, &lens, &tok))) return rc;
     float* pred = ctx->sc_f;
@@ -160,7 +169,7 @@ int rnnt_ctc_nll(rnnt_ctx* ctx, const float* enc_dev, const int32_t* enc_lens_ho
     const int V = ctx->cfg.vocab_size;
     if ((long long)B * T >= 0x7fffffffLL) return fail(ctx, RNNT_ERR_SHAPE, "rnnt_ctc_nll: B=%d T=%d frames in one call", B, T);
     hipStream_t s = (hipStream_t)stream;
-    if ((rc = grow(ctx, &ctx->sc_lat, &ctx->sc_lat_cap, (size_t)B * T * V))) return rc;
+    if ((rc = reserve(ctx, ctx->sc_lat, (size_t)B * T * V))) return rc;
     std::vector<int> host;
     int *tg, *lens, *tok;
     if ((rc = score_upload(ctx, s, enc_lens_host, targets_host, target_lens_host, B, Umax, false, host, &tg, &lens, &tok))) return rc;
@@ -177,7 +186,15 @@ int rnnt_ctc_nll(rnnt_ctx* ctx, const float* enc_dev, const int32_t* enc_lens_ho
 
 // ---- forced alignment ------------------------------------------------------------------------------------------------------------------
 // Device outputs of an alignment call, downloaded in ONE copy: best [B] f64 | nll [B] f64 | path [B][n] int32.
-static size_t align_out_doubles(int B, size_t n) { return 2 * (size_t)B + ((size_t)B * n + 1) / 2; }
+struct AlignOut { double *best, *nll; int* path; size_t total; };
+static AlignOut align_out(Carve<double> c, size_t B, size_t n) {
+    AlignOut o;
+    o.best = c.take(B);
+    o.nll = c.take(B);
+    o.path = reinterpret_cast<int*>(c.take((B * n + 1) / 2));
+    o.total = c.off;
+    return o;
+}
 
 static int align_check(rnnt_ctx* ctx, const char* what, const float* dev, const int32_t* enc_lens, const int32_t* targets, const int32_t* target_lens,
                        int32_t B, int32_t T, int32_t Umax, double* best_host, int32_t* path_host, bool labels) {
@@ -185,20 +202,22 @@ static int align_check(rnnt_ctx* ctx, const char* what, const float* dev, const 
     return score_check(ctx, what, dev, enc_lens, targets, target_lens, B, T, Umax, best_host, labels);
 }
 
-// back-pointer words and outputs of one call (n path entries per row); grow-only
+// back-pointer words and outputs of one call (n path entries per row)
 static int align_buffers(rnnt_ctx* ctx, size_t bp_words, int B, size_t n) {
     int rc;
-    if ((rc = grow(ctx, &ctx->al_bp, &ctx->al_bp_cap, bp_words))) return rc;
-    return grow(ctx, &ctx->al_out, &ctx->al_out_cap, align_out_doubles(B, n));
+    if ((rc = reserve(ctx, ctx->al_bp, bp_words))) return rc;
+    return reserve(ctx, ctx->al_out, align_out({}, B, n).total);
 }
 
 static int align_download(rnnt_ctx* ctx, hipStream_t s, int B, size_t n, double* best_host, double* nll_host, int32_t* path_host) {
-    std::vector<double> host(align_out_doubles(B, n));
-    HIPCHK(hipMemcpyAsync(host.data(), ctx->al_out, host.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    const size_t total = align_out({}, B, n).total;
+    std::vector<double> host(total);
+    HIPCHK(hipMemcpyAsync(host.data(), ctx->al_out, total * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    memcpy(best_host, host.data(), (size_t)B * sizeof(double));
-    if (nll_host) memcpy(nll_host, host.data() + B, (size_t)B * sizeof(double));
-    memcpy(path_host, host.data() + 2 * (size_t)B, (size_t)B * n * sizeof(int32_t));
+    const AlignOut h = align_out({host.data()}, B, n);
+    memcpy(best_host, h.best, (size_t)B * sizeof(double));
+    if (nll_host) memcpy(nll_host, h.nll, (size_t)B * sizeof(double));
+    memcpy(path_host, h.path, (size_t)B * n * sizeof(int32_t));
     return RNNT_OK;
 }
 
@@ -207,8 +226,8 @@ static int transducer_viterbi_run(rnnt_ctx* ctx, hipStream_t s, const float* pic
     const int ts = Umax > 0 ? Umax : 1;
     {
         ProfScope prof(ctx, s, TAG_SCORE_VITERBI);
-        hipLaunchKernelGGL(transducer_viterbi, dim3(B), dim3(256), 0, s, pick, lens, B, T, Umax + 1, ts, ctx->al_bp, ctx->al_out,
-                           reinterpret_cast<int*>(ctx->al_out + 2 * (size_t)B));
+        const AlignOut o = align_out({ctx->al_out}, B, ts);
+        hipLaunchKernelGGL(transducer_viterbi, dim3(B), dim3(256), 0, s, pick, lens, B, T, Umax + 1, ts, ctx->al_bp, o.best, o.path);
         LAUNCHCHK("transducer_viterbi");
     }
     return align_download(ctx, s, B, ts, best_host, nll_host, emit_host);
@@ -245,7 +264,7 @@ int rnnt_transducer_align(rnnt_ctx* ctx, const float* enc_dev, const int32_t* en
         return rc;
     if (nll_host) {
         ProfScope prof(ctx, s, TAG_SCORE_ALPHA);
-        hipLaunchKernelGGL(transducer_alpha, dim3(B), dim3(256), 0, s, pick, lens, B, T, Umax + 1, ctx->al_out + B);
+        hipLaunchKernelGGL(transducer_alpha, dim3(B), dim3(256), 0, s, pick, lens, B, T, Umax + 1, align_out({ctx->al_out}, B, 0).nll);   // (nll sits in front of the path: its place does not depend on n)
         LAUNCHCHK("transducer_alpha");
     }
     return transducer_viterbi_run(ctx, s, pick, lens, B, T, Umax, best_host, nll_host, emit_host);
@@ -261,8 +280,9 @@ static int ctc_viterbi_run(rnnt_ctx* ctx, hipStream_t s, const float* lp, const 
     if ((rc = score_upload(ctx, s, enc_lens_host, targets_host, target_lens_host, B, Umax, false, host, &tg, &lens, &tok))) return rc;
     {
         ProfScope prof(ctx, s, TAG_SCORE_VITERBI);
-        hipLaunchKernelGGL(ctc_viterbi, dim3(B), dim3(512), 0, s, lp, tg, lens, B, T, ctx->cfg.vocab_size, ts, ctx->cfg.blank_id, ctx->al_bp,
-                           ctx->al_out, reinterpret_cast<int*>(ctx->al_out + 2 * (size_t)B));
+        const AlignOut o = align_out({ctx->al_out}, B, T);
+        hipLaunchKernelGGL(ctc_viterbi, dim3(B), dim3(512), 0, s, lp, tg, lens, B, T, ctx->cfg.vocab_size, ts, ctx->cfg.blank_id, ctx->al_bp, o.best,
+                           o.path);
         LAUNCHCHK("ctc_viterbi");
     }
     return align_download(ctx, s, B, T, best_host, nullptr, align_host);
@@ -285,7 +305,7 @@ int rnnt_ctc_align(rnnt_ctx* ctx, const float* enc_dev, const int32_t* enc_lens_
         return rc;
     if (!ctx->wctc) return fail(ctx, RNNT_ERR_STATE, "rnnt_ctc_align: ctc_head.ctc_lo.* not loaded");
     if ((long long)B * T >= 0x7fffffffLL) return fail(ctx, RNNT_ERR_SHAPE, "rnnt_ctc_align: B=%d T=%d frames in one call", B, T);
-    if ((rc = grow(ctx, &ctx->sc_lat, &ctx->sc_lat_cap, (size_t)B * T * ctx->cfg.vocab_size))) return rc;
+    if ((rc = reserve(ctx, ctx->sc_lat, (size_t)B * T * ctx->cfg.vocab_size))) return rc;
     if ((rc = rnnt_ctc_logprobs(ctx, enc_dev, B * T, ctx->sc_lat, stream))) return rc;
     return ctc_viterbi_run(ctx, (hipStream_t)stream, ctx->sc_lat, enc_lens_host, targets_host, target_lens_host, B, T, Umax, best_host, align_host);
 }

@@ -51,12 +51,50 @@ struct ProfScope {   // records a start/stop event pair around one launch when i
     }
 };
 
-template <typename T>
-int dmalloc(rnnt_ctx* ctx, T** p, size_t n) {
-    if (hipMalloc(reinterpret_cast<void**>(p), n * sizeof(T)) != hipSuccess)
-        return fail(ctx, RNNT_ERR_OOM, "hipMalloc of %zu bytes failed", n * sizeof(T));
+// n elements for an empty owner.  A refused allocation must not linger as HIP's per-thread last error: LAUNCHCHK of the next
+// launch on this thread, in any context, would report it.
+template <typename T, bool HOST>
+int dmalloc(rnnt_ctx* ctx, DevBuf<T, HOST>& b, size_t n) {
+    const size_t bytes = n * sizeof(T);
+    void* q = nullptr;
+    const hipError_t e = HOST ? hipHostMalloc(&q, bytes) : hipMalloc(&q, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(ctx, HOST ? RNNT_ERR_HIP : RNNT_ERR_OOM, "%s of %zu bytes failed", HOST ? "hipHostMalloc" : "hipMalloc", bytes);
+    }
+    b.p = static_cast<T*>(q);
+    b.cap = q ? n : 0;
+    if (!HOST) live_device_bytes += (int64_t)(b.cap * sizeof(T));
     return RNNT_OK;
 }
+
+// at least n elements: grow-only, contents are not preserved; a buffer that already holds n is left alone
+template <typename T, bool HOST>
+int reserve(rnnt_ctx* ctx, DevBuf<T, HOST>& b, size_t n) {
+    if (n <= b.cap) return RNNT_OK;
+    b.release();
+    return dmalloc(ctx, b, n);
+}
+
+// exactly n elements: re-allocated when the size differs (the caller has synchronised the stream that may still read the old one)
+template <typename T>
+int reserve_exact(rnnt_ctx* ctx, DevBuf<T>& b, size_t n) {
+    if (n != b.cap) b.release();
+    return reserve(ctx, b, n);
+}
+
+// The layout of a carved buffer, written once: take(n) hands out consecutive regions of n elements.  Walk it without a base for the
+// size to reserve (off), then over the buffer -- or over a host copy of the same block -- for the pointers.
+template <typename T>
+struct Carve {
+    T* base = nullptr;
+    size_t off = 0;
+    T* take(size_t n) {
+        T* r = base ? base + off : nullptr;
+        off += n;
+        return r;
+    }
+};
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is per device: keep the "already raised" record in the context (one context = one
 // device, one host thread at a time), not in a process-wide static (a second device, or a second host thread, would miss it).
@@ -99,7 +137,7 @@ inline void div_magic(int d, unsigned& magic, int& shift) {
 // fast-path flags and division magics of one GEMM descriptor (gemm16's a_row_off / c_row_off)
 int prepare_gemm(rnnt_ctx* ctx, GemmP& g) {
     g.Wh = g.Wl = nullptr;
-    if (ctx->numerics != RNNT_NUM_F32 && ctx->blob_hi && g.W >= ctx->blob && g.W < ctx->blob + ctx->blob_floats) {
+    if (ctx->numerics != RNNT_NUM_F32 && ctx->blob_hi && g.W >= ctx->blob && g.W < ctx->blob + ctx->blob.cap) {
         g.Wh = ctx->blob_hi + (g.W - ctx->blob);
         g.Wl = ctx->blob_lo + (g.W - ctx->blob);
     }
@@ -557,16 +595,6 @@ int emit_frames(rnnt_ctx* ctx, hipStream_t s, const float* x, int B, int tq, int
     else { g.a_n1 = tq; g.a_n2 = tq; g.a_s0 = fs; g.a_s1 = 0; g.a_s2 = D; }
     g.c_n = tq; g.c_s0 = fs; g.c_r0 = fpos; g.c_mod = BIG; g.c_s1 = D;
     return launch_gemm(ctx, s, &g, 1, TAG_ENC_PROJ);
-}
-
-template <typename T>
-int grow(rnnt_ctx* ctx, T** p, size_t* cap, size_t need) {
-    if (need <= *cap) return RNNT_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    int rc = dmalloc(ctx, p, need);
-    *cap = rc ? 0 : need;
-    return rc;
 }
 
 // ---- per-slot beam state of the stream pool (rnnt_pool_chunk_beam; kernels in rnnt_beam.hip.h) --------------------------------------

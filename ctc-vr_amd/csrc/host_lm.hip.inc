@@ -44,8 +44,8 @@ int lm_res_upload(rnnt_ctx* ctx, hipStream_t s, const std::vector<std::vector<Lm
     ctx->lm_res_ok = 0;
     if (!lm_res_plan(tabs, ctx->lm_rhdr_host, ctx->lm_rrows_host, ctx->lm_res_stride)) return RNNT_OK;
     int rc;
-    if ((rc = grow(ctx, &ctx->lm_rhdr, &ctx->lm_rhdr_cap, ctx->lm_rhdr_host.size()))) return rc;
-    if ((rc = grow(ctx, &ctx->lm_rrows, &ctx->lm_rrows_cap, ctx->lm_rrows_host.size()))) return rc;
+    if ((rc = reserve(ctx, ctx->lm_rhdr, ctx->lm_rhdr_host.size()))) return rc;
+    if ((rc = reserve(ctx, ctx->lm_rrows, ctx->lm_rrows_host.size()))) return rc;
     HIPCHK(hipMemcpyAsync(ctx->lm_rhdr, ctx->lm_rhdr_host.data(), ctx->lm_rhdr_host.size() * sizeof(LmResHdr), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(ctx->lm_rrows, ctx->lm_rrows_host.data(), ctx->lm_rrows_host.size() * sizeof(LmRow), hipMemcpyHostToDevice, s));
     ctx->lm_res_ok = 1;
@@ -123,19 +123,17 @@ int encoder_chunks_lm(rnnt_ctx* ctx, hipStream_t s, const float* fbank_dev, int 
     const long long M = (long long)B * F;
     if (M * RNNT_FSUB >= (1ll << 31)) return RNNT_OK;
     int rc;
-    // ---- buffers (grow-only; sized by the context limits so one allocation serves every call) ---------------------------------
+    // ---- buffers (sized by the context limits so one allocation serves every call) ----------------------------------------------
     const int fmax = std::max(ctx->fcap, ctx->tmax);              // frames per stream a call can bring (a full-context pass: tmax)
     if (F > fmax) return RNNT_OK;
     const int gs = RNNT_LORDER + fmax;                            // rows per stream of a layer's linear post-GLU buffer
-    if (!ctx->lm_h) {
-        const size_t rows = (size_t)Bm * fmax;
-        if ((rc = dmalloc(ctx, &ctx->lm_x, rows * D))) return rc;
-        if ((rc = dmalloc(ctx, &ctx->lm_h, rows * FF))) return rc;
-        if ((rc = dmalloc(ctx, &ctx->lm_q, rows * D))) return rc;
-        if ((rc = dmalloc(ctx, &ctx->lm_a, rows * D))) return rc;
-        if ((rc = dmalloc(ctx, &ctx->lm_d, rows * D))) return rc;
-        if ((rc = dmalloc(ctx, &ctx->lm_g, (size_t)L * Bm * gs * D))) return rc;
-    }
+    const size_t rows = (size_t)Bm * fmax;
+    if ((rc = reserve(ctx, ctx->lm_x, rows * D))) return rc;
+    if ((rc = reserve(ctx, ctx->lm_h, rows * FF))) return rc;
+    if ((rc = reserve(ctx, ctx->lm_q, rows * D))) return rc;
+    if ((rc = reserve(ctx, ctx->lm_a, rows * D))) return rc;
+    if ((rc = reserve(ctx, ctx->lm_d, rows * D))) return rc;
+    if ((rc = reserve(ctx, ctx->lm_g, (size_t)L * Bm * gs * D))) return rc;
     float* x = ctx->lm_x;
     bool ctx_in_done = false;                                      // (c) already launched on the side stream
     // An error exit between the fork onto the side stream and the join still joins it: work already enqueued there writes x, lm_g
@@ -149,7 +147,7 @@ int encoder_chunks_lm(rnnt_ctx* ctx, hipStream_t s, const float* fbank_dev, int 
         }
     } side_join{ctx, s, false};
     // ---- (a) subsampling: every run of equal-length chunks in one slab, stream-major ------------------------------------------
-    if ((rc = grow(ctx, &ctx->wf_starts, &ctx->wf_starts_cap, (size_t)C))) return rc;
+    if ((rc = reserve(ctx, ctx->wf_starts, (size_t)C))) return rc;
     HIPCHK(hipMemcpyAsync(ctx->wf_starts, chunk_start, C * sizeof(int), hipMemcpyHostToDevice, s));
     {
         const size_t slab_bytes = 2048ull << 20;
@@ -179,11 +177,11 @@ int encoder_chunks_lm(rnnt_ctx* ctx, hipStream_t s, const float* fbank_dev, int 
             if (side && k + 1 == cls.size()) { need1b = per1 * nc; need2b = per2 * nc; }
             else { if (!fused_cls(c0, nc)) need1 = std::max(need1, per1 * nc); need2 = std::max(need2, per2 * nc); }
         }
-        if ((rc = grow(ctx, &ctx->lm_y1, &ctx->lm_y1_cap, need1))) return rc;
-        if ((rc = grow(ctx, &ctx->lm_y2, &ctx->lm_y2_cap, need2))) return rc;
+        if ((rc = reserve(ctx, ctx->lm_y1, need1))) return rc;
+        if ((rc = reserve(ctx, ctx->lm_y2, need2))) return rc;
         if (side) {
-            if ((rc = grow(ctx, &ctx->lm_y1b, &ctx->lm_y1b_cap, need1b))) return rc;
-            if ((rc = grow(ctx, &ctx->lm_y2b, &ctx->lm_y2b_cap, need2b))) return rc;
+            if ((rc = reserve(ctx, ctx->lm_y1b, need1b))) return rc;
+            if ((rc = reserve(ctx, ctx->lm_y2b, need2b))) return rc;
             if (!ctx->sub_stream) HIPCHK(hipStreamCreateWithFlags(&ctx->sub_stream, hipStreamNonBlocking));
             if (!ctx->sub_ev[0]) {
                 HIPCHK(hipEventCreateWithFlags(&ctx->sub_ev[0], hipEventDisableTiming));
@@ -231,11 +229,11 @@ int encoder_chunks_lm(rnnt_ctx* ctx, hipStream_t s, const float* fbank_dev, int 
             need1 = std::max(need1, n * sub1_len(kv.first) * RNNT_F1 * D);
             need2 = std::max(need2, n * sub_len(kv.first) * RNNT_FSUB * D);
         }
-        if ((rc = grow(ctx, &ctx->lm_y1, &ctx->lm_y1_cap, need1))) return rc;
-        if ((rc = grow(ctx, &ctx->lm_y2, &ctx->lm_y2_cap, need2))) return rc;
-        if ((rc = grow(ctx, &ctx->rg_fb, &ctx->rg_fb_cap, need_fb))) return rc;
-        if ((rc = grow(ctx, &ctx->rg_xt, &ctx->rg_xt_cap, need_xt))) return rc;
-        if ((rc = grow(ctx, &ctx->rg_ent, &ctx->rg_ent_cap, n_ent))) return rc;
+        if ((rc = reserve(ctx, ctx->lm_y1, need1))) return rc;
+        if ((rc = reserve(ctx, ctx->lm_y2, need2))) return rc;
+        if ((rc = reserve(ctx, ctx->rg_fb, need_fb))) return rc;
+        if ((rc = reserve(ctx, ctx->rg_xt, need_xt))) return rc;
+        if ((rc = reserve(ctx, ctx->rg_ent, n_ent))) return rc;
         std::vector<int2> ent;
         ent.reserve(n_ent);
         for (auto& kv : classes)                                    // per class: gather entries (stream, first fbank frame), then scatter entries (stream, first row)
@@ -294,7 +292,7 @@ int encoder_chunks_lm(rnnt_ctx* ctx, hipStream_t s, const float* fbank_dev, int 
         for (int k = 0; k < LM_ROWS; ++k) empty.r[k].f = -1;
         flat.assign((size_t)B * rg_blocks, empty);
         for (int b = 0; b < B; ++b) std::copy(per[b].begin(), per[b].end(), flat.begin() + (size_t)b * rg_blocks);
-        if ((rc = grow(ctx, &ctx->lm_blocks, &ctx->lm_blocks_cap, flat.size()))) return rc;
+        if ((rc = reserve(ctx, ctx->lm_blocks, flat.size()))) return rc;
         HIPCHK(hipMemcpyAsync(ctx->lm_blocks, flat.data(), flat.size() * sizeof(LmBlock), hipMemcpyHostToDevice, s));
         ctx->lm_key.clear();                                        // never equal to a uniform call's key
         std::vector<std::vector<LmRow>> tabs(B);
@@ -325,7 +323,7 @@ int encoder_chunks_lm(rnnt_ctx* ctx, hipStream_t s, const float* fbank_dev, int 
             }
         }
         flush();
-        if ((rc = grow(ctx, &ctx->lm_blocks, &ctx->lm_blocks_cap, blocks.size()))) return rc;
+        if ((rc = reserve(ctx, ctx->lm_blocks, blocks.size()))) return rc;
         HIPCHK(hipMemcpyAsync(ctx->lm_blocks, blocks.data(), blocks.size() * sizeof(LmBlock), hipMemcpyHostToDevice, s));
         if ((rc = lm_res_upload(ctx, s, {lm_rows_of(blocks.data(), blocks.size())}))) return rc;
         ctx->lm_key = plan_key;

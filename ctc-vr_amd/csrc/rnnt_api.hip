@@ -15,6 +15,7 @@
 #include <string>
 #include <algorithm>
 #include <array>
+#include <atomic>
 #include <vector>
 
 namespace {
@@ -25,7 +26,7 @@ constexpr int BIG = INT_MAX;
 struct LayerW {
     const float *ln_ffm_g, *ln_ffm_b, *w1m, *b1m, *w2m, *b2m;
     const float *ln_mha_g, *ln_mha_b, *wq, *bq, *wk, *bk, *wv, *bv, *wo, *bo, *pu, *pv;
-    float* ptab;   // [5000][256] = pe * W_pos^T
+    float* ptab;   // [5000][256] = pe * W_pos^T (view of rnnt_ctx::ptab)
     const float *wpos;
     const float *ln_conv_g, *ln_conv_b, *pw1, *bpw1, *wdw_t, *bdw, *bn_s, *bn_t, *pw2, *bpw2;
     const float *ln_ff_g, *ln_ff_b, *w1, *b1, *w2, *b2, *ln_fin_g, *ln_fin_b;
@@ -76,6 +77,31 @@ struct CtxGraph {
     std::vector<double> tscore, nscore, oscore;
 };
 
+// Device bytes currently held through DevBuf owners, process-wide (rnnt_live_device_bytes).
+std::atomic<int64_t> live_device_bytes{0};
+
+// Owner of one allocation -- device memory, or pinned host memory when HOST: a pointer and its capacity in elements, freed by the
+// destructor.  It converts to T*, so launches, copies and pointer arithmetic read as with a raw pointer.  Allocation goes through
+// reserve / reserve_exact (host_launch.hip.inc); release() is the only place memory is given back.
+template <typename T, bool HOST = false>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
+    void release() {
+        if (p && HOST) (void)hipHostFree(p);
+        else if (p) { (void)hipFree(p); live_device_bytes -= (int64_t)(cap * sizeof(T)); }
+        p = nullptr;
+        cap = 0;
+    }
+    operator T*() const { return p; }
+};
+template <typename T>
+using PinnedBuf = DevBuf<T, true>;
+
 enum WfType { WF_FFN1M, WF_FFN2M, WF_QKV, WF_OUT, WF_PW1, WF_PW2, WF_FFN1, WF_FFN2, WF_ATTN, WF_DW, WF_LN, WF_BLOCK_FRONT, WF_BLOCK_BACK };
 
 }  // namespace
@@ -88,61 +114,57 @@ struct rnnt_ctx {
     int numerics = 0;
 
     // packed weights (one device blob)
-    float* blob = nullptr;
-    size_t blob_floats = 0;
-    unsigned short *blob_hi = nullptr, *blob_lo = nullptr;   // 16-bit hi / lo planes of the blob (split-operand numerics modes)
+    DevBuf<float> blob;
+    DevBuf<unsigned short> blob_hi, blob_lo;                 // 16-bit hi / lo planes of the blob (split-operand numerics modes)
     // fused Conformer-block kernels (rnnt_fused.hip.h): fragment-major packed layer weights of the current numerics mode and
     // the per-layer pointer table in device memory
-    uint4* fuse_w = nullptr;
-    size_t fuse_w_vecs = 0;
-    LayerDev* layers_dev = nullptr;
+    DevBuf<uint4> fuse_w;
+    DevBuf<LayerDev> layers_dev;
     const uint4* conv2_wp = nullptr;          // fragment-major packed conv2 weights of the current numerics mode (gemm_bw)
-    unsigned char* joint_wfrag = nullptr;     // joint.ffn_out as the LDS-DMA ring's stage stream (pack_joint_w), split modes and bf16
-    size_t joint_wfrag_bytes = 0;
-    int* joint_counter = nullptr;             // joint_lattice_rows' dynamic row-tile queue (zeroed before every launch)
+    DevBuf<unsigned char> joint_wfrag;        // joint.ffn_out as the LDS-DMA ring's stage stream (pack_joint_w), split modes and bf16
+    DevBuf<int> joint_counter;                // joint_lattice_rows' dynamic row-tile queue (zeroed before every launch)
     std::map<const void*, int> dyn_lds;       // kernels whose dynamic-LDS limit was raised for THIS context's device (ensure_dyn_lds)
     std::vector<LayerDev> layers_host;        // host copy (packed-weight pointers for gemm_as / ffn_as launches)
     int use_as = 1;                            // RNNT_AS=0: LDS-tiled gemm_bf for every layer contraction of the layer-major schedule
     int use_fused = 1;                         // RNNT_FUSED=0: the unfused wavefront (11 launches per stage)
-    FuseItem* wf_ftab = nullptr;
-    size_t wf_fcap = 0;
+    DevBuf<FuseItem> wf_ftab;
     int wf_fused_plan = 0;                     // the cached plan (wf_key) was built for the fused schedule
     LayerW lw[L];
+    DevBuf<float> ptab[L];                     // LayerW::ptab
     const float *conv1_wt, *conv1_b, *conv2_w, *conv2_b, *emb_w, *emb_b, *pe, *after_g, *after_b;
     const float *ln_conv_g_all, *ln_conv_b_all, *glu0;
     const float *whh_il, *wih_il, *b_lstm_il, *pred_embed, *wpr, *bpr, *wenc, *benc, *wpf, *bpf, *wout, *bout;
-    float* egate = nullptr;   // [vocab][1024] interleaved input-gate table
+    DevBuf<float> egate;      // [vocab][1024] interleaved input-gate table
 
     // geometry
     int tmax = 0, t1max = 0, cap = 0, tcap = 0, fcap = 0, fstride = 0, vpad = 0;
     // activations
-    float *y1 = nullptr, *y2 = nullptr, *x = nullptr, *hbuf = nullptr, *qbuf = nullptr, *abuf = nullptr, *dbuf = nullptr;
-    float *kcache = nullptr, *vcache = nullptr, *gring = nullptr, *xring = nullptr;
-    float *encbuf = nullptr, *encp = nullptr;
+    DevBuf<float> y1, y2, x, hbuf, qbuf, abuf, dbuf;
+    DevBuf<float> kcache, vcache, gring, xring;
+    DevBuf<float> encbuf, encp;
     // decode state
     // LSTM state: two buffers [2][B][256] per h and c; sel[b] says which one is committed, the other receives the candidate
-    float *h = nullptr, *c = nullptr, *pred = nullptr, *z = nullptr, *logits = nullptr;
-    int *tok = nullptr, *fidx = nullptr, *nsym = nullptr, *count = nullptr, *tokens = nullptr, *n_active = nullptr, *klen = nullptr, *sel = nullptr;
-    unsigned long long* key = nullptr;
-    int* dec_ctrl = nullptr;   // persistent decoder control block: [0] frames_ready, [1] error, [2] evaluations, [4] abort word of greedy_multi
+    DevBuf<float> h, c, pred, z, logits;
+    DevBuf<int> tok, fidx, nsym, count, tokens, n_active, klen, sel;
+    DevBuf<unsigned long long> key;
+    DevBuf<int> dec_ctrl;      // persistent decoder control block: [0] frames_ready, [1] error, [2] evaluations, [4] abort word of greedy_multi
     int use_persistent = 1;
     int attn_stream = 1;       // RNNT_ATTN_STREAM=0: LDS-tiled attention kernel for every chunk
     int fuse_after_norm = 1;   // RNNT_FUSE_AFTER_NORM=0: keep after_norm as its own launch in the pipelined greedy path
     int overlap_ok = -1;       // -1 not probed; 1: kernels of the decode stream run concurrently with the caller's stream
     int use_multi = 1;         // RNNT_DEC_MULTI=0: one CU per stream (greedy_stream) instead of greedy_multi (4 CUs per stream)
     int n_cus = 0;
-    unsigned long long *gm_x1 = nullptr, *gm_xa = nullptr;   // greedy_multi mailboxes
-    long long* gm_dbg = nullptr;              // [16] greedy_multi phase timers (RNNT_GM_DBG=1)
+    DevBuf<unsigned long long> gm_x1, gm_xa;  // greedy_multi mailboxes
+    DevBuf<long long> gm_dbg;                 // [16] greedy_multi phase timers (RNNT_GM_DBG=1)
     const float *wjc = nullptr, *bjc = nullptr;   // folded joint.pred_ffn o predictor.projection
     const float *wctc = nullptr, *bctc = nullptr; // ctc_head.ctc_lo (optional)
     // beam search: state pools [rows][n_steps+1][512] (ping-pong), per-row buffers
     int max_rows = 0;
-    float *pool[2] = {nullptr, nullptr}, *bpred = nullptr, *bz = nullptr, *blogits = nullptr, *b_blank = nullptr, *b_toplp = nullptr;
-    int *b_tok = nullptr, *b_frame = nullptr, *b_active = nullptr, *b_steps = nullptr, *b_toptok = nullptr, *b_srcrow = nullptr, *b_srcstep = nullptr;
+    DevBuf<float> pool[2], bpred, bz, blogits, b_blank, b_toplp;
+    DevBuf<int> b_tok, b_frame, b_active, b_steps, b_toptok, b_srcrow, b_srcstep;
     int pool_cur = 0;
-    int* pinned = nullptr;   // host-pinned scratch (n_active read-back)
-    float* scratch = nullptr;  // device scratch for getters / step API
-    size_t scratch_floats = 0;
+    PinnedBuf<int> pinned;   // host-pinned scratch (n_active read-back)
+    DevBuf<float> scratch;   // device scratch for getters / step API
 
     // stream state (all streams lock step)
     int n_streams = 0;
@@ -155,17 +177,15 @@ struct rnnt_ctx {
     // reads, written by one async copy from the pinned host copy (pool_ev: that copy has left the host buffer).
     std::vector<SlotPos> slot_pos;
     bool pool_mode = false;
-    int* pool_tab = nullptr;                   // device: [max_streams] PoolRow + [max_streams] int
-    int* pool_tab_host = nullptr;              // pinned
+    DevBuf<int> pool_tab;                      // device: [max_streams] PoolRow + [max_streams] int
+    PinnedBuf<int> pool_tab_host;
     hipEvent_t pool_ev = nullptr;
     int gemm_m_cap = 0;                        // > 0 during a pool call: GEMM kernels / tiles are chosen as for at most this many rows
     // wavefront (whole-utterance) path: per-chunk x rows, per-layer scratch, subsampling slabs, descriptor tables
-    float *wf_x = nullptr, *wf_h = nullptr, *wf_q = nullptr, *wf_a = nullptr, *wf_d = nullptr, *wf_y1 = nullptr, *wf_y2 = nullptr;
+    DevBuf<float> wf_x, wf_h, wf_q, wf_a, wf_d, wf_y1, wf_y2;
     int wf_slab = 0;
-    int* wf_starts = nullptr;
-    size_t wf_starts_cap = 0;
-    GemmP* wf_gtab = nullptr; AttnP* wf_atab = nullptr; DwP* wf_dtab = nullptr; LnP* wf_ltab = nullptr;
-    size_t wf_gcap = 0, wf_acap = 0, wf_dcap = 0, wf_lcap = 0;
+    DevBuf<int> wf_starts;
+    DevBuf<GemmP> wf_gtab; DevBuf<AttnP> wf_atab; DevBuf<DwP> wf_dtab; DevBuf<LnP> wf_ltab;
     hipStream_t dec_stream = nullptr;          // decode runs here while the encoder wavefront runs on the caller's stream
     hipStream_t sub_stream = nullptr;          // subsampling slabs
     int wf_sub_async = 1;                      // RNNT_WF_SUB_ASYNC=0: the wavefront's subsampling slabs on the caller's stream
@@ -186,22 +206,18 @@ struct rnnt_ctx {
     int attn_bf = 1;                           // RNNT_ATTN_BF=0: exact-f32 MFMA attention (rel_attention_lm_mfma) in every mode
     int attn_resident = 1;                     // RNNT_ATTN_RESIDENT=0: always the tiled rel_attention_lm_bf, never rel_attention_lm_res
     int conv1_fuse = 1;                        // RNNT_CONV1_FUSE=0: conv1_relu_rows + gemm_bw over the y1 slab, never gemm_bw_c1
-    float *lm_x = nullptr, *lm_h = nullptr, *lm_q = nullptr, *lm_a = nullptr, *lm_d = nullptr, *lm_g = nullptr, *lm_y1 = nullptr, *lm_y2 = nullptr;
-    size_t lm_y1_cap = 0, lm_y2_cap = 0, lm_blocks_cap = 0;
-    float *lm_y1b = nullptr, *lm_y2b = nullptr;      // slabs of the tail chunk class (subsampled on sub_stream beside the main class)
-    size_t lm_y1b_cap = 0, lm_y2b_cap = 0;
+    DevBuf<float> lm_x, lm_h, lm_q, lm_a, lm_d, lm_g, lm_y1, lm_y2;
+    DevBuf<float> lm_y1b, lm_y2b;                  // slabs of the tail chunk class (subsampled on sub_stream beside the main class)
     hipEvent_t sub_ev[2] = {nullptr, nullptr};     // fork / join of the tail class on sub_stream
     // ragged batches (rnnt_decode_ragged): gathered tail frames, their subsampled rows, gather / scatter entries
-    float *rg_fb = nullptr, *rg_xt = nullptr;
-    int2* rg_ent = nullptr;
-    size_t rg_fb_cap = 0, rg_xt_cap = 0, rg_ent_cap = 0;
-    LmBlock* lm_blocks = nullptr;
+    DevBuf<float> rg_fb, rg_xt;
+    DevBuf<int2> rg_ent;
+    DevBuf<LmBlock> lm_blocks;
     std::vector<LmBlock> lm_blocks_host;
     std::vector<int> lm_key;
     // rel_attention_lm_res tables (host_lm.hip.inc: lm_res_plan), rebuilt with the block table
-    LmResHdr* lm_rhdr = nullptr;
-    LmRow* lm_rrows = nullptr;
-    size_t lm_rhdr_cap = 0, lm_rrows_cap = 0;
+    DevBuf<LmResHdr> lm_rhdr;
+    DevBuf<LmRow> lm_rrows;
     std::vector<LmResHdr> lm_rhdr_host;
     std::vector<LmRow> lm_rrows_host;
     int lm_res_ok = 0, lm_res_stride = 0;
@@ -211,51 +227,44 @@ struct rnnt_ctx {
     int use_beam_chain = 1;    // RNNT_BEAM_CHAIN=0: launched extension steps (5 kernels + one host sync per step)
     // device-resident bookkeeping (rnnt_beam_decode): token lists [2][max_rows][bd_lcap] (ping-pong, grown on demand), per-row
     // lengths / scores / hashes [2][max_rows], hypotheses per stream and per-stream end frames [max_streams]
-    int* bd_tok = nullptr;
-    size_t bd_tok_cap = 0;
-    int *bd_len = nullptr, *bd_nh = nullptr, *bd_fend = nullptr;
-    double* bd_sc = nullptr;
-    unsigned long long* bd_hs = nullptr;
+    DevBuf<int> bd_tok, bd_len, bd_nh, bd_fend;
+    DevBuf<double> bd_sc;
+    DevBuf<unsigned long long> bd_hs;
     // per-slot beam state of the stream pool (rnnt_pool_chunk_beam), separate from the lock-step state above and allocated on the
     // first beam call: hypothesis i of slot b is row b * max_beam + i of two buffer sets -- state pools, token lists
     // [2][max_rows][max_tokens], lengths / scores / hashes [2][max_rows] -- plus the hypotheses per slot.  Slots advance
     // independently, so the current set is per slot (ps_cur, host); ps_lbound is a host upper bound of the slot's longest hypothesis.
-    float* ps_pool[2] = {nullptr, nullptr};
-    int *ps_tok = nullptr, *ps_len = nullptr, *ps_nh = nullptr;
-    double* ps_sc = nullptr;
-    unsigned long long* ps_hs = nullptr;
+    DevBuf<float> ps_pool[2];
+    DevBuf<int> ps_tok, ps_len, ps_nh;
+    DevBuf<double> ps_sc;
+    DevBuf<unsigned long long> ps_hs;
     std::vector<int> ps_cur, ps_lbound;
-    // feature front-end (rnnt_fbank): DFT / mel matrices for (fb_rate, fb_nfft) and grow-only work buffers
-    float *fb_dft = nullptr, *fb_mel = nullptr, *fb_pad = nullptr, *fb_spec = nullptr, *fb_pow = nullptr;
-    size_t fb_pad_cap = 0, fb_spec_cap = 0, fb_pow_cap = 0;
+    // feature front-end (rnnt_fbank): DFT / mel matrices for (fb_rate, fb_nfft) and work buffers
+    DevBuf<float> fb_dft, fb_mel, fb_pad, fb_spec, fb_pow;
     int fb_rate = 0, fb_nfft = 0;
-    // teacher-forced scoring (api_score.hip.inc): grow-only work buffers -- predictor outputs / LSTM ping-pong / internal pick
-    // lattice (sc_f), step tokens / targets / lengths (sc_i), per-utterance results (sc_nll), and the materialised log-softmax
-    // lattice of the fallback path or the CTC log-probabilities (sc_lat)
-    float *sc_f = nullptr, *sc_lat = nullptr;
-    int* sc_i = nullptr;
-    double* sc_nll = nullptr;
-    size_t sc_f_cap = 0, sc_lat_cap = 0, sc_i_cap = 0, sc_nll_cap = 0;
-    // forced alignment (api_score.hip.inc): grow-only back-pointer words and the outputs of one call (best | nll | path)
-    unsigned* al_bp = nullptr;
-    double* al_out = nullptr;
-    size_t al_bp_cap = 0, al_out_cap = 0;
-    // prefix beam search (api_prefix.hip.inc): its own grow-only buffers, sized by B * beam rows and T + 1 tokens -- projected frames /
-    // CTC log-probabilities / state pools / top-k values (pb_f), token lists / lengths / counts / top-k tokens (pb_i), scores and
-    // hashes (pb_d), and the packed block of one call's results (pb_out)
-    float* pb_f = nullptr;
-    int* pb_i = nullptr;
-    double *pb_d = nullptr, *pb_out = nullptr;
-    size_t pb_f_cap = 0, pb_i_cap = 0, pb_d_cap = 0, pb_out_cap = 0;
+    // teacher-forced scoring (api_score.hip.inc): predictor outputs / LSTM ping-pong / internal pick lattice (sc_f), step tokens /
+    // targets / lengths (sc_i), per-utterance results (sc_nll), and the materialised log-softmax lattice of the fallback path or
+    // the CTC log-probabilities (sc_lat)
+    DevBuf<float> sc_f, sc_lat;
+    DevBuf<int> sc_i;
+    DevBuf<double> sc_nll;
+    // forced alignment (api_score.hip.inc): back-pointer words and the outputs of one call (best | nll | path)
+    DevBuf<unsigned> al_bp;
+    DevBuf<double> al_out;
+    // prefix beam search (api_prefix.hip.inc), sized by B * beam rows and T + 1 tokens -- projected frames / CTC log-probabilities /
+    // state pools / top-k values (pb_f), token lists / lengths / counts / top-k tokens (pb_i), scores and hashes (pb_d), and the
+    // packed block of one call's results (pb_out)
+    DevBuf<float> pb_f;
+    DevBuf<int> pb_i;
+    DevBuf<double> pb_d, pb_out;
     // CTC prefix beam search (api_ctc_prefix.hip.inc): the context graph of rnnt_context_set (host tables, device ints / doubles) and
-    // the call's own grow-only buffers -- lengths, prefix and time arenas, packed results (cp_i), scores (cp_d), log-probabilities
-    // of rnnt_ctc_prefix_beam_decode (cp_lp)
+    // the call's own buffers -- lengths, prefix and time arenas, packed results (cp_i), scores (cp_d), log-probabilities of
+    // rnnt_ctc_prefix_beam_decode (cp_lp)
     CtxGraph cg;
     bool cg_on = false;
-    int *cg_i = nullptr, *cp_i = nullptr;
-    double *cg_d = nullptr, *cp_d = nullptr;
-    float* cp_lp = nullptr;
-    size_t cg_i_cap = 0, cg_d_cap = 0, cp_i_cap = 0, cp_d_cap = 0, cp_lp_cap = 0;
+    DevBuf<int> cg_i, cp_i;
+    DevBuf<double> cg_d, cp_d;
+    DevBuf<float> cp_lp;
     hipStream_t cap_stream = nullptr;          // stream-capture scratch stream
     struct DecGraph { int n_streams, k; hipGraphExec_t exec; };
     std::vector<DecGraph> dec_graphs;          // K greedy steps captured once per (n_streams, K)
@@ -265,6 +274,16 @@ struct rnnt_ctx {
     int prof_tag = -1;
     std::vector<hipEvent_t> prof_ev;
     size_t prof_used = 0;
+
+    // The only free list: streams, events and graphs here, every buffer through its owner's destructor.  No user-provided
+    // constructor -- rnnt_create's `new rnnt_ctx()` value-initialises lw[] and the raw weight views to null.
+    ~rnnt_ctx() {
+        for (auto& g : dec_graphs) (void)hipGraphExecDestroy(g.exec);
+        for (hipEvent_t e : {pool_ev, sub_ev[0], sub_ev[1]}) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : prof_ev) (void)hipEventDestroy(e);
+        for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
+        for (hipStream_t st : {dec_stream, cap_stream, sub_stream}) if (st) (void)hipStreamDestroy(st);
+    }
 };
 
 #include "host_launch.hip.inc"

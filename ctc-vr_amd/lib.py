@@ -22,6 +22,7 @@ SIGNATURES = {
     "rnnt_destroy": (None, [c_vp]),
     "rnnt_last_error": (ctypes.c_char_p, [c_vp]),
     "rnnt_abi_version": (c_i32, []),
+    "rnnt_live_device_bytes": (c_i64, []),
     "rnnt_load_tensor": (c_i32, [c_vp, ctypes.c_char_p, c_vp, c_i32, ctypes.POINTER(c_i64)]),
     "rnnt_decode_ragged": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp]),
     "rnnt_load_packed": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(c_i32), ctypes.POINTER(c_i64)]),
@@ -108,6 +109,7 @@ class RnntError(RuntimeError):
 # rnnt_status values of a refusal (call outside its supported range / sequence), as opposed to a HIP failure
 ERR_ARG, ERR_STATE = -1, -5
 ERR_SHAPE = -2
+ERR_OOM = -3          # a device allocation was refused
 
 
 def load(build_if_needed=True):
@@ -134,6 +136,11 @@ def load(build_if_needed=True):
         fn.restype, fn.argtypes = res, args
     _LIB = lib
     return lib
+
+
+def live_device_bytes():
+    """rnnt_live_device_bytes: device bytes the contexts of this process hold at this moment."""
+    return int(load().rnnt_live_device_bytes())
 
 
 def _np_ptr(a):
@@ -257,7 +264,7 @@ class RnntEngine:
             if self.ctx:
                 self.lib.rnnt_destroy(self.ctx)
                 self.ctx = c_vp()
-            raise RnntError(f"rnnt_create: {msg} (status {rc})")
+            raise RnntError(f"rnnt_create: {msg} (status {rc})", rc)
         self.n_streams = 0
 
     def close(self):

@@ -83,6 +83,11 @@ int rnnt_create(const rnnt_config* cfg, rnnt_ctx** out);
 void rnnt_destroy(rnnt_ctx* ctx);
 const char* rnnt_last_error(const rnnt_ctx* ctx);
 int rnnt_abi_version(void);
+/* Device bytes that the contexts of this process hold at this moment: the sum of the sizes requested from hipMalloc for every
+ * buffer of every live context (create-time buffers, weights, and the work buffers that entry points allocate on their first call
+ * or grow), not the allocator's rounding.  rnnt_destroy gives all of a context's bytes back; a failed rnnt_create followed by
+ * rnnt_destroy leaves the count where it was.  For sizing a deployment: read it after one call of each entry point in use. */
+int64_t rnnt_live_device_bytes(void);
 
 /* -- weights --------------------------------------------------------------------------------- */
 /* replaces load_state_dict(checkpoint['model']) (online_rnnt_decode.py:49-50): one call per
