@@ -200,6 +200,7 @@ int rnnt_context_set(rnnt_ctx* ctx, int32_t n_phrases, const int32_t* phrase_len
     if (n_phrases == 0) {
         ctx->cg_on = false;
         ctx->cg = CtxGraph();
+        ++ctx->cg_gen;
         return RNNT_OK;
     }
     CtxGraph g;
@@ -223,6 +224,7 @@ int rnnt_context_set(rnnt_ctx* ctx, int32_t n_phrases, const int32_t* phrase_len
     HIPCHK(hipMemcpy(ctx->cg_d, hd.data(), hd.size() * sizeof(double), hipMemcpyHostToDevice));
     ctx->cg = std::move(g);
     ctx->cg_on = true;
+    ++ctx->cg_gen;                                                   // a pool search biased by the previous graph holds its node ids (api_pool_ctc.hip.inc)
     return RNNT_OK;
 }
 
@@ -351,14 +353,10 @@ int rnnt_ctc_prefix_beam_logprobs(rnnt_ctx* ctx, const float* lp_dev, const int3
     if ((rc = reserve(ctx, ctx->cp_d, 2 * R))) return rc;
     i = {ctx->cp_i};
     lay();   // pointers
-    p.o_nh = o.nh; p.o_len = o.len; p.o_tok = o.tok; p.o_time = o.time;
-    p.o_sc = ctx->cp_d; p.o_cs = ctx->cp_d + R;
+    p.o.nh = o.nh; p.o.len = o.len; p.o.tok = o.tok; p.o.time = o.time;
+    p.o.sc = ctx->cp_d; p.o.cs = ctx->cp_d + R;
     p.lp = lp_dev; p.lens = d_lens; p.T = T; p.V = V; p.blank = ctx->cfg.blank_id; p.beam = beam_size; p.lcap = (int)lcap;
-    if (use_context) {
-        const size_t n = ctx->cg.token.size(), m = ctx->cg.ctok.size();
-        p.g_fail = ctx->cg_i; p.g_off = ctx->cg_i + n; p.g_ctok = ctx->cg_i + 2 * n + 1; p.g_cid = p.g_ctok + m;
-        p.g_tscore = ctx->cg_d; p.g_nscore = ctx->cg_d + n; p.g_oscore = ctx->cg_d + 2 * n;
-    }
+    if (use_context) p.g = ctx_graph_dev(ctx);
     HIPCHK(hipMemcpyAsync(d_lens, enc_lens_host, B * sizeof(int), hipMemcpyHostToDevice, s));            // the upload
     {
         ProfScope prof(ctx, s, TAG_CTC_PREFIX);

@@ -119,21 +119,25 @@ int rnnt_stream_open(rnnt_ctx* ctx, int32_t slot, void* stream) {
                        ctx->cfg.blank_id);
     LAUNCHCHK("stream_slot_reset");
     if ((rc = pool_beam_reset(ctx, s, slot, 1))) return rc;   // the slot's beam: one empty hypothesis (once the beam state exists)
+    if ((rc = pool_ctc_reset(ctx, s, slot, 1))) return rc;    // the slot's CTC prefix search: the start hypothesis (likewise)
     pool_enter(ctx);
     ctx->slot_pos[slot] = SlotPos{0, 0, 0};
     return RNNT_OK;
 }
 
 namespace {
-enum { POOL_ENCODE = 0, POOL_GREEDY = 1, POOL_BEAM = 2 };
+enum { POOL_ENCODE = 0, POOL_GREEDY = 1, POOL_BEAM = 2, POOL_CTC_PREFIX = 3 };
 
-// rnnt_pool_chunk (mode POOL_ENCODE / POOL_GREEDY) and rnnt_pool_chunk_beam (POOL_BEAM): validation, the call's table, the encoder
-// launches and the position bookkeeping are one code path; only what follows the encoder differs.
+// rnnt_pool_chunk (mode POOL_ENCODE / POOL_GREEDY), rnnt_pool_chunk_beam (POOL_BEAM) and rnnt_pool_chunk_ctc_prefix (POOL_CTC_PREFIX):
+// validation, the call's table, the encoder launches and the position bookkeeping are one code path; only what follows the encoder
+// differs.  use_context: POOL_CTC_PREFIX only.
 int pool_chunk_run(rnnt_ctx* ctx, const char* fn, int32_t n_active, const int32_t* slots_host, const float* fbank_dev, int32_t T,
-                   const int32_t* offsets_host, const int32_t* required_host, int mode, int32_t beam_size, int32_t* frames_out, void* stream) {
+                   const int32_t* offsets_host, const int32_t* required_host, int mode, int32_t beam_size, int32_t* frames_out, void* stream,
+                   int32_t use_context = 0) {
     if (!ctx || !slots_host || !fbank_dev || !offsets_host || !required_host) return fail(ctx, RNNT_ERR_ARG, "%s: null argument", fn);
     if (!ctx->finalized || ctx->n_streams < 1) return fail(ctx, RNNT_ERR_STATE, "%s: no weights / no streams", fn);
     if (mode == POOL_GREEDY && !ctx->use_persistent) return fail(ctx, RNNT_ERR_STATE, "%s: the greedy decode of a pool call needs the resident decoder", fn);
+    if (mode == POOL_CTC_PREFIX && !ctx->wctc) return fail(ctx, RNNT_ERR_STATE, "%s: ctc_head.ctc_lo.* not loaded", fn);
     const int V = ctx->cfg.vocab_size, NS = ctx->cfg.n_steps, W = ctx->cfg.max_beam;
     if (mode == POOL_BEAM) {   // rnnt_beam_decode's range
         if (ctx->max_rows == 0) return fail(ctx, RNNT_ERR_STATE, "%s: context created with max_beam = 0", fn);
@@ -188,6 +192,11 @@ int pool_chunk_run(rnnt_ctx* ctx, const char* fn, int32_t n_active, const int32_
             if (longest + grow_by > ctx->cfg.max_tokens)
                 return fail(ctx, RNNT_ERR_SHAPE, "%s: slot %d: longest hypothesis %d + %d new tokens possible exceeds max_tokens %d", fn, slot, longest, grow_by, ctx->cfg.max_tokens);
         }
+    }
+    if (mode == POOL_CTC_PREFIX) {   // the search's own refusals, before anything is launched or moved; then its buffers
+        if ((rc = pool_ctc_check(ctx, fn, n, slots_host, tq, beam_size, use_context))) return rc;
+        if ((rc = reserve(ctx, ctx->cp_lp, (size_t)n * tq * V))) return rc;
+        if ((rc = pool_ctc_alloc(ctx, s))) return rc;
     }
     if ((rc = pool_alloc(ctx))) return rc;
     if (mode == POOL_BEAM && (rc = pool_beam_alloc(ctx, s))) return rc;
@@ -244,6 +253,14 @@ int pool_chunk_run(rnnt_ctx* ctx, const char* fn, int32_t n_active, const int32_
         }
         return RNNT_OK;   // the frames are consumed: frames_buffered stays 0
     }
+    if (mode == POOL_CTC_PREFIX) {
+        // ---- log_softmax(ctc_lo(.)) of the compact after_norm rows (kernel choices as for one stream's rows), then the slots' searches ----
+        {
+            GemmCapScope cap_scope(ctx);
+            if ((rc = rnnt_ctc_logprobs(ctx, ctx->x, n * tq, ctx->cp_lp, stream))) return rc;
+        }
+        return pool_ctc_launch(ctx, s, n, slots_host, ctx->cp_lp, tq, beam_size, use_context);   // the frames are consumed: frames_buffered stays 0
+    }
     if (mode == POOL_ENCODE) {   // frames [0, t') of the active slots stay buffered for rnnt_get_enc_frames until rnnt_frames_discard
         hipLaunchKernelGGL(pool_scatter_frames, dim3(grid_for((long long)n * tq * (D / 4))), dim3(256), 0, s, ctx->x, ctx->encbuf, rows_dev, n, tq,
                            (long long)ctx->fstride * D);
@@ -272,6 +289,12 @@ int rnnt_pool_chunk_beam(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_h
                          const int32_t* required_host, int32_t beam_size, int32_t* frames_out, void* stream) {
     return pool_chunk_run(ctx, "rnnt_pool_chunk_beam", n_active, slots_host, fbank_dev, T, offsets_host, required_host, POOL_BEAM, beam_size, frames_out,
                           stream);
+}
+
+int rnnt_pool_chunk_ctc_prefix(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, const float* fbank_dev, int32_t T, const int32_t* offsets_host,
+                               const int32_t* required_host, int32_t beam_size, int32_t use_context, int32_t* frames_out, void* stream) {
+    return pool_chunk_run(ctx, "rnnt_pool_chunk_ctc_prefix", n_active, slots_host, fbank_dev, T, offsets_host, required_host, POOL_CTC_PREFIX, beam_size,
+                          frames_out, stream, use_context);
 }
 
 namespace {

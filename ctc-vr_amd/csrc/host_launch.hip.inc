@@ -34,7 +34,8 @@ enum { TAG_NONE = 0, TAG_CONV1 = 1, TAG_CONV2 = 2, TAG_EMBED = 3, TAG_FFN1 = 4, 
        TAG_SCORE_PICK = 40, TAG_SCORE_ALPHA = 41,     // scoring: the picked lattice (fused kernel, or lattice + gather); transducer_alpha / ctc_alpha
        TAG_SCORE_VITERBI = 42,                        // forced alignment: transducer_viterbi / ctc_viterbi, back-trace included
        TAG_PREFIX_STEP = 43, TAG_PREFIX_MERGE = 44,   // prefix beam search: prefix_step / prefix_merge, one launch each per frame
-       TAG_CTC_PREFIX = 45 };                         // CTC prefix beam search: ctc_prefix_search, one launch per call
+       TAG_CTC_PREFIX = 45,                           // CTC prefix beam search: ctc_prefix_search, one launch per call
+       TAG_CTC_PREFIX_POOL = 46, TAG_CTC_PREFIX_PACK = 47 };   // its resumable form per slot of the stream pool: ctc_prefix_search_pool / ctc_prefix_pack
 
 struct ProfScope {   // records a start/stop event pair around one launch when its site is selected
     rnnt_ctx* ctx; hipStream_t s; bool on;
@@ -613,6 +614,25 @@ int pool_beam_reset(rnnt_ctx* ctx, hipStream_t s, int slot0, int n) {
     hipLaunchKernelGGL(beam_slot_reset, dim3(n), dim3(256), 0, s, pool_beam_params(ctx), slot0, ctx->cfg.n_steps + 1);
     LAUNCHCHK("beam_slot_reset");
     for (int b = slot0; b < slot0 + n; ++b) { ctx->ps_cur[b] = 0; ctx->ps_lbound[b] = 0; }
+    return RNNT_OK;
+}
+
+// ---- per-slot CTC prefix search of the stream pool (api_pool_ctc.hip.inc; kernels in rnnt_ctc_prefix.hip.h) ---------------------------
+// the uploaded tables of rnnt_context_set as the kernels take them
+CpGraph ctx_graph_dev(const rnnt_ctx* ctx) {
+    const size_t n = ctx->cg.token.size(), m = ctx->cg.ctok.size();
+    CpGraph g;
+    g.fail = ctx->cg_i; g.off = ctx->cg_i + n; g.ctok = ctx->cg_i + 2 * n + 1; g.cid = g.ctok + m;
+    g.tscore = ctx->cg_d; g.nscore = ctx->cg_d + n; g.oscore = ctx->cg_d + 2 * n;
+    return g;
+}
+
+// the start hypothesis for slots [slot0, slot0 + n): the host record always, the device record once it exists (pool_ctc_alloc resets all)
+int pool_ctc_reset(rnnt_ctx* ctx, hipStream_t s, int slot0, int n) {
+    for (int b = slot0; b < slot0 + n && b < (int)ctx->pc_slot.size(); ++b) ctx->pc_slot[b] = rnnt_ctx::PcSlot{0, 0, 0, 0};
+    if (!ctx->pc_state) return RNNT_OK;
+    hipLaunchKernelGGL(ctc_prefix_slot_reset, dim3(n), dim3(64), 0, s, ctx->pc_state.p, slot0);
+    LAUNCHCHK("ctc_prefix_slot_reset");
     return RNNT_OK;
 }
 

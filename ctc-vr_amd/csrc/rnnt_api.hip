@@ -265,6 +265,19 @@ struct rnnt_ctx {
     DevBuf<int> cg_i, cp_i;
     DevBuf<double> cg_d, cp_d;
     DevBuf<float> cp_lp;
+    // CTC prefix search per slot of the stream pool (api_pool_ctc.hip.inc), allocated on its first use: the hypothesis record of every
+    // slot, the two arenas [max_streams][max_cache_frames * CP_MAX_BEAM + 1], the call's table (slot and frames walked per active
+    // row, one async copy from pinned memory), one read's packed block.  Host per slot: frames walked, and beam / use_context / graph
+    // generation of the search in progress (beam == 0: fresh).  cg_gen counts rnnt_context_set calls.
+    struct PcSlot { int frames_done, beam, use_context; int64_t gen; };
+    std::vector<PcSlot> pc_slot;
+    int64_t cg_gen = 0;
+    DevBuf<CpSlotState> pc_state;
+    DevBuf<int2> pc_parena, pc_tarena;
+    DevBuf<int> pc_tab;
+    PinnedBuf<int> pc_tab_host;
+    hipEvent_t pc_ev = nullptr;
+    DevBuf<double> pc_out;
     hipStream_t cap_stream = nullptr;          // stream-capture scratch stream
     struct DecGraph { int n_streams, k; hipGraphExec_t exec; };
     std::vector<DecGraph> dec_graphs;          // K greedy steps captured once per (n_streams, K)
@@ -279,7 +292,7 @@ struct rnnt_ctx {
     // constructor -- rnnt_create's `new rnnt_ctx()` value-initialises lw[] and the raw weight views to null.
     ~rnnt_ctx() {
         for (auto& g : dec_graphs) (void)hipGraphExecDestroy(g.exec);
-        for (hipEvent_t e : {pool_ev, sub_ev[0], sub_ev[1]}) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : {pool_ev, pc_ev, sub_ev[0], sub_ev[1]}) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : prof_ev) (void)hipEventDestroy(e);
         for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
         for (hipStream_t st : {dec_stream, cap_stream, sub_stream}) if (st) (void)hipStreamDestroy(st);
@@ -298,6 +311,7 @@ extern "C" {
 #include "api_ops.hip.inc"
 #include "api_score.hip.inc"
 #include "api_state.hip.inc"
+#include "api_pool_ctc.hip.inc"
 #include "api_pool.hip.inc"
 #include "api_prefix.hip.inc"
 #include "api_ctc_prefix.hip.inc"

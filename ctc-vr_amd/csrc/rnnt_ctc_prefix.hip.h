@@ -24,20 +24,80 @@
 //   prune        every entry counts the entries that precede it (greater total, or equal total and lower key): the stable
 //                descending sort of search.py:220-223 without a loop of block arg-max steps; rank < beam survives and writes row rank
 // The epilogue zero-fills the utterance's output rows, replaces the context score by finalize's -node_score, and walks both arenas.
+//
+// The frame step (cp_frame), the hypothesis record (CpHyps, cp_put) and the packer (cp_pack) are ONE piece of code for two kernels:
+//   ctc_prefix_search       the one-launch search above: frames [0, len) from the start hypothesis, packed by its epilogue
+//   ctc_prefix_search_pool  the resumable form of the stream pool (rnnt_pool_ctc_prefix_logprobs): one workgroup per active row loads
+//                           its slot's CpSlotState from device memory, walks the call's t new frames and stores the state back;
+//                           ctc_prefix_pack packs a slot's hypotheses on demand.  Frames are absolute within the utterance and the
+//                           arena nodes of frame t are 1 + t * CP_MAX_BEAM + rank / t * CP_MAX_BEAM + a, so the arena layout does
+//                           not depend on the beam.  Node ids are only ever compared for equality, so the two numberings give the
+//                           same search.
+// Arenas of the pool: [max_streams][max_cache_frames * CP_MAX_BEAM + 1] int2 each, i.e. 1.28 MB per slot per arena at
+// max_cache_frames = 5000, allocated on the first use of the pool's search.
 #pragma once
 
 constexpr int CP_NT = 256, CP_MAX_BEAM = 16, CP_SLOTS = CP_MAX_BEAM + CP_MAX_BEAM * CP_MAX_BEAM, CP_NOKEY = 0x7fffffff;
 constexpr int CP_MAX_NODES = 4096;
 
+// context graph (fail == nullptr: none): flat node arrays, children as a CSR of (token, child) sorted by token per node
+struct CpGraph {
+    const int* fail; const int* off; const int* ctok; const int* cid;
+    const double* tscore; const double* nscore; const double* oscore;
+};
+
+// packed results: [B], [B][beam], [B][beam][lcap] x 2, [B][beam] x 2
+struct CpOutP { int* nh; int* len; int* tok; int* time; double* sc; double* cs; };
+
 struct CtcPrefixP {
     const float* lp;             // [B][T][V] log-probabilities
     const int* lens;             // [B]
     int T, V, blank, beam, lcap;
-    // context graph (g_fail == nullptr: none): flat node arrays, children as a CSR of (token, child) sorted by token per node
-    const int* g_fail; const int* g_off; const int* g_ctok; const int* g_cid;
-    const double* g_tscore; const double* g_nscore; const double* g_oscore;
+    CpGraph g;
     int2* parena; int2* tarena;  // [B][T * beam + 1] each
-    int* o_nh; int* o_len; int* o_tok; int* o_time; double* o_sc; double* o_cs;   // [B], [B][beam], [B][beam][lcap] x 2, [B][beam] x 2
+    CpOutP o;
+};
+
+// The hypotheses of a search at a frame boundary: its whole state besides the two arenas.  In LDS while frames are walked; the
+// stream pool keeps one per slot in device memory between calls (CpSlotState).
+struct CpHyps {
+    double s[CP_MAX_BEAM], ns[CP_MAX_BEAM], vs[CP_MAX_BEAM], vns[CP_MAX_BEAM], cs[CP_MAX_BEAM], score[CP_MAX_BEAM], vit[CP_MAX_BEAM];
+    unsigned long long hash[CP_MAX_BEAM], phash[CP_MAX_BEAM];        // running hash of the prefix, and of the prefix less its last token
+    int cst[CP_MAX_BEAM], node[CP_MAX_BEAM], pnode[CP_MAX_BEAM], last[CP_MAX_BEAM], plen[CP_MAX_BEAM];
+    int tns[CP_MAX_BEAM], tls[CP_MAX_BEAM];                          // times_s: node, length
+    int tnn[CP_MAX_BEAM], tnp[CP_MAX_BEAM], tln[CP_MAX_BEAM];        // times_ns: node, its parent, length
+    int tn[CP_MAX_BEAM], tl[CP_MAX_BEAM];                            // times(): times_s if v_s > v_ns else times_ns
+};
+struct CpSlotState { CpHyps h; int nh, pad; };                       // 7 f64, 2 u64 and 12 int per hypothesis + the count: 1928 bytes
+
+// per-frame work area in LDS
+struct CpWork {
+    unsigned long long wtop[CP_NT / 64][CP_MAX_BEAM];
+    int top_tok[CP_MAX_BEAM];
+    double top_p[CP_MAX_BEAM];
+    double e_tot[CP_SLOTS];
+    int e_key[CP_SLOTS];
+};
+
+// the resumable search of the stream pool: row i of the call is slot slots[i], whose frames [t0[i], t0[i] + t) these are
+struct CtcPrefixPoolP {
+    const float* lp;             // [n][t][V] log-probabilities
+    const int* slots;            // [n]
+    const int* t0;               // [n] frames the slot's search has walked before this call
+    int t, V, blank, beam;
+    CpGraph g;
+    int2* parena; int2* tarena;  // [max_streams][astride] each, astride = max_cache_frames * CP_MAX_BEAM + 1
+    size_t astride;
+    CpSlotState* state;          // [max_streams]
+};
+
+// one slot's hypotheses as the one-launch search's epilogue packs them; fin_nscore != nullptr: finalize's context score
+struct CtcPrefixPackP {
+    const CpSlotState* state;    // the slot's record
+    const int2* pa; const int2* ta;
+    const double* fin_nscore;
+    int beam, lcap;
+    CpOutP o;
 };
 
 // f32 value and index -> a key whose unsigned order is "value descending, then index ascending" read from the top; -0 counts as +0
@@ -97,59 +157,239 @@ __device__ inline unsigned long long cp_wave_max(unsigned long long k) {
     return k;
 }
 
-__global__ __launch_bounds__(CP_NT) void ctc_prefix_search(CtcPrefixP p) {
-    __shared__ unsigned long long wtop[CP_NT / 64][CP_MAX_BEAM];
-    __shared__ int top_tok[CP_MAX_BEAM];
-    __shared__ double top_p[CP_MAX_BEAM];
-    __shared__ double h_s[CP_MAX_BEAM], h_ns[CP_MAX_BEAM], h_vs[CP_MAX_BEAM], h_vns[CP_MAX_BEAM], h_cs[CP_MAX_BEAM], h_score[CP_MAX_BEAM],
-        h_vit[CP_MAX_BEAM];
-    __shared__ unsigned long long h_hash[CP_MAX_BEAM], h_phash[CP_MAX_BEAM];      // running hash of the prefix, and of the prefix less its last token
-    __shared__ int h_cst[CP_MAX_BEAM], h_node[CP_MAX_BEAM], h_pnode[CP_MAX_BEAM], h_last[CP_MAX_BEAM], h_plen[CP_MAX_BEAM];
-    __shared__ int h_tns[CP_MAX_BEAM], h_tls[CP_MAX_BEAM];                        // times_s: node, length
-    __shared__ int h_tnn[CP_MAX_BEAM], h_tnp[CP_MAX_BEAM], h_tln[CP_MAX_BEAM];    // times_ns: node, its parent, length
-    __shared__ int h_tn[CP_MAX_BEAM], h_tl[CP_MAX_BEAM];                          // times(): times_s if v_s > v_ns else times_ns
-    __shared__ double e_tot[CP_SLOTS];
-    __shared__ int e_key[CP_SLOTS];
+// is hypothesis i the prefix of hypothesis j less j's last token?
+__device__ __forceinline__ bool cp_is_parent(const CpHyps& H, const int2* pa, int i, int j) {
+    if (H.plen[j] != H.plen[i] + 1) return false;
+    int x = H.pnode[j], y = H.node[i];
+    if (x == y) return true;
+    if (H.phash[j] != H.hash[i]) return false;
+    while (x != y) {                                                 // equal depth: the chains meet at the root at the latest
+        const int2 ex = pa[x], ey = pa[y];
+        if (ex.y != ey.y) return false;
+        x = ex.x; y = ey.x;
+    }
+    return true;
+}
 
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int len = p.lens[b], beam = p.beam, V = p.V, blank = p.blank;
+// survivor `a` of frame t: hypothesis row a of the next frame (stride: time-arena nodes per frame)
+__device__ __forceinline__ void cp_put(CpHyps& H, int2* ta, int stride, int a, int t, double s, double ns, double vs, double vns, double cs, int cst,
+                                       int node, int pnode, int last, int plen, unsigned long long hash, unsigned long long phash, int tns, int tls,
+                                       int tnn, int tnp, int tln, bool tnew) {
+    H.hash[a] = hash; H.phash[a] = phash;
+    if (tnew) {
+        tnn = t * stride + a;
+        ta[tnn] = make_int2(tnp, t);
+    }
+    H.s[a] = s; H.ns[a] = ns; H.vs[a] = vs; H.vns[a] = vns; H.cs[a] = cs; H.cst[a] = cst;
+    H.score[a] = prefix_log_add(s, ns);
+    H.vit[a] = vs > vns ? vs : vns;
+    H.node[a] = node; H.pnode[a] = pnode; H.last[a] = last; H.plen[a] = plen;
+    H.tns[a] = tns; H.tls[a] = tls; H.tnn[a] = tnn; H.tnp[a] = tnp; H.tln[a] = tln;
+    H.tn[a] = vs > vns ? tns : tnn;
+    H.tl[a] = vs > vns ? tls : tln;
+}
+
+// the start hypothesis (search.py:142-149): the empty prefix, s = 0, ns = -inf, v_s = v_ns = 0, context root
+__device__ __forceinline__ void cp_put_start(CpHyps& H) {
+    cp_put(H, nullptr, 0, 0, 0, 0.0, -INFINITY, 0.0, 0.0, 0.0, 0, 0, -1, -1, 0, BEAM_HASH0, 0ull, -1, 0, -1, -1, 0, false);
+}
+
+// One frame of the search for the whole workgroup (CP_NT threads, four barriers): frame t of the utterance, whose row the caller
+// holds in (v0, v1); next_row (or nullptr) is prefetched into them.  stride: arena nodes per frame.  nh: hypotheses before / after.
+__device__ __forceinline__ void cp_frame(CpHyps& H, CpWork& W, const CpGraph& g, int2* pa, int2* ta, const float* next_row, int t, int stride,
+                                         int beam, int V, int blank, int& nh, float& v0, float& v1) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bool graph = g.fail != nullptr;
+    // ---- first prune: top-beam of the frame ------------------------------------------------------------------------------
+    unsigned long long k0 = tid < V ? cp_key(v0, tid) : 0ull, k1 = tid + CP_NT < V ? cp_key(v1, tid + CP_NT) : 0ull;
+    if (next_row) {
+        if (tid < V) v0 = next_row[tid];
+        if (tid + CP_NT < V) v1 = next_row[tid + CP_NT];
+    }
+    for (int q = 0; q < beam; ++q) {
+        const unsigned long long w = cp_wave_max(k0 > k1 ? k0 : k1);
+        if (lane == 0) W.wtop[wave][q] = w;
+        if (k0 == w) k0 = 0ull;
+        else if (k1 == w) k1 = 0ull;
+    }
+    __syncthreads();
+    if (tid < 64) {
+        const int q = tid & 15, w = tid >> 4;
+        const unsigned long long my = q < beam ? W.wtop[w][q] : 0ull;
+        if (my) {
+            int rank = 0;
+            for (int ww = 0; ww < CP_NT / 64; ++ww)
+                for (int qq = 0; qq < beam; ++qq) rank += W.wtop[ww][qq] > my;
+            if (rank < beam) { W.top_tok[rank] = cp_key_index(my); W.top_p[rank] = (double)cp_key_value(my); }
+        }
+    }
+    __syncthreads();
+
+    // ---- expansion: the entry "P_j unchanged" (thread j) ---------------------------------------------------------------------
+    int keyU = CP_NOKEY, Ucst = 0, Uts = -1, Utls = 0, Utnp = -1, Utln = 0;
+    int Unode = 0, Upnode = -1, Ulast = -1, Uplen = 0;
+    unsigned long long Uhash = 0ull, Uphash = 0ull, Nphash = 0ull;
+    double Us = -INFINITY, Uns = -INFINITY, Uvs = -INFINITY, Uvns = -INFINITY, Uctp = -INFINITY, Ucs = 0.0, totU = 0.0;
+    bool Uhas = false, Unew = false;
+    if (tid < nh) {
+        const int j = tid;
+        Unode = H.node[j]; Upnode = H.pnode[j]; Ulast = H.last[j]; Uplen = H.plen[j]; Uhash = H.hash[j]; Uphash = H.phash[j];
+        int par = -1;
+        for (int i = 0; i < nh; ++i)
+            if (cp_is_parent(H, pa, i, j)) par = i;
+        // the extension P_par + u == P_j (search.py:188-201 when par ends in u, else :203-217)
+        auto ext = [&](int r, int i, int u, double pr) {
+            if (keyU == CP_NOKEY) keyU = (r * CP_MAX_BEAM + i) * 2 + 1;
+            const bool rep = H.last[i] == u;
+            const double add = (rep ? H.s[i] : H.score[i]) + pr, vv = (rep ? H.vs[i] : H.vit[i]) + pr;
+            Uns = prefix_log_add(Uns, add);
+            if (Uvns < vv) {
+                Uvns = vv; Uctp = pr;
+                Unew = true; Utnp = rep ? H.tns[i] : H.tn[i]; Utln = (rep ? H.tls[i] : H.tl[i]) + 1;
+            }
+            if (!Uhas) {
+                Uhas = true;
+                Ucs = H.cs[i];
+                if (graph) {
+                    int nx;
+                    Ucs += cg_step(g.fail, g.off, g.ctok, g.cid, g.tscore, g.nscore, g.oscore, H.cst[i], u, &nx);
+                    Ucst = nx;
+                }
+            }
+        };
+        for (int r = 0; r < beam; ++r) {
+            const int u = W.top_tok[r];
+            const double pr = W.top_p[r];
+            if (u == blank) {                                                    // :162-171
+                if (keyU == CP_NOKEY) keyU = (r * CP_MAX_BEAM + j) * 2;
+                Us = prefix_log_add(Us, H.score[j] + pr);
+                Uvs = H.vit[j] + pr;
+                Uts = H.tn[j]; Utls = H.tl[j];
+                if (!Uhas) { Uhas = true; Ucs = H.cs[j]; Ucst = H.cst[j]; }
+            } else if (u == Ulast) {
+                if (par >= 0 && par < j) ext(r, par, u, pr);
+                if (keyU == CP_NOKEY) keyU = (r * CP_MAX_BEAM + j) * 2;          // :172-186
+                Uns = prefix_log_add(Uns, H.ns[j] + pr);
+                if (Uvns < H.vns[j] + pr) {
+                    Uvns = H.vns[j] + pr;
+                    if (Uctp < pr) {
+                        Uctp = pr;
+                        if (H.tln[j] > 0) { Unew = true; Utnp = H.tnp[j]; Utln = H.tln[j]; }   // times_ns[-1] = t
+                    }
+                }
+                if (!Uhas) { Uhas = true; Ucs = H.cs[j]; Ucst = H.cst[j]; }
+                if (par > j) ext(r, par, u, pr);
+            }
+        }
+        totU = prefix_log_add(Us, Uns) + Ucs;
+    }
+    if (tid < CP_MAX_BEAM) { W.e_key[tid] = keyU; W.e_tot[tid] = totU; }
+
+    // ---- expansion: the entry "P_i + top[r]" (thread i * beam + r) unless that prefix is live ------------------------------------
+    int keyN = CP_NOKEY, Ncst = 0, Ntnp = -1, Ntln = 0, Npnode = 0, Nlast = 0, Nplen = 0;
+    double Nns = -INFINITY, Nvns = -INFINITY, Ncs = 0.0, totN = 0.0;
+    bool Nnew = false;
+    if (tid < nh * beam) {
+        const int i = tid / beam, r = tid - i * beam, u = W.top_tok[r];
+        bool live = u == blank;
+        Npnode = H.node[i]; Nphash = H.hash[i];
+        for (int j = 0; j < nh && !live; ++j) live = H.last[j] == u && cp_is_parent(H, pa, i, j);
+        if (!live) {
+            const double pr = W.top_p[r];
+            const bool rep = H.last[i] == u;
+            const double add = (rep ? H.s[i] : H.score[i]) + pr, vv = (rep ? H.vs[i] : H.vit[i]) + pr;
+            keyN = (r * CP_MAX_BEAM + i) * 2 + 1;
+            Nns = prefix_log_add(-INFINITY, add);
+            if (-INFINITY < vv) { Nvns = vv; Nnew = true; Ntnp = rep ? H.tns[i] : H.tn[i]; Ntln = (rep ? H.tls[i] : H.tl[i]) + 1; }
+            Ncs = H.cs[i];
+            if (graph) {
+                int nx;
+                Ncs += cg_step(g.fail, g.off, g.ctok, g.cid, g.tscore, g.nscore, g.oscore, H.cst[i], u, &nx);
+                Ncst = nx;
+            }
+            Nlast = u; Nplen = H.plen[i] + 1;
+            totN = prefix_log_add(-INFINITY, Nns) + Ncs;
+        }
+        W.e_key[CP_MAX_BEAM + tid] = keyN;
+        W.e_tot[CP_MAX_BEAM + tid] = totN;
+    }
+    __syncthreads();
+
+    // ---- second prune: rank by counting, stable over first-insertion order ---------------------------------------------------
+    int rankU = 0, rankN = 0, nact = 0;
+    const int nslots = CP_MAX_BEAM + nh * beam;
+    for (int e = 0; e < nslots; ++e) {
+        const int k = W.e_key[e];
+        if (k == CP_NOKEY) continue;
+        const double tt = W.e_tot[e];
+        ++nact;
+        rankU += (tt > totU) | ((tt == totU) & (k < keyU));
+        rankN += (tt > totN) | ((tt == totN) & (k < keyN));
+    }
+    if (keyU != CP_NOKEY && rankU < beam)
+        cp_put(H, ta, stride, rankU, t, Us, Uns, Uvs, Uvns, Ucs, Ucst, Unode, Upnode, Ulast, Uplen, Uhash, Uphash, Uts, Utls, -1, Utnp, Utln, Unew);   // a fresh times_ns is []
+    if (keyN != CP_NOKEY && rankN < beam) {
+        const int node = 1 + t * stride + rankN;
+        pa[node] = make_int2(Npnode, Nlast);
+        cp_put(H, ta, stride, rankN, t, -INFINITY, Nns, -INFINITY, Nvns, Ncs, Ncst, node, Npnode, Nlast, Nplen, beam_hash_step(Nphash, Nlast), Nphash, -1, 0, -1, Ntnp,
+               Ntln, Nnew);
+    }
+    nh = nact < beam ? nact : beam;
+    __syncthreads();
+}
+
+// Row b of the packed result from the nh hypotheses in H (whole workgroup, CP_NT threads): zero fill, then scores and tokens on one
+// wave and times on another.  fin_nscore != nullptr: finalize (context_graph.py:264) REPLACES the context score (search.py:229-231).
+__device__ __forceinline__ void cp_pack(const CpHyps& H, int nh, const int2* pa, const int2* ta, const double* fin_nscore, const CpOutP& o, int b,
+                                        int beam, int lcap) {
+    const int tid = threadIdx.x;
+    const size_t r0 = (size_t)b * beam;
+    for (int q = tid; q < beam * lcap; q += CP_NT) { o.tok[r0 * lcap + q] = 0; o.time[r0 * lcap + q] = 0; }
+    if (tid < beam) { o.len[r0 + tid] = 0; o.sc[r0 + tid] = 0.0; o.cs[r0 + tid] = 0.0; }
+    if (tid == 0) o.nh[b] = nh;
+    __syncthreads();
+    if (tid < nh) {                                                  // scores and tokens
+        const int a = tid, n = H.plen[a];
+        const double cs = fin_nscore ? -fin_nscore[H.cst[a]] : H.cs[a];
+        o.sc[r0 + a] = H.score[a] + cs;
+        o.cs[r0 + a] = cs;
+        o.len[r0 + a] = n;
+        int node = H.node[a];
+        for (int q = n - 1; q >= 0; --q) {
+            const int2 e = pa[node];
+            o.tok[(r0 + a) * lcap + q] = e.y;
+            node = e.x;
+        }
+    } else if (tid >= 64 && tid < 64 + nh) {                         // times, on another wave
+        const int a = tid - 64;
+        int node = H.tn[a];
+        for (int q = H.tl[a] - 1; q >= 0 && node >= 0; --q) {
+            const int2 e = ta[node];
+            o.time[(r0 + a) * lcap + q] = e.y;
+            node = e.x;
+        }
+    }
+}
+
+// element `i` of every array of a hypothesis record (threads i < CP_MAX_BEAM copy a record between LDS and device memory)
+__device__ __forceinline__ void cp_hyps_copy(CpHyps& d, const CpHyps& s, int i) {
+    d.s[i] = s.s[i]; d.ns[i] = s.ns[i]; d.vs[i] = s.vs[i]; d.vns[i] = s.vns[i]; d.cs[i] = s.cs[i]; d.score[i] = s.score[i]; d.vit[i] = s.vit[i];
+    d.hash[i] = s.hash[i]; d.phash[i] = s.phash[i];
+    d.cst[i] = s.cst[i]; d.node[i] = s.node[i]; d.pnode[i] = s.pnode[i]; d.last[i] = s.last[i]; d.plen[i] = s.plen[i];
+    d.tns[i] = s.tns[i]; d.tls[i] = s.tls[i]; d.tnn[i] = s.tnn[i]; d.tnp[i] = s.tnp[i]; d.tln[i] = s.tln[i]; d.tn[i] = s.tn[i]; d.tl[i] = s.tl[i];
+}
+
+__global__ __launch_bounds__(CP_NT) void ctc_prefix_search(CtcPrefixP p) {
+    __shared__ CpHyps H;
+    __shared__ CpWork W;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int len = p.lens[b], beam = p.beam, V = p.V;
     const size_t astride = (size_t)p.T * beam + 1;
     int2* pa = p.parena + (size_t)b * astride;
     int2* ta = p.tarena + (size_t)b * astride;
     const float* rows = p.lp + (size_t)b * p.T * V;
-    const bool graph = p.g_fail != nullptr;
 
-    // is hypothesis i the prefix of hypothesis j less j's last token?
-    auto is_parent = [&](int i, int j) -> bool {
-        if (h_plen[j] != h_plen[i] + 1) return false;
-        int x = h_pnode[j], y = h_node[i];
-        if (x == y) return true;
-        if (h_phash[j] != h_hash[i]) return false;
-        while (x != y) {                                             // equal depth: the chains meet at the root at the latest
-            const int2 ex = pa[x], ey = pa[y];
-            if (ex.y != ey.y) return false;
-            x = ex.x; y = ey.x;
-        }
-        return true;
-    };
-    // survivor `a` of frame t: hypothesis row a of the next frame
-    auto put = [&](int a, int t, double s, double ns, double vs, double vns, double cs, int cst, int node, int pnode, int last, int plen,
-                   unsigned long long hash, unsigned long long phash, int tns, int tls, int tnn, int tnp, int tln, bool tnew) {
-        h_hash[a] = hash; h_phash[a] = phash;
-        if (tnew) {
-            tnn = t * beam + a;
-            ta[tnn] = make_int2(tnp, t);
-        }
-        h_s[a] = s; h_ns[a] = ns; h_vs[a] = vs; h_vns[a] = vns; h_cs[a] = cs; h_cst[a] = cst;
-        h_score[a] = prefix_log_add(s, ns);
-        h_vit[a] = vs > vns ? vs : vns;
-        h_node[a] = node; h_pnode[a] = pnode; h_last[a] = last; h_plen[a] = plen;
-        h_tns[a] = tns; h_tls[a] = tls; h_tnn[a] = tnn; h_tnp[a] = tnp; h_tln[a] = tln;
-        h_tn[a] = vs > vns ? tns : tnn;
-        h_tl[a] = vs > vns ? tls : tln;
-    };
-
-    if (tid == 0) put(0, 0, 0.0, -INFINITY, 0.0, 0.0, 0.0, 0, 0, -1, -1, 0, BEAM_HASH0, 0ull, -1, 0, -1, -1, 0, false);   // search.py:142-149
+    if (tid == 0) cp_put_start(H);
     int nh = 1;
     float v0 = 0.f, v1 = 0.f;
     if (len > 0) {
@@ -157,171 +397,55 @@ __global__ __launch_bounds__(CP_NT) void ctc_prefix_search(CtcPrefixP p) {
         if (tid + CP_NT < V) v1 = rows[tid + CP_NT];
     }
     __syncthreads();
-
-    for (int t = 0; t < len; ++t) {
-        // ---- first prune: top-beam of the frame ------------------------------------------------------------------------------
-        unsigned long long k0 = tid < V ? cp_key(v0, tid) : 0ull, k1 = tid + CP_NT < V ? cp_key(v1, tid + CP_NT) : 0ull;
-        if (t + 1 < len) {
-            const float* nx = rows + (size_t)(t + 1) * V;
-            if (tid < V) v0 = nx[tid];
-            if (tid + CP_NT < V) v1 = nx[tid + CP_NT];
-        }
-        for (int q = 0; q < beam; ++q) {
-            const unsigned long long w = cp_wave_max(k0 > k1 ? k0 : k1);
-            if (lane == 0) wtop[wave][q] = w;
-            if (k0 == w) k0 = 0ull;
-            else if (k1 == w) k1 = 0ull;
-        }
-        __syncthreads();
-        if (tid < 64) {
-            const int q = tid & 15, w = tid >> 4;
-            const unsigned long long my = q < beam ? wtop[w][q] : 0ull;
-            if (my) {
-                int rank = 0;
-                for (int ww = 0; ww < CP_NT / 64; ++ww)
-                    for (int qq = 0; qq < beam; ++qq) rank += wtop[ww][qq] > my;
-                if (rank < beam) { top_tok[rank] = cp_key_index(my); top_p[rank] = (double)cp_key_value(my); }
-            }
-        }
-        __syncthreads();
-
-        // ---- expansion: the entry "P_j unchanged" (thread j) ---------------------------------------------------------------------
-        int keyU = CP_NOKEY, Ucst = 0, Uts = -1, Utls = 0, Utnp = -1, Utln = 0;
-        int Unode = 0, Upnode = -1, Ulast = -1, Uplen = 0;
-        unsigned long long Uhash = 0ull, Uphash = 0ull, Nphash = 0ull;
-        double Us = -INFINITY, Uns = -INFINITY, Uvs = -INFINITY, Uvns = -INFINITY, Uctp = -INFINITY, Ucs = 0.0, totU = 0.0;
-        bool Uhas = false, Unew = false;
-        if (tid < nh) {
-            const int j = tid;
-            Unode = h_node[j]; Upnode = h_pnode[j]; Ulast = h_last[j]; Uplen = h_plen[j]; Uhash = h_hash[j]; Uphash = h_phash[j];
-            int par = -1;
-            for (int i = 0; i < nh; ++i)
-                if (is_parent(i, j)) par = i;
-            // the extension P_par + u == P_j (search.py:188-201 when par ends in u, else :203-217)
-            auto ext = [&](int r, int i, int u, double pr) {
-                if (keyU == CP_NOKEY) keyU = (r * CP_MAX_BEAM + i) * 2 + 1;
-                const bool rep = h_last[i] == u;
-                const double add = (rep ? h_s[i] : h_score[i]) + pr, vv = (rep ? h_vs[i] : h_vit[i]) + pr;
-                Uns = prefix_log_add(Uns, add);
-                if (Uvns < vv) {
-                    Uvns = vv; Uctp = pr;
-                    Unew = true; Utnp = rep ? h_tns[i] : h_tn[i]; Utln = (rep ? h_tls[i] : h_tl[i]) + 1;
-                }
-                if (!Uhas) {
-                    Uhas = true;
-                    Ucs = h_cs[i];
-                    if (graph) {
-                        int nx;
-                        Ucs += cg_step(p.g_fail, p.g_off, p.g_ctok, p.g_cid, p.g_tscore, p.g_nscore, p.g_oscore, h_cst[i], u, &nx);
-                        Ucst = nx;
-                    }
-                }
-            };
-            for (int r = 0; r < beam; ++r) {
-                const int u = top_tok[r];
-                const double pr = top_p[r];
-                if (u == blank) {                                                    // :162-171
-                    if (keyU == CP_NOKEY) keyU = (r * CP_MAX_BEAM + j) * 2;
-                    Us = prefix_log_add(Us, h_score[j] + pr);
-                    Uvs = h_vit[j] + pr;
-                    Uts = h_tn[j]; Utls = h_tl[j];
-                    if (!Uhas) { Uhas = true; Ucs = h_cs[j]; Ucst = h_cst[j]; }
-                } else if (u == Ulast) {
-                    if (par >= 0 && par < j) ext(r, par, u, pr);
-                    if (keyU == CP_NOKEY) keyU = (r * CP_MAX_BEAM + j) * 2;          // :172-186
-                    Uns = prefix_log_add(Uns, h_ns[j] + pr);
-                    if (Uvns < h_vns[j] + pr) {
-                        Uvns = h_vns[j] + pr;
-                        if (Uctp < pr) {
-                            Uctp = pr;
-                            if (h_tln[j] > 0) { Unew = true; Utnp = h_tnp[j]; Utln = h_tln[j]; }   // times_ns[-1] = t
-                        }
-                    }
-                    if (!Uhas) { Uhas = true; Ucs = h_cs[j]; Ucst = h_cst[j]; }
-                    if (par > j) ext(r, par, u, pr);
-                }
-            }
-            totU = prefix_log_add(Us, Uns) + Ucs;
-        }
-        if (tid < CP_MAX_BEAM) { e_key[tid] = keyU; e_tot[tid] = totU; }
-
-        // ---- expansion: the entry "P_i + top[r]" (thread i * beam + r) unless that prefix is live ------------------------------------
-        int keyN = CP_NOKEY, Ncst = 0, Ntnp = -1, Ntln = 0, Npnode = 0, Nlast = 0, Nplen = 0;
-        double Nns = -INFINITY, Nvns = -INFINITY, Ncs = 0.0, totN = 0.0;
-        bool Nnew = false;
-        if (tid < nh * beam) {
-            const int i = tid / beam, r = tid - i * beam, u = top_tok[r];
-            bool live = u == blank;
-            Npnode = h_node[i]; Nphash = h_hash[i];
-            for (int j = 0; j < nh && !live; ++j) live = h_last[j] == u && is_parent(i, j);
-            if (!live) {
-                const double pr = top_p[r];
-                const bool rep = h_last[i] == u;
-                const double add = (rep ? h_s[i] : h_score[i]) + pr, vv = (rep ? h_vs[i] : h_vit[i]) + pr;
-                keyN = (r * CP_MAX_BEAM + i) * 2 + 1;
-                Nns = prefix_log_add(-INFINITY, add);
-                if (-INFINITY < vv) { Nvns = vv; Nnew = true; Ntnp = rep ? h_tns[i] : h_tn[i]; Ntln = (rep ? h_tls[i] : h_tl[i]) + 1; }
-                Ncs = h_cs[i];
-                if (graph) {
-                    int nx;
-                    Ncs += cg_step(p.g_fail, p.g_off, p.g_ctok, p.g_cid, p.g_tscore, p.g_nscore, p.g_oscore, h_cst[i], u, &nx);
-                    Ncst = nx;
-                }
-                Nlast = u; Nplen = h_plen[i] + 1;
-                totN = prefix_log_add(-INFINITY, Nns) + Ncs;
-            }
-            e_key[CP_MAX_BEAM + tid] = keyN;
-            e_tot[CP_MAX_BEAM + tid] = totN;
-        }
-        __syncthreads();
-
-        // ---- second prune: rank by counting, stable over first-insertion order ---------------------------------------------------
-        int rankU = 0, rankN = 0, nact = 0;
-        const int nslots = CP_MAX_BEAM + nh * beam;
-        for (int e = 0; e < nslots; ++e) {
-            const int k = e_key[e];
-            if (k == CP_NOKEY) continue;
-            const double tt = e_tot[e];
-            ++nact;
-            rankU += (tt > totU) | ((tt == totU) & (k < keyU));
-            rankN += (tt > totN) | ((tt == totN) & (k < keyN));
-        }
-        if (keyU != CP_NOKEY && rankU < beam)
-            put(rankU, t, Us, Uns, Uvs, Uvns, Ucs, Ucst, Unode, Upnode, Ulast, Uplen, Uhash, Uphash, Uts, Utls, -1, Utnp, Utln, Unew);   // a fresh times_ns is []
-        if (keyN != CP_NOKEY && rankN < beam) {
-            const int node = 1 + t * beam + rankN;
-            pa[node] = make_int2(Npnode, Nlast);
-            put(rankN, t, -INFINITY, Nns, -INFINITY, Nvns, Ncs, Ncst, node, Npnode, Nlast, Nplen, beam_hash_step(Nphash, Nlast), Nphash, -1, 0, -1, Ntnp, Ntln, Nnew);
-        }
-        nh = nact < beam ? nact : beam;
-        __syncthreads();
-    }
-
+    for (int t = 0; t < len; ++t)
+        cp_frame(H, W, p.g, pa, ta, t + 1 < len ? rows + (size_t)(t + 1) * V : nullptr, t, beam, beam, V, p.blank, nh, v0, v1);
     // ---- epilogue: this utterance's rows of the packed result -----------------------------------------------------------------------
-    const size_t r0 = (size_t)b * beam;
-    for (int q = tid; q < beam * p.lcap; q += CP_NT) { p.o_tok[r0 * p.lcap + q] = 0; p.o_time[r0 * p.lcap + q] = 0; }
-    if (tid < beam) { p.o_len[r0 + tid] = 0; p.o_sc[r0 + tid] = 0.0; p.o_cs[r0 + tid] = 0.0; }
-    if (tid == 0) p.o_nh[b] = nh;
+    cp_pack(H, nh, pa, ta, p.g.fail ? p.g.nscore : nullptr, p.o, b, beam, p.lcap);
+}
+
+// The resumable form: workgroup i continues the search of slot slots[i] over the call's t rows, frames [t0[i], t0[i] + t) of its
+// utterance.  The prefetch of the next row stays inside those rows.  No epilogue (ctc_prefix_pack).
+__global__ __launch_bounds__(CP_NT) void ctc_prefix_search_pool(CtcPrefixPoolP p) {
+    __shared__ CpHyps H;
+    __shared__ CpWork W;
+    const int i = blockIdx.x, tid = threadIdx.x;
+    const int slot = p.slots[i], t0 = p.t0[i], V = p.V;
+    int2* pa = p.parena + (size_t)slot * p.astride;
+    int2* ta = p.tarena + (size_t)slot * p.astride;
+    const float* rows = p.lp + (size_t)i * p.t * V;
+    CpSlotState* st = p.state + slot;
+
+    if (tid < CP_MAX_BEAM) cp_hyps_copy(H, st->h, tid);
+    int nh = st->nh;
+    float v0 = 0.f, v1 = 0.f;
+    if (tid < V) v0 = rows[tid];
+    if (tid + CP_NT < V) v1 = rows[tid + CP_NT];
     __syncthreads();
-    if (tid < nh) {                                                  // scores and tokens
-        const int a = tid, n = h_plen[a];
-        const double cs = graph ? -p.g_nscore[h_cst[a]] : h_cs[a];    // finalize (context_graph.py:264) REPLACES the score (search.py:229-231)
-        p.o_sc[r0 + a] = h_score[a] + cs;
-        p.o_cs[r0 + a] = cs;
-        p.o_len[r0 + a] = n;
-        int node = h_node[a];
-        for (int q = n - 1; q >= 0; --q) {
-            const int2 e = pa[node];
-            p.o_tok[(r0 + a) * p.lcap + q] = e.y;
-            node = e.x;
-        }
-    } else if (tid >= 64 && tid < 64 + nh) {                         // times, on another wave
-        const int a = tid - 64;
-        int node = h_tn[a];
-        for (int q = h_tl[a] - 1; q >= 0 && node >= 0; --q) {
-            const int2 e = ta[node];
-            p.o_time[(r0 + a) * p.lcap + q] = e.y;
-            node = e.x;
-        }
-    }
+    for (int f = 0; f < p.t; ++f)
+        cp_frame(H, W, p.g, pa, ta, f + 1 < p.t ? rows + (size_t)(f + 1) * V : nullptr, t0 + f, CP_MAX_BEAM, p.beam, V, p.blank, nh, v0, v1);
+    if (tid < CP_MAX_BEAM) cp_hyps_copy(st->h, H, tid);
+    if (tid == 0) st->nh = nh;
+}
+
+// one slot's hypotheses as they stand, in the layout of the one-launch search for B = 1; reads only
+__global__ __launch_bounds__(CP_NT) void ctc_prefix_pack(CtcPrefixPackP p) {
+    __shared__ CpHyps H;
+    const int tid = threadIdx.x;
+    if (tid < CP_MAX_BEAM) cp_hyps_copy(H, p.state->h, tid);
+    const int nh = p.state->nh;
+    __syncthreads();
+    cp_pack(H, nh, p.pa, p.ta, p.fin_nscore, p.o, 0, p.beam, p.lcap);
+}
+
+// the start hypothesis in the records of slots [slot0, slot0 + gridDim.x); every other entry of a record is zero
+__global__ __launch_bounds__(64) void ctc_prefix_slot_reset(CpSlotState* state, int slot0) {
+    __shared__ CpSlotState z;
+    const int tid = threadIdx.x;
+    for (int q = tid; q < (int)(sizeof(CpSlotState) / sizeof(int)); q += 64) reinterpret_cast<int*>(&z)[q] = 0;
+    __syncthreads();
+    if (tid == 0) { cp_put_start(z.h); z.nh = 1; }
+    __syncthreads();
+    CpSlotState* st = state + slot0 + blockIdx.x;
+    if (tid < CP_MAX_BEAM) cp_hyps_copy(st->h, z.h, tid);
+    if (tid == 0) { st->nh = z.nh; st->pad = 0; }
 }

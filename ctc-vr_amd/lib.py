@@ -65,6 +65,10 @@ SIGNATURES = {
                                           c_vp, c_vp, c_vp]),
     "rnnt_ctc_prefix_beam_logprobs": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rnnt_ctc_prefix_beam_decode": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rnnt_stream_ctc_prefix_reset": (c_i32, [c_vp, c_i32, c_vp]),
+    "rnnt_pool_ctc_prefix_logprobs": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
+    "rnnt_pool_chunk_ctc_prefix": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32p, c_vp]),
+    "rnnt_stream_get_ctc_prefix": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32p, c_vp]),
     "rnnt_transducer_nll": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "rnnt_ctc_nll": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "rnnt_transducer_align": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
@@ -250,7 +254,8 @@ def ctc_prefix_beam_host(lp, enc_lens, blank, beam_size, phrases=None, context_s
 class RnntEngine:
     """One context = one GPU = up to `max_streams` streams: lock-stepped (encoder_chunk / encoder_chunks / decode_ragged), or the
     slots of a stream pool that open, advance and close independently (stream_open / pool_chunk / stream_tokens, and per-slot beam
-    search through pool_chunk_beam / stream_beam / stream_beam_states)."""
+    search through pool_chunk_beam / stream_beam / stream_beam_states, per-slot CTC prefix beam search with hot words through
+    pool_chunk_ctc_prefix / pool_ctc_prefix_logprobs / stream_ctc_prefix / stream_ctc_prefix_reset)."""
 
     def __init__(self, max_streams=1, max_chunk_frames=64, max_cache_frames=1024, max_enc_frames=1024, max_tokens=4096,
                  vocab_size=412, blank_id=5, n_steps=10, device=0, max_beam=0):
@@ -579,6 +584,47 @@ class RnntEngine:
         """rnnt_ctc_prefix_beam_decode: the same over encoder frames [B, T, 256] (rnnt_ctc_logprobs first)."""
         return self._ctc_prefix(self.lib.rnnt_ctc_prefix_beam_decode, "rnnt_ctc_prefix_beam_decode", enc_ptr, enc_lens, B, T, beam_size, use_context,
                                 raw, stream)
+
+    # ---- the same search per slot of the stream pool ----------------------------------------------------
+    def stream_ctc_prefix_reset(self, slot=-1, stream=None):
+        """rnnt_stream_ctc_prefix_reset: the start hypothesis for one slot's CTC prefix search (-1: all slots)."""
+        self._chk(self.lib.rnnt_stream_ctc_prefix_reset(self.ctx, slot, stream), "rnnt_stream_ctc_prefix_reset")
+
+    def pool_ctc_prefix_logprobs(self, slots, lp_ptr, t, beam_size=10, use_context=False, stream=None):
+        """rnnt_pool_ctc_prefix_logprobs: advance the searches of the listed slots by t frames of log-probabilities [len(slots), t, vocab]
+        on the device; one launch, no synchronisation."""
+        a = np.ascontiguousarray(slots, np.int32)
+        assert a.ndim == 1
+        self._chk(self.lib.rnnt_pool_ctc_prefix_logprobs(self.ctx, a.size, _np_ptr(a), lp_ptr, t, beam_size, 1 if use_context else 0, stream),
+                  "rnnt_pool_ctc_prefix_logprobs")
+
+    def pool_chunk_ctc_prefix(self, slots, fbank_ptr, chunk_frames, offsets, required, beam_size=10, use_context=False, stream=None):
+        """rnnt_pool_chunk_ctc_prefix: pool_chunk's encoder for the listed slots, the CTC log-probabilities of their new frames, and
+        their searches advanced by those frames; the frames are consumed.  Does not synchronise (stream_ctc_prefix does).  Returns t'."""
+        a, o, r = (np.ascontiguousarray(v, np.int32) for v in (slots, offsets, required))
+        assert a.ndim == 1 and a.size == o.size == r.size
+        t = c_i32(0)
+        self._chk(self.lib.rnnt_pool_chunk_ctc_prefix(self.ctx, a.size, _np_ptr(a), fbank_ptr, chunk_frames, _np_ptr(o), _np_ptr(r), beam_size,
+                                                      1 if use_context else 0, ctypes.byref(t), stream), "rnnt_pool_chunk_ctc_prefix")
+        return t.value
+
+    def stream_ctc_prefix(self, slot, final=False, raw=False, cap_hyps=None, cap_tokens=None, stream=None):
+        """rnnt_stream_get_ctc_prefix: [(tokens, score, times, context score)] of one slot in the search's order, as they stand
+        (final: as the one-launch search returns them had the utterance ended here).  raw: also the result arrays of a B = 1 call
+        (n_hyp, lens, tokens, times, scores, context scores) and the frames walked.  cap_hyps / cap_tokens None: what the slot needs
+        (its beam and the frames it has walked, asked of the library first: a host-only call), so a read costs what it returns."""
+        frames = c_i32(0)
+        if cap_hyps is None or cap_tokens is None:
+            need = c_i32(0)
+            self._chk(self.lib.rnnt_stream_get_ctc_prefix(self.ctx, slot, 0, 0, 0, ctypes.byref(need), None, None, None, None, None,
+                                                          ctypes.byref(frames), stream), "rnnt_stream_get_ctc_prefix")
+            cap_hyps = need.value if cap_hyps is None else cap_hyps
+            cap_tokens = frames.value if cap_tokens is None else cap_tokens
+        out = _ctc_prefix_out(1, cap_hyps, max(cap_tokens, 1))
+        self._chk(self.lib.rnnt_stream_get_ctc_prefix(self.ctx, slot, 1 if final else 0, cap_hyps, out[2].shape[2], *[_np_ptr(a) for a in out],
+                                                      ctypes.byref(frames), stream), "rnnt_stream_get_ctc_prefix")
+        hyps = _ctc_prefix_hyps(out)[0]
+        return (hyps, out, frames.value) if raw else hyps
 
     def prefix_merge_device(self, hyps, top_lp, top_tok, blank, beam_size, stream=None):
         """rnnt_prefix_merge_device: prefix_merge_host's arguments and results through one prefix_merge launch."""

@@ -837,7 +837,10 @@ class StreamingBatch:
         return self.engine.tokens(_stream_ptr())
 
 
-def pool_plan(queue, offsets, beams=None):
+_POOL_KINDS = ("greedy", "beam", "ctc_prefix")
+
+
+def pool_plan(queue, offsets, beams=None, ctc_prefix=None):
     """The library calls of one StreamPool.step as a pure function (no GPU, no tensors).
 
     queue: [(slot, length)] in feed order, several entries per slot allowed; offsets: {slot: encoder offset so far}.
@@ -851,9 +854,21 @@ def pool_plan(queue, offsets, beams=None):
     beams: {slot: beam size} (0 or absent = greedy), None = all greedy and the result above.  With it every call is
     (length, slots, offsets, beam_size): one chunk length AND one beam size per call -- beam_size 0 is an rnnt_pool_chunk call,
     beam_size > 0 an rnnt_pool_chunk_beam call -- so greedy and beam slots never share a call; inside a round the classes run in
-    ascending (length, beam size).  Feed order per slot and the round structure are the same."""
+    ascending (length, beam size).  Feed order per slot and the round structure are the same.
+
+    ctc_prefix: {slot: (beam size, use_context)} of the slots whose utterance runs the CTC prefix beam search, None = no such slot and
+    the results above.  With it (an empty dict included) every call is (length, slots, offsets, beam_size, kind, use_context), kind
+    one of "greedy" / "beam" / "ctc_prefix" -- an rnnt_pool_chunk, rnnt_pool_chunk_beam or rnnt_pool_chunk_ctc_prefix call -- with one
+    (length, kind, beam size, use_context) class per call; inside a round the classes run in ascending (length, kind in that order,
+    beam size, use_context).  A slot listed in ctc_prefix is not looked up in beams."""
     offs = dict(offsets)
-    rounds: List[Dict[Tuple[int, int], List[Tuple[int, int]]]] = []   # round -> (length, beam) -> [(slot, queue index)]
+
+    def klass(slot, length):
+        if ctc_prefix is not None and slot in ctc_prefix:
+            return int(length), 2, int(ctc_prefix[slot][0]), int(bool(ctc_prefix[slot][1]))
+        beam = int(beams.get(slot, 0)) if beams else 0
+        return int(length), 1 if beam > 0 else 0, beam, 0
+    rounds: List[Dict[Tuple[int, int, int, int], List[Tuple[int, int]]]] = []   # round -> (length, kind, beam, use_context) -> [(slot, queue index)]
     depth: Dict[int, int] = {}
     index: List[Optional[Tuple[int, int]]] = [None] * len(queue)
     for k, (slot, length) in enumerate(queue):
@@ -863,17 +878,20 @@ def pool_plan(queue, offsets, beams=None):
         depth[slot] = r + 1
         while len(rounds) <= r:
             rounds.append({})
-        rounds[r].setdefault((int(length), int(beams.get(slot, 0)) if beams else 0), []).append((slot, k))
+        rounds[r].setdefault(klass(slot, length), []).append((slot, k))
     calls = []
     for rnd in rounds:
-        for length, beam in sorted(rnd):
+        for length, kind, beam, use_context in sorted(rnd):
             slots, call_offs = [], []
-            for slot, k in rnd[(length, beam)]:
+            for slot, k in rnd[(length, kind, beam, use_context)]:
                 index[k] = (len(calls), len(slots))
                 slots.append(slot)
                 call_offs.append(offs.get(slot, 0))
                 offs[slot] = offs.get(slot, 0) + length // 4
-            calls.append((length, slots, call_offs) if beams is None else (length, slots, call_offs, beam))
+            if ctc_prefix is not None:
+                calls.append((length, slots, call_offs, beam, _POOL_KINDS[kind], bool(use_context)))
+            else:
+                calls.append((length, slots, call_offs) if beams is None else (length, slots, call_offs, beam))
     return calls, offs, index
 
 
@@ -884,13 +902,18 @@ class StreamPool:
     an utterance are those of process_single_chunk on a model that holds only that stream, whatever the other slots do.
     Beam search per slot (max_beam > 0): open(beam_size=k) gives the slot a beam of its own, resident on the device, advanced by
     rnnt_pool_chunk_beam; beams(slot) returns what process_single_chunk_beam_search returns after each chunk, and close(slot) the
-    final hypotheses.  Greedy and beam slots live side by side in one pool; a library call holds slots of one kind."""
+    final hypotheses.  Greedy and beam slots live side by side in one pool; a library call holds slots of one kind.
+    CTC prefix beam search with hot words per slot: open(ctc_prefix_beam=k, context=None | ContextBias) gives the slot WeNet's
+    ctc_prefix_beam_search on the CTC head, carried across chunks on the device by rnnt_pool_chunk_ctc_prefix (one call = encode +
+    CTC + search of the new frames); ctc_hyps(slot) reads the hypotheses as they stand and close(slot) returns the final ones, those
+    of the one-launch search over the utterance's frames.  The pool holds one context graph at a time."""
 
     def __init__(self, state_dict, n_slots: int, vocab_size: int = 412, blank_id: int = 5, max_chunk_frames: int = 64,
                  max_cache_frames: int = 512, max_tokens: int = 4096, device: int = 0, numerics=None, packed=None, engine=None,
                  max_beam: int = 0):
         """state_dict / packed: as StreamingBatch.  engine: an object with reset / stream_open / pool_chunk / stream_tokens (and
-        pool_chunk_beam / stream_beam for beam slots) to drive instead of a new RnntEngine (a recording fake in the CPU tests).
+        pool_chunk_beam / stream_beam for beam slots, pool_chunk_ctc_prefix / stream_ctc_prefix / context_set for CTC prefix slots)
+        to drive instead of a new RnntEngine (a recording fake in the CPU tests).
         max_beam: the largest beam_size open() may be given (0: greedy only)."""
         self.n = n_slots
         self.blank_id = blank_id
@@ -906,6 +929,7 @@ class StreamPool:
             else:
                 engine.load_state_dict(state_dict, numerics=numerics)
         self.engine = engine
+        self._context: Optional[ContextBias] = None     # the ContextBias whose graph the context holds (it outlives reset())
         self.reset()
 
     def reset(self):
@@ -915,6 +939,7 @@ class StreamPool:
         self._offset: Dict[int, int] = {}
         self._ntok: Dict[int, int] = {}
         self._beam: Dict[int, int] = {}                 # beam size of the open slots (0 = greedy)
+        self._ctc: Dict[int, Tuple[int, Optional[ContextBias]]] = {}   # (beam, context) of the open CTC prefix slots
         self._queue: List[Tuple[int, torch.Tensor]] = []
         self._carry: Dict[int, List[int]] = {}          # increments of other slots produced by the step inside a close()
 
@@ -922,17 +947,35 @@ class StreamPool:
     def _stream(t):
         return _stream_ptr() if (t is None and torch.cuda.is_available()) or (t is not None and t.is_cuda) else None
 
-    def open(self, beam_size: int = 0) -> int:
+    def open(self, beam_size: int = 0, ctc_prefix_beam: int = 0, context: Optional[ContextBias] = None) -> int:
         """The lowest free slot, reset for a new utterance (reset_streaming_cache for that slot alone).  beam_size > 0: the slot's
         utterance is beam-searched with that beam (its hypotheses start as the one empty hypothesis); raises RnntError at once
-        when this pool cannot do it."""
+        when this pool cannot do it.  ctc_prefix_beam > 0 (not together with beam_size): the slot's utterance runs the CTC prefix beam
+        search with that beam, biased by `context` when given.  The pool holds one graph at a time: a context other than the current
+        one is uploaded (context_set) unless another biased slot is still open, which raises RnntError.  A refused open() -- a
+        graph the library rejects included (an empty phrase, the blank, a token outside the vocabulary) -- takes no slot."""
+        if ctc_prefix_beam:
+            if beam_size:
+                raise RnntError("stream pool: beam_size and ctc_prefix_beam are mutually exclusive")
+            if ctc_prefix_beam < 1 or ctc_prefix_beam > min(16, self.vocab_size) or self.vocab_size > 512:
+                raise RnntError(f"stream pool: ctc_prefix_beam {ctc_prefix_beam} outside [1, min(16, vocabulary {self.vocab_size})] or vocabulary > 512")
+            if context is not None and context is not self._context and any(c is not None for _, c in self._ctc.values()):
+                raise RnntError("stream pool: another context graph is in use by an open slot (one graph per pool at a time)")
+        elif context is not None:
+            raise RnntError("stream pool: context needs ctc_prefix_beam")
         if beam_size < 0 or beam_size > 0 and (beam_size > min(self.max_beam, 16) or self.vocab_size > 512):
             raise RnntError(f"stream pool: beam_size {beam_size} outside [0, min(max_beam {self.max_beam}, 16)] or vocabulary "
                             f"{self.vocab_size} > 512")
         if not self._free:
             raise RnntError(f"stream pool full: all {self.n} slots are open")
-        slot = self._free.pop(0)
+        if context is not None and context is not self._context:   # before a slot is taken: the library may refuse the graph
+            self.engine.context_set(context.phrases, context.context_score)
+            self._context = context
+        slot = self._free[0]
         self.engine.stream_open(slot, self._stream(None))
+        self._free.pop(0)
+        if ctc_prefix_beam:
+            self._ctc[slot] = (int(ctc_prefix_beam), context)
         self._offset[slot] = 0
         self._ntok[slot] = 0
         self._beam[slot] = int(beam_size)
@@ -953,19 +996,24 @@ class StreamPool:
     def step(self) -> Dict[int, List[int]]:
         """Advance every slot that has chunks queued: one rnnt_pool_chunk call per chunk length of the greedy slots and one
         rnnt_pool_chunk_beam call per (chunk length, beam size) of the beam slots (pool_plan), the rows of a call gathered into one
-        contiguous device tensor.  Returns {slot: tokens emitted by this step} for the GREEDY slots that advanced; a beam slot's
-        hypotheses are read with beams(slot)."""
+        contiguous device tensor; CTC prefix slots likewise through one rnnt_pool_chunk_ctc_prefix call per (chunk length, beam size,
+        use_context).  Returns {slot: tokens emitted by this step} for the GREEDY slots that advanced; a beam slot's hypotheses are
+        read with beams(slot), a CTC prefix slot's with ctc_hyps(slot)."""
         out, self._carry = self._carry, {}
         if not self._queue:
             return out
-        calls, offs, index = pool_plan([(slot, c.size(0)) for slot, c in self._queue], self._offset, self._beam)
+        calls, offs, index = pool_plan([(slot, c.size(0)) for slot, c in self._queue], self._offset, self._beam,
+                                       {slot: (b, c is not None) for slot, (b, c) in self._ctc.items()})
         rows: List[List[Optional[torch.Tensor]]] = [[None] * len(call[1]) for call in calls]
         for (slot, c), at in zip(self._queue, index):
             rows[at[0]][at[1]] = c
         touched = []
-        for (length, slots, call_offs, beam), chunks in zip(calls, rows):
+        for (length, slots, call_offs, beam, kind, use_context), chunks in zip(calls, rows):
             x = torch.stack(chunks, 0).contiguous()
-            if beam > 0:
+            if kind == "ctc_prefix":
+                self.engine.pool_chunk_ctc_prefix(slots, x.data_ptr(), length, call_offs, call_offs, beam, use_context, self._stream(x))
+                continue
+            if kind == "beam":
                 self.engine.pool_chunk_beam(slots, x.data_ptr(), length, call_offs, call_offs, beam, self._stream(x))
                 continue
             self.engine.pool_chunk(slots, x.data_ptr(), length, call_offs, call_offs, True, self._stream(x))
@@ -985,15 +1033,27 @@ class StreamPool:
             raise RnntError(f"slot {slot} is not an open beam slot")
         return [BeamHypothesis(t, lp) for t, lp in self.engine.stream_beam(slot, self._stream(None))]
 
+    def ctc_hyps(self, slot: int, final: bool = False):
+        """[(tokens, score, times)] of a CTC prefix slot in the search's order, as they stand after the chunks stepped so far (times:
+        encoder-frame indices since the slot was opened).  final: what the one-launch search returns had the utterance ended here
+        (finalize's context score instead of the running one).  Reading changes nothing."""
+        if slot not in self._ctc:
+            raise RnntError(f"slot {slot} is not an open CTC prefix slot")
+        return [(tok, score, times) for tok, score, times, _ in self.engine.stream_ctc_prefix(slot, final, stream=self._stream(None))]
+
     def close(self, slot: int):
-        """Finish the slot's utterance (queued chunks are processed first) and free the slot; returns all its tokens (greedy slot)
-        or its final hypotheses (beam slot)."""
+        """Finish the slot's utterance (queued chunks are processed first) and free the slot; returns all its tokens (greedy slot),
+        its final hypotheses (beam slot) or ctc_hyps(slot, final=True) (CTC prefix slot)."""
         if slot not in self._offset:
             raise RnntError(f"slot {slot} is not open")
         if any(s == slot for s, _ in self._queue):
             self._carry = self.step()                   # the other slots' increments are handed out by the next step()
         self._carry.pop(slot, None)
-        res = self.beams(slot) if self._beam[slot] > 0 else self.engine.stream_tokens(slot, 0, self._stream(None))
+        if slot in self._ctc:
+            res = self.ctc_hyps(slot, final=True)
+            del self._ctc[slot]
+        else:
+            res = self.beams(slot) if self._beam[slot] > 0 else self.engine.stream_tokens(slot, 0, self._stream(None))
         del self._offset[slot], self._ntok[slot], self._beam[slot]
         self._free.append(slot)
         self._free.sort()

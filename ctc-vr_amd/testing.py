@@ -525,7 +525,7 @@ def _gap_stats(stats, vals, beam_size, name):
             stats["nonzero_gap"] = min(stats.get("nonzero_gap", math.inf), a - b)
 
 
-def ctc_prefix_beam_ref(lp, length, blank, beam_size, graph=None, stats=None):
+def ctc_prefix_beam_ref(lp, length, blank, beam_size, graph=None, stats=None, finalize=True):
     """WeNet's ctc_prefix_beam_search (search.py:139-236) for ONE utterance in plain Python: lp [T, vocab] float32, frames
     [0, length), graph a context_graph_ref or None.  Per frame: the top beam_size of the row, value descending and lower index first
     on equal values; outer loop over those tokens, inner over the hypotheses in their order; blank / repeat / other as the
@@ -533,7 +533,8 @@ def ctc_prefix_beam_ref(lp, length, blank, beam_size, graph=None, stats=None):
     only when the token's value also exceeds the entry's current one); an entry's context comes from the first contribution that
     touches it, and since it is a function of the token string alone every later contribution must agree, which is asserted; sort
     by score + context score descending, stable over first insertion, truncate.  At the end a graph REPLACES every context score
-    by finalize's and the list is not re-sorted.
+    by finalize's and the list is not re-sorted; finalize=False skips that and returns the running context scores (score =
+    log_add(s, ns) + running), what a search that goes on holds at this frame (rnnt_stream_get_ctc_prefix with final = 0).
     Returns (hyps, prune_gap, top_gap): hyps [(tokens, score, times, context score)]; prune_gap the smallest difference between
     consecutive total scores of any frame's sorted entries, top_gap between consecutive values of any frame's top beam_size + 1
     (inf where there is nothing to compare).  stats: a dict whose "stale_times" counts the repeats that raised v_ns and kept the
@@ -622,7 +623,7 @@ def ctc_prefix_beam_ref(lp, length, blank, beam_size, graph=None, stats=None):
             parent_born = {q: parent_born[q] if q in old else old[q[:-1]] for q, _ in cur if q}
     out = []
     for prefix, h in cur:
-        cs = graph.finalize(h.ctx_state) if graph is not None else 0.0
+        cs = 0.0 if graph is None else graph.finalize(h.ctx_state) if finalize else h.ctx_score
         out.append((list(prefix), h.score() + cs, list(h.times()), cs))
     return out, prune_gap, top_gap
 

@@ -410,6 +410,51 @@ int rnnt_ctc_prefix_beam_logprobs(rnnt_ctx* ctx, const float* lp_dev, const int3
 int rnnt_ctc_prefix_beam_decode(rnnt_ctx* ctx, const float* enc_dev, const int32_t* enc_lens_host, int32_t B, int32_t T,
                                 int32_t beam_size, int32_t use_context, int32_t cap_tokens, int32_t* n_hyp_host, int32_t* lens_host,
                                 int32_t* tokens_host, int32_t* times_host, double* scores_host, double* ctx_scores_host, void* stream);
+
+/* -- the same search per slot of the stream pool, carried across calls ---------------------------- */
+/* The search is a per-frame recursion whose state at a frame boundary is its <= 16 hypothesis records and two append-only arenas, so
+ * a search that stops at the end of a call and resumes at the next is, bit for bit, the one-launch search over the same rows,
+ * whatever the split.  Per slot the device keeps one record (about 2 KB) and [max_cache_frames * 16 + 1] (parent, value) pairs of
+ * either arena -- 1.28 MB per slot per arena at max_cache_frames = 5000 -- allocated on the first use.  Frames, and the times
+ * returned, are absolute encoder-frame indices since the slot's reset; a slot holds at most max_cache_frames of them.
+ * A slot's search is fresh after a reset; its first advancing call fixes beam_size and use_context until the next reset.
+ * rnnt_context_set starts a new graph generation: a search biased (use_context != 0) under an older generation is refused with
+ * RNNT_ERR_STATE until its slot is reset (its context states are node ids of a graph that no longer exists); unbiased searches go
+ * on.  Every refusal is decided before the first launch and changes no slot's state, position or frame count.  A slot's greedy
+ * state, its RNN-T beam and its CTC prefix search are independent of one another; a library call holds slots of one kind.
+ *
+ * start state (empty prefix, s = 0, ns = -inf, v_s = v_ns = 0, context root) for one slot, or all slots with slot = -1; any context,
+ * weights not needed.  rnnt_stream_open does this for its slot, rnnt_streams_reset for all (once the state exists). */
+int rnnt_stream_ctc_prefix_reset(rnnt_ctx* ctx, int32_t slot, void* stream);
+/* advance the searches of the listed slots (distinct, in [0, max_streams)) by t >= 1 frames of log-probabilities the caller holds:
+ * lp_dev [n_active, t, vocab] f32 device, row i belongs to slot slots_host[i].  ONE launch (ctc_prefix_search_pool: one workgroup per
+ * active row), no copy back, no synchronisation.  Any context (weights not needed).
+ * RNNT_ERR_ARG: null pointer, duplicated or out-of-range slot, t < 1, beam_size outside [1, min(16, vocab)], vocabulary > 512,
+ * beam_size or use_context differing from the search in progress.  RNNT_ERR_SHAPE: a slot's frames so far + t > max_cache_frames.
+ * RNNT_ERR_STATE: use_context with no graph set, or a stale graph generation. */
+int rnnt_pool_ctc_prefix_logprobs(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, const float* lp_dev, int32_t t,
+                                  int32_t beam_size, int32_t use_context, void* stream);
+/* rnnt_pool_chunk for the listed slots (same arguments, validation, encoder launches, position bookkeeping and refusals), then
+ * log_softmax(ctc_lo(.)) of the n_active * t' new encoder frames (rnnt_ctc_logprobs' arithmetic, kernel choices as for one stream's
+ * rows) and the launch above.  Frames are consumed: one call = encode + CTC + search.  Does not synchronise.  Also RNNT_ERR_STATE
+ * when the weights are not finalized, ctc_head.ctc_lo.* is not loaded, or frames are still buffered. */
+int rnnt_pool_chunk_ctc_prefix(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, const float* fbank_dev, int32_t chunk_frames,
+                               const int32_t* offsets_host, const int32_t* required_host, int32_t beam_size, int32_t use_context,
+                               int32_t* frames_out, void* stream);
+/* the slot's hypotheses now, in the search's order; layout and zero fill as rnnt_ctc_prefix_beam_logprobs for B = 1: lens / scores /
+ * ctx_scores (optional) [cap_hyps], tokens / times [cap_hyps][cap_tokens], with cap_hyps >= the slot's beam (1 for a fresh slot) and
+ * cap_tokens >= the frames walked.  final != 0: what the one-launch search returns had the utterance ended here (with a graph the
+ * context score is REPLACED by finalize's, no re-sort).  final == 0: context scores are the running ones and score = log_add(s, ns) +
+ * running.  A fresh slot has fixed no use_context: final != 0 finalizes its root under the graph that is set, if any (context score
+ * -0.0, as the one-launch search with use_context over no frames; +0.0 with no graph set or final == 0).  Reading changes nothing:
+ * the search goes on afterwards.  *frames_out (optional) = frames walked so far.  One pack launch (ctc_prefix_pack), one download,
+ * synchronises.  RNNT_ERR_STATE for final != 0 on a biased search of a stale graph generation.
+ * Size query: with lens_host, tokens_host, times_host and scores_host all NULL nothing is launched or copied; *n_hyp receives the
+ * cap_hyps the slot needs (its beam, 1 for a fresh slot) and *frames_out the cap_tokens it needs (cap_hyps / cap_tokens are ignored). */
+int rnnt_stream_get_ctc_prefix(rnnt_ctx* ctx, int32_t slot, int32_t final, int32_t cap_hyps, int32_t cap_tokens, int32_t* n_hyp,
+                               int32_t* lens_host, int32_t* tokens_host, int32_t* times_host, double* scores_host,
+                               double* ctx_scores_host, int32_t* frames_out, void* stream);
+
 /* The same search as a pure C++ function (no context, no GPU): lp_host [B, T, vocab], the graph passed as phrases (n_phrases == 0:
  * none).  The CPU seam the device path is compared against: tokens, times and order exact. */
 int rnnt_ctc_prefix_beam_host(const float* lp_host, const int32_t* enc_lens_host, int32_t B, int32_t T, int32_t vocab, int32_t blank,
@@ -516,7 +561,8 @@ const float* rnnt_enc_frames_dev(rnnt_ctx* ctx, int32_t* frames_out, int32_t* st
  * projection, 20 LSTM cell, 21 predictor projection, 22 joint pred_ffn+tanh, 23 joint ffn_out, 40 the picked lattice of
  * rnnt_transducer_nll, 41 its alpha recursion (and rnnt_ctc_nll's), 42 the Viterbi launch of the rnnt_*_align calls, 43 prefix_step
  * and 44 prefix_merge of rnnt_prefix_beam_decode (one launch each per frame), 45 ctc_prefix_search of the rnnt_ctc_prefix_beam_*
- * calls (one launch per call).
+ * calls (one launch per call), 46 ctc_prefix_search_pool of rnnt_pool_ctc_prefix_logprobs / rnnt_pool_chunk_ctc_prefix (the resumable
+ * search launch), 47 ctc_prefix_pack of rnnt_stream_get_ctc_prefix (the pack launch).
  * rnnt_profile_end synchronises the recorded events and returns the summed kernel time and launch count. */
 int rnnt_profile_begin(rnnt_ctx* ctx, int32_t tag);
 int rnnt_profile_end(rnnt_ctx* ctx, double* total_ms, int64_t* n_launches);
