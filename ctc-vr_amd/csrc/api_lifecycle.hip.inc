@@ -502,6 +502,7 @@ int rnnt_streams_reset(rnnt_ctx* ctx, int32_t n_streams, void* stream) {
         HIPCHK(hipMemsetAsync(ctx->pool[0], 0, (size_t)ctx->max_rows * (ctx->cfg.n_steps + 1) * 512 * sizeof(float), s));
     }
     int rc;
+    pool_wave_reset(ctx, 0, B);                             // the per-slot streaming front-ends of the stream pool
     if ((rc = pool_beam_reset(ctx, s, 0, B))) return rc;   // the per-slot beam state of the stream pool, once it exists
     return pool_ctc_reset(ctx, s, 0, B);                    // and its per-slot CTC prefix searches
 }

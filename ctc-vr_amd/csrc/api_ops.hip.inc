@@ -210,6 +210,49 @@ int rnnt_greedy_search_full(rnnt_ctx* ctx, const float* fbank_dev, const int32_t
     return RNNT_OK;
 }
 
+namespace {
+// The DFT rows (w cos, -w sin interleaved, periodic Hamming window) and the HTK mel filterbank of (sample_rate, n_fft), in double on
+// the host and cached on the device until another pair is asked for.  rnnt_fbank and rnnt_pool_wave multiply by the same two matrices.
+int fbank_matrices(rnnt_ctx* ctx, hipStream_t s, int sample_rate, int n_fft) {
+    if (ctx->fb_rate == sample_rate && ctx->fb_nfft == n_fft) return RNNT_OK;
+    const int n_mels = 80, nfreq = n_fft / 2 + 1, n2p = (2 * nfreq + 63) / 64 * 64, kp = (nfreq + 63) / 64 * 64;
+    int rc;
+    HIPCHK(hipStreamSynchronize(s));
+    if ((rc = reserve_exact(ctx, ctx->fb_dft, (size_t)n2p * n_fft))) return rc;
+    if ((rc = reserve_exact(ctx, ctx->fb_mel, (size_t)n_mels * kp))) return rc;
+    const double pi = 3.14159265358979323846;
+    std::vector<float> dft((size_t)n2p * n_fft, 0.f), mel((size_t)n_mels * kp, 0.f);
+    std::vector<double> win(n_fft);
+    for (int n = 0; n < n_fft; ++n) win[n] = 0.54 - 0.46 * cos(2.0 * pi * n / n_fft);   // torch.hamming_window (periodic)
+    for (int k = 0; k < nfreq; ++k)
+        for (int n = 0; n < n_fft; ++n) {
+            const long long kn = ((long long)k * n) % n_fft;                              // exact phase reduction
+            const double ph = 2.0 * pi * (double)kn / n_fft;
+            dft[(size_t)(2 * k) * n_fft + n] = (float)(win[n] * cos(ph));
+            dft[(size_t)(2 * k + 1) * n_fft + n] = (float)(-win[n] * sin(ph));
+        }
+    // torchaudio.functional.melscale_fbanks(n_freqs, 0, rate/2, 80, rate, norm=None, mel_scale="htk")
+    const double fmax = (double)(sample_rate / 2);   // all_freqs = linspace(0, sample_rate // 2, n_freqs)
+    const double m_max = 2595.0 * log10(1.0 + fmax / 700.0);             // f_max = float(sample_rate // 2)
+    std::vector<double> fpts(n_mels + 2);
+    for (int i = 0; i < n_mels + 2; ++i) fpts[i] = 700.0 * (pow(10.0, (m_max * i / (n_mels + 1)) / 2595.0) - 1.0);
+    for (int k = 0; k < nfreq; ++k) {
+        const double f = fmax * k / (nfreq - 1);
+        for (int m = 0; m < n_mels; ++m) {
+            const double down = (f - fpts[m]) / (fpts[m + 1] - fpts[m]);
+            const double up = (fpts[m + 2] - f) / (fpts[m + 2] - fpts[m + 1]);
+            const double v = down < up ? down : up;
+            mel[(size_t)m * kp + k] = (float)(v > 0.0 ? v : 0.0);
+        }
+    }
+    HIPCHK(hipMemcpy(ctx->fb_dft, dft.data(), dft.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ctx->fb_mel, mel.data(), mel.size() * sizeof(float), hipMemcpyHostToDevice));
+    ctx->fb_rate = sample_rate;
+    ctx->fb_nfft = n_fft;
+    return RNNT_OK;
+}
+}  // namespace
+
 // Feature front-end on the device (SURVEY.md §8f): the reference's extract_audio_features (data/dataloader.py:15-41) =
 // torchaudio MelSpectrogram(sample_rate, n_fft, n_mels=80, hop_length=512, window_fn=hamming_window, power=2.0)
 // [defaults: win_length = n_fft, center=True, pad_mode="reflect", onesided, HTK mel scale, norm=None, f_min=0,
@@ -231,40 +274,7 @@ int rnnt_fbank(rnnt_ctx* ctx, const float* wave_dev, int32_t B, int32_t n_sample
     const long long M = (long long)B * T;
     if (M > 0x7fffffffLL / 8) return fail(ctx, RNNT_ERR_SHAPE, "rnnt_fbank: %lld frames in one call", M);
     int rc;
-    if (ctx->fb_rate != sample_rate || ctx->fb_nfft != n_fft) {   // matrices in double on the host, once per (rate, n_fft)
-        HIPCHK(hipStreamSynchronize(s));
-        if ((rc = reserve_exact(ctx, ctx->fb_dft, (size_t)n2p * n_fft))) return rc;
-        if ((rc = reserve_exact(ctx, ctx->fb_mel, (size_t)n_mels * kp))) return rc;
-        const double pi = 3.14159265358979323846;
-        std::vector<float> dft((size_t)n2p * n_fft, 0.f), mel((size_t)n_mels * kp, 0.f);
-        std::vector<double> win(n_fft);
-        for (int n = 0; n < n_fft; ++n) win[n] = 0.54 - 0.46 * cos(2.0 * pi * n / n_fft);   // torch.hamming_window (periodic)
-        for (int k = 0; k < nfreq; ++k)
-            for (int n = 0; n < n_fft; ++n) {
-                const long long kn = ((long long)k * n) % n_fft;                              // exact phase reduction
-                const double ph = 2.0 * pi * (double)kn / n_fft;
-                dft[(size_t)(2 * k) * n_fft + n] = (float)(win[n] * cos(ph));
-                dft[(size_t)(2 * k + 1) * n_fft + n] = (float)(-win[n] * sin(ph));
-            }
-        // torchaudio.functional.melscale_fbanks(n_freqs, 0, rate/2, 80, rate, norm=None, mel_scale="htk")
-        const double fmax = (double)(sample_rate / 2);   // all_freqs = linspace(0, sample_rate // 2, n_freqs)
-        const double m_max = 2595.0 * log10(1.0 + fmax / 700.0);             // f_max = float(sample_rate // 2)
-        std::vector<double> fpts(n_mels + 2);
-        for (int i = 0; i < n_mels + 2; ++i) fpts[i] = 700.0 * (pow(10.0, (m_max * i / (n_mels + 1)) / 2595.0) - 1.0);
-        for (int k = 0; k < nfreq; ++k) {
-            const double f = fmax * k / (nfreq - 1);
-            for (int m = 0; m < n_mels; ++m) {
-                const double down = (f - fpts[m]) / (fpts[m + 1] - fpts[m]);
-                const double up = (fpts[m + 2] - f) / (fpts[m + 2] - fpts[m + 1]);
-                const double v = down < up ? down : up;
-                mel[(size_t)m * kp + k] = (float)(v > 0.0 ? v : 0.0);
-            }
-        }
-        HIPCHK(hipMemcpy(ctx->fb_dft, dft.data(), dft.size() * sizeof(float), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(ctx->fb_mel, mel.data(), mel.size() * sizeof(float), hipMemcpyHostToDevice));
-        ctx->fb_rate = sample_rate;
-        ctx->fb_nfft = n_fft;
-    }
+    if ((rc = fbank_matrices(ctx, s, sample_rate, n_fft))) return rc;   // once per (rate, n_fft)
     if ((rc = reserve(ctx, ctx->fb_pad, (size_t)B * pstride))) return rc;
     if ((rc = reserve(ctx, ctx->fb_spec, (size_t)M * n2p))) return rc;
     if ((rc = reserve(ctx, ctx->fb_pow, (size_t)M * kp))) return rc;

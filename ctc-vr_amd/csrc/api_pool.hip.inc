@@ -120,6 +120,7 @@ int rnnt_stream_open(rnnt_ctx* ctx, int32_t slot, void* stream) {
     LAUNCHCHK("stream_slot_reset");
     if ((rc = pool_beam_reset(ctx, s, slot, 1))) return rc;   // the slot's beam: one empty hypothesis (once the beam state exists)
     if ((rc = pool_ctc_reset(ctx, s, slot, 1))) return rc;    // the slot's CTC prefix search: the start hypothesis (likewise)
+    pool_wave_reset(ctx, slot, 1);                            // the slot's streaming front-end: no samples, no frames
     pool_enter(ctx);
     ctx->slot_pos[slot] = SlotPos{0, 0, 0};
     return RNNT_OK;

@@ -35,7 +35,8 @@ enum { TAG_NONE = 0, TAG_CONV1 = 1, TAG_CONV2 = 2, TAG_EMBED = 3, TAG_FFN1 = 4, 
        TAG_SCORE_VITERBI = 42,                        // forced alignment: transducer_viterbi / ctc_viterbi, back-trace included
        TAG_PREFIX_STEP = 43, TAG_PREFIX_MERGE = 44,   // prefix beam search: prefix_step / prefix_merge, one launch each per frame
        TAG_CTC_PREFIX = 45,                           // CTC prefix beam search: ctc_prefix_search, one launch per call
-       TAG_CTC_PREFIX_POOL = 46, TAG_CTC_PREFIX_PACK = 47 };   // its resumable form per slot of the stream pool: ctc_prefix_search_pool / ctc_prefix_pack
+       TAG_CTC_PREFIX_POOL = 46, TAG_CTC_PREFIX_PACK = 47,     // its resumable form per slot of the stream pool: ctc_prefix_search_pool / ctc_prefix_pack
+       TAG_WAVE_STAGE = 48 };                         // streaming front-end of the stream pool: wave_stage of rnnt_pool_wave
 
 struct ProfScope {   // records a start/stop event pair around one launch when its site is selected
     rnnt_ctx* ctx; hipStream_t s; bool on;
@@ -634,6 +635,12 @@ int pool_ctc_reset(rnnt_ctx* ctx, hipStream_t s, int slot0, int n) {
     hipLaunchKernelGGL(ctc_prefix_slot_reset, dim3(n), dim3(64), 0, s, ctx->pc_state.p, slot0);
     LAUNCHCHK("ctc_prefix_slot_reset");
     return RNNT_OK;
+}
+
+// ---- per-slot streaming front-end of the stream pool (api_pool_wave.hip.inc; kernels in rnnt_frontend.hip.h) ---------------------------
+// a fresh utterance for slots [slot0, slot0 + n): host records only -- a fresh slot's carry is empty, so the device carry needs no reset
+void pool_wave_reset(rnnt_ctx* ctx, int slot0, int n) {
+    for (int b = slot0; b < slot0 + n && b < (int)ctx->wv_slot.size(); ++b) ctx->wv_slot[b] = rnnt_ctx::WvSlot{0, 0, 0, 0, 0};
 }
 
 }  // namespace

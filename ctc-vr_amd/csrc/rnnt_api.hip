@@ -278,6 +278,16 @@ struct rnnt_ctx {
     PinnedBuf<int> pc_tab_host;
     hipEvent_t pc_ev = nullptr;
     DevBuf<double> pc_out;
+    // streaming feature front-end per slot of the stream pool (api_pool_wave.hip.inc), allocated on its first use: the carry of every
+    // slot [max_streams][WAVE_CARRY_CAP], the staged rows of one call (grow-only), the call's table (slot, samples so far, new samples,
+    // final per active row; one async copy from pinned memory).  Host per slot: samples received and frames emitted since the reset,
+    // the (sample_rate, n_fft) its first push fixed (n_fft == 0: fresh) and whether its utterance has ended.
+    struct WvSlot { int samples, frames, rate, nfft, finished; };
+    std::vector<WvSlot> wv_slot;
+    DevBuf<float> wv_carry, wv_stage;
+    DevBuf<int> wv_tab;
+    PinnedBuf<int> wv_tab_host;
+    hipEvent_t wv_ev = nullptr;
     hipStream_t cap_stream = nullptr;          // stream-capture scratch stream
     struct DecGraph { int n_streams, k; hipGraphExec_t exec; };
     std::vector<DecGraph> dec_graphs;          // K greedy steps captured once per (n_streams, K)
@@ -292,7 +302,7 @@ struct rnnt_ctx {
     // constructor -- rnnt_create's `new rnnt_ctx()` value-initialises lw[] and the raw weight views to null.
     ~rnnt_ctx() {
         for (auto& g : dec_graphs) (void)hipGraphExecDestroy(g.exec);
-        for (hipEvent_t e : {pool_ev, pc_ev, sub_ev[0], sub_ev[1]}) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : {pool_ev, pc_ev, wv_ev, sub_ev[0], sub_ev[1]}) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : prof_ev) (void)hipEventDestroy(e);
         for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
         for (hipStream_t st : {dec_stream, cap_stream, sub_stream}) if (st) (void)hipStreamDestroy(st);
@@ -313,6 +323,7 @@ extern "C" {
 #include "api_state.hip.inc"
 #include "api_pool_ctc.hip.inc"
 #include "api_pool.hip.inc"
+#include "api_pool_wave.hip.inc"
 #include "api_prefix.hip.inc"
 #include "api_ctc_prefix.hip.inc"
 }  // extern "C"

@@ -14,7 +14,7 @@
 //                  direct row streaming), dwconv_bn_silu, conv_ring_init
 //   rnnt_decode    greedy_decide (launched path), greedy_stream / greedy_multi (resident decoders),
 //                  publish_frames, probe_overlap_wait, unpack_keys
-//   rnnt_frontend  reflect_pad, power_spectrum (rnnt_fbank)
+//   rnnt_frontend  reflect_pad, power_spectrum (rnnt_fbank); wave_stage, wave_carry_roll and their index helper (rnnt_pool_wave)
 //   rnnt_beam      beam_chain, beam_reduce, beam_gather, log_softmax_rows
 //   rnnt_prefix    prefix_step, prefix_merge, prefix_init, prefix_pack (rnnt_prefix_beam_decode)
 //   rnnt_misc      fill_i32, gather_att_cache, gather_cnn_cache

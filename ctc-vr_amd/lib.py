@@ -76,6 +76,10 @@ SIGNATURES = {
     "rnnt_ctc_align": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "rnnt_ctc_align_logprobs": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "rnnt_fbank": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32p, c_vp]),
+    "rnnt_pool_wave": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp]),
+    "rnnt_stream_wave_reset": (c_i32, [c_vp, c_i32, c_vp]),
+    "rnnt_stream_get_wave_state": (c_i32, [c_vp, c_i32, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_vp, c_i32, c_vp]),
+    "rnnt_wave_stage_host": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32p, c_i32p, c_i32p, c_vp, c_i32, c_i32p]),
     "rnnt_greedy_search_full": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "rnnt_get_att_cache": (c_i32, [c_vp, c_i32, c_vp, c_i32p, c_vp]),
     "rnnt_get_cnn_cache": (c_i32, [c_vp, c_i32, c_vp, c_vp]),
@@ -251,11 +255,26 @@ def ctc_prefix_beam_host(lp, enc_lens, blank, beam_size, phrases=None, context_s
     return (_ctc_prefix_hyps(out), out) if raw else _ctc_prefix_hyps(out)
 
 
+def wave_stage_host(carry, samples_so_far, new, final, n_fft=1024):
+    """rnnt_wave_stage_host (no context, no GPU): one slot's push of the streaming front-end -- carry (float32 [n]) and the samples
+    received before, `new` samples, final -> (staged row from the push's first new frame on: frame r at r * 512, first frame index,
+    frames emitted, carry after the push)."""
+    carry, new = np.ascontiguousarray(carry, np.float32), np.ascontiguousarray(new, np.float32)
+    staged, out = np.zeros(new.size + 3 * n_fft + 1024, np.float32), np.zeros(n_fft, np.float32)
+    sl, f0, nf, nc = c_i32(0), c_i32(0), c_i32(0), c_i32(0)
+    rc = load().rnnt_wave_stage_host(_np_ptr(carry), carry.size, int(samples_so_far), _np_ptr(new), new.size, 1 if final else 0, n_fft, _np_ptr(staged),
+                                     staged.size, ctypes.byref(sl), ctypes.byref(f0), ctypes.byref(nf), _np_ptr(out), out.size, ctypes.byref(nc))
+    if rc != 0:
+        raise RnntError(f"rnnt_wave_stage_host: bad argument (status {rc})", rc)
+    return staged[:sl.value].copy(), f0.value, nf.value, out[:nc.value].copy()
+
+
 class RnntEngine:
     """One context = one GPU = up to `max_streams` streams: lock-stepped (encoder_chunk / encoder_chunks / decode_ragged), or the
     slots of a stream pool that open, advance and close independently (stream_open / pool_chunk / stream_tokens, and per-slot beam
     search through pool_chunk_beam / stream_beam / stream_beam_states, per-slot CTC prefix beam search with hot words through
-    pool_chunk_ctc_prefix / pool_ctc_prefix_logprobs / stream_ctc_prefix / stream_ctc_prefix_reset)."""
+    pool_chunk_ctc_prefix / pool_ctc_prefix_logprobs / stream_ctc_prefix / stream_ctc_prefix_reset, audio in per slot through
+    pool_wave / wave_state / stream_wave_reset)."""
 
     def __init__(self, max_streams=1, max_chunk_frames=64, max_cache_frames=1024, max_enc_frames=1024, max_tokens=4096,
                  vocab_size=412, blank_id=5, n_steps=10, device=0, max_beam=0):
@@ -625,6 +644,35 @@ class RnntEngine:
                                                       ctypes.byref(frames), stream), "rnnt_stream_get_ctc_prefix")
         hyps = _ctc_prefix_hyps(out)[0]
         return (hyps, out, frames.value) if raw else hyps
+
+    def pool_wave(self, slots, wave_ptr, n_samples, samples, final, out_ptr, cap_frames, sample_rate=16000, n_fft=1024, stream=None):
+        """rnnt_pool_wave: the streaming feature front-end for the listed slots -- row i of the device tensor at wave_ptr
+        ([len(slots), n_samples] float32) holds samples[i] new samples of slots[i], final[i]: its utterance ends with them; the new
+        frames of row i go to row i of the device tensor at out_ptr ([len(slots), cap_frames, 80]).  Returns the frames written per
+        row (int32 [len(slots)]).  Does not synchronise."""
+        a, n, f = (np.ascontiguousarray(v, np.int32) for v in (slots, samples, [1 if x else 0 for x in final]))
+        assert a.ndim == 1 and a.size == n.size == f.size
+        frames = np.zeros(a.size, np.int32)
+        self._chk(self.lib.rnnt_pool_wave(self.ctx, a.size, _np_ptr(a), wave_ptr, n_samples, _np_ptr(n), _np_ptr(f), sample_rate, n_fft, out_ptr,
+                                          cap_frames, _np_ptr(frames), stream), "rnnt_pool_wave")
+        return frames
+
+    def stream_wave_reset(self, slot, stream=None):
+        """rnnt_stream_wave_reset: a fresh utterance for one slot's front-end (-1: all slots)."""
+        self._chk(self.lib.rnnt_stream_wave_reset(self.ctx, slot, stream), "rnnt_stream_wave_reset")
+
+    def wave_state(self, slot, stream=None):
+        """rnnt_stream_get_wave_state: dict of samples, frames, sample_rate, n_fft, finished and carry (float32 array) of one slot;
+        synchronises."""
+        v = [c_i32(0) for _ in range(6)]
+        self._chk(self.lib.rnnt_stream_get_wave_state(self.ctx, slot, *[ctypes.byref(x) for x in v], None, 0, stream), "rnnt_stream_get_wave_state")
+        carry = np.zeros(max(v[5].value, 1), np.float32)
+        self._chk(self.lib.rnnt_stream_get_wave_state(self.ctx, slot, *[ctypes.byref(x) for x in v], _np_ptr(carry), carry.size, stream),
+                  "rnnt_stream_get_wave_state")
+        return {"samples": v[0].value, "frames": v[1].value, "sample_rate": v[2].value, "n_fft": v[3].value, "finished": bool(v[4].value),
+                "carry": carry[:v[5].value]}
+
+    wave_stage_host = staticmethod(wave_stage_host)
 
     def prefix_merge_device(self, hyps, top_lp, top_tok, blank, beam_size, stream=None):
         """rnnt_prefix_merge_device: prefix_merge_host's arguments and results through one prefix_merge launch."""

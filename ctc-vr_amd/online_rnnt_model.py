@@ -895,6 +895,55 @@ def pool_plan(queue, offsets, beams=None, ctc_prefix=None):
     return calls, offs, index
 
 
+def wave_frames(n: int, n_fft: int, final: bool) -> int:
+    """Frames of the streaming front-end emittable from n samples (rnnt_pool_wave's host arithmetic): frame f covers samples
+    [f*512 - n_fft/2, f*512 + n_fft/2); before the end of the utterance every frame whose span ends by n, and none until frame 0's
+    left reflection exists (n >= n_fft/2 + 1); at the end all 1 + n // 512, or none for n <= n_fft/2."""
+    half = n_fft // 2
+    if final:
+        return 1 + n // 512 if n > half else 0
+    return (n - half) // 512 + 1 if n >= half + 1 else 0
+
+
+def wave_plan(queue, samples, fifo, chunk_frames, n_fft=1024):
+    """The audio side of one StreamPool.step as a pure function (no GPU, no tensors): ONE rnnt_pool_wave call whatever the number of
+    slots and packets, then the chunks that leave the per-slot frame FIFOs.
+
+    queue: [(slot, n_samples, final)] in feed order, several packets per slot allowed (they are concatenated; the utterance is final
+    when any of them says so); samples: {slot: samples received before}; fifo: {slot: frames waiting from earlier steps}.
+    Returns (call, chunks, new_samples, new_fifo): call = (slots, counts, finals, frames) -- the rows of the call in order of each
+    slot's first packet, the new samples, final flag and frames emitted per row -- or None for an empty queue; chunks = [(slot, start,
+    length)] in row order: slices of the slot's FIFO (old frames, then the new ones) that go to the chunk queue, every full
+    chunk_frames and, at final, the remainder as the slot's last chunk (feed() skips it under 7 frames, as process_single_chunk
+    does); new_fifo = frames left waiting."""
+    new_samples, new_fifo = dict(samples), dict(fifo)
+    if not queue:
+        return None, [], new_samples, new_fifo
+    slots, counts, finals = [], {}, {}
+    for slot, n, final in queue:
+        if slot not in counts:
+            slots.append(slot)
+            counts[slot], finals[slot] = 0, False
+        assert not finals[slot], f"slot {slot}: a packet after the final one"
+        counts[slot] += int(n)
+        finals[slot] = bool(final)
+    frames, chunks = [], []
+    for slot in slots:
+        before = samples.get(slot, 0)
+        nf = wave_frames(before + counts[slot], n_fft, finals[slot]) - wave_frames(before, n_fft, False)
+        frames.append(nf)
+        new_samples[slot] = before + counts[slot]
+        have, at = fifo.get(slot, 0) + nf, 0
+        while have - at >= chunk_frames:
+            chunks.append((slot, at, chunk_frames))
+            at += chunk_frames
+        if finals[slot] and have > at:
+            chunks.append((slot, at, have - at))
+            at = have
+        new_fifo[slot] = have - at
+    return (slots, [counts[s] for s in slots], [finals[s] for s in slots], frames), chunks, new_samples, new_fifo
+
+
 class StreamPool:
     """A context's slots, each with its own life (not in the reference, which is B=1): open() a slot when a caller connects, feed()
     it a chunk whenever the caller has one, step() to advance whatever subset of slots has chunks queued -- each at its own cache
@@ -906,16 +955,24 @@ class StreamPool:
     CTC prefix beam search with hot words per slot: open(ctc_prefix_beam=k, context=None | ContextBias) gives the slot WeNet's
     ctc_prefix_beam_search on the CTC head, carried across chunks on the device by rnnt_pool_chunk_ctc_prefix (one call = encode +
     CTC + search of the new frames); ctc_hyps(slot) reads the hypotheses as they stand and close(slot) returns the final ones, those
-    of the one-launch search over the utterance's frames.  The pool holds one context graph at a time."""
+    of the one-launch search over the utterance's frames.  The pool holds one context graph at a time.
+    Audio in: feed_wave(slot, samples, final) queues PCM packets instead of feature chunks; step() first turns the packets of all
+    slots into fbank frames with ONE rnnt_pool_wave call (the streaming form of rnnt_fbank: per slot the frames of the whole
+    waveform, whatever the packet split), collects them in a per-slot device FIFO and moves every full chunk_frames, and at final
+    the remainder, to the chunk queue.  A slot is fed either way, never both."""
 
     def __init__(self, state_dict, n_slots: int, vocab_size: int = 412, blank_id: int = 5, max_chunk_frames: int = 64,
                  max_cache_frames: int = 512, max_tokens: int = 4096, device: int = 0, numerics=None, packed=None, engine=None,
-                 max_beam: int = 0):
+                 max_beam: int = 0, sample_rate: int = 16000, n_fft: int = 1024, chunk_frames: int = 16):
         """state_dict / packed: as StreamingBatch.  engine: an object with reset / stream_open / pool_chunk / stream_tokens (and
         pool_chunk_beam / stream_beam for beam slots, pool_chunk_ctc_prefix / stream_ctc_prefix / context_set for CTC prefix slots)
         to drive instead of a new RnntEngine (a recording fake in the CPU tests).
-        max_beam: the largest beam_size open() may be given (0: greedy only)."""
+        max_beam: the largest beam_size open() may be given (0: greedy only).
+        sample_rate / n_fft / chunk_frames: the front-end of feed_wave and the chunk length its frames are fed in (the engine also
+        needs pool_wave then)."""
         self.n = n_slots
+        self.sample_rate, self.n_fft, self.chunk_frames = int(sample_rate), int(n_fft), int(chunk_frames)
+        self._wave_device = torch.device("cuda", device) if engine is None else None   # an injected engine: where the packets are
         self.blank_id = blank_id
         self.max_beam = max_beam
         self.vocab_size = vocab_size
@@ -942,6 +999,11 @@ class StreamPool:
         self._ctc: Dict[int, Tuple[int, Optional[ContextBias]]] = {}   # (beam, context) of the open CTC prefix slots
         self._queue: List[Tuple[int, torch.Tensor]] = []
         self._carry: Dict[int, List[int]] = {}          # increments of other slots produced by the step inside a close()
+        self._wave_queue: List[Tuple[int, torch.Tensor, bool]] = []   # PCM packets (slot, samples, final) in feed order
+        self._wave_samples: Dict[int, int] = {}         # samples received by the open wave slots
+        self._wave_fifo: Dict[int, torch.Tensor] = {}   # [k, 80] frames waiting for a full chunk
+        self._wave_final: Dict[int, bool] = {}          # the open wave slots: has the final packet been queued
+        self._fed: Dict[int, str] = {}                  # "feed" / "wave": how the open slot is fed (fixed by its first packet or chunk)
 
     @staticmethod
     def _stream(t):
@@ -979,19 +1041,80 @@ class StreamPool:
         self._offset[slot] = 0
         self._ntok[slot] = 0
         self._beam[slot] = int(beam_size)
+        self._forget_wave(slot)
         return slot
+
+    def _forget_wave(self, slot: int):
+        for d in (self._wave_samples, self._wave_fifo, self._wave_final, self._fed):
+            d.pop(slot, None)
 
     def feed(self, slot: int, chunk: torch.Tensor) -> bool:
         """Queue one chunk [T, 80] (float32, on the device) for an open slot; the next step() encodes and decodes it.  A chunk of
-        fewer than 7 frames is skipped as in process_single_chunk (:356-359): returns False and the slot's offset stays."""
+        fewer than 7 frames is skipped as in process_single_chunk (:356-359): returns False and the slot's offset stays.  Raises
+        RnntError on a slot fed through feed_wave."""
         if slot not in self._offset:
             raise RnntError(f"slot {slot} is not open")
+        if self._fed.setdefault(slot, "feed") != "feed":
+            raise RnntError(f"slot {slot} is fed audio (feed_wave): feature chunks cannot be mixed in")
+        return self._feed_chunk(slot, chunk)
+
+    def _feed_chunk(self, slot: int, chunk: torch.Tensor) -> bool:
         assert chunk.dim() == 2 and chunk.size(1) == 80 and chunk.dtype == torch.float32
         if chunk.size(0) < 7:
             print(f"Warning: Chunk too small ({chunk.size(0)} frames), skipping")
             return False
         self._queue.append((slot, chunk))
         return True
+
+    def feed_wave(self, slot: int, samples: torch.Tensor, final: bool = False):
+        """Queue one PCM packet (1-D float32, on the host or the device; it may be empty) for an open slot; final: the utterance ends
+        with it.  The next step() turns the queued packets of all slots into frames with one rnnt_pool_wave call and feeds every
+        full chunk_frames of them, at final also the remainder.  Raises RnntError on a slot fed through feed(), or after its final
+        packet."""
+        if slot not in self._offset:
+            raise RnntError(f"slot {slot} is not open")
+        if self._fed.setdefault(slot, "wave") != "wave":
+            raise RnntError(f"slot {slot} is fed feature chunks (feed): audio cannot be mixed in")
+        if self._wave_final.get(slot, False):
+            raise RnntError(f"slot {slot}: its utterance has ended (final packet already queued)")
+        assert samples.dim() == 1 and samples.dtype == torch.float32
+        self._wave_final[slot] = bool(final)
+        self._wave_queue.append((slot, samples, bool(final)))
+
+    def _wave_step(self):
+        """The queued packets of all slots through ONE rnnt_pool_wave call (wave_plan); full chunks leave the FIFOs for the chunk queue."""
+        queue, self._wave_queue = self._wave_queue, []
+        fifo_len = {slot: f.size(0) for slot, f in self._wave_fifo.items()}
+        call, chunks, self._wave_samples, fifo_left = wave_plan([(slot, p.numel(), fin) for slot, p, fin in queue], self._wave_samples, fifo_len,
+                                                                self.chunk_frames, self.n_fft)
+        slots, counts, finals, frames = call
+        dev = self._wave_device if self._wave_device is not None else queue[0][1].device
+        parts: Dict[int, List[torch.Tensor]] = {slot: [] for slot in slots}
+        for slot, p, _ in queue:
+            parts[slot].append(p)
+        rows = [parts[s][0] if len(parts[s]) == 1 else torch.cat(parts[s]) for s in slots]      # a slot's packets side by side in its row
+        if any(r.device != rows[0].device for r in rows):
+            rows = [r.to(dev) for r in rows]
+        if max(counts) == 0:
+            wave = torch.zeros(len(slots), 1, dtype=torch.float32, device=dev)
+        elif min(counts) == max(counts):
+            wave = torch.stack(rows, 0).to(dev)
+        else:
+            wave = torch.nn.utils.rnn.pad_sequence(rows, batch_first=True).to(dev)                # rows padded to the longest
+        n_max, cap = wave.size(1), max(max(frames), 1)
+        out = torch.empty(len(slots), cap, 80, dtype=torch.float32, device=dev)
+        got = self.engine.pool_wave(slots, wave.data_ptr(), n_max, counts, finals, out.data_ptr(), cap, self.sample_rate, self.n_fft, self._stream(wave))
+        assert [int(g) for g in got] == frames, f"rnnt_pool_wave wrote {list(got)} frames, the plan says {frames}"
+        for i, slot in enumerate(slots):
+            if frames[i]:
+                old = self._wave_fifo.get(slot)
+                self._wave_fifo[slot] = out[i, :frames[i]] if old is None or old.size(0) == 0 else torch.cat([old, out[i, :frames[i]]], 0)
+        taken: Dict[int, int] = {}
+        for slot, start, length in chunks:
+            self._feed_chunk(slot, self._wave_fifo[slot][start:start + length].contiguous())
+            taken[slot] = start + length
+        for slot, k in taken.items():
+            self._wave_fifo[slot] = self._wave_fifo[slot][k:]
 
     def step(self) -> Dict[int, List[int]]:
         """Advance every slot that has chunks queued: one rnnt_pool_chunk call per chunk length of the greedy slots and one
@@ -1000,6 +1123,8 @@ class StreamPool:
         use_context).  Returns {slot: tokens emitted by this step} for the GREEDY slots that advanced; a beam slot's hypotheses are
         read with beams(slot), a CTC prefix slot's with ctc_hyps(slot)."""
         out, self._carry = self._carry, {}
+        if self._wave_queue:
+            self._wave_step()
         if not self._queue:
             return out
         calls, offs, index = pool_plan([(slot, c.size(0)) for slot, c in self._queue], self._offset, self._beam,
@@ -1046,9 +1171,12 @@ class StreamPool:
         its final hypotheses (beam slot) or ctc_hyps(slot, final=True) (CTC prefix slot)."""
         if slot not in self._offset:
             raise RnntError(f"slot {slot} is not open")
-        if any(s == slot for s, _ in self._queue):
+        if self._fed.get(slot) == "wave" and not self._wave_final[slot]:
+            self.feed_wave(slot, torch.zeros(0, dtype=torch.float32), final=True)   # the caller hung up: flush the tail
+        if any(s == slot for s, _ in self._queue) or any(s == slot for s, _, _ in self._wave_queue):
             self._carry = self.step()                   # the other slots' increments are handed out by the next step()
         self._carry.pop(slot, None)
+        self._forget_wave(slot)
         if slot in self._ctc:
             res = self.ctc_hyps(slot, final=True)
             del self._ctc[slot]

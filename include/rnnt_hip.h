@@ -541,6 +541,47 @@ int rnnt_greedy_search_full(rnnt_ctx* ctx, const float* fbank_dev, const int32_t
 int rnnt_fbank(rnnt_ctx* ctx, const float* wave_dev, int32_t B, int32_t n_samples, int32_t sample_rate, int32_t n_fft,
                float* out_dev, int32_t* frames_out, void* stream);
 
+/* -- audio in for the stream pool: rnnt_fbank per slot, fed in packets -------------------------------------------------------------- */
+/* AmplitudeToDB() has no top_db, so frame f depends on x[f*512 - n_fft/2, f*512 + n_fft/2) of the reflect-padded signal alone and the
+ * features are computable frame by frame.  Per slot, the frames emitted since its reset are the rows of rnnt_fbank over the slot's
+ * whole waveform, concatenated in order, nothing twice: hop 512, 80 mels, periodic Hamming window, power 2, centred, reflect
+ * padding, dB with the 1e-10 clamp.  With N samples received and the utterance not final, the frames with f*512 + n_fft/2 <= N are
+ * out, and none before N >= n_fft/2 + 1 (frame 0's left reflection reads sample n_fft/2).  At final the remaining frames up to
+ * 1 + N/512 follow with the right reflection j -> 2(N-1) - j.  A final slot with N <= n_fft/2 emits nothing and is no error.
+ *   wave_dev [n_active, n_samples] f32 device: row i holds samples_host[i] in [0, n_samples] new samples of slot slots_host[i];
+ *   final_host[i] != 0: that slot's utterance ends with them (0 new samples: flush the tail);  a row with 0 samples and final == 0
+ *   is a no-op;  out_dev [n_active, cap_frames, 80] f32 device, frames_host[i] rows of row i are written (the rest unspecified).
+ * State per slot, allocated on the first call through the context's owning buffers: on the device the carry -- the samples a pending
+ * frame or the final reflection can still read, x[max(0, f*512 - n_fft/2 - 1), N) for the next frame f, at most n_fft floats (the
+ * final frame centred on N = k*512 reflects one sample before its own span) -- and on the host samples, frames, finished and the
+ * (sample_rate, n_fft) the slot's first push fixed until its next reset.  rnnt_stream_open resets its slot, rnnt_streams_reset and
+ * rnnt_stream_wave_reset(-1) all.  Any context works (weights are not needed).
+ * Launches, whatever n_active: wave_stage (carry | new samples | reflections into 16-byte aligned zero-filled rows, a row's first new
+ * frame at a fixed position), rnnt_fbank's DFT GEMM / power_spectrum / mel GEMM over n_active x max-frames implicit frames with the
+ * same cached matrices and kernel choices as for one stream's rows (gemm16: a frame's bits depend on neither neighbours nor packet
+ * split, and equal rnnt_fbank's whenever that call has under 1024 frames), wave_carry_roll (new carry read from the staged rows).
+ * Frame counts are host arithmetic: no synchronisation.  Every refusal is decided before the first launch and changes nothing:
+ * RNNT_ERR_ARG null pointer, duplicated or out-of-range slot, samples_host[i] outside [0, n_samples], (sample_rate, n_fft) differing
+ * from the slot's utterance in progress, cap_frames below a row's frame count; RNNT_ERR_SHAPE n_fft or sample_rate outside rnnt_fbank's
+ * range; RNNT_ERR_STATE a push to a slot already final and not reset. */
+int rnnt_pool_wave(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, const float* wave_dev, int32_t n_samples,
+                   const int32_t* samples_host, const int32_t* final_host, int32_t sample_rate, int32_t n_fft, float* out_dev,
+                   int32_t cap_frames, int32_t* frames_host, void* stream);
+/* a fresh utterance (no samples, no frames, no fixed sample_rate / n_fft) for one slot, or all with slot = -1.  Host only. */
+int rnnt_stream_wave_reset(rnnt_ctx* ctx, int32_t slot, void* stream);
+/* one slot's front-end state; every output is optional.  carry_host == NULL: host only.  Otherwise the *n_carry_out carried samples
+ * are copied into carry_host [cap_carry] and the stream is synchronised.  A fresh or finished slot carries nothing. */
+int rnnt_stream_get_wave_state(rnnt_ctx* ctx, int32_t slot, int32_t* samples_out, int32_t* frames_out, int32_t* sample_rate_out,
+                               int32_t* n_fft_out, int32_t* finished_out, int32_t* n_carry_out, float* carry_host, int32_t cap_carry,
+                               void* stream);
+/* One slot's push as a pure C++ function (no context, no GPU) through the index helper the two kernels use: carry_in [n_carry_in] and
+ * samples_so_far before, new_samples [n_new], final -> staged_out: the staged row from the push's first new frame on (frame r of the
+ * push starts at r * 512; *staged_len_out samples), *first_frame_out, *n_frames_out, and the carry after it.  n_carry_in must be the
+ * carry length the arithmetic gives for samples_so_far (RNNT_ERR_ARG). */
+int rnnt_wave_stage_host(const float* carry_in, int32_t n_carry_in, int32_t samples_so_far, const float* new_samples, int32_t n_new,
+                         int32_t final, int32_t n_fft, float* staged_out, int32_t cap_staged, int32_t* staged_len_out,
+                         int32_t* first_frame_out, int32_t* n_frames_out, float* carry_out, int32_t cap_carry, int32_t* n_carry_out);
+
 /* -- state read-back in the reference's layouts (parity tests, facade attributes) -------------- */
 /* streaming_att_cache of one stream: [12, 4, len, 128] (K = [...,:64], V = [...,64:],
  * wenet/transformer/encoder.py:284); *len_out = cached frames.  dst_host may be NULL to query len. */
@@ -562,7 +603,7 @@ const float* rnnt_enc_frames_dev(rnnt_ctx* ctx, int32_t* frames_out, int32_t* st
  * rnnt_transducer_nll, 41 its alpha recursion (and rnnt_ctc_nll's), 42 the Viterbi launch of the rnnt_*_align calls, 43 prefix_step
  * and 44 prefix_merge of rnnt_prefix_beam_decode (one launch each per frame), 45 ctc_prefix_search of the rnnt_ctc_prefix_beam_*
  * calls (one launch per call), 46 ctc_prefix_search_pool of rnnt_pool_ctc_prefix_logprobs / rnnt_pool_chunk_ctc_prefix (the resumable
- * search launch), 47 ctc_prefix_pack of rnnt_stream_get_ctc_prefix (the pack launch).
+ * search launch), 47 ctc_prefix_pack of rnnt_stream_get_ctc_prefix (the pack launch), 48 wave_stage of rnnt_pool_wave (the staging launch).
  * rnnt_profile_end synchronises the recorded events and returns the summed kernel time and launch count. */
 int rnnt_profile_begin(rnnt_ctx* ctx, int32_t tag);
 int rnnt_profile_end(rnnt_ctx* ctx, double* total_ms, int64_t* n_launches);
