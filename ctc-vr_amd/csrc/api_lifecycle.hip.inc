@@ -504,5 +504,6 @@ int rnnt_streams_reset(rnnt_ctx* ctx, int32_t n_streams, void* stream) {
     int rc;
     pool_wave_reset(ctx, 0, B);                             // the per-slot streaming front-ends of the stream pool
     if ((rc = pool_beam_reset(ctx, s, 0, B))) return rc;   // the per-slot beam state of the stream pool, once it exists
+    if ((rc = pool_hist_reset(ctx, s, 0, B))) return rc;   // no slot keeps its encoder frames
     return pool_ctc_reset(ctx, s, 0, B);                    // and its per-slot CTC prefix searches
 }

@@ -121,6 +121,7 @@ int rnnt_stream_open(rnnt_ctx* ctx, int32_t slot, void* stream) {
     if ((rc = pool_beam_reset(ctx, s, slot, 1))) return rc;   // the slot's beam: one empty hypothesis (once the beam state exists)
     if ((rc = pool_ctc_reset(ctx, s, slot, 1))) return rc;    // the slot's CTC prefix search: the start hypothesis (likewise)
     pool_wave_reset(ctx, slot, 1);                            // the slot's streaming front-end: no samples, no frames
+    if ((rc = pool_hist_reset(ctx, s, slot, 1))) return rc;   // the slot keeps no encoder frames unless asked again
     pool_enter(ctx);
     ctx->slot_pos[slot] = SlotPos{0, 0, 0};
     return RNNT_OK;
@@ -169,6 +170,7 @@ int pool_chunk_run(rnnt_ctx* ctx, const char* fn, int32_t n_active, const int32_
         PoolRow& r = rows[i];
         r.slot = slot; r.T2 = k.T2; r.kv_row0 = k.kv_row0; r.pos_start = k.pos_start; r.ring_pos = k.ring_pos;
         r.kv_w0 = k.kv_w0(); r.ring_w0 = k.ring_pos % ctx->cap; r.zero = 0;
+        if (int hrc = pool_hist_check(ctx, fn, slot, tq)) return hrc;
     }
     hipStream_t s = (hipStream_t)stream;
     int rc;
@@ -219,6 +221,7 @@ int pool_chunk_run(rnnt_ctx* ctx, const char* fn, int32_t n_active, const int32_
             if ((rc = run_layer_pool(ctx, s, l, n, tq, rows_dev, rows.data()))) return rc;
         // after_norm in place over the compact rows, then the joint's encoder projection into frames [0, t') of every active slot
         if ((rc = launch_ln(ctx, s, LnP{ctx->x, ctx->after_g, ctx->after_b, ctx->x, n * tq, BIG, 0, 0LL, (long long)D}))) return rc;
+        if ((rc = pool_hist_append_rows(ctx, s, n, slots_host, slots_dev, tq))) return rc;   // slots that keep their frames (rnnt_stream_keep_frames)
         GemmP g = plain_gemm(ctx->x, D, ctx->wenc, D, ctx->benc, ctx->encp, D, n * tq, D, D);
         g.c_n = tq; g.c_s0 = (long long)ctx->fstride * D; g.c_r0 = 0; g.c_mod = BIG; g.c_s1 = D;
         g.c_tab = ctx->pool_tab; g.c_tab_col = POOL_COL_ZERO;

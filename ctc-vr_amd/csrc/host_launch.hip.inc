@@ -643,4 +643,36 @@ void pool_wave_reset(rnnt_ctx* ctx, int slot0, int n) {
     for (int b = slot0; b < slot0 + n && b < (int)ctx->wv_slot.size(); ++b) ctx->wv_slot[b] = rnnt_ctx::WvSlot{0, 0, 0, 0, 0};
 }
 
+// ---- per-slot encoder-frame history of the stream pool (api_pool_hist.hip.inc; kernels in rnnt_encoder.hip.h) ----------------------------
+// flag and length of slots [slot0, slot0 + n) cleared, on the host and (once the tables exist) on the device; buffers stay
+int pool_hist_reset(rnnt_ctx* ctx, hipStream_t s, int slot0, int n) {
+    for (int b = slot0; b < slot0 + n && b < (int)ctx->hs_slot.size(); ++b) ctx->hs_slot[b] = rnnt_ctx::HsSlot{0, 0};
+    if (!ctx->hs_len) return RNNT_OK;
+    hipLaunchKernelGGL(pool_hist_set, dim3((n + 63) / 64), dim3(64), 0, s, ctx->hs_ptr.p, ctx->hs_len.p, slot0, n, (float*)nullptr);
+    LAUNCHCHK("pool_hist_set");
+    return RNNT_OK;
+}
+
+// with the other slot checks of a pool call: a kept slot whose history cannot take tq more rows refuses the call
+int pool_hist_check(rnnt_ctx* ctx, const char* fn, int slot, int tq) {
+    if (slot >= (int)ctx->hs_slot.size() || !ctx->hs_slot[slot].keep) return RNNT_OK;
+    if (ctx->hs_slot[slot].len + tq > ctx->cfg.max_cache_frames)
+        return fail(ctx, RNNT_ERR_SHAPE, "%s: slot %d: kept frames %d + %d exceed max_cache_frames %d", fn, slot, ctx->hs_slot[slot].len, tq, ctx->cfg.max_cache_frames);
+    return RNNT_OK;
+}
+
+// after the call's after_norm: one launch, and only when a listed slot keeps frames
+int pool_hist_append_rows(rnnt_ctx* ctx, hipStream_t s, int n, const int32_t* slots_host, const int* slots_dev, int tq) {
+    bool any = false;
+    for (int i = 0; i < n; ++i) {
+        if (slots_host[i] >= (int)ctx->hs_slot.size() || !ctx->hs_slot[slots_host[i]].keep) continue;
+        ctx->hs_slot[slots_host[i]].len += tq;
+        any = true;
+    }
+    if (!any) return RNNT_OK;
+    hipLaunchKernelGGL(pool_hist_append, dim3(n), dim3(256), 0, s, ctx->x.p, slots_dev, ctx->hs_ptr.p, ctx->hs_len.p, tq);
+    LAUNCHCHK("pool_hist_append");
+    return RNNT_OK;
+}
+
 }  // namespace

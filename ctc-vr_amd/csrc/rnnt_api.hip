@@ -288,6 +288,15 @@ struct rnnt_ctx {
     DevBuf<int> wv_tab;
     PinnedBuf<int> wv_tab_host;
     hipEvent_t wv_ev = nullptr;
+    // encoder-frame history per slot of the stream pool (api_pool_hist.hip.inc), allocated on a slot's first rnnt_stream_keep_frames:
+    // hs_buf[slot] [max_cache_frames][256], the device tables hs_ptr / hs_len [max_streams] the append and gather kernels index by
+    // slot, the dense staging of rnnt_pool_rescore (grow-only).  Host per slot: the flag and the mirrored length.
+    struct HsSlot { int keep, len; };
+    std::vector<HsSlot> hs_slot;
+    std::vector<DevBuf<float>> hs_buf;
+    DevBuf<float*> hs_ptr;
+    DevBuf<int> hs_len;
+    DevBuf<float> hs_stage;
     hipStream_t cap_stream = nullptr;          // stream-capture scratch stream
     struct DecGraph { int n_streams, k; hipGraphExec_t exec; };
     std::vector<DecGraph> dec_graphs;          // K greedy steps captured once per (n_streams, K)
@@ -323,6 +332,7 @@ extern "C" {
 #include "api_state.hip.inc"
 #include "api_pool_ctc.hip.inc"
 #include "api_pool.hip.inc"
+#include "api_pool_hist.hip.inc"
 #include "api_pool_wave.hip.inc"
 #include "api_prefix.hip.inc"
 #include "api_ctc_prefix.hip.inc"

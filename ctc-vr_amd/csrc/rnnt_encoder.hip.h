@@ -537,3 +537,42 @@ __global__ void pool_scatter_frames(const float* __restrict__ src, float* __rest
         stg4(dst + (long long)ldgi(&rows[i].slot) * fstride_f + (long long)f * RNNT_D + c4 * 4, ldg4(src + (long long)m * RNNT_D + c4 * 4));
     }
 }
+
+// ---- per-slot encoder-frame history of the stream pool (rnnt_stream_keep_frames; api_pool_hist.hip.inc) ---------------------------------
+// hist_ptr [max_streams]: a slot's history [max_cache_frames][256], null while it keeps none; hist_len [max_streams]: its rows so
+// far.  Both are written by pool_hist_set (keep / open / reset) and hist_len by pool_hist_append; the host mirrors the lengths and
+// has checked len + tq <= max_cache_frames for every kept slot of the call.
+__global__ void pool_hist_set(float** hist_ptr, int* hist_len, int slot0, int n, float* ptr) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) { hist_ptr[slot0 + i] = ptr; hist_len[slot0 + i] = 0; }
+}
+
+// Every pool call that lists a kept slot: the tq compact after_norm rows of active row i (src [n_active * tq][256]) behind the history
+// of slot slots[i].  One workgroup per active row -- slots of a call are distinct, so a length has one reader and one writer --
+// float4 copies, then the length moves on.
+__global__ __launch_bounds__(256) void pool_hist_append(const float* __restrict__ src, const int* __restrict__ slots, float* const* hist_ptr,
+                                                        int* hist_len, int tq) {
+    const int i = blockIdx.x, slot = ldgi(slots + i);
+    float* const dst = hist_ptr[slot];
+    if (!dst) return;
+    const int len = hist_len[slot];
+    const float* s = src + (long long)i * tq * RNNT_D;
+    float* d = dst + (long long)len * RNNT_D;
+    for (int id = threadIdx.x; id < tq * (RNNT_D / 4); id += 256) stg4(d + id * 4, ldg4(s + id * 4));
+    __syncthreads();                                           // every lane has read the old length
+    if (threadIdx.x == 0) hist_len[slot] = len + tq;
+}
+
+// rnnt_pool_rescore: the histories of the listed slots side by side, dst [n][Tmax][256]; rows beyond a slot's length are left as
+// they are (never read).  Tmax = the longest listed history (host mirror).
+__global__ void pool_hist_gather(float* __restrict__ dst, const int* __restrict__ slots, float* const* hist_ptr, const int* hist_len, int n,
+                                 int Tmax) {
+    const long long total = (long long)n * Tmax * (RNNT_D / 4);
+    for (long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x; id < total; id += (long long)gridDim.x * blockDim.x) {
+        const int c4 = (int)(id & 63);
+        const long long m = id >> 6;
+        const int i = (int)(m / Tmax), f = (int)(m - (long long)i * Tmax);
+        const int slot = ldgi(slots + i);
+        if (f < hist_len[slot]) stg4(dst + m * RNNT_D + c4 * 4, ldg4(hist_ptr[slot] + (long long)f * RNNT_D + c4 * 4));
+    }
+}

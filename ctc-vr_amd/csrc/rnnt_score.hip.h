@@ -59,6 +59,41 @@ __global__ __launch_bounds__(256) void transducer_alpha(const float* __restrict_
     if (u == Ub) nll[b] = -(a + (double)ldg1(pb + ((long long)(Tb - 1) * U1 + Ub) * 2));
 }
 
+// transducer_alpha over the n-best layout of rnnt_transducer_nll_nbest: the N hypotheses of an utterance lie side by side along U,
+// pick [B][T][N * U1][2], so cell (t, u) of hypothesis n is at ((b T + t) N U1 + n U1 + u) * 2.  One workgroup per (b, n) =
+// blockIdx.x; tlens [B]: T_b in [1, T]; ulens [B][N]: U_bn in [0, U1 - 1]; nhyp [B].  Workgroups with n >= nhyp[b] store 0 and
+// leave (their lengths are not read).  Same recursion, same order of operations; launched with 256 threads, U1 <= 256.
+__global__ __launch_bounds__(256) void transducer_alpha_nbest(const float* __restrict__ pick, const int* __restrict__ tlens,
+                                                              const int* __restrict__ ulens, const int* __restrict__ nhyp, int T, int N,
+                                                              int U1, double* __restrict__ nll) {
+    __shared__ double xa[2][SCORE_UMAX + 1];
+    const int bn = blockIdx.x, b = bn / N, n = bn - b * N, u = threadIdx.x;
+    if (n >= ldgi(nhyp + b)) {                                 // uniform over the workgroup
+        if (u == 0) nll[bn] = 0.0;
+        return;
+    }
+    const int Tb = ldgi(tlens + b), Ub = ldgi(ulens + bn);
+    const long long US = (long long)N * U1;                    // cells per frame
+    const float* pb = pick + ((long long)b * T * US + (long long)n * U1) * 2;
+    double a = -INFINITY;
+    const int nd = Tb + Ub;
+    for (int d = 0; d < nd; ++d) {
+        const int t = d - u;
+        const bool live = u <= Ub && t >= 0 && t < Tb;
+        if (live) {
+            if (d == 0) a = 0.0;
+            else {
+                const double below = t > 0 ? a + (double)ldg1(pb + ((long long)(t - 1) * US + u) * 2) : -INFINITY;
+                const double left = u > 0 ? xa[(d - 1) & 1][u - 1] + (double)ldg1(pb + ((long long)t * US + u - 1) * 2 + 1) : -INFINITY;
+                a = t == 0 ? left : (u == 0 ? below : score_logaddexp(below, left));
+            }
+        }
+        xa[d & 1][u] = a;
+        __syncthreads();
+    }
+    if (u == Ub) nll[bn] = -(a + (double)ldg1(pb + ((long long)(Tb - 1) * US + Ub) * 2));
+}
+
 // Standard CTC forward over the S = 2 L_b + 1 extended states (blank, y_1, blank, ..., y_L, blank) and T_b frames, the
 // recursion of nn.CTCLoss: alpha_t[s] = logsumexp(alpha_{t-1}[s], alpha_{t-1}[s-1], alpha_{t-1}[s-2] if y differs) + lp[t][ext s].
 // nll = -logaddexp(alpha[S-1], alpha[S-2]); an infeasible pair (fewer frames than labels plus adjacent repeats) keeps both at

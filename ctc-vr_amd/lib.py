@@ -71,6 +71,11 @@ SIGNATURES = {
     "rnnt_stream_get_ctc_prefix": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32p, c_vp]),
     "rnnt_transducer_nll": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "rnnt_ctc_nll": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "rnnt_transducer_nll_nbest": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "rnnt_rescore_select_host": (c_i32, [c_i32, c_vp, c_vp, ctypes.c_double, ctypes.c_double, c_vp, c_i32p]),
+    "rnnt_stream_keep_frames": (c_i32, [c_vp, c_i32, c_i32, c_vp]),
+    "rnnt_stream_get_frames": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32p, c_vp]),
+    "rnnt_pool_rescore": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
     "rnnt_transducer_align": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rnnt_transducer_align_pick": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "rnnt_ctc_align": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
@@ -185,6 +190,35 @@ def prefix_merge_host(hyps, top_lp, top_tok, blank, beam_size):
     if m < 0:
         raise RnntError(f"rnnt_prefix_merge_host: bad argument (status {m})", m)
     return out
+
+
+def rescore_select(first_scores, nll, first_weight, transducer_weight):
+    """rnnt_rescore_select_host (no context, no GPU): the choice of transducer_attention_rescoring among one utterance's
+    hypotheses -> (best index, totals float64 [n]); total = first * first_weight + (-nll) * transducer_weight, the first of equal
+    totals wins, a NaN total is never chosen."""
+    fs, nl = np.ascontiguousarray(first_scores, np.float64), np.ascontiguousarray(nll, np.float64)
+    assert fs.ndim == 1 and fs.shape == nl.shape
+    total, best = np.zeros(max(fs.size, 1), np.float64), c_i32(0)
+    rc = load().rnnt_rescore_select_host(fs.size, _np_ptr(fs), _np_ptr(nl), float(first_weight), float(transducer_weight), _np_ptr(total),
+                                         ctypes.byref(best))
+    if rc != 0:
+        raise RnntError(f"rnnt_rescore_select_host: bad argument (status {rc})", rc)
+    return best.value, total[:fs.size]
+
+
+def pack_nbest(hyps, N=None, umax=None):
+    """[[tokens, ...] per utterance] -> (n_hyp int32 [B], lens int32 [B, N], tokens int32 [B, N, umax]) of the n-best scoring calls;
+    N / umax default to the largest count / length present (N at least 1).  Unused entries are 0 (never read)."""
+    B = len(hyps)
+    N = max([len(h) for h in hyps] + [1]) if N is None else N
+    umax = max([len(t) for h in hyps for t in h] + [0]) if umax is None else umax
+    nh = np.array([len(h) for h in hyps], np.int32)
+    lens, toks = np.zeros((B, N), np.int32), np.zeros((B, N, umax), np.int32)
+    for b, h in enumerate(hyps):
+        for n, t in enumerate(h):
+            lens[b, n] = len(t)
+            toks[b, n, :len(t)] = t
+    return nh, lens, toks
 
 
 def _phrase_args(phrases):
@@ -695,6 +729,62 @@ class RnntEngine:
         nll = np.zeros(B, np.float64)
         self._chk(self.lib.rnnt_transducer_nll(self.ctx, enc_ptr, _np_ptr(el), _np_ptr(tg), _np_ptr(tl), B, T, umax, _np_ptr(nll), pick_ptr, stream),
                   "rnnt_transducer_nll")
+        return nll
+
+    # ---- two-pass decoding -----------------------------------------------------------------------
+    @staticmethod
+    def _nbest_args(n_hyp, hyp_lens, hyp_tokens, B):
+        nh, hl = np.ascontiguousarray(n_hyp, np.int32), np.ascontiguousarray(hyp_lens, np.int32)
+        assert nh.size == B and hl.ndim == 2 and hl.shape[0] == B
+        N = hl.shape[1]
+        ht = np.ascontiguousarray(hyp_tokens, np.int32)
+        ht = ht.reshape(B, N, ht.size // (B * N))
+        return nh, hl, ht, N, ht.shape[2]
+
+    def transducer_nll_nbest(self, enc_ptr, enc_lens, n_hyp, hyp_lens, hyp_tokens, B, T, pick_ptr=None, stream=None):
+        """rnnt_transducer_nll_nbest: transducer negative log-likelihood (float64 [B, N]) of N hypotheses per utterance -- n_hyp [B],
+        hyp_lens [B, N], hyp_tokens [B, N, Umax] (pack_nbest) -- over encoder frames enc [B, T, 256] on the device, projected once;
+        0 where n >= n_hyp[b].  pick_ptr: optional device float [B, T, N * (Umax + 1), 2] receiving the picked lattice."""
+        el = np.ascontiguousarray(enc_lens, np.int32)
+        nh, hl, ht, N, umax = self._nbest_args(n_hyp, hyp_lens, hyp_tokens, B)
+        assert el.size == B
+        nll = np.zeros((B, N), np.float64)
+        self._chk(self.lib.rnnt_transducer_nll_nbest(self.ctx, enc_ptr, _np_ptr(el), _np_ptr(nh), _np_ptr(hl), _np_ptr(ht), B, T, N, umax, _np_ptr(nll),
+                                                     pick_ptr, stream), "rnnt_transducer_nll_nbest")
+        return nll
+
+    rescore_select = staticmethod(rescore_select)
+
+    def stream_keep_frames(self, slot, keep=True, stream=None):
+        """rnnt_stream_keep_frames: from now on the pool calls that encode `slot` append its encoder outputs to the slot's history
+        (valid on a slot that has not advanced since it was opened); keep=False clears the flag and the length."""
+        self._chk(self.lib.rnnt_stream_keep_frames(self.ctx, slot, 1 if keep else 0, stream), "rnnt_stream_keep_frames")
+
+    def stream_frames_len(self, slot):
+        """frames in the slot's history (host only); RnntError(ERR_STATE) on a slot that keeps none"""
+        n = c_i32(0)
+        self._chk(self.lib.rnnt_stream_get_frames(self.ctx, slot, 0, 0, None, ctypes.byref(n), None), "rnnt_stream_get_frames")
+        return n.value
+
+    def stream_frames(self, slot, start=0, stream=None):
+        """rnnt_stream_get_frames: frames [start, len) of the slot's history as a device tensor [len - start, 256] (a copy, made on
+        `stream`: torch's current stream when None)."""
+        import torch
+        n = max(self.stream_frames_len(slot) - start, 0)
+        out = torch.empty(n, 256, device=torch.device("cuda", self.cfg.device), dtype=torch.float32)
+        if n:
+            s = torch.cuda.current_stream(out.device).cuda_stream if stream is None else stream
+            self._chk(self.lib.rnnt_stream_get_frames(self.ctx, slot, start, n, out.data_ptr(), None, s), "rnnt_stream_get_frames")
+        return out
+
+    def pool_rescore(self, slots, n_hyp, hyp_lens, hyp_tokens, stream=None):
+        """rnnt_pool_rescore: transducer_nll_nbest over the kept frames of the listed slots, one call -> float64 [len(slots), N]."""
+        a = np.ascontiguousarray(slots, np.int32)
+        assert a.ndim == 1
+        nh, hl, ht, N, umax = self._nbest_args(n_hyp, hyp_lens, hyp_tokens, a.size)
+        nll = np.zeros((a.size, N), np.float64)
+        self._chk(self.lib.rnnt_pool_rescore(self.ctx, a.size, _np_ptr(a), _np_ptr(nh), _np_ptr(hl), _np_ptr(ht), N, umax, _np_ptr(nll), stream),
+                  "rnnt_pool_rescore")
         return nll
 
     def ctc_nll(self, enc_ptr, enc_lens, targets, target_lens, B, T, stream=None):

@@ -13,7 +13,7 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 import torch
 
-from .lib import ERR_ARG, ERR_STATE, RnntEngine, RnntError
+from .lib import ERR_ARG, ERR_SHAPE, ERR_STATE, RnntEngine, RnntError, pack_nbest, rescore_select
 
 
 def _stream_ptr():
@@ -125,6 +125,29 @@ def timestamps_from_peaks(peaks, max_duration, frame_rate=0.04, max_token_durati
         end = min(max_duration, pk * frame_rate + half) if i == last else min((pk + peaks[i + 1]) / 2 * frame_rate, pk * frame_rate + half)
         times.append((start, end))
     return times
+
+
+def check_rescoring_args(attn_weight=0.0, reverse_weight=0.0, decoding_chunk_size=-1, beam_search_type="transducer"):
+    """What transducer_attention_rescoring cannot do here, said before anything runs (ValueError)."""
+    if attn_weight != 0:
+        raise ValueError(f"attn_weight={attn_weight}: this model has no attention decoder, so there is no attention score to weigh (pass 0)")
+    if reverse_weight != 0:
+        raise ValueError(f"reverse_weight={reverse_weight}: this model has no (right-to-left) attention decoder (pass 0)")
+    if decoding_chunk_size != -1:
+        raise ValueError(f"decoding_chunk_size={decoding_chunk_size}: rescoring runs on the full-context encoder, like the other offline "
+                         "searches (pass -1); chunked two-pass decoding is StreamPool.rescore")
+    if beam_search_type not in ("transducer", "ctc"):
+        raise ValueError(f"beam_search_type={beam_search_type!r}: 'transducer' or 'ctc'")
+
+
+def select_rescored(hyps, first_scores, nll, first_weight, transducer_weight):
+    """One utterance's (best_index, [(tokens, first_score, td_score, total)]) in the first pass's order: td_score = -nll and the
+    choice of rnnt_rescore_select_host (wenet/transducer/transducer.py:372-393 with attn_weight = 0).  nll None: no valid frame to
+    score against -- td_score = nan, best_index = 0."""
+    if nll is None:
+        return 0, [(list(t), float(f), float("nan"), float("nan")) for t, f in zip(hyps, first_scores)]
+    best, total = rescore_select(first_scores, nll, first_weight, transducer_weight)
+    return best, [(list(t), float(f), -float(x), float(tt)) for t, f, x, tt in zip(hyps, first_scores, nll, total)]
 
 
 class ContextBias:
@@ -568,6 +591,11 @@ class OnlineRNNTModel:
         self._prefix_states_batch = [(torch.from_numpy(h[b, :len(hyps[b])].copy()), torch.from_numpy(c[b, :len(hyps[b])].copy())) for b in range(B)]
         return hyps
 
+    def _set_context(self, context: Optional["ContextBias"]):
+        if context is not self._context_bias:                       # the graph lives in the context until another one replaces it
+            self._engine.context_set(context.phrases if context is not None else [], context.context_score if context is not None else 0.0)
+            self._context_bias = context
+
     def ctc_prefix_beam_search(self, audios: torch.Tensor, audio_lens: torch.Tensor, beam_size: int = 10, context: Optional["ContextBias"] = None):
         """WeNet's ctc_prefix_beam_search (wenet/transformer/search.py:125-247) on the CTC head over the deterministic full-context
         encoder, for a padded batch audios [B, T, 80]: one rnnt_encoder_full call and one rnnt_ctc_prefix_beam_decode call (the CTC
@@ -588,11 +616,61 @@ class OnlineRNNTModel:
         self._chunks_done = None
         n1 = np.maximum(0, (np.minimum(lens, T) - 1) // 2)         # valid frames after masks[:, :, 2::2][:, :, 2::2]
         enc_lens = np.maximum(0, (n1 - 1) // 2).astype(np.int32)
-        if context is not self._context_bias:                       # the graph lives in the context until another one replaces it
-            self._engine.context_set(context.phrases if context is not None else [], context.context_score if context is not None else 0.0)
-            self._context_bias = context
+        self._set_context(context)
         hyps = self._engine.ctc_prefix_beam_decode(enc.data_ptr(), enc_lens, B, tq, beam_size, context is not None, False, s)
         return [[(tok, score, times) for tok, score, times, _ in row] for row in hyps]
+
+    # ---- two-pass decoding (wenet/transducer/transducer.py:261-395) -------------------------------------------------
+    def rescoring_batch(self, audios: torch.Tensor, audio_lens: torch.Tensor, beam_size: int = 10, ctc_weight: float = 0.3,
+                        transducer_weight: float = 0.7, beam_search_type: str = "ctc", context: Optional["ContextBias"] = None,
+                        search_ctc_weight: float = 1.0, search_transducer_weight: float = 0.0):
+        """Transducer rescoring of n-best for a padded batch audios [B, T, 80]: one full-context encoder call, one search call
+        (beam_search_type "ctc": rnnt_ctc_prefix_beam_decode, biased by `context` when given; "transducer":
+        rnnt_prefix_beam_decode with the two search weights over each utterance's valid frames, the leading blank dropped, :327),
+        one rnnt_transducer_nll_nbest call over the same frames and, per utterance, the choice of rnnt_rescore_select_host:
+        total = first_score * ctc_weight + td_score * transducer_weight (:388-390 with attn_weight = 0; the defaults are the
+        fusion weights of the reference's beam_search, :223-224).  beam_size <= 16.
+        Returns per utterance (best_index, [(tokens, first_score, td_score, total)]) in the first pass's order; an utterance with
+        no valid encoder frame comes back with td_score = nan and best_index = 0.  Invalidates the streaming state."""
+        check_rescoring_args(beam_search_type=beam_search_type)
+        if context is not None and beam_search_type != "ctc":
+            raise ValueError("context biases the CTC prefix search only (beam_search_type='ctc')")
+        enc, enc_lens, _, _ = self._encode_for_scoring(audios, audio_lens, torch.zeros(audios.size(0), 0), torch.zeros(audios.size(0)))
+        B, tq, s = enc.size(0), enc.size(1), _stream_ptr()
+        if beam_search_type == "ctc":
+            self._set_context(context)
+            first = [[(tok, score) for tok, score, _, _ in row]
+                     for row in self._engine.ctc_prefix_beam_decode(enc.data_ptr(), enc_lens, B, tq, beam_size, context is not None, False, s)]
+        else:
+            rows = self._engine.prefix_beam_decode(enc.data_ptr(), enc_lens, B, tq, beam_size, search_ctc_weight, search_transducer_weight, False, s)
+            first = [[(tok[1:], score) for tok, score in row] for row in rows]
+        valid = [b for b in range(enc.size(0)) if enc_lens[b] >= 1 and first[b]]
+        nll = {}
+        if valid:
+            sub = enc if len(valid) == enc.size(0) else enc.index_select(0, torch.tensor(valid, device=enc.device)).contiguous()
+            nh, hl, ht = pack_nbest([[t for t, _ in first[b]] for b in valid])
+            out = self._engine.transducer_nll_nbest(sub.data_ptr(), enc_lens[valid], nh, hl, ht, len(valid), sub.size(1), None, _stream_ptr())
+            nll = {b: out[i, :nh[i]] for i, b in enumerate(valid)}
+        return [select_rescored([t for t, _ in row], [f for _, f in row], nll.get(b), ctc_weight, transducer_weight) for b, row in enumerate(first)]
+
+    def transducer_attention_rescoring(self, speech: torch.Tensor, speech_lengths: torch.Tensor, beam_size: int, decoding_chunk_size: int = -1,
+                                       num_decoding_left_chunks: int = -1, simulate_streaming: bool = False, reverse_weight: float = 0.0,
+                                       ctc_weight: float = 0.0, attn_weight: float = 0.0, transducer_weight: float = 0.0,
+                                       search_ctc_weight: float = 1.0, search_transducer_weight: float = 0.0,
+                                       beam_search_type: str = "transducer"):
+        """Transducer.transducer_attention_rescoring (wenet/transducer/transducer.py:261-395), B = 1, same signature and return value
+        (tokens, score): n-best from the first pass -- "transducer": the prefix beam search with the two search weights, "ctc": the
+        CTC prefix beam search -- every hypothesis re-scored with the full transducer likelihood over the same frames, the best of
+        first_score * ctc_weight + td_score * transducer_weight.  This model has no attention decoder: attn_weight and
+        reverse_weight must be 0; the encoder is the full-context one (decoding_chunk_size -1), num_decoding_left_chunks and
+        simulate_streaming have nothing to act on.  The reference's `assert len(hyps) == beam_size` is not kept: a short
+        utterance may yield fewer.  score is -inf when no total compares greater (:372), e.g. no valid frame."""
+        check_rescoring_args(attn_weight, reverse_weight, decoding_chunk_size, beam_search_type)
+        assert speech.shape[0] == speech_lengths.shape[0] == 1, "transducer_attention_rescoring is batch-1 in the reference (:313)"
+        best, rows = self.rescoring_batch(speech, speech_lengths, beam_size, ctc_weight, transducer_weight, beam_search_type, None,
+                                          search_ctc_weight, search_transducer_weight)[0]
+        total = rows[best][3]
+        return rows[best][0], (total if total > -float("inf") else -float("inf"))
 
     def greedy_search_full(self, audios, audio_lens, n_steps: int = 64):
         """basic_greedy_search over the deterministic full-context encoder; audios [B,T,80] with B <= max_streams,
@@ -959,13 +1037,18 @@ class StreamPool:
     Audio in: feed_wave(slot, samples, final) queues PCM packets instead of feature chunks; step() first turns the packets of all
     slots into fbank frames with ONE rnnt_pool_wave call (the streaming form of rnnt_fbank: per slot the frames of the whole
     waveform, whatever the packet split), collects them in a per-slot device FIFO and moves every full chunk_frames, and at final
-    the remainder, to the chunk queue.  A slot is fed either way, never both."""
+    the remainder, to the chunk queue.  A slot is fed either way, never both.
+    Two-pass decoding: open(..., keep_frames=True) makes the slot keep its encoder frames on the device; rescore(slots, ctc_weight,
+    transducer_weight) re-scores the n-best of CTC prefix slots with the transducer likelihood over their own frames in one library
+    call (WeNet's transducer_attention_rescoring, per slot and mid-utterance if wanted), frames(slot) reads the frames and
+    token_times(slot) aligns a greedy slot's tokens over them."""
 
     def __init__(self, state_dict, n_slots: int, vocab_size: int = 412, blank_id: int = 5, max_chunk_frames: int = 64,
                  max_cache_frames: int = 512, max_tokens: int = 4096, device: int = 0, numerics=None, packed=None, engine=None,
                  max_beam: int = 0, sample_rate: int = 16000, n_fft: int = 1024, chunk_frames: int = 16):
         """state_dict / packed: as StreamingBatch.  engine: an object with reset / stream_open / pool_chunk / stream_tokens (and
-        pool_chunk_beam / stream_beam for beam slots, pool_chunk_ctc_prefix / stream_ctc_prefix / context_set for CTC prefix slots)
+        pool_chunk_beam / stream_beam for beam slots, pool_chunk_ctc_prefix / stream_ctc_prefix / context_set for CTC prefix slots,
+        stream_keep_frames / stream_frames / pool_rescore / transducer_align for slots that keep their frames)
         to drive instead of a new RnntEngine (a recording fake in the CPU tests).
         max_beam: the largest beam_size open() may be given (0: greedy only).
         sample_rate / n_fft / chunk_frames: the front-end of feed_wave and the chunk length its frames are fed in (the engine also
@@ -996,6 +1079,7 @@ class StreamPool:
         self._offset: Dict[int, int] = {}
         self._ntok: Dict[int, int] = {}
         self._beam: Dict[int, int] = {}                 # beam size of the open slots (0 = greedy)
+        self._keep: Dict[int, bool] = {}                # keep_frames of the slot's last open()
         self._ctc: Dict[int, Tuple[int, Optional[ContextBias]]] = {}   # (beam, context) of the open CTC prefix slots
         self._queue: List[Tuple[int, torch.Tensor]] = []
         self._carry: Dict[int, List[int]] = {}          # increments of other slots produced by the step inside a close()
@@ -1009,13 +1093,15 @@ class StreamPool:
     def _stream(t):
         return _stream_ptr() if (t is None and torch.cuda.is_available()) or (t is not None and t.is_cuda) else None
 
-    def open(self, beam_size: int = 0, ctc_prefix_beam: int = 0, context: Optional[ContextBias] = None) -> int:
+    def open(self, beam_size: int = 0, ctc_prefix_beam: int = 0, context: Optional[ContextBias] = None, keep_frames: bool = False) -> int:
         """The lowest free slot, reset for a new utterance (reset_streaming_cache for that slot alone).  beam_size > 0: the slot's
         utterance is beam-searched with that beam (its hypotheses start as the one empty hypothesis); raises RnntError at once
         when this pool cannot do it.  ctc_prefix_beam > 0 (not together with beam_size): the slot's utterance runs the CTC prefix beam
         search with that beam, biased by `context` when given.  The pool holds one graph at a time: a context other than the current
         one is uploaded (context_set) unless another biased slot is still open, which raises RnntError.  A refused open() -- a
-        graph the library rejects included (an empty phrase, the blank, a token outside the vocabulary) -- takes no slot."""
+        graph the library rejects included (an empty phrase, the blank, a token outside the vocabulary) -- takes no slot.
+        keep_frames: the slot keeps the encoder frames of its utterance on the device (rnnt_stream_keep_frames, max_cache_frames KB),
+        what frames(), rescore() and token_times() read."""
         if ctc_prefix_beam:
             if beam_size:
                 raise RnntError("stream pool: beam_size and ctc_prefix_beam are mutually exclusive")
@@ -1035,7 +1121,10 @@ class StreamPool:
             self._context = context
         slot = self._free[0]
         self.engine.stream_open(slot, self._stream(None))
+        if keep_frames:
+            self.engine.stream_keep_frames(slot, True, self._stream(None))
         self._free.pop(0)
+        self._keep[slot] = bool(keep_frames)
         if ctc_prefix_beam:
             self._ctc[slot] = (int(ctc_prefix_beam), context)
         self._offset[slot] = 0
@@ -1165,6 +1254,51 @@ class StreamPool:
         if slot not in self._ctc:
             raise RnntError(f"slot {slot} is not an open CTC prefix slot")
         return [(tok, score, times) for tok, score, times, _ in self.engine.stream_ctc_prefix(slot, final, stream=self._stream(None))]
+
+    def _require_kept(self, slot: int):
+        if slot not in self._offset or not self._keep.get(slot, False):
+            raise RnntError(f"slot {slot} is not an open slot that keeps its frames (open(keep_frames=True))", ERR_STATE)
+
+    def frames(self, slot: int) -> torch.Tensor:
+        """The encoder frames [t, 256] of the slot's utterance so far (a device tensor, a copy): what the chunks stepped so far gave,
+        the rows rnnt_get_enc_frames returns per chunk, concatenated."""
+        self._require_kept(slot)
+        return self.engine.stream_frames(slot, 0, self._stream(None))
+
+    def rescore(self, slots: List[int], ctc_weight: float, transducer_weight: float):
+        """The second pass for CTC prefix slots opened with keep_frames=True: per slot ctc_hyps(final=True), then ONE
+        rnnt_pool_rescore call for all listed slots -- every hypothesis re-scored with the transducer likelihood over the slot's kept
+        frames -- then the choice of rnnt_rescore_select_host with total = ctc_score * ctc_weight + td_score * transducer_weight.
+        Returns {slot: (best_index, [(tokens, ctc_score, td_score, total)])} in the search's order.  Only reads the slots: their
+        searches go on, so partial results may be re-scored mid-utterance (queued chunks are not in them: step() first)."""
+        slots = [int(x) for x in slots]
+        for slot in slots:
+            if slot not in self._ctc:
+                raise RnntError(f"slot {slot} is not an open CTC prefix slot")
+            self._require_kept(slot)
+        first = [self.ctc_hyps(slot, final=True) for slot in slots]
+        nh, hl, ht = pack_nbest([[tok for tok, _, _ in row] for row in first])
+        nll = self.engine.pool_rescore(slots, nh, hl, ht, self._stream(None))
+        return {slot: select_rescored([tok for tok, _, _ in row], [sc for _, sc, _ in row], nll[i, :nh[i]], ctc_weight, transducer_weight)
+                for i, (slot, row) in enumerate(zip(slots, first))}
+
+    def token_times(self, slot: int, frame_rate: float = 0.04):
+        """[(start_s, end_s)] per token emitted so far by a GREEDY slot that keeps its frames: the best transducer alignment
+        (rnnt_transducer_align) of its tokens over its kept frames, then timestamps_from_peaks of the emit frames with max_duration
+        = the frames so far.  Raises RnntError beyond 255 tokens (the alignment's range)."""
+        self._require_kept(slot)
+        if self._beam.get(slot, 0) > 0 or slot in self._ctc:
+            raise RnntError(f"slot {slot} is not a greedy slot")
+        s = self._stream(None)
+        tokens = self.engine.stream_tokens(slot, 0, s)
+        if len(tokens) > 255:
+            raise RnntError(f"slot {slot}: {len(tokens)} tokens, the alignment holds at most 255", ERR_SHAPE)
+        enc = self.engine.stream_frames(slot, 0, s)
+        t = enc.size(0)
+        if t == 0 or not tokens:
+            return []
+        _, emit = self.engine.transducer_align(enc.data_ptr(), [t], np.asarray(tokens, np.int32).reshape(1, -1), [len(tokens)], 1, t, stream=s)
+        return timestamps_from_peaks(emit[0, :len(tokens)].tolist(), t * frame_rate, frame_rate)
 
     def close(self, slot: int):
         """Finish the slot's utterance (queued chunks are processed first) and free the slot; returns all its tokens (greedy slot),

@@ -210,6 +210,27 @@ def transducer_nll_ref(pick, T_b, U_b):
     return -(alpha[T_b - 1, U_b] + p[T_b - 1, U_b, 0])
 
 
+def nbest_pick_slice(pick, n, U1):
+    """Hypothesis n's lattice [T, U1, 2] of one utterance's n-best picked lattice [T, N * U1, 2] (rnnt_transducer_nll_nbest lays the
+    hypotheses side by side along U), the argument of transducer_nll_ref."""
+    return np.asarray(pick)[:, n * U1:(n + 1) * U1]
+
+
+def rescore_select_ref(first_scores, nll, first_weight, transducer_weight):
+    """The choice of Transducer.transducer_attention_rescoring (wenet/transducer/transducer.py:372-393) with attn_weight = 0, in
+    Python floats: score = beam_score[i] * ctc_weight + td_s * transducer_weight with td_s = -nll[i]; best_index starts at 0 with
+    -inf and moves on `score > best_score` only, so -inf * 0.0 = nan is never chosen.  Returns (best_index, [score])."""
+    best_score, best_index, totals = -float("inf"), 0, []
+    for i in range(len(first_scores)):
+        td_s = -float(nll[i])
+        score = float(first_scores[i]) * float(first_weight) + td_s * float(transducer_weight)
+        totals.append(score)
+        if score > best_score:
+            best_score = score
+            best_index = i
+    return best_index, totals
+
+
 def transducer_nll_bruteforce(pick, T_b, U_b):
     """The same likelihood as an explicit sum over every alignment: each one is an order of T_b - 1 blanks and U_b labels
     (C(T_b - 1 + U_b, U_b) of them) followed by the final blank at (T_b - 1, U_b); exact summation (math.fsum) of the path

@@ -473,7 +473,8 @@ int rnnt_ctc_prefix_beam_host(const float* lp_host, const int32_t* enc_lens_host
  *   enc_dev [B, T, 256] device; enc_lens_host [B] (T_b in [1, T]); targets_host [B, Umax] int32; target_lens_host [B] (U_b in
  *   [0, Umax]); nll_host [B] double; pick_dev: NULL, or device float [B, T, Umax + 1, 2] that receives the picked lattice
  *   (for every cell t < T_b, u <= U_b, label slot u < U_b: bitwise rnnt_joint(mode 1) at those two columns; other cells undefined).
- * Rows need not be distinct utterances: the same frames with B transcripts is hypothesis rescoring.  Entries of targets_host
+ * Rows need not be distinct utterances: the same frames with B transcripts is hypothesis rescoring (rnnt_transducer_nll_nbest
+ * does that without repeating the frames).  Entries of targets_host
  * beyond a row's length, and frames beyond T_b, are never read into a result.  Like rnnt_joint the call leaves streaming, pool
  * and beam state alone.  Exact-f32 mode and vocabularies outside the lattice kernel's range (> 416 or not a multiple of 4)
  * materialise the whole log-softmax lattice in a grow-only buffer and gather the two columns: same values, slow by design.
@@ -490,6 +491,62 @@ int rnnt_transducer_nll(rnnt_ctx* ctx, const float* enc_dev, const int32_t* enc_
  * ctc_head.ctc_lo.{weight,bias}.  Synchronises. */
 int rnnt_ctc_nll(rnnt_ctx* ctx, const float* enc_dev, const int32_t* enc_lens_host, const int32_t* targets_host,
                  const int32_t* target_lens_host, int32_t B, int32_t T, int32_t Umax, double* nll_host, void* stream);
+
+/* -- two-pass decoding: a cheap first pass yields n-best, the transducer likelihood re-scores it (the reference's WeNet layer:
+ * Transducer.transducer_attention_rescoring with _cal_transducer_score, wenet/transducer/transducer.py:160-185, 261-395) ------- */
+/* rnnt_transducer_nll for N hypotheses per utterance WITHOUT repeating the utterance's frames N times: nll_host[b][n] is what
+ * rnnt_transducer_nll defines for frames b and transcript (b, n), n < n_hyp_host[b]; entries n >= n_hyp_host[b] are 0.  The
+ * hypotheses of an utterance lie side by side along U of one lattice -- pred [B][N * (Umax + 1)][256] -- so joint.enc_ffn runs over
+ * the B*T frames once and the context scratch holds B*T + B*N*(Umax+1) rows instead of B*N*(T + Umax + 1).  The predictor runs
+ * Umax + 1 steps over B*N rows (rows of missing hypotheses on blanks), the unchanged lattice kernel writes the picked lattice with
+ * U = N * (Umax + 1), and transducer_alpha_nbest (one workgroup per (b, n), rnnt_transducer_nll's recursion in f64) reads cell
+ * (t, u) of hypothesis n at ((b T + t) N (Umax+1) + n (Umax+1) + u) * 2.  One upload, one download of B*N doubles, one synchronisation.
+ *   enc_dev [B, T, 256] device; enc_lens_host [B] (T_b in [1, T]); n_hyp_host [B] (in [1, N]); hyp_lens_host [B, N] (in [0, Umax];
+ *   an empty hypothesis is valid); hyp_tokens_host [B, N, Umax] int32; nll_host [B, N] double; pick_dev: NULL, or device float
+ *   [B, T, N * (Umax + 1), 2] that receives the picked lattice (valid cells as for rnnt_transducer_nll, per hypothesis: bitwise
+ *   rnnt_joint(mode 1) over pred [B, N * (Umax + 1), 256] at those two columns).
+ * Frames beyond T_b, tokens beyond a hypothesis' length, and lengths and tokens of rows n >= n_hyp_host[b] are never read into a
+ * result.  Exact-f32 mode and vocabularies outside the lattice kernel's range take rnnt_transducer_nll's fallback with the same U.
+ * Like rnnt_joint the call leaves streaming, pool, beam and CTC-prefix state alone.  Profile tags: 20 / 21 the predictor steps,
+ * 13 / 22 the two projections, 40 the pick, 41 the recursion.
+ * Refusals, all decided on the host before the first launch, changing nothing: null pointer, B < 1, N outside [1, 16], n_hyp outside
+ * [1, N], T_b outside [1, T], a length outside [0, Umax], a label outside [0, vocab) or equal to blank_id inside a length:
+ * RNNT_ERR_ARG; Umax > 255, B*T*256 + B*N*(Umax+1)*256 floats beyond the context scratch, or B*T*N*(Umax+1) >= 2^31 - 64:
+ * RNNT_ERR_SHAPE; weights not finalized: RNNT_ERR_STATE. */
+int rnnt_transducer_nll_nbest(rnnt_ctx* ctx, const float* enc_dev, const int32_t* enc_lens_host, const int32_t* n_hyp_host,
+                              const int32_t* hyp_lens_host, const int32_t* hyp_tokens_host, int32_t B, int32_t T, int32_t N,
+                              int32_t Umax, double* nll_host, float* pick_dev, void* stream);
+/* The choice among one utterance's re-scored hypotheses as a pure C++ function (no context, no GPU): transducer.py:372-393 with
+ * attn_weight = 0.  total_out[i] = first_scores[i] * first_weight + (-nll[i]) * transducer_weight, each product and the sum rounded
+ * separately in f64; *best_out starts at 0 with -inf and moves on strict > only, so the first of equal totals wins and a NaN total
+ * (-inf * 0.0, as in Python) is never chosen; if none compares greater *best_out is 0.  RNNT_ERR_ARG: null pointer or n_hyp < 1. */
+int rnnt_rescore_select_host(int32_t n_hyp, const double* first_scores, const double* nll, double first_weight,
+                             double transducer_weight, double* total_out, int32_t* best_out);
+
+/* -- frames that outlive their chunk: the per-slot encoder-frame history of the stream pool ------------------------------------------ */
+/* keep != 0: from now on every pool call that encodes `slot` (rnnt_pool_chunk in either mode, rnnt_pool_chunk_beam,
+ * rnnt_pool_chunk_ctc_prefix) appends the slot's t' new encoder outputs -- the after_norm rows rnnt_get_enc_frames returns, before
+ * the joint projection -- to a history [max_cache_frames][256] f32 of the slot (ONE extra launch per pool call, pool_hist_append,
+ * and only when a listed slot keeps frames).  Valid on a slot that has not advanced since it was opened or reset (RNNT_ERR_STATE
+ * otherwise: its first frames are gone); the context enters pool mode.  The history is an owning device buffer per slot,
+ * max_cache_frames KB: allocated on the slot's first keep, reused by its later utterances, counted by rnnt_live_device_bytes, freed
+ * by rnnt_destroy.  rnnt_stream_open clears its slot's flag and length, rnnt_streams_reset all: a slot keeps nothing unless asked
+ * again.  A pool call that would take a kept slot past max_cache_frames is refused with RNNT_ERR_SHAPE before its first launch and
+ * moves no slot.  keep == 0: the flag and the length are cleared (any time).  Does not synchronise. */
+int rnnt_stream_keep_frames(rnnt_ctx* ctx, int32_t slot, int32_t keep, void* stream);
+/* frames [from, len) of the slot's history, at most cap_frames, device to device into dst_dev [cap_frames, 256] on `stream`;
+ * *n_out (optional) = len - from (0 when from >= len).  dst_dev may be NULL with cap_frames = 0 to query.  The length is the host's:
+ * no synchronisation.  RNNT_ERR_STATE on a slot that keeps no frames. */
+int rnnt_stream_get_frames(rnnt_ctx* ctx, int32_t slot, int32_t from, int32_t cap_frames, float* dst_dev, int32_t* n_out, void* stream);
+/* The second pass of a streaming server: rnnt_transducer_nll_nbest over the kept frames of the n listed slots (distinct, each
+ * keeping >= 1 frame).  pool_hist_gather stages their histories into a dense grow-only [n][Tmax][256] buffer (Tmax = the longest
+ * history of the call; rows beyond a slot's length are never read), then that pipeline runs with B = n, T = Tmax, T_b = the
+ * history lengths: n_hyp_host [n], hyp_lens_host [n, N], hyp_tokens_host [n, N, Umax], nll_host [n, N] as there.  The call only
+ * reads slot state: searches and streams go on afterwards, so partial results may be re-scored mid-utterance.  Refusals as
+ * rnnt_transducer_nll_nbest, plus RNNT_ERR_ARG for a duplicated or out-of-range slot and RNNT_ERR_STATE for a listed slot that
+ * keeps no frames or has none yet; all before the first launch.  Synchronises. */
+int rnnt_pool_rescore(rnnt_ctx* ctx, int32_t n, const int32_t* slots_host, const int32_t* n_hyp_host, const int32_t* hyp_lens_host,
+                      const int32_t* hyp_tokens_host, int32_t N, int32_t Umax, double* nll_host, void* stream);
 
 /* -- forced alignment: WHERE in the frames each token of a given transcript lies (the reference's WeNet layer: force_align,
  * gen_ctc_peak_time, gen_timestamps_from_peak, DecodeResult.times; wenet/utils/ctc_utils.py) ------------------------------------ */
@@ -599,7 +656,8 @@ const float* rnnt_enc_frames_dev(rnnt_ctx* ctx, int32_t* frames_out, int32_t* st
 /* per-launch-site timing with HIP events recorded on the launch stream (bench.py roofline leg).
  * tag selects ONE launch site: 1 conv1, 2 conv2 (implicit GEMM), 3 embed linear, 4 FFN w_1, 5 FFN w_2, 6 QKV,
  * 7 attention, 8 attention out-proj, 9 pointwise_conv1+GLU, 10 depthwise conv, 11 pointwise_conv2, 13 joint enc
- * projection, 20 LSTM cell, 21 predictor projection, 22 joint pred_ffn+tanh, 23 joint ffn_out, 40 the picked lattice of
+ * projection, 20 LSTM cell, 21 predictor projection, 22 joint pred_ffn+tanh, 23 joint ffn_out (13 and 20 - 22 also tag the
+ * teacher-forced predictor steps and the two projections of the scoring and alignment calls), 40 the picked lattice of
  * rnnt_transducer_nll, 41 its alpha recursion (and rnnt_ctc_nll's), 42 the Viterbi launch of the rnnt_*_align calls, 43 prefix_step
  * and 44 prefix_merge of rnnt_prefix_beam_decode (one launch each per frame), 45 ctc_prefix_search of the rnnt_ctc_prefix_beam_*
  * calls (one launch per call), 46 ctc_prefix_search_pool of rnnt_pool_ctc_prefix_logprobs / rnnt_pool_chunk_ctc_prefix (the resumable
