@@ -21,6 +21,7 @@ int rnnt_create(const rnnt_config* cfg, rnnt_ctx** out) {
     HIPCHK(hipDeviceGetAttribute(&ctx->n_cus, hipDeviceAttributeMultiprocessorCount, cfg->device));
     if (const char* ae = getenv("RNNT_ATTN_STREAM")) ctx->attn_stream = (ae[0] == '0') ? 0 : 1;
     if (const char* be = getenv("RNNT_BEAM_CHAIN")) ctx->use_beam_chain = (be[0] == '0') ? 0 : 1;
+    if (const char* pg = getenv("RNNT_PREFIX_GROUP")) ctx->prefix_group = pg[0] == '1' ? 1 : (pg[0] == '4' ? 4 : 0);
     if (const char* fu = getenv("RNNT_FUSED")) ctx->use_fused = atoi(fu);   // 0 off, 1 split-operand modes (default), 2 every mode
     if (const char* fe = getenv("RNNT_FUSE_AFTER_NORM")) ctx->fuse_after_norm = (fe[0] == '0') ? 0 : 1;
     if (const char* me = getenv("RNNT_WF_MERGE")) { const int m = atoi(me); ctx->wf_merge = m < 1 ? 1 : (m > WF_MERGE_MAX ? WF_MERGE_MAX : m); }
@@ -505,5 +506,6 @@ int rnnt_streams_reset(rnnt_ctx* ctx, int32_t n_streams, void* stream) {
     pool_wave_reset(ctx, 0, B);                             // the per-slot streaming front-ends of the stream pool
     if ((rc = pool_beam_reset(ctx, s, 0, B))) return rc;   // the per-slot beam state of the stream pool, once it exists
     if ((rc = pool_hist_reset(ctx, s, 0, B))) return rc;   // no slot keeps its encoder frames
-    return pool_ctc_reset(ctx, s, 0, B);                    // and its per-slot CTC prefix searches
+    if ((rc = pool_ctc_reset(ctx, s, 0, B))) return rc;    // its per-slot CTC prefix searches
+    return pool_prefix_reset(ctx, s, 0, B);                 // and its per-slot transducer prefix searches
 }

@@ -50,12 +50,6 @@ void pool_enter(rnnt_ctx* ctx) {
     ctx->pool_mode = true;
 }
 
-struct GemmCapScope {   // row-count dependent kernel choices as for one stream, for the launches of one pool call
-    rnnt_ctx* ctx;
-    explicit GemmCapScope(rnnt_ctx* c) : ctx(c) { ctx->gemm_m_cap = 1023; }
-    ~GemmCapScope() { ctx->gemm_m_cap = 0; }
-};
-
 // attention of one layer for the n active rows.  The kernel is chosen PER ROW exactly as launch_attn chooses it for that row's
 // T2 (attn_stream_ok): the streaming kernel for <= 4 new frames and <= 4096 keys, the LDS-tiled one otherwise; a launch whose
 // grid holds rows of the other kind lets their workgroups exit.  LDS of the streaming kernel: sized for the deepest row it serves.
@@ -120,6 +114,7 @@ int rnnt_stream_open(rnnt_ctx* ctx, int32_t slot, void* stream) {
     LAUNCHCHK("stream_slot_reset");
     if ((rc = pool_beam_reset(ctx, s, slot, 1))) return rc;   // the slot's beam: one empty hypothesis (once the beam state exists)
     if ((rc = pool_ctc_reset(ctx, s, slot, 1))) return rc;    // the slot's CTC prefix search: the start hypothesis (likewise)
+    if ((rc = pool_prefix_reset(ctx, s, slot, 1))) return rc; // the slot's transducer prefix search: [blank] (likewise)
     pool_wave_reset(ctx, slot, 1);                            // the slot's streaming front-end: no samples, no frames
     if ((rc = pool_hist_reset(ctx, s, slot, 1))) return rc;   // the slot keeps no encoder frames unless asked again
     pool_enter(ctx);
@@ -128,14 +123,14 @@ int rnnt_stream_open(rnnt_ctx* ctx, int32_t slot, void* stream) {
 }
 
 namespace {
-enum { POOL_ENCODE = 0, POOL_GREEDY = 1, POOL_BEAM = 2, POOL_CTC_PREFIX = 3 };
+enum { POOL_ENCODE = 0, POOL_GREEDY = 1, POOL_BEAM = 2, POOL_CTC_PREFIX = 3, POOL_PREFIX = 4 };
 
-// rnnt_pool_chunk (mode POOL_ENCODE / POOL_GREEDY), rnnt_pool_chunk_beam (POOL_BEAM) and rnnt_pool_chunk_ctc_prefix (POOL_CTC_PREFIX):
-// validation, the call's table, the encoder launches and the position bookkeeping are one code path; only what follows the encoder
-// differs.  use_context: POOL_CTC_PREFIX only.
+// rnnt_pool_chunk (mode POOL_ENCODE / POOL_GREEDY), rnnt_pool_chunk_beam (POOL_BEAM), rnnt_pool_chunk_ctc_prefix (POOL_CTC_PREFIX) and
+// rnnt_pool_chunk_prefix (POOL_PREFIX): validation, the call's table, the encoder launches and the position bookkeeping are one code
+// path; only what follows the encoder differs.  use_context: POOL_CTC_PREFIX only; ctc_weight / transducer_weight: POOL_PREFIX only.
 int pool_chunk_run(rnnt_ctx* ctx, const char* fn, int32_t n_active, const int32_t* slots_host, const float* fbank_dev, int32_t T,
                    const int32_t* offsets_host, const int32_t* required_host, int mode, int32_t beam_size, int32_t* frames_out, void* stream,
-                   int32_t use_context = 0) {
+                   int32_t use_context = 0, float ctc_weight = 0.f, float transducer_weight = 0.f) {
     if (!ctx || !slots_host || !fbank_dev || !offsets_host || !required_host) return fail(ctx, RNNT_ERR_ARG, "%s: null argument", fn);
     if (!ctx->finalized || ctx->n_streams < 1) return fail(ctx, RNNT_ERR_STATE, "%s: no weights / no streams", fn);
     if (mode == POOL_GREEDY && !ctx->use_persistent) return fail(ctx, RNNT_ERR_STATE, "%s: the greedy decode of a pool call needs the resident decoder", fn);
@@ -201,15 +196,20 @@ int pool_chunk_run(rnnt_ctx* ctx, const char* fn, int32_t n_active, const int32_
         if ((rc = reserve(ctx, ctx->cp_lp, (size_t)n * tq * V))) return rc;
         if ((rc = pool_ctc_alloc(ctx, s))) return rc;
     }
+    if (mode == POOL_PREFIX) {       // likewise for the transducer prefix search
+        if ((rc = pool_prefix_check(ctx, fn, n, slots_host, tq, beam_size, ctc_weight, transducer_weight))) return rc;
+        if ((rc = pool_prefix_alloc(ctx, s, (size_t)n * tq, ctc_weight > 0.f))) return rc;
+    }
     if ((rc = pool_alloc(ctx))) return rc;
     if (mode == POOL_BEAM && (rc = pool_beam_alloc(ctx, s))) return rc;
     // ---- the call's table: one async copy, no synchronisation before the launches ---------------------------------------------------
     HIPCHK(hipEventSynchronize(ctx->pool_ev));             // the previous call's copy has left the pinned buffer (normally long ago)
     memcpy(ctx->pool_tab_host, rows.data(), (size_t)n * sizeof(PoolRow));
     for (int i = 0; i < n; ++i) ctx->pool_tab_host[(size_t)n * POOL_ROW_INTS + i] = rows[i].slot;
-    if (mode == POOL_BEAM)
-        for (int i = 0; i < n; ++i) ctx->pool_tab_host[(size_t)n * (POOL_ROW_INTS + 1) + i] = ctx->ps_cur[rows[i].slot];
-    HIPCHK(hipMemcpyAsync(ctx->pool_tab, ctx->pool_tab_host, (size_t)n * (POOL_ROW_INTS + (mode == POOL_BEAM ? 2 : 1)) * sizeof(int), hipMemcpyHostToDevice, s));
+    const bool with_cur = mode == POOL_BEAM || mode == POOL_PREFIX;   // the searches with two buffer sets: the slot's current one
+    if (with_cur)
+        for (int i = 0; i < n; ++i) ctx->pool_tab_host[(size_t)n * (POOL_ROW_INTS + 1) + i] = mode == POOL_BEAM ? ctx->ps_cur[rows[i].slot] : ctx->pp_cur[rows[i].slot];
+    HIPCHK(hipMemcpyAsync(ctx->pool_tab, ctx->pool_tab_host, (size_t)n * (POOL_ROW_INTS + (with_cur ? 2 : 1)) * sizeof(int), hipMemcpyHostToDevice, s));
     HIPCHK(hipEventRecord(ctx->pool_ev, s));
     const PoolRow* rows_dev = reinterpret_cast<const PoolRow*>(ctx->pool_tab.p);
     const int* slots_dev = ctx->pool_tab + (size_t)n * POOL_ROW_INTS;
@@ -222,9 +222,12 @@ int pool_chunk_run(rnnt_ctx* ctx, const char* fn, int32_t n_active, const int32_
         // after_norm in place over the compact rows, then the joint's encoder projection into frames [0, t') of every active slot
         if ((rc = launch_ln(ctx, s, LnP{ctx->x, ctx->after_g, ctx->after_b, ctx->x, n * tq, BIG, 0, 0LL, (long long)D}))) return rc;
         if ((rc = pool_hist_append_rows(ctx, s, n, slots_host, slots_dev, tq))) return rc;   // slots that keep their frames (rnnt_stream_keep_frames)
-        GemmP g = plain_gemm(ctx->x, D, ctx->wenc, D, ctx->benc, ctx->encp, D, n * tq, D, D);
-        g.c_n = tq; g.c_s0 = (long long)ctx->fstride * D; g.c_r0 = 0; g.c_mod = BIG; g.c_s1 = D;
-        g.c_tab = ctx->pool_tab; g.c_tab_col = POOL_COL_ZERO;
+        // (the transducer prefix search reads the call's frames compact, row i * t' + f, from its own buffer)
+        GemmP g = plain_gemm(ctx->x, D, ctx->wenc, D, ctx->benc, mode == POOL_PREFIX ? ctx->pp_encp.p : ctx->encp.p, D, n * tq, D, D);
+        if (mode != POOL_PREFIX) {
+            g.c_n = tq; g.c_s0 = (long long)ctx->fstride * D; g.c_r0 = 0; g.c_mod = BIG; g.c_s1 = D;
+            g.c_tab = ctx->pool_tab; g.c_tab_col = POOL_COL_ZERO;
+        }
         if ((rc = launch_gemm(ctx, s, &g, 1, TAG_ENC_PROJ))) return rc;
     }
     for (int i = 0; i < n; ++i) ctx->slot_pos[rows[i].slot].advance(rows[i].T2, tq, required_host[i]);
@@ -265,6 +268,15 @@ int pool_chunk_run(rnnt_ctx* ctx, const char* fn, int32_t n_active, const int32_
         }
         return pool_ctc_launch(ctx, s, n, slots_host, ctx->cp_lp, tq, beam_size, use_context);   // the frames are consumed: frames_buffered stays 0
     }
+    if (mode == POOL_PREFIX) {
+        // ---- the CTC log-probabilities of the compact after_norm rows when the search fuses them, then the slots' searches ----
+        if (ctc_weight > 0.f) {
+            GemmCapScope cap_scope(ctx);
+            if ((rc = rnnt_ctc_logprobs(ctx, ctx->x, n * tq, ctx->pp_ctc, stream))) return rc;
+        }
+        return pool_prefix_launch(ctx, s, n, slots_host, slots_dev, ctx->pool_tab + (size_t)n * (POOL_ROW_INTS + 1), tq, beam_size, ctc_weight,
+                                  transducer_weight);   // the frames are consumed: frames_buffered stays 0
+    }
     if (mode == POOL_ENCODE) {   // frames [0, t') of the active slots stay buffered for rnnt_get_enc_frames until rnnt_frames_discard
         hipLaunchKernelGGL(pool_scatter_frames, dim3(grid_for((long long)n * tq * (D / 4))), dim3(256), 0, s, ctx->x, ctx->encbuf, rows_dev, n, tq,
                            (long long)ctx->fstride * D);
@@ -299,6 +311,12 @@ int rnnt_pool_chunk_ctc_prefix(rnnt_ctx* ctx, int32_t n_active, const int32_t* s
                                const int32_t* required_host, int32_t beam_size, int32_t use_context, int32_t* frames_out, void* stream) {
     return pool_chunk_run(ctx, "rnnt_pool_chunk_ctc_prefix", n_active, slots_host, fbank_dev, T, offsets_host, required_host, POOL_CTC_PREFIX, beam_size,
                           frames_out, stream, use_context);
+}
+
+int rnnt_pool_chunk_prefix(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, const float* fbank_dev, int32_t T, const int32_t* offsets_host,
+                           const int32_t* required_host, int32_t beam_size, float ctc_weight, float transducer_weight, int32_t* frames_out, void* stream) {
+    return pool_chunk_run(ctx, "rnnt_pool_chunk_prefix", n_active, slots_host, fbank_dev, T, offsets_host, required_host, POOL_PREFIX, beam_size,
+                          frames_out, stream, 0, ctc_weight, transducer_weight);
 }
 
 namespace {

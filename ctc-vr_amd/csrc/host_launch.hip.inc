@@ -36,7 +36,8 @@ enum { TAG_NONE = 0, TAG_CONV1 = 1, TAG_CONV2 = 2, TAG_EMBED = 3, TAG_FFN1 = 4, 
        TAG_PREFIX_STEP = 43, TAG_PREFIX_MERGE = 44,   // prefix beam search: prefix_step / prefix_merge, one launch each per frame
        TAG_CTC_PREFIX = 45,                           // CTC prefix beam search: ctc_prefix_search, one launch per call
        TAG_CTC_PREFIX_POOL = 46, TAG_CTC_PREFIX_PACK = 47,     // its resumable form per slot of the stream pool: ctc_prefix_search_pool / ctc_prefix_pack
-       TAG_WAVE_STAGE = 48 };                         // streaming front-end of the stream pool: wave_stage of rnnt_pool_wave
+       TAG_WAVE_STAGE = 48,                           // streaming front-end of the stream pool: wave_stage of rnnt_pool_wave
+       TAG_PREFIX_STEP_POOL = 49, TAG_PREFIX_MERGE_POOL = 50 };   // prefix beam search per slot of the stream pool: prefix_step_pool / prefix_merge_pool, one launch each per frame
 
 struct ProfScope {   // records a start/stop event pair around one launch when its site is selected
     rnnt_ctx* ctx; hipStream_t s; bool on;
@@ -107,6 +108,12 @@ int ensure_dyn_lds(rnnt_ctx* ctx, const void* fn, size_t bytes) {
     ctx->dyn_lds[fn] = (int)bytes;
     return RNNT_OK;
 }
+
+struct GemmCapScope {   // row-count dependent kernel choices as for one stream, for the launches of one pool call (or of a search that must not depend on its batch)
+    rnnt_ctx* ctx;
+    explicit GemmCapScope(rnnt_ctx* c) : ctx(c) { ctx->gemm_m_cap = 1023; }
+    ~GemmCapScope() { ctx->gemm_m_cap = 0; }
+};
 
 constexpr int WF_MERGE_MAX = 4;   // chunks of one layer per wavefront stage (rnnt_encoder_chunks), upper bound
 inline int sub_len(int T) { return ((T - 3) / 2 + 1 - 3) / 2 + 1; }   // subsampling.py:188-193
@@ -634,6 +641,24 @@ int pool_ctc_reset(rnnt_ctx* ctx, hipStream_t s, int slot0, int n) {
     if (!ctx->pc_state) return RNNT_OK;
     hipLaunchKernelGGL(ctc_prefix_slot_reset, dim3(n), dim3(64), 0, s, ctx->pc_state.p, slot0);
     LAUNCHCHK("ctc_prefix_slot_reset");
+    return RNNT_OK;
+}
+
+// ---- per-slot transducer prefix beam search of the stream pool (api_pool_prefix.hip.inc; kernels in rnnt_prefix.hip.h) -----------------
+PrefixPoolP pool_prefix_params(const rnnt_ctx* ctx) {
+    PrefixPoolP q;
+    memset(&q, 0, sizeof(q));
+    for (int t = 0; t < 2; ++t) { q.pool[t] = ctx->pp_pool[t]; q.tk[t] = ctx->pp_tk[t]; q.len[t] = ctx->pp_len[t]; q.sc[t] = ctx->pp_sc[t]; q.hs[t] = ctx->pp_hs[t]; }
+    q.nh = ctx->pp_nh;
+    return q;
+}
+
+// the start hypothesis [blank] for slots [slot0, slot0 + n): the host record always, the device rows once they exist (pool_prefix_alloc resets all)
+int pool_prefix_reset(rnnt_ctx* ctx, hipStream_t s, int slot0, int n) {
+    for (int b = slot0; b < slot0 + n && b < (int)ctx->pp_slot.size(); ++b) { ctx->pp_slot[b] = rnnt_ctx::PpSlot{0, 0, 0.f, 0.f}; ctx->pp_cur[b] = 0; }
+    if (!ctx->pp_nh) return RNNT_OK;
+    hipLaunchKernelGGL(prefix_init_pool, dim3(n), dim3(256), 0, s, pool_prefix_params(ctx), slot0, ctx->cfg.max_cache_frames + 1, ctx->cfg.blank_id);
+    LAUNCHCHK("prefix_init_pool");
     return RNNT_OK;
 }
 

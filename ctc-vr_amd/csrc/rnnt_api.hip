@@ -278,6 +278,22 @@ struct rnnt_ctx {
     PinnedBuf<int> pc_tab_host;
     hipEvent_t pc_ev = nullptr;
     DevBuf<double> pc_out;
+    // transducer prefix beam search per slot of the stream pool (api_pool_prefix.hip.inc), allocated on its first use: hypothesis i of
+    // slot b is row b * PB_MAX_BEAM + i of two buffer sets -- states [rows][2][512], token lists [rows][max_cache_frames + 1],
+    // lengths / scores / hashes [rows] -- plus the hypotheses per slot, the step's top-k [rows][PB_MAX_BEAM], the frames of one call
+    // (projected, CTC log-probabilities; grow-only), the seam form's table (slot and current set per active row, one async copy from
+    // pinned memory) and one read's packed block.  Host per slot: the current set (pp_cur; slots advance independently), and the
+    // frames walked, beam and weights of the search in progress (beam == 0: fresh).
+    int prefix_group = 0;                      // RNNT_PREFIX_GROUP: 0 by the size of the launch, 1 / 4 hypotheses per prefix_step_pool workgroup always
+    struct PpSlot { int frames_done, beam; float cw, tw; };
+    std::vector<PpSlot> pp_slot;
+    std::vector<int> pp_cur;
+    DevBuf<float> pp_pool[2], pp_toplp, pp_encp, pp_ctc;
+    DevBuf<int> pp_tk[2], pp_len[2], pp_nh, pp_toptok, pp_tab;
+    DevBuf<double> pp_sc[2], pp_out;
+    DevBuf<unsigned long long> pp_hs[2];
+    PinnedBuf<int> pp_tab_host;
+    hipEvent_t pp_ev = nullptr;
     // streaming feature front-end per slot of the stream pool (api_pool_wave.hip.inc), allocated on its first use: the carry of every
     // slot [max_streams][WAVE_CARRY_CAP], the staged rows of one call (grow-only), the call's table (slot, samples so far, new samples,
     // final per active row; one async copy from pinned memory).  Host per slot: samples received and frames emitted since the reset,
@@ -311,7 +327,7 @@ struct rnnt_ctx {
     // constructor -- rnnt_create's `new rnnt_ctx()` value-initialises lw[] and the raw weight views to null.
     ~rnnt_ctx() {
         for (auto& g : dec_graphs) (void)hipGraphExecDestroy(g.exec);
-        for (hipEvent_t e : {pool_ev, pc_ev, wv_ev, sub_ev[0], sub_ev[1]}) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : {pool_ev, pc_ev, pp_ev, wv_ev, sub_ev[0], sub_ev[1]}) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : prof_ev) (void)hipEventDestroy(e);
         for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
         for (hipStream_t st : {dec_stream, cap_stream, sub_stream}) if (st) (void)hipStreamDestroy(st);
@@ -331,6 +347,7 @@ extern "C" {
 #include "api_score.hip.inc"
 #include "api_state.hip.inc"
 #include "api_pool_ctc.hip.inc"
+#include "api_pool_prefix.hip.inc"
 #include "api_pool.hip.inc"
 #include "api_pool_hist.hip.inc"
 #include "api_pool_wave.hip.inc"

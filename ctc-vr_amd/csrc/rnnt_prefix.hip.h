@@ -29,49 +29,80 @@ struct PrefixStepP {
 // log-softmax; then the shallow fusion log(tw * exp(lp) + cw * exp(ctc)) in f32 with separately rounded products and sum
 // (prefix_beam_search.py:99-101) and the top-k over the WHOLE vocabulary, blank included (:104): value descending, lower index
 // first on equal values.
-__global__ __launch_bounds__(512) void prefix_step(PrefixStepP p) {
+//
+// prefix_step_rows<G> is that evaluation for the cnt <= G hypotheses in rows r0 .. r0 + cnt - 1 (all of one utterance, all at frame
+// row fr of encp / ctc) by one 512-thread workgroup: the four matrix-vector products read the weights ONCE for the G vectors
+// (dec_matvec<G>: every vector's sum is formed in the same order whatever G is), the cell and the log-softmax / top-k are per
+// hypothesis -- wave g does hypothesis g's.  Vectors beyond cnt repeat row r0's inputs and write nothing, so every barrier is
+// reached by the whole workgroup.  Both the batch kernel (G = 1) and the pool kernel call it: the two cannot drift.
+template <int G>
+__device__ __forceinline__ void prefix_step_rows(const PrefixStepP& p, int r0, int cnt, long long fr) {
     constexpr int NTH = 512;
-    __shared__ __attribute__((aligned(16))) float hs[1][RNNT_D], cs[RNNT_D], h2[1][RNNT_D], pr[1][RNNT_D], zs[1][RNNT_D];
-    __shared__ __attribute__((aligned(16))) float gates[4 * RNNT_D];
-    __shared__ float lg[512];
-    const int r = blockIdx.x, b = r / p.beam, i = r - b * p.beam, tid = threadIdx.x;
-    if (i >= ldgi(p.nh + b) || p.f >= ldgi(p.lens + b)) return;    // whole workgroup: before the first barrier
-    const int tok = ldgi(p.tk + (long long)r * p.lcap + ldgi(p.len + r) - 1);
-    float* pool = p.pool + (long long)r * 1024;
-    const long long fr = (long long)b * p.T + p.f;
+    __shared__ __attribute__((aligned(16))) float hs[G][RNNT_D], cs[G][RNNT_D], h2[G][RNNT_D], pr[G][RNNT_D], zs[G][RNNT_D];
+    __shared__ __attribute__((aligned(16))) float gates[G][4 * RNNT_D];
+    __shared__ float lg[G][512];
+    const int tid = threadIdx.x;
+    int tok[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        const int r = r0 + (g < cnt ? g : 0);
+        tok[g] = ldgi(p.tk + (long long)r * p.lcap + ldgi(p.len + r) - 1);
+    }
     const float* enc = p.encp + fr * RNNT_D;
-    if (tid < RNNT_D) { hs[0][tid] = ldg1(pool + tid); cs[tid] = ldg1(pool + RNNT_D + tid); }
+    if (tid < RNNT_D) {
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const float* pool = p.pool + (long long)(r0 + (g < cnt ? g : 0)) * 1024;
+            hs[g][tid] = ldg1(pool + tid);
+            cs[g][tid] = ldg1(pool + RNNT_D + tid);
+        }
+    }
     __syncthreads();
-    dec_matvec<1, NTH>(p.whh, 4 * RNNT_D, hs, [&](int n, const float* acc) {                       // predictor.forward_step (predictor.py:185-210)
-        gates[n] = acc[0] + ldg1(p.egate + (long long)tok * (4 * RNNT_D) + n);
+    dec_matvec<G, NTH>(p.whh, 4 * RNNT_D, hs, [&](int n, const float* acc) {                       // predictor.forward_step (predictor.py:185-210)
+#pragma unroll
+        for (int g = 0; g < G; ++g) gates[g][n] = acc[g] + ldg1(p.egate + (long long)tok[g] * (4 * RNNT_D) + n);
     });
     __syncthreads();
     if (tid < RNNT_D) {
-        const float4 gt = *reinterpret_cast<const float4*>(&gates[4 * tid]);
-        const float cc = sigmoidf_(gt.y) * cs[tid] + sigmoidf_(gt.x) * tanhf(gt.z);
-        const float hh = sigmoidf_(gt.w) * tanhf(cc);
-        h2[0][tid] = hh;
-        stg1(pool + 512 + tid, hh);
-        stg1(pool + 512 + RNNT_D + tid, cc);
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const float4 gt = *reinterpret_cast<const float4*>(&gates[g][4 * tid]);
+            const float cc = sigmoidf_(gt.y) * cs[g][tid] + sigmoidf_(gt.x) * tanhf(gt.z);
+            const float hh = sigmoidf_(gt.w) * tanhf(cc);
+            h2[g][tid] = hh;
+            if (g < cnt) {
+                float* pool = p.pool + (long long)(r0 + g) * 1024;
+                stg1(pool + 512 + tid, hh);
+                stg1(pool + 512 + RNNT_D + tid, cc);
+            }
+        }
     }
     __syncthreads();
-    dec_matvec<1, NTH>(p.wpr, RNNT_D, h2, [&](int n, const float* acc) { pr[0][n] = acc[0] + ldg1(p.bpr + n); });   // predictor.projection
-    __syncthreads();
-    dec_matvec<1, NTH>(p.wpf, RNNT_D, pr, [&](int n, const float* acc) {                           // joint (joint.py:54-66)
-        zs[0][n] = tanhf(acc[0] + ldg1(p.bpf + n) + ldg1(enc + n));
+    dec_matvec<G, NTH>(p.wpr, RNNT_D, h2, [&](int n, const float* acc) {                           // predictor.projection
+#pragma unroll
+        for (int g = 0; g < G; ++g) pr[g][n] = acc[g] + ldg1(p.bpr + n);
     });
     __syncthreads();
-    dec_matvec<1, NTH>(p.wout, p.vocab, zs, [&](int n, const float* acc) { lg[n] = acc[0] + ldg1(p.bout + n); });
+    dec_matvec<G, NTH>(p.wpf, RNNT_D, pr, [&](int n, const float* acc) {                           // joint (joint.py:54-66)
+#pragma unroll
+        for (int g = 0; g < G; ++g) zs[g][n] = tanhf(acc[g] + ldg1(p.bpf + n) + ldg1(enc + n));
+    });
     __syncthreads();
-    if (tid >= 64) return;                                          // no barrier below
-    const int lane = tid;
+    dec_matvec<G, NTH>(p.wout, p.vocab, zs, [&](int n, const float* acc) {
+#pragma unroll
+        for (int g = 0; g < G; ++g) lg[g][n] = acc[g] + ldg1(p.bout + n);
+    });
+    __syncthreads();
+    const int w = tid >> 6, lane = tid & 63;
+    if (w >= cnt) return;                                           // no barrier below; wave w: hypothesis w of the group
+    const int r = r0 + w;
     const float* ctc = p.ctc ? p.ctc + fr * p.vocab : nullptr;
     float v[8];
     float mx = -INFINITY;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int idx = lane + 64 * j;
-        v[j] = idx < p.vocab ? lg[idx] : -INFINITY;
+        v[j] = idx < p.vocab ? lg[w][idx] : -INFINITY;
         mx = fmaxf(mx, v[j]);
     }
     mx = wave_max(mx);
@@ -110,6 +141,13 @@ __global__ __launch_bounds__(512) void prefix_step(PrefixStepP p) {
     }
 }
 
+// the batch form: one workgroup per fixed row b * beam + i
+__global__ __launch_bounds__(512) void prefix_step(PrefixStepP p) {
+    const int r = blockIdx.x, b = r / p.beam, i = r - b * p.beam;
+    if (i >= ldgi(p.nh + b) || p.f >= ldgi(p.lens + b)) return;    // whole workgroup: before the first barrier
+    prefix_step_rows<1>(p, r, 1, (long long)b * p.T + p.f);
+}
+
 struct PrefixMergeP {
     const float* pool_in; float* pool_out;      // [rows][2][512]; pool_in == nullptr: no state gather (rnnt_prefix_merge_device)
     const int* tk_in; int* tk_out;              // [rows][lcap]
@@ -119,7 +157,7 @@ struct PrefixMergeP {
     int* nh;                                    // [B] hypotheses per utterance (read, then rewritten)
     const int* lens;                            // [B] frames per utterance
     const float* top_lp; const int* top_tok;    // [rows][k]
-    int* src_row; int* src_slot;                // [rows] where each survivor's state came from (hypothesis index, slot)
+    int* src_row; int* src_slot;                // [rows] where each survivor's state came from (hypothesis index, slot); both null: not wanted
     int lcap, k, beam, blank, f;
 };
 
@@ -139,7 +177,9 @@ __host__ __device__ inline double prefix_log_add(double a, double b) {
 //   order       stable descending sort of the survivors: repeated block-wide argmax, ties to the lower candidate index
 //   truncation  to `beam`; tokens, hashes and states gathered into rows row0 + a of the other set
 // An utterance past its last frame (f >= lens[b]) is carried over unchanged.
-__global__ __launch_bounds__(PB_NT) void prefix_merge(PrefixMergeP p) {
+// prefix_merge_rows: the merge of the utterance whose hypothesis count is nh[u] (and frame count lens[u], when lens is given) and
+// whose rows start at row0 of either set; one workgroup.  Called by the batch kernel and by the pool kernel.
+__device__ __forceinline__ void prefix_merge_rows(const PrefixMergeP& p, int u, int row0) {
     __shared__ double sc[PB_MAX_CAND];
     __shared__ unsigned long long hsh[PB_MAX_CAND];
     __shared__ int clen[PB_MAX_CAND], ctok[PB_MAX_CAND], first[PB_MAX_CAND], rep[PB_MAX_CAND];
@@ -148,9 +188,9 @@ __global__ __launch_bounds__(PB_NT) void prefix_merge(PrefixMergeP p) {
     __shared__ double red_v[PB_NT / 64];
     __shared__ int red_i[PB_NT / 64];
     __shared__ int s_best;
-    const int tid = threadIdx.x, b = blockIdx.x, row0 = b * p.beam;
-    const int nh = p.nh[b];
-    if (p.lens && p.f >= p.lens[b]) {                                // finished: carry the rows over unchanged
+    const int tid = threadIdx.x;
+    const int nh = p.nh[u];
+    if (p.lens && p.f >= p.lens[u]) {                                // finished: carry the rows over unchanged
         for (int i = 0; i < nh; ++i) {
             const int r = row0 + i, len = p.len_in[r];
             for (int q = tid; q < len; q += PB_NT) p.tk_out[(long long)r * p.lcap + q] = p.tk_in[(long long)r * p.lcap + q];
@@ -244,12 +284,13 @@ __global__ __launch_bounds__(PB_NT) void prefix_merge(PrefixMergeP p) {
             p.len_out[nr] = len;
             p.sc_out[nr] = sc[c];
             p.hs_out[nr] = hsh[c];
-            p.src_row[nr] = j;
-            p.src_slot[nr] = slot;
+            if (p.src_row) { p.src_row[nr] = j; p.src_slot[nr] = slot; }
         }
     }
-    if (tid == 0) p.nh[b] = n_acc;
+    if (tid == 0) p.nh[u] = n_acc;
 }
+
+__global__ __launch_bounds__(PB_NT) void prefix_merge(PrefixMergeP p) { prefix_merge_rows(p, blockIdx.x, blockIdx.x * p.beam); }
 
 // Start of a call: every utterance holds the one hypothesis [blank] with score 0 and the zero LSTM state (:68-77) in set 0.
 __global__ __launch_bounds__(256) void prefix_init(float* pool, int* tk, int* len, double* sc, unsigned long long* hs, int* nh, int beam,
@@ -286,5 +327,91 @@ __global__ __launch_bounds__(256) void prefix_pack(const float* pool, const int*
         out[r] = live ? sc[r] : 0.0;
         o_len[r] = n;
         if (i == 0) oi[b] = nh[b];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Stream pool (rnnt_pool_prefix_frames / rnnt_pool_chunk_prefix): every slot keeps its search in HBM between calls, in FIXED rows --
+// hypothesis i of slot b is row b * PB_MAX_BEAM + i (the stride is the largest beam, not the slot's) of two buffer sets (token
+// lists [rows][lcap], lengths, f64 scores, hashes, states [rows][2][512]) plus nh[slot].  Slots advance independently, so which set
+// is current is per slot: cur0[a] at the call's first frame for active row a (host bookkeeping, sent with the call's table),
+// flipped once per frame.  A launch covers the ACTIVE slots only; idle slots are neither read nor written.  The frames of a call
+// are compact: row a * t + f of encp / ctc is frame f of active row a.
+// ------------------------------------------------------------------------------------------------
+struct PrefixPoolP {
+    const int* slots;            // [n] slot of active row a
+    const int* cur0;             // [n] current buffer set of that slot at frame 0 of the call
+    float* pool[2];
+    int* tk[2]; int* len[2];
+    double* sc[2];
+    unsigned long long* hs[2];
+    int* nh;                     // [slots]
+};
+constexpr int PB_GROUP = 4;      // hypotheses of one slot per workgroup of the grouped prefix_step_pool: one pass over the weights for all of them
+
+// prefix_step for the live hypotheses of the active slots at frame p.f of the call: workgroup -> (active row a, group of G rows); p
+// carries the weights, the call's frames (T = frames per active row), top_lp / top_tok [all rows][k] and the scalars, the state
+// pointers come from the slot's current set.  G = PB_GROUP: ~44 KB LDS, a quarter of the weight traffic; G = 1: the batch kernel's
+// shape.  Both give the same bits (prefix_step_rows); the host picks by the size of the launch.
+template <int G>
+__global__ __launch_bounds__(512) void prefix_step_pool(PrefixStepP p, PrefixPoolP q, int groups) {
+    const int a = blockIdx.x / groups, i0 = (blockIdx.x - a * groups) * G;
+    const int slot = ldgi(q.slots + a), nh = ldgi(q.nh + slot);
+    if (i0 >= nh) return;                                          // no hypothesis in this group: before the first barrier
+    const int cur = (ldgi(q.cur0 + a) + p.f) & 1;
+    p.pool = q.pool[cur]; p.tk = q.tk[cur]; p.len = q.len[cur];
+    prefix_step_rows<G>(p, slot * PB_MAX_BEAM + i0, min(G, nh - i0), (long long)a * p.T + p.f);
+}
+
+// prefix_merge for one ACTIVE slot per workgroup: from the slot's current set into its other one.  p carries prefix_step_pool's
+// outputs and the call's scalars (lens = nullptr: the slot has this frame); its buffer pointers are set here.
+__global__ __launch_bounds__(PB_NT) void prefix_merge_pool(PrefixMergeP p, PrefixPoolP q) {
+    const int a = blockIdx.x, slot = ldgi(q.slots + a);
+    const int cur = (ldgi(q.cur0 + a) + p.f) & 1, nxt = cur ^ 1;
+    p.pool_in = q.pool[cur]; p.pool_out = q.pool[nxt];
+    p.tk_in = q.tk[cur]; p.tk_out = q.tk[nxt];
+    p.len_in = q.len[cur]; p.len_out = q.len[nxt];
+    p.sc_in = q.sc[cur]; p.sc_out = q.sc[nxt];
+    p.hs_in = q.hs[cur]; p.hs_out = q.hs[nxt];
+    p.nh = q.nh;
+    prefix_merge_rows(p, slot, slot * PB_MAX_BEAM);
+}
+
+// The reset of slots [slot0, slot0 + gridDim.x): prefix_init's start (hypothesis [blank], score 0, zero state) in set 0; the host's
+// set index goes to 0 with it.  Touches no other slot.
+__global__ __launch_bounds__(256) void prefix_init_pool(PrefixPoolP q, int slot0, int lcap, int blank) {
+    const int slot = slot0 + blockIdx.x, r = slot * PB_MAX_BEAM;
+    for (int e = threadIdx.x; e < 512; e += 256) q.pool[0][(long long)r * 1024 + e] = 0.f;
+    if (threadIdx.x == 0) {
+        q.tk[0][(long long)r * lcap] = blank;
+        q.len[0][r] = 1;
+        q.sc[0][r] = 0.0;
+        q.hs[0][r] = beam_hash_step(BEAM_HASH0, blank);
+        q.nh[slot] = 1;
+    }
+}
+
+// One slot's set `cur` into ONE block for one download (rnnt_stream_get_prefix), one workgroup per row i < beam: scores f64 [beam] |
+// n_hyp | lengths [beam] | tokens [beam][ocap] | h [beam][256] | c [beam][256] (states only if with_states).  Rows without a
+// hypothesis are zero.  ocap >= every length (1 + the frames walked).
+__global__ __launch_bounds__(256) void prefix_pack_pool(PrefixPoolP q, int slot, int cur, int beam, int lcap, int ocap, int with_states, double* out) {
+    const int i = blockIdx.x, r = slot * PB_MAX_BEAM + i, tid = threadIdx.x;
+    int* oi = reinterpret_cast<int*>(out + beam);
+    int* o_len = oi + 1;
+    int* o_tk = o_len + beam;
+    float* o_h = reinterpret_cast<float*>(o_tk + (long long)beam * ocap);
+    float* o_c = o_h + (long long)beam * RNNT_D;
+    const int nh = q.nh[slot];
+    const bool live = i < nh;
+    const int n = live ? min(q.len[cur][r], ocap) : 0;
+    for (int e = tid; e < ocap; e += 256) o_tk[(long long)i * ocap + e] = e < n ? q.tk[cur][(long long)r * lcap + e] : 0;
+    if (with_states) {
+        o_h[(long long)i * RNNT_D + tid] = live ? q.pool[cur][(long long)r * 1024 + tid] : 0.f;
+        o_c[(long long)i * RNNT_D + tid] = live ? q.pool[cur][(long long)r * 1024 + RNNT_D + tid] : 0.f;
+    }
+    if (tid == 0) {
+        out[i] = live ? q.sc[cur][r] : 0.0;
+        o_len[i] = n;
+        if (i == 0) oi[0] = nh;
     }
 }

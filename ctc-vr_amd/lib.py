@@ -69,6 +69,10 @@ SIGNATURES = {
     "rnnt_pool_ctc_prefix_logprobs": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "rnnt_pool_chunk_ctc_prefix": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32p, c_vp]),
     "rnnt_stream_get_ctc_prefix": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32p, c_vp]),
+    "rnnt_stream_prefix_reset": (c_i32, [c_vp, c_i32, c_vp]),
+    "rnnt_pool_prefix_frames": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, ctypes.c_float, ctypes.c_float, c_vp]),
+    "rnnt_pool_chunk_prefix": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, ctypes.c_float, ctypes.c_float, c_i32p, c_vp]),
+    "rnnt_stream_get_prefix": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rnnt_transducer_nll": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "rnnt_ctc_nll": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "rnnt_transducer_nll_nbest": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
@@ -307,7 +311,8 @@ class RnntEngine:
     """One context = one GPU = up to `max_streams` streams: lock-stepped (encoder_chunk / encoder_chunks / decode_ragged), or the
     slots of a stream pool that open, advance and close independently (stream_open / pool_chunk / stream_tokens, and per-slot beam
     search through pool_chunk_beam / stream_beam / stream_beam_states, per-slot CTC prefix beam search with hot words through
-    pool_chunk_ctc_prefix / pool_ctc_prefix_logprobs / stream_ctc_prefix / stream_ctc_prefix_reset, audio in per slot through
+    pool_chunk_ctc_prefix / pool_ctc_prefix_logprobs / stream_ctc_prefix / stream_ctc_prefix_reset, the transducer prefix beam search per
+    slot through pool_chunk_prefix / pool_prefix_frames / stream_prefix / stream_prefix_reset, audio in per slot through
     pool_wave / wave_state / stream_wave_reset)."""
 
     def __init__(self, max_streams=1, max_chunk_frames=64, max_cache_frames=1024, max_enc_frames=1024, max_tokens=4096,
@@ -678,6 +683,49 @@ class RnntEngine:
                                                       ctypes.byref(frames), stream), "rnnt_stream_get_ctc_prefix")
         hyps = _ctc_prefix_hyps(out)[0]
         return (hyps, out, frames.value) if raw else hyps
+
+    # ---- the transducer prefix beam search per slot of the stream pool ----------------------------------
+    def stream_prefix_reset(self, slot=-1, stream=None):
+        """rnnt_stream_prefix_reset: the start hypothesis [blank] for one slot's transducer prefix search (-1: all slots)."""
+        self._chk(self.lib.rnnt_stream_prefix_reset(self.ctx, slot, stream), "rnnt_stream_prefix_reset")
+
+    def pool_prefix_frames(self, slots, enc_ptr, t, beam_size=5, ctc_weight=0.3, transducer_weight=0.7, stream=None):
+        """rnnt_pool_prefix_frames: advance the prefix beam searches of the listed slots by t encoder frames [len(slots), t, 256] on
+        the device; two launches per frame, no synchronisation."""
+        a = np.ascontiguousarray(slots, np.int32)
+        assert a.ndim == 1
+        self._chk(self.lib.rnnt_pool_prefix_frames(self.ctx, a.size, _np_ptr(a), enc_ptr, t, beam_size, ctc_weight, transducer_weight, stream),
+                  "rnnt_pool_prefix_frames")
+
+    def pool_chunk_prefix(self, slots, fbank_ptr, chunk_frames, offsets, required, beam_size=5, ctc_weight=0.3, transducer_weight=0.7, stream=None):
+        """rnnt_pool_chunk_prefix: pool_chunk's encoder for the listed slots and their prefix beam searches advanced by the new frames;
+        the frames are consumed.  Does not synchronise (stream_prefix does).  Returns t'."""
+        a, o, r = (np.ascontiguousarray(v, np.int32) for v in (slots, offsets, required))
+        assert a.ndim == 1 and a.size == o.size == r.size
+        t = c_i32(0)
+        self._chk(self.lib.rnnt_pool_chunk_prefix(self.ctx, a.size, _np_ptr(a), fbank_ptr, chunk_frames, _np_ptr(o), _np_ptr(r), beam_size, ctc_weight,
+                                                  transducer_weight, ctypes.byref(t), stream), "rnnt_pool_chunk_prefix")
+        return t.value
+
+    def stream_prefix_size(self, slot):
+        """rnnt_stream_get_prefix's size query (host only): (beam, frames walked, bound on the longest token list) of one slot."""
+        need = np.zeros(3, np.int32)
+        self._chk(self.lib.rnnt_stream_get_prefix(self.ctx, slot, 0, 0, _np_ptr(need), None, None, None, None, None, None), "rnnt_stream_get_prefix")
+        return int(need[0]), int(need[1]), int(need[2])
+
+    def stream_prefix(self, slot, states=False, stream=None):
+        """rnnt_stream_get_prefix: [(tokens incl. the leading blank, score)] of one slot, best first, as they stand; with states also
+        (h, c), each [n_hyp, 256].  Sized by the library's size query first (a host-only call), so a read costs what it returns."""
+        w, _, cap = self.stream_prefix_size(slot)
+        nh, lens = np.zeros(1, np.int32), np.zeros(w, np.int32)
+        toks, sc = np.zeros((w, cap), np.int32), np.zeros(w, np.float64)
+        h = np.zeros((w, 256), np.float32) if states else None
+        c = np.zeros((w, 256), np.float32) if states else None
+        self._chk(self.lib.rnnt_stream_get_prefix(self.ctx, slot, w, cap, _np_ptr(nh), _np_ptr(lens), _np_ptr(toks), _np_ptr(sc),
+                                                  _np_ptr(h) if states else None, _np_ptr(c) if states else None, stream), "rnnt_stream_get_prefix")
+        n = int(nh[0])
+        hyps = [(toks[i, :lens[i]].tolist(), float(sc[i])) for i in range(n)]
+        return (hyps, h[:n], c[:n]) if states else hyps
 
     def pool_wave(self, slots, wave_ptr, n_samples, samples, final, out_ptr, cap_frames, sample_rate=16000, n_fft=1024, stream=None):
         """rnnt_pool_wave: the streaming feature front-end for the listed slots -- row i of the device tensor at wave_ptr

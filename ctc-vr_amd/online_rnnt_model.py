@@ -915,10 +915,10 @@ class StreamingBatch:
         return self.engine.tokens(_stream_ptr())
 
 
-_POOL_KINDS = ("greedy", "beam", "ctc_prefix")
+_POOL_KINDS = ("greedy", "beam", "ctc_prefix", "prefix")
 
 
-def pool_plan(queue, offsets, beams=None, ctc_prefix=None):
+def pool_plan(queue, offsets, beams=None, ctc_prefix=None, prefix=None):
     """The library calls of one StreamPool.step as a pure function (no GPU, no tensors).
 
     queue: [(slot, length)] in feed order, several entries per slot allowed; offsets: {slot: encoder offset so far}.
@@ -938,15 +938,23 @@ def pool_plan(queue, offsets, beams=None, ctc_prefix=None):
     the results above.  With it (an empty dict included) every call is (length, slots, offsets, beam_size, kind, use_context), kind
     one of "greedy" / "beam" / "ctc_prefix" -- an rnnt_pool_chunk, rnnt_pool_chunk_beam or rnnt_pool_chunk_ctc_prefix call -- with one
     (length, kind, beam size, use_context) class per call; inside a round the classes run in ascending (length, kind in that order,
-    beam size, use_context).  A slot listed in ctc_prefix is not looked up in beams."""
+    beam size, use_context).  A slot listed in ctc_prefix is not looked up in beams.
+
+    prefix: {slot: (beam size, ctc_weight, transducer_weight)} of the slots whose utterance runs the transducer prefix beam search, None
+    = no such slot and the results above.  With it (an empty dict included) every call is (length, slots, offsets, beam_size, kind,
+    use_context, weights): kind "prefix" is an rnnt_pool_chunk_prefix call with weights = (ctc_weight, transducer_weight), every other
+    kind is as above with weights None.  One (length, kind, beam size, use_context, weights) class per call -- slots with different
+    weights never share one -- in ascending order inside a round.  A slot listed in prefix is looked up in neither ctc_prefix nor beams."""
     offs = dict(offsets)
 
     def klass(slot, length):
+        if prefix is not None and slot in prefix:
+            return int(length), 3, int(prefix[slot][0]), 0, float(prefix[slot][1]), float(prefix[slot][2])
         if ctc_prefix is not None and slot in ctc_prefix:
-            return int(length), 2, int(ctc_prefix[slot][0]), int(bool(ctc_prefix[slot][1]))
+            return int(length), 2, int(ctc_prefix[slot][0]), int(bool(ctc_prefix[slot][1])), 0.0, 0.0
         beam = int(beams.get(slot, 0)) if beams else 0
-        return int(length), 1 if beam > 0 else 0, beam, 0
-    rounds: List[Dict[Tuple[int, int, int, int], List[Tuple[int, int]]]] = []   # round -> (length, kind, beam, use_context) -> [(slot, queue index)]
+        return int(length), 1 if beam > 0 else 0, beam, 0, 0.0, 0.0
+    rounds: List[Dict[tuple, List[Tuple[int, int]]]] = []   # round -> (length, kind, beam, use_context, weights) -> [(slot, queue index)]
     depth: Dict[int, int] = {}
     index: List[Optional[Tuple[int, int]]] = [None] * len(queue)
     for k, (slot, length) in enumerate(queue):
@@ -959,14 +967,16 @@ def pool_plan(queue, offsets, beams=None, ctc_prefix=None):
         rounds[r].setdefault(klass(slot, length), []).append((slot, k))
     calls = []
     for rnd in rounds:
-        for length, kind, beam, use_context in sorted(rnd):
+        for length, kind, beam, use_context, cw, tw in sorted(rnd):
             slots, call_offs = [], []
-            for slot, k in rnd[(length, kind, beam, use_context)]:
+            for slot, k in rnd[(length, kind, beam, use_context, cw, tw)]:
                 index[k] = (len(calls), len(slots))
                 slots.append(slot)
                 call_offs.append(offs.get(slot, 0))
                 offs[slot] = offs.get(slot, 0) + length // 4
-            if ctc_prefix is not None:
+            if prefix is not None:
+                calls.append((length, slots, call_offs, beam, _POOL_KINDS[kind], bool(use_context), (cw, tw) if kind == 3 else None))
+            elif ctc_prefix is not None:
                 calls.append((length, slots, call_offs, beam, _POOL_KINDS[kind], bool(use_context)))
             else:
                 calls.append((length, slots, call_offs) if beams is None else (length, slots, call_offs, beam))
@@ -1041,13 +1051,18 @@ class StreamPool:
     Two-pass decoding: open(..., keep_frames=True) makes the slot keep its encoder frames on the device; rescore(slots, ctc_weight,
     transducer_weight) re-scores the n-best of CTC prefix slots with the transducer likelihood over their own frames in one library
     call (WeNet's transducer_attention_rescoring, per slot and mid-utterance if wanted), frames(slot) reads the frames and
-    token_times(slot) aligns a greedy slot's tokens over them."""
+    token_times(slot) aligns a greedy slot's tokens over them.
+    Transducer prefix beam search per slot: open(prefix_beam=k, ctc_weight=, transducer_weight=) gives the slot WeNet's CTC-fused
+    prefix beam search (rnnt_prefix_beam_decode's), carried across chunks on the device by rnnt_pool_chunk_prefix; prefix_hyps(slot)
+    reads the hypotheses as they stand, close(slot) returns the final ones -- those of the one-call search over the utterance's
+    frames -- and rescore() takes such a slot as the first pass of the reference's own two-pass recipe."""
 
     def __init__(self, state_dict, n_slots: int, vocab_size: int = 412, blank_id: int = 5, max_chunk_frames: int = 64,
                  max_cache_frames: int = 512, max_tokens: int = 4096, device: int = 0, numerics=None, packed=None, engine=None,
                  max_beam: int = 0, sample_rate: int = 16000, n_fft: int = 1024, chunk_frames: int = 16):
         """state_dict / packed: as StreamingBatch.  engine: an object with reset / stream_open / pool_chunk / stream_tokens (and
         pool_chunk_beam / stream_beam for beam slots, pool_chunk_ctc_prefix / stream_ctc_prefix / context_set for CTC prefix slots,
+        pool_chunk_prefix / stream_prefix for transducer prefix slots,
         stream_keep_frames / stream_frames / pool_rescore / transducer_align for slots that keep their frames)
         to drive instead of a new RnntEngine (a recording fake in the CPU tests).
         max_beam: the largest beam_size open() may be given (0: greedy only).
@@ -1081,6 +1096,7 @@ class StreamPool:
         self._beam: Dict[int, int] = {}                 # beam size of the open slots (0 = greedy)
         self._keep: Dict[int, bool] = {}                # keep_frames of the slot's last open()
         self._ctc: Dict[int, Tuple[int, Optional[ContextBias]]] = {}   # (beam, context) of the open CTC prefix slots
+        self._prefix: Dict[int, Tuple[int, float, float]] = {}   # (beam, ctc_weight, transducer_weight) of the open transducer prefix slots
         self._queue: List[Tuple[int, torch.Tensor]] = []
         self._carry: Dict[int, List[int]] = {}          # increments of other slots produced by the step inside a close()
         self._wave_queue: List[Tuple[int, torch.Tensor, bool]] = []   # PCM packets (slot, samples, final) in feed order
@@ -1093,7 +1109,8 @@ class StreamPool:
     def _stream(t):
         return _stream_ptr() if (t is None and torch.cuda.is_available()) or (t is not None and t.is_cuda) else None
 
-    def open(self, beam_size: int = 0, ctc_prefix_beam: int = 0, context: Optional[ContextBias] = None, keep_frames: bool = False) -> int:
+    def open(self, beam_size: int = 0, ctc_prefix_beam: int = 0, context: Optional[ContextBias] = None, keep_frames: bool = False,
+             prefix_beam: int = 0, ctc_weight: float = 0.3, transducer_weight: float = 0.7) -> int:
         """The lowest free slot, reset for a new utterance (reset_streaming_cache for that slot alone).  beam_size > 0: the slot's
         utterance is beam-searched with that beam (its hypotheses start as the one empty hypothesis); raises RnntError at once
         when this pool cannot do it.  ctc_prefix_beam > 0 (not together with beam_size): the slot's utterance runs the CTC prefix beam
@@ -1101,7 +1118,18 @@ class StreamPool:
         one is uploaded (context_set) unless another biased slot is still open, which raises RnntError.  A refused open() -- a
         graph the library rejects included (an empty phrase, the blank, a token outside the vocabulary) -- takes no slot.
         keep_frames: the slot keeps the encoder frames of its utterance on the device (rnnt_stream_keep_frames, max_cache_frames KB),
-        what frames(), rescore() and token_times() read."""
+        what frames(), rescore() and token_times() read.
+        prefix_beam > 0 (not together with beam_size or ctc_prefix_beam, and without context): the slot's utterance runs the
+        transducer prefix beam search with that beam and the fusion weights ctc_weight / transducer_weight (>= 0, not both 0)."""
+        if prefix_beam:
+            if beam_size or ctc_prefix_beam:
+                raise RnntError("stream pool: prefix_beam, beam_size and ctc_prefix_beam are mutually exclusive")
+            if context is not None:
+                raise RnntError("stream pool: context biases the CTC prefix search only (ctc_prefix_beam)")
+            if prefix_beam < 1 or prefix_beam > min(16, self.vocab_size) or self.vocab_size > 512:
+                raise RnntError(f"stream pool: prefix_beam {prefix_beam} outside [1, min(16, vocabulary {self.vocab_size})] or vocabulary > 512")
+            if not ctc_weight >= 0 or not transducer_weight >= 0 or (ctc_weight == 0 and transducer_weight == 0):
+                raise RnntError(f"stream pool: weights {ctc_weight} / {transducer_weight} (negative, or both zero)")
         if ctc_prefix_beam:
             if beam_size:
                 raise RnntError("stream pool: beam_size and ctc_prefix_beam are mutually exclusive")
@@ -1127,6 +1155,8 @@ class StreamPool:
         self._keep[slot] = bool(keep_frames)
         if ctc_prefix_beam:
             self._ctc[slot] = (int(ctc_prefix_beam), context)
+        if prefix_beam:
+            self._prefix[slot] = (int(prefix_beam), float(ctc_weight), float(transducer_weight))
         self._offset[slot] = 0
         self._ntok[slot] = 0
         self._beam[slot] = int(beam_size)
@@ -1209,21 +1239,25 @@ class StreamPool:
         """Advance every slot that has chunks queued: one rnnt_pool_chunk call per chunk length of the greedy slots and one
         rnnt_pool_chunk_beam call per (chunk length, beam size) of the beam slots (pool_plan), the rows of a call gathered into one
         contiguous device tensor; CTC prefix slots likewise through one rnnt_pool_chunk_ctc_prefix call per (chunk length, beam size,
-        use_context).  Returns {slot: tokens emitted by this step} for the GREEDY slots that advanced; a beam slot's hypotheses are
-        read with beams(slot), a CTC prefix slot's with ctc_hyps(slot)."""
+        use_context), transducer prefix slots through one rnnt_pool_chunk_prefix call per (chunk length, beam size, weights).  Returns
+        {slot: tokens emitted by this step} for the GREEDY slots that advanced; a beam slot's hypotheses are read with beams(slot), a
+        CTC prefix slot's with ctc_hyps(slot), a transducer prefix slot's with prefix_hyps(slot)."""
         out, self._carry = self._carry, {}
         if self._wave_queue:
             self._wave_step()
         if not self._queue:
             return out
         calls, offs, index = pool_plan([(slot, c.size(0)) for slot, c in self._queue], self._offset, self._beam,
-                                       {slot: (b, c is not None) for slot, (b, c) in self._ctc.items()})
+                                       {slot: (b, c is not None) for slot, (b, c) in self._ctc.items()}, self._prefix)
         rows: List[List[Optional[torch.Tensor]]] = [[None] * len(call[1]) for call in calls]
         for (slot, c), at in zip(self._queue, index):
             rows[at[0]][at[1]] = c
         touched = []
-        for (length, slots, call_offs, beam, kind, use_context), chunks in zip(calls, rows):
+        for (length, slots, call_offs, beam, kind, use_context, weights), chunks in zip(calls, rows):
             x = torch.stack(chunks, 0).contiguous()
+            if kind == "prefix":
+                self.engine.pool_chunk_prefix(slots, x.data_ptr(), length, call_offs, call_offs, beam, weights[0], weights[1], self._stream(x))
+                continue
             if kind == "ctc_prefix":
                 self.engine.pool_chunk_ctc_prefix(slots, x.data_ptr(), length, call_offs, call_offs, beam, use_context, self._stream(x))
                 continue
@@ -1255,6 +1289,13 @@ class StreamPool:
             raise RnntError(f"slot {slot} is not an open CTC prefix slot")
         return [(tok, score, times) for tok, score, times, _ in self.engine.stream_ctc_prefix(slot, final, stream=self._stream(None))]
 
+    def prefix_hyps(self, slot: int):
+        """[(tokens including the leading blank, score)] of a transducer prefix slot, best first, as they stand after the chunks
+        stepped so far.  Reading changes nothing."""
+        if slot not in self._prefix:
+            raise RnntError(f"slot {slot} is not an open transducer prefix slot")
+        return self.engine.stream_prefix(slot, stream=self._stream(None))
+
     def _require_kept(self, slot: int):
         if slot not in self._offset or not self._keep.get(slot, False):
             raise RnntError(f"slot {slot} is not an open slot that keeps its frames (open(keep_frames=True))", ERR_STATE)
@@ -1266,20 +1307,23 @@ class StreamPool:
         return self.engine.stream_frames(slot, 0, self._stream(None))
 
     def rescore(self, slots: List[int], ctc_weight: float, transducer_weight: float):
-        """The second pass for CTC prefix slots opened with keep_frames=True: per slot ctc_hyps(final=True), then ONE
+        """The second pass for CTC prefix and transducer prefix slots opened with keep_frames=True: per slot ctc_hyps(final=True) --
+        or prefix_hyps with the leading blank dropped and the search's score as the first score, the reference's default first pass
+        (beam_search_type="transducer", wenet/transducer/transducer.py:327) --, then ONE
         rnnt_pool_rescore call for all listed slots -- every hypothesis re-scored with the transducer likelihood over the slot's kept
         frames -- then the choice of rnnt_rescore_select_host with total = ctc_score * ctc_weight + td_score * transducer_weight.
         Returns {slot: (best_index, [(tokens, ctc_score, td_score, total)])} in the search's order.  Only reads the slots: their
         searches go on, so partial results may be re-scored mid-utterance (queued chunks are not in them: step() first)."""
         slots = [int(x) for x in slots]
         for slot in slots:
-            if slot not in self._ctc:
-                raise RnntError(f"slot {slot} is not an open CTC prefix slot")
+            if slot not in self._ctc and slot not in self._prefix:
+                raise RnntError(f"slot {slot} is not an open CTC prefix or transducer prefix slot")
             self._require_kept(slot)
-        first = [self.ctc_hyps(slot, final=True) for slot in slots]
-        nh, hl, ht = pack_nbest([[tok for tok, _, _ in row] for row in first])
+        first = [[(tok[1:], sc) for tok, sc in self.prefix_hyps(slot)] if slot in self._prefix else
+                 [(tok, sc) for tok, sc, _ in self.ctc_hyps(slot, final=True)] for slot in slots]
+        nh, hl, ht = pack_nbest([[tok for tok, _ in row] for row in first])
         nll = self.engine.pool_rescore(slots, nh, hl, ht, self._stream(None))
-        return {slot: select_rescored([tok for tok, _, _ in row], [sc for _, sc, _ in row], nll[i, :nh[i]], ctc_weight, transducer_weight)
+        return {slot: select_rescored([tok for tok, _ in row], [sc for _, sc in row], nll[i, :nh[i]], ctc_weight, transducer_weight)
                 for i, (slot, row) in enumerate(zip(slots, first))}
 
     def token_times(self, slot: int, frame_rate: float = 0.04):
@@ -1287,7 +1331,7 @@ class StreamPool:
         (rnnt_transducer_align) of its tokens over its kept frames, then timestamps_from_peaks of the emit frames with max_duration
         = the frames so far.  Raises RnntError beyond 255 tokens (the alignment's range)."""
         self._require_kept(slot)
-        if self._beam.get(slot, 0) > 0 or slot in self._ctc:
+        if self._beam.get(slot, 0) > 0 or slot in self._ctc or slot in self._prefix:
             raise RnntError(f"slot {slot} is not a greedy slot")
         s = self._stream(None)
         tokens = self.engine.stream_tokens(slot, 0, s)
@@ -1302,7 +1346,7 @@ class StreamPool:
 
     def close(self, slot: int):
         """Finish the slot's utterance (queued chunks are processed first) and free the slot; returns all its tokens (greedy slot),
-        its final hypotheses (beam slot) or ctc_hyps(slot, final=True) (CTC prefix slot)."""
+        its final hypotheses (beam slot), ctc_hyps(slot, final=True) (CTC prefix slot) or prefix_hyps(slot) (transducer prefix slot)."""
         if slot not in self._offset:
             raise RnntError(f"slot {slot} is not open")
         if self._fed.get(slot) == "wave" and not self._wave_final[slot]:
@@ -1311,7 +1355,10 @@ class StreamPool:
             self._carry = self.step()                   # the other slots' increments are handed out by the next step()
         self._carry.pop(slot, None)
         self._forget_wave(slot)
-        if slot in self._ctc:
+        if slot in self._prefix:
+            res = self.prefix_hyps(slot)
+            del self._prefix[slot]
+        elif slot in self._ctc:
             res = self.ctc_hyps(slot, final=True)
             del self._ctc[slot]
         else:

@@ -455,6 +455,50 @@ int rnnt_stream_get_ctc_prefix(rnnt_ctx* ctx, int32_t slot, int32_t final, int32
                                int32_t* lens_host, int32_t* tokens_host, int32_t* times_host, double* scores_host,
                                double* ctx_scores_host, int32_t* frames_out, void* stream);
 
+/* -- the transducer prefix beam search (rnnt_prefix_beam_decode) per slot of the stream pool, carried across calls ------------- */
+/* The search emits at most one symbol per frame and is frame-synchronous: its state at a frame boundary is the slot's <= 16
+ * hypotheses (token list, f64 score, hash, two LSTM states each).  The pool kernels run the frame step of rnnt_prefix_beam_decode
+ * (the same device functions) on rows that stay on the device between calls, so a search fed in pieces is, bit for bit, the B = 1
+ * one-call search over the same frames, whatever the split.  Per slot the device keeps 16 fixed rows of two buffer sets -- token lists
+ * of max_cache_frames + 1 ints, lengths, scores, hashes, states [2][512] f32 -- allocated on the first use (about 8 KB * 16 * 2 of
+ * states and 8 * 16 * (max_cache_frames + 1) bytes of tokens per slot), counted by rnnt_live_device_bytes.  A slot holds at most
+ * max_cache_frames frames.  A slot's search is fresh after a reset; its first advancing call fixes beam_size and the two weights
+ * until the next reset.  Every refusal is decided before the first launch and changes no slot's state, position or frame count.  A
+ * slot's greedy state, its RNN-T beam, its CTC prefix search and this search are independent of one another, and
+ * rnnt_prefix_beam_decode's own buffers are not touched; a library call holds slots of one kind.
+ *
+ * the start hypothesis [blank] (score 0, zero LSTM state) for one slot, or all slots with slot = -1.  rnnt_stream_open does this for
+ * its slot, rnnt_streams_reset for all (once the state exists). */
+int rnnt_stream_prefix_reset(rnnt_ctx* ctx, int32_t slot, void* stream);
+/* advance the searches of the listed slots (distinct, in [0, max_streams)) by t >= 1 encoder frames the caller holds: enc_dev
+ * [n_active, t, 256] f32 device (after_norm rows, as rnnt_prefix_beam_decode takes them), row i belongs to slot slots_host[i].
+ * joint.enc_ffn and, when ctc_weight > 0, rnnt_ctc_logprobs over the n_active * t rows (kernel choices of a small call), then per
+ * frame one prefix_step_pool launch (one hypothesis per workgroup, or -- once n_active * beam_size exceeds 1.5 workgroups per CU --
+ * up to 4 hypotheses of one slot per workgroup, one pass over the predictor and joint weights for all of them: the same bits either
+ * way; RNNT_PREFIX_GROUP=1 / 4 at rnnt_create forces one) and one prefix_merge_pool launch (one workgroup per active slot).  One async copy of the call's table, launches
+ * only, no synchronisation.
+ * RNNT_ERR_ARG: null pointer, duplicated or out-of-range slot, n_active outside [1, max_streams], t < 1, beam_size outside
+ * [1, min(16, vocab)], vocabulary > 512, a negative weight or both zero, beam_size or a weight differing from the search in progress.
+ * RNNT_ERR_SHAPE: a slot's frames so far + t > max_cache_frames.  RNNT_ERR_STATE: weights not finalized, or ctc_weight > 0 without
+ * ctc_head.ctc_lo.*. */
+int rnnt_pool_prefix_frames(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, const float* enc_dev, int32_t t, int32_t beam_size,
+                            float ctc_weight, float transducer_weight, void* stream);
+/* rnnt_pool_chunk for the listed slots (same arguments, validation, encoder launches, rnnt_stream_keep_frames history, position
+ * bookkeeping and refusals), then the search above over the n_active * t' new encoder frames (2 launches per frame).  Frames are
+ * consumed: one call = encode + (CTC) + search.  Does not synchronise.  Also RNNT_ERR_STATE when frames are still buffered. */
+int rnnt_pool_chunk_prefix(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, const float* fbank_dev, int32_t chunk_frames,
+                           const int32_t* offsets_host, const int32_t* required_host, int32_t beam_size, float ctc_weight,
+                           float transducer_weight, int32_t* frames_out, void* stream);
+/* the slot's hypotheses now, best first, layout and zero fill as rnnt_prefix_beam_decode for B = 1: lens / scores [cap_hyps], tokens
+ * [cap_hyps][cap_tokens] INCLUDING the leading blank, h / c [cap_hyps][256] (both or neither), *n_hyp the hypotheses held; cap_hyps >=
+ * the slot's beam (1 for a fresh slot), cap_tokens >= 1 + the frames walked.  Reading changes nothing: the search goes on afterwards.
+ * One pack launch (prefix_pack_pool), one download, synchronises.
+ * Size query: with lens_host, tokens_host, scores_host, h_host and c_host all NULL nothing is launched or copied and n_hyp receives
+ * THREE ints: the cap_hyps the slot needs (its beam, 1 for a fresh slot), the frames walked, and the cap_tokens it needs (a bound on
+ * the longest list: 1 + the frames walked).  cap_hyps / cap_tokens are ignored. */
+int rnnt_stream_get_prefix(rnnt_ctx* ctx, int32_t slot, int32_t cap_hyps, int32_t cap_tokens, int32_t* n_hyp, int32_t* lens_host,
+                           int32_t* tokens_host, double* scores_host, float* h_host, float* c_host, void* stream);
+
 /* The same search as a pure C++ function (no context, no GPU): lp_host [B, T, vocab], the graph passed as phrases (n_phrases == 0:
  * none).  The CPU seam the device path is compared against: tokens, times and order exact. */
 int rnnt_ctc_prefix_beam_host(const float* lp_host, const int32_t* enc_lens_host, int32_t B, int32_t T, int32_t vocab, int32_t blank,
@@ -661,7 +705,8 @@ const float* rnnt_enc_frames_dev(rnnt_ctx* ctx, int32_t* frames_out, int32_t* st
  * rnnt_transducer_nll, 41 its alpha recursion (and rnnt_ctc_nll's), 42 the Viterbi launch of the rnnt_*_align calls, 43 prefix_step
  * and 44 prefix_merge of rnnt_prefix_beam_decode (one launch each per frame), 45 ctc_prefix_search of the rnnt_ctc_prefix_beam_*
  * calls (one launch per call), 46 ctc_prefix_search_pool of rnnt_pool_ctc_prefix_logprobs / rnnt_pool_chunk_ctc_prefix (the resumable
- * search launch), 47 ctc_prefix_pack of rnnt_stream_get_ctc_prefix (the pack launch), 48 wave_stage of rnnt_pool_wave (the staging launch).
+ * search launch), 47 ctc_prefix_pack of rnnt_stream_get_ctc_prefix (the pack launch), 48 wave_stage of rnnt_pool_wave (the staging launch),
+ * 49 prefix_step_pool and 50 prefix_merge_pool of rnnt_pool_prefix_frames / rnnt_pool_chunk_prefix (one launch each per frame).
  * rnnt_profile_end synchronises the recorded events and returns the summed kernel time and launch count. */
 int rnnt_profile_begin(rnnt_ctx* ctx, int32_t tag);
 int rnnt_profile_end(rnnt_ctx* ctx, double* total_ms, int64_t* n_launches);
