@@ -1,22 +1,24 @@
 // C ABI: WeNet's CTC-fused transducer prefix beam search (wenet/transducer/search/prefix_beam_search.py:42-148) per slot of the stream
 // pool, carried across calls (rnnt_stream_prefix_reset, rnnt_pool_prefix_frames, rnnt_stream_get_prefix; rnnt_pool_chunk_prefix is in
-// api_pool.hip.inc with the other encoder forms).  Included by rnnt_api.hip inside extern "C".  Kernels: rnnt_prefix.hip.h.
+// api_pool.hip.inc with the other encoder forms; the _ctx forms add hot-word biasing by the graph of rnnt_context_set).  Included by rnnt_api.hip inside extern "C".  Kernels: rnnt_prefix.hip.h.
 //
 // The search emits at most one symbol per frame and is frame-synchronous: its whole state at a frame boundary is the <= 16 hypotheses
-// of the slot (token list, f64 score, hash, two LSTM states each).  The pool kernels run the frame step of rnnt_prefix_beam_decode
+// of the slot (token list, f64 score, hash, context state and score, two LSTM states each).  The pool kernels run the frame step of rnnt_prefix_beam_decode
 // (prefix_step_rows / prefix_merge_rows, the same code) on rows that stay in HBM between calls, so a search fed in pieces is bit for
 // bit the one-call search over the same frames, whatever the split.  Device state: rnnt_ctx::pp_*, rows slot * PB_MAX_BEAM + i of two
 // buffer sets, allocated on the first use.  Host state per slot: the current set (pp_cur), and the frames walked, the beam and the
-// two weights of the search in progress (PpSlot).
+// two weights, use_context and graph generation of the search in progress (PpSlot).
 //
-// Rules: a slot's search is fresh after a reset; its first advancing call fixes beam_size, ctc_weight and transducer_weight until the
-// next reset (other values: RNNT_ERR_ARG).  Every refusal is decided before the first launch and changes nothing.
+// Rules: a slot's search is fresh after a reset; its first advancing call fixes beam_size, ctc_weight, transducer_weight and
+// use_context until the next reset (other values: RNNT_ERR_ARG).  rnnt_context_set starts a new graph generation: a search biased
+// under an older one holds node ids of a graph that no longer exists and is refused (RNNT_ERR_STATE) until its slot is reset;
+// unbiased searches go on (the rule of api_pool_ctc.hip.inc).  Every refusal is decided before the first launch and changes nothing.
 
 namespace {
 
 std::vector<rnnt_ctx::PpSlot>& pool_prefix_slots(rnnt_ctx* ctx) {
     if (ctx->pp_slot.empty()) {
-        ctx->pp_slot.assign((size_t)ctx->cfg.max_streams, rnnt_ctx::PpSlot{0, 0, 0.f, 0.f});
+        ctx->pp_slot.assign((size_t)ctx->cfg.max_streams, rnnt_ctx::PpSlot{0, 0, 0.f, 0.f, 0, 0});
         ctx->pp_cur.assign((size_t)ctx->cfg.max_streams, 0);
     }
     return ctx->pp_slot;
@@ -37,6 +39,8 @@ int pool_prefix_alloc(rnnt_ctx* ctx, hipStream_t s, size_t frames, bool with_ctc
         if ((rc = reserve(ctx, ctx->pp_len[t], R))) return rc;
         if ((rc = reserve(ctx, ctx->pp_sc[t], R))) return rc;
         if ((rc = reserve(ctx, ctx->pp_hs[t], R))) return rc;
+        if ((rc = reserve(ctx, ctx->pp_cst[t], R))) return rc;
+        if ((rc = reserve(ctx, ctx->pp_cs[t], R))) return rc;
     }
     if ((rc = reserve(ctx, ctx->pp_toplp, R * PB_MAX_BEAM))) return rc;
     if ((rc = reserve(ctx, ctx->pp_toptok, R * PB_MAX_BEAM))) return rc;
@@ -51,7 +55,7 @@ int pool_prefix_alloc(rnnt_ctx* ctx, hipStream_t s, size_t frames, bool with_ctc
 
 // Everything that can refuse an advance of the listed slots by t frames, slot range and duplicates aside (rnnt_prefix_beam_decode's
 // range, then the slots' own); changes nothing.
-int pool_prefix_check(rnnt_ctx* ctx, const char* fn, int n, const int* slots, int t, int beam_size, float cw, float tw) {
+int pool_prefix_check(rnnt_ctx* ctx, const char* fn, int n, const int* slots, int t, int beam_size, float cw, float tw, int use_context) {
     const int V = ctx->cfg.vocab_size;
     if (!ctx->finalized) return fail(ctx, RNNT_ERR_STATE, "%s: weights not finalized", fn);
     if (t < 1) return fail(ctx, RNNT_ERR_ARG, "%s: %d frames", fn, t);
@@ -60,12 +64,16 @@ int pool_prefix_check(rnnt_ctx* ctx, const char* fn, int n, const int* slots, in
         return fail(ctx, RNNT_ERR_ARG, "%s: beam_size %d outside [1, min(%d, vocab %d)]", fn, beam_size, PB_MAX_BEAM, V);
     if (!(cw >= 0.f) || !(tw >= 0.f) || (cw == 0.f && tw == 0.f)) return fail(ctx, RNNT_ERR_ARG, "%s: weights %g / %g (negative, or both zero)", fn, cw, tw);
     if (cw > 0.f && !ctx->wctc) return fail(ctx, RNNT_ERR_STATE, "%s: ctc_weight > 0 and ctc_head.ctc_lo.* not loaded", fn);
+    if (use_context && !ctx->cg_on) return fail(ctx, RNNT_ERR_STATE, "%s: use_context without a context graph (rnnt_context_set)", fn);
     const std::vector<rnnt_ctx::PpSlot>& ps = pool_prefix_slots(ctx);
     for (int i = 0; i < n; ++i) {
         const rnnt_ctx::PpSlot& q = ps[slots[i]];
-        if (q.beam != 0 && (q.beam != beam_size || q.cw != cw || q.tw != tw))
-            return fail(ctx, RNNT_ERR_ARG, "%s: slot %d: beam_size %d / weights %g, %g differ from the search in progress (%d / %g, %g); reset the slot first", fn,
-                        slots[i], beam_size, cw, tw, q.beam, q.cw, q.tw);
+        if (q.beam != 0 && (q.beam != beam_size || q.cw != cw || q.tw != tw || (q.use_context != 0) != (use_context != 0)))
+            return fail(ctx, RNNT_ERR_ARG,
+                        "%s: slot %d: beam_size %d / weights %g, %g / use_context %d differ from the search in progress (%d / %g, %g / %d); reset the slot first", fn,
+                        slots[i], beam_size, cw, tw, use_context != 0, q.beam, q.cw, q.tw, q.use_context);
+        if (q.beam != 0 && q.use_context && q.gen != ctx->cg_gen)
+            return fail(ctx, RNNT_ERR_STATE, "%s: slot %d: the context graph changed since its search began; reset the slot first", fn, slots[i]);
         if ((long long)q.frames_done + t > ctx->cfg.max_cache_frames)
             return fail(ctx, RNNT_ERR_SHAPE, "%s: slot %d: %d + %d frames exceed max_cache_frames %d", fn, slots[i], q.frames_done, t, ctx->cfg.max_cache_frames);
     }
@@ -75,7 +83,7 @@ int pool_prefix_check(rnnt_ctx* ctx, const char* fn, int n, const int* slots, in
 // the frame loop: pool_prefix_check has passed, the state exists, pp_encp (and pp_ctc when cw > 0) hold the call's n * t compact rows
 // and slots_dev / cur0_dev [n] are on their way to the device.  Launches only, 2 per frame; then the host bookkeeping.
 int pool_prefix_launch(rnnt_ctx* ctx, hipStream_t s, int n, const int* slots, const int* slots_dev, const int* cur0_dev, int t, int beam_size, float cw,
-                       float tw) {
+                       float tw, int use_context) {
     PrefixStepP p;
     memset(&p, 0, sizeof(p));
     p.whh = ctx->whh_il; p.egate = ctx->egate; p.wpr = ctx->wpr; p.bpr = ctx->bpr; p.wpf = ctx->wpf; p.bpf = ctx->bpf;
@@ -85,6 +93,9 @@ int pool_prefix_launch(rnnt_ctx* ctx, hipStream_t s, int n, const int* slots, co
     PrefixMergeP m;
     memset(&m, 0, sizeof(m));
     m.top_lp = ctx->pp_toplp; m.top_tok = ctx->pp_toptok; m.lcap = p.lcap; m.k = beam_size; m.beam = beam_size; m.blank = ctx->cfg.blank_id;
+    CpGraph graph;
+    memset(&graph, 0, sizeof(graph));
+    if (use_context) graph = ctx_graph_dev(ctx);
     PrefixPoolP q = pool_prefix_params(ctx);
     q.slots = slots_dev; q.cur0 = cur0_dev;
     // One hypothesis per workgroup finishes a frame sooner while every workgroup gets a CU of its own; PB_GROUP hypotheses per
@@ -102,7 +113,8 @@ int pool_prefix_launch(rnnt_ctx* ctx, hipStream_t s, int n, const int* slots, co
         }
         {
             ProfScope prof(ctx, s, TAG_PREFIX_MERGE_POOL);
-            hipLaunchKernelGGL(prefix_merge_pool, dim3(n), dim3(PB_NT), 0, s, m, q);
+            if (use_context) hipLaunchKernelGGL(prefix_merge_pool_ctx, dim3(n), dim3(PB_NT), 0, s, m, q, graph);
+            else hipLaunchKernelGGL(prefix_merge_pool, dim3(n), dim3(PB_NT), 0, s, m, q);
             LAUNCHCHK("prefix_merge_pool");
         }
     }
@@ -110,7 +122,7 @@ int pool_prefix_launch(rnnt_ctx* ctx, hipStream_t s, int n, const int* slots, co
     for (int i = 0; i < n; ++i) {
         rnnt_ctx::PpSlot& r = ps[slots[i]];
         r.frames_done += t;
-        r.beam = beam_size; r.cw = cw; r.tw = tw;   // fixed by the first call; later ones passed the check with the same values
+        r.beam = beam_size; r.cw = cw; r.tw = tw; r.use_context = use_context != 0; r.gen = ctx->cg_gen;   // fixed by the first call; later ones passed the check with the same values
         ctx->pp_cur[slots[i]] ^= t & 1;
     }
     return RNNT_OK;
@@ -127,6 +139,11 @@ int rnnt_stream_prefix_reset(rnnt_ctx* ctx, int32_t slot, void* stream) {
 
 int rnnt_pool_prefix_frames(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, const float* enc_dev, int32_t t, int32_t beam_size,
                             float ctc_weight, float transducer_weight, void* stream) {
+    return rnnt_pool_prefix_frames_ctx(ctx, n_active, slots_host, enc_dev, t, beam_size, ctc_weight, transducer_weight, 0, stream);
+}
+
+int rnnt_pool_prefix_frames_ctx(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, const float* enc_dev, int32_t t, int32_t beam_size,
+                                float ctc_weight, float transducer_weight, int32_t use_context, void* stream) {
     const char* fn = "rnnt_pool_prefix_frames";
     if (!ctx) return RNNT_ERR_ARG;
     if (!slots_host || !enc_dev) return fail(ctx, RNNT_ERR_ARG, "%s: null argument", fn);
@@ -140,7 +157,7 @@ int rnnt_pool_prefix_frames(rnnt_ctx* ctx, int32_t n_active, const int32_t* slot
         seen[slot] = 1;
     }
     int rc;
-    if ((rc = pool_prefix_check(ctx, fn, n_active, slots_host, t, beam_size, ctc_weight, transducer_weight))) return rc;
+    if ((rc = pool_prefix_check(ctx, fn, n_active, slots_host, t, beam_size, ctc_weight, transducer_weight, use_context))) return rc;
     const size_t frames = (size_t)n_active * t;
     if (frames * 512 >= ((size_t)1 << 31)) return fail(ctx, RNNT_ERR_SHAPE, "%s: n_active=%d t=%d too large for one call", fn, n_active, t);
     hipStream_t s = (hipStream_t)stream;
@@ -158,11 +175,21 @@ int rnnt_pool_prefix_frames(rnnt_ctx* ctx, int32_t n_active, const int32_t* slot
         if ((rc = launch_gemm(ctx, s, &g, 1, TAG_ENC_PROJ))) return rc;
         if (with_ctc && (rc = rnnt_ctc_logprobs(ctx, enc_dev, (int)frames, ctx->pp_ctc, stream))) return rc;
     }
-    return pool_prefix_launch(ctx, s, n, slots_host, ctx->pp_tab, ctx->pp_tab + n, t, beam_size, ctc_weight, transducer_weight);
+    return pool_prefix_launch(ctx, s, n, slots_host, ctx->pp_tab, ctx->pp_tab + n, t, beam_size, ctc_weight, transducer_weight, use_context);
 }
 
 int rnnt_stream_get_prefix(rnnt_ctx* ctx, int32_t slot, int32_t cap_hyps, int32_t cap_tokens, int32_t* n_hyp, int32_t* lens_host, int32_t* tokens_host,
                            double* scores_host, float* h_host, float* c_host, void* stream) {
+    return rnnt_stream_get_prefix_ctx(ctx, slot, 0, cap_hyps, cap_tokens, n_hyp, lens_host, tokens_host, scores_host, nullptr, h_host, c_host, stream);
+}
+
+// The same for a biased search: scores_host are the totals (score + context score), ctx_scores_host [cap_hyps] (may be NULL) the
+// context part -- the running one, or with final != 0 finalize's, i.e. what rnnt_prefix_beam_decode_ctx would return had the utterance
+// ended here (no re-sort).  Reading changes nothing.  final != 0 on a search biased under an older graph generation: RNNT_ERR_STATE.
+// An unbiased slot reads as rnnt_stream_get_prefix does, with context scores 0; a fresh slot too, but with final != 0 and a graph set
+// it finalizes its root, as the one-call search over no frames does.
+int rnnt_stream_get_prefix_ctx(rnnt_ctx* ctx, int32_t slot, int32_t final, int32_t cap_hyps, int32_t cap_tokens, int32_t* n_hyp, int32_t* lens_host,
+                               int32_t* tokens_host, double* scores_host, double* ctx_scores_host, float* h_host, float* c_host, void* stream) {
     const char* fn = "rnnt_stream_get_prefix";
     if (!ctx) return RNNT_ERR_ARG;
     const bool query = !lens_host && !tokens_host && !scores_host && !h_host && !c_host;   // the sizes a read needs: host only
@@ -176,20 +203,24 @@ int rnnt_stream_get_prefix(rnnt_ctx* ctx, int32_t slot, int32_t cap_hyps, int32_
     }
     if (cap_hyps < beam) return fail(ctx, RNNT_ERR_ARG, "%s: beam %d, room for %d hypotheses", fn, beam, cap_hyps);
     if (cap_tokens < 1 + q.frames_done) return fail(ctx, RNNT_ERR_ARG, "%s: cap_tokens %d < 1 + %d frames", fn, cap_tokens, q.frames_done);
+    // finalize needs the graph the search ran under; a fresh slot has fixed none and finalizes its root under the graph that is set, if any
+    const bool biased = q.beam > 0 ? q.use_context != 0 : (final != 0 && ctx->cg_on), fin = biased && final != 0;
+    if (fin && q.beam > 0 && (!ctx->cg_on || q.gen != ctx->cg_gen))
+        return fail(ctx, RNNT_ERR_STATE, "%s: slot %d: the context graph changed since its search began (final = 0 still reads it)", fn, slot);
     hipStream_t s = (hipStream_t)stream;
     int rc;
     if ((rc = pool_prefix_alloc(ctx, s, 0, false))) return rc;
     const size_t R = (size_t)beam, ocap = (size_t)q.frames_done + 1, with_states = h_host ? 1 : 0;
-    const size_t out_bytes = R * sizeof(double) + sizeof(int) * (1 + R + R * ocap) + (with_states ? 2 * R * D * sizeof(float) : 0);
+    const size_t out_bytes = 2 * R * sizeof(double) + sizeof(int) * (1 + R + R * ocap) + (with_states ? 2 * R * D * sizeof(float) : 0);
     const size_t out_doubles = (out_bytes + sizeof(double) - 1) / sizeof(double);
     if ((rc = reserve(ctx, ctx->pp_out, out_doubles))) return rc;
     hipLaunchKernelGGL(prefix_pack_pool, dim3((unsigned)R), dim3(256), 0, s, pool_prefix_params(ctx), slot, ctx->pp_cur[slot], beam,
-                       ctx->cfg.max_cache_frames + 1, (int)ocap, (int)with_states, ctx->pp_out.p);
+                       ctx->cfg.max_cache_frames + 1, (int)ocap, (int)with_states, biased ? 1 : 0, fin ? ctx_graph_dev(ctx).nscore : nullptr, ctx->pp_out.p);
     LAUNCHCHK("prefix_pack_pool");
     std::vector<double> out(out_doubles);
     HIPCHK(hipMemcpyAsync(out.data(), ctx->pp_out, out_bytes, hipMemcpyDeviceToHost, s));                 // the download
     HIPCHK(hipStreamSynchronize(s));
-    const int* oi = reinterpret_cast<const int*>(out.data() + R);
+    const int* oi = reinterpret_cast<const int*>(out.data() + 2 * R);
     const int *o_len = oi + 1, *o_tk = o_len + R;
     const float* o_h = reinterpret_cast<const float*>(o_tk + R * ocap);
     const size_t H = (size_t)cap_hyps;
@@ -199,6 +230,10 @@ int rnnt_stream_get_prefix(rnnt_ctx* ctx, int32_t slot, int32_t cap_hyps, int32_
     std::fill(tokens_host, tokens_host + H * cap_tokens, 0);
     memcpy(lens_host, o_len, R * sizeof(int));
     memcpy(scores_host, out.data(), R * sizeof(double));
+    if (ctx_scores_host) {
+        std::fill(ctx_scores_host, ctx_scores_host + H, 0.0);
+        memcpy(ctx_scores_host, out.data() + R, R * sizeof(double));
+    }
     for (size_t r = 0; r < R; ++r) memcpy(tokens_host + r * cap_tokens, o_tk + r * ocap, (size_t)o_len[r] * sizeof(int));
     if (with_states) {
         std::fill(h_host, h_host + H * D, 0.f);

@@ -7,11 +7,21 @@
 // (log_add of the list [survivor, candidate] in double, the first one's tokens and state stay); stable descending sort;
 // truncation.  Hypotheses are passed flat: hyp_len[n_hyp], hyp_tokens (concatenated), hyp_score[n_hyp]; top_lp / top_tok
 // [n_hyp][k]; outputs likewise (out_tokens needs room for beam_size * (longest input + 1) ints).  Returns the number of survivors.
-int rnnt_prefix_merge_host(int32_t n_hyp, const int32_t* hyp_len, const int32_t* hyp_tokens, const double* hyp_score, const float* top_lp,
+//
+// With a context graph g (rnnt_prefix_merge_ctx_host; search.py:95-104,169-171,214-235 carried over to this frame step): hypothesis j
+// also holds a context state hyp_cst[j] and score hyp_cs[j]; a blank candidate copies them, any other token takes one
+// forward_one_step from the state and adds its score; fusion keeps the first candidate's (both are functions of the token sequence);
+// the sort key is score + context score.  out_score stays the fused score; out_cst / out_cs are the survivors' context state / score.
+namespace {
+int ctx_graph_build(int n_phrases, const int32_t* lens, const int32_t* tokens, double context_score, int vocab, int blank, CtxGraph& g,
+                    std::string& err);   // api_ctc_prefix.hip.inc
+
+int prefix_merge_host_impl(int32_t n_hyp, const int32_t* hyp_len, const int32_t* hyp_tokens, const double* hyp_score, const float* top_lp,
                            const int32_t* top_tok, int32_t k, int32_t blank, int32_t beam_size, int32_t* out_len, int32_t* out_tokens,
-                           double* out_score, int32_t* out_src_row, int32_t* out_src_slot) {
+                           double* out_score, int32_t* out_src_row, int32_t* out_src_slot, const CtxGraph* g, const int32_t* hyp_cst,
+                           const double* hyp_cs, int32_t* out_cst, double* out_cs) {
     if (n_hyp < 1 || k < 1 || beam_size < 1 || !hyp_len || !hyp_score || !top_lp || !top_tok || !out_len || !out_tokens || !out_score) return RNNT_ERR_ARG;
-    struct Cand { std::vector<int> tokens; double score; int row, slot; };
+    struct Cand { std::vector<int> tokens; double score; int row, slot; int cst; double cs; };
     std::vector<Cand> fused;
     size_t off = 0;
     for (int j = 0; j < n_hyp; ++j) {
@@ -20,8 +30,15 @@ int rnnt_prefix_merge_host(int32_t n_hyp, const int32_t* hyp_len, const int32_t*
         for (int t = 0; t < k; ++t) {
             const float sum = s32 + top_lp[(size_t)j * k + t];                      // :105, f32
             const int tok = top_tok[(size_t)j * k + t];
-            Cand c{std::vector<int>(hyp_tokens + off, hyp_tokens + off + hyp_len[j]), (double)sum, j, tok == blank ? 0 : 1};
+            Cand c{std::vector<int>(hyp_tokens + off, hyp_tokens + off + hyp_len[j]), (double)sum, j, tok == blank ? 0 : 1, 0, 0.0};
             if (tok != blank) c.tokens.push_back(tok);
+            if (g) {                                                                // copy_context / update_context
+                c.cst = hyp_cst[j];
+                c.cs = hyp_cs[j];
+                if (tok != blank)
+                    c.cs += cg_step(g->fail.data(), g->off.data(), g->ctok.data(), g->cid.data(), g->tscore.data(), g->nscore.data(), g->oscore.data(),
+                                    hyp_cst[j], tok, &c.cst);
+            }
             bool merged = false;
             for (Cand& f : fused)
                 if (f.tokens == c.tokens) {
@@ -33,7 +50,8 @@ int rnnt_prefix_merge_host(int32_t n_hyp, const int32_t* hyp_len, const int32_t*
         }
         off += hyp_len[j];
     }
-    std::stable_sort(fused.begin(), fused.end(), [](const Cand& a, const Cand& b) { return a.score > b.score; });
+    if (g) std::stable_sort(fused.begin(), fused.end(), [](const Cand& a, const Cand& b) { return a.score + a.cs > b.score + b.cs; });
+    else std::stable_sort(fused.begin(), fused.end(), [](const Cand& a, const Cand& b) { return a.score > b.score; });
     if ((int)fused.size() > beam_size) fused.resize(beam_size);
     off = 0;
     for (size_t a = 0; a < fused.size(); ++a) {
@@ -42,16 +60,44 @@ int rnnt_prefix_merge_host(int32_t n_hyp, const int32_t* hyp_len, const int32_t*
         out_score[a] = fused[a].score;
         if (out_src_row) out_src_row[a] = fused[a].row;
         if (out_src_slot) out_src_slot[a] = fused[a].slot;
+        if (out_cst) out_cst[a] = fused[a].cst;
+        if (out_cs) out_cs[a] = fused[a].cs;
     }
     return (int)fused.size();
+}
+}  // namespace
+
+int rnnt_prefix_merge_host(int32_t n_hyp, const int32_t* hyp_len, const int32_t* hyp_tokens, const double* hyp_score, const float* top_lp,
+                           const int32_t* top_tok, int32_t k, int32_t blank, int32_t beam_size, int32_t* out_len, int32_t* out_tokens,
+                           double* out_score, int32_t* out_src_row, int32_t* out_src_slot) {
+    return prefix_merge_host_impl(n_hyp, hyp_len, hyp_tokens, hyp_score, top_lp, top_tok, k, blank, beam_size, out_len, out_tokens, out_score, out_src_row,
+                                  out_src_slot, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+// The same with the graph over n_phrases token lists (as rnnt_ctc_prefix_beam_host takes them; tokens only need to be >= 0 here) and
+// the hypotheses' context states (node ids of that graph) and scores.  Returns the number of survivors.
+int rnnt_prefix_merge_ctx_host(int32_t n_hyp, const int32_t* hyp_len, const int32_t* hyp_tokens, const double* hyp_score, const int32_t* hyp_ctx_state,
+                               const double* hyp_ctx_score, const float* top_lp, const int32_t* top_tok, int32_t k, int32_t blank, int32_t beam_size,
+                               int32_t n_phrases, const int32_t* phrase_lens, const int32_t* phrase_tokens, double context_score, int32_t* out_len,
+                               int32_t* out_tokens, double* out_score, int32_t* out_src_row, int32_t* out_src_slot, int32_t* out_ctx_state,
+                               double* out_ctx_score) {
+    if (n_phrases < 1 || n_hyp < 1 || !hyp_ctx_state || !hyp_ctx_score || !out_ctx_state || !out_ctx_score) return RNNT_ERR_ARG;
+    CtxGraph g;
+    std::string err;
+    const int rc = ctx_graph_build(n_phrases, phrase_lens, phrase_tokens, context_score, -1, -1, g, err);
+    if (rc) return rc;
+    for (int j = 0; j < n_hyp; ++j)
+        if (hyp_ctx_state[j] < 0 || hyp_ctx_state[j] >= (int)g.token.size()) return RNNT_ERR_ARG;
+    return prefix_merge_host_impl(n_hyp, hyp_len, hyp_tokens, hyp_score, top_lp, top_tok, k, blank, beam_size, out_len, out_tokens, out_score, out_src_row,
+                                  out_src_slot, &g, hyp_ctx_state, hyp_ctx_score, out_ctx_state, out_ctx_score);
 }
 
 namespace {
 // The call's own buffers: rows = B * beam fixed rows, token lists of lcap ints, `frames` = B * T projected frames.
 struct PrefixBuf {
     float *encp, *ctc, *pool[2], *top_lp;
-    int *tk[2], *len[2], *nh, *lens, *top_tok, *src_row, *src_slot;
-    double* sc[2];
+    int *tk[2], *len[2], *nh, *lens, *top_tok, *src_row, *src_slot, *cst[2];
+    double *sc[2], *cs[2];
     unsigned long long* hs[2];
 };
 int prefix_buffers(rnnt_ctx* ctx, size_t B, size_t rows, size_t lcap, size_t frames, bool with_ctc, int k, PrefixBuf& o) {
@@ -71,7 +117,9 @@ int prefix_buffers(rnnt_ctx* ctx, size_t B, size_t rows, size_t lcap, size_t fra
         o.top_tok = i.take(rows * k);
         o.src_row = i.take(rows);
         o.src_slot = i.take(rows);
+        for (int*& q : o.cst) q = i.take(rows);
         for (double*& q : o.sc) q = d.take(rows);
+        for (double*& q : o.cs) q = d.take(rows);
         for (unsigned long long*& q : o.hs) q = reinterpret_cast<unsigned long long*>(d.take(rows));
     };
     lay();   // sizes
@@ -96,6 +144,21 @@ PrefixMergeP prefix_merge_params(const PrefixBuf& u, int t, bool states, int lca
     m.lcap = lcap; m.k = k; m.beam = beam; m.blank = blank; m.f = f;
     return m;
 }
+
+// the graph and set t's context rows; one prefix_merge launch, biased when g.fail != nullptr
+PrefixCtxP prefix_ctx_params(const PrefixBuf& u, int t, const CpGraph& g) {
+    PrefixCtxP x;
+    memset(&x, 0, sizeof(x));
+    x.g = g; x.cst_in = u.cst[t]; x.cst_out = u.cst[t ^ 1]; x.cs_in = u.cs[t]; x.cs_out = u.cs[t ^ 1];
+    return x;
+}
+int launch_prefix_merge(rnnt_ctx* ctx, hipStream_t s, int B, const PrefixMergeP& m, const PrefixBuf& u, int t, const CpGraph& g) {
+    ProfScope prof(ctx, s, TAG_PREFIX_MERGE);
+    if (g.fail) hipLaunchKernelGGL(prefix_merge_ctx, dim3(B), dim3(PB_NT), 0, s, m, prefix_ctx_params(u, t, g));
+    else hipLaunchKernelGGL(prefix_merge, dim3(B), dim3(PB_NT), 0, s, m);
+    LAUNCHCHK("prefix_merge");
+    return RNNT_OK;
+}
 }  // namespace
 
 // Prefix beam search of a padded batch in one call: joint.enc_ffn and the CTC log-probabilities of the B*T frames once, then per
@@ -105,6 +168,18 @@ PrefixMergeP prefix_merge_params(const PrefixBuf& u, int t, bool states, int lca
 int rnnt_prefix_beam_decode(rnnt_ctx* ctx, const float* enc_dev, const int32_t* enc_lens_host, int32_t B, int32_t T, int32_t beam_size,
                             float ctc_weight, float transducer_weight, int32_t cap_tokens, int32_t* n_hyp_host, int32_t* lens_host,
                             int32_t* tokens_host, double* scores_host, float* h_host, float* c_host, void* stream) {
+    return rnnt_prefix_beam_decode_ctx(ctx, enc_dev, enc_lens_host, B, T, beam_size, ctc_weight, transducer_weight, 0, cap_tokens, n_hyp_host, lens_host,
+                                       tokens_host, scores_host, nullptr, h_host, c_host, stream);
+}
+
+// The same with hot-word biasing by the graph of rnnt_context_set when use_context != 0 (none set: RNNT_ERR_STATE, before the first
+// launch): prefix_merge keeps a context state and score per hypothesis and orders by the total; at the end finalize replaces the
+// context scores (no re-sort, so the totals need not descend).  scores_host are the totals, ctx_scores_host [B, beam_size] (may be
+// NULL) their context part.  use_context == 0: the unbiased search, bit for bit, context scores 0.
+int rnnt_prefix_beam_decode_ctx(rnnt_ctx* ctx, const float* enc_dev, const int32_t* enc_lens_host, int32_t B, int32_t T, int32_t beam_size,
+                                float ctc_weight, float transducer_weight, int32_t use_context, int32_t cap_tokens, int32_t* n_hyp_host,
+                                int32_t* lens_host, int32_t* tokens_host, double* scores_host, double* ctx_scores_host, float* h_host, float* c_host,
+                                void* stream) {
     if (!ctx || !enc_dev || !enc_lens_host || !n_hyp_host || !lens_host || !tokens_host || !scores_host || (!h_host != !c_host))
         return fail(ctx, RNNT_ERR_ARG, "rnnt_prefix_beam_decode: null argument");
     if (!ctx->finalized) return fail(ctx, RNNT_ERR_STATE, "weights not finalized");
@@ -124,6 +199,7 @@ int rnnt_prefix_beam_decode(rnnt_ctx* ctx, const float* enc_dev, const int32_t* 
     if (cap_tokens < 1 + fmax) return fail(ctx, RNNT_ERR_ARG, "rnnt_prefix_beam_decode: cap_tokens %d < 1 + %d frames", cap_tokens, fmax);
     const bool with_ctc = ctc_weight > 0.f;
     if (with_ctc && !ctx->wctc) return fail(ctx, RNNT_ERR_STATE, "rnnt_prefix_beam_decode: ctc_weight > 0 and ctc_head.ctc_lo.* not loaded");
+    if (use_context && !ctx->cg_on) return fail(ctx, RNNT_ERR_STATE, "rnnt_prefix_beam_decode: use_context without a context graph (rnnt_context_set)");
     const size_t frames = (size_t)B * T, R = (size_t)B * beam_size, lcap = (size_t)fmax + 1;
     if (frames * 512 >= ((size_t)1 << 31) || R * lcap >= ((size_t)1 << 31))
         return fail(ctx, RNNT_ERR_SHAPE, "rnnt_prefix_beam_decode: B=%d T=%d beam=%d too large for one call", B, T, beam_size);
@@ -132,11 +208,15 @@ int rnnt_prefix_beam_decode(rnnt_ctx* ctx, const float* enc_dev, const int32_t* 
     int rc;
     PrefixBuf u;
     if ((rc = prefix_buffers(ctx, B, R, lcap, frames, with_ctc, k, u))) return rc;
-    const size_t out_bytes = R * sizeof(double) + sizeof(int) * ((size_t)B + R + R * lcap) + (with_states ? 2 * R * D * sizeof(float) : 0);
+    const size_t out_bytes = 2 * R * sizeof(double) + sizeof(int) * ((size_t)B + R + R * lcap) + (with_states ? 2 * R * D * sizeof(float) : 0);
     const size_t out_doubles = (out_bytes + sizeof(double) - 1) / sizeof(double);
     if ((rc = reserve(ctx, ctx->pb_out, out_doubles))) return rc;
+    CpGraph graph;
+    memset(&graph, 0, sizeof(graph));
+    if (use_context) graph = ctx_graph_dev(ctx);
     HIPCHK(hipMemcpyAsync(u.lens, enc_lens_host, B * sizeof(int), hipMemcpyHostToDevice, s));            // the upload
-    hipLaunchKernelGGL(prefix_init, dim3(B), dim3(256), 0, s, u.pool[0], u.tk[0], u.len[0], u.sc[0], u.hs[0], u.nh, beam_size, (int)lcap, blank);
+    hipLaunchKernelGGL(prefix_init, dim3(B), dim3(256), 0, s, u.pool[0], u.tk[0], u.len[0], u.sc[0], u.hs[0], u.cst[0], u.cs[0], u.nh, beam_size, (int)lcap,
+                       blank);
     LAUNCHCHK("prefix_init");
     if (fmax > 0) {   // once per call: joint.enc_ffn and log_softmax(ctc_lo(.)) over the B*T frames, with the kernel / tile choices of a
                       // small call whatever B is, so that an utterance's sums do not depend on the batch it is in
@@ -159,23 +239,20 @@ int rnnt_prefix_beam_decode(rnnt_ctx* ctx, const float* enc_dev, const int32_t* 
             hipLaunchKernelGGL(prefix_step, dim3((unsigned)R), dim3(512), 0, s, p);
             LAUNCHCHK("prefix_step");
         }
-        {
-            ProfScope prof(ctx, s, TAG_PREFIX_MERGE);
-            hipLaunchKernelGGL(prefix_merge, dim3(B), dim3(PB_NT), 0, s, prefix_merge_params(u, t, true, (int)lcap, k, beam_size, blank, f));
-            LAUNCHCHK("prefix_merge");
-        }
+        if ((rc = launch_prefix_merge(ctx, s, B, prefix_merge_params(u, t, true, (int)lcap, k, beam_size, blank, f), u, t, graph))) return rc;
         t ^= 1;
     }
-    hipLaunchKernelGGL(prefix_pack, dim3((unsigned)R), dim3(256), 0, s, u.pool[t], u.tk[t], u.len[t], u.sc[t], u.nh, B, beam_size, (int)lcap,
-                       with_states, ctx->pb_out);
+    hipLaunchKernelGGL(prefix_pack, dim3((unsigned)R), dim3(256), 0, s, u.pool[t], u.tk[t], u.len[t], u.sc[t], use_context ? u.cst[t] : nullptr, u.cs[t],
+                       graph.nscore, u.nh, B, beam_size, (int)lcap, with_states, ctx->pb_out.p);
     LAUNCHCHK("prefix_pack");
     std::vector<double> out(out_doubles);
     HIPCHK(hipMemcpyAsync(out.data(), ctx->pb_out, out_bytes, hipMemcpyDeviceToHost, s));                // the download
     HIPCHK(hipStreamSynchronize(s));
-    const int* oi = reinterpret_cast<const int*>(out.data() + R);
+    const int* oi = reinterpret_cast<const int*>(out.data() + 2 * R);
     const int *o_len = oi + B, *o_tk = o_len + R;
     const float* o_h = reinterpret_cast<const float*>(o_tk + R * lcap);
     memcpy(scores_host, out.data(), R * sizeof(double));
+    if (ctx_scores_host) memcpy(ctx_scores_host, out.data() + R, R * sizeof(double));
     memcpy(n_hyp_host, oi, B * sizeof(int));
     memcpy(lens_host, o_len, R * sizeof(int));
     for (size_t r = 0; r < R; ++r) memcpy(tokens_host + r * cap_tokens, o_tk + r * lcap, (size_t)o_len[r] * sizeof(int));
@@ -188,10 +265,20 @@ int rnnt_prefix_beam_decode(rnnt_ctx* ctx, const float* enc_dev, const int32_t* 
 
 // One prefix_merge launch on flat host inputs for ONE utterance (test seam against rnnt_prefix_merge_host): same arguments and
 // results.  Uses the prefix search's own buffers only; no LSTM state is gathered.  Synchronises.
-int rnnt_prefix_merge_device(rnnt_ctx* ctx, int32_t n_hyp, const int32_t* hyp_len, const int32_t* hyp_tokens, const double* hyp_score,
+namespace {
+int prefix_merge_device_impl(rnnt_ctx* ctx, int32_t n_hyp, const int32_t* hyp_len, const int32_t* hyp_tokens, const double* hyp_score,
                              const float* top_lp, const int32_t* top_tok, int32_t k, int32_t blank, int32_t beam_size, int32_t* out_len,
-                             int32_t* out_tokens, double* out_score, int32_t* out_src_row, int32_t* out_src_slot, void* stream) {
+                             int32_t* out_tokens, double* out_score, int32_t* out_src_row, int32_t* out_src_slot, void* stream, bool biased,
+                             const int32_t* hyp_cst, const double* hyp_cs, int32_t* out_cst, double* out_cs) {
     if (!ctx) return RNNT_ERR_ARG;
+    if (biased) {
+        if (!hyp_cst || !hyp_cs || !out_cst || !out_cs) return fail(ctx, RNNT_ERR_ARG, "rnnt_prefix_merge_ctx_device: null argument");
+        if (!ctx->cg_on) return fail(ctx, RNNT_ERR_STATE, "rnnt_prefix_merge_ctx_device: no context graph (rnnt_context_set)");
+        for (int i = 0; i < n_hyp && i < PB_MAX_BEAM; ++i)
+            if (hyp_cst[i] < 0 || hyp_cst[i] >= (int)ctx->cg.token.size())
+                return fail(ctx, RNNT_ERR_ARG, "rnnt_prefix_merge_ctx_device: hypothesis %d: context state %d outside the graph's %d nodes", i, hyp_cst[i],
+                            (int)ctx->cg.token.size());
+    }
     if (!hyp_len || !hyp_score || !top_lp || !top_tok || !out_len || !out_tokens || !out_score)
         return fail(ctx, RNNT_ERR_ARG, "rnnt_prefix_merge_device: null argument");
     if (n_hyp < 1 || n_hyp > PB_MAX_BEAM || k < 1 || k > PB_MAX_BEAM || beam_size < 1 || beam_size > PB_MAX_BEAM)
@@ -224,14 +311,26 @@ int rnnt_prefix_merge_device(rnnt_ctx* ctx, int32_t n_hyp, const int32_t* hyp_le
     HIPCHK(hipMemcpyAsync(u.nh, nh.data(), sizeof(int), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(u.top_lp, top_lp, (size_t)n_hyp * k * sizeof(float), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(u.top_tok, top_tok, (size_t)n_hyp * k * sizeof(int), hipMemcpyHostToDevice, s));
+    CpGraph graph;
+    memset(&graph, 0, sizeof(graph));
+    std::vector<int> cst(width, 0);
+    std::vector<double> cs(width, 0.0);
+    if (biased) {
+        graph = ctx_graph_dev(ctx);
+        std::copy(hyp_cst, hyp_cst + n_hyp, cst.begin());
+        std::copy(hyp_cs, hyp_cs + n_hyp, cs.begin());
+        HIPCHK(hipMemcpyAsync(u.cst[0], cst.data(), width * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(u.cs[0], cs.data(), width * sizeof(double), hipMemcpyHostToDevice, s));
+    }
     PrefixMergeP m = prefix_merge_params(u, 0, false, (int)lcap, k, beam_size, blank, 0);
     m.lens = nullptr;                                                // the utterance has this frame
-    {
-        ProfScope prof(ctx, s, TAG_PREFIX_MERGE);
-        hipLaunchKernelGGL(prefix_merge, dim3(1), dim3(PB_NT), 0, s, m);
-        LAUNCHCHK("prefix_merge");
+    if ((rc = launch_prefix_merge(ctx, s, 1, m, u, 0, graph))) return rc;
+    std::vector<int> srow(width), sslot(width), ocst(width, 0);
+    std::vector<double> ocs(width, 0.0);
+    if (biased) {
+        HIPCHK(hipMemcpyAsync(ocst.data(), u.cst[1], width * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(ocs.data(), u.cs[1], width * sizeof(double), hipMemcpyDeviceToHost, s));
     }
-    std::vector<int> srow(width), sslot(width);
     HIPCHK(hipMemcpyAsync(nh.data(), u.nh, sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(len.data(), u.len[1], width * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(sc.data(), u.sc[1], width * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -246,6 +345,25 @@ int rnnt_prefix_merge_device(rnnt_ctx* ctx, int32_t n_hyp, const int32_t* hyp_le
         out_score[a] = sc[a];
         if (out_src_row) out_src_row[a] = srow[a];
         if (out_src_slot) out_src_slot[a] = sslot[a];
+        if (biased) { out_cst[a] = ocst[a]; out_cs[a] = ocs[a]; }
     }
     return nh[0];
+}
+}  // namespace
+
+int rnnt_prefix_merge_device(rnnt_ctx* ctx, int32_t n_hyp, const int32_t* hyp_len, const int32_t* hyp_tokens, const double* hyp_score,
+                             const float* top_lp, const int32_t* top_tok, int32_t k, int32_t blank, int32_t beam_size, int32_t* out_len,
+                             int32_t* out_tokens, double* out_score, int32_t* out_src_row, int32_t* out_src_slot, void* stream) {
+    return prefix_merge_device_impl(ctx, n_hyp, hyp_len, hyp_tokens, hyp_score, top_lp, top_tok, k, blank, beam_size, out_len, out_tokens, out_score,
+                                    out_src_row, out_src_slot, stream, false, nullptr, nullptr, nullptr, nullptr);
+}
+
+// One prefix_merge launch with the graph that is set on the context (none: RNNT_ERR_STATE): rnnt_prefix_merge_device's arguments plus
+// the hypotheses' context states and scores; the survivors' come back in out_ctx_state / out_ctx_score, out_score stays the fused score.
+int rnnt_prefix_merge_ctx_device(rnnt_ctx* ctx, int32_t n_hyp, const int32_t* hyp_len, const int32_t* hyp_tokens, const double* hyp_score,
+                                 const int32_t* hyp_ctx_state, const double* hyp_ctx_score, const float* top_lp, const int32_t* top_tok, int32_t k,
+                                 int32_t blank, int32_t beam_size, int32_t* out_len, int32_t* out_tokens, double* out_score, int32_t* out_src_row,
+                                 int32_t* out_src_slot, int32_t* out_ctx_state, double* out_ctx_score, void* stream) {
+    return prefix_merge_device_impl(ctx, n_hyp, hyp_len, hyp_tokens, hyp_score, top_lp, top_tok, k, blank, beam_size, out_len, out_tokens, out_score,
+                                    out_src_row, out_src_slot, stream, true, hyp_ctx_state, hyp_ctx_score, out_ctx_state, out_ctx_score);
 }

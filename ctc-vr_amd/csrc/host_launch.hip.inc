@@ -648,14 +648,14 @@ int pool_ctc_reset(rnnt_ctx* ctx, hipStream_t s, int slot0, int n) {
 PrefixPoolP pool_prefix_params(const rnnt_ctx* ctx) {
     PrefixPoolP q;
     memset(&q, 0, sizeof(q));
-    for (int t = 0; t < 2; ++t) { q.pool[t] = ctx->pp_pool[t]; q.tk[t] = ctx->pp_tk[t]; q.len[t] = ctx->pp_len[t]; q.sc[t] = ctx->pp_sc[t]; q.hs[t] = ctx->pp_hs[t]; }
+    for (int t = 0; t < 2; ++t) { q.pool[t] = ctx->pp_pool[t]; q.tk[t] = ctx->pp_tk[t]; q.len[t] = ctx->pp_len[t]; q.sc[t] = ctx->pp_sc[t]; q.hs[t] = ctx->pp_hs[t]; q.cst[t] = ctx->pp_cst[t]; q.cs[t] = ctx->pp_cs[t]; }
     q.nh = ctx->pp_nh;
     return q;
 }
 
 // the start hypothesis [blank] for slots [slot0, slot0 + n): the host record always, the device rows once they exist (pool_prefix_alloc resets all)
 int pool_prefix_reset(rnnt_ctx* ctx, hipStream_t s, int slot0, int n) {
-    for (int b = slot0; b < slot0 + n && b < (int)ctx->pp_slot.size(); ++b) { ctx->pp_slot[b] = rnnt_ctx::PpSlot{0, 0, 0.f, 0.f}; ctx->pp_cur[b] = 0; }
+    for (int b = slot0; b < slot0 + n && b < (int)ctx->pp_slot.size(); ++b) { ctx->pp_slot[b] = rnnt_ctx::PpSlot{0, 0, 0.f, 0.f, 0, 0}; ctx->pp_cur[b] = 0; }
     if (!ctx->pp_nh) return RNNT_OK;
     hipLaunchKernelGGL(prefix_init_pool, dim3(n), dim3(256), 0, s, pool_prefix_params(ctx), slot0, ctx->cfg.max_cache_frames + 1, ctx->cfg.blank_id);
     LAUNCHCHK("prefix_init_pool");

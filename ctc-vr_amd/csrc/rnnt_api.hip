@@ -283,14 +283,15 @@ struct rnnt_ctx {
     // lengths / scores / hashes [rows] -- plus the hypotheses per slot, the step's top-k [rows][PB_MAX_BEAM], the frames of one call
     // (projected, CTC log-probabilities; grow-only), the seam form's table (slot and current set per active row, one async copy from
     // pinned memory) and one read's packed block.  Host per slot: the current set (pp_cur; slots advance independently), and the
-    // frames walked, beam and weights of the search in progress (beam == 0: fresh).
+    // frames walked, beam, weights, use_context and graph generation of the search in progress (beam == 0: fresh).  A biased search
+    // also keeps a context state and score per row (pp_cst / pp_cs).
     int prefix_group = 0;                      // RNNT_PREFIX_GROUP: 0 by the size of the launch, 1 / 4 hypotheses per prefix_step_pool workgroup always
-    struct PpSlot { int frames_done, beam; float cw, tw; };
+    struct PpSlot { int frames_done, beam; float cw, tw; int use_context; int64_t gen; };
     std::vector<PpSlot> pp_slot;
     std::vector<int> pp_cur;
     DevBuf<float> pp_pool[2], pp_toplp, pp_encp, pp_ctc;
-    DevBuf<int> pp_tk[2], pp_len[2], pp_nh, pp_toptok, pp_tab;
-    DevBuf<double> pp_sc[2], pp_out;
+    DevBuf<int> pp_tk[2], pp_len[2], pp_cst[2], pp_nh, pp_toptok, pp_tab;
+    DevBuf<double> pp_sc[2], pp_cs[2], pp_out;
     DevBuf<unsigned long long> pp_hs[2];
     PinnedBuf<int> pp_tab_host;
     hipEvent_t pp_ev = nullptr;

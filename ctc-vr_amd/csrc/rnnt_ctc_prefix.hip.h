@@ -40,11 +40,7 @@
 constexpr int CP_NT = 256, CP_MAX_BEAM = 16, CP_SLOTS = CP_MAX_BEAM + CP_MAX_BEAM * CP_MAX_BEAM, CP_NOKEY = 0x7fffffff;
 constexpr int CP_MAX_NODES = 4096;
 
-// context graph (fail == nullptr: none): flat node arrays, children as a CSR of (token, child) sorted by token per node
-struct CpGraph {
-    const int* fail; const int* off; const int* ctok; const int* cid;
-    const double* tscore; const double* nscore; const double* oscore;
-};
+// the context graph (CpGraph, cg_child, cg_step): rnnt_ctxgraph.hip.h
 
 // packed results: [B], [B][beam], [B][beam][lcap] x 2, [B][beam] x 2
 struct CpOutP { int* nh; int* len; int* tok; int* time; double* sc; double* cs; };
@@ -116,37 +112,6 @@ __host__ __device__ inline float cp_key_value(unsigned long long k) {
     return v;
 }
 __host__ __device__ inline int cp_key_index(unsigned long long k) { return (int)(0xffffffffu - (unsigned)k); }
-
-// the child of `node` over `tok`, or -1: binary search in the node's sorted CSR row
-__host__ __device__ inline int cg_child(const int* off, const int* ctok, const int* cid, int node, int tok) {
-    int lo = off[node], hi = off[node + 1];
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1, v = ctok[mid];
-        if (v == tok) return cid[mid];
-        if (v < tok) lo = mid + 1; else hi = mid;
-    }
-    return -1;
-}
-
-// ContextGraph.forward_one_step (context_graph.py:212-247) on the flat tables: returns the step's score, *next = the node it lands in
-__host__ __device__ inline double cg_step(const int* fail, const int* off, const int* ctok, const int* cid, const double* tscore,
-                                          const double* nscore, const double* oscore, int state, int tok, int* next) {
-    int node = cg_child(off, ctok, cid, state, tok);
-    double score;
-    if (node >= 0) score = tscore[node];
-    else {
-        node = fail[state];
-        while (cg_child(off, ctok, cid, node, tok) < 0) {
-            node = fail[node];
-            if (node == 0) break;                                    // root
-        }
-        const int c = cg_child(off, ctok, cid, node, tok);
-        if (c >= 0) node = c;
-        score = nscore[node] - nscore[state];                        // the score of the fail path
-    }
-    *next = node;
-    return score + oscore[node];
-}
 
 __device__ inline unsigned long long cp_wave_max(unsigned long long k) {
 #pragma unroll

@@ -3,8 +3,8 @@
 // Part of rnnt_kernels.hip.h (include that umbrella, not this file).
 //
 // Rows are fixed: hypothesis i of utterance b is row b * beam + i of two buffer sets (token lists [rows][lcap], lengths, f64 scores,
-// 64-bit running hashes as in beam_merge_stream_dev, LSTM states [rows][2][512]: slot 0 = the hypothesis' state, slot 1 = the
-// state after its last token went through the predictor).  prefix_step reads the current set and writes slot 1 and the row's
+// 64-bit running hashes as in beam_merge_stream_dev, context state and f64 context score (biased searches only), LSTM states
+// [rows][2][512]: slot 0 = the hypothesis' state, slot 1 = the state after its last token went through the predictor).  prefix_step reads the current set and writes slot 1 and the row's
 // top-k; prefix_merge reads the current set and writes the other one.  A hypothesis always holds its leading blank, so len >= 1.
 #pragma once
 
@@ -160,6 +160,13 @@ struct PrefixMergeP {
     int* src_row; int* src_slot;                // [rows] where each survivor's state came from (hypothesis index, slot); both null: not wanted
     int lcap, k, beam, blank, f;
 };
+// hot-word biasing: the graph and, per row of either set, the context state and score.  The host launches the _ctx kernels
+// (prefix_merge_rows<true>) when g.fail != nullptr and the plain ones otherwise, whose code and arguments are what they were.
+struct PrefixCtxP {
+    CpGraph g;
+    const int* cst_in; int* cst_out;            // [rows] context state: the graph node of the hypothesis' token sequence
+    const double* cs_in; double* cs_out;        // [rows] context score, kept beside the running score
+};
 
 // list form of wenet.utils.common.log_add for two values, as Python evaluates it: -inf if both are, else max + log(sum of exp)
 __host__ __device__ inline double prefix_log_add(double a, double b) {
@@ -176,10 +183,17 @@ __host__ __device__ inline double prefix_log_add(double a, double b) {
 //               length, then every token); every first candidate then adds its followers in ascending order
 //   order       stable descending sort of the survivors: repeated block-wide argmax, ties to the lower candidate index
 //   truncation  to `beam`; tokens, hashes and states gathered into rows row0 + a of the other set
+// With a context graph (search.py:95-104,169-171,214-235 carried over): candidate c also takes its context state and score in its own
+// thread -- a blank copies row j's, any other token is one cg_step from row j's state, its score added to row j's -- into two more
+// LDS arrays (3 KB).  Both are functions of the token sequence alone, so fusion keeps the first candidate's.  The order is then by
+// total = fused score + context score (ties to the lower candidate index as before) and the survivors' state and score are
+// gathered with the rest.  The first prune (prefix_step) does not see the graph, as search.py:156 does not.  Without a graph
+// (GRAPH = false: x is not read, the two arrays do not exist) the arithmetic is what it was: the key is the fused score itself.
 // An utterance past its last frame (f >= lens[b]) is carried over unchanged.
 // prefix_merge_rows: the merge of the utterance whose hypothesis count is nh[u] (and frame count lens[u], when lens is given) and
 // whose rows start at row0 of either set; one workgroup.  Called by the batch kernel and by the pool kernel.
-__device__ __forceinline__ void prefix_merge_rows(const PrefixMergeP& p, int u, int row0) {
+template <bool GRAPH>
+__device__ __forceinline__ void prefix_merge_rows(const PrefixMergeP& p, const PrefixCtxP& x, int u, int row0) {
     __shared__ double sc[PB_MAX_CAND];
     __shared__ unsigned long long hsh[PB_MAX_CAND];
     __shared__ int clen[PB_MAX_CAND], ctok[PB_MAX_CAND], first[PB_MAX_CAND], rep[PB_MAX_CAND];
@@ -188,6 +202,8 @@ __device__ __forceinline__ void prefix_merge_rows(const PrefixMergeP& p, int u, 
     __shared__ double red_v[PB_NT / 64];
     __shared__ int red_i[PB_NT / 64];
     __shared__ int s_best;
+    __shared__ double ccs[PB_MAX_CAND];
+    __shared__ int ccst[PB_MAX_CAND];
     const int tid = threadIdx.x;
     const int nh = p.nh[u];
     if (p.lens && p.f >= p.lens[u]) {                                // finished: carry the rows over unchanged
@@ -196,7 +212,10 @@ __device__ __forceinline__ void prefix_merge_rows(const PrefixMergeP& p, int u, 
             for (int q = tid; q < len; q += PB_NT) p.tk_out[(long long)r * p.lcap + q] = p.tk_in[(long long)r * p.lcap + q];
             if (p.pool_in)
                 for (int e = tid; e < 512; e += PB_NT) p.pool_out[(long long)r * 1024 + e] = p.pool_in[(long long)r * 1024 + e];
-            if (tid == 0) { p.len_out[r] = len; p.sc_out[r] = p.sc_in[r]; p.hs_out[r] = p.hs_in[r]; }
+            if (tid == 0) {
+                p.len_out[r] = len; p.sc_out[r] = p.sc_in[r]; p.hs_out[r] = p.hs_in[r];
+                if constexpr (GRAPH) { x.cst_out[r] = x.cst_in[r]; x.cs_out[r] = x.cs_in[r]; }
+            }
         }
         return;
     }
@@ -212,6 +231,13 @@ __device__ __forceinline__ void prefix_merge_rows(const PrefixMergeP& p, int u, 
         clen[tid] = p.len_in[r] + (bl ? 0 : 1);
         hsh[tid] = bl ? p.hs_in[r] : beam_hash_step(p.hs_in[r], tok);
         taken[tid] = 0;
+        if constexpr (GRAPH) {                                       // copy_context / update_context; the fail chain diverges per lane, and is short
+            int nx = x.cst_in[r];
+            double cs = x.cs_in[r];
+            if (!bl) cs += cg_step(x.g.fail, x.g.off, x.g.ctok, x.g.cid, x.g.tscore, x.g.nscore, x.g.oscore, nx, tok, &nx);
+            ccst[tid] = nx;
+            ccs[tid] = cs;
+        }
     }
     __syncthreads();
     if (tid < C) {                                                   // first candidate with the same hash and length
@@ -253,7 +279,11 @@ __device__ __forceinline__ void prefix_merge_rows(const PrefixMergeP& p, int u, 
     while (n_acc < p.beam) {
         double bv = -INFINITY;
         int bi = PB_NONE;
-        if (tid < C && rep[tid] == tid && !taken[tid]) { bv = sc[tid]; bi = tid; }
+        if (tid < C && rep[tid] == tid && !taken[tid]) {
+            if constexpr (GRAPH) bv = sc[tid] + ccs[tid];
+            else bv = sc[tid];
+            bi = tid;
+        }
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) {
             const double ov = __shfl_xor(bv, off, 64);
@@ -284,17 +314,19 @@ __device__ __forceinline__ void prefix_merge_rows(const PrefixMergeP& p, int u, 
             p.len_out[nr] = len;
             p.sc_out[nr] = sc[c];
             p.hs_out[nr] = hsh[c];
+            if constexpr (GRAPH) { x.cst_out[nr] = ccst[c]; x.cs_out[nr] = ccs[c]; }
             if (p.src_row) { p.src_row[nr] = j; p.src_slot[nr] = slot; }
         }
     }
     if (tid == 0) p.nh[u] = n_acc;
 }
 
-__global__ __launch_bounds__(PB_NT) void prefix_merge(PrefixMergeP p) { prefix_merge_rows(p, blockIdx.x, blockIdx.x * p.beam); }
+__global__ __launch_bounds__(PB_NT) void prefix_merge(PrefixMergeP p) { prefix_merge_rows<false>(p, PrefixCtxP{}, blockIdx.x, blockIdx.x * p.beam); }
+__global__ __launch_bounds__(PB_NT) void prefix_merge_ctx(PrefixMergeP p, PrefixCtxP x) { prefix_merge_rows<true>(p, x, blockIdx.x, blockIdx.x * p.beam); }
 
 // Start of a call: every utterance holds the one hypothesis [blank] with score 0 and the zero LSTM state (:68-77) in set 0.
-__global__ __launch_bounds__(256) void prefix_init(float* pool, int* tk, int* len, double* sc, unsigned long long* hs, int* nh, int beam,
-                                                   int lcap, int blank) {
+__global__ __launch_bounds__(256) void prefix_init(float* pool, int* tk, int* len, double* sc, unsigned long long* hs, int* cst, double* cs, int* nh,
+                                                   int beam, int lcap, int blank) {
     const int b = blockIdx.x, r = b * beam;
     for (int e = threadIdx.x; e < 512; e += 256) pool[(long long)r * 1024 + e] = 0.f;
     if (threadIdx.x == 0) {
@@ -302,16 +334,20 @@ __global__ __launch_bounds__(256) void prefix_init(float* pool, int* tk, int* le
         len[r] = 1;
         sc[r] = 0.0;
         hs[r] = beam_hash_step(BEAM_HASH0, blank);
+        cst[r] = 0;                                                  // the context root; the leading blank is never fed to the graph
+        cs[r] = 0.0;
         nh[b] = 1;
     }
 }
 
-// End of a call: the final set into ONE block for one download: scores f64 [rows] | n_hyp [B] | lengths [rows] | tokens
-// [rows][lcap] | h [rows][256] | c [rows][256] (states only if with_states).  Rows without a hypothesis are zero.
-__global__ __launch_bounds__(256) void prefix_pack(const float* pool, const int* tk, const int* len, const double* sc, const int* nh, int B,
-                                                   int beam, int lcap, int with_states, double* out) {
+// End of a call: the final set into ONE block for one download: scores f64 [rows] | context scores f64 [rows] | n_hyp [B] | lengths
+// [rows] | tokens [rows][lcap] | h [rows][256] | c [rows][256] (states only if with_states).  Rows without a hypothesis are zero.
+// cst != nullptr: a biased search, whose returned score is the total; fin_nscore != nullptr: the utterance has ended and finalize
+// (context_graph.py:264) REPLACES the context score (search.py:229-231), in the total too.
+__global__ __launch_bounds__(256) void prefix_pack(const float* pool, const int* tk, const int* len, const double* sc, const int* cst, const double* cs,
+                                                   const double* fin_nscore, const int* nh, int B, int beam, int lcap, int with_states, double* out) {
     const int r = blockIdx.x, b = r / beam, i = r - b * beam, rows = B * beam, tid = threadIdx.x;
-    int* oi = reinterpret_cast<int*>(out + rows);
+    int* oi = reinterpret_cast<int*>(out + 2 * rows);
     int* o_len = oi + B;
     int* o_tk = o_len + rows;
     float* o_h = reinterpret_cast<float*>(o_tk + (long long)rows * lcap);
@@ -324,7 +360,9 @@ __global__ __launch_bounds__(256) void prefix_pack(const float* pool, const int*
         o_c[(long long)r * RNNT_D + tid] = live ? pool[(long long)r * 1024 + RNNT_D + tid] : 0.f;
     }
     if (tid == 0) {
-        out[r] = live ? sc[r] : 0.0;
+        const double c = live && cst ? (fin_nscore ? -fin_nscore[cst[r]] : cs[r]) : 0.0;
+        out[r] = live ? (cst ? sc[r] + c : sc[r]) : 0.0;
+        out[rows + r] = c;
         o_len[r] = n;
         if (i == 0) oi[b] = nh[b];
     }
@@ -345,6 +383,7 @@ struct PrefixPoolP {
     int* tk[2]; int* len[2];
     double* sc[2];
     unsigned long long* hs[2];
+    int* cst[2]; double* cs[2];  // context state and score per row (read and written by biased searches only)
     int* nh;                     // [slots]
 };
 constexpr int PB_GROUP = 4;      // hypotheses of one slot per workgroup of the grouped prefix_step_pool: one pass over the weights for all of them
@@ -364,8 +403,9 @@ __global__ __launch_bounds__(512) void prefix_step_pool(PrefixStepP p, PrefixPoo
 }
 
 // prefix_merge for one ACTIVE slot per workgroup: from the slot's current set into its other one.  p carries prefix_step_pool's
-// outputs and the call's scalars (lens = nullptr: the slot has this frame); its buffer pointers are set here.
-__global__ __launch_bounds__(PB_NT) void prefix_merge_pool(PrefixMergeP p, PrefixPoolP q) {
+// outputs and the call's scalars (lens = nullptr: the slot has this frame); its buffer pointers are set here.  GRAPH: biased by g.
+template <bool GRAPH>
+__device__ __forceinline__ void prefix_merge_pool_rows(PrefixMergeP p, const PrefixPoolP& q, const CpGraph& g) {
     const int a = blockIdx.x, slot = ldgi(q.slots + a);
     const int cur = (ldgi(q.cur0 + a) + p.f) & 1, nxt = cur ^ 1;
     p.pool_in = q.pool[cur]; p.pool_out = q.pool[nxt];
@@ -374,8 +414,16 @@ __global__ __launch_bounds__(PB_NT) void prefix_merge_pool(PrefixMergeP p, Prefi
     p.sc_in = q.sc[cur]; p.sc_out = q.sc[nxt];
     p.hs_in = q.hs[cur]; p.hs_out = q.hs[nxt];
     p.nh = q.nh;
-    prefix_merge_rows(p, slot, slot * PB_MAX_BEAM);
+    PrefixCtxP x{};
+    if constexpr (GRAPH) {
+        x.g = g;
+        x.cst_in = q.cst[cur]; x.cst_out = q.cst[nxt];
+        x.cs_in = q.cs[cur]; x.cs_out = q.cs[nxt];
+    }
+    prefix_merge_rows<GRAPH>(p, x, slot, slot * PB_MAX_BEAM);
 }
+__global__ __launch_bounds__(PB_NT) void prefix_merge_pool(PrefixMergeP p, PrefixPoolP q) { prefix_merge_pool_rows<false>(p, q, CpGraph{}); }
+__global__ __launch_bounds__(PB_NT) void prefix_merge_pool_ctx(PrefixMergeP p, PrefixPoolP q, CpGraph g) { prefix_merge_pool_rows<true>(p, q, g); }
 
 // The reset of slots [slot0, slot0 + gridDim.x): prefix_init's start (hypothesis [blank], score 0, zero state) in set 0; the host's
 // set index goes to 0 with it.  Touches no other slot.
@@ -387,16 +435,20 @@ __global__ __launch_bounds__(256) void prefix_init_pool(PrefixPoolP q, int slot0
         q.len[0][r] = 1;
         q.sc[0][r] = 0.0;
         q.hs[0][r] = beam_hash_step(BEAM_HASH0, blank);
+        q.cst[0][r] = 0;
+        q.cs[0][r] = 0.0;
         q.nh[slot] = 1;
     }
 }
 
 // One slot's set `cur` into ONE block for one download (rnnt_stream_get_prefix), one workgroup per row i < beam: scores f64 [beam] |
-// n_hyp | lengths [beam] | tokens [beam][ocap] | h [beam][256] | c [beam][256] (states only if with_states).  Rows without a
-// hypothesis are zero.  ocap >= every length (1 + the frames walked).
-__global__ __launch_bounds__(256) void prefix_pack_pool(PrefixPoolP q, int slot, int cur, int beam, int lcap, int ocap, int with_states, double* out) {
+// context scores f64 [beam] | n_hyp | lengths [beam] | tokens [beam][ocap] | h [beam][256] | c [beam][256] (states only if
+// with_states).  Rows without a hypothesis are zero.  ocap >= every length (1 + the frames walked).  biased / fin_nscore: as
+// prefix_pack's cst / fin_nscore.
+__global__ __launch_bounds__(256) void prefix_pack_pool(PrefixPoolP q, int slot, int cur, int beam, int lcap, int ocap, int with_states, int biased,
+                                                        const double* fin_nscore, double* out) {
     const int i = blockIdx.x, r = slot * PB_MAX_BEAM + i, tid = threadIdx.x;
-    int* oi = reinterpret_cast<int*>(out + beam);
+    int* oi = reinterpret_cast<int*>(out + 2 * beam);
     int* o_len = oi + 1;
     int* o_tk = o_len + beam;
     float* o_h = reinterpret_cast<float*>(o_tk + (long long)beam * ocap);
@@ -410,7 +462,9 @@ __global__ __launch_bounds__(256) void prefix_pack_pool(PrefixPoolP q, int slot,
         o_c[(long long)i * RNNT_D + tid] = live ? q.pool[cur][(long long)r * 1024 + RNNT_D + tid] : 0.f;
     }
     if (tid == 0) {
-        out[i] = live ? q.sc[cur][r] : 0.0;
+        const double c = live && biased ? (fin_nscore ? -fin_nscore[q.cst[cur][r]] : q.cs[cur][r]) : 0.0;
+        out[i] = live ? (biased ? q.sc[cur][r] + c : q.sc[cur][r]) : 0.0;
+        out[beam + i] = c;
         o_len[i] = n;
         if (i == 0) oi[0] = nh;
     }

@@ -58,6 +58,12 @@ SIGNATURES = {
     "rnnt_prefix_beam_decode": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, ctypes.c_float, ctypes.c_float, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rnnt_prefix_merge_host": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rnnt_prefix_merge_device": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rnnt_prefix_beam_decode_ctx": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, ctypes.c_float, ctypes.c_float, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                            c_vp, c_vp, c_vp]),
+    "rnnt_prefix_merge_ctx_host": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, ctypes.c_double, c_vp, c_vp,
+                                           c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rnnt_prefix_merge_ctx_device": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                             c_vp, c_vp]),
     "rnnt_context_set": (c_i32, [c_vp, c_i32, c_vp, c_vp, ctypes.c_double]),
     "rnnt_context_walk_host": (c_i32, [c_i32, c_vp, c_vp, ctypes.c_double, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "rnnt_context_dump_host": (c_i32, [c_i32, c_vp, c_vp, ctypes.c_double, c_i32p, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
@@ -73,6 +79,9 @@ SIGNATURES = {
     "rnnt_pool_prefix_frames": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, ctypes.c_float, ctypes.c_float, c_vp]),
     "rnnt_pool_chunk_prefix": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, ctypes.c_float, ctypes.c_float, c_i32p, c_vp]),
     "rnnt_stream_get_prefix": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rnnt_pool_prefix_frames_ctx": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, ctypes.c_float, ctypes.c_float, c_i32, c_vp]),
+    "rnnt_pool_chunk_prefix_ctx": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, ctypes.c_float, ctypes.c_float, c_i32, c_i32p, c_vp]),
+    "rnnt_stream_get_prefix_ctx": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rnnt_transducer_nll": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "rnnt_ctc_nll": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "rnnt_transducer_nll_nbest": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
@@ -196,6 +205,44 @@ def prefix_merge_host(hyps, top_lp, top_tok, blank, beam_size):
     return out
 
 
+def _prefix_merge_ctx_call(fn, head, hyps, top_lp, top_tok, blank, beam_size, graph=(), tail=()):
+    """Flat arguments of rnnt_prefix_merge_ctx_host / rnnt_prefix_merge_ctx_device (hyps [(tokens, score, context state, context
+    score)]; graph: the host form's phrase arguments) -> the call's return value and [(tokens, score, src_row, src_slot, context
+    state, context score)] of the survivors."""
+    n = len(hyps)
+    hl = np.array([len(h[0]) for h in hyps], np.int32)
+    ht = np.array([x for h in hyps for x in h[0]] or [0], np.int32)
+    hs = np.array([h[1] for h in hyps], np.float64)
+    hst = np.array([h[2] for h in hyps], np.int32)
+    hcs = np.array([h[3] for h in hyps], np.float64)
+    tl = np.ascontiguousarray(top_lp, np.float32).reshape(n, -1)
+    tt = np.ascontiguousarray(top_tok, np.int32).reshape(n, -1)
+    assert tt.shape == tl.shape
+    cap = max(beam_size, 1)
+    out_len, out_tok = np.zeros(cap, np.int32), np.zeros(cap * (int(hl.max(initial=0)) + 1) + 1, np.int32)
+    out_sc, out_row, out_slot = np.zeros(cap, np.float64), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+    out_st, out_cs = np.zeros(cap, np.int32), np.zeros(cap, np.float64)
+    m = fn(*head, n, _np_ptr(hl), _np_ptr(ht), _np_ptr(hs), _np_ptr(hst), _np_ptr(hcs), _np_ptr(tl), _np_ptr(tt), tl.shape[1], blank, beam_size, *graph,
+           _np_ptr(out_len), _np_ptr(out_tok), _np_ptr(out_sc), _np_ptr(out_row), _np_ptr(out_slot), _np_ptr(out_st), _np_ptr(out_cs), *tail)
+    out, o = [], 0
+    for a in range(max(m, 0)):
+        out.append((out_tok[o:o + out_len[a]].tolist(), float(out_sc[a]), int(out_row[a]), int(out_slot[a]), int(out_st[a]), float(out_cs[a])))
+        o += out_len[a]
+    return m, out
+
+
+def prefix_merge_ctx_host(hyps, top_lp, top_tok, blank, beam_size, phrases, context_score):
+    """rnnt_prefix_merge_ctx_host (no context, no GPU): prefix_merge_host with the context graph over `phrases`.  hyps [(tokens,
+    score, context state, context score)] -> [(tokens, fused score, src_row, src_slot, context state, context score)] of the
+    survivors, ordered by fused score + context score."""
+    n, pl, pt = _phrase_args(phrases)
+    m, out = _prefix_merge_ctx_call(load().rnnt_prefix_merge_ctx_host, (), hyps, top_lp, top_tok, blank, beam_size,
+                                    (n, _np_ptr(pl), _np_ptr(pt), float(context_score)))
+    if m < 0:
+        raise RnntError(f"rnnt_prefix_merge_ctx_host: bad argument (status {m})", m)
+    return out
+
+
 def rescore_select(first_scores, nll, first_weight, transducer_weight):
     """rnnt_rescore_select_host (no context, no GPU): the choice of transducer_attention_rescoring among one utterance's
     hypotheses -> (best index, totals float64 [n]); total = first * first_weight + (-nll) * transducer_weight, the first of equal
@@ -312,7 +359,7 @@ class RnntEngine:
     slots of a stream pool that open, advance and close independently (stream_open / pool_chunk / stream_tokens, and per-slot beam
     search through pool_chunk_beam / stream_beam / stream_beam_states, per-slot CTC prefix beam search with hot words through
     pool_chunk_ctc_prefix / pool_ctc_prefix_logprobs / stream_ctc_prefix / stream_ctc_prefix_reset, the transducer prefix beam search per
-    slot through pool_chunk_prefix / pool_prefix_frames / stream_prefix / stream_prefix_reset, audio in per slot through
+    slot through pool_chunk_prefix / pool_prefix_frames / stream_prefix / stream_prefix_reset (with hot words: the _ctx forms), audio in per slot through
     pool_wave / wave_state / stream_wave_reset)."""
 
     def __init__(self, max_streams=1, max_chunk_frames=64, max_cache_frames=1024, max_enc_frames=1024, max_tokens=4096,
@@ -619,6 +666,26 @@ class RnntEngine:
         hyps = [[(toks[b, i, :lens[b, i]].tolist(), float(sc[b, i])) for i in range(nh[b])] for b in range(B)]
         return (hyps, h, c) if want_states else hyps
 
+    def prefix_beam_decode_ctx(self, enc_ptr, enc_lens, B, T, beam_size=5, ctc_weight=0.3, transducer_weight=0.7, use_context=True, want_states=False,
+                               stream=None):
+        """rnnt_prefix_beam_decode_ctx: prefix_beam_decode biased by the graph of context_set when use_context.  Returns per
+        utterance [(tokens incl. the leading blank, total score, context score)] in the search's order (finalize replaces the
+        context scores at the end without a re-sort, so the totals need not descend); with want_states also (h, c)."""
+        el = np.ascontiguousarray(enc_lens, np.int32)
+        assert el.size == B
+        w = max(beam_size, 1)
+        cap = int(el.max(initial=0)) + 1
+        nh, lens = np.zeros(B, np.int32), np.zeros((B, w), np.int32)
+        toks, sc, cs = np.zeros((B, w, cap), np.int32), np.zeros((B, w), np.float64), np.zeros((B, w), np.float64)
+        h = np.zeros((B, w, 256), np.float32) if want_states else None
+        c = np.zeros((B, w, 256), np.float32) if want_states else None
+        self._chk(self.lib.rnnt_prefix_beam_decode_ctx(self.ctx, enc_ptr, _np_ptr(el), B, T, beam_size, ctc_weight, transducer_weight, 1 if use_context else 0,
+                                                       cap, _np_ptr(nh), _np_ptr(lens), _np_ptr(toks), _np_ptr(sc), _np_ptr(cs),
+                                                       _np_ptr(h) if want_states else None, _np_ptr(c) if want_states else None, stream),
+                  "rnnt_prefix_beam_decode_ctx")
+        hyps = [[(toks[b, i, :lens[b, i]].tolist(), float(sc[b, i]), float(cs[b, i])) for i in range(nh[b])] for b in range(B)]
+        return (hyps, h, c) if want_states else hyps
+
     # ---- CTC prefix beam search with contextual biasing ------------------------------------------
     def context_set(self, phrases, context_score=6.0):
         """rnnt_context_set: build and upload the context graph over phrases [[token, ...], ...]; an empty list clears it."""
@@ -707,6 +774,39 @@ class RnntEngine:
                                                   transducer_weight, ctypes.byref(t), stream), "rnnt_pool_chunk_prefix")
         return t.value
 
+    def pool_prefix_frames_ctx(self, slots, enc_ptr, t, beam_size=5, ctc_weight=0.3, transducer_weight=0.7, use_context=True, stream=None):
+        """rnnt_pool_prefix_frames_ctx: pool_prefix_frames for searches biased by the graph of context_set (use_context)."""
+        a = np.ascontiguousarray(slots, np.int32)
+        assert a.ndim == 1
+        self._chk(self.lib.rnnt_pool_prefix_frames_ctx(self.ctx, a.size, _np_ptr(a), enc_ptr, t, beam_size, ctc_weight, transducer_weight,
+                                                       1 if use_context else 0, stream), "rnnt_pool_prefix_frames_ctx")
+
+    def pool_chunk_prefix_ctx(self, slots, fbank_ptr, chunk_frames, offsets, required, beam_size=5, ctc_weight=0.3, transducer_weight=0.7, use_context=True,
+                              stream=None):
+        """rnnt_pool_chunk_prefix_ctx: pool_chunk_prefix for searches biased by the graph of context_set (use_context).  Returns t'."""
+        a, o, r = (np.ascontiguousarray(v, np.int32) for v in (slots, offsets, required))
+        assert a.ndim == 1 and a.size == o.size == r.size
+        t = c_i32(0)
+        self._chk(self.lib.rnnt_pool_chunk_prefix_ctx(self.ctx, a.size, _np_ptr(a), fbank_ptr, chunk_frames, _np_ptr(o), _np_ptr(r), beam_size, ctc_weight,
+                                                      transducer_weight, 1 if use_context else 0, ctypes.byref(t), stream), "rnnt_pool_chunk_prefix_ctx")
+        return t.value
+
+    def stream_prefix_ctx(self, slot, final=False, states=False, stream=None):
+        """rnnt_stream_get_prefix_ctx: [(tokens incl. the leading blank, total score, context score)] of one slot in the search's
+        order, as they stand (final: finalize's context scores, what the one-call search returns had the utterance ended here);
+        with states also (h, c), each [n_hyp, 256].  Reading changes nothing."""
+        w, _, cap = self.stream_prefix_size(slot)
+        nh, lens = np.zeros(1, np.int32), np.zeros(w, np.int32)
+        toks, sc, cs = np.zeros((w, cap), np.int32), np.zeros(w, np.float64), np.zeros(w, np.float64)
+        h = np.zeros((w, 256), np.float32) if states else None
+        c = np.zeros((w, 256), np.float32) if states else None
+        self._chk(self.lib.rnnt_stream_get_prefix_ctx(self.ctx, slot, 1 if final else 0, w, cap, _np_ptr(nh), _np_ptr(lens), _np_ptr(toks), _np_ptr(sc),
+                                                      _np_ptr(cs), _np_ptr(h) if states else None, _np_ptr(c) if states else None, stream),
+                  "rnnt_stream_get_prefix_ctx")
+        n = int(nh[0])
+        hyps = [(toks[i, :lens[i]].tolist(), float(sc[i]), float(cs[i])) for i in range(n)]
+        return (hyps, h[:n], c[:n]) if states else hyps
+
     def stream_prefix_size(self, slot):
         """rnnt_stream_get_prefix's size query (host only): (beam, frames walked, bound on the longest token list) of one slot."""
         need = np.zeros(3, np.int32)
@@ -761,6 +861,14 @@ class RnntEngine:
         m, out = _prefix_merge_call(self.lib.rnnt_prefix_merge_device, (self.ctx,), hyps, top_lp, top_tok, blank, beam_size, (stream,))
         if m < 0:
             self._chk(m, "rnnt_prefix_merge_device")
+        return out
+
+    def prefix_merge_ctx_device(self, hyps, top_lp, top_tok, blank, beam_size, stream=None):
+        """rnnt_prefix_merge_ctx_device: prefix_merge_ctx_host's hypotheses and results through one prefix_merge launch with the
+        graph of context_set."""
+        m, out = _prefix_merge_ctx_call(self.lib.rnnt_prefix_merge_ctx_device, (self.ctx,), hyps, top_lp, top_tok, blank, beam_size, (), (stream,))
+        if m < 0:
+            self._chk(m, "rnnt_prefix_merge_ctx_device")
         return out
 
     def _score_args(self, enc_lens, targets, target_lens, B):

@@ -198,7 +198,7 @@ class OnlineRNNTModel:
                                   n_steps=10, device=device, max_beam=max_beam)
         self.numerics = numerics          # None -> $RNNT_NUMERICS or "fp32" (lib.numerics_id)
         self._loaded = False
-        self._context_bias = None         # the ContextBias whose graph the context holds (ctc_prefix_beam_search)
+        self._context_bias = None         # the ContextBias whose graph the context holds (ctc_prefix_beam_search, prefix_beam_search_batch)
         self._chunks_done = None          # None = reset_streaming_cache not called yet (attributes are None, :138-143)
         self._tok_count = 0
         self.streaming_beam_hypotheses = None
@@ -499,14 +499,20 @@ class OnlineRNNTModel:
         return self.greedy_search_full(audios, audio_lens), None, None
 
     def prefix_beam_search(self, audios: torch.Tensor, audio_lens: torch.Tensor, beam_size: int = 5, ctc_weight: float = 0.3,
-                           transducer_weight: float = 0.7):
+                           transducer_weight: float = 0.7, context: Optional["ContextBias"] = None):
         """WeNet prefix beam search (wenet/transducer/search/prefix_beam_search.py:42-148) on the full-context encoder
         (decoding_chunk_size=-1), B = 1: at most one symbol per frame, CTC shallow fusion, prefix merging with log_add.
         Device: encoder (rnnt_encoder_full), CTC posteriors (rnnt_ctc_logprobs), one predictor step and one joint + log_softmax
         per frame for all hypotheses (rnnt_predictor_step, rnnt_joint).  Host: the fusion / top-k (float32, torch CPU ops as
         in the reference), candidate order, log_add merge (Python double, the LIST form the reference's call site was written
         for: its vendored log_add(*args) raises TypeError on a merge), stable sort, truncation.
-        Returns [(tokens incl. the leading blank, score)], best first."""
+        context: hot words, with the semantics of wenet/transformer/search.py:95-104,169-171,214-235 carried over (the reference's
+        transducer search has none), in Python doubles on testing.context_graph_ref: every hypothesis holds a graph state and a
+        context score beside its score ([blank]: root, 0); a blank candidate copies them, any other token takes one step and adds
+        its score; merged candidates keep the first one's; the sort is by score + context score; after the last frame finalize
+        replaces the context scores, without a re-sort.  The first prune (top-k) does not see the graph.
+        Returns [(tokens incl. the leading blank, score)], best first; with a context the scores are the totals and
+        self._prefix_context_scores holds [(running, finalized)] context scores per hypothesis."""
         import math
         self._require_loaded()
         assert audios.size(0) == 1, "prefix_beam_search is batch-1 in the reference (:58)"
@@ -521,6 +527,11 @@ class OnlineRNNTModel:
         eng.ctc_logprobs(enc.data_ptr(), tq, ctc_dev.data_ptr(), s)
         ctc = ctc_dev.cpu()
         hyps, scores = [[self.blank_id]], [0.0]
+        graph = None
+        if context is not None:
+            from .testing import context_graph_ref
+            graph = context_graph_ref(context.phrases, context.context_score)
+        cstate, cscore = [0], [0.0]
         h = torch.zeros(1, 256, device=dev)
         c = torch.zeros(1, 256, device=dev)
 
@@ -540,13 +551,14 @@ class OnlineRNNTModel:
             logp = torch.log(torch.add(transducer_weight * torch.exp(logp), ctc_weight * torch.exp(ctc[i].unsqueeze(0))))   # :99-101
             top_lp, top_ix = logp.topk(beam_size)                                                                            # :104
             sc = torch.add(torch.tensor(scores).unsqueeze(1), top_lp)                                                        # :105 (float32)
-            cand = []                                            # [tokens, score, state row in cat(h, h2)]
+            cand = []                                            # [tokens, score, state row in cat(h, h2), context state, context score]
             for j in range(n):
                 for t in range(beam_size):
                     if int(top_ix[j, t]) == self.blank_id:
-                        cand.append([list(hyps[j]), sc[j, t].item(), j])
+                        cand.append([list(hyps[j]), sc[j, t].item(), j, cstate[j], cscore[j]])
                     else:
-                        cand.append([list(hyps[j]) + [int(top_ix[j, t])], sc[j, t].item(), n + j])
+                        step, nxt = graph.step(cstate[j], int(top_ix[j, t])) if graph is not None else (0.0, 0)
+                        cand.append([list(hyps[j]) + [int(top_ix[j, t])], sc[j, t].item(), n + j, nxt, cscore[j] + step])
             fused = [cand[0]]
             for cnd in cand[1:]:
                 for f in fused:
@@ -555,22 +567,34 @@ class OnlineRNNTModel:
                         break
                 else:
                     fused.append(cnd)
-            fused.sort(key=lambda v: v[1], reverse=True)
+            if graph is not None:
+                fused.sort(key=lambda v: v[1] + v[4], reverse=True)
+            else:
+                fused.sort(key=lambda v: v[1], reverse=True)
             fused = fused[:beam_size]
+            cstate, cscore = [f[3] for f in fused], [f[4] for f in fused]
             rows = torch.tensor([f[2] for f in fused], device=dev)
             h = torch.cat([h, h2], 0).index_select(0, rows).contiguous()
             c = torch.cat([c, c2], 0).index_select(0, rows).contiguous()
             hyps, scores = [f[0] for f in fused], [f[1] for f in fused]
         self._prefix_states = (h, c)
+        if graph is not None:
+            fin = [graph.finalize(st) for st in cstate]
+            self._prefix_context_scores = list(zip(cscore, fin))
+            scores = [sc + f for sc, f in zip(scores, fin)]
         return list(zip(hyps, scores))
 
     def prefix_beam_search_batch(self, audios: torch.Tensor, audio_lens: torch.Tensor, beam_size: int = 5, ctc_weight: float = 0.3,
-                                 transducer_weight: float = 0.7, walk_padding: bool = True):
+                                 transducer_weight: float = 0.7, walk_padding: bool = True, context: Optional["ContextBias"] = None,
+                                 with_context_scores: bool = False):
         """prefix_beam_search for a padded batch audios [B, T, 80] of utterances of different lengths, with the frame loop on the
         device: one rnnt_encoder_full call and one rnnt_prefix_beam_decode call (two launches per encoder frame, one
         synchronisation at the end).  walk_padding: every utterance walks all T' encoder frames, the padded ones included, as the
         reference does (:64,76) and prefix_beam_search above; False: each stops after its own valid frames.  Equal values in the
         top-k are taken lower index first (torch.topk leaves that order open).
+        context: a ContextBias whose phrases boost the hypotheses that match them (rnnt_prefix_beam_decode_ctx; semantics as in
+        prefix_beam_search): the scores are then the totals, which carry finalize's correction and need not descend;
+        with_context_scores: every hypothesis is (tokens, score, context score), so score - context score is the unbiased score.
         Returns one [(tokens incl. the leading blank, score)] per utterance, best first; the hypotheses' final LSTM states stay in
         self._prefix_states_batch, one (h, c) pair of host tensors [n_hyp, 256] per utterance.  Invalidates the streaming state."""
         self._require_loaded()
@@ -587,7 +611,15 @@ class OnlineRNNTModel:
         else:
             n1 = np.maximum(0, (np.minimum(lens, T) - 1) // 2)     # valid frames after masks[:, :, 2::2][:, :, 2::2]
             enc_lens = np.maximum(0, (n1 - 1) // 2).astype(np.int32)
-        hyps, h, c = self._engine.prefix_beam_decode(enc.data_ptr(), enc_lens, B, tq, beam_size, ctc_weight, transducer_weight, True, s)
+        if context is None and not with_context_scores:
+            hyps, h, c = self._engine.prefix_beam_decode(enc.data_ptr(), enc_lens, B, tq, beam_size, ctc_weight, transducer_weight, True, s)
+        else:
+            if context is not None:
+                self._set_context(context)
+            hyps, h, c = self._engine.prefix_beam_decode_ctx(enc.data_ptr(), enc_lens, B, tq, beam_size, ctc_weight, transducer_weight, context is not None,
+                                                             True, s)
+            if not with_context_scores:
+                hyps = [[(tok, score) for tok, score, _ in row] for row in hyps]
         self._prefix_states_batch = [(torch.from_numpy(h[b, :len(hyps[b])].copy()), torch.from_numpy(c[b, :len(hyps[b])].copy())) for b in range(B)]
         return hyps
 
@@ -626,21 +658,24 @@ class OnlineRNNTModel:
                         search_ctc_weight: float = 1.0, search_transducer_weight: float = 0.0):
         """Transducer rescoring of n-best for a padded batch audios [B, T, 80]: one full-context encoder call, one search call
         (beam_search_type "ctc": rnnt_ctc_prefix_beam_decode, biased by `context` when given; "transducer":
-        rnnt_prefix_beam_decode with the two search weights over each utterance's valid frames, the leading blank dropped, :327),
+        rnnt_prefix_beam_decode with the two search weights over each utterance's valid frames, the leading blank dropped, :327;
+        with `context` rnnt_prefix_beam_decode_ctx, whose totals are the first-pass scores, as for "ctc"),
         one rnnt_transducer_nll_nbest call over the same frames and, per utterance, the choice of rnnt_rescore_select_host:
         total = first_score * ctc_weight + td_score * transducer_weight (:388-390 with attn_weight = 0; the defaults are the
         fusion weights of the reference's beam_search, :223-224).  beam_size <= 16.
         Returns per utterance (best_index, [(tokens, first_score, td_score, total)]) in the first pass's order; an utterance with
         no valid encoder frame comes back with td_score = nan and best_index = 0.  Invalidates the streaming state."""
         check_rescoring_args(beam_search_type=beam_search_type)
-        if context is not None and beam_search_type != "ctc":
-            raise ValueError("context biases the CTC prefix search only (beam_search_type='ctc')")
         enc, enc_lens, _, _ = self._encode_for_scoring(audios, audio_lens, torch.zeros(audios.size(0), 0), torch.zeros(audios.size(0)))
         B, tq, s = enc.size(0), enc.size(1), _stream_ptr()
         if beam_search_type == "ctc":
             self._set_context(context)
             first = [[(tok, score) for tok, score, _, _ in row]
                      for row in self._engine.ctc_prefix_beam_decode(enc.data_ptr(), enc_lens, B, tq, beam_size, context is not None, False, s)]
+        elif context is not None:
+            self._set_context(context)
+            rows = self._engine.prefix_beam_decode_ctx(enc.data_ptr(), enc_lens, B, tq, beam_size, search_ctc_weight, search_transducer_weight, True, False, s)
+            first = [[(tok[1:], score) for tok, score, _ in row] for row in rows]
         else:
             rows = self._engine.prefix_beam_decode(enc.data_ptr(), enc_lens, B, tq, beam_size, search_ctc_weight, search_transducer_weight, False, s)
             first = [[(tok[1:], score) for tok, score in row] for row in rows]
@@ -944,12 +979,14 @@ def pool_plan(queue, offsets, beams=None, ctc_prefix=None, prefix=None):
     = no such slot and the results above.  With it (an empty dict included) every call is (length, slots, offsets, beam_size, kind,
     use_context, weights): kind "prefix" is an rnnt_pool_chunk_prefix call with weights = (ctc_weight, transducer_weight), every other
     kind is as above with weights None.  One (length, kind, beam size, use_context, weights) class per call -- slots with different
-    weights never share one -- in ascending order inside a round.  A slot listed in prefix is looked up in neither ctc_prefix nor beams."""
+    weights never share one -- in ascending order inside a round.  A slot listed in prefix is looked up in neither ctc_prefix nor beams.
+    A fourth element of a prefix entry is its use_context (hot-word biasing, an rnnt_pool_chunk_prefix_ctx call): biased and unbiased
+    prefix slots of one length go in two calls."""
     offs = dict(offsets)
 
     def klass(slot, length):
         if prefix is not None and slot in prefix:
-            return int(length), 3, int(prefix[slot][0]), 0, float(prefix[slot][1]), float(prefix[slot][2])
+            return int(length), 3, int(prefix[slot][0]), int(bool(prefix[slot][3])) if len(prefix[slot]) > 3 else 0, float(prefix[slot][1]), float(prefix[slot][2])
         if ctc_prefix is not None and slot in ctc_prefix:
             return int(length), 2, int(ctc_prefix[slot][0]), int(bool(ctc_prefix[slot][1])), 0.0, 0.0
         beam = int(beams.get(slot, 0)) if beams else 0
@@ -1053,7 +1090,8 @@ class StreamPool:
     call (WeNet's transducer_attention_rescoring, per slot and mid-utterance if wanted), frames(slot) reads the frames and
     token_times(slot) aligns a greedy slot's tokens over them.
     Transducer prefix beam search per slot: open(prefix_beam=k, ctc_weight=, transducer_weight=) gives the slot WeNet's CTC-fused
-    prefix beam search (rnnt_prefix_beam_decode's), carried across chunks on the device by rnnt_pool_chunk_prefix; prefix_hyps(slot)
+    prefix beam search (rnnt_prefix_beam_decode's), carried across chunks on the device by rnnt_pool_chunk_prefix (with
+    prefix_context=ContextBias: biased by hot words, rnnt_pool_chunk_prefix_ctx; the pool's one graph serves both searches); prefix_hyps(slot)
     reads the hypotheses as they stand, close(slot) returns the final ones -- those of the one-call search over the utterance's
     frames -- and rescore() takes such a slot as the first pass of the reference's own two-pass recipe."""
 
@@ -1097,6 +1135,7 @@ class StreamPool:
         self._keep: Dict[int, bool] = {}                # keep_frames of the slot's last open()
         self._ctc: Dict[int, Tuple[int, Optional[ContextBias]]] = {}   # (beam, context) of the open CTC prefix slots
         self._prefix: Dict[int, Tuple[int, float, float]] = {}   # (beam, ctc_weight, transducer_weight) of the open transducer prefix slots
+        self._prefix_ctx: Dict[int, ContextBias] = {}   # the context of the biased ones among them
         self._queue: List[Tuple[int, torch.Tensor]] = []
         self._carry: Dict[int, List[int]] = {}          # increments of other slots produced by the step inside a close()
         self._wave_queue: List[Tuple[int, torch.Tensor, bool]] = []   # PCM packets (slot, samples, final) in feed order
@@ -1110,7 +1149,7 @@ class StreamPool:
         return _stream_ptr() if (t is None and torch.cuda.is_available()) or (t is not None and t.is_cuda) else None
 
     def open(self, beam_size: int = 0, ctc_prefix_beam: int = 0, context: Optional[ContextBias] = None, keep_frames: bool = False,
-             prefix_beam: int = 0, ctc_weight: float = 0.3, transducer_weight: float = 0.7) -> int:
+             prefix_beam: int = 0, ctc_weight: float = 0.3, transducer_weight: float = 0.7, prefix_context: Optional[ContextBias] = None) -> int:
         """The lowest free slot, reset for a new utterance (reset_streaming_cache for that slot alone).  beam_size > 0: the slot's
         utterance is beam-searched with that beam (its hypotheses start as the one empty hypothesis); raises RnntError at once
         when this pool cannot do it.  ctc_prefix_beam > 0 (not together with beam_size): the slot's utterance runs the CTC prefix beam
@@ -1120,7 +1159,15 @@ class StreamPool:
         keep_frames: the slot keeps the encoder frames of its utterance on the device (rnnt_stream_keep_frames, max_cache_frames KB),
         what frames(), rescore() and token_times() read.
         prefix_beam > 0 (not together with beam_size or ctc_prefix_beam, and without context): the slot's utterance runs the
-        transducer prefix beam search with that beam and the fusion weights ctc_weight / transducer_weight (>= 0, not both 0)."""
+        transducer prefix beam search with that beam and the fusion weights ctc_weight / transducer_weight (>= 0, not both 0), biased
+        by prefix_context when given (`context` belongs to ctc_prefix_beam).  The one graph of the pool serves both kinds: a graph other
+        than the current one is refused while any biased slot of either kind is open."""
+        biased_open = any(c is not None for _, c in self._ctc.values()) or bool(self._prefix_ctx)
+        if prefix_context is not None:
+            if not prefix_beam:
+                raise RnntError("stream pool: prefix_context needs prefix_beam")
+            if prefix_context is not self._context and biased_open:
+                raise RnntError("stream pool: another context graph is in use by an open slot (one graph per pool at a time)")
         if prefix_beam:
             if beam_size or ctc_prefix_beam:
                 raise RnntError("stream pool: prefix_beam, beam_size and ctc_prefix_beam are mutually exclusive")
@@ -1135,7 +1182,7 @@ class StreamPool:
                 raise RnntError("stream pool: beam_size and ctc_prefix_beam are mutually exclusive")
             if ctc_prefix_beam < 1 or ctc_prefix_beam > min(16, self.vocab_size) or self.vocab_size > 512:
                 raise RnntError(f"stream pool: ctc_prefix_beam {ctc_prefix_beam} outside [1, min(16, vocabulary {self.vocab_size})] or vocabulary > 512")
-            if context is not None and context is not self._context and any(c is not None for _, c in self._ctc.values()):
+            if context is not None and context is not self._context and biased_open:
                 raise RnntError("stream pool: another context graph is in use by an open slot (one graph per pool at a time)")
         elif context is not None:
             raise RnntError("stream pool: context needs ctc_prefix_beam")
@@ -1144,9 +1191,10 @@ class StreamPool:
                             f"{self.vocab_size} > 512")
         if not self._free:
             raise RnntError(f"stream pool full: all {self.n} slots are open")
-        if context is not None and context is not self._context:   # before a slot is taken: the library may refuse the graph
-            self.engine.context_set(context.phrases, context.context_score)
-            self._context = context
+        graph = context if context is not None else prefix_context
+        if graph is not None and graph is not self._context:       # before a slot is taken: the library may refuse the graph
+            self.engine.context_set(graph.phrases, graph.context_score)
+            self._context = graph
         slot = self._free[0]
         self.engine.stream_open(slot, self._stream(None))
         if keep_frames:
@@ -1157,6 +1205,8 @@ class StreamPool:
             self._ctc[slot] = (int(ctc_prefix_beam), context)
         if prefix_beam:
             self._prefix[slot] = (int(prefix_beam), float(ctc_weight), float(transducer_weight))
+            if prefix_context is not None:
+                self._prefix_ctx[slot] = prefix_context
         self._offset[slot] = 0
         self._ntok[slot] = 0
         self._beam[slot] = int(beam_size)
@@ -1239,7 +1289,8 @@ class StreamPool:
         """Advance every slot that has chunks queued: one rnnt_pool_chunk call per chunk length of the greedy slots and one
         rnnt_pool_chunk_beam call per (chunk length, beam size) of the beam slots (pool_plan), the rows of a call gathered into one
         contiguous device tensor; CTC prefix slots likewise through one rnnt_pool_chunk_ctc_prefix call per (chunk length, beam size,
-        use_context), transducer prefix slots through one rnnt_pool_chunk_prefix call per (chunk length, beam size, weights).  Returns
+        use_context), transducer prefix slots through one rnnt_pool_chunk_prefix call per (chunk length, beam size, weights) -- the biased
+        ones among them through rnnt_pool_chunk_prefix_ctx calls of their own.  Returns
         {slot: tokens emitted by this step} for the GREEDY slots that advanced; a beam slot's hypotheses are read with beams(slot), a
         CTC prefix slot's with ctc_hyps(slot), a transducer prefix slot's with prefix_hyps(slot)."""
         out, self._carry = self._carry, {}
@@ -1248,13 +1299,17 @@ class StreamPool:
         if not self._queue:
             return out
         calls, offs, index = pool_plan([(slot, c.size(0)) for slot, c in self._queue], self._offset, self._beam,
-                                       {slot: (b, c is not None) for slot, (b, c) in self._ctc.items()}, self._prefix)
+                                       {slot: (b, c is not None) for slot, (b, c) in self._ctc.items()},
+                                       {slot: v + (True,) if slot in self._prefix_ctx else v for slot, v in self._prefix.items()})
         rows: List[List[Optional[torch.Tensor]]] = [[None] * len(call[1]) for call in calls]
         for (slot, c), at in zip(self._queue, index):
             rows[at[0]][at[1]] = c
         touched = []
         for (length, slots, call_offs, beam, kind, use_context, weights), chunks in zip(calls, rows):
             x = torch.stack(chunks, 0).contiguous()
+            if kind == "prefix" and use_context:
+                self.engine.pool_chunk_prefix_ctx(slots, x.data_ptr(), length, call_offs, call_offs, beam, weights[0], weights[1], True, self._stream(x))
+                continue
             if kind == "prefix":
                 self.engine.pool_chunk_prefix(slots, x.data_ptr(), length, call_offs, call_offs, beam, weights[0], weights[1], self._stream(x))
                 continue
@@ -1289,12 +1344,17 @@ class StreamPool:
             raise RnntError(f"slot {slot} is not an open CTC prefix slot")
         return [(tok, score, times) for tok, score, times, _ in self.engine.stream_ctc_prefix(slot, final, stream=self._stream(None))]
 
-    def prefix_hyps(self, slot: int):
+    def prefix_hyps(self, slot: int, final: bool = False, with_context_scores: bool = False):
         """[(tokens including the leading blank, score)] of a transducer prefix slot, best first, as they stand after the chunks
-        stepped so far.  Reading changes nothing."""
+        stepped so far.  A biased slot's scores are the totals (score + context score); final: with finalize's context scores, what
+        the one-call search returns had the utterance ended here (no re-sort); with_context_scores: (tokens, score, context score).
+        Reading changes nothing."""
         if slot not in self._prefix:
             raise RnntError(f"slot {slot} is not an open transducer prefix slot")
-        return self.engine.stream_prefix(slot, stream=self._stream(None))
+        if slot not in self._prefix_ctx and not with_context_scores:
+            return self.engine.stream_prefix(slot, stream=self._stream(None))
+        hyps = self.engine.stream_prefix_ctx(slot, final, stream=self._stream(None))
+        return hyps if with_context_scores else [(tok, score) for tok, score, _ in hyps]
 
     def _require_kept(self, slot: int):
         if slot not in self._offset or not self._keep.get(slot, False):
@@ -1308,7 +1368,7 @@ class StreamPool:
 
     def rescore(self, slots: List[int], ctc_weight: float, transducer_weight: float):
         """The second pass for CTC prefix and transducer prefix slots opened with keep_frames=True: per slot ctc_hyps(final=True) --
-        or prefix_hyps with the leading blank dropped and the search's score as the first score, the reference's default first pass
+        or prefix_hyps (a biased slot's final totals) with the leading blank dropped and the search's score as the first score, the reference's default first pass
         (beam_search_type="transducer", wenet/transducer/transducer.py:327) --, then ONE
         rnnt_pool_rescore call for all listed slots -- every hypothesis re-scored with the transducer likelihood over the slot's kept
         frames -- then the choice of rnnt_rescore_select_host with total = ctc_score * ctc_weight + td_score * transducer_weight.
@@ -1319,7 +1379,7 @@ class StreamPool:
             if slot not in self._ctc and slot not in self._prefix:
                 raise RnntError(f"slot {slot} is not an open CTC prefix or transducer prefix slot")
             self._require_kept(slot)
-        first = [[(tok[1:], sc) for tok, sc in self.prefix_hyps(slot)] if slot in self._prefix else
+        first = [[(tok[1:], sc) for tok, sc in self.prefix_hyps(slot, final=True)] if slot in self._prefix else
                  [(tok, sc) for tok, sc, _ in self.ctc_hyps(slot, final=True)] for slot in slots]
         nh, hl, ht = pack_nbest([[tok for tok, _ in row] for row in first])
         nll = self.engine.pool_rescore(slots, nh, hl, ht, self._stream(None))
@@ -1346,7 +1406,7 @@ class StreamPool:
 
     def close(self, slot: int):
         """Finish the slot's utterance (queued chunks are processed first) and free the slot; returns all its tokens (greedy slot),
-        its final hypotheses (beam slot), ctc_hyps(slot, final=True) (CTC prefix slot) or prefix_hyps(slot) (transducer prefix slot)."""
+        its final hypotheses (beam slot), ctc_hyps(slot, final=True) (CTC prefix slot) or prefix_hyps(slot, final=True) (transducer prefix slot)."""
         if slot not in self._offset:
             raise RnntError(f"slot {slot} is not open")
         if self._fed.get(slot) == "wave" and not self._wave_final[slot]:
@@ -1356,8 +1416,9 @@ class StreamPool:
         self._carry.pop(slot, None)
         self._forget_wave(slot)
         if slot in self._prefix:
-            res = self.prefix_hyps(slot)
+            res = self.prefix_hyps(slot, final=True)
             del self._prefix[slot]
+            self._prefix_ctx.pop(slot, None)
         elif slot in self._ctc:
             res = self.ctc_hyps(slot, final=True)
             del self._ctc[slot]

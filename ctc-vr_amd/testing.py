@@ -507,6 +507,32 @@ class context_graph_ref:
         return scores, states, self.finalize(state)
 
 
+def prefix_merge_ctx_ref(hyps, top_lp, top_tok, blank, beam_size, graph):
+    """prefix_merge_ref with hot-word biasing (wenet/transformer/search.py:95-104,169-171,214-235 carried over to the transducer
+    frame step).  hyps [(tokens, score, context state, context score)], graph: a context_graph_ref.  A blank candidate copies its
+    parent's context state and score (copy_context), any other token takes graph.step from the parent's state and adds the step's
+    score to the parent's (update_context); fusion is prefix_merge_ref's and keeps the first candidate's context (a function of the
+    token sequence alone); stable descending sort by fused score + context score; truncation.
+    Returns [(tokens, fused score, src_row, src_slot, context state, context score)]."""
+    k = len(top_lp[0])
+    plain = prefix_merge_ref([(h[0], h[1]) for h in hyps], top_lp, top_tok, blank, len(hyps) * k)     # every fused survivor, keyed by its first candidate
+    out = []
+    for toks, score, j, slot in plain:
+        state, cs = int(hyps[j][2]), float(hyps[j][3])
+        if slot == 1:
+            step, state = graph.step(state, int(toks[-1]))
+            cs = cs + step
+        out.append((toks, score, j, slot, state, cs))
+    first = {}
+    for j in range(len(hyps)):                                       # candidate order of the survivors: prefix_merge_ref's sort lost it
+        for tok in top_tok[j]:
+            key = tuple(hyps[j][0]) + (() if int(tok) == blank else (int(tok),))
+            first.setdefault(key, len(first))
+    out.sort(key=lambda v: first[tuple(v[0])])
+    out.sort(key=lambda v: v[1] + v[5], reverse=True)
+    return out[:beam_size]
+
+
 def _log_add2(a, b):
     if a == -math.inf and b == -math.inf:
         return -math.inf

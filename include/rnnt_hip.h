@@ -362,6 +362,37 @@ int rnnt_prefix_merge_device(rnnt_ctx* ctx, int32_t n_hyp, const int32_t* hyp_le
                              const float* top_lp, const int32_t* top_tok, int32_t k, int32_t blank, int32_t beam_size,
                              int32_t* out_len, int32_t* out_tokens, double* out_score, int32_t* out_src_row, int32_t* out_src_slot,
                              void* stream);
+/* -- hot-word biasing in the prefix beam search (the graph of rnnt_context_set, below) -------------------------------------------
+ * The reference's transducer search has no context graph; the semantics are those of wenet/transformer/search.py:95-104,169-171,
+ * 214-235 carried over to this frame step.  Every hypothesis holds a context state (graph node; [blank] holds the root, the leading
+ * blank is never fed to the graph) and an f64 context score beside its running score.  prefix_step is untouched: the first prune
+ * does not see the graph (search.py:156).  In prefix_merge a blank candidate copies its parent's state and score, any other token
+ * takes one forward_one_step from the parent's state and adds its score; prefix fusion keeps the first candidate's (both are
+ * functions of the token sequence); the second prune orders by total = fused score + context score, equal totals to the lower
+ * candidate index.  At the end of the utterance finalize REPLACES the context score of every survivor; there is no re-sort, so the
+ * returned totals need not descend.  A graph whose context_score is 0 gives the unbiased tokens and scores exactly.
+ *
+ * rnnt_prefix_beam_decode plus use_context and ctx_scores_host [B, beam_size] (may be NULL): scores_host are the totals,
+ * ctx_scores_host their context part (unbiased score = score - context score).  use_context == 0 is rnnt_prefix_beam_decode, bit
+ * for bit, with context scores 0.  Also RNNT_ERR_STATE: use_context without a graph set, decided before the first launch. */
+int rnnt_prefix_beam_decode_ctx(rnnt_ctx* ctx, const float* enc_dev, const int32_t* enc_lens_host, int32_t B, int32_t T, int32_t beam_size,
+                                float ctc_weight, float transducer_weight, int32_t use_context, int32_t cap_tokens, int32_t* n_hyp_host,
+                                int32_t* lens_host, int32_t* tokens_host, double* scores_host, double* ctx_scores_host, float* h_host,
+                                float* c_host, void* stream);
+/* rnnt_prefix_merge_host with a graph, passed as phrases as rnnt_ctc_prefix_beam_host takes them (n_phrases >= 1; tokens only need
+ * to be >= 0): plus hyp_ctx_state / hyp_ctx_score [n_hyp] in (node ids of that graph, creation order, root = 0) and the survivors'
+ * out_ctx_state / out_ctx_score out.  out_score stays the fused score; the order is by out_score + out_ctx_score. */
+int rnnt_prefix_merge_ctx_host(int32_t n_hyp, const int32_t* hyp_len, const int32_t* hyp_tokens, const double* hyp_score,
+                               const int32_t* hyp_ctx_state, const double* hyp_ctx_score, const float* top_lp, const int32_t* top_tok,
+                               int32_t k, int32_t blank, int32_t beam_size, int32_t n_phrases, const int32_t* phrase_lens,
+                               const int32_t* phrase_tokens, double context_score, int32_t* out_len, int32_t* out_tokens, double* out_score,
+                               int32_t* out_src_row, int32_t* out_src_slot, int32_t* out_ctx_state, double* out_ctx_score);
+/* The same through ONE prefix_merge launch with the graph that is set on the context (none: RNNT_ERR_STATE; a context state outside
+ * the graph: RNNT_ERR_ARG).  Synchronises. */
+int rnnt_prefix_merge_ctx_device(rnnt_ctx* ctx, int32_t n_hyp, const int32_t* hyp_len, const int32_t* hyp_tokens, const double* hyp_score,
+                                 const int32_t* hyp_ctx_state, const double* hyp_ctx_score, const float* top_lp, const int32_t* top_tok,
+                                 int32_t k, int32_t blank, int32_t beam_size, int32_t* out_len, int32_t* out_tokens, double* out_score,
+                                 int32_t* out_src_row, int32_t* out_src_slot, int32_t* out_ctx_state, double* out_ctx_score, void* stream);
 
 /* -- CTC prefix beam search with contextual biasing: WeNet's ctc_prefix_beam_search (wenet/transformer/search.py:125-247) --------- */
 /* The context graph ("hot words") of wenet/utils/context_graph.py:144-210 over n_phrases token lists (phrase_tokens_host holds them
@@ -498,6 +529,25 @@ int rnnt_pool_chunk_prefix(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots
  * the longest list: 1 + the frames walked).  cap_hyps / cap_tokens are ignored. */
 int rnnt_stream_get_prefix(rnnt_ctx* ctx, int32_t slot, int32_t cap_hyps, int32_t cap_tokens, int32_t* n_hyp, int32_t* lens_host,
                            int32_t* tokens_host, double* scores_host, float* h_host, float* c_host, void* stream);
+/* The pool calls with hot-word biasing (semantics: rnnt_prefix_beam_decode_ctx): the calls above plus use_context; the rows also keep
+ * a context state (int) and score (f64) per hypothesis in both buffer sets, counted by rnnt_live_device_bytes.  A slot's first
+ * advancing call fixes use_context together with the beam and the two weights until its reset; a differing value: RNNT_ERR_ARG.
+ * The graph-generation rule of the CTC pool search applies: after rnnt_context_set a search biased under an older generation is
+ * refused with RNNT_ERR_STATE until its slot is reset, unbiased searches go on; use_context without a graph: RNNT_ERR_STATE.  Every
+ * refusal is decided before the first launch and moves no slot.  A call lists slots of one use_context. */
+int rnnt_pool_prefix_frames_ctx(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, const float* enc_dev, int32_t t,
+                                int32_t beam_size, float ctc_weight, float transducer_weight, int32_t use_context, void* stream);
+int rnnt_pool_chunk_prefix_ctx(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, const float* fbank_dev, int32_t chunk_frames,
+                               const int32_t* offsets_host, const int32_t* required_host, int32_t beam_size, float ctc_weight,
+                               float transducer_weight, int32_t use_context, int32_t* frames_out, void* stream);
+/* rnnt_stream_get_prefix plus final and ctx_scores_host [cap_hyps] (may be NULL): scores_host are the totals, ctx_scores_host their
+ * context part -- the running one, or with final != 0 finalize's: what rnnt_prefix_beam_decode_ctx would return had the utterance
+ * ended here (no re-sort).  Reading changes nothing.  final != 0 on a search biased under an older graph generation: RNNT_ERR_STATE.
+ * An unbiased slot reads as rnnt_stream_get_prefix does, with context scores 0; so does a fresh slot, except that with final != 0 and
+ * a graph set it finalizes its root, as the one-call search over no frames does. */
+int rnnt_stream_get_prefix_ctx(rnnt_ctx* ctx, int32_t slot, int32_t final, int32_t cap_hyps, int32_t cap_tokens, int32_t* n_hyp,
+                               int32_t* lens_host, int32_t* tokens_host, double* scores_host, double* ctx_scores_host, float* h_host,
+                               float* c_host, void* stream);
 
 /* The same search as a pure C++ function (no context, no GPU): lp_host [B, T, vocab], the graph passed as phrases (n_phrases == 0:
  * none).  The CPU seam the device path is compared against: tokens, times and order exact. */
