@@ -29,8 +29,7 @@ int rnnt_beam_frame(rnnt_ctx* ctx, int32_t frame_idx, int32_t n_rows, const int3
     if (ctx->use_beam_chain && V <= 512) {   // one resident workgroup per row runs its whole extension chain
         BeamChainP c;
         memset(&c, 0, sizeof(c));
-        c.whh = ctx->whh_il; c.egate = ctx->egate; c.wpr = ctx->wpr; c.bpr = ctx->bpr; c.wpf = ctx->wpf; c.bpf = ctx->bpf;
-        c.wout = ctx->wout; c.bout = ctx->bout; c.encp = ctx->encp; c.pool = pool; c.frame = ctx->b_frame; c.tok_in = ctx->b_tok;
+        dec_weights(ctx, c); c.encp = ctx->encp; c.pool = pool; c.frame = ctx->b_frame; c.tok_in = ctx->b_tok;
         c.steps = ctx->b_steps; c.blank_lp = ctx->b_blank; c.top_lp = ctx->b_toplp; c.top_tok = ctx->b_toptok;
         c.vocab = V; c.blank = ctx->cfg.blank_id; c.k = beam_k; c.n_steps = NS; c.slots = slots;
         hipLaunchKernelGGL(beam_chain, dim3(R), dim3(512), 0, s, c);
@@ -348,8 +347,7 @@ int rnnt_beam_decode(rnnt_ctx* ctx, int32_t frame_begin, const int32_t* frame_en
     // ---- frame loop: launches only ----------------------------------------------------------------------------------------------
     BeamChainP c;
     memset(&c, 0, sizeof(c));
-    c.whh = ctx->whh_il; c.egate = ctx->egate; c.wpr = ctx->wpr; c.bpr = ctx->bpr; c.wpf = ctx->wpf; c.bpf = ctx->bpf;
-    c.wout = ctx->wout; c.bout = ctx->bout; c.encp = ctx->encp; c.frame = ctx->b_frame; c.tok_in = ctx->b_tok; c.live = ctx->b_active;
+    dec_weights(ctx, c); c.encp = ctx->encp; c.frame = ctx->b_frame; c.tok_in = ctx->b_tok; c.live = ctx->b_active;
     c.steps = ctx->b_steps; c.blank_lp = ctx->b_blank; c.top_lp = ctx->b_toplp; c.top_tok = ctx->b_toptok;
     c.vocab = V; c.blank = ctx->cfg.blank_id; c.k = k; c.n_steps = NS; c.slots = slots;
     for (int f = frame_begin; f < fmax; ++f) {

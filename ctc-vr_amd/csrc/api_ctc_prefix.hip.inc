@@ -305,20 +305,6 @@ int rnnt_ctc_prefix_beam_host(const float* lp_host, const int32_t* enc_lens_host
     return RNNT_OK;
 }
 
-// The block of a search's results that is downloaded in one copy, on the device or in its host copy: n_hyp [B] | lens [R] |
-// tokens [R][lcap] | times [R][lcap]; total: its ints.
-struct CpOut { int *nh, *len, *tok, *time; size_t total; };
-static CpOut cp_out(Carve<int>& c, size_t B, size_t R, size_t lcap) {
-    CpOut o;
-    const size_t at = c.off;
-    o.nh = c.take(B);
-    o.len = c.take(R);
-    o.tok = c.take(R * lcap);
-    o.time = c.take(R * lcap);
-    o.total = c.off - at;
-    return o;
-}
-
 // ctc_prefix_beam_search over log-probabilities lp_dev [B, T, vocab] already on the device: one upload (the lengths), ONE launch of
 // ctc_prefix_search (one workgroup per utterance, frame loop inside, results packed by its epilogue), one download, one
 // synchronisation.  Any context; weights are not needed.  Touches only its own buffers.
@@ -370,17 +356,7 @@ int rnnt_ctc_prefix_beam_logprobs(rnnt_ctx* ctx, const float* lp_dev, const int3
     HIPCHK(hipStreamSynchronize(s));
     Carve<int> hc{oi.data()};
     const CpOut h = cp_out(hc, B, R, lcap);
-    memcpy(n_hyp_host, h.nh, B * sizeof(int));
-    memcpy(lens_host, h.len, R * sizeof(int));
-    memcpy(scores_host, od.data(), R * sizeof(double));
-    if (ctx_scores_host) memcpy(ctx_scores_host, od.data() + R, R * sizeof(double));
-    std::fill(tokens_host, tokens_host + R * cap_tokens, 0);
-    std::fill(times_host, times_host + R * cap_tokens, 0);
-    const size_t ncopy = std::min<size_t>(lcap, cap_tokens);
-    for (size_t r = 0; r < R; ++r) {
-        memcpy(tokens_host + r * cap_tokens, h.tok + r * lcap, ncopy * sizeof(int));
-        memcpy(times_host + r * cap_tokens, h.time + r * lcap, ncopy * sizeof(int));
-    }
+    cp_out_copy(h, od.data(), B, R, lcap, R, (size_t)cap_tokens, n_hyp_host, lens_host, tokens_host, times_host, scores_host, ctx_scores_host);
     return RNNT_OK;
 }
 

@@ -37,6 +37,8 @@ int rnnt_create(const rnnt_config* cfg, rnnt_ctx** out) {
     if (const char* e_ = getenv("RNNT_CONV1_FUSE")) ctx->conv1_fuse = atoi(e_);
     if (const char* se = getenv("RNNT_WF_SUB_ASYNC")) ctx->wf_sub_async = (se[0] == '0') ? 0 : 1;
     const int B = cfg->max_streams;
+    ctx->slot = std::vector<PoolSlot>((size_t)B);   // max_streams is fixed here, so the pool's per-slot host state is too
+    ctx->hs_buf = std::vector<DevBuf<float>>((size_t)B);
     ctx->tmax = sub_len(cfg->max_chunk_frames);
     ctx->t1max = sub1_len(cfg->max_chunk_frames);
     ctx->cap = RNNT_LORDER + WF_MERGE_MAX * ctx->tmax;   // several chunks of one layer may be in flight in one wavefront stage
@@ -491,7 +493,7 @@ int rnnt_streams_reset(rnnt_ctx* ctx, int32_t n_streams, void* stream) {
     ctx->frames_buffered = 0; ctx->frames_decoded = 0;
     ctx->launches = 0; ctx->greedy_steps = 0;
     ctx->pool_mode = false;                      // all slots share one position again
-    ctx->slot_pos.assign(B, SlotPos{0, 0, 0});
+    for (PoolSlot& q : ctx->slot) q.pos = SlotPos{0, 0, 0};
     hipLaunchKernelGGL(conv_ring_init, dim3(grid_for((long long)L * B * ctx->cap * D)), dim3(256), 0, s, ctx->gring, ctx->xring, ctx->glu0, B, ctx->cap);
     LAUNCHCHK("conv_ring_init");
     hipLaunchKernelGGL(decode_state_reset, dim3(grid_for((long long)2 * B * D)), dim3(256), 0, s, ctx->h, ctx->c, ctx->sel, ctx->key, ctx->fidx, ctx->nsym,
@@ -502,10 +504,5 @@ int rnnt_streams_reset(rnnt_ctx* ctx, int32_t n_streams, void* stream) {
         ctx->pool_cur = 0;
         HIPCHK(hipMemsetAsync(ctx->pool[0], 0, (size_t)ctx->max_rows * (ctx->cfg.n_steps + 1) * 512 * sizeof(float), s));
     }
-    int rc;
-    pool_wave_reset(ctx, 0, B);                             // the per-slot streaming front-ends of the stream pool
-    if ((rc = pool_beam_reset(ctx, s, 0, B))) return rc;   // the per-slot beam state of the stream pool, once it exists
-    if ((rc = pool_hist_reset(ctx, s, 0, B))) return rc;   // no slot keeps its encoder frames
-    if ((rc = pool_ctc_reset(ctx, s, 0, B))) return rc;    // its per-slot CTC prefix searches
-    return pool_prefix_reset(ctx, s, 0, B);                 // and its per-slot transducer prefix searches
+    return pool_slot_reset(ctx, s, 0, B);   // the per-slot states of the stream pool
 }

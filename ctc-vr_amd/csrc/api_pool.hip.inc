@@ -3,7 +3,7 @@
 //
 // Every stream's state already lives per stream on the device (K/V cache, the two conv rings, LSTM h/c, last token, token buffer);
 // the lock-step entry points only share its POSITION (SlotPos: cache_len, kv_start, conv_pos).  Here the position is per slot: plain
-// host integers in ctx->slot_pos, planned and advanced by the same SlotPos methods as ctx->pos, and mirrored for each call into one
+// host integers in ctx->slot[b].pos, planned and advanced by the same SlotPos methods as ctx->pos, and mirrored for each call into one
 // small device table (PoolRow per active row + the slot list of the decoder), written by ONE async copy from pinned memory.  The
 // rows of a call are compact -- row i * t' + f is frame f of active row i -- and every access to per-stream storage goes through
 // slots[i]: the K/V and ring appends through GemmP::c_tab, attention / depthwise conv / decoder through their pool forms.  Idle
@@ -17,12 +17,7 @@
 namespace {
 
 int pool_alloc(rnnt_ctx* ctx) {
-    const size_t n = (size_t)ctx->cfg.max_streams * (POOL_ROW_INTS + 2);   // + the slot list + the beam buffer index per active row
-    int rc;
-    if ((rc = reserve(ctx, ctx->pool_tab, n))) return rc;
-    if ((rc = reserve(ctx, ctx->pool_tab_host, n))) return rc;
-    if (!ctx->pool_ev) HIPCHK(hipEventCreateWithFlags(&ctx->pool_ev, hipEventDisableTiming));
-    return RNNT_OK;
+    return calltab_alloc(ctx, ctx->pool_tab, (size_t)ctx->cfg.max_streams * (POOL_ROW_INTS + 2));   // + the slot list + the beam buffer index per active row
 }
 
 // the per-slot beam state (rnnt_ctx::ps_*), on the first beam call of a context with max_beam > 0: every slot starts with one
@@ -38,15 +33,13 @@ int pool_beam_alloc(rnnt_ctx* ctx, hipStream_t s) {
     if ((rc = reserve(ctx, ctx->ps_sc, 2 * R))) return rc;
     if ((rc = reserve(ctx, ctx->ps_hs, 2 * R))) return rc;
     if ((rc = reserve(ctx, ctx->ps_nh, B))) return rc;   // last: its presence says the state exists (pool_beam_reset)
-    ctx->ps_cur.assign(B, 0);
-    ctx->ps_lbound.assign(B, 0);
     return pool_beam_reset(ctx, s, 0, (int)B);
 }
 
 // from here on every slot has its own position (the lock-step entry points refuse until rnnt_streams_reset)
 void pool_enter(rnnt_ctx* ctx) {
     if (ctx->pool_mode) return;
-    ctx->slot_pos.assign(ctx->cfg.max_streams, ctx->pos);
+    for (PoolSlot& q : ctx->slot) q.pos = ctx->pos;
     ctx->pool_mode = true;
 }
 
@@ -112,13 +105,9 @@ int rnnt_stream_open(rnnt_ctx* ctx, int32_t slot, void* stream) {
                        ctx->cfg.max_streams, ctx->cap, slot, ctx->h, ctx->c, ctx->sel, ctx->key, ctx->fidx, ctx->nsym, ctx->count, ctx->tok,
                        ctx->cfg.blank_id);
     LAUNCHCHK("stream_slot_reset");
-    if ((rc = pool_beam_reset(ctx, s, slot, 1))) return rc;   // the slot's beam: one empty hypothesis (once the beam state exists)
-    if ((rc = pool_ctc_reset(ctx, s, slot, 1))) return rc;    // the slot's CTC prefix search: the start hypothesis (likewise)
-    if ((rc = pool_prefix_reset(ctx, s, slot, 1))) return rc; // the slot's transducer prefix search: [blank] (likewise)
-    pool_wave_reset(ctx, slot, 1);                            // the slot's streaming front-end: no samples, no frames
-    if ((rc = pool_hist_reset(ctx, s, slot, 1))) return rc;   // the slot keeps no encoder frames unless asked again
+    if ((rc = pool_slot_reset(ctx, s, slot, 1))) return rc;
     pool_enter(ctx);
-    ctx->slot_pos[slot] = SlotPos{0, 0, 0};
+    ctx->slot[slot].pos = SlotPos{0, 0, 0};
     return RNNT_OK;
 }
 
@@ -146,47 +135,45 @@ int pool_chunk_run(rnnt_ctx* ctx, const char* fn, int32_t n_active, const int32_
     if (ctx->frames_buffered != 0)
         return fail(ctx, RNNT_ERR_STATE, "%s: %d buffered frames of an earlier call (rnnt_frames_discard / rnnt_frames_consume first)", fn, ctx->frames_buffered);
     const int n = n_active;
-    if (n < 1 || n > ctx->n_streams) return fail(ctx, RNNT_ERR_ARG, "%s: %d active slots of %d", fn, n, ctx->n_streams);
-    if (T < 7 || T > ctx->cfg.max_chunk_frames) return fail(ctx, RNNT_ERR_SHAPE, "chunk of %d frames outside [7, %d]", T, ctx->cfg.max_chunk_frames);
-    const int tq = sub_len(T);
-    if (tq > ctx->fcap) return fail(ctx, RNNT_ERR_SHAPE, "encoder-frame buffer capacity %d exceeded", ctx->fcap);
+    int tq = 0;
     // ---- validate every listed slot before anything changes: a wrong slot is a write into another caller's cache --------------------
-    auto pos_of = [&](int slot) { return ctx->pool_mode ? ctx->slot_pos[slot] : ctx->pos; };
     std::string err;
-    std::vector<char> seen((size_t)ctx->n_streams, 0);
-    std::vector<PoolRow> rows((size_t)n);
-    for (int i = 0; i < n; ++i) {
-        const int slot = slots_host[i];
-        if (slot < 0 || slot >= ctx->n_streams) return fail(ctx, RNNT_ERR_ARG, "%s: row %d: slot %d outside [0, %d)", fn, i, slot, ctx->n_streams);
-        if (seen[slot]) return fail(ctx, RNNT_ERR_ARG, "%s: slot %d listed twice", fn, slot);
-        seen[slot] = 1;
+    std::vector<PoolRow> rows;
+    hipStream_t s = (hipStream_t)stream;
+    int rc = pool_slots_check(ctx, fn, n, slots_host, ctx->n_streams, "active slots", [&] {
+        if (T < 7 || T > ctx->cfg.max_chunk_frames) return fail(ctx, RNNT_ERR_SHAPE, "chunk of %d frames outside [7, %d]", T, ctx->cfg.max_chunk_frames);
+        tq = sub_len(T);
+        if (tq > ctx->fcap) return fail(ctx, RNNT_ERR_SHAPE, "encoder-frame buffer capacity %d exceeded", ctx->fcap);
+        rows.resize((size_t)n);
+        return (int)RNNT_OK;
+    }, [&](int i, int slot) {
         ChunkInfo k;
-        if (!pos_of(slot).plan(tq, offsets_host[i], ctx->tcap, k, err)) return fail(ctx, RNNT_ERR_SHAPE, "slot %d: %s", slot, err.c_str());
+        if (!(ctx->pool_mode ? ctx->slot[slot].pos : ctx->pos).plan(tq, offsets_host[i], ctx->tcap, k, err)) return fail(ctx, RNNT_ERR_SHAPE, "slot %d: %s", slot, err.c_str());
         PoolRow& r = rows[i];
         r.slot = slot; r.T2 = k.T2; r.kv_row0 = k.kv_row0; r.pos_start = k.pos_start; r.ring_pos = k.ring_pos;
         r.kv_w0 = k.kv_w0(); r.ring_w0 = k.ring_pos % ctx->cap; r.zero = 0;
-        if (int hrc = pool_hist_check(ctx, fn, slot, tq)) return hrc;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    int rc;
+        return pool_hist_check(ctx, fn, slot, tq);
+    });
+    if (rc) return rc;
     if (mode == POOL_BEAM) {
-        // token capacity: a hypothesis grows by at most n_steps tokens per frame.  ps_lbound is a conservative bound of the slot's
+        // token capacity: a hypothesis grows by at most n_steps tokens per frame.  beam_lbound is a conservative bound of the slot's
         // longest one; only when it would pass max_tokens is it refreshed from the device's lengths (one small synchronising copy, rare)
         const int grow_by = tq * NS;
         for (int i = 0; i < n; ++i) {
             const int slot = rows[i].slot;
+            PoolSlot& q = ctx->slot[slot];
             if (!ctx->ps_nh) {
                 if (grow_by > ctx->cfg.max_tokens) return fail(ctx, RNNT_ERR_SHAPE, "%s: slot %d: %d new tokens possible, max_tokens %d", fn, slot, grow_by, ctx->cfg.max_tokens);
                 continue;
             }
-            if (ctx->ps_lbound[slot] + grow_by <= ctx->cfg.max_tokens) continue;
+            if (q.beam_lbound + grow_by <= ctx->cfg.max_tokens) continue;
             std::vector<int> len((size_t)W + 1);
-            HIPCHK(hipMemcpyAsync(len.data(), ctx->ps_len + (size_t)ctx->ps_cur[slot] * ctx->max_rows + (size_t)slot * W, W * sizeof(int), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(len.data(), ctx->ps_len + (size_t)q.beam_cur * ctx->max_rows + (size_t)slot * W, W * sizeof(int), hipMemcpyDeviceToHost, s));
             HIPCHK(hipMemcpyAsync(len.data() + W, ctx->ps_nh + slot, sizeof(int), hipMemcpyDeviceToHost, s));
             HIPCHK(hipStreamSynchronize(s));
             int longest = 0;
             for (int h = 0; h < len[W] && h < W; ++h) longest = std::max(longest, len[h]);
-            ctx->ps_lbound[slot] = longest;
+            q.beam_lbound = longest;
             if (longest + grow_by > ctx->cfg.max_tokens)
                 return fail(ctx, RNNT_ERR_SHAPE, "%s: slot %d: longest hypothesis %d + %d new tokens possible exceeds max_tokens %d", fn, slot, longest, grow_by, ctx->cfg.max_tokens);
         }
@@ -203,15 +190,15 @@ int pool_chunk_run(rnnt_ctx* ctx, const char* fn, int32_t n_active, const int32_
     if ((rc = pool_alloc(ctx))) return rc;
     if (mode == POOL_BEAM && (rc = pool_beam_alloc(ctx, s))) return rc;
     // ---- the call's table: one async copy, no synchronisation before the launches ---------------------------------------------------
-    HIPCHK(hipEventSynchronize(ctx->pool_ev));             // the previous call's copy has left the pinned buffer (normally long ago)
-    memcpy(ctx->pool_tab_host, rows.data(), (size_t)n * sizeof(PoolRow));
-    for (int i = 0; i < n; ++i) ctx->pool_tab_host[(size_t)n * POOL_ROW_INTS + i] = rows[i].slot;
+    int* tab;
+    if ((rc = calltab_fill(ctx, ctx->pool_tab, tab))) return rc;
+    memcpy(tab, rows.data(), (size_t)n * sizeof(PoolRow));
+    for (int i = 0; i < n; ++i) tab[(size_t)n * POOL_ROW_INTS + i] = rows[i].slot;
     const bool with_cur = mode == POOL_BEAM || mode == POOL_PREFIX;   // the searches with two buffer sets: the slot's current one
     if (with_cur)
-        for (int i = 0; i < n; ++i) ctx->pool_tab_host[(size_t)n * (POOL_ROW_INTS + 1) + i] = mode == POOL_BEAM ? ctx->ps_cur[rows[i].slot] : ctx->pp_cur[rows[i].slot];
-    HIPCHK(hipMemcpyAsync(ctx->pool_tab, ctx->pool_tab_host, (size_t)n * (POOL_ROW_INTS + (with_cur ? 2 : 1)) * sizeof(int), hipMemcpyHostToDevice, s));
-    HIPCHK(hipEventRecord(ctx->pool_ev, s));
-    const PoolRow* rows_dev = reinterpret_cast<const PoolRow*>(ctx->pool_tab.p);
+        for (int i = 0; i < n; ++i) tab[(size_t)n * (POOL_ROW_INTS + 1) + i] = mode == POOL_BEAM ? ctx->slot[rows[i].slot].beam_cur : ctx->slot[rows[i].slot].prefix_cur;
+    if ((rc = calltab_send(ctx, ctx->pool_tab, (size_t)n * (POOL_ROW_INTS + (with_cur ? 2 : 1)), s))) return rc;
+    const PoolRow* rows_dev = reinterpret_cast<const PoolRow*>(ctx->pool_tab.dev.p);
     const int* slots_dev = ctx->pool_tab + (size_t)n * POOL_ROW_INTS;
     pool_enter(ctx);
     {
@@ -230,14 +217,13 @@ int pool_chunk_run(rnnt_ctx* ctx, const char* fn, int32_t n_active, const int32_
         }
         if ((rc = launch_gemm(ctx, s, &g, 1, TAG_ENC_PROJ))) return rc;
     }
-    for (int i = 0; i < n; ++i) ctx->slot_pos[rows[i].slot].advance(rows[i].T2, tq, required_host[i]);
+    for (int i = 0; i < n; ++i) ctx->slot[rows[i].slot].pos.advance(rows[i].T2, tq, required_host[i]);
     if (frames_out) *frames_out = tq;
     if (mode == POOL_BEAM) {
         // ---- the per-frame loop of _decode_chunk_beam_search over frames [0, t') of exactly the active slots: launches only -------------
         BeamChainP c;
         memset(&c, 0, sizeof(c));
-        c.whh = ctx->whh_il; c.egate = ctx->egate; c.wpr = ctx->wpr; c.bpr = ctx->bpr; c.wpf = ctx->wpf; c.bpf = ctx->bpf;
-        c.wout = ctx->wout; c.bout = ctx->bout; c.encp = ctx->encp;
+        dec_weights(ctx, c); c.encp = ctx->encp;
         c.steps = ctx->b_steps; c.blank_lp = ctx->b_blank; c.top_lp = ctx->b_toplp; c.top_tok = ctx->b_toptok;
         c.vocab = V; c.blank = ctx->cfg.blank_id; c.k = beam_size < V - 1 ? beam_size : V - 1; c.n_steps = NS; c.slots = NS + 1;   // :467
         BeamMergeP m;
@@ -255,8 +241,8 @@ int pool_chunk_run(rnnt_ctx* ctx, const char* fn, int32_t n_active, const int32_
             LAUNCHCHK("beam_merge_pool");
         }
         for (int i = 0; i < n; ++i) {
-            ctx->ps_cur[rows[i].slot] ^= tq & 1;
-            ctx->ps_lbound[rows[i].slot] += tq * NS;
+            ctx->slot[rows[i].slot].beam_cur ^= tq & 1;
+            ctx->slot[rows[i].slot].beam_lbound += tq * NS;
         }
         return RNNT_OK;   // the frames are consumed: frames_buffered stays 0
     }
@@ -336,7 +322,7 @@ int pool_beam_peek(rnnt_ctx* ctx, const char* fn, int slot, hipStream_t s, std::
     if ((rc = pool_beam_alloc(ctx, s))) return rc;
     const int W = ctx->cfg.max_beam;
     len.assign((size_t)W + 1, 0);
-    HIPCHK(hipMemcpyAsync(len.data(), ctx->ps_len + (size_t)ctx->ps_cur[slot] * ctx->max_rows + (size_t)slot * W, W * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(len.data(), ctx->ps_len + (size_t)ctx->slot[slot].beam_cur * ctx->max_rows + (size_t)slot * W, W * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(len.data() + W, ctx->ps_nh + slot, sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     nh = len[W];
@@ -354,7 +340,7 @@ int rnnt_stream_get_beam(rnnt_ctx* ctx, int32_t slot, int32_t cap_hyps, int32_t 
     if (n_hyp) *n_hyp = nh;
     if (!lens_host && !tokens_host && !scores_host) return RNNT_OK;
     if (cap_hyps < nh) return fail(ctx, RNNT_ERR_ARG, "rnnt_stream_get_beam: %d hypotheses, room for %d", nh, cap_hyps);
-    const size_t row0 = (size_t)ctx->ps_cur[slot] * ctx->max_rows + (size_t)slot * ctx->cfg.max_beam, lcap = (size_t)ctx->cfg.max_tokens;
+    const size_t row0 = (size_t)ctx->slot[slot].beam_cur * ctx->max_rows + (size_t)slot * ctx->cfg.max_beam, lcap = (size_t)ctx->cfg.max_tokens;
     for (int i = 0; i < nh; ++i) {
         if (lens_host) lens_host[i] = len[i];
         if (!tokens_host || len[i] == 0) continue;
@@ -376,7 +362,7 @@ int rnnt_stream_get_beam_states(rnnt_ctx* ctx, int32_t slot, int32_t cap_hyps, f
     if (cap_hyps < nh) return fail(ctx, RNNT_ERR_ARG, "rnnt_stream_get_beam_states: %d hypotheses, room for %d", nh, cap_hyps);
     if (nh == 0) return RNNT_OK;
     const size_t pitch = (size_t)(ctx->cfg.n_steps + 1) * 512 * sizeof(float);
-    const float* pool = ctx->ps_pool[ctx->ps_cur[slot]] + (size_t)slot * ctx->cfg.max_beam * (ctx->cfg.n_steps + 1) * 512;
+    const float* pool = ctx->ps_pool[ctx->slot[slot].beam_cur] + (size_t)slot * ctx->cfg.max_beam * (ctx->cfg.n_steps + 1) * 512;
     HIPCHK(hipMemcpy2DAsync(h_host, D * sizeof(float), pool, pitch, D * sizeof(float), nh, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpy2DAsync(c_host, D * sizeof(float), pool + D, pitch, D * sizeof(float), nh, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));

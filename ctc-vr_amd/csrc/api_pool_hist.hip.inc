@@ -6,7 +6,7 @@
 // after_norm rows -- the encoder output before the joint projection, what rnnt_get_enc_frames returns -- to an owning device buffer
 // [max_cache_frames][256] of the slot: max_cache_frames KB, allocated on the first keep, reused by the slot's later utterances, freed
 // with the context.  The device finds a row's destination through hs_ptr / hs_len [max_streams] (null / 0 while a slot keeps none);
-// the host mirrors flag and length in hs_slot.  Kernels: pool_hist_set, pool_hist_append, pool_hist_gather (rnnt_encoder.hip.h).
+// the host mirrors flag and length in PoolSlot::hist.  Kernels: pool_hist_set, pool_hist_append, pool_hist_gather (rnnt_encoder.hip.h).
 
 int rnnt_stream_keep_frames(rnnt_ctx* ctx, int32_t slot, int32_t keep, void* stream) {
     if (!ctx) return RNNT_ERR_ARG;
@@ -14,12 +14,10 @@ int rnnt_stream_keep_frames(rnnt_ctx* ctx, int32_t slot, int32_t keep, void* str
     if (slot < 0 || slot >= ctx->n_streams) return fail(ctx, RNNT_ERR_ARG, "rnnt_stream_keep_frames: slot %d outside [0, %d)", slot, ctx->n_streams);
     hipStream_t s = (hipStream_t)stream;
     if (!keep) return pool_hist_reset(ctx, s, slot, 1);
-    if ((ctx->pool_mode ? ctx->slot_pos[slot] : ctx->pos).conv_pos != 0)
+    if ((ctx->pool_mode ? ctx->slot[slot].pos : ctx->pos).conv_pos != 0)
         return fail(ctx, RNNT_ERR_STATE, "rnnt_stream_keep_frames: slot %d has advanced since it was opened (its first frames are gone)", slot);
     const size_t B = ctx->cfg.max_streams;
     int rc;
-    if (ctx->hs_buf.empty()) ctx->hs_buf = std::vector<DevBuf<float>>(B);
-    if (ctx->hs_slot.empty()) ctx->hs_slot.assign(B, rnnt_ctx::HsSlot{0, 0});
     if ((rc = reserve(ctx, ctx->hs_buf[slot], (size_t)ctx->cfg.max_cache_frames * D))) return rc;
     if (!ctx->hs_len) {
         if ((rc = reserve(ctx, ctx->hs_ptr, B))) return rc;
@@ -28,7 +26,7 @@ int rnnt_stream_keep_frames(rnnt_ctx* ctx, int32_t slot, int32_t keep, void* str
     }
     hipLaunchKernelGGL(pool_hist_set, dim3(1), dim3(64), 0, s, ctx->hs_ptr.p, ctx->hs_len.p, slot, 1, ctx->hs_buf[slot].p);
     LAUNCHCHK("pool_hist_set");
-    ctx->hs_slot[slot] = rnnt_ctx::HsSlot{1, 0};
+    ctx->slot[slot].hist = HsSlot{1, 0};
     pool_enter(ctx);   // from here on the slot's frames come through the pool's entry points only
     return RNNT_OK;
 }
@@ -37,8 +35,9 @@ int rnnt_stream_get_frames(rnnt_ctx* ctx, int32_t slot, int32_t from, int32_t ca
     if (!ctx) return RNNT_ERR_ARG;
     if (slot < 0 || slot >= ctx->n_streams || from < 0 || cap_frames < 0 || (cap_frames > 0 && !dst_dev))
         return fail(ctx, RNNT_ERR_ARG, "rnnt_stream_get_frames: bad argument");
-    if (slot >= (int)ctx->hs_slot.size() || !ctx->hs_slot[slot].keep) return fail(ctx, RNNT_ERR_STATE, "rnnt_stream_get_frames: slot %d keeps no frames", slot);
-    const int avail = ctx->hs_slot[slot].len > from ? ctx->hs_slot[slot].len - from : 0;
+    const HsSlot& h = ctx->slot[slot].hist;
+    if (!h.keep) return fail(ctx, RNNT_ERR_STATE, "rnnt_stream_get_frames: slot %d keeps no frames", slot);
+    const int avail = h.len > from ? h.len - from : 0;
     if (n_out) *n_out = avail;
     const int ncopy = avail < cap_frames ? avail : cap_frames;
     if (ncopy > 0)
@@ -51,24 +50,17 @@ int rnnt_pool_rescore(rnnt_ctx* ctx, int32_t n, const int32_t* slots_host, const
     const char* fn = "rnnt_pool_rescore";
     if (!ctx) return RNNT_ERR_ARG;
     if (!slots_host) return fail(ctx, RNNT_ERR_ARG, "%s: null argument", fn);
-    if (n < 1 || n > ctx->n_streams) return fail(ctx, RNNT_ERR_ARG, "%s: %d slots of %d", fn, n, ctx->n_streams);
-    std::vector<char> seen((size_t)ctx->n_streams, 0);
+    int rc;
+    if ((rc = pool_slots_check(ctx, fn, n, slots_host, ctx->n_streams, "slots"))) return rc;
     std::vector<int32_t> lens((size_t)n);
     int Tmax = 0;
     for (int i = 0; i < n; ++i) {
-        const int slot = slots_host[i];
-        if (slot < 0 || slot >= ctx->n_streams) return fail(ctx, RNNT_ERR_ARG, "%s: row %d: slot %d outside [0, %d)", fn, i, slot, ctx->n_streams);
-        if (seen[slot]) return fail(ctx, RNNT_ERR_ARG, "%s: slot %d listed twice", fn, slot);
-        seen[slot] = 1;
-    }
-    for (int i = 0; i < n; ++i) {
-        const int slot = slots_host[i];
-        if (slot >= (int)ctx->hs_slot.size() || !ctx->hs_slot[slot].keep) return fail(ctx, RNNT_ERR_STATE, "%s: slot %d keeps no frames", fn, slot);
-        if (ctx->hs_slot[slot].len < 1) return fail(ctx, RNNT_ERR_STATE, "%s: slot %d has no frames yet", fn, slot);
-        lens[i] = ctx->hs_slot[slot].len;
+        const HsSlot& h = ctx->slot[slots_host[i]].hist;
+        if (!h.keep) return fail(ctx, RNNT_ERR_STATE, "%s: slot %d keeps no frames", fn, slots_host[i]);
+        if (h.len < 1) return fail(ctx, RNNT_ERR_STATE, "%s: slot %d has no frames yet", fn, slots_host[i]);
+        lens[i] = h.len;
         Tmax = std::max(Tmax, lens[i]);
     }
-    int rc;
     if ((rc = nbest_check(ctx, fn, lens.data(), n_hyp_host, hyp_lens_host, hyp_tokens_host, n, Tmax, N, Umax, nll_host, nullptr))) return rc;
     if ((rc = reserve(ctx, ctx->hs_stage, (size_t)n * Tmax * D))) return rc;
     return nbest_run(ctx, nullptr, slots_host, lens.data(), n_hyp_host, hyp_lens_host, hyp_tokens_host, n, Tmax, N, Umax, nll_host, nullptr, stream);

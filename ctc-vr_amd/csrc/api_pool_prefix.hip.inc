@@ -6,8 +6,8 @@
 // of the slot (token list, f64 score, hash, context state and score, two LSTM states each).  The pool kernels run the frame step of rnnt_prefix_beam_decode
 // (prefix_step_rows / prefix_merge_rows, the same code) on rows that stay in HBM between calls, so a search fed in pieces is bit for
 // bit the one-call search over the same frames, whatever the split.  Device state: rnnt_ctx::pp_*, rows slot * PB_MAX_BEAM + i of two
-// buffer sets, allocated on the first use.  Host state per slot: the current set (pp_cur), and the frames walked, the beam and the
-// two weights, use_context and graph generation of the search in progress (PpSlot).
+// buffer sets, allocated on the first use.  Host state per slot: the current set (PoolSlot::prefix_cur), and the frames walked, the beam
+// and the two weights, use_context and graph generation of the search in progress (PoolSlot::prefix, a SearchSlot).
 //
 // Rules: a slot's search is fresh after a reset; its first advancing call fixes beam_size, ctc_weight, transducer_weight and
 // use_context until the next reset (other values: RNNT_ERR_ARG).  rnnt_context_set starts a new graph generation: a search biased
@@ -16,14 +16,6 @@
 
 namespace {
 
-std::vector<rnnt_ctx::PpSlot>& pool_prefix_slots(rnnt_ctx* ctx) {
-    if (ctx->pp_slot.empty()) {
-        ctx->pp_slot.assign((size_t)ctx->cfg.max_streams, rnnt_ctx::PpSlot{0, 0, 0.f, 0.f, 0, 0});
-        ctx->pp_cur.assign((size_t)ctx->cfg.max_streams, 0);
-    }
-    return ctx->pp_slot;
-}
-
 // the device state, on the first use: every slot starts from [blank]; and room for a call's `frames` projected frames (and their
 // CTC log-probabilities)
 int pool_prefix_alloc(rnnt_ctx* ctx, hipStream_t s, size_t frames, bool with_ctc) {
@@ -31,7 +23,6 @@ int pool_prefix_alloc(rnnt_ctx* ctx, hipStream_t s, size_t frames, bool with_ctc
     if ((rc = reserve(ctx, ctx->pp_encp, frames * D))) return rc;
     if (with_ctc && (rc = reserve(ctx, ctx->pp_ctc, frames * (size_t)ctx->cfg.vocab_size))) return rc;
     if (ctx->pp_nh) return RNNT_OK;
-    pool_prefix_slots(ctx);
     const size_t B = (size_t)ctx->cfg.max_streams, R = B * PB_MAX_BEAM, lcap = (size_t)ctx->cfg.max_cache_frames + 1;
     for (int t = 0; t < 2; ++t) {
         if ((rc = reserve(ctx, ctx->pp_pool[t], R * 1024))) return rc;
@@ -44,9 +35,7 @@ int pool_prefix_alloc(rnnt_ctx* ctx, hipStream_t s, size_t frames, bool with_ctc
     }
     if ((rc = reserve(ctx, ctx->pp_toplp, R * PB_MAX_BEAM))) return rc;
     if ((rc = reserve(ctx, ctx->pp_toptok, R * PB_MAX_BEAM))) return rc;
-    if ((rc = reserve(ctx, ctx->pp_tab, 2 * B))) return rc;
-    if ((rc = reserve(ctx, ctx->pp_tab_host, 2 * B))) return rc;
-    if (!ctx->pp_ev) HIPCHK(hipEventCreateWithFlags(&ctx->pp_ev, hipEventDisableTiming));
+    if ((rc = calltab_alloc(ctx, ctx->pp_tab, 2 * B))) return rc;
     if ((rc = reserve(ctx, ctx->pp_nh, B))) return rc;   // last: its presence says the state exists (pool_prefix_reset)
     hipLaunchKernelGGL(prefix_init_pool, dim3((unsigned)B), dim3(256), 0, s, pool_prefix_params(ctx), 0, (int)lcap, ctx->cfg.blank_id);   // host records stay: a reset slot is fresh there already
     LAUNCHCHK("prefix_init_pool");
@@ -65,19 +54,7 @@ int pool_prefix_check(rnnt_ctx* ctx, const char* fn, int n, const int* slots, in
     if (!(cw >= 0.f) || !(tw >= 0.f) || (cw == 0.f && tw == 0.f)) return fail(ctx, RNNT_ERR_ARG, "%s: weights %g / %g (negative, or both zero)", fn, cw, tw);
     if (cw > 0.f && !ctx->wctc) return fail(ctx, RNNT_ERR_STATE, "%s: ctc_weight > 0 and ctc_head.ctc_lo.* not loaded", fn);
     if (use_context && !ctx->cg_on) return fail(ctx, RNNT_ERR_STATE, "%s: use_context without a context graph (rnnt_context_set)", fn);
-    const std::vector<rnnt_ctx::PpSlot>& ps = pool_prefix_slots(ctx);
-    for (int i = 0; i < n; ++i) {
-        const rnnt_ctx::PpSlot& q = ps[slots[i]];
-        if (q.beam != 0 && (q.beam != beam_size || q.cw != cw || q.tw != tw || (q.use_context != 0) != (use_context != 0)))
-            return fail(ctx, RNNT_ERR_ARG,
-                        "%s: slot %d: beam_size %d / weights %g, %g / use_context %d differ from the search in progress (%d / %g, %g / %d); reset the slot first", fn,
-                        slots[i], beam_size, cw, tw, use_context != 0, q.beam, q.cw, q.tw, q.use_context);
-        if (q.beam != 0 && q.use_context && q.gen != ctx->cg_gen)
-            return fail(ctx, RNNT_ERR_STATE, "%s: slot %d: the context graph changed since its search began; reset the slot first", fn, slots[i]);
-        if ((long long)q.frames_done + t > ctx->cfg.max_cache_frames)
-            return fail(ctx, RNNT_ERR_SHAPE, "%s: slot %d: %d + %d frames exceed max_cache_frames %d", fn, slots[i], q.frames_done, t, ctx->cfg.max_cache_frames);
-    }
-    return RNNT_OK;
+    return search_slot_check(ctx, fn, &PoolSlot::prefix, n, slots, t, beam_size, cw, tw, use_context, true);
 }
 
 // the frame loop: pool_prefix_check has passed, the state exists, pp_encp (and pp_ctc when cw > 0) hold the call's n * t compact rows
@@ -86,8 +63,7 @@ int pool_prefix_launch(rnnt_ctx* ctx, hipStream_t s, int n, const int* slots, co
                        float tw, int use_context) {
     PrefixStepP p;
     memset(&p, 0, sizeof(p));
-    p.whh = ctx->whh_il; p.egate = ctx->egate; p.wpr = ctx->wpr; p.bpr = ctx->bpr; p.wpf = ctx->wpf; p.bpf = ctx->bpf;
-    p.wout = ctx->wout; p.bout = ctx->bout; p.encp = ctx->pp_encp; p.ctc = cw > 0.f ? ctx->pp_ctc.p : nullptr;
+    dec_weights(ctx, p); p.encp = ctx->pp_encp; p.ctc = cw > 0.f ? ctx->pp_ctc.p : nullptr;
     p.top_lp = ctx->pp_toplp; p.top_tok = ctx->pp_toptok; p.vocab = ctx->cfg.vocab_size; p.k = beam_size; p.beam = beam_size; p.T = t;
     p.lcap = ctx->cfg.max_cache_frames + 1; p.tw = tw; p.cw = cw;
     PrefixMergeP m;
@@ -118,13 +94,8 @@ int pool_prefix_launch(rnnt_ctx* ctx, hipStream_t s, int n, const int* slots, co
             LAUNCHCHK("prefix_merge_pool");
         }
     }
-    std::vector<rnnt_ctx::PpSlot>& ps = pool_prefix_slots(ctx);
-    for (int i = 0; i < n; ++i) {
-        rnnt_ctx::PpSlot& r = ps[slots[i]];
-        r.frames_done += t;
-        r.beam = beam_size; r.cw = cw; r.tw = tw; r.use_context = use_context != 0; r.gen = ctx->cg_gen;   // fixed by the first call; later ones passed the check with the same values
-        ctx->pp_cur[slots[i]] ^= t & 1;
-    }
+    search_slot_commit(ctx, &PoolSlot::prefix, n, slots, t, beam_size, cw, tw, use_context);
+    for (int i = 0; i < n; ++i) ctx->slot[slots[i]].prefix_cur ^= t & 1;
     return RNNT_OK;
 }
 
@@ -147,16 +118,8 @@ int rnnt_pool_prefix_frames_ctx(rnnt_ctx* ctx, int32_t n_active, const int32_t* 
     const char* fn = "rnnt_pool_prefix_frames";
     if (!ctx) return RNNT_ERR_ARG;
     if (!slots_host || !enc_dev) return fail(ctx, RNNT_ERR_ARG, "%s: null argument", fn);
-    const int B = ctx->cfg.max_streams;
-    if (n_active < 1 || n_active > B) return fail(ctx, RNNT_ERR_ARG, "%s: %d active slots of %d", fn, n_active, B);
-    std::vector<char> seen((size_t)B, 0);
-    for (int i = 0; i < n_active; ++i) {
-        const int slot = slots_host[i];
-        if (slot < 0 || slot >= B) return fail(ctx, RNNT_ERR_ARG, "%s: row %d: slot %d outside [0, %d)", fn, i, slot, B);
-        if (seen[slot]) return fail(ctx, RNNT_ERR_ARG, "%s: slot %d listed twice", fn, slot);
-        seen[slot] = 1;
-    }
     int rc;
+    if ((rc = pool_slots_check(ctx, fn, n_active, slots_host, ctx->cfg.max_streams))) return rc;
     if ((rc = pool_prefix_check(ctx, fn, n_active, slots_host, t, beam_size, ctc_weight, transducer_weight, use_context))) return rc;
     const size_t frames = (size_t)n_active * t;
     if (frames * 512 >= ((size_t)1 << 31)) return fail(ctx, RNNT_ERR_SHAPE, "%s: n_active=%d t=%d too large for one call", fn, n_active, t);
@@ -164,10 +127,10 @@ int rnnt_pool_prefix_frames_ctx(rnnt_ctx* ctx, int32_t n_active, const int32_t* 
     const bool with_ctc = ctc_weight > 0.f;
     if ((rc = pool_prefix_alloc(ctx, s, frames, with_ctc))) return rc;
     const int n = n_active;
-    HIPCHK(hipEventSynchronize(ctx->pp_ev));               // the previous call's copy has left the pinned buffer
-    for (int i = 0; i < n; ++i) { ctx->pp_tab_host[i] = slots_host[i]; ctx->pp_tab_host[n + i] = ctx->pp_cur[slots_host[i]]; }
-    HIPCHK(hipMemcpyAsync(ctx->pp_tab, ctx->pp_tab_host, 2 * (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));   // the call's table
-    HIPCHK(hipEventRecord(ctx->pp_ev, s));
+    int* tab;
+    if ((rc = calltab_fill(ctx, ctx->pp_tab, tab))) return rc;
+    for (int i = 0; i < n; ++i) { tab[i] = slots_host[i]; tab[n + i] = ctx->slot[slots_host[i]].prefix_cur; }
+    if ((rc = calltab_send(ctx, ctx->pp_tab, 2 * (size_t)n, s))) return rc;   // the call's table
     {   // joint.enc_ffn and log_softmax(ctc_lo(.)) over the call's rows with the kernel / tile choices of a small call, as
         // rnnt_prefix_beam_decode forms them: a frame's sums do not depend on the call it arrives in
         GemmCapScope cap(ctx);
@@ -195,7 +158,7 @@ int rnnt_stream_get_prefix_ctx(rnnt_ctx* ctx, int32_t slot, int32_t final, int32
     const bool query = !lens_host && !tokens_host && !scores_host && !h_host && !c_host;   // the sizes a read needs: host only
     if (!n_hyp || (!query && (!lens_host || !tokens_host || !scores_host || (!h_host != !c_host)))) return fail(ctx, RNNT_ERR_ARG, "%s: null argument", fn);
     if (slot < 0 || slot >= ctx->cfg.max_streams) return fail(ctx, RNNT_ERR_ARG, "%s: slot %d outside [0, %d)", fn, slot, ctx->cfg.max_streams);
-    const rnnt_ctx::PpSlot q = pool_prefix_slots(ctx)[slot];
+    const SearchSlot q = ctx->slot[slot].prefix;
     const int beam = q.beam > 0 ? q.beam : 1;                        // a fresh slot holds [blank] alone
     if (query) {
         n_hyp[0] = beam; n_hyp[1] = q.frames_done; n_hyp[2] = 1 + q.frames_done;   // one symbol per frame at most, after the leading blank
@@ -203,43 +166,28 @@ int rnnt_stream_get_prefix_ctx(rnnt_ctx* ctx, int32_t slot, int32_t final, int32
     }
     if (cap_hyps < beam) return fail(ctx, RNNT_ERR_ARG, "%s: beam %d, room for %d hypotheses", fn, beam, cap_hyps);
     if (cap_tokens < 1 + q.frames_done) return fail(ctx, RNNT_ERR_ARG, "%s: cap_tokens %d < 1 + %d frames", fn, cap_tokens, q.frames_done);
-    // finalize needs the graph the search ran under; a fresh slot has fixed none and finalizes its root under the graph that is set, if any
-    const bool biased = q.beam > 0 ? q.use_context != 0 : (final != 0 && ctx->cg_on), fin = biased && final != 0;
-    if (fin && q.beam > 0 && (!ctx->cg_on || q.gen != ctx->cg_gen))
-        return fail(ctx, RNNT_ERR_STATE, "%s: slot %d: the context graph changed since its search began (final = 0 still reads it)", fn, slot);
-    hipStream_t s = (hipStream_t)stream;
+    SearchRead rd;
     int rc;
+    if ((rc = search_slot_read(ctx, fn, slot, q, final, rd))) return rc;
+    hipStream_t s = (hipStream_t)stream;
     if ((rc = pool_prefix_alloc(ctx, s, 0, false))) return rc;
     const size_t R = (size_t)beam, ocap = (size_t)q.frames_done + 1, with_states = h_host ? 1 : 0;
-    const size_t out_bytes = 2 * R * sizeof(double) + sizeof(int) * (1 + R + R * ocap) + (with_states ? 2 * R * D * sizeof(float) : 0);
-    const size_t out_doubles = (out_bytes + sizeof(double) - 1) / sizeof(double);
+    const size_t out_bytes = prefix_out(nullptr, 1, R, ocap, with_states).bytes, out_doubles = (out_bytes + sizeof(double) - 1) / sizeof(double);
     if ((rc = reserve(ctx, ctx->pp_out, out_doubles))) return rc;
-    hipLaunchKernelGGL(prefix_pack_pool, dim3((unsigned)R), dim3(256), 0, s, pool_prefix_params(ctx), slot, ctx->pp_cur[slot], beam,
-                       ctx->cfg.max_cache_frames + 1, (int)ocap, (int)with_states, biased ? 1 : 0, fin ? ctx_graph_dev(ctx).nscore : nullptr, ctx->pp_out.p);
+    hipLaunchKernelGGL(prefix_pack_pool, dim3((unsigned)R), dim3(256), 0, s, pool_prefix_params(ctx), slot, ctx->slot[slot].prefix_cur, beam,
+                       ctx->cfg.max_cache_frames + 1, (int)ocap, (int)with_states, rd.biased ? 1 : 0, rd.fin ? ctx_graph_dev(ctx).nscore : nullptr, ctx->pp_out.p);
     LAUNCHCHK("prefix_pack_pool");
     std::vector<double> out(out_doubles);
     HIPCHK(hipMemcpyAsync(out.data(), ctx->pp_out, out_bytes, hipMemcpyDeviceToHost, s));                 // the download
     HIPCHK(hipStreamSynchronize(s));
-    const int* oi = reinterpret_cast<const int*>(out.data() + 2 * R);
-    const int *o_len = oi + 1, *o_tk = o_len + R;
-    const float* o_h = reinterpret_cast<const float*>(o_tk + R * ocap);
+    const PrefixOut o = prefix_out(out.data(), 1, R, ocap, with_states);
     const size_t H = (size_t)cap_hyps;
-    *n_hyp = oi[0];
+    *n_hyp = o.nh[0];
     std::fill(lens_host, lens_host + H, 0);
     std::fill(scores_host, scores_host + H, 0.0);
     std::fill(tokens_host, tokens_host + H * cap_tokens, 0);
-    memcpy(lens_host, o_len, R * sizeof(int));
-    memcpy(scores_host, out.data(), R * sizeof(double));
-    if (ctx_scores_host) {
-        std::fill(ctx_scores_host, ctx_scores_host + H, 0.0);
-        memcpy(ctx_scores_host, out.data() + R, R * sizeof(double));
-    }
-    for (size_t r = 0; r < R; ++r) memcpy(tokens_host + r * cap_tokens, o_tk + r * ocap, (size_t)o_len[r] * sizeof(int));
-    if (with_states) {
-        std::fill(h_host, h_host + H * D, 0.f);
-        std::fill(c_host, c_host + H * D, 0.f);
-        memcpy(h_host, o_h, R * D * sizeof(float));
-        memcpy(c_host, o_h + R * D, R * D * sizeof(float));
-    }
+    if (ctx_scores_host) std::fill(ctx_scores_host, ctx_scores_host + H, 0.0);
+    if (with_states) { std::fill(h_host, h_host + H * D, 0.f); std::fill(c_host, c_host + H * D, 0.f); }
+    prefix_out_copy(o, R, ocap, (size_t)cap_tokens, lens_host, tokens_host, scores_host, ctx_scores_host, h_host, c_host);
     return RNNT_OK;
 }

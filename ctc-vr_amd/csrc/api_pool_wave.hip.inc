@@ -11,15 +11,10 @@
 // order), so a frame's bits depend neither on the neighbours nor on how the samples were split into packets, and they are the bits of
 // rnnt_fbank over the whole waveform whenever that call has fewer than 1024 frames (it takes gemm16 too).
 //
-// Host state per slot (rnnt_ctx::WvSlot): samples, frames, the (sample_rate, n_fft) of the utterance in progress, finished.  Frame
+// Host state per slot (PoolSlot::wave, a WvSlot): samples, frames, the (sample_rate, n_fft) of the utterance in progress, finished.  Frame
 // counts are host arithmetic (wave_plan_row): the call does not synchronise.  Every refusal is decided before the first launch.
 
 namespace {
-
-std::vector<rnnt_ctx::WvSlot>& pool_wave_slots(rnnt_ctx* ctx) {
-    if (ctx->wv_slot.empty()) ctx->wv_slot.assign((size_t)ctx->cfg.max_streams, rnnt_ctx::WvSlot{0, 0, 0, 0, 0});
-    return ctx->wv_slot;
-}
 
 static_assert(WAVE_CARRY_CAP >= WAVE_MAX_NFFT, "a carry holds up to n_fft samples");
 
@@ -27,9 +22,7 @@ int pool_wave_alloc(rnnt_ctx* ctx, hipStream_t s) {
     if (ctx->wv_carry) return RNNT_OK;
     const size_t B = (size_t)ctx->cfg.max_streams;
     int rc;
-    if ((rc = reserve(ctx, ctx->wv_tab, WAVE_TAB_INTS * B))) return rc;
-    if ((rc = reserve(ctx, ctx->wv_tab_host, WAVE_TAB_INTS * B))) return rc;
-    if (!ctx->wv_ev) HIPCHK(hipEventCreateWithFlags(&ctx->wv_ev, hipEventDisableTiming));
+    if ((rc = calltab_alloc(ctx, ctx->wv_tab, WAVE_TAB_INTS * B))) return rc;
     if ((rc = reserve(ctx, ctx->wv_carry, B * WAVE_CARRY_CAP))) return rc;   // last: its presence says the state exists
     HIPCHK(hipMemsetAsync(ctx->wv_carry, 0, B * WAVE_CARRY_CAP * sizeof(float), s));
     return RNNT_OK;
@@ -53,26 +46,22 @@ int rnnt_pool_wave(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, c
     const char* fn = "rnnt_pool_wave";
     if (!ctx) return RNNT_ERR_ARG;
     if (!slots_host || !wave_dev || !samples_host || !final_host || !out_dev || !frames_host) return fail(ctx, RNNT_ERR_ARG, "%s: null argument", fn);
-    const int B = ctx->cfg.max_streams, n = n_active, n_mels = 80;
-    if (n < 1 || n > B) return fail(ctx, RNNT_ERR_ARG, "%s: %d active slots of %d", fn, n, B);
-    if (n_samples < 0 || cap_frames < 0) return fail(ctx, RNNT_ERR_ARG, "%s: n_samples %d / cap_frames %d negative", fn, n_samples, cap_frames);
-    if (!wave_shape_ok(sample_rate, n_fft))
-        return fail(ctx, RNNT_ERR_SHAPE, "%s: sample_rate=%d n_fft=%d (n_fft must be a multiple of 64 in [64, %d])", fn, sample_rate, n_fft, WAVE_MAX_NFFT);
+    const int n = n_active, n_mels = 80;
     // ---- every refusal before anything changes ----------------------------------------------------------------------------------------
-    const std::vector<rnnt_ctx::WvSlot>& ws = pool_wave_slots(ctx);
-    std::vector<char> seen((size_t)B, 0);
+    int rc = pool_slots_check(ctx, fn, n, slots_host, ctx->cfg.max_streams, "active slots", [&] {
+        if (n_samples < 0 || cap_frames < 0) return fail(ctx, RNNT_ERR_ARG, "%s: n_samples %d / cap_frames %d negative", fn, n_samples, cap_frames);
+        if (!wave_shape_ok(sample_rate, n_fft))
+            return fail(ctx, RNNT_ERR_SHAPE, "%s: sample_rate=%d n_fft=%d (n_fft must be a multiple of 64 in [64, %d])", fn, sample_rate, n_fft, WAVE_MAX_NFFT);
+        return (int)RNNT_OK;
+    }, [&](int i, int) {
+        if (samples_host[i] >= 0 && samples_host[i] <= n_samples) return (int)RNNT_OK;
+        return fail(ctx, RNNT_ERR_ARG, "%s: row %d: %d samples outside [0, %d]", fn, i, samples_host[i], n_samples);
+    });
+    if (rc) return rc;
     std::vector<WaveRow> rows((size_t)n);
     int max_f = 0, max_len = WAVE_PRE;
     for (int i = 0; i < n; ++i) {
-        const int slot = slots_host[i];
-        if (slot < 0 || slot >= B) return fail(ctx, RNNT_ERR_ARG, "%s: row %d: slot %d outside [0, %d)", fn, i, slot, B);
-        if (seen[slot]) return fail(ctx, RNNT_ERR_ARG, "%s: slot %d listed twice", fn, slot);
-        seen[slot] = 1;
-        if (samples_host[i] < 0 || samples_host[i] > n_samples)
-            return fail(ctx, RNNT_ERR_ARG, "%s: row %d: %d samples outside [0, %d]", fn, i, samples_host[i], n_samples);
-    }
-    for (int i = 0; i < n; ++i) {
-        const rnnt_ctx::WvSlot& q = ws[slots_host[i]];
+        const WvSlot& q = ctx->slot[slots_host[i]].wave;
         const int fin = final_host[i] != 0;
         if (q.finished) return fail(ctx, RNNT_ERR_STATE, "%s: slot %d: its utterance has ended; open or reset the slot first", fn, slots_host[i]);
         if (q.nfft != 0 && (q.rate != sample_rate || q.nfft != n_fft))
@@ -95,23 +84,22 @@ int rnnt_pool_wave(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, c
     const long long M = (long long)n * max_f;
     if (M > 0x7fffffffLL / 8 || (long long)n * stride > 0x7fffffffLL) return fail(ctx, RNNT_ERR_SHAPE, "%s: %lld frames / %lld staged samples in one call", fn, M, (long long)n * stride);
     hipStream_t s = (hipStream_t)stream;
-    int rc;
     if ((rc = pool_wave_alloc(ctx, s))) return rc;
     if (max_f > 0 && (rc = fbank_matrices(ctx, s, sample_rate, n_fft))) return rc;
     if ((rc = reserve(ctx, ctx->wv_stage, (size_t)n * stride))) return rc;
     if ((rc = reserve(ctx, ctx->fb_spec, (size_t)M * n2p))) return rc;
     if ((rc = reserve(ctx, ctx->fb_pow, (size_t)M * kp))) return rc;
     // ---- the call's table: one async copy, no synchronisation before the launches ---------------------------------------------------
-    HIPCHK(hipEventSynchronize(ctx->wv_ev));               // the previous call's copy has left the pinned buffer
+    int* tab;
+    if ((rc = calltab_fill(ctx, ctx->wv_tab, tab))) return rc;
     for (int i = 0; i < n; ++i) {
-        int* e = ctx->wv_tab_host + (size_t)i * WAVE_TAB_INTS;
+        int* e = tab + (size_t)i * WAVE_TAB_INTS;
         e[0] = slots_host[i]; e[1] = rows[i].n_old; e[2] = rows[i].n_new; e[3] = rows[i].final;
     }
-    HIPCHK(hipMemcpyAsync(ctx->wv_tab, ctx->wv_tab_host, (size_t)n * WAVE_TAB_INTS * sizeof(int), hipMemcpyHostToDevice, s));
-    HIPCHK(hipEventRecord(ctx->wv_ev, s));
+    if ((rc = calltab_send(ctx, ctx->wv_tab, (size_t)n * WAVE_TAB_INTS, s))) return rc;
     {
         ProfScope prof(ctx, s, TAG_WAVE_STAGE);
-        hipLaunchKernelGGL(wave_stage, dim3(grid_for((long long)n * stride)), dim3(256), 0, s, wave_dev, ctx->wv_carry.p, ctx->wv_stage.p, ctx->wv_tab.p, n,
+        hipLaunchKernelGGL(wave_stage, dim3(grid_for((long long)n * stride)), dim3(256), 0, s, wave_dev, ctx->wv_carry.p, ctx->wv_stage.p, ctx->wv_tab.dev.p, n,
                            n_samples, n_fft, stride);
         LAUNCHCHK("wave_stage");
     }
@@ -128,13 +116,12 @@ int rnnt_pool_wave(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, c
         g2.c_n = max_f; g2.c_s0 = (long long)cap_frames * n_mels; g2.c_r0 = 0; g2.c_mod = BIG; g2.c_s1 = n_mels;
         if ((rc = launch_gemm(ctx, s, &g2, 1))) return rc;
     }
-    hipLaunchKernelGGL(wave_carry_roll, dim3(grid_for((long long)n * n_fft)), dim3(256), 0, s, ctx->wv_stage.p, ctx->wv_carry.p, ctx->wv_tab.p, n, n_fft, stride);
+    hipLaunchKernelGGL(wave_carry_roll, dim3(grid_for((long long)n * n_fft)), dim3(256), 0, s, ctx->wv_stage.p, ctx->wv_carry.p, ctx->wv_tab.dev.p, n, n_fft, stride);
     LAUNCHCHK("wave_carry_roll");
-    std::vector<rnnt_ctx::WvSlot>& wm = pool_wave_slots(ctx);
     for (int i = 0; i < n; ++i) {
         frames_host[i] = rows[i].nf;
         if (rows[i].n_new == 0 && !rows[i].final) continue;     // a no-op row fixes nothing
-        rnnt_ctx::WvSlot& q = wm[slots_host[i]];
+        WvSlot& q = ctx->slot[slots_host[i]].wave;
         q.samples = rows[i].n_tot; q.frames = rows[i].f0 + rows[i].nf; q.rate = sample_rate; q.nfft = n_fft; q.finished = rows[i].final;
     }
     return RNNT_OK;
@@ -145,7 +132,7 @@ int rnnt_stream_get_wave_state(rnnt_ctx* ctx, int32_t slot, int32_t* samples_out
     const char* fn = "rnnt_stream_get_wave_state";
     if (!ctx) return RNNT_ERR_ARG;
     if (slot < 0 || slot >= ctx->cfg.max_streams) return fail(ctx, RNNT_ERR_ARG, "%s: slot %d outside [0, %d)", fn, slot, ctx->cfg.max_streams);
-    const rnnt_ctx::WvSlot q = pool_wave_slots(ctx)[slot];
+    const WvSlot q = ctx->slot[slot].wave;
     const int n_carry = q.nfft && !q.finished ? wave_plan_row(q.samples, 0, 0, q.nfft).cl_old : 0;   // a finished utterance reads nothing more
     if (samples_out) *samples_out = q.samples;
     if (frames_out) *frames_out = q.frames;

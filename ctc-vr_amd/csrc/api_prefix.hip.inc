@@ -208,8 +208,7 @@ int rnnt_prefix_beam_decode_ctx(rnnt_ctx* ctx, const float* enc_dev, const int32
     int rc;
     PrefixBuf u;
     if ((rc = prefix_buffers(ctx, B, R, lcap, frames, with_ctc, k, u))) return rc;
-    const size_t out_bytes = 2 * R * sizeof(double) + sizeof(int) * ((size_t)B + R + R * lcap) + (with_states ? 2 * R * D * sizeof(float) : 0);
-    const size_t out_doubles = (out_bytes + sizeof(double) - 1) / sizeof(double);
+    const size_t out_bytes = prefix_out(nullptr, B, R, lcap, with_states).bytes, out_doubles = (out_bytes + sizeof(double) - 1) / sizeof(double);
     if ((rc = reserve(ctx, ctx->pb_out, out_doubles))) return rc;
     CpGraph graph;
     memset(&graph, 0, sizeof(graph));
@@ -227,8 +226,7 @@ int rnnt_prefix_beam_decode_ctx(rnnt_ctx* ctx, const float* enc_dev, const int32
     }
     PrefixStepP p;
     memset(&p, 0, sizeof(p));
-    p.whh = ctx->whh_il; p.egate = ctx->egate; p.wpr = ctx->wpr; p.bpr = ctx->bpr; p.wpf = ctx->wpf; p.bpf = ctx->bpf;
-    p.wout = ctx->wout; p.bout = ctx->bout; p.encp = u.encp; p.ctc = u.ctc; p.nh = u.nh; p.lens = u.lens;
+    dec_weights(ctx, p); p.encp = u.encp; p.ctc = u.ctc; p.nh = u.nh; p.lens = u.lens;
     p.top_lp = u.top_lp; p.top_tok = u.top_tok; p.vocab = V; p.k = k; p.beam = beam_size; p.T = T; p.lcap = (int)lcap;
     p.tw = transducer_weight; p.cw = ctc_weight;
     int t = 0;
@@ -248,18 +246,9 @@ int rnnt_prefix_beam_decode_ctx(rnnt_ctx* ctx, const float* enc_dev, const int32
     std::vector<double> out(out_doubles);
     HIPCHK(hipMemcpyAsync(out.data(), ctx->pb_out, out_bytes, hipMemcpyDeviceToHost, s));                // the download
     HIPCHK(hipStreamSynchronize(s));
-    const int* oi = reinterpret_cast<const int*>(out.data() + 2 * R);
-    const int *o_len = oi + B, *o_tk = o_len + R;
-    const float* o_h = reinterpret_cast<const float*>(o_tk + R * lcap);
-    memcpy(scores_host, out.data(), R * sizeof(double));
-    if (ctx_scores_host) memcpy(ctx_scores_host, out.data() + R, R * sizeof(double));
-    memcpy(n_hyp_host, oi, B * sizeof(int));
-    memcpy(lens_host, o_len, R * sizeof(int));
-    for (size_t r = 0; r < R; ++r) memcpy(tokens_host + r * cap_tokens, o_tk + r * lcap, (size_t)o_len[r] * sizeof(int));
-    if (with_states) {
-        memcpy(h_host, o_h, R * D * sizeof(float));
-        memcpy(c_host, o_h + R * D, R * D * sizeof(float));
-    }
+    const PrefixOut o = prefix_out(out.data(), B, R, lcap, with_states);
+    memcpy(n_hyp_host, o.nh, B * sizeof(int));
+    prefix_out_copy(o, R, lcap, (size_t)cap_tokens, lens_host, tokens_host, scores_host, ctx_scores_host, h_host, c_host);
     return RNNT_OK;
 }
 

@@ -13,7 +13,7 @@ int rnnt_get_att_cache(rnnt_ctx* ctx, int32_t b, float* dst_host, int32_t* len_o
     if (!ctx || b < 0 || b >= ctx->n_streams) return fail(ctx, RNNT_ERR_ARG, "rnnt_get_att_cache: bad stream index");
     hipStream_t s = (hipStream_t)stream;
     // stream pool: the slot's own cache window
-    const SlotPos& p = ctx->pool_mode ? ctx->slot_pos[b] : ctx->pos;
+    const SlotPos& p = ctx->pool_mode ? ctx->slot[b].pos : ctx->pos;
     const int cache_len = p.cache_len, kv_start = p.kv_start;
     if (len_out) *len_out = cache_len;
     if (!dst_host || cache_len == 0) return RNNT_OK;
@@ -30,7 +30,7 @@ int rnnt_get_cnn_cache(rnnt_ctx* ctx, int32_t b, float* dst_host, void* stream) 
     if (!ctx || !dst_host || b < 0 || b >= ctx->n_streams) return fail(ctx, RNNT_ERR_ARG, "rnnt_get_cnn_cache: bad argument");
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(gather_cnn_cache, dim3(L * RNNT_LORDER), dim3(64), 0, s, ctx->xring, ctx->ln_conv_g_all, ctx->ln_conv_b_all, ctx->scratch, b,
-                       ctx->cfg.max_streams, ctx->cap, (ctx->pool_mode ? ctx->slot_pos[b] : ctx->pos).conv_pos);
+                       ctx->cfg.max_streams, ctx->cap, (ctx->pool_mode ? ctx->slot[b].pos : ctx->pos).conv_pos);
     LAUNCHCHK("gather_cnn_cache");
     HIPCHK(hipMemcpyAsync(dst_host, ctx->scratch, (size_t)L * D * RNNT_LORDER * sizeof(float), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));

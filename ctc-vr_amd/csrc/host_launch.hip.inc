@@ -99,6 +99,33 @@ struct Carve {
     }
 };
 
+// ---- the call tables of the stream pool (CallTab): room for n ints on both sides and the event, once -----------------------------------
+int calltab_alloc(rnnt_ctx* ctx, CallTab& t, size_t n) {
+    int rc;
+    if ((rc = reserve(ctx, t.dev, n))) return rc;
+    if ((rc = reserve(ctx, t.host, n))) return rc;
+    if (!t.ev) HIPCHK(hipEventCreateWithFlags(&t.ev, hipEventDisableTiming));
+    return RNNT_OK;
+}
+// the pinned copy, free to be filled: the previous call's copy has left it (normally long ago)
+int calltab_fill(rnnt_ctx* ctx, CallTab& t, int*& host) {
+    HIPCHK(hipEventSynchronize(t.ev));
+    host = t.host;
+    return RNNT_OK;
+}
+// its first n ints to the device: one async copy, no synchronisation before the launches that read it
+int calltab_send(rnnt_ctx* ctx, CallTab& t, size_t n, hipStream_t s) {
+    HIPCHK(hipMemcpyAsync(t.dev, t.host, n * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipEventRecord(t.ev, s));
+    return RNNT_OK;
+}
+
+// the decoder and joint weights that the beam's and the prefix search's step kernels share (BeamChainP, PrefixStepP)
+template <typename P>
+void dec_weights(const rnnt_ctx* ctx, P& p) {
+    p.whh = ctx->whh_il; p.egate = ctx->egate; p.wpr = ctx->wpr; p.bpr = ctx->bpr; p.wpf = ctx->wpf; p.bpf = ctx->bpf; p.wout = ctx->wout; p.bout = ctx->bout;
+}
+
 // hipFuncAttributeMaxDynamicSharedMemorySize is per device: keep the "already raised" record in the context (one context = one
 // device, one host thread at a time), not in a process-wide static (a second device, or a second host thread, would miss it).
 int ensure_dyn_lds(rnnt_ctx* ctx, const void* fn, size_t bytes) {
@@ -621,7 +648,7 @@ int pool_beam_reset(rnnt_ctx* ctx, hipStream_t s, int slot0, int n) {
     if (!ctx->ps_nh) return RNNT_OK;
     hipLaunchKernelGGL(beam_slot_reset, dim3(n), dim3(256), 0, s, pool_beam_params(ctx), slot0, ctx->cfg.n_steps + 1);
     LAUNCHCHK("beam_slot_reset");
-    for (int b = slot0; b < slot0 + n; ++b) { ctx->ps_cur[b] = 0; ctx->ps_lbound[b] = 0; }
+    for (int b = slot0; b < slot0 + n; ++b) { ctx->slot[b].beam_cur = 0; ctx->slot[b].beam_lbound = 0; }
     return RNNT_OK;
 }
 
@@ -635,9 +662,40 @@ CpGraph ctx_graph_dev(const rnnt_ctx* ctx) {
     return g;
 }
 
+// The block of a CTC prefix search's results that is downloaded in one copy, on the device or in its host copy (the one-call search
+// with its B, a slot's read with B = 1): n_hyp [B] | lens [R] | tokens [R][lcap] | times [R][lcap]; total: its ints.
+struct CpOut { int *nh, *len, *tok, *time; size_t total; };
+CpOut cp_out(Carve<int>& c, size_t B, size_t R, size_t lcap) {
+    CpOut o;
+    const size_t at = c.off;
+    o.nh = c.take(B);
+    o.len = c.take(R);
+    o.tok = c.take(R * lcap);
+    o.time = c.take(R * lcap);
+    o.total = c.off - at;
+    return o;
+}
+// its host copy h (and the scores | context scores od [2][R]) into the caller's arrays: H >= R rows of cap_tokens, zero beyond what was found
+void cp_out_copy(const CpOut& h, const double* od, size_t B, size_t R, size_t lcap, size_t H, size_t cap_tokens, int32_t* n_hyp, int32_t* lens,
+                 int32_t* tokens, int32_t* times, double* scores, double* ctx_scores) {
+    memcpy(n_hyp, h.nh, B * sizeof(int));
+    std::fill(lens, lens + H, 0);
+    std::fill(scores, scores + H, 0.0);
+    std::fill(tokens, tokens + H * cap_tokens, 0);
+    std::fill(times, times + H * cap_tokens, 0);
+    memcpy(lens, h.len, R * sizeof(int));
+    memcpy(scores, od, R * sizeof(double));
+    if (ctx_scores) { std::fill(ctx_scores, ctx_scores + H, 0.0); memcpy(ctx_scores, od + R, R * sizeof(double)); }
+    const size_t ncopy = std::min(lcap, cap_tokens);
+    for (size_t r = 0; r < R; ++r) {
+        memcpy(tokens + r * cap_tokens, h.tok + r * lcap, ncopy * sizeof(int));
+        memcpy(times + r * cap_tokens, h.time + r * lcap, ncopy * sizeof(int));
+    }
+}
+
 // the start hypothesis for slots [slot0, slot0 + n): the host record always, the device record once it exists (pool_ctc_alloc resets all)
 int pool_ctc_reset(rnnt_ctx* ctx, hipStream_t s, int slot0, int n) {
-    for (int b = slot0; b < slot0 + n && b < (int)ctx->pc_slot.size(); ++b) ctx->pc_slot[b] = rnnt_ctx::PcSlot{0, 0, 0, 0};
+    for (int b = slot0; b < slot0 + n; ++b) ctx->slot[b].ctc = SearchSlot{};
     if (!ctx->pc_state) return RNNT_OK;
     hipLaunchKernelGGL(ctc_prefix_slot_reset, dim3(n), dim3(64), 0, s, ctx->pc_state.p, slot0);
     LAUNCHCHK("ctc_prefix_slot_reset");
@@ -653,9 +711,37 @@ PrefixPoolP pool_prefix_params(const rnnt_ctx* ctx) {
     return q;
 }
 
+// The block prefix_pack / prefix_pack_pool write and one copy downloads, on the device or in its host copy (the one-call search with
+// its B, a slot's read with B = 1): scores [R] | context scores [R] as doubles, the ints n_hyp [B] | lens [R] | tokens [R][lcap], and
+// with_states the floats h [R][256] | c [R][256].  bytes: its size.
+struct PrefixOut { double *sc, *cs; int *nh, *len, *tk; float *h, *c; size_t bytes; };
+PrefixOut prefix_out(double* base, size_t B, size_t R, size_t lcap, bool with_states) {
+    Carve<char> b{reinterpret_cast<char*>(base)};
+    auto take = [&](auto*& q, size_t n) { q = reinterpret_cast<std::remove_reference_t<decltype(q)>>(b.take(n * sizeof(*q))); };
+    PrefixOut o;
+    take(o.sc, R);
+    take(o.cs, R);
+    take(o.nh, B);
+    take(o.len, R);
+    take(o.tk, R * lcap);
+    take(o.h, with_states ? R * D : 0);
+    take(o.c, with_states ? R * D : 0);
+    o.bytes = b.off;
+    return o;
+}
+// its host copy into the caller's arrays (rows of cap_tokens; a row's tokens up to its length)
+void prefix_out_copy(const PrefixOut& o, size_t R, size_t lcap, size_t cap_tokens, int32_t* lens, int32_t* tokens, double* scores, double* ctx_scores,
+                     float* h, float* c) {
+    memcpy(lens, o.len, R * sizeof(int));
+    memcpy(scores, o.sc, R * sizeof(double));
+    if (ctx_scores) memcpy(ctx_scores, o.cs, R * sizeof(double));
+    for (size_t r = 0; r < R; ++r) memcpy(tokens + r * cap_tokens, o.tk + r * lcap, (size_t)o.len[r] * sizeof(int));
+    if (h) { memcpy(h, o.h, R * D * sizeof(float)); memcpy(c, o.c, R * D * sizeof(float)); }
+}
+
 // the start hypothesis [blank] for slots [slot0, slot0 + n): the host record always, the device rows once they exist (pool_prefix_alloc resets all)
 int pool_prefix_reset(rnnt_ctx* ctx, hipStream_t s, int slot0, int n) {
-    for (int b = slot0; b < slot0 + n && b < (int)ctx->pp_slot.size(); ++b) { ctx->pp_slot[b] = rnnt_ctx::PpSlot{0, 0, 0.f, 0.f, 0, 0}; ctx->pp_cur[b] = 0; }
+    for (int b = slot0; b < slot0 + n; ++b) { ctx->slot[b].prefix = SearchSlot{}; ctx->slot[b].prefix_cur = 0; }
     if (!ctx->pp_nh) return RNNT_OK;
     hipLaunchKernelGGL(prefix_init_pool, dim3(n), dim3(256), 0, s, pool_prefix_params(ctx), slot0, ctx->cfg.max_cache_frames + 1, ctx->cfg.blank_id);
     LAUNCHCHK("prefix_init_pool");
@@ -665,13 +751,13 @@ int pool_prefix_reset(rnnt_ctx* ctx, hipStream_t s, int slot0, int n) {
 // ---- per-slot streaming front-end of the stream pool (api_pool_wave.hip.inc; kernels in rnnt_frontend.hip.h) ---------------------------
 // a fresh utterance for slots [slot0, slot0 + n): host records only -- a fresh slot's carry is empty, so the device carry needs no reset
 void pool_wave_reset(rnnt_ctx* ctx, int slot0, int n) {
-    for (int b = slot0; b < slot0 + n && b < (int)ctx->wv_slot.size(); ++b) ctx->wv_slot[b] = rnnt_ctx::WvSlot{0, 0, 0, 0, 0};
+    for (int b = slot0; b < slot0 + n; ++b) ctx->slot[b].wave = WvSlot{};
 }
 
 // ---- per-slot encoder-frame history of the stream pool (api_pool_hist.hip.inc; kernels in rnnt_encoder.hip.h) ----------------------------
 // flag and length of slots [slot0, slot0 + n) cleared, on the host and (once the tables exist) on the device; buffers stay
 int pool_hist_reset(rnnt_ctx* ctx, hipStream_t s, int slot0, int n) {
-    for (int b = slot0; b < slot0 + n && b < (int)ctx->hs_slot.size(); ++b) ctx->hs_slot[b] = rnnt_ctx::HsSlot{0, 0};
+    for (int b = slot0; b < slot0 + n; ++b) ctx->slot[b].hist = HsSlot{};
     if (!ctx->hs_len) return RNNT_OK;
     hipLaunchKernelGGL(pool_hist_set, dim3((n + 63) / 64), dim3(64), 0, s, ctx->hs_ptr.p, ctx->hs_len.p, slot0, n, (float*)nullptr);
     LAUNCHCHK("pool_hist_set");
@@ -680,9 +766,9 @@ int pool_hist_reset(rnnt_ctx* ctx, hipStream_t s, int slot0, int n) {
 
 // with the other slot checks of a pool call: a kept slot whose history cannot take tq more rows refuses the call
 int pool_hist_check(rnnt_ctx* ctx, const char* fn, int slot, int tq) {
-    if (slot >= (int)ctx->hs_slot.size() || !ctx->hs_slot[slot].keep) return RNNT_OK;
-    if (ctx->hs_slot[slot].len + tq > ctx->cfg.max_cache_frames)
-        return fail(ctx, RNNT_ERR_SHAPE, "%s: slot %d: kept frames %d + %d exceed max_cache_frames %d", fn, slot, ctx->hs_slot[slot].len, tq, ctx->cfg.max_cache_frames);
+    const HsSlot& h = ctx->slot[slot].hist;
+    if (h.keep && h.len + tq > ctx->cfg.max_cache_frames)
+        return fail(ctx, RNNT_ERR_SHAPE, "%s: slot %d: kept frames %d + %d exceed max_cache_frames %d", fn, slot, h.len, tq, ctx->cfg.max_cache_frames);
     return RNNT_OK;
 }
 
@@ -690,13 +776,88 @@ int pool_hist_check(rnnt_ctx* ctx, const char* fn, int slot, int tq) {
 int pool_hist_append_rows(rnnt_ctx* ctx, hipStream_t s, int n, const int32_t* slots_host, const int* slots_dev, int tq) {
     bool any = false;
     for (int i = 0; i < n; ++i) {
-        if (slots_host[i] >= (int)ctx->hs_slot.size() || !ctx->hs_slot[slots_host[i]].keep) continue;
-        ctx->hs_slot[slots_host[i]].len += tq;
+        if (!ctx->slot[slots_host[i]].hist.keep) continue;
+        ctx->slot[slots_host[i]].hist.len += tq;
         any = true;
     }
     if (!any) return RNNT_OK;
     hipLaunchKernelGGL(pool_hist_append, dim3(n), dim3(256), 0, s, ctx->x.p, slots_dev, ctx->hs_ptr.p, ctx->hs_len.p, tq);
     LAUNCHCHK("pool_hist_append");
+    return RNNT_OK;
+}
+
+// ---- what the per-slot forms share ------------------------------------------------------------------------------------------------------
+// every per-slot state of slots [slot0, slot0 + n) fresh (rnnt_stream_open: one slot; rnnt_streams_reset: all); the five write
+// disjoint buffers, so this one order serves both
+int pool_slot_reset(rnnt_ctx* ctx, hipStream_t s, int slot0, int n) {
+    int rc;
+    if ((rc = pool_beam_reset(ctx, s, slot0, n)) || (rc = pool_ctc_reset(ctx, s, slot0, n)) || (rc = pool_prefix_reset(ctx, s, slot0, n))) return rc;
+    pool_wave_reset(ctx, slot0, n);
+    return pool_hist_reset(ctx, s, slot0, n);
+}
+
+// The one place that refuses the slot list of a pool call: a row count outside [1, limit], a slot outside [0, limit), a slot listed
+// twice.  The limit is the entry point's own: n_streams for pool_chunk_run and rnnt_pool_rescore, max_streams for the seams
+// (prefix frames, CTC log-probabilities, wave).  between() holds the refusals an entry point makes after the row count and before
+// the first slot, row(i, slot) those of row i once its slot has passed, so the order of its refusals is its own.
+template <typename Between, typename Row>
+int pool_slots_check(rnnt_ctx* ctx, const char* fn, int n, const int32_t* slots, int limit, const char* what, Between between, Row row) {
+    if (n < 1 || n > limit) return fail(ctx, RNNT_ERR_ARG, "%s: %d %s of %d", fn, n, what, limit);
+    if (int rc = between()) return rc;
+    std::vector<char> seen((size_t)limit, 0);
+    for (int i = 0; i < n; ++i) {
+        const int slot = slots[i];
+        if (slot < 0 || slot >= limit) return fail(ctx, RNNT_ERR_ARG, "%s: row %d: slot %d outside [0, %d)", fn, i, slot, limit);
+        if (seen[slot]) return fail(ctx, RNNT_ERR_ARG, "%s: slot %d listed twice", fn, slot);
+        seen[slot] = 1;
+        if (int rc = row(i, slot)) return rc;
+    }
+    return RNNT_OK;
+}
+int pool_slots_check(rnnt_ctx* ctx, const char* fn, int n, const int32_t* slots, int limit, const char* what = "active slots") {
+    return pool_slots_check(ctx, fn, n, slots, limit, what, [] { return (int)RNNT_OK; }, [](int, int) { return (int)RNNT_OK; });
+}
+
+// The rules of a search in progress (PoolSlot::ctc or ::prefix) for the listed slots advancing by t frames: the first advancing call
+// fixed the parameters until the next reset; a search biased under an older graph generation holds node ids of a graph that no longer
+// exists; max_cache_frames bounds a search.  weights: the transducer form's message carries them (the CTC search keeps 0).
+int search_slot_check(rnnt_ctx* ctx, const char* fn, SearchSlot PoolSlot::*search, int n, const int* slots, int t, int beam_size, float cw, float tw,
+                      int use_context, bool weights) {
+    for (int i = 0; i < n; ++i) {
+        const SearchSlot& q = ctx->slot[slots[i]].*search;
+        if (q.beam != 0 && (q.beam != beam_size || q.cw != cw || q.tw != tw || (q.use_context != 0) != (use_context != 0))) {
+            if (weights)
+                return fail(ctx, RNNT_ERR_ARG,
+                            "%s: slot %d: beam_size %d / weights %g, %g / use_context %d differ from the search in progress (%d / %g, %g / %d); reset the slot first", fn,
+                            slots[i], beam_size, cw, tw, use_context != 0, q.beam, q.cw, q.tw, q.use_context);
+            return fail(ctx, RNNT_ERR_ARG, "%s: slot %d: beam_size %d / use_context %d differ from the search in progress (%d / %d); reset the slot first", fn,
+                        slots[i], beam_size, use_context != 0, q.beam, q.use_context);
+        }
+        if (q.beam != 0 && q.use_context && q.gen != ctx->cg_gen)
+            return fail(ctx, RNNT_ERR_STATE, "%s: slot %d: the context graph changed since its search began; reset the slot first", fn, slots[i]);
+        if ((long long)q.frames_done + t > ctx->cfg.max_cache_frames)
+            return fail(ctx, RNNT_ERR_SHAPE, "%s: slot %d: %d + %d frames exceed max_cache_frames %d", fn, slots[i], q.frames_done, t, ctx->cfg.max_cache_frames);
+    }
+    return RNNT_OK;
+}
+
+// after the launches: t more frames walked; the parameters are fixed by the first call (later ones passed the check with the same values)
+void search_slot_commit(rnnt_ctx* ctx, SearchSlot PoolSlot::*search, int n, const int* slots, int t, int beam_size, float cw, float tw, int use_context) {
+    for (int i = 0; i < n; ++i) {
+        SearchSlot& q = ctx->slot[slots[i]].*search;
+        q.frames_done += t;
+        q.beam = beam_size; q.cw = cw; q.tw = tw; q.use_context = use_context != 0; q.gen = ctx->cg_gen;
+    }
+}
+
+// What a read of a slot's search does about the context graph.  biased: it carries context scores (a fresh slot has fixed no graph
+// and finalizes its root under the one that is set, if any).  fin: it finalizes, which needs the graph the search ran under.
+struct SearchRead { bool biased, fin; };
+int search_slot_read(rnnt_ctx* ctx, const char* fn, int slot, const SearchSlot& q, int final, SearchRead& r) {
+    r.biased = q.beam > 0 ? q.use_context != 0 : (final != 0 && ctx->cg_on);
+    r.fin = r.biased && final != 0;
+    if (r.fin && q.beam > 0 && (!ctx->cg_on || q.gen != ctx->cg_gen))
+        return fail(ctx, RNNT_ERR_STATE, "%s: slot %d: the context graph changed since its search began (final = 0 still reads it)", fn, slot);
     return RNNT_OK;
 }
 

@@ -102,6 +102,32 @@ struct DevBuf {
 template <typename T>
 using PinnedBuf = DevBuf<T, true>;
 
+// Per slot of the stream pool, on the host.  SearchSlot, a prefix search carried across calls: the frames walked, and what its first
+// advancing call fixed until the next reset -- beam (0: fresh), the two weights (0 for the CTC search), use_context, the graph
+// generation (rnnt_ctx::cg_gen).  WvSlot, the front-end: samples received and frames emitted since the reset, the (sample_rate,
+// n_fft) its first push fixed (n_fft == 0: fresh), whether its utterance has ended.  HsSlot, the frame history: flag and length.
+struct SearchSlot { int frames_done, beam; float cw, tw; int use_context; int64_t gen; };
+struct WvSlot { int samples, frames, rate, nfft, finished; };
+struct HsSlot { int keep, len; };
+// One record per slot (rnnt_ctx::slot, sized to max_streams by rnnt_create; pool_slot_reset makes slots fresh): the position, the
+// current buffer set of the beam and of the transducer prefix search, a host upper bound of the beam's longest hypothesis.
+struct PoolSlot {
+    SlotPos pos{0, 0, 0};
+    int beam_cur = 0, beam_lbound = 0, prefix_cur = 0;
+    SearchSlot ctc{}, prefix{};
+    WvSlot wave{};
+    HsSlot hist{};
+};
+// The table of one pool call: ints filled in pinned memory and sent by ONE async copy; the event says the copy has left the pinned
+// buffer, so the next call may fill it again (calltab_alloc / calltab_fill / calltab_send, host_launch.hip.inc).
+struct CallTab {
+    DevBuf<int> dev;
+    PinnedBuf<int> host;
+    hipEvent_t ev = nullptr;
+    ~CallTab() { if (ev) (void)hipEventDestroy(ev); }
+    operator int*() const { return dev.p; }
+};
+
 enum WfType { WF_FFN1M, WF_FFN2M, WF_QKV, WF_OUT, WF_PW1, WF_PW2, WF_FFN1, WF_FFN2, WF_ATTN, WF_DW, WF_LN, WF_BLOCK_FRONT, WF_BLOCK_BACK };
 
 }  // namespace
@@ -171,15 +197,13 @@ struct rnnt_ctx {
     SlotPos pos{0, 0, 0};
     int frames_buffered = 0, frames_decoded = 0;
     int64_t launches = 0, greedy_steps = 0;
-    // stream pool (api_pool.hip.inc): once rnnt_stream_open or rnnt_pool_chunk has run, every slot has its own position and `pos`
-    // above is dead until the next rnnt_streams_reset.  Positions are host integers advanced by the reference's bookkeeping
-    // (encoder.py:254-264) and mirrored per call into ONE device table: n PoolRow entries followed by the n slot indices the decoder
-    // reads, written by one async copy from the pinned host copy (pool_ev: that copy has left the host buffer).
-    std::vector<SlotPos> slot_pos;
+    // stream pool (api_pool.hip.inc): once rnnt_stream_open or rnnt_pool_chunk has run, every slot has its own position (slot[b].pos)
+    // and `pos` above is dead until the next rnnt_streams_reset.  Positions are host integers advanced by the reference's bookkeeping
+    // (encoder.py:254-264) and mirrored per call into ONE device table: n PoolRow entries, the n slot indices the decoder reads and
+    // the current buffer set per active row of a search that has two ([max_streams] (POOL_ROW_INTS + 2) ints).
+    std::vector<PoolSlot> slot;
     bool pool_mode = false;
-    DevBuf<int> pool_tab;                      // device: [max_streams] PoolRow + [max_streams] int
-    PinnedBuf<int> pool_tab_host;
-    hipEvent_t pool_ev = nullptr;
+    CallTab pool_tab;
     int gemm_m_cap = 0;                        // > 0 during a pool call: GEMM kernels / tiles are chosen as for at most this many rows
     // wavefront (whole-utterance) path: per-chunk x rows, per-layer scratch, subsampling slabs, descriptor tables
     DevBuf<float> wf_x, wf_h, wf_q, wf_a, wf_d, wf_y1, wf_y2;
@@ -233,12 +257,11 @@ struct rnnt_ctx {
     // per-slot beam state of the stream pool (rnnt_pool_chunk_beam), separate from the lock-step state above and allocated on the
     // first beam call: hypothesis i of slot b is row b * max_beam + i of two buffer sets -- state pools, token lists
     // [2][max_rows][max_tokens], lengths / scores / hashes [2][max_rows] -- plus the hypotheses per slot.  Slots advance
-    // independently, so the current set is per slot (ps_cur, host); ps_lbound is a host upper bound of the slot's longest hypothesis.
+    // independently, so the current set is per slot (PoolSlot::beam_cur, with beam_lbound).
     DevBuf<float> ps_pool[2];
     DevBuf<int> ps_tok, ps_len, ps_nh;
     DevBuf<double> ps_sc;
     DevBuf<unsigned long long> ps_hs;
-    std::vector<int> ps_cur, ps_lbound;
     // feature front-end (rnnt_fbank): DFT / mel matrices for (fb_rate, fb_nfft) and work buffers
     DevBuf<float> fb_dft, fb_mel, fb_pad, fb_spec, fb_pow;
     int fb_rate = 0, fb_nfft = 0;
@@ -267,49 +290,32 @@ struct rnnt_ctx {
     DevBuf<float> cp_lp;
     // CTC prefix search per slot of the stream pool (api_pool_ctc.hip.inc), allocated on its first use: the hypothesis record of every
     // slot, the two arenas [max_streams][max_cache_frames * CP_MAX_BEAM + 1], the call's table (slot and frames walked per active
-    // row, one async copy from pinned memory), one read's packed block.  Host per slot: frames walked, and beam / use_context / graph
-    // generation of the search in progress (beam == 0: fresh).  cg_gen counts rnnt_context_set calls.
-    struct PcSlot { int frames_done, beam, use_context; int64_t gen; };
-    std::vector<PcSlot> pc_slot;
+    // row, [max_streams] 2 ints), one read's packed block.  Host per slot: PoolSlot::ctc.  cg_gen counts rnnt_context_set calls.
     int64_t cg_gen = 0;
     DevBuf<CpSlotState> pc_state;
     DevBuf<int2> pc_parena, pc_tarena;
-    DevBuf<int> pc_tab;
-    PinnedBuf<int> pc_tab_host;
-    hipEvent_t pc_ev = nullptr;
+    CallTab pc_tab;
     DevBuf<double> pc_out;
     // transducer prefix beam search per slot of the stream pool (api_pool_prefix.hip.inc), allocated on its first use: hypothesis i of
     // slot b is row b * PB_MAX_BEAM + i of two buffer sets -- states [rows][2][512], token lists [rows][max_cache_frames + 1],
     // lengths / scores / hashes [rows] -- plus the hypotheses per slot, the step's top-k [rows][PB_MAX_BEAM], the frames of one call
-    // (projected, CTC log-probabilities; grow-only), the seam form's table (slot and current set per active row, one async copy from
-    // pinned memory) and one read's packed block.  Host per slot: the current set (pp_cur; slots advance independently), and the
-    // frames walked, beam, weights, use_context and graph generation of the search in progress (beam == 0: fresh).  A biased search
+    // (projected, CTC log-probabilities; grow-only), the seam form's table (slot and current set per active row, [max_streams] 2 ints)
+    // and one read's packed block.  Host per slot: PoolSlot::prefix and prefix_cur (slots advance independently).  A biased search
     // also keeps a context state and score per row (pp_cst / pp_cs).
     int prefix_group = 0;                      // RNNT_PREFIX_GROUP: 0 by the size of the launch, 1 / 4 hypotheses per prefix_step_pool workgroup always
-    struct PpSlot { int frames_done, beam; float cw, tw; int use_context; int64_t gen; };
-    std::vector<PpSlot> pp_slot;
-    std::vector<int> pp_cur;
     DevBuf<float> pp_pool[2], pp_toplp, pp_encp, pp_ctc;
-    DevBuf<int> pp_tk[2], pp_len[2], pp_cst[2], pp_nh, pp_toptok, pp_tab;
+    DevBuf<int> pp_tk[2], pp_len[2], pp_cst[2], pp_nh, pp_toptok;
     DevBuf<double> pp_sc[2], pp_cs[2], pp_out;
     DevBuf<unsigned long long> pp_hs[2];
-    PinnedBuf<int> pp_tab_host;
-    hipEvent_t pp_ev = nullptr;
+    CallTab pp_tab;
     // streaming feature front-end per slot of the stream pool (api_pool_wave.hip.inc), allocated on its first use: the carry of every
     // slot [max_streams][WAVE_CARRY_CAP], the staged rows of one call (grow-only), the call's table (slot, samples so far, new samples,
-    // final per active row; one async copy from pinned memory).  Host per slot: samples received and frames emitted since the reset,
-    // the (sample_rate, n_fft) its first push fixed (n_fft == 0: fresh) and whether its utterance has ended.
-    struct WvSlot { int samples, frames, rate, nfft, finished; };
-    std::vector<WvSlot> wv_slot;
+    // final per active row, [max_streams] WAVE_TAB_INTS ints).  Host per slot: PoolSlot::wave.
     DevBuf<float> wv_carry, wv_stage;
-    DevBuf<int> wv_tab;
-    PinnedBuf<int> wv_tab_host;
-    hipEvent_t wv_ev = nullptr;
+    CallTab wv_tab;
     // encoder-frame history per slot of the stream pool (api_pool_hist.hip.inc), allocated on a slot's first rnnt_stream_keep_frames:
     // hs_buf[slot] [max_cache_frames][256], the device tables hs_ptr / hs_len [max_streams] the append and gather kernels index by
-    // slot, the dense staging of rnnt_pool_rescore (grow-only).  Host per slot: the flag and the mirrored length.
-    struct HsSlot { int keep, len; };
-    std::vector<HsSlot> hs_slot;
+    // slot, the dense staging of rnnt_pool_rescore (grow-only).  Host per slot: PoolSlot::hist.
     std::vector<DevBuf<float>> hs_buf;
     DevBuf<float*> hs_ptr;
     DevBuf<int> hs_len;
@@ -324,11 +330,11 @@ struct rnnt_ctx {
     std::vector<hipEvent_t> prof_ev;
     size_t prof_used = 0;
 
-    // The only free list: streams, events and graphs here, every buffer through its owner's destructor.  No user-provided
+    // The only free list: streams, events and graphs here, every buffer and call table through its owner's destructor.  No user-provided
     // constructor -- rnnt_create's `new rnnt_ctx()` value-initialises lw[] and the raw weight views to null.
     ~rnnt_ctx() {
         for (auto& g : dec_graphs) (void)hipGraphExecDestroy(g.exec);
-        for (hipEvent_t e : {pool_ev, pc_ev, pp_ev, wv_ev, sub_ev[0], sub_ev[1]}) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : {sub_ev[0], sub_ev[1]}) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : prof_ev) (void)hipEventDestroy(e);
         for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
         for (hipStream_t st : {dec_stream, cap_stream, sub_stream}) if (st) (void)hipStreamDestroy(st);

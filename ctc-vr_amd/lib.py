@@ -173,13 +173,15 @@ def _np_ptr(a):
     return a.ctypes.data_as(c_vp)
 
 
-def _prefix_merge_call(fn, head, hyps, top_lp, top_tok, blank, beam_size, tail=()):
+def _prefix_merge_call(fn, head, hyps, top_lp, top_tok, blank, beam_size, tail=(), graph=None):
     """Flat arguments of rnnt_prefix_merge_host / rnnt_prefix_merge_device -> the call's return value and
-    [(tokens, score, src_row, src_slot)] of the survivors."""
+    [(tokens, score, src_row, src_slot)] of the survivors.  graph not None: the _ctx forms -- hyps [(tokens, score, context state,
+    context score)], graph the host form's phrase arguments (() for the device form), survivors with (context state, context
+    score) appended."""
     n = len(hyps)
-    hl = np.array([len(t) for t, _ in hyps], np.int32)
-    ht = np.array([x for t, _ in hyps for x in t] or [0], np.int32)
-    hs = np.array([sc for _, sc in hyps], np.float64)
+    hl = np.array([len(h[0]) for h in hyps], np.int32)
+    ht = np.array([x for h in hyps for x in h[0]] or [0], np.int32)
+    hs = np.array([h[1] for h in hyps], np.float64)
     tl = np.ascontiguousarray(top_lp, np.float32).reshape(n, -1)
     tt = np.ascontiguousarray(top_tok, np.int32).reshape(n, -1)
     k = tl.shape[1]
@@ -187,11 +189,17 @@ def _prefix_merge_call(fn, head, hyps, top_lp, top_tok, blank, beam_size, tail=(
     cap = max(beam_size, 1)
     out_len, out_tok = np.zeros(cap, np.int32), np.zeros(cap * (int(hl.max(initial=0)) + 1) + 1, np.int32)
     out_sc, out_row, out_slot = np.zeros(cap, np.float64), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
-    m = fn(*head, n, _np_ptr(hl), _np_ptr(ht), _np_ptr(hs), _np_ptr(tl), _np_ptr(tt), k, blank, beam_size, _np_ptr(out_len), _np_ptr(out_tok),
-           _np_ptr(out_sc), _np_ptr(out_row), _np_ptr(out_slot), *tail)
+    hyp_ctx = out_ctx = ()
+    if graph is not None:
+        hst, hcs = np.array([h[2] for h in hyps], np.int32), np.array([h[3] for h in hyps], np.float64)
+        out_st, out_cs = np.zeros(cap, np.int32), np.zeros(cap, np.float64)
+        hyp_ctx, out_ctx = (_np_ptr(hst), _np_ptr(hcs)), (_np_ptr(out_st), _np_ptr(out_cs))
+    m = fn(*head, n, _np_ptr(hl), _np_ptr(ht), _np_ptr(hs), *hyp_ctx, _np_ptr(tl), _np_ptr(tt), k, blank, beam_size, *(graph or ()),
+           _np_ptr(out_len), _np_ptr(out_tok), _np_ptr(out_sc), _np_ptr(out_row), _np_ptr(out_slot), *out_ctx, *tail)
     out, o = [], 0
     for a in range(max(m, 0)):
-        out.append((out_tok[o:o + out_len[a]].tolist(), float(out_sc[a]), int(out_row[a]), int(out_slot[a])))
+        ctx_part = (int(out_st[a]), float(out_cs[a])) if graph is not None else ()
+        out.append((out_tok[o:o + out_len[a]].tolist(), float(out_sc[a]), int(out_row[a]), int(out_slot[a])) + ctx_part)
         o += out_len[a]
     return m, out
 
@@ -205,39 +213,13 @@ def prefix_merge_host(hyps, top_lp, top_tok, blank, beam_size):
     return out
 
 
-def _prefix_merge_ctx_call(fn, head, hyps, top_lp, top_tok, blank, beam_size, graph=(), tail=()):
-    """Flat arguments of rnnt_prefix_merge_ctx_host / rnnt_prefix_merge_ctx_device (hyps [(tokens, score, context state, context
-    score)]; graph: the host form's phrase arguments) -> the call's return value and [(tokens, score, src_row, src_slot, context
-    state, context score)] of the survivors."""
-    n = len(hyps)
-    hl = np.array([len(h[0]) for h in hyps], np.int32)
-    ht = np.array([x for h in hyps for x in h[0]] or [0], np.int32)
-    hs = np.array([h[1] for h in hyps], np.float64)
-    hst = np.array([h[2] for h in hyps], np.int32)
-    hcs = np.array([h[3] for h in hyps], np.float64)
-    tl = np.ascontiguousarray(top_lp, np.float32).reshape(n, -1)
-    tt = np.ascontiguousarray(top_tok, np.int32).reshape(n, -1)
-    assert tt.shape == tl.shape
-    cap = max(beam_size, 1)
-    out_len, out_tok = np.zeros(cap, np.int32), np.zeros(cap * (int(hl.max(initial=0)) + 1) + 1, np.int32)
-    out_sc, out_row, out_slot = np.zeros(cap, np.float64), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
-    out_st, out_cs = np.zeros(cap, np.int32), np.zeros(cap, np.float64)
-    m = fn(*head, n, _np_ptr(hl), _np_ptr(ht), _np_ptr(hs), _np_ptr(hst), _np_ptr(hcs), _np_ptr(tl), _np_ptr(tt), tl.shape[1], blank, beam_size, *graph,
-           _np_ptr(out_len), _np_ptr(out_tok), _np_ptr(out_sc), _np_ptr(out_row), _np_ptr(out_slot), _np_ptr(out_st), _np_ptr(out_cs), *tail)
-    out, o = [], 0
-    for a in range(max(m, 0)):
-        out.append((out_tok[o:o + out_len[a]].tolist(), float(out_sc[a]), int(out_row[a]), int(out_slot[a]), int(out_st[a]), float(out_cs[a])))
-        o += out_len[a]
-    return m, out
-
-
 def prefix_merge_ctx_host(hyps, top_lp, top_tok, blank, beam_size, phrases, context_score):
     """rnnt_prefix_merge_ctx_host (no context, no GPU): prefix_merge_host with the context graph over `phrases`.  hyps [(tokens,
     score, context state, context score)] -> [(tokens, fused score, src_row, src_slot, context state, context score)] of the
     survivors, ordered by fused score + context score."""
     n, pl, pt = _phrase_args(phrases)
-    m, out = _prefix_merge_ctx_call(load().rnnt_prefix_merge_ctx_host, (), hyps, top_lp, top_tok, blank, beam_size,
-                                    (n, _np_ptr(pl), _np_ptr(pt), float(context_score)))
+    m, out = _prefix_merge_call(load().rnnt_prefix_merge_ctx_host, (), hyps, top_lp, top_tok, blank, beam_size,
+                                graph=(n, _np_ptr(pl), _np_ptr(pt), float(context_score)))
     if m < 0:
         raise RnntError(f"rnnt_prefix_merge_ctx_host: bad argument (status {m})", m)
     return out
@@ -446,11 +428,15 @@ class RnntEngine:
         """rnnt_pool_chunk: one chunk of `chunk_frames` frames for every listed slot, row i of the device tensor at fbank_ptr
         ([len(slots), chunk_frames, 80]) belonging to slots[i] and encoded with (offsets[i], required[i]) at that slot's own
         position; greedy: decode + consume the new frames of exactly those slots.  Returns t', the new encoder frames per slot."""
+        return self._pool_chunk("rnnt_pool_chunk", slots, fbank_ptr, chunk_frames, offsets, required, (1 if greedy else 0,), stream)
+
+    def _pool_chunk(self, name, slots, fbank_ptr, chunk_frames, offsets, required, extra, stream):
+        """What the rnnt_pool_chunk* entry points share: (slots, offsets, required) as int32 arrays of one length, the entry point's
+        own arguments (extra) after them, t' back."""
         a, o, r = (np.ascontiguousarray(v, np.int32) for v in (slots, offsets, required))
         assert a.ndim == 1 and a.size == o.size == r.size
         t = c_i32(0)
-        self._chk(self.lib.rnnt_pool_chunk(self.ctx, a.size, _np_ptr(a), fbank_ptr, chunk_frames, _np_ptr(o), _np_ptr(r), 1 if greedy else 0,
-                                           ctypes.byref(t), stream), "rnnt_pool_chunk")
+        self._chk(getattr(self.lib, name)(self.ctx, a.size, _np_ptr(a), fbank_ptr, chunk_frames, _np_ptr(o), _np_ptr(r), *extra, ctypes.byref(t), stream), name)
         return t.value
 
     def stream_tokens(self, slot, start=0, stream=None):
@@ -467,12 +453,7 @@ class RnntEngine:
         """rnnt_pool_chunk_beam: pool_chunk's encoder for the listed slots, then the beam recursion over the new frames of exactly
         those slots, each on its own device-resident beam; the frames are consumed.  Does not synchronise (stream_beam does).
         Returns t'.  Raises RnntError when the call refuses (max_beam = 0, beam_size > min(max_beam, 16), vocab > 512, ...)."""
-        a, o, r = (np.ascontiguousarray(v, np.int32) for v in (slots, offsets, required))
-        assert a.ndim == 1 and a.size == o.size == r.size
-        t = c_i32(0)
-        self._chk(self.lib.rnnt_pool_chunk_beam(self.ctx, a.size, _np_ptr(a), fbank_ptr, chunk_frames, _np_ptr(o), _np_ptr(r), beam_size,
-                                                ctypes.byref(t), stream), "rnnt_pool_chunk_beam")
-        return t.value
+        return self._pool_chunk("rnnt_pool_chunk_beam", slots, fbank_ptr, chunk_frames, offsets, required, (beam_size,), stream)
 
     def stream_beam(self, slot, stream=None):
         """rnnt_stream_get_beam: [(tokens, log_prob), ...] of one slot in beam order."""
@@ -652,25 +633,11 @@ class RnntEngine:
         over its first enc_lens[b] frames, the whole frame loop on the device.  Returns per utterance [(tokens incl. the leading
         blank, score)], best first; with want_states also (h, c), each [B, beam_size, 256] (rows beyond an utterance's hypotheses
         are zero)."""
-        el = np.ascontiguousarray(enc_lens, np.int32)
-        assert el.size == B
-        w = max(beam_size, 1)
-        cap = int(el.max(initial=0)) + 1
-        nh, lens = np.zeros(B, np.int32), np.zeros((B, w), np.int32)
-        toks, sc = np.zeros((B, w, cap), np.int32), np.zeros((B, w), np.float64)
-        h = np.zeros((B, w, 256), np.float32) if want_states else None
-        c = np.zeros((B, w, 256), np.float32) if want_states else None
-        self._chk(self.lib.rnnt_prefix_beam_decode(self.ctx, enc_ptr, _np_ptr(el), B, T, beam_size, ctc_weight, transducer_weight, cap, _np_ptr(nh),
-                                                   _np_ptr(lens), _np_ptr(toks), _np_ptr(sc), _np_ptr(h) if want_states else None,
-                                                   _np_ptr(c) if want_states else None, stream), "rnnt_prefix_beam_decode")
-        hyps = [[(toks[b, i, :lens[b, i]].tolist(), float(sc[b, i])) for i in range(nh[b])] for b in range(B)]
-        return (hyps, h, c) if want_states else hyps
+        return self._prefix_decode(enc_ptr, enc_lens, B, T, beam_size, ctc_weight, transducer_weight, None, want_states, stream)
 
-    def prefix_beam_decode_ctx(self, enc_ptr, enc_lens, B, T, beam_size=5, ctc_weight=0.3, transducer_weight=0.7, use_context=True, want_states=False,
-                               stream=None):
-        """rnnt_prefix_beam_decode_ctx: prefix_beam_decode biased by the graph of context_set when use_context.  Returns per
-        utterance [(tokens incl. the leading blank, total score, context score)] in the search's order (finalize replaces the
-        context scores at the end without a re-sort, so the totals need not descend); with want_states also (h, c)."""
+    def _prefix_decode(self, enc_ptr, enc_lens, B, T, beam_size, ctc_weight, transducer_weight, use_context, want_states, stream):
+        """rnnt_prefix_beam_decode (use_context None) or rnnt_prefix_beam_decode_ctx (which also has a context score per hypothesis)."""
+        biased = use_context is not None
         el = np.ascontiguousarray(enc_lens, np.int32)
         assert el.size == B
         w = max(beam_size, 1)
@@ -679,12 +646,20 @@ class RnntEngine:
         toks, sc, cs = np.zeros((B, w, cap), np.int32), np.zeros((B, w), np.float64), np.zeros((B, w), np.float64)
         h = np.zeros((B, w, 256), np.float32) if want_states else None
         c = np.zeros((B, w, 256), np.float32) if want_states else None
-        self._chk(self.lib.rnnt_prefix_beam_decode_ctx(self.ctx, enc_ptr, _np_ptr(el), B, T, beam_size, ctc_weight, transducer_weight, 1 if use_context else 0,
-                                                       cap, _np_ptr(nh), _np_ptr(lens), _np_ptr(toks), _np_ptr(sc), _np_ptr(cs),
-                                                       _np_ptr(h) if want_states else None, _np_ptr(c) if want_states else None, stream),
-                  "rnnt_prefix_beam_decode_ctx")
-        hyps = [[(toks[b, i, :lens[b, i]].tolist(), float(sc[b, i]), float(cs[b, i])) for i in range(nh[b])] for b in range(B)]
+        name = "rnnt_prefix_beam_decode_ctx" if biased else "rnnt_prefix_beam_decode"
+        self._chk(getattr(self.lib, name)(self.ctx, enc_ptr, _np_ptr(el), B, T, beam_size, ctc_weight, transducer_weight,
+                                          *((1 if use_context else 0,) if biased else ()), cap, _np_ptr(nh), _np_ptr(lens), _np_ptr(toks), _np_ptr(sc),
+                                          *((_np_ptr(cs),) if biased else ()), _np_ptr(h) if want_states else None, _np_ptr(c) if want_states else None,
+                                          stream), name)
+        hyps = [[(toks[b, i, :lens[b, i]].tolist(), float(sc[b, i])) + ((float(cs[b, i]),) if biased else ()) for i in range(nh[b])] for b in range(B)]
         return (hyps, h, c) if want_states else hyps
+
+    def prefix_beam_decode_ctx(self, enc_ptr, enc_lens, B, T, beam_size=5, ctc_weight=0.3, transducer_weight=0.7, use_context=True, want_states=False,
+                               stream=None):
+        """rnnt_prefix_beam_decode_ctx: prefix_beam_decode biased by the graph of context_set when use_context.  Returns per
+        utterance [(tokens incl. the leading blank, total score, context score)] in the search's order (finalize replaces the
+        context scores at the end without a re-sort, so the totals need not descend); with want_states also (h, c)."""
+        return self._prefix_decode(enc_ptr, enc_lens, B, T, beam_size, ctc_weight, transducer_weight, bool(use_context), want_states, stream)
 
     # ---- CTC prefix beam search with contextual biasing ------------------------------------------
     def context_set(self, phrases, context_score=6.0):
@@ -726,12 +701,7 @@ class RnntEngine:
     def pool_chunk_ctc_prefix(self, slots, fbank_ptr, chunk_frames, offsets, required, beam_size=10, use_context=False, stream=None):
         """rnnt_pool_chunk_ctc_prefix: pool_chunk's encoder for the listed slots, the CTC log-probabilities of their new frames, and
         their searches advanced by those frames; the frames are consumed.  Does not synchronise (stream_ctc_prefix does).  Returns t'."""
-        a, o, r = (np.ascontiguousarray(v, np.int32) for v in (slots, offsets, required))
-        assert a.ndim == 1 and a.size == o.size == r.size
-        t = c_i32(0)
-        self._chk(self.lib.rnnt_pool_chunk_ctc_prefix(self.ctx, a.size, _np_ptr(a), fbank_ptr, chunk_frames, _np_ptr(o), _np_ptr(r), beam_size,
-                                                      1 if use_context else 0, ctypes.byref(t), stream), "rnnt_pool_chunk_ctc_prefix")
-        return t.value
+        return self._pool_chunk("rnnt_pool_chunk_ctc_prefix", slots, fbank_ptr, chunk_frames, offsets, required, (beam_size, 1 if use_context else 0), stream)
 
     def stream_ctc_prefix(self, slot, final=False, raw=False, cap_hyps=None, cap_tokens=None, stream=None):
         """rnnt_stream_get_ctc_prefix: [(tokens, score, times, context score)] of one slot in the search's order, as they stand
@@ -767,12 +737,7 @@ class RnntEngine:
     def pool_chunk_prefix(self, slots, fbank_ptr, chunk_frames, offsets, required, beam_size=5, ctc_weight=0.3, transducer_weight=0.7, stream=None):
         """rnnt_pool_chunk_prefix: pool_chunk's encoder for the listed slots and their prefix beam searches advanced by the new frames;
         the frames are consumed.  Does not synchronise (stream_prefix does).  Returns t'."""
-        a, o, r = (np.ascontiguousarray(v, np.int32) for v in (slots, offsets, required))
-        assert a.ndim == 1 and a.size == o.size == r.size
-        t = c_i32(0)
-        self._chk(self.lib.rnnt_pool_chunk_prefix(self.ctx, a.size, _np_ptr(a), fbank_ptr, chunk_frames, _np_ptr(o), _np_ptr(r), beam_size, ctc_weight,
-                                                  transducer_weight, ctypes.byref(t), stream), "rnnt_pool_chunk_prefix")
-        return t.value
+        return self._pool_chunk("rnnt_pool_chunk_prefix", slots, fbank_ptr, chunk_frames, offsets, required, (beam_size, ctc_weight, transducer_weight), stream)
 
     def pool_prefix_frames_ctx(self, slots, enc_ptr, t, beam_size=5, ctc_weight=0.3, transducer_weight=0.7, use_context=True, stream=None):
         """rnnt_pool_prefix_frames_ctx: pool_prefix_frames for searches biased by the graph of context_set (use_context)."""
@@ -784,27 +749,30 @@ class RnntEngine:
     def pool_chunk_prefix_ctx(self, slots, fbank_ptr, chunk_frames, offsets, required, beam_size=5, ctc_weight=0.3, transducer_weight=0.7, use_context=True,
                               stream=None):
         """rnnt_pool_chunk_prefix_ctx: pool_chunk_prefix for searches biased by the graph of context_set (use_context).  Returns t'."""
-        a, o, r = (np.ascontiguousarray(v, np.int32) for v in (slots, offsets, required))
-        assert a.ndim == 1 and a.size == o.size == r.size
-        t = c_i32(0)
-        self._chk(self.lib.rnnt_pool_chunk_prefix_ctx(self.ctx, a.size, _np_ptr(a), fbank_ptr, chunk_frames, _np_ptr(o), _np_ptr(r), beam_size, ctc_weight,
-                                                      transducer_weight, 1 if use_context else 0, ctypes.byref(t), stream), "rnnt_pool_chunk_prefix_ctx")
-        return t.value
+        return self._pool_chunk("rnnt_pool_chunk_prefix_ctx", slots, fbank_ptr, chunk_frames, offsets, required,
+                                (beam_size, ctc_weight, transducer_weight, 1 if use_context else 0), stream)
 
     def stream_prefix_ctx(self, slot, final=False, states=False, stream=None):
         """rnnt_stream_get_prefix_ctx: [(tokens incl. the leading blank, total score, context score)] of one slot in the search's
         order, as they stand (final: finalize's context scores, what the one-call search returns had the utterance ended here);
         with states also (h, c), each [n_hyp, 256].  Reading changes nothing."""
+        return self._stream_prefix(slot, bool(final), states, stream)
+
+    def _stream_prefix(self, slot, final, states, stream):
+        """rnnt_stream_get_prefix (final None) or rnnt_stream_get_prefix_ctx (which also has a context score per hypothesis).  Sized
+        by the library's size query first (a host-only call), so a read costs what it returns."""
+        biased = final is not None
         w, _, cap = self.stream_prefix_size(slot)
         nh, lens = np.zeros(1, np.int32), np.zeros(w, np.int32)
         toks, sc, cs = np.zeros((w, cap), np.int32), np.zeros(w, np.float64), np.zeros(w, np.float64)
         h = np.zeros((w, 256), np.float32) if states else None
         c = np.zeros((w, 256), np.float32) if states else None
-        self._chk(self.lib.rnnt_stream_get_prefix_ctx(self.ctx, slot, 1 if final else 0, w, cap, _np_ptr(nh), _np_ptr(lens), _np_ptr(toks), _np_ptr(sc),
-                                                      _np_ptr(cs), _np_ptr(h) if states else None, _np_ptr(c) if states else None, stream),
-                  "rnnt_stream_get_prefix_ctx")
+        name = "rnnt_stream_get_prefix_ctx" if biased else "rnnt_stream_get_prefix"
+        self._chk(getattr(self.lib, name)(self.ctx, slot, *((1 if final else 0,) if biased else ()), w, cap, _np_ptr(nh), _np_ptr(lens), _np_ptr(toks),
+                                          _np_ptr(sc), *((_np_ptr(cs),) if biased else ()), _np_ptr(h) if states else None,
+                                          _np_ptr(c) if states else None, stream), name)
         n = int(nh[0])
-        hyps = [(toks[i, :lens[i]].tolist(), float(sc[i]), float(cs[i])) for i in range(n)]
+        hyps = [(toks[i, :lens[i]].tolist(), float(sc[i])) + ((float(cs[i]),) if biased else ()) for i in range(n)]
         return (hyps, h[:n], c[:n]) if states else hyps
 
     def stream_prefix_size(self, slot):
@@ -816,16 +784,7 @@ class RnntEngine:
     def stream_prefix(self, slot, states=False, stream=None):
         """rnnt_stream_get_prefix: [(tokens incl. the leading blank, score)] of one slot, best first, as they stand; with states also
         (h, c), each [n_hyp, 256].  Sized by the library's size query first (a host-only call), so a read costs what it returns."""
-        w, _, cap = self.stream_prefix_size(slot)
-        nh, lens = np.zeros(1, np.int32), np.zeros(w, np.int32)
-        toks, sc = np.zeros((w, cap), np.int32), np.zeros(w, np.float64)
-        h = np.zeros((w, 256), np.float32) if states else None
-        c = np.zeros((w, 256), np.float32) if states else None
-        self._chk(self.lib.rnnt_stream_get_prefix(self.ctx, slot, w, cap, _np_ptr(nh), _np_ptr(lens), _np_ptr(toks), _np_ptr(sc),
-                                                  _np_ptr(h) if states else None, _np_ptr(c) if states else None, stream), "rnnt_stream_get_prefix")
-        n = int(nh[0])
-        hyps = [(toks[i, :lens[i]].tolist(), float(sc[i])) for i in range(n)]
-        return (hyps, h[:n], c[:n]) if states else hyps
+        return self._stream_prefix(slot, None, states, stream)
 
     def pool_wave(self, slots, wave_ptr, n_samples, samples, final, out_ptr, cap_frames, sample_rate=16000, n_fft=1024, stream=None):
         """rnnt_pool_wave: the streaming feature front-end for the listed slots -- row i of the device tensor at wave_ptr
@@ -866,7 +825,7 @@ class RnntEngine:
     def prefix_merge_ctx_device(self, hyps, top_lp, top_tok, blank, beam_size, stream=None):
         """rnnt_prefix_merge_ctx_device: prefix_merge_ctx_host's hypotheses and results through one prefix_merge launch with the
         graph of context_set."""
-        m, out = _prefix_merge_ctx_call(self.lib.rnnt_prefix_merge_ctx_device, (self.ctx,), hyps, top_lp, top_tok, blank, beam_size, (), (stream,))
+        m, out = _prefix_merge_call(self.lib.rnnt_prefix_merge_ctx_device, (self.ctx,), hyps, top_lp, top_tok, blank, beam_size, (stream,), graph=())
         if m < 0:
             self._chk(m, "rnnt_prefix_merge_ctx_device")
         return out
