@@ -209,6 +209,7 @@ int pool_chunk_run(rnnt_ctx* ctx, const char* fn, int32_t n_active, const int32_
         // after_norm in place over the compact rows, then the joint's encoder projection into frames [0, t') of every active slot
         if ((rc = launch_ln(ctx, s, LnP{ctx->x, ctx->after_g, ctx->after_b, ctx->x, n * tq, BIG, 0, 0LL, (long long)D}))) return rc;
         if ((rc = pool_hist_append_rows(ctx, s, n, slots_host, slots_dev, tq))) return rc;   // slots that keep their frames (rnnt_stream_keep_frames)
+        if ((rc = pool_endpoint_rows(ctx, s, n, slots_host, slots_dev, ctx->x, tq))) return rc;   // slots that detect their endpoint (rnnt_stream_endpoint)
         // (the transducer prefix search reads the call's frames compact, row i * t' + f, from its own buffer)
         GemmP g = plain_gemm(ctx->x, D, ctx->wenc, D, ctx->benc, mode == POOL_PREFIX ? ctx->pp_encp.p : ctx->encp.p, D, n * tq, D, D);
         if (mode != POOL_PREFIX) {

@@ -786,13 +786,43 @@ int pool_hist_append_rows(rnnt_ctx* ctx, hipStream_t s, int n, const int32_t* sl
     return RNNT_OK;
 }
 
+// ---- per-slot endpoint detection of the stream pool (api_pool_endpoint.hip.inc; kernels in rnnt_endpoint.hip.h) --------------------------
+// what rnnt_stream_endpoint and rnnt_endpoint_scan_host accept, and the one float both sides compare against
+bool endpoint_config_ok(const rnnt_endpoint_config* c) {
+    return c->blank_threshold > 0.f && c->blank_threshold < 1.f && c->min_speech_frames >= 0 && c->rule1_trailing >= 0 && c->rule2_trailing >= 0 &&
+           c->rule3_frames >= 0;
+}
+float endpoint_log_thr(const rnnt_endpoint_config* c) { return (float)log((double)c->blank_threshold); }
+
+// the on flag of slots [slot0, slot0 + n) cleared, on the host and -- when one of them was on -- on the device (one launch)
+int pool_endpoint_reset(rnnt_ctx* ctx, hipStream_t s, int slot0, int n) {
+    bool any = false;
+    for (int b = slot0; b < slot0 + n; ++b) { any = any || ctx->slot[b].ep; ctx->slot[b].ep = 0; }
+    if (!any) return RNNT_OK;
+    hipLaunchKernelGGL(pool_endpoint_set, dim3((n + 63) / 64), dim3(64), 0, s, ctx->ep_cfg.p, ctx->ep_state.p, slot0, n, EpCfg{});
+    LAUNCHCHK("pool_endpoint_set");
+    return RNNT_OK;
+}
+
+// t compact rows per active row at src advance the listed endpoint slots: one launch, and only when a listed slot has endpointing on
+int pool_endpoint_rows(rnnt_ctx* ctx, hipStream_t s, int n, const int32_t* slots_host, const int* slots_dev, const float* src, int t) {
+    bool any = false;
+    for (int i = 0; i < n; ++i) any = any || ctx->slot[slots_host[i]].ep;
+    if (!any) return RNNT_OK;
+    hipLaunchKernelGGL(pool_endpoint, dim3(n), dim3(EP_THREADS), 0, s, src, slots_dev, ctx->ep_cfg.p, ctx->ep_state.p, t, ctx->wctc, ctx->bctc, ctx->cfg.vocab_size,
+                       ctx->cfg.blank_id);
+    LAUNCHCHK("pool_endpoint");
+    return RNNT_OK;
+}
+
 // ---- what the per-slot forms share ------------------------------------------------------------------------------------------------------
-// every per-slot state of slots [slot0, slot0 + n) fresh (rnnt_stream_open: one slot; rnnt_streams_reset: all); the five write
+// every per-slot state of slots [slot0, slot0 + n) fresh (rnnt_stream_open: one slot; rnnt_streams_reset: all); the six write
 // disjoint buffers, so this one order serves both
 int pool_slot_reset(rnnt_ctx* ctx, hipStream_t s, int slot0, int n) {
     int rc;
     if ((rc = pool_beam_reset(ctx, s, slot0, n)) || (rc = pool_ctc_reset(ctx, s, slot0, n)) || (rc = pool_prefix_reset(ctx, s, slot0, n))) return rc;
     pool_wave_reset(ctx, slot0, n);
+    if ((rc = pool_endpoint_reset(ctx, s, slot0, n))) return rc;
     return pool_hist_reset(ctx, s, slot0, n);
 }
 

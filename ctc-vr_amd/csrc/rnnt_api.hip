@@ -106,6 +106,7 @@ using PinnedBuf = DevBuf<T, true>;
 // advancing call fixed until the next reset -- beam (0: fresh), the two weights (0 for the CTC search), use_context, the graph
 // generation (rnnt_ctx::cg_gen).  WvSlot, the front-end: samples received and frames emitted since the reset, the (sample_rate,
 // n_fft) its first push fixed (n_fft == 0: fresh), whether its utterance has ended.  HsSlot, the frame history: flag and length.
+// ep: endpoint detection is on (the config and the counters live on the device, api_pool_endpoint.hip.inc).
 struct SearchSlot { int frames_done, beam; float cw, tw; int use_context; int64_t gen; };
 struct WvSlot { int samples, frames, rate, nfft, finished; };
 struct HsSlot { int keep, len; };
@@ -117,6 +118,7 @@ struct PoolSlot {
     SearchSlot ctc{}, prefix{};
     WvSlot wave{};
     HsSlot hist{};
+    int ep = 0;
 };
 // The table of one pool call: ints filled in pinned memory and sent by ONE async copy; the event says the copy has left the pinned
 // buffer, so the next call may fill it again (calltab_alloc / calltab_fill / calltab_send, host_launch.hip.inc).
@@ -320,6 +322,13 @@ struct rnnt_ctx {
     DevBuf<float*> hs_ptr;
     DevBuf<int> hs_len;
     DevBuf<float> hs_stage;
+    // endpoint detection per slot of the stream pool (api_pool_endpoint.hip.inc), allocated on the first rnnt_stream_endpoint: config
+    // (with the on flag) and the five counters per slot [max_streams], the call table of the seam form (the slot list), the pinned
+    // block one rnnt_pool_get_endpoints read lands in.  Host per slot: PoolSlot::ep (the on flag only).
+    DevBuf<EpCfg> ep_cfg;
+    DevBuf<int> ep_state;
+    CallTab ep_tab;
+    PinnedBuf<int> ep_host;
     hipStream_t cap_stream = nullptr;          // stream-capture scratch stream
     struct DecGraph { int n_streams, k; hipGraphExec_t exec; };
     std::vector<DecGraph> dec_graphs;          // K greedy steps captured once per (n_streams, K)
@@ -357,6 +366,7 @@ extern "C" {
 #include "api_pool_prefix.hip.inc"
 #include "api_pool.hip.inc"
 #include "api_pool_hist.hip.inc"
+#include "api_pool_endpoint.hip.inc"
 #include "api_pool_wave.hip.inc"
 #include "api_prefix.hip.inc"
 #include "api_ctc_prefix.hip.inc"

@@ -16,6 +16,12 @@ class RnntConfig(ctypes.Structure):
                 ("n_steps", c_i32), ("device", c_i32), ("max_beam", c_i32)]
 
 
+class RnntEndpointConfig(ctypes.Structure):
+    """rnnt_endpoint_config: blank threshold in (0, 1), S, and the three rules in encoder frames (0: rule off)."""
+    _fields_ = [("blank_threshold", ctypes.c_float), ("min_speech_frames", c_i32), ("rule1_trailing", c_i32), ("rule2_trailing", c_i32),
+                ("rule3_frames", c_i32)]
+
+
 # symbol -> (restype, argtypes); exactly the entry points declared in include/rnnt_hip.h
 SIGNATURES = {
     "rnnt_create": (c_i32, [ctypes.POINTER(RnntConfig), ctypes.POINTER(c_vp)]),
@@ -89,6 +95,11 @@ SIGNATURES = {
     "rnnt_stream_keep_frames": (c_i32, [c_vp, c_i32, c_i32, c_vp]),
     "rnnt_stream_get_frames": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32p, c_vp]),
     "rnnt_pool_rescore": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
+    "rnnt_stream_endpoint": (c_i32, [c_vp, c_i32, ctypes.POINTER(RnntEndpointConfig), c_vp]),
+    "rnnt_pool_endpoint_frames": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp]),
+    "rnnt_pool_get_endpoints": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "rnnt_ctc_blank_logprob": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp]),
+    "rnnt_endpoint_scan_host": (c_i32, [c_vp, c_i32, ctypes.POINTER(RnntEndpointConfig), c_vp]),
     "rnnt_transducer_align": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rnnt_transducer_align_pick": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "rnnt_ctc_align": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
@@ -320,6 +331,31 @@ def ctc_prefix_beam_host(lp, enc_lens, blank, beam_size, phrases=None, context_s
     if rc != 0:
         raise RnntError(f"rnnt_ctc_prefix_beam_host: bad argument (status {rc})", rc)
     return (_ctc_prefix_hyps(out), out) if raw else _ctc_prefix_hyps(out)
+
+
+def _endpoint_config(cfg):
+    """RnntEndpointConfig from one, from a 5-tuple (blank_threshold, min_speech_frames, rule1, rule2, rule3) or from an object with
+    those attributes (the facade's EndpointConfig)."""
+    if isinstance(cfg, RnntEndpointConfig):
+        return cfg
+    if isinstance(cfg, (tuple, list)):
+        thr, s, r1, r2, r3 = cfg
+    else:
+        thr, s, r1, r2, r3 = cfg.blank_threshold, cfg.min_speech_frames, cfg.rule1_trailing, cfg.rule2_trailing, cfg.rule3_frames
+    return RnntEndpointConfig(float(thr), int(s), int(r1), int(r2), int(r3))
+
+
+def endpoint_scan_host(blank_lp, cfg, state=None):
+    """rnnt_endpoint_scan_host (no context, no GPU): the endpoint state [frames, trailing, speech, rule, at] after the float32
+    log-posteriors blank_lp, starting from `state` (None: a fresh slot's zeros).  Returns a new int32 array [5]."""
+    lp = np.ascontiguousarray(blank_lp, np.float32).reshape(-1)
+    st = np.zeros(5, np.int32) if state is None else np.ascontiguousarray(state, np.int32).copy()
+    assert st.shape == (5,)
+    c = _endpoint_config(cfg)
+    rc = load().rnnt_endpoint_scan_host(_np_ptr(lp) if lp.size else None, lp.size, ctypes.byref(c), _np_ptr(st))
+    if rc != 0:
+        raise RnntError(f"rnnt_endpoint_scan_host: bad config or argument (status {rc})", rc)
+    return st
 
 
 def wave_stage_host(carry, samples_so_far, new, final, n_fft=1024):
@@ -874,6 +910,34 @@ class RnntEngine:
         """rnnt_stream_keep_frames: from now on the pool calls that encode `slot` append its encoder outputs to the slot's history
         (valid on a slot that has not advanced since it was opened); keep=False clears the flag and the length."""
         self._chk(self.lib.rnnt_stream_keep_frames(self.ctx, slot, 1 if keep else 0, stream), "rnnt_stream_keep_frames")
+
+    # ---- endpoint detection per slot of the stream pool --------------------------------------------------
+    def stream_endpoint(self, slot, cfg, stream=None):
+        """rnnt_stream_endpoint: from now on the pool calls that encode `slot` advance its endpoint state (valid on a slot that has
+        not advanced since it was opened); cfg: see _endpoint_config, None turns it off."""
+        c = None if cfg is None else ctypes.byref(_endpoint_config(cfg))
+        self._chk(self.lib.rnnt_stream_endpoint(self.ctx, slot, c, stream), "rnnt_stream_endpoint")
+
+    def pool_endpoint_frames(self, slots, enc_ptr, t, stream=None):
+        """rnnt_pool_endpoint_frames: advance the endpoint states of the listed slots by t encoder frames [len(slots), t, 256] on the
+        device; one launch, no synchronisation."""
+        a = np.ascontiguousarray(slots, np.int32)
+        assert a.ndim == 1
+        self._chk(self.lib.rnnt_pool_endpoint_frames(self.ctx, a.size, _np_ptr(a), enc_ptr, t, stream), "rnnt_pool_endpoint_frames")
+
+    def pool_endpoints(self, slots, stream=None):
+        """rnnt_pool_get_endpoints: int32 [len(slots), 5] = frames, trailing, speech, rule, at of the listed slots; one download."""
+        a = np.ascontiguousarray(slots, np.int32)
+        assert a.ndim == 1
+        out = np.zeros((a.size, 5), np.int32)
+        self._chk(self.lib.rnnt_pool_get_endpoints(self.ctx, a.size, _np_ptr(a), _np_ptr(out), stream), "rnnt_pool_get_endpoints")
+        return out
+
+    def ctc_blank_logprob(self, enc_ptr, rows, out_ptr, stream=None):
+        """rnnt_ctc_blank_logprob: out [rows] = log_softmax(ctc_lo(enc))[blank] for enc [rows, 256] on the device."""
+        self._chk(self.lib.rnnt_ctc_blank_logprob(self.ctx, enc_ptr, rows, out_ptr, stream), "rnnt_ctc_blank_logprob")
+
+    endpoint_scan_host = staticmethod(endpoint_scan_host)
 
     def stream_frames_len(self, slot):
         """frames in the slot's history (host only); RnntError(ERR_STATE) on a slot that keeps none"""

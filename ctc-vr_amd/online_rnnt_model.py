@@ -8,6 +8,7 @@ independent streams in one context, and `StreamPool`, slots of one context that 
 independently (callers that connect and hang up whenever they like); each stream's result equals the
 reference's B=1 result.
 """
+from collections import namedtuple
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
@@ -1069,6 +1070,30 @@ def wave_plan(queue, samples, fifo, chunk_frames, n_fft=1024):
     return (slots, [counts[s] for s in slots], [finals[s] for s in slots], frames), chunks, new_samples, new_fifo
 
 
+FRAME_MS = 40    # one encoder frame of the pool (OnlineRNNTModel.FRAME_SECONDS), in the integer milliseconds EndpointConfig divides by
+
+# what StreamPool.endpoints() returns per slot: the rule that fired (0: none yet; it is sticky) and the frame count at which it did,
+# then the running counters -- encoder frames so far, the trailing blank run, the non-blank frames
+Endpoint = namedtuple("Endpoint", ["rule", "at_frame", "frames", "trailing", "speech"])
+
+
+class EndpointConfig:
+    """When is the caller done: the rule of rnnt_stream_endpoint (include/rnnt_hip.h) in milliseconds, WeNet's runtime endpointer's
+    shape and defaults.  A frame is blank when the CTC head's blank posterior exceeds blank_threshold; rule 1 fires after rule1_ms of
+    trailing blank with nothing said yet, rule 2 after rule2_ms of trailing blank once min_speech_frames non-blank frames were seen,
+    rule 3 at rule3_ms of audio; 0 switches a rule off.  Milliseconds become encoder frames of 40 ms by floor division: 125, 25 and
+    500 frames by default."""
+
+    def __init__(self, blank_threshold: float = 0.8, rule1_ms: int = 5000, rule2_ms: int = 1000, rule3_ms: int = 20000, min_speech_frames: int = 1):
+        assert OnlineRNNTModel.FRAME_SECONDS * 1000 == FRAME_MS
+        self.blank_threshold = float(blank_threshold)
+        self.min_speech_frames = int(min_speech_frames)
+        self.rule1_trailing, self.rule2_trailing, self.rule3_frames = (int(ms) // FRAME_MS for ms in (rule1_ms, rule2_ms, rule3_ms))
+
+    def as_tuple(self):
+        return (self.blank_threshold, self.min_speech_frames, self.rule1_trailing, self.rule2_trailing, self.rule3_frames)
+
+
 class StreamPool:
     """A context's slots, each with its own life (not in the reference, which is B=1): open() a slot when a caller connects, feed()
     it a chunk whenever the caller has one, step() to advance whatever subset of slots has chunks queued -- each at its own cache
@@ -1093,7 +1118,10 @@ class StreamPool:
     prefix beam search (rnnt_prefix_beam_decode's), carried across chunks on the device by rnnt_pool_chunk_prefix (with
     prefix_context=ContextBias: biased by hot words, rnnt_pool_chunk_prefix_ctx; the pool's one graph serves both searches); prefix_hyps(slot)
     reads the hypotheses as they stand, close(slot) returns the final ones -- those of the one-call search over the utterance's
-    frames -- and rescore() takes such a slot as the first pass of the reference's own two-pass recipe."""
+    frames -- and rescore() takes such a slot as the first pass of the reference's own two-pass recipe.
+    When is the caller done: open(..., endpoint=EndpointConfig(...)) makes the library watch the slot's CTC blank posterior inside the
+    pool calls that encode it (any slot kind, one extra launch per call); endpoints() reads rule and counters of all such slots with
+    one download."""
 
     def __init__(self, state_dict, n_slots: int, vocab_size: int = 412, blank_id: int = 5, max_chunk_frames: int = 64,
                  max_cache_frames: int = 512, max_tokens: int = 4096, device: int = 0, numerics=None, packed=None, engine=None,
@@ -1101,7 +1129,8 @@ class StreamPool:
         """state_dict / packed: as StreamingBatch.  engine: an object with reset / stream_open / pool_chunk / stream_tokens (and
         pool_chunk_beam / stream_beam for beam slots, pool_chunk_ctc_prefix / stream_ctc_prefix / context_set for CTC prefix slots,
         pool_chunk_prefix / stream_prefix for transducer prefix slots,
-        stream_keep_frames / stream_frames / pool_rescore / transducer_align for slots that keep their frames)
+        stream_keep_frames / stream_frames / pool_rescore / transducer_align for slots that keep their frames,
+        stream_endpoint / pool_endpoints for slots opened with an EndpointConfig)
         to drive instead of a new RnntEngine (a recording fake in the CPU tests).
         max_beam: the largest beam_size open() may be given (0: greedy only).
         sample_rate / n_fft / chunk_frames: the front-end of feed_wave and the chunk length its frames are fed in (the engine also
@@ -1133,6 +1162,7 @@ class StreamPool:
         self._ntok: Dict[int, int] = {}
         self._beam: Dict[int, int] = {}                 # beam size of the open slots (0 = greedy)
         self._keep: Dict[int, bool] = {}                # keep_frames of the slot's last open()
+        self._endpoint: Dict[int, EndpointConfig] = {}  # the open slots that detect their endpoint
         self._ctc: Dict[int, Tuple[int, Optional[ContextBias]]] = {}   # (beam, context) of the open CTC prefix slots
         self._prefix: Dict[int, Tuple[int, float, float]] = {}   # (beam, ctc_weight, transducer_weight) of the open transducer prefix slots
         self._prefix_ctx: Dict[int, ContextBias] = {}   # the context of the biased ones among them
@@ -1149,7 +1179,8 @@ class StreamPool:
         return _stream_ptr() if (t is None and torch.cuda.is_available()) or (t is not None and t.is_cuda) else None
 
     def open(self, beam_size: int = 0, ctc_prefix_beam: int = 0, context: Optional[ContextBias] = None, keep_frames: bool = False,
-             prefix_beam: int = 0, ctc_weight: float = 0.3, transducer_weight: float = 0.7, prefix_context: Optional[ContextBias] = None) -> int:
+             prefix_beam: int = 0, ctc_weight: float = 0.3, transducer_weight: float = 0.7, prefix_context: Optional[ContextBias] = None,
+             endpoint: Optional[EndpointConfig] = None) -> int:
         """The lowest free slot, reset for a new utterance (reset_streaming_cache for that slot alone).  beam_size > 0: the slot's
         utterance is beam-searched with that beam (its hypotheses start as the one empty hypothesis); raises RnntError at once
         when this pool cannot do it.  ctc_prefix_beam > 0 (not together with beam_size): the slot's utterance runs the CTC prefix beam
@@ -1161,7 +1192,9 @@ class StreamPool:
         prefix_beam > 0 (not together with beam_size or ctc_prefix_beam, and without context): the slot's utterance runs the
         transducer prefix beam search with that beam and the fusion weights ctc_weight / transducer_weight (>= 0, not both 0), biased
         by prefix_context when given (`context` belongs to ctc_prefix_beam).  The one graph of the pool serves both kinds: a graph other
-        than the current one is refused while any biased slot of either kind is open."""
+        than the current one is refused while any biased slot of either kind is open.
+        endpoint: the slot (of any kind) detects its endpoint under that config (rnnt_stream_endpoint); endpoints() reads the result.
+        A config the library refuses takes no slot."""
         biased_open = any(c is not None for _, c in self._ctc.values()) or bool(self._prefix_ctx)
         if prefix_context is not None:
             if not prefix_beam:
@@ -1199,6 +1232,9 @@ class StreamPool:
         self.engine.stream_open(slot, self._stream(None))
         if keep_frames:
             self.engine.stream_keep_frames(slot, True, self._stream(None))
+        if endpoint is not None:
+            self.engine.stream_endpoint(slot, endpoint.as_tuple(), self._stream(None))
+            self._endpoint[slot] = endpoint
         self._free.pop(0)
         self._keep[slot] = bool(keep_frames)
         if ctc_prefix_beam:
@@ -1356,6 +1392,21 @@ class StreamPool:
         hyps = self.engine.stream_prefix_ctx(slot, final, stream=self._stream(None))
         return hyps if with_context_scores else [(tok, score) for tok, score, _ in hyps]
 
+    def endpoints(self, slots: Optional[List[int]] = None) -> Dict[int, Endpoint]:
+        """{slot: Endpoint(rule, at_frame, frames, trailing, speech)} of the open slots that detect their endpoint, or of the listed
+        ones (each must be such a slot), after the chunks stepped so far: ONE engine call (one download) for all of them, none when
+        there is nothing to read.  Chunks still queued are not in it: step() first.  Reading changes nothing."""
+        if slots is None:
+            slots = sorted(self._endpoint)
+        slots = [int(x) for x in slots]
+        for slot in slots:
+            if slot not in self._endpoint:
+                raise RnntError(f"slot {slot} is not an open slot that detects its endpoint (open(endpoint=EndpointConfig(...)))", ERR_STATE)
+        if not slots:
+            return {}
+        st = self.engine.pool_endpoints(slots, self._stream(None))
+        return {slot: Endpoint(int(r[3]), int(r[4]), int(r[0]), int(r[1]), int(r[2])) for slot, r in zip(slots, st)}
+
     def _require_kept(self, slot: int):
         if slot not in self._offset or not self._keep.get(slot, False):
             raise RnntError(f"slot {slot} is not an open slot that keeps its frames (open(keep_frames=True))", ERR_STATE)
@@ -1415,6 +1466,7 @@ class StreamPool:
             self._carry = self.step()                   # the other slots' increments are handed out by the next step()
         self._carry.pop(slot, None)
         self._forget_wave(slot)
+        self._endpoint.pop(slot, None)                  # the library clears its flag when the slot is opened again
         if slot in self._prefix:
             res = self.prefix_hyps(slot, final=True)
             del self._prefix[slot]

@@ -642,6 +642,56 @@ int rnnt_stream_get_frames(rnnt_ctx* ctx, int32_t slot, int32_t from, int32_t ca
 int rnnt_pool_rescore(rnnt_ctx* ctx, int32_t n, const int32_t* slots_host, const int32_t* n_hyp_host, const int32_t* hyp_lens_host,
                       const int32_t* hyp_tokens_host, int32_t N, int32_t Umax, double* nll_host, void* stream);
 
+/* -- when is the caller done: endpoint detection per slot of the stream pool ------------------------------------------------------------ */
+/* The rule has the shape of WeNet's runtime endpointer, on the CTC head's blank posterior per encoder frame.  Per-slot state, five
+ * int32: frames, trailing, speech, rule, at -- all 0 after open / reset.  For every new encoder frame, in order, with lp = that
+ * frame's blank log-posterior log_softmax(ctc_lo(enc))[blank_id] (f32 in every numerics mode) and
+ * log_thr = (float)log((double)blank_threshold), computed once where the config is accepted:
+ *     frames += 1
+ *     if (lp > log_thr) trailing += 1; else { trailing = 0; speech += 1; }          -- a NaN counts as speech
+ *     if (rule == 0) {
+ *         r = (R1 > 0 && speech <  S && trailing >= R1) ? 1
+ *           : (R2 > 0 && speech >= S && trailing >= R2) ? 2
+ *           : (R3 > 0 && frames >= R3)                  ? 3 : 0;
+ *         if (r) { rule = r; at = frames; }
+ *     }
+ * Rules are evaluated per frame, not per call; the first to fire is sticky and the counters run on, so a slot's state depends only on
+ * its frames, never on how they were split into calls.  With all three rules off the slot only counts.  "Something was said" is the
+ * CTC speech count, not "the decoder has tokens": one rule for every slot kind, and the device needs nothing from the decoders.  A
+ * caller who wants the decoder-based form applies it on the host from the returned frames / trailing and its own tokens. */
+typedef struct {
+    float   blank_threshold;    /* in (0, 1): a frame is blank iff its CTC blank posterior exceeds it */
+    int32_t min_speech_frames;  /* S >= 0: "something was said" once speech >= S                       */
+    int32_t rule1_trailing;     /* R1: nothing said yet and trailing >= R1; 0 = rule off               */
+    int32_t rule2_trailing;     /* R2: something said and trailing >= R2;   0 = rule off               */
+    int32_t rule3_frames;       /* R3: frames >= R3;                        0 = rule off               */
+} rnnt_endpoint_config;         /* 20 bytes */
+/* cfg != NULL: from now on every pool call that encodes `slot` (rnnt_pool_chunk in either mode, rnnt_pool_chunk_beam,
+ * rnnt_pool_chunk_ctc_prefix, rnnt_pool_chunk_prefix[_ctx]) advances the slot's state by its t' new frames: ONE extra launch per
+ * pool call (pool_endpoint, after the history append), and only when a listed slot has endpointing on.  Valid on a slot that has not
+ * advanced since it was opened or reset (RNNT_ERR_STATE otherwise); the state starts at zero and the context enters pool mode.
+ * RNNT_ERR_STATE without finalized weights or without ctc_head.ctc_lo.*; RNNT_ERR_ARG for a threshold outside (0, 1), a negative
+ * count or a slot out of range.  The config and state tables [max_streams] are reserved on the first use and counted by
+ * rnnt_live_device_bytes.  rnnt_stream_open clears its slot's flag, rnnt_streams_reset all: a slot detects nothing unless asked
+ * again.  cfg == NULL: endpointing off for the slot (any time).  Does not synchronise. */
+int rnnt_stream_endpoint(rnnt_ctx* ctx, int32_t slot, const rnnt_endpoint_config* cfg, void* stream);
+/* The seam: the states of the n_active listed slots (distinct, endpointing on) advance by t >= 1 caller-held encoder frames
+ * enc_dev [n_active][t][256] (16-byte aligned), row i belonging to slots_host[i].  One launch, no synchronisation.  RNNT_ERR_ARG:
+ * null pointer, n_active outside [1, max_streams], t < 1, a duplicated or out-of-range slot; RNNT_ERR_STATE: a listed slot with
+ * endpointing off.  Every refusal happens before the launch and changes nothing. */
+int rnnt_pool_endpoint_frames(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, const float* enc_dev, int32_t t, void* stream);
+/* state_host [n][5] = frames, trailing, speech, rule, at of each listed slot (distinct, endpointing on: RNNT_ERR_STATE otherwise).
+ * ONE device-to-host copy of the state table for the whole call; the rows are picked on the host.  Synchronises. */
+int rnnt_pool_get_endpoints(rnnt_ctx* ctx, int32_t n, const int32_t* slots_host, int32_t* state_host, void* stream);
+/* out_dev [rows] = log_softmax(ctc_lo(enc))[blank_id] for enc_dev [rows, 256] (16-byte aligned): the stateless kernel under the
+ * above.  f32 FMA arithmetic in every numerics mode, online (max, sum) over the vocabulary, nothing of size rows x vocab written.
+ * Preconditions as rnnt_ctc_logprobs.  Does not synchronise. */
+int rnnt_ctc_blank_logprob(rnnt_ctx* ctx, const float* enc_dev, int32_t rows, float* out_dev, void* stream);
+/* The rule as a pure C++ function (no context, no GPU), the very function the kernel runs: state [5] advances by the t >= 0
+ * log-posteriors blank_lp [t].  RNNT_ERR_ARG on a null pointer (blank_lp may be NULL when t = 0), t < 0 or a config
+ * rnnt_stream_endpoint refuses. */
+int rnnt_endpoint_scan_host(const float* blank_lp, int32_t t, const rnnt_endpoint_config* cfg, int32_t* state);
+
 /* -- forced alignment: WHERE in the frames each token of a given transcript lies (the reference's WeNet layer: force_align,
  * gen_ctc_peak_time, gen_timestamps_from_peak, DecodeResult.times; wenet/utils/ctc_utils.py) ------------------------------------ */
 /* The best monotonic alignment of each row's transcript: the max-plus (Viterbi) twin of rnnt_transducer_nll's recursion in f64,
