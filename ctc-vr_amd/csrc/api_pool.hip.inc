@@ -39,7 +39,7 @@ int pool_beam_alloc(rnnt_ctx* ctx, hipStream_t s) {
 // from here on every slot has its own position (the lock-step entry points refuse until rnnt_streams_reset)
 void pool_enter(rnnt_ctx* ctx) {
     if (ctx->pool_mode) return;
-    for (PoolSlot& q : ctx->slot) q.pos = ctx->pos;
+    for (PoolSlot& q : ctx->slot) { q.pos = ctx->pos; q.seg.frames = ctx->pos.conv_pos; }   // lock step: conv_pos counts the frames since the reset
     ctx->pool_mode = true;
 }
 
@@ -108,6 +108,7 @@ int rnnt_stream_open(rnnt_ctx* ctx, int32_t slot, void* stream) {
     if ((rc = pool_slot_reset(ctx, s, slot, 1))) return rc;
     pool_enter(ctx);
     ctx->slot[slot].pos = SlotPos{0, 0, 0};
+    ctx->slot[slot].seg = SegSlot{};
     return RNNT_OK;
 }
 
@@ -218,7 +219,10 @@ int pool_chunk_run(rnnt_ctx* ctx, const char* fn, int32_t n_active, const int32_
         }
         if ((rc = launch_gemm(ctx, s, &g, 1, TAG_ENC_PROJ))) return rc;
     }
-    for (int i = 0; i < n; ++i) ctx->slot[rows[i].slot].pos.advance(rows[i].T2, tq, required_host[i]);
+    for (int i = 0; i < n; ++i) {
+        ctx->slot[rows[i].slot].pos.advance(rows[i].T2, tq, required_host[i]);
+        ctx->slot[rows[i].slot].seg.frames += tq;
+    }
     if (frames_out) *frames_out = tq;
     if (mode == POOL_BEAM) {
         // ---- the per-frame loop of _decode_chunk_beam_search over frames [0, t') of exactly the active slots: launches only -------------

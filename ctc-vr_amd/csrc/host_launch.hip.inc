@@ -820,6 +820,7 @@ int pool_endpoint_rows(rnnt_ctx* ctx, hipStream_t s, int n, const int32_t* slots
 // disjoint buffers, so this one order serves both
 int pool_slot_reset(rnnt_ctx* ctx, hipStream_t s, int slot0, int n) {
     int rc;
+    for (int b = slot0; b < slot0 + n; ++b) ctx->slot[b].seg = SegSlot{};
     if ((rc = pool_beam_reset(ctx, s, slot0, n)) || (rc = pool_ctc_reset(ctx, s, slot0, n)) || (rc = pool_prefix_reset(ctx, s, slot0, n))) return rc;
     pool_wave_reset(ctx, slot0, n);
     if ((rc = pool_endpoint_reset(ctx, s, slot0, n))) return rc;

@@ -106,10 +106,13 @@ using PinnedBuf = DevBuf<T, true>;
 // advancing call fixed until the next reset -- beam (0: fresh), the two weights (0 for the CTC search), use_context, the graph
 // generation (rnnt_ctx::cg_gen).  WvSlot, the front-end: samples received and frames emitted since the reset, the (sample_rate,
 // n_fft) its first push fixed (n_fft == 0: fresh), whether its utterance has ended.  HsSlot, the frame history: flag and length.
-// ep: endpoint detection is on (the config and the counters live on the device, api_pool_endpoint.hip.inc).
+// ep: endpoint detection is on (the config and the counters live on the device, api_pool_endpoint.hip.inc).  SegSlot, the segment
+// record (api_pool_segment.hip.inc): segments started since the slot was opened, the encoder frames it had encoded when the current
+// one began, and those encoded since it was opened (the encoder position does not say: a fresh segment restarts it).
 struct SearchSlot { int frames_done, beam; float cw, tw; int use_context; int64_t gen; };
 struct WvSlot { int samples, frames, rate, nfft, finished; };
 struct HsSlot { int keep, len; };
+struct SegSlot { int index, start, frames; };
 // One record per slot (rnnt_ctx::slot, sized to max_streams by rnnt_create; pool_slot_reset makes slots fresh): the position, the
 // current buffer set of the beam and of the transducer prefix search, a host upper bound of the beam's longest hypothesis.
 struct PoolSlot {
@@ -119,6 +122,7 @@ struct PoolSlot {
     WvSlot wave{};
     HsSlot hist{};
     int ep = 0;
+    SegSlot seg{};
 };
 // The table of one pool call: ints filled in pinned memory and sent by ONE async copy; the event says the copy has left the pinned
 // buffer, so the next call may fill it again (calltab_alloc / calltab_fill / calltab_send, host_launch.hip.inc).
@@ -329,6 +333,7 @@ struct rnnt_ctx {
     DevBuf<int> ep_state;
     CallTab ep_tab;
     PinnedBuf<int> ep_host;
+    CallTab seg_tab;                           // the slot list of one rnnt_pool_segment call, [max_streams]
     hipStream_t cap_stream = nullptr;          // stream-capture scratch stream
     struct DecGraph { int n_streams, k; hipGraphExec_t exec; };
     std::vector<DecGraph> dec_graphs;          // K greedy steps captured once per (n_streams, K)
@@ -367,6 +372,7 @@ extern "C" {
 #include "api_pool.hip.inc"
 #include "api_pool_hist.hip.inc"
 #include "api_pool_endpoint.hip.inc"
+#include "api_pool_segment.hip.inc"
 #include "api_pool_wave.hip.inc"
 #include "api_prefix.hip.inc"
 #include "api_ctc_prefix.hip.inc"

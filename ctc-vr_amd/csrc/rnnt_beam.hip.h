@@ -422,13 +422,14 @@ __global__ __launch_bounds__(BM_NT) void beam_merge_pool(BeamMergeP p, BeamPoolP
 
 // rnnt_stream_open / rnnt_streams_reset for the per-slot beam state of slots [slot0, slot0 + gridDim.x): one empty hypothesis with
 // score 0.0, the initial hash and the zero LSTM state (online_rnnt_model.py:407-415) in buffer set 0 (the host's index goes to 0
-// with it).  Touches no other slot.
-__global__ __launch_bounds__(256) void beam_slot_reset(BeamPoolP q, int slot0, int state_slots) {
-    const int slot = slot0 + blockIdx.x, r0 = slot * q.W;
+// with it).  Touches no other slot.  beam_slot_start: the same for one slot, by a workgroup of 256.
+__device__ __forceinline__ void beam_slot_start(const BeamPoolP& q, int slot, int state_slots) {
+    const int r0 = slot * q.W;
     for (int e = threadIdx.x; e < 512; e += 256) q.pool[0][(long long)r0 * state_slots * 512 + e] = 0.f;
     if (threadIdx.x < q.W) { q.len[r0 + threadIdx.x] = 0; q.sc[r0 + threadIdx.x] = 0.0; q.hs[r0 + threadIdx.x] = BEAM_HASH0; }
     if (threadIdx.x == 0) q.nh[slot] = 1;
 }
+__global__ __launch_bounds__(256) void beam_slot_reset(BeamPoolP q, int slot0, int state_slots) { beam_slot_start(q, slot0 + blockIdx.x, state_slots); }
 
 // End of rnnt_beam_decode: fixed-slot row r = b * width + i (i < nh[b]) -> compacted row (hypotheses of streams < b) + i,
 // LSTM state into slot 0 of the other pool, token list / length / score into the other token buffers.

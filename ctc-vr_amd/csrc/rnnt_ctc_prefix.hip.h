@@ -402,15 +402,20 @@ __global__ __launch_bounds__(CP_NT) void ctc_prefix_pack(CtcPrefixPackP p) {
     cp_pack(H, nh, p.pa, p.ta, p.fin_nscore, p.o, 0, p.beam, p.lcap);
 }
 
-// the start hypothesis in the records of slots [slot0, slot0 + gridDim.x); every other entry of a record is zero
-__global__ __launch_bounds__(64) void ctc_prefix_slot_reset(CpSlotState* state, int slot0) {
-    __shared__ CpSlotState z;
+// the start hypothesis in the record *st, every other entry of it zero; z: an LDS record of the workgroup (>= CP_MAX_BEAM threads,
+// all of them here)
+__device__ __forceinline__ void ctc_prefix_slot_start(CpSlotState* st, CpSlotState& z) {
     const int tid = threadIdx.x;
-    for (int q = tid; q < (int)(sizeof(CpSlotState) / sizeof(int)); q += 64) reinterpret_cast<int*>(&z)[q] = 0;
+    for (int q = tid; q < (int)(sizeof(CpSlotState) / sizeof(int)); q += blockDim.x) reinterpret_cast<int*>(&z)[q] = 0;
     __syncthreads();
     if (tid == 0) { cp_put_start(z.h); z.nh = 1; }
     __syncthreads();
-    CpSlotState* st = state + slot0 + blockIdx.x;
     if (tid < CP_MAX_BEAM) cp_hyps_copy(st->h, z.h, tid);
     if (tid == 0) { st->nh = z.nh; st->pad = 0; }
+}
+
+// the start hypothesis in the records of slots [slot0, slot0 + gridDim.x)
+__global__ __launch_bounds__(64) void ctc_prefix_slot_reset(CpSlotState* state, int slot0) {
+    __shared__ CpSlotState z;
+    ctc_prefix_slot_start(state + slot0 + blockIdx.x, z);
 }

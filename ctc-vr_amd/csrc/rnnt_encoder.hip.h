@@ -510,20 +510,31 @@ __global__ void conv_ring_init(float* __restrict__ g, float* __restrict__ xring,
 // rnnt_stream_open: the state rnnt_streams_reset gives every stream, for ONE slot.  Rings of all 12 layers (post-GLU ring <-
 // GLU(b_pw1), conv-input ring <- 0), both LSTM state buffers <- 0, committed buffer 0, last token = blank, token count 0, frame
 // index 0.  The K/V rows need no clearing: the slot's cache length is 0 on the host.  Touches no other slot's storage.
-__global__ void stream_slot_reset(float* __restrict__ g, float* __restrict__ xring, const float* __restrict__ glu0 /*[L][256]*/, int B, int cap, int slot,
-                                  float* __restrict__ h, float* __restrict__ c, int* sel, unsigned long long* key, int* fidx, int* nsym, int* count, int* tok, int blank) {
+// The two halves as device functions over the elements first, first + stride, ... (pool_segment_reset runs them too): the rings
+// [L][B][cap][256] of one slot, and the greedy decoder's state of one slot (the thread with first == 0 writes the scalars).
+__device__ __forceinline__ void ring_slot_fill(float* __restrict__ g, float* __restrict__ xring, const float* __restrict__ glu0 /*[L][256]*/, int B, int cap,
+                                               int slot, long long first, long long stride) {
     const long long per = (long long)cap * RNNT_D, n = (long long)RNNT_L * per;
-    for (long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x; id < n; id += (long long)gridDim.x * blockDim.x) {
+    for (long long id = first; id < n; id += stride) {
         const int l = (int)(id / per);
         const long long off = ((long long)l * B + slot) * per + (id - (long long)l * per);
         g[off] = glu0[l * RNNT_D + (int)(id & 255)];
         xring[off] = 0.f;
-        if (id < 2 * RNNT_D) {   // [2][B][256]: buffer id / 256, unit id % 256
-            const long long so = (id >> 8) * (long long)B * RNNT_D + (long long)slot * RNNT_D + (id & 255);
-            h[so] = 0.f; c[so] = 0.f;
-        }
-        if (id == 0) { sel[slot] = 0; key[slot] = 0ull; fidx[slot] = 0; nsym[slot] = 0; count[slot] = 0; tok[slot] = blank; }
     }
+}
+__device__ __forceinline__ void greedy_slot_start(float* __restrict__ h, float* __restrict__ c, int* sel, unsigned long long* key, int* fidx, int* nsym,
+                                                  int* count, int* tok, int B, int slot, int blank, long long first, long long stride) {
+    for (long long id = first; id < 2 * RNNT_D; id += stride) {   // [2][B][256]: buffer id / 256, unit id % 256
+        const long long so = (id >> 8) * (long long)B * RNNT_D + (long long)slot * RNNT_D + (id & 255);
+        h[so] = 0.f; c[so] = 0.f;
+    }
+    if (first == 0) { sel[slot] = 0; key[slot] = 0ull; fidx[slot] = 0; nsym[slot] = 0; count[slot] = 0; tok[slot] = blank; }
+}
+__global__ void stream_slot_reset(float* __restrict__ g, float* __restrict__ xring, const float* __restrict__ glu0 /*[L][256]*/, int B, int cap, int slot,
+                                  float* __restrict__ h, float* __restrict__ c, int* sel, unsigned long long* key, int* fidx, int* nsym, int* count, int* tok, int blank) {
+    const long long first = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
+    ring_slot_fill(g, xring, glu0, B, cap, slot, first, stride);
+    greedy_slot_start(h, c, sel, key, fidx, nsym, count, tok, B, slot, blank, first, stride);
 }
 // rnnt_pool_chunk with greedy == 0: the after_norm rows of the call (compact, [n_active * tq][256]) into frames [0, tq) of their
 // slots' rows of the encoder-frame buffer, for rnnt_get_enc_frames.

@@ -426,9 +426,9 @@ __global__ __launch_bounds__(PB_NT) void prefix_merge_pool(PrefixMergeP p, Prefi
 __global__ __launch_bounds__(PB_NT) void prefix_merge_pool_ctx(PrefixMergeP p, PrefixPoolP q, CpGraph g) { prefix_merge_pool_rows<true>(p, q, g); }
 
 // The reset of slots [slot0, slot0 + gridDim.x): prefix_init's start (hypothesis [blank], score 0, zero state) in set 0; the host's
-// set index goes to 0 with it.  Touches no other slot.
-__global__ __launch_bounds__(256) void prefix_init_pool(PrefixPoolP q, int slot0, int lcap, int blank) {
-    const int slot = slot0 + blockIdx.x, r = slot * PB_MAX_BEAM;
+// set index goes to 0 with it.  Touches no other slot.  prefix_slot_start: the same for one slot, by a workgroup of 256.
+__device__ __forceinline__ void prefix_slot_start(const PrefixPoolP& q, int slot, int lcap, int blank) {
+    const int r = slot * PB_MAX_BEAM;
     for (int e = threadIdx.x; e < 512; e += 256) q.pool[0][(long long)r * 1024 + e] = 0.f;
     if (threadIdx.x == 0) {
         q.tk[0][(long long)r * lcap] = blank;
@@ -440,6 +440,7 @@ __global__ __launch_bounds__(256) void prefix_init_pool(PrefixPoolP q, int slot0
         q.nh[slot] = 1;
     }
 }
+__global__ __launch_bounds__(256) void prefix_init_pool(PrefixPoolP q, int slot0, int lcap, int blank) { prefix_slot_start(q, slot0 + blockIdx.x, lcap, blank); }
 
 // One slot's set `cur` into ONE block for one download (rnnt_stream_get_prefix), one workgroup per row i < beam: scores f64 [beam] |
 // context scores f64 [beam] | n_hyp | lengths [beam] | tokens [beam][ocap] | h [beam][256] | c [beam][256] (states only if

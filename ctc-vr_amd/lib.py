@@ -100,6 +100,8 @@ SIGNATURES = {
     "rnnt_pool_get_endpoints": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp]),
     "rnnt_ctc_blank_logprob": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp]),
     "rnnt_endpoint_scan_host": (c_i32, [c_vp, c_i32, ctypes.POINTER(RnntEndpointConfig), c_vp]),
+    "rnnt_pool_segment": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp]),
+    "rnnt_stream_get_segment": (c_i32, [c_vp, c_i32, c_i32p, c_i32p]),
     "rnnt_transducer_align": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rnnt_transducer_align_pick": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "rnnt_ctc_align": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
@@ -938,6 +940,20 @@ class RnntEngine:
         self._chk(self.lib.rnnt_ctc_blank_logprob(self.ctx, enc_ptr, rows, out_ptr, stream), "rnnt_ctc_blank_logprob")
 
     endpoint_scan_host = staticmethod(endpoint_scan_host)
+
+    # ---- segments: the next utterance in a slot that stays open -------------------------------------------
+    def pool_segment(self, slots, keep_encoder=True, stream=None):
+        """rnnt_pool_segment: a new segment in the listed slots -- their decoders, endpoint counters and history length start over;
+        keep_encoder=False restarts their encoder too (the next chunk's offset is 0).  One copy, one launch, no synchronisation."""
+        a = np.ascontiguousarray(slots, np.int32)
+        assert a.ndim == 1
+        self._chk(self.lib.rnnt_pool_segment(self.ctx, a.size, _np_ptr(a), 1 if keep_encoder else 0, stream), "rnnt_pool_segment")
+
+    def stream_segment(self, slot):
+        """rnnt_stream_get_segment: (index, start_frame) of the slot's current segment (host only)."""
+        index, start = c_i32(0), c_i32(0)
+        self._chk(self.lib.rnnt_stream_get_segment(self.ctx, slot, ctypes.byref(index), ctypes.byref(start)), "rnnt_stream_get_segment")
+        return index.value, start.value
 
     def stream_frames_len(self, slot):
         """frames in the slot's history (host only); RnntError(ERR_STATE) on a slot that keeps none"""

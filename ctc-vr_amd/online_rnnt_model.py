@@ -1077,6 +1077,12 @@ FRAME_MS = 40    # one encoder frame of the pool (OnlineRNNTModel.FRAME_SECONDS)
 Endpoint = namedtuple("Endpoint", ["rule", "at_frame", "frames", "trailing", "speech"])
 
 
+# One finished utterance of a slot that stays open (StreamPool.next_segment / segments): its number in the slot's session, the encoder
+# frames the slot had encoded before it and in it, what close() would have returned for it, and the endpoint state it ended with
+# (None on a slot without an EndpointConfig).  Frame indices inside result / endpoint are relative to the segment: add start_frame.
+Segment = namedtuple("Segment", ["index", "start_frame", "frames", "result", "endpoint"])
+
+
 class EndpointConfig:
     """When is the caller done: the rule of rnnt_stream_endpoint (include/rnnt_hip.h) in milliseconds, WeNet's runtime endpointer's
     shape and defaults.  A frame is blank when the CTC head's blank posterior exceeds blank_threshold; rule 1 fires after rule1_ms of
@@ -1121,7 +1127,12 @@ class StreamPool:
     frames -- and rescore() takes such a slot as the first pass of the reference's own two-pass recipe.
     When is the caller done: open(..., endpoint=EndpointConfig(...)) makes the library watch the slot's CTC blank posterior inside the
     pool calls that encode it (any slot kind, one extra launch per call); endpoints() reads rule and counters of all such slots with
-    one download."""
+    one download.
+    Segments: next_segment(slot, keep_encoder=True) ends the slot's utterance and starts the next one in the same slot -- its result is
+    returned as a Segment, its decoders start over (rnnt_pool_segment), its audio stream and its configuration stay.  keep_encoder=True
+    is WeNet's continuous decoding (the encoder's caches run on), False restarts the encoder too, which is how a session outlives
+    max_cache_frames.  open(..., endpoint=, on_endpoint="keep" | "fresh") lets step() do it whenever the slot's rule has fired;
+    segments(slot) hands out what it finished."""
 
     def __init__(self, state_dict, n_slots: int, vocab_size: int = 412, blank_id: int = 5, max_chunk_frames: int = 64,
                  max_cache_frames: int = 512, max_tokens: int = 4096, device: int = 0, numerics=None, packed=None, engine=None,
@@ -1130,7 +1141,8 @@ class StreamPool:
         pool_chunk_beam / stream_beam for beam slots, pool_chunk_ctc_prefix / stream_ctc_prefix / context_set for CTC prefix slots,
         pool_chunk_prefix / stream_prefix for transducer prefix slots,
         stream_keep_frames / stream_frames / pool_rescore / transducer_align for slots that keep their frames,
-        stream_endpoint / pool_endpoints for slots opened with an EndpointConfig)
+        stream_endpoint / pool_endpoints for slots opened with an EndpointConfig,
+        pool_segment / stream_segment for next_segment and on_endpoint)
         to drive instead of a new RnntEngine (a recording fake in the CPU tests).
         max_beam: the largest beam_size open() may be given (0: greedy only).
         sample_rate / n_fft / chunk_frames: the front-end of feed_wave and the chunk length its frames are fed in (the engine also
@@ -1163,6 +1175,9 @@ class StreamPool:
         self._beam: Dict[int, int] = {}                 # beam size of the open slots (0 = greedy)
         self._keep: Dict[int, bool] = {}                # keep_frames of the slot's last open()
         self._endpoint: Dict[int, EndpointConfig] = {}  # the open slots that detect their endpoint
+        self._on_endpoint: Dict[int, str] = {}          # "keep" / "fresh": the open slots step() segments when their rule has fired
+        self._segments: Dict[int, List[Segment]] = {}   # what step() finished for them, until segments(slot) takes it
+        self._seg: Dict[int, Tuple[int, int]] = {}      # (index, start_frame) of the open slots' current segment
         self._ctc: Dict[int, Tuple[int, Optional[ContextBias]]] = {}   # (beam, context) of the open CTC prefix slots
         self._prefix: Dict[int, Tuple[int, float, float]] = {}   # (beam, ctc_weight, transducer_weight) of the open transducer prefix slots
         self._prefix_ctx: Dict[int, ContextBias] = {}   # the context of the biased ones among them
@@ -1180,7 +1195,7 @@ class StreamPool:
 
     def open(self, beam_size: int = 0, ctc_prefix_beam: int = 0, context: Optional[ContextBias] = None, keep_frames: bool = False,
              prefix_beam: int = 0, ctc_weight: float = 0.3, transducer_weight: float = 0.7, prefix_context: Optional[ContextBias] = None,
-             endpoint: Optional[EndpointConfig] = None) -> int:
+             endpoint: Optional[EndpointConfig] = None, on_endpoint: Optional[str] = None) -> int:
         """The lowest free slot, reset for a new utterance (reset_streaming_cache for that slot alone).  beam_size > 0: the slot's
         utterance is beam-searched with that beam (its hypotheses start as the one empty hypothesis); raises RnntError at once
         when this pool cannot do it.  ctc_prefix_beam > 0 (not together with beam_size): the slot's utterance runs the CTC prefix beam
@@ -1194,7 +1209,14 @@ class StreamPool:
         by prefix_context when given (`context` belongs to ctc_prefix_beam).  The one graph of the pool serves both kinds: a graph other
         than the current one is refused while any biased slot of either kind is open.
         endpoint: the slot (of any kind) detects its endpoint under that config (rnnt_stream_endpoint); endpoints() reads the result.
-        A config the library refuses takes no slot."""
+        A config the library refuses takes no slot.
+        on_endpoint: "keep" / "fresh" (needs endpoint): after its chunk calls step() reads the endpoints once and, for every such slot
+        whose rule has fired, does what next_segment(slot, keep_encoder = on_endpoint == "keep") does; segments(slot) returns the
+        finished Segments.  None: the slot's utterance ends with close() or next_segment() only."""
+        if on_endpoint not in (None, "keep", "fresh"):
+            raise RnntError(f"stream pool: on_endpoint {on_endpoint!r} is not None, 'keep' or 'fresh'")
+        if on_endpoint is not None and endpoint is None:
+            raise RnntError("stream pool: on_endpoint needs endpoint (an EndpointConfig)")
         biased_open = any(c is not None for _, c in self._ctc.values()) or bool(self._prefix_ctx)
         if prefix_context is not None:
             if not prefix_beam:
@@ -1246,6 +1268,11 @@ class StreamPool:
         self._offset[slot] = 0
         self._ntok[slot] = 0
         self._beam[slot] = int(beam_size)
+        self._seg[slot] = (0, 0)
+        self._segments.pop(slot, None)
+        if on_endpoint is not None:
+            self._on_endpoint[slot] = on_endpoint
+            self._segments[slot] = []
         self._forget_wave(slot)
         return slot
 
@@ -1363,7 +1390,62 @@ class StreamPool:
             new = self.engine.stream_tokens(slot, self._ntok[slot], self._stream(None))
             self._ntok[slot] += len(new)
             out[slot] = out.get(slot, []) + new
+        if self._on_endpoint:
+            self._segment_fired()
         return out
+
+    def _result(self, slot: int):
+        """What close() returns for the slot's utterance as it stands."""
+        if slot in self._prefix:
+            return self.prefix_hyps(slot, final=True)
+        if slot in self._ctc:
+            return self.ctc_hyps(slot, final=True)
+        return self.beams(slot) if self._beam[slot] > 0 else self.engine.stream_tokens(slot, 0, self._stream(None))
+
+    def _finish(self, slots: List[int], keep_encoder: bool, eps: Dict[int, Endpoint]) -> List[Segment]:
+        """The results of the listed slots, then ONE rnnt_pool_segment call for all of them, then the facade's own records."""
+        results = [self._result(slot) for slot in slots]
+        self.engine.pool_segment(slots, keep_encoder, self._stream(None))
+        segs = []
+        for slot, res in zip(slots, results):
+            index, start = self._seg[slot]
+            self._seg[slot] = tuple(int(v) for v in self.engine.stream_segment(slot))
+            self._ntok[slot] = 0
+            if not keep_encoder:
+                self._offset[slot] = 0                  # the encoder starts over; with it kept the estimated offset runs on, as the cache does
+            segs.append(Segment(index, start, self._seg[slot][1] - start, res, eps.get(slot)))
+        return segs
+
+    def _segment_fired(self):
+        """step() with on_endpoint slots: ONE endpoints() read, then the slots whose rule has fired, one _finish per flavour."""
+        eps = self.endpoints(sorted(self._on_endpoint))
+        for flavour in ("keep", "fresh"):
+            fired = [slot for slot, e in eps.items() if e.rule != 0 and self._on_endpoint[slot] == flavour]
+            if fired:
+                for seg, slot in zip(self._finish(fired, flavour == "keep", eps), fired):
+                    self._segments[slot].append(seg)
+
+    def next_segment(self, slot: int, keep_encoder: bool = True) -> Segment:
+        """End the slot's utterance and start the next one in the same slot (queued chunks and packets are processed first, as in
+        close()): returns its Segment -- result: what close() would have returned -- and leaves the slot open with its decoders, its
+        endpoint counters and its kept frames started over.  The audio stream (feed_wave) goes on across the boundary: nothing is
+        flushed, frames waiting for a full chunk belong to the next segment.  keep_encoder=True: the encoder's caches and the offset
+        run on (continuous decoding); False: the encoder starts over too, the next chunk's offset is 0.  hot words, keep_frames and
+        the endpoint config stay as open() set them."""
+        if slot not in self._offset:
+            raise RnntError(f"slot {slot} is not open")
+        if any(s == slot for s, _ in self._queue) or any(s == slot for s, _, _ in self._wave_queue):
+            self._carry = self.step()                   # the other slots' increments are handed out by the next step()
+        self._carry.pop(slot, None)
+        eps = self.endpoints([slot]) if slot in self._endpoint else {}
+        return self._finish([slot], bool(keep_encoder), eps)[0]
+
+    def segments(self, slot: int) -> List[Segment]:
+        """The Segments step() has finished for a slot opened with on_endpoint since the last call, oldest first (they survive close())."""
+        done = self._segments.get(slot, [])
+        if slot in self._segments:
+            self._segments[slot] = []
+        return done
 
     def beams(self, slot: int) -> List[BeamHypothesis]:
         """The current hypotheses of a beam slot, in beam order: what process_single_chunk_beam_search returns after each chunk
@@ -1374,7 +1456,7 @@ class StreamPool:
 
     def ctc_hyps(self, slot: int, final: bool = False):
         """[(tokens, score, times)] of a CTC prefix slot in the search's order, as they stand after the chunks stepped so far (times:
-        encoder-frame indices since the slot was opened).  final: what the one-launch search returns had the utterance ended here
+        encoder-frame indices since the slot was opened, or since its current segment began).  final: what the one-launch search returns had the utterance ended here
         (finalize's context score instead of the running one).  Reading changes nothing."""
         if slot not in self._ctc:
             raise RnntError(f"slot {slot} is not an open CTC prefix slot")
@@ -1467,16 +1549,12 @@ class StreamPool:
         self._carry.pop(slot, None)
         self._forget_wave(slot)
         self._endpoint.pop(slot, None)                  # the library clears its flag when the slot is opened again
-        if slot in self._prefix:
-            res = self.prefix_hyps(slot, final=True)
-            del self._prefix[slot]
-            self._prefix_ctx.pop(slot, None)
-        elif slot in self._ctc:
-            res = self.ctc_hyps(slot, final=True)
-            del self._ctc[slot]
-        else:
-            res = self.beams(slot) if self._beam[slot] > 0 else self.engine.stream_tokens(slot, 0, self._stream(None))
-        del self._offset[slot], self._ntok[slot], self._beam[slot]
+        self._on_endpoint.pop(slot, None)
+        res = self._result(slot)
+        self._prefix.pop(slot, None)
+        self._prefix_ctx.pop(slot, None)
+        self._ctc.pop(slot, None)
+        del self._offset[slot], self._ntok[slot], self._beam[slot], self._seg[slot]
         self._free.append(slot)
         self._free.sort()
         return res

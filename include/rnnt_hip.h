@@ -692,6 +692,33 @@ int rnnt_ctc_blank_logprob(rnnt_ctx* ctx, const float* enc_dev, int32_t rows, fl
  * rnnt_stream_endpoint refuses. */
 int rnnt_endpoint_scan_host(const float* blank_lp, int32_t t, const rnnt_endpoint_config* cfg, int32_t* state);
 
+/* -- segments: the next utterance in a slot that stays open ------------------------------------------------------------------------------ */
+/* What follows an endpoint.  A segment boundary ends one utterance in each of the n listed slots (distinct, in [0, n_streams)) and
+ * starts the next without rnnt_stream_open: the slot, its configuration and its audio stream stay.  Per listed slot, in both flavours:
+ *   greedy state      as rnnt_stream_open leaves it: both LSTM buffers 0, last token = blank, token count 0;
+ *   beam              the one empty hypothesis with score 0 and zero state;
+ *   prefix searches   the start state of rnnt_stream_ctc_prefix_reset / rnnt_stream_prefix_reset; the next advancing call may fix
+ *                     another beam size, other weights, another use_context, and a biased one binds the graph current at that call;
+ *   endpoint          the five counters 0; the config and the on flag stay;
+ *   frame history     length 0; the keep flag and the buffer stay;
+ *   segment record    index + 1, start_frame = the encoder frames the slot had encoded since it was opened (see below).
+ * A state kind the context has never allocated costs nothing.
+ * keep_encoder != 0 (continuous decoding): nothing of the encoder or the audio front-end of any slot is read or written -- K/V rows,
+ * position (cache length, window start, ring position), both conv rings, the wave state.  The caller's offsets run on.
+ * keep_encoder == 0: also the encoder state of rnnt_stream_open for the listed slots -- the conv rings of all layers as for a fresh
+ * stream, an empty cache at position 0; the next chunk's offset is 0.  The wave front-end (carry, samples, frames, sample rate /
+ * n_fft), the endpoint config and the keep flag survive.  This is how a slot outlives max_cache_frames and the positional table.
+ * Cost: ONE async copy of the slot list and ONE launch whatever n and whatever state kinds exist; no synchronisation, no download;
+ * enqueued on `stream` in order.  The context enters pool mode; slots not listed are untouched.
+ * Refusals, all before the launch and changing nothing: RNNT_ERR_ARG for a null list, n outside [1, n_streams], a slot out of range
+ * or listed twice; RNNT_ERR_STATE without weights / streams or with frames still buffered. */
+int rnnt_pool_segment(rnnt_ctx* ctx, int32_t n, const int32_t* slots_host, int32_t keep_encoder, void* stream);
+/* Host only: index_out = segments started in `slot` since rnnt_stream_open / rnnt_streams_reset (0: none), start_frame_out = the
+ * encoder frames the slot had encoded, since then, when its current segment began.  The frame indices the getters return -- CTC
+ * times, alignment emit frames, the endpoint's `at` -- are relative to the segment; add start_frame_out for the session's.  Either
+ * pointer may be NULL.  RNNT_ERR_ARG for a slot outside [0, max_streams). */
+int rnnt_stream_get_segment(rnnt_ctx* ctx, int32_t slot, int32_t* index_out, int32_t* start_frame_out);
+
 /* -- forced alignment: WHERE in the frames each token of a given transcript lies (the reference's WeNet layer: force_align,
  * gen_ctc_peak_time, gen_timestamps_from_peak, DecodeResult.times; wenet/utils/ctc_utils.py) ------------------------------------ */
 /* The best monotonic alignment of each row's transcript: the max-plus (Viterbi) twin of rnnt_transducer_nll's recursion in f64,
