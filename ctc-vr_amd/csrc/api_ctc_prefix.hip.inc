@@ -86,17 +86,22 @@ struct CpHyp {
     std::vector<int> prefix, times_s, times_ns;
     double s = -INFINITY, ns = -INFINITY, v_s = -INFINITY, v_ns = -INFINITY, cur_token_prob = -INFINITY, context_score = 0.0;
     int context_state = 0;
+    double ngram_score = 0.0;                                                        // with an n-gram model: its score and state
+    int ngram_state = 0;
     bool has_context = false;
     double score() const { return prefix_log_add(s, ns); }
     double viterbi_score() const { return v_s > v_ns ? v_s : v_ns; }
     const std::vector<int>& times() const { return v_s > v_ns ? times_s : times_ns; }
-    double total_score() const { return score() + context_score; }
+    double total_score() const { return score() + context_score + ngram_score; }
 };
 
 // search.py:139-236 for one utterance: lp [len][V]; graph may be null.  The dictionary of a frame is a vector in first-insertion order.
-void ctc_prefix_search_host(const float* lp, int len, int V, int blank, int beam, const CtxGraph* g, std::vector<CpHyp>& cur) {
+// ng (may be null): an n-gram model fused under the same first-touch rule as the graph; its end term is added at the end.
+void ctc_prefix_search_host(const float* lp, int len, int V, int blank, int beam, const CtxGraph* g, const NgModel* ng, std::vector<CpHyp>& cur) {
+    const NgTables nt = ng ? ng->tables() : NgTables{};
     cur.assign(1, CpHyp());
     cur[0].s = 0.0; cur[0].v_s = 0.0; cur[0].v_ns = 0.0;
+    if (ng) cur[0].ngram_state = nt.start;
     for (int t = 0; t < len; ++t) {
         const float* row = lp + (size_t)t * V;
         std::vector<unsigned long long> keys(V);
@@ -111,14 +116,22 @@ void ctc_prefix_search_host(const float* lp, int len, int V, int blank, int beam
             return next.size() - 1;
         };
         auto copy_context = [&](CpHyp& n, const CpHyp& h) {
-            if (!g || n.has_context) return;
+            if ((!g && !ng) || n.has_context) return;
             n.context_score = h.context_score; n.context_state = h.context_state; n.has_context = true;
+            n.ngram_score = h.ngram_score; n.ngram_state = h.ngram_state;
         };
         auto update_context = [&](CpHyp& n, const CpHyp& h, int u) {
-            if (!g || n.has_context) return;
+            if ((!g && !ng) || n.has_context) return;
             int nx;
-            const double sc = ctx_graph_step(*g, h.context_state, u, &nx);
-            n.context_score = h.context_score; n.context_score += sc; n.context_state = nx; n.has_context = true;
+            if (g) {
+                const double sc = ctx_graph_step(*g, h.context_state, u, &nx);
+                n.context_score = h.context_score; n.context_score += sc; n.context_state = nx;
+            }
+            if (ng) {
+                n.ngram_score = h.ngram_score + ng_step(nt, h.ngram_state, u, &nx);
+                n.ngram_state = nx;
+            }
+            n.has_context = true;
         };
         for (int r = 0; r < beam; ++r) {
             const int u = cp_key_index(keys[r]);
@@ -173,6 +186,8 @@ void ctc_prefix_search_host(const float* lp, int len, int V, int blank, int beam
     }
     if (g)
         for (CpHyp& h : cur) { h.context_score = -g->nscore[h.context_state]; h.context_state = 0; }   // :227-232, not re-sorted
+    if (ng)
+        for (CpHyp& h : cur) h.ngram_score += ng_eos(nt, h.ngram_state);                               // likewise
 }
 
 int ctc_prefix_check(rnnt_ctx* ctx, const char* who, const void* in, const int32_t* enc_lens, int B, int T, int V, int beam_size, int cap_tokens,
@@ -275,6 +290,18 @@ int rnnt_ctc_prefix_beam_host(const float* lp_host, const int32_t* enc_lens_host
                               int32_t beam_size, int32_t n_phrases, const int32_t* phrase_lens, const int32_t* phrase_tokens, double context_score,
                               int32_t cap_tokens, int32_t* n_hyp_host, int32_t* lens_host, int32_t* tokens_host, int32_t* times_host,
                               double* scores_host, double* ctx_scores_host) {
+    return rnnt_ctc_prefix_beam_ngram_host(lp_host, enc_lens_host, B, T, vocab, blank, beam_size, n_phrases, phrase_lens, phrase_tokens, context_score, 0,
+                                           nullptr, nullptr, nullptr, nullptr, 0.0, 0.0, 0.0, cap_tokens, n_hyp_host, lens_host, tokens_host, times_host,
+                                           scores_host, ctx_scores_host, nullptr);
+}
+
+// The same with an n-gram model fused (the list as rnnt_ngram_set takes it; n_ngrams == 0: none) and its scores ngram_scores_host
+// [B, beam_size] (may be NULL).
+int rnnt_ctc_prefix_beam_ngram_host(const float* lp_host, const int32_t* enc_lens_host, int32_t B, int32_t T, int32_t vocab, int32_t blank,
+                                    int32_t beam_size, int32_t n_phrases, const int32_t* phrase_lens, const int32_t* phrase_tokens, double context_score,
+                                    int32_t n_ngrams, const int32_t* ngram_lens, const int32_t* ngram_tokens, const double* logp, const double* bow,
+                                    double lm_weight, double length_bonus, double unk_logp, int32_t cap_tokens, int32_t* n_hyp_host, int32_t* lens_host,
+                                    int32_t* tokens_host, int32_t* times_host, double* scores_host, double* ctx_scores_host, double* ngram_scores_host) {
     int fmax, rc;
     if ((rc = ctc_prefix_check(nullptr, "rnnt_ctc_prefix_beam_host", lp_host, enc_lens_host, B, T, vocab, beam_size, cap_tokens, n_hyp_host, lens_host,
                                tokens_host, times_host, scores_host, &fmax)))
@@ -282,15 +309,19 @@ int rnnt_ctc_prefix_beam_host(const float* lp_host, const int32_t* enc_lens_host
     CtxGraph g;
     std::string err;
     if (n_phrases && (rc = ctx_graph_build(n_phrases, phrase_lens, phrase_tokens, context_score, vocab, blank, g, err))) return rc;
+    NgModel ng;
+    if (n_ngrams && (rc = ngram_build(n_ngrams, ngram_lens, ngram_tokens, logp, bow, lm_weight, length_bonus, unk_logp, vocab, blank, ng, err))) return rc;
     const size_t R = (size_t)B * beam_size;
     std::fill(lens_host, lens_host + R, 0);
     std::fill(tokens_host, tokens_host + R * cap_tokens, 0);
     std::fill(times_host, times_host + R * cap_tokens, 0);
     std::fill(scores_host, scores_host + R, 0.0);
     if (ctx_scores_host) std::fill(ctx_scores_host, ctx_scores_host + R, 0.0);
+    if (ngram_scores_host) std::fill(ngram_scores_host, ngram_scores_host + R, 0.0);
     for (int b = 0; b < B; ++b) {
         std::vector<CpHyp> hyps;
-        ctc_prefix_search_host(lp_host + (size_t)b * T * vocab, enc_lens_host[b], vocab, blank, beam_size, n_phrases ? &g : nullptr, hyps);
+        ctc_prefix_search_host(lp_host + (size_t)b * T * vocab, enc_lens_host[b], vocab, blank, beam_size, n_phrases ? &g : nullptr, n_ngrams ? &ng : nullptr,
+                               hyps);
         n_hyp_host[b] = (int)hyps.size();
         for (size_t a = 0; a < hyps.size(); ++a) {
             const size_t r = (size_t)b * beam_size + a;
@@ -300,6 +331,7 @@ int rnnt_ctc_prefix_beam_host(const float* lp_host, const int32_t* enc_lens_host
             std::copy(tm.begin(), tm.end(), times_host + r * cap_tokens);
             scores_host[r] = hyps[a].total_score();
             if (ctx_scores_host) ctx_scores_host[r] = hyps[a].context_score;
+            if (ngram_scores_host) ngram_scores_host[r] = hyps[a].ngram_score;
         }
     }
     return RNNT_OK;
@@ -311,6 +343,15 @@ int rnnt_ctc_prefix_beam_host(const float* lp_host, const int32_t* enc_lens_host
 int rnnt_ctc_prefix_beam_logprobs(rnnt_ctx* ctx, const float* lp_dev, const int32_t* enc_lens_host, int32_t B, int32_t T, int32_t beam_size,
                                   int32_t use_context, int32_t cap_tokens, int32_t* n_hyp_host, int32_t* lens_host, int32_t* tokens_host,
                                   int32_t* times_host, double* scores_host, double* ctx_scores_host, void* stream) {
+    return rnnt_ctc_prefix_beam_logprobs_ngram(ctx, lp_dev, enc_lens_host, B, T, beam_size, use_context, 0, cap_tokens, n_hyp_host, lens_host, tokens_host,
+                                               times_host, scores_host, ctx_scores_host, nullptr, stream);
+}
+
+// The same with the model of rnnt_ngram_set fused when use_ngram (ctc_prefix_search<true>); ngram_scores_host [B, beam_size] or NULL.
+int rnnt_ctc_prefix_beam_logprobs_ngram(rnnt_ctx* ctx, const float* lp_dev, const int32_t* enc_lens_host, int32_t B, int32_t T, int32_t beam_size,
+                                        int32_t use_context, int32_t use_ngram, int32_t cap_tokens, int32_t* n_hyp_host, int32_t* lens_host,
+                                        int32_t* tokens_host, int32_t* times_host, double* scores_host, double* ctx_scores_host,
+                                        double* ngram_scores_host, void* stream) {
     if (!ctx) return RNNT_ERR_ARG;
     const int V = ctx->cfg.vocab_size;
     int fmax, rc;
@@ -318,6 +359,8 @@ int rnnt_ctc_prefix_beam_logprobs(rnnt_ctx* ctx, const float* lp_dev, const int3
                                tokens_host, times_host, scores_host, &fmax)))
         return rc;
     if (use_context && !ctx->cg_on) return fail(ctx, RNNT_ERR_STATE, "rnnt_ctc_prefix_beam_logprobs: use_context without a context graph (rnnt_context_set)");
+    if (use_ngram && !ctx->ng_on) return fail(ctx, RNNT_ERR_STATE, "rnnt_ctc_prefix_beam_logprobs: use_ngram without an n-gram model (rnnt_ngram_set)");
+    const size_t nd = use_ngram ? 3 : 2;                              // scores | context scores | n-gram scores
     const size_t R = (size_t)B * beam_size, lcap = std::max(fmax, 1), astride = (size_t)T * beam_size + 1;
     if ((size_t)B * T * V >= ((size_t)1 << 40) || (size_t)B * astride >= ((size_t)1 << 30) || R * lcap >= ((size_t)1 << 30))
         return fail(ctx, RNNT_ERR_SHAPE, "rnnt_ctc_prefix_beam_logprobs: B=%d T=%d beam=%d too large for one call", B, T, beam_size);
@@ -336,27 +379,31 @@ int rnnt_ctc_prefix_beam_logprobs(rnnt_ctx* ctx, const float* lp_dev, const int3
     };
     lay();   // sizes
     if ((rc = reserve(ctx, ctx->cp_i, i.off))) return rc;
-    if ((rc = reserve(ctx, ctx->cp_d, 2 * R))) return rc;
+    if ((rc = reserve(ctx, ctx->cp_d, nd * R))) return rc;
     i = {ctx->cp_i};
     lay();   // pointers
     p.o.nh = o.nh; p.o.len = o.len; p.o.tok = o.tok; p.o.time = o.time;
     p.o.sc = ctx->cp_d; p.o.cs = ctx->cp_d + R;
     p.lp = lp_dev; p.lens = d_lens; p.T = T; p.V = V; p.blank = ctx->cfg.blank_id; p.beam = beam_size; p.lcap = (int)lcap;
     if (use_context) p.g = ctx_graph_dev(ctx);
+    if (use_ngram) { p.ng = ngram_dev(ctx); p.o.ls = ctx->cp_d + 2 * R; }
     HIPCHK(hipMemcpyAsync(d_lens, enc_lens_host, B * sizeof(int), hipMemcpyHostToDevice, s));            // the upload
     {
         ProfScope prof(ctx, s, TAG_CTC_PREFIX);
-        hipLaunchKernelGGL(ctc_prefix_search, dim3(B), dim3(CP_NT), 0, s, p);
+        if (use_ngram) hipLaunchKernelGGL(ctc_prefix_search<true>, dim3(B), dim3(CP_NT), 0, s, p);
+        else hipLaunchKernelGGL(ctc_prefix_search<false>, dim3(B), dim3(CP_NT), 0, s, p);
         LAUNCHCHK("ctc_prefix_search");
     }
     std::vector<int> oi(o.total);
-    std::vector<double> od(2 * R);
+    std::vector<double> od(nd * R);
     HIPCHK(hipMemcpyAsync(oi.data(), o.nh, o.total * sizeof(int), hipMemcpyDeviceToHost, s));            // the download (two blocks)
-    HIPCHK(hipMemcpyAsync(od.data(), ctx->cp_d, 2 * R * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(od.data(), ctx->cp_d, nd * R * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     Carve<int> hc{oi.data()};
     const CpOut h = cp_out(hc, B, R, lcap);
-    cp_out_copy(h, od.data(), B, R, lcap, R, (size_t)cap_tokens, n_hyp_host, lens_host, tokens_host, times_host, scores_host, ctx_scores_host);
+    cp_out_copy(h, od.data(), B, R, lcap, R, (size_t)cap_tokens, n_hyp_host, lens_host, tokens_host, times_host, scores_host, ctx_scores_host,
+                use_ngram ? ngram_scores_host : nullptr);
+    if (!use_ngram && ngram_scores_host) std::fill(ngram_scores_host, ngram_scores_host + R, 0.0);
     return RNNT_OK;
 }
 
@@ -364,12 +411,21 @@ int rnnt_ctc_prefix_beam_logprobs(rnnt_ctx* ctx, const float* lp_dev, const int3
 int rnnt_ctc_prefix_beam_decode(rnnt_ctx* ctx, const float* enc_dev, const int32_t* enc_lens_host, int32_t B, int32_t T, int32_t beam_size,
                                 int32_t use_context, int32_t cap_tokens, int32_t* n_hyp_host, int32_t* lens_host, int32_t* tokens_host,
                                 int32_t* times_host, double* scores_host, double* ctx_scores_host, void* stream) {
+    return rnnt_ctc_prefix_beam_decode_ngram(ctx, enc_dev, enc_lens_host, B, T, beam_size, use_context, 0, cap_tokens, n_hyp_host, lens_host, tokens_host,
+                                             times_host, scores_host, ctx_scores_host, nullptr, stream);
+}
+
+int rnnt_ctc_prefix_beam_decode_ngram(rnnt_ctx* ctx, const float* enc_dev, const int32_t* enc_lens_host, int32_t B, int32_t T, int32_t beam_size,
+                                      int32_t use_context, int32_t use_ngram, int32_t cap_tokens, int32_t* n_hyp_host, int32_t* lens_host,
+                                      int32_t* tokens_host, int32_t* times_host, double* scores_host, double* ctx_scores_host,
+                                      double* ngram_scores_host, void* stream) {
     if (!ctx) return RNNT_ERR_ARG;
     int fmax, rc;
     if ((rc = ctc_prefix_check(ctx, "rnnt_ctc_prefix_beam_decode", enc_dev, enc_lens_host, B, T, ctx->cfg.vocab_size, beam_size, cap_tokens, n_hyp_host,
                                lens_host, tokens_host, times_host, scores_host, &fmax)))
         return rc;
     if (use_context && !ctx->cg_on) return fail(ctx, RNNT_ERR_STATE, "rnnt_ctc_prefix_beam_decode: use_context without a context graph (rnnt_context_set)");
+    if (use_ngram && !ctx->ng_on) return fail(ctx, RNNT_ERR_STATE, "rnnt_ctc_prefix_beam_decode: use_ngram without an n-gram model (rnnt_ngram_set)");
     if (!ctx->finalized) return fail(ctx, RNNT_ERR_STATE, "weights not finalized");
     if (!ctx->wctc) return fail(ctx, RNNT_ERR_STATE, "rnnt_ctc_prefix_beam_decode: ctc_head.ctc_lo.* not loaded");
     if ((long long)B * T >= 0x7fffffffLL / 512) return fail(ctx, RNNT_ERR_SHAPE, "rnnt_ctc_prefix_beam_decode: B=%d T=%d frames in one call", B, T);
@@ -378,6 +434,6 @@ int rnnt_ctc_prefix_beam_decode(rnnt_ctx* ctx, const float* enc_dev, const int32
         GemmCapScope cap(ctx);
         if ((rc = rnnt_ctc_logprobs(ctx, enc_dev, B * T, ctx->cp_lp, stream))) return rc;
     }
-    return rnnt_ctc_prefix_beam_logprobs(ctx, ctx->cp_lp, enc_lens_host, B, T, beam_size, use_context, cap_tokens, n_hyp_host, lens_host, tokens_host,
-                                         times_host, scores_host, ctx_scores_host, stream);
+    return rnnt_ctc_prefix_beam_logprobs_ngram(ctx, ctx->cp_lp, enc_lens_host, B, T, beam_size, use_context, use_ngram, cap_tokens, n_hyp_host, lens_host,
+                                               tokens_host, times_host, scores_host, ctx_scores_host, ngram_scores_host, stream);
 }

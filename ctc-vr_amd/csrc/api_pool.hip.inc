@@ -117,10 +117,11 @@ enum { POOL_ENCODE = 0, POOL_GREEDY = 1, POOL_BEAM = 2, POOL_CTC_PREFIX = 3, POO
 
 // rnnt_pool_chunk (mode POOL_ENCODE / POOL_GREEDY), rnnt_pool_chunk_beam (POOL_BEAM), rnnt_pool_chunk_ctc_prefix (POOL_CTC_PREFIX) and
 // rnnt_pool_chunk_prefix (POOL_PREFIX): validation, the call's table, the encoder launches and the position bookkeeping are one code
-// path; only what follows the encoder differs.  use_context: POOL_CTC_PREFIX and POOL_PREFIX; ctc_weight / transducer_weight: POOL_PREFIX only.
+// path; only what follows the encoder differs.  use_context: POOL_CTC_PREFIX and POOL_PREFIX; ctc_weight / transducer_weight: POOL_PREFIX only;
+// use_ngram: POOL_CTC_PREFIX only.
 int pool_chunk_run(rnnt_ctx* ctx, const char* fn, int32_t n_active, const int32_t* slots_host, const float* fbank_dev, int32_t T,
                    const int32_t* offsets_host, const int32_t* required_host, int mode, int32_t beam_size, int32_t* frames_out, void* stream,
-                   int32_t use_context = 0, float ctc_weight = 0.f, float transducer_weight = 0.f) {
+                   int32_t use_context = 0, float ctc_weight = 0.f, float transducer_weight = 0.f, int32_t use_ngram = 0) {
     if (!ctx || !slots_host || !fbank_dev || !offsets_host || !required_host) return fail(ctx, RNNT_ERR_ARG, "%s: null argument", fn);
     if (!ctx->finalized || ctx->n_streams < 1) return fail(ctx, RNNT_ERR_STATE, "%s: no weights / no streams", fn);
     if (mode == POOL_GREEDY && !ctx->use_persistent) return fail(ctx, RNNT_ERR_STATE, "%s: the greedy decode of a pool call needs the resident decoder", fn);
@@ -180,7 +181,7 @@ int pool_chunk_run(rnnt_ctx* ctx, const char* fn, int32_t n_active, const int32_
         }
     }
     if (mode == POOL_CTC_PREFIX) {   // the search's own refusals, before anything is launched or moved; then its buffers
-        if ((rc = pool_ctc_check(ctx, fn, n, slots_host, tq, beam_size, use_context))) return rc;
+        if ((rc = pool_ctc_check(ctx, fn, n, slots_host, tq, beam_size, use_context, use_ngram))) return rc;
         if ((rc = reserve(ctx, ctx->cp_lp, (size_t)n * tq * V))) return rc;
         if ((rc = pool_ctc_alloc(ctx, s))) return rc;
     }
@@ -257,7 +258,7 @@ int pool_chunk_run(rnnt_ctx* ctx, const char* fn, int32_t n_active, const int32_
             GemmCapScope cap_scope(ctx);
             if ((rc = rnnt_ctc_logprobs(ctx, ctx->x, n * tq, ctx->cp_lp, stream))) return rc;
         }
-        return pool_ctc_launch(ctx, s, n, slots_host, ctx->cp_lp, tq, beam_size, use_context);   // the frames are consumed: frames_buffered stays 0
+        return pool_ctc_launch(ctx, s, n, slots_host, ctx->cp_lp, tq, beam_size, use_context, use_ngram);   // the frames are consumed: frames_buffered stays 0
     }
     if (mode == POOL_PREFIX) {
         // ---- the CTC log-probabilities of the compact after_norm rows when the search fuses them, then the slots' searches ----
@@ -302,6 +303,13 @@ int rnnt_pool_chunk_ctc_prefix(rnnt_ctx* ctx, int32_t n_active, const int32_t* s
                                const int32_t* required_host, int32_t beam_size, int32_t use_context, int32_t* frames_out, void* stream) {
     return pool_chunk_run(ctx, "rnnt_pool_chunk_ctc_prefix", n_active, slots_host, fbank_dev, T, offsets_host, required_host, POOL_CTC_PREFIX, beam_size,
                           frames_out, stream, use_context);
+}
+
+int rnnt_pool_chunk_ctc_prefix_ngram(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, const float* fbank_dev, int32_t T, const int32_t* offsets_host,
+                                     const int32_t* required_host, int32_t beam_size, int32_t use_context, int32_t use_ngram, int32_t* frames_out,
+                                     void* stream) {
+    return pool_chunk_run(ctx, "rnnt_pool_chunk_ctc_prefix", n_active, slots_host, fbank_dev, T, offsets_host, required_host, POOL_CTC_PREFIX, beam_size,
+                          frames_out, stream, use_context, 0.f, 0.f, use_ngram);
 }
 
 int rnnt_pool_chunk_prefix(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, const float* fbank_dev, int32_t T, const int32_t* offsets_host,

@@ -662,6 +662,15 @@ CpGraph ctx_graph_dev(const rnnt_ctx* ctx) {
     return g;
 }
 
+// the uploaded tables of rnnt_ngram_set as the kernels take them
+NgTables ngram_dev(const rnnt_ctx* ctx) {
+    const size_t n = ctx->ng.fail.size(), m = ctx->ng.ctok.size();
+    NgTables g = ctx->ng.tables();
+    g.fail = ctx->ng_i; g.off = ctx->ng_i + n; g.ctok = ctx->ng_i + 2 * n + 1; g.cid = g.ctok + m; g.root = g.cid + m;
+    g.W = ctx->ng_d; g.B = ctx->ng_d + n;
+    return g;
+}
+
 // The block of a CTC prefix search's results that is downloaded in one copy, on the device or in its host copy (the one-call search
 // with its B, a slot's read with B = 1): n_hyp [B] | lens [R] | tokens [R][lcap] | times [R][lcap]; total: its ints.
 struct CpOut { int *nh, *len, *tok, *time; size_t total; };
@@ -675,9 +684,11 @@ CpOut cp_out(Carve<int>& c, size_t B, size_t R, size_t lcap) {
     o.total = c.off - at;
     return o;
 }
-// its host copy h (and the scores | context scores od [2][R]) into the caller's arrays: H >= R rows of cap_tokens, zero beyond what was found
+// its host copy h (and the scores | context scores | with ng_scores the n-gram scores, od [2 or 3][R]) into the caller's arrays: H >= R
+// rows of cap_tokens, zero beyond what was found
 void cp_out_copy(const CpOut& h, const double* od, size_t B, size_t R, size_t lcap, size_t H, size_t cap_tokens, int32_t* n_hyp, int32_t* lens,
-                 int32_t* tokens, int32_t* times, double* scores, double* ctx_scores) {
+                 int32_t* tokens, int32_t* times, double* scores, double* ctx_scores, double* ng_scores = nullptr) {
+    if (ng_scores) { std::fill(ng_scores, ng_scores + H, 0.0); memcpy(ng_scores, od + 2 * R, R * sizeof(double)); }
     memcpy(n_hyp, h.nh, B * sizeof(int));
     std::fill(lens, lens + H, 0);
     std::fill(scores, scores + H, 0.0);

@@ -13,6 +13,7 @@
 #include <functional>
 #include <map>
 #include <string>
+#include <unordered_map>
 #include <algorithm>
 #include <array>
 #include <atomic>
@@ -77,6 +78,20 @@ struct CtxGraph {
     std::vector<double> tscore, nscore, oscore;
 };
 
+// Back-off n-gram model of the CTC prefix beam search (api_ngram.hip.inc) as flat tables, prescaled: node ids in list order, root = 0
+struct NgModel {
+    std::vector<int> fail, off, ctok, cid, root;
+    std::vector<double> W, B;
+    double U = 0.0;
+    int start = 0, eos = -1;
+    NgTables tables() const {
+        NgTables g;
+        g.fail = fail.data(); g.off = off.data(); g.ctok = ctok.data(); g.cid = cid.data(); g.root = root.data(); g.W = W.data(); g.B = B.data();
+        g.U = U; g.start = start; g.eos = eos;
+        return g;
+    }
+};
+
 // Device bytes currently held through DevBuf owners, process-wide (rnnt_live_device_bytes).
 std::atomic<int64_t> live_device_bytes{0};
 
@@ -104,12 +119,12 @@ using PinnedBuf = DevBuf<T, true>;
 
 // Per slot of the stream pool, on the host.  SearchSlot, a prefix search carried across calls: the frames walked, and what its first
 // advancing call fixed until the next reset -- beam (0: fresh), the two weights (0 for the CTC search), use_context, the graph
-// generation (rnnt_ctx::cg_gen).  WvSlot, the front-end: samples received and frames emitted since the reset, the (sample_rate,
+// generation (rnnt_ctx::cg_gen); the CTC search also use_ngram and the model generation (rnnt_ctx::ng_gen).  WvSlot, the front-end: samples received and frames emitted since the reset, the (sample_rate,
 // n_fft) its first push fixed (n_fft == 0: fresh), whether its utterance has ended.  HsSlot, the frame history: flag and length.
 // ep: endpoint detection is on (the config and the counters live on the device, api_pool_endpoint.hip.inc).  SegSlot, the segment
 // record (api_pool_segment.hip.inc): segments started since the slot was opened, the encoder frames it had encoded when the current
 // one began, and those encoded since it was opened (the encoder position does not say: a fresh segment restarts it).
-struct SearchSlot { int frames_done, beam; float cw, tw; int use_context; int64_t gen; };
+struct SearchSlot { int frames_done, beam; float cw, tw; int use_context; int64_t gen; int use_ngram; int64_t ngen; };
 struct WvSlot { int samples, frames, rate, nfft, finished; };
 struct HsSlot { int keep, len; };
 struct SegSlot { int index, start, frames; };
@@ -302,6 +317,13 @@ struct rnnt_ctx {
     DevBuf<int2> pc_parena, pc_tarena;
     CallTab pc_tab;
     DevBuf<double> pc_out;
+    // n-gram model of rnnt_ngram_set (api_ngram.hip.inc): host tables, device ints (fail | off | ctok | cid | root) and doubles (W | B);
+    // ng_gen counts rnnt_ngram_set calls.  rnnt_ngram_score's own buffers: lengths | tokens (ngs_i), step scores | totals (ngs_d).
+    NgModel ng;
+    bool ng_on = false;
+    int64_t ng_gen = 0;
+    DevBuf<int> ng_i, ngs_i;
+    DevBuf<double> ng_d, ngs_d;
     // transducer prefix beam search per slot of the stream pool (api_pool_prefix.hip.inc), allocated on its first use: hypothesis i of
     // slot b is row b * PB_MAX_BEAM + i of two buffer sets -- states [rows][2][512], token lists [rows][max_cache_frames + 1],
     // lengths / scores / hashes [rows] -- plus the hypotheses per slot, the step's top-k [rows][PB_MAX_BEAM], the frames of one call
@@ -367,6 +389,7 @@ extern "C" {
 #include "api_ops.hip.inc"
 #include "api_score.hip.inc"
 #include "api_state.hip.inc"
+#include "api_ngram.hip.inc"
 #include "api_pool_ctc.hip.inc"
 #include "api_pool_prefix.hip.inc"
 #include "api_pool.hip.inc"

@@ -40,16 +40,18 @@
 constexpr int CP_NT = 256, CP_MAX_BEAM = 16, CP_SLOTS = CP_MAX_BEAM + CP_MAX_BEAM * CP_MAX_BEAM, CP_NOKEY = 0x7fffffff;
 constexpr int CP_MAX_NODES = 4096;
 
-// the context graph (CpGraph, cg_child, cg_step): rnnt_ctxgraph.hip.h
+// the context graph (CpGraph, cg_child, cg_step): rnnt_ctxgraph.hip.h; the n-gram model (NgTables, ng_step): rnnt_ngram.hip.h.
+// The kernels are templates over NG, "an n-gram model is fused": NG = false compiles the search without it.
 
-// packed results: [B], [B][beam], [B][beam][lcap] x 2, [B][beam] x 2
-struct CpOutP { int* nh; int* len; int* tok; int* time; double* sc; double* cs; };
+// packed results: [B], [B][beam], [B][beam][lcap] x 2, [B][beam] x 2, and (NG, optional) the n-gram scores [B][beam]
+struct CpOutP { int* nh; int* len; int* tok; int* time; double* sc; double* cs; double* ls; };
 
 struct CtcPrefixP {
     const float* lp;             // [B][T][V] log-probabilities
     const int* lens;             // [B]
     int T, V, blank, beam, lcap;
     CpGraph g;
+    NgTables ng;
     int2* parena; int2* tarena;  // [B][T * beam + 1] each
     CpOutP o;
 };
@@ -63,8 +65,10 @@ struct CpHyps {
     int tns[CP_MAX_BEAM], tls[CP_MAX_BEAM];                          // times_s: node, length
     int tnn[CP_MAX_BEAM], tnp[CP_MAX_BEAM], tln[CP_MAX_BEAM];        // times_ns: node, its parent, length
     int tn[CP_MAX_BEAM], tl[CP_MAX_BEAM];                            // times(): times_s if v_s > v_ns else times_ns
+    double ls[CP_MAX_BEAM];                                          // n-gram score and state (NG_START until the first step)
+    int lst[CP_MAX_BEAM];
 };
-struct CpSlotState { CpHyps h; int nh, pad; };                       // 7 f64, 2 u64 and 12 int per hypothesis + the count: 1928 bytes
+struct CpSlotState { CpHyps h; int nh, pad; };                       // 8 f64, 2 u64 and 13 int per hypothesis + the count: 2120 bytes
 
 // per-frame work area in LDS
 struct CpWork {
@@ -82,17 +86,20 @@ struct CtcPrefixPoolP {
     const int* t0;               // [n] frames the slot's search has walked before this call
     int t, V, blank, beam;
     CpGraph g;
+    NgTables ng;
     int2* parena; int2* tarena;  // [max_streams][astride] each, astride = max_cache_frames * CP_MAX_BEAM + 1
     size_t astride;
     CpSlotState* state;          // [max_streams]
 };
 
-// one slot's hypotheses as the one-launch search's epilogue packs them; fin_nscore != nullptr: finalize's context score
+// one slot's hypotheses as the one-launch search's epilogue packs them; fin_nscore != nullptr: finalize's context score; final: the
+// n-gram end term is added (NG)
 struct CtcPrefixPackP {
     const CpSlotState* state;    // the slot's record
     const int2* pa; const int2* ta;
     const double* fin_nscore;
-    int beam, lcap;
+    NgTables ng;
+    int beam, lcap, final;
     CpOutP o;
 };
 
@@ -137,8 +144,9 @@ __device__ __forceinline__ bool cp_is_parent(const CpHyps& H, const int2* pa, in
 }
 
 // survivor `a` of frame t: hypothesis row a of the next frame (stride: time-arena nodes per frame)
+template <bool NG>
 __device__ __forceinline__ void cp_put(CpHyps& H, int2* ta, int stride, int a, int t, double s, double ns, double vs, double vns, double cs, int cst,
-                                       int node, int pnode, int last, int plen, unsigned long long hash, unsigned long long phash, int tns, int tls,
+                                       double ls, int lst, int node, int pnode, int last, int plen, unsigned long long hash, unsigned long long phash, int tns, int tls,
                                        int tnn, int tnp, int tln, bool tnew) {
     H.hash[a] = hash; H.phash[a] = phash;
     if (tnew) {
@@ -146,6 +154,7 @@ __device__ __forceinline__ void cp_put(CpHyps& H, int2* ta, int stride, int a, i
         ta[tnn] = make_int2(tnp, t);
     }
     H.s[a] = s; H.ns[a] = ns; H.vs[a] = vs; H.vns[a] = vns; H.cs[a] = cs; H.cst[a] = cst;
+    if (NG) { H.ls[a] = ls; H.lst[a] = lst; }
     H.score[a] = prefix_log_add(s, ns);
     H.vit[a] = vs > vns ? vs : vns;
     H.node[a] = node; H.pnode[a] = pnode; H.last[a] = last; H.plen[a] = plen;
@@ -154,14 +163,15 @@ __device__ __forceinline__ void cp_put(CpHyps& H, int2* ta, int stride, int a, i
     H.tl[a] = vs > vns ? tls : tln;
 }
 
-// the start hypothesis (search.py:142-149): the empty prefix, s = 0, ns = -inf, v_s = v_ns = 0, context root
+// the start hypothesis (search.py:142-149): the empty prefix, s = 0, ns = -inf, v_s = v_ns = 0, context root, n-gram start marker
 __device__ __forceinline__ void cp_put_start(CpHyps& H) {
-    cp_put(H, nullptr, 0, 0, 0, 0.0, -INFINITY, 0.0, 0.0, 0.0, 0, 0, -1, -1, 0, BEAM_HASH0, 0ull, -1, 0, -1, -1, 0, false);
+    cp_put<true>(H, nullptr, 0, 0, 0, 0.0, -INFINITY, 0.0, 0.0, 0.0, 0, 0.0, NG_START, 0, -1, -1, 0, BEAM_HASH0, 0ull, -1, 0, -1, -1, 0, false);
 }
 
 // One frame of the search for the whole workgroup (CP_NT threads, four barriers): frame t of the utterance, whose row the caller
 // holds in (v0, v1); next_row (or nullptr) is prefetched into them.  stride: arena nodes per frame.  nh: hypotheses before / after.
-__device__ __forceinline__ void cp_frame(CpHyps& H, CpWork& W, const CpGraph& g, int2* pa, int2* ta, const float* next_row, int t, int stride,
+template <bool NG>
+__device__ __forceinline__ void cp_frame(CpHyps& H, CpWork& W, const CpGraph& g, const NgTables& ng, int2* pa, int2* ta, const float* next_row, int t, int stride,
                                          int beam, int V, int blank, int& nh, float& v0, float& v1) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const bool graph = g.fail != nullptr;
@@ -191,10 +201,10 @@ __device__ __forceinline__ void cp_frame(CpHyps& H, CpWork& W, const CpGraph& g,
     __syncthreads();
 
     // ---- expansion: the entry "P_j unchanged" (thread j) ---------------------------------------------------------------------
-    int keyU = CP_NOKEY, Ucst = 0, Uts = -1, Utls = 0, Utnp = -1, Utln = 0;
+    int keyU = CP_NOKEY, Ucst = 0, Ulst = NG_START, Uts = -1, Utls = 0, Utnp = -1, Utln = 0;
     int Unode = 0, Upnode = -1, Ulast = -1, Uplen = 0;
     unsigned long long Uhash = 0ull, Uphash = 0ull, Nphash = 0ull;
-    double Us = -INFINITY, Uns = -INFINITY, Uvs = -INFINITY, Uvns = -INFINITY, Uctp = -INFINITY, Ucs = 0.0, totU = 0.0;
+    double Us = -INFINITY, Uns = -INFINITY, Uvs = -INFINITY, Uvns = -INFINITY, Uctp = -INFINITY, Ucs = 0.0, Uls = 0.0, totU = 0.0;
     bool Uhas = false, Unew = false;
     if (tid < nh) {
         const int j = tid;
@@ -220,6 +230,11 @@ __device__ __forceinline__ void cp_frame(CpHyps& H, CpWork& W, const CpGraph& g,
                     Ucs += cg_step(g.fail, g.off, g.ctok, g.cid, g.tscore, g.nscore, g.oscore, H.cst[i], u, &nx);
                     Ucst = nx;
                 }
+                if (NG) {
+                    int nx;
+                    Uls = H.ls[i] + ng_step(ng, H.lst[i], u, &nx);
+                    Ulst = nx;
+                }
             }
         };
         for (int r = 0; r < beam; ++r) {
@@ -230,7 +245,7 @@ __device__ __forceinline__ void cp_frame(CpHyps& H, CpWork& W, const CpGraph& g,
                 Us = prefix_log_add(Us, H.score[j] + pr);
                 Uvs = H.vit[j] + pr;
                 Uts = H.tn[j]; Utls = H.tl[j];
-                if (!Uhas) { Uhas = true; Ucs = H.cs[j]; Ucst = H.cst[j]; }
+                if (!Uhas) { Uhas = true; Ucs = H.cs[j]; Ucst = H.cst[j]; Uls = H.ls[j]; Ulst = H.lst[j]; }
             } else if (u == Ulast) {
                 if (par >= 0 && par < j) ext(r, par, u, pr);
                 if (keyU == CP_NOKEY) keyU = (r * CP_MAX_BEAM + j) * 2;          // :172-186
@@ -242,17 +257,18 @@ __device__ __forceinline__ void cp_frame(CpHyps& H, CpWork& W, const CpGraph& g,
                         if (H.tln[j] > 0) { Unew = true; Utnp = H.tnp[j]; Utln = H.tln[j]; }   // times_ns[-1] = t
                     }
                 }
-                if (!Uhas) { Uhas = true; Ucs = H.cs[j]; Ucst = H.cst[j]; }
+                if (!Uhas) { Uhas = true; Ucs = H.cs[j]; Ucst = H.cst[j]; Uls = H.ls[j]; Ulst = H.lst[j]; }
                 if (par > j) ext(r, par, u, pr);
             }
         }
         totU = prefix_log_add(Us, Uns) + Ucs;
+        if (NG) totU += Uls;
     }
     if (tid < CP_MAX_BEAM) { W.e_key[tid] = keyU; W.e_tot[tid] = totU; }
 
     // ---- expansion: the entry "P_i + top[r]" (thread i * beam + r) unless that prefix is live ------------------------------------
-    int keyN = CP_NOKEY, Ncst = 0, Ntnp = -1, Ntln = 0, Npnode = 0, Nlast = 0, Nplen = 0;
-    double Nns = -INFINITY, Nvns = -INFINITY, Ncs = 0.0, totN = 0.0;
+    int keyN = CP_NOKEY, Ncst = 0, Nlst = NG_START, Ntnp = -1, Ntln = 0, Npnode = 0, Nlast = 0, Nplen = 0;
+    double Nns = -INFINITY, Nvns = -INFINITY, Ncs = 0.0, Nls = 0.0, totN = 0.0;
     bool Nnew = false;
     if (tid < nh * beam) {
         const int i = tid / beam, r = tid - i * beam, u = W.top_tok[r];
@@ -272,8 +288,14 @@ __device__ __forceinline__ void cp_frame(CpHyps& H, CpWork& W, const CpGraph& g,
                 Ncs += cg_step(g.fail, g.off, g.ctok, g.cid, g.tscore, g.nscore, g.oscore, H.cst[i], u, &nx);
                 Ncst = nx;
             }
+            if (NG) {
+                int nx;
+                Nls = H.ls[i] + ng_step(ng, H.lst[i], u, &nx);
+                Nlst = nx;
+            }
             Nlast = u; Nplen = H.plen[i] + 1;
             totN = prefix_log_add(-INFINITY, Nns) + Ncs;
+            if (NG) totN += Nls;
         }
         W.e_key[CP_MAX_BEAM + tid] = keyN;
         W.e_tot[CP_MAX_BEAM + tid] = totN;
@@ -292,11 +314,11 @@ __device__ __forceinline__ void cp_frame(CpHyps& H, CpWork& W, const CpGraph& g,
         rankN += (tt > totN) | ((tt == totN) & (k < keyN));
     }
     if (keyU != CP_NOKEY && rankU < beam)
-        cp_put(H, ta, stride, rankU, t, Us, Uns, Uvs, Uvns, Ucs, Ucst, Unode, Upnode, Ulast, Uplen, Uhash, Uphash, Uts, Utls, -1, Utnp, Utln, Unew);   // a fresh times_ns is []
+        cp_put<NG>(H, ta, stride, rankU, t, Us, Uns, Uvs, Uvns, Ucs, Ucst, Uls, Ulst, Unode, Upnode, Ulast, Uplen, Uhash, Uphash, Uts, Utls, -1, Utnp, Utln, Unew);   // a fresh times_ns is []
     if (keyN != CP_NOKEY && rankN < beam) {
         const int node = 1 + t * stride + rankN;
         pa[node] = make_int2(Npnode, Nlast);
-        cp_put(H, ta, stride, rankN, t, -INFINITY, Nns, -INFINITY, Nvns, Ncs, Ncst, node, Npnode, Nlast, Nplen, beam_hash_step(Nphash, Nlast), Nphash, -1, 0, -1, Ntnp,
+        cp_put<NG>(H, ta, stride, rankN, t, -INFINITY, Nns, -INFINITY, Nvns, Ncs, Ncst, Nls, Nlst, node, Npnode, Nlast, Nplen, beam_hash_step(Nphash, Nlast), Nphash, -1, 0, -1, Ntnp,
                Ntln, Nnew);
     }
     nh = nact < beam ? nact : beam;
@@ -305,18 +327,30 @@ __device__ __forceinline__ void cp_frame(CpHyps& H, CpWork& W, const CpGraph& g,
 
 // Row b of the packed result from the nh hypotheses in H (whole workgroup, CP_NT threads): zero fill, then scores and tokens on one
 // wave and times on another.  fin_nscore != nullptr: finalize (context_graph.py:264) REPLACES the context score (search.py:229-231).
-__device__ __forceinline__ void cp_pack(const CpHyps& H, int nh, const int2* pa, const int2* ta, const double* fin_nscore, const CpOutP& o, int b,
-                                        int beam, int lcap) {
+// NG: the score carries the n-gram score, with the end term when `final`.
+template <bool NG>
+__device__ __forceinline__ void cp_pack(const CpHyps& H, int nh, const int2* pa, const int2* ta, const double* fin_nscore, const NgTables& ng, bool final,
+                                        const CpOutP& o, int b, int beam, int lcap) {
     const int tid = threadIdx.x;
     const size_t r0 = (size_t)b * beam;
     for (int q = tid; q < beam * lcap; q += CP_NT) { o.tok[r0 * lcap + q] = 0; o.time[r0 * lcap + q] = 0; }
-    if (tid < beam) { o.len[r0 + tid] = 0; o.sc[r0 + tid] = 0.0; o.cs[r0 + tid] = 0.0; }
+    if (tid < beam) {
+        o.len[r0 + tid] = 0; o.sc[r0 + tid] = 0.0; o.cs[r0 + tid] = 0.0;
+        if (NG && o.ls) o.ls[r0 + tid] = 0.0;
+    }
     if (tid == 0) o.nh[b] = nh;
     __syncthreads();
     if (tid < nh) {                                                  // scores and tokens
         const int a = tid, n = H.plen[a];
         const double cs = fin_nscore ? -fin_nscore[H.cst[a]] : H.cs[a];
-        o.sc[r0 + a] = H.score[a] + cs;
+        double sc = H.score[a] + cs;
+        if (NG) {
+            double ls = H.ls[a];
+            if (final) ls += ng_eos(ng, H.lst[a]);
+            sc += ls;
+            if (o.ls) o.ls[r0 + a] = ls;
+        }
+        o.sc[r0 + a] = sc;
         o.cs[r0 + a] = cs;
         o.len[r0 + a] = n;
         int node = H.node[a];
@@ -336,14 +370,18 @@ __device__ __forceinline__ void cp_pack(const CpHyps& H, int nh, const int2* pa,
     }
 }
 
-// element `i` of every array of a hypothesis record (threads i < CP_MAX_BEAM copy a record between LDS and device memory)
+// element `i` of every array of a hypothesis record (threads i < CP_MAX_BEAM copy a record between LDS and device memory); the
+// n-gram pair only where a model is fused or the record is made
+template <bool NG>
 __device__ __forceinline__ void cp_hyps_copy(CpHyps& d, const CpHyps& s, int i) {
+    if (NG) { d.ls[i] = s.ls[i]; d.lst[i] = s.lst[i]; }
     d.s[i] = s.s[i]; d.ns[i] = s.ns[i]; d.vs[i] = s.vs[i]; d.vns[i] = s.vns[i]; d.cs[i] = s.cs[i]; d.score[i] = s.score[i]; d.vit[i] = s.vit[i];
     d.hash[i] = s.hash[i]; d.phash[i] = s.phash[i];
     d.cst[i] = s.cst[i]; d.node[i] = s.node[i]; d.pnode[i] = s.pnode[i]; d.last[i] = s.last[i]; d.plen[i] = s.plen[i];
     d.tns[i] = s.tns[i]; d.tls[i] = s.tls[i]; d.tnn[i] = s.tnn[i]; d.tnp[i] = s.tnp[i]; d.tln[i] = s.tln[i]; d.tn[i] = s.tn[i]; d.tl[i] = s.tl[i];
 }
 
+template <bool NG>
 __global__ __launch_bounds__(CP_NT) void ctc_prefix_search(CtcPrefixP p) {
     __shared__ CpHyps H;
     __shared__ CpWork W;
@@ -363,13 +401,14 @@ __global__ __launch_bounds__(CP_NT) void ctc_prefix_search(CtcPrefixP p) {
     }
     __syncthreads();
     for (int t = 0; t < len; ++t)
-        cp_frame(H, W, p.g, pa, ta, t + 1 < len ? rows + (size_t)(t + 1) * V : nullptr, t, beam, beam, V, p.blank, nh, v0, v1);
+        cp_frame<NG>(H, W, p.g, p.ng, pa, ta, t + 1 < len ? rows + (size_t)(t + 1) * V : nullptr, t, beam, beam, V, p.blank, nh, v0, v1);
     // ---- epilogue: this utterance's rows of the packed result -----------------------------------------------------------------------
-    cp_pack(H, nh, pa, ta, p.g.fail ? p.g.nscore : nullptr, p.o, b, beam, p.lcap);
+    cp_pack<NG>(H, nh, pa, ta, p.g.fail ? p.g.nscore : nullptr, p.ng, true, p.o, b, beam, p.lcap);
 }
 
 // The resumable form: workgroup i continues the search of slot slots[i] over the call's t rows, frames [t0[i], t0[i] + t) of its
 // utterance.  The prefetch of the next row stays inside those rows.  No epilogue (ctc_prefix_pack).
+template <bool NG>
 __global__ __launch_bounds__(CP_NT) void ctc_prefix_search_pool(CtcPrefixPoolP p) {
     __shared__ CpHyps H;
     __shared__ CpWork W;
@@ -380,26 +419,27 @@ __global__ __launch_bounds__(CP_NT) void ctc_prefix_search_pool(CtcPrefixPoolP p
     const float* rows = p.lp + (size_t)i * p.t * V;
     CpSlotState* st = p.state + slot;
 
-    if (tid < CP_MAX_BEAM) cp_hyps_copy(H, st->h, tid);
+    if (tid < CP_MAX_BEAM) cp_hyps_copy<NG>(H, st->h, tid);
     int nh = st->nh;
     float v0 = 0.f, v1 = 0.f;
     if (tid < V) v0 = rows[tid];
     if (tid + CP_NT < V) v1 = rows[tid + CP_NT];
     __syncthreads();
     for (int f = 0; f < p.t; ++f)
-        cp_frame(H, W, p.g, pa, ta, f + 1 < p.t ? rows + (size_t)(f + 1) * V : nullptr, t0 + f, CP_MAX_BEAM, p.beam, V, p.blank, nh, v0, v1);
-    if (tid < CP_MAX_BEAM) cp_hyps_copy(st->h, H, tid);
+        cp_frame<NG>(H, W, p.g, p.ng, pa, ta, f + 1 < p.t ? rows + (size_t)(f + 1) * V : nullptr, t0 + f, CP_MAX_BEAM, p.beam, V, p.blank, nh, v0, v1);
+    if (tid < CP_MAX_BEAM) cp_hyps_copy<NG>(st->h, H, tid);
     if (tid == 0) st->nh = nh;
 }
 
 // one slot's hypotheses as they stand, in the layout of the one-launch search for B = 1; reads only
+template <bool NG>
 __global__ __launch_bounds__(CP_NT) void ctc_prefix_pack(CtcPrefixPackP p) {
     __shared__ CpHyps H;
     const int tid = threadIdx.x;
-    if (tid < CP_MAX_BEAM) cp_hyps_copy(H, p.state->h, tid);
+    if (tid < CP_MAX_BEAM) cp_hyps_copy<NG>(H, p.state->h, tid);
     const int nh = p.state->nh;
     __syncthreads();
-    cp_pack(H, nh, p.pa, p.ta, p.fin_nscore, p.o, 0, p.beam, p.lcap);
+    cp_pack<NG>(H, nh, p.pa, p.ta, p.fin_nscore, p.ng, p.final != 0, p.o, 0, p.beam, p.lcap);
 }
 
 // the start hypothesis in the record *st, every other entry of it zero; z: an LDS record of the workgroup (>= CP_MAX_BEAM threads,
@@ -410,7 +450,7 @@ __device__ __forceinline__ void ctc_prefix_slot_start(CpSlotState* st, CpSlotSta
     __syncthreads();
     if (tid == 0) { cp_put_start(z.h); z.nh = 1; }
     __syncthreads();
-    if (tid < CP_MAX_BEAM) cp_hyps_copy(st->h, z.h, tid);
+    if (tid < CP_MAX_BEAM) cp_hyps_copy<true>(st->h, z.h, tid);
     if (tid == 0) { st->nh = z.nh; st->pad = 0; }
 }
 

@@ -81,6 +81,17 @@ SIGNATURES = {
     "rnnt_pool_ctc_prefix_logprobs": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "rnnt_pool_chunk_ctc_prefix": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32p, c_vp]),
     "rnnt_stream_get_ctc_prefix": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32p, c_vp]),
+    "rnnt_ngram_set": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, ctypes.c_double, ctypes.c_double, ctypes.c_double]),
+    "rnnt_ngram_walk_host": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp,
+                                     ctypes.POINTER(ctypes.c_double), c_i32p]),
+    "rnnt_ngram_score": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "rnnt_ctc_prefix_beam_logprobs_ngram": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rnnt_ctc_prefix_beam_decode_ngram": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rnnt_ctc_prefix_beam_ngram_host": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, ctypes.c_double, c_i32, c_vp, c_vp, c_vp, c_vp,
+                                                ctypes.c_double, ctypes.c_double, ctypes.c_double, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rnnt_pool_ctc_prefix_logprobs_ngram": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "rnnt_pool_chunk_ctc_prefix_ngram": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32p, c_vp]),
+    "rnnt_stream_get_ctc_prefix_ngram": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32p, c_vp]),
     "rnnt_stream_prefix_reset": (c_i32, [c_vp, c_i32, c_vp]),
     "rnnt_pool_prefix_frames": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, ctypes.c_float, ctypes.c_float, c_vp]),
     "rnnt_pool_chunk_prefix": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, ctypes.c_float, ctypes.c_float, c_i32p, c_vp]),
@@ -333,6 +344,61 @@ def ctc_prefix_beam_host(lp, enc_lens, blank, beam_size, phrases=None, context_s
     if rc != 0:
         raise RnntError(f"rnnt_ctc_prefix_beam_host: bad argument (status {rc})", rc)
     return (_ctc_prefix_hyps(out), out) if raw else _ctc_prefix_hyps(out)
+
+
+def _ngram_args(ngram):
+    """An NgramLM (or None) -> the model arguments of the n-gram entry points: (n, lens int32, tokens int32, logp f64, bow f64,
+    lm_weight, length_bonus, unk_logp), with the arrays kept alive by the tuple."""
+    grams = list(ngram.ngrams) if ngram is not None else []
+    lens = np.array([len(g[0]) for g in grams] or [0], np.int32)
+    toks = np.array([int(t) for g in grams for t in g[0]] or [0], np.int32)
+    logp = np.array([float(g[1]) for g in grams] or [0.0], np.float64)
+    bow = np.array([float(g[2]) for g in grams] or [0.0], np.float64)
+    w, lb, unk = (ngram.lm_weight, ngram.length_bonus, ngram.unk_logp) if ngram is not None else (0.0, 0.0, 0.0)
+    return len(grams), lens, toks, logp, bow, float(w), float(lb), float(unk)
+
+
+def _ngram_call_args(a):
+    return (a[0], _np_ptr(a[1]), _np_ptr(a[2]), _np_ptr(a[3]), _np_ptr(a[4]), a[5], a[6], a[7])
+
+
+def ngram_walk_host(ngram, vocab, blank, tokens):
+    """rnnt_ngram_walk_host (no context, no GPU): feed `tokens` through the model's step from its start state -> (step scores float64
+    [n], node ids int32 [n], the end term of the last state, the model's node count)."""
+    a = _ngram_args(ngram)
+    tk = np.array(list(tokens) or [0], np.int32)
+    m = len(tokens)
+    sc, st, eos, nn = np.zeros(max(m, 1), np.float64), np.zeros(max(m, 1), np.int32), ctypes.c_double(0.0), c_i32(0)
+    rc = load().rnnt_ngram_walk_host(*_ngram_call_args(a), vocab, blank, m, _np_ptr(tk), _np_ptr(sc), _np_ptr(st), ctypes.byref(eos), ctypes.byref(nn))
+    if rc != 0:
+        raise RnntError(f"rnnt_ngram_walk_host: bad argument (status {rc})", rc)
+    return sc[:m], st[:m], eos.value, nn.value
+
+
+def ctc_prefix_beam_ngram_host(lp, enc_lens, blank, beam_size, phrases=None, context_score=0.0, ngram=None, raw=False):
+    """rnnt_ctc_prefix_beam_ngram_host (no context, no GPU): ctc_prefix_beam_host with the NgramLM `ngram` fused.  Per utterance
+    [(tokens, score, times, context score, n-gram score)]; raw: also the result arrays, the n-gram scores last."""
+    lp = np.ascontiguousarray(lp, np.float32)
+    B, T, V = lp.shape
+    el = np.ascontiguousarray(enc_lens, np.int32)
+    assert el.size == B
+    n, pl, pt = _phrase_args(phrases)
+    a = _ngram_args(ngram)
+    cap = max(int(el.max(initial=0)), 1)
+    out = _ctc_prefix_out(B, beam_size, cap)
+    ls = np.zeros_like(out[4])
+    rc = load().rnnt_ctc_prefix_beam_ngram_host(_np_ptr(lp), _np_ptr(el), B, T, V, blank, beam_size, n, _np_ptr(pl), _np_ptr(pt), float(context_score),
+                                                *_ngram_call_args(a), cap, *[_np_ptr(x) for x in out], _np_ptr(ls))
+    if rc != 0:
+        raise RnntError(f"rnnt_ctc_prefix_beam_ngram_host: bad argument (status {rc})", rc)
+    hyps = _ctc_prefix_ngram_hyps(out, ls)
+    return (hyps, out + (ls,)) if raw else hyps
+
+
+def _ctc_prefix_ngram_hyps(out, ls):
+    """_ctc_prefix_hyps with the n-gram score as a fifth element."""
+    nh = out[0]
+    return [[h + (float(ls[b, i]),) for i, h in enumerate(row)] for b, row in zip(range(len(nh)), _ctc_prefix_hyps(out))]
 
 
 def _endpoint_config(cfg):
@@ -722,6 +788,70 @@ class RnntEngine:
         """rnnt_ctc_prefix_beam_decode: the same over encoder frames [B, T, 256] (rnnt_ctc_logprobs first)."""
         return self._ctc_prefix(self.lib.rnnt_ctc_prefix_beam_decode, "rnnt_ctc_prefix_beam_decode", enc_ptr, enc_lens, B, T, beam_size, use_context,
                                 raw, stream)
+
+    # ---- n-gram shallow fusion in the CTC prefix beam search -----------------------------------------------
+    def ngram_set(self, ngram):
+        """rnnt_ngram_set: build and upload the NgramLM `ngram`; None clears it."""
+        a = _ngram_args(ngram)
+        self._chk(self.lib.rnnt_ngram_set(self.ctx, *_ngram_call_args(a)), "rnnt_ngram_set")
+
+    def ngram_score(self, seqs, with_eos=True, stream=None):
+        """rnnt_ngram_score: the token sequences `seqs` scored by the model that is set, one launch -> (step scores float64
+        [n, cap], totals float64 [n]); cap is the longest length (at least 1)."""
+        n, cap = len(seqs), max([len(q) for q in seqs] + [1])
+        lens, toks = np.array([len(q) for q in seqs] or [0], np.int32), np.zeros((max(n, 1), cap), np.int32)
+        for i, q in enumerate(seqs):
+            toks[i, :len(q)] = q
+        step, tot = np.zeros((max(n, 1), cap), np.float64), np.zeros(max(n, 1), np.float64)
+        self._chk(self.lib.rnnt_ngram_score(self.ctx, n, _np_ptr(lens), _np_ptr(toks), cap, 1 if with_eos else 0, _np_ptr(step), _np_ptr(tot), stream),
+                  "rnnt_ngram_score")
+        return step[:n], tot[:n]
+
+    def _ctc_prefix_ngram(self, fn, name, dev_ptr, enc_lens, B, T, beam_size, use_context, use_ngram, raw, stream):
+        el = np.ascontiguousarray(enc_lens, np.int32)
+        assert el.size == B
+        out = _ctc_prefix_out(B, beam_size, max(int(el.max(initial=0)), 1))
+        ls = np.zeros_like(out[4])
+        self._chk(fn(self.ctx, dev_ptr, _np_ptr(el), B, T, beam_size, 1 if use_context else 0, 1 if use_ngram else 0, out[2].shape[2],
+                     *[_np_ptr(a) for a in out], _np_ptr(ls), stream), name)
+        hyps = _ctc_prefix_ngram_hyps(out, ls)
+        return (hyps, out + (ls,)) if raw else hyps
+
+    def ctc_prefix_beam_logprobs_ngram(self, lp_ptr, enc_lens, B, T, beam_size=10, use_context=False, use_ngram=True, raw=False, stream=None):
+        """rnnt_ctc_prefix_beam_logprobs_ngram: ctc_prefix_beam_logprobs with the model of ngram_set fused when use_ngram.  Per
+        utterance [(tokens, score, times, context score, n-gram score)] in the search's order (not re-sorted after the end term)."""
+        return self._ctc_prefix_ngram(self.lib.rnnt_ctc_prefix_beam_logprobs_ngram, "rnnt_ctc_prefix_beam_logprobs_ngram", lp_ptr, enc_lens, B, T, beam_size,
+                                      use_context, use_ngram, raw, stream)
+
+    def ctc_prefix_beam_decode_ngram(self, enc_ptr, enc_lens, B, T, beam_size=10, use_context=False, use_ngram=True, raw=False, stream=None):
+        """rnnt_ctc_prefix_beam_decode_ngram: the same over encoder frames [B, T, 256] (rnnt_ctc_logprobs first)."""
+        return self._ctc_prefix_ngram(self.lib.rnnt_ctc_prefix_beam_decode_ngram, "rnnt_ctc_prefix_beam_decode_ngram", enc_ptr, enc_lens, B, T, beam_size,
+                                      use_context, use_ngram, raw, stream)
+
+    def pool_ctc_prefix_logprobs_ngram(self, slots, lp_ptr, t, beam_size=10, use_context=False, use_ngram=True, stream=None):
+        """rnnt_pool_ctc_prefix_logprobs_ngram: pool_ctc_prefix_logprobs for searches that fuse the model of ngram_set (use_ngram)."""
+        a = np.ascontiguousarray(slots, np.int32)
+        assert a.ndim == 1
+        self._chk(self.lib.rnnt_pool_ctc_prefix_logprobs_ngram(self.ctx, a.size, _np_ptr(a), lp_ptr, t, beam_size, 1 if use_context else 0,
+                                                               1 if use_ngram else 0, stream), "rnnt_pool_ctc_prefix_logprobs_ngram")
+
+    def pool_chunk_ctc_prefix_ngram(self, slots, fbank_ptr, chunk_frames, offsets, required, beam_size=10, use_context=False, use_ngram=True, stream=None):
+        """rnnt_pool_chunk_ctc_prefix_ngram: pool_chunk_ctc_prefix for searches that fuse the model of ngram_set.  Returns t'."""
+        return self._pool_chunk("rnnt_pool_chunk_ctc_prefix_ngram", slots, fbank_ptr, chunk_frames, offsets, required,
+                                (beam_size, 1 if use_context else 0, 1 if use_ngram else 0), stream)
+
+    def stream_ctc_prefix_ngram(self, slot, final=False, raw=False, stream=None):
+        """rnnt_stream_get_ctc_prefix_ngram: stream_ctc_prefix with the n-gram score as a fifth element of every hypothesis (the
+        running one, or with final the one with the end term; zero for a slot that fuses no model)."""
+        frames, need = c_i32(0), c_i32(0)
+        self._chk(self.lib.rnnt_stream_get_ctc_prefix_ngram(self.ctx, slot, 0, 0, 0, ctypes.byref(need), None, None, None, None, None, None,
+                                                            ctypes.byref(frames), stream), "rnnt_stream_get_ctc_prefix_ngram")
+        out = _ctc_prefix_out(1, need.value, max(frames.value, 1))
+        ls = np.zeros_like(out[4])
+        self._chk(self.lib.rnnt_stream_get_ctc_prefix_ngram(self.ctx, slot, 1 if final else 0, need.value, out[2].shape[2], *[_np_ptr(a) for a in out],
+                                                            _np_ptr(ls), ctypes.byref(frames), stream), "rnnt_stream_get_ctc_prefix_ngram")
+        hyps = _ctc_prefix_ngram_hyps(out, ls)[0]
+        return (hyps, out + (ls,), frames.value) if raw else hyps
 
     # ---- the same search per slot of the stream pool ----------------------------------------------------
     def stream_ctc_prefix_reset(self, slot=-1, stream=None):

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from .lib import ERR_ARG, ERR_SHAPE, ERR_STATE, RnntEngine, RnntError, pack_nbest, rescore_select
+from .ngram import NgramLM
 
 
 def _stream_ptr():
@@ -200,6 +201,7 @@ class OnlineRNNTModel:
         self.numerics = numerics          # None -> $RNNT_NUMERICS or "fp32" (lib.numerics_id)
         self._loaded = False
         self._context_bias = None         # the ContextBias whose graph the context holds (ctc_prefix_beam_search, prefix_beam_search_batch)
+        self._ngram_lm = None             # the NgramLM whose model the context holds (ctc_prefix_beam_search, rescoring_batch)
         self._chunks_done = None          # None = reset_streaming_cache not called yet (attributes are None, :138-143)
         self._tok_count = 0
         self.streaming_beam_hypotheses = None
@@ -629,7 +631,13 @@ class OnlineRNNTModel:
             self._engine.context_set(context.phrases if context is not None else [], context.context_score if context is not None else 0.0)
             self._context_bias = context
 
-    def ctc_prefix_beam_search(self, audios: torch.Tensor, audio_lens: torch.Tensor, beam_size: int = 10, context: Optional["ContextBias"] = None):
+    def _set_ngram(self, ngram: "NgramLM"):
+        if ngram is not self._ngram_lm:                             # the model lives in the context until another one replaces it
+            self._engine.ngram_set(ngram)
+            self._ngram_lm = ngram
+
+    def ctc_prefix_beam_search(self, audios: torch.Tensor, audio_lens: torch.Tensor, beam_size: int = 10, context: Optional["ContextBias"] = None,
+                               ngram: Optional["NgramLM"] = None):
         """WeNet's ctc_prefix_beam_search (wenet/transformer/search.py:125-247) on the CTC head over the deterministic full-context
         encoder, for a padded batch audios [B, T, 80]: one rnnt_encoder_full call and one rnnt_ctc_prefix_beam_decode call (the CTC
         log-probabilities, then ONE launch that walks every utterance's own valid frames).  context: a ContextBias whose phrases
@@ -637,7 +645,9 @@ class OnlineRNNTModel:
         lower index first (torch.topk leaves that order open).
         Returns per utterance [(tokens, score, times)] in the reference's order (nbest, nbest_scores, nbest_times): best first by
         score + running context score; with a context the returned scores carry finalize's correction and need not descend.
-        Invalidates the streaming state."""
+        ngram: an NgramLM fused into the search (rnnt_ctc_prefix_beam_decode_ngram): the second prune sees score + context score +
+        n-gram score, the end term is added after the last frame, and the rows come back stably sorted by that final score,
+        descending.  Invalidates the streaming state."""
         self._require_loaded()
         B, T = audios.size(0), audios.size(1)
         x = audios.to(self.device, torch.float32).contiguous()
@@ -650,13 +660,17 @@ class OnlineRNNTModel:
         n1 = np.maximum(0, (np.minimum(lens, T) - 1) // 2)         # valid frames after masks[:, :, 2::2][:, :, 2::2]
         enc_lens = np.maximum(0, (n1 - 1) // 2).astype(np.int32)
         self._set_context(context)
+        if ngram is not None:
+            self._set_ngram(ngram)
+            hyps = self._engine.ctc_prefix_beam_decode_ngram(enc.data_ptr(), enc_lens, B, tq, beam_size, context is not None, True, False, s)
+            return [sorted(((h[0], h[1], h[2]) for h in row), key=lambda h: h[1], reverse=True) for row in hyps]
         hyps = self._engine.ctc_prefix_beam_decode(enc.data_ptr(), enc_lens, B, tq, beam_size, context is not None, False, s)
         return [[(tok, score, times) for tok, score, times, _ in row] for row in hyps]
 
     # ---- two-pass decoding (wenet/transducer/transducer.py:261-395) -------------------------------------------------
     def rescoring_batch(self, audios: torch.Tensor, audio_lens: torch.Tensor, beam_size: int = 10, ctc_weight: float = 0.3,
                         transducer_weight: float = 0.7, beam_search_type: str = "ctc", context: Optional["ContextBias"] = None,
-                        search_ctc_weight: float = 1.0, search_transducer_weight: float = 0.0):
+                        search_ctc_weight: float = 1.0, search_transducer_weight: float = 0.0, ngram: Optional["NgramLM"] = None):
         """Transducer rescoring of n-best for a padded batch audios [B, T, 80]: one full-context encoder call, one search call
         (beam_search_type "ctc": rnnt_ctc_prefix_beam_decode, biased by `context` when given; "transducer":
         rnnt_prefix_beam_decode with the two search weights over each utterance's valid frames, the leading blank dropped, :327;
@@ -665,11 +679,19 @@ class OnlineRNNTModel:
         total = first_score * ctc_weight + td_score * transducer_weight (:388-390 with attn_weight = 0; the defaults are the
         fusion weights of the reference's beam_search, :223-224).  beam_size <= 16.
         Returns per utterance (best_index, [(tokens, first_score, td_score, total)]) in the first pass's order; an utterance with
-        no valid encoder frame comes back with td_score = nan and best_index = 0.  Invalidates the streaming state."""
+        no valid encoder frame comes back with td_score = nan and best_index = 0.  Invalidates the streaming state.
+        ngram (beam_search_type "ctc" only): the first pass fuses that NgramLM; its totals are the first-pass scores."""
         check_rescoring_args(beam_search_type=beam_search_type)
+        if ngram is not None and beam_search_type != "ctc":
+            raise ValueError(f"ngram fuses into the CTC prefix search only, not beam_search_type={beam_search_type!r}")
         enc, enc_lens, _, _ = self._encode_for_scoring(audios, audio_lens, torch.zeros(audios.size(0), 0), torch.zeros(audios.size(0)))
         B, tq, s = enc.size(0), enc.size(1), _stream_ptr()
-        if beam_search_type == "ctc":
+        if beam_search_type == "ctc" and ngram is not None:
+            self._set_context(context)
+            self._set_ngram(ngram)
+            first = [[(h[0], h[1]) for h in row]
+                     for row in self._engine.ctc_prefix_beam_decode_ngram(enc.data_ptr(), enc_lens, B, tq, beam_size, context is not None, True, False, s)]
+        elif beam_search_type == "ctc":
             self._set_context(context)
             first = [[(tok, score) for tok, score, _, _ in row]
                      for row in self._engine.ctc_prefix_beam_decode(enc.data_ptr(), enc_lens, B, tq, beam_size, context is not None, False, s)]
@@ -951,10 +973,10 @@ class StreamingBatch:
         return self.engine.tokens(_stream_ptr())
 
 
-_POOL_KINDS = ("greedy", "beam", "ctc_prefix", "prefix")
+_POOL_KINDS = ("greedy", "beam", "ctc_prefix", "prefix", "ctc_prefix_ngram")
 
 
-def pool_plan(queue, offsets, beams=None, ctc_prefix=None, prefix=None):
+def pool_plan(queue, offsets, beams=None, ctc_prefix=None, prefix=None, ngram=None):
     """The library calls of one StreamPool.step as a pure function (no GPU, no tensors).
 
     queue: [(slot, length)] in feed order, several entries per slot allowed; offsets: {slot: encoder offset so far}.
@@ -982,10 +1004,16 @@ def pool_plan(queue, offsets, beams=None, ctc_prefix=None, prefix=None):
     kind is as above with weights None.  One (length, kind, beam size, use_context, weights) class per call -- slots with different
     weights never share one -- in ascending order inside a round.  A slot listed in prefix is looked up in neither ctc_prefix nor beams.
     A fourth element of a prefix entry is its use_context (hot-word biasing, an rnnt_pool_chunk_prefix_ctx call): biased and unbiased
-    prefix slots of one length go in two calls."""
+    prefix slots of one length go in two calls.
+
+    ngram: the slots among ctc_prefix whose search fuses the n-gram model (None or empty: none, and the results above).  Their calls
+    have kind "ctc_prefix_ngram" (an rnnt_pool_chunk_ctc_prefix_ngram call), ordered after "prefix": such slots never share a call
+    with the other CTC prefix slots."""
     offs = dict(offsets)
 
     def klass(slot, length):
+        if ngram and ctc_prefix is not None and slot in ngram and slot in ctc_prefix and not (prefix is not None and slot in prefix):
+            return int(length), 4, int(ctc_prefix[slot][0]), int(bool(ctc_prefix[slot][1])), 0.0, 0.0
         if prefix is not None and slot in prefix:
             return int(length), 3, int(prefix[slot][0]), int(bool(prefix[slot][3])) if len(prefix[slot]) > 3 else 0, float(prefix[slot][1]), float(prefix[slot][2])
         if ctc_prefix is not None and slot in ctc_prefix:
@@ -1164,6 +1192,7 @@ class StreamPool:
                 engine.load_state_dict(state_dict, numerics=numerics)
         self.engine = engine
         self._context: Optional[ContextBias] = None     # the ContextBias whose graph the context holds (it outlives reset())
+        self._ngram: Optional[NgramLM] = None           # likewise the NgramLM whose model the context holds
         self.reset()
 
     def reset(self):
@@ -1179,6 +1208,7 @@ class StreamPool:
         self._segments: Dict[int, List[Segment]] = {}   # what step() finished for them, until segments(slot) takes it
         self._seg: Dict[int, Tuple[int, int]] = {}      # (index, start_frame) of the open slots' current segment
         self._ctc: Dict[int, Tuple[int, Optional[ContextBias]]] = {}   # (beam, context) of the open CTC prefix slots
+        self._ctc_ngram: Dict[int, NgramLM] = {}        # the model of those among them that fuse one
         self._prefix: Dict[int, Tuple[int, float, float]] = {}   # (beam, ctc_weight, transducer_weight) of the open transducer prefix slots
         self._prefix_ctx: Dict[int, ContextBias] = {}   # the context of the biased ones among them
         self._queue: List[Tuple[int, torch.Tensor]] = []
@@ -1195,7 +1225,7 @@ class StreamPool:
 
     def open(self, beam_size: int = 0, ctc_prefix_beam: int = 0, context: Optional[ContextBias] = None, keep_frames: bool = False,
              prefix_beam: int = 0, ctc_weight: float = 0.3, transducer_weight: float = 0.7, prefix_context: Optional[ContextBias] = None,
-             endpoint: Optional[EndpointConfig] = None, on_endpoint: Optional[str] = None) -> int:
+             endpoint: Optional[EndpointConfig] = None, on_endpoint: Optional[str] = None, ngram: Optional[NgramLM] = None) -> int:
         """The lowest free slot, reset for a new utterance (reset_streaming_cache for that slot alone).  beam_size > 0: the slot's
         utterance is beam-searched with that beam (its hypotheses start as the one empty hypothesis); raises RnntError at once
         when this pool cannot do it.  ctc_prefix_beam > 0 (not together with beam_size): the slot's utterance runs the CTC prefix beam
@@ -1212,7 +1242,15 @@ class StreamPool:
         A config the library refuses takes no slot.
         on_endpoint: "keep" / "fresh" (needs endpoint): after its chunk calls step() reads the endpoints once and, for every such slot
         whose rule has fired, does what next_segment(slot, keep_encoder = on_endpoint == "keep") does; segments(slot) returns the
-        finished Segments.  None: the slot's utterance ends with close() or next_segment() only."""
+        finished Segments.  None: the slot's utterance ends with close() or next_segment() only.
+        ngram (needs ctc_prefix_beam): the slot's search fuses that NgramLM (rnnt_pool_chunk_ctc_prefix_ngram calls of their own).  The
+        pool holds one model at a time, with the graph's rule: a model other than the current one is uploaded (ngram_set) unless
+        another slot that fuses one is still open, which raises RnntError and takes no slot."""
+        if ngram is not None:
+            if not ctc_prefix_beam:
+                raise RnntError("stream pool: ngram needs ctc_prefix_beam")
+            if ngram is not self._ngram and self._ctc_ngram:
+                raise RnntError("stream pool: another n-gram model is in use by an open slot (one model per pool at a time)")
         if on_endpoint not in (None, "keep", "fresh"):
             raise RnntError(f"stream pool: on_endpoint {on_endpoint!r} is not None, 'keep' or 'fresh'")
         if on_endpoint is not None and endpoint is None:
@@ -1250,6 +1288,9 @@ class StreamPool:
         if graph is not None and graph is not self._context:       # before a slot is taken: the library may refuse the graph
             self.engine.context_set(graph.phrases, graph.context_score)
             self._context = graph
+        if ngram is not None and ngram is not self._ngram:         # likewise
+            self.engine.ngram_set(ngram)
+            self._ngram = ngram
         slot = self._free[0]
         self.engine.stream_open(slot, self._stream(None))
         if keep_frames:
@@ -1261,6 +1302,8 @@ class StreamPool:
         self._keep[slot] = bool(keep_frames)
         if ctc_prefix_beam:
             self._ctc[slot] = (int(ctc_prefix_beam), context)
+            if ngram is not None:
+                self._ctc_ngram[slot] = ngram
         if prefix_beam:
             self._prefix[slot] = (int(prefix_beam), float(ctc_weight), float(transducer_weight))
             if prefix_context is not None:
@@ -1363,7 +1406,8 @@ class StreamPool:
             return out
         calls, offs, index = pool_plan([(slot, c.size(0)) for slot, c in self._queue], self._offset, self._beam,
                                        {slot: (b, c is not None) for slot, (b, c) in self._ctc.items()},
-                                       {slot: v + (True,) if slot in self._prefix_ctx else v for slot, v in self._prefix.items()})
+                                       {slot: v + (True,) if slot in self._prefix_ctx else v for slot, v in self._prefix.items()},
+                                       set(self._ctc_ngram))
         rows: List[List[Optional[torch.Tensor]]] = [[None] * len(call[1]) for call in calls]
         for (slot, c), at in zip(self._queue, index):
             rows[at[0]][at[1]] = c
@@ -1375,6 +1419,9 @@ class StreamPool:
                 continue
             if kind == "prefix":
                 self.engine.pool_chunk_prefix(slots, x.data_ptr(), length, call_offs, call_offs, beam, weights[0], weights[1], self._stream(x))
+                continue
+            if kind == "ctc_prefix_ngram":
+                self.engine.pool_chunk_ctc_prefix_ngram(slots, x.data_ptr(), length, call_offs, call_offs, beam, use_context, True, self._stream(x))
                 continue
             if kind == "ctc_prefix":
                 self.engine.pool_chunk_ctc_prefix(slots, x.data_ptr(), length, call_offs, call_offs, beam, use_context, self._stream(x))
@@ -1460,6 +1507,8 @@ class StreamPool:
         (finalize's context score instead of the running one).  Reading changes nothing."""
         if slot not in self._ctc:
             raise RnntError(f"slot {slot} is not an open CTC prefix slot")
+        if slot in self._ctc_ngram:                     # the totals carry the n-gram score (final: with the end term)
+            return [(h[0], h[1], h[2]) for h in self.engine.stream_ctc_prefix_ngram(slot, final, stream=self._stream(None))]
         return [(tok, score, times) for tok, score, times, _ in self.engine.stream_ctc_prefix(slot, final, stream=self._stream(None))]
 
     def prefix_hyps(self, slot: int, final: bool = False, with_context_scores: bool = False):
@@ -1554,6 +1603,7 @@ class StreamPool:
         self._prefix.pop(slot, None)
         self._prefix_ctx.pop(slot, None)
         self._ctc.pop(slot, None)
+        self._ctc_ngram.pop(slot, None)
         del self._offset[slot], self._ntok[slot], self._beam[slot], self._seg[slot]
         self._free.append(slot)
         self._free.sort()

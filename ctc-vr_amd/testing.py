@@ -675,6 +675,177 @@ def ctc_prefix_beam_ref(lp, length, blank, beam_size, graph=None, stats=None, fi
     return out, prune_gap, top_gap
 
 
+# ---- back-off n-gram model fused in the CTC prefix beam search (semantics: include/rnnt_hip.h, rnnt_ngram_set) -------------------
+class ngram_ref:
+    """The automaton of rnnt_ngram_set over ngrams [(tokens, logp, bow), ...] in Python floats: a trie in list order (node i + 1 is
+    n-gram i, the root node 0; every n-gram's prefix must be listed before it), BOS = vocab, EOS = vocab + 1, fail[c] the node of the
+    longest proper suffix of c's n-gram that is listed (the root if none), and the prescaled values W = lm_weight * logp +
+    length_bonus (no bonus for an n-gram that ends in EOS), B = lm_weight * bow, U = lm_weight * unk_logp + length_bonus -- each one
+    multiplication then one addition.  step only adds, in the order the library adds."""
+
+    def __init__(self, ngrams, vocab, blank, lm_weight, length_bonus, unk_logp):
+        self.vocab, self.blank, self.bos, self.eos_tok = int(vocab), int(blank), int(vocab), int(vocab) + 1
+        lm_weight, length_bonus = float(lm_weight), float(length_bonus)
+        self.node = {(): 0}                                          # token string -> node
+        self.next, self.W, self.B, strings = [{}], [0.0], [0.0], [()]
+        self.has_eos = False
+        for toks, logp, bow in ngrams:
+            toks = tuple(int(t) for t in toks)
+            assert 1 <= len(toks) <= 8 and toks not in self.node and toks[:-1] in self.node, toks
+            assert all(0 <= t < vocab + 2 and t != blank for t in toks) and self.bos not in toks[1:] and self.eos_tok not in toks[:-1], toks
+            c = len(self.W)
+            self.node[toks] = c
+            self.next[self.node[toks[:-1]]][toks[-1]] = c
+            self.next.append({})
+            strings.append(toks)
+            w = lm_weight * float(logp)
+            self.W.append(w if toks[-1] == self.eos_tok else w + length_bonus)
+            self.B.append(lm_weight * float(bow))
+            self.has_eos = self.has_eos or toks[-1] == self.eos_tok
+        u = lm_weight * float(unk_logp)
+        self.U = u + length_bonus
+        self.fail = [0] * len(self.W)
+        for c, toks in enumerate(strings):
+            for i in range(1, len(toks)):
+                if toks[i:] in self.node:
+                    self.fail[c] = self.node[toks[i:]]
+                    break
+        self.start = self.next[0].get(self.bos, 0)
+
+    def step(self, state, tok):
+        """(score of the step, node it lands in)"""
+        acc, node = 0.0, state
+        while True:
+            c = self.next[node].get(tok, -1)
+            if c >= 0:
+                return acc + self.W[c], c
+            if node == 0:
+                return acc + self.U, 0
+            acc += self.B[node]
+            node = self.fail[node]
+
+    def eos(self, state):
+        return self.step(state, self.eos_tok)[0] if self.has_eos else 0.0
+
+    def walk(self, tokens):
+        """tokens from the start state -> (step scores, node ids, the end term of the last state)"""
+        state, scores, states = self.start, [], []
+        for tok in tokens:
+            sc, state = self.step(state, int(tok))
+            scores.append(sc); states.append(state)
+        return scores, states, self.eos(state)
+
+
+class _NgramEntry(_PrefixEntry):
+    __slots__ = ("ng_state", "ng_score")
+
+    def __init__(self):
+        super().__init__()
+        self.ng_state, self.ng_score = 0, 0.0
+
+    def total(self):
+        return self.score() + self.ctx_score + self.ng_score
+
+
+def ctc_prefix_beam_ngram_ref(lp, length, blank, beam_size, graph=None, ngram=None, stats=None, finalize=True):
+    """ctc_prefix_beam_ref with an ngram_ref fused (either of graph and ngram may be None): every entry also carries an n-gram
+    score and state, copied where the context is copied and advanced by ngram.step where the context is advanced, under the same
+    first-touch flag; the second prune sorts by score + context score + n-gram score, the first prune stays acoustic; at the end
+    (finalize) the n-gram score gains ngram.eos(state) and the list is not re-sorted.  The gap statistics are those of
+    ctc_prefix_beam_ref, taken over the totals with the n-gram term.
+    Returns (hyps, prune_gap, top_gap): hyps [(tokens, score, times, context score, n-gram score)]."""
+    lp = np.asarray(lp, np.float32)
+    start = _NgramEntry()
+    start.s, start.v_s, start.v_ns = 0.0, 0.0, 0.0
+    if ngram is not None:
+        start.ng_state = ngram.start
+    cur = [((), start)]
+    prune_gap = top_gap = math.inf
+    born, parent_born = {(): 0}, {}
+
+    def context(entry, src, tok):
+        if graph is None and ngram is None:
+            return
+        state, score, ng_state, ng_score = src.ctx_state, src.ctx_score, src.ng_state, src.ng_score
+        if tok is not None:
+            if graph is not None:
+                sc, state = graph.step(src.ctx_state, tok)
+                score = src.ctx_score + sc
+            if ngram is not None:
+                sc, ng_state = ngram.step(src.ng_state, tok)
+                ng_score = src.ng_score + sc
+        if entry.touched:
+            assert (entry.ctx_state, entry.ctx_score, entry.ng_state, entry.ng_score) == (state, score, ng_state, ng_score), \
+                "context and n-gram score are functions of the token string alone"
+        else:
+            entry.ctx_state, entry.ctx_score, entry.ng_state, entry.ng_score, entry.touched = state, score, ng_state, ng_score, True
+
+    for t in range(int(length)):
+        row = lp[t] + np.float32(0.0)
+        order = sorted(range(row.size), key=lambda v: (-row[v], v))
+        vals = [float(row[v]) for v in order[:beam_size + 1]]
+        for a, b in zip(vals, vals[1:]):
+            if a > -math.inf:
+                top_gap = min(top_gap, a - b)
+        if stats is not None:
+            _gap_stats(stats, vals, beam_size, "top_ties")
+        nxt = {}
+        if stats is not None and any(q[:-1] == pfx for q, _ in cur for pfx, _ in cur if q):
+            stats["both_live"] = stats.get("both_live", 0) + 1
+        for u in order[:beam_size]:
+            prob = float(row[u])
+            for prefix, h in cur:
+                last = prefix[-1] if prefix else None
+                if u == blank:
+                    e = nxt.setdefault(prefix, _NgramEntry())
+                    e.s = _log_add2(e.s, h.score() + prob)
+                    e.v_s = h.viterbi() + prob
+                    e.times_s = list(h.times())
+                    context(e, h, None)
+                    continue
+                if u == last:
+                    e = nxt.setdefault(prefix, _NgramEntry())
+                    e.ns = _log_add2(e.ns, h.ns + prob)
+                    if e.v_ns < h.v_ns + prob:
+                        e.v_ns = h.v_ns + prob
+                        if e.cur < prob:
+                            e.cur = prob
+                            e.times_ns = list(h.times_ns)
+                            e.times_ns[-1] = t
+                        elif stats is not None:
+                            stats["stale_times"] = stats.get("stale_times", 0) + 1
+                    context(e, h, None)
+                    add, vit, tm = h.s, h.v_s, h.times_s
+                else:
+                    add, vit, tm = h.score(), h.viterbi(), h.times()
+                if stats is not None and prefix + (u,) in born and parent_born[prefix + (u,)] != born[prefix]:
+                    stats["rebuilt_parent"] = stats.get("rebuilt_parent", 0) + 1
+                e = nxt.setdefault(prefix + (u,), _NgramEntry())
+                e.ns = _log_add2(e.ns, add + prob)
+                if e.v_ns < vit + prob:
+                    e.v_ns, e.cur = vit + prob, prob
+                    e.times_ns = list(tm) + [t]
+                context(e, h, u)
+        ranked = sorted(nxt.items(), key=lambda kv: kv[1].total(), reverse=True)
+        tot = [e.total() for _, e in ranked]
+        for a, b in zip(tot, tot[1:]):
+            if a > -math.inf:
+                prune_gap = min(prune_gap, a - b)
+        if stats is not None:
+            _gap_stats(stats, tot, beam_size, "prune_ties")
+        cur = ranked[:beam_size]
+        if stats is not None:
+            old = born
+            born = {q: old.get(q, t + 1) for q, _ in cur}
+            parent_born = {q: parent_born[q] if q in old else old[q[:-1]] for q, _ in cur if q}
+    out = []
+    for prefix, h in cur:
+        cs = 0.0 if graph is None else graph.finalize(h.ctx_state) if finalize else h.ctx_score
+        ls = 0.0 if ngram is None else h.ng_score + ngram.eos(h.ng_state) if finalize else h.ng_score
+        out.append((list(prefix), h.score() + cs + ls, list(h.times()), cs, ls))
+    return out, prune_gap, top_gap
+
+
 # ---- streaming encoder: one stream through the oracle's forward_chunk under any window policy (tests) ---------------------------
 _REF_SD = {}
 

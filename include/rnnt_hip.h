@@ -445,7 +445,7 @@ int rnnt_ctc_prefix_beam_decode(rnnt_ctx* ctx, const float* enc_dev, const int32
 /* -- the same search per slot of the stream pool, carried across calls ---------------------------- */
 /* The search is a per-frame recursion whose state at a frame boundary is its <= 16 hypothesis records and two append-only arenas, so
  * a search that stops at the end of a call and resumes at the next is, bit for bit, the one-launch search over the same rows,
- * whatever the split.  Per slot the device keeps one record (about 2 KB) and [max_cache_frames * 16 + 1] (parent, value) pairs of
+ * whatever the split.  Per slot the device keeps one record (2120 bytes) and [max_cache_frames * 16 + 1] (parent, value) pairs of
  * either arena -- 1.28 MB per slot per arena at max_cache_frames = 5000 -- allocated on the first use.  Frames, and the times
  * returned, are absolute encoder-frame indices since the slot's reset; a slot holds at most max_cache_frames of them.
  * A slot's search is fresh after a reset; its first advancing call fixes beam_size and use_context until the next reset.
@@ -555,6 +555,79 @@ int rnnt_ctc_prefix_beam_host(const float* lp_host, const int32_t* enc_lens_host
                               int32_t beam_size, int32_t n_phrases, const int32_t* phrase_lens, const int32_t* phrase_tokens,
                               double context_score, int32_t cap_tokens, int32_t* n_hyp_host, int32_t* lens_host, int32_t* tokens_host,
                               int32_t* times_host, double* scores_host, double* ctx_scores_host);
+
+/* -- n-gram language model, shallow fusion in the CTC prefix beam search -------------------------------------------------------- */
+/* The model is a list of n_ngrams n-grams (tokens_host concatenated, lens_host their lengths, 1 <= k <= 8; logp_host / bow_host
+ * natural-log probability and back-off weight, f64, finite).  Tokens are model ids in [0, vocab_size) other than the blank, plus
+ * BOS = vocab_size (first position only) and EOS = vocab_size + 1 (last position only).  Every n-gram's prefix (all but its last
+ * token) must be listed before it, so the list is a trie in insertion order: n-gram i is node i + 1, the root node 0.  fail[c] is the
+ * node of the longest proper suffix of c's n-gram that is listed (the root if none); the list need not be suffix-closed.
+ * Values are prescaled once on the host, each ONE f64 multiplication then ONE f64 addition (no FMA):
+ *   W[c] = lm_weight * logp[c] + length_bonus   (an n-gram that ends in EOS: lm_weight * logp[c], no bonus)
+ *   B[c] = lm_weight * bow[c]                   U = lm_weight * unk_logp + length_bonus
+ * step(state, tok) -> (score, next): acc = 0, node = state; loop { c = child(node, tok); if c: return (acc + W[c], c); if node is
+ * the root: return (acc + U, root); acc += B[node]; node = fail[node] }.  Additions only, in this order: host, device and an f64
+ * restatement give the same bits.  The start state is child(root, BOS), the root when [BOS] is not listed; eos(state) is
+ * step(state, EOS).score, 0 when no n-gram ends in EOS.
+ * In the search every hypothesis carries an n-gram score (f64, from 0) and state beside its context score and state: copied where the
+ * context is copied, advanced by step where the context is advanced, under the same first-touch rule.  The second prune sorts by
+ * score() + context score + n-gram score; the first prune stays acoustic; at the end eos(state) is added and the list is NOT
+ * re-sorted.  use_context and use_ngram are independent.
+ *
+ * rnnt_ngram_set builds and uploads the model (n_ngrams == 0 clears it) and starts a new model generation.  Device form: flat node
+ * arrays, a CSR of (token, child) sorted by token per node, and the root's children as a dense row [vocab_size + 2].
+ * Refusals, RNNT_ERR_ARG: an empty n-gram or one longer than 8; a token outside [0, vocab_size + 2) or the blank; BOS not first or
+ * EOS not last; a prefix not listed earlier; an n-gram listed twice; a value that is not finite; lm_weight < 0; more than 1 << 22
+ * nodes. */
+int rnnt_ngram_set(rnnt_ctx* ctx, int32_t n_ngrams, const int32_t* lens_host, const int32_t* tokens_host, const double* logp_host,
+                   const double* bow_host, double lm_weight, double length_bonus, double unk_logp);
+/* Test seam (no context, no GPU): builds the model over the given vocabulary and blank and feeds tokens [n_tokens] (ids in
+ * [0, vocab) other than the blank) through step from the start state; step_score_out / state_out [n_tokens] and *eos_out (the end
+ * term of the last state) and *n_nodes_out (root included) may each be NULL. */
+int rnnt_ngram_walk_host(int32_t n_ngrams, const int32_t* lens, const int32_t* ngram_tokens, const double* logp, const double* bow,
+                         double lm_weight, double length_bonus, double unk_logp, int32_t vocab, int32_t blank, int32_t n_tokens,
+                         const int32_t* tokens, double* step_score_out, int32_t* state_out, double* eos_out, int32_t* n_nodes_out);
+/* n >= 1 token sequences scored by the model that is set, each from the start state, in ONE launch (ngram_score_rows, one sequence
+ * per thread): tokens_host [n, cap], lens_host [n] in [0, cap]; step_scores_host [n, cap] (may be NULL; zero beyond a length) the
+ * per-token step scores, totals_host [n] their sum in walk order, plus eos(last state) when with_eos.  One upload, one download,
+ * one synchronisation.  RNNT_ERR_STATE when no model is set; RNNT_ERR_ARG for a token outside [0, vocab_size) or the blank. */
+int rnnt_ngram_score(rnnt_ctx* ctx, int32_t n, const int32_t* lens_host, const int32_t* tokens_host, int32_t cap, int32_t with_eos,
+                     double* step_scores_host, double* totals_host, void* stream);
+/* rnnt_ctc_prefix_beam_logprobs / _decode plus use_ngram (the model of rnnt_ngram_set is fused) and ngram_scores_host
+ * [B, beam_size] f64 or NULL (the n-gram part of scores_host, end term included; zero without use_ngram).  With use_ngram == 0 the
+ * result is, bit for bit, that of the calls without the suffix, which are these calls.  use_ngram with no model set: RNNT_ERR_STATE. */
+int rnnt_ctc_prefix_beam_logprobs_ngram(rnnt_ctx* ctx, const float* lp_dev, const int32_t* enc_lens_host, int32_t B, int32_t T,
+                                        int32_t beam_size, int32_t use_context, int32_t use_ngram, int32_t cap_tokens,
+                                        int32_t* n_hyp_host, int32_t* lens_host, int32_t* tokens_host, int32_t* times_host,
+                                        double* scores_host, double* ctx_scores_host, double* ngram_scores_host, void* stream);
+int rnnt_ctc_prefix_beam_decode_ngram(rnnt_ctx* ctx, const float* enc_dev, const int32_t* enc_lens_host, int32_t B, int32_t T,
+                                      int32_t beam_size, int32_t use_context, int32_t use_ngram, int32_t cap_tokens,
+                                      int32_t* n_hyp_host, int32_t* lens_host, int32_t* tokens_host, int32_t* times_host,
+                                      double* scores_host, double* ctx_scores_host, double* ngram_scores_host, void* stream);
+/* rnnt_ctc_prefix_beam_host plus the model, passed as the list rnnt_ngram_set takes (n_ngrams == 0: none), and ngram_scores_host. */
+int rnnt_ctc_prefix_beam_ngram_host(const float* lp_host, const int32_t* enc_lens_host, int32_t B, int32_t T, int32_t vocab,
+                                    int32_t blank, int32_t beam_size, int32_t n_phrases, const int32_t* phrase_lens,
+                                    const int32_t* phrase_tokens, double context_score, int32_t n_ngrams, const int32_t* ngram_lens,
+                                    const int32_t* ngram_tokens, const double* logp, const double* bow, double lm_weight,
+                                    double length_bonus, double unk_logp, int32_t cap_tokens, int32_t* n_hyp_host, int32_t* lens_host,
+                                    int32_t* tokens_host, int32_t* times_host, double* scores_host, double* ctx_scores_host,
+                                    double* ngram_scores_host);
+/* The pool calls of the CTC prefix search plus use_ngram (the two advancing calls) or ngram_scores_host [cap_hyps] (the read; may be
+ * NULL).  A slot's first advancing call fixes use_ngram together with beam_size and use_context until its reset; a differing value:
+ * RNNT_ERR_ARG.  The slot record (2120 bytes) holds an n-gram score and state per hypothesis; a reset record (rnnt_stream_ctc_prefix_reset,
+ * rnnt_stream_open, rnnt_streams_reset, rnnt_pool_segment) holds a start marker that the first step resolves to the start state of the
+ * model set at that first call.  After rnnt_ngram_set a search that uses the model under an older generation is refused with
+ * RNNT_ERR_STATE (advance, and read with final != 0) until its slot is reset; searches that do not use it go on.  final != 0 adds
+ * the end term, final == 0 returns the running n-gram score; either way scores_host holds the totals.  A call lists slots of one
+ * use_ngram. */
+int rnnt_pool_ctc_prefix_logprobs_ngram(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, const float* lp_dev, int32_t t,
+                                        int32_t beam_size, int32_t use_context, int32_t use_ngram, void* stream);
+int rnnt_pool_chunk_ctc_prefix_ngram(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, const float* fbank_dev,
+                                     int32_t chunk_frames, const int32_t* offsets_host, const int32_t* required_host, int32_t beam_size,
+                                     int32_t use_context, int32_t use_ngram, int32_t* frames_out, void* stream);
+int rnnt_stream_get_ctc_prefix_ngram(rnnt_ctx* ctx, int32_t slot, int32_t final, int32_t cap_hyps, int32_t cap_tokens, int32_t* n_hyp,
+                                     int32_t* lens_host, int32_t* tokens_host, int32_t* times_host, double* scores_host,
+                                     double* ctx_scores_host, double* ngram_scores_host, int32_t* frames_out, void* stream);
 
 /* -- teacher-forced scoring: how likely is a GIVEN transcript (forward only, no gradients) ----------------------------------- */
 /* Transducer negative log-likelihood: the RNN-T term of the reference's forward with texts (model/online_rnnt_model.py:240-255),
