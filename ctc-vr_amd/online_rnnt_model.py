@@ -973,7 +973,58 @@ class StreamingBatch:
         return self.engine.tokens(_stream_ptr())
 
 
-_POOL_KINDS = ("greedy", "beam", "ctc_prefix", "prefix", "ctc_prefix_ngram")
+_PLAN_ORDER = ("greedy", "beam", "ctc_prefix", "prefix", "ctc_prefix_ngram")   # the classes of a round run in this order of kinds
+
+
+class Decoder(namedtuple("Decoder", ["kind", "beam", "use_context", "weights", "use_ngram"])):
+    """The decoder a pool slot was opened with, fixed for its utterance: kind ("greedy", "beam", "ctc_prefix" or "prefix", a row of
+    _KINDS), beam size (0 for greedy), hot-word biasing, the (ctc_weight, transducer_weight) of a "prefix" slot (None otherwise) and
+    n-gram fusion (a "ctc_prefix" slot's).  Slots with equal decoders may share a library call."""
+    __slots__ = ()
+
+    @property
+    def plan_kind(self):
+        """the kind as pool_plan names it: the CTC prefix slots that fuse a model are a kind of their own, ordered last"""
+        return "ctc_prefix_ngram" if self.use_ngram else self.kind
+
+    @property
+    def plan_key(self):
+        return (_PLAN_ORDER.index(self.plan_kind), self.beam, int(self.use_context)) + (self.weights or (0.0, 0.0))
+
+
+GREEDY = Decoder("greedy", 0, False, None, False)
+
+# one library call of a step: one chunk length, one decoder, every slot at most once
+Call = namedtuple("Call", ["length", "slots", "offsets", "decoder"])
+
+
+def plan_calls(queue, offsets, decoders):
+    """The library calls of one StreamPool.step as a pure function (no GPU, no tensors): pool_plan's rounds, < 7-frame skip, offset
+    bookkeeping and index, with decoders = {slot: Decoder} (an absent slot is greedy) in place of its four tables.  Returns (calls,
+    new_offsets, index), every call one Call; inside a round the classes run in ascending (length, Decoder.plan_key)."""
+    offs = dict(offsets)
+    rounds: List[Dict[Tuple[int, Decoder], List[Tuple[int, int]]]] = []   # round -> (length, decoder) -> [(slot, queue index)]
+    depth: Dict[int, int] = {}
+    index: List[Optional[Tuple[int, int]]] = [None] * len(queue)
+    for k, (slot, length) in enumerate(queue):
+        if length < 7:
+            continue
+        r = depth.get(slot, 0)
+        depth[slot] = r + 1
+        while len(rounds) <= r:
+            rounds.append({})
+        rounds[r].setdefault((int(length), decoders.get(slot, GREEDY)), []).append((slot, k))
+    calls = []
+    for rnd in rounds:
+        for length, decoder in sorted(rnd, key=lambda c: (c[0], c[1].plan_key)):
+            slots, call_offs = [], []
+            for slot, k in rnd[(length, decoder)]:
+                index[k] = (len(calls), len(slots))
+                slots.append(slot)
+                call_offs.append(offs.get(slot, 0))
+                offs[slot] = offs.get(slot, 0) + length // 4
+            calls.append(Call(length, slots, call_offs, decoder))
+    return calls, offs, index
 
 
 def pool_plan(queue, offsets, beams=None, ctc_prefix=None, prefix=None, ngram=None):
@@ -1009,44 +1060,19 @@ def pool_plan(queue, offsets, beams=None, ctc_prefix=None, prefix=None, ngram=No
     ngram: the slots among ctc_prefix whose search fuses the n-gram model (None or empty: none, and the results above).  Their calls
     have kind "ctc_prefix_ngram" (an rnnt_pool_chunk_ctc_prefix_ngram call), ordered after "prefix": such slots never share a call
     with the other CTC prefix slots."""
-    offs = dict(offsets)
-
-    def klass(slot, length):
-        if ngram and ctc_prefix is not None and slot in ngram and slot in ctc_prefix and not (prefix is not None and slot in prefix):
-            return int(length), 4, int(ctc_prefix[slot][0]), int(bool(ctc_prefix[slot][1])), 0.0, 0.0
+    decoders = {}
+    for slot in {slot for slot, _ in queue}:
         if prefix is not None and slot in prefix:
-            return int(length), 3, int(prefix[slot][0]), int(bool(prefix[slot][3])) if len(prefix[slot]) > 3 else 0, float(prefix[slot][1]), float(prefix[slot][2])
-        if ctc_prefix is not None and slot in ctc_prefix:
-            return int(length), 2, int(ctc_prefix[slot][0]), int(bool(ctc_prefix[slot][1])), 0.0, 0.0
-        beam = int(beams.get(slot, 0)) if beams else 0
-        return int(length), 1 if beam > 0 else 0, beam, 0, 0.0, 0.0
-    rounds: List[Dict[tuple, List[Tuple[int, int]]]] = []   # round -> (length, kind, beam, use_context, weights) -> [(slot, queue index)]
-    depth: Dict[int, int] = {}
-    index: List[Optional[Tuple[int, int]]] = [None] * len(queue)
-    for k, (slot, length) in enumerate(queue):
-        if length < 7:
-            continue
-        r = depth.get(slot, 0)
-        depth[slot] = r + 1
-        while len(rounds) <= r:
-            rounds.append({})
-        rounds[r].setdefault(klass(slot, length), []).append((slot, k))
-    calls = []
-    for rnd in rounds:
-        for length, kind, beam, use_context, cw, tw in sorted(rnd):
-            slots, call_offs = [], []
-            for slot, k in rnd[(length, kind, beam, use_context, cw, tw)]:
-                index[k] = (len(calls), len(slots))
-                slots.append(slot)
-                call_offs.append(offs.get(slot, 0))
-                offs[slot] = offs.get(slot, 0) + length // 4
-            if prefix is not None:
-                calls.append((length, slots, call_offs, beam, _POOL_KINDS[kind], bool(use_context), (cw, tw) if kind == 3 else None))
-            elif ctc_prefix is not None:
-                calls.append((length, slots, call_offs, beam, _POOL_KINDS[kind], bool(use_context)))
-            else:
-                calls.append((length, slots, call_offs) if beams is None else (length, slots, call_offs, beam))
-    return calls, offs, index
+            p = prefix[slot]
+            decoders[slot] = Decoder("prefix", int(p[0]), bool(p[3]) if len(p) > 3 else False, (float(p[1]), float(p[2])), False)
+        elif ctc_prefix is not None and slot in ctc_prefix:
+            decoders[slot] = Decoder("ctc_prefix", int(ctc_prefix[slot][0]), bool(ctc_prefix[slot][1]), None, bool(ngram) and slot in ngram)
+        elif beams and slot in beams:
+            decoders[slot] = Decoder("beam" if int(beams[slot]) > 0 else "greedy", int(beams[slot]), False, None, False)
+    calls, offs, index = plan_calls(queue, offsets, decoders)
+    width = 7 if prefix is not None else 6 if ctc_prefix is not None else 4 if beams is not None else 3     # the only code that knows them
+    return [(c.length, c.slots, c.offsets, c.decoder.beam, c.decoder.plan_kind, c.decoder.use_context, c.decoder.weights)[:width]
+            for c in calls], offs, index
 
 
 def wave_frames(n: int, n_fft: int, final: bool) -> int:
@@ -1128,6 +1154,108 @@ class EndpointConfig:
         return (self.blank_threshold, self.min_speech_frames, self.rule1_trailing, self.rule2_trailing, self.rule3_frames)
 
 
+# ---- the slot kinds of the pool: the only place that knows what a kind is opened with, advanced by and read through ------------------
+# what: the kind's name in a refusal.  collects_tokens: step() hands out its new tokens.  advance(decoder) -> the engine method of its
+# chunk call and that call's arguments between (slots, ptr, length, offsets, offsets) and the stream.  read(engine, decoder, slot, final,
+# stream) -> its hypotheses, which is also what close() and a Segment return.  first_pass(hyps) -> [(tokens, score)] for rescore(), None:
+# the kind is no first pass.  Engine methods are looked up when they are called: an engine needs only those of the kinds it serves.
+_Kind = namedtuple("_Kind", ["what", "collects_tokens", "advance", "read", "first_pass"])
+
+
+def _read_ctc_prefix(engine, d, slot, final, stream):
+    if d.use_ngram:                                     # the totals carry the n-gram score (final: with the end term)
+        return [(h[0], h[1], h[2]) for h in engine.stream_ctc_prefix_ngram(slot, final, stream=stream)]
+    return [(tok, score, times) for tok, score, times, _ in engine.stream_ctc_prefix(slot, final, stream=stream)]
+
+
+def _read_prefix(engine, d, slot, final, stream, with_context_scores=False):
+    if not d.use_context and not with_context_scores:
+        return engine.stream_prefix(slot, stream=stream)            # no context score to finalize: final reads the same
+    hyps = engine.stream_prefix_ctx(slot, final, stream=stream)
+    return hyps if with_context_scores else [(tok, score) for tok, score, _ in hyps]
+
+
+_KINDS = {
+    "greedy": _Kind("greedy", True, lambda d: ("pool_chunk", (True,)),
+                    lambda engine, d, slot, final, stream: engine.stream_tokens(slot, 0, stream), None),
+    "beam": _Kind("beam", False, lambda d: ("pool_chunk_beam", (d.beam,)),
+                  lambda engine, d, slot, final, stream: [BeamHypothesis(t, lp) for t, lp in engine.stream_beam(slot, stream)], None),
+    "ctc_prefix": _Kind("CTC prefix", False,
+                        lambda d: ("pool_chunk_ctc_prefix_ngram", (d.beam, d.use_context, True)) if d.use_ngram else
+                                  ("pool_chunk_ctc_prefix", (d.beam, d.use_context)),
+                        _read_ctc_prefix, lambda hyps: [(tok, score) for tok, score, _ in hyps]),
+    "prefix": _Kind("transducer prefix", False,
+                    lambda d: ("pool_chunk_prefix_ctx", (d.beam,) + d.weights + (True,)) if d.use_context else
+                              ("pool_chunk_prefix", (d.beam,) + d.weights),
+                    _read_prefix, lambda hyps: [(tok[1:], score) for tok, score in hyps]),      # the first pass drops the leading blank
+}
+
+
+def _decoder_of_open(pool, beam_size, ctc_prefix_beam, context, prefix_beam, ctc_weight, transducer_weight, prefix_context, endpoint,
+                     on_endpoint, ngram) -> Decoder:
+    """The Decoder that open()'s keywords select, or the RnntError of the first rule they break.  The order of the checks is part of the
+    facade's behaviour: an open() with several faults reports the first one here."""
+    if ngram is not None:
+        if not ctc_prefix_beam:
+            raise RnntError("stream pool: ngram needs ctc_prefix_beam")
+        if ngram is not pool._ngram and any(r.ngram is not None for r in pool._slots.values()):
+            raise RnntError("stream pool: another n-gram model is in use by an open slot (one model per pool at a time)")
+    if on_endpoint not in (None, "keep", "fresh"):
+        raise RnntError(f"stream pool: on_endpoint {on_endpoint!r} is not None, 'keep' or 'fresh'")
+    if on_endpoint is not None and endpoint is None:
+        raise RnntError("stream pool: on_endpoint needs endpoint (an EndpointConfig)")
+    biased_open = any(r.context is not None for r in pool._slots.values())
+    if prefix_context is not None:
+        if not prefix_beam:
+            raise RnntError("stream pool: prefix_context needs prefix_beam")
+        if prefix_context is not pool._context and biased_open:
+            raise RnntError("stream pool: another context graph is in use by an open slot (one graph per pool at a time)")
+    if prefix_beam:
+        if beam_size or ctc_prefix_beam:
+            raise RnntError("stream pool: prefix_beam, beam_size and ctc_prefix_beam are mutually exclusive")
+        if context is not None:
+            raise RnntError("stream pool: context biases the CTC prefix search only (ctc_prefix_beam)")
+        if prefix_beam < 1 or prefix_beam > min(16, pool.vocab_size) or pool.vocab_size > 512:
+            raise RnntError(f"stream pool: prefix_beam {prefix_beam} outside [1, min(16, vocabulary {pool.vocab_size})] or vocabulary > 512")
+        if not ctc_weight >= 0 or not transducer_weight >= 0 or (ctc_weight == 0 and transducer_weight == 0):
+            raise RnntError(f"stream pool: weights {ctc_weight} / {transducer_weight} (negative, or both zero)")
+    if ctc_prefix_beam:
+        if beam_size:
+            raise RnntError("stream pool: beam_size and ctc_prefix_beam are mutually exclusive")
+        if ctc_prefix_beam < 1 or ctc_prefix_beam > min(16, pool.vocab_size) or pool.vocab_size > 512:
+            raise RnntError(f"stream pool: ctc_prefix_beam {ctc_prefix_beam} outside [1, min(16, vocabulary {pool.vocab_size})] or vocabulary > 512")
+        if context is not None and context is not pool._context and biased_open:
+            raise RnntError("stream pool: another context graph is in use by an open slot (one graph per pool at a time)")
+    elif context is not None:
+        raise RnntError("stream pool: context needs ctc_prefix_beam")
+    if beam_size < 0 or beam_size > 0 and (beam_size > min(pool.max_beam, 16) or pool.vocab_size > 512):
+        raise RnntError(f"stream pool: beam_size {beam_size} outside [0, min(max_beam {pool.max_beam}, 16)] or vocabulary "
+                        f"{pool.vocab_size} > 512")
+    if prefix_beam:
+        return Decoder("prefix", int(prefix_beam), prefix_context is not None, (float(ctc_weight), float(transducer_weight)), False)
+    if ctc_prefix_beam:
+        return Decoder("ctc_prefix", int(ctc_prefix_beam), context is not None, None, ngram is not None)
+    return Decoder("beam", int(beam_size), False, None, False) if beam_size else GREEDY
+
+
+class _Slot:
+    """What the pool keeps of one open slot; "open" is "has a record", and close() drops it whole."""
+
+    def __init__(self, decoder: Decoder, context: Optional[ContextBias], ngram: Optional[NgramLM], keep_frames: bool,
+                 endpoint: Optional[EndpointConfig], on_endpoint: Optional[str]):
+        self.decoder, self.context, self.ngram = decoder, context, ngram    # with the graph and the model it was opened with
+        self.keep_frames = keep_frames
+        self.endpoint = endpoint                        # the slot detects its endpoint under this config
+        self.on_endpoint = on_endpoint                  # "keep" / "fresh": step() segments the slot when its rule has fired
+        self.offset = 0                                 # encoder offset so far
+        self.ntok = 0                                   # tokens already handed out by step()
+        self.segment = (0, 0)                           # (index, start_frame) of the current segment
+        self.fed: Optional[str] = None                  # "feed" / "wave": how the slot is fed (fixed by its first chunk or packet)
+        self.wave_samples = 0                           # a wave slot: samples received,
+        self.wave_fifo: Optional[torch.Tensor] = None   # [k, 80] frames waiting for a full chunk,
+        self.wave_final = False                         # and whether the final packet has been queued
+
+
 class StreamPool:
     """A context's slots, each with its own life (not in the reference, which is B=1): open() a slot when a caller connects, feed()
     it a chunk whenever the caller has one, step() to advance whatever subset of slots has chunks queued -- each at its own cache
@@ -1199,29 +1327,31 @@ class StreamPool:
         """All slots free; the context freshly reset (the lock-step entry points work again until the first open)."""
         self.engine.reset(self.n, self._stream(None))
         self._free = list(range(self.n))
-        self._offset: Dict[int, int] = {}
-        self._ntok: Dict[int, int] = {}
-        self._beam: Dict[int, int] = {}                 # beam size of the open slots (0 = greedy)
-        self._keep: Dict[int, bool] = {}                # keep_frames of the slot's last open()
-        self._endpoint: Dict[int, EndpointConfig] = {}  # the open slots that detect their endpoint
-        self._on_endpoint: Dict[int, str] = {}          # "keep" / "fresh": the open slots step() segments when their rule has fired
-        self._segments: Dict[int, List[Segment]] = {}   # what step() finished for them, until segments(slot) takes it
-        self._seg: Dict[int, Tuple[int, int]] = {}      # (index, start_frame) of the open slots' current segment
-        self._ctc: Dict[int, Tuple[int, Optional[ContextBias]]] = {}   # (beam, context) of the open CTC prefix slots
-        self._ctc_ngram: Dict[int, NgramLM] = {}        # the model of those among them that fuse one
-        self._prefix: Dict[int, Tuple[int, float, float]] = {}   # (beam, ctc_weight, transducer_weight) of the open transducer prefix slots
-        self._prefix_ctx: Dict[int, ContextBias] = {}   # the context of the biased ones among them
+        self._slots: Dict[int, _Slot] = {}              # the open slots
+        # the one thing kept per slot outside its record: what step() finished for an on_endpoint slot, until segments(slot) takes it.
+        # segments() hands these out after close() too, so they outlive the record; the slot's next open() discards them
+        self._segments: Dict[int, List[Segment]] = {}
         self._queue: List[Tuple[int, torch.Tensor]] = []
         self._carry: Dict[int, List[int]] = {}          # increments of other slots produced by the step inside a close()
         self._wave_queue: List[Tuple[int, torch.Tensor, bool]] = []   # PCM packets (slot, samples, final) in feed order
-        self._wave_samples: Dict[int, int] = {}         # samples received by the open wave slots
-        self._wave_fifo: Dict[int, torch.Tensor] = {}   # [k, 80] frames waiting for a full chunk
-        self._wave_final: Dict[int, bool] = {}          # the open wave slots: has the final packet been queued
-        self._fed: Dict[int, str] = {}                  # "feed" / "wave": how the open slot is fed (fixed by its first packet or chunk)
 
     @staticmethod
     def _stream(t):
         return _stream_ptr() if (t is None and torch.cuda.is_available()) or (t is not None and t.is_cuda) else None
+
+    def _open_slot(self, slot: int) -> _Slot:
+        if slot not in self._slots:
+            raise RnntError(f"slot {slot} is not open")
+        return self._slots[slot]
+
+    def _slot_of_kind(self, slot: int, kind: str) -> _Slot:
+        rec = self._slots.get(slot)
+        if rec is None or rec.decoder.kind != kind:
+            raise RnntError(f"slot {slot} is not an open {_KINDS[kind].what} slot")
+        return rec
+
+    def _queued(self, slot: int) -> bool:
+        return any(s == slot for s, _ in self._queue) or any(s == slot for s, _, _ in self._wave_queue)
 
     def open(self, beam_size: int = 0, ctc_prefix_beam: int = 0, context: Optional[ContextBias] = None, keep_frames: bool = False,
              prefix_beam: int = 0, ctc_weight: float = 0.3, transducer_weight: float = 0.7, prefix_context: Optional[ContextBias] = None,
@@ -1246,42 +1376,8 @@ class StreamPool:
         ngram (needs ctc_prefix_beam): the slot's search fuses that NgramLM (rnnt_pool_chunk_ctc_prefix_ngram calls of their own).  The
         pool holds one model at a time, with the graph's rule: a model other than the current one is uploaded (ngram_set) unless
         another slot that fuses one is still open, which raises RnntError and takes no slot."""
-        if ngram is not None:
-            if not ctc_prefix_beam:
-                raise RnntError("stream pool: ngram needs ctc_prefix_beam")
-            if ngram is not self._ngram and self._ctc_ngram:
-                raise RnntError("stream pool: another n-gram model is in use by an open slot (one model per pool at a time)")
-        if on_endpoint not in (None, "keep", "fresh"):
-            raise RnntError(f"stream pool: on_endpoint {on_endpoint!r} is not None, 'keep' or 'fresh'")
-        if on_endpoint is not None and endpoint is None:
-            raise RnntError("stream pool: on_endpoint needs endpoint (an EndpointConfig)")
-        biased_open = any(c is not None for _, c in self._ctc.values()) or bool(self._prefix_ctx)
-        if prefix_context is not None:
-            if not prefix_beam:
-                raise RnntError("stream pool: prefix_context needs prefix_beam")
-            if prefix_context is not self._context and biased_open:
-                raise RnntError("stream pool: another context graph is in use by an open slot (one graph per pool at a time)")
-        if prefix_beam:
-            if beam_size or ctc_prefix_beam:
-                raise RnntError("stream pool: prefix_beam, beam_size and ctc_prefix_beam are mutually exclusive")
-            if context is not None:
-                raise RnntError("stream pool: context biases the CTC prefix search only (ctc_prefix_beam)")
-            if prefix_beam < 1 or prefix_beam > min(16, self.vocab_size) or self.vocab_size > 512:
-                raise RnntError(f"stream pool: prefix_beam {prefix_beam} outside [1, min(16, vocabulary {self.vocab_size})] or vocabulary > 512")
-            if not ctc_weight >= 0 or not transducer_weight >= 0 or (ctc_weight == 0 and transducer_weight == 0):
-                raise RnntError(f"stream pool: weights {ctc_weight} / {transducer_weight} (negative, or both zero)")
-        if ctc_prefix_beam:
-            if beam_size:
-                raise RnntError("stream pool: beam_size and ctc_prefix_beam are mutually exclusive")
-            if ctc_prefix_beam < 1 or ctc_prefix_beam > min(16, self.vocab_size) or self.vocab_size > 512:
-                raise RnntError(f"stream pool: ctc_prefix_beam {ctc_prefix_beam} outside [1, min(16, vocabulary {self.vocab_size})] or vocabulary > 512")
-            if context is not None and context is not self._context and biased_open:
-                raise RnntError("stream pool: another context graph is in use by an open slot (one graph per pool at a time)")
-        elif context is not None:
-            raise RnntError("stream pool: context needs ctc_prefix_beam")
-        if beam_size < 0 or beam_size > 0 and (beam_size > min(self.max_beam, 16) or self.vocab_size > 512):
-            raise RnntError(f"stream pool: beam_size {beam_size} outside [0, min(max_beam {self.max_beam}, 16)] or vocabulary "
-                            f"{self.vocab_size} > 512")
+        decoder = _decoder_of_open(self, beam_size, ctc_prefix_beam, context, prefix_beam, ctc_weight, transducer_weight, prefix_context,
+                                   endpoint, on_endpoint, ngram)
         if not self._free:
             raise RnntError(f"stream pool full: all {self.n} slots are open")
         graph = context if context is not None else prefix_context
@@ -1297,39 +1393,20 @@ class StreamPool:
             self.engine.stream_keep_frames(slot, True, self._stream(None))
         if endpoint is not None:
             self.engine.stream_endpoint(slot, endpoint.as_tuple(), self._stream(None))
-            self._endpoint[slot] = endpoint
         self._free.pop(0)
-        self._keep[slot] = bool(keep_frames)
-        if ctc_prefix_beam:
-            self._ctc[slot] = (int(ctc_prefix_beam), context)
-            if ngram is not None:
-                self._ctc_ngram[slot] = ngram
-        if prefix_beam:
-            self._prefix[slot] = (int(prefix_beam), float(ctc_weight), float(transducer_weight))
-            if prefix_context is not None:
-                self._prefix_ctx[slot] = prefix_context
-        self._offset[slot] = 0
-        self._ntok[slot] = 0
-        self._beam[slot] = int(beam_size)
-        self._seg[slot] = (0, 0)
+        self._slots[slot] = _Slot(decoder, graph, ngram, bool(keep_frames), endpoint, on_endpoint)
         self._segments.pop(slot, None)
         if on_endpoint is not None:
-            self._on_endpoint[slot] = on_endpoint
             self._segments[slot] = []
-        self._forget_wave(slot)
         return slot
-
-    def _forget_wave(self, slot: int):
-        for d in (self._wave_samples, self._wave_fifo, self._wave_final, self._fed):
-            d.pop(slot, None)
 
     def feed(self, slot: int, chunk: torch.Tensor) -> bool:
         """Queue one chunk [T, 80] (float32, on the device) for an open slot; the next step() encodes and decodes it.  A chunk of
         fewer than 7 frames is skipped as in process_single_chunk (:356-359): returns False and the slot's offset stays.  Raises
         RnntError on a slot fed through feed_wave."""
-        if slot not in self._offset:
-            raise RnntError(f"slot {slot} is not open")
-        if self._fed.setdefault(slot, "feed") != "feed":
+        rec = self._open_slot(slot)
+        rec.fed = rec.fed or "feed"
+        if rec.fed != "feed":
             raise RnntError(f"slot {slot} is fed audio (feed_wave): feature chunks cannot be mixed in")
         return self._feed_chunk(slot, chunk)
 
@@ -1346,22 +1423,25 @@ class StreamPool:
         with it.  The next step() turns the queued packets of all slots into frames with one rnnt_pool_wave call and feeds every
         full chunk_frames of them, at final also the remainder.  Raises RnntError on a slot fed through feed(), or after its final
         packet."""
-        if slot not in self._offset:
-            raise RnntError(f"slot {slot} is not open")
-        if self._fed.setdefault(slot, "wave") != "wave":
+        rec = self._open_slot(slot)
+        rec.fed = rec.fed or "wave"
+        if rec.fed != "wave":
             raise RnntError(f"slot {slot} is fed feature chunks (feed): audio cannot be mixed in")
-        if self._wave_final.get(slot, False):
+        if rec.wave_final:
             raise RnntError(f"slot {slot}: its utterance has ended (final packet already queued)")
         assert samples.dim() == 1 and samples.dtype == torch.float32
-        self._wave_final[slot] = bool(final)
+        rec.wave_final = bool(final)
         self._wave_queue.append((slot, samples, bool(final)))
 
     def _wave_step(self):
         """The queued packets of all slots through ONE rnnt_pool_wave call (wave_plan); full chunks leave the FIFOs for the chunk queue."""
         queue, self._wave_queue = self._wave_queue, []
-        fifo_len = {slot: f.size(0) for slot, f in self._wave_fifo.items()}
-        call, chunks, self._wave_samples, fifo_left = wave_plan([(slot, p.numel(), fin) for slot, p, fin in queue], self._wave_samples, fifo_len,
-                                                                self.chunk_frames, self.n_fft)
+        recs = {slot: self._slots[slot] for slot, _, _ in queue}
+        call, chunks, samples, _ = wave_plan([(slot, p.numel(), fin) for slot, p, fin in queue], {slot: r.wave_samples for slot, r in recs.items()},
+                                             {slot: r.wave_fifo.size(0) for slot, r in recs.items() if r.wave_fifo is not None},
+                                             self.chunk_frames, self.n_fft)
+        for slot, n in samples.items():
+            recs[slot].wave_samples = n
         slots, counts, finals, frames = call
         dev = self._wave_device if self._wave_device is not None else queue[0][1].device
         parts: Dict[int, List[torch.Tensor]] = {slot: [] for slot in slots}
@@ -1382,18 +1462,18 @@ class StreamPool:
         assert [int(g) for g in got] == frames, f"rnnt_pool_wave wrote {list(got)} frames, the plan says {frames}"
         for i, slot in enumerate(slots):
             if frames[i]:
-                old = self._wave_fifo.get(slot)
-                self._wave_fifo[slot] = out[i, :frames[i]] if old is None or old.size(0) == 0 else torch.cat([old, out[i, :frames[i]]], 0)
+                old = recs[slot].wave_fifo
+                recs[slot].wave_fifo = out[i, :frames[i]] if old is None or old.size(0) == 0 else torch.cat([old, out[i, :frames[i]]], 0)
         taken: Dict[int, int] = {}
         for slot, start, length in chunks:
-            self._feed_chunk(slot, self._wave_fifo[slot][start:start + length].contiguous())
+            self._feed_chunk(slot, recs[slot].wave_fifo[start:start + length].contiguous())
             taken[slot] = start + length
         for slot, k in taken.items():
-            self._wave_fifo[slot] = self._wave_fifo[slot][k:]
+            recs[slot].wave_fifo = recs[slot].wave_fifo[k:]
 
     def step(self) -> Dict[int, List[int]]:
         """Advance every slot that has chunks queued: one rnnt_pool_chunk call per chunk length of the greedy slots and one
-        rnnt_pool_chunk_beam call per (chunk length, beam size) of the beam slots (pool_plan), the rows of a call gathered into one
+        rnnt_pool_chunk_beam call per (chunk length, beam size) of the beam slots (plan_calls), the rows of a call gathered into one
         contiguous device tensor; CTC prefix slots likewise through one rnnt_pool_chunk_ctc_prefix call per (chunk length, beam size,
         use_context), transducer prefix slots through one rnnt_pool_chunk_prefix call per (chunk length, beam size, weights) -- the biased
         ones among them through rnnt_pool_chunk_prefix_ctx calls of their own.  Returns
@@ -1404,70 +1484,57 @@ class StreamPool:
             self._wave_step()
         if not self._queue:
             return out
-        calls, offs, index = pool_plan([(slot, c.size(0)) for slot, c in self._queue], self._offset, self._beam,
-                                       {slot: (b, c is not None) for slot, (b, c) in self._ctc.items()},
-                                       {slot: v + (True,) if slot in self._prefix_ctx else v for slot, v in self._prefix.items()},
-                                       set(self._ctc_ngram))
-        rows: List[List[Optional[torch.Tensor]]] = [[None] * len(call[1]) for call in calls]
+        recs = {slot: self._slots[slot] for slot, _ in self._queue}
+        calls, offs, index = plan_calls([(slot, c.size(0)) for slot, c in self._queue], {slot: r.offset for slot, r in recs.items()},
+                                        {slot: r.decoder for slot, r in recs.items()})
+        rows: List[List[Optional[torch.Tensor]]] = [[None] * len(call.slots) for call in calls]
         for (slot, c), at in zip(self._queue, index):
             rows[at[0]][at[1]] = c
         touched = []
-        for (length, slots, call_offs, beam, kind, use_context, weights), chunks in zip(calls, rows):
+        for call, chunks in zip(calls, rows):
             x = torch.stack(chunks, 0).contiguous()
-            if kind == "prefix" and use_context:
-                self.engine.pool_chunk_prefix_ctx(slots, x.data_ptr(), length, call_offs, call_offs, beam, weights[0], weights[1], True, self._stream(x))
-                continue
-            if kind == "prefix":
-                self.engine.pool_chunk_prefix(slots, x.data_ptr(), length, call_offs, call_offs, beam, weights[0], weights[1], self._stream(x))
-                continue
-            if kind == "ctc_prefix_ngram":
-                self.engine.pool_chunk_ctc_prefix_ngram(slots, x.data_ptr(), length, call_offs, call_offs, beam, use_context, True, self._stream(x))
-                continue
-            if kind == "ctc_prefix":
-                self.engine.pool_chunk_ctc_prefix(slots, x.data_ptr(), length, call_offs, call_offs, beam, use_context, self._stream(x))
-                continue
-            if kind == "beam":
-                self.engine.pool_chunk_beam(slots, x.data_ptr(), length, call_offs, call_offs, beam, self._stream(x))
-                continue
-            self.engine.pool_chunk(slots, x.data_ptr(), length, call_offs, call_offs, True, self._stream(x))
-            touched.extend(s for s in slots if s not in touched)
-        self._offset = offs
+            kind = _KINDS[call.decoder.kind]
+            method, args = kind.advance(call.decoder)
+            getattr(self.engine, method)(call.slots, x.data_ptr(), call.length, call.offsets, call.offsets, *args, self._stream(x))
+            if kind.collects_tokens:
+                touched.extend(s for s in call.slots if s not in touched)
+        for slot, offset in offs.items():
+            recs[slot].offset = offset
         self._queue = []
+        stream = self._stream(None)
         for slot in touched:
-            new = self.engine.stream_tokens(slot, self._ntok[slot], self._stream(None))
-            self._ntok[slot] += len(new)
+            new = self.engine.stream_tokens(slot, recs[slot].ntok, stream)
+            recs[slot].ntok += len(new)
             out[slot] = out.get(slot, []) + new
-        if self._on_endpoint:
-            self._segment_fired()
+        auto = [slot for slot, r in self._slots.items() if r.on_endpoint is not None]
+        if auto:
+            self._segment_fired(sorted(auto))
         return out
 
-    def _result(self, slot: int):
-        """What close() returns for the slot's utterance as it stands."""
-        if slot in self._prefix:
-            return self.prefix_hyps(slot, final=True)
-        if slot in self._ctc:
-            return self.ctc_hyps(slot, final=True)
-        return self.beams(slot) if self._beam[slot] > 0 else self.engine.stream_tokens(slot, 0, self._stream(None))
+    def _read(self, slot: int, rec: _Slot, final: bool, *how):
+        """The slot's hypotheses as its kind reads them; final=True: what close() returns for the utterance as it stands."""
+        return _KINDS[rec.decoder.kind].read(self.engine, rec.decoder, slot, final, self._stream(None), *how)
 
     def _finish(self, slots: List[int], keep_encoder: bool, eps: Dict[int, Endpoint]) -> List[Segment]:
         """The results of the listed slots, then ONE rnnt_pool_segment call for all of them, then the facade's own records."""
-        results = [self._result(slot) for slot in slots]
-        self.engine.pool_segment(slots, keep_encoder, self._stream(None))
+        recs, stream = [self._slots[slot] for slot in slots], self._stream(None)
+        results = [_KINDS[r.decoder.kind].read(self.engine, r.decoder, slot, True, stream) for slot, r in zip(slots, recs)]
+        self.engine.pool_segment(slots, keep_encoder, stream)
         segs = []
-        for slot, res in zip(slots, results):
-            index, start = self._seg[slot]
-            self._seg[slot] = tuple(int(v) for v in self.engine.stream_segment(slot))
-            self._ntok[slot] = 0
+        for slot, rec, res in zip(slots, recs, results):
+            index, start = rec.segment
+            rec.segment = tuple(int(v) for v in self.engine.stream_segment(slot))
+            rec.ntok = 0
             if not keep_encoder:
-                self._offset[slot] = 0                  # the encoder starts over; with it kept the estimated offset runs on, as the cache does
-            segs.append(Segment(index, start, self._seg[slot][1] - start, res, eps.get(slot)))
+                rec.offset = 0                          # the encoder starts over; with it kept the estimated offset runs on, as the cache does
+            segs.append(Segment(index, start, rec.segment[1] - start, res, eps.get(slot)))
         return segs
 
-    def _segment_fired(self):
+    def _segment_fired(self, auto: List[int]):
         """step() with on_endpoint slots: ONE endpoints() read, then the slots whose rule has fired, one _finish per flavour."""
-        eps = self.endpoints(sorted(self._on_endpoint))
+        eps = self.endpoints(auto)
         for flavour in ("keep", "fresh"):
-            fired = [slot for slot, e in eps.items() if e.rule != 0 and self._on_endpoint[slot] == flavour]
+            fired = [slot for slot, e in eps.items() if e.rule != 0 and self._slots[slot].on_endpoint == flavour]
             if fired:
                 for seg, slot in zip(self._finish(fired, flavour == "keep", eps), fired):
                     self._segments[slot].append(seg)
@@ -1479,12 +1546,11 @@ class StreamPool:
         flushed, frames waiting for a full chunk belong to the next segment.  keep_encoder=True: the encoder's caches and the offset
         run on (continuous decoding); False: the encoder starts over too, the next chunk's offset is 0.  hot words, keep_frames and
         the endpoint config stay as open() set them."""
-        if slot not in self._offset:
-            raise RnntError(f"slot {slot} is not open")
-        if any(s == slot for s, _ in self._queue) or any(s == slot for s, _, _ in self._wave_queue):
+        rec = self._open_slot(slot)
+        if self._queued(slot):
             self._carry = self.step()                   # the other slots' increments are handed out by the next step()
         self._carry.pop(slot, None)
-        eps = self.endpoints([slot]) if slot in self._endpoint else {}
+        eps = self.endpoints([slot]) if rec.endpoint is not None else {}
         return self._finish([slot], bool(keep_encoder), eps)[0]
 
     def segments(self, slot: int) -> List[Segment]:
@@ -1497,50 +1563,40 @@ class StreamPool:
     def beams(self, slot: int) -> List[BeamHypothesis]:
         """The current hypotheses of a beam slot, in beam order: what process_single_chunk_beam_search returns after each chunk
         (:605-645), also after a skipped < 7-frame chunk (:616-619).  Chunks still queued are not in them: step() first."""
-        if self._beam.get(slot, 0) <= 0:
-            raise RnntError(f"slot {slot} is not an open beam slot")
-        return [BeamHypothesis(t, lp) for t, lp in self.engine.stream_beam(slot, self._stream(None))]
+        return self._read(slot, self._slot_of_kind(slot, "beam"), False)
 
     def ctc_hyps(self, slot: int, final: bool = False):
         """[(tokens, score, times)] of a CTC prefix slot in the search's order, as they stand after the chunks stepped so far (times:
         encoder-frame indices since the slot was opened, or since its current segment began).  final: what the one-launch search returns had the utterance ended here
         (finalize's context score instead of the running one).  Reading changes nothing."""
-        if slot not in self._ctc:
-            raise RnntError(f"slot {slot} is not an open CTC prefix slot")
-        if slot in self._ctc_ngram:                     # the totals carry the n-gram score (final: with the end term)
-            return [(h[0], h[1], h[2]) for h in self.engine.stream_ctc_prefix_ngram(slot, final, stream=self._stream(None))]
-        return [(tok, score, times) for tok, score, times, _ in self.engine.stream_ctc_prefix(slot, final, stream=self._stream(None))]
+        return self._read(slot, self._slot_of_kind(slot, "ctc_prefix"), final)
 
     def prefix_hyps(self, slot: int, final: bool = False, with_context_scores: bool = False):
         """[(tokens including the leading blank, score)] of a transducer prefix slot, best first, as they stand after the chunks
         stepped so far.  A biased slot's scores are the totals (score + context score); final: with finalize's context scores, what
         the one-call search returns had the utterance ended here (no re-sort); with_context_scores: (tokens, score, context score).
         Reading changes nothing."""
-        if slot not in self._prefix:
-            raise RnntError(f"slot {slot} is not an open transducer prefix slot")
-        if slot not in self._prefix_ctx and not with_context_scores:
-            return self.engine.stream_prefix(slot, stream=self._stream(None))
-        hyps = self.engine.stream_prefix_ctx(slot, final, stream=self._stream(None))
-        return hyps if with_context_scores else [(tok, score) for tok, score, _ in hyps]
+        return self._read(slot, self._slot_of_kind(slot, "prefix"), final, with_context_scores)
 
     def endpoints(self, slots: Optional[List[int]] = None) -> Dict[int, Endpoint]:
         """{slot: Endpoint(rule, at_frame, frames, trailing, speech)} of the open slots that detect their endpoint, or of the listed
         ones (each must be such a slot), after the chunks stepped so far: ONE engine call (one download) for all of them, none when
         there is nothing to read.  Chunks still queued are not in it: step() first.  Reading changes nothing."""
         if slots is None:
-            slots = sorted(self._endpoint)
+            slots = sorted(slot for slot, r in self._slots.items() if r.endpoint is not None)
         slots = [int(x) for x in slots]
         for slot in slots:
-            if slot not in self._endpoint:
+            if slot not in self._slots or self._slots[slot].endpoint is None:
                 raise RnntError(f"slot {slot} is not an open slot that detects its endpoint (open(endpoint=EndpointConfig(...)))", ERR_STATE)
         if not slots:
             return {}
         st = self.engine.pool_endpoints(slots, self._stream(None))
         return {slot: Endpoint(int(r[3]), int(r[4]), int(r[0]), int(r[1]), int(r[2])) for slot, r in zip(slots, st)}
 
-    def _require_kept(self, slot: int):
-        if slot not in self._offset or not self._keep.get(slot, False):
+    def _require_kept(self, slot: int) -> _Slot:
+        if slot not in self._slots or not self._slots[slot].keep_frames:
             raise RnntError(f"slot {slot} is not an open slot that keeps its frames (open(keep_frames=True))", ERR_STATE)
+        return self._slots[slot]
 
     def frames(self, slot: int) -> torch.Tensor:
         """The encoder frames [t, 256] of the slot's utterance so far (a device tensor, a copy): what the chunks stepped so far gave,
@@ -1558,11 +1614,10 @@ class StreamPool:
         searches go on, so partial results may be re-scored mid-utterance (queued chunks are not in them: step() first)."""
         slots = [int(x) for x in slots]
         for slot in slots:
-            if slot not in self._ctc and slot not in self._prefix:
+            if slot not in self._slots or _KINDS[self._slots[slot].decoder.kind].first_pass is None:
                 raise RnntError(f"slot {slot} is not an open CTC prefix or transducer prefix slot")
             self._require_kept(slot)
-        first = [[(tok[1:], sc) for tok, sc in self.prefix_hyps(slot, final=True)] if slot in self._prefix else
-                 [(tok, sc) for tok, sc, _ in self.ctc_hyps(slot, final=True)] for slot in slots]
+        first = [_KINDS[self._slots[slot].decoder.kind].first_pass(self._read(slot, self._slots[slot], True)) for slot in slots]
         nh, hl, ht = pack_nbest([[tok for tok, _ in row] for row in first])
         nll = self.engine.pool_rescore(slots, nh, hl, ht, self._stream(None))
         return {slot: select_rescored([tok for tok, _ in row], [sc for _, sc in row], nll[i, :nh[i]], ctc_weight, transducer_weight)
@@ -1572,8 +1627,7 @@ class StreamPool:
         """[(start_s, end_s)] per token emitted so far by a GREEDY slot that keeps its frames: the best transducer alignment
         (rnnt_transducer_align) of its tokens over its kept frames, then timestamps_from_peaks of the emit frames with max_duration
         = the frames so far.  Raises RnntError beyond 255 tokens (the alignment's range)."""
-        self._require_kept(slot)
-        if self._beam.get(slot, 0) > 0 or slot in self._ctc or slot in self._prefix:
+        if self._require_kept(slot).decoder.kind != "greedy":
             raise RnntError(f"slot {slot} is not a greedy slot")
         s = self._stream(None)
         tokens = self.engine.stream_tokens(slot, 0, s)
@@ -1589,22 +1643,14 @@ class StreamPool:
     def close(self, slot: int):
         """Finish the slot's utterance (queued chunks are processed first) and free the slot; returns all its tokens (greedy slot),
         its final hypotheses (beam slot), ctc_hyps(slot, final=True) (CTC prefix slot) or prefix_hyps(slot, final=True) (transducer prefix slot)."""
-        if slot not in self._offset:
-            raise RnntError(f"slot {slot} is not open")
-        if self._fed.get(slot) == "wave" and not self._wave_final[slot]:
+        rec = self._open_slot(slot)
+        if rec.fed == "wave" and not rec.wave_final:
             self.feed_wave(slot, torch.zeros(0, dtype=torch.float32), final=True)   # the caller hung up: flush the tail
-        if any(s == slot for s, _ in self._queue) or any(s == slot for s, _, _ in self._wave_queue):
+        if self._queued(slot):
             self._carry = self.step()                   # the other slots' increments are handed out by the next step()
         self._carry.pop(slot, None)
-        self._forget_wave(slot)
-        self._endpoint.pop(slot, None)                  # the library clears its flag when the slot is opened again
-        self._on_endpoint.pop(slot, None)
-        res = self._result(slot)
-        self._prefix.pop(slot, None)
-        self._prefix_ctx.pop(slot, None)
-        self._ctc.pop(slot, None)
-        self._ctc_ngram.pop(slot, None)
-        del self._offset[slot], self._ntok[slot], self._beam[slot], self._seg[slot]
+        res = self._read(slot, rec, True)
+        del self._slots[slot]                           # nothing else to forget; the library clears its flags when the slot is opened again
         self._free.append(slot)
         self._free.sort()
         return res

@@ -168,7 +168,7 @@ def test_stream_pool_routes_biased_prefix_slots():
     g, g2 = ContextBias([[1, 2]], 6.0), ContextBias([[3]], 2.0)
     b0 = pool.open(prefix_beam=4, prefix_context=g)
     u1 = pool.open(prefix_beam=4)
-    assert (b0, u1) == (0, 1) and fake.graphs == [([[1, 2]], 6.0)] and pool._prefix[b0] == (4, 0.3, 0.7)
+    assert (b0, u1) == (0, 1) and fake.graphs == [([[1, 2]], 6.0)] and pool._slots[b0].decoder == ("prefix", 4, True, (0.3, 0.7), False)
     for s in (b0, u1):
         assert pool.feed(s, torch.zeros(16, 80))
     pool.step()
@@ -184,7 +184,7 @@ def test_stream_pool_routes_biased_prefix_slots():
         assert fake.opened == [0, 1] and pool._free == [2, 3] and len(fake.graphs) == 1, kw
     c2 = pool.open(ctc_prefix_beam=4, context=g)                      # the current graph serves both kinds
     assert c2 == 2 and len(fake.graphs) == 1
-    assert pool.close(b0) == [([5, 1], 7.5)] and b0 not in pool._prefix_ctx        # close() reads the final totals
+    assert pool.close(b0) == [([5, 1], 7.5)] and b0 not in pool._slots        # close() reads the final totals
     with pytest.raises(rlib.RnntError):
         pool.open(prefix_beam=4, prefix_context=g2)                   # the biased CTC slot still holds the graph
     assert pool._free == [0, 3]

@@ -253,11 +253,11 @@ def test_open_refused_by_the_library_takes_no_slot():
     for _ in range(3):                                          # more refusals than the pool has slots
         with pytest.raises(rlib.RnntError):
             pool.open(ctc_prefix_beam=4, context=ContextBias([[]], 2.0))
-        assert pool._free == free and fake.opened == opened and pool._context is ctx and pool._ctc == {} and pool._offset == {}
+        assert pool._free == free and fake.opened == opened and pool._context is ctx and pool._slots == {}
     fake.bad_graph, fake.bad_open = False, True
     with pytest.raises(rlib.RnntError):
         pool.open(ctc_prefix_beam=4)
-    assert pool._free == free and pool._ctc == {} and pool._offset == {}
+    assert pool._free == free and pool._slots == {}
     fake.bad_open = False
     assert pool.open(ctc_prefix_beam=4, context=good) == 0 and pool.open() == 1 and len(fake.graphs) == 1
     assert pool.close(0) == [([], 1.0, [])]

@@ -166,9 +166,9 @@ def test_open_exclusivity_and_range_errors_take_no_slot():
     for kw in bad:
         with pytest.raises(rlib.RnntError):
             pool.open(**kw)
-        assert fake.opened == [] and pool._free == [0, 1] and pool._prefix == {} and pool._offset == {}, kw
+        assert fake.opened == [] and pool._free == [0, 1] and pool._slots == {}, kw
     assert pool.open(prefix_beam=16, ctc_weight=0.0, transducer_weight=1.0) == 0
-    assert pool._prefix == {0: (16, 0.0, 1.0)}
+    assert {s: r.decoder for s, r in pool._slots.items()} == {0: ("prefix", 16, False, (0.0, 1.0), False)}
     wide = StreamPool(None, 1, engine=FakeEngine(), vocab_size=600)
     with pytest.raises(rlib.RnntError):
         wide.open(prefix_beam=4)                               # vocabulary > 512
@@ -210,7 +210,7 @@ def test_stream_pool_routes_prefix_slots():
     pool.feed(p1, torch.zeros(16, 80))
     assert pool.close(p1) == [([5, 10, 11], -1.5), ([5, 10, 11, 7], -2.5)]
     assert fake.calls[n_calls:] == [("prefix", [1], 16, [4], [4], 5, (0.3, 0.7))]
-    assert 1 not in pool._prefix and pool.open() == 1 and pool.step() == {}      # the freed slot is reused, as any kind
+    assert 1 not in pool._slots and pool.open() == 1 and pool.step() == {}      # the freed slot is reused, as any kind
 
 
 def test_rescore_takes_prefix_slots():
