@@ -279,7 +279,9 @@ int launch_gemm(rnnt_ctx* ctx, hipStream_t s, const GemmP* gs, int ng, int tag =
         return RNNT_OK;
     }
     const bool wide = maxN >= 512;
-    const int wkk = K >= 1024 ? 8 : 4;
+    // 8 waves over K from 1024 on where K splits into eight multiples of 16; otherwise 4 (the front-end's K = n_fft or
+    // roundup64(n_fft/2 + 1) is a multiple of 64 but, above 1024, often not of 128: 1088, 1600, 2112, ...)
+    const int wkk = K >= 1024 && K % 128 == 0 ? 8 : 4;
     if (K % (wkk * 16) != 0) return fail(ctx, RNNT_ERR_SHAPE, "gemm16 K=%d not divisible by %d", K, wkk * 16);
     if (wide) { if (wkk == 8) launch_gemm16<8, 2>(s, gb, maxM, maxN, ng); else launch_gemm16<4, 2>(s, gb, maxM, maxN, ng); }
     else { if (wkk == 8) launch_gemm16<8, 1>(s, gb, maxM, maxN, ng); else launch_gemm16<4, 1>(s, gb, maxM, maxN, ng); }

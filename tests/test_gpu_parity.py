@@ -488,8 +488,10 @@ def test_ctc_greedy_search_matches_reference(seed, np_state_dict, numerics):
 
 def test_fbank_frontend_against_oracle(models):
     """rnnt_fbank (windowed DFT + mel projection as f32 MFMA GEMMs, dB epilogue) vs the NumPy float64 restatement of
-    torchaudio's MelSpectrogram + AmplitudeToDB.  PARITY UNPINNED against the reference itself (no torchaudio here, no
-    fixture in the reference); tolerance 2e-3 dB on bins above -60 dB (f32 DFT by GEMM vs f64 FFT), 0.05 dB below."""
+    torchaudio's MelSpectrogram + AmplitudeToDB.  PARITY HALF PINNED: the oracle's spectrogram half is held to torch.stft
+    (test_fbank_cpu.py), its mel / dB half is a restatement (no torchaudio here, no fixture in the reference); tolerance
+    2e-3 dB on bins above -60 dB (f32 DFT by GEMM vs f64 FFT), 0.05 dB below.  The whole range and the bars by depth under
+    the frame's peak: test_fbank.py."""
     from oracle import fbank_oracle as F
     from ctc_vr_amd.features import extract_audio_features
     eng = models(0, 16)._engine
