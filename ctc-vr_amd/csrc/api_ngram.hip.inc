@@ -1,4 +1,4 @@
-// C ABI: the back-off n-gram model the CTC prefix beam search fuses (rnnt_ngram_set, rnnt_ngram_walk_host, rnnt_ngram_score).
+// C ABI: the back-off n-gram model the CTC and the transducer prefix beam search fuse (rnnt_ngram_set, rnnt_ngram_walk_host, rnnt_ngram_score).
 // Included by rnnt_api.hip inside extern "C".  Tables, step and the scoring kernel: rnnt_ngram.hip.h.  The builder and the walk are
 // pure C++ (no context, no GPU).
 //
@@ -125,7 +125,7 @@ int rnnt_ngram_set(rnnt_ctx* ctx, int32_t n_ngrams, const int32_t* lens_host, co
     HIPCHK(hipMemcpy(ctx->ng_d, hd.data(), hd.size() * sizeof(double), hipMemcpyHostToDevice));
     ctx->ng = std::move(m);
     ctx->ng_on = true;
-    ++ctx->ng_gen;                                                   // a pool search fused with the previous model holds its node ids (api_pool_ctc.hip.inc)
+    ++ctx->ng_gen;                                                   // a pool search fused with the previous model holds its node ids (api_pool_ctc.hip.inc, api_pool_prefix.hip.inc)
     return RNNT_OK;
 }
 

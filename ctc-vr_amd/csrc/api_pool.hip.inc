@@ -118,7 +118,7 @@ enum { POOL_ENCODE = 0, POOL_GREEDY = 1, POOL_BEAM = 2, POOL_CTC_PREFIX = 3, POO
 // rnnt_pool_chunk (mode POOL_ENCODE / POOL_GREEDY), rnnt_pool_chunk_beam (POOL_BEAM), rnnt_pool_chunk_ctc_prefix (POOL_CTC_PREFIX) and
 // rnnt_pool_chunk_prefix (POOL_PREFIX): validation, the call's table, the encoder launches and the position bookkeeping are one code
 // path; only what follows the encoder differs.  use_context: POOL_CTC_PREFIX and POOL_PREFIX; ctc_weight / transducer_weight: POOL_PREFIX only;
-// use_ngram: POOL_CTC_PREFIX only.
+// use_ngram: POOL_CTC_PREFIX and POOL_PREFIX.
 int pool_chunk_run(rnnt_ctx* ctx, const char* fn, int32_t n_active, const int32_t* slots_host, const float* fbank_dev, int32_t T,
                    const int32_t* offsets_host, const int32_t* required_host, int mode, int32_t beam_size, int32_t* frames_out, void* stream,
                    int32_t use_context = 0, float ctc_weight = 0.f, float transducer_weight = 0.f, int32_t use_ngram = 0) {
@@ -186,7 +186,7 @@ int pool_chunk_run(rnnt_ctx* ctx, const char* fn, int32_t n_active, const int32_
         if ((rc = pool_ctc_alloc(ctx, s))) return rc;
     }
     if (mode == POOL_PREFIX) {       // likewise for the transducer prefix search
-        if ((rc = pool_prefix_check(ctx, fn, n, slots_host, tq, beam_size, ctc_weight, transducer_weight, use_context))) return rc;
+        if ((rc = pool_prefix_check(ctx, fn, n, slots_host, tq, beam_size, ctc_weight, transducer_weight, use_context, use_ngram))) return rc;
         if ((rc = pool_prefix_alloc(ctx, s, (size_t)n * tq, ctc_weight > 0.f))) return rc;
     }
     if ((rc = pool_alloc(ctx))) return rc;
@@ -267,7 +267,7 @@ int pool_chunk_run(rnnt_ctx* ctx, const char* fn, int32_t n_active, const int32_
             if ((rc = rnnt_ctc_logprobs(ctx, ctx->x, n * tq, ctx->pp_ctc, stream))) return rc;
         }
         return pool_prefix_launch(ctx, s, n, slots_host, slots_dev, ctx->pool_tab + (size_t)n * (POOL_ROW_INTS + 1), tq, beam_size, ctc_weight,
-                                  transducer_weight, use_context);   // the frames are consumed: frames_buffered stays 0
+                                  transducer_weight, use_context, use_ngram);   // the frames are consumed: frames_buffered stays 0
     }
     if (mode == POOL_ENCODE) {   // frames [0, t') of the active slots stay buffered for rnnt_get_enc_frames until rnnt_frames_discard
         hipLaunchKernelGGL(pool_scatter_frames, dim3(grid_for((long long)n * tq * (D / 4))), dim3(256), 0, s, ctx->x, ctx->encbuf, rows_dev, n, tq,
@@ -321,8 +321,15 @@ int rnnt_pool_chunk_prefix(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots
 int rnnt_pool_chunk_prefix_ctx(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, const float* fbank_dev, int32_t T, const int32_t* offsets_host,
                                const int32_t* required_host, int32_t beam_size, float ctc_weight, float transducer_weight, int32_t use_context,
                                int32_t* frames_out, void* stream) {
+    return rnnt_pool_chunk_prefix_ngram(ctx, n_active, slots_host, fbank_dev, T, offsets_host, required_host, beam_size, ctc_weight, transducer_weight,
+                                        use_context, 0, frames_out, stream);
+}
+
+int rnnt_pool_chunk_prefix_ngram(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, const float* fbank_dev, int32_t T, const int32_t* offsets_host,
+                                 const int32_t* required_host, int32_t beam_size, float ctc_weight, float transducer_weight, int32_t use_context,
+                                 int32_t use_ngram, int32_t* frames_out, void* stream) {
     return pool_chunk_run(ctx, "rnnt_pool_chunk_prefix", n_active, slots_host, fbank_dev, T, offsets_host, required_host, POOL_PREFIX, beam_size,
-                          frames_out, stream, use_context, ctc_weight, transducer_weight);
+                          frames_out, stream, use_context, ctc_weight, transducer_weight, use_ngram);
 }
 
 namespace {

@@ -719,21 +719,22 @@ int pool_ctc_reset(rnnt_ctx* ctx, hipStream_t s, int slot0, int n) {
 PrefixPoolP pool_prefix_params(const rnnt_ctx* ctx) {
     PrefixPoolP q;
     memset(&q, 0, sizeof(q));
-    for (int t = 0; t < 2; ++t) { q.pool[t] = ctx->pp_pool[t]; q.tk[t] = ctx->pp_tk[t]; q.len[t] = ctx->pp_len[t]; q.sc[t] = ctx->pp_sc[t]; q.hs[t] = ctx->pp_hs[t]; q.cst[t] = ctx->pp_cst[t]; q.cs[t] = ctx->pp_cs[t]; }
+    for (int t = 0; t < 2; ++t) { q.pool[t] = ctx->pp_pool[t]; q.tk[t] = ctx->pp_tk[t]; q.len[t] = ctx->pp_len[t]; q.sc[t] = ctx->pp_sc[t]; q.hs[t] = ctx->pp_hs[t]; q.cst[t] = ctx->pp_cst[t]; q.cs[t] = ctx->pp_cs[t]; q.nst[t] = ctx->pp_nst[t]; q.ns[t] = ctx->pp_ns[t]; }
     q.nh = ctx->pp_nh;
     return q;
 }
 
 // The block prefix_pack / prefix_pack_pool write and one copy downloads, on the device or in its host copy (the one-call search with
-// its B, a slot's read with B = 1): scores [R] | context scores [R] as doubles, the ints n_hyp [B] | lens [R] | tokens [R][lcap], and
-// with_states the floats h [R][256] | c [R][256].  bytes: its size.
-struct PrefixOut { double *sc, *cs; int *nh, *len, *tk; float *h, *c; size_t bytes; };
+// its B, a slot's read with B = 1): scores [R] | context scores [R] | n-gram scores [R] as doubles, the ints n_hyp [B] | lens [R] |
+// tokens [R][lcap], and with_states the floats h [R][256] | c [R][256].  bytes: its size.
+struct PrefixOut { double *sc, *cs, *ns; int *nh, *len, *tk; float *h, *c; size_t bytes; };
 PrefixOut prefix_out(double* base, size_t B, size_t R, size_t lcap, bool with_states) {
     Carve<char> b{reinterpret_cast<char*>(base)};
     auto take = [&](auto*& q, size_t n) { q = reinterpret_cast<std::remove_reference_t<decltype(q)>>(b.take(n * sizeof(*q))); };
     PrefixOut o;
     take(o.sc, R);
     take(o.cs, R);
+    take(o.ns, R);
     take(o.nh, B);
     take(o.len, R);
     take(o.tk, R * lcap);
@@ -744,10 +745,11 @@ PrefixOut prefix_out(double* base, size_t B, size_t R, size_t lcap, bool with_st
 }
 // its host copy into the caller's arrays (rows of cap_tokens; a row's tokens up to its length)
 void prefix_out_copy(const PrefixOut& o, size_t R, size_t lcap, size_t cap_tokens, int32_t* lens, int32_t* tokens, double* scores, double* ctx_scores,
-                     float* h, float* c) {
+                     double* ng_scores, float* h, float* c) {
     memcpy(lens, o.len, R * sizeof(int));
     memcpy(scores, o.sc, R * sizeof(double));
     if (ctx_scores) memcpy(ctx_scores, o.cs, R * sizeof(double));
+    if (ng_scores) memcpy(ng_scores, o.ns, R * sizeof(double));
     for (size_t r = 0; r < R; ++r) memcpy(tokens + r * cap_tokens, o.tk + r * lcap, (size_t)o.len[r] * sizeof(int));
     if (h) { memcpy(h, o.h, R * D * sizeof(float)); memcpy(c, o.c, R * D * sizeof(float)); }
 }

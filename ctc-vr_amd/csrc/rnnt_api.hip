@@ -119,7 +119,7 @@ using PinnedBuf = DevBuf<T, true>;
 
 // Per slot of the stream pool, on the host.  SearchSlot, a prefix search carried across calls: the frames walked, and what its first
 // advancing call fixed until the next reset -- beam (0: fresh), the two weights (0 for the CTC search), use_context, the graph
-// generation (rnnt_ctx::cg_gen); the CTC search also use_ngram and the model generation (rnnt_ctx::ng_gen).  WvSlot, the front-end: samples received and frames emitted since the reset, the (sample_rate,
+// generation (rnnt_ctx::cg_gen); either search also use_ngram and the model generation (rnnt_ctx::ng_gen).  WvSlot, the front-end: samples received and frames emitted since the reset, the (sample_rate,
 // n_fft) its first push fixed (n_fft == 0: fresh), whether its utterance has ended.  HsSlot, the frame history: flag and length.
 // ep: endpoint detection is on (the config and the counters live on the device, api_pool_endpoint.hip.inc).  SegSlot, the segment
 // record (api_pool_segment.hip.inc): segments started since the slot was opened, the encoder frames it had encoded when the current
@@ -329,11 +329,12 @@ struct rnnt_ctx {
     // lengths / scores / hashes [rows] -- plus the hypotheses per slot, the step's top-k [rows][PB_MAX_BEAM], the frames of one call
     // (projected, CTC log-probabilities; grow-only), the seam form's table (slot and current set per active row, [max_streams] 2 ints)
     // and one read's packed block.  Host per slot: PoolSlot::prefix and prefix_cur (slots advance independently).  A biased search
-    // also keeps a context state and score per row (pp_cst / pp_cs).
+    // also keeps a context state and score per row (pp_cst / pp_cs), a search that fuses the n-gram model an n-gram state and score
+    // (pp_nst / pp_ns).
     int prefix_group = 0;                      // RNNT_PREFIX_GROUP: 0 by the size of the launch, 1 / 4 hypotheses per prefix_step_pool workgroup always
     DevBuf<float> pp_pool[2], pp_toplp, pp_encp, pp_ctc;
-    DevBuf<int> pp_tk[2], pp_len[2], pp_cst[2], pp_nh, pp_toptok;
-    DevBuf<double> pp_sc[2], pp_cs[2], pp_out;
+    DevBuf<int> pp_tk[2], pp_len[2], pp_cst[2], pp_nst[2], pp_nh, pp_toptok;
+    DevBuf<double> pp_sc[2], pp_cs[2], pp_ns[2], pp_out;
     DevBuf<unsigned long long> pp_hs[2];
     CallTab pp_tab;
     // streaming feature front-end per slot of the stream pool (api_pool_wave.hip.inc), allocated on its first use: the carry of every

@@ -1,4 +1,5 @@
-// Back-off n-gram model for shallow fusion in the CTC prefix search (rnnt_ctc_prefix.hip.h) as the flat tables rnnt_ngram_set uploads,
+// Back-off n-gram model for shallow fusion in the CTC prefix search (rnnt_ctc_prefix.hip.h) and the transducer prefix search
+// (rnnt_prefix.hip.h) as the flat tables rnnt_ngram_set uploads,
 // its step, and the kernel that scores given token sequences with it (ngram_score_rows).
 // Part of rnnt_kernels.hip.h (include that umbrella, not this file).
 //

@@ -167,6 +167,13 @@ struct PrefixCtxP {
     const int* cst_in; int* cst_out;            // [rows] context state: the graph node of the hypothesis' token sequence
     const double* cs_in; double* cs_out;        // [rows] context score, kept beside the running score
 };
+// n-gram shallow fusion: the model and, per row of either set, the n-gram state and score.  The host launches the _ngram kernels
+// (prefix_merge_rows<., true>) when the search fuses a model; the others neither take nor read this block.
+struct PrefixNgP {
+    NgTables g;
+    const int* nst_in; int* nst_out;            // [rows] n-gram state: the model node of the token sequence, NG_START before the first token
+    const double* ns_in; double* ns_out;        // [rows] n-gram score, kept beside the running score
+};
 
 // list form of wenet.utils.common.log_add for two values, as Python evaluates it: -inf if both are, else max + log(sum of exp)
 __host__ __device__ inline double prefix_log_add(double a, double b) {
@@ -189,11 +196,16 @@ __host__ __device__ inline double prefix_log_add(double a, double b) {
 // total = fused score + context score (ties to the lower candidate index as before) and the survivors' state and score are
 // gathered with the rest.  The first prune (prefix_step) does not see the graph, as search.py:156 does not.  Without a graph
 // (GRAPH = false: x is not read, the two arrays do not exist) the arithmetic is what it was: the key is the fused score itself.
+// With an n-gram model (NG; the CTC search's rule, rnnt_ctc_prefix.hip.h, carried over): candidate c likewise takes its n-gram state and
+// score in its own thread -- a blank copies row j's, any other token is one ng_step from row j's state (NG_START: the model's start
+// state), its score added to row j's -- into two more LDS arrays (3 KB); fusion keeps the first candidate's; the order is by
+// fused score + context score + n-gram score, left to right, a term whose feature is off left out.  NG = false: n is not read, the
+// two arrays do not exist, the code is what it was.
 // An utterance past its last frame (f >= lens[b]) is carried over unchanged.
 // prefix_merge_rows: the merge of the utterance whose hypothesis count is nh[u] (and frame count lens[u], when lens is given) and
 // whose rows start at row0 of either set; one workgroup.  Called by the batch kernel and by the pool kernel.
-template <bool GRAPH>
-__device__ __forceinline__ void prefix_merge_rows(const PrefixMergeP& p, const PrefixCtxP& x, int u, int row0) {
+template <bool GRAPH, bool NG>
+__device__ __forceinline__ void prefix_merge_rows(const PrefixMergeP& p, const PrefixCtxP& x, const PrefixNgP& n, int u, int row0) {
     __shared__ double sc[PB_MAX_CAND];
     __shared__ unsigned long long hsh[PB_MAX_CAND];
     __shared__ int clen[PB_MAX_CAND], ctok[PB_MAX_CAND], first[PB_MAX_CAND], rep[PB_MAX_CAND];
@@ -204,6 +216,8 @@ __device__ __forceinline__ void prefix_merge_rows(const PrefixMergeP& p, const P
     __shared__ int s_best;
     __shared__ double ccs[PB_MAX_CAND];
     __shared__ int ccst[PB_MAX_CAND];
+    __shared__ double cns[PB_MAX_CAND];
+    __shared__ int cnst[PB_MAX_CAND];
     const int tid = threadIdx.x;
     const int nh = p.nh[u];
     if (p.lens && p.f >= p.lens[u]) {                                // finished: carry the rows over unchanged
@@ -215,6 +229,7 @@ __device__ __forceinline__ void prefix_merge_rows(const PrefixMergeP& p, const P
             if (tid == 0) {
                 p.len_out[r] = len; p.sc_out[r] = p.sc_in[r]; p.hs_out[r] = p.hs_in[r];
                 if constexpr (GRAPH) { x.cst_out[r] = x.cst_in[r]; x.cs_out[r] = x.cs_in[r]; }
+                if constexpr (NG) { n.nst_out[r] = n.nst_in[r]; n.ns_out[r] = n.ns_in[r]; }
             }
         }
         return;
@@ -237,6 +252,13 @@ __device__ __forceinline__ void prefix_merge_rows(const PrefixMergeP& p, const P
             if (!bl) cs += cg_step(x.g.fail, x.g.off, x.g.ctok, x.g.cid, x.g.tscore, x.g.nscore, x.g.oscore, nx, tok, &nx);
             ccst[tid] = nx;
             ccs[tid] = cs;
+        }
+        if constexpr (NG) {                                          // the back-off chain diverges per lane, and is at most the model's order long
+            int nx = n.nst_in[r];
+            double ns = n.ns_in[r];
+            if (!bl) ns += ng_step(n.g, nx, tok, &nx);
+            cnst[tid] = nx;
+            cns[tid] = ns;
         }
     }
     __syncthreads();
@@ -282,6 +304,7 @@ __device__ __forceinline__ void prefix_merge_rows(const PrefixMergeP& p, const P
         if (tid < C && rep[tid] == tid && !taken[tid]) {
             if constexpr (GRAPH) bv = sc[tid] + ccs[tid];
             else bv = sc[tid];
+            if constexpr (NG) bv = bv + cns[tid];
             bi = tid;
         }
 #pragma unroll
@@ -315,18 +338,21 @@ __device__ __forceinline__ void prefix_merge_rows(const PrefixMergeP& p, const P
             p.sc_out[nr] = sc[c];
             p.hs_out[nr] = hsh[c];
             if constexpr (GRAPH) { x.cst_out[nr] = ccst[c]; x.cs_out[nr] = ccs[c]; }
+            if constexpr (NG) { n.nst_out[nr] = cnst[c]; n.ns_out[nr] = cns[c]; }
             if (p.src_row) { p.src_row[nr] = j; p.src_slot[nr] = slot; }
         }
     }
     if (tid == 0) p.nh[u] = n_acc;
 }
 
-__global__ __launch_bounds__(PB_NT) void prefix_merge(PrefixMergeP p) { prefix_merge_rows<false>(p, PrefixCtxP{}, blockIdx.x, blockIdx.x * p.beam); }
-__global__ __launch_bounds__(PB_NT) void prefix_merge_ctx(PrefixMergeP p, PrefixCtxP x) { prefix_merge_rows<true>(p, x, blockIdx.x, blockIdx.x * p.beam); }
+__global__ __launch_bounds__(PB_NT) void prefix_merge(PrefixMergeP p) { prefix_merge_rows<false, false>(p, PrefixCtxP{}, PrefixNgP{}, blockIdx.x, blockIdx.x * p.beam); }
+__global__ __launch_bounds__(PB_NT) void prefix_merge_ctx(PrefixMergeP p, PrefixCtxP x) { prefix_merge_rows<true, false>(p, x, PrefixNgP{}, blockIdx.x, blockIdx.x * p.beam); }
+__global__ __launch_bounds__(PB_NT) void prefix_merge_ngram(PrefixMergeP p, PrefixNgP n) { prefix_merge_rows<false, true>(p, PrefixCtxP{}, n, blockIdx.x, blockIdx.x * p.beam); }
+__global__ __launch_bounds__(PB_NT) void prefix_merge_ctx_ngram(PrefixMergeP p, PrefixCtxP x, PrefixNgP n) { prefix_merge_rows<true, true>(p, x, n, blockIdx.x, blockIdx.x * p.beam); }
 
 // Start of a call: every utterance holds the one hypothesis [blank] with score 0 and the zero LSTM state (:68-77) in set 0.
-__global__ __launch_bounds__(256) void prefix_init(float* pool, int* tk, int* len, double* sc, unsigned long long* hs, int* cst, double* cs, int* nh,
-                                                   int beam, int lcap, int blank) {
+__global__ __launch_bounds__(256) void prefix_init(float* pool, int* tk, int* len, double* sc, unsigned long long* hs, int* cst, double* cs, int* nst,
+                                                   double* ns, int* nh, int beam, int lcap, int blank) {
     const int b = blockIdx.x, r = b * beam;
     for (int e = threadIdx.x; e < 512; e += 256) pool[(long long)r * 1024 + e] = 0.f;
     if (threadIdx.x == 0) {
@@ -336,18 +362,27 @@ __global__ __launch_bounds__(256) void prefix_init(float* pool, int* tk, int* le
         hs[r] = beam_hash_step(BEAM_HASH0, blank);
         cst[r] = 0;                                                  // the context root; the leading blank is never fed to the graph
         cs[r] = 0.0;
+        nst[r] = NG_START;                                           // resolved by the first step under the model of the call; the blank is never fed to it
+        ns[r] = 0.0;
         nh[b] = 1;
     }
 }
 
-// End of a call: the final set into ONE block for one download: scores f64 [rows] | context scores f64 [rows] | n_hyp [B] | lengths
-// [rows] | tokens [rows][lcap] | h [rows][256] | c [rows][256] (states only if with_states).  Rows without a hypothesis are zero.
+// The n-gram part of a packed hypothesis: its running score, plus the end term (NG_START resolves to the start state) when the
+// utterance has ended.
+__device__ __forceinline__ double prefix_pack_ngram(const NgTables& g, int state, double score, bool fin) { return fin ? score + ng_eos(g, state) : score; }
+
+// End of a call: the final set into ONE block for one download: scores f64 [rows] | context scores f64 [rows] | n-gram scores f64
+// [rows] | n_hyp [B] | lengths [rows] | tokens [rows][lcap] | h [rows][256] | c [rows][256] (states only if with_states).  Rows
+// without a hypothesis are zero.
 // cst != nullptr: a biased search, whose returned score is the total; fin_nscore != nullptr: the utterance has ended and finalize
-// (context_graph.py:264) REPLACES the context score (search.py:229-231), in the total too.
+// (context_graph.py:264) REPLACES the context score (search.py:229-231), in the total too.  nst != nullptr: a search fused with the
+// model ng; the utterance has ended, so the end term is added to the n-gram part and -- after the context part -- to the total.
 __global__ __launch_bounds__(256) void prefix_pack(const float* pool, const int* tk, const int* len, const double* sc, const int* cst, const double* cs,
-                                                   const double* fin_nscore, const int* nh, int B, int beam, int lcap, int with_states, double* out) {
+                                                   const double* fin_nscore, const int* nst, const double* ns, NgTables ng, const int* nh, int B, int beam,
+                                                   int lcap, int with_states, double* out) {
     const int r = blockIdx.x, b = r / beam, i = r - b * beam, rows = B * beam, tid = threadIdx.x;
-    int* oi = reinterpret_cast<int*>(out + 2 * rows);
+    int* oi = reinterpret_cast<int*>(out + 3 * rows);
     int* o_len = oi + B;
     int* o_tk = o_len + rows;
     float* o_h = reinterpret_cast<float*>(o_tk + (long long)rows * lcap);
@@ -361,8 +396,12 @@ __global__ __launch_bounds__(256) void prefix_pack(const float* pool, const int*
     }
     if (tid == 0) {
         const double c = live && cst ? (fin_nscore ? -fin_nscore[cst[r]] : cs[r]) : 0.0;
-        out[r] = live ? (cst ? sc[r] + c : sc[r]) : 0.0;
+        const double g = live && nst ? prefix_pack_ngram(ng, nst[r], ns[r], true) : 0.0;
+        double tot = live ? (cst ? sc[r] + c : sc[r]) : 0.0;
+        if (live && nst) tot = tot + g;
+        out[r] = tot;
         out[rows + r] = c;
+        out[2 * rows + r] = g;
         o_len[r] = n;
         if (i == 0) oi[b] = nh[b];
     }
@@ -384,6 +423,7 @@ struct PrefixPoolP {
     double* sc[2];
     unsigned long long* hs[2];
     int* cst[2]; double* cs[2];  // context state and score per row (read and written by biased searches only)
+    int* nst[2]; double* ns[2];  // n-gram state and score per row (read and written by searches that fuse a model only)
     int* nh;                     // [slots]
 };
 constexpr int PB_GROUP = 4;      // hypotheses of one slot per workgroup of the grouped prefix_step_pool: one pass over the weights for all of them
@@ -403,9 +443,10 @@ __global__ __launch_bounds__(512) void prefix_step_pool(PrefixStepP p, PrefixPoo
 }
 
 // prefix_merge for one ACTIVE slot per workgroup: from the slot's current set into its other one.  p carries prefix_step_pool's
-// outputs and the call's scalars (lens = nullptr: the slot has this frame); its buffer pointers are set here.  GRAPH: biased by g.
-template <bool GRAPH>
-__device__ __forceinline__ void prefix_merge_pool_rows(PrefixMergeP p, const PrefixPoolP& q, const CpGraph& g) {
+// outputs and the call's scalars (lens = nullptr: the slot has this frame); its buffer pointers are set here.  GRAPH: biased by g;
+// NG: fused with the model ng.
+template <bool GRAPH, bool NG>
+__device__ __forceinline__ void prefix_merge_pool_rows(PrefixMergeP p, const PrefixPoolP& q, const CpGraph& g, const NgTables& ng) {
     const int a = blockIdx.x, slot = ldgi(q.slots + a);
     const int cur = (ldgi(q.cur0 + a) + p.f) & 1, nxt = cur ^ 1;
     p.pool_in = q.pool[cur]; p.pool_out = q.pool[nxt];
@@ -420,10 +461,18 @@ __device__ __forceinline__ void prefix_merge_pool_rows(PrefixMergeP p, const Pre
         x.cst_in = q.cst[cur]; x.cst_out = q.cst[nxt];
         x.cs_in = q.cs[cur]; x.cs_out = q.cs[nxt];
     }
-    prefix_merge_rows<GRAPH>(p, x, slot, slot * PB_MAX_BEAM);
+    PrefixNgP n{};
+    if constexpr (NG) {
+        n.g = ng;
+        n.nst_in = q.nst[cur]; n.nst_out = q.nst[nxt];
+        n.ns_in = q.ns[cur]; n.ns_out = q.ns[nxt];
+    }
+    prefix_merge_rows<GRAPH, NG>(p, x, n, slot, slot * PB_MAX_BEAM);
 }
-__global__ __launch_bounds__(PB_NT) void prefix_merge_pool(PrefixMergeP p, PrefixPoolP q) { prefix_merge_pool_rows<false>(p, q, CpGraph{}); }
-__global__ __launch_bounds__(PB_NT) void prefix_merge_pool_ctx(PrefixMergeP p, PrefixPoolP q, CpGraph g) { prefix_merge_pool_rows<true>(p, q, g); }
+__global__ __launch_bounds__(PB_NT) void prefix_merge_pool(PrefixMergeP p, PrefixPoolP q) { prefix_merge_pool_rows<false, false>(p, q, CpGraph{}, NgTables{}); }
+__global__ __launch_bounds__(PB_NT) void prefix_merge_pool_ctx(PrefixMergeP p, PrefixPoolP q, CpGraph g) { prefix_merge_pool_rows<true, false>(p, q, g, NgTables{}); }
+__global__ __launch_bounds__(PB_NT) void prefix_merge_pool_ngram(PrefixMergeP p, PrefixPoolP q, NgTables ng) { prefix_merge_pool_rows<false, true>(p, q, CpGraph{}, ng); }
+__global__ __launch_bounds__(PB_NT) void prefix_merge_pool_ctx_ngram(PrefixMergeP p, PrefixPoolP q, CpGraph g, NgTables ng) { prefix_merge_pool_rows<true, true>(p, q, g, ng); }
 
 // The reset of slots [slot0, slot0 + gridDim.x): prefix_init's start (hypothesis [blank], score 0, zero state) in set 0; the host's
 // set index goes to 0 with it.  Touches no other slot.  prefix_slot_start: the same for one slot, by a workgroup of 256.
@@ -437,19 +486,22 @@ __device__ __forceinline__ void prefix_slot_start(const PrefixPoolP& q, int slot
         q.hs[0][r] = beam_hash_step(BEAM_HASH0, blank);
         q.cst[0][r] = 0;
         q.cs[0][r] = 0.0;
+        q.nst[0][r] = NG_START;
+        q.ns[0][r] = 0.0;
         q.nh[slot] = 1;
     }
 }
 __global__ __launch_bounds__(256) void prefix_init_pool(PrefixPoolP q, int slot0, int lcap, int blank) { prefix_slot_start(q, slot0 + blockIdx.x, lcap, blank); }
 
 // One slot's set `cur` into ONE block for one download (rnnt_stream_get_prefix), one workgroup per row i < beam: scores f64 [beam] |
-// context scores f64 [beam] | n_hyp | lengths [beam] | tokens [beam][ocap] | h [beam][256] | c [beam][256] (states only if
-// with_states).  Rows without a hypothesis are zero.  ocap >= every length (1 + the frames walked).  biased / fin_nscore: as
-// prefix_pack's cst / fin_nscore.
+// context scores f64 [beam] | n-gram scores f64 [beam] | n_hyp | lengths [beam] | tokens [beam][ocap] | h [beam][256] | c [beam][256]
+// (states only if with_states).  Rows without a hypothesis are zero.  ocap >= every length (1 + the frames walked).  biased /
+// fin_nscore: as prefix_pack's cst / fin_nscore.  fused: the search fuses a model, its n-gram scores are part of the totals;
+// ng_final: with the end term under ng (the running score otherwise; ng is not read then).
 __global__ __launch_bounds__(256) void prefix_pack_pool(PrefixPoolP q, int slot, int cur, int beam, int lcap, int ocap, int with_states, int biased,
-                                                        const double* fin_nscore, double* out) {
+                                                        const double* fin_nscore, int fused, int ng_final, NgTables ng, double* out) {
     const int i = blockIdx.x, r = slot * PB_MAX_BEAM + i, tid = threadIdx.x;
-    int* oi = reinterpret_cast<int*>(out + 2 * beam);
+    int* oi = reinterpret_cast<int*>(out + 3 * beam);
     int* o_len = oi + 1;
     int* o_tk = o_len + beam;
     float* o_h = reinterpret_cast<float*>(o_tk + (long long)beam * ocap);
@@ -464,8 +516,12 @@ __global__ __launch_bounds__(256) void prefix_pack_pool(PrefixPoolP q, int slot,
     }
     if (tid == 0) {
         const double c = live && biased ? (fin_nscore ? -fin_nscore[q.cst[cur][r]] : q.cs[cur][r]) : 0.0;
-        out[i] = live ? (biased ? q.sc[cur][r] + c : q.sc[cur][r]) : 0.0;
+        const double g = live && fused ? prefix_pack_ngram(ng, q.nst[cur][r], q.ns[cur][r], ng_final != 0) : 0.0;
+        double tot = live ? (biased ? q.sc[cur][r] + c : q.sc[cur][r]) : 0.0;
+        if (live && fused) tot = tot + g;
+        out[i] = tot;
         out[beam + i] = c;
+        out[2 * beam + i] = g;
         o_len[i] = n;
         if (i == 0) oi[0] = nh;
     }

@@ -99,6 +99,14 @@ SIGNATURES = {
     "rnnt_pool_prefix_frames_ctx": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, ctypes.c_float, ctypes.c_float, c_i32, c_vp]),
     "rnnt_pool_chunk_prefix_ctx": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, ctypes.c_float, ctypes.c_float, c_i32, c_i32p, c_vp]),
     "rnnt_stream_get_prefix_ctx": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rnnt_prefix_beam_decode_ngram": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, ctypes.c_float, ctypes.c_float, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp,
+                                              c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rnnt_prefix_merge_ngram_host": (c_i32, [c_i32] + [c_vp] * 9 + [c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, ctypes.c_double, c_i32, c_vp, c_vp, c_vp, c_vp,
+                                                                  ctypes.c_double, ctypes.c_double, ctypes.c_double, c_i32] + [c_vp] * 9),
+    "rnnt_prefix_merge_ngram_device": (c_i32, [c_vp, c_i32] + [c_vp] * 9 + [c_i32, c_i32, c_i32, c_i32] + [c_vp] * 10),
+    "rnnt_pool_prefix_frames_ngram": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, ctypes.c_float, ctypes.c_float, c_i32, c_i32, c_vp]),
+    "rnnt_pool_chunk_prefix_ngram": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, ctypes.c_float, ctypes.c_float, c_i32, c_i32, c_i32p, c_vp]),
+    "rnnt_stream_get_prefix_ngram": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rnnt_transducer_nll": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "rnnt_ctc_nll": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "rnnt_transducer_nll_nbest": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
@@ -246,6 +254,47 @@ def prefix_merge_ctx_host(hyps, top_lp, top_tok, blank, beam_size, phrases, cont
                                 graph=(n, _np_ptr(pl), _np_ptr(pt), float(context_score)))
     if m < 0:
         raise RnntError(f"rnnt_prefix_merge_ctx_host: bad argument (status {m})", m)
+    return out
+
+
+def _prefix_merge_ngram_call(fn, head, hyps, top_lp, top_tok, blank, beam_size, mid, tail=()):
+    """Flat arguments of rnnt_prefix_merge_ngram_host / _device: hyps [(tokens, score, context state, context score, n-gram state,
+    n-gram score)], `mid` what the form passes between beam_size and the outputs -> the call's return value and [(tokens, fused
+    score, src_row, src_slot, context state, context score, n-gram state, n-gram score)] of the survivors."""
+    n = len(hyps)
+    hl = np.array([len(h[0]) for h in hyps], np.int32)
+    ht = np.array([x for h in hyps for x in h[0]] or [0], np.int32)
+    hs, hcs, hns = (np.array([h[i] for h in hyps], np.float64) for i in (1, 3, 5))
+    hst, hnst = (np.array([h[i] for h in hyps], np.int32) for i in (2, 4))
+    tl = np.ascontiguousarray(top_lp, np.float32).reshape(n, -1)
+    tt = np.ascontiguousarray(top_tok, np.int32).reshape(n, -1)
+    assert tt.shape == tl.shape
+    cap = max(beam_size, 1)
+    out_len, out_tok = np.zeros(cap, np.int32), np.zeros(cap * (int(hl.max(initial=0)) + 1) + 1, np.int32)
+    out_sc, out_cs, out_ns = (np.zeros(cap, np.float64) for _ in range(3))
+    out_row, out_slot, out_st, out_nst = (np.zeros(cap, np.int32) for _ in range(4))
+    m = fn(*head, n, _np_ptr(hl), _np_ptr(ht), _np_ptr(hs), _np_ptr(hst), _np_ptr(hcs), _np_ptr(hnst), _np_ptr(hns), _np_ptr(tl), _np_ptr(tt),
+           tl.shape[1], blank, beam_size, *mid, _np_ptr(out_len), _np_ptr(out_tok), _np_ptr(out_sc), _np_ptr(out_row), _np_ptr(out_slot),
+           _np_ptr(out_st), _np_ptr(out_cs), _np_ptr(out_nst), _np_ptr(out_ns), *tail)
+    out, o = [], 0
+    for a in range(max(m, 0)):
+        out.append((out_tok[o:o + out_len[a]].tolist(), float(out_sc[a]), int(out_row[a]), int(out_slot[a]), int(out_st[a]), float(out_cs[a]),
+                    int(out_nst[a]), float(out_ns[a])))
+        o += out_len[a]
+    return m, out
+
+
+def prefix_merge_ngram_host(hyps, top_lp, top_tok, blank, beam_size, phrases, context_score, ngram, vocab):
+    """rnnt_prefix_merge_ngram_host (no context, no GPU): prefix_merge_ctx_host with the NgramLM `ngram` over a vocabulary of `vocab`
+    ids (None: no model; phrases None or empty: no graph).  hyps [(tokens, score, context state, context score, n-gram state, n-gram
+    score)], the n-gram state a node id or -1 (the start marker) -> [(tokens, fused score, src_row, src_slot, context state, context
+    score, n-gram state, n-gram score)] of the survivors, ordered by fused score (+ context score) (+ n-gram score)."""
+    n, pl, pt = _phrase_args(phrases)
+    a = _ngram_args(ngram)
+    m, out = _prefix_merge_ngram_call(load().rnnt_prefix_merge_ngram_host, (), hyps, top_lp, top_tok, blank, beam_size,
+                                      (n, _np_ptr(pl), _np_ptr(pt), float(context_score)) + _ngram_call_args(a) + (int(vocab),))
+    if m < 0:
+        raise RnntError(f"rnnt_prefix_merge_ngram_host: bad argument (status {m})", m)
     return out
 
 
@@ -765,6 +814,26 @@ class RnntEngine:
         context scores at the end without a re-sort, so the totals need not descend); with want_states also (h, c)."""
         return self._prefix_decode(enc_ptr, enc_lens, B, T, beam_size, ctc_weight, transducer_weight, bool(use_context), want_states, stream)
 
+    def prefix_beam_decode_ngram(self, enc_ptr, enc_lens, B, T, beam_size=5, ctc_weight=0.3, transducer_weight=0.7, use_context=False, use_ngram=True,
+                                 want_states=False, stream=None):
+        """rnnt_prefix_beam_decode_ngram: prefix_beam_decode_ctx with the model of ngram_set fused when use_ngram.  Returns per
+        utterance [(tokens incl. the leading blank, total score, context score, n-gram score)] in the search's order (the end term
+        is added without a re-sort, so the totals need not descend); with want_states also (h, c)."""
+        el = np.ascontiguousarray(enc_lens, np.int32)
+        assert el.size == B
+        w = max(beam_size, 1)
+        cap = int(el.max(initial=0)) + 1
+        nh, lens, toks = np.zeros(B, np.int32), np.zeros((B, w), np.int32), np.zeros((B, w, cap), np.int32)
+        sc, cs, ns = (np.zeros((B, w), np.float64) for _ in range(3))
+        h = np.zeros((B, w, 256), np.float32) if want_states else None
+        c = np.zeros((B, w, 256), np.float32) if want_states else None
+        self._chk(self.lib.rnnt_prefix_beam_decode_ngram(self.ctx, enc_ptr, _np_ptr(el), B, T, beam_size, ctc_weight, transducer_weight,
+                                                         1 if use_context else 0, 1 if use_ngram else 0, cap, _np_ptr(nh), _np_ptr(lens), _np_ptr(toks),
+                                                         _np_ptr(sc), _np_ptr(cs), _np_ptr(ns), _np_ptr(h) if want_states else None,
+                                                         _np_ptr(c) if want_states else None, stream), "rnnt_prefix_beam_decode_ngram")
+        hyps = [[(toks[b, i, :lens[b, i]].tolist(), float(sc[b, i]), float(cs[b, i]), float(ns[b, i])) for i in range(nh[b])] for b in range(B)]
+        return (hyps, h, c) if want_states else hyps
+
     # ---- CTC prefix beam search with contextual biasing ------------------------------------------
     def context_set(self, phrases, context_score=6.0):
         """rnnt_context_set: build and upload the context graph over phrases [[token, ...], ...]; an empty list clears it."""
@@ -920,6 +989,36 @@ class RnntEngine:
         return self._pool_chunk("rnnt_pool_chunk_prefix_ctx", slots, fbank_ptr, chunk_frames, offsets, required,
                                 (beam_size, ctc_weight, transducer_weight, 1 if use_context else 0), stream)
 
+    def pool_prefix_frames_ngram(self, slots, enc_ptr, t, beam_size=5, ctc_weight=0.3, transducer_weight=0.7, use_context=False, use_ngram=True, stream=None):
+        """rnnt_pool_prefix_frames_ngram: pool_prefix_frames_ctx for searches that fuse the model of ngram_set (use_ngram)."""
+        a = np.ascontiguousarray(slots, np.int32)
+        assert a.ndim == 1
+        self._chk(self.lib.rnnt_pool_prefix_frames_ngram(self.ctx, a.size, _np_ptr(a), enc_ptr, t, beam_size, ctc_weight, transducer_weight,
+                                                         1 if use_context else 0, 1 if use_ngram else 0, stream), "rnnt_pool_prefix_frames_ngram")
+
+    def pool_chunk_prefix_ngram(self, slots, fbank_ptr, chunk_frames, offsets, required, beam_size=5, ctc_weight=0.3, transducer_weight=0.7,
+                                use_context=False, use_ngram=True, stream=None):
+        """rnnt_pool_chunk_prefix_ngram: pool_chunk_prefix_ctx for searches that fuse the model of ngram_set.  Returns t'."""
+        return self._pool_chunk("rnnt_pool_chunk_prefix_ngram", slots, fbank_ptr, chunk_frames, offsets, required,
+                                (beam_size, ctc_weight, transducer_weight, 1 if use_context else 0, 1 if use_ngram else 0), stream)
+
+    def stream_prefix_ngram(self, slot, final=False, states=False, stream=None):
+        """rnnt_stream_get_prefix_ngram: [(tokens incl. the leading blank, total score, context score, n-gram score)] of one slot in
+        the search's order, as they stand (final: finalize's context scores and the n-gram scores with the end term, what the
+        one-call search returns had the utterance ended here; zero n-gram scores for a slot that fuses no model); with states also
+        (h, c), each [n_hyp, 256].  Reading changes nothing."""
+        w, _, cap = self.stream_prefix_size(slot)
+        nh, lens, toks = np.zeros(1, np.int32), np.zeros(w, np.int32), np.zeros((w, cap), np.int32)
+        sc, cs, ns = (np.zeros(w, np.float64) for _ in range(3))
+        h = np.zeros((w, 256), np.float32) if states else None
+        c = np.zeros((w, 256), np.float32) if states else None
+        self._chk(self.lib.rnnt_stream_get_prefix_ngram(self.ctx, slot, 1 if final else 0, w, cap, _np_ptr(nh), _np_ptr(lens), _np_ptr(toks), _np_ptr(sc),
+                                                        _np_ptr(cs), _np_ptr(ns), _np_ptr(h) if states else None, _np_ptr(c) if states else None, stream),
+                  "rnnt_stream_get_prefix_ngram")
+        n = int(nh[0])
+        hyps = [(toks[i, :lens[i]].tolist(), float(sc[i]), float(cs[i]), float(ns[i])) for i in range(n)]
+        return (hyps, h[:n], c[:n]) if states else hyps
+
     def stream_prefix_ctx(self, slot, final=False, states=False, stream=None):
         """rnnt_stream_get_prefix_ctx: [(tokens incl. the leading blank, total score, context score)] of one slot in the search's
         order, as they stand (final: finalize's context scores, what the one-call search returns had the utterance ended here);
@@ -988,6 +1087,15 @@ class RnntEngine:
         m, out = _prefix_merge_call(self.lib.rnnt_prefix_merge_device, (self.ctx,), hyps, top_lp, top_tok, blank, beam_size, (stream,))
         if m < 0:
             self._chk(m, "rnnt_prefix_merge_device")
+        return out
+
+    def prefix_merge_ngram_device(self, hyps, top_lp, top_tok, blank, beam_size, use_context=False, stream=None):
+        """rnnt_prefix_merge_ngram_device: prefix_merge_ngram_host's hypotheses and results through one prefix_merge launch with the
+        model of ngram_set and, when use_context, the graph of context_set."""
+        m, out = _prefix_merge_ngram_call(self.lib.rnnt_prefix_merge_ngram_device, (self.ctx,), hyps, top_lp, top_tok, blank, beam_size,
+                                          (1 if use_context else 0,), (stream,))
+        if m < 0:
+            self._chk(m, "rnnt_prefix_merge_ngram_device")
         return out
 
     def prefix_merge_ctx_device(self, hyps, top_lp, top_tok, blank, beam_size, stream=None):

@@ -1,4 +1,4 @@
-"""Back-off n-gram language model for shallow fusion in the CTC prefix beam search (rnnt_ngram_set; semantics in
+"""Back-off n-gram language model for shallow fusion in the CTC and the transducer prefix beam search (rnnt_ngram_set; semantics in
 include/rnnt_hip.h).  Host data only: the library builds the automaton."""
 import math
 from typing import Dict, List, Sequence, Tuple

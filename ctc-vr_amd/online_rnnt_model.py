@@ -201,7 +201,7 @@ class OnlineRNNTModel:
         self.numerics = numerics          # None -> $RNNT_NUMERICS or "fp32" (lib.numerics_id)
         self._loaded = False
         self._context_bias = None         # the ContextBias whose graph the context holds (ctc_prefix_beam_search, prefix_beam_search_batch)
-        self._ngram_lm = None             # the NgramLM whose model the context holds (ctc_prefix_beam_search, rescoring_batch)
+        self._ngram_lm = None             # the NgramLM whose model the context holds (ctc_prefix_beam_search, prefix_beam_search_batch, rescoring_batch)
         self._chunks_done = None          # None = reset_streaming_cache not called yet (attributes are None, :138-143)
         self._tok_count = 0
         self.streaming_beam_hypotheses = None
@@ -502,7 +502,7 @@ class OnlineRNNTModel:
         return self.greedy_search_full(audios, audio_lens), None, None
 
     def prefix_beam_search(self, audios: torch.Tensor, audio_lens: torch.Tensor, beam_size: int = 5, ctc_weight: float = 0.3,
-                           transducer_weight: float = 0.7, context: Optional["ContextBias"] = None):
+                           transducer_weight: float = 0.7, context: Optional["ContextBias"] = None, ngram: Optional["NgramLM"] = None):
         """WeNet prefix beam search (wenet/transducer/search/prefix_beam_search.py:42-148) on the full-context encoder
         (decoding_chunk_size=-1), B = 1: at most one symbol per frame, CTC shallow fusion, prefix merging with log_add.
         Device: encoder (rnnt_encoder_full), CTC posteriors (rnnt_ctc_logprobs), one predictor step and one joint + log_softmax
@@ -515,7 +515,14 @@ class OnlineRNNTModel:
         its score; merged candidates keep the first one's; the sort is by score + context score; after the last frame finalize
         replaces the context scores, without a re-sort.  The first prune (top-k) does not see the graph.
         Returns [(tokens incl. the leading blank, score)], best first; with a context the scores are the totals and
-        self._prefix_context_scores holds [(running, finalized)] context scores per hypothesis."""
+        self._prefix_context_scores holds [(running, finalized)] context scores per hypothesis.
+        ngram: an NgramLM fused into the search (semantics: include/rnnt_hip.h, rnnt_prefix_beam_decode_ngram), in Python doubles on
+        testing.ngram_ref: every hypothesis also holds an n-gram state and score ([blank]: the start marker, 0), copied and stepped
+        where the context is; the sort is by score + context score + n-gram score, left to right, a term whose feature is off left
+        out; after the last frame context finalize comes first, then every survivor's n-gram score gains the end term of its state,
+        without a re-sort.  self._prefix_ngram_scores then holds [(running, final)] n-gram scores per hypothesis, and
+        self._prefix_min_gap the smallest difference between adjacent totals at any frame's second prune, the pair across the beam
+        boundary included (inf when no frame had two candidates)."""
         import math
         self._require_loaded()
         assert audios.size(0) == 1, "prefix_beam_search is batch-1 in the reference (:58)"
@@ -534,7 +541,14 @@ class OnlineRNNTModel:
         if context is not None:
             from .testing import context_graph_ref
             graph = context_graph_ref(context.phrases, context.context_score)
+        lm = None
+        if ngram is not None:
+            from .testing import ngram_ref
+            lm = ngram_ref(ngram.ngrams, V, self.blank_id, ngram.lm_weight, ngram.length_bonus, ngram.unk_logp)
+        from .testing import NG_START, ngram_eos_ref, ngram_step_ref, prefix_total_ref
         cstate, cscore = [0], [0.0]
+        nstate, nscore = [NG_START], [0.0]
+        min_gap = math.inf
         h = torch.zeros(1, 256, device=dev)
         c = torch.zeros(1, 256, device=dev)
 
@@ -554,14 +568,15 @@ class OnlineRNNTModel:
             logp = torch.log(torch.add(transducer_weight * torch.exp(logp), ctc_weight * torch.exp(ctc[i].unsqueeze(0))))   # :99-101
             top_lp, top_ix = logp.topk(beam_size)                                                                            # :104
             sc = torch.add(torch.tensor(scores).unsqueeze(1), top_lp)                                                        # :105 (float32)
-            cand = []                                            # [tokens, score, state row in cat(h, h2), context state, context score]
+            cand = []                # [tokens, score, state row in cat(h, h2), context state, context score, n-gram state, n-gram score]
             for j in range(n):
                 for t in range(beam_size):
                     if int(top_ix[j, t]) == self.blank_id:
-                        cand.append([list(hyps[j]), sc[j, t].item(), j, cstate[j], cscore[j]])
+                        cand.append([list(hyps[j]), sc[j, t].item(), j, cstate[j], cscore[j], nstate[j], nscore[j]])
                     else:
                         step, nxt = graph.step(cstate[j], int(top_ix[j, t])) if graph is not None else (0.0, 0)
-                        cand.append([list(hyps[j]) + [int(top_ix[j, t])], sc[j, t].item(), n + j, nxt, cscore[j] + step])
+                        lstep, lnxt = ngram_step_ref(lm, nstate[j], int(top_ix[j, t])) if lm is not None else (0.0, NG_START)
+                        cand.append([list(hyps[j]) + [int(top_ix[j, t])], sc[j, t].item(), n + j, nxt, cscore[j] + step, lnxt, nscore[j] + lstep])
             fused = [cand[0]]
             for cnd in cand[1:]:
                 for f in fused:
@@ -570,12 +585,17 @@ class OnlineRNNTModel:
                         break
                 else:
                     fused.append(cnd)
-            if graph is not None:
+            if lm is not None:
+                fused.sort(key=lambda v: prefix_total_ref(v[1], v[4] if graph is not None else None, v[6]), reverse=True)
+                tot = [prefix_total_ref(v[1], v[4] if graph is not None else None, v[6]) for v in fused[:beam_size + 1]]
+                min_gap = min([min_gap] + [a - b for a, b in zip(tot, tot[1:])])
+            elif graph is not None:
                 fused.sort(key=lambda v: v[1] + v[4], reverse=True)
             else:
                 fused.sort(key=lambda v: v[1], reverse=True)
             fused = fused[:beam_size]
             cstate, cscore = [f[3] for f in fused], [f[4] for f in fused]
+            nstate, nscore = [f[5] for f in fused], [f[6] for f in fused]
             rows = torch.tensor([f[2] for f in fused], device=dev)
             h = torch.cat([h, h2], 0).index_select(0, rows).contiguous()
             c = torch.cat([c, c2], 0).index_select(0, rows).contiguous()
@@ -585,11 +605,16 @@ class OnlineRNNTModel:
             fin = [graph.finalize(st) for st in cstate]
             self._prefix_context_scores = list(zip(cscore, fin))
             scores = [sc + f for sc, f in zip(scores, fin)]
+        if lm is not None:
+            fin = [ns + ngram_eos_ref(lm, st) for st, ns in zip(nstate, nscore)]
+            self._prefix_ngram_scores = list(zip(nscore, fin))
+            self._prefix_min_gap = min_gap
+            scores = [sc + f for sc, f in zip(scores, fin)]
         return list(zip(hyps, scores))
 
     def prefix_beam_search_batch(self, audios: torch.Tensor, audio_lens: torch.Tensor, beam_size: int = 5, ctc_weight: float = 0.3,
                                  transducer_weight: float = 0.7, walk_padding: bool = True, context: Optional["ContextBias"] = None,
-                                 with_context_scores: bool = False):
+                                 with_context_scores: bool = False, ngram: Optional["NgramLM"] = None, with_ngram_scores: bool = False):
         """prefix_beam_search for a padded batch audios [B, T, 80] of utterances of different lengths, with the frame loop on the
         device: one rnnt_encoder_full call and one rnnt_prefix_beam_decode call (two launches per encoder frame, one
         synchronisation at the end).  walk_padding: every utterance walks all T' encoder frames, the padded ones included, as the
@@ -598,6 +623,8 @@ class OnlineRNNTModel:
         context: a ContextBias whose phrases boost the hypotheses that match them (rnnt_prefix_beam_decode_ctx; semantics as in
         prefix_beam_search): the scores are then the totals, which carry finalize's correction and need not descend;
         with_context_scores: every hypothesis is (tokens, score, context score), so score - context score is the unbiased score.
+        ngram: an NgramLM fused into the search (rnnt_prefix_beam_decode_ngram; semantics as in prefix_beam_search): the scores are
+        the totals, end term included, and need not descend; with_ngram_scores: every hypothesis ends with its n-gram score.
         Returns one [(tokens incl. the leading blank, score)] per utterance, best first; the hypotheses' final LSTM states stay in
         self._prefix_states_batch, one (h, c) pair of host tensors [n_hyp, 256] per utterance.  Invalidates the streaming state."""
         self._require_loaded()
@@ -614,7 +641,16 @@ class OnlineRNNTModel:
         else:
             n1 = np.maximum(0, (np.minimum(lens, T) - 1) // 2)     # valid frames after masks[:, :, 2::2][:, :, 2::2]
             enc_lens = np.maximum(0, (n1 - 1) // 2).astype(np.int32)
-        if context is None and not with_context_scores:
+        if ngram is not None or with_ngram_scores:
+            if context is not None:
+                self._set_context(context)
+            if ngram is not None:
+                self._set_ngram(ngram)
+            hyps, h, c = self._engine.prefix_beam_decode_ngram(enc.data_ptr(), enc_lens, B, tq, beam_size, ctc_weight, transducer_weight, context is not None,
+                                                               ngram is not None, True, s)
+            hyps = [[(tok, score) + ((cs,) if with_context_scores else ()) + ((ns,) if with_ngram_scores else ()) for tok, score, cs, ns in row]
+                    for row in hyps]
+        elif context is None and not with_context_scores:
             hyps, h, c = self._engine.prefix_beam_decode(enc.data_ptr(), enc_lens, B, tq, beam_size, ctc_weight, transducer_weight, True, s)
         else:
             if context is not None:
@@ -973,19 +1009,19 @@ class StreamingBatch:
         return self.engine.tokens(_stream_ptr())
 
 
-_PLAN_ORDER = ("greedy", "beam", "ctc_prefix", "prefix", "ctc_prefix_ngram")   # the classes of a round run in this order of kinds
+_PLAN_ORDER = ("greedy", "beam", "ctc_prefix", "prefix", "ctc_prefix_ngram", "prefix_ngram")   # the classes of a round run in this order of kinds
 
 
 class Decoder(namedtuple("Decoder", ["kind", "beam", "use_context", "weights", "use_ngram"])):
     """The decoder a pool slot was opened with, fixed for its utterance: kind ("greedy", "beam", "ctc_prefix" or "prefix", a row of
     _KINDS), beam size (0 for greedy), hot-word biasing, the (ctc_weight, transducer_weight) of a "prefix" slot (None otherwise) and
-    n-gram fusion (a "ctc_prefix" slot's).  Slots with equal decoders may share a library call."""
+    n-gram fusion (a "ctc_prefix" or "prefix" slot's).  Slots with equal decoders may share a library call."""
     __slots__ = ()
 
     @property
     def plan_kind(self):
-        """the kind as pool_plan names it: the CTC prefix slots that fuse a model are a kind of their own, ordered last"""
-        return "ctc_prefix_ngram" if self.use_ngram else self.kind
+        """the kind as pool_plan names it: the CTC prefix and transducer prefix slots that fuse a model are kinds of their own, ordered last"""
+        return self.kind + "_ngram" if self.use_ngram else self.kind
 
     @property
     def plan_key(self):
@@ -1055,7 +1091,8 @@ def pool_plan(queue, offsets, beams=None, ctc_prefix=None, prefix=None, ngram=No
     kind is as above with weights None.  One (length, kind, beam size, use_context, weights) class per call -- slots with different
     weights never share one -- in ascending order inside a round.  A slot listed in prefix is looked up in neither ctc_prefix nor beams.
     A fourth element of a prefix entry is its use_context (hot-word biasing, an rnnt_pool_chunk_prefix_ctx call): biased and unbiased
-    prefix slots of one length go in two calls.
+    prefix slots of one length go in two calls.  A fifth element is its use_ngram (n-gram fusion, an rnnt_pool_chunk_prefix_ngram
+    call): such calls have kind "prefix_ngram", ordered after "ctc_prefix_ngram", and never share a call with the other prefix slots.
 
     ngram: the slots among ctc_prefix whose search fuses the n-gram model (None or empty: none, and the results above).  Their calls
     have kind "ctc_prefix_ngram" (an rnnt_pool_chunk_ctc_prefix_ngram call), ordered after "prefix": such slots never share a call
@@ -1064,7 +1101,8 @@ def pool_plan(queue, offsets, beams=None, ctc_prefix=None, prefix=None, ngram=No
     for slot in {slot for slot, _ in queue}:
         if prefix is not None and slot in prefix:
             p = prefix[slot]
-            decoders[slot] = Decoder("prefix", int(p[0]), bool(p[3]) if len(p) > 3 else False, (float(p[1]), float(p[2])), False)
+            decoders[slot] = Decoder("prefix", int(p[0]), bool(p[3]) if len(p) > 3 else False, (float(p[1]), float(p[2])),
+                                     bool(p[4]) if len(p) > 4 else False)
         elif ctc_prefix is not None and slot in ctc_prefix:
             decoders[slot] = Decoder("ctc_prefix", int(ctc_prefix[slot][0]), bool(ctc_prefix[slot][1]), None, bool(ngram) and slot in ngram)
         elif beams and slot in beams:
@@ -1168,7 +1206,10 @@ def _read_ctc_prefix(engine, d, slot, final, stream):
     return [(tok, score, times) for tok, score, times, _ in engine.stream_ctc_prefix(slot, final, stream=stream)]
 
 
-def _read_prefix(engine, d, slot, final, stream, with_context_scores=False):
+def _read_prefix(engine, d, slot, final, stream, with_context_scores=False, with_ngram_scores=False):
+    if d.use_ngram or with_ngram_scores:                # the totals carry the n-gram score (final: with the end term)
+        return [(tok, score) + ((cs,) if with_context_scores else ()) + ((ns,) if with_ngram_scores else ())
+                for tok, score, cs, ns in engine.stream_prefix_ngram(slot, final, stream=stream)]
     if not d.use_context and not with_context_scores:
         return engine.stream_prefix(slot, stream=stream)            # no context score to finalize: final reads the same
     hyps = engine.stream_prefix_ctx(slot, final, stream=stream)
@@ -1185,20 +1226,26 @@ _KINDS = {
                                   ("pool_chunk_ctc_prefix", (d.beam, d.use_context)),
                         _read_ctc_prefix, lambda hyps: [(tok, score) for tok, score, _ in hyps]),
     "prefix": _Kind("transducer prefix", False,
-                    lambda d: ("pool_chunk_prefix_ctx", (d.beam,) + d.weights + (True,)) if d.use_context else
+                    lambda d: ("pool_chunk_prefix_ngram", (d.beam,) + d.weights + (d.use_context, True)) if d.use_ngram else
+                              ("pool_chunk_prefix_ctx", (d.beam,) + d.weights + (True,)) if d.use_context else
                               ("pool_chunk_prefix", (d.beam,) + d.weights),
                     _read_prefix, lambda hyps: [(tok[1:], score) for tok, score in hyps]),      # the first pass drops the leading blank
 }
 
 
 def _decoder_of_open(pool, beam_size, ctc_prefix_beam, context, prefix_beam, ctc_weight, transducer_weight, prefix_context, endpoint,
-                     on_endpoint, ngram) -> Decoder:
+                     on_endpoint, ngram, prefix_ngram=None) -> Decoder:
     """The Decoder that open()'s keywords select, or the RnntError of the first rule they break.  The order of the checks is part of the
     facade's behaviour: an open() with several faults reports the first one here."""
     if ngram is not None:
         if not ctc_prefix_beam:
             raise RnntError("stream pool: ngram needs ctc_prefix_beam")
         if ngram is not pool._ngram and any(r.ngram is not None for r in pool._slots.values()):
+            raise RnntError("stream pool: another n-gram model is in use by an open slot (one model per pool at a time)")
+    if prefix_ngram is not None:
+        if not prefix_beam:
+            raise RnntError("stream pool: prefix_ngram needs prefix_beam")
+        if prefix_ngram is not pool._ngram and any(r.ngram is not None for r in pool._slots.values()):
             raise RnntError("stream pool: another n-gram model is in use by an open slot (one model per pool at a time)")
     if on_endpoint not in (None, "keep", "fresh"):
         raise RnntError(f"stream pool: on_endpoint {on_endpoint!r} is not None, 'keep' or 'fresh'")
@@ -1232,7 +1279,7 @@ def _decoder_of_open(pool, beam_size, ctc_prefix_beam, context, prefix_beam, ctc
         raise RnntError(f"stream pool: beam_size {beam_size} outside [0, min(max_beam {pool.max_beam}, 16)] or vocabulary "
                         f"{pool.vocab_size} > 512")
     if prefix_beam:
-        return Decoder("prefix", int(prefix_beam), prefix_context is not None, (float(ctc_weight), float(transducer_weight)), False)
+        return Decoder("prefix", int(prefix_beam), prefix_context is not None, (float(ctc_weight), float(transducer_weight)), prefix_ngram is not None)
     if ctc_prefix_beam:
         return Decoder("ctc_prefix", int(ctc_prefix_beam), context is not None, None, ngram is not None)
     return Decoder("beam", int(beam_size), False, None, False) if beam_size else GREEDY
@@ -1355,7 +1402,8 @@ class StreamPool:
 
     def open(self, beam_size: int = 0, ctc_prefix_beam: int = 0, context: Optional[ContextBias] = None, keep_frames: bool = False,
              prefix_beam: int = 0, ctc_weight: float = 0.3, transducer_weight: float = 0.7, prefix_context: Optional[ContextBias] = None,
-             endpoint: Optional[EndpointConfig] = None, on_endpoint: Optional[str] = None, ngram: Optional[NgramLM] = None) -> int:
+             endpoint: Optional[EndpointConfig] = None, on_endpoint: Optional[str] = None, ngram: Optional[NgramLM] = None,
+             prefix_ngram: Optional[NgramLM] = None) -> int:
         """The lowest free slot, reset for a new utterance (reset_streaming_cache for that slot alone).  beam_size > 0: the slot's
         utterance is beam-searched with that beam (its hypotheses start as the one empty hypothesis); raises RnntError at once
         when this pool cannot do it.  ctc_prefix_beam > 0 (not together with beam_size): the slot's utterance runs the CTC prefix beam
@@ -1375,9 +1423,12 @@ class StreamPool:
         finished Segments.  None: the slot's utterance ends with close() or next_segment() only.
         ngram (needs ctc_prefix_beam): the slot's search fuses that NgramLM (rnnt_pool_chunk_ctc_prefix_ngram calls of their own).  The
         pool holds one model at a time, with the graph's rule: a model other than the current one is uploaded (ngram_set) unless
-        another slot that fuses one is still open, which raises RnntError and takes no slot."""
+        another slot that fuses one is still open, which raises RnntError and takes no slot.
+        prefix_ngram (needs prefix_beam): the slot's transducer prefix search fuses that NgramLM (rnnt_pool_chunk_prefix_ngram calls of
+        their own; `ngram` belongs to ctc_prefix_beam).  The one model of the pool serves both kinds, as the one graph does."""
         decoder = _decoder_of_open(self, beam_size, ctc_prefix_beam, context, prefix_beam, ctc_weight, transducer_weight, prefix_context,
-                                   endpoint, on_endpoint, ngram)
+                                   endpoint, on_endpoint, ngram, prefix_ngram)
+        ngram = ngram if ngram is not None else prefix_ngram
         if not self._free:
             raise RnntError(f"stream pool full: all {self.n} slots are open")
         graph = context if context is not None else prefix_context
@@ -1571,12 +1622,13 @@ class StreamPool:
         (finalize's context score instead of the running one).  Reading changes nothing."""
         return self._read(slot, self._slot_of_kind(slot, "ctc_prefix"), final)
 
-    def prefix_hyps(self, slot: int, final: bool = False, with_context_scores: bool = False):
+    def prefix_hyps(self, slot: int, final: bool = False, with_context_scores: bool = False, with_ngram_scores: bool = False):
         """[(tokens including the leading blank, score)] of a transducer prefix slot, best first, as they stand after the chunks
         stepped so far.  A biased slot's scores are the totals (score + context score); final: with finalize's context scores, what
         the one-call search returns had the utterance ended here (no re-sort); with_context_scores: (tokens, score, context score).
-        Reading changes nothing."""
-        return self._read(slot, self._slot_of_kind(slot, "prefix"), final, with_context_scores)
+        A slot that fuses a model (prefix_ngram) has its n-gram score in the totals too -- the running one, or with final the one
+        with the end term; with_ngram_scores: every hypothesis ends with it.  Reading changes nothing."""
+        return self._read(slot, self._slot_of_kind(slot, "prefix"), final, with_context_scores, with_ngram_scores)
 
     def endpoints(self, slots: Optional[List[int]] = None) -> Dict[int, Endpoint]:
         """{slot: Endpoint(rule, at_frame, frames, trailing, speech)} of the open slots that detect their endpoint, or of the listed
@@ -1606,7 +1658,7 @@ class StreamPool:
 
     def rescore(self, slots: List[int], ctc_weight: float, transducer_weight: float):
         """The second pass for CTC prefix and transducer prefix slots opened with keep_frames=True: per slot ctc_hyps(final=True) --
-        or prefix_hyps (a biased slot's final totals) with the leading blank dropped and the search's score as the first score, the reference's default first pass
+        or prefix_hyps (the final totals of a biased slot or one that fuses a model) with the leading blank dropped and the search's score as the first score, the reference's default first pass
         (beam_search_type="transducer", wenet/transducer/transducer.py:327) --, then ONE
         rnnt_pool_rescore call for all listed slots -- every hypothesis re-scored with the transducer likelihood over the slot's kept
         frames -- then the choice of rnnt_rescore_select_host with total = ctc_score * ctc_weight + td_score * transducer_weight.

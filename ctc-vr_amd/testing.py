@@ -846,6 +846,59 @@ def ctc_prefix_beam_ngram_ref(lp, length, blank, beam_size, graph=None, ngram=No
     return out, prune_gap, top_gap
 
 
+# ---- n-gram shallow fusion in the transducer prefix beam search (semantics: include/rnnt_hip.h, rnnt_prefix_beam_decode_ngram) ----
+NG_START = -1     # the n-gram state of a hypothesis before its first token: the start state of the model the search runs under
+
+
+def ngram_step_ref(ngram, state, tok):
+    """ngram.step with the start marker resolved: (score of the step, node it lands in)."""
+    return ngram.step(ngram.start if state == NG_START else state, tok)
+
+
+def ngram_eos_ref(ngram, state):
+    return ngram.eos(ngram.start if state == NG_START else state)
+
+
+def prefix_merge_ngram_ref(hyps, top_lp, top_tok, blank, beam_size, graph, ngram):
+    """prefix_merge_ref with hot-word biasing (graph: a context_graph_ref or None) and n-gram shallow fusion (ngram: an ngram_ref or
+    None).  hyps [(tokens, score, context state, context score, n-gram state, n-gram score)]; [blank] holds NG_START.  A blank
+    candidate copies its parent's context and n-gram state and score; any other token takes graph.step / ngram.step from the
+    parent's state and adds the step's score to the parent's; fusion is prefix_merge_ref's and keeps the first candidate's values
+    (functions of the token sequence alone); stable descending sort by fused score + context score + n-gram score, left to right, a
+    term whose feature is off left out; truncation.
+    Returns [(tokens, fused score, src_row, src_slot, context state, context score, n-gram state, n-gram score)]."""
+    k = len(top_lp[0])
+    plain = prefix_merge_ref([(h[0], h[1]) for h in hyps], top_lp, top_tok, blank, len(hyps) * k)     # every fused survivor, keyed by its first candidate
+    out = []
+    for toks, score, j, slot in plain:
+        cst, cs, nst, ns = int(hyps[j][2]), float(hyps[j][3]), int(hyps[j][4]), float(hyps[j][5])
+        if slot == 1 and graph is not None:
+            step, cst = graph.step(cst, int(toks[-1]))
+            cs = cs + step
+        if slot == 1 and ngram is not None:
+            step, nst = ngram_step_ref(ngram, nst, int(toks[-1]))
+            ns = ns + step
+        out.append((toks, score, j, slot, cst, cs, nst, ns))
+    first = {}
+    for j in range(len(hyps)):                                       # candidate order of the survivors: prefix_merge_ref's sort lost it
+        for tok in top_tok[j]:
+            key = tuple(hyps[j][0]) + (() if int(tok) == blank else (int(tok),))
+            first.setdefault(key, len(first))
+    out.sort(key=lambda v: first[tuple(v[0])])
+    out.sort(key=lambda v: prefix_total_ref(v[1], v[5] if graph is not None else None, v[7] if ngram is not None else None), reverse=True)
+    return out[:beam_size]
+
+
+def prefix_total_ref(score, ctx_score=None, ng_score=None):
+    """The key of the second prune and the returned total: score + context score + n-gram score, left to right; None: feature off."""
+    t = score
+    if ctx_score is not None:
+        t = t + ctx_score
+    if ng_score is not None:
+        t = t + ng_score
+    return t
+
+
 # ---- streaming encoder: one stream through the oracle's forward_chunk under any window policy (tests) ---------------------------
 _REF_SD = {}
 

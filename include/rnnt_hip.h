@@ -629,6 +629,76 @@ int rnnt_stream_get_ctc_prefix_ngram(rnnt_ctx* ctx, int32_t slot, int32_t final,
                                      int32_t* lens_host, int32_t* tokens_host, int32_t* times_host, double* scores_host,
                                      double* ctx_scores_host, double* ngram_scores_host, int32_t* frames_out, void* stream);
 
+/* -- n-gram shallow fusion in the transducer prefix beam search (the model of rnnt_ngram_set, above) ------------------------------
+ * The rule of the CTC search carried over to the transducer frame step, as the hot words were.  THE DEFINITION:
+ *   - Every hypothesis carries (ngram_state, ngram_score) beside (context_state, context_score); neither is ever folded into the
+ *     running score.  [blank] holds the start MARKER (-1) and 0.0: the leading blank is never fed to the model, and the marker
+ *     resolves to the model's start state at the first step, so every reset path (the start of a call, rnnt_stream_prefix_reset,
+ *     rnnt_stream_open, rnnt_streams_reset, rnnt_pool_segment) is model-agnostic.
+ *   - First prune: untouched.  prefix_step does not see the model.
+ *   - Candidates: a blank copies its parent's state and score; any other token takes step(parent state, token) and adds the step's
+ *     score to the parent's.
+ *   - Prefix fusion: unchanged; the first candidate's state and score stay (both are functions of the token sequence alone).
+ *   - Second prune: the key is fused score + context score + n-gram score, evaluated left to right; a term whose feature is off is
+ *     left out, not added as 0.0.  Equal totals go to the lower candidate index; truncation to beam_size.
+ *   - End of the utterance: each survivor's n-gram score gains eos(state) (the marker resolves to the start state).  No re-sort.  The
+ *     returned total includes the end term; context finalize replaces the context score first, then the end term is added:
+ *     total = score + finalized context score + (n-gram score + eos).  A non-final read of a pool slot returns the running score.
+ *   - With use_ngram == 0, or a model with lm_weight = 0 and length_bonus = 0, tokens and scores are bit for bit those without the
+ *     model, and all n-gram scores are 0.
+ *
+ * rnnt_prefix_beam_decode_ctx plus use_ngram and ngram_scores_host [B, beam_size] (may be NULL): scores_host are the totals,
+ * ngram_scores_host their n-gram part, end term included.  use_ngram == 0 is rnnt_prefix_beam_decode_ctx, bit for bit, which is this
+ * call.  Also RNNT_ERR_STATE: use_ngram without a model set, decided before the first launch. */
+int rnnt_prefix_beam_decode_ngram(rnnt_ctx* ctx, const float* enc_dev, const int32_t* enc_lens_host, int32_t B, int32_t T,
+                                  int32_t beam_size, float ctc_weight, float transducer_weight, int32_t use_context, int32_t use_ngram,
+                                  int32_t cap_tokens, int32_t* n_hyp_host, int32_t* lens_host, int32_t* tokens_host, double* scores_host,
+                                  double* ctx_scores_host, double* ngram_scores_host, float* h_host, float* c_host, void* stream);
+/* rnnt_prefix_merge_ctx_host plus the model, passed as rnnt_ngram_walk_host takes it (the list, the three scalars, the vocabulary;
+ * the blank is the call's; n_ngrams == 0: none), and hyp_ng_state / hyp_ng_score [n_hyp] in (node ids of that model, or -1 = the
+ * start marker), the survivors' out_ng_state / out_ng_score out.  n_phrases == 0 means no graph: the context arguments may be NULL
+ * and the context outputs, if given, receive 0.  out_score stays the fused score; the order is by out_score (+ out_ctx_score)
+ * (+ out_ng_score).  With a model every candidate token other than the blank must be in [0, vocab). */
+int rnnt_prefix_merge_ngram_host(int32_t n_hyp, const int32_t* hyp_len, const int32_t* hyp_tokens, const double* hyp_score,
+                                 const int32_t* hyp_ctx_state, const double* hyp_ctx_score, const int32_t* hyp_ng_state,
+                                 const double* hyp_ng_score, const float* top_lp, const int32_t* top_tok, int32_t k, int32_t blank,
+                                 int32_t beam_size, int32_t n_phrases, const int32_t* phrase_lens, const int32_t* phrase_tokens,
+                                 double context_score, int32_t n_ngrams, const int32_t* ngram_lens, const int32_t* ngram_tokens,
+                                 const double* logp, const double* bow, double lm_weight, double length_bonus, double unk_logp,
+                                 int32_t vocab, int32_t* out_len, int32_t* out_tokens, double* out_score, int32_t* out_src_row,
+                                 int32_t* out_src_slot, int32_t* out_ctx_state, double* out_ctx_score, int32_t* out_ng_state,
+                                 double* out_ng_score);
+/* The same through ONE prefix_merge launch with the model that is set on the context (none: RNNT_ERR_STATE) and, when use_context
+ * != 0, its graph (none: RNNT_ERR_STATE); an n-gram state outside [-1, nodes) or a candidate token outside the model's vocabulary:
+ * RNNT_ERR_ARG.  Synchronises. */
+int rnnt_prefix_merge_ngram_device(rnnt_ctx* ctx, int32_t n_hyp, const int32_t* hyp_len, const int32_t* hyp_tokens,
+                                   const double* hyp_score, const int32_t* hyp_ctx_state, const double* hyp_ctx_score,
+                                   const int32_t* hyp_ng_state, const double* hyp_ng_score, const float* top_lp, const int32_t* top_tok,
+                                   int32_t k, int32_t blank, int32_t beam_size, int32_t use_context, int32_t* out_len,
+                                   int32_t* out_tokens, double* out_score, int32_t* out_src_row, int32_t* out_src_slot,
+                                   int32_t* out_ctx_state, double* out_ctx_score, int32_t* out_ng_state, double* out_ng_score,
+                                   void* stream);
+/* The pool calls of the transducer prefix search plus use_ngram (the two advancing calls) or ngram_scores_host [cap_hyps] (the read;
+ * may be NULL).  The rows also keep an n-gram state (int) and score (f64) per hypothesis in both buffer sets, allocated with the
+ * rest, counted by rnnt_live_device_bytes, released by rnnt_destroy.  A slot's first advancing call fixes use_ngram together with
+ * the beam, the two weights and use_context until its reset; a differing value: RNNT_ERR_ARG.  use_ngram without a model:
+ * RNNT_ERR_STATE.  rnnt_ngram_set starts a model generation: a search fused under an older one is refused with RNNT_ERR_STATE
+ * (advance, and read with final != 0) until its slot is reset; unfused searches go on.  The context keeps ONE model for this search
+ * and the CTC prefix search, as it keeps one graph.  Every refusal is decided before the first launch and changes nothing.  final
+ * != 0 adds the end term (after context finalize), final == 0 returns the running n-gram score; either way scores_host holds the
+ * totals.  A slot that fuses no model reads n-gram scores 0.  A call lists slots of one use_ngram.  The calls without the suffix
+ * are these calls with use_ngram = 0. */
+int rnnt_pool_prefix_frames_ngram(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, const float* enc_dev, int32_t t,
+                                  int32_t beam_size, float ctc_weight, float transducer_weight, int32_t use_context, int32_t use_ngram,
+                                  void* stream);
+int rnnt_pool_chunk_prefix_ngram(rnnt_ctx* ctx, int32_t n_active, const int32_t* slots_host, const float* fbank_dev,
+                                 int32_t chunk_frames, const int32_t* offsets_host, const int32_t* required_host, int32_t beam_size,
+                                 float ctc_weight, float transducer_weight, int32_t use_context, int32_t use_ngram, int32_t* frames_out,
+                                 void* stream);
+int rnnt_stream_get_prefix_ngram(rnnt_ctx* ctx, int32_t slot, int32_t final, int32_t cap_hyps, int32_t cap_tokens, int32_t* n_hyp,
+                                 int32_t* lens_host, int32_t* tokens_host, double* scores_host, double* ctx_scores_host,
+                                 double* ngram_scores_host, float* h_host, float* c_host, void* stream);
+
 /* -- teacher-forced scoring: how likely is a GIVEN transcript (forward only, no gradients) ----------------------------------- */
 /* Transducer negative log-likelihood: the RNN-T term of the reference's forward with texts (model/online_rnnt_model.py:240-255),
  * torchaudio.functional.rnnt_loss(reduction="none") -- minus the log of the sum over all monotonic alignments; its `clamp` only
