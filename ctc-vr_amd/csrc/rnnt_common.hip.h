@@ -17,6 +17,7 @@
 //   rnnt_frontend  reflect_pad, power_spectrum (rnnt_fbank); wave_stage, wave_carry_roll and their index helper (rnnt_pool_wave)
 //   rnnt_beam      beam_chain, beam_reduce, beam_gather, log_softmax_rows
 //   rnnt_prefix    prefix_step, prefix_merge, prefix_init, prefix_pack (rnnt_prefix_beam_decode)
+//   rnnt_loss      loss_pick, transducer_alpha_beta, loss_coef, loss_grad (rnnt_transducer_loss: the loss with its gradient)
 //   rnnt_misc      fill_i32, gather_att_cache, gather_cnn_cache
 #pragma once
 #include <hip/hip_runtime.h>

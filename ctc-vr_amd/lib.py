@@ -110,6 +110,9 @@ SIGNATURES = {
     "rnnt_transducer_nll": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "rnnt_ctc_nll": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "rnnt_transducer_nll_nbest": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "rnnt_transducer_loss_workspace": (c_i32, [c_i32, c_i32, c_i32, ctypes.POINTER(c_i64)]),
+    "rnnt_transducer_loss": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.c_float, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "rnnt_transducer_loss_host": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.c_float, c_vp, c_vp]),
     "rnnt_rescore_select_host": (c_i32, [c_i32, c_vp, c_vp, ctypes.c_double, ctypes.c_double, c_vp, c_i32p]),
     "rnnt_stream_keep_frames": (c_i32, [c_vp, c_i32, c_i32, c_vp]),
     "rnnt_stream_get_frames": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32p, c_vp]),
@@ -473,6 +476,54 @@ def endpoint_scan_host(blank_lp, cfg, state=None):
     if rc != 0:
         raise RnntError(f"rnnt_endpoint_scan_host: bad config or argument (status {rc})", rc)
     return st
+
+
+def _loss_args(targets, logit_lens, target_lens, B, umax):
+    tg = np.ascontiguousarray(targets, np.int32).reshape(B, umax)
+    ll, tl = np.ascontiguousarray(logit_lens, np.int32), np.ascontiguousarray(target_lens, np.int32)
+    if ll.shape != (B,) or tl.shape != (B,):
+        raise RnntError(f"rnnt_transducer_loss: {B} rows, but lengths of shapes {ll.shape} and {tl.shape}", ERR_ARG)
+    return tg, ll, tl
+
+
+_LOSS_REFUSALS = {ERR_ARG: "a length, label, blank or pointer outside its range", ERR_SHAPE: "Umax > 255, too many cells or a workspace too small"}
+
+
+def _loss_chk(rc, what, B, T, umax, V, blank):
+    if rc != 0:
+        raise RnntError(f"{what}: {_LOSS_REFUSALS.get(rc, 'HIP failure')} (B={B} T={T} Umax={umax} V={V} blank={blank}; status {rc})", rc)
+
+
+def transducer_loss_workspace(B, T, U1):
+    """rnnt_transducer_loss_workspace: bytes of the device workspace one rnnt_transducer_loss call of this shape needs."""
+    n = c_i64(0)
+    _loss_chk(load().rnnt_transducer_loss_workspace(B, T, U1, ctypes.byref(n)), "rnnt_transducer_loss_workspace", B, T, U1 - 1, "-", "-")
+    return int(n.value)
+
+
+def transducer_loss_host(logits, targets, logit_lens, target_lens, blank, fused_log_softmax=True, clamp=-1.0, want_grad=True):
+    """rnnt_transducer_loss_host (no context, no GPU): logits [B, T, Umax + 1, V] float32 -> (nll [B] float64, grad float64 of the
+    logits' shape or None).  Raises RnntError on a refusal."""
+    x = np.ascontiguousarray(logits, np.float32)
+    B, T, U1, V = x.shape
+    tg, ll, tl = _loss_args(targets, logit_lens, target_lens, B, U1 - 1)
+    nll = np.zeros(B, np.float64)
+    grad = np.zeros(x.shape, np.float64) if want_grad else None
+    rc = load().rnnt_transducer_loss_host(_np_ptr(x), _np_ptr(tg) if tg.size else None, _np_ptr(ll), _np_ptr(tl), B, T, U1 - 1, V, blank,
+                                          int(bool(fused_log_softmax)), float(clamp), _np_ptr(nll), _np_ptr(grad) if want_grad else None)
+    _loss_chk(rc, "rnnt_transducer_loss_host", B, T, U1 - 1, V, blank)
+    return nll, grad
+
+
+def transducer_loss_device(logits_ptr, shape, targets, logit_lens, target_lens, blank, fused_log_softmax, clamp, nll_ptr, grad_ptr, work_ptr,
+                           work_bytes, stream=None):
+    """rnnt_transducer_loss over device pointers: logits float32 of `shape` = (B, T, Umax + 1, V), nll [B] float64, grad float32 of
+    `shape` or None, the workspace of transducer_loss_workspace(B, T, Umax + 1).  Launches on `stream` and returns: no synchronisation."""
+    B, T, U1, V = shape
+    tg, ll, tl = _loss_args(targets, logit_lens, target_lens, B, U1 - 1)
+    rc = load().rnnt_transducer_loss(logits_ptr, _np_ptr(tg) if tg.size else None, _np_ptr(ll), _np_ptr(tl), B, T, U1 - 1, V, blank,
+                                     int(bool(fused_log_softmax)), float(clamp), nll_ptr, grad_ptr, work_ptr, work_bytes, stream)
+    _loss_chk(rc, "rnnt_transducer_loss", B, T, U1 - 1, V, blank)
 
 
 def wave_stage_host(carry, samples_so_far, new, final, n_fft=1024):

@@ -253,6 +253,81 @@ def transducer_nll_bruteforce(pick, T_b, U_b):
     return -(mx + math.log(math.fsum(math.exp(v - mx) for v in logs)))
 
 
+# ---- transducer loss with gradients: float64 yardstick and the device path's arithmetic contract (tests) ------------------------
+def transducer_loss_ref(logits, targets, T_b, U_b, blank, fused_log_softmax=True):
+    """(nll, grad) of one row by float64 torch autograd through log_softmax and the alpha recursion of transducer_nll_ref.
+    logits [T, U1, V] (only t < T_b, u <= U_b is read), targets: at least U_b labels.  grad [T, U1, V] float64 = d nll / d logits,
+    0 outside the valid cells.  fused_log_softmax=False: the input holds log-probabilities, differentiated as they stand."""
+    import torch
+    full = torch.as_tensor(np.asarray(logits))
+    x = full[:T_b, :U_b + 1].double().clone().requires_grad_(True)
+    lp = torch.log_softmax(x, -1) if fused_log_softmax else x
+    ninf = torch.tensor(-math.inf, dtype=torch.float64)
+    alpha = [[None] * (U_b + 1) for _ in range(T_b)]
+    for t in range(T_b):
+        for u in range(U_b + 1):
+            if t == 0 and u == 0:
+                alpha[t][u] = torch.zeros((), dtype=torch.float64)
+                continue
+            below = alpha[t - 1][u] + lp[t - 1, u, blank] if t > 0 else ninf
+            left = alpha[t][u - 1] + lp[t, u - 1, int(targets[u - 1])] if u > 0 else ninf
+            alpha[t][u] = below if u == 0 else (left if t == 0 else torch.logaddexp(below, left))
+    nll = -(alpha[T_b - 1][U_b] + lp[T_b - 1, U_b, blank])
+    nll.backward()
+    grad = np.zeros(tuple(full.shape), np.float64)
+    grad[:T_b, :U_b + 1] = x.grad.numpy()
+    return float(nll.detach()), grad
+
+
+def _loss_from_picks(x, lse, pb, pl, targets, T_b, U_b, blank, fused_log_softmax, shape):
+    """The gradient formula of rnnt_transducer_loss in float64 from a valid region's logits x [T_b, U_b + 1, V], lse and the two
+    picked values [T_b, U_b + 1]: both recursions, then g_k = p_k occ - blank term - label term."""
+    al = np.full((T_b, U_b + 1), -math.inf)
+    be = np.full((T_b, U_b + 1), -math.inf)
+    for t in range(T_b):
+        for u in range(U_b + 1):
+            if t == 0 and u == 0:
+                al[t, u] = 0.0
+                continue
+            al[t, u] = _logaddexp(al[t - 1, u] + pb[t - 1, u] if t > 0 else -math.inf, al[t, u - 1] + pl[t, u - 1] if u > 0 else -math.inf)
+    for t in range(T_b - 1, -1, -1):
+        for u in range(U_b, -1, -1):
+            if t == T_b - 1 and u == U_b:
+                be[t, u] = pb[t, u]
+                continue
+            be[t, u] = _logaddexp(be[t + 1, u] + pb[t, u] if t + 1 < T_b else -math.inf, be[t, u + 1] + pl[t, u] if u < U_b else -math.inf)
+    logZ = be[0, 0]
+    grad = np.zeros(shape, np.float64)
+    for t in range(T_b):
+        for u in range(U_b + 1):
+            g = np.exp(x[t, u] - lse[t, u]) * math.exp(al[t, u] + be[t, u] - logZ) if fused_log_softmax else np.zeros(x.shape[-1])
+            if t < T_b - 1:
+                g[blank] -= math.exp(al[t, u] + pb[t, u] + be[t + 1, u] - logZ)
+            elif u == U_b:
+                g[blank] -= math.exp(al[t, u] + pb[t, u] - logZ)
+            if u < U_b:
+                g[int(targets[u])] -= math.exp(al[t, u] + pl[t, u] + be[t, u + 1] - logZ)
+            grad[t, u] = g
+    return -logZ, grad
+
+
+def transducer_loss_f32_emulation(logits, targets, T_b, U_b, blank, fused_log_softmax=True):
+    """The arithmetic contract of the device path, on the CPU: lse (torch's CPU logsumexp) and the two picked values logit - lse in
+    float32, everything after them -- both recursions, p_k = exp(logit_k - lse), the three factors -- in float64.  Arguments and
+    result as transducer_loss_ref.  Its distance from transducer_loss_ref is what float32 picks cost; the device is held to a
+    small multiple of it."""
+    import torch
+    full = torch.as_tensor(np.asarray(logits))
+    x32 = full[:T_b, :U_b + 1].float()
+    lse32 = torch.logsumexp(x32, -1) if fused_log_softmax else torch.zeros(T_b, U_b + 1)
+    tg = torch.as_tensor(np.asarray(targets)[:U_b].astype(np.int64))
+    pb = (x32[..., blank] - lse32).double().numpy()
+    pl = np.full((T_b, U_b + 1), -math.inf)
+    if U_b:
+        pl[:, :U_b] = (x32[:, :U_b].gather(2, tg[None, :, None].expand(T_b, U_b, 1))[..., 0] - lse32[:, :U_b]).double().numpy()
+    return _loss_from_picks(x32.double().numpy(), lse32.double().numpy(), pb, pl, targets, T_b, U_b, blank, fused_log_softmax, tuple(full.shape))
+
+
 # ---- forced alignment: float64 restatements of the two Viterbi recursions (tests) ----------------------------------------------
 def _transducer_forward(p, T_b, U_b):
     """v[t, u] and the move into each cell (True: the label move from (t, u-1)); the blank move wins ties."""

@@ -699,7 +699,7 @@ int rnnt_stream_get_prefix_ngram(rnnt_ctx* ctx, int32_t slot, int32_t final, int
                                  int32_t* lens_host, int32_t* tokens_host, double* scores_host, double* ctx_scores_host,
                                  double* ngram_scores_host, float* h_host, float* c_host, void* stream);
 
-/* -- teacher-forced scoring: how likely is a GIVEN transcript (forward only, no gradients) ----------------------------------- */
+/* -- teacher-forced scoring: how likely is a GIVEN transcript (forward only; rnnt_transducer_loss below has gradients) ----------------------------------- */
 /* Transducer negative log-likelihood: the RNN-T term of the reference's forward with texts (model/online_rnnt_model.py:240-255),
  * torchaudio.functional.rnnt_loss(reduction="none") -- minus the log of the sum over all monotonic alignments; its `clamp` only
  * touches gradients.  Per row b: joint.enc_ffn of its frames, the predictor over [blank, y_1 .. y_Umax] from the zero state
@@ -728,6 +728,44 @@ int rnnt_transducer_nll(rnnt_ctx* ctx, const float* enc_dev, const int32_t* enc_
  * ctc_head.ctc_lo.{weight,bias}.  Synchronises. */
 int rnnt_ctc_nll(rnnt_ctx* ctx, const float* enc_dev, const int32_t* enc_lens_host, const int32_t* targets_host,
                  const int32_t* target_lens_host, int32_t B, int32_t T, int32_t Umax, double* nll_host, void* stream);
+
+/* -- training: the transducer loss WITH its gradient over a caller's joint lattice (torchaudio.functional.rnnt_loss) -------------- */
+/* The three entry points take no context: a loss needs no weights and no model, so a refusal is its status code alone.
+ * Per row b the loss is rnnt_transducer_nll's likelihood -- minus the log of the sum over all monotonic alignments -- computed from
+ * logits [B, T, Umax + 1, V] float32 (what rnnt_joint(mode 0) and the reference's joint write), and grad is d nll_b / d logits:
+ *   loss_pick: one pass over the valid cells (t < T_b, u <= U_b): the max-subtracted log-sum-exp over V in a fixed order (no
+ *     atomics: two calls agree bit for bit), lse [B, T, U1] and pick [B, T, U1, 2] = (logit_blank - lse, logit_{y_{u+1}} - lse) in
+ *     rnnt_transducer_nll's layout (label slot for u < U_b only);
+ *   transducer_alpha_beta: rnnt_transducer_nll's forward recursion and its mirror image, beta[T_b-1,U_b] = pick_blank, beta[t,u] =
+ *     logaddexp(beta[t+1,u] + pick_blank[t,u], beta[t,u+1] + pick_label[t,u]), both f64 and both stored; nll_b = -beta[0,0];
+ *   loss_coef, loss_grad: with p_k = exp(logit_k - lse) and logZ = beta[0,0], g_k = p_k exp(alpha + beta - logZ), minus
+ *     exp(alpha + pick_blank + beta[t+1,u] - logZ) at k = blank (at t = T_b - 1 only for u = U_b, with beta[T_b,U_b] := 0), minus
+ *     exp(alpha + pick_label + beta[t,u+1] - logZ) at k = y_{u+1} (u < U_b); clamp > 0 clamps every g_k to [-clamp, clamp].
+ * float32 lse, picks, p_k and the three per-cell factors; f64 recursions and exponents.  The lattice is read twice and written once.
+ *   logits_dev [B, T, Umax + 1, V] device, 16-byte aligned; targets_host [B, Umax] int32 (may be NULL when Umax = 0);
+ *   logit_lens_host [B] (T_b in [1, T]); target_lens_host [B] (U_b in [0, Umax]); V >= 2 is any size; blank in [0, V);
+ *   fused_log_softmax = 0: the input holds log-probabilities already (lse taken as 0, no p_k term: the gradient with respect to them);
+ *   nll_dev [B] double, device; grad_dev: NULL (value only: the same nll bit for bit), or device float [B, T, Umax + 1, V], 16-byte
+ *   aligned, EVERY element written: exactly 0 outside the valid cells; workspace_dev: device, 16-byte aligned, at least the bytes
+ *   rnnt_transducer_loss_workspace(B, T, Umax + 1) reports.  It begins with [B] doubles that receive -(alpha[T_b-1,U_b] +
+ *   pick_blank), the same likelihood from the forward recursion; the rest (alpha, beta, factors, pick, lse, lengths, targets) is scratch.
+ * Cells outside the valid region, and targets beyond a row's length, are never read: they may hold anything, NaN included.
+ * One upload of lengths and targets (an asynchronous copy from pageable host memory, which the runtime may complete before it
+ * returns), then four launches (two without grad_dev) on `stream`; no stream or device synchronisation, the stream orders
+ * the outputs.  Refusals, all decided on the host before the first launch, changing nothing: a null pointer, a misaligned device
+ * pointer, B < 1, T_b outside [1, T], U_b outside [0, Umax], V < 2, blank outside [0, V), a label outside [0, V) or equal to blank
+ * inside a row's length: RNNT_ERR_ARG; Umax > 255, B * T * (Umax + 1) >= 2^31 - 1, a workspace that is too small: RNNT_ERR_SHAPE. */
+int rnnt_transducer_loss_workspace(int32_t B, int32_t T, int32_t U1, int64_t* bytes_out);
+int rnnt_transducer_loss(const float* logits_dev, const int32_t* targets_host, const int32_t* logit_lens_host,
+                         const int32_t* target_lens_host, int32_t B, int32_t T, int32_t Umax, int32_t V, int32_t blank,
+                         int32_t fused_log_softmax, float clamp, double* nll_dev, float* grad_dev, void* workspace_dev,
+                         int64_t workspace_bytes, void* stream);
+/* The same loss as a pure C++ function (no context, no GPU), f64 throughout over the float32 logits: logits_host as logits_dev,
+ * nll_host [B] double, grad_host NULL or double [B, T, Umax + 1, V] (0 outside the valid cells).  Same ranges and refusals, without
+ * the alignment and workspace ones; a refused call writes nothing. */
+int rnnt_transducer_loss_host(const float* logits_host, const int32_t* targets_host, const int32_t* logit_lens_host,
+                              const int32_t* target_lens_host, int32_t B, int32_t T, int32_t Umax, int32_t V, int32_t blank,
+                              int32_t fused_log_softmax, float clamp, double* nll_host, double* grad_host);
 
 /* -- two-pass decoding: a cheap first pass yields n-best, the transducer likelihood re-scores it (the reference's WeNet layer:
  * Transducer.transducer_attention_rescoring with _cal_transducer_score, wenet/transducer/transducer.py:160-185, 261-395) ------- */
