@@ -66,7 +66,7 @@ int rnnt_create(const rnnt_config* cfg, rnnt_ctx** out) {
     ALLOC(pred, (size_t)B * D); ALLOC(z, (size_t)B * D); ALLOC(logits, (size_t)B * ctx->vpad);
     ALLOC(tok, B); ALLOC(fidx, B); ALLOC(nsym, B); ALLOC(count, B); ALLOC(tokens, (size_t)B * cfg->max_tokens);
     ALLOC(n_active, 4); ALLOC(klen, B); ALLOC(dec_ctrl, 32);
-    ALLOC(gm_dbg, 16);
+    ALLOC(gm_dbg, (size_t)B * GM_DBG_W);
     ALLOC(gm_x1, (size_t)2 * B * GM_PARTS * GM_X1);
     ALLOC(gm_xa, (size_t)2 * B * GM_PARTS * 2 * GREEDY_KF);
     if (cfg->max_beam > 0) {

@@ -140,7 +140,9 @@ int launch_multi_decoder(rnnt_ctx* ctx, hipStream_t s, const DecP& common) {
     // tags restart at 1 every launch: no word of an earlier launch may survive
     HIPCHK(hipMemsetAsync(ctx->gm_x1, 0, (size_t)2 * B * GM_PARTS * GM_X1 * sizeof(unsigned long long), s));
     HIPCHK(hipMemsetAsync(ctx->gm_xa, 0, (size_t)2 * B * GM_PARTS * 2 * GREEDY_KF * sizeof(unsigned long long), s));
-    const size_t lds = ((size_t)rows_per * GM_WLD + 4 * D + GREEDY_KF * D + 16 * GREEDY_KF + GM_PARTS * 2 * GREEDY_KF + 8 + GREEDY_KF * 4 * 128) * sizeof(float);
+    const size_t lds = ((size_t)rows_per * GM_WLD + 4 * D + GREEDY_KF * D + 16 * GREEDY_KF + GM_PARTS * 2 * GREEDY_KF + 8 + GREEDY_KF * 4 * 128) * sizeof(float)
+                       + GM_DBG_W * sizeof(long long);
+    ctx->gm_dbg_rows = gdbg ? B : 0;
     { const int rc_attr = ensure_dyn_lds(ctx, reinterpret_cast<const void*>(&greedy_multi<GREEDY_KF>), 160 * 1024); if (rc_attr) return rc_attr; }
     hipLaunchKernelGGL(greedy_multi<GREEDY_KF>, dim3((unsigned)((B + 7) / 8 * 8 * GM_PARTS)), dim3(512), lds, s, d);
     LAUNCHCHK("greedy_multi");
@@ -193,13 +195,28 @@ int finish_persistent_decoder(rnnt_ctx* ctx, hipStream_t s) {
     HIPCHK(hipMemcpyAsync(ctx->pinned + 12, ctx->dec_ctrl, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     ctx->greedy_steps += ctx->pinned[14];
-    if (getenv("RNNT_GM_DBG") && multi_decoder_ok(ctx, ctx->n_streams)) {
-        long long t[16];
-        (void)hipMemcpy(t, ctx->gm_dbg, sizeof(t), hipMemcpyDeviceToHost);
-        const double ev = t[8] > 0 ? (double)t[8] : 1.0, sy = t[9] > 0 ? (double)t[9] : 1.0;
-        fprintf(stderr, "[greedy_multi] stream 0: %lld passes, %lld symbols; us per pass: frames %.2f, decide-tail %.2f, z+logits %.2f, wait XA %.2f; "
-                        "us per symbol: W_hh %.2f, cell+W_c %.2f, wait X1 %.2f\n",
-                t[8], t[9], t[0] / ev / 100.0, t[6] / ev / 100.0, t[4] / ev / 100.0, t[5] / ev / 100.0, t[1] / sy / 100.0, t[2] / sy / 100.0, t[3] / sy / 100.0);
+    if (ctx->gm_dbg_rows > 0) {
+        // RNNT_GM_DBG: the stamps of one stream group of the launch -- the one with the largest token count (the slowest chain of the
+        // batch), or row RNNT_GM_DBG_STREAM -- as microseconds per pass, dirty (predictor) and non-dirty passes apart
+        const int rows = ctx->gm_dbg_rows;
+        ctx->gm_dbg_rows = 0;
+        std::vector<long long> t((size_t)rows * GM_DBG_W);
+        (void)hipMemcpy(t.data(), ctx->gm_dbg, t.size() * sizeof(long long), hipMemcpyDeviceToHost);
+        int row = 0;
+        const char* want = getenv("RNNT_GM_DBG_STREAM");
+        if (want && atoi(want) >= 0 && atoi(want) < rows) row = atoi(want);
+        else for (int i = 1; i < rows; ++i) if (t[(size_t)i * GM_DBG_W + 24] > t[(size_t)row * GM_DBG_W + 24]) row = i;
+        const long long* r = t.data() + (size_t)row * GM_DBG_W;
+        static const char* const name[10] = {"frames", "W_hh", "cell+W_c", "wait X1", "tanh", "quarter sums", "finish+argmax", "XA store", "wait XA", "tail"};
+        fprintf(stderr, "[greedy_multi] row %d (stream %lld, %lld tokens): %lld dirty + %lld non-dirty passes; us per pass, dirty / non-dirty:", row, r[25], r[24],
+                r[22], r[10]);
+        double sum[2] = {0.0, 0.0};
+        for (int k = 0; k < 10; ++k) {
+            const double d = r[12 + k] / 100.0 / (double)(r[22] > 0 ? r[22] : 1), n = r[k] / 100.0 / (double)(r[10] > 0 ? r[10] : 1);
+            sum[0] += d; sum[1] += n;
+            fprintf(stderr, " %s %.2f / %.2f,", name[k], d, n);
+        }
+        fprintf(stderr, " total %.2f / %.2f\n", sum[0], sum[1]);
     }
     if (ctx->pinned[13] != 0) return fail(ctx, RNNT_ERR_STATE, "persistent decoder gave up (code %d: 1 = frame wait, 2 = greedy_multi exchange wait)", ctx->pinned[13]);
     return RNNT_OK;

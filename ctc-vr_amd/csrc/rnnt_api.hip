@@ -202,7 +202,8 @@ struct rnnt_ctx {
     int use_multi = 1;         // RNNT_DEC_MULTI=0: one CU per stream (greedy_stream) instead of greedy_multi (4 CUs per stream)
     int n_cus = 0;
     DevBuf<unsigned long long> gm_x1, gm_xa;  // greedy_multi mailboxes
-    DevBuf<long long> gm_dbg;                 // [16] greedy_multi phase timers (RNNT_GM_DBG=1)
+    DevBuf<long long> gm_dbg;                 // [max_streams][GM_DBG_W] greedy_multi phase timers (RNNT_GM_DBG=1)
+    int gm_dbg_rows = 0;                      // stream groups of the last greedy_multi launch that wrote them
     const float *wjc = nullptr, *bjc = nullptr;   // folded joint.pred_ffn o predictor.projection
     const float *wctc = nullptr, *bctc = nullptr; // ctc_head.ctc_lo (optional)
     // beam search: state pools [rows][n_steps+1][512] (ping-pong), per-row buffers

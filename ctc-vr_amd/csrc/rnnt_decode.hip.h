@@ -365,11 +365,12 @@ __device__ __forceinline__ void st_tag(unsigned long long* p, unsigned payload, 
 #define GM_PARTS 4
 #define GM_X1 320            // words per part: 64 h' + 256 pp partials
 #define GM_WLD 260           // LDS row stride of the W_out slice (floats)
+#define GM_DBG_W 32          // stamp words per stream: [12 c + k] phase k of non-dirty (c = 0) / dirty (c = 1) passes, [12 c + 10] passes, [24] count, [25] stream
 struct DecMP : DecP {           // slots: stream group i (mailboxes i) decodes stream slots[i]
     unsigned long long* x1;      // [2][B][4][GM_X1]
     unsigned long long* xa;      // [2][B][4][2 * KF]
     int rows_per;                // ceil(vocab / 4): vocabulary rows of a part (<= 128), resident in LDS
-    long long* dbg;              // optional [16]: phase timers of workgroup (stream 0, part 0), 100 MHz ticks (RNNT_GM_DBG=1)
+    long long* dbg;              // optional [B][GM_DBG_W]: phase timers of part 0 of every stream group, 100 MHz ticks (RNNT_GM_DBG=1)
 };
 
 // spin until the word carries `tag`; false on abort / timeout (sets the error and abort words)
@@ -404,10 +405,10 @@ __device__ __forceinline__ bool gm_poll(const DecMP& p, const unsigned long long
 template <int KF>
 __global__ __launch_bounds__(512) void greedy_multi(DecMP p) {
     extern __shared__ __attribute__((aligned(16))) float gm_smem[];
-    float* Wo = gm_smem;                                  // [rows_per][GM_WLD]  this part's vocabulary rows of W_out
-    float* hs = Wo + p.rows_per * GM_WLD;                 // [256] committed h
-    float* h2 = hs + RNNT_D;                              // [256] candidate h'
-    float* pp = h2 + RNNT_D;                              // [256] W_c h' + b_c
+    long long* tsh = reinterpret_cast<long long*>(gm_smem);   // [GM_DBG_W] phase stamps (touched only under RNNT_GM_DBG)
+    float* Wo = gm_smem + 2 * GM_DBG_W;                   // [rows_per][GM_WLD]  this part's vocabulary rows of W_out
+    float* hb = Wo + p.rows_per * GM_WLD;                 // [2][256] h ping-pong: the committed h in one half, the candidate h' in the other; a commit swaps the roles
+    float* pp = hb + 2 * RNNT_D;                          // [256] W_c h' + b_c
     float* mypp = pp + RNNT_D;                            // [256] this part's partial
     float* zs = mypp + RNNT_D;                            // [KF][256]
     float* redv = zs + KF * RNNT_D;                       // [8 waves][KF]
@@ -426,7 +427,9 @@ __global__ __launch_bounds__(512) void greedy_multi(DecMP p) {
     const bool cell = (tid0 & 7) == 0;
     const int v0 = p.rows_per * pw;                        // first vocabulary row of this part
     float cc = 0.f, cc2 = 0.f;
+#if !GM_WHH_REGS
     float* gates = zs;                                     // [256] gate pre-activations of this part (zs is free during the predictor step)
+#endif
 #if GM_WHH_REGS
     float whh_r[128];                                      // W_hh[256 pw + tid / 2][128 (tid & 1) .. +128)
     {
@@ -454,24 +457,33 @@ __global__ __launch_bounds__(512) void greedy_multi(DecMP p) {
     }
     // ---- state ---------------------------------------------------------------------------------------------------------------
     const long long soff = (long long)(ldgi(p.sel + b) & 1) * p.bstride + (long long)b * RNNT_D;
-    if (tid < RNNT_D) hs[tid] = ldg1(p.h + soff + tid);
+    if (tid < RNNT_D) hb[tid] = ldg1(p.h + soff + tid);
     cc = cell ? ldg1(p.c + soff + cell_unit) : 0.f;
     cc2 = cc;
     if (tid == 0) *s_bad = 0;
+    if (tid < GM_DBG_W) tsh[tid] = 0;
     }
+    // The bias words a thread adds on every pass, fetched once: b_out of its row in the logit finish (and, for wave 0, of the row 64
+    // further on, which it finishes too in a one-frame pass), b_c of its pp element in the X1 gather.
+    const int rfin = tid0 & 127;
+    const float bout_r = (rfin < p.rows_per && v0 + rfin < p.vocab) ? ldg1(p.bout + v0 + rfin) : 0.f;
+    const float bout_h = (tid0 < 64 && tid0 + 64 < p.rows_per && v0 + tid0 + 64 < p.vocab) ? ldg1(p.bout + v0 + tid0 + 64) : 0.f;
+    const float bjc_r = tid0 < RNNT_D ? ldg1(p.bjc + tid0) : 0.f;
     int tok = ldgi(p.tok + b), fidx = p.slots ? 0 : ldgi(p.fidx + b), nsym = ldgi(p.nsym + b), count = ldgi(p.count + b);
     const int n_total = p.nlim ? min(p.n_total, ldgi(p.nlim + b)) : p.n_total;
     const float* encp = p.encp + (long long)b * p.fstride_f;
     unsigned long long* x1b = p.x1 + (long long)bi * GM_PARTS * GM_X1;
     unsigned long long* xab = p.xa + (long long)bi * GM_PARTS * 2 * KF;
-    const long long x1par = (long long)p.B * GM_PARTS * GM_X1, xapar = (long long)p.B * GM_PARTS * 2 * KF;
-    unsigned ev1 = 0, ev3 = 0;
-    int evals = 0, seen_ready = 0;
+    const unsigned x1par = (unsigned)p.B * GM_PARTS * GM_X1, xapar = (unsigned)p.B * GM_PARTS * 2 * KF;   // words between the two parities (4 B <= CUs: small)
+    unsigned ev1 = 1, ev3 = 0;   // ev1: sequence number of the X1 exchange of the next predictor step = 1 + commits so far
+    int seen_ready = 0;
     bool dirty = true, bad = false;
-    long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tl = (long long)__builtin_amdgcn_s_memrealtime();
-    const bool tdbg = p.dbg != nullptr && b == 0 && pw == 0 && tid0 == 0;
-#define GM_T(k) { if (tdbg) { const long long t_ = (long long)__builtin_amdgcn_s_memrealtime(); tacc[k] += t_ - tl; tl = t_; } }
-    int nsymev = 0;
+    // Phase stamps (RNNT_GM_DBG): thread 0 of part 0 adds the ticks since its last stamp to an LDS word with a no-return atomic, so a
+    // stamp costs one clock read and holds no registers; dirty and non-dirty passes are kept apart.
+    long long tl = (long long)__builtin_amdgcn_s_memrealtime();
+    const bool tdbg = p.dbg != nullptr && pw == 0 && tid0 == 0;
+#define GM_T(k) { if (tdbg) { const long long t_ = (long long)__builtin_amdgcn_s_memrealtime(); \
+                              (void)__hip_atomic_fetch_add(tsh + (dirty ? 12 : 0) + (k), t_ - tl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); tl = t_; } }
     __syncthreads();
     while (fidx < n_total) {
         // Every index below is derived from an OPAQUE copy of the thread id made inside the iteration: with plain loop-invariant
@@ -480,7 +492,8 @@ __global__ __launch_bounds__(512) void greedy_multi(DecMP p) {
         int tid = tid0;
         asm volatile("" : "+v"(tid));
         const int lane = tid & 63, wave = tid >> 6, row2 = tid >> 1, kh = tid & 1;
-        (void)lane;
+        float* hs = hb + (ev1 & 1 ? 0 : RNNT_D);             // committed h: the half changes with every commit
+        float* h2 = hb + (ev1 & 1 ? RNNT_D : 0);             // candidate h'
         // ---- frames available (bounded wait; the sequential schedule publishes everything before the launch) -----------------
         int avail = seen_ready;
         if (avail <= fidx) {
@@ -515,12 +528,12 @@ __global__ __launch_bounds__(512) void greedy_multi(DecMP p) {
             const int e = tid + 512 * i2, k = e >> 8;
             er[i2] = k < kf ? ldg1(encp + (long long)(fidx + k) * RNNT_D + (e & 255)) : 0.f;
         }
+        if (tdbg) (void)__hip_atomic_fetch_add(tsh + (dirty ? 12 : 0) + 10, 1ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         GM_T(0)
         if (dirty) {
-            ++nsymev;
             // ---- predictor step on this part's 64 units (predictor.py:200-204), then X1 ---------------------------------------
-            ++ev1;
             unsigned long long* xw = x1b + (ev1 & 1) * x1par;
+            float gi = 0.f, gf = 0.f, gg = 0.f, go = 0.f;     // gate pre-activations of this lane group's hidden unit
 #if GM_WHH_REGS
             {
                 const float eg = ldg1(p.egate + (long long)tok * (4 * RNNT_D) + 256 * pw + row2);
@@ -535,8 +548,14 @@ __global__ __launch_bounds__(512) void greedy_multi(DecMP p) {
                     if ((j & 3) == 3) __builtin_amdgcn_sched_barrier(0);
                 }
                 float g = (a0 + a1) + (a2 + a3);
-                g += __shfl_xor(g, 1, 64);
-                if (!kh) gates[row2] = g + eg;
+                g += __shfl_xor(g, 1, 64);                   // both lanes of a row hold the same bits (the sum commutes)
+                // The i, f, g, o rows of a hidden unit sit in lane pairs 0-1, 2-3, 4-5, 6-7 of one group of eight lanes, so the unit's
+                // first lane takes them through DPP and no LDS round trip or barrier stands between the product and the cell:
+                // f from lane ^ 2, o from the mirror lane 7, g from the mirror of the quad swap (lane 5).
+                gi = g + eg;
+                gf = xor_partner<2>(gi);
+                go = xor_partner<4>(gi);
+                gg = xor_partner<4>(gf);
             }
 #else
             {
@@ -544,14 +563,17 @@ __global__ __launch_bounds__(512) void greedy_multi(DecMP p) {
                 dec_matvec<1, 512, 4>(p.whh + (long long)(256 * pw) * RNNT_D, RNNT_D, reinterpret_cast<const float (*)[RNNT_D]>(hs),
                                       [&](int n, const float* acc) { gates[n] = acc[0] + ldg1(eg + n); });
             }
-#endif
             __syncthreads();
+            if (cell) {
+                const float4 gt = *reinterpret_cast<const float4*>(&gates[4 * (tid >> 3)]);     // i, f, g, o of this unit
+                gi = gt.x; gf = gt.y; gg = gt.z; go = gt.w;
+            }
+#endif
             GM_T(1)
             if (cell) {
                 const int unit = 64 * pw + (tid >> 3);
-                const float4 gt = *reinterpret_cast<const float4*>(&gates[4 * (tid >> 3)]);     // i, f, g, o of this unit
-                cc2 = sigmoidf_(gt.y) * cc + sigmoidf_(gt.x) * tanhf(gt.z);
-                const float hn = sigmoidf_(gt.w) * tanhf(cc2);
+                cc2 = sigmoidf_(gf) * cc + sigmoidf_(gi) * tanhf(gg);
+                const float hn = sigmoidf_(go) * tanhf(cc2);
                 h2[unit] = hn;
                 st_tag(xw + pw * GM_X1 + (unit - 64 * pw), __float_as_uint(hn), ev1);
             }
@@ -588,7 +610,9 @@ __global__ __launch_bounds__(512) void greedy_multi(DecMP p) {
                     }
                     sum = q == 0 ? v : sum + v;
                 }
-                pp[tid] = sum + ldg1(p.bjc + tid);
+                const float ppv = sum + bjc_r;
+                pp[tid] = ppv;
+                zs[tid] = tanhf(ppv + er[0]);                 // the one frame of this pass: its joint activations, formed by the thread that holds pp[n]
             } else if (tid < RNNT_D + 192) {
                 const int idx = tid - RNNT_D;
                 int q = idx >> 6;
@@ -600,16 +624,19 @@ __global__ __launch_bounds__(512) void greedy_multi(DecMP p) {
             if (bad) *s_bad = 1;
             __syncthreads();
             if (*s_bad) { bad = true; break; }
-            dirty = false;
             GM_T(3)
         }
-        // ---- joint activations of kf frames (every part computes all 256) ------------------------------------------------------
+        // ---- joint activations of kf frames (every part computes all 256).  A predictor pass has one frame and formed them in the X1
+        // gather above, behind that phase's barrier: no second barrier and no trip of pp through LDS on the symbol chain. ---------------
+        if (!dirty) {
 #pragma unroll
-        for (int i2 = 0; i2 < KF * RNNT_D / 512; ++i2) {
-            const int e = tid + 512 * i2, k = e >> 8;
-            zs[e] = k < kf ? tanhf(pp[e & 255] + er[i2]) : 0.f;
+            for (int i2 = 0; i2 < KF * RNNT_D / 512; ++i2) {
+                const int e = tid + 512 * i2, k = e >> 8;
+                zs[e] = k < kf ? tanhf(pp[e & 255] + er[i2]) : 0.f;
+            }
+            __syncthreads();
         }
-        __syncthreads();
+        GM_T(4)
         // ---- logits of this part's vocabulary rows.  Thread (row = tid & 127, quarter of K = tid >> 7): a wave reads 64 consecutive
         // rows at one quarter, so the 16 lanes of a ds_read_b128 cycle hit 16 distinct slots (row stride 260 floats) and z is a
         // broadcast; the four quarter sums meet in LDS, then thread (frame, row) finishes the logit and the argmax runs per frame.
@@ -638,45 +665,88 @@ __global__ __launch_bounds__(512) void greedy_multi(DecMP p) {
             }
         }
         __syncthreads();
-        {
-            const int k = tid >> 7, r = tid & 127;         // KF * 128 = 512 threads
-            const int vr = v0 + r;
-            const bool vin = k < kf && r < p.rows_per && vr < p.vocab;
-            float v = -INFINITY;
-            int ix = 0x7fffffff;
-            if (vin) {
-                v = ((lpart[(k * 4) * 128 + r] + lpart[(k * 4 + 1) * 128 + r]) + (lpart[(k * 4 + 2) * 128 + r] + lpart[(k * 4 + 3) * 128 + r])) + ldg1(p.bout + vr);
-                ix = vr;
-            }
-            // ascending butterfly; DPP partners for 1..8 (xor_partner: the (value, index) pair is uniform in quads / 8-groups by then)
-#define GM_STEP(O_) { const float ov = xor_partner<O_>(v); const int oi = __builtin_bit_cast(int, xor_partner<O_>(__builtin_bit_cast(float, ix))); \
-                      if (ov > v || (ov == v && oi < ix)) { v = ov; ix = oi; } }
-            GM_STEP(1) GM_STEP(2) GM_STEP(4) GM_STEP(8) GM_STEP(16) GM_STEP(32)
-#undef GM_STEP
-            if (lane == 0) { redv[wave] = v; redi[wave] = ix; }   // wave 2 k, 2 k + 1 = frame k
-        }
-        __syncthreads();
-        GM_T(4)
+        GM_T(5)
         ++ev3;
         unsigned long long* xq = xab + (ev3 & 1) * xapar;
-        if (tid < KF) {
-            float v = redv[2 * tid];
-            int ix = redi[2 * tid];
+        // ascending butterfly; DPP partners for 1..8 (xor_partner: the (value, index) pair is uniform in quads / 8-groups by then)
+#define GM_STEP(O_) { const float ov = xor_partner<O_>(v); const int oi = __builtin_bit_cast(int, xor_partner<O_>(__builtin_bit_cast(float, ix))); \
+                      if (ov > v || (ov == v && oi < ix)) { v = ov; ix = oi; } }
+        if (kf == 1) {
+            // One frame (every pass after a symbol): wave 0 alone finishes the part's rows, lane l rows l and l + 64, compares the two in
+            // registers, runs one butterfly and stores the XA words itself -- no second barrier and no trip through redv / redi.  The
+            // order (larger value, then smaller index) is total, so the winner is the one the two-wave merge below would name.
+            if (wave == 0) {
+                float v = -INFINITY;
+                int ix = 0x7fffffff;
+                if (lane < p.rows_per && v0 + lane < p.vocab) {
+                    v = ((lpart[lane] + lpart[128 + lane]) + (lpart[2 * 128 + lane] + lpart[3 * 128 + lane])) + bout_r;
+                    ix = v0 + lane;
+                }
+                if (lane + 64 < p.rows_per && v0 + lane + 64 < p.vocab) {
+                    const float ov = ((lpart[64 + lane] + lpart[128 + 64 + lane]) + (lpart[2 * 128 + 64 + lane] + lpart[3 * 128 + 64 + lane])) + bout_h;
+                    const int oi = v0 + lane + 64;
+                    if (ov > v || (ov == v && oi < ix)) { v = ov; ix = oi; }
+                }
+                // Only the stores below need the winner, so the rows of 16 lanes meet by DPP row broadcasts instead of two LDS permutes:
+                // lane 15 / 47 into rows 1 / 3, then lane 31 into rows 2 and 3; lane 63 holds the wave's best and is read back uniformly.
+#define GM_BCAST(C_, M_) { const float ov = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, v), __builtin_bit_cast(int, v), C_, M_, 0xF, false)); \
+                           const int oi = __builtin_amdgcn_update_dpp(ix, ix, C_, M_, 0xF, false); \
+                           if (ov > v || (ov == v && oi < ix)) { v = ov; ix = oi; } }
+                GM_STEP(1) GM_STEP(2) GM_STEP(4) GM_STEP(8) GM_BCAST(0x142, 0xA) GM_BCAST(0x143, 0xC)
+#undef GM_BCAST
+                v = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
+                ix = __builtin_amdgcn_readlane(ix, 63);
+                GM_T(6)
+                if (lane < KF) {                              // frames 1 .. KF - 1 of the pass carry "no row", as in the general form
+                    unsigned u = 0u;
+                    if (lane != 0) ix = 0x7fffffff;
+                    if (ix != 0x7fffffff) {
+                        u = __float_as_uint(v);
+                        u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);   // order-preserving; > 0 for every real value
+                    }
+                    st_tag(xq + pw * 2 * KF + 2 * lane, u, ev3);
+                    st_tag(xq + pw * 2 * KF + 2 * lane + 1, (unsigned)ix, ev3);
+                    xav[pw * 2 * KF + 2 * lane] = u;
+                    xav[pw * 2 * KF + 2 * lane + 1] = (unsigned)ix;
+                }
+            }
+        } else {
             {
-                const float ov = redv[2 * tid + 1];
-                const int oi = redi[2 * tid + 1];
-                if (ov > v || (ov == v && oi < ix)) { v = ov; ix = oi; }
+                const int k = tid >> 7, r = tid & 127;         // KF * 128 = 512 threads
+                const bool vin = k < kf && r < p.rows_per && v0 + r < p.vocab;
+                float v = -INFINITY;
+                int ix = 0x7fffffff;
+                if (vin) {
+                    v = ((lpart[(k * 4) * 128 + r] + lpart[(k * 4 + 1) * 128 + r]) + (lpart[(k * 4 + 2) * 128 + r] + lpart[(k * 4 + 3) * 128 + r])) + bout_r;
+                    ix = v0 + r;
+                }
+                GM_STEP(1) GM_STEP(2) GM_STEP(4) GM_STEP(8) GM_STEP(16) GM_STEP(32)
+                if (lane == 0) { redv[wave] = v; redi[wave] = ix; }   // wave 2 k, 2 k + 1 = frame k
             }
-            unsigned u = 0u;
-            if (ix != 0x7fffffff) {
-                u = __float_as_uint(v);
-                u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);   // order-preserving; > 0 for every real value
+            __syncthreads();
+            GM_T(6)
+            if (tid < KF) {
+                float v = redv[2 * tid];
+                int ix = redi[2 * tid];
+                {
+                    const float ov = redv[2 * tid + 1];
+                    const int oi = redi[2 * tid + 1];
+                    if (ov > v || (ov == v && oi < ix)) { v = ov; ix = oi; }
+                }
+                unsigned u = 0u;
+                if (ix != 0x7fffffff) {
+                    u = __float_as_uint(v);
+                    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);   // order-preserving; > 0 for every real value
+                }
+                st_tag(xq + pw * 2 * KF + 2 * tid, u, ev3);
+                st_tag(xq + pw * 2 * KF + 2 * tid + 1, (unsigned)ix, ev3);
+                xav[pw * 2 * KF + 2 * tid] = u;
+                xav[pw * 2 * KF + 2 * tid + 1] = (unsigned)ix;
             }
-            st_tag(xq + pw * 2 * KF + 2 * tid, u, ev3);
-            st_tag(xq + pw * 2 * KF + 2 * tid + 1, (unsigned)ix, ev3);
-            xav[pw * 2 * KF + 2 * tid] = u;
-            xav[pw * 2 * KF + 2 * tid + 1] = (unsigned)ix;
-        } else if (tid >= 64 && tid < 64 + (GM_PARTS - 1) * 2 * KF) {
+        }
+#undef GM_STEP
+        GM_T(7)
+        if (tid >= 64 && tid < 64 + (GM_PARTS - 1) * 2 * KF) {
             const int idx = tid - 64;
             int q = idx / (2 * KF);
             const int w = idx - q * 2 * KF;
@@ -686,7 +756,7 @@ __global__ __launch_bounds__(512) void greedy_multi(DecMP p) {
             xav[q * 2 * KF + w] = val;
         }
         __syncthreads();
-        GM_T(5)
+        GM_T(8)
         if (*s_bad) { bad = true; break; }
         // ---- decisions, in frame order (identical in every thread of every part) ---------------------------------------------------
         bool commit = false;
@@ -708,27 +778,29 @@ __global__ __launch_bounds__(512) void greedy_multi(DecMP p) {
             commit = true;
             break;
         }
-        __syncthreads();                                     // xav / redv fully consumed before the next pass rewrites them
+        // No barrier closes the pass.  xav, redv / redi, lpart, zs and s_bad are next written behind at least one barrier of the next
+        // pass (the tanh barrier; redi[0] of the frame wait is read before the exchange barrier above), and a commit copies nothing: the
+        // candidate buffer becomes the committed one.  The buffer that turns candidate was last read by the W_hh product of an earlier
+        // pass and is next written by the cell phase, so the predictor step of the next pass may start in a wave as soon as it is here.
         if (commit) {
-            if (tid < RNNT_D) hs[tid] = h2[tid];
+            ++ev1;
             cc = cc2;
-            dirty = true;
-            __syncthreads();
         }
-        ++evals;
-        GM_T(6)
+        GM_T(9)
+        dirty = commit;                                      // the predictor step runs again only after a symbol
     }
     if (tdbg) {
-        for (int k = 0; k < 8; ++k) p.dbg[k] = tacc[k];
-        p.dbg[8] = evals; p.dbg[9] = nsymev;
+        tsh[24] = count; tsh[25] = b;
+        long long* out = p.dbg + (long long)((blockIdx.x >> 5) * 8 + (blockIdx.x & 7)) * GM_DBG_W;   // row bi
+        for (int k = 0; k < GM_DBG_W; ++k) out[k] = tsh[k];
     }
 #undef GM_T
     // ---- canonical state for the host / the next call (buffer 0 becomes the committed one) ---------------------------------
-    if (pw == 0 && tid0 < RNNT_D) stg1(p.h + (long long)b * RNNT_D + tid0, hs[tid0]);
+    if (pw == 0 && tid0 < RNNT_D) stg1(p.h + (long long)b * RNNT_D + tid0, hb[(ev1 & 1 ? 0 : RNNT_D) + tid0]);
     if (cell) stg1(p.c + (long long)b * RNNT_D + cell_unit, cc);
     if (pw == 0 && tid0 == 0) {
         p.sel[b] = 0; p.tok[b] = tok; p.fidx[b] = p.slots ? 0 : fidx; p.nsym[b] = nsym; p.count[b] = count;   // pool: frames consumed
-        atomicAdd(p.ctrl + 2, evals);
+        atomicAdd(p.ctrl + 2, (int)ev3);                   // passes = XA exchanges
     }
     (void)bad;
 }
