@@ -92,6 +92,27 @@ int rnnt_profile_end(rnnt_ctx* ctx, double* total_ms, int64_t* n_launches) {
     return RNNT_OK;
 }
 
+int rnnt_form_log_begin(rnnt_ctx* ctx) {
+    if (!ctx) return RNNT_ERR_ARG;
+    ctx->form_log.clear();
+    ctx->form_log_on = true;
+    return RNNT_OK;
+}
+
+int rnnt_form_log_end(rnnt_ctx* ctx, char* buf, int64_t cap, int64_t* needed) {
+    if (!ctx) return RNNT_ERR_ARG;
+    ctx->form_log_on = false;
+    std::string text;
+    for (const auto& kv : ctx->form_log) text += kv.first + "\t" + std::to_string(kv.second) + "\n";
+    if (needed) *needed = (int64_t)text.size() + 1;
+    if (buf && cap > 0) {
+        const size_t n = std::min(text.size(), (size_t)cap - 1);
+        memcpy(buf, text.data(), n);
+        buf[n] = 0;
+    }
+    return RNNT_OK;
+}
+
 int rnnt_get_counters(rnnt_ctx* ctx, int64_t* launches, int64_t* greedy_steps) {
     if (!ctx) return RNNT_ERR_ARG;
     if (launches) *launches = ctx->launches;

@@ -19,11 +19,19 @@ int fail(rnnt_ctx* ctx, int code, const char* fmt, ...) {
         if (e_ != hipSuccess) return fail(ctx, RNNT_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
-#define LAUNCHCHK(name)                                                                                \
+// the launch-error check alone: inside a launch macro whose call site then names the launch form with LAUNCHCHK
+#define LAUNCHERR(name)                                                                                \
     do {                                                                                               \
         hipError_t e_ = hipGetLastError();                                                             \
         if (e_ != hipSuccess) return fail(ctx, RNNT_ERR_HIP, "launch %s failed: %s", name, hipGetErrorString(e_)); \
+    } while (0)
+
+// after every launch: the error check, the launch count and -- while a form log is open -- the form name of the site
+#define LAUNCHCHK(name)                                                                                \
+    do {                                                                                               \
+        LAUNCHERR(name);                                                                               \
         ctx->launches++;                                                                               \
+        if (ctx->form_log_on) ctx->form_log[name]++;                                                   \
     } while (0)
 
 // launch-site tags (rnnt_profile_begin)
@@ -263,19 +271,18 @@ int launch_gemm(rnnt_ctx* ctx, hipStream_t s, const GemmP* gs, int ng, int tag =
         // spills: 186 VGPRs, no scratch; not LDS size), so round 3 removed the MT = 4 instantiations and the RNNT_BF_TILE
         // override altogether (gemm_bf_body static_asserts MT <= 2): the default path never dispatched them (conv2 of a whole
         // batch runs gemm_bw), and a kernel with an unexplained race does not stay in the product.
-        if (gs[0].a_tanh) launch_gemm_bf<2, 2, true>(nm, s, gb, maxM, maxN, ng);
-        else if (selM >= 1024 && maxN >= 256) launch_gemm_bf<2, 2>(nm, s, gb, maxM, maxN, ng);
-        else if (maxN >= 512 || selM >= 1024) launch_gemm_bf<1, 2>(nm, s, gb, maxM, maxN, ng);
-        else launch_gemm_bf<1, 1>(nm, s, gb, maxM, maxN, ng);
-        LAUNCHCHK("gemm_bf");
+        // (the name each branch logs is the launch form: kernel<MT,NT>, the tiles being 32 * MT rows by 32 * NT columns)
+        if (gs[0].a_tanh) { launch_gemm_bf<2, 2, true>(nm, s, gb, maxM, maxN, ng); LAUNCHCHK("gemm_bf<2,2,tanh>"); }
+        else if (selM >= 1024 && maxN >= 256) { launch_gemm_bf<2, 2>(nm, s, gb, maxM, maxN, ng); LAUNCHCHK("gemm_bf<2,2>"); }
+        else if (maxN >= 512 || selM >= 1024) { launch_gemm_bf<1, 2>(nm, s, gb, maxM, maxN, ng); LAUNCHCHK("gemm_bf<1,2>"); }
+        else { launch_gemm_bf<1, 1>(nm, s, gb, maxM, maxN, ng); LAUNCHCHK("gemm_bf<1,1>"); }
         return RNNT_OK;
     }
     if (selM >= 1024 && K % 32 == 0 && dense_epi) {
         // large M (full-context encoder, batched subsampling, joint lattice): LDS-tiled kernel, no split-K
-        if (gs[0].a_tanh) launch_gemm_ns<2, 2, true>(s, gb, maxM, maxN, ng);
-        else if (maxN >= 512) launch_gemm_ns<2, 2>(s, gb, maxM, maxN, ng);
-        else launch_gemm_ns<1, 2>(s, gb, maxM, maxN, ng);
-        LAUNCHCHK("gemm_ns");
+        if (gs[0].a_tanh) { launch_gemm_ns<2, 2, true>(s, gb, maxM, maxN, ng); LAUNCHCHK("gemm_ns<2,2,tanh>"); }
+        else if (maxN >= 512) { launch_gemm_ns<2, 2>(s, gb, maxM, maxN, ng); LAUNCHCHK("gemm_ns<2,2>"); }
+        else { launch_gemm_ns<1, 2>(s, gb, maxM, maxN, ng); LAUNCHCHK("gemm_ns<1,2>"); }
         return RNNT_OK;
     }
     const bool wide = maxN >= 512;
@@ -283,9 +290,11 @@ int launch_gemm(rnnt_ctx* ctx, hipStream_t s, const GemmP* gs, int ng, int tag =
     // roundup64(n_fft/2 + 1) is a multiple of 64 but, above 1024, often not of 128: 1088, 1600, 2112, ...)
     const int wkk = K >= 1024 && K % 128 == 0 ? 8 : 4;
     if (K % (wkk * 16) != 0) return fail(ctx, RNNT_ERR_SHAPE, "gemm16 K=%d not divisible by %d", K, wkk * 16);
-    if (wide) { if (wkk == 8) launch_gemm16<8, 2>(s, gb, maxM, maxN, ng); else launch_gemm16<4, 2>(s, gb, maxM, maxN, ng); }
-    else { if (wkk == 8) launch_gemm16<8, 1>(s, gb, maxM, maxN, ng); else launch_gemm16<4, 1>(s, gb, maxM, maxN, ng); }
-    LAUNCHCHK("gemm16");
+    // gemm16<WK,NT>: WK waves over K, 16 rows by 16 * NT columns
+    if (wide && wkk == 8) { launch_gemm16<8, 2>(s, gb, maxM, maxN, ng); LAUNCHCHK("gemm16<8,2>"); }
+    else if (wide) { launch_gemm16<4, 2>(s, gb, maxM, maxN, ng); LAUNCHCHK("gemm16<4,2>"); }
+    else if (wkk == 8) { launch_gemm16<8, 1>(s, gb, maxM, maxN, ng); LAUNCHCHK("gemm16<8,1>"); }
+    else { launch_gemm16<4, 1>(s, gb, maxM, maxN, ng); LAUNCHCHK("gemm16<4,1>"); }
     return RNNT_OK;
 }
 
@@ -378,10 +387,9 @@ static int attn_nq(int tq) { return tq <= 4 ? 1 : (tq <= 8 ? 2 : 4); }
     do {                                                                                               \
         const int nq_ = attn_nq(tq);                                                                   \
         const dim3 grid_(gx, ((tq) + 4 * nq_ - 1) / (4 * nq_), gz);                                    \
-        if (nq_ == 1) hipLaunchKernelGGL(KERNEL<1>, grid_, dim3(256), 0, s, __VA_ARGS__);              \
-        else if (nq_ == 2) hipLaunchKernelGGL(KERNEL<2>, grid_, dim3(256), 0, s, __VA_ARGS__);         \
-        else hipLaunchKernelGGL(KERNEL<4>, grid_, dim3(256), 0, s, __VA_ARGS__);                       \
-        LAUNCHCHK(#KERNEL);                                                                            \
+        if (nq_ == 1) { hipLaunchKernelGGL(KERNEL<1>, grid_, dim3(256), 0, s, __VA_ARGS__); LAUNCHCHK(#KERNEL "<1>"); }      \
+        else if (nq_ == 2) { hipLaunchKernelGGL(KERNEL<2>, grid_, dim3(256), 0, s, __VA_ARGS__); LAUNCHCHK(#KERNEL "<2>"); } \
+        else { hipLaunchKernelGGL(KERNEL<4>, grid_, dim3(256), 0, s, __VA_ARGS__); LAUNCHCHK(#KERNEL "<4>"); }               \
     } while (0)
 
 int launch_attn(rnnt_ctx* ctx, hipStream_t s, const AttnP& a, int B) {
@@ -453,13 +461,15 @@ int run_subsample(rnnt_ctx* ctx, hipStream_t s, const float* fbank, int B, int T
         if (!y1) return fail(ctx, RNNT_ERR_STATE, "run_subsample: no conv1 slab");
         ProfScope prof(ctx, s, tag1);
         static const int c1_rows = getenv("RNNT_CONV1_ROWS") ? atoi(getenv("RNNT_CONV1_ROWS")) : 1;
-        if (c1_rows && !ctx->gemm_m_cap && (long long)VB * ((t1 + C1_TB - 1) / C1_TB) >= 256)   // enough (stream, 8-row block) pairs to fill the chip: coalesced row stores
+        if (c1_rows && !ctx->gemm_m_cap && (long long)VB * ((t1 + C1_TB - 1) / C1_TB) >= 256) {   // enough (stream, 8-row block) pairs to fill the chip: coalesced row stores
             hipLaunchKernelGGL(conv1_relu_rows, dim3(VB, (t1 + C1_TB - 1) / C1_TB), dim3(256), 0, s, fbank, ctx->conv1_wt, ctx->conv1_b, y1, B, Tstride, t1,
                                starts_dev, nc, out_cn > 0 ? 1 : 0);
-        else
+            LAUNCHCHK("conv1_relu_rows");
+        } else {
             hipLaunchKernelGGL(conv1_relu, dim3(grid_for((long long)VB * t1 * RNNT_F1 * D)), dim3(256), 0, s, fbank, ctx->conv1_wt, ctx->conv1_b,
                                y1, B, Tstride, t1, starts_dev, nc, out_cn > 0 ? 1 : 0);
-        LAUNCHCHK("conv1_relu");
+            LAUNCHCHK("conv1_relu");
+        }
     }
     // conv2 as implicit GEMM: rows (v,t',f), K = (kh, kw, ci) = 3 segments of 768 contiguous floats of y1
     GemmP g = plain_gemm(y1, 0, ctx->conv2_w, 2304, ctx->conv2_b, y2, D, VB * tq * RNNT_FSUB, D, 2304, EPI_RELU);
@@ -478,7 +488,7 @@ int run_subsample(rnnt_ctx* ctx, hipStream_t s, const float* fbank, int B, int T
         case RNNT_NUM_F16X3: BW_LAUNCH_NUM(KERNEL, RNNT_NUM_F16X3, __VA_ARGS__) break;                 \
         default: BW_LAUNCH_NUM(KERNEL, RNNT_NUM_BF16X3, __VA_ARGS__) break;                            \
     }                                                                                                  \
-    LAUNCHCHK(#KERNEL)
+    LAUNCHERR(#KERNEL)   /* the call site counts the launch under its form name, KERNEL<waves> */
     if (fused) {
         // the same tiles with the conv1 operand formed from the fbank in the tile staging (gemm_bw_c1): g.A stays null
         ProfScope prof(ctx, s, tag2);
@@ -487,12 +497,14 @@ int run_subsample(rnnt_ctx* ctx, hipStream_t s, const float* fbank, int B, int T
         const dim3 grid((g.M + 127) / 128);
         const Conv1Src src{fbank, ctx->conv1_wt, ctx->conv1_b, starts_dev, B, Tstride, nc, out_cn > 0 ? 1 : 0};
         BW_LAUNCH(gemm_bw_c1, g, ctx->conv2_wp, src);
+        if (nw8) LAUNCHCHK("gemm_bw_c1<8>"); else LAUNCHCHK("gemm_bw_c1<4>");
     } else if (ctx->numerics != RNNT_NUM_F32 && conv2_bw && ctx->conv2_wp && g.M >= 32768 && !ctx->gemm_m_cap) {
         // whole-utterance slab: 128 x 256 tiles, weights streamed from L2 in fragment order, A rows four k-steps ahead (gemm_bw)
         ProfScope prof(ctx, s, tag2);
         if ((rc = prepare_gemm(ctx, g))) return rc;
         const dim3 grid((g.M + 127) / 128);
         BW_LAUNCH(gemm_bw, g, ctx->conv2_wp);
+        if (nw8) LAUNCHCHK("gemm_bw<8>"); else LAUNCHCHK("gemm_bw<4>");
 #undef BW_LAUNCH
 #undef BW_LAUNCH_NUM
     } else if (ctx->numerics != RNNT_NUM_F32) {
@@ -503,9 +515,8 @@ int run_subsample(rnnt_ctx* ctx, hipStream_t s, const float* fbank, int B, int T
         memset(&gb, 0, sizeof(gb));
         gb.g[0] = g;
         if ((rc = prepare_gemm(ctx, gb.g[0]))) return rc;
-        if (conv2_lds == 2 && nc > 1) launch_gemm_ns<2, 2, false, true>(s, gb, g.M, g.N, 1);   // experiment: non-temporal A
-        else launch_gemm_ns<2, 2>(s, gb, g.M, g.N, 1);
-        LAUNCHCHK("gemm_ns");
+        if (conv2_lds == 2 && nc > 1) { launch_gemm_ns<2, 2, false, true>(s, gb, g.M, g.N, 1); LAUNCHCHK("gemm_ns<2,2,nt>"); }   // experiment: non-temporal A
+        else { launch_gemm_ns<2, 2>(s, gb, g.M, g.N, 1); LAUNCHCHK("gemm_ns<2,2>"); }
     } else if ((rc = launch_gemm(ctx, s, &g, 1, tag2))) return rc;
     // Linear(4864 -> 256) * sqrt(256); y2 is [VB*t', f*256 + c] (weight columns permuted to match)
     GemmP go = plain_gemm(y2, RNNT_FSUB * D, ctx->emb_w, RNNT_FSUB * D, ctx->emb_b, xout, D, VB * tq, D, RNNT_FSUB * D, EPI_SCALE, 16.0f);
@@ -527,11 +538,11 @@ int launch_fused_t(rnnt_ctx* ctx, hipStream_t s, bool back, const FuseItem* tab,
     if (back) {
         if ((rc_attr = ensure_dyn_lds(ctx, reinterpret_cast<const void*>(&block_back<NUM, MT>), lds))) return rc_attr;
         hipLaunchKernelGGL((block_back<NUM, MT>), grid, dim3(FUSE_THREADS), lds, s, ctx->layers_dev, tab, ctx->wf_x, n_items, n_groups, S, B, ctx->cap);
-        LAUNCHCHK("block_back");
+        if (MT == 1) LAUNCHCHK("block_back<1>"); else if (MT == 2) LAUNCHCHK("block_back<2>"); else LAUNCHCHK("block_back<3>");
     } else {
         if ((rc_attr = ensure_dyn_lds(ctx, reinterpret_cast<const void*>(&block_front<NUM, MT>), lds))) return rc_attr;
         hipLaunchKernelGGL((block_front<NUM, MT>), grid, dim3(FUSE_THREADS), lds, s, ctx->layers_dev, tab, ctx->wf_x, n_items, n_groups, S, B, (long long)ctx->tcap);
-        LAUNCHCHK("block_front");
+        if (MT == 1) LAUNCHCHK("block_front<1>"); else if (MT == 2) LAUNCHCHK("block_front<2>"); else LAUNCHCHK("block_front<3>");
     }
     return RNNT_OK;
 }
@@ -589,9 +600,8 @@ int launch_gemm_tab(rnnt_ctx* ctx, hipStream_t s, const GemmP* tab_dev, int n, i
         case RNNT_NUM_F16X3: hipLaunchKernelGGL((gemm_bf_tab<2, true, MT_, NT_>), grid_for_tab(ntn, ntm, X), dim3(256), 0, s, tab_dev, n, ntn, ntm, X); break; \
         default: hipLaunchKernelGGL((gemm_bf_tab<2, false, MT_, NT_>), grid_for_tab(ntn, ntm, X), dim3(256), 0, s, tab_dev, n, ntn, ntm, X); break; \
     }
-        if (N >= 512) BF_TAB(1, 2) else BF_TAB(1, 1)
+        if (N >= 512) { BF_TAB(1, 2) LAUNCHCHK("gemm_bf_tab<1,2>"); } else { BF_TAB(1, 1) LAUNCHCHK("gemm_bf_tab<1,1>"); }
 #undef BF_TAB
-        LAUNCHCHK("gemm_bf_tab");
         return RNNT_OK;
     }
     if (ns_mode && n >= ns_min && K % 32 == 0) {   // enough groups: no split-K, epilogue from registers
@@ -602,22 +612,23 @@ int launch_gemm_tab(rnnt_ctx* ctx, hipStream_t s, const GemmP* tab_dev, int n, i
         case 1: hipLaunchKernelGGL((gemm_ns_tab<MT_, NT_, BK_, 1>), grid_for_tab(ntn, ntm, X), dim3(256), 0, s, tab_dev, n, ntn, ntm, X); break; \
         default: hipLaunchKernelGGL((gemm_ns_tab<MT_, NT_, BK_, 2>), grid_for_tab(ntn, ntm, X), dim3(256), 0, s, tab_dev, n, ntn, ntm, X); break; \
     }
-        if (N >= 512) NS_TAB(1, 2, 32)            // ffn1 / pointwise_conv1: 32x64 tiles
-        else if (K >= 1024) NS_TAB(1, 1, 64)      // ffn2: 32x32 tiles, BK = 64
-        else NS_TAB(1, 1, 32)                     // q/k/v, linear_out, pointwise_conv2: 32x32 tiles
+        if (N >= 512) { NS_TAB(1, 2, 32) LAUNCHCHK("gemm_ns_tab<1,2,32>"); }            // ffn1 / pointwise_conv1: 32x64 tiles
+        else if (K >= 1024) { NS_TAB(1, 1, 64) LAUNCHCHK("gemm_ns_tab<1,1,64>"); }      // ffn2: 32x32 tiles, BK = 64
+        else { NS_TAB(1, 1, 32) LAUNCHCHK("gemm_ns_tab<1,1,32>"); }                     // q/k/v, linear_out, pointwise_conv2: 32x32 tiles
 #undef NS_TAB
-        LAUNCHCHK("gemm_ns_tab");
         return RNNT_OK;
     }
     const int wk = K >= 1024 ? 8 : 4;
     if (K % (wk * 16) != 0) return fail(ctx, RNNT_ERR_SHAPE, "gemm16 K=%d not divisible by %d", K, wk * 16);
     const long long out = (long long)n * maxM * N;
-    if (out >= 256ll * 64 * 64 * 2 && wk == 4) launch_gemm16_tab<4, 4, 4>(s, tab_dev, n, maxM, N);
-    else if (out >= 256ll * 32 * 64 && wk == 4) launch_gemm16_tab<4, 2, 4>(s, tab_dev, n, maxM, N);
-    else if (out >= 256ll * 32 * 64 && wk == 8) launch_gemm16_tab<8, 2, 4>(s, tab_dev, n, maxM, N);
-    else if (N >= 512) { if (wk == 8) launch_gemm16_tab<8, 1, 2>(s, tab_dev, n, maxM, N); else launch_gemm16_tab<4, 1, 2>(s, tab_dev, n, maxM, N); }
-    else { if (wk == 8) launch_gemm16_tab<8, 1, 1>(s, tab_dev, n, maxM, N); else launch_gemm16_tab<4, 1, 1>(s, tab_dev, n, maxM, N); }
-    LAUNCHCHK("gemm16_tab");
+    // gemm16_tab<WK,MT,NT>: WK waves over K, 16 * MT rows by 16 * NT columns
+    if (out >= 256ll * 64 * 64 * 2 && wk == 4) { launch_gemm16_tab<4, 4, 4>(s, tab_dev, n, maxM, N); LAUNCHCHK("gemm16_tab<4,4,4>"); }
+    else if (out >= 256ll * 32 * 64 && wk == 4) { launch_gemm16_tab<4, 2, 4>(s, tab_dev, n, maxM, N); LAUNCHCHK("gemm16_tab<4,2,4>"); }
+    else if (out >= 256ll * 32 * 64 && wk == 8) { launch_gemm16_tab<8, 2, 4>(s, tab_dev, n, maxM, N); LAUNCHCHK("gemm16_tab<8,2,4>"); }
+    else if (N >= 512 && wk == 8) { launch_gemm16_tab<8, 1, 2>(s, tab_dev, n, maxM, N); LAUNCHCHK("gemm16_tab<8,1,2>"); }
+    else if (N >= 512) { launch_gemm16_tab<4, 1, 2>(s, tab_dev, n, maxM, N); LAUNCHCHK("gemm16_tab<4,1,2>"); }
+    else if (wk == 8) { launch_gemm16_tab<8, 1, 1>(s, tab_dev, n, maxM, N); LAUNCHCHK("gemm16_tab<8,1,1>"); }
+    else { launch_gemm16_tab<4, 1, 1>(s, tab_dev, n, maxM, N); LAUNCHCHK("gemm16_tab<4,1,1>"); }
     return RNNT_OK;
 }
 

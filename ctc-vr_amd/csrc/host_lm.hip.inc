@@ -89,7 +89,7 @@ int launch_ffn_as_t(rnnt_ctx* ctx, hipStream_t s, const FfnP& p) {
     const size_t lds = FFN_LDS(NUM, NW) + ((p.H0 || p.dw.g || p.w1p2) ? FFN_XROWS : 0);  // both operand images; result rows and the tail's image overlay them; the head's x' rows behind
     { const int rc_attr = ensure_dyn_lds(ctx, reinterpret_cast<const void*>(&ffn_as<NUM, AS_MT, NW>), lds); if (rc_attr) return rc_attr; }
     hipLaunchKernelGGL((ffn_as<NUM, AS_MT, NW>), dim3((p.M + 16 * AS_MT - 1) / (16 * AS_MT)), dim3(64 * NW), lds, s, p);
-    LAUNCHCHK("ffn_as");
+    if (NW == 16) LAUNCHCHK("ffn_as<16>"); else if (NW == 4) LAUNCHCHK("ffn_as<4>"); else LAUNCHCHK("ffn_as<8>");
     return RNNT_OK;
 }
 int launch_ffn_as(rnnt_ctx* ctx, hipStream_t s, const FfnP& p) {
@@ -429,11 +429,16 @@ int encoder_chunks_lm(rnnt_ctx* ctx, hipStream_t s, const float* fbank_dev, int 
                 if (ctx->numerics == RNNT_NUM_BF16X3) hipLaunchKernelGGL((rel_attention_lm_res<2, false>), dim3(B * RNNT_H), dim3(64 * LMR_NW), LMR_LDS, s, r);
                 else if (ctx->numerics == RNNT_NUM_F16X3) hipLaunchKernelGGL((rel_attention_lm_res<2, true>), dim3(B * RNNT_H), dim3(64 * LMR_NW), LMR_LDS, s, r);
                 else hipLaunchKernelGGL((rel_attention_lm_res<1, false>), dim3(B * RNNT_H), dim3(64 * LMR_NW), LMR_LDS, s, r);
-            } else if (ctx->numerics == RNNT_NUM_F32 || !ctx->attn_bf) hipLaunchKernelGGL(rel_attention_lm_mfma, ag, dim3(256), LM2_LDS, s, a);
-            else if (ctx->numerics == RNNT_NUM_BF16X3) hipLaunchKernelGGL((rel_attention_lm_bf<2, false>), ag, dim3(256), LMB_LDS, s, a);
-            else if (ctx->numerics == RNNT_NUM_F16X3) hipLaunchKernelGGL((rel_attention_lm_bf<2, true>), ag, dim3(256), LMB_LDS, s, a);
-            else hipLaunchKernelGGL((rel_attention_lm_bf<1, false>), ag, dim3(256), LMB_LDS, s, a);
-            LAUNCHCHK("rel_attention_lm");
+                LAUNCHCHK("rel_attention_lm_res");
+            } else if (ctx->numerics == RNNT_NUM_F32 || !ctx->attn_bf) {
+                hipLaunchKernelGGL(rel_attention_lm_mfma, ag, dim3(256), LM2_LDS, s, a);
+                LAUNCHCHK("rel_attention_lm_mfma");
+            } else {
+                if (ctx->numerics == RNNT_NUM_BF16X3) hipLaunchKernelGGL((rel_attention_lm_bf<2, false>), ag, dim3(256), LMB_LDS, s, a);
+                else if (ctx->numerics == RNNT_NUM_F16X3) hipLaunchKernelGGL((rel_attention_lm_bf<2, true>), ag, dim3(256), LMB_LDS, s, a);
+                else hipLaunchKernelGGL((rel_attention_lm_bf<1, false>), ag, dim3(256), LMB_LDS, s, a);
+                LAUNCHCHK("rel_attention_lm_bf");
+            }
         }
         dbg("attn", l, ctx->lm_a, M * D);
         // x += conv_module(LN(x)) (convolution.py:98-153): pointwise_conv1 + GLU into the linear buffer behind the left context

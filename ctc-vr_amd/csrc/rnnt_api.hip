@@ -367,6 +367,9 @@ struct rnnt_ctx {
     int prof_tag = -1;
     std::vector<hipEvent_t> prof_ev;
     size_t prof_used = 0;
+    // optional launch-form log (rnnt_form_log_begin / _end): the name LAUNCHCHK is given at every launch site, counted on the host
+    bool form_log_on = false;
+    std::map<std::string, int64_t> form_log;
 
     // The only free list: streams, events and graphs here, every buffer and call table through its owner's destructor.  No user-provided
     // constructor -- rnnt_create's `new rnnt_ctx()` value-initialises lw[] and the raw weight views to null.

@@ -141,6 +141,8 @@ SIGNATURES = {
     "rnnt_enc_frames_dev": (c_vp, [c_vp, c_i32p, c_i32p]),
     "rnnt_profile_begin": (c_i32, [c_vp, c_i32]),
     "rnnt_profile_end": (c_i32, [c_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_i64)]),
+    "rnnt_form_log_begin": (c_i32, [c_vp]),
+    "rnnt_form_log_end": (c_i32, [c_vp, ctypes.c_char_p, c_i64, ctypes.POINTER(c_i64)]),
     "rnnt_get_counters": (c_i32, [c_vp, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
 }
 
@@ -1365,6 +1367,18 @@ class RnntEngine:
         ms, n = ctypes.c_double(0), c_i64(0)
         self._chk(self.lib.rnnt_profile_end(self.ctx, ctypes.byref(ms), ctypes.byref(n)), "rnnt_profile_end")
         return ms.value, n.value
+
+    def form_log_begin(self):
+        """Start counting every launch of this context under the form name of its launch site (rnnt_form_log_begin)."""
+        self._chk(self.lib.rnnt_form_log_begin(self.ctx), "rnnt_form_log_begin")
+
+    def form_log_end(self):
+        """Stop the log -> {form name: launches}, e.g. {"gemm_bf<2,2>": 1, "ffn_as<8>": 36, ...}."""
+        need = c_i64(0)
+        self._chk(self.lib.rnnt_form_log_end(self.ctx, None, 0, ctypes.byref(need)), "rnnt_form_log_end")
+        buf = ctypes.create_string_buffer(need.value)
+        self._chk(self.lib.rnnt_form_log_end(self.ctx, buf, need.value, ctypes.byref(need)), "rnnt_form_log_end")
+        return {name: int(n) for name, n in (line.split("\t") for line in buf.value.decode().splitlines())}
 
     def counters(self):
         a, b = c_i64(0), c_i64(0)

@@ -1019,6 +1019,16 @@ const float* rnnt_enc_frames_dev(rnnt_ctx* ctx, int32_t* frames_out, int32_t* st
 int rnnt_profile_begin(rnnt_ctx* ctx, int32_t tag);
 int rnnt_profile_end(rnnt_ctx* ctx, double* total_ms, int64_t* n_launches);
 
+/* launch-form log (tests): between begin and end every kernel launch of the context is counted on the host under the form name
+ * of its launch site -- the kernel with every choice the host made for it, e.g. "gemm_bf<2,2>", "gemm16<8,1>", "ffn_as<8>",
+ * "conv1_relu_rows", "rel_attention<4>".  Off (the default) it costs one branch per launch; on or off there is no device work and
+ * no synchronisation.  Launches replayed from a captured graph are not seen (the encoder calls launch eagerly).  end stops the log
+ * and writes "name\tcount\n" per distinct name, sorted by name and NUL-terminated, into buf[cap] (cut at cap - 1 characters);
+ * *needed is the size of the whole text with its NUL, and the counts are kept until the next begin, so a short buffer can be
+ * followed by a second end. */
+int rnnt_form_log_begin(rnnt_ctx* ctx);
+int rnnt_form_log_end(rnnt_ctx* ctx, char* buf, int64_t cap, int64_t* needed);
+
 /* counters for bench/roofline: number of kernel launches and greedy steps since the last reset. */
 int rnnt_get_counters(rnnt_ctx* ctx, int64_t* launches, int64_t* greedy_steps);
 
