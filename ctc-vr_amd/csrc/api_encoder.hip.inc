@@ -294,8 +294,7 @@ int wf_build_tables(rnnt_ctx* ctx, hipStream_t s, int total_frames, const std::v
     // unless RNNT_FUSED=2: its fused form is MFMA-bound at 3 row tiles and not tuned)
     bool fused = ctx->use_fused == 2 || (ctx->use_fused == 1 && ctx->numerics != RNNT_NUM_F32);
     for (int c = 0; c < C; ++c) fused = fused && ci[c].tq <= FUSE_MAXF;
-    static const int fuse_merge = getenv("RNNT_FUSE_MERGE") ? atoi(getenv("RNNT_FUSE_MERGE")) : FUSE_MAXC;
-    static const int fuse_frames = getenv("RNNT_FUSE_FRAMES") ? atoi(getenv("RNNT_FUSE_FRAMES")) : 12;
+    const int fuse_merge = ctx->fuse_merge, fuse_frames = ctx->fuse_frames;
     const int KM = fused ? (fuse_merge < 1 ? 1 : (fuse_merge > FUSE_MAXC ? FUSE_MAXC : fuse_merge)) : ctx->wf_merge;
     std::vector<int> key = {ctx->n_streams, C, KM, total_frames, ctx->pos.cache_len, ctx->pos.kv_start, ctx->pos.conv_pos,
                             ctx->frames_buffered, fused ? 1 + fuse_frames : 0};
@@ -343,7 +342,7 @@ int wf_build_tables(rnnt_ctx* ctx, hipStream_t s, int total_frames, const std::v
 // consecutive pairs: the tail-merged last chunk (5 frames) does not switch its whole stage to the tiled kernel
 int wf_attention(rnnt_ctx* ctx, hipStream_t s, int st, const std::vector<ChunkInfo>& ci, const AttnP* tab, int pn) {
     ProfScope prof(ctx, s, TAG_ATTN);
-    static const int attn_pair_major = getenv("RNNT_ATTN_PAIR_MAJOR") ? atoi(getenv("RNNT_ATTN_PAIR_MAJOR")) : 1;
+    const int attn_pair_major = ctx->attn_pair_major;
     const std::vector<int>& sc_first = ctx->wf_sc_first;
     const int NSC = (int)sc_first.size() - 1, B = ctx->n_streams;
     std::vector<const ChunkInfo*> pq;                       // the stage's pairs in table order: layer-major
@@ -425,7 +424,7 @@ int wf_decode_stage(rnnt_ctx* ctx, hipStream_t s, hipStream_t s2, bool resident,
     }
     HIPCHK(hipEventRecord(e, s));
     HIPCHK(hipStreamWaitEvent(s2, e, 0));
-    static const int slack = getenv("RNNT_DEC_SLACK") ? atoi(getenv("RNNT_DEC_SLACK")) : 8;
+    const int slack = ctx->dec_slack;
     const int budget = (n_new + slack + 3) / 4 * 4;   // the stage's frames + a little slack; few distinct graph sizes
     dec_steps += budget;
     return greedy_steps(ctx, s2, budget, ready);

@@ -36,6 +36,20 @@ int rnnt_create(const rnnt_config* cfg, rnnt_ctx** out) {
     if (const char* e_ = getenv("RNNT_ATTN_RESIDENT")) ctx->attn_resident = atoi(e_);
     if (const char* e_ = getenv("RNNT_CONV1_FUSE")) ctx->conv1_fuse = atoi(e_);
     if (const char* se = getenv("RNNT_WF_SUB_ASYNC")) ctx->wf_sub_async = (se[0] == '0') ? 0 : 1;
+    if (const char* e_ = getenv("RNNT_FFN_NW")) ctx->ffn_nw = atoi(e_);
+    if (const char* e_ = getenv("RNNT_GEMM_PD")) ctx->gemm_pd = atoi(e_);
+    if (const char* e_ = getenv("RNNT_CONV2_BW")) ctx->conv2_bw = atoi(e_);
+    if (const char* e_ = getenv("RNNT_CONV1_ROWS")) ctx->conv1_rows = atoi(e_);
+    if (const char* e_ = getenv("RNNT_CONV2_LDS")) ctx->conv2_lds = atoi(e_);
+    if (const char* e_ = getenv("RNNT_BW_NW")) ctx->bw_nw = atoi(e_);
+    if (const char* e_ = getenv("RNNT_GEMM_NS")) ctx->gemm_ns = atoi(e_);
+    if (const char* e_ = getenv("RNNT_NS_MIN_GROUPS")) ctx->ns_min_groups = atoi(e_);
+    if (const char* e_ = getenv("RNNT_XCD_X")) ctx->xcd_x = atoi(e_);
+    if (const char* e_ = getenv("RNNT_FUSE_MERGE")) ctx->fuse_merge = atoi(e_);
+    if (const char* e_ = getenv("RNNT_FUSE_FRAMES")) ctx->fuse_frames = atoi(e_);
+    if (const char* e_ = getenv("RNNT_ATTN_PAIR_MAJOR")) ctx->attn_pair_major = atoi(e_);
+    if (const char* e_ = getenv("RNNT_DEC_SLACK")) ctx->dec_slack = atoi(e_);
+    if (const char* e_ = getenv("RNNT_DRAIN_STEPS")) ctx->drain_steps = atoi(e_);
     const int B = cfg->max_streams;
     ctx->slot = std::vector<PoolSlot>((size_t)B);   // max_streams is fixed here, so the pool's per-slot host state is too
     ctx->hs_buf = std::vector<DevBuf<float>>((size_t)B);

@@ -73,8 +73,8 @@ int rnnt_joint(rnnt_ctx* ctx, const float* enc_dev, const float* pred_dev, int32
         g.a_n1 = T * U; g.a_n2 = U; g.a_s0 = (long long)U * D; g.a_s1 = 0; g.a_s2 = D;   // A row = pp[b, u]
         g.a_tanh = 1; g.X = e; g.x_n = U; g.x_s0 = D;                                    // X row = e[(b,t)] = e[m / U]
         if ((rc = prepare_gemm(ctx, g))) return rc;
-        launch_gemm_ns<2, 2, true>(s, gb, g.M, V, 1);
-        LAUNCHCHK("gemm_ns(joint lattice)");
+        launch_gemm_ns<2, 2, true>(ctx, s, gb, g.M, V, 1);
+        if (prefetch_depth(ctx) == 1) LAUNCHCHK("gemm_ns(joint lattice;pd1)"); else LAUNCHCHK("gemm_ns(joint lattice)");
     }
     if (mode == 1) {
         const long long rows = (long long)B * T * U;

@@ -91,7 +91,7 @@ int greedy_drain(rnnt_ctx* ctx, hipStream_t s, int n_frames, int done_steps) {
         HIPCHK(hipStreamSynchronize(s));
         if (ctx->pinned[0] <= 0) break;
         if (done_steps > max_steps) return fail(ctx, RNNT_ERR_STATE, "greedy decode did not terminate");
-        static const int dstep = getenv("RNNT_DRAIN_STEPS") ? atoi(getenv("RNNT_DRAIN_STEPS")) : 4;
+        const int dstep = ctx->drain_steps;
         if ((rc = greedy_steps(ctx, s, dstep, n_frames))) return rc;
         done_steps += dstep;
     }

@@ -207,15 +207,14 @@ void launch_gemm16(hipStream_t s, const GemmBatch& gb, int maxM, int maxN, int n
 }
 
 // gemm_ns with the XCD-aware 1-D grid (see the kernel): ceil(ntm / 8) * 8 * ntn workgroups per descriptor
-static int prefetch_depth() {   // K blocks in flight per workgroup (register ring of gemm_ns_body): 1 or 2
-    static const int pd = getenv("RNNT_GEMM_PD") ? atoi(getenv("RNNT_GEMM_PD")) : 2;
-    return pd;
+static int prefetch_depth(const rnnt_ctx* ctx) {   // K blocks in flight per workgroup (register ring of gemm_ns_body): 1 or 2
+    return ctx->gemm_pd == 1 ? 1 : 2;
 }
 template <int MT, int NT, bool ATANH = false, bool ANT = false>
-void launch_gemm_ns(hipStream_t s, const GemmBatch& gb, int maxM, int maxN, int ng) {
+void launch_gemm_ns(const rnnt_ctx* ctx, hipStream_t s, const GemmBatch& gb, int maxM, int maxN, int ng) {
     const int ntn = (maxN + 32 * NT - 1) / (32 * NT), ntm = (maxM + 32 * MT - 1) / (32 * MT);
     dim3 grid(((ntm + 7) / 8) * 8 * ntn, 1, ng);
-    switch (prefetch_depth()) {
+    switch (prefetch_depth(ctx)) {
         case 1: hipLaunchKernelGGL((gemm_ns<MT, NT, 32, 1, ATANH, ANT>), grid, dim3(256), 0, s, gb, ntn, ntm); break;
         default: hipLaunchKernelGGL((gemm_ns<MT, NT, 32, 2, ATANH, ANT>), grid, dim3(256), 0, s, gb, ntn, ntm); break;
     }
@@ -280,9 +279,11 @@ int launch_gemm(rnnt_ctx* ctx, hipStream_t s, const GemmP* gs, int ng, int tag =
     }
     if (selM >= 1024 && K % 32 == 0 && dense_epi) {
         // large M (full-context encoder, batched subsampling, joint lattice): LDS-tiled kernel, no split-K
-        if (gs[0].a_tanh) { launch_gemm_ns<2, 2, true>(s, gb, maxM, maxN, ng); LAUNCHCHK("gemm_ns<2,2,tanh>"); }
-        else if (maxN >= 512) { launch_gemm_ns<2, 2>(s, gb, maxM, maxN, ng); LAUNCHCHK("gemm_ns<2,2>"); }
-        else { launch_gemm_ns<1, 2>(s, gb, maxM, maxN, ng); LAUNCHCHK("gemm_ns<1,2>"); }
+        // (with one K block in flight, RNNT_GEMM_PD=1, the forms log names of their own)
+        const bool pd1 = prefetch_depth(ctx) == 1;
+        if (gs[0].a_tanh) { launch_gemm_ns<2, 2, true>(ctx, s, gb, maxM, maxN, ng); if (pd1) LAUNCHCHK("gemm_ns<2,2,tanh;pd1>"); else LAUNCHCHK("gemm_ns<2,2,tanh>"); }
+        else if (maxN >= 512) { launch_gemm_ns<2, 2>(ctx, s, gb, maxM, maxN, ng); if (pd1) LAUNCHCHK("gemm_ns<2,2;pd1>"); else LAUNCHCHK("gemm_ns<2,2>"); }
+        else { launch_gemm_ns<1, 2>(ctx, s, gb, maxM, maxN, ng); if (pd1) LAUNCHCHK("gemm_ns<1,2;pd1>"); else LAUNCHCHK("gemm_ns<1,2>"); }
         return RNNT_OK;
     }
     const bool wide = maxN >= 512;
@@ -434,14 +435,11 @@ int run_layer(rnnt_ctx* ctx, hipStream_t s, int l, int B, int tq, int T2, int kv
     return launch_ln(ctx, s, d.lnf);
 }
 
-static bool conv2_bw_on() {
-    static const int conv2_bw = getenv("RNNT_CONV2_BW") ? atoi(getenv("RNNT_CONV2_BW")) : 1;
-    return conv2_bw != 0;
-}
+static bool conv2_bw_on(const rnnt_ctx* ctx) { return ctx->conv2_bw != 0; }
 // conv2 of M rows forms its conv1 operand itself (gemm_bw_c1): no conv1 launch, no y1 slab.  The same condition as gemm_bw's, plus
 // the per-context knob; the caller must also allow it (fuse_ok: the layer-major schedule's main classes).
 static bool conv2_fused(const rnnt_ctx* ctx, long long M) {
-    return ctx->conv1_fuse && ctx->numerics != RNNT_NUM_F32 && conv2_bw_on() && ctx->conv2_wp && M >= 32768 && M < (1ll << 31);
+    return ctx->conv1_fuse && ctx->numerics != RNNT_NUM_F32 && conv2_bw_on(ctx) && ctx->conv2_wp && M >= 32768 && M < (1ll << 31);
 }
 // Conv2dSubsampling4 (+ x16) (subsampling.py:203-228) of `nc` equal-length chunks of every stream at once:
 // virtual stream v = c*B + b; output rows (v, r) -> xout[(v*tq + r)][256].  starts_dev == null: one chunk at 0.
@@ -460,8 +458,7 @@ int run_subsample(rnnt_ctx* ctx, hipStream_t s, const float* fbank, int B, int T
     if (!fused) {
         if (!y1) return fail(ctx, RNNT_ERR_STATE, "run_subsample: no conv1 slab");
         ProfScope prof(ctx, s, tag1);
-        static const int c1_rows = getenv("RNNT_CONV1_ROWS") ? atoi(getenv("RNNT_CONV1_ROWS")) : 1;
-        if (c1_rows && !ctx->gemm_m_cap && (long long)VB * ((t1 + C1_TB - 1) / C1_TB) >= 256) {   // enough (stream, 8-row block) pairs to fill the chip: coalesced row stores
+        if (ctx->conv1_rows && !ctx->gemm_m_cap && (long long)VB * ((t1 + C1_TB - 1) / C1_TB) >= 256) {   // enough (stream, 8-row block) pairs to fill the chip: coalesced row stores
             hipLaunchKernelGGL(conv1_relu_rows, dim3(VB, (t1 + C1_TB - 1) / C1_TB), dim3(256), 0, s, fbank, ctx->conv1_wt, ctx->conv1_b, y1, B, Tstride, t1,
                                starts_dev, nc, out_cn > 0 ? 1 : 0);
             LAUNCHCHK("conv1_relu_rows");
@@ -476,10 +473,10 @@ int run_subsample(rnnt_ctx* ctx, hipStream_t s, const float* fbank, int B, int T
     g.a_n1 = tq * RNNT_FSUB; g.a_n2 = RNNT_FSUB;
     g.a_s0 = (long long)t1 * RNNT_F1 * D; g.a_s1 = 2LL * RNNT_F1 * D; g.a_s2 = 2LL * D;
     g.a_seg = 768; g.a_seg_stride = (long long)RNNT_F1 * D;
-    static const int conv2_lds = getenv("RNNT_CONV2_LDS") ? atoi(getenv("RNNT_CONV2_LDS")) : 1;
-    const bool conv2_bw = conv2_bw_on();
-    // gemm_bw / gemm_bw_c1 of the numerics mode on `grid`, 8 waves (two per SIMD) or 4 (RNNT_BW_NW=4, same results)
-    static const bool nw8 = getenv("RNNT_BW_NW") ? atoi(getenv("RNNT_BW_NW")) == 8 : true;
+    const int conv2_lds = ctx->conv2_lds;
+    const bool conv2_bw = conv2_bw_on(ctx);
+    // gemm_bw / gemm_bw_c1 of the numerics mode on `grid`, 8 waves (two per SIMD) or 4 (RNNT_BW_NW=4, same bits: test_kernel_forms.py)
+    const bool nw8 = ctx->bw_nw == 8;
 #define BW_LAUNCH_NUM(KERNEL, NUM_, ...) { if (nw8) hipLaunchKernelGGL((KERNEL<NUM_, 8>), grid, dim3(512), 0, s, __VA_ARGS__); \
                                            else hipLaunchKernelGGL((KERNEL<NUM_, 4>), grid, dim3(256), 0, s, __VA_ARGS__); }
 #define BW_LAUNCH(KERNEL, ...)                                                                         \
@@ -515,8 +512,9 @@ int run_subsample(rnnt_ctx* ctx, hipStream_t s, const float* fbank, int B, int T
         memset(&gb, 0, sizeof(gb));
         gb.g[0] = g;
         if ((rc = prepare_gemm(ctx, gb.g[0]))) return rc;
-        if (conv2_lds == 2 && nc > 1) { launch_gemm_ns<2, 2, false, true>(s, gb, g.M, g.N, 1); LAUNCHCHK("gemm_ns<2,2,nt>"); }   // experiment: non-temporal A
-        else { launch_gemm_ns<2, 2>(s, gb, g.M, g.N, 1); LAUNCHCHK("gemm_ns<2,2>"); }
+        const bool pd1 = prefetch_depth(ctx) == 1;
+        if (conv2_lds == 2 && nc > 1) { launch_gemm_ns<2, 2, false, true>(ctx, s, gb, g.M, g.N, 1); if (pd1) LAUNCHCHK("gemm_ns<2,2,nt;pd1>"); else LAUNCHCHK("gemm_ns<2,2,nt>"); }   // experiment: non-temporal A
+        else { launch_gemm_ns<2, 2>(ctx, s, gb, g.M, g.N, 1); if (pd1) LAUNCHCHK("gemm_ns<2,2;pd1>"); else LAUNCHCHK("gemm_ns<2,2>"); }
     } else if ((rc = launch_gemm(ctx, s, &g, 1, tag2))) return rc;
     // Linear(4864 -> 256) * sqrt(256); y2 is [VB*t', f*256 + c] (weight columns permuted to match)
     GemmP go = plain_gemm(y2, RNNT_FSUB * D, ctx->emb_w, RNNT_FSUB * D, ctx->emb_b, xout, D, VB * tq, D, RNNT_FSUB * D, EPI_SCALE, 16.0f);
@@ -578,10 +576,9 @@ void launch_gemm16_tab(hipStream_t s, const GemmP* tab, int n, int maxM, int max
 // workgroups to spend registers on operand reuse (64x64 / 32x64 tiles); few groups keep the 16-row tiles.
 int launch_gemm_tab(rnnt_ctx* ctx, hipStream_t s, const GemmP* tab_dev, int n, int maxM, int N, int K, int tag) {
     ProfScope prof(ctx, s, tag);
-    static const int ns_mode = getenv("RNNT_GEMM_NS") ? atoi(getenv("RNNT_GEMM_NS")) : 1;
-    static const int ns_min = getenv("RNNT_NS_MIN_GROUPS") ? atoi(getenv("RNNT_NS_MIN_GROUPS")) : 2;   // pipeline fill/drain stages have few pairs
+    const int ns_mode = ctx->gemm_ns, ns_min = ctx->ns_min_groups;   // pipeline fill/drain stages have few pairs
     // XCDs per descriptor of the 1-D grids (see gemm_ns_tab): the largest split that keeps the groups balanced
-    static const int x_env = getenv("RNNT_XCD_X") ? atoi(getenv("RNNT_XCD_X")) : 0;
+    const int x_env = ctx->xcd_x;
     auto pick_x = [&](int ntn) {
         if (x_env == 1 || x_env == 2 || x_env == 4 || x_env == 8) return x_env;
         for (int X = 2; X < 8; X *= 2)
@@ -608,13 +605,14 @@ int launch_gemm_tab(rnnt_ctx* ctx, hipStream_t s, const GemmP* tab_dev, int n, i
         // tile choice from tools/microbench2.hip (12 groups x 192 rows): the kernel is occupancy/latency-bound, so the
         // narrow shapes want many small workgroups; only K = 1024 profits from 64-deep K blocks (half the barriers)
 #define NS_TAB(MT_, NT_, BK_)                                                                                              \
-    switch (prefetch_depth()) {                                                                                            \
+    switch (prefetch_depth(ctx)) {                                                                                         \
         case 1: hipLaunchKernelGGL((gemm_ns_tab<MT_, NT_, BK_, 1>), grid_for_tab(ntn, ntm, X), dim3(256), 0, s, tab_dev, n, ntn, ntm, X); break; \
         default: hipLaunchKernelGGL((gemm_ns_tab<MT_, NT_, BK_, 2>), grid_for_tab(ntn, ntm, X), dim3(256), 0, s, tab_dev, n, ntn, ntm, X); break; \
     }
-        if (N >= 512) { NS_TAB(1, 2, 32) LAUNCHCHK("gemm_ns_tab<1,2,32>"); }            // ffn1 / pointwise_conv1: 32x64 tiles
-        else if (K >= 1024) { NS_TAB(1, 1, 64) LAUNCHCHK("gemm_ns_tab<1,1,64>"); }      // ffn2: 32x32 tiles, BK = 64
-        else { NS_TAB(1, 1, 32) LAUNCHCHK("gemm_ns_tab<1,1,32>"); }                     // q/k/v, linear_out, pointwise_conv2: 32x32 tiles
+        const bool pd1 = prefetch_depth(ctx) == 1;
+        if (N >= 512) { NS_TAB(1, 2, 32) if (pd1) LAUNCHCHK("gemm_ns_tab<1,2,32;pd1>"); else LAUNCHCHK("gemm_ns_tab<1,2,32>"); }        // ffn1 / pointwise_conv1: 32x64 tiles
+        else if (K >= 1024) { NS_TAB(1, 1, 64) if (pd1) LAUNCHCHK("gemm_ns_tab<1,1,64;pd1>"); else LAUNCHCHK("gemm_ns_tab<1,1,64>"); }  // ffn2: 32x32 tiles, BK = 64
+        else { NS_TAB(1, 1, 32) if (pd1) LAUNCHCHK("gemm_ns_tab<1,1,32;pd1>"); else LAUNCHCHK("gemm_ns_tab<1,1,32>"); }                 // q/k/v, linear_out, pointwise_conv2: 32x32 tiles
 #undef NS_TAB
         return RNNT_OK;
     }

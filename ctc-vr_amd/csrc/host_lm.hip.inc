@@ -95,8 +95,9 @@ int launch_ffn_as_t(rnnt_ctx* ctx, hipStream_t s, const FfnP& p) {
 int launch_ffn_as(rnnt_ctx* ctx, hipStream_t s, const FfnP& p) {
     ProfScope prof(ctx, s, p.A0 ? TAG_OUT_PW1 : (p.w1p2 ? TAG_FFN_MERGED : (p.n_tail > 0 ? TAG_FFN_QKV : TAG_FFN_FUSED)));
     // waves per workgroup: 8 = two per SIMD, one wave's waits on weight fragments under the other's MFMAs (bitwise the same
-    // results as 4; FFN 52 -> 47 us, FFN + q/k/v 102 -> 87 us, linear_out + pointwise_conv1 48 -> 39 us); RNNT_FFN_NW=4 reverts
-    static const int nw = getenv("RNNT_FFN_NW") ? atoi(getenv("RNNT_FFN_NW")) : 8;
+    // results as 4; FFN 52 -> 47 us, FFN + q/k/v 102 -> 87 us, linear_out + pointwise_conv1 48 -> 39 us); RNNT_FFN_NW=4 reverts, =16
+    // runs 1024-thread workgroups (the same bits too: a column's sums do not depend on the wave that owns it; test_kernel_forms.py)
+    const int nw = ctx->ffn_nw;
 #define FFN_NW_DISPATCH(NUM_) return nw == 16 ? launch_ffn_as_t<NUM_, 16>(ctx, s, p) : nw == 4 ? launch_ffn_as_t<NUM_, 4>(ctx, s, p) : launch_ffn_as_t<NUM_, 8>(ctx, s, p)
     switch (ctx->numerics) {
         case RNNT_NUM_BF16X3: FFN_NW_DISPATCH(RNNT_NUM_BF16X3);

@@ -252,6 +252,21 @@ struct rnnt_ctx {
     int attn_bf = 1;                           // RNNT_ATTN_BF=0: exact-f32 MFMA attention (rel_attention_lm_mfma) in every mode
     int attn_resident = 1;                     // RNNT_ATTN_RESIDENT=0: always the tiled rel_attention_lm_bf, never rel_attention_lm_res
     int conv1_fuse = 1;                        // RNNT_CONV1_FUSE=0: conv1_relu_rows + gemm_bw over the y1 slab, never gemm_bw_c1
+    // launch-form knobs, read at rnnt_create like the ones above (a process can hold contexts of every value side by side)
+    int ffn_nw = 8;                            // RNNT_FFN_NW: waves per ffn_as workgroup, 4 / 8 / 16 (anything else: 8)
+    int gemm_pd = 2;                           // RNNT_GEMM_PD=1: one K block in flight per gemm_ns / gemm_ns_tab workgroup instead of two
+    int conv2_bw = 1;                          // RNNT_CONV2_BW=0: conv2 never on gemm_bw / gemm_bw_c1 (launch_gemm's tiles at every M)
+    int conv1_rows = 1;                        // RNNT_CONV1_ROWS=0: conv1_relu at every shape, never conv1_relu_rows
+    int conv2_lds = 1;                         // RNNT_CONV2_LDS: exact-f32 conv2 of >= 2048 rows: 0 launch_gemm, 1 gemm_ns<2,2>, 2 non-temporal A (nc > 1)
+    int bw_nw = 8;                             // RNNT_BW_NW=4: gemm_bw / gemm_bw_c1 with 4 waves (anything but 8 selects 4)
+    int gemm_ns = 1;                           // RNNT_GEMM_NS=0: exact-f32 stage GEMMs on gemm16_tab whatever the number of descriptors
+    int ns_min_groups = 2;                     // RNNT_NS_MIN_GROUPS: fewest descriptors of a stage GEMM that go to gemm_ns_tab
+    int xcd_x = 0;                             // RNNT_XCD_X = 1 / 2 / 4 / 8: XCDs per descriptor of the table GEMMs' 1-D grids (else chosen per launch)
+    int fuse_merge = FUSE_MAXC;                // RNNT_FUSE_MERGE: chunks of one layer per fused wavefront stage, clamped to 1..FUSE_MAXC
+    int fuse_frames = 12;                      // RNNT_FUSE_FRAMES: frames per stream of one fused tile (at most FUSE_MAXF)
+    int attn_pair_major = 1;                   // RNNT_ATTN_PAIR_MAJOR=0: rel_attention_stream_tab's workgroups head-major instead of pair-major
+    int dec_slack = 8;                         // RNNT_DEC_SLACK: graph decoder steps per wavefront stage beyond the stage's new frames
+    int drain_steps = 4;                       // RNNT_DRAIN_STEPS: graph decoder steps per round of greedy_drain
     DevBuf<float> lm_x, lm_h, lm_q, lm_a, lm_d, lm_g, lm_y1, lm_y2;
     DevBuf<float> lm_y1b, lm_y2b;                  // slabs of the tail chunk class (subsampled on sub_stream beside the main class)
     hipEvent_t sub_ev[2] = {nullptr, nullptr};     // fork / join of the tail class on sub_stream

@@ -1,7 +1,8 @@
 """Shapes, float64 references and the coverage table shared by test_kernel_forms_cpu.py and test_kernel_forms.py: the encoder's host
 code chooses a kernel form by shape (host_launch.hip.inc: launch_gemm, run_subsample, launch_gemm_tab; host_lm.hip.inc: the
 layer-major schedule), and every shape here sits just above or just below one of its thresholds.  rnnt_encoder_full is the call that
-reaches them with a float64 oracle (oracle.rnnt_oracle.encoder_full).  No GPU is touched here."""
+reaches them with a float64 oracle (oracle.rnnt_oracle.encoder_full).  The forms, tile maps and stage plans that a knob selects
+(read per context at rnnt_create) have cases of their own on the same shapes: KNOB_FULL, KNOB_WF, KNOB_CASES.  No GPU is touched here."""
 import os
 import re
 
@@ -32,6 +33,27 @@ VARIANTS = {
     "nolm": {"RNNT_LM": "0"},                           # eager run_subsample + run_layer, tiled rel_attention<4> under klen
     "nofuse": {"RNNT_CONV1_FUSE": "0"},                 # conv2-32768 only: conv1_relu_rows + gemm_bw instead of gemm_bw_c1
     "unchained": {"RNNT_LM_QKV_TAIL": "0", "RNNT_LM_OUT_CHAIN": "0", "RNNT_LM_PW2_HEAD": "0"},   # layer-1024, split modes: gemm_as, dwconv_lm
+    # ---- the launch-form knobs of KNOB_FULL / KNOB_WF below (per context like the ones above; no case of CASES sets them) ----
+    "bw4": {"RNNT_BW_NW": "4"},                         # gemm_bw_c1<4>
+    "bw4-nofuse": {"RNNT_BW_NW": "4", "RNNT_CONV1_FUSE": "0"},   # gemm_bw<4>
+    "ffn4": {"RNNT_FFN_NW": "4"}, "ffn16": {"RNNT_FFN_NW": "16"},
+    "nobw": {"RNNT_CONV2_BW": "0"},                     # conv2 of 32851 rows on gemm_bf<2,2>
+    "norows": {"RNNT_CONV1_ROWS": "0"},                 # conv1_relu where conv1_relu_rows would run
+    "pd1": {"RNNT_GEMM_PD": "1"},                       # gemm_ns with one K block in flight
+    "attnf32": {"RNNT_ATTN_BF": "0"},                   # exact-f32 attention in a split mode
+    # wavefront contexts (RNNT_LM=0)
+    "nolm-lds2": {"RNNT_LM": "0", "RNNT_CONV2_LDS": "2"}, "nolm-lds0": {"RNNT_LM": "0", "RNNT_CONV2_LDS": "0"},
+    "nolm-lds2-pd1": {"RNNT_LM": "0", "RNNT_CONV2_LDS": "2", "RNNT_GEMM_PD": "1"},
+    "nolm-ns0": {"RNNT_LM": "0", "RNNT_GEMM_NS": "0"}, "nolm-nsmin1": {"RNNT_LM": "0", "RNNT_NS_MIN_GROUPS": "1"},
+    "nolm-pd1": {"RNNT_LM": "0", "RNNT_GEMM_PD": "1"},
+    **{f"nolm-x{x}": {"RNNT_LM": "0", "RNNT_XCD_X": str(x)} for x in (1, 2, 4, 8)},
+    "nolm-apm0": {"RNNT_LM": "0", "RNNT_ATTN_PAIR_MAJOR": "0"},
+    "nolm-subsync": {"RNNT_LM": "0", "RNNT_WF_SUB_ASYNC": "0"},   # the wavefront's subsampling on the caller's stream
+    "nolm-unfused": {"RNNT_LM": "0", "RNNT_FUSED": "0"},
+    **{f"nolm-unfused-x{x}": {"RNNT_LM": "0", "RNNT_FUSED": "0", "RNNT_XCD_X": str(x)} for x in (1, 2, 4, 8)},
+    "nolm-unfused-merge1": {"RNNT_LM": "0", "RNNT_FUSED": "0", "RNNT_WF_MERGE": "1"},
+    "nolm-fmerge1": {"RNNT_LM": "0", "RNNT_FUSE_MERGE": "1"}, "nolm-fmerge2": {"RNNT_LM": "0", "RNNT_FUSE_MERGE": "2"},
+    "nolm-fframes8": {"RNNT_LM": "0", "RNNT_FUSE_FRAMES": "8"}, "nolm-fframes16": {"RNNT_LM": "0", "RNNT_FUSE_FRAMES": "16"},
 }
 KNOBS = sorted({k for v in VARIANTS.values() for k in v})
 
@@ -156,6 +178,41 @@ def wf_ref(stream):
     return _CACHE[key]
 
 
+def wf_cfg(kind):
+    return {"wf": WF, "fwf": FUSED_WF, "fknob": FUSE_KNOB}[kind]
+
+
+def wf_kind_plan(kind):
+    c = wf_cfg(kind)
+    return W.make_plan(c["len"], c["policy"], c["chunks"])
+
+
+def wf_kind_input(kind):
+    """[B, chunks * len, 80] float32 of a wavefront shape (read-only; "wf": stream B - 1 is stream 0 again)"""
+    if kind == "wf":
+        return wf_input()
+    if kind == "fwf":
+        return fused_wf_input()
+    if "fkx" not in _CACHE:
+        c = FUSE_KNOB
+        x = T.synth_fbank(c["B"], c["len"] * c["chunks"], seed=c["seed"])
+        x.setflags(write=False)
+        _CACHE["fkx"] = x
+    return _CACHE["fkx"]
+
+
+def wf_kind_ref(kind, stream):
+    """float64 frames of one stream of a wavefront shape (encoder_stream_ref over its chunk plan), computed once per session"""
+    if kind == "wf":
+        return wf_ref(stream)
+    if kind == "fwf":
+        return fused_wf_ref(stream)
+    key = ("fkref", stream)
+    if key not in _CACHE:
+        _CACHE[key] = np.concatenate([r["frames"] for r in T.encoder_stream_ref(state_dict(), wf_kind_input(kind)[stream].copy(), wf_kind_plan(kind))], 0)
+    return _CACHE[key]
+
+
 # ---- form names of the two host files ------------------------------------------------------------------------------------------------
 def source_forms():
     """Every form name a launch site of the two host files can log: the literals given to LAUNCHCHK, and the names the tiled
@@ -234,7 +291,102 @@ def fused_wf_ref(b):
     return _CACHE[key]
 
 
-KNOB = "needs a process-static knob"
+# ---- the knobs that were process-static: one context per value, in the same process ------------------------------------------------
+# rnnt_encoder_full cases beside CASES: (pair, side, mode, variant) -> the default-knob case of the same shape and mode whose frames
+# the code claims (or this table records) to be bit-identical, or None where only the float64 bar is asserted
+KNOB_FULL = {}
+for _m in SPLIT:
+    KNOB_FULL[("conv2-32768", "above", _m, "bw4")] = "default"             # "RNNT_BW_NW=4, same results" (host_launch.hip.inc)
+    KNOB_FULL[("conv2-32768", "above", _m, "bw4-nofuse")] = "nofuse"
+    KNOB_FULL[("conv2-32768", "above", _m, "nobw")] = None                 # other tiles (64 rows, k order of gemm_bf): float64 bar only
+    for _p in ("layer-1024", "conv2-2048"):
+        KNOB_FULL[(_p, "above", _m, "ffn4")] = "default"                   # "bitwise the same results as 4" (host_lm.hip.inc)
+        KNOB_FULL[(_p, "above", _m, "ffn16")] = "default"                  # "the same bits too" (host_lm.hip.inc): a column's sums do not depend on its wave
+    KNOB_FULL[("conv2-2048", "above", _m, "attnf32")] = None
+KNOB_FULL[("layer-1024", "above", "fp32", "norows")] = "default"           # conv1_relu and conv1_relu_rows: the same nine fmaf per output
+KNOB_FULL[("layer-1024", "above", "bf16x3", "norows")] = "default"
+KNOB_FULL[("layer-1024", "above", "fp32", "pd1")] = None                   # the prefetch depth reorders loads, not sums: recorded
+KNOB_FULL_IDS = {c: case_id(*c) for c in KNOB_FULL}
+
+# wavefront cases: id -> (shape kind, mode, variant, the variant it is compared with bit by bit or None, whether equality is asserted)
+# "wf": 64 streams x 2 chunks (fp32; conv2 M = 19456 >= 2048 with nc = 2); "fwf": FUSED_WF's three streams, fused or (RNNT_FUSED=0)
+# on gemm_bf_tab; "fknob": three streams x 8 chunks of 19 frames (t' = 4), the shape on which the fuse knobs move the stage plan
+FUSE_KNOB = {"B": 3, "len": 19, "chunks": 8, "policy": "all", "seed": 8107}
+KNOB_WF = {
+    "wavefront-fp32-nolm-lds2": ("wf", "fp32", "nolm-lds2", "nolm", True),          # a non-temporal load changes no arithmetic
+    "wavefront-fp32-nolm-lds0": ("wf", "fp32", "nolm-lds0", "nolm", False),
+    "wavefront-fp32-nolm-lds2-pd1": ("wf", "fp32", "nolm-lds2-pd1", "nolm", False),
+    "wavefront-fp32-nolm-ns0": ("wf", "fp32", "nolm-ns0", "nolm", False),
+    "wavefront-fp32-nolm-nsmin1": ("wf", "fp32", "nolm-nsmin1", "nolm", False),
+    "wavefront-fp32-nolm-pd1": ("wf", "fp32", "nolm-pd1", "nolm", False),
+    **{f"wavefront-fp32-nolm-x{x}": ("wf", "fp32", f"nolm-x{x}", "nolm", True) for x in (1, 2, 4, 8)},   # X only deals tiles to workgroups
+    "wavefront-fp32-nolm-apm0": ("wf", "fp32", "nolm-apm0", "nolm", True),             # t' = 16: no direct-stream attention, the knob is not read
+    "wavefront-fp32-nolm-subsync": ("wf", "fp32", "nolm-subsync", "nolm", True),       # the same launches on the same arguments, on one stream
+    "wavefront-t4-fp32-nolm": ("fknob", "fp32", "nolm", None, False),
+    "wavefront-t4-fp32-nolm-apm0": ("fknob", "fp32", "nolm-apm0", "nolm", False),
+    **{f"wavefront-unfused-{m}": ("fwf", m, "nolm-unfused", None, False) for m in SPLIT},
+    **{f"wavefront-unfused-{m}-x{x}": ("fwf", m, f"nolm-unfused-x{x}", "nolm-unfused", True) for m in SPLIT for x in (1, 2, 4, 8)},
+    **{f"wavefront-unfused-{m}-merge1": ("fwf", m, "nolm-unfused-merge1", "nolm-unfused", False) for m in SPLIT},
+    **{f"fuse-knobs-{m}": ("fknob", m, "nolm", None, False) for m in SPLIT},
+    **{f"fuse-knobs-{m}-{k}": ("fknob", m, f"nolm-{k}", "nolm", False) for m in SPLIT for k in ("fmerge1", "fmerge2", "fframes8", "fframes16")},
+}
+KNOB_IDS = list(KNOB_FULL_IDS.values()) + list(KNOB_WF)
+# streams of the 64-stream shape that a knob case holds to float64.  Rows are stream-major, 16 per stream, so a 64-row tile
+# (gemm16_tab<4,4,4>) holds streams 4k .. 4k + 3 in its four 16-row subtiles and a 32-row tile two: streams 0, 1, 2 and 63 sit in
+# subtiles 0, 1, 2 and 3.  (Every stream is also held to the default context's frames, which WF["streams"] hold to float64.)
+WF_KNOB_STREAMS = (0, 1, 2, 63)
+
+# stage plans of the fused wavefront on FUSE_KNOB (8 chunks of t' = 4, R = -1): chunks per super-chunk = min(RNNT_FUSE_MERGE,
+# floor(min(RNNT_FUSE_FRAMES, 16) / 4)); stages = super-chunks + 11, one block_front and one block_back launch per stage.  Three streams
+# x (chunks x 4) frames per tile -> the half-block's row tiles MT = ceil(3 * frames / 16).
+FUSE_PLANS = {"nolm": (3, 3), "nolm-fmerge1": (1, 1), "nolm-fmerge2": (2, 2), "nolm-fframes8": (2, 2), "nolm-fframes16": (4, 3)}   # variant -> (chunks per stage, MT)
+
+
+def fuse_launches(variant):
+    """-> (stages = block_front launches = block_back launches, MT of the full stages) of a FUSE_KNOB case"""
+    per, mt = FUSE_PLANS[variant]
+    return -(-FUSE_KNOB["chunks"] // per) + 11, mt
+
+
+DECODE = "test_decode_edges.py::test_graph_decoder_step_budget"
+# knob -> the ids of the cases that create a context under it (KNOB_CASES), or, for the knobs other test files hold, file::test
+KNOB_CASES = {
+    "RNNT_BW_NW": [i for c, i in KNOB_FULL_IDS.items() if c[3] in ("bw4", "bw4-nofuse")],
+    "RNNT_FFN_NW": [i for c, i in KNOB_FULL_IDS.items() if c[3].startswith("ffn")],
+    "RNNT_CONV2_BW": [i for c, i in KNOB_FULL_IDS.items() if c[3] == "nobw"],
+    "RNNT_CONV1_ROWS": [i for c, i in KNOB_FULL_IDS.items() if c[3] == "norows"],
+    "RNNT_ATTN_BF": [i for c, i in KNOB_FULL_IDS.items() if c[3] == "attnf32"],
+    "RNNT_GEMM_PD": [i for c, i in KNOB_FULL_IDS.items() if c[3] == "pd1"] + ["wavefront-fp32-nolm-pd1", "wavefront-fp32-nolm-lds2-pd1"],
+    "RNNT_CONV2_LDS": ["wavefront-fp32-nolm-lds2", "wavefront-fp32-nolm-lds0", "wavefront-fp32-nolm-lds2-pd1"],
+    "RNNT_GEMM_NS": ["wavefront-fp32-nolm-ns0"],
+    "RNNT_NS_MIN_GROUPS": ["wavefront-fp32-nolm-nsmin1"],
+    "RNNT_XCD_X": [i for i in KNOB_WF if i[-3:-1] == "-x"],
+    "RNNT_ATTN_PAIR_MAJOR": ["wavefront-fp32-nolm-apm0", "wavefront-t4-fp32-nolm-apm0"],
+    "RNNT_FUSE_MERGE": [i for i in KNOB_WF if "-fmerge" in i],
+    "RNNT_FUSE_FRAMES": [i for i in KNOB_WF if "-fframes" in i],
+    "RNNT_WF_MERGE": [i for i in KNOB_WF if i.endswith("-merge1")],
+    "RNNT_FUSED": [i for i in KNOB_WF if i.startswith("wavefront-unfused")],
+    "RNNT_DEC_SLACK": [DECODE], "RNNT_DRAIN_STEPS": [DECODE], "RNNT_NO_GRAPH": [DECODE],
+    "RNNT_WF_SUB_ASYNC": ["wavefront-fp32-nolm-subsync"],
+    "RNNT_LM": _ids(variants=["nolm"]) + [WF_ID], "RNNT_AS": _ids(variants=["noas"]), "RNNT_CONV1_FUSE": _ids(variants=["nofuse"]),
+    "RNNT_LM_QKV_TAIL": _ids(variants=["unchained"]), "RNNT_LM_OUT_CHAIN": _ids(variants=["unchained"]), "RNNT_LM_PW2_HEAD": _ids(variants=["unchained"]),
+    "RNNT_ATTN_STREAM": TILED_IDS,
+    "RNNT_LM_FFN_MERGE": ["test_gpu_parity.py"], "RNNT_LM_SIDE": ["test_gpu_parity.py"],
+    "RNNT_ATTN_RESIDENT": ["test_attention_resident.py"], "RNNT_PERSISTENT": ["test_decode_edges.py"], "RNNT_DEC_MULTI": ["test_decode_edges.py"],
+    "RNNT_BEAM_CHAIN": ["test_beam_device.py"], "RNNT_PREFIX_GROUP": ["test_stream_pool_prefix.py"],
+}
+# knobs of DESIGN §10 that change no device work (diagnostics, and names §10 lists as removed), each with its reason
+KNOBS_WITHOUT_DEVICE_EFFECT = {
+    "RNNT_LM_DEBUG": "diagnostic: host-side checksums printed after every launch of the layer-major schedule",
+    "RNNT_GM_DBG": "diagnostic: greedy_multi writes phase stamps into a buffer of their own",
+    "RNNT_GM_DBG_STREAM": "diagnostic: which row's stamps the host prints",
+    "RNNT_TIMING": "diagnostic: host timers printed to stderr",
+    "RNNT_BF_TILE": "removed with the 128-row tiles (named in §10 as gone)",
+    "RNNT_COOP": "removed with the cooperative decoder (named in §10 as gone)",
+    "RNNT_DEC_KF": "removed with the greedy_stream instantiations nothing used (named in §10 as gone)",
+}
+
+
 SHAPE = "needs a shape beyond a few-second test"
 POOL = "stream-pool only"
 NONE = "no encoder call reaches it"
@@ -254,8 +406,8 @@ COVERAGE = {
                         + _ids(["conv2-32768"], ["above"], SPLIT, ["nolm", "nofuse"]) + [WF_ID]),
     "gemm_bw_c1<8>": _ids(["conv2-32768"], ["above"], SPLIT, ["default", "noas"]),
     "gemm_bw<8>": _ids(["conv2-32768"], ["above"], SPLIT, ["nolm", "nofuse"]),
-    "gemm_bw_c1<4>": KNOB + " (RNNT_BW_NW=4)",
-    "gemm_bw<4>": KNOB + " (RNNT_BW_NW=4)",
+    "gemm_bw_c1<4>": [i for i in KNOB_CASES["RNNT_BW_NW"] if i.endswith("-bw4")],
+    "gemm_bw<4>": [i for i in KNOB_CASES["RNNT_BW_NW"] if i.endswith("-bw4-nofuse")],
     # launch_gemm, split-operand modes: conv2 below 32768 rows and the embed GEMM everywhere; every layer contraction under
     # RNNT_AS=0, RNNT_LM=0 and (attention out-projection, pointwise_conv2) unchained
     "gemm_bf<2,2>": _ids(modes=SPLIT),
@@ -266,7 +418,12 @@ COVERAGE = {
     "gemm_ns<2,2>": _ids(BIG2, modes=["fp32"]) + _ids(["conv2-2048"], ["above"], ["fp32"]) + [WF_ID],
     "gemm_ns<1,2>": _ids(["layer-1024"], ["above"], ["fp32"]) + _ids(["conv2-32768"], modes=["fp32"]) + _ids(["conv2-2048"], ["below"], ["fp32"]) + [WF_ID],
     "gemm_ns<2,2,tanh>": NONE + ": the joint's tanh operand (rnnt_joint and the scoring calls; the decoder side is held by its own tests)",
-    "gemm_ns<2,2,nt>": KNOB + " (RNNT_CONV2_LDS=2)",
+    "gemm_ns<2,2,nt>": ["wavefront-fp32-nolm-lds2"],
+    # one K block in flight (RNNT_GEMM_PD=1): names of their own
+    "gemm_ns<2,2;pd1>": ["layer-1024-above-fp32-pd1", "wavefront-fp32-nolm-pd1"],
+    "gemm_ns<1,2;pd1>": ["layer-1024-above-fp32-pd1", "wavefront-fp32-nolm-pd1"],
+    "gemm_ns<2,2,nt;pd1>": ["wavefront-fp32-nolm-lds2-pd1"],
+    "gemm_ns<2,2,tanh;pd1>": NONE + ": the joint's tanh operand (rnnt_joint and the scoring calls; the decoder side is held by its own tests)",
     "gemm16<4,1>": _ids(["layer-1024"], ["below"], ["fp32"]) + _ids(["conv2-2048"], modes=["fp32"]) + [WINDOW, WHOLE],
     "gemm16<4,2>": _ids(["layer-1024"], ["below"], ["fp32"]) + _ids(["conv2-2048"], modes=["fp32"]) + [WINDOW, WHOLE],
     "gemm16<8,1>": _ids(["layer-1024"], ["below"], ["fp32"]) + _ids(["conv2-2048"], modes=["fp32"]) + [WINDOW, WHOLE],
@@ -274,8 +431,8 @@ COVERAGE = {
     # layer-major schedule
     "lm_ctx_in": _ids(variants=LM),
     "ffn_as<8>": _ids(modes=SPLIT, variants=["default", "nofuse", "unchained"]) + [WHOLE],
-    "ffn_as<4>": KNOB + " (RNNT_FFN_NW=4)",
-    "ffn_as<16>": KNOB + " (RNNT_FFN_NW=16)",
+    "ffn_as<4>": [i for i in KNOB_CASES["RNNT_FFN_NW"] if i.endswith("ffn4")],
+    "ffn_as<16>": [i for i in KNOB_CASES["RNNT_FFN_NW"] if i.endswith("ffn16")],
     "gemm_as": _ids(modes=SPLIT, variants=["unchained"]),
     "rel_attention_lm_res": _ids(["conv2-2048"], modes=SPLIT, variants=LM) + [WHOLE],
     "rel_attention_lm_bf": _ids(BIG2, modes=SPLIT, variants=LM) + [WHOLE],          # t' >= 246 keys do not fit the resident plan
@@ -293,14 +450,15 @@ COVERAGE = {
     # wavefront schedule
     "block_front<1>": [WHOLE], "block_front<2>": [WHOLE], "block_front<3>": FUSED_WF_IDS,
     "block_back<1>": [WHOLE], "block_back<2>": [WHOLE], "block_back<3>": FUSED_WF_IDS,
-    "gemm_bf_tab<1,1>": [WHOLE], "gemm_bf_tab<1,2>": [WHOLE],
+    "gemm_bf_tab<1,1>": [WHOLE] + [f"wavefront-unfused-{m}" for m in SPLIT], "gemm_bf_tab<1,2>": [WHOLE] + [f"wavefront-unfused-{m}" for m in SPLIT],
     "gemm_ns_tab<1,1,32>": [WF_ID, WHOLE], "gemm_ns_tab<1,1,64>": [WF_ID, WHOLE], "gemm_ns_tab<1,2,32>": [WF_ID, WHOLE],
+    "gemm_ns_tab<1,1,32;pd1>": ["wavefront-fp32-nolm-pd1"], "gemm_ns_tab<1,1,64;pd1>": ["wavefront-fp32-nolm-pd1"], "gemm_ns_tab<1,2,32;pd1>": ["wavefront-fp32-nolm-pd1"],
     "gemm16_tab<4,1,1>": [WF_ID, WHOLE], "gemm16_tab<8,1,1>": [WF_ID, WHOLE], "gemm16_tab<4,1,2>": [WHOLE],
     "gemm16_tab<4,2,4>": [WF_ID],                        # ffn w_1 and pointwise_conv1 of the single-descriptor stages: 1024 rows x N >= 512
-    # the two larger tiles need one descriptor of >= 2048 rows (two or more descriptors go to gemm_ns_tab): the log of the 64 x 16
-    # row case shows <4,2,4> and the 16-row tiles only, and the shape is not grown
-    "gemm16_tab<4,4,4>": SHAPE + ": a single descriptor of >= 2048 rows x 1024 columns (128 streams x 16 frames), or RNNT_GEMM_NS=0",
-    "gemm16_tab<8,2,4>": SHAPE + ": a single K = 1024 descriptor of >= 2048 rows (128 streams x 16 frames), or RNNT_GEMM_NS=0",
+    # the two larger tiles need n * maxM * N >= 2 097 152 (K < 1024) / >= 524 288 (K = 1024): in a default context one descriptor of
+    # >= 2048 rows (two or more go to gemm_ns_tab); under RNNT_GEMM_NS=0 the two-descriptor stages of the 64 x 16 row case reach both
+    "gemm16_tab<4,4,4>": ["wavefront-fp32-nolm-ns0"],
+    "gemm16_tab<8,2,4>": ["wavefront-fp32-nolm-ns0"],
     "gemm16_tab<8,1,2>": NONE + ": no stage GEMM class has K = 1024 with N >= 512",
     # helpers of the stream pool that live in host_launch.hip.inc
     "beam_slot_reset": POOL, "ctc_prefix_slot_reset": POOL, "prefix_init_pool": POOL, "pool_hist_set": POOL, "pool_hist_append": POOL,

@@ -151,9 +151,10 @@ def maxdiff(a, b):
 _ENG = {}
 
 
-def _engine(V, blank, numerics, w=KERNEL_W, max_streams=16, max_cache=256, twins=(), max_beam=0):
+def _engine(V, blank, numerics, w=KERNEL_W, max_streams=16, max_cache=256, twins=(), max_beam=0, tag=None):
+    """tag: names the per-context knobs the caller has put into the environment (a context reads them at rnnt_create)"""
     from ctc_vr_amd.lib import RnntEngine
-    key = (V, blank, numerics, w, max_streams, max_cache, tuple(twins), max_beam)
+    key = (V, blank, numerics, w, max_streams, max_cache, tuple(twins), max_beam, tag)
     if key not in _ENG:
         e = RnntEngine(max_streams=max_streams, max_chunk_frames=32, max_cache_frames=max_cache, max_enc_frames=64, vocab_size=V,
                        blank_id=blank, max_beam=max_beam)
@@ -196,15 +197,17 @@ def _check_out(buf, n, ref, tol=LOGIT_TOL):
     return out
 
 
-def _run_joint(V, blank, numerics, shape, seed):
+def _run_joint(V, blank, numerics, shape, seed, tag=None):
+    """-> the [B, T, U, V] outputs of mode 0 and mode 1"""
     B, Tn, U = shape
-    eng = _engine(V, blank, numerics, w=JOINT_W, max_cache=max(256, -(-B * (Tn + U) * 256 // 6144)))   # rnnt_joint's scratch: 12 x 4 x 128 floats per cache frame
+    eng = _engine(V, blank, numerics, w=JOINT_W, max_cache=max(256, -(-B * (Tn + U) * 256 // 6144)), tag=tag)   # rnnt_joint's scratch: 12 x 4 x 128 floats per cache frame
     g = torch.Generator().manual_seed(seed)
     enc = torch.randn(B, Tn, 256, generator=g).cuda()
     prd = (torch.randn(B, U, 256, generator=g) * 0.5).cuda()
     ref = _joint64(_sd(V, blank, JOINT_W), enc, prd)
     s = torch.cuda.current_stream().cuda_stream
     n = B * Tn * U * V
+    outs = []
     for mode, want in ((0, ref), (1, torch.log_softmax(ref, dim=-1))):
         buf = _out_buffer(n)
         eng.joint(enc.data_ptr(), prd.data_ptr(), B, Tn, U, mode, buf.data_ptr(), s)
@@ -214,6 +217,8 @@ def _run_joint(V, blank, numerics, shape, seed):
         eng.joint(enc.data_ptr(), prd.data_ptr(), B, Tn, U, mode, again.data_ptr(), s)
         torch.cuda.synchronize()
         assert torch.equal(again[:n].view(out.shape), out)                         # the tile queue hands out tiles in another order
+        outs.append(out.clone())
+    return outs
 
 
 def _multi_tile_shapes():
@@ -241,6 +246,25 @@ def test_joint_lattice_vocab(V, numerics):
     """V = 412, 416 (whole last tile), 404 (partial last tile: padded columns carry a -inf bias) and 8 take the rows kernel in the
     split modes; V = 413 (V % 4 != 0), 600 and 4336 take the gemm_ns + log_softmax_rows fallback, as does every V in fp32."""
     _run_joint(V, 0, numerics, (3, 37, 11), V)
+
+
+def test_joint_lattice_prefetch_depth_one(monkeypatch):
+    """exact-f32 joint lattice (gemm_ns with the tanh operand, 1221 rows: 19 full 64-row tiles and one of 5) in a context created under
+    RNNT_GEMM_PD=1: within LOGIT_TOL of float64 like the default depth, and the form log names the launch ...;pd1) -- the default
+    context logs the plain name.  Printed: whether the two depths give the same bits."""
+    monkeypatch.setenv("RNNT_NUMERICS", "fp32")
+    logs, outs = {}, {}
+    for tag, pd in (("pd2", None), ("pd1", "1")):
+        monkeypatch.delenv("RNNT_GEMM_PD", raising=False)
+        if pd:
+            monkeypatch.setenv("RNNT_GEMM_PD", pd)
+        eng = _engine(412, 0, "fp32", w=JOINT_W, max_cache=256, tag=tag)
+        eng.form_log_begin()
+        outs[tag] = _run_joint(412, 0, "fp32", (3, 37, 11), 412, tag=tag)
+        logs[tag] = eng.form_log_end()
+    print(f"joint lattice: depth 2 {logs['pd2']}; depth 1 {logs['pd1']}; bit-identical: {[torch.equal(a, b) for a, b in zip(outs['pd1'], outs['pd2'])]}")
+    assert "gemm_ns(joint lattice;pd1)" in logs["pd1"] and "gemm_ns(joint lattice)" not in logs["pd1"]
+    assert "gemm_ns(joint lattice)" in logs["pd2"] and "gemm_ns(joint lattice;pd1)" not in logs["pd2"]
 
 
 # ---- B. predictor step ---------------------------------------------------------------------------------------------------------
@@ -356,6 +380,65 @@ def test_greedy_decode_paths(path, cfg, regime, monkeypatch):
     numerics = path if path in PARITY_MODES else "fp32"
     entries = ("per_chunk", "whole") if path == "persistent0" else ("per_chunk", "whole", "ragged")
     _check_greedy(cfg[0], cfg[1], regime, entries, numerics)
+
+
+# per-context step budgets of the graph decoder (RNNT_PERSISTENT=0): id -> knobs beside RNNT_PERSISTENT=0.  RNNT_DEC_SLACK is read by the
+# wavefront's per-stage decode batches (RNNT_LM=0), RNNT_DRAIN_STEPS by greedy_drain behind either schedule.
+BUDGETS = {
+    "wavefront-slack0": {"RNNT_LM": "0", "RNNT_DEC_SLACK": "0"}, "wavefront-slack3": {"RNNT_LM": "0", "RNNT_DEC_SLACK": "3"},
+    "wavefront-drain1": {"RNNT_LM": "0", "RNNT_DRAIN_STEPS": "1"}, "wavefront-drain7": {"RNNT_LM": "0", "RNNT_DRAIN_STEPS": "7"},
+    "layer-major-drain1": {"RNNT_DRAIN_STEPS": "1"}, "layer-major-drain7": {"RNNT_DRAIN_STEPS": "7"},
+    # RNNT_NO_GRAPH=1: the same step batches enqueued launch by launch instead of as captured graphs
+    "wavefront-nograph": {"RNNT_LM": "0", "RNNT_NO_GRAPH": "1"}, "layer-major-nograph": {"RNNT_NO_GRAPH": "1"},
+}
+_BUDGET = {}
+
+
+def _graph_decode(knobs, monkeypatch):
+    """the three 200-frame inputs through rnnt_encoder_chunks with greedy decoding in a context created under RNNT_PERSISTENT=0 and
+    `knobs` (every other budget knob unset) -> tokens per stream, token counts, (h, c, last token) per stream, the call's (launches,
+    evaluation steps enqueued)"""
+    key = tuple(sorted(knobs.items()))
+    if key not in _BUDGET:
+        from ctc_vr_amd.online_rnnt_model import StreamingBatch
+        for k in ("RNNT_LM", "RNNT_DEC_SLACK", "RNNT_DRAIN_STEPS", "RNNT_NO_GRAPH"):
+            monkeypatch.delenv(k, raising=False)
+        monkeypatch.setenv("RNNT_PERSISTENT", "0")
+        monkeypatch.setenv("RNNT_NUMERICS", "fp32")
+        for k, v in knobs.items():
+            monkeypatch.setenv(k, v)
+        V, blank = 412, 0
+        sb = StreamingBatch(_sd(V, blank, CONFIGS[(V, blank)]["mixed"]), 3, vocab_size=V, blank_id=blank, max_chunk_frames=48, max_cache_frames=128,
+                            max_enc_frames=64, max_tokens=512, numerics="fp32")
+        c0 = sb.engine.counters()
+        toks = sb.decode_script(_inputs().cuda().contiguous(), CHUNK, pipelined=True)
+        s = torch.cuda.current_stream().cuda_stream
+        _BUDGET[key] = (toks, sb.engine.token_counts(s).tolist(), [sb.engine.predictor_state(b, s) for b in range(3)],
+                        tuple(a - b for a, b in zip(sb.engine.counters(), c0)))
+        sb.engine.close()
+    return _BUDGET[key]
+
+
+@pytest.mark.parametrize("budget", list(BUDGETS))
+def test_graph_decoder_step_budget(budget, monkeypatch):
+    """RNNT_DEC_SLACK in {0, 3} and RNNT_DRAIN_STEPS in {1, 7} change how many evaluation steps the graph decoder enqueues per
+    wavefront stage and per drain round, RNNT_NO_GRAPH=1 how a batch of steps is enqueued, never what a step computes: tokens, counts and the predictor's (h, c, last token) are
+    bit-identical to the same context with the default budgets (8 and 4), whose tokens are the oracle's; the context's launch and
+    step counters show that the budget did change"""
+    knobs = BUDGETS[budget]
+    base = {k: v for k, v in knobs.items() if k == "RNNT_LM"}
+    want, got = _graph_decode(base, monkeypatch), _graph_decode(knobs, monkeypatch)
+    per, margin = _oracle_greedy(412, 0, CONFIGS[(412, 0)]["mixed"])
+    assert margin >= MARGIN, margin
+    assert want[0] == [_tokens(per[s]) for s in range(3)]
+    print(f"{budget}: (launches, steps enqueued) {got[3]} against {want[3]} with the default budgets; tokens per stream {got[1]}")
+    assert got[0] == want[0] and got[1] == want[1]
+    for b in range(3):
+        assert np.array_equal(got[2][b][0], want[2][b][0]) and np.array_equal(got[2][b][1], want[2][b][1]) and got[2][b][2] == want[2][b][2], b
+    if "RNNT_NO_GRAPH" in knobs:
+        assert got[3][1] == want[3][1], "the same batches, so the same number of steps enqueued"
+    else:
+        assert got[3] != want[3], "the knob changed neither the launches nor the steps enqueued"
 
 
 def test_token_buffer_isolation():

@@ -3,6 +3,7 @@ host_launch.hip.inc are; every form name of the two host files has a row in kern
 decision); wrong tiles planted in the float32 oracle -- the faults a large form's last partial tile, its LayerNorm prologue, its K/V
 scatter and its padded-row mask could have -- move the valid frames by what the frame bar can or cannot see; and the float32
 oracle's own distance from float64 at the shapes above the thresholds."""
+import os
 import re
 
 import numpy as np
@@ -56,30 +57,127 @@ def test_shape_arithmetic():
 
 def test_coverage_table_names_every_form():
     """every form-name literal of host_launch.hip.inc and host_lm.hip.inc is a key of the coverage table and the table names no form
-    that does not exist; a row is either test ids that exist or a reason: a process-static knob, a shape
-    beyond a few-second test, stream-pool only, or no encoder call reaches it"""
+    that does not exist; a row is either test ids that exist or a reason: a shape beyond a few-second test, stream-pool only, or
+    no encoder call reaches it -- no form is left behind a knob, since every knob is read per context"""
     forms = K.source_forms()
     assert len(forms) >= 50 and "gemm_bf<2,2>" in forms and "rel_attention<4>" in forms and "ffn_as<8>" in forms
     for path in K.HOST_FILES:                           # no launch site is left with a name built at run time
         assert not re.findall(r"LAUNCHCHK\((?![\"#])", open(path, encoding="utf-8").read().split("#define LAUNCHCHK", 1)[-1]), path
     assert sorted(forms - set(K.COVERAGE)) == [], "forms without a row in kernel_forms.COVERAGE"
     assert sorted(set(K.COVERAGE) - forms) == [], "rows of kernel_forms.COVERAGE for forms that no launch site names"
-    ids = {K.case_id(*c) for c in K.CASES} | set(K.EXTRA_IDS)
+    ids = {K.case_id(*c) for c in K.CASES} | set(K.EXTRA_IDS) | set(K.KNOB_IDS)
+    assert len(ids) == len(K.CASES) + len(K.EXTRA_IDS) + len(K.KNOB_IDS)
     for form, v in K.COVERAGE.items():
         if isinstance(v, str):
-            assert v.startswith((K.KNOB, K.POOL, K.SHAPE, K.NONE)), (form, v)
+            assert v.startswith((K.POOL, K.SHAPE, K.NONE)) and "knob" not in v, (form, v)
         else:
             assert v and all(i in ids or i in K.EXISTING for i in v), (form, [i for i in v if i not in ids and i not in K.EXISTING])
     for c in K.CASES:
         assert K.expected_forms(K.case_id(*c)), c
+    for form in ("ffn_as<4>", "ffn_as<16>", "gemm_bw<4>", "gemm_bw_c1<4>", "gemm_ns<2,2,nt>", "gemm16_tab<4,4,4>", "gemm16_tab<8,2,4>"):
+        assert isinstance(K.COVERAGE[form], list) and set(K.COVERAGE[form]) <= set(K.KNOB_IDS), form     # the seven that no test had run
 
 
 def test_design_table_is_the_coverage_table():
     """DESIGN §3 carries one row per form, generated from the coverage table (kernel_forms.design_rows)"""
-    import os
     design = open(os.path.join(K.ROOT, "DESIGN.md"), encoding="utf-8").read()
     missing = [r for r in K.design_rows() if r not in design]
     assert not missing, missing
+
+
+CSRC = os.path.join(K.ROOT, "ctc-vr_amd", "csrc")
+DIAGNOSTICS = {"RNNT_LM_DEBUG", "RNNT_TIMING", "RNNT_GM_DBG"}
+
+
+def test_no_knob_is_read_once_per_process():
+    """no function-local `static` initialised from getenv is left under csrc, apart from the three diagnostics: a knob read that
+    way has one value per process, and a test process could hold only one of its kernel forms to float64"""
+    found = {}
+    for name in sorted(os.listdir(CSRC)):
+        text = open(os.path.join(CSRC, name), encoding="utf-8").read()
+        text = re.sub(r"//[^\n]*", "", text)                      # statement by statement, not line by line: an initialiser may wrap
+        for m in re.finditer(r"\bstatic\b[^;{}]*\bgetenv\s*\([^;]*;", text):
+            found[f"{name}:{text.count(chr(10), 0, m.start()) + 1}"] = set(re.findall(r'getenv\("(\w+)"\)', m.group(0)))
+    assert all(v and v <= DIAGNOSTICS for v in found.values()), {k: v for k, v in found.items() if not (v and v <= DIAGNOSTICS)}
+    assert set().union(*found.values()) == DIAGNOSTICS, found
+    # and every knob of the tables is read in rnnt_create
+    life = open(os.path.join(CSRC, "api_lifecycle.hip.inc"), encoding="utf-8").read()
+    create = life[life.index("int rnnt_create("):life.index("ALLOC(y1")]
+    for knob in K.KNOBS:
+        assert f'getenv("{knob}")' in create, knob
+
+
+def test_every_design_knob_is_held_or_has_no_device_effect():
+    """every RNNT_* knob DESIGN §10 names is either in KNOB_CASES, with case ids of test_kernel_forms.py that create a context under
+    it (or the test file that does), or in the short list of knobs that change no device work, with the reason"""
+    design = open(os.path.join(K.ROOT, "DESIGN.md"), encoding="utf-8").read()
+    sec = design[design.index("## 10. Environment knobs"):]
+    named = set(re.findall(r"RNNT_[A-Z0-9_]+", sec))
+    assert len(named) >= 40 and {"RNNT_FFN_NW", "RNNT_XCD_X", "RNNT_DRAIN_STEPS", "RNNT_GEMM_PD"} <= named
+    assert "per context, read at `rnnt_create`" in sec
+    both = set(K.KNOB_CASES) & set(K.KNOBS_WITHOUT_DEVICE_EFFECT)
+    assert not both, both
+    missing = named - set(K.KNOB_CASES) - set(K.KNOBS_WITHOUT_DEVICE_EFFECT)
+    assert not missing, sorted(missing)
+    assert len(K.KNOBS_WITHOUT_DEVICE_EFFECT) <= 10 and all(len(r) > 20 for r in K.KNOBS_WITHOUT_DEVICE_EFFECT.values())
+    ids = {K.case_id(*c) for c in K.CASES} | set(K.EXTRA_IDS) | set(K.KNOB_IDS)
+    tests_dir = os.path.join(K.ROOT, "tests")
+    for knob, held in K.KNOB_CASES.items():
+        assert held, knob
+        for i in held:
+            if i in ids:
+                continue
+            path, _, fn = i.partition("::")                      # a test of another file: it exists and sets the knob
+            src = open(os.path.join(tests_dir, path), encoding="utf-8").read()
+            assert knob in src and (not fn or f"def {fn}(" in src), (knob, i)
+    # a case listed under a knob sets that knob
+    for knob, held in K.KNOB_CASES.items():
+        for i in held:
+            variant = next((c[3] for c, n in K.KNOB_FULL_IDS.items() if n == i), K.KNOB_WF[i][2] if i in K.KNOB_WF else None)
+            assert variant is None or knob in K.VARIANTS[variant], (knob, i)
+    for knob in K.KNOBS:                                         # and no knob of a variant is left out
+        assert knob in K.KNOB_CASES, knob
+
+
+def test_gemm16_tab_thresholds_of_the_knob_cases():
+    """launch_gemm_tab's tile choice for the stages of the 64 x 16-row wavefront case: out = n * maxM * N against 256 * 64 * 64 * 2
+    (K < 1024) and 256 * 32 * 64 (K = 1024 too).  Default context: one descriptor goes to gemm16_tab and reaches <4,2,4> at most;
+    RNNT_GEMM_NS=0 sends the two-descriptor stages there and they reach <4,4,4> and <8,2,4>; the thresholds are the source's"""
+    src = open(K.HOST_FILES[0], encoding="utf-8").read()
+    assert 'out >= 256ll * 64 * 64 * 2 && wk == 4) { launch_gemm16_tab<4, 4, 4>' in src
+    assert 'out >= 256ll * 32 * 64 && wk == 8) { launch_gemm16_tab<8, 2, 4>' in src
+    assert "const int wk = K >= 1024 ? 8 : 4;" in src and "const long long out = (long long)n * maxM * N;" in src
+    big, mid = 256 * 64 * 64 * 2, 256 * 32 * 64
+    assert (big, mid) == (2097152, 524288)
+    M = K.WF["B"] * K.sub_len(K.WF["len"])
+    assert M == 1024
+
+    def tile(n, N, Kd):
+        out, wk = n * M * N, 8 if Kd >= 1024 else 4
+        if out >= big and wk == 4:
+            return "<4,4,4>"
+        if out >= mid:
+            return "<4,2,4>" if wk == 4 else "<8,2,4>"
+        return "<8,1,2>" if N >= 512 and wk == 8 else "<4,1,2>" if N >= 512 else "<8,1,1>" if wk == 8 else "<4,1,1>"
+    classes = {"ffn1": (1, 1024, 256), "ffn2": (1, 256, 1024), "qkv": (3, 256, 256), "out": (1, 256, 256), "pw1": (1, 512, 256), "pw2": (1, 256, 256)}
+    one = {k: tile(m, N, Kd) for k, (m, N, Kd) in classes.items() if m == 1}    # (q/k/v of one pair are three descriptors: gemm_ns_tab)
+    two = {k: tile(2 * m, N, Kd) for k, (m, N, Kd) in classes.items()}
+    assert one == {"ffn1": "<4,2,4>", "ffn2": "<8,1,1>", "out": "<4,1,1>", "pw1": "<4,2,4>", "pw2": "<4,1,1>"}
+    assert two == {"ffn1": "<4,4,4>", "ffn2": "<8,2,4>", "qkv": "<4,2,4>", "out": "<4,2,4>", "pw1": "<4,2,4>", "pw2": "<4,2,4>"}
+    assert 2 * M * 1024 == big and 2 * M * 256 == mid                        # both exactly AT their thresholds
+    assert K.COVERAGE["gemm16_tab<4,4,4>"] == K.COVERAGE["gemm16_tab<8,2,4>"] == ["wavefront-fp32-nolm-ns0"]
+    # the fuse knobs' stage plans on three streams x 8 chunks of t' = 4 (wf_build_tables, launch_fused): chunks per stage and row tiles
+    tq, B, C = K.sub_len(K.FUSE_KNOB["len"]), K.FUSE_KNOB["B"], K.FUSE_KNOB["chunks"]
+    assert (tq, B, C) == (4, 3, 8)
+    for variant, (per, mt) in K.FUSE_PLANS.items():
+        kn = K.VARIANTS[variant]
+        merge, frames = int(kn.get("RNNT_FUSE_MERGE", 4)), min(int(kn.get("RNNT_FUSE_FRAMES", 12)), 16)
+        assert per == min(max(merge, 1), 4, frames // tq), variant
+        S = min(48 // (per * tq), B)
+        assert mt == -(-S * per * tq // 16), variant
+    assert sorted(K.fuse_launches(v)[0] for v in K.FUSE_PLANS) == [13, 14, 15, 15, 19]
+    # on FUSED_WF itself (chunks of t' = 16 = FUSE_MAXF) a second chunk never fits a tile: neither knob can move its plan
+    assert K.sub_len(K.FUSED_WF["len"]) * 2 > 16
 
 
 # ---- planted faults ------------------------------------------------------------------------------------------------------------------
