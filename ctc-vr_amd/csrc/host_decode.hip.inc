@@ -216,7 +216,11 @@ int finish_persistent_decoder(rnnt_ctx* ctx, hipStream_t s) {
             sum[0] += d; sum[1] += n;
             fprintf(stderr, " %s %.2f / %.2f,", name[k], d, n);
         }
-        fprintf(stderr, " total %.2f / %.2f\n", sum[0], sum[1]);
+        // The early W_hh product is off the chain: wave 0 forms its share behind its XA stores (inside what used to be its XA wait, so
+        // the dirty total includes it), waves 1-7 from the quarter-sum barrier on (wave 7's time: the product under full LDS contention).
+        const double e0 = r[23] / 100.0 / (double)(r[22] > 0 ? r[22] : 1), e7 = r[26] / 100.0 / (double)(r[22] > 0 ? r[22] : 1);
+        fprintf(stderr, " total %.2f / %.2f; hidden early W_hh per dirty pass: wave 0 %.2f (after its XA store), wave 7 %.2f (from the quarter-sum barrier)\n",
+                sum[0] + e0, sum[1], e0, e7);
     }
     if (ctx->pinned[13] != 0) return fail(ctx, RNNT_ERR_STATE, "persistent decoder gave up (code %d: 1 = frame wait, 2 = greedy_multi exchange wait)", ctx->pinned[13]);
     return RNNT_OK;

@@ -344,7 +344,9 @@ __global__ void probe_overlap_wait(int* ctrl, long long ticks) {
 //       pp = b_c + sum of the four partials (added in part order, so all four hold the same bits)
 //   XA  per frame of the pass: the part's (max logit, argmax) over its vocabulary rows  ->  every part takes the same decision
 // (a run of blank frames costs one XA only: as in greedy_stream the predictor is re-evaluated only after a symbol and up to KF
-// frames share a pass).  Every exchanged 32-bit value travels as one 8-byte word (payload | tag << 32) written with one
+// frames share a pass).  The W_hh x h product of a predictor step is formed one step early, inside the XA exchange of the pass that
+// made h (its h' then): the committed h of a step is always an earlier candidate, whole in LDS long before the decision that commits
+// it, and only egate[tok] needs that decision -- so the product is off the symbol chain (g_next / have_g in the kernel).  Every exchanged 32-bit value travels as one 8-byte word (payload | tag << 32) written with one
 // write-through store and polled with L1-bypassing loads: valid iff the tag matches the exchange's sequence number; buffers
 // alternate by that number's parity (a part can only be one exchange ahead of the slowest of its group).  Same state machine and
 // per-logit operand order as the reference loop (online_rnnt_model.py:193-220); h' and pp are summed in a different (fixed)
@@ -365,7 +367,7 @@ __device__ __forceinline__ void st_tag(unsigned long long* p, unsigned payload, 
 #define GM_PARTS 4
 #define GM_X1 320            // words per part: 64 h' + 256 pp partials
 #define GM_WLD 260           // LDS row stride of the W_out slice (floats)
-#define GM_DBG_W 32          // stamp words per stream: [12 c + k] phase k of non-dirty (c = 0) / dirty (c = 1) passes, [12 c + 10] passes, [24] count, [25] stream
+#define GM_DBG_W 32          // stamp words per stream: [12 c + k] phase k of non-dirty (c = 0) / dirty (c = 1) passes, [12 c + 10] passes, [23] wave 0's / [26] wave 7's early W_hh product, [24] count, [25] stream
 struct DecMP : DecP {           // slots: stream group i (mailboxes i) decodes stream slots[i]
     unsigned long long* x1;      // [2][B][4][GM_X1]
     unsigned long long* xa;      // [2][B][4][2 * KF]
@@ -478,13 +480,44 @@ __global__ __launch_bounds__(512) void greedy_multi(DecMP p) {
     unsigned ev1 = 1, ev3 = 0;   // ev1: sequence number of the X1 exchange of the next predictor step = 1 + commits so far
     int seen_ready = 0;
     bool dirty = true, bad = false;
+#if GM_WHH_REGS
+    // W_hh x candidate h', formed ahead of the pass that needs it (see the one-frame branch of the argmax exchange).  Loop state: both
+    // outlive the decision loop's continue / break and every pass that leaves the candidate alone.
+    float g_next = 0.f;
+    bool have_g = false;
+#endif
     // Phase stamps (RNNT_GM_DBG): thread 0 of part 0 adds the ticks since its last stamp to an LDS word with a no-return atomic, so a
-    // stamp costs one clock read and holds no registers; dirty and non-dirty passes are kept apart.
+    // stamp costs one clock read and holds no registers; dirty and non-dirty passes are kept apart.  The first thread of wave 7 times
+    // its early W_hh product the same way (word 26, its otherwise idle `tl`): wave 0's own share is stamp 11 of the dirty passes.
     long long tl = (long long)__builtin_amdgcn_s_memrealtime();
     const bool tdbg = p.dbg != nullptr && pw == 0 && tid0 == 0;
+    const bool tdbg7 = p.dbg != nullptr && pw == 0 && tid0 == 448;
 #define GM_T(k) { if (tdbg) { const long long t_ = (long long)__builtin_amdgcn_s_memrealtime(); \
                               (void)__hip_atomic_fetch_add(tsh + (dirty ? 12 : 0) + (k), t_ - tl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); tl = t_; } }
+#if GM_WHH_REGS
+    // G_ = this thread's half row of W_hh x the h buffer H_, both lanes of a row holding the same bits afterwards (the sum commutes).
+    // One body for the two places that form the product, so the operand order is the same in both.  (A macro: through a lambda that
+    // captures whh_r hipcc keeps the 128 weights in scratch.)
+#define GM_WHH_DOT(G_, H_) { \
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f; \
+        _Pragma("unroll") \
+        for (int j = 0; j < 32; ++j) { \
+            const float4 hv = *reinterpret_cast<const float4*>(&(H_)[128 * kh + 4 * j]); \
+            a0 = fmaf(whh_r[4 * j], hv.x, a0); \
+            a1 = fmaf(whh_r[4 * j + 1], hv.y, a1); \
+            a2 = fmaf(whh_r[4 * j + 2], hv.z, a2); \
+            a3 = fmaf(whh_r[4 * j + 3], hv.w, a3); \
+            if ((j & 3) == 3) __builtin_amdgcn_sched_barrier(0); \
+        } \
+        G_ = (a0 + a1) + (a2 + a3); \
+        G_ += __shfl_xor(G_, 1, 64); }
+#endif
     __syncthreads();
+#if GM_WHH_REGS
+    // The first predictor step of a call has no earlier pass to form its product in: form it here from the loaded h, once, so the loop
+    // holds the product in ONE place (with a second, conditional copy at the head of the predictor step hipcc spills the weights).
+    { const int kh = tid0 & 1; GM_WHH_DOT(g_next, hb) have_g = true; }
+#endif
     while (fidx < n_total) {
         // Every index below is derived from an OPAQUE copy of the thread id made inside the iteration: with plain loop-invariant
         // indices LLVM hoists a few hundred LDS / global address computations out of this loop and then spills them (and the
@@ -492,7 +525,9 @@ __global__ __launch_bounds__(512) void greedy_multi(DecMP p) {
         int tid = tid0;
         asm volatile("" : "+v"(tid));
         const int lane = tid & 63, wave = tid >> 6, row2 = tid >> 1, kh = tid & 1;
+#if !GM_WHH_REGS
         float* hs = hb + (ev1 & 1 ? 0 : RNNT_D);             // committed h: the half changes with every commit
+#endif
         float* h2 = hb + (ev1 & 1 ? RNNT_D : 0);             // candidate h'
         // ---- frames available (bounded wait; the sequential schedule publishes everything before the launch) -----------------
         int avail = seen_ready;
@@ -537,18 +572,9 @@ __global__ __launch_bounds__(512) void greedy_multi(DecMP p) {
 #if GM_WHH_REGS
             {
                 const float eg = ldg1(p.egate + (long long)tok * (4 * RNNT_D) + 256 * pw + row2);
-                float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-#pragma unroll
-                for (int j = 0; j < 32; ++j) {
-                    const float4 hv = *reinterpret_cast<const float4*>(&hs[128 * kh + 4 * j]);
-                    a0 = fmaf(whh_r[4 * j], hv.x, a0);
-                    a1 = fmaf(whh_r[4 * j + 1], hv.y, a1);
-                    a2 = fmaf(whh_r[4 * j + 2], hv.z, a2);
-                    a3 = fmaf(whh_r[4 * j + 3], hv.w, a3);
-                    if ((j & 3) == 3) __builtin_amdgcn_sched_barrier(0);
-                }
-                float g = (a0 + a1) + (a2 + a3);
-                g += __shfl_xor(g, 1, 64);                   // both lanes of a row hold the same bits (the sum commutes)
+                // W_hh x hs is not formed here: hs is the candidate that the commit before this pass made the committed h, and its
+                // product was formed inside an earlier pass's argmax exchange (the first pass of a call: in front of the loop).
+                const float g = g_next;                      // both lanes of a row hold the same bits
                 // The i, f, g, o rows of a hidden unit sit in lane pairs 0-1, 2-3, 4-5, 6-7 of one group of eight lanes, so the unit's
                 // first lane takes them through DPP and no LDS round trip or barrier stands between the product and the cell:
                 // f from lane ^ 2, o from the mirror lane 7, g from the mirror of the quad swap (lane 5).
@@ -570,6 +596,9 @@ __global__ __launch_bounds__(512) void greedy_multi(DecMP p) {
             }
 #endif
             GM_T(1)
+#if GM_WHH_REGS
+            have_g = false;                                   // the cell phase below writes a new candidate
+#endif
             if (cell) {
                 const int unit = 64 * pw + (tid >> 3);
                 cc2 = sigmoidf_(gf) * cc + sigmoidf_(gi) * tanhf(gg);
@@ -709,7 +738,34 @@ __global__ __launch_bounds__(512) void greedy_multi(DecMP p) {
                     xav[pw * 2 * KF + 2 * lane] = u;
                     xav[pw * 2 * KF + 2 * lane + 1] = (unsigned)ix;
                 }
+                GM_T(7)
             }
+#if GM_WHH_REGS
+            // ---- the NEXT predictor step's W_hh x h', in the window of this exchange.  The committed h of a predictor step is always
+            // the candidate of the pass that emitted the symbol or of an earlier one, and the candidate has been whole in LDS since the
+            // barrier that closed its X1 gather; only egate[tok] waits for a decision.  From the quarter-sum barrier above to the
+            // exchange barrier below wave 0 alone finishes the rows, takes the argmax and stores the XA words, 24 threads of wave 1 poll
+            // and the LDS pipe idles (>= 1.3 us against the product's 0.9), so waves 1-7 form the product at once, wave 1's pollers
+            // before they poll (the other parts' words are at least as far away), wave 0 behind its stores.  Same loop, same operand
+            // order, same bits as the product in place.  Hazards:
+            //   * h2 is read here strictly between those two barriers.  The next writer of EITHER h buffer is the cell phase of a later
+            //     predictor pass, behind this pass's exchange barrier; the last writer of h2 was this or an earlier predictor pass's X1
+            //     gather, in front of the quarter-sum barrier.
+            //   * A candidate is committed by whichever later pass emits the next symbol, so g_next is used exactly once per candidate
+            //     (the last candidate of a call is formed for nothing).  After a commit the buffer roles swap and g_next belongs to what
+            //     is now hs; without one the candidate stays and so does g_next: a non-predictor pass neither forms nor reads it (a
+            //     one-frame pass of that kind finds have_g set).  The n_steps cap commits like any symbol.
+            //   * The exchange is untouched: same words, tags, parity, bounded waits and abort word, and no barrier is added.
+            //   * have_g is uniform over the workgroup: cleared by the cell phase, set here in the same pass (a predictor pass has one
+            //     frame), so every predictor step finds its product ready; the first one of a call takes the one formed before the loop.
+            if (!have_g) {
+                if (tdbg7) tl = (long long)__builtin_amdgcn_s_memrealtime();
+                GM_WHH_DOT(g_next, h2)
+                have_g = true;
+                if (tdbg7) (void)__hip_atomic_fetch_add(tsh + 26, (long long)__builtin_amdgcn_s_memrealtime() - tl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                GM_T(11)
+            }
+#endif
         } else {
             {
                 const int k = tid >> 7, r = tid & 127;         // KF * 128 = 512 threads
@@ -743,9 +799,9 @@ __global__ __launch_bounds__(512) void greedy_multi(DecMP p) {
                 xav[pw * 2 * KF + 2 * tid] = u;
                 xav[pw * 2 * KF + 2 * tid + 1] = (unsigned)ix;
             }
+            GM_T(7)
         }
 #undef GM_STEP
-        GM_T(7)
         if (tid >= 64 && tid < 64 + (GM_PARTS - 1) * 2 * KF) {
             const int idx = tid - 64;
             int q = idx / (2 * KF);
@@ -795,6 +851,9 @@ __global__ __launch_bounds__(512) void greedy_multi(DecMP p) {
         for (int k = 0; k < GM_DBG_W; ++k) out[k] = tsh[k];
     }
 #undef GM_T
+#if GM_WHH_REGS
+#undef GM_WHH_DOT
+#endif
     // ---- canonical state for the host / the next call (buffer 0 becomes the committed one) ---------------------------------
     if (pw == 0 && tid0 < RNNT_D) stg1(p.h + (long long)b * RNNT_D + tid0, hb[(ev1 & 1 ? 0 : RNNT_D) + tid0]);
     if (cell) stg1(p.c + (long long)b * RNNT_D + cell_unit, cc);
