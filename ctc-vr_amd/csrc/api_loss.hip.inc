@@ -1,6 +1,7 @@
 // C ABI: the transducer loss with its gradient over a caller's joint lattice (torchaudio.functional.rnnt_loss), and its pure C++
 // twin.  No context: a loss needs no weights and no model, so refusals are status codes without a message.
-// Included by rnnt_api.hip inside extern "C".  Kernels: rnnt_loss.hip.h.
+// rnnt_transducer_loss_elem is the device entry point for float, bfloat16 and float16 lattices; rnnt_transducer_loss is its float case.
+// Included by rnnt_api.hip inside extern "C" (the one template, loss_launch, steps out of it).  Kernels: rnnt_loss.hip.h.
 
 // lengths and labels of a loss call, checked on the host before anything is launched or written
 static int loss_check(const void* logits, const int32_t* targets, const int32_t* logit_lens, const int32_t* target_lens, int32_t B, int32_t T,
@@ -54,10 +55,29 @@ int rnnt_transducer_loss_workspace(int32_t B, int32_t T, int32_t U1, int64_t* by
         if ((expr) != hipSuccess) return RNNT_ERR_HIP; \
     } while (0)
 
-int rnnt_transducer_loss(const float* logits_dev, const int32_t* targets_host, const int32_t* logit_lens_host, const int32_t* target_lens_host, int32_t B,
-                         int32_t T, int32_t Umax, int32_t V, int32_t blank, int32_t fused_log_softmax, float clamp, double* nll_dev, float* grad_dev,
-                         void* workspace_dev, int64_t workspace_bytes, void* stream) {
+// The two lattice passes over elements E, with LP and LG lanes per cell; the recursions and the factors between them do not see E.
+extern "C++" template <typename E, int LP, int LG>
+static void loss_launch(const LossWork& w, const void* logits, void* grad, int B, int T, int U1, int V, int ts, int blank, int fused, float clamp,
+                        double* nll, hipStream_t s) {
+    const int ncell = B * T * U1;
+    const dim3 pick((unsigned)((ncell + 256 / LP - 1) / (256 / LP))), lattice((unsigned)((ncell + 256 / LG - 1) / (256 / LG)));   // 256 / L cells each, no loop
+    const dim3 cells((unsigned)grid_for(ncell));
+    const E* x = (const E*)logits;
+    E* g = (E*)grad;
+    hipLaunchKernelGGL((loss_pick<E, LP>), pick, dim3(256), 0, s, x, w.tg, w.lens, B, T, U1, V, ts, blank, fused, w.lse, w.pick);
+    hipLaunchKernelGGL(transducer_alpha_beta, dim3(2 * B), dim3(256), 0, s, w.pick, w.lens, B, T, U1, w.alpha, w.beta, w.nll_alpha, nll);
+    if (g) {
+        hipLaunchKernelGGL(loss_coef, cells, dim3(256), 0, s, w.pick, w.lse, w.alpha, w.beta, w.lens, B, T, U1, fused, w.coef);
+        if (fused) hipLaunchKernelGGL((loss_grad<E, LG, true>), lattice, dim3(256), 0, s, x, w.tg, w.lens, w.coef, B, T, U1, V, ts, blank, clamp, g);
+        else hipLaunchKernelGGL((loss_grad<E, LG, false>), lattice, dim3(256), 0, s, x, w.tg, w.lens, w.coef, B, T, U1, V, ts, blank, clamp, g);
+    }
+}
+
+int rnnt_transducer_loss_elem(const void* logits_dev, const int32_t* targets_host, const int32_t* logit_lens_host, const int32_t* target_lens_host,
+                              int32_t B, int32_t T, int32_t Umax, int32_t V, int32_t blank, int32_t elem, int32_t fused_log_softmax, float clamp,
+                              double* nll_dev, void* grad_dev, void* workspace_dev, int64_t workspace_bytes, void* stream) {
     int rc;
+    if (elem != RNNT_LOSS_F32 && elem != RNNT_LOSS_BF16 && elem != RNNT_LOSS_F16) return RNNT_ERR_ARG;   // before any pointer is followed
     if ((rc = loss_check(logits_dev, targets_host, logit_lens_host, target_lens_host, B, T, Umax, V, blank, nll_dev))) return rc;
     if (!workspace_dev || ((uintptr_t)logits_dev | (uintptr_t)grad_dev | (uintptr_t)workspace_dev) & 15) return RNNT_ERR_ARG;
     const int U1 = Umax + 1, ts = Umax > 0 ? Umax : 1;
@@ -73,17 +93,19 @@ int rnnt_transducer_loss(const float* logits_dev, const int32_t* targets_host, c
     }
     // (pageable source: the runtime has taken the bytes when the call returns, so `host` may go; what follows is launches only)
     LOSS_HIPCHK(hipMemcpyAsync(w.lens, host.data(), w.ints * sizeof(int), hipMemcpyHostToDevice, s));
-    const int ncell = B * T * U1, fused = fused_log_softmax != 0;
-    const dim3 lattice((unsigned)((ncell + LOSS_CELLS - 1) / LOSS_CELLS)), cells((unsigned)grid_for(ncell));   // one workgroup per 16 cells, no loop
-    hipLaunchKernelGGL(loss_pick, lattice, dim3(256), 0, s, logits_dev, w.tg, w.lens, B, T, U1, V, ts, blank, fused, w.lse, w.pick);
-    hipLaunchKernelGGL(transducer_alpha_beta, dim3(2 * B), dim3(256), 0, s, w.pick, w.lens, B, T, U1, w.alpha, w.beta, w.nll_alpha, nll_dev);
-    if (grad_dev) {
-        hipLaunchKernelGGL(loss_coef, cells, dim3(256), 0, s, w.pick, w.lse, w.alpha, w.beta, w.lens, B, T, U1, fused, w.coef);
-        if (fused) hipLaunchKernelGGL(loss_grad<true>, lattice, dim3(256), 0, s, logits_dev, w.tg, w.lens, w.coef, B, T, U1, V, ts, blank, clamp, grad_dev);
-        else hipLaunchKernelGGL(loss_grad<false>, lattice, dim3(256), 0, s, logits_dev, w.tg, w.lens, w.coef, B, T, U1, V, ts, blank, clamp, grad_dev);
-    }
+    const int fused = fused_log_softmax != 0;
+    if (elem == RNNT_LOSS_F32) loss_launch<float, LOSS_LANES, LOSS_LANES>(w, logits_dev, grad_dev, B, T, U1, V, ts, blank, fused, clamp, nll_dev, s);
+    else if (elem == RNNT_LOSS_BF16) loss_launch<loss_bf16, LOSS_LANES_16BIT_PICK, LOSS_LANES_16BIT_GRAD>(w, logits_dev, grad_dev, B, T, U1, V, ts, blank, fused, clamp, nll_dev, s);
+    else loss_launch<loss_f16, LOSS_LANES_16BIT_PICK, LOSS_LANES_16BIT_GRAD>(w, logits_dev, grad_dev, B, T, U1, V, ts, blank, fused, clamp, nll_dev, s);
     LOSS_HIPCHK(hipGetLastError());
     return RNNT_OK;
+}
+
+int rnnt_transducer_loss(const float* logits_dev, const int32_t* targets_host, const int32_t* logit_lens_host, const int32_t* target_lens_host, int32_t B,
+                         int32_t T, int32_t Umax, int32_t V, int32_t blank, int32_t fused_log_softmax, float clamp, double* nll_dev, float* grad_dev,
+                         void* workspace_dev, int64_t workspace_bytes, void* stream) {
+    return rnnt_transducer_loss_elem(logits_dev, targets_host, logit_lens_host, target_lens_host, B, T, Umax, V, blank, RNNT_LOSS_F32, fused_log_softmax,
+                                     clamp, nll_dev, grad_dev, workspace_dev, workspace_bytes, stream);
 }
 #undef LOSS_HIPCHK
 

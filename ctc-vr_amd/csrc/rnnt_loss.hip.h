@@ -12,27 +12,99 @@
 // multiple of 4 start at any of the four phases -- with at most three single floats in front and three behind.  One wave per cell
 // left a lane with at most two loads in flight at V = 412 and a chain of dependent latencies per cell (lengths, row, picked
 // values): 61 % of the copy rate in loss_pick; the narrow groups put four rows' loads in flight per wave for every V.
-// Which lane sums which elements, and in which order, depends only on (cell, V): no atomics, so two launches agree bit for bit.
+// Which lane sums which elements, and in which order, depends only on (cell, V, element type): no atomics, so two launches agree
+// bit for bit.
 // Cells outside t < T_b, u <= U_b are never read; loss_grad writes zeros there.
 // Cell indices are ints (the host refuses B * T * U1 >= 2^31); element offsets cell * V are 64-bit.
+//
+// The two passes are templates over the lattice element E: float, bfloat16 or float16, for logits AND gradient.  A 16-byte vector
+// holds EPV = 16 / sizeof(E) elements, so a 16-bit row starts at any of EIGHT phases and has at most seven single elements in front
+// and behind (still fewer than a cell's lanes).  Every element is widened to float exactly on load (a shift, a convert); lse, the
+// picks, p_k and g_k are the float32 arithmetic of the float lattice; g_k is clamped in float32 and rounded once, to nearest even,
+// by the plain cast at the store.  L is the lanes per cell (16, or 8: half a DPP row, the butterflies stop at xor 4).
 #pragma once
 
-#define LOSS_LANES 16            // lanes per cell: one DPP row, so the reductions below need no LDS and no bpermute
-#define LOSS_CELLS 16            // cells in flight per 256-thread workgroup
-#define LOSS_BATCH 4             // float4 loads a lane issues before it uses the first
+#define LOSS_LANES 16            // lanes per cell of a float lattice: one DPP row, so the reductions below need no LDS and no bpermute
+#ifndef LOSS_LANES_16BIT_PICK    // lanes per cell of a 16-bit lattice, per pass: 16 against 8 measured at the joint shape,
+#define LOSS_LANES_16BIT_PICK 8  // loss_pick is faster with 8 (two batches of loads per lane at V = 412, eight cells per wave),
+#endif
+#ifndef LOSS_LANES_16BIT_GRAD
+#define LOSS_LANES_16BIT_GRAD 16 // loss_grad with 16; -D overrides either for that measurement
+#endif
+#define LOSS_BATCH 4             // 16-byte loads a lane issues before it uses the first
 
-// all-reduce over the 16 lanes of a cell (xor_partner's ascending butterfly: every lane ends with the same bits)
-__device__ __forceinline__ float row16_max(float v) {
+typedef __bf16 loss_bf16;
+typedef _Float16 loss_f16;
+
+// all-reduce over the L lanes of a cell (xor_partner's ascending butterfly: every lane ends with the same bits)
+template <int L>
+__device__ __forceinline__ float row_max(float v) {
     v = fmaxf(v, xor_partner<1>(v));
     v = fmaxf(v, xor_partner<2>(v));
     v = fmaxf(v, xor_partner<4>(v));
-    return fmaxf(v, xor_partner<8>(v));
+    return L == 16 ? fmaxf(v, xor_partner<8>(v)) : v;
 }
-__device__ __forceinline__ float row16_sum(float v) {
+template <int L>
+__device__ __forceinline__ float row_sum(float v) {
     v += xor_partner<1>(v);
     v += xor_partner<2>(v);
     v += xor_partner<4>(v);
-    return v + xor_partner<8>(v);
+    return L == 16 ? v + xor_partner<8>(v) : v;
+}
+
+// One 16-byte vector of the lattice as floats, and the loads and stores of an element type: single elements and whole vectors.
+template <typename E>
+struct LossVec {
+    static constexpr int N = 16 / sizeof(E);
+    float x[N];
+};
+template <typename E>
+__device__ __forceinline__ float loss_ld1(const E* p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (float)*(const RNNT_GAS E*)p;
+#else
+    return (float)*p;
+#endif
+}
+template <typename E>
+__device__ __forceinline__ void loss_st1(E* p, float v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    *(RNNT_GAS E*)p = (E)v;
+#else
+    *p = (E)v;
+#endif
+}
+template <typename E>
+__device__ __forceinline__ LossVec<E> loss_ldv(const E* p) {
+    typedef E ev __attribute__((ext_vector_type(LossVec<E>::N)));
+#if defined(__HIP_DEVICE_COMPILE__)
+    const ev v = *(const RNNT_GAS ev*)p;
+#else
+    const ev v = *reinterpret_cast<const ev*>(p);
+#endif
+    LossVec<E> o;
+#pragma unroll
+    for (int j = 0; j < LossVec<E>::N; ++j) o.x[j] = (float)v[j];
+    return o;
+}
+template <typename E>
+__device__ __forceinline__ void loss_stv(E* p, const LossVec<E>& o) {
+    typedef E ev __attribute__((ext_vector_type(LossVec<E>::N)));
+    ev v;
+#pragma unroll
+    for (int j = 0; j < LossVec<E>::N; ++j) v[j] = (E)o.x[j];
+#if defined(__HIP_DEVICE_COMPILE__)
+    *(RNNT_GAS ev*)p = v;
+#else
+    *reinterpret_cast<ev*>(p) = v;
+#endif
+}
+template <typename E>
+__device__ __forceinline__ LossVec<E> loss_fill(float v) {
+    LossVec<E> o;
+#pragma unroll
+    for (int j = 0; j < LossVec<E>::N; ++j) o.x[j] = v;
+    return o;
 }
 
 // exp on v_exp_f32: |x| 2^-24 relative through the product with log2 e, which the terms that matter (x near 0) do not feel
@@ -50,69 +122,80 @@ __device__ __forceinline__ bool loss_cell(int c, const int* __restrict__ lens, i
     return o.t < o.Tb && o.u <= o.Ub;
 }
 
-// The pieces of row `e0 .. e0 + V` (element offsets from a 16-byte aligned base): head single floats, n4 float4s, tail floats.
-struct LossRow { int head, n4, tail; };
+// The pieces of row `e0 .. e0 + V` (element offsets from a 16-byte aligned base): head single elements, nvec vectors of EPV, tail
+// elements.
+struct LossRow { int head, nvec, tail; };
+template <int EPV>
 __device__ __forceinline__ LossRow loss_row(long long e0, int V) {
     LossRow r;
-    r.head = min(V, (int)((4 - (e0 & 3)) & 3));
-    r.n4 = (V - r.head) >> 2;
-    r.tail = V - r.head - 4 * r.n4;
+    r.head = min(V, (int)((EPV - (e0 & (EPV - 1))) & (EPV - 1)));
+    r.nvec = (int)((unsigned)(V - r.head) / EPV);
+    r.tail = V - r.head - EPV * r.nvec;
     return r;
 }
 
-// running (max, sum of exp(x - max)) of one lane; a lane that has seen nothing, or only -inf, holds (-inf, 0)
-__device__ __forceinline__ void lse_take(float& m, float& s, float mx, float4 v) {
+// running (max, sum of exp(x - max)) of one lane; a lane that has seen nothing, or only -inf, holds (-inf, 0).
+// One vector: the exponentials are summed as a fixed tree, four by four.  One element: the same with a single term (what a float4
+// of (x, -inf, -inf, -inf) gives, bit for bit: its other three terms are +0).
+template <int N>
+__device__ __forceinline__ void lse_take(float& m, float& s, const float (&x)[N]) {
+    static_assert(N == 4 || N == 8, "a 16-byte vector of 4- or 2-byte elements");
+    float mx = fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3]));
+    if constexpr (N == 8) mx = fmaxf(mx, fmaxf(fmaxf(x[4], x[5]), fmaxf(x[6], x[7])));
     const float mn = fmaxf(m, mx);
     const float ms = mn == -INFINITY ? 0.0f : mn;
-    s = s * loss_exp(m - ms) + ((loss_exp(v.x - ms) + loss_exp(v.y - ms)) + (loss_exp(v.z - ms) + loss_exp(v.w - ms)));
+    float e = (loss_exp(x[0] - ms) + loss_exp(x[1] - ms)) + (loss_exp(x[2] - ms) + loss_exp(x[3] - ms));
+    if constexpr (N == 8) e += (loss_exp(x[4] - ms) + loss_exp(x[5] - ms)) + (loss_exp(x[6] - ms) + loss_exp(x[7] - ms));
+    s = s * loss_exp(m - ms) + e;
+    m = mn;
+}
+__device__ __forceinline__ void lse_take1(float& m, float& s, float x) {
+    const float mn = fmaxf(m, x);
+    const float ms = mn == -INFINITY ? 0.0f : mn;
+    s = s * loss_exp(m - ms) + loss_exp(x - ms);
     m = mn;
 }
 
 // lens [2][B]: T_b in [1, T], U_b in [0, U1 - 1]; targets [B][ts]; labels inside a row's length are in [0, V) (checked on the host).
 // fused = 0: the input holds log-probabilities already, lse = 0 and only the two picked values are read.
-__global__ __launch_bounds__(256) void loss_pick(const float* __restrict__ logits, const int* __restrict__ targets, const int* __restrict__ lens,
+template <typename E, int L>
+__global__ __launch_bounds__(256) void loss_pick(const E* __restrict__ logits, const int* __restrict__ targets, const int* __restrict__ lens,
                                                  int B, int T, int U1, int V, int ts, int blank, int fused, float* __restrict__ lse,
                                                  float* __restrict__ pick) {
-    const int lane = threadIdx.x & (LOSS_LANES - 1);
+    constexpr int EPV = LossVec<E>::N;
+    const int lane = threadIdx.x & (L - 1);
     const int ncell = B * T * U1;
-    const int c = blockIdx.x * LOSS_CELLS + threadIdx.x / LOSS_LANES;   // launched with ceil(cells / LOSS_CELLS) workgroups
+    const int c = blockIdx.x * (256 / L) + threadIdx.x / L;    // launched with ceil(cells / (256 / L)) workgroups
     if (c >= ncell) return;
     LossCell q;
-    if (!loss_cell(c, lens, B, T, U1, q)) return;              // uniform over the cell's 16 lanes
+    if (!loss_cell(c, lens, B, T, U1, q)) return;              // uniform over the cell's lanes
     const long long e0 = (long long)c * V;
-    const float* row = logits + e0;
+    const E* row = logits + e0;
     float xb = 0.0f, xl = 0.0f;                            // the two picked logits: asked for before the row, not after the reduction
     if (lane == 0) {
-        xb = ldg1(row + blank);
-        if (q.u < q.Ub) xl = ldg1(row + ldgi(targets + (long long)q.b * ts + q.u));
+        xb = loss_ld1(row + blank);
+        if (q.u < q.Ub) xl = loss_ld1(row + ldgi(targets + (long long)q.b * ts + q.u));
     }
     float l = 0.0f;
     if (fused) {
-        const LossRow r = loss_row(e0, V);
+        const LossRow r = loss_row<EPV>(e0, V);
         float m = -INFINITY, s = 0.0f;
-        const float ninf = -INFINITY;
-        if (lane < r.head) {
-            const float x = ldg1(row + lane);
-            lse_take(m, s, x, make_float4(x, ninf, ninf, ninf));
-        }
-        const float* body = row + r.head;
-        for (int i = lane; i < r.n4; i += LOSS_LANES * LOSS_BATCH) {
-            float4 v[LOSS_BATCH];
+        if (lane < r.head) lse_take1(m, s, loss_ld1(row + lane));
+        const E* body = row + r.head;
+        for (int i = lane; i < r.nvec; i += L * LOSS_BATCH) {
+            LossVec<E> v[LOSS_BATCH];
 #pragma unroll
             for (int j = 0; j < LOSS_BATCH; ++j) {
-                const int ii = i + LOSS_LANES * j;
-                v[j] = ii < r.n4 ? ldg4(body + 4 * (long long)ii) : make_float4(ninf, ninf, ninf, ninf);
+                const int ii = i + L * j;
+                v[j] = ii < r.nvec ? loss_ldv(body + EPV * (long long)ii) : loss_fill<E>(-INFINITY);
             }
 #pragma unroll
-            for (int j = 0; j < LOSS_BATCH; ++j) lse_take(m, s, fmaxf(fmaxf(v[j].x, v[j].y), fmaxf(v[j].z, v[j].w)), v[j]);
+            for (int j = 0; j < LOSS_BATCH; ++j) lse_take(m, s, v[j].x);
         }
-        if (lane < r.tail) {
-            const float x = ldg1(body + 4 * (long long)r.n4 + lane);
-            lse_take(m, s, x, make_float4(x, ninf, ninf, ninf));
-        }
-        const float M = row16_max(m);
+        if (lane < r.tail) lse_take1(m, s, loss_ld1(body + EPV * (long long)r.nvec + lane));
+        const float M = row_max<L>(m);
         const float Ms = M == -INFINITY ? 0.0f : M;
-        const float S = row16_sum(s * loss_exp(m - Ms));
+        const float S = row_sum<L>(s * loss_exp(m - Ms));
         l = Ms + logf(S);
     }
     if (lane == 0) {
@@ -215,47 +298,51 @@ __device__ __forceinline__ float loss_g(float x, int k, float4 cf, int blank, in
     return clamp > 0.0f ? fminf(fmaxf(g, -clamp), clamp) : g;
 }
 
-template <bool FUSED>
-__global__ __launch_bounds__(256) void loss_grad(const float* __restrict__ logits, const int* __restrict__ targets, const int* __restrict__ lens,
+template <typename E, int L, bool FUSED>
+__global__ __launch_bounds__(256) void loss_grad(const E* __restrict__ logits, const int* __restrict__ targets, const int* __restrict__ lens,
                                                  const float* __restrict__ coef, int B, int T, int U1, int V, int ts, int blank, float clamp,
-                                                 float* __restrict__ grad) {
-    const int lane = threadIdx.x & (LOSS_LANES - 1);
+                                                 E* __restrict__ grad) {
+    constexpr int EPV = LossVec<E>::N;
+    const int lane = threadIdx.x & (L - 1);
     const int ncell = B * T * U1;
-    const int c = blockIdx.x * LOSS_CELLS + threadIdx.x / LOSS_LANES;   // launched with ceil(cells / LOSS_CELLS) workgroups
+    const int c = blockIdx.x * (256 / L) + threadIdx.x / L;    // launched with ceil(cells / (256 / L)) workgroups
     if (c >= ncell) return;
     LossCell q;
     const bool valid = loss_cell(c, lens, B, T, U1, q);
     const long long e0 = (long long)c * V;
-    const LossRow r = loss_row(e0, V);
-    const float* row = logits + e0;
-    float* out = grad + e0;
-    const float* body = row + r.head;
-    float* obody = out + r.head;
-    const int t0 = r.head + 4 * r.n4;                      // first element of the tail
-    if (!valid) {                                          // uniform over the cell's 16 lanes
-        const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (lane < r.head) stg1(out + lane, 0.0f);
-        for (int i = lane; i < r.n4; i += LOSS_LANES) stg4(obody + 4 * (long long)i, z);
-        if (lane < r.tail) stg1(out + t0 + lane, 0.0f);
+    const LossRow r = loss_row<EPV>(e0, V);
+    const E* row = logits + e0;
+    E* out = grad + e0;
+    const E* body = row + r.head;
+    E* obody = out + r.head;
+    const int t0 = r.head + EPV * r.nvec;                  // first element of the tail
+    if (!valid) {                                          // uniform over the cell's lanes
+        const LossVec<E> z = loss_fill<E>(0.0f);
+        if (lane < r.head) loss_st1(out + lane, 0.0f);
+        for (int i = lane; i < r.nvec; i += L) loss_stv(obody + EPV * (long long)i, z);
+        if (lane < r.tail) loss_st1(out + t0 + lane, 0.0f);
         return;
     }
     const float4 cf = ldg4(coef + 4 * (long long)c);
     const int y = q.u < q.Ub ? ldgi(targets + (long long)q.b * ts + q.u) : -1;
-    if (lane < r.head) stg1(out + lane, loss_g<FUSED>(FUSED ? ldg1(row + lane) : 0.0f, lane, cf, blank, y, clamp));
-    for (int i = lane; i < r.n4; i += LOSS_LANES * LOSS_BATCH) {
-        float4 v[LOSS_BATCH];
+    if (lane < r.head) loss_st1(out + lane, loss_g<FUSED>(FUSED ? loss_ld1(row + lane) : 0.0f, lane, cf, blank, y, clamp));
+    for (int i = lane; i < r.nvec; i += L * LOSS_BATCH) {
+        LossVec<E> v[LOSS_BATCH];
 #pragma unroll
         for (int j = 0; j < LOSS_BATCH; ++j) {
-            const int ii = i + LOSS_LANES * j;
-            v[j] = FUSED && ii < r.n4 ? ldg4(body + 4 * (long long)ii) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            const int ii = i + L * j;
+            v[j] = FUSED && ii < r.nvec ? loss_ldv(body + EPV * (long long)ii) : loss_fill<E>(0.0f);
         }
 #pragma unroll
         for (int j = 0; j < LOSS_BATCH; ++j) {
-            const int ii = i + LOSS_LANES * j, k = r.head + 4 * ii;
-            if (ii < r.n4)
-                stg4(obody + 4 * (long long)ii, make_float4(loss_g<FUSED>(v[j].x, k, cf, blank, y, clamp), loss_g<FUSED>(v[j].y, k + 1, cf, blank, y, clamp),
-                                                             loss_g<FUSED>(v[j].z, k + 2, cf, blank, y, clamp), loss_g<FUSED>(v[j].w, k + 3, cf, blank, y, clamp)));
+            const int ii = i + L * j, k = r.head + EPV * ii;
+            if (ii < r.nvec) {
+                LossVec<E> g;
+#pragma unroll
+                for (int n = 0; n < EPV; ++n) g.x[n] = loss_g<FUSED>(v[j].x[n], k + n, cf, blank, y, clamp);
+                loss_stv(obody + EPV * (long long)ii, g);
+            }
         }
     }
-    if (lane < r.tail) stg1(out + t0 + lane, loss_g<FUSED>(FUSED ? ldg1(row + t0 + lane) : 0.0f, t0 + lane, cf, blank, y, clamp));
+    if (lane < r.tail) loss_st1(out + t0 + lane, loss_g<FUSED>(FUSED ? loss_ld1(row + t0 + lane) : 0.0f, t0 + lane, cf, blank, y, clamp));
 }

@@ -112,6 +112,8 @@ SIGNATURES = {
     "rnnt_transducer_nll_nbest": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "rnnt_transducer_loss_workspace": (c_i32, [c_i32, c_i32, c_i32, ctypes.POINTER(c_i64)]),
     "rnnt_transducer_loss": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.c_float, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "rnnt_transducer_loss_elem": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.c_float, c_vp, c_vp, c_vp, c_i64,
+                                          c_vp]),
     "rnnt_transducer_loss_host": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.c_float, c_vp, c_vp]),
     "rnnt_rescore_select_host": (c_i32, [c_i32, c_vp, c_vp, ctypes.c_double, ctypes.c_double, c_vp, c_i32p]),
     "rnnt_stream_keep_frames": (c_i32, [c_vp, c_i32, c_i32, c_vp]),
@@ -488,7 +490,10 @@ def _loss_args(targets, logit_lens, target_lens, B, umax):
     return tg, ll, tl
 
 
-_LOSS_REFUSALS = {ERR_ARG: "a length, label, blank or pointer outside its range", ERR_SHAPE: "Umax > 255, too many cells or a workspace too small"}
+LOSS_F32, LOSS_BF16, LOSS_F16 = 0, 1, 2          # RNNT_LOSS_*: the lattice element of rnnt_transducer_loss_elem
+
+_LOSS_REFUSALS = {ERR_ARG: "a length, label, blank, element code or pointer outside its range",
+                  ERR_SHAPE: "Umax > 255, too many cells or a workspace too small"}
 
 
 def _loss_chk(rc, what, B, T, umax, V, blank):
@@ -518,14 +523,18 @@ def transducer_loss_host(logits, targets, logit_lens, target_lens, blank, fused_
 
 
 def transducer_loss_device(logits_ptr, shape, targets, logit_lens, target_lens, blank, fused_log_softmax, clamp, nll_ptr, grad_ptr, work_ptr,
-                           work_bytes, stream=None):
+                           work_bytes, stream=None, elem=None):
     """rnnt_transducer_loss over device pointers: logits float32 of `shape` = (B, T, Umax + 1, V), nll [B] float64, grad float32 of
-    `shape` or None, the workspace of transducer_loss_workspace(B, T, Umax + 1).  Launches on `stream` and returns: no synchronisation."""
+    `shape` or None, the workspace of transducer_loss_workspace(B, T, Umax + 1).  Launches on `stream` and returns: no synchronisation.
+    elem (LOSS_F32, LOSS_BF16 or LOSS_F16) calls rnnt_transducer_loss_elem instead: logits and grad hold elements of that type."""
     B, T, U1, V = shape
     tg, ll, tl = _loss_args(targets, logit_lens, target_lens, B, U1 - 1)
-    rc = load().rnnt_transducer_loss(logits_ptr, _np_ptr(tg) if tg.size else None, _np_ptr(ll), _np_ptr(tl), B, T, U1 - 1, V, blank,
-                                     int(bool(fused_log_softmax)), float(clamp), nll_ptr, grad_ptr, work_ptr, work_bytes, stream)
-    _loss_chk(rc, "rnnt_transducer_loss", B, T, U1 - 1, V, blank)
+    head = (logits_ptr, _np_ptr(tg) if tg.size else None, _np_ptr(ll), _np_ptr(tl), B, T, U1 - 1, V, blank)
+    tail = (int(bool(fused_log_softmax)), float(clamp), nll_ptr, grad_ptr, work_ptr, work_bytes, stream)
+    if elem is None:
+        _loss_chk(load().rnnt_transducer_loss(*head, *tail), "rnnt_transducer_loss", B, T, U1 - 1, V, blank)
+    else:
+        _loss_chk(load().rnnt_transducer_loss_elem(*head, int(elem), *tail), f"rnnt_transducer_loss_elem(elem={elem})", B, T, U1 - 1, V, blank)
 
 
 def wave_stage_host(carry, samples_so_far, new, final, n_fft=1024):

@@ -760,6 +760,21 @@ int rnnt_transducer_loss(const float* logits_dev, const int32_t* targets_host, c
                          const int32_t* target_lens_host, int32_t B, int32_t T, int32_t Umax, int32_t V, int32_t blank,
                          int32_t fused_log_softmax, float clamp, double* nll_dev, float* grad_dev, void* workspace_dev,
                          int64_t workspace_bytes, void* stream);
+/* rnnt_transducer_loss over a lattice of 16-bit elements, read and written as such: elem names the type of logits_dev AND grad_dev
+ * (RNNT_LOSS_F32 float, RNNT_LOSS_BF16 bfloat16, RNNT_LOSS_F16 IEEE half), every other argument is rnnt_transducer_loss's.  Each
+ * element is widened to float32 exactly on load; lse, picks, p_k, g_k and the clamp are the float32 arithmetic above, the
+ * recursions f64; g_k is rounded ONCE, to nearest even, to the element type at the store (zeros outside the valid cells).  nll_dev
+ * stays double [B]; the workspace and rnnt_transducer_loss_workspace do not depend on elem.  A 16-bit row is single elements up to
+ * the first 16-byte boundary, vectors of 8, single elements (at most 7 either side), so logits_dev and grad_dev are 16-byte aligned
+ * as before.  elem = RNNT_LOSS_F32 IS rnnt_transducer_loss (which forwards here): the same launches, the same bits.  Refusals as
+ * rnnt_transducer_loss, plus an elem that is none of the three: RNNT_ERR_ARG, decided first, before any pointer is followed. */
+#define RNNT_LOSS_F32 0
+#define RNNT_LOSS_BF16 1
+#define RNNT_LOSS_F16 2
+int rnnt_transducer_loss_elem(const void* logits_dev, const int32_t* targets_host, const int32_t* logit_lens_host,
+                              const int32_t* target_lens_host, int32_t B, int32_t T, int32_t Umax, int32_t V, int32_t blank,
+                              int32_t elem, int32_t fused_log_softmax, float clamp, double* nll_dev, void* grad_dev,
+                              void* workspace_dev, int64_t workspace_bytes, void* stream);
 /* The same loss as a pure C++ function (no context, no GPU), f64 throughout over the float32 logits: logits_host as logits_dev,
  * nll_host [B] double, grad_host NULL or double [B, T, Umax + 1, V] (0 outside the valid cells).  Same ranges and refusals, without
  * the alignment and workspace ones; a refused call writes nothing. */
