@@ -1,8 +1,9 @@
-"""rnnt_loss: the transducer loss with gradients, torchaudio.functional.rnnt_loss's signature over librnnt_hip.so.
+"""rnnt_loss and transducer_joint: the training-side functions over librnnt_hip.so.
 
-CUDA tensors run rnnt_transducer_loss (float32) or rnnt_transducer_loss_elem (bfloat16, float16: the lattice is read and the
-gradient written in 16 bits) on torch's current stream; CPU tensors run rnnt_transducer_loss_host, the plain C++ twin.  There is
-no eager-PyTorch path."""
+rnnt_loss: the transducer loss with gradients, torchaudio.functional.rnnt_loss's signature.  CUDA tensors run rnnt_transducer_loss
+(float32) or rnnt_transducer_loss_elem (bfloat16, float16: the lattice is read and the gradient written in 16 bits) on torch's
+current stream; CPU tensors run rnnt_transducer_loss_host, the plain C++ twin.  transducer_joint / TransducerJoint: the joint
+lattice in front of it with its backward (rnnt_joint_lattice_forward / _backward).  There is no eager-PyTorch path on the device."""
 import numpy as np
 import torch
 
@@ -77,3 +78,108 @@ def rnnt_loss(logits, targets, logit_lengths, target_lengths, blank=-1, clamp=-1
     V = logits.size(-1)
     costs = _RnntLoss.apply(logits, targets, logit_lengths, target_lengths, V - 1 if blank == -1 else int(blank), float(clamp), bool(fused_log_softmax))
     return costs if reduction == "none" else (costs.mean() if reduction == "mean" else costs.sum())
+
+
+# ---- the joint lattice with gradients (rnnt_joint_lattice_forward / _backward) ---------------------------------------------------
+def _aligned(t):
+    """contiguous and 16-byte aligned (a view into a larger tensor may start anywhere)"""
+    t = t.detach().contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def _lens_np(lens):
+    return None if lens is None else (lens.detach().cpu().numpy() if isinstance(lens, torch.Tensor) else np.asarray(lens)).astype(np.int32)
+
+
+class _TransducerJoint(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, e, p, w, b, logit_lengths, target_lengths):
+        B, T, D = e.shape
+        U1, V = p.shape[1], w.shape[0]
+        ea, pa, wa, ba = _aligned(e), _aligned(p), _aligned(w), _aligned(b)
+        if ea.is_cuda:
+            with torch.cuda.device(ea.device):
+                nbytes = rlib.joint_lattice_workspace(B, T, U1, V)
+                work = torch.empty(nbytes, dtype=torch.uint8, device=ea.device)
+                out = torch.empty(B, T, U1, V, dtype=torch.float32, device=ea.device)
+                rlib.joint_lattice_forward_device(ea.data_ptr(), pa.data_ptr(), wa.data_ptr(), ba.data_ptr(), (B, T, U1, V), out.data_ptr(),
+                                                  work.data_ptr(), nbytes, torch.cuda.current_stream().cuda_stream)
+        else:                                                      # the host side is f64 like every host twin, one batch row at a time
+            rlib.joint_lattice_workspace(B, T, U1, V)              # the same refusals as on the device
+            w64, b64 = wa.double(), ba.double()
+            out = torch.stack([(torch.tanh(ea[i].double().unsqueeze(1) + pa[i].double().unsqueeze(0)) @ w64.T + b64).float() for i in range(B)])
+        ctx.save_for_backward(e, p, w, b)
+        ctx.lens = (_lens_np(logit_lengths), _lens_np(target_lengths))
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        e, p, w, b = ctx.saved_tensors
+        B, T, _ = e.shape
+        U1, V = p.shape[1], w.shape[0]
+        ll, tl = ctx.lens
+        ea, pa, wa, ga = _aligned(e), _aligned(p), _aligned(w), _aligned(grad_out.to(torch.float32))
+        if ea.is_cuda:
+            with torch.cuda.device(ea.device):
+                nbytes = rlib.joint_lattice_workspace(B, T, U1, V)
+                work = torch.empty(nbytes, dtype=torch.uint8, device=ea.device)
+                de, dp, dw, db = torch.empty_like(ea), torch.empty_like(pa), torch.empty_like(wa), torch.empty(V, dtype=torch.float32, device=ea.device)
+                rlib.joint_lattice_backward_device(ea.data_ptr(), pa.data_ptr(), wa.data_ptr(), ga.data_ptr(), ll, tl, (B, T, U1, V), de.data_ptr(),
+                                                   dp.data_ptr(), dw.data_ptr(), db.data_ptr(), work.data_ptr(), nbytes,
+                                                   torch.cuda.current_stream().cuda_stream)
+        else:
+            de, dp, dw, db = (torch.from_numpy(a.astype(np.float32)) for a in
+                              rlib.joint_lattice_backward_host(ea.numpy(), pa.numpy(), wa.numpy(), ga.numpy(), ll, tl))
+        return de, dp, dw, db, None, None
+
+
+def transducer_joint(enc_proj, pred_proj, weight, bias, logit_lengths=None, target_lengths=None):
+    """The joint lattice of the reference's TransducerJoint (prejoin linear, add, tanh) behind its two projections, differentiable:
+    logits[b, t, u, :] = tanh(enc_proj[b, t, :] + pred_proj[b, u, :]) @ weight.T + bias, float32 [B, T, U1, V].
+
+    enc_proj [B, T, 256] = joint.enc_ffn(encoder output), pred_proj [B, U1, 256] = joint.pred_ffn(predictor output), weight [V, 256] and
+    bias [V] = joint.ffn_out's; V a multiple of 4 in 4..416.  All four float32 on one device: CUDA tensors run rnnt_joint_lattice_forward
+    and, in .backward(), rnnt_joint_lattice_backward on torch's current stream (bf16x3 MFMAs, bit-for-bit repeatable); CPU tensors run
+    the float64 host side (rnnt_joint_lattice_backward_host for the gradients).  Neither tanh(e + p) nor e + p is ever stored: the
+    backward recomputes tanh from the four inputs, which are all that is saved.
+
+    logit_lengths [B] (frames per row) and target_lengths [B] (labels per row), as given to rnnt_loss: when present the backward never
+    reads the incoming gradient at cells with t >= T_b or u > U_b (rnnt_loss writes exact zeros there; another caller's padding may
+    hold anything) and they contribute nothing.  The forward writes every cell either way.
+
+    Any dtype but float32: TypeError.  A refused call (V out of range, a length out of range, too many cells) raises RnntError with the
+    library's status code."""
+    for name, t in (("enc_proj", enc_proj), ("pred_proj", pred_proj), ("weight", weight), ("bias", bias)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise TypeError(f"transducer_joint: {name} must be a float32 tensor, got {getattr(t, 'dtype', type(t))}")
+    D = rlib.JOINT_D
+    if enc_proj.dim() != 3 or pred_proj.dim() != 3 or weight.dim() != 2 or bias.dim() != 1 or enc_proj.size(2) != D or pred_proj.size(2) != D or \
+            weight.size(1) != D or pred_proj.size(0) != enc_proj.size(0) or bias.size(0) != weight.size(0):
+        raise RnntError(f"transducer_joint: want enc_proj [B, T, {D}], pred_proj [B, U1, {D}], weight [V, {D}], bias [V]; got "
+                        f"{tuple(enc_proj.shape)}, {tuple(pred_proj.shape)}, {tuple(weight.shape)}, {tuple(bias.shape)}", rlib.ERR_ARG)
+    if len({t.device for t in (enc_proj, pred_proj, weight, bias)}) != 1:
+        raise RnntError("transducer_joint: the four tensors must be on one device", rlib.ERR_ARG)
+    B = enc_proj.size(0)
+    for name, lens, hi in (("logit_lengths", logit_lengths, enc_proj.size(1)), ("target_lengths", target_lengths, pred_proj.size(1) - 1)):
+        if lens is not None:                                       # refused at the forward, not first in the backward
+            a = _lens_np(lens)
+            if a.shape != (B,) or (a < (1 if name == "logit_lengths" else 0)).any() or (a > hi).any():
+                raise RnntError(f"transducer_joint: {name} must be [{B}] values up to {hi}, got {a.tolist()}", rlib.ERR_ARG)
+    return _TransducerJoint.apply(enc_proj, pred_proj, weight, bias, logit_lengths, target_lengths)
+
+
+class TransducerJoint(torch.nn.Module):
+    """The reference's TransducerJoint (model/component/joint.py) in its one trained configuration -- prejoin linear, add, tanh, no
+    postjoin linear -- with the reference's parameter names (enc_ffn, pred_ffn, ffn_out), so its `joint.*` checkpoint entries load.
+    The two small projections are nn.Linear (torch autograd); the lattice and its backward are transducer_joint."""
+
+    def __init__(self, vocab_size, enc_output_size, pred_output_size, join_dim=256):
+        super().__init__()
+        if join_dim != rlib.JOINT_D:
+            raise RnntError(f"TransducerJoint: the lattice kernels are built for join_dim {rlib.JOINT_D}, got {join_dim}", rlib.ERR_SHAPE)
+        self.enc_ffn = torch.nn.Linear(enc_output_size, join_dim)
+        self.pred_ffn = torch.nn.Linear(pred_output_size, join_dim)
+        self.ffn_out = torch.nn.Linear(join_dim, vocab_size)
+
+    def forward(self, enc_out, pred_out, logit_lengths=None, target_lengths=None):
+        return transducer_joint(self.enc_ffn(enc_out), self.pred_ffn(pred_out), self.ffn_out.weight, self.ffn_out.bias, logit_lengths, target_lengths)

@@ -115,6 +115,10 @@ SIGNATURES = {
     "rnnt_transducer_loss_elem": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.c_float, c_vp, c_vp, c_vp, c_i64,
                                           c_vp]),
     "rnnt_transducer_loss_host": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.c_float, c_vp, c_vp]),
+    "rnnt_joint_lattice_workspace": (c_i32, [c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_i64)]),
+    "rnnt_joint_lattice_forward": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp]),
+    "rnnt_joint_lattice_backward": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "rnnt_joint_lattice_backward_host": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "rnnt_rescore_select_host": (c_i32, [c_i32, c_vp, c_vp, ctypes.c_double, ctypes.c_double, c_vp, c_i32p]),
     "rnnt_stream_keep_frames": (c_i32, [c_vp, c_i32, c_i32, c_vp]),
     "rnnt_stream_get_frames": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32p, c_vp]),
@@ -535,6 +539,65 @@ def transducer_loss_device(logits_ptr, shape, targets, logit_lens, target_lens, 
         _loss_chk(load().rnnt_transducer_loss(*head, *tail), "rnnt_transducer_loss", B, T, U1 - 1, V, blank)
     else:
         _loss_chk(load().rnnt_transducer_loss_elem(*head, int(elem), *tail), f"rnnt_transducer_loss_elem(elem={elem})", B, T, U1 - 1, V, blank)
+
+
+_JOINT_REFUSALS = {ERR_ARG: "a null or misaligned pointer, B, T or U1 < 1, or a length outside its range",
+                   ERR_SHAPE: "V outside 4..416 or not a multiple of 4, too many cells, or a workspace too small"}
+JOINT_D = 256                                    # the joint width the lattice kernels are built for
+
+
+def _joint_chk(rc, what, B, T, U1, V):
+    if rc != 0:
+        raise RnntError(f"{what}: {_JOINT_REFUSALS.get(rc, 'HIP failure')} (B={B} T={T} U1={U1} V={V}; status {rc})", rc)
+
+
+def _joint_lens(lens, B, what):
+    if lens is None:
+        return None
+    a = np.ascontiguousarray(lens, np.int32)
+    if a.shape != (B,):
+        raise RnntError(f"{what}: {B} rows, but lengths of shape {a.shape}", ERR_ARG)
+    return a
+
+
+def joint_lattice_workspace(B, T, U1, V):
+    """rnnt_joint_lattice_workspace: bytes of the device workspace one forward or backward call of this shape needs."""
+    n = c_i64(0)
+    _joint_chk(load().rnnt_joint_lattice_workspace(B, T, U1, V, ctypes.byref(n)), "rnnt_joint_lattice_workspace", B, T, U1, V)
+    return int(n.value)
+
+
+def joint_lattice_forward_device(e_ptr, p_ptr, w_ptr, b_ptr, shape, logits_ptr, work_ptr, work_bytes, stream=None):
+    """rnnt_joint_lattice_forward over device pointers; shape = (B, T, U1, V).  Launches on `stream` and returns."""
+    B, T, U1, V = shape
+    _joint_chk(load().rnnt_joint_lattice_forward(e_ptr, p_ptr, w_ptr, b_ptr, B, T, U1, V, logits_ptr, work_ptr, work_bytes, stream),
+               "rnnt_joint_lattice_forward", B, T, U1, V)
+
+
+def joint_lattice_backward_device(e_ptr, p_ptr, w_ptr, g_ptr, logit_lens, target_lens, shape, de_ptr, dp_ptr, dw_ptr, db_ptr, work_ptr, work_bytes,
+                                  stream=None):
+    """rnnt_joint_lattice_backward over device pointers; shape = (B, T, U1, V), logit_lens / target_lens host arrays or None."""
+    B, T, U1, V = shape
+    ll, tl = _joint_lens(logit_lens, B, "rnnt_joint_lattice_backward"), _joint_lens(target_lens, B, "rnnt_joint_lattice_backward")
+    rc = load().rnnt_joint_lattice_backward(e_ptr, p_ptr, w_ptr, g_ptr, None if ll is None else _np_ptr(ll), None if tl is None else _np_ptr(tl), B, T, U1, V,
+                                            de_ptr, dp_ptr, dw_ptr, db_ptr, work_ptr, work_bytes, stream)
+    _joint_chk(rc, "rnnt_joint_lattice_backward", B, T, U1, V)
+
+
+def joint_lattice_backward_host(e, p, w, g, logit_lens=None, target_lens=None, out=None):
+    """rnnt_joint_lattice_backward_host (no context, no GPU): e [B, T, 256], p [B, U1, 256], w [V, 256], g [B, T, U1, V] float32 ->
+    (de, dp, dw, db) float64.  out: four float64 arrays to write into (a refused call leaves them alone).  Raises RnntError on a refusal."""
+    e, p, w, g = (np.ascontiguousarray(a, np.float32) for a in (e, p, w, g))
+    B, T, U1, V = g.shape
+    if e.shape != (B, T, JOINT_D) or p.shape != (B, U1, JOINT_D) or w.shape != (V, JOINT_D):
+        raise RnntError(f"rnnt_joint_lattice_backward_host: g {g.shape} wants e {(B, T, JOINT_D)}, p {(B, U1, JOINT_D)}, w {(V, JOINT_D)}; "
+                        f"got {e.shape}, {p.shape}, {w.shape}", ERR_ARG)
+    ll, tl = _joint_lens(logit_lens, B, "rnnt_joint_lattice_backward_host"), _joint_lens(target_lens, B, "rnnt_joint_lattice_backward_host")
+    de, dp, dw, db = out if out is not None else (np.zeros(e.shape), np.zeros(p.shape), np.zeros(w.shape), np.zeros(V))
+    rc = load().rnnt_joint_lattice_backward_host(_np_ptr(e), _np_ptr(p), _np_ptr(w), _np_ptr(g), None if ll is None else _np_ptr(ll),
+                                                 None if tl is None else _np_ptr(tl), B, T, U1, V, _np_ptr(de), _np_ptr(dp), _np_ptr(dw), _np_ptr(db))
+    _joint_chk(rc, "rnnt_joint_lattice_backward_host", B, T, U1, V)
+    return de, dp, dw, db
 
 
 def wave_stage_host(carry, samples_so_far, new, final, n_fft=1024):

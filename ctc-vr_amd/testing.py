@@ -1021,3 +1021,85 @@ def encoder_stream_ref(np_sd, x, plan, dtype=None):
     finally:
         torch.set_num_threads(threads)
     return out
+
+
+# ---- the joint lattice with gradients: float64 yardstick and the device path's arithmetic contract (tests) -----------------------
+JR_PRESCALE = np.float32(2.8853900817779268)      # 2 log2(e): rnnt_joint.hip.h
+
+
+def joint_live_cells(B, T, U1, logit_lens=None, target_lens=None):
+    """[B, T, U1] bool: the cells a joint backward with these lengths reads (all of them without lengths)."""
+    live = np.ones((B, T, U1), bool)
+    for b in range(B):
+        if logit_lens is not None:
+            live[b, int(logit_lens[b]):] = False
+        if target_lens is not None:
+            live[b, :, int(target_lens[b]) + 1:] = False
+    return live
+
+
+def joint_backward_ref(e, p, w, g, logit_lens=None, target_lens=None):
+    """(de, dp, dW, db) float64 by torch autograd of tanh(e.unsqueeze(2) + p.unsqueeze(1)) @ W.T + b in float64 on the CPU for a given
+    g = d loss / d logits [B, T, U1, V]; with lengths, g outside the live cells is taken as 0 whatever it holds."""
+    import torch
+    g = np.asarray(g)
+    B, T, U1, V = g.shape
+    live = joint_live_cells(B, T, U1, logit_lens, target_lens)
+    g64 = torch.from_numpy(np.where(live[..., None], g, 0.0).astype(np.float64))
+    e64, p64, w64 = (torch.from_numpy(np.asarray(a, np.float32).astype(np.float64)).requires_grad_(True) for a in (e, p, w))
+    b64 = torch.zeros(V, dtype=torch.float64, requires_grad=True)
+    out = torch.tanh(e64.unsqueeze(2) + p64.unsqueeze(1)) @ w64.T + b64
+    out.backward(g64)
+    return tuple(a.grad.numpy() for a in (e64, p64, w64, b64))
+
+
+def _bf16_planes(x):
+    x32 = np.ascontiguousarray(np.asarray(x, np.float32))
+    hi = _round16(x32, "bf16")
+    return hi, _round16(x32 - hi, "bf16")
+
+
+def _mm_bf16x3(a, b):
+    """a [m, k] @ b [k, n] as the bf16x3 MFMA forms it: both operands as two bf16 planes (split_planes_ref's), the three products
+    lo hi + hi lo + hi hi, each product exact in float32 and accumulated in float32 (three float32 matrix products)."""
+    ah, al = _bf16_planes(a)
+    bh, bl = _bf16_planes(b)
+    return ((al @ bh) + (ah @ bl)) + (ah @ bh)
+
+
+def joint_tanh_f32(e, p):
+    """tanh(e + p) [B, T, U1, 256] as the lattice kernels form it, in float32: t = JR_PRESCALE e + JR_PRESCALE p (each product
+    rounded), h = 1 - 2 / (exp2(t) + 1) -- exp2 overflow gives exactly 1, underflow exactly -1."""
+    e32, p32 = np.asarray(e, np.float32), np.asarray(p, np.float32)
+    with np.errstate(over="ignore"):
+        t = (JR_PRESCALE * e32)[:, :, None, :] + (JR_PRESCALE * p32)[:, None, :, :]
+        return (np.float32(1.0) - np.float32(2.0) / (np.exp2(t) + np.float32(1.0))).astype(np.float32)
+
+
+def joint_forward_emulation(e, p, w, b):
+    """The forward's arithmetic contract on the CPU: float32 tanh, the bf16x3 contraction with W, plus the bias; [B, T, U1, V] float32."""
+    h = joint_tanh_f32(e, p)
+    B, T, U1, D_ = h.shape
+    w32 = np.asarray(w, np.float32)
+    return (_mm_bf16x3(h.reshape(-1, D_), w32.T) + np.asarray(b, np.float32)).reshape(B, T, U1, w32.shape[0])
+
+
+def joint_backward_emulation(e, p, w, g, logit_lens=None, target_lens=None):
+    """The arithmetic contract of rnnt_joint_lattice_backward on the CPU, (de, dp, dW, db) float32: dh = g W and dW = g^T h as bf16x3
+    contractions (operand planes via the split_planes_ref rounding, float32 products accumulated in float32), float32 tanh as the
+    forward forms it, 1 - h^2 and dz in float32, and the sums over u (de), t (dp) and the cells (db) as plain float32 chains in
+    memory order.  Its distance from joint_backward_ref is what this arithmetic costs; the device, which adds in another (fixed)
+    order, is held to a small multiple of it.  Cells outside the lengths enter as g = 0, h = 0."""
+    g = np.asarray(g)
+    B, T, U1, V = g.shape
+    live = joint_live_cells(B, T, U1, logit_lens, target_lens)[..., None]
+    g0 = np.where(live, g, np.float32(0.0)).astype(np.float32).reshape(-1, V)
+    h = np.where(live, joint_tanh_f32(e, p), np.float32(0.0)).astype(np.float32)
+    w32 = np.asarray(w, np.float32)
+    dh = _mm_bf16x3(g0, w32).reshape(h.shape)
+    dz = np.where(live, dh * (np.float32(1.0) - h * h), np.float32(0.0)).astype(np.float32)
+    de = np.cumsum(dz, axis=2, dtype=np.float32)[:, :, -1]
+    dp = np.cumsum(dz, axis=1, dtype=np.float32)[:, -1]
+    dw = _mm_bf16x3(g0.T, h.reshape(-1, h.shape[-1]))
+    db = np.cumsum(g0, axis=0, dtype=np.float32)[-1]
+    return de, dp, dw, db

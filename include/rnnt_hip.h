@@ -782,6 +782,43 @@ int rnnt_transducer_loss_host(const float* logits_host, const int32_t* targets_h
                               const int32_t* target_lens_host, int32_t B, int32_t T, int32_t Umax, int32_t V, int32_t blank,
                               int32_t fused_log_softmax, float clamp, double* nll_host, double* grad_host);
 
+/* -- the joint lattice with gradients, for training (TransducerJoint.forward, model/component/joint.py:48-69, prejoin linear / add /
+ * tanh): the step in front of rnnt_transducer_loss.  No context, no finalized weights: the weights are the trainer's own float32
+ * tensors and change every step.  With e = joint.enc_ffn(enc) [B, T, 256], p = joint.pred_ffn(pred) [B, U1, 256], W = joint.ffn_out.weight
+ * [V, 256], b = joint.ffn_out.bias [V], M = B T U1 cells (u fastest):
+ *   forward   logits[b,t,u,:] = tanh(e[b,t,:] + p[b,u,:]) W^T + b   [B, T, U1, V] float32: pack_joint_w packs W into the workspace,
+ *             joint_prescale forms JR_PRESCALE e and JR_PRESCALE p there, and the unchanged joint_lattice_rows<2, false, false> (bf16x3,
+ *             raw logits) writes the lattice: tanh(e + p) exists in registers only.
+ *   backward  for g = d loss / d logits [B, T, U1, V] float32:  h = tanh(e + p) recomputed as the forward formed it, dh = g W,
+ *             dz = dh (1 - h^2), d_e[b,t,:] = sum_u dz, d_p[b,u,:] = sum_t dz, dW[v,k] = sum_m g[m,v] h[m,k], db[v] = sum_m g[m,v],
+ *             all float32, every element written.  Both contractions are bf16x3 MFMAs (two bf16 planes per operand, three products,
+ *             float32 accumulation: bf16 planes keep the exponent range a gradient scaled by 1 / B needs); tanh, 1 - h^2 and the
+ *             sums over u, t and cells are float32.  No atomics: sums that cross workgroups go through partial slabs in the workspace
+ *             and are added in a fixed order, so two calls on the same inputs agree bit for bit.  Nothing of M x 256 or M x V
+ *             elements is written.  logit_lens_host [B] (T_b in [1, T]) and target_lens_host [B] (U_b in [0, U1 - 1]) may each be NULL
+ *             (every frame / every u counts); cells with t >= T_b or u > U_b are never read in g and contribute exact zeros.
+ * Ranges (joint_lattice_rows'): the joint width is 256; 4 <= V <= 416 with V % 4 == 0; M < 2^31 - 64.  Every device pointer is 16-byte
+ * aligned.  The workspace serves either direction (the backward does not need the forward's contents):
+ *   bytes = 425984 + 4 max(256 B (T + U1) + 4,  4 ceil(B / 2) + 256 (NUB B T + NC B U1 + NS V) + NS V)   with
+ *   NUB = ceil(U1 / 16), TC = 4 ceil(ceil(T / max(1, floor(512 / (B NUB)))) / 4), NC = ceil(T / TC),
+ *   CS = 32 ceil(ceil(M / 32) / max(1, floor(512 / ceil(V / 64)))), NS = ceil(M / CS)
+ * (NS V 1 KiB <= 32 MiB + V KiB whatever M).  A call allocates nothing and synchronises nothing: launches (and the backward's one
+ * upload of the lengths, from pageable memory) on `stream`.  Refusals, decided on the host before the first launch, changing nothing:
+ * a null or misaligned pointer, B, T or U1 < 1, a length outside its range: RNNT_ERR_ARG; V outside its range, M too large, a
+ * workspace too small: RNNT_ERR_SHAPE. */
+int rnnt_joint_lattice_workspace(int32_t B, int32_t T, int32_t U1, int32_t V, int64_t* bytes_out);
+int rnnt_joint_lattice_forward(const float* e_dev, const float* p_dev, const float* w_dev, const float* b_dev, int32_t B, int32_t T,
+                               int32_t U1, int32_t V, float* logits_dev, void* workspace_dev, int64_t workspace_bytes, void* stream);
+int rnnt_joint_lattice_backward(const float* e_dev, const float* p_dev, const float* w_dev, const float* g_dev,
+                                const int32_t* logit_lens_host, const int32_t* target_lens_host, int32_t B, int32_t T, int32_t U1,
+                                int32_t V, float* de_dev, float* dp_dev, float* dw_dev, float* db_dev, void* workspace_dev,
+                                int64_t workspace_bytes, void* stream);
+/* The backward as a pure C++ function (no context, no GPU): f64 throughout over the float32 inputs, outputs double [B, T, 256],
+ * [B, U1, 256], [V, 256], [V].  Same ranges and refusals, without the alignment and workspace ones; a refused call writes nothing. */
+int rnnt_joint_lattice_backward_host(const float* e_host, const float* p_host, const float* w_host, const float* g_host,
+                                     const int32_t* logit_lens_host, const int32_t* target_lens_host, int32_t B, int32_t T, int32_t U1,
+                                     int32_t V, double* de_host, double* dp_host, double* dw_host, double* db_host);
+
 /* -- two-pass decoding: a cheap first pass yields n-best, the transducer likelihood re-scores it (the reference's WeNet layer:
  * Transducer.transducer_attention_rescoring with _cal_transducer_score, wenet/transducer/transducer.py:160-185, 261-395) ------- */
 /* rnnt_transducer_nll for N hypotheses per utterance WITHOUT repeating the utterance's frames N times: nll_host[b][n] is what
