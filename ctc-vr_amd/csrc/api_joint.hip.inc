@@ -155,8 +155,10 @@ int rnnt_joint_lattice_backward(const float* e_dev, const float* p_dev, const fl
 }
 #undef JOINT_HIPCHK
 
-// The same gradients in plain C++ (no GPU): f64 throughout over the float32 inputs, cell by cell in memory order.
-int rnnt_joint_lattice_backward_host(const float* e_host, const float* p_host, const float* w_host, const float* g_host, const int32_t* logit_lens_host,
+// The same gradients in plain C++ (no GPU): f64 throughout over the float32 inputs, cell by cell in memory order.  g of type G (float:
+// rnnt_joint_lattice_backward_host; double: the gradient rnnt_joint_loss_host forms for itself).
+extern "C++" template <typename G>
+static int joint_backward_host_cells(const float* e_host, const float* p_host, const float* w_host, const G* g_host, const int32_t* logit_lens_host,
                                      const int32_t* target_lens_host, int32_t B, int32_t T, int32_t U1, int32_t V, double* de_host, double* dp_host,
                                      double* dw_host, double* db_host) {
     if (!e_host || !p_host || !w_host || !g_host || !de_host || !dp_host || !dw_host || !db_host) return RNNT_ERR_ARG;
@@ -177,7 +179,7 @@ int rnnt_joint_lattice_backward_host(const float* e_host, const float* p_host, c
             for (int u = 0; u <= Ub; ++u) {
                 const float* er = e_host + ((size_t)b * T + t) * Dn;
                 const float* pr = p_host + ((size_t)b * U1 + u) * Dn;
-                const float* gr = g_host + (((size_t)b * T + t) * U1 + u) * V;
+                const G* gr = g_host + (((size_t)b * T + t) * U1 + u) * V;
                 for (size_t k = 0; k < Dn; ++k) { h[k] = tanh((double)er[k] + (double)pr[k]); dh[k] = 0.0; }
                 for (int v = 0; v < V; ++v) {
                     const double gv = (double)gr[v];
@@ -196,4 +198,10 @@ int rnnt_joint_lattice_backward_host(const float* e_host, const float* p_host, c
             }
     }
     return RNNT_OK;
+}
+
+int rnnt_joint_lattice_backward_host(const float* e_host, const float* p_host, const float* w_host, const float* g_host, const int32_t* logit_lens_host,
+                                     const int32_t* target_lens_host, int32_t B, int32_t T, int32_t U1, int32_t V, double* de_host, double* dp_host,
+                                     double* dw_host, double* db_host) {
+    return joint_backward_host_cells<float>(e_host, p_host, w_host, g_host, logit_lens_host, target_lens_host, B, T, U1, V, de_host, dp_host, dw_host, db_host);
 }

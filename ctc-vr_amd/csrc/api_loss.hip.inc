@@ -109,10 +109,12 @@ int rnnt_transducer_loss(const float* logits_dev, const int32_t* targets_host, c
 }
 #undef LOSS_HIPCHK
 
-// The same loss in plain C++ (no GPU): f64 throughout over the float32 logits, row by row.
-int rnnt_transducer_loss_host(const float* logits_host, const int32_t* targets_host, const int32_t* logit_lens_host, const int32_t* target_lens_host,
-                              int32_t B, int32_t T, int32_t Umax, int32_t V, int32_t blank, int32_t fused_log_softmax, float clamp, double* nll_host,
-                              double* grad_host) {
+// The same loss in plain C++ (no GPU): f64 throughout over logits of type X (float: rnnt_transducer_loss_host; double: the lattice
+// rnnt_joint_loss_host forms for itself), row by row.
+extern "C++" template <typename X>
+static int loss_host_rows(const X* logits_host, const int32_t* targets_host, const int32_t* logit_lens_host, const int32_t* target_lens_host,
+                          int32_t B, int32_t T, int32_t Umax, int32_t V, int32_t blank, int32_t fused_log_softmax, float clamp, double* nll_host,
+                          double* grad_host) {
     int rc;
     if ((rc = loss_check(logits_host, targets_host, logit_lens_host, target_lens_host, B, T, Umax, V, blank, nll_host))) return rc;
     const int U1 = Umax + 1;
@@ -125,12 +127,12 @@ int rnnt_transducer_loss_host(const float* logits_host, const int32_t* targets_h
     std::vector<double> lse(cells), pb(cells), pl(cells), al(cells), be(cells);
     for (int b = 0; b < B; ++b) {
         const int Tb = logit_lens_host[b], Ub = target_lens_host[b];
-        const float* lb = logits_host + (size_t)b * cells * V;
+        const X* lb = logits_host + (size_t)b * cells * V;
         const int32_t* yb = targets_host + (size_t)b * Umax;
         auto at = [&](int t, int u) { return (size_t)t * U1 + u; };
         for (int t = 0; t < Tb; ++t)
             for (int u = 0; u <= Ub; ++u) {
-                const float* x = lb + at(t, u) * V;
+                const X* x = lb + at(t, u) * V;
                 double l = 0.0;
                 if (fused_log_softmax) {
                     double mx = ninf, sum = 0.0;
@@ -166,7 +168,7 @@ int rnnt_transducer_loss_host(const float* logits_host, const int32_t* targets_h
                     continue;
                 }
                 const size_t c = at(t, u);
-                const float* x = lb + c * V;
+                const X* x = lb + c * V;
                 const double occ = exp(al[c] + be[c] - logZ);
                 double tb = 0.0, tl = 0.0;
                 if (t < Tb - 1) tb = exp(al[c] + pb[c] + be[at(t + 1, u)] - logZ);
@@ -182,4 +184,11 @@ int rnnt_transducer_loss_host(const float* logits_host, const int32_t* targets_h
             }
     }
     return RNNT_OK;
+}
+
+int rnnt_transducer_loss_host(const float* logits_host, const int32_t* targets_host, const int32_t* logit_lens_host, const int32_t* target_lens_host,
+                              int32_t B, int32_t T, int32_t Umax, int32_t V, int32_t blank, int32_t fused_log_softmax, float clamp, double* nll_host,
+                              double* grad_host) {
+    return loss_host_rows<float>(logits_host, targets_host, logit_lens_host, target_lens_host, B, T, Umax, V, blank, fused_log_softmax, clamp, nll_host,
+                                 grad_host);
 }

@@ -65,7 +65,7 @@ struct JointRP {
     const float* p;              // [B*U][256]  JR_PRESCALE * joint.pred_ffn(pred)
     const unsigned char* wfrag;  // pack_joint_w stream: [16 or 8 stages][26 pieces][64 lanes][8 x 16 bit]
     const float* bias;           // [V]
-    float* out;                  // [M][V]
+    float* out;                  // [M][V]; the lse form (LSE = true): lse [M]
     long long M;                 // B*T*U
     int T, U, V;
     int ntiles;                  // ceil(M / 64)
@@ -164,9 +164,11 @@ __device__ __forceinline__ void jr_vmcnt0() { asm volatile("s_waitcnt vmcnt(0)" 
 // values the transducer recursion reads leave the chip -- 8 bytes per lattice row instead of 4 V.  Column v of a row sits in tile
 // v / 16, lane group (v % 16) / 4, register v % 4; it is selected by compile-time-unrolled compares (a dynamic index would send
 // the accumulators to scratch) and stored by the lane that owns it.  Bitwise the values the LSM form writes at those columns.
-template <int NSPLIT, bool F16, bool LSM, bool PICK = false>
+// LSE (with PICK): the row's log-sum-exp, which the epilogue forms anyway, is stored too -- `out` (free in the pick form) is lse [M].
+template <int NSPLIT, bool F16, bool LSM, bool PICK = false, bool LSE = false>
 __global__ __launch_bounds__(256, JR_WGS_PER_CU) void joint_lattice_rows(JointRP P) {
     static_assert(!PICK || LSM, "the pick form is defined on the log-softmax");
+    static_assert(!LSE || PICK, "the lse store belongs to the pick form");
     constexpr bool LO = NSPLIT == 2;
     constexpr int NSTG = LO ? 16 : 8;                          // ring stages per row tile
     constexpr int TPS = LO ? 13 : 26;                          // vocabulary tiles per stage
@@ -331,6 +333,9 @@ __global__ __launch_bounds__(256, JR_WGS_PER_CU) void joint_lattice_rows(JointRP
             const float lse = mx + __logf(sm);                 // log_softmax = x - logsumexp(x)
 #pragma unroll
             for (int t = 0; t < JR_NT; ++t) { acc[t][0] -= lse; acc[t][1] -= lse; acc[t][2] -= lse; acc[t][3] -= lse; }
+            if constexpr (LSE) {
+                if (kq == 0 && m < P.M) stg1(P.out + m, lse);
+            }
         }
         JR_STAMP(3);                                           // epilogue arithmetic
         if constexpr (PICK) {

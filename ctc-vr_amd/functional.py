@@ -3,7 +3,9 @@
 rnnt_loss: the transducer loss with gradients, torchaudio.functional.rnnt_loss's signature.  CUDA tensors run rnnt_transducer_loss
 (float32) or rnnt_transducer_loss_elem (bfloat16, float16: the lattice is read and the gradient written in 16 bits) on torch's
 current stream; CPU tensors run rnnt_transducer_loss_host, the plain C++ twin.  transducer_joint / TransducerJoint: the joint
-lattice in front of it with its backward (rnnt_joint_lattice_forward / _backward).  There is no eager-PyTorch path on the device."""
+lattice in front of it with its backward (rnnt_joint_lattice_forward / _backward).  transducer_joint_loss / TransducerJoint.loss: the
+two fused, so that no [B, T, U1, V] tensor exists on the device (rnnt_joint_loss_forward / _backward).  There is no eager-PyTorch path
+on the device."""
 import numpy as np
 import torch
 
@@ -168,10 +170,102 @@ def transducer_joint(enc_proj, pred_proj, weight, bias, logit_lengths=None, targ
     return _TransducerJoint.apply(enc_proj, pred_proj, weight, bias, logit_lengths, target_lengths)
 
 
+# ---- the fused joint and loss (rnnt_joint_loss_forward / _backward): no [B, T, U1, V] tensor on the device ------------------------
+class _TransducerJointLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, e, p, w, b, targets, logit_lengths, target_lengths, blank, clamp):
+        B, T, D = e.shape
+        U1, V = p.shape[1], w.shape[0]
+        ea, pa, wa, ba = _aligned(e), _aligned(p), _aligned(w), _aligned(b)
+        tg = targets.detach().cpu().numpy().astype(np.int32)
+        if tg.shape != (B, U1 - 1):
+            raise RnntError(f"transducer_joint_loss: pred_proj {tuple(p.shape)} wants targets of shape {(B, U1 - 1)}, got {tg.shape}", rlib.ERR_ARG)
+        ll, tl = _lens_np(logit_lengths), _lens_np(target_lengths)
+        if ea.is_cuda:
+            with torch.cuda.device(ea.device):
+                wbytes, sbytes = rlib.joint_loss_workspace(B, T, U1, V)
+                work = torch.empty(wbytes, dtype=torch.uint8, device=ea.device)
+                state = torch.empty(sbytes, dtype=torch.uint8, device=ea.device)
+                nll = torch.empty(B, dtype=torch.float64, device=ea.device)
+                rlib.joint_loss_forward_device(ea.data_ptr(), pa.data_ptr(), wa.data_ptr(), ba.data_ptr(), tg, ll, tl, (B, T, U1, V), blank, nll.data_ptr(),
+                                               state.data_ptr(), sbytes, work.data_ptr(), wbytes, torch.cuda.current_stream().cuda_stream)
+            ctx.save_for_backward(e, p, w, b, state)
+        else:                                                      # the float64 host twin: there the lattice and its gradient exist
+            nll = torch.from_numpy(rlib.joint_loss_host(ea.numpy(), pa.numpy(), wa.numpy(), ba.numpy(), tg, ll, tl, blank, clamp)[0])
+            ctx.save_for_backward(e, p, w, b)
+        ctx.tg = tg
+        ctx.args = (ll, tl, blank, clamp)
+        return nll.to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        e, p, w, b = ctx.saved_tensors[:4]
+        B, T, _ = e.shape
+        U1, V = p.shape[1], w.shape[0]
+        ll, tl, blank, clamp = ctx.args
+        ea, pa, wa, ba = _aligned(e), _aligned(p), _aligned(w), _aligned(b)
+        if ea.is_cuda:
+            with torch.cuda.device(ea.device):
+                scale = _aligned(grad_out.float())
+                wbytes, sbytes = rlib.joint_loss_workspace(B, T, U1, V)
+                work = torch.empty(wbytes, dtype=torch.uint8, device=ea.device)
+                de, dp, dw, db = torch.empty_like(ea), torch.empty_like(pa), torch.empty_like(wa), torch.empty(V, dtype=torch.float32, device=ea.device)
+                state = ctx.saved_tensors[4]
+                rlib.joint_loss_backward_device(ea.data_ptr(), pa.data_ptr(), wa.data_ptr(), ba.data_ptr(), state.data_ptr(), sbytes, scale.data_ptr(), clamp,
+                                                (B, T, U1, V), blank, de.data_ptr(), dp.data_ptr(), dw.data_ptr(), db.data_ptr(), work.data_ptr(), wbytes,
+                                                torch.cuda.current_stream().cuda_stream)
+        else:
+            outs = rlib.joint_loss_host(ea.numpy(), pa.numpy(), wa.numpy(), ba.numpy(), ctx.tg, ll, tl, blank, clamp, grad_out.detach().double().numpy())[1]
+            de, dp, dw, db = (torch.from_numpy(a.astype(np.float32)) for a in outs)
+        return de, dp, dw, db, None, None, None, None, None
+
+
+def transducer_joint_loss(enc_proj, pred_proj, weight, bias, targets, logit_lengths, target_lengths, blank=-1, clamp=-1.0, reduction="mean"):
+    """rnnt_loss(transducer_joint(enc_proj, pred_proj, weight, bias), targets, logit_lengths, target_lengths, ...) as ONE differentiable
+    function that never stores the [B, T, U1, V] lattice or its gradient on the device.
+
+    enc_proj [B, T, 256], pred_proj [B, Umax + 1, 256], weight [V, 256], bias [V] float32 as for transducer_joint (V a multiple of 4 in
+    4..416, Umax <= 255); targets [B, Umax], logit_lengths [B], target_lengths [B], blank (-1: V - 1), clamp and reduction as for
+    rnnt_loss.  Returns float32 costs, [B] or reduced.
+
+    CUDA tensors: the forward runs rnnt_joint_loss_forward on torch's current stream (the lattice kernel keeps a cell's vocabulary row
+    in registers and leaves two picked log-probabilities and lse per cell; the f64 recursions follow) and computes no gradient.  It
+    saves the four inputs and one `state` tensor of 16 bytes per cell plus the lengths and targets.  The backward runs
+    rnnt_joint_loss_backward with the incoming gradient [B] as the per-row scale: the logits are recomputed in registers (bf16x3
+    MFMAs), g = clamp(d nll_b / d logits) * grad_out[b] is formed there and contracted at once.  Bit-for-bit repeatable.
+    The recomputed logits differ from the forward's in summation order only.
+
+    CPU tensors run rnnt_joint_loss_host, which composes the float64 host sides of the joint forward, rnnt_transducer_loss_host, the
+    scaling and rnnt_joint_lattice_backward_host with nothing rounded between them (forward and backward each run it): on the CPU the
+    lattice and its gradient DO exist, in float64, inside that call.
+
+    Any dtype but float32: TypeError.  A refused call (shapes, V, a length or label out of range, the blank inside a transcript,
+    Umax > 255, ...) raises RnntError with the library's status code."""
+    for name, t in (("enc_proj", enc_proj), ("pred_proj", pred_proj), ("weight", weight), ("bias", bias)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise TypeError(f"transducer_joint_loss: {name} must be a float32 tensor, got {getattr(t, 'dtype', type(t))}")
+    if reduction not in REDUCTIONS:
+        raise ValueError(f"transducer_joint_loss: reduction must be one of {REDUCTIONS}, got {reduction!r}")
+    D = rlib.JOINT_D
+    if enc_proj.dim() != 3 or pred_proj.dim() != 3 or weight.dim() != 2 or bias.dim() != 1 or enc_proj.size(2) != D or pred_proj.size(2) != D or \
+            weight.size(1) != D or pred_proj.size(0) != enc_proj.size(0) or bias.size(0) != weight.size(0):
+        raise RnntError(f"transducer_joint_loss: want enc_proj [B, T, {D}], pred_proj [B, U1, {D}], weight [V, {D}], bias [V]; got "
+                        f"{tuple(enc_proj.shape)}, {tuple(pred_proj.shape)}, {tuple(weight.shape)}, {tuple(bias.shape)}", rlib.ERR_ARG)
+    if len({t.device for t in (enc_proj, pred_proj, weight, bias)}) != 1:
+        raise RnntError("transducer_joint_loss: the four tensors must be on one device", rlib.ERR_ARG)
+    if targets is None or logit_lengths is None or target_lengths is None:
+        raise RnntError("transducer_joint_loss: targets, logit_lengths and target_lengths are required", rlib.ERR_ARG)
+    V = weight.size(0)
+    costs = _TransducerJointLoss.apply(enc_proj, pred_proj, weight, bias, targets, logit_lengths, target_lengths, V - 1 if blank == -1 else int(blank),
+                                       float(clamp))
+    return costs if reduction == "none" else (costs.mean() if reduction == "mean" else costs.sum())
+
+
 class TransducerJoint(torch.nn.Module):
     """The reference's TransducerJoint (model/component/joint.py) in its one trained configuration -- prejoin linear, add, tanh, no
     postjoin linear -- with the reference's parameter names (enc_ffn, pred_ffn, ffn_out), so its `joint.*` checkpoint entries load.
-    The two small projections are nn.Linear (torch autograd); the lattice and its backward are transducer_joint."""
+    The two small projections are nn.Linear (torch autograd); the lattice and its backward are transducer_joint; `loss` is the lattice
+    and the transducer loss in one, transducer_joint_loss."""
 
     def __init__(self, vocab_size, enc_output_size, pred_output_size, join_dim=256):
         super().__init__()
@@ -183,3 +277,9 @@ class TransducerJoint(torch.nn.Module):
 
     def forward(self, enc_out, pred_out, logit_lengths=None, target_lengths=None):
         return transducer_joint(self.enc_ffn(enc_out), self.pred_ffn(pred_out), self.ffn_out.weight, self.ffn_out.bias, logit_lengths, target_lengths)
+
+    def loss(self, enc_out, pred_out, targets, logit_lengths, target_lengths, **kw):
+        """The transducer loss of this joint's lattice without the lattice: the two projections, then transducer_joint_loss (blank, clamp
+        and reduction as keywords)."""
+        return transducer_joint_loss(self.enc_ffn(enc_out), self.pred_ffn(pred_out), self.ffn_out.weight, self.ffn_out.bias, targets, logit_lengths,
+                                     target_lengths, **kw)

@@ -119,6 +119,12 @@ SIGNATURES = {
     "rnnt_joint_lattice_forward": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp]),
     "rnnt_joint_lattice_backward": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "rnnt_joint_lattice_backward_host": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "rnnt_joint_loss_workspace": (c_i32, [c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
+    "rnnt_joint_loss_forward": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "rnnt_joint_loss_host": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.c_float, c_vp, c_vp, c_vp, c_vp,
+                                     c_vp, c_vp]),
+    "rnnt_joint_loss_backward": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, ctypes.c_float, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp,
+                                         c_vp, c_i64, c_vp]),
     "rnnt_rescore_select_host": (c_i32, [c_i32, c_vp, c_vp, ctypes.c_double, ctypes.c_double, c_vp, c_i32p]),
     "rnnt_stream_keep_frames": (c_i32, [c_vp, c_i32, c_i32, c_vp]),
     "rnnt_stream_get_frames": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32p, c_vp]),
@@ -598,6 +604,62 @@ def joint_lattice_backward_host(e, p, w, g, logit_lens=None, target_lens=None, o
                                                  None if tl is None else _np_ptr(tl), B, T, U1, V, _np_ptr(de), _np_ptr(dp), _np_ptr(dw), _np_ptr(db))
     _joint_chk(rc, "rnnt_joint_lattice_backward_host", B, T, U1, V)
     return de, dp, dw, db
+
+
+_JOINT_LOSS_REFUSALS = {ERR_ARG: "a null or misaligned pointer, B or T < 1, or a blank, length or label outside its range",
+                        ERR_SHAPE: "V outside 4..416 or not a multiple of 4, Umax > 255, too many cells, or a workspace or state too small"}
+
+
+def _joint_loss_chk(rc, what, B, T, U1, V, blank):
+    if rc != 0:
+        raise RnntError(f"{what}: {_JOINT_LOSS_REFUSALS.get(rc, 'HIP failure')} (B={B} T={T} U1={U1} V={V} blank={blank}; status {rc})", rc)
+
+
+def joint_loss_workspace(B, T, U1, V):
+    """rnnt_joint_loss_workspace: (work_bytes, state_bytes) of the device buffers a fused joint-and-loss call of this shape needs."""
+    wb, sb = c_i64(0), c_i64(0)
+    _joint_loss_chk(load().rnnt_joint_loss_workspace(B, T, U1, V, ctypes.byref(wb), ctypes.byref(sb)), "rnnt_joint_loss_workspace", B, T, U1, V, "-")
+    return int(wb.value), int(sb.value)
+
+
+def joint_loss_forward_device(e_ptr, p_ptr, w_ptr, b_ptr, targets, logit_lens, target_lens, shape, blank, nll_ptr, state_ptr, state_bytes, work_ptr,
+                              work_bytes, stream=None):
+    """rnnt_joint_loss_forward over device pointers; shape = (B, T, Umax + 1, V), targets [B, Umax], logit_lens and target_lens [B] host
+    arrays; nll [B] float64.  Launches on `stream` and returns: no synchronisation."""
+    B, T, U1, V = shape
+    tg, ll, tl = _loss_args(targets, logit_lens, target_lens, B, U1 - 1)
+    rc = load().rnnt_joint_loss_forward(e_ptr, p_ptr, w_ptr, b_ptr, _np_ptr(tg) if tg.size else None, _np_ptr(ll), _np_ptr(tl), B, T, U1 - 1, V, blank,
+                                        nll_ptr, state_ptr, state_bytes, work_ptr, work_bytes, stream)
+    _joint_loss_chk(rc, "rnnt_joint_loss_forward", B, T, U1, V, blank)
+
+
+def joint_loss_backward_device(e_ptr, p_ptr, w_ptr, b_ptr, state_ptr, state_bytes, row_scale_ptr, clamp, shape, blank, de_ptr, dp_ptr, dw_ptr, db_ptr,
+                               work_ptr, work_bytes, stream=None):
+    """rnnt_joint_loss_backward over device pointers; shape = (B, T, Umax + 1, V), the state a forward of the same arguments left,
+    row_scale [B] float32 on the device.  Launches on `stream` and returns: no host arrays, no upload, no synchronisation."""
+    B, T, U1, V = shape
+    rc = load().rnnt_joint_loss_backward(e_ptr, p_ptr, w_ptr, b_ptr, state_ptr, state_bytes, row_scale_ptr, float(clamp), B, T, U1 - 1, V, blank,
+                                         de_ptr, dp_ptr, dw_ptr, db_ptr, work_ptr, work_bytes, stream)
+    _joint_loss_chk(rc, "rnnt_joint_loss_backward", B, T, U1, V, blank)
+
+
+def joint_loss_host(e, p, w, b, targets, logit_lens, target_lens, blank, clamp=-1.0, row_scale=None):
+    """rnnt_joint_loss_host (no context, no GPU): e [B, T, 256], p [B, Umax + 1, 256], w [V, 256], b [V] float32 -> nll [B] float64, and
+    with row_scale [B] also (de, dp, dw, db) float64 of sum_b row_scale[b] nll_b.  Float64 throughout; the lattice exists on the host."""
+    e, p, w, b = (np.ascontiguousarray(a, np.float32) for a in (e, p, w, b))
+    B, T, U1, V = e.shape[0], e.shape[1], p.shape[1], w.shape[0]
+    if e.shape != (B, T, JOINT_D) or p.shape != (B, U1, JOINT_D) or w.shape != (V, JOINT_D) or b.shape != (V,):
+        raise RnntError(f"rnnt_joint_loss_host: want e [B, T, {JOINT_D}], p [B, U1, {JOINT_D}], w [V, {JOINT_D}], b [V]; got {e.shape}, {p.shape}, "
+                        f"{w.shape}, {b.shape}", ERR_ARG)
+    tg, ll, tl = _loss_args(targets, logit_lens, target_lens, B, U1 - 1)
+    nll = np.zeros(B, np.float64)
+    rs = None if row_scale is None else np.ascontiguousarray(row_scale, np.float64).reshape(B)
+    outs = None if rs is None else (np.zeros(e.shape), np.zeros(p.shape), np.zeros(w.shape), np.zeros(V))
+    rc = load().rnnt_joint_loss_host(_np_ptr(e), _np_ptr(p), _np_ptr(w), _np_ptr(b), _np_ptr(tg) if tg.size else None, _np_ptr(ll), _np_ptr(tl), B, T, U1 - 1,
+                                     V, blank, float(clamp), None if rs is None else _np_ptr(rs), _np_ptr(nll),
+                                     *((None,) * 4 if outs is None else (_np_ptr(a) for a in outs)))
+    _joint_loss_chk(rc, "rnnt_joint_loss_host", B, T, U1, V, blank)
+    return nll, outs
 
 
 def wave_stage_host(carry, samples_so_far, new, final, n_fft=1024):

@@ -819,6 +819,48 @@ int rnnt_joint_lattice_backward_host(const float* e_host, const float* p_host, c
                                      const int32_t* logit_lens_host, const int32_t* target_lens_host, int32_t B, int32_t T, int32_t U1,
                                      int32_t V, double* de_host, double* dp_host, double* dw_host, double* db_host);
 
+/* -- the fused transducer joint and loss: train without the [B, T, U1, V] lattice ------------------------------------------------ */
+/* nll_b = the transducer loss (rnnt_transducer_loss, fused log-softmax) of logits[b,t,u,:] = tanh(e[b,t,:] + p[b,u,:]) W^T + bias
+ * (rnnt_joint_lattice_forward), and in a second call its gradients, with neither the lattice nor its gradient ever stored: the
+ * lattice is recomputed in registers three times (forward, d_e / d_p, dW / db).  Context-free, the caller's buffers, a stream; no
+ * allocation, no synchronisation.  U1 = Umax + 1, M = B T U1 cells.
+ *   forward   pack_joint_w, joint_prescale, the pick form of joint_lattice_rows (bf16x3) storing per cell the two picked
+ *             log-probabilities and lse, transducer_alpha_beta (f64), loss_coef.  nll_dev [B] f64 = -beta[0,0]; the cross-check
+ *             -(alpha[T_b-1,U_b] + pick) lies at the head of the workspace ([B] f64).  `state` receives what the backward needs:
+ *             coef [M][4] floats (lse, occupancy, blank term, label term) and the device copy of lengths and targets.
+ *   backward  g = clamp(d nll_b / d logits) row_scale[b] (clamp <= 0: none; the order of rnnt_transducer_loss followed by a scaling)
+ *             is formed in registers from the recomputed logits and `state`, and contracted as in rnnt_joint_lattice_backward:
+ *             de [B, T, 256], dp [B, U1, 256], dw [V, 256], db [V] float32, every element written.  row_scale_dev [B] float32 is
+ *             d loss / d nll_b on the device (dW and db sum over batch rows, so it cannot be applied afterwards).  No host arrays,
+ *             no upload.  No atomics: two calls on the same inputs agree bit for bit.  Cells with t >= T_b or u > U_b contribute
+ *             exact zeros and neither e, p nor state of such a cell is read.
+ * Ranges (the intersection of the two families): the joint width is 256; 4 <= V <= 416 with V % 4 == 0; Umax <= 255; M < 2^31 - 64;
+ * blank in [0, V); labels in [0, V) and never the blank; T_b in [1, T], U_b in [0, Umax].  Every device pointer is 16-byte aligned.
+ *   state_bytes = 16 M + 16 ceil((2 B + B max(Umax, 1)) / 4)
+ *   work_bytes  = max(8 (B + B % 2) + 16 M + 425984 + 4 (256 B (T + U1) + 4 + 2 M + 4 ceil(M / 4)),
+ *                     65536 ceil(V / 32) + 4 (256 (NUB B T + NC B U1 + NS V) + NS V))       (NUB, NC, NS of rnnt_joint_lattice_workspace)
+ * Neither holds a term in M V.  Refusals, decided on the host before the first launch, changing nothing: a null or misaligned
+ * pointer, B or T < 1, Umax < 0, a blank, length or label outside its range: RNNT_ERR_ARG; V outside its range, Umax > 255, M too
+ * large, state_bytes or work_bytes too small: RNNT_ERR_SHAPE. */
+int rnnt_joint_loss_workspace(int32_t B, int32_t T, int32_t U1, int32_t V, int64_t* work_bytes, int64_t* state_bytes);
+int rnnt_joint_loss_forward(const float* e_dev, const float* p_dev, const float* w_dev, const float* b_dev, const int32_t* targets_host,
+                            const int32_t* logit_lens_host, const int32_t* target_lens_host, int32_t B, int32_t T, int32_t Umax,
+                            int32_t V, int32_t blank, double* nll_dev, void* state_dev, int64_t state_bytes, void* work_dev,
+                            int64_t work_bytes, void* stream);
+int rnnt_joint_loss_backward(const float* e_dev, const float* p_dev, const float* w_dev, const float* b_dev, const void* state_dev,
+                             int64_t state_bytes, const float* row_scale_dev, float clamp, int32_t B, int32_t T, int32_t Umax,
+                             int32_t V, int32_t blank, float* de_dev, float* dp_dev, float* dw_dev, float* db_dev, void* work_dev,
+                             int64_t work_bytes, void* stream);
+/* The same function in plain C++ (no context, no GPU): float64 throughout over the float32 inputs -- the host sides of the lattice,
+ * of rnnt_transducer_loss_host and of rnnt_joint_lattice_backward_host composed with nothing rounded between them (on the host the
+ * lattice and its gradient exist, in f64).  row_scale_host [B] f64, or NULL: nll_host [B] only, the four outputs untouched.  Outputs
+ * double [B, T, 256], [B, U1, 256], [V, 256], [V].  Same ranges and refusals, without the alignment, state and workspace ones; a
+ * refused call writes nothing. */
+int rnnt_joint_loss_host(const float* e_host, const float* p_host, const float* w_host, const float* b_host, const int32_t* targets_host,
+                         const int32_t* logit_lens_host, const int32_t* target_lens_host, int32_t B, int32_t T, int32_t Umax, int32_t V,
+                         int32_t blank, float clamp, const double* row_scale_host, double* nll_host, double* de_host, double* dp_host,
+                         double* dw_host, double* db_host);
+
 /* -- two-pass decoding: a cheap first pass yields n-best, the transducer likelihood re-scores it (the reference's WeNet layer:
  * Transducer.transducer_attention_rescoring with _cal_transducer_score, wenet/transducer/transducer.py:160-185, 261-395) ------- */
 /* rnnt_transducer_nll for N hypotheses per utterance WITHOUT repeating the utterance's frames N times: nll_host[b][n] is what
