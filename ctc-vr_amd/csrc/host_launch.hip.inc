@@ -45,7 +45,8 @@ enum { TAG_NONE = 0, TAG_CONV1 = 1, TAG_CONV2 = 2, TAG_EMBED = 3, TAG_FFN1 = 4, 
        TAG_CTC_PREFIX = 45,                           // CTC prefix beam search: ctc_prefix_search, one launch per call
        TAG_CTC_PREFIX_POOL = 46, TAG_CTC_PREFIX_PACK = 47,     // its resumable form per slot of the stream pool: ctc_prefix_search_pool / ctc_prefix_pack
        TAG_WAVE_STAGE = 48,                           // streaming front-end of the stream pool: wave_stage of rnnt_pool_wave
-       TAG_PREFIX_STEP_POOL = 49, TAG_PREFIX_MERGE_POOL = 50 };   // prefix beam search per slot of the stream pool: prefix_step_pool / prefix_merge_pool, one launch each per frame
+       TAG_PREFIX_STEP_POOL = 49, TAG_PREFIX_MERGE_POOL = 50,     // prefix beam search per slot of the stream pool: prefix_step_pool / prefix_merge_pool, one launch each per frame
+       TAG_CTC_LOSS_PICK = 51, TAG_CTC_LOSS_RECURSION = 52, TAG_CTC_LOSS_OCC = 53, TAG_CTC_LOSS_GRAD = 54 };   // rnnt_ctc_loss: ctc_loss_pick / ctc_alpha_beta / ctc_loss_occ / ctc_loss_grad, one launch each per call
 
 struct ProfScope {   // records a start/stop event pair around one launch when its site is selected
     rnnt_ctx* ctx; hipStream_t s; bool on;

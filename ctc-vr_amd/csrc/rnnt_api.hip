@@ -409,6 +409,7 @@ extern "C" {
 #include "api_ops.hip.inc"
 #include "api_score.hip.inc"
 #include "api_loss.hip.inc"
+#include "api_ctc_loss.hip.inc"
 #include "api_joint.hip.inc"
 #include "api_joint_loss.hip.inc"
 #include "api_state.hip.inc"

@@ -1,11 +1,12 @@
-"""rnnt_loss and transducer_joint: the training-side functions over librnnt_hip.so.
+"""rnnt_loss, transducer_joint and ctc_loss: the training-side functions over librnnt_hip.so.
 
 rnnt_loss: the transducer loss with gradients, torchaudio.functional.rnnt_loss's signature.  CUDA tensors run rnnt_transducer_loss
 (float32) or rnnt_transducer_loss_elem (bfloat16, float16: the lattice is read and the gradient written in 16 bits) on torch's
 current stream; CPU tensors run rnnt_transducer_loss_host, the plain C++ twin.  transducer_joint / TransducerJoint: the joint
 lattice in front of it with its backward (rnnt_joint_lattice_forward / _backward).  transducer_joint_loss / TransducerJoint.loss: the
-two fused, so that no [B, T, U1, V] tensor exists on the device (rnnt_joint_loss_forward / _backward).  There is no eager-PyTorch path
-on the device."""
+two fused, so that no [B, T, U1, V] tensor exists on the device (rnnt_joint_loss_forward / _backward).  ctc_loss / CTCHead: the CTC term of the reference's
+objective, torch.nn.functional.ctc_loss's signature (rnnt_ctc_loss / rnnt_ctc_loss_elem / rnnt_ctc_loss_host).  There is no
+eager-PyTorch path on the device."""
 import numpy as np
 import torch
 
@@ -283,3 +284,132 @@ class TransducerJoint(torch.nn.Module):
         and reduction as keywords)."""
         return transducer_joint_loss(self.enc_ffn(enc_out), self.pred_ffn(pred_out), self.ffn_out.weight, self.ffn_out.bias, targets, logit_lengths,
                                      target_lengths, **kw)
+
+
+# ---- the CTC loss with gradients (rnnt_ctc_loss): torch.nn.functional.ctc_loss's signature ----------------------------------------
+def _ctc_strides(x):
+    """(stride_b, stride_t) in elements of a [T, B, V] tensor whose frames rnnt_ctc_loss can address as they lie, else None"""
+    T, B, V = x.shape
+    st, sb, sv = x.stride()
+    if B == 1:
+        sb = max(sb, T * st) if T > 1 else V
+    if T == 1:
+        st = B * sb
+    if (V > 1 and sv != 1) or sb < V or st < V or not (sb >= T * st or st >= B * sb):
+        return None
+    return None if x.data_ptr() % 16 else (sb, st)
+
+
+class _CtcLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, log_probs, tg, il, tl, blank, fused_log_softmax):
+        x = log_probs.detach()
+        T, B, V = x.shape
+        if x.is_cuda:
+            strides = _ctc_strides(x)
+            if strides is None:
+                x = _aligned(x)
+                strides = (V, B * V)
+            sb, st = strides
+            with torch.cuda.device(x.device):
+                nbytes = rlib.ctc_loss_workspace(B, T, tg.shape[1])
+                work = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+                nll = torch.empty(B, dtype=torch.float64, device=x.device)
+                grad = torch.empty_strided((T, B, V), (st, sb, 1), dtype=x.dtype, device=x.device)
+                rlib.ctc_loss_device(x.data_ptr(), (B, T, V), (sb, st), tg, il, tl, blank, fused_log_softmax, nll.data_ptr(), grad.data_ptr(),
+                                     work.data_ptr(), nbytes, torch.cuda.current_stream().cuda_stream,
+                                     elem=None if x.dtype == torch.float32 else ELEMS[x.dtype])
+        else:                                                      # 16-bit input widens exactly; the f64 gradient is rounded f32 -> E
+            nll_np, grad_np = rlib.ctc_loss_host(x.float().transpose(0, 1).numpy(), tg, il, tl, blank, fused_log_softmax)
+            nll, grad = torch.from_numpy(nll_np), torch.from_numpy(grad_np.astype(np.float32)).transpose(0, 1).to(x.dtype)
+        ctx.save_for_backward(grad)
+        return nll.to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (grad,) = ctx.saved_tensors
+        if grad.dtype == torch.float32:
+            return grad * grad_out.to(grad.dtype).view(1, -1, 1), None, None, None, None, None
+        # 16 bits: the product is formed in float32 per element and rounded once; the scale itself is never rounded to 16 bits
+        return torch.mul(grad, grad_out.to(torch.float32).view(1, -1, 1), out=torch.empty_like(grad)), None, None, None, None, None
+
+
+def ctc_loss(log_probs, targets, input_lengths, target_lengths, blank=0, reduction="mean", zero_infinity=False, fused_log_softmax=False):
+    """The CTC loss of torch.nn.functional.ctc_loss, with its signature and argument conventions.
+
+    log_probs [T, B, V] float32, bfloat16 or float16; targets [B, Lmax] padded integer labels, or 1-D: the rows' labels one after the
+    other (unpacked on the host); input_lengths [B] (frames per row, 1..T); target_lengths [B] (labels per row, 0..Lmax <= 255).
+    reduction: "none" ([B]), "sum", or "mean" = mean_b(nll_b / max(L_b, 1)), torch's definition.  Returns a FLOAT32 tensor on
+    log_probs' device whatever their dtype; `.backward()` gives log_probs.grad in log_probs' dtype.
+
+    fused_log_softmax=True: `log_probs` holds LOGITS; the function takes the log-softmax itself (float32, max-subtracted) and returns
+    the gradient with respect to the logits, p_k - occupancy, so a trainer's separate log-softmax forward and backward over [T, B, V]
+    disappear.  False (torch's meaning): the input holds log-probabilities and is differentiated as it stands.
+
+    Any batch and frame strides with unit stride over V run without a copy: a contiguous [T, B, V] tensor, and the transposed view of
+    a contiguous [B, T, V] one (what the reference passes).  Anything else (or a base that is not 16-byte aligned) is made
+    contiguous.  A 16-bit input is read and its gradient written in 16 bits, each gradient element rounded once, to nearest even.
+
+    A row whose frames cannot hold its transcript has loss +inf -- 0 with zero_infinity=True -- and a gradient of EXACTLY 0 either
+    way: a deliberate departure from torch, which writes NaN into such a row unless zero_infinity is set.  Frames t >= T_b and
+    targets beyond a row's length are never read; the gradient of such frames is exactly 0.
+
+    The forward computes d nll_b / d input eagerly and saves it; the backward scales it per row.  CUDA tensors run rnnt_ctc_loss /
+    rnnt_ctc_loss_elem on torch's current stream; CPU tensors run rnnt_ctc_loss_host, the float64 C++ twin.  Any other dtype: TypeError.
+    A refused call (a length or label out of range, the blank inside a transcript, Lmax > 255, ...) raises RnntError with the
+    library's status code."""
+    if not isinstance(log_probs, torch.Tensor) or log_probs.dtype not in ELEMS:
+        raise TypeError(f"ctc_loss: log_probs must be a float32, bfloat16 or float16 tensor, got {getattr(log_probs, 'dtype', type(log_probs))}")
+    if log_probs.dim() != 3:
+        raise RnntError(f"ctc_loss: log_probs must be [T, B, V], got {tuple(log_probs.shape)}", rlib.ERR_ARG)
+    if reduction not in REDUCTIONS:
+        raise ValueError(f"ctc_loss: reduction must be one of {REDUCTIONS}, got {reduction!r}")
+    B = log_probs.size(1)
+    il, tl = _lens_np(input_lengths).reshape(-1), _lens_np(target_lengths).reshape(-1)
+    tg = _lens_np(targets)
+    if il.shape != (B,) or tl.shape != (B,):
+        raise RnntError(f"ctc_loss: {B} rows, but lengths of shapes {il.shape} and {tl.shape}", rlib.ERR_ARG)
+    if tg.ndim == 1:                                               # concatenated: row b is the next L_b labels
+        if (tl < 0).any() or int(tl.sum()) != tg.size:
+            raise RnntError(f"ctc_loss: {tg.size} concatenated targets, but target_lengths sum to {int(tl.sum())}", rlib.ERR_ARG)
+        flat, tg, at = tg, np.zeros((B, int(tl.max()) if B else 0), np.int32), 0
+        for b in range(B):
+            tg[b, :tl[b]] = flat[at:at + tl[b]]
+            at += tl[b]
+    elif tg.ndim != 2 or tg.shape[0] != B:
+        raise RnntError(f"ctc_loss: targets must be [{B}, Lmax] or 1-D, got {tg.shape}", rlib.ERR_ARG)
+    costs = _CtcLoss.apply(log_probs, np.ascontiguousarray(tg), il, tl, int(blank), bool(fused_log_softmax))
+    if zero_infinity:
+        costs = torch.where(torch.isinf(costs), torch.zeros_like(costs), costs)
+    if reduction == "none":
+        return costs
+    if reduction == "sum":
+        return costs.sum()
+    return (costs / torch.from_numpy(np.maximum(tl, 1)).to(device=costs.device, dtype=costs.dtype)).mean()
+
+
+class CTCHead(torch.nn.Module):
+    """The reference's OnlineCTC (model/online_rnnt_model.py) with its parameter name, ctc_lo, so `ctc_head.ctc_lo.*` checkpoint
+    entries load.  The projection is nn.Linear (torch autograd, the split TransducerJoint makes too); the log-softmax, the loss and
+    their backward are ctc_loss with fused_log_softmax=True over the transposed view of the logits: no [T, B, V] copy, no separate
+    log-softmax pass."""
+
+    def __init__(self, vocab_size, encoder_output_size, dropout_rate=0.0, blank_id=0):
+        super().__init__()
+        self.ctc_lo = torch.nn.Linear(encoder_output_size, vocab_size)
+        self.dropout_rate = dropout_rate
+        self.blank_id = blank_id
+
+    def forward(self, hs_pad, hlens, ys_pad, ys_lens, return_log_probs=False):
+        """hs_pad [B, T, D], hlens [B], ys_pad [B, Lmax] (anything beyond a row's length, e.g. -1), ys_lens [B] -> (loss, ys_hat): the
+        reference's loss (reduction "mean", zero_infinity) and, only when asked for, its [B, T, V] log-probabilities (else None)."""
+        logits = self.ctc_lo(torch.nn.functional.dropout(hs_pad, p=self.dropout_rate))
+        loss = ctc_loss(logits.transpose(0, 1), ys_pad, hlens, ys_lens, blank=self.blank_id, reduction="mean", zero_infinity=True,
+                        fused_log_softmax=True)
+        return loss, (logits.log_softmax(2) if return_log_probs else None)
+
+    def log_softmax(self, hs_pad):
+        return torch.nn.functional.log_softmax(self.ctc_lo(hs_pad), dim=2)
+
+    def argmax(self, hs_pad):
+        return torch.argmax(self.ctc_lo(hs_pad), dim=2)

@@ -115,6 +115,10 @@ SIGNATURES = {
     "rnnt_transducer_loss_elem": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.c_float, c_vp, c_vp, c_vp, c_i64,
                                           c_vp]),
     "rnnt_transducer_loss_host": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.c_float, c_vp, c_vp]),
+    "rnnt_ctc_loss_workspace": (c_i32, [c_i32, c_i32, c_i32, ctypes.POINTER(c_i64)]),
+    "rnnt_ctc_loss": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "rnnt_ctc_loss_elem": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "rnnt_ctc_loss_host": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "rnnt_joint_lattice_workspace": (c_i32, [c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_i64)]),
     "rnnt_joint_lattice_forward": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp]),
     "rnnt_joint_lattice_backward": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
@@ -545,6 +549,67 @@ def transducer_loss_device(logits_ptr, shape, targets, logit_lens, target_lens, 
         _loss_chk(load().rnnt_transducer_loss(*head, *tail), "rnnt_transducer_loss", B, T, U1 - 1, V, blank)
     else:
         _loss_chk(load().rnnt_transducer_loss_elem(*head, int(elem), *tail), f"rnnt_transducer_loss_elem(elem={elem})", B, T, U1 - 1, V, blank)
+
+
+_CTC_LOSS_REFUSALS = {ERR_ARG: "a length, label, blank, stride, element code or pointer outside its range",
+                      ERR_SHAPE: "Lmax > 255, too many states or a workspace too small"}
+
+
+def _ctc_loss_chk(rc, what, B, T, lmax, V, blank):
+    if rc != 0:
+        raise RnntError(f"{what}: {_CTC_LOSS_REFUSALS.get(rc, 'HIP failure')} (B={B} T={T} Lmax={lmax} V={V} blank={blank}; status {rc})", rc)
+
+
+def _ctc_loss_args(targets, logit_lens, target_lens, B):
+    tg = np.ascontiguousarray(targets, np.int32)
+    ll, tl = np.ascontiguousarray(logit_lens, np.int32), np.ascontiguousarray(target_lens, np.int32)
+    if tg.ndim != 2 or tg.shape[0] != B or ll.shape != (B,) or tl.shape != (B,):
+        raise RnntError(f"rnnt_ctc_loss: {B} rows, but targets of shape {tg.shape} and lengths of shapes {ll.shape} and {tl.shape}", ERR_ARG)
+    return tg, ll, tl
+
+
+def ctc_loss_workspace(B, T, lmax):
+    """rnnt_ctc_loss_workspace: bytes of the device workspace one rnnt_ctc_loss call of this shape needs."""
+    n = c_i64(0)
+    _ctc_loss_chk(load().rnnt_ctc_loss_workspace(B, T, lmax, ctypes.byref(n)), "rnnt_ctc_loss_workspace", B, T, lmax, "-", "-")
+    return int(n.value)
+
+
+def ctc_loss_host(logits, targets, logit_lens, target_lens, blank, fused_log_softmax=True, want_grad=True):
+    """rnnt_ctc_loss_host (no context, no GPU): logits float32, indexed [b, t, v] -- a contiguous [B, T, V] array or the transposed view
+    of a contiguous [T, B, V] one runs as it lies, anything else is copied -- targets [B, Lmax] -> (nll [B] float64, +inf for an
+    infeasible row; grad float64 indexed and laid out like the logits, or None).  Raises RnntError on a refusal."""
+    x = np.asarray(logits, np.float32)
+    B, T, V = x.shape
+    if not (x.transpose(1, 0, 2).flags.c_contiguous and B > 1 and T > 1):
+        x = np.ascontiguousarray(x)
+    tg, ll, tl = _ctc_loss_args(targets, logit_lens, target_lens, B)
+    sb, st = (T * V, V) if x.flags.c_contiguous else (V, B * V)
+    nll = np.zeros(B, np.float64)
+    grad = None
+    if want_grad:
+        grad = np.zeros((B, T, V), np.float64) if x.flags.c_contiguous else np.zeros((T, B, V), np.float64).transpose(1, 0, 2)
+    rc = load().rnnt_ctc_loss_host(_np_ptr(x), sb, st, _np_ptr(tg) if tg.size else None, _np_ptr(ll), _np_ptr(tl), B, T, tg.shape[1], V, blank,
+                                   int(bool(fused_log_softmax)), _np_ptr(nll), _np_ptr(grad) if want_grad else None)
+    _ctc_loss_chk(rc, "rnnt_ctc_loss_host", B, T, tg.shape[1], V, blank)
+    return nll, grad
+
+
+def ctc_loss_device(logits_ptr, shape, strides, targets, logit_lens, target_lens, blank, fused_log_softmax, nll_ptr, grad_ptr, work_ptr,
+                    work_bytes, stream=None, elem=None):
+    """rnnt_ctc_loss over device pointers: frame (b, t) of `shape` = (B, T, V) starts at element b * strides[0] + t * strides[1];
+    targets [B, Lmax]; nll [B] float64; grad with the logits' type and strides, or None (value only); the workspace of
+    ctc_loss_workspace(B, T, Lmax).  Launches on `stream` and returns: no synchronisation.  elem (LOSS_F32, LOSS_BF16 or LOSS_F16)
+    calls rnnt_ctc_loss_elem instead: logits and grad hold elements of that type."""
+    B, T, V = shape
+    tg, ll, tl = _ctc_loss_args(targets, logit_lens, target_lens, B)
+    lmax = tg.shape[1]
+    head = (logits_ptr, int(strides[0]), int(strides[1]), _np_ptr(tg) if tg.size else None, _np_ptr(ll), _np_ptr(tl), B, T, lmax, V, blank)
+    tail = (int(bool(fused_log_softmax)), nll_ptr, grad_ptr, work_ptr, work_bytes, stream)
+    if elem is None:
+        _ctc_loss_chk(load().rnnt_ctc_loss(*head, *tail), "rnnt_ctc_loss", B, T, lmax, V, blank)
+    else:
+        _ctc_loss_chk(load().rnnt_ctc_loss_elem(*head, int(elem), *tail), f"rnnt_ctc_loss_elem(elem={elem})", B, T, lmax, V, blank)
 
 
 _JOINT_REFUSALS = {ERR_ARG: "a null or misaligned pointer, B, T or U1 < 1, or a length outside its range",

@@ -472,6 +472,116 @@ def ctc_align_bruteforce(lp, targets, T_b, blank):
     return out
 
 
+# ---- CTC loss with gradients: float64 yardstick, the device path's arithmetic contract and the sum over all paths (tests) ---------
+def _ctc_skip(ext):
+    """skip[s]: state s may be entered from s - 2 (a label that differs from the label before it)"""
+    e = np.asarray(ext)
+    skip = np.zeros(len(e), bool)
+    skip[3::2] = e[3::2] != e[1:-2:2]
+    return skip
+
+
+def ctc_loss_ref(x, targets, T_b, blank, fused_log_softmax=True):
+    """(nll, grad) of one row by float64 torch autograd through log_softmax and the forward recursion over the extended states,
+    vectorised over the states with one step per frame.  x [T, V] (only t < T_b is read), targets: the row's L labels.  grad [T, V]
+    float64 = d nll / d x, 0 for t >= T_b.  fused_log_softmax=False: x holds log-probabilities, differentiated as they stand.  A
+    transcript the frames cannot hold: (inf, zeros)."""
+    import torch
+    full = torch.as_tensor(np.asarray(x))
+    ext = _ctc_ext(np.asarray(targets), blank)
+    S = len(ext)
+    cols = torch.as_tensor(np.asarray(ext, np.int64))
+    skip = torch.as_tensor(_ctc_skip(ext))
+    xv = full[:T_b].double().clone().requires_grad_(True)
+    lp = (torch.log_softmax(xv, -1) if fused_log_softmax else xv)[:, cols]        # [T_b, S]
+    ninf = torch.full((S,), -math.inf, dtype=torch.float64)
+
+    def lse(v):                                                    # logsumexp over dim 0 whose all -inf columns stay -inf without a NaN gradient
+        dead = torch.isinf(v.detach().max(0).values)
+        out = torch.logsumexp(torch.where(dead, torch.zeros_like(v), v), 0)
+        return torch.where(dead, torch.full_like(out, -math.inf), out)
+    alpha = torch.where(torch.arange(S) < 2, lp[0], ninf)
+    for t in range(1, T_b):
+        a1 = torch.cat([ninf[:1], alpha[:-1]])
+        a2 = torch.where(skip, torch.cat([ninf[:2], alpha[:-2]])[:S], ninf)
+        alpha = lse(torch.stack([alpha, a1, a2])) + lp[t]
+    nll = -lse(alpha[max(S - 2, 0):].unsqueeze(1))[0]
+    grad = np.zeros(tuple(full.shape), np.float64)
+    if not math.isfinite(float(nll.detach())):
+        return math.inf, grad
+    nll.backward()
+    grad[:T_b] = xv.grad.numpy()
+    return float(nll.detach()), grad
+
+
+def _ctc_lse3(a, a1, a2):
+    mx = np.maximum(a, np.maximum(a1, a2))
+    mx = np.where(np.isinf(mx), 0.0, mx)
+    with np.errstate(divide="ignore"):
+        return np.log(np.exp(a - mx) + np.exp(a1 - mx) + np.exp(a2 - mx)) + mx
+
+
+def _ctc_loss_from_lp(lp, p, ext, shape):
+    """Both recursions of rnnt_ctc_loss in float64 over lp [T_b, S] (the log-probabilities of the extended states' columns), then
+    g = p - occupancy with p [T_b, V] (zeros when the input held log-probabilities)."""
+    T_b, S = lp.shape
+    skip = _ctc_skip(ext)
+    ninf = np.full(S + 2, -math.inf)
+    al, be = np.full((T_b, S), -math.inf), np.full((T_b, S), -math.inf)
+    al[0, :2] = lp[0, :2]
+    for t in range(1, T_b):
+        prev = np.concatenate([ninf[:2], al[t - 1]])
+        al[t] = _ctc_lse3(prev[2:], prev[1:-1], np.where(skip, prev[:-2], -math.inf)) + lp[t]
+    be[T_b - 1, max(S - 2, 0):] = lp[T_b - 1, max(S - 2, 0):]
+    skip_fwd = np.concatenate([skip[2:], [False, False]])[:S]     # s -> s + 2
+    for t in range(T_b - 2, -1, -1):
+        nxt = np.concatenate([be[t + 1], ninf[:2]])
+        be[t] = _ctc_lse3(nxt[:-2], nxt[1:-1], np.where(skip_fwd, nxt[2:], -math.inf)) + lp[t]
+    nll = -_logaddexp(al[T_b - 1, S - 1], al[T_b - 1, S - 2] if S > 1 else -math.inf)
+    grad = np.zeros(shape, np.float64)
+    if not math.isfinite(nll):
+        return math.inf, grad
+    ab = al + be
+    with np.errstate(invalid="ignore"):
+        occ = np.where(np.isinf(ab), 0.0, np.exp(ab - lp + nll))
+    g = p.copy()
+    for s in range(S):                                             # ascending states, as ctc_loss_occ adds them
+        g[:, ext[s]] -= occ[:, s]
+    grad[:T_b] = g
+    return nll, grad
+
+
+def ctc_loss_f32_emulation(x, targets, T_b, blank, fused_log_softmax=True):
+    """The arithmetic contract of the device path, on the CPU: lse (torch's CPU logsumexp) and the picked values x - lse in float32,
+    everything after them -- both recursions, p_k = exp(x_k - lse), the occupancies -- in float64.  Arguments and result as
+    ctc_loss_ref.  Its distance from ctc_loss_ref is what float32 picks cost; the device is held to a small multiple of it."""
+    import torch
+    full = torch.as_tensor(np.asarray(x))
+    x32 = full[:T_b].float()
+    ext = _ctc_ext(np.asarray(targets), blank)
+    lse32 = torch.logsumexp(x32, -1) if fused_log_softmax else torch.zeros(T_b)
+    lp = (x32[:, torch.as_tensor(np.asarray(ext, np.int64))] - lse32[:, None]).double().numpy()
+    p = np.exp(x32.double().numpy() - lse32.double().numpy()[:, None]) if fused_log_softmax else np.zeros(tuple(x32.shape))
+    return _ctc_loss_from_lp(lp, p, ext, tuple(full.shape))
+
+
+def ctc_loss_bruteforce(lp, targets, T_b, blank):
+    """The same likelihood as an explicit sum over all V^T_b label sequences of T_b frames: those that collapse (merge repeats, drop
+    blanks) to the transcript, summed exactly (math.fsum) relative to the best one.  lp [T, V] log-probabilities.  inf when none does."""
+    from itertools import product
+    p = np.asarray(lp, np.float64)
+    want = [int(y) for y in targets]
+    logs = []
+    for path in product(range(p.shape[1]), repeat=T_b):
+        got = [k for i, k in enumerate(path) if k != blank and (i == 0 or k != path[i - 1])]
+        if got == want:
+            logs.append(sum(p[t, k] for t, k in enumerate(path)))
+    if not logs or max(logs) == -math.inf:
+        return math.inf
+    mx = max(logs)
+    return -(mx + math.log(math.fsum(math.exp(v - mx) for v in logs)))
+
+
 # ---- prefix beam search: one frame's merge for one utterance (tests) ------------------------------------------------------------
 def _log_add(args):
     """wenet.utils.common.log_add in the list form its prefix-beam-search call site uses."""

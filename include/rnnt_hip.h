@@ -782,6 +782,60 @@ int rnnt_transducer_loss_host(const float* logits_host, const int32_t* targets_h
                               const int32_t* target_lens_host, int32_t B, int32_t T, int32_t Umax, int32_t V, int32_t blank,
                               int32_t fused_log_softmax, float clamp, double* nll_host, double* grad_host);
 
+/* -- training: the CTC loss WITH its gradient (torch.nn.functional.ctc_loss; the reference's OnlineCTC.forward after ctc_lo,
+ * model/online_rnnt_model.py:22-32) ------------------------------------------------------------------------------------------- */
+/* Context-free like rnnt_transducer_loss: the caller's buffers and a stream, no allocation, no synchronisation, a refusal is its
+ * status code alone.  Per row b the loss is rnnt_ctc_nll's likelihood -- minus the log of the sum over all paths of T_b frames that
+ * collapse to the row's L_b labels -- over the S = 2 L_b + 1 extended states (blank, y_1, blank, .., y_L, blank), and grad is
+ * d nll_b / d input:
+ *   ctc_loss_pick: one pass over the valid frames (t < T_b): the max-subtracted float32 log-sum-exp over V (fused_log_softmax) and
+ *     pick [B, T, Lmax + 1] = (lp_blank, lp_{y_1}, .., lp_{y_L}), lp = input - lse;
+ *   ctc_alpha_beta: rnnt_ctc_nll's forward recursion and its mirror image from the last frame, both f64, both stored, each holding
+ *     its own frame's lp (torch's convention); nll_b = -logaddexp(alpha[T_b-1][S-1], alpha[T_b-1][S-2]); +inf for a transcript its
+ *     frames cannot hold (T_b < L_b + adjacent repeats);
+ *   ctc_loss_occ: occ[t, k] = sum over the states s on column k of exp(alpha_t[s] + beta_t[s] - lp[t, k] + nll_b), one thread per
+ *     (frame, distinct column) adding its states in ascending order (f64) -- a repeated label and the blank put several states on
+ *     one column; the table of columns and states is built on the host from the host targets.  No floating-point atomics;
+ *   ctc_loss_grad: g[t, k] = p_k - occ[t, k] with p_k = exp(input_k - lse) (fused), or -occ[t, k] (the input holds log-probabilities),
+ *     every element of [B, T, V] written exactly once; EXACTLY 0 for frames t >= T_b and for every frame of a row whose nll is +inf
+ *     (a deliberate departure: torch writes NaN into such a row unless zero_infinity is set).
+ * Which lane sums which columns depends on V alone, not on the strides, the alignment or the element type: two calls agree bit for
+ * bit, the three layouts below agree bit for bit, and a 16-bit input gives the nll bits of the float32 call on the widened input and
+ * that call's gradient rounded once, to nearest even.
+ *   logits_dev: device, 16-byte aligned; frame (b, t) is the V elements from element b stride_b + t stride_t (unit stride over V; the
+ *   rows themselves may start on any element).  stride_b, stride_t >= V, and stride_b >= T stride_t (a contiguous [B, T, V]) or
+ *   stride_t >= B stride_b (a contiguous [T, B, V], or the transposed view the reference passes): all run without a copy; the gradient
+ *   is written with the same strides.  elem: RNNT_LOSS_F32 / _BF16 / _F16, the type of logits_dev AND grad_dev, widened exactly on load.
+ *   targets_host [B, Lmax] int32 (may be NULL when Lmax = 0; entries beyond a row's length are never read); logit_lens_host [B] (T_b in
+ *   [1, T]); target_lens_host [B] (L_b in [0, Lmax]); V >= 2; blank in [0, V); nll_dev [B] double, device; grad_dev: NULL (value only:
+ *   the same nll bit for bit, B workgroups of the forward recursion alone, two launches) or device, 16-byte aligned; workspace_dev:
+ *   device, 16-byte aligned, at least the bytes rnnt_ctc_loss_workspace reports.  With grad_dev it begins with [B] doubles that receive
+ *   -logaddexp(beta[0][0], beta[0][1]), the same likelihood from the backward recursion (in the convention where beta leaves its own
+ *   frame out: -logaddexp(beta[0][0] + lp[0][blank], beta[0][1] + lp[0][y_1])); the rest is scratch.
+ * One upload of lengths, targets and the column tables (an asynchronous copy from pageable host memory), then four launches (two
+ * without grad_dev) on `stream`, whatever the data.  Profile tags 51 - 54 name the four launches; without a context
+ * rnnt_profile_begin cannot select them.  Refusals, all decided on the host before the first launch, changing nothing: an elem that is
+ * none of the three (decided first), a null or misaligned pointer, B < 1, T_b outside [1, T], L_b outside [0, Lmax], V < 2, blank
+ * outside [0, V), a label outside [0, V) or equal to blank inside a row's length, a stride < V, overlapping rows: RNNT_ERR_ARG;
+ * Lmax > 255, B * T * (2 Lmax + 1) >= 2^31 - 1, a workspace that is too small: RNNT_ERR_SHAPE. */
+int rnnt_ctc_loss_workspace(int32_t B, int32_t T, int32_t Lmax, int64_t* bytes_out);
+int rnnt_ctc_loss_elem(const void* logits_dev, int64_t stride_b, int64_t stride_t, const int32_t* targets_host,
+                       const int32_t* logit_lens_host, const int32_t* target_lens_host, int32_t B, int32_t T, int32_t Lmax, int32_t V,
+                       int32_t blank, int32_t elem, int32_t fused_log_softmax, double* nll_dev, void* grad_dev, void* workspace_dev,
+                       int64_t workspace_bytes, void* stream);
+/* elem = RNNT_LOSS_F32: the same launches, the same bits. */
+int rnnt_ctc_loss(const float* logits_dev, int64_t stride_b, int64_t stride_t, const int32_t* targets_host,
+                  const int32_t* logit_lens_host, const int32_t* target_lens_host, int32_t B, int32_t T, int32_t Lmax, int32_t V,
+                  int32_t blank, int32_t fused_log_softmax, double* nll_dev, float* grad_dev, void* workspace_dev,
+                  int64_t workspace_bytes, void* stream);
+/* The same loss as a pure C++ function (no context, no GPU), f64 throughout over the float32 input with the same strides: nll_host [B]
+ * double (+inf for an infeasible row), grad_host NULL or double with the input's strides (only the V elements of each frame are
+ * written; 0 in padding frames and infeasible rows).  Same ranges and refusals, without the alignment and workspace ones; a refused
+ * call writes nothing. */
+int rnnt_ctc_loss_host(const float* logits_host, int64_t stride_b, int64_t stride_t, const int32_t* targets_host,
+                       const int32_t* logit_lens_host, const int32_t* target_lens_host, int32_t B, int32_t T, int32_t Lmax, int32_t V,
+                       int32_t blank, int32_t fused_log_softmax, double* nll_host, double* grad_host);
+
 /* -- the joint lattice with gradients, for training (TransducerJoint.forward, model/component/joint.py:48-69, prejoin linear / add /
  * tanh): the step in front of rnnt_transducer_loss.  No context, no finalized weights: the weights are the trainer's own float32
  * tensors and change every step.  With e = joint.enc_ffn(enc) [B, T, 256], p = joint.pred_ffn(pred) [B, U1, 256], W = joint.ffn_out.weight
@@ -1109,6 +1163,8 @@ const float* rnnt_enc_frames_dev(rnnt_ctx* ctx, int32_t* frames_out, int32_t* st
  * calls (one launch per call), 46 ctc_prefix_search_pool of rnnt_pool_ctc_prefix_logprobs / rnnt_pool_chunk_ctc_prefix (the resumable
  * search launch), 47 ctc_prefix_pack of rnnt_stream_get_ctc_prefix (the pack launch), 48 wave_stage of rnnt_pool_wave (the staging launch),
  * 49 prefix_step_pool and 50 prefix_merge_pool of rnnt_pool_prefix_frames / rnnt_pool_chunk_prefix (one launch each per frame).
+ * (51 ctc_loss_pick, 52 ctc_alpha_beta, 53 ctc_loss_occ and 54 ctc_loss_grad name the launches of the context-free rnnt_ctc_loss;
+ * a context cannot select them.)
  * rnnt_profile_end synchronises the recorded events and returns the summed kernel time and launch count. */
 int rnnt_profile_begin(rnnt_ctx* ctx, int32_t tag);
 int rnnt_profile_end(rnnt_ctx* ctx, double* total_ms, int64_t* n_launches);
