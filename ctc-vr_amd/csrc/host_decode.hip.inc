@@ -219,8 +219,12 @@ int finish_persistent_decoder(rnnt_ctx* ctx, hipStream_t s) {
         // The early W_hh product is off the chain: wave 0 forms its share behind its XA stores (inside what used to be its XA wait, so
         // the dirty total includes it), waves 1-7 from the quarter-sum barrier on (wave 7's time: the product under full LDS contention).
         const double e0 = r[23] / 100.0 / (double)(r[22] > 0 ? r[22] : 1), e7 = r[26] / 100.0 / (double)(r[22] > 0 ? r[22] : 1);
-        fprintf(stderr, " total %.2f / %.2f; hidden early W_hh per dirty pass: wave 0 %.2f (after its XA store), wave 7 %.2f (from the quarter-sum barrier)\n",
-                sum[0] + e0, sum[1], e0, e7);
+        // Marks inside two phases of a dirty pass: the cell alone (the rest of "cell+W_c" is a barrier and the W_c partials) and the
+        // arrival of the X1 words (the rest of "wait X1" is the pp sum, the frame's tanh and the barrier).
+        const double mc = r[27] / 100.0 / (double)(r[22] > 0 ? r[22] : 1), mx = r[28] / 100.0 / (double)(r[22] > 0 ? r[22] : 1);
+        fprintf(stderr, " total %.2f / %.2f; hidden early W_hh per dirty pass: wave 0 %.2f (after its XA store), wave 7 %.2f (from the quarter-sum barrier);"
+                        " of cell+W_c the cell %.2f, of wait X1 the arrival %.2f\n",
+                sum[0] + e0, sum[1], e0, e7, mc, mx);
     }
     if (ctx->pinned[13] != 0) return fail(ctx, RNNT_ERR_STATE, "persistent decoder gave up (code %d: 1 = frame wait, 2 = greedy_multi exchange wait)", ctx->pinned[13]);
     return RNNT_OK;

@@ -367,7 +367,7 @@ __device__ __forceinline__ void st_tag(unsigned long long* p, unsigned payload, 
 #define GM_PARTS 4
 #define GM_X1 320            // words per part: 64 h' + 256 pp partials
 #define GM_WLD 260           // LDS row stride of the W_out slice (floats)
-#define GM_DBG_W 32          // stamp words per stream: [12 c + k] phase k of non-dirty (c = 0) / dirty (c = 1) passes, [12 c + 10] passes, [23] wave 0's / [26] wave 7's early W_hh product, [24] count, [25] stream
+#define GM_DBG_W 32          // stamp words per stream: [12 c + k] phase k of non-dirty (c = 0) / dirty (c = 1) passes, [12 c + 10] passes, [23] wave 0's / [26] wave 7's early W_hh product, [24] count, [25] stream, [27] / [28] marks inside the cell + W_c and the X1 phases of dirty passes
 struct DecMP : DecP {           // slots: stream group i (mailboxes i) decodes stream slots[i]
     unsigned long long* x1;      // [2][B][4][GM_X1]
     unsigned long long* xa;      // [2][B][4][2 * KF]
@@ -393,6 +393,38 @@ __device__ __forceinline__ bool gm_poll(const DecMP& p, const unsigned long long
             }
         }
     }
+}
+
+// gm_poll for the three foreign words of one gather thread: the three loads are in flight together and ONE loop spins over whichever
+// words are still missing, so a wait costs the arrival plus one L2 round trip (three gm_polls in a row are three dependent round
+// trips: no load of the second can pass the first one's spin loop).  Every word keeps what gm_poll gives it: the tag test, the abort
+// word and the wall-clock bound that sets the error and abort words.  A valid word stays valid for the whole exchange (the writer can
+// only be one exchange ahead, in the buffer of the other parity), so a word that has arrived is not read again.
+__device__ __forceinline__ bool gm_poll3(const DecMP& p, const unsigned long long* s0, const unsigned long long* s1, const unsigned long long* s2,
+                                         unsigned tag, unsigned& o0, unsigned& o1, unsigned& o2) {
+    unsigned long long v0 = ld_tag(s0), v1 = ld_tag(s1), v2 = ld_tag(s2);
+    bool m0 = (unsigned)(v0 >> 32) != tag, m1 = (unsigned)(v1 >> 32) != tag, m2 = (unsigned)(v2 >> 32) != tag;
+    if (m0 || m1 || m2) {
+        const long long t0 = (long long)__builtin_amdgcn_s_memrealtime();
+        int it = 0;
+        while (true) {
+            if (m0) v0 = ld_tag(s0);
+            if (m1) v1 = ld_tag(s1);
+            if (m2) v2 = ld_tag(s2);
+            m0 = (unsigned)(v0 >> 32) != tag; m1 = (unsigned)(v1 >> 32) != tag; m2 = (unsigned)(v2 >> 32) != tag;
+            if (!(m0 || m1 || m2)) break;
+            if ((++it & 63) == 0) {
+                if (ld_sc1i(p.ctrl + 4) != 0) return false;
+                if ((long long)__builtin_amdgcn_s_memrealtime() - t0 > p.timeout_ticks) {
+                    st_sc1i(p.ctrl + 1, 2);
+                    st_sc1i(p.ctrl + 4, 1);
+                    return false;
+                }
+            }
+        }
+    }
+    o0 = (unsigned)v0; o1 = (unsigned)v1; o2 = (unsigned)v2;
+    return true;
 }
 
 // 512 threads.  Where the 423 KB of a part's weights live: the W_out rows in LDS (107 KB for V = 412), the W_hh slice in
@@ -494,6 +526,9 @@ __global__ __launch_bounds__(512) void greedy_multi(DecMP p) {
     const bool tdbg7 = p.dbg != nullptr && pw == 0 && tid0 == 448;
 #define GM_T(k) { if (tdbg) { const long long t_ = (long long)__builtin_amdgcn_s_memrealtime(); \
                               (void)__hip_atomic_fetch_add(tsh + (dirty ? 12 : 0) + (k), t_ - tl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); tl = t_; } }
+    // A mark inside a phase: the ticks since the last stamp into word W_, the phase's own stamp untouched (word 27: the cell, of
+    // "cell + W_c"; word 28: the arrival of the X1 words, of "wait X1", whose rest is the pp sum, the tanh and the barrier).
+#define GM_TM(W_) { if (tdbg) (void)__hip_atomic_fetch_add(tsh + (W_), (long long)__builtin_amdgcn_s_memrealtime() - tl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 #if GM_WHH_REGS
     // G_ = this thread's half row of W_hh x the h buffer H_, both lanes of a row holding the same bits afterwards (the sum commutes).
     // One body for the two places that form the product, so the operand order is the same in both.  (A macro: through a lambda that
@@ -568,7 +603,7 @@ __global__ __launch_bounds__(512) void greedy_multi(DecMP p) {
         if (dirty) {
             // ---- predictor step on this part's 64 units (predictor.py:200-204), then X1 ---------------------------------------
             unsigned long long* xw = x1b + (ev1 & 1) * x1par;
-            float gi = 0.f, gf = 0.f, gg = 0.f, go = 0.f;     // gate pre-activations of this lane group's hidden unit
+            float gi = 0.f, gf = 0.f, gg = 0.f, go = 0.f;     // gate activations of this lane group's hidden unit
 #if GM_WHH_REGS
             {
                 const float eg = ldg1(p.egate + (long long)tok * (4 * RNNT_D) + 256 * pw + row2);
@@ -579,6 +614,10 @@ __global__ __launch_bounds__(512) void greedy_multi(DecMP p) {
                 // first lane takes them through DPP and no LDS round trip or barrier stands between the product and the cell:
                 // f from lane ^ 2, o from the mirror lane 7, g from the mirror of the quad swap (lane 5).
                 gi = g + eg;
+                // Each lane pair applies its own gate's activation first (tanh on the g rows, lanes 4-5; the logistic on i, f, o), so
+                // the cell below is left with one product-sum and one tanh instead of five transcendentals in a row on one lane of
+                // eight.  Same functions of the same inputs: the same bits.  From here on gi .. go hold ACTIVATIONS.
+                gi = (tid & 6) == 4 ? tanhf(gi) : sigmoidf_(gi);
                 gf = xor_partner<2>(gi);
                 go = xor_partner<4>(gi);
                 gg = xor_partner<4>(gf);
@@ -592,7 +631,7 @@ __global__ __launch_bounds__(512) void greedy_multi(DecMP p) {
             __syncthreads();
             if (cell) {
                 const float4 gt = *reinterpret_cast<const float4*>(&gates[4 * (tid >> 3)]);     // i, f, g, o of this unit
-                gi = gt.x; gf = gt.y; gg = gt.z; go = gt.w;
+                gi = sigmoidf_(gt.x); gf = sigmoidf_(gt.y); gg = tanhf(gt.z); go = sigmoidf_(gt.w);   // activations, as in the register form
             }
 #endif
             GM_T(1)
@@ -601,11 +640,12 @@ __global__ __launch_bounds__(512) void greedy_multi(DecMP p) {
 #endif
             if (cell) {
                 const int unit = 64 * pw + (tid >> 3);
-                cc2 = sigmoidf_(gf) * cc + sigmoidf_(gi) * tanhf(gg);
-                const float hn = sigmoidf_(go) * tanhf(cc2);
+                cc2 = gf * cc + gi * gg;                      // the same expression over the same values: contracts to the same fused operations
+                const float hn = go * tanhf(cc2);
                 h2[unit] = hn;
                 st_tag(xw + pw * GM_X1 + (unit - 64 * pw), __float_as_uint(hn), ev1);
             }
+            GM_TM(27)
             __syncthreads();
             {
                 float q0 = 0.f, q1 = 0.f;
@@ -626,20 +666,17 @@ __global__ __launch_bounds__(512) void greedy_multi(DecMP p) {
             }
             __syncthreads();
             GM_T(2)
-            // gather: threads 0..255 sum the four partials of pp[n] in part order; threads 256..447 fetch the other parts' h'
+            // gather: threads 0..255 sum the four partials of pp[n] in part order, the three foreign ones polled together (gm_poll3);
+            // threads 256..447 fetch the other parts' h'
             if (tid < RNNT_D) {
-                float sum = 0.f;
-#pragma unroll
-                for (int q = 0; q < GM_PARTS; ++q) {
-                    float v = mypp[tid];
-                    if (q != pw) {
-                        unsigned w = 0;
-                        if (!gm_poll(p, xw + q * GM_X1 + 64 + tid, ev1, w)) bad = true;
-                        v = __uint_as_float(w);
-                    }
-                    sum = q == 0 ? v : sum + v;
-                }
-                const float ppv = sum + bjc_r;
+                const int q0 = pw == 0 ? 1 : 0, q1 = pw <= 1 ? 2 : 1, q2 = pw <= 2 ? 3 : 2;      // the other parts, ascending
+                const unsigned long long* src = xw + 64 + tid;
+                unsigned w0 = 0, w1 = 0, w2 = 0;
+                if (!gm_poll3(p, src + q0 * GM_X1, src + q1 * GM_X1, src + q2 * GM_X1, ev1, w0, w1, w2)) bad = true;
+                GM_TM(28)
+                const float mine = mypp[tid], o0 = __uint_as_float(w0), o1 = __uint_as_float(w1), o2 = __uint_as_float(w2);
+                const float v1 = pw == 0 ? o0 : (pw == 1 ? mine : o1), v2 = pw <= 1 ? o1 : (pw == 2 ? mine : o2);
+                const float ppv = ((((pw == 0 ? mine : o0) + v1) + v2) + (pw == 3 ? mine : o2)) + bjc_r;
                 pp[tid] = ppv;
                 zs[tid] = tanhf(ppv + er[0]);                 // the one frame of this pass: its joint activations, formed by the thread that holds pp[n]
             } else if (tid < RNNT_D + 192) {
