@@ -18,6 +18,8 @@
 //   rnnt_beam      beam_chain, beam_reduce, beam_gather, log_softmax_rows
 //   rnnt_prefix    prefix_step, prefix_merge, prefix_init, prefix_pack (rnnt_prefix_beam_decode)
 //   rnnt_loss      loss_pick, transducer_alpha_beta, loss_coef, loss_grad (rnnt_transducer_loss: the loss with its gradient)
+//   rnnt_lstm      lstm_pack_whh, lstm_gemm, lstm_seq_fwd, lstm_seq_bwd, lstm_db_part, lstm_slab_reduce (rnnt_lstm_forward / _backward:
+//                  the predictor's LSTM over a whole label sequence with back-propagation through time)
 //   rnnt_misc      fill_i32, gather_att_cache, gather_cnn_cache
 #pragma once
 #include <hip/hip_runtime.h>

@@ -5,8 +5,9 @@ rnnt_loss: the transducer loss with gradients, torchaudio.functional.rnnt_loss's
 current stream; CPU tensors run rnnt_transducer_loss_host, the plain C++ twin.  transducer_joint / TransducerJoint: the joint
 lattice in front of it with its backward (rnnt_joint_lattice_forward / _backward).  transducer_joint_loss / TransducerJoint.loss: the
 two fused, so that no [B, T, U1, V] tensor exists on the device (rnnt_joint_loss_forward / _backward).  ctc_loss / CTCHead: the CTC term of the reference's
-objective, torch.nn.functional.ctc_loss's signature (rnnt_ctc_loss / rnnt_ctc_loss_elem / rnnt_ctc_loss_host).  There is no
-eager-PyTorch path on the device."""
+objective, torch.nn.functional.ctc_loss's signature (rnnt_ctc_loss / rnnt_ctc_loss_elem / rnnt_ctc_loss_host).  lstm_predictor /
+RNNPredictor: the predictor's LSTM over a whole label sequence with back-propagation through time (rnnt_lstm_forward / _backward /
+_host), under the reference's parameter names.  There is no eager-PyTorch path on the device."""
 import numpy as np
 import torch
 
@@ -413,3 +414,151 @@ class CTCHead(torch.nn.Module):
 
     def argmax(self, hs_pad):
         return torch.argmax(self.ctc_lo(hs_pad), dim=2)
+
+
+# ---- the predictor's LSTM over a whole label sequence with gradients (rnnt_lstm_forward / _backward) ------------------------------
+class _LstmPredictor(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, h0, c0, lengths):
+        B, U1, D = x.shape
+        xa, wia, wha, bia, bha = (_aligned(t) for t in (x, w_ih, w_hh, b_ih, b_hh))
+        h0a, c0a = (None if t is None else _aligned(t) for t in (h0, c0))
+        lens = _lens_np(lengths)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        if xa.is_cuda:
+            with torch.cuda.device(xa.device):
+                wbytes, sbytes = rlib.lstm_workspace(B, U1)
+                work = torch.empty(wbytes, dtype=torch.uint8, device=xa.device)
+                state = torch.empty(sbytes, dtype=torch.uint8, device=xa.device)
+                out = torch.empty(B, U1, D, dtype=torch.float32, device=xa.device)
+                hn, cn = torch.empty(B, D, dtype=torch.float32, device=xa.device), torch.empty(B, D, dtype=torch.float32, device=xa.device)
+                rlib.lstm_forward_device(xa.data_ptr(), wia.data_ptr(), wha.data_ptr(), bia.data_ptr(), bha.data_ptr(), ptr(h0a), ptr(c0a), lens, (B, U1),
+                                         out.data_ptr(), hn.data_ptr(), cn.data_ptr(), state.data_ptr(), sbytes, work.data_ptr(), wbytes,
+                                         torch.cuda.current_stream().cuda_stream)
+        else:                                                      # the float64 host twin, rounded once; it saves nothing: the backward runs it again
+            npy = lambda t: None if t is None else t.numpy()
+            out, hn, cn = (torch.from_numpy(a.astype(np.float32)) for a in
+                           rlib.lstm_host(xa.numpy(), wia.numpy(), wha.numpy(), bia.numpy(), bha.numpy(), npy(h0a), npy(c0a), lens))
+            state = torch.empty(0, dtype=torch.uint8)
+        ctx.has = (h0 is not None, c0 is not None)
+        ctx.lens = lens
+        ctx.save_for_backward(x, w_ih, w_hh, b_ih, b_hh, *(t for t in (h0, c0) if t is not None), out, state)
+        ctx.mark_non_differentiable(hn, cn)
+        return out, hn, cn
+
+    @staticmethod
+    def backward(ctx, dout, _dhn, _dcn):
+        saved = list(ctx.saved_tensors)
+        x, w_ih, w_hh, b_ih, b_hh = saved[:5]
+        state, out = saved.pop(), saved.pop()
+        rest = saved[5:]
+        h0 = rest.pop(0) if ctx.has[0] else None
+        c0 = rest.pop(0) if ctx.has[1] else None
+        B, U1, D = x.shape
+        xa, wia, wha, da = (_aligned(t) for t in (x, w_ih, w_hh, dout.to(torch.float32)))
+        h0a, c0a = (None if t is None else _aligned(t) for t in (h0, c0))
+        ptr = lambda t: None if t is None else t.data_ptr()
+        if xa.is_cuda:
+            with torch.cuda.device(xa.device):
+                wbytes, sbytes = rlib.lstm_workspace(B, U1)
+                work = torch.empty(wbytes, dtype=torch.uint8, device=xa.device)
+                new = lambda *s: torch.empty(*s, dtype=torch.float32, device=xa.device)
+                dx, dwi, dwh, db, dh0, dc0 = new(B, U1, D), new(4 * D, D), new(4 * D, D), new(4 * D), new(B, D), new(B, D)
+                rlib.lstm_backward_device(xa.data_ptr(), wia.data_ptr(), wha.data_ptr(), ptr(h0a), ptr(c0a), _aligned(out).data_ptr(), state.data_ptr(), sbytes,
+                                          da.data_ptr(), ctx.lens, (B, U1), dx.data_ptr(), dwi.data_ptr(), dwh.data_ptr(), db.data_ptr(), dh0.data_ptr(),
+                                          dc0.data_ptr(), work.data_ptr(), wbytes, torch.cuda.current_stream().cuda_stream)
+        else:
+            npy = lambda t: None if t is None else t.numpy()
+            dx, dwi, dwh, db, dh0, dc0 = (torch.from_numpy(a.astype(np.float32)) for a in
+                                          rlib.lstm_host(xa.numpy(), wia.numpy(), wha.numpy(), b_ih.detach().numpy(), b_hh.detach().numpy(), npy(h0a), npy(c0a), ctx.lens,
+                                                         dout=da.numpy())[3:])
+        return dx, dwi, dwh, db, db.clone(), dh0 if ctx.has[0] else None, dc0 if ctx.has[1] else None, None
+
+
+def lstm_predictor(x, w_ih, w_hh, b_ih, b_hh, h0=None, c0=None, lengths=None):
+    """The predictor's LSTM layer -- torch.nn.LSTM(256, 256, one layer, batch_first) -- over a whole label sequence, differentiable:
+    (out [B, U1, 256], hN [B, 256], cN [B, 256]).
+
+    x [B, U1, 256]; w_ih, w_hh [1024, 256] and b_ih, b_hh [1024] in torch.nn.LSTM's layout (gate order i, f, g, o); h0, c0 [B, 256] or
+    None (zeros); lengths [B] (valid steps per row, 1..U1; the transducer caller passes target_lengths + 1) or None.  All float32 on one
+    device.  `out` is differentiable with respect to x, the four weights, h0 and c0; hN and cN are the state after each row's last
+    valid step and are returned non-differentiable.  With lengths, x and the incoming gradient beyond a row's length are never read,
+    and out and x.grad there are exactly 0.
+
+    CUDA tensors run rnnt_lstm_forward and, in .backward(), rnnt_lstm_backward on torch's current stream: one recurrence launch each
+    whatever U1 is, float32 throughout with the inference predictor's activations, bit-for-bit repeatable.  Saved for the backward:
+    the inputs, out and one state tensor (the activated gates and c of every step, 5120 bytes per row and step).  CPU tensors run
+    rnnt_lstm_host, the float64 C++ twin (the backward runs it again instead of saving a state).
+
+    Any dtype but float32: TypeError.  Shape or device disagreements, or a length out of range: RnntError(ERR_ARG); U1 > 256:
+    RnntError(ERR_SHAPE)."""
+    named = (("x", x), ("w_ih", w_ih), ("w_hh", w_hh), ("b_ih", b_ih), ("b_hh", b_hh), ("h0", h0), ("c0", c0))
+    for name, t in named:
+        if (t is not None or name not in ("h0", "c0")) and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32):
+            raise TypeError(f"lstm_predictor: {name} must be a float32 tensor, got {getattr(t, 'dtype', type(t))}")
+    D = rlib.LSTM_D
+    B = x.size(0) if x.dim() == 3 else -1
+    if x.dim() != 3 or x.size(2) != D or tuple(w_ih.shape) != (4 * D, D) or tuple(w_hh.shape) != (4 * D, D) or tuple(b_ih.shape) != (4 * D,) or \
+            tuple(b_hh.shape) != (4 * D,) or any(t is not None and tuple(t.shape) != (B, D) for t in (h0, c0)):
+        raise RnntError(f"lstm_predictor: want x [B, U1, {D}], w_ih and w_hh [{4 * D}, {D}], b_ih and b_hh [{4 * D}], h0 and c0 [B, {D}]; got "
+                        + ", ".join(f"{n} {tuple(t.shape)}" for n, t in named if t is not None), rlib.ERR_ARG)
+    if len({t.device for _, t in named if t is not None}) != 1:
+        raise RnntError("lstm_predictor: every tensor must be on one device", rlib.ERR_ARG)
+    if lengths is not None:
+        a = _lens_np(lengths)
+        if a.shape != (B,) or (a < 1).any() or (a > x.size(1)).any():
+            raise RnntError(f"lstm_predictor: lengths must be [{B}] values in 1..{x.size(1)}, got {a.tolist()}", rlib.ERR_ARG)
+    return _LstmPredictor.apply(x, w_ih, w_hh, b_ih, b_hh, h0, c0, lengths)
+
+
+class _LstmParams(torch.nn.Module):
+    """the four parameters of a one-layer torch.nn.LSTM under its names, initialised as torch does (uniform in +-1 / sqrt(hidden))"""
+
+    def __init__(self, input_size, hidden_size):
+        super().__init__()
+        k = hidden_size ** -0.5
+        for name, shape in (("weight_ih_l0", (4 * hidden_size, input_size)), ("weight_hh_l0", (4 * hidden_size, hidden_size)),
+                            ("bias_ih_l0", (4 * hidden_size,)), ("bias_hh_l0", (4 * hidden_size,))):
+            setattr(self, name, torch.nn.Parameter(torch.empty(shape).uniform_(-k, k)))
+
+
+class RNNPredictor(torch.nn.Module):
+    """The reference's RNNPredictor (model/component/predictor.py) in its one trained configuration -- embedding 256, one LSTM layer of
+    256, projection to 256 -- with the reference's parameter names (embed.weight, rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0,
+    rnn.bias_hh_l0, projection.weight, projection.bias), so the `predictor.*` entries of a checkpoint load with strict=True.  The
+    embedding, its dropout and the projection are torch modules (the split TransducerJoint and CTCHead make too); the LSTM is
+    lstm_predictor."""
+
+    def __init__(self, voca_size, embed_size, output_size, embed_dropout, hidden_size, num_layers, bias=True, rnn_type="lstm", dropout=0.1):
+        super().__init__()
+        D = rlib.LSTM_D
+        if (embed_size, output_size, hidden_size, num_layers, bool(bias), rnn_type) != (D, D, D, 1, True, "lstm"):
+            raise RnntError(f"RNNPredictor: the LSTM kernels are built for embed / output / hidden {D}, one lstm layer with bias; got embed_size={embed_size} "
+                            f"output_size={output_size} hidden_size={hidden_size} num_layers={num_layers} bias={bias} rnn_type={rnn_type!r}", rlib.ERR_SHAPE)
+        self.n_layers = num_layers
+        self.hidden_size = hidden_size
+        self._output_size = output_size
+        self.embed = torch.nn.Embedding(voca_size, embed_size)
+        self.dropout = torch.nn.Dropout(embed_dropout)
+        self.rnn = _LstmParams(embed_size, hidden_size)
+        self.projection = torch.nn.Linear(hidden_size, output_size)
+
+    def output_size(self):
+        return self._output_size
+
+    def init_state(self, batch_size, device, method="zero"):
+        assert batch_size > 0
+        return [torch.zeros(self.n_layers, batch_size, self.hidden_size, device=device) for _ in range(2)]
+
+    def lstm(self, input_tensor, cache=None, lengths=None):
+        """(out [B, U1, 256] before the projection, hN, cN [1, B, 256]) -- the reference's self.rnn(embed, states)"""
+        embed = self.dropout(self.embed(input_tensor))
+        h0, c0 = (None, None) if cache is None else (cache[0][0], cache[1][0])
+        r = self.rnn
+        out, hn, cn = lstm_predictor(embed, r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0, h0, c0, lengths)
+        return out, hn.unsqueeze(0), cn.unsqueeze(0)
+
+    def forward(self, input_tensor, cache=None, lengths=None):
+        """input_tensor [B, U1] token ids (add_blank(texts)); cache None (the zero state) or [h, c], each [1, B, 256]; lengths [B] valid
+        steps per row or None -> [B, U1, 256]."""
+        return self.projection(self.lstm(input_tensor, cache, lengths)[0])

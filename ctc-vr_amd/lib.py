@@ -129,6 +129,10 @@ SIGNATURES = {
                                      c_vp, c_vp]),
     "rnnt_joint_loss_backward": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, ctypes.c_float, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp,
                                          c_vp, c_i64, c_vp]),
+    "rnnt_lstm_workspace": (c_i32, [c_i32, c_i32, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
+    "rnnt_lstm_forward": (c_i32, [c_vp] * 8 + [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "rnnt_lstm_backward": (c_i32, [c_vp] * 7 + [c_i64, c_vp, c_vp, c_i32, c_i32] + [c_vp] * 7 + [c_i64, c_vp]),
+    "rnnt_lstm_host": (c_i32, [c_vp] * 8 + [c_i32, c_i32] + [c_vp] * 10),
     "rnnt_rescore_select_host": (c_i32, [c_i32, c_vp, c_vp, ctypes.c_double, ctypes.c_double, c_vp, c_i32p]),
     "rnnt_stream_keep_frames": (c_i32, [c_vp, c_i32, c_i32, c_vp]),
     "rnnt_stream_get_frames": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32p, c_vp]),
@@ -725,6 +729,65 @@ def joint_loss_host(e, p, w, b, targets, logit_lens, target_lens, blank, clamp=-
                                      *((None,) * 4 if outs is None else (_np_ptr(a) for a in outs)))
     _joint_loss_chk(rc, "rnnt_joint_loss_host", B, T, U1, V, blank)
     return nll, outs
+
+
+_LSTM_REFUSALS = {ERR_ARG: "a null or misaligned pointer, B or U1 < 1, or a length outside 1..U1",
+                  ERR_SHAPE: "U1 > 256, too many rows, or a workspace or state too small"}
+LSTM_D = 256                                     # input and hidden width the LSTM kernels are built for
+
+
+def _lstm_chk(rc, what, B, U1):
+    if rc != 0:
+        raise RnntError(f"{what}: {_LSTM_REFUSALS.get(rc, 'HIP failure')} (B={B} U1={U1}; status {rc})", rc)
+
+
+def lstm_workspace(B, U1):
+    """rnnt_lstm_workspace: (work_bytes, state_bytes) of the device buffers an LSTM forward or backward call of this shape needs."""
+    wb, sb = c_i64(0), c_i64(0)
+    _lstm_chk(load().rnnt_lstm_workspace(B, U1, ctypes.byref(wb), ctypes.byref(sb)), "rnnt_lstm_workspace", B, U1)
+    return int(wb.value), int(sb.value)
+
+
+def lstm_forward_device(x_ptr, w_ih_ptr, w_hh_ptr, b_ih_ptr, b_hh_ptr, h0_ptr, c0_ptr, lens, shape, out_ptr, hn_ptr, cn_ptr, state_ptr, state_bytes,
+                        work_ptr, work_bytes, stream=None):
+    """rnnt_lstm_forward over device pointers; shape = (B, U1), lens a host array [B] or None; h0 / c0 / hn / cn / state may be None.
+    Launches on `stream` and returns."""
+    B, U1 = shape
+    ln = _joint_lens(lens, B, "rnnt_lstm_forward")
+    rc = load().rnnt_lstm_forward(x_ptr, w_ih_ptr, w_hh_ptr, b_ih_ptr, b_hh_ptr, h0_ptr, c0_ptr, None if ln is None else _np_ptr(ln), B, U1, out_ptr, hn_ptr,
+                                  cn_ptr, state_ptr, state_bytes, work_ptr, work_bytes, stream)
+    _lstm_chk(rc, "rnnt_lstm_forward", B, U1)
+
+
+def lstm_backward_device(x_ptr, w_ih_ptr, w_hh_ptr, h0_ptr, c0_ptr, out_ptr, state_ptr, state_bytes, dout_ptr, lens, shape, dx_ptr, dw_ih_ptr, dw_hh_ptr,
+                         db_ptr, dh0_ptr, dc0_ptr, work_ptr, work_bytes, stream=None):
+    """rnnt_lstm_backward over device pointers; shape = (B, U1), the out and state a forward of the same arguments left."""
+    B, U1 = shape
+    ln = _joint_lens(lens, B, "rnnt_lstm_backward")
+    rc = load().rnnt_lstm_backward(x_ptr, w_ih_ptr, w_hh_ptr, h0_ptr, c0_ptr, out_ptr, state_ptr, state_bytes, dout_ptr, None if ln is None else _np_ptr(ln),
+                                   B, U1, dx_ptr, dw_ih_ptr, dw_hh_ptr, db_ptr, dh0_ptr, dc0_ptr, work_ptr, work_bytes, stream)
+    _lstm_chk(rc, "rnnt_lstm_backward", B, U1)
+
+
+def lstm_host(x, w_ih, w_hh, b_ih, b_hh, h0=None, c0=None, lens=None, dout=None, out=None):
+    """rnnt_lstm_host (no context, no GPU): x [B, U1, 256], w_ih / w_hh [1024, 256], b_ih / b_hh [1024], h0 / c0 [B, 256] or None float32 ->
+    (out, hn, cn) float64, and with dout [B, U1, 256] also (dx, dw_ih, dw_hh, db, dh0, dc0) float64.  out: the arrays to write into, in
+    that order (a refused call leaves them alone).  Raises RnntError on a refusal."""
+    f = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+    x, w_ih, w_hh, b_ih, b_hh, h0, c0, dout = (f(a) for a in (x, w_ih, w_hh, b_ih, b_hh, h0, c0, dout))
+    D, G = LSTM_D, 4 * LSTM_D
+    if x.ndim != 3 or x.shape[2] != D or w_ih.shape != (G, D) or w_hh.shape != (G, D) or b_ih.shape != (G,) or b_hh.shape != (G,) or \
+            any(a is not None and a.shape != (x.shape[0], D) for a in (h0, c0)) or (dout is not None and dout.shape != x.shape):
+        raise RnntError(f"rnnt_lstm_host: want x [B, U1, {D}], weights [{G}, {D}], biases [{G}], h0 / c0 [B, {D}], dout like x; got x {x.shape}", ERR_ARG)
+    B, U1 = x.shape[:2]
+    ln = _joint_lens(lens, B, "rnnt_lstm_host")
+    n_out = 3 if dout is None else 9
+    if out is None:
+        out = [np.zeros(s) for s in ((B, U1, D), (B, D), (B, D), (B, U1, D), (G, D), (G, D), (G,), (B, D), (B, D))[:n_out]]
+    p = lambda a: None if a is None else _np_ptr(a)
+    rc = load().rnnt_lstm_host(p(x), p(w_ih), p(w_hh), p(b_ih), p(b_hh), p(h0), p(c0), p(ln), B, U1, p(dout), *(p(a) for a in out), *((None,) * (9 - len(out))))
+    _lstm_chk(rc, "rnnt_lstm_host", B, U1)
+    return tuple(out)
 
 
 def wave_stage_host(carry, samples_so_far, new, final, n_fft=1024):

@@ -1213,3 +1213,95 @@ def joint_backward_emulation(e, p, w, g, logit_lens=None, target_lens=None):
     dw = _mm_bf16x3(g0.T, h.reshape(-1, h.shape[-1]))
     db = np.cumsum(g0, axis=0, dtype=np.float32)[-1]
     return de, dp, dw, db
+
+
+# ---- the predictor's LSTM with gradients: float64 yardstick and the device path's arithmetic contract (tests) ---------------------
+LSTM_NAMES = ("out", "dx", "dW_ih", "dW_hh", "db", "dh0", "dc0")
+
+
+def _lstm_mask(B, U1, lens):
+    """[B, U1] bool: the steps a row runs (all of them without lengths)"""
+    return np.ones((B, U1), bool) if lens is None else np.arange(U1)[None, :] < np.asarray(lens).reshape(B, 1)
+
+
+def lstm_ref(x, w_ih, w_hh, b_ih, b_hh, dout, h0=None, c0=None, lens=None, final=False):
+    """(out, dx, dW_ih, dW_hh, db, dh0, dc0) float64 by torch autograd on the CPU of the step loop written out, gates (i, f, g, o) from
+    x_u W_ih^T + b_ih + b_hh + h W_hh^T.  With lens a 0/1 mask freezes a row's state and zeroes its outputs and its dout beyond its
+    length (whatever x and dout hold there).  final=True appends (hN, cN)."""
+    import torch
+    x = np.asarray(x)
+    B, U1, Dn = x.shape
+    live = _lstm_mask(B, U1, lens)
+    t64 = lambda a, grad=True: torch.from_numpy(np.asarray(a, np.float32).astype(np.float64)).requires_grad_(grad)
+    x64 = t64(np.where(live[..., None], x, np.float32(0.0)))
+    g64 = t64(np.where(live[..., None], dout, np.float32(0.0)), False)
+    wi, wh, bi, bh = (t64(a) for a in (w_ih, w_hh, b_ih, b_hh))
+    h_0 = t64(np.zeros((B, Dn), np.float32) if h0 is None else h0)
+    c_0 = t64(np.zeros((B, Dn), np.float32) if c0 is None else c0)
+    m = torch.from_numpy(live.astype(np.float64))
+    h, c, outs = h_0, c_0, []
+    for u in range(U1):
+        gates = x64[:, u] @ wi.T + bi + bh + h @ wh.T
+        gi, gf, gg, go = gates.chunk(4, dim=1)
+        c_new = torch.sigmoid(gf) * c + torch.sigmoid(gi) * torch.tanh(gg)
+        h_new = torch.sigmoid(go) * torch.tanh(c_new)
+        mu = m[:, u:u + 1]
+        c = mu * c_new + (1.0 - mu) * c
+        h = mu * h_new + (1.0 - mu) * h
+        outs.append(mu * h_new)
+    out = torch.stack(outs, dim=1)
+    out.backward(g64)
+    res = (out.detach().numpy(), x64.grad.numpy(), wi.grad.numpy(), wh.grad.numpy(), bi.grad.numpy(), h_0.grad.numpy(), c_0.grad.numpy())
+    return res + (h.detach().numpy(), c.detach().numpy()) if final else res
+
+
+def lstm_sigmoid_f32(v):
+    """the library's logistic function in float32: 1 / (1 + exp2(-v log2 e)); exp2 overflow gives exactly 0, underflow exactly 1"""
+    with np.errstate(over="ignore", under="ignore"):
+        return (np.float32(1.0) / (np.float32(1.0) + np.exp2(np.float32(-1.4426950408889634) * np.asarray(v, np.float32)))).astype(np.float32)
+
+
+def lstm_f32_emulation(x, w_ih, w_hh, b_ih, b_hh, dout, h0=None, c0=None, lens=None):
+    """The arithmetic contract of rnnt_lstm_forward / _backward on the CPU, (out, dx, dW_ih, dW_hh, db, dh0, dc0) float32: every product,
+    sum and activation in float32, the device's logistic formula, float32 tanh, the saved gates and c reused by the backward, plain
+    float32 contractions and db as a float32 chain in memory order.  Its distance from lstm_ref is what this arithmetic costs; the
+    device, which adds in another (fixed) order, is held to a small multiple of it."""
+    f = np.float32
+    x = np.asarray(x, f)
+    B, U1, Dn = x.shape
+    live = _lstm_mask(B, U1, lens)
+    x0 = np.where(live[..., None], x, f(0.0)).astype(f)
+    g0 = np.where(live[..., None], np.asarray(dout, f), f(0.0)).astype(f)
+    wi, wh = np.asarray(w_ih, f), np.asarray(w_hh, f)
+    xg = (x0.reshape(-1, Dn) @ wi.T + (np.asarray(b_ih, f) + np.asarray(b_hh, f))).reshape(B, U1, 4 * Dn)
+    h = np.zeros((B, Dn), f) if h0 is None else np.asarray(h0, f).copy()
+    c = np.zeros((B, Dn), f) if c0 is None else np.asarray(c0, f).copy()
+    c_first = c.copy()
+    out, hprev, st = np.zeros((B, U1, Dn), f), np.zeros((B, U1, Dn), f), np.zeros((B, U1, 5, Dn), f)
+    for u in range(U1):
+        m = live[:, u:u + 1]
+        hprev[:, u] = np.where(m, h, f(0.0))
+        pre = (xg[:, u] + h @ wh.T).astype(f)
+        gi, gf, go = lstm_sigmoid_f32(pre[:, :Dn]), lstm_sigmoid_f32(pre[:, Dn:2 * Dn]), lstm_sigmoid_f32(pre[:, 3 * Dn:])
+        gg = np.tanh(pre[:, 2 * Dn:3 * Dn]).astype(f)
+        c_new = (gf * c + gi * gg).astype(f)
+        h_new = (go * np.tanh(c_new)).astype(f)
+        st[:, u] = np.stack([gi, gf, gg, go, c_new], axis=1)
+        out[:, u] = np.where(m, h_new, f(0.0))
+        c, h = np.where(m, c_new, c).astype(f), np.where(m, h_new, h).astype(f)
+    dG = np.zeros((B, U1, 4 * Dn), f)
+    dh, dc = np.zeros((B, Dn), f), np.zeros((B, Dn), f)
+    one = f(1.0)
+    for u in range(U1 - 1, -1, -1):
+        m = live[:, u:u + 1]
+        gi, gf, gg, go, cc = (st[:, u, k] for k in range(5))
+        cprev = st[:, u - 1, 4] if u > 0 else c_first
+        d = (g0[:, u] + dh).astype(f)
+        tc = np.tanh(cc).astype(f)
+        dct = (dc + d * go * (one - tc * tc)).astype(f)
+        dg_u = np.concatenate([dct * gg * (gi * (one - gi)), dct * cprev * (gf * (one - gf)), dct * gi * (one - gg * gg), d * tc * (go * (one - go))], axis=1)
+        dG[:, u] = np.where(m, dg_u, f(0.0))
+        dc = np.where(m, dct * gf, dc).astype(f)
+        dh = np.where(m, dG[:, u] @ wh, dh).astype(f)
+    dG2 = dG.reshape(-1, 4 * Dn)
+    return (out, (dG2 @ wi).reshape(B, U1, Dn), dG2.T @ x0.reshape(-1, Dn), dG2.T @ hprev.reshape(-1, Dn), np.cumsum(dG2, axis=0, dtype=f)[-1], dh, dc)

@@ -915,6 +915,43 @@ int rnnt_joint_loss_host(const float* e_host, const float* p_host, const float* 
                          int32_t blank, float clamp, const double* row_scale_host, double* nll_host, double* de_host, double* dp_host,
                          double* dw_host, double* db_host);
 
+/* -- the predictor's LSTM layer over a whole label sequence, with gradients -------------------------------------------------------- */
+/* torch.nn.LSTM(256, 256, one layer, batch_first) in torch's layout: x [B, U1, 256], w_ih and w_hh [1024, 256], b_ih and b_hh [1024],
+ * gate order i, f, g, o; h0, c0 [B, 256] or NULL (zeros); out [B, U1, 256]; hn, cn [B, 256] or NULL.  float32 throughout, with the
+ * activations of the inference predictor, so the sequence forward and the step call differ in summation order only.  Context-free,
+ * the caller's buffers, a stream; no allocation, no synchronisation; the launch count does not depend on U1.
+ *   forward   lstm_pack_whh, lstm_gemm (xg = x W_ih^T + b_ih + b_hh for all B U1 rows, exact-f32 MFMA), then ONE recurrence launch
+ *             lstm_seq_fwd that walks u = 0 .. U1-1: one workgroup per 4 batch rows, none waits on another.  With state_dev it saves
+ *             per row and step the activated i, f, g, o and c ([B, U1, 5, 256] floats) for the backward; NULL: forward only.
+ *   backward  ONE recurrence launch lstm_seq_bwd walking u = U1-1 .. 0 (dG [B U1, 1024] into the workspace, dh0 and dc0 [B, 256] or
+ *             NULL), then dx = dG W_ih, dW_ih = dG^T x, dW_hh = dG^T h_prev (out shifted by one step behind h0) as slabs of 256 rows
+ *             summed in slab order, db = sum dG (it is both db_ih and db_hh).  No atomics: two calls agree bit for bit.  c0_dev must
+ *             be the forward's (the forget gate's gradient at step 0 needs it).
+ * lens_host [B] or NULL: row b runs lens[b] steps (1..U1).  Beyond them x and dout are never read, out and dx are exactly 0, and
+ * hn / cn / dh0 / dc0 belong to the row's own first and last valid steps.
+ *   state_bytes = 5120 B U1
+ *   work_bytes  = 4 (4 ceil(B / 4) + 262144 + 1024 B U1 + 525312 ceil(B U1 / 256))
+ * Refusals, decided on the host before the first launch, changing nothing: a null required pointer, a pointer that is not 16-byte
+ * aligned, B < 1, U1 < 1, a length outside [1, U1]: RNNT_ERR_ARG; U1 > 256, 1280 B U1 >= 2^31 - 1, work_bytes or state_bytes too
+ * small: RNNT_ERR_SHAPE. */
+int rnnt_lstm_workspace(int32_t B, int32_t U1, int64_t* work_bytes, int64_t* state_bytes);
+int rnnt_lstm_forward(const float* x_dev, const float* w_ih_dev, const float* w_hh_dev, const float* b_ih_dev, const float* b_hh_dev,
+                      const float* h0_dev, const float* c0_dev, const int32_t* lens_host, int32_t B, int32_t U1, float* out_dev,
+                      float* hn_dev, float* cn_dev, void* state_dev, int64_t state_bytes, void* work_dev, int64_t work_bytes,
+                      void* stream);
+int rnnt_lstm_backward(const float* x_dev, const float* w_ih_dev, const float* w_hh_dev, const float* h0_dev, const float* c0_dev,
+                       const float* out_dev, const void* state_dev, int64_t state_bytes, const float* dout_dev,
+                       const int32_t* lens_host, int32_t B, int32_t U1, float* dx_dev, float* dw_ih_dev, float* dw_hh_dev,
+                       float* db_dev, float* dh0_dev, float* dc0_dev, void* work_dev, int64_t work_bytes, void* stream);
+/* Both directions in plain C++ (no context, no GPU): float64 throughout over the float32 inputs.  out_host [B, U1, 256], hn_host and
+ * cn_host [B, 256] or NULL.  dout_host NULL: forward only, the six gradient outputs untouched; else dx_host [B, U1, 256], dw_ih_host
+ * and dw_hh_host [1024, 256], db_host [1024] are required and dh0_host, dc0_host [B, 256] may be NULL.  Same ranges and refusals,
+ * without the alignment, state and workspace ones; a refused call writes nothing. */
+int rnnt_lstm_host(const float* x_host, const float* w_ih_host, const float* w_hh_host, const float* b_ih_host, const float* b_hh_host,
+                   const float* h0_host, const float* c0_host, const int32_t* lens_host, int32_t B, int32_t U1, const float* dout_host,
+                   double* out_host, double* hn_host, double* cn_host, double* dx_host, double* dw_ih_host, double* dw_hh_host,
+                   double* db_host, double* dh0_host, double* dc0_host);
+
 /* -- two-pass decoding: a cheap first pass yields n-best, the transducer likelihood re-scores it (the reference's WeNet layer:
  * Transducer.transducer_attention_rescoring with _cal_transducer_score, wenet/transducer/transducer.py:160-185, 261-395) ------- */
 /* rnnt_transducer_nll for N hypotheses per utterance WITHOUT repeating the utterance's frames N times: nll_host[b][n] is what
