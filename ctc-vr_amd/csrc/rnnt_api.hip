@@ -413,6 +413,7 @@ extern "C" {
 #include "api_joint.hip.inc"
 #include "api_joint_loss.hip.inc"
 #include "api_lstm.hip.inc"
+#include "api_attn.hip.inc"
 #include "api_state.hip.inc"
 #include "api_ngram.hip.inc"
 #include "api_pool_ctc.hip.inc"

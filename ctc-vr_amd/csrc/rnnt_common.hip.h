@@ -20,6 +20,8 @@
 //   rnnt_loss      loss_pick, transducer_alpha_beta, loss_coef, loss_grad (rnnt_transducer_loss: the loss with its gradient)
 //   rnnt_lstm      lstm_pack_whh, lstm_gemm, lstm_seq_fwd, lstm_seq_bwd, lstm_db_part, lstm_slab_reduce (rnnt_lstm_forward / _backward:
 //                  the predictor's LSTM over a whole label sequence with back-propagation through time)
+//   rnnt_attn_grad attn_fwd, attn_delta, attn_bwd_k, attn_bwd_q, attn_bias_reduce (rnnt_rel_attention_forward / _backward: an encoder
+//                  layer's attention core with gradients, flash-style on exact-f32 MFMA, no LDS)
 //   rnnt_misc      fill_i32, gather_att_cache, gather_cnn_cache
 #pragma once
 #include <hip/hip_runtime.h>

@@ -7,7 +7,9 @@ lattice in front of it with its backward (rnnt_joint_lattice_forward / _backward
 two fused, so that no [B, T, U1, V] tensor exists on the device (rnnt_joint_loss_forward / _backward).  ctc_loss / CTCHead: the CTC term of the reference's
 objective, torch.nn.functional.ctc_loss's signature (rnnt_ctc_loss / rnnt_ctc_loss_elem / rnnt_ctc_loss_host).  lstm_predictor /
 RNNPredictor: the predictor's LSTM over a whole label sequence with back-propagation through time (rnnt_lstm_forward / _backward /
-_host), under the reference's parameter names.  There is no eager-PyTorch path on the device."""
+_host), under the reference's parameter names.  rel_attention / RelPositionMultiHeadedAttention: the attention core of an encoder layer
+(relative positions, chunk mask) with gradients and no [T, T] tensor (rnnt_rel_attention_forward / _backward / _host).  There is no
+eager-PyTorch path on the device."""
 import numpy as np
 import torch
 
@@ -562,3 +564,126 @@ class RNNPredictor(torch.nn.Module):
         """input_tensor [B, U1] token ids (add_blank(texts)); cache None (the zero state) or [h, c], each [1, B, 256]; lengths [B] valid
         steps per row or None -> [B, U1, 256]."""
         return self.projection(self.lstm(input_tensor, cache, lengths)[0])
+
+
+# ---- an encoder layer's attention core with gradients (rnnt_rel_attention_forward / _backward) -----------------------------------------
+class _RelAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, p, u, vb, lengths, chunk_size, num_left_chunks):
+        B, T, D = q.shape
+        qa, ka, va, pa, ua, vba = (_aligned(t) for t in (q, k, v, p, u, vb))
+        lens = _lens_np(lengths)
+        if qa.is_cuda:
+            with torch.cuda.device(qa.device):
+                wbytes, sbytes = rlib.rel_attention_workspace(B, T)
+                work = torch.empty(wbytes, dtype=torch.uint8, device=qa.device)
+                state = torch.empty(sbytes, dtype=torch.uint8, device=qa.device)
+                out = torch.empty(B, T, D, dtype=torch.float32, device=qa.device)
+                rlib.rel_attention_forward_device(qa.data_ptr(), ka.data_ptr(), va.data_ptr(), pa.data_ptr(), ua.data_ptr(), vba.data_ptr(), lens, (B, T),
+                                                  chunk_size, num_left_chunks, out.data_ptr(), state.data_ptr(), sbytes, work.data_ptr(), wbytes,
+                                                  torch.cuda.current_stream().cuda_stream)
+        else:                                                      # the float64 host twin, rounded once; it saves nothing: the backward runs it again
+            (out64,) = rlib.rel_attention_host(qa.numpy(), ka.numpy(), va.numpy(), pa.numpy(), ua.numpy(), vba.numpy(), lens, chunk_size, num_left_chunks)
+            out = torch.from_numpy(out64.astype(np.float32))
+            state = torch.empty(0, dtype=torch.uint8)
+        ctx.mask = (lens, chunk_size, num_left_chunks)
+        ctx.save_for_backward(q, k, v, p, u, vb, out, state)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, p, u, vb, out, state = ctx.saved_tensors
+        lens, chunk_size, num_left_chunks = ctx.mask
+        B, T, D = q.shape
+        qa, ka, va, pa, ua, vba, da = (_aligned(t) for t in (q, k, v, p, u, vb, dout.to(torch.float32)))
+        if qa.is_cuda:
+            with torch.cuda.device(qa.device):
+                wbytes, sbytes = rlib.rel_attention_workspace(B, T)
+                work = torch.empty(wbytes, dtype=torch.uint8, device=qa.device)
+                new = lambda *s: torch.empty(*s, dtype=torch.float32, device=qa.device)
+                dq, dk, dv, dp, du, dvb = new(B, T, D), new(B, T, D), new(B, T, D), new(T, D), new(*u.shape), new(*vb.shape)
+                rlib.rel_attention_backward_device(qa.data_ptr(), ka.data_ptr(), va.data_ptr(), pa.data_ptr(), ua.data_ptr(), vba.data_ptr(),
+                                                   _aligned(out).data_ptr(), state.data_ptr(), sbytes, da.data_ptr(), lens, (B, T), chunk_size,
+                                                   num_left_chunks, dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), dp.data_ptr(), du.data_ptr(), dvb.data_ptr(),
+                                                   work.data_ptr(), wbytes, torch.cuda.current_stream().cuda_stream)
+        else:
+            dq, dk, dv, dp, du, dvb = (torch.from_numpy(a.astype(np.float32)) for a in
+                                       rlib.rel_attention_host(qa.numpy(), ka.numpy(), va.numpy(), pa.numpy(), ua.numpy(), vba.numpy(), lens, chunk_size,
+                                                               num_left_chunks, dout=da.numpy())[1:])
+        return dq, dk, dv, dp, du, dvb, None, None, None
+
+
+def rel_attention(q, k, v, p, pos_bias_u, pos_bias_v, lengths=None, chunk_size=0, num_left_chunks=-1):
+    """The attention core of the reference's encoder layer (RelPositionMultiHeadedAttention between its Linears,
+    wenet/transformer/attention.py:364-420, with the mask of add_optional_chunk_mask), differentiable: out [B, T, 256].
+
+        s[b,h,i,j] = ((q[b,i,h] + u[h]) . k[b,j,h] + (q[b,i,h] + vb[h]) . p[j,h]) / 8,   a = softmax of s over the visible j,   out = a v
+        visible(b,i,j) = j < lengths[b] and (chunk_size <= 0 or j < min(T, (i // chunk_size + 1) chunk_size))
+                         and (chunk_size <= 0 or num_left_chunks < 0 or j >= (i // chunk_size - num_left_chunks) chunk_size)
+
+    q, k, v [B, T, 256] as linear_q / _k / _v write them (head h at columns 64 h ..); p [T, 256] = linear_pos(pos_emb[0]); pos_bias_u,
+    pos_bias_v [4, 64]; lengths [B] (keys per row, 1..T) or None.  All float32 on one device.  Only keys are masked: every query row is
+    live and its gradient flows to the visible keys; a row with no visible key gives zeros and no gradient.  k and v at j >= lengths[b]
+    are never read, and dk, dv there are exactly 0.
+
+    CUDA tensors run rnnt_rel_attention_forward and, in .backward(), rnnt_rel_attention_backward on torch's current stream: no
+    [T, T] tensor reaches memory, exact-float32 MFMA contractions with a float32 online softmax, bit-for-bit repeatable.  Saved for
+    the backward: the six inputs, out and one log-sum-exp per (b, h, i) (16 B T bytes).  CPU tensors run rnnt_rel_attention_host, the
+    float64 C++ twin (the backward runs it again instead of saving a state).
+
+    Any dtype but float32: TypeError.  Shape or device disagreements, a length out of range, or num_left_chunks >= 0 without a
+    chunk_size: RnntError(ERR_ARG); T > lib.ATTN_TMAX (4096): RnntError(ERR_SHAPE)."""
+    named = (("q", q), ("k", k), ("v", v), ("p", p), ("pos_bias_u", pos_bias_u), ("pos_bias_v", pos_bias_v))
+    for name, t in named:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise TypeError(f"rel_attention: {name} must be a float32 tensor, got {getattr(t, 'dtype', type(t))}")
+    D, hb = rlib.ATTN_D, (rlib.ATTN_H, rlib.ATTN_DK)
+    if q.dim() != 3 or q.size(2) != D or k.shape != q.shape or v.shape != q.shape or tuple(p.shape) != (q.size(1), D) or tuple(pos_bias_u.shape) != hb or \
+            tuple(pos_bias_v.shape) != hb:
+        raise RnntError(f"rel_attention: want q, k, v [B, T, {D}], p [T, {D}], pos_bias_u and pos_bias_v [{hb[0]}, {hb[1]}]; got "
+                        + ", ".join(f"{n} {tuple(t.shape)}" for n, t in named), rlib.ERR_ARG)
+    if len({t.device for _, t in named}) != 1:
+        raise RnntError("rel_attention: every tensor must be on one device", rlib.ERR_ARG)
+    B, T = q.shape[:2]
+    if lengths is not None:
+        a = _lens_np(lengths)
+        if a.shape != (B,) or (a < 1).any() or (a > T).any():
+            raise RnntError(f"rel_attention: lengths must be [{B}] values in 1..{T}, got {a.tolist()}", rlib.ERR_ARG)
+    chunk_size, num_left_chunks = int(chunk_size), int(num_left_chunks)
+    if num_left_chunks >= 0 and chunk_size <= 0:
+        raise RnntError(f"rel_attention: num_left_chunks={num_left_chunks} counts chunks, but chunk_size={chunk_size}", rlib.ERR_ARG)
+    return _RelAttention.apply(q, k, v, p, pos_bias_u, pos_bias_v, lengths, chunk_size, num_left_chunks)
+
+
+class RelPositionMultiHeadedAttention(torch.nn.Module):
+    """The reference's RelPositionMultiHeadedAttention (wenet/transformer/attention.py) in its one trained configuration -- 4 heads over
+    256 features -- as self-attention without a cache, with the reference's parameter names (linear_q / _k / _v / _out with bias,
+    linear_pos without, pos_bias_u, pos_bias_v), so a layer's `self_attn.*` checkpoint entries load with strict=True.  The five
+    Linears are torch modules under torch autograd (the split TransducerJoint and RNNPredictor make too); what lies between them is
+    rel_attention.  The mask is (lengths, chunk_size, num_left_chunks) instead of a [B, T, T] tensor.  Dropout on the attention
+    weights is not built: dropout_rate must be 0."""
+
+    def __init__(self, n_head, n_feat, dropout_rate=0.0):
+        super().__init__()
+        if (n_head, n_feat) != (rlib.ATTN_H, rlib.ATTN_D) or dropout_rate != 0:
+            raise RnntError(f"RelPositionMultiHeadedAttention: the attention kernels are built for {rlib.ATTN_H} heads over {rlib.ATTN_D} features without "
+                            f"dropout on the weights; got n_head={n_head} n_feat={n_feat} dropout_rate={dropout_rate}", rlib.ERR_SHAPE)
+        self.h, self.d_k = n_head, n_feat // n_head
+        self.linear_q = torch.nn.Linear(n_feat, n_feat)
+        self.linear_k = torch.nn.Linear(n_feat, n_feat)
+        self.linear_v = torch.nn.Linear(n_feat, n_feat)
+        self.linear_out = torch.nn.Linear(n_feat, n_feat)
+        self.linear_pos = torch.nn.Linear(n_feat, n_feat, bias=False)
+        self.pos_bias_u = torch.nn.Parameter(torch.empty(self.h, self.d_k))
+        self.pos_bias_v = torch.nn.Parameter(torch.empty(self.h, self.d_k))
+        torch.nn.init.xavier_uniform_(self.pos_bias_u)
+        torch.nn.init.xavier_uniform_(self.pos_bias_v)
+
+    def forward(self, x, pos_emb, lengths=None, chunk_size=0, num_left_chunks=-1):
+        """x [B, T, 256] (query = key = value); pos_emb [1, T, 256]; lengths [B] keys per row or None -> [B, T, 256]"""
+        if pos_emb.dim() != 3 or pos_emb.size(0) != 1 or pos_emb.size(1) != x.size(1):
+            raise RnntError(f"RelPositionMultiHeadedAttention: pos_emb must be [1, T, {rlib.ATTN_D}] for x {tuple(x.shape)}, got {tuple(pos_emb.shape)}",
+                            rlib.ERR_ARG)
+        out = rel_attention(self.linear_q(x), self.linear_k(x), self.linear_v(x), self.linear_pos(pos_emb[0]), self.pos_bias_u, self.pos_bias_v, lengths,
+                            chunk_size, num_left_chunks)
+        return self.linear_out(out)

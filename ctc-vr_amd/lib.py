@@ -133,6 +133,10 @@ SIGNATURES = {
     "rnnt_lstm_forward": (c_i32, [c_vp] * 8 + [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "rnnt_lstm_backward": (c_i32, [c_vp] * 7 + [c_i64, c_vp, c_vp, c_i32, c_i32] + [c_vp] * 7 + [c_i64, c_vp]),
     "rnnt_lstm_host": (c_i32, [c_vp] * 8 + [c_i32, c_i32] + [c_vp] * 10),
+    "rnnt_rel_attention_workspace": (c_i32, [c_i32, c_i32, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
+    "rnnt_rel_attention_forward": (c_i32, [c_vp] * 7 + [c_i32] * 4 + [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "rnnt_rel_attention_backward": (c_i32, [c_vp] * 8 + [c_i64, c_vp, c_vp] + [c_i32] * 4 + [c_vp] * 7 + [c_i64, c_vp]),
+    "rnnt_rel_attention_host": (c_i32, [c_vp] * 7 + [c_i32] * 4 + [c_vp] * 8),
     "rnnt_rescore_select_host": (c_i32, [c_i32, c_vp, c_vp, ctypes.c_double, ctypes.c_double, c_vp, c_i32p]),
     "rnnt_stream_keep_frames": (c_i32, [c_vp, c_i32, c_i32, c_vp]),
     "rnnt_stream_get_frames": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32p, c_vp]),
@@ -787,6 +791,66 @@ def lstm_host(x, w_ih, w_hh, b_ih, b_hh, h0=None, c0=None, lens=None, dout=None,
     p = lambda a: None if a is None else _np_ptr(a)
     rc = load().rnnt_lstm_host(p(x), p(w_ih), p(w_hh), p(b_ih), p(b_hh), p(h0), p(c0), p(ln), B, U1, p(dout), *(p(a) for a in out), *((None,) * (9 - len(out))))
     _lstm_chk(rc, "rnnt_lstm_host", B, U1)
+    return tuple(out)
+
+
+ATTN_H, ATTN_DK, ATTN_D = 4, 64, 256             # heads, width of a head, model width the attention kernels are built for
+ATTN_TMAX = 4096                                 # the library's cap on T (include/rnnt_hip.h)
+_ATTN_REFUSALS = {ERR_ARG: "a null or misaligned pointer, B or T < 1, a length outside 1..T, or num_left_chunks >= 0 without a chunk_size",
+                  ERR_SHAPE: f"T > {ATTN_TMAX}, too many rows, or a workspace or state too small"}
+
+
+def _attn_chk(rc, what, B, T, chunk, left):
+    if rc != 0:
+        raise RnntError(f"{what}: {_ATTN_REFUSALS.get(rc, 'HIP failure')} (B={B} T={T} chunk_size={chunk} num_left_chunks={left}; status {rc})", rc)
+
+
+def rel_attention_workspace(B, T):
+    """rnnt_rel_attention_workspace: (work_bytes, state_bytes) of the device buffers an attention forward or backward call of this shape needs."""
+    wb, sb = c_i64(0), c_i64(0)
+    _attn_chk(load().rnnt_rel_attention_workspace(B, T, ctypes.byref(wb), ctypes.byref(sb)), "rnnt_rel_attention_workspace", B, T, 0, -1)
+    return int(wb.value), int(sb.value)
+
+
+def rel_attention_forward_device(q_ptr, k_ptr, v_ptr, p_ptr, u_ptr, vb_ptr, lens, shape, chunk_size, num_left_chunks, out_ptr, state_ptr, state_bytes,
+                                 work_ptr, work_bytes, stream=None):
+    """rnnt_rel_attention_forward over device pointers; shape = (B, T), lens a host array [B] or None; state may be None (forward only).
+    Launches on `stream` and returns."""
+    B, T = shape
+    ln = _joint_lens(lens, B, "rnnt_rel_attention_forward")
+    rc = load().rnnt_rel_attention_forward(q_ptr, k_ptr, v_ptr, p_ptr, u_ptr, vb_ptr, None if ln is None else _np_ptr(ln), B, T, chunk_size, num_left_chunks,
+                                           out_ptr, state_ptr, state_bytes, work_ptr, work_bytes, stream)
+    _attn_chk(rc, "rnnt_rel_attention_forward", B, T, chunk_size, num_left_chunks)
+
+
+def rel_attention_backward_device(q_ptr, k_ptr, v_ptr, p_ptr, u_ptr, vb_ptr, out_ptr, state_ptr, state_bytes, dout_ptr, lens, shape, chunk_size,
+                                  num_left_chunks, dq_ptr, dk_ptr, dv_ptr, dp_ptr, du_ptr, dvb_ptr, work_ptr, work_bytes, stream=None):
+    """rnnt_rel_attention_backward over device pointers; shape = (B, T), the out and state a forward of the same arguments left."""
+    B, T = shape
+    ln = _joint_lens(lens, B, "rnnt_rel_attention_backward")
+    rc = load().rnnt_rel_attention_backward(q_ptr, k_ptr, v_ptr, p_ptr, u_ptr, vb_ptr, out_ptr, state_ptr, state_bytes, dout_ptr,
+                                            None if ln is None else _np_ptr(ln), B, T, chunk_size, num_left_chunks, dq_ptr, dk_ptr, dv_ptr, dp_ptr, du_ptr,
+                                            dvb_ptr, work_ptr, work_bytes, stream)
+    _attn_chk(rc, "rnnt_rel_attention_backward", B, T, chunk_size, num_left_chunks)
+
+
+def rel_attention_host(q, k, v, p, u, vb, lens=None, chunk_size=0, num_left_chunks=-1, dout=None):
+    """rnnt_rel_attention_host (no context, no GPU): q, k, v [B, T, 256], p [T, 256], u, vb [4, 64] float32 -> (out,) float64, and with
+    dout [B, T, 256] (out, dq, dk, dv, dp, du, dvb) float64.  Raises RnntError on a refusal."""
+    f = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+    q, k, v, p, u, vb, dout = (f(a) for a in (q, k, v, p, u, vb, dout))
+    D = ATTN_D
+    if q.ndim != 3 or q.shape[2] != D or k.shape != q.shape or v.shape != q.shape or p.shape != (q.shape[1], D) or u.shape != (ATTN_H, ATTN_DK) or \
+            vb.shape != (ATTN_H, ATTN_DK) or (dout is not None and dout.shape != q.shape):
+        raise RnntError(f"rnnt_rel_attention_host: want q, k, v, dout [B, T, {D}], p [T, {D}], u and vb [{ATTN_H}, {ATTN_DK}]; got q {q.shape}, k {k.shape}, "
+                        f"v {v.shape}, p {p.shape}, u {u.shape}, vb {vb.shape}", ERR_ARG)
+    B, T = q.shape[:2]
+    ln = _joint_lens(lens, B, "rnnt_rel_attention_host")
+    out = [np.zeros(s) for s in ((B, T, D),) + (() if dout is None else ((B, T, D), (B, T, D), (B, T, D), (T, D), (ATTN_H, ATTN_DK), (ATTN_H, ATTN_DK)))]
+    ptr = lambda a: None if a is None else _np_ptr(a)
+    rc = load().rnnt_rel_attention_host(ptr(q), ptr(k), ptr(v), ptr(p), ptr(u), ptr(vb), ptr(ln), B, T, int(chunk_size), int(num_left_chunks), ptr(dout),
+                                        *(ptr(a) for a in out), *((None,) * (7 - len(out))))
+    _attn_chk(rc, "rnnt_rel_attention_host", B, T, chunk_size, num_left_chunks)
     return tuple(out)
 
 

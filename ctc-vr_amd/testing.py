@@ -1305,3 +1305,105 @@ def lstm_f32_emulation(x, w_ih, w_hh, b_ih, b_hh, dout, h0=None, c0=None, lens=N
         dh = np.where(m, dG[:, u] @ wh, dh).astype(f)
     dG2 = dG.reshape(-1, 4 * Dn)
     return (out, (dG2 @ wi).reshape(B, U1, Dn), dG2.T @ x0.reshape(-1, Dn), dG2.T @ hprev.reshape(-1, Dn), np.cumsum(dG2, axis=0, dtype=f)[-1], dh, dc)
+
+
+# ---- an encoder layer's attention core with gradients: float64 yardstick and the device path's arithmetic contract (tests) --------
+ATTN_NAMES = ("out", "dq", "dk", "dv", "dp", "du", "dvb")
+ATTN_TILE = 16                                   # keys per tile of the device's online softmax (rnnt_attn_grad.hip.h)
+
+
+def chunk_visible(T, lengths, chunk_size, num_left_chunks):
+    """bool [B, T, T]: visible[b, i, j] of rnnt_rel_attention_forward -- j < len_b, and with chunk_size > 0 also
+    j < min(T, (i // chunk_size + 1) chunk_size) and, with num_left_chunks >= 0, j >= (i // chunk_size - num_left_chunks) chunk_size.
+    lengths None: one row of T keys."""
+    lens = np.full(1, T, np.int64) if lengths is None else np.asarray(lengths, np.int64).reshape(-1)
+    i, j = np.arange(T)[:, None], np.arange(T)[None, :]
+    win = np.ones((T, T), bool)
+    if chunk_size > 0:
+        win = j < np.minimum(T, (i // chunk_size + 1) * chunk_size)
+        if num_left_chunks >= 0:
+            win = win & (j >= (i // chunk_size - num_left_chunks) * chunk_size)
+    return win[None] & (j[None] < lens[:, None, None])
+
+
+def _attn_heads(a, T):
+    """[B, T, 256] -> [B, 4, T, 64] (a copy)"""
+    a = np.asarray(a)
+    return np.ascontiguousarray(a.reshape(a.shape[0], T, 4, 64).transpose(0, 2, 1, 3))
+
+
+def _attn_args(q, k, v, lens):
+    """(B, T, lens [B], k and v with zeros at j >= len_b: what lies there is never read)"""
+    B, T = np.asarray(q).shape[:2]
+    lens = np.full(B, T, np.int64) if lens is None else np.asarray(lens, np.int64).reshape(B)
+    live = (np.arange(T)[None, :] < lens[:, None])[..., None]
+    return B, T, lens, np.where(live, k, np.float32(0.0)).astype(np.float32), np.where(live, v, np.float32(0.0)).astype(np.float32)
+
+
+def rel_attention_ref(q, k, v, p, u, vb, dout, lens=None, chunk_size=0, num_left_chunks=-1):
+    """(out, dq, dk, dv, dp, du, dvb) float64 by torch autograd on the CPU of the formula written out densely:
+    s = ((q + u) k^T + (q + vb) p^T) / 8 per head, softmax over the visible keys (0 at hidden ones, all 0 for a row without a visible
+    key), out = a v, gradients of (out * dout).sum()."""
+    import torch
+    B, T, _, k0, v0 = _attn_args(q, k, v, lens)
+    vis = torch.from_numpy(chunk_visible(T, np.full(B, T) if lens is None else lens, chunk_size, num_left_chunks))[:, None]       # [B, 1, T, T]
+    t64 = lambda a, grad=True: torch.from_numpy(np.asarray(a, np.float32).astype(np.float64)).requires_grad_(grad)
+    q64, k64, v64, p64, u64, vb64 = (t64(a) for a in (q, k0, v0, p, u, vb))
+    g64 = t64(dout, False)
+    hd = lambda a: a.view(a.shape[0], T, 4, 64).transpose(1, 2)                  # [B, 4, T, 64]
+    qh, kh, vh, ph = hd(q64), hd(k64), hd(v64), p64.view(1, T, 4, 64).transpose(1, 2)
+    s = ((qh + u64[None, :, None, :]) @ kh.transpose(-1, -2) + (qh + vb64[None, :, None, :]) @ ph.transpose(-1, -2)) / 8.0
+    m = s.detach().masked_fill(~vis, -math.inf).amax(-1, keepdim=True)
+    m = torch.where(torch.isfinite(m), m, torch.zeros_like(m))
+    e = torch.where(vis, torch.exp(torch.where(vis, s, m) - m), torch.zeros_like(s))
+    l = e.sum(-1, keepdim=True)
+    a = e / torch.where(l > 0, l, torch.ones_like(l))
+    out = (a @ vh).transpose(1, 2).reshape(B, T, 256)
+    out.backward(g64)
+    return (out.detach().numpy(),) + tuple(t.grad.numpy() for t in (q64, k64, v64, p64, u64, vb64))
+
+
+def rel_attention_emulation(q, k, v, p, u, vb, dout, lens=None, chunk_size=0, num_left_chunks=-1):
+    """The arithmetic contract of rnnt_rel_attention_forward / _backward on the CPU, (out, dq, dk, dv, dp, du, dvb) float32.  Every
+    contraction is a float32 product (the device's exact-f32 MFMA: float32 products, float32 accumulation); the softmax runs online
+    over tiles of 16 keys in float32 -- running max, exp, running sum, the rescaling of out -- and saves m + log(l) per row; the
+    backward recomputes a = exp(s - lse) per key tile, delta = dout . out, ds = a (dout v^T - delta) / 8 in float32, and adds dp over
+    the rows and du, dvb over rows and queries as float32 chains in index order.  A probability is formed from visible keys only.  Its
+    distance from rel_attention_ref is what this arithmetic costs; the device, which adds in another (fixed) order, is held to a
+    small multiple of it."""
+    f = np.float32
+    B, T, lens, k0, v0 = _attn_args(q, k, v, lens)
+    vis = chunk_visible(T, lens, chunk_size, num_left_chunks)[:, None]           # [B, 1, T, T]
+    qh, kh, vh, gh = (_attn_heads(np.asarray(a, f), T) for a in (q, k0, v0, dout))
+    ph = _attn_heads(np.asarray(p, f)[None], T)                                  # [1, 4, T, 64]
+    u32, vb32 = np.asarray(u, f)[None, :, None, :], np.asarray(vb, f)[None, :, None, :]
+    qu, qv = (qh + u32).astype(f), (qh + vb32).astype(f)
+    tr = lambda a: a.transpose(0, 1, 3, 2)
+    tiles = [slice(j0, min(T, j0 + ATTN_TILE)) for j0 in range(0, T, ATTN_TILE)]
+    scores = lambda sl: ((qu @ tr(kh[:, :, sl]) + qv @ tr(ph[:, :, sl])) * f(0.125)).astype(f)
+    m, l, o = np.full((B, 4, T), -np.inf, f), np.zeros((B, 4, T), f), np.zeros((B, 4, T, 64), f)
+    for sl in tiles:
+        s, vt = scores(sl), vis[..., sl]
+        mn = np.maximum(m, np.where(vt, s, f(-np.inf)).max(-1))
+        alpha = np.exp(np.where(np.isinf(m), f(0.0), m - np.where(np.isinf(mn), f(0.0), mn))).astype(f)
+        pe = np.where(vt, np.exp(np.where(vt, s - np.where(np.isinf(mn), f(0.0), mn)[..., None], f(0.0))), f(0.0)).astype(f)
+        l = (l * alpha + pe.sum(-1, dtype=f)).astype(f)
+        o = (o * alpha[..., None] + pe @ vh[:, :, sl]).astype(f)
+        m = mn
+    dead = np.isinf(m)
+    l1 = np.where(dead, f(1.0), l)
+    out = np.where(dead[..., None], f(0.0), o / l1[..., None]).astype(f)
+    lse = np.where(dead, f(0.0), m + np.log(l1)).astype(f)
+    delta = (gh * out).sum(-1, dtype=f)
+    A, Bm = np.zeros((B, 4, T, 64), f), np.zeros((B, 4, T, 64), f)
+    dk, dv, dpp = np.zeros_like(A), np.zeros_like(A), np.zeros_like(A)
+    for sl in tiles:
+        s, vt = scores(sl), vis[..., sl]
+        a = np.where(vt, np.exp(np.where(vt, s - lse[..., None], f(0.0))), f(0.0)).astype(f)
+        ds = (a * (gh @ tr(vh[:, :, sl]) - delta[..., None]) * f(0.125)).astype(f)
+        A += ds @ kh[:, :, sl]
+        Bm += ds @ ph[:, :, sl]
+        dv[:, :, sl], dk[:, :, sl], dpp[:, :, sl] = tr(a) @ gh, tr(ds) @ qu, tr(ds) @ qv
+    back = lambda a: a.transpose(0, 2, 1, 3).reshape(a.shape[0], T, 256)
+    chain = lambda a: np.cumsum(a, axis=0, dtype=f)[-1]
+    return (back(out), back(A + Bm), back(dk), back(dv), chain(back(dpp)), chain(back(A).reshape(B * T, 4, 64)), chain(back(Bm).reshape(B * T, 4, 64)))

@@ -952,6 +952,51 @@ int rnnt_lstm_host(const float* x_host, const float* w_ih_host, const float* w_h
                    double* out_host, double* hn_host, double* cn_host, double* dx_host, double* dw_ih_host, double* dw_hh_host,
                    double* db_host, double* dh0_host, double* dc0_host);
 
+/* -- the attention core of an encoder layer (relative positions, chunk mask), with gradients ----------------------------------------- */
+/* The reference's RelPositionMultiHeadedAttention between its Linears (wenet/transformer/attention.py:364-420, rel_shift commented
+ * out there, so the positional term is indexed by the key's absolute position), H = 4 heads of 64:
+ *   s[b,h,i,j] = ((q[b,i,h,:] + u[h,:]) . k[b,j,h,:] + (q[b,i,h,:] + vb[h,:]) . p[j,h,:]) / 8
+ *   visible(b,i,j) = j < len_b and (chunk_size <= 0 or j < min(T, (i / chunk_size + 1) chunk_size))
+ *                    and (chunk_size <= 0 or num_left_chunks < 0 or j >= (i / chunk_size - num_left_chunks) chunk_size)
+ *   a = softmax of s over the visible j (0 at hidden j; all 0 for a row with no visible key);  out[b,i,h,:] = sum_j a[b,h,i,j] v[b,j,h,:]
+ * q, k, v, out, dout, dq, dk, dv [B, T, 256] with head h at columns 64 h .. 64 h + 63 (as linear_q writes and linear_out reads);
+ * p, dp [T, 256] (linear_pos(pos_emb[0])); u, vb, du, dvb [4, 64] (pos_bias_u, pos_bias_v).  All float32, contiguous, 16-byte
+ * aligned.  Only keys are masked: every query row i < T is live, padded ones included.  Keys and values at j >= len_b are never
+ * read.  Context-free, the caller's buffers, a stream; no allocation, no synchronisation; nothing of T x T size reaches memory.
+ *   forward   ONE launch attn_fwd: a wave per (b, h, 16 queries) walks the 16-key tiles inside the tile's window and len_b, online
+ *             softmax.  With state_dev it saves one float32 log-sum-exp per (b, h, i) ([B, 4, T]; +inf marks a row with no visible
+ *             key); NULL: forward only.
+ *   backward  attn_delta (dout . out), attn_bwd_k (key-owned: dk, dv, the row's dp partial), attn_bwd_q (query-owned: dq, the tile's
+ *             du and dvb partials), then dp summed over rows and du / dvb over (row, query tile) in index order.  The probabilities
+ *             are recomputed from q, k, p and the saved log-sum-exp in both passes.  No atomics: two calls agree bit for bit.
+ * Arithmetic: every contraction on v_mfma_f32_16x16x4_f32 (exact float32 products, float32 accumulation); max, exp, sums, delta,
+ * ds in float32.  A probability is never formed from a hidden key (a select, not exp(-inf)).
+ * lens_host [B] or NULL (every row T keys).  T is capped at 4096.  The lengths are copied from a host array of the call's own; with
+ * more than 16384 rows the call waits for that copy (the stream) before it returns, the one case in which it synchronises.
+ *   state_bytes = 16 B T
+ *   work_bytes  = 4 (4 ceil(B / 4) + 260 B T + 512 B ceil(T / 16))
+ * Refusals, decided on the host before the first launch, changing nothing: a null required pointer, a pointer that is not 16-byte
+ * aligned, B < 1, T < 1, a length outside [1, T], num_left_chunks >= 0 with chunk_size <= 0: RNNT_ERR_ARG; T > 4096,
+ * 256 B T >= 2^31 - 1, work_bytes or state_bytes too small: RNNT_ERR_SHAPE. */
+int rnnt_rel_attention_workspace(int32_t B, int32_t T, int64_t* work_bytes, int64_t* state_bytes);
+int rnnt_rel_attention_forward(const float* q_dev, const float* k_dev, const float* v_dev, const float* p_dev, const float* u_dev,
+                               const float* vb_dev, const int32_t* lens_host, int32_t B, int32_t T, int32_t chunk_size,
+                               int32_t num_left_chunks, float* out_dev, void* state_dev, int64_t state_bytes, void* work_dev,
+                               int64_t work_bytes, void* stream);
+int rnnt_rel_attention_backward(const float* q_dev, const float* k_dev, const float* v_dev, const float* p_dev, const float* u_dev,
+                                const float* vb_dev, const float* out_dev, const void* state_dev, int64_t state_bytes,
+                                const float* dout_dev, const int32_t* lens_host, int32_t B, int32_t T, int32_t chunk_size,
+                                int32_t num_left_chunks, float* dq_dev, float* dk_dev, float* dv_dev, float* dp_dev, float* du_dev,
+                                float* dvb_dev, void* work_dev, int64_t work_bytes, void* stream);
+/* Both directions in plain C++ (no context, no GPU): float64 throughout over the float32 inputs; it holds one [T] row of scores.
+ * out_host [B, T, 256].  dout_host NULL: forward only, the six gradient outputs untouched; else dq_host, dk_host, dv_host
+ * [B, T, 256], dp_host [T, 256], du_host, dvb_host [4, 64] are required.  Same ranges and refusals, without the alignment, state
+ * and workspace ones; a refused call writes nothing. */
+int rnnt_rel_attention_host(const float* q_host, const float* k_host, const float* v_host, const float* p_host, const float* u_host,
+                            const float* vb_host, const int32_t* lens_host, int32_t B, int32_t T, int32_t chunk_size,
+                            int32_t num_left_chunks, const float* dout_host, double* out_host, double* dq_host, double* dk_host,
+                            double* dv_host, double* dp_host, double* du_host, double* dvb_host);
+
 /* -- two-pass decoding: a cheap first pass yields n-best, the transducer likelihood re-scores it (the reference's WeNet layer:
  * Transducer.transducer_attention_rescoring with _cal_transducer_score, wenet/transducer/transducer.py:160-185, 261-395) ------- */
 /* rnnt_transducer_nll for N hypotheses per utterance WITHOUT repeating the utterance's frames N times: nll_host[b][n] is what
